@@ -1,7 +1,17 @@
 #!/usr/bin/env python3
 """Benchmark of the separation hot path (BASELINE.json metric: clips/sec, one clip = 10 s @ 16 kHz).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W untimed and K timed steps, writes the last timed step's outputs if --dump-outputs is given, and
+prints the result line: `value` (clips/s), `ms_per_step` (one timed step) and the workload.  --full adds everything else the
+benchmark measures: the eager and the HIP-event-instrumented loops (launch.eager_ms_per_step, kernel_ms_per_step, roofline),
+the exchange step, the extra compute modes and workloads of --modes (bf16, bf16x3, multi-STFT, evaluator) and the CPU baseline.
+
+--dump-outputs DIR: after the timed loop, the separated waveforms of the last timed step - what a caller of lass_separate
+receives - as DIR/waveform.npy (float32, shape (B, L); DIR/waveform_rank<r>.npy per rank when N > 1).  Inputs and weights are
+seeded, so the same arguments give the same inputs on every run.  An output larger than its share of 64 MB is written as a
+fixed sample: the flat elements at np.sort(np.random.default_rng(0).choice(size, n, replace=False)).
 
 N = 1 runs in this process.  N > 1 without WORLD_SIZE in the environment: this process touches no GPU, builds the
 library in a child, starts N fresh ranks (`python -m torch.distributed.run --nproc-per-node N bench.py ...`, one rank
@@ -13,10 +23,10 @@ synthetic mixtures already resident in HBM.  Workload at N=1 = BASELINE.json con
 10 s @ 16 kHz, fixed (precomputed) condition embeddings, seeded random-init weights.  For N>1 every rank separates its
 own 16 clips (weak scaling; clip-level sharding, no data-path collective: configs[3] at N=8); after the timed loop each
 rank reduces its clips to SDR / SDRi / SI-SDR rows on the device and ONE all-gather of those rows ends the
-job.  value = clips of all ranks / max-over-ranks time.  Prints ONE JSON line on rank 0.
+job (--full).  value = clips of all ranks / max-over-ranks time.  Prints ONE JSON line on rank 0.
 
-Timing protocol: `value` comes from an un-instrumented loop; the per-kernel-class milliseconds (roofline) come from a
-second, shorter loop with HIP events around every class on the launch stream (lass_set_profiling).
+Timing protocol: `value` comes from an un-instrumented loop; with --full the per-kernel-class milliseconds (roofline) come
+from a second, shorter loop with HIP events around every class on the launch stream (lass_set_profiling).
 """
 import argparse
 import json
@@ -51,10 +61,15 @@ def parse_args(argv=None):
                                                              "960000 = 30 s @ 32 kHz with --workload multistft)")
     ap.add_argument("--dtype", choices=["f32", "bf16", "bf16x3"], default="f32",
                     help="headline arithmetic: f32 = BASELINE configs[1]; bf16 = configs[2] (bf16-MFMA convolutions)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: eager and HIP-event-instrumented loops (roofline), the "
+                         "exchange step, the --modes legs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--modes", default="auto",
-                    help="extra compute modes timed after the headline region and reported under `modes` "
+                    help="with --full: extra compute modes timed after the headline region and reported under `modes` "
                          "(comma list of bf16,bf16x3; 'auto' = both at N=1 with --dtype f32, 'none' = skip)")
-    ap.add_argument("--profile-steps", type=int, default=5, help="steps of the second, HIP-event-instrumented loop")
+    ap.add_argument("--profile-steps", type=int, default=5, help="with --full: steps of the second, HIP-event-instrumented loop")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend of the one exchange step; gloo also lets ranks share a GPU "
                          "(rehearsal on a 1-GPU box)")
@@ -64,6 +79,12 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-full", action="store_true", help="(default since round 4; kept for old command lines)")
     ap.add_argument("--print-launch", action="store_true", help="N>1 parent: print the launch command and exit")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full and args.modes not in ("auto", "none"):
+        ap.error("--modes times legs beyond the headline: it needs --full")
+    if args.dump_outputs is not None:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     ms = args.workload == "multistft"
     if args.batch is None:
         args.batch = 1 if ms else 16
@@ -89,14 +110,27 @@ def half_batch_overlap(mode: str, B: int) -> bool:
     return bool(os.environ.get("LASS_SPLIT", "1") != "0" and B >= 8 and B % 2 == 0)
 
 
+def absolute_dump_dir(argv):
+    """argv with the --dump-outputs directory made absolute: the ranks run in ROOT, not in the caller's directory."""
+    out, it = [], iter(argv)
+    for a in it:
+        if a == "--dump-outputs":
+            out += [a, os.path.abspath(next(it, ""))]
+        elif a.startswith("--dump-outputs="):
+            out.append("--dump-outputs=" + os.path.abspath(a.split("=", 1)[1]))
+        else:
+            out.append(a)
+    return out
+
+
 def parent_launch(args, argv) -> int:
     """Spawn the ranks as fresh children (a GPU-initialised process must never exec or fork into ranks)."""
-    cmd = launch_command(argv, args.gpus, free_port())
+    cmd = launch_command(absolute_dump_dir(argv), args.gpus, free_port())
     if args.print_launch:
         print(json.dumps({"launch": cmd}))
         return 0
-    # build once, in a child, so the ranks find an up-to-date library (they re-check under a file lock)
-    subprocess.run([sys.executable, "-c", "import __graft_entry__ as g; g.build()"], cwd=ROOT, check=True,
+    # build once, in a child, so the ranks find an up-to-date library (each rank checks it again)
+    subprocess.run([sys.executable, "-c", "import bench, __graft_entry__ as g; bench.ensure_library(g)"], cwd=ROOT, check=True,
                    stdout=sys.stderr)
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -123,6 +157,14 @@ def parent_launch(args, argv) -> int:
     return p.returncode
 
 
+def ensure_library(ge):
+    """ge.build() only when the library is missing or stale.  A current library is loaded as it is: the benchmark also runs
+    in a checkout that another user built and that is read-only to this one, where the lock file build() takes cannot be
+    created (and a build() that takes it even for a current library must not be called there)."""
+    if ge._stale():
+        ge.build()
+
+
 # ---- helpers of a rank ---------------------------------------------------------------------------------------------------
 def host_cores() -> int:
     """CPU threads this process may actually use: affinity mask, capped by the cgroup CPU quota; a GPU box exposes all
@@ -139,6 +181,24 @@ def host_cores() -> int:
     if env:
         return int(env)
     return min(n, 16)
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6  # all files of one --dump-outputs run together
+
+
+def dump_outputs(out_dir, arrays, rank=0, world=1):
+    """--dump-outputs: {name: tensor} -> out_dir/<name>.npy (<name>_rank<r>.npy when N > 1) in float32.  An array above its
+    share of DUMP_LIMIT_BYTES is written as a fixed sample of its flat elements (seed 0, sorted indices: the same elements
+    for the same shape on every run)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // (world * len(arrays)) - 4096  # (room for the .npy header)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy" if world == 1 else f"{name}_rank{rank}.npy"), a)
 
 
 def cpu_model() -> str:
@@ -259,7 +319,7 @@ def main():
     import torch
     import torch.distributed as dist
     import __graft_entry__ as ge
-    ge.build()
+    ensure_library(ge)
     from lass_amd import arch, synthetic
     from lass_amd import dist as ldist
     from lass_amd.metrics import stats_to_db
@@ -270,13 +330,14 @@ def main():
     dev_index = local_rank % ndev if args.backend == "gloo" else local_rank
     torch.cuda.set_device(dev_index)
     dev = torch.device("cuda", dev_index)
-    # The exchange step runs on a real process group at every N: under the launcher its rendezvous comes from the
-    # environment; a plain N=1 run makes a single-rank group so the RCCL path executes there too.
+    # Under the launcher the ranks need their process group for the barriers and the max-over-ranks time; its rendezvous
+    # comes from the environment.  The exchange step (--full) runs on a real process group at every N: an N=1 run with
+    # --full makes a single-rank group so the RCCL path executes there too; a plain N=1 run needs none.
     pg_error = None
     try:
         if launched:
             dist.init_process_group(args.backend, **({"device_id": dev} if args.backend == "nccl" else {}))
-        else:
+        elif args.full:
             dist.init_process_group(args.backend, init_method=f"tcp://127.0.0.1:{free_port()}", rank=0, world_size=1,
                                     **({"device_id": dev} if args.backend == "nccl" else {}))
     except Exception as e:  # a single-GPU run still reports its throughput; N>1 cannot continue
@@ -349,6 +410,45 @@ def main():
     extra_warm = max(0, 3 - args.warmup) if eng.graph_stats()[0] else 0
     dt = timed(eng, args.steps, args.warmup + extra_warm)
     assert not check or torch.isfinite(out).all()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"waveform": out}, rank, world)
+
+    def headline():
+        """The fields every run reports: the timed loop's rate and what it ran."""
+        return {
+            "metric": "clips/sec (30s@32kHz)" if ms_workload else "clips/sec (10s@16kHz)", "value": world * B * args.steps / dt, "unit": "clips/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+            "config": {"workload": (f"multi-STFT ResUNet30 (windows 256/512/2048 at n_fft 2048, authored spec: DESIGN.md section 9) "
+                                    f"{'fp32' if args.dtype == 'f32' else args.dtype + ' MFMA convolutions'}, batch={B}/GPU, "
+                                    f"{L / rate:.0f}s@32kHz clips, seeded random-init weights (BASELINE configs[4] per GPU; a clip "
+                                    f"here is {L / rate:.0f} s, not the metric's 10 s: see realtime_factor)") if ms_workload else
+                                   (f"ResUNet30 separate() {'fp32' if args.dtype == 'f32' else args.dtype + ' MFMA convolutions'}, "
+                                    f"batch={B}/GPU, {L / 16000:.0f}s@16kHz clips, fixed precomputed condition embedding, "
+                                    f"seeded random-init weights (BASELINE configs[{1 if args.dtype == 'f32' else 2}]"
+                                    f"{'; configs[3] sharding' if world > 1 else ''})"),
+                       "clips_per_gpu_per_step": B, "samples_per_clip": L, "sample_rate": int(rate),
+                       "parallelism": f"clip-sharded x{world}"},
+            "realtime_factor": world * B * args.steps / dt * (L / rate),
+            "full": args.full,
+        }
+
+    def launch_record():
+        graph_on, graph_caps, graph_replays = eng.graph_stats()
+        return {"hipgraph_replay": graph_on, "captures": graph_caps, "replays_in_headline_loops": graph_replays,
+                "half_batch_overlap": half_batch_overlap(args.dtype, B), "extra_warmup_for_capture": extra_warm}
+
+    if not args.full:
+        if rank == 0:
+            res = headline()
+            res["launch"] = launch_record()
+            sys.stdout.flush()
+            os.write(real_stdout, (json.dumps(res) + "\n").encode())
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: everything beyond the headline ---------------------------------------------------------------------
     # the same step launched eagerly (no hipGraph replay): what the HIP-event-instrumented loop below runs on
     eng.set_graph_replay(False)
     dt_eager = min(timed(eng, args.steps, 1), timed(eng, args.steps, 1))  # (the faster of two passes: a host hiccup shows at 40 launches per step)
@@ -377,7 +477,7 @@ def main():
     else:
         exch["error"] = pg_error
 
-    graph_on, graph_caps, graph_replays = eng.graph_stats()
+    launch = launch_record()
     psteps = max(1, min(args.profile_steps, args.steps))
     prof = profiled(eng, psteps)
 
@@ -547,25 +647,10 @@ def main():
                   "bf16": "conv_bf16_kernel x22 + enc1_fused / dec6u_fused_bf16_kernel (a ConvBlockRes each, decoder_block6's with its "
                           "transposed conv inside): direct 3x3 + fused 1x1 shortcuts on v_mfma_f32_32x32x16_bf16",
                   "bf16x3": "conv_bf16_kernel (split operands, 3 MFMAs per product) x26"}[args.dtype]
-        res = {
-            "metric": "clips/sec (30s@32kHz)" if ms_workload else "clips/sec (10s@16kHz)", "value": world * B * args.steps / dt, "unit": "clips/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-            "config": {"workload": (f"multi-STFT ResUNet30 (windows 256/512/2048 at n_fft 2048, authored spec: DESIGN.md section 9) "
-                                    f"{'fp32' if args.dtype == 'f32' else args.dtype + ' MFMA convolutions'}, batch={B}/GPU, "
-                                    f"{L / rate:.0f}s@32kHz clips, seeded random-init weights (BASELINE configs[4] per GPU; a clip "
-                                    f"here is {L / rate:.0f} s, not the metric's 10 s: see realtime_factor)") if ms_workload else
-                                   (f"ResUNet30 separate() {'fp32' if args.dtype == 'f32' else args.dtype + ' MFMA convolutions'}, "
-                                    f"batch={B}/GPU, {L / 16000:.0f}s@16kHz clips, fixed precomputed condition embedding, "
-                                    f"seeded random-init weights (BASELINE configs[{1 if args.dtype == 'f32' else 2}]"
-                                    f"{'; configs[3] sharding' if world > 1 else ''})"),
-                       "clips_per_gpu_per_step": B, "samples_per_clip": L, "sample_rate": int(rate),
-                       "parallelism": f"clip-sharded x{world}"},
-            "realtime_factor": world * B * args.steps / dt * (L / rate),
+        res = headline()
+        res.update({
             "exchange": exch,
-            "launch": {"hipgraph_replay": graph_on, "captures": graph_caps, "replays_in_headline_loops": graph_replays,
-                       "half_batch_overlap": half_batch_overlap(args.dtype, B),
-                       "extra_warmup_for_capture": extra_warm,
+            "launch": {**launch,
                        "eager_ms_per_step": dt_eager / args.steps * 1e3,
                        "profiled_ms_per_step": sum(v for v in head["kernel_ms_per_step"].values()),
                        "note": "ms_per_step / value: the timed loop replays ONE captured hipGraph of the ~40 launches per "
@@ -591,7 +676,7 @@ def main():
                          "hbm_frac": head["hbm_frac"], "hbm_model": head["hbm_model"],
                          "whole_step_tflops": total_flops / (dt / args.steps) / 1e12},
             "kernel_ms_per_step": head["kernel_ms_per_step"],
-        }
+        })
         if modes:
             res["modes"] = modes
         if world == 1 and not args.no_cpu_baseline and args.dtype == "f32":

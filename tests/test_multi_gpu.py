@@ -63,6 +63,76 @@ def test_bench_rank_refuses_mismatched_world():
     assert r.returncode != 0 and "WORLD_SIZE=2" in r.stderr
 
 
+def _import_bench():
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import importlib
+    return importlib.import_module("bench")
+
+
+def test_bench_plain_run_options(monkeypatch, tmp_path):
+    """A plain run times the headline only: the extra legs are off unless --full, asking for --modes legs without --full is
+    refused, --steps 0 is refused, and the --dump-outputs directory reaches the ranks as an absolute path (they run in ROOT)."""
+    bench = _import_bench()
+    a = bench.parse_args(["--steps", "4", "--warmup", "2"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 4, 2)
+    assert bench.parse_args(["--full", "--modes", "bf16"]).modes == "bf16"
+    assert bench.parse_args(["--modes", "none"]).full is False
+    for bad in (["--modes", "bf16"], ["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+    monkeypatch.chdir(tmp_path)
+    assert bench.parse_args(["--dump-outputs", "out"]).dump_outputs == os.path.join(str(tmp_path), "out")
+    cmd = bench.launch_command(bench.absolute_dump_dir(["--gpus", "2", "--dump-outputs", "out", "--dump-outputs=o2", "--full"]), 2, 1)
+    assert cmd[-6:] == ["--gpus", "2", "--dump-outputs", os.path.join(str(tmp_path), "out"),
+                        "--dump-outputs=" + os.path.join(str(tmp_path), "o2"), "--full"]
+
+
+def test_bench_dump_outputs_files_and_sample(monkeypatch, tmp_path):
+    """--dump-outputs writes float32 <name>.npy (<name>_rank<r>.npy when N > 1); an output above its share of the size limit
+    is a fixed sample of its flat elements - the same elements on every run."""
+    bench = _import_bench()
+    x = torch.arange(2 * 3000, dtype=torch.float32).reshape(2, 3000)
+    bench.dump_outputs(str(tmp_path / "a"), {"waveform": x})
+    got = np.load(str(tmp_path / "a" / "waveform.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, x.numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 2 * (4096 + 4000))  # two ranks: 4000 bytes = 1000 elements each
+    for r in (0, 1):
+        bench.dump_outputs(str(tmp_path / "b"), {"waveform": x.double()}, rank=r, world=2)
+    s0, s1 = (np.load(str(tmp_path / "b" / f"waveform_rank{r}.npy")) for r in (0, 1))
+    assert s0.dtype == np.float32 and s0.shape == (1000,) and np.array_equal(s0, s1)
+    assert np.all(np.diff(s0) > 0) and np.all(np.isin(s0, x.numpy()))  # sorted flat indices of x = the values themselves
+    assert sorted(os.listdir(str(tmp_path / "b"))) == ["waveform_rank0.npy", "waveform_rank1.npy"]
+
+
+def test_current_library_needs_no_write_access(monkeypatch):
+    """A checkout built by another user may be read-only to the one that runs the benchmark: with a current library,
+    neither bench.py nor build() opens anything for writing (no build lock); a stale one is still built."""
+    import builtins
+    import types
+    bench = _import_bench()
+    import __graft_entry__ as ge
+    from lass_amd import _lib
+    real_open = builtins.open
+
+    def read_only_open(path, mode="r", *a, **kw):
+        if any(c in mode for c in "wax+"):
+            raise PermissionError(13, "Permission denied", path)
+        return real_open(path, mode, *a, **kw)
+
+    monkeypatch.setattr(ge, "_stale", lambda: False)
+    monkeypatch.setattr(_lib, "load", lambda: types.SimpleNamespace(lass_version=lambda: 100))
+    monkeypatch.setattr(builtins, "open", read_only_open)
+    ge.build()
+    calls = []
+    fake = types.SimpleNamespace(_stale=lambda: False, build=lambda: calls.append("build"))
+    bench.ensure_library(fake)
+    assert calls == []
+    fake._stale = lambda: True
+    bench.ensure_library(fake)
+    assert calls == ["build"]
+
+
 _EVAL_WORKER = r"""
 import os, sys
 root, csv_path, audio_dir, out_dir = sys.argv[1:5]
@@ -183,7 +253,7 @@ def test_bench_self_launches_two_ranks_on_one_gpu():
     """`python bench.py --gpus 2` exactly as the driver calls it (no launcher around it): two fresh ranks, one JSON line,
     the exchange step in the job.  gloo because both ranks share the one GPU of the test box (RCCL refuses that)."""
     res = _bench_json(["--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--batch", "2",
-                       "--length", "32000", "--no-cpu-baseline", "--modes", "none"])
+                       "--length", "32000", "--no-cpu-baseline", "--modes", "none", "--full"])
     assert res["n_gpus"] == 2 and res["steps"] == 2 and res["scaling"] == "weak"
     assert res["exchange"]["ranks"] == 2 and res["exchange"]["rows"] == 4 and res["exchange"]["allgather_ms"] > 0
     assert res["value"] == pytest.approx(2 * 2 * 2 / (res["ms_per_step"] * 2e-3), rel=1e-6)
@@ -196,7 +266,7 @@ def test_bench_two_ranks_at_the_full_configs3_per_rank_shape():
     rank and step - with two ranks (gloo: both share the test box's one GPU; the driver's run uses RCCL, one GPU each).  The
     exchange step gathers 2 x 16 rows, `value` is the whole job's clips over the max-over-ranks time."""
     res = _bench_json(["--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "3", "--modes", "none",
-                       "--no-cpu-baseline"], timeout=1500)
+                       "--no-cpu-baseline", "--full"], timeout=1500)
     assert res["n_gpus"] == 2 and res["steps"] == 3 and res["scaling"] == "weak" and res["dtype"] == "f32"
     cfg = res["config"]
     assert cfg["clips_per_gpu_per_step"] == 16 and cfg["samples_per_clip"] == 160000 and "configs[3] sharding" in cfg["workload"]
@@ -214,7 +284,7 @@ def test_bench_multistft_workload_two_ranks():
     """configs[4]'s per-GPU job (multi-STFT ResUNet, ONE 30 s @ 32 kHz clip per rank and step) through the same bench command
     and exchange step: `--workload multistft`, two gloo ranks on the one GPU."""
     res = _bench_json(["--gpus", "2", "--backend", "gloo", "--workload", "multistft", "--steps", "2", "--warmup", "3",
-                       "--modes", "none", "--no-cpu-baseline"], timeout=1500)
+                       "--modes", "none", "--no-cpu-baseline", "--full"], timeout=1500)
     assert res["n_gpus"] == 2 and res["metric"] == "clips/sec (30s@32kHz)"
     cfg = res["config"]
     assert cfg["clips_per_gpu_per_step"] == 1 and cfg["samples_per_clip"] == 960000 and cfg["sample_rate"] == 32000
@@ -229,9 +299,9 @@ def test_bench_multistft_workload_two_ranks():
 @pytest.mark.gpu
 def test_bench_single_rank_runs_the_rccl_exchange():
     """N=1: the per-clip metric rows still go through a torch.distributed all_gather on backend "nccl" (= RCCL), so the
-    path configs[3] relies on executes on every bench run; roofline.frac is an executed-FLOP fraction (<= 1)."""
+    path configs[3] relies on executes on every --full bench run; roofline.frac is an executed-FLOP fraction (<= 1)."""
     res = _bench_json(["--steps", "2", "--warmup", "1", "--batch", "2", "--length", "32000", "--no-cpu-baseline",
-                       "--modes", "bf16"])
+                       "--modes", "bf16", "--full"])
     ex = res["exchange"]
     assert ex.get("error") is None and ex["rccl_ranks"] == 1 and ex["rows"] == 2 and np.isfinite(ex["mean_sdr"])
     rf = res["roofline"]
@@ -240,3 +310,26 @@ def test_bench_single_rank_runs_the_rccl_exchange():
     assert 2.25 < rf["winograd_mult_reduction"] < 4.0 and "decoder_block6.conv1" in rf["winograd_f4x4_layers"]
     assert "eager_ms_per_step" in res["launch"] and res["launch"]["eager_ms_per_step"] > 0
     assert set(res["modes"]) == {"bf16"} and 0 < res["modes"]["bf16"]["frac"] <= 1.0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_reports_headline_and_dumps_outputs(tmp_path):
+    """A plain run (no --full): the headline line only - exactly --steps timed steps, ms_per_step = one of them - and
+    --dump-outputs holds the separated waveforms of the last timed step, which match the CPU oracle on the same inputs."""
+    from lass_amd import synthetic
+    from oracle import resunet as orr
+    B, L = 2, 32000
+    res = _bench_json(["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", str(B), "--length", str(L),
+                       "--dump-outputs", str(tmp_path / "out")])
+    assert (res["metric"], res["unit"], res["higher_is_better"], res["dtype"]) == ("clips/sec (10s@16kHz)", "clips/s", True, "f32")
+    assert res["steps"] == 3 and res["full"] is False and res["ms_per_step"] > 0
+    assert res["value"] == pytest.approx(B * 3 / (res["ms_per_step"] * 3e-3), rel=1e-6)
+    assert not {"roofline", "exchange", "modes", "cpu_baseline", "kernel_ms_per_step"} & set(res)
+    assert os.listdir(str(tmp_path / "out")) == ["waveform.npy"]
+    wav = np.load(str(tmp_path / "out" / "waveform.npy"))
+    assert wav.dtype == np.float32 and wav.shape == (B, L)
+    _, mix = synthetic.make_mixtures(B, L)
+    ref = orr.forward(orr.to_torch(synthetic.make_state_dict()),
+                      {"mixture": torch.from_numpy(mix)[:, None, :],
+                       "condition": torch.from_numpy(synthetic.make_condition(B))})["waveform"][:, 0].numpy()
+    assert float(np.sqrt(np.mean((wav - ref) ** 2))) <= 1e-4

@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 for i in 1 2; do for L in A B; do
   LIB=$A; [ $L = B ] && LIB=$B
-  LASS_HIP_LIB=$R/lass_amd/csrc/$LIB timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$L$i -o x -- python3 $R/bench.py --steps 5 --warmup 3 --no-cpu-baseline --modes none > $O/bench_$L$i.json 2> $O/err_$L$i.log || { tail -5 $O/err_$L$i.log; exit 1; }
+  LASS_HIP_LIB=$R/lass_amd/csrc/$LIB timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$L$i -o x -- python3 $R/bench.py --full --steps 5 --warmup 3 --no-cpu-baseline --modes none > $O/bench_$L$i.json 2> $O/err_$L$i.log || { tail -5 $O/err_$L$i.log; exit 1; }
 done; done
 cd $R
 python3 - <<PY

@@ -7,14 +7,14 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O
 cd $R
 for i in 1 2; do for L in A B; do
   LIB=$A; [ $L = B ] && LIB=$B
-  LASS_HIP_LIB=$R/lass_amd/csrc/$LIB timeout -k 10 300 python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --modes none $ARGS > $O/bench_$L$i.json 2> $O/err_$L$i.log || { tail -5 $O/err_$L$i.log; exit 1; }
+  LASS_HIP_LIB=$R/lass_amd/csrc/$LIB timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --modes none $ARGS > $O/bench_$L$i.json 2> $O/err_$L$i.log || { tail -5 $O/err_$L$i.log; exit 1; }
   python3 -c "
 import json; v = json.load(open('$O/bench_$L$i.json')); print('$L$i $LIB clips/s %.1f ms/step %.3f conv %.3f tconv %.3f' % (v['value'], v['ms_per_step'], v['kernel_ms_per_step']['conv3x3_mfma'], v['kernel_ms_per_step']['tconv_mfma']), flush=True)"
 done; done
 cd /tmp && export TMPDIR=/tmp
 for L in A B; do
   LIB=$A; [ $L = B ] && LIB=$B
-  LASS_SPLIT=0 LASS_HIP_LIB=$R/lass_amd/csrc/$LIB timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/trace_$L -o x -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --modes none $ARGS > $O/tbench_$L.json 2> $O/terr_$L.log || { tail -5 $O/terr_$L.log; exit 1; }
+  LASS_SPLIT=0 LASS_HIP_LIB=$R/lass_amd/csrc/$LIB timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/trace_$L -o x -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --modes none $ARGS > $O/tbench_$L.json 2> $O/terr_$L.log || { tail -5 $O/terr_$L.log; exit 1; }
 done
 cd $R
 python3 - <<PY

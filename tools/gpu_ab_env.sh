@@ -4,7 +4,7 @@ TAG=$1; VAR=$2; VA=$3; VB=$4; shift 4
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
 for i in 1 2; do for L in A B; do
   V=$VA; [ $L = B ] && V=$VB
-  env $VAR=$V timeout -k 10 300 python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline "$@" > $O/bench_$L$i.json 2> $O/err_$L$i.log || { tail -5 $O/err_$L$i.log; exit 1; }
+  env $VAR=$V timeout -k 10 300 python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline "$@" > $O/bench_$L$i.json 2> $O/err_$L$i.log || { tail -5 $O/err_$L$i.log; exit 1; }
   python3 - <<PY
 import json
 v = json.load(open("$O/bench_$L$i.json"))

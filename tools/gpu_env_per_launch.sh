@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r5u; rm -rf $O; mkdir -p $O
 for V in 1 2; do
   VAL=$VA; [ $V = 2 ] && VAL=$VB
   export $VAR=$VAL
-  LASS_SPLIT=0 timeout -k 10 200 rocprofv3 --kernel-trace --output-format csv -d $O/t$V -o x -- python3 $R/bench.py --steps 3 --warmup 1 --modes none --no-cpu-baseline "$@" > $O/b$V.json 2> $O/e$V.log || { tail -3 $O/e$V.log; exit 1; }
+  LASS_SPLIT=0 timeout -k 10 200 rocprofv3 --kernel-trace --output-format csv -d $O/t$V -o x -- python3 $R/bench.py --full --steps 3 --warmup 1 --modes none --no-cpu-baseline "$@" > $O/b$V.json 2> $O/e$V.log || { tail -3 $O/e$V.log; exit 1; }
 done
 cd $R
 python3 - <<PY

@@ -8,7 +8,7 @@ tail -4 $O/test.log
 grep -q "pytest rc 0" $O/test.log || exit 1
 timeout -k 10 300 python tools/conv_bench.py --iters 5 > $O/conv_bench.log 2>&1 || exit 1
 cat $O/conv_bench.log
-timeout -k 10 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline ${BENCH_ARGS:---modes none} > $O/bench.json 2> $O/bench.err || exit 1
+timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline ${BENCH_ARGS:---modes none} > $O/bench.json 2> $O/bench.err || exit 1
 python - <<PY
 import json
 d=json.loads([l for l in open("$O/bench.json") if l.startswith("{")][0])

@@ -2,7 +2,7 @@
 TAG=${1:-kstats}; shift
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o x -- python3 $R/bench.py --steps 5 --warmup 3 --no-cpu-baseline "$@" > $O/bench.json 2> $O/err.log || { tail -5 $O/err.log; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o x -- python3 $R/bench.py --full --steps 5 --warmup 3 --no-cpu-baseline "$@" > $O/bench.json 2> $O/err.log || { tail -5 $O/err.log; exit 1; }
 cd $R
 python3 - <<PY
 import csv,glob

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-launch MFMA utilisation of the SHIPPED pipeline from a rocprofv3 --pmc pass over
-`bench.py --steps 1 --warmup 1 --dtype D --modes none` (B=16, 10 s clips): the conv / transposed-conv launches of the LAST
+`bench.py --full --steps 1 --warmup 1 --dtype D --modes none` (B=16, 10 s clips): the conv / transposed-conv launches of the LAST
 step (everything behind the last stft2_kernel dispatch), in launch order = lass_separate's order (api.hip separate_impl):
     mfma_util = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 XCDs * 1024 SIMDs)          (MI355X_MICROARCH.md: the SQ
 counter counts cycles per SIMD summed over the chip, GRBM_GUI_ACTIVE is summed over the 8 XCDs)

@@ -2,7 +2,7 @@
 """Where the waves of each launch of the SHIPPED pipeline spend their cycles: shares of SQ_WAVE_CYCLES that are parked
 (SQ_WAIT_ANY: s_waitcnt / s_barrier), issue-stalled (SQ_WAIT_INST_ANY: the instruction cannot issue - matrix / vector pipe busy,
 operand dependency, memory queue full) and issuing (SQ_ACTIVE_INST_ANY), plus the vector-ALU, LDS and vector-memory shares, from
-two rocprofv3 --pmc passes over `bench.py --steps 1 --warmup 1 --dtype D --modes none` (tools/gpu_sq_counters.sh), last step.
+two rocprofv3 --pmc passes over `bench.py --full --steps 1 --warmup 1 --dtype D --modes none` (tools/gpu_sq_counters.sh), last step.
 Usage: sq_wait_table.py sq_pass1.csv sq_pass2.csv > table.md"""
 import collections
 import csv

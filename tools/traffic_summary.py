@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Fold rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes (separate runs of `bench.py --steps 1 --warmup 1 --modes none`)
+"""Fold rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes (separate runs of `bench.py --full --steps 1 --warmup 1 --modes none`)
 into profiles/<round>/conv_traffic_<dtype>.json: HBM-side bytes per launch of the dominant kernel class (conv3x3_mfma:
 the 26 Winograd / bf16 3x3 launches of a step), last step only.
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-launch HBM-side traffic of the SHIPPED pipeline from the two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) over
-`bench.py --steps 1 --warmup 1 --dtype D --modes none`: the conv launches of the last step in lass_separate's order, with
+`bench.py --full --steps 1 --warmup 1 --dtype D --modes none`: the conv launches of the last step in lass_separate's order, with
 the gfx950 unit corrections of tools/traffic_summary.py (both counters in units of 1024 B, FETCH_SIZE reporting half of the
 bytes read; fetch_calibration.json).  Usage: traffic_table.py fetch.csv write.csv [f32|bf16] > t.md"""
 import sys
