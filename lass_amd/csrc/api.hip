@@ -4,7 +4,6 @@
 // one launch.  torch.cat of the decoder (:258) is virtual: encoder blocks write their skip output straight into the
 // second channel half of the decoder's concat buffer and the transposed conv writes the first half.
 #include <hip/hip_runtime.h>
-#include <atomic>
 
 #include <algorithm>
 #include <cmath>
@@ -54,7 +53,6 @@ struct ResBlock {  // one ConvBlockRes
     int s1 = -1, s2 = -1;  // site indices
     float *w1 = nullptr, *w2 = nullptr, *wsc = nullptr;  // re-laid-out
     float *u1 = nullptr, *u2 = nullptr, *usc = nullptr;  // Winograd-domain copies (when enabled)
-    float *u1r = nullptr, *u2r = nullptr, *uscr = nullptr;  // 32-cout blocks: resident LDS images of wino32.hip
     float *u1f = nullptr, *u2f = nullptr;                   // conv1 / conv2 in the F(4x4,3x3) domain (wino4.hip), deep-K blocks
     void *b1 = nullptr, *b2 = nullptr, *bsc16 = nullptr;  // bf16 copies (LASS_COMPUTE_BF16 / _BF16X3)
     void *b1l = nullptr, *b2l = nullptr, *bscl = nullptr;  // lo halves of the hi+lo split (LASS_COMPUTE_BF16X3)
@@ -110,9 +108,6 @@ struct lass_ctx {
     bool wino = true;          // Winograd F(2x2,3x3) kernels for the 3x3 convs at W >= 32 (LASS_WINO=0: direct only)
     int wino4_mincin = 32;     // 3x3 convs with at least that many input channels (and >= 32-wide images) run as Winograd
                                // F(4x4,3x3) (wino4.hip); LASS_WINO4=<min Cin>, 0 = off (F(2x2,3x3) everywhere)
-    bool wino32 = true;        // weights-resident persistent kernel for the 32-cout layers (LASS_WINO32=0: wino.hip everywhere)
-    int live_class = 0;        // what this finalized context counts as in the process-wide packed-f32 guard (0 none, 1 bf16 MFMA
-                               // kernels, 2 routes launches to wino32.hip): see packed_guard_enter
     bool fuse_preconv = true;  // LASS_FUSE_PRECONV=0 materialises pre_conv's output with its own kernel
     bool fuse_pool = true;  // LASS_FUSE_POOL=0 selects the stand-alone pool kernel (A/B + parity of both paths)
     bool fuse_catb = true;  // bf16 mode: decoder concats as blocked bf16 copies (LASS_FUSE_CATB=0: f32 concat)
@@ -139,9 +134,9 @@ struct lass_ctx {
         size_t need = 0;         // workspace bytes the captured plan addresses (re-checked on every replay)
         int seen = 0;            // calls with this key so far
         unsigned long used = 0;  // g_tick of the last call (LRU)
-        bool split = false;      // the captured launch sequence runs part-batches (their layouts are what the workspace holds)
+        bool split = false;      // the captured launch sequence runs half-batches (their layouts are what the workspace holds)
     };
-    // (B, L) -> did the LAST lass_separate of that shape run as part-batches?  lass_workspace_tensor refuses only then: eager
+    // (B, L) -> did the LAST lass_separate of that shape run as half-batches?  lass_workspace_tensor refuses only then: eager
     // calls (the first calls of a key, LASS_GRAPH=0, changing pointers) leave the whole-batch layout, taps stay readable.
     std::map<std::pair<int, int>, bool> last_split;
     static constexpr int kGraphSlots = 4;
@@ -160,9 +155,8 @@ struct lass_ctx {
     // the unsplit launch, without one 2 % faster; a graph's branches do not care).  LASS_SPLIT=2: eager launches too; 0: never.
     // DESIGN.md section 5b has the measurements and the co-residency hazard found on the way.
     int split_batch = 1;
-    int split_parts = 2;  // LASS_SPLIT_PARTS: 2 or 4 part-batches (each of at least 4 clips)
-    hipStream_t s2[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
+    hipStream_t s2 = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     unsigned long gen = 0;         // bumped by lass_finalize: a graph holds weight pointers
     long g_replays = 0, g_captures = 0;
     bool profiling = false;
@@ -454,7 +448,7 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
         p.in = x0; p.in_bs = HW;
         p.pre_w = pre->w; p.pre_b = pre->b;
     }
-    p.w_wino = rb.u1; p.w_wino32 = rb.u1r; p.w_wino4 = rb.u1f;
+    p.w_wino = rb.u1; p.w_wino4 = rb.u1f;
     p.w_bf16 = rb.b1; p.w_bf16_lo = rb.b1l;
     const bool bf1 = c->compute_mode != LASS_COMPUTE_F32 && rb.b1 && rb.b2 && lass_bf16_supported(p) &&
                      (!x0 || W % 32 == 0) && rb.cout % 16 == 0 && (rb.cin == rb.cout || (rb.bsc16 && rb.cin % 16 == 0));
@@ -472,8 +466,6 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
             HIP_TRY(c, lass_launch_conv_bf16(x0 ? CONV1_ACT_PRE : CONV1_ACT, p, st));
         else if (wino1 && rb.u1f && lass_wino4_supported(x0 ? CONV1_ACT_PRE : CONV1_ACT, p))
             HIP_TRY(c, lass_launch_wino4(x0 ? CONV1_ACT_PRE : CONV1_ACT, p, st));
-        else if (wino1 && c->wino32 && lass_wino32_supported(x0 ? CONV1_ACT_PRE : CONV1_ACT, p))
-            HIP_TRY(c, lass_launch_wino32(x0 ? CONV1_ACT_PRE : CONV1_ACT, p, st));
         else if (wino1)
             HIP_TRY(c, lass_launch_wino(x0 ? CONV1_ACT_PRE : CONV1_ACT, p, st));
         else
@@ -484,7 +476,7 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
     q.in = a2; q.in_bs = rb.cout * HW; q.Cin = rb.cout; q.w = rb.w2; q.Nw = rb.cout; q.N = rb.cout;
     q.out = out; q.out_bs = out_bs; q.B = B; q.H = H; q.W = W;
     q.pool_out = pool_out; q.pool_h = pool_h; q.pool_bs = pool_bs;
-    q.w_wino = rb.u2; q.w2_wino = rb.usc; q.w_wino32 = rb.u2r; q.w2_wino32 = rb.uscr; q.w_wino4 = rb.u2f;
+    q.w_wino = rb.u2; q.w2_wino = rb.usc; q.w_wino4 = rb.u2f;
     if (mh) {  // the block output is consumed by the fused head and never written
         q.out = nullptr;
         q.mask_w = rawp(c, "base.after_conv.weight"); q.mask_b = rawp(c, "base.after_conv.bias");
@@ -558,8 +550,6 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
             HIP_TRY(c, lass_launch_conv_bf16(x0 ? CONV2_IDENT_PRE : CONV2_IDENT, q, st));
         else if (wino2 && x0 && rb.u2f && lass_wino4_supported(CONV2_IDENT_PRE, q))
             HIP_TRY(c, lass_launch_wino4(CONV2_IDENT_PRE, q, st));
-        else if (wino2 && c->wino32 && lass_wino32_supported(x0 ? CONV2_IDENT_PRE : CONV2_IDENT, q))
-            HIP_TRY(c, lass_launch_wino32(x0 ? CONV2_IDENT_PRE : CONV2_IDENT, q, st));
         else if (wino2)
             HIP_TRY(c, lass_launch_wino(x0 ? CONV2_IDENT_PRE : CONV2_IDENT, q, st));
         else
@@ -569,8 +559,6 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
             HIP_TRY(c, lass_launch_conv_bf16(CONV2_SHORTCUT, q, st));
         else if (wino2 && rb.u2f && lass_wino4_supported(CONV2_SHORTCUT, q))
             HIP_TRY(c, lass_launch_wino4(CONV2_SHORTCUT, q, st));
-        else if (wino2 && c->wino32 && lass_wino32_supported(CONV2_SHORTCUT, q))
-            HIP_TRY(c, lass_launch_wino32(CONV2_SHORTCUT, q, st));
         else if (wino2)
             HIP_TRY(c, lass_launch_wino(CONV2_SHORTCUT, q, st));
         else
@@ -692,10 +680,6 @@ void drop_graphs(lass_ctx* c) {
 
 // A batch is split into two overlapping half-batches when it is large enough for each half to fill the GPU on its own
 bool split_halves(const lass_ctx* c, int B) { return c->split_batch > 0 && !c->profiling && B >= 8 && (B % 2) == 0; }
-int split_parts(const lass_ctx* c, int B) {
-    if (!split_halves(c, B)) return 1;
-    return c->split_parts == 4 && B >= 16 && (B % 4) == 0 ? 4 : 2;
-}
 
 const ResBlock* find_block(const lass_ctx* c, const std::string& prefix) {
     for (const auto& rb : c->enc) if (rb.prefix == prefix) return &rb;
@@ -739,7 +723,6 @@ static int create_impl(lass_ctx** out, int device_id, const Geometry& geom) {
     c->device = device_id;
     c->g = geom;
     if (const char* e = getenv("LASS_WINO")) c->wino = atoi(e) != 0;
-    if (const char* e = getenv("LASS_WINO32")) c->wino32 = atoi(e) != 0;
     if (const char* e = getenv("LASS_FUSE_POOL")) c->fuse_pool = atoi(e) != 0;
     if (const char* e = getenv("LASS_FUSE_MASK")) c->fuse_mask = atoi(e) != 0;
     if (const char* e = getenv("LASS_FUSE_CATB")) c->fuse_catb = atoi(e) != 0;
@@ -747,7 +730,6 @@ static int create_impl(lass_ctx** out, int device_id, const Geometry& geom) {
     if (const char* e = getenv("LASS_FUSE_UP")) c->fuse_up = atoi(e) != 0;
     if (const char* e = getenv("LASS_WINO4")) c->wino4_mincin = atoi(e);
     if (const char* e = getenv("LASS_SPLIT")) c->split_batch = std::max(0, std::min(2, atoi(e)));
-    if (const char* e = getenv("LASS_SPLIT_PARTS")) c->split_parts = atoi(e) == 4 ? 4 : 2;
     if (const char* e = getenv("LASS_FUSE_PRECONV")) c->fuse_preconv = atoi(e) != 0;
     if (const char* e = getenv("LASS_GRAPH")) c->use_graph = atoi(e) != 0;
     c->prof.resize(P_COUNT);
@@ -809,43 +791,8 @@ int lass_create_multistft(lass_ctx** out, int device_id, int n_fft, int n_window
     return create_impl(out, device_id, g);
 }
 
-// Process-wide guard for the one kernel file that carries packed-f32 arithmetic (wino32.hip's hand-written float2 transform).
-// On gfx950 a wave executing v_pk_*_f32 beside a workgroup that feeds v_mfma_f32_32x32x16_bf16 from LDS returned wrong values
-// (the x half of a packed result, lanes 48-63, from right operands).  Every other kernel is built without
-// packed f32 (-fno-slp-vectorize + ISA audit); wino32.hip runs only in f32 contexts behind LASS_WINO4 != 32.  Two contexts of one
-// process may launch on two streams, so a context that can route to wino32.hip and a context with bf16 MFMA kernels must not be
-// alive together: the second one to finalize is refused.
-static std::atomic<int> g_live_bf16{0}, g_live_w32{0};
-static void packed_guard_leave(lass_ctx* c) {
-    if (c->live_class == 1) --g_live_bf16;
-    if (c->live_class == 2) --g_live_w32;
-    c->live_class = 0;
-}
-static bool routes_to_wino32(const lass_ctx* c, int compute_mode) {
-    // wino4.hip takes every layer wino32.hip could serve when its threshold is at most the 32 channels of those layers
-    return compute_mode == LASS_COMPUTE_F32 && c->wino && c->wino32 && (c->wino4_mincin <= 0 || c->wino4_mincin > kPreCh);
-}
-static int packed_guard_enter(lass_ctx* c, int compute_mode) {
-    packed_guard_leave(c);
-    if (compute_mode != LASS_COMPUTE_F32) {
-        if (g_live_w32.load() > 0)
-            return fail(c, LASS_ERR_STATE, "lass_finalize: a context of this process routes launches to wino32.hip (LASS_WINO4), whose packed-f32 "
-                                           "arithmetic is unsafe beside bf16 MFMA kernels on gfx950 - destroy it first, or leave LASS_WINO4 at its default");
-        ++g_live_bf16;
-        c->live_class = 1;
-    } else if (routes_to_wino32(c, compute_mode)) {
-        if (g_live_bf16.load() > 0)
-            return fail(c, LASS_ERR_STATE, "lass_finalize: LASS_WINO4 routes this f32 context to wino32.hip, whose packed-f32 arithmetic is unsafe "
-                                           "beside the bf16 MFMA kernels of another live context on gfx950 - destroy that context first, or set LASS_WINO32=0");
-        ++g_live_w32;
-        c->live_class = 2;
-    }
-    return 0;
-}
-
 int lass_destroy(lass_ctx* c) {
     if (!c) return LASS_ERR_ARG;
-    packed_guard_leave(c);
     (void)hipSetDevice(c->device);
     free_owned(c);
     for (auto& kv : c->raw) (void)hipFree(kv.second.d);
@@ -853,10 +800,8 @@ int lass_destroy(lass_ctx* c) {
     (void)hipDeviceSynchronize();  // no replay of a graph below is in flight any more
     drop_graphs(c);
     if (c->g_stream) (void)hipStreamDestroy(c->g_stream);
-    for (int i = 0; i < 3; ++i) {
-        if (c->s2[i]) (void)hipStreamDestroy(c->s2[i]);
-        if (c->ev_join[i]) (void)hipEventDestroy(c->ev_join[i]);
-    }
+    if (c->s2) (void)hipStreamDestroy(c->s2);
+    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     (void)hipFree(c->tw2k);
     delete c;
@@ -896,7 +841,6 @@ int lass_finalize(lass_ctx* c, int compute_mode) {
     if (!c) return LASS_ERR_ARG;
     if (compute_mode != LASS_COMPUTE_F32 && compute_mode != LASS_COMPUTE_BF16 && compute_mode != LASS_COMPUTE_BF16X3)
         return fail(c, LASS_ERR_ARG, "unsupported compute mode");
-    if (int r = packed_guard_enter(c, compute_mode)) return r;
     c->last_split.clear();
     c->compute_mode = compute_mode;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -944,7 +888,6 @@ int lass_finalize(lass_ctx* c, int compute_mode) {
         HIP_TRY(c, lass_launch_relayout_conv(w1, rb.cout, rb.cin, 9, rb.w1, st));
         HIP_TRY(c, lass_launch_relayout_conv(w2, rb.cout, rb.cout, 9, rb.w2, st));
         rb.u1 = rb.u2 = rb.usc = nullptr;
-        rb.u1r = rb.u2r = rb.uscr = nullptr;
         rb.u1f = rb.u2f = nullptr;
         rb.b1 = rb.b2 = rb.bsc16 = rb.b1l = rb.b2l = rb.bscl = nullptr;
         const bool bfm = c->compute_mode == LASS_COMPUTE_BF16 || c->compute_mode == LASS_COMPUTE_BF16X3;
@@ -983,16 +926,6 @@ int lass_finalize(lass_ctx* c, int compute_mode) {
                 if (dev_alloc(c, &rb.u2f, (size_t)36 * rb.cout * rb.cout)) return LASS_ERR_HIP;
                 HIP_TRY(c, lass_launch_wino4_weights(w2, rb.cout, rb.cout, rb.u2f, st));
             }
-            // full-resolution 32-channel blocks, and encoder_block2 (32 -> 64) as two 32-cout slices: wino32.hip
-            if ((rb.cout == 32 && rb.cin % 8 == 0) || (rb.cout == 64 && rb.cin == 32)) {
-                const size_t ns = rb.cout / 32;
-                if (dev_alloc(c, &rb.u1r, ns * 512 * rb.cin) || dev_alloc(c, &rb.u2r, ns * 512 * rb.cout)) return LASS_ERR_HIP;
-                HIP_TRY(c, lass_launch_wino32_weights(w1, rb.cout, rb.cin, rb.u1r, st));
-                HIP_TRY(c, lass_launch_wino32_weights(w2, rb.cout, rb.cout, rb.u2r, st));
-            } else if (rb.cout == 128 && rb.cin == 64) {  // encoder_block3.conv1 as four slices (conv2's weights do not fit)
-                if (dev_alloc(c, &rb.u1r, (size_t)4 * 512 * rb.cin)) return LASS_ERR_HIP;
-                HIP_TRY(c, lass_launch_wino32_weights(w1, rb.cout, rb.cin, rb.u1r, st));
-            }
         }
         rb.wsc = nullptr;
         rb.bsc = nullptr;
@@ -1017,10 +950,6 @@ int lass_finalize(lass_ctx* c, int compute_mode) {
             if (c->wino && c->compute_mode == LASS_COMPUTE_F32) {
                 if (dev_alloc(c, &rb.usc, (size_t)4 * rb.cout * rb.cin)) return LASS_ERR_HIP;
                 HIP_TRY(c, lass_launch_wino_shortcut_weights(ws, rb.cout, rb.cin, rb.usc, st));
-                if ((rb.cout == 32 && rb.cin % 8 == 0) || (rb.cout == 64 && rb.cin == 32)) {
-                    if (dev_alloc(c, &rb.uscr, (size_t)(rb.cout / 32) * 128 * rb.cin)) return LASS_ERR_HIP;
-                    HIP_TRY(c, lass_launch_wino32_shortcut_weights(ws, rb.cout, rb.cin, rb.uscr, st));
-                }
             }
         }
         return 0;
@@ -1074,11 +1003,11 @@ int lass_workspace_bytes(const lass_ctx* c, int B, int L, size_t* bytes) {
     Plan pl;
     if (make_plan(c, B, L, &pl)) return LASS_ERR_ARG;  // B < 1, L <= 512 or L beyond the 32-bit per-clip addressing limit
     *bytes = pl.total;
-    if (const int P = split_parts(c, B); P > 1) {  // the part-batch plans side by side (they differ from the whole plan by alignment padding only)
+    if (split_halves(c, B)) {  // the half-batch plans side by side (they differ from the whole plan by alignment padding only)
         Plan ph;
-        if (make_plan(c, B / P, L, &ph)) return LASS_ERR_ARG;
-        const size_t all = P * ((ph.total + 255) / 256 * 256);
-        if (all > *bytes) *bytes = all;
+        if (make_plan(c, B / 2, L, &ph)) return LASS_ERR_ARG;
+        const size_t both = 2 * ((ph.total + 255) / 256 * 256);
+        if (both > *bytes) *bytes = both;
     }
     return 0;
 }
@@ -1231,7 +1160,7 @@ int lass_front_end(lass_ctx* c, const float* wav, int B, int L, float* mag, floa
 int lass_workspace_tensor(const lass_ctx* c, int B, int L, const char* name_c, size_t* offset, int64_t shape[4],
                           int64_t strides[4]) {
     if (!c || !name_c || !offset || !shape || !strides) return LASS_ERR_ARG;
-    // a batch whose LAST separation ran as part-batches (B >= 8, LASS_SPLIT: the replayed graph by default) holds their layouts
+    // a batch whose LAST separation ran as half-batches (B >= 8, LASS_SPLIT: the replayed graph by default) holds their layouts
     // in its workspace, not this one; after an eager, unsplit call - or before any call - the whole-batch layout is what is there
     if (auto it = c->last_split.find({B, L}); it != c->last_split.end() && it->second) return LASS_ERR_STATE;
     Plan pl;
@@ -1513,35 +1442,29 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
 static int separate_any(lass_ctx* c, const float* mixture, const float* condition, float* out, int B, int L, void* workspace,
                         size_t workspace_bytes, hipStream_t stream, bool capturing) {
     Plan ph;
-    const int P = c->finalized ? split_parts(c, B) : 1;
-    if (P < 2 || !mixture || !condition || !out || !workspace || (!capturing && c->split_batch < 2) || make_plan(c, B / P, L, &ph) ||
-        P * ((ph.total + 255) / 256 * 256) > workspace_bytes) {
+    if (!c->finalized || !split_halves(c, B) || !mixture || !condition || !out || !workspace || (!capturing && c->split_batch < 2) ||
+        make_plan(c, B / 2, L, &ph) || 2 * ((ph.total + 255) / 256 * 256) > workspace_bytes) {
         c->last_split[{B, L}] = false;
         return separate_impl(c, mixture, nullptr, condition, out, B, L, workspace, workspace_bytes, stream, "lass_separate");
     }
     c->last_split[{B, L}] = true;
     HIP_TRY(c, hipSetDevice(c->device));
     if (!c->ev_fork) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-    for (int i = 0; i < P - 1; ++i)
-        if (!c->s2[i]) {
-            HIP_TRY(c, hipStreamCreateWithFlags(&c->s2[i], hipStreamNonBlocking));
-            HIP_TRY(c, hipEventCreateWithFlags(&c->ev_join[i], hipEventDisableTiming));
-        }
-    const int h = B / P;
-    const size_t part_ws = (ph.total + 255) / 256 * 256;
+    if (!c->s2) {
+        HIP_TRY(c, hipStreamCreateWithFlags(&c->s2, hipStreamNonBlocking));
+        HIP_TRY(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
+    }
+    const int h = B / 2;
+    const size_t half_ws = (ph.total + 255) / 256 * 256;
     HIP_TRY(c, hipEventRecord(c->ev_fork, stream));
-    for (int i = 0; i < P - 1; ++i) HIP_TRY(c, hipStreamWaitEvent(c->s2[i], c->ev_fork, 0));
-    int r = 0;
-    for (int i = 0; i < P; ++i) {
-        const int ri = separate_impl(c, mixture + (size_t)i * h * L, nullptr, condition + (size_t)i * h * LASS_COND, out + (size_t)i * h * L,
-                                     h, L, (char*)workspace + i * part_ws, part_ws, i ? c->s2[i - 1] : stream, "lass_separate");
-        if (!r) r = ri;
-    }
-    // the joins are recorded even after a failure: a capturing stream must get its branches back
-    for (int i = 0; i < P - 1; ++i) {
-        HIP_TRY(c, hipEventRecord(c->ev_join[i], c->s2[i]));
-        HIP_TRY(c, hipStreamWaitEvent(stream, c->ev_join[i], 0));
-    }
+    HIP_TRY(c, hipStreamWaitEvent(c->s2, c->ev_fork, 0));
+    int r = separate_impl(c, mixture, nullptr, condition, out, h, L, workspace, half_ws, stream, "lass_separate");
+    const int r2 = separate_impl(c, mixture + (size_t)h * L, nullptr, condition + (size_t)h * LASS_COND, out + (size_t)h * L, h, L,
+                                 (char*)workspace + half_ws, half_ws, c->s2, "lass_separate");
+    if (!r) r = r2;
+    // the join is recorded even after a failure: a capturing stream must get its branch back
+    HIP_TRY(c, hipEventRecord(c->ev_join, c->s2));
+    HIP_TRY(c, hipStreamWaitEvent(stream, c->ev_join, 0));
     return r;
 }
 
@@ -1599,10 +1522,10 @@ int lass_separate(lass_ctx* c, const float* mixture, const float* condition, flo
                     ((uintptr_t)workspace & 255) != 0)
                     return separate_any(c, mixture, condition, out, B, L, workspace, workspace_bytes, (hipStream_t)stream, false);
                 slot->need = pl0.total;
-                if (const int P = split_parts(c, B); P > 1) {  // (checked again at capture time by separate_any: smaller workspaces run unsplit)
+                if (split_halves(c, B)) {  // (checked again at capture time by separate_any: smaller workspaces run unsplit)
                     Plan ph0;
-                    if (!make_plan(c, B / P, L, &ph0) && P * ((ph0.total + 255) / 256 * 256) <= workspace_bytes)
-                        slot->need = std::max(slot->need, P * ((ph0.total + 255) / 256 * 256));
+                    if (!make_plan(c, B / 2, L, &ph0) && 2 * ((ph0.total + 255) / 256 * 256) <= workspace_bytes)
+                        slot->need = std::max(slot->need, 2 * ((ph0.total + 255) / 256 * 256));
                 }
             }
             HIP_TRY(c, hipSetDevice(c->device));
@@ -1612,11 +1535,12 @@ int lass_separate(lass_ctx* c, const float* mixture, const float* condition, flo
                 const int r = separate_any(c, mixture, condition, out, B, L, workspace, workspace_bytes, c->g_stream, true);
                 hipGraph_t graph = nullptr;
                 const hipError_t e = hipStreamEndCapture(c->g_stream, &graph);  // always ends the capture, also after a failure
-                if (r == 0 && e == hipSuccess && graph && hipGraphInstantiate(&slot->exec, graph, nullptr, nullptr, 0) == hipSuccess)
+                if (r == 0 && e == hipSuccess && graph && hipGraphInstantiate(&slot->exec, graph, nullptr, nullptr, 0) == hipSuccess) {
                     ok = true;
-                if (auto it = c->last_split.find({B, L}); it != c->last_split.end()) slot->split = it->second;
-                else
+                    if (auto it = c->last_split.find({B, L}); it != c->last_split.end()) slot->split = it->second;
+                } else {
                     slot->exec = nullptr;
+                }
                 if (graph) (void)hipGraphDestroy(graph);
             }
             if (ok) {

@@ -515,16 +515,6 @@ int env_int(const char* name, int dflt) {
     return e ? atoi(e) : dflt;
 }
 
-// -1 = automatic (double-buffered LDS for the 64-wide 3x3 tiles, where it measured 1-9 % faster; single-buffered for
-// the 32-wide tiles and the 1-tap kernels, which prefer the higher occupancy); 0 / 1 force a variant (A/B runs).
-int conv_variant() {
-    static int v = [] {
-        const char* e = getenv("LASS_CONV_VARIANT");
-        return e ? atoi(e) : -1;
-    }();
-    return v;
-}
-
 #ifdef LASS_CONV_DIAG
 void diag_report(long long* dbuf, size_t nblk, const ConvArgs& p, int taps) {
     std::vector<long long> h(nblk * 8);
@@ -575,16 +565,11 @@ hipError_t launch_one(const ConvArgs& p0, hipStream_t stream) {
         ~Rep() { diag_report(d, n, p, TAPS); }
     } rep{dbuf, nblk, p};
 #endif
-    const int var = conv_variant();
-    const int kc = TAPS == 9 ? 8 : 16;
-    const int nchunks = p.Cin / kc;
-    // double-buffered kernel (one barrier per chunk) for the 64-wide tiles with many chunks, where it measured 1-9 %
-    // faster; the single-buffered kernel (higher occupancy) everywhere else
-    const bool db = var < 0 ? (TAPS == 9 && NCO == 2 && PW == 32 && nchunks >= 16 && !(FLAGS & F_RES))
-                            : ((var & 1) != 0 && !(FLAGS & F_RES));
+    // double-buffered kernel (one barrier per chunk) for the 64-wide 3x3 tiles with many chunks (16 and more of 8
+    // channels), where it measured 1-9 % faster; the single-buffered kernel (higher occupancy) everywhere else
     constexpr bool HAS_DB = TAPS == 9 && NCO == 2 && PW == 32 && !(FLAGS & F_RES);  // geometries the db kernel exists for
     if constexpr (HAS_DB) {
-        if (db) {
+        if (p.Cin / 8 >= 16) {
             hipLaunchKernelGGL((conv_kernel_db<TAPS, NCO, NPX, PW, FLAGS>), grid, dim3(NTHREADS), 0, stream, p);
             return hipGetLastError();
         }

@@ -323,16 +323,13 @@ struct Reg1x1 {
     }
 };
 
-#ifndef LASS_HALF_SLAB
-#define LASS_HALF_SLAB 1
-#endif
 // The instantiations that run the half-slab schedule (see HALF_SLAB below) are built for three waves per SIMD: the encoder
 // blocks' conv2 + shortcut kernels of the blocked-bf16 pipeline.  Measured per launch against the two-slab build: encoder
 // conv2 + shortcut (154 registers, no spill) 0.906; decoder conv2 + shortcut, whose activated output needs two more tables,
 // 0.981 at 168 registers WITH 100 B of scratch per thread (0.2 GB of spill traffic per launch) - left at two slabs; the
 // conv1 kernels, whose launch is nearly all main phase, 1.022 - left at two slabs and two workgroups per CU.
 template <int TAPS, int NCO, int NPX, int FLAGS, int SPLIT>
-constexpr bool half_slab_v = LASS_HALF_SLAB && (FLAGS & F_INBF16) != 0 && (FLAGS & F_PHASEB) != 0 && (FLAGS & F_EPIACT) == 0 && SPLIT == 1 &&
+constexpr bool half_slab_v = (FLAGS & F_INBF16) != 0 && (FLAGS & F_PHASEB) != 0 && (FLAGS & F_EPIACT) == 0 && SPLIT == 1 &&
                              TAPS == 9 && NCO == 2 && NPX == 2;
 
 template <int TAPS, int NCO, int NPX, int PW, int FLAGS, int SPLIT>
@@ -360,11 +357,8 @@ __global__ __launch_bounds__(NTHREADS, (half_slab_v<TAPS, NCO, NPX, FLAGS, SPLIT
     // Round 5: 1x1 contractions whose operands are blocked bf16 go from global memory straight into the MFMA (Reg1x1):
     // RF_MAIN = the whole K loop of a 1x1 kernel (transposed convs), RF_SC = the 1x1 shortcut folded into the 3x3 chunk loop
     // (at most RF_Q shortcut chunks per 3x3 chunk; a launch with more falls back to the ring schedule behind the main loop).
-#ifndef LASS_RF1X1
-#define LASS_RF1X1 1
-#endif
-    constexpr bool RF_MAIN = LASS_RF1X1 && TAPS == 1 && INBF && PA::WDMA && !HASB;
-    constexpr bool RF_SC = LASS_RF1X1 && TAPS == 9 && HASB && IN2BF && INBF && PA::WDMA && PB::WDMA;
+    constexpr bool RF_MAIN = TAPS == 1 && INBF && PA::WDMA && !HASB;
+    constexpr bool RF_SC = TAPS == 9 && HASB && IN2BF && INBF && PA::WDMA && PB::WDMA;
     constexpr int RF_Q = HALF_SLAB ? 1 : 2;  // (the half-slab kernels live within 168 registers: three workgroups per CU)
     constexpr int PA_LDS = INBF ? 2 * PA::IN_U4 + (PA::WDMA && !HALF_SLAB ? 2 : 1) * PA::W_U4 : PA::LDS_U4;
     constexpr int PB_LDS = IN2BF ? (PB::WDMA ? 4 : 2) * PB::IN_U4 + (PB::WDMA ? 4 : 1) * PB::W_U4 : PB::LDS_U4;  // WDMA: >= 4 ring slots
@@ -660,11 +654,9 @@ __global__ __launch_bounds__(NTHREADS, (half_slab_v<TAPS, NCO, NPX, FLAGS, SPLIT
         const v4i32 wd_rs = make_rsrc_words(wb2, wbytes2);
         const v4i32 wdl_rs = SPLIT == 2 ? make_rsrc_words(wb2_lo, wbytes2) : wd_rs;
         const unsigned img0 = (unsigned)(size_t)(__attribute__((address_space(3))) uint4*)lds4;
-        const unsigned wl0 = img0 + (unsigned)(2 * PB::IN_U4 * 16);
         pb.init_dma(lane, wave, y0, x0, p.H, p.W);
         pb.init_wdma(lane, p.Nw);
         __syncthreads();  // phase A has finished with the LDS
-#ifndef LASS_SC_TWO_BUFFERS
         {
             // A chunk of the 1x1 shortcut is ONE tap: NCO x NPX MFMAs (128 cycles) against a DMA round trip of a microsecond, and
             // Cin2 / 16 = 2 ... 48 of them follow each other - a two-buffer pipeline pays the whole latency per chunk.  The
@@ -695,21 +687,6 @@ __global__ __launch_bounds__(NTHREADS, (half_slab_v<TAPS, NCO, NPX, FLAGS, SPLIT
                 PB::compute(slot, slot + PB::IN_U4, acc, lane, wave);
             }
         }
-#else   // the round-3 schedule (two buffers, one DMA round trip per chunk): -DLASS_SC_TWO_BUFFERS, for A/B
-        pb.issue_dma(r_rs, r_rs, 0u, img0, wave);
-        pb.issue_wdma(wd_rs, wdl_rs, 0u, p.Nw, wl0, wave);
-        for (int ch = 0; ch < nB; ++ch) {
-            const int cur = ch & 1;
-            wait_vmcnt<0>();
-            __syncthreads();
-            if (ch + 1 < nB) {
-                pb.issue_dma(r_rs, r_rs, (unsigned)((ch + 1) * 2 * HW) * 16u, img0 + (unsigned)((cur ^ 1) * PB::IN_U4 * 16), wave);
-                pb.issue_wdma(wd_rs, wdl_rs, (unsigned)((ch + 1) * 2 * p.Nw) * 16u, p.Nw,
-                              wl0 + (unsigned)((cur ^ 1) * PB::W_U4 * 16), wave);
-            }
-            PB::compute(lds4 + cur * PB::IN_U4, lds4 + 2 * PB::IN_U4 + cur * PB::W_U4, acc, lane, wave);
-        }
-#endif
         } else {
             uint4* wl_b = lds4 + 2 * PB::IN_U4;
             const unsigned img0 = (unsigned)(size_t)(__attribute__((address_space(3))) uint4*)lds4;
@@ -841,24 +818,9 @@ hipError_t launch_bf16(const ConvArgs& p, hipStream_t stream) {
     constexpr bool NARROW = (FLAGS & (F_MASK | F_RESPRE | F_PRECONV)) != 0;  // 32-cout-only kernels (host-checked N == 32)
     if constexpr (NARROW) {
         if (pw != 32 || p.N != 32) return hipErrorInvalidValue;
-        if constexpr ((FLAGS & F_INBF16) != 0) {
-            static const int force = [] { const char* e = getenv("LASS_BF16_NPX"); return e ? atoi(e) : 0; }();
-            if (force == 4) return launch_bf16_one<TAPS, 1, 4, 32, FLAGS>(p, stream);
-        }
         return launch_bf16_one<TAPS, 1, 2, 32, FLAGS>(p, stream);
     } else
     if (pw == 32) {
-        if constexpr ((FLAGS & F_INBF16) != 0) {
-            // DMA-fed kernels: 16-row tiles (each wave 4 px-tiles x NCO cout-tiles: 0.75 instead of 1 fragment read per
-            // MFMA, the weight slab shared by twice the pixels) wherever that still leaves >= 2 workgroups per CU slot
-            const long wgs16 = (long)(p.W / 32) * ((p.H + 15) / 16) * (p.N / (p.N % 64 == 0 ? 64 : 32)) * p.B;
-            static const int force = [] { const char* e = getenv("LASS_BF16_NPX"); return e ? atoi(e) : 0; }();
-            (void)wgs16;
-            if (force == 4) {  // measured r2: 16-row tiles lose 15-20 % on every layer (occupancy beats LDS traffic)
-                if (p.N % 64 == 0) return launch_bf16_one<TAPS, 2, 4, 32, FLAGS>(p, stream);
-                return launch_bf16_one<TAPS, 1, 4, 32, FLAGS>(p, stream);
-            }
-        }
         if (p.N % 64 == 0) return launch_bf16_one<TAPS, 2, 2, 32, FLAGS>(p, stream);
         return launch_bf16_one<TAPS, 1, 2, 32, FLAGS>(p, stream);
     }

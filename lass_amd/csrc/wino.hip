@@ -39,19 +39,8 @@ constexpr int KCB = 32;  // shortcut phase: 32 channels x 4 xi per chunk (the sa
 // Wave priority by phase.  A wave's staging / transform chain (a few dozen VALU and LDS instructions strung between
 // barriers) is longer than its MFMA phase, and its VALU instructions queue behind the SIMD partner's back-to-back f32
 // MFMAs (which occupy the vector issue port): the preparing wave is the critical path, so it gets the higher priority.
-#ifndef LASS_PRIO
-#define LASS_PRIO 1
-#endif
-__device__ __forceinline__ void prep_prio() {
-#if LASS_PRIO
-    __builtin_amdgcn_s_setprio(2);
-#endif
-}
-__device__ __forceinline__ void mfma_prio() {
-#if LASS_PRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
-}
+__device__ __forceinline__ void prep_prio() { __builtin_amdgcn_s_setprio(2); }
+__device__ __forceinline__ void mfma_prio() { __builtin_amdgcn_s_setprio(0); }
 
 // Halo-tile staging: [KC][IR][IP] raw (activated) input, walked in channel pairs (see conv.hip Phase).
 template <int IR, int IP, int HALO, int KCH, bool PRO, bool PRE = false, int NTH = NTHREADS>
@@ -684,19 +673,16 @@ hipError_t launch_wino_v(const ConvArgs& p0, hipStream_t stream) {
 
 // The patch-staging schedule wins on the 16- / 8-bin layers (-9...-13 %: few, short tiles) and loses 3-7 % on the large
 // ones (its 16 instead of ~9 prologue evaluations per thread and chunk are VALU work next to f32 MFMAs), so it is the
-// default below W = 32 only; LASS_WINO_PATCH=0/1 forces it off / on everywhere (A/B switch).
+// default below W = 32 only.
 template <int FLAGS>
 hipError_t launch_wino(const ConvArgs& p, hipStream_t stream) {
-    static const int force = [] { const char* e = getenv("LASS_WINO_PATCH"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }();
-    const bool patch = force >= 0 ? force == 1 : p.W < 32;
-    return patch ? launch_wino_v<FLAGS, true>(p, stream) : launch_wino_v<FLAGS, false>(p, stream);
+    return p.W < 32 ? launch_wino_v<FLAGS, true>(p, stream) : launch_wino_v<FLAGS, false>(p, stream);
 }
 
 }  // namespace
 
 bool lass_wino_supported(const ConvArgs& p) {
-    static const bool small_ok = [] { const char* e = getenv("LASS_WINO_SMALL"); return !e || atoi(e) != 0; }();
-    const bool w_ok = (p.W >= 32 && (p.W % 32) == 0) || (small_ok && (p.W == 16 || p.W == 8) && p.N % 64 == 0);
+    const bool w_ok = (p.W >= 32 && (p.W % 32) == 0) || ((p.W == 16 || p.W == 8) && p.N % 64 == 0);
     return w_ok && (p.H % 2) == 0 && p.Cin % (2 * KC) == 0 && p.N % 32 == 0 && (p.Nw % 32) == 0;
 }
 

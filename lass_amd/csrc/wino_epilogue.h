@@ -1,4 +1,4 @@
-// wino_epilogue.h - output transform Y = A^T M A and the fused epilogue of the Winograd kernels (wino.hip, wino32.hip):
+// wino_epilogue.h - output transform Y = A^T M A and the fused epilogue of the Winograd kernels (wino.hip):
 // bias / residual / epilogue activation / 2x2 (or 1x2) avg-pool / output head (after_conv + complex ratio mask).
 // A wave holds 32 couts x 16 tiles with all 16 xi accumulators: acc[xi][t][r] = M_xi[cout = t*16 + kq*4 + r][tile = l15]
 // (kq = lane >> 4, l15 = lane & 15), so everything below is register-local.

@@ -1,6 +1,6 @@
 # A/B of two builds of the library on the same box: per-kernel average durations of the f32 bench, alternating A B A B.
 # usage: bash tools/gpu_ab.sh TAG libA.so libB.so [kernel-name regex]
-TAG=$1; A=$2; B=$3; PAT=${4:-wino32}
+TAG=$1; A=$2; B=$3; PAT=${4:-wino4_kernel}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 for i in 1 2; do for L in A B; do
@@ -15,5 +15,5 @@ for tag in ("A1", "B1", "A2", "B2"):
     rows = [r for r in csv.DictReader(open(f)) if re.search("$PAT", r["Name"])]
     rows.sort(key=lambda r: r["Name"])
     v = json.load(open("$O/bench_%s.json" % tag))
-    print(tag, "clips/s %.1f" % v["value"], "conv_ms %.2f" % v["roofline"]["class_ms_per_step"], " | ".join("%s %.1f" % (re.sub(r".*wino32_kernel<([^>]*)>.*", r"\1", r["Name"])[:14], float(r["AverageNs"]) / 1e3) for r in rows))
+    print(tag, "clips/s %.1f" % v["value"], "conv_ms %.2f" % v["roofline"]["class_ms_per_step"], " | ".join("%s %.1f" % (re.sub(r".*_kernel<([^>]*)>.*", r"\1", r["Name"])[:14], float(r["AverageNs"]) / 1e3) for r in rows))
 PY

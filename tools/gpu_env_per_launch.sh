@@ -1,6 +1,7 @@
 # Per-launch durations of the last step under two values of an environment switch, side by side (rocprofv3 --kernel-trace, LASS_SPLIT=0).
 # usage: bash tools/gpu_env_per_launch.sh VAR VALUE_A VALUE_B [bench args, default: f32 headline]
-VAR=${1:-LASS_WINO4_NG}; VA=${2:-1}; VB=${3:-2}; shift 3 2>/dev/null
+[ $# -ge 3 ] || { echo "usage: $0 VAR VALUE_A VALUE_B [bench args]" >&2; exit 2; }
+VAR=$1; VA=$2; VB=$3; shift 3
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r5u; rm -rf $O; mkdir -p $O
 for V in 1 2; do

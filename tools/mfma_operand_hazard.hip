@@ -3,8 +3,8 @@
 //     hipcc -O3 --offload-arch=gfx950 -S --cuda-device-only tools/mfma_operand_hazard.hip -o - | grep -B4 v_mfma
 // k_ab: v_mul (A) / v_add (B), s_waitcnt, s_nop 0, v_mfma   - two wait states behind the writer of an A / B operand;
 // k_c:  v_pk_mul (SrcC), s_waitcnt, s_nop 0, v_mfma         - the same behind a writer of the accumulator input.
-// An `asm volatile` MFMA gets no such padding (cdna_hip_programming.md 5.7 item 2): wino32.hip's statements therefore open with
-// `s_nop 1`, and tools/audit_wino32_isa.py checks the two wait states in the shipped ISA (tests/test_host_cpu.py).
+// An `asm volatile` MFMA gets no such padding: the retired wino32.hip opened its MFMA statements with `s_nop 1` for that
+// reason.  The library's MFMAs are builtins now.
 #include <hip/hip_runtime.h>
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 __global__ void k_ab(float* o, float x, float y) {

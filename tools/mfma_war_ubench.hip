@@ -1,6 +1,6 @@
 // Write-after-read on the operands of hand-issued MFMAs (inline asm: hipcc's hazard handling does not see them).
 // NM v_mfma_f32_16x16x4_f32 back to back on operand register b (or a), then NOPS wait states, then `v_mov b, junk`;
-// the reference never touches b.  Prints how many lanes differ.  Measured on MI355X: see wino32.hip.
+// the reference never touches b.  Prints how many lanes differ.  Measured on MI355X: profiles/r03/ubench/.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>

@@ -1,5 +1,5 @@
 // Micro-benchmark: cost of packed-f32 vector instructions (v_pk_add_f32 / v_pk_fma_f32 / v_pk_mul_f32) next to
-// v_mfma_f32_16x16x4_f32, in the shape wino32.hip runs: 32 MFMAs back to back, then a burst of NV vector instructions,
+// v_mfma_f32_16x16x4_f32, in the shape the retired wino32.hip ran: 32 MFMAs back to back, then a burst of NV vector instructions,
 // two waves per SIMD.  hipcc --offload-arch=gfx950 -O3 tools/pk_valu_ubench.hip -o tools/bin/pk_ubench
 #include <hip/hip_runtime.h>
 #include <cstdio>
