@@ -251,6 +251,42 @@ int lass_mix_at_snr(lass_ctx* ctx, float* source, const float* noise, const floa
 int lass_segment_mix(lass_ctx* ctx, const float* waveforms, int B, int L, const int* mix_num, const float* comp_db, int max_comp,
                      const float* noise_db, float* mixture, float* segment, double* scratch, void* stream);
 
+/* ---- CLAP text encoder (query embeddings) ----------------------------------------------------------------------- */
+
+/* The text tower of the query encoder: caption token ids -> (N,512) L2-normalised float32 embeddings.
+ * Replaces: CLAP_Encoder.get_query_embed(modality="text") (models/clap_encoder.py:78-116) = CLAP.get_text_embedding ->
+ * encode_text for text_branch_type "roberta" (CLAP/open_clip/model.py:516-531, 658-665, 732-751): RoBERTa-base
+ * (hidden 768, 12 heads, FFN 3072, post-LN, LayerNorm eps 1e-5, exact-erf GELU, pad id 1), pooler tanh(Wp h[:,0] + bp),
+ * Linear(768,512) -> ReLU -> Linear(512,512), F.normalize.  f32 throughout, contractions on the f32 MFMA.
+ * A separate handle: the separator's lass_ctx is untouched.  Same conventions (return codes, caller's stream, no CPU
+ * fallback: without a gfx950 device lass_text_create fails). */
+typedef struct lass_text_ctx lass_text_ctx;
+
+int lass_text_create(lass_text_ctx** out, int device_id);
+int lass_text_destroy(lass_text_ctx* ctx);
+/* Last error of this context (or of the failed lass_text_create when ctx == NULL).  Never NULL. */
+const char* lass_text_last_error(const lass_text_ctx* ctx);
+/* Upload one f32 tensor (host or device pointer), key relative to the CLAP model: "text_branch.embeddings.*",
+ * "text_branch.encoder.layer.<i>.*", "text_branch.pooler.dense.*", "text_projection.{0,2}.*" - the checkpoint's
+ * `query_encoder.model.<key>`.  Shapes are checked; any other key is LASS_ERR_ARG.  Vocabulary and position-table
+ * sizes are taken from the tensors, the layer count from the layer indices present. */
+int lass_text_set_param(lass_text_ctx* ctx, const char* name, const void* data, const int64_t* shape, int ndim);
+/* Checks that every parameter of layers 0 .. L-1 and of the embeddings / pooler / projection is present, fuses each
+ * layer's query/key/value weights into one (2304,768) matrix.  Must be called again after any lass_text_set_param. */
+int lass_text_finalize(lass_text_ctx* ctx);
+/* Encoder layers of a finalized context (0 before lass_text_finalize). */
+int lass_text_layers(const lass_text_ctx* ctx);
+/* Workspace bytes lass_text_encode needs for N captions padded to S tokens (1 <= S <= 512). */
+int lass_text_workspace_bytes(const lass_text_ctx* ctx, int N, int S, size_t* bytes);
+/* input_ids (N,S) int64 DEVICE pointer, attention_mask (N,S) int64 HOST pointer (it decides which rows are computed and
+ * sizes every launch, so no device-to-host read is needed) -> out (N,512) f32, and pooler_output (N,768) f32 into
+ * `pooler_out` unless NULL.  Only positions with attention_mask != 0 are computed (a packed batch of sum-of-lengths
+ * rows); position ids still count over the whole id row, so the result equals the padded computation.  attention_mask[:,0]
+ * must be nonzero for every caption.  Ids must lie in [0, vocab) - the caller checks; out-of-range ids are clamped.
+ * The mask is staged in pinned memory: a call waits for the previous call's (small) upload before it rewrites it. */
+int lass_text_encode(lass_text_ctx* ctx, const int64_t* input_ids, const int64_t* attention_mask, int N, int S,
+                     float* out, float* pooler_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- instrumentation ---------------------------------------------------------------------------------------- */
 
 /* When enabled, lass_separate brackets each kernel class with HIP events on `stream` (costs a few us per launch).

@@ -51,6 +51,15 @@ SYMBOLS = [
     ("lass_mask_apply", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                 c_void_p, c_void_p]),
     ("lass_sdr_stats", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    ("lass_text_create", c_int, [POINTER(c_void_p), c_int]),
+    ("lass_text_destroy", c_int, [c_void_p]),
+    ("lass_text_last_error", c_char_p, [c_void_p]),
+    ("lass_text_set_param", c_int, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int]),
+    ("lass_text_finalize", c_int, [c_void_p]),
+    ("lass_text_layers", c_int, [c_void_p]),
+    ("lass_text_workspace_bytes", c_int, [c_void_p, c_int, c_int, POINTER(c_size_t)]),
+    ("lass_text_encode", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                 c_void_p]),
     ("lass_set_profiling", c_int, [c_void_p, c_int]),
     ("lass_profile_count", c_int, [c_void_p]),
     ("lass_profile_get", c_int, [c_void_p, c_int, POINTER(c_char_p), POINTER(c_double), POINTER(c_int)]),

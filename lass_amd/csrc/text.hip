@@ -1,0 +1,614 @@
+// text.hip - the CLAP text tower on the device: RoBERTa-base encoder + pooler + text projection + L2 normalisation
+// (CLAP/open_clip/model.py:516-531, 658-665, 732-751 for text_branch_type "roberta"), behind its own lass_text_ctx.
+//
+// Every launch works on a PACKED token matrix: the M = sum of real tokens rows of all captions (attention_mask != 0),
+// caption n owning rows [cap_off[n], cap_off[n+1]).  Dropping the masked positions is exact: position ids are computed
+// from the full id row (HF create_position_ids_from_input_ids) and a masked key has weight exactly zero in the reference
+// softmax, so no real row ever depends on a padded one.  No work is spent on padding.
+//
+// Batch invariance: every kernel computes a row (a token, or a caption in the head) from that row's inputs alone in a
+// fixed order - the GEMM tile is one shape for all M and each output element is a k-ordered chain of f32 MFMA FMAs,
+// reductions are per row, attention is per (caption, head, query) - so a caption's embedding is bit-identical whatever
+// batch, padding length or packed position it comes with.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../../include/lass_hip.h"
+
+namespace {
+
+constexpr int kHid = 768, kHeads = 12, kDh = 64, kFF = 3072, kProj = 512, kMaxLen = 512, kPad = 1;
+constexpr float kLnEps = 1e-5f;  // roberta-base config.json layer_norm_eps (HF RobertaConfig() defaults to 1e-12)
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+__device__ __forceinline__ float wave_sum(float v) {
+    // xor butterfly: every lane ends with the same bits
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+__device__ __forceinline__ int wave_isum(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// LayerNorm of one 768-wide row held as 12 values per lane (element lane + 64 j), written to y.
+__device__ __forceinline__ void ln_row(float (&x)[12], const float* __restrict__ g, const float* __restrict__ b,
+                                       float* __restrict__ y, int lane) {
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 12; ++j) s += x[j];
+    const float mean = wave_sum(s) * (1.0f / kHid);
+    float q = 0.f;
+#pragma unroll
+    for (int j = 0; j < 12; ++j) {
+        const float d = x[j] - mean;
+        q += d * d;
+    }
+    const float rstd = 1.0f / sqrtf(wave_sum(q) * (1.0f / kHid) + kLnEps);
+#pragma unroll
+    for (int j = 0; j < 12; ++j) {
+        const int k = lane + 64 * j;
+        y[k] = (x[j] - mean) * rstd * g[k] + b[k];
+    }
+}
+
+// Embeddings (RobertaEmbeddings.forward): word[id] + token_type[0] + position[pos], then LayerNorm.  One wave per packed
+// row; pos = (id != pad) ? #{c <= s : ids[n][c] != pad} + 1 : pad, counted over the caller's full id row.
+__global__ __launch_bounds__(256) void k_embed_ln(const int64_t* __restrict__ ids, int S, const int* __restrict__ src, int M,
+                                                  const float* __restrict__ we, int vocab, const float* __restrict__ pe,
+                                                  int npos, const float* __restrict__ te, const float* __restrict__ g,
+                                                  const float* __restrict__ b, float* __restrict__ h) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= M) return;
+    const int n = src[r] / S, s = src[r] % S;
+    const int64_t* row = ids + (size_t)n * S;
+    int cnt = 0;
+    for (int c = lane; c <= s; c += 64) cnt += row[c] != kPad;
+    cnt = wave_isum(cnt);
+    const int64_t id64 = row[s];
+    // ids are range-checked by the host (ClapTextEncoder.encode_ids); the clamps only keep a bad id from reading outside
+    const int id = (int)(id64 < 0 ? 0 : (id64 >= vocab ? vocab - 1 : id64));
+    int pos = id64 != kPad ? cnt + 1 : kPad;
+    pos = pos < npos ? pos : npos - 1;
+    float x[12];
+#pragma unroll
+    for (int j = 0; j < 12; ++j) {
+        const int k = lane + 64 * j;
+        x[j] = (we[(size_t)id * kHid + k] + te[k]) + pe[(size_t)pos * kHid + k];
+    }
+    ln_row(x, g, b, h + (size_t)r * kHid, lane);
+}
+
+// In-place LayerNorm of M rows of 768 (the residual sum was added by the GEMM epilogue).
+__global__ __launch_bounds__(256) void k_ln(float* __restrict__ h, int M, const float* __restrict__ g,
+                                            const float* __restrict__ b) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= M) return;
+    float* row = h + (size_t)r * kHid;
+    float x[12];
+#pragma unroll
+    for (int j = 0; j < 12; ++j) x[j] = row[lane + 64 * j];
+    ln_row(x, g, b, row, lane);
+}
+
+enum Epi { EPI_BIAS = 0, EPI_GELU = 1, EPI_RESID = 2, EPI_TANH = 3, EPI_RELU = 4 };
+
+constexpr int BM = 64, BN = 64, BK = 16, LDT = BM + 32;  // +32: the two k rows one MFMA reads land in different banks
+
+// Y[M,N] = epi(X[M,K] . W[N,K]^T + bias), row-major, N % 64 == 0, K % 16 == 0.  EPI_RESID adds Y's previous value
+// (the residual stream, updated in place: each element is read and written by the same lane).  256 threads = 4 waves,
+// each a 32x32 quarter of the 64x64 tile on v_mfma_f32_32x32x2_f32 (exact f32, k-ordered FMA chain).  One tile shape for
+// every M, so a row's result does not depend on M or on where the row sits.
+template <int EPI>
+__global__ __launch_bounds__(256) void k_gemm(const float* __restrict__ X, const float* __restrict__ W,
+                                              const float* __restrict__ bias, float* Y, int M, int N, int K) {
+    __shared__ __attribute__((aligned(16))) float As[BK * LDT], Bs[BK * LDT];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int wm = w & 1, wn = w >> 1;
+    const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
+    const int lr = t >> 2, lc = (t & 3) * 4;  // this thread's staging row and k quad
+    const bool xrow = m0 + lr < M;
+    const float* xp = X + (size_t)(xrow ? m0 + lr : 0) * K + lc;
+    const float* wp = W + (size_t)(n0 + lr) * K + lc;
+    float4 ra = xrow ? *(const float4*)xp : make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 rb = *(const float4*)wp;
+    f32x16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    const int ai = wm * 32 + (lane & 31), bi = wn * 32 + (lane & 31), kh = lane >> 5;
+    for (int k0 = 0; k0 < K; k0 += BK) {
+        __syncthreads();
+        As[(lc + 0) * LDT + lr] = ra.x;
+        As[(lc + 1) * LDT + lr] = ra.y;
+        As[(lc + 2) * LDT + lr] = ra.z;
+        As[(lc + 3) * LDT + lr] = ra.w;
+        Bs[(lc + 0) * LDT + lr] = rb.x;
+        Bs[(lc + 1) * LDT + lr] = rb.y;
+        Bs[(lc + 2) * LDT + lr] = rb.z;
+        Bs[(lc + 3) * LDT + lr] = rb.w;
+        __syncthreads();
+        if (k0 + BK < K) {
+            ra = xrow ? *(const float4*)(xp + k0 + BK) : make_float4(0.f, 0.f, 0.f, 0.f);
+            rb = *(const float4*)(wp + k0 + BK);
+        }
+#pragma unroll
+        for (int kk = 0; kk < BK / 2; ++kk) {
+            const float a = As[(2 * kk + kh) * LDT + ai];
+            const float bb = Bs[(2 * kk + kh) * LDT + bi];
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bb, acc, 0, 0, 0);
+        }
+    }
+    const int n = n0 + wn * 32 + (lane & 31);
+    const float bn = bias[n];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int m = m0 + wm * 32 + (i & 3) + 8 * (i >> 2) + 4 * kh;
+        if (m >= M) continue;
+        float v = acc[i] + bn;
+        float* yp = Y + (size_t)m * N + n;
+        if (EPI == EPI_GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
+        if (EPI == EPI_RESID) v = v + *yp;
+        if (EPI == EPI_TANH) v = tanhf(v);
+        if (EPI == EPI_RELU) v = fmaxf(v, 0.f);
+        *yp = v;
+    }
+}
+
+constexpr int AQ = 64;  // queries per workgroup (one per lane) and keys per LDS block
+constexpr int AC = 16;  // keys per online-softmax step
+
+// Self-attention of one (query block, head, caption): softmax(q k^T / 8) v over the caption's real tokens only.  One wave;
+// lane = query.  K/V of the caption stream through LDS in blocks of 64 keys with an online softmax, so any length <= 512
+// fits.  qkv rows: [q | k | v], 768 each, head h at columns 64h.
+__global__ __launch_bounds__(64) void k_attn(const float* __restrict__ qkv, const int* __restrict__ cap_off,
+                                             float* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) float Ks[AQ * kDh], Vs[AQ * kDh];
+    const int lane = threadIdx.x, h = blockIdx.y, n = blockIdx.z;
+    const int off = cap_off[n], len = cap_off[n + 1] - off;
+    const int q0 = blockIdx.x * AQ;
+    if (q0 >= len) return;
+    const int qi = q0 + lane;
+    const bool live = qi < len;
+    float q[kDh], o[kDh];
+    const float* qp = qkv + (size_t)(off + (live ? qi : 0)) * (3 * kHid) + h * kDh;
+#pragma unroll
+    for (int d = 0; d < kDh; d += 4) {
+        const float4 v = *(const float4*)(qp + d);
+        q[d] = v.x; q[d + 1] = v.y; q[d + 2] = v.z; q[d + 3] = v.w;
+    }
+#pragma unroll
+    for (int d = 0; d < kDh; ++d) o[d] = 0.f;
+    float mrun = -INFINITY, lrun = 0.f;
+    for (int k0 = 0; k0 < len; k0 += AQ) {
+        const int nk = min(AQ, len - k0);
+        __syncthreads();
+        for (int j = 0; j < AQ; ++j) {  // coalesced: row j of K and V, element `lane`; rows past the caption are zero
+            const float* kp = qkv + (size_t)(off + k0 + j) * (3 * kHid) + kHid + h * kDh + lane;
+            Ks[j * kDh + lane] = j < nk ? kp[0] : 0.f;
+            Vs[j * kDh + lane] = j < nk ? kp[kHid] : 0.f;
+        }
+        __syncthreads();
+        for (int c0 = 0; c0 < nk; c0 += AC) {
+            float s[AC];
+            float cmax = -INFINITY;
+#pragma unroll
+            for (int j = 0; j < AC; ++j) {
+                const float* kr = Ks + (c0 + j) * kDh;
+                float dot = 0.f;
+#pragma unroll
+                for (int d = 0; d < kDh; d += 4) {
+                    const float4 kv = *(const float4*)(kr + d);
+                    dot = fmaf(q[d], kv.x, dot);
+                    dot = fmaf(q[d + 1], kv.y, dot);
+                    dot = fmaf(q[d + 2], kv.z, dot);
+                    dot = fmaf(q[d + 3], kv.w, dot);
+                }
+                s[j] = c0 + j < nk ? dot * 0.125f : -INFINITY;
+                cmax = fmaxf(cmax, s[j]);
+            }
+            const float mnew = fmaxf(mrun, cmax);
+            const float scale = expf(mrun - mnew);
+            float psum = 0.f;
+#pragma unroll
+            for (int j = 0; j < AC; ++j) {
+                s[j] = expf(s[j] - mnew);
+                psum += s[j];
+            }
+            lrun = lrun * scale + psum;
+#pragma unroll
+            for (int d = 0; d < kDh; ++d) o[d] *= scale;
+#pragma unroll
+            for (int j = 0; j < AC; ++j) {
+                const float* vr = Vs + (c0 + j) * kDh;
+#pragma unroll
+                for (int d = 0; d < kDh; d += 4) {
+                    const float4 vv = *(const float4*)(vr + d);
+                    o[d] = fmaf(s[j], vv.x, o[d]);
+                    o[d + 1] = fmaf(s[j], vv.y, o[d + 1]);
+                    o[d + 2] = fmaf(s[j], vv.z, o[d + 2]);
+                    o[d + 3] = fmaf(s[j], vv.w, o[d + 3]);
+                }
+            }
+            mrun = mnew;
+        }
+    }
+    if (!live) return;
+    const float inv = 1.0f / lrun;
+    float* op = out + (size_t)(off + qi) * kHid + h * kDh;
+#pragma unroll
+    for (int d = 0; d < kDh; d += 4) *(float4*)(op + d) = make_float4(o[d] * inv, o[d + 1] * inv, o[d + 2] * inv, o[d + 3] * inv);
+}
+
+// h[:, 0] of every caption (its first packed row: attention_mask[:, 0] == 1) -> cls (N, 768).
+__global__ __launch_bounds__(256) void k_gather_cls(const float* __restrict__ h, const int* __restrict__ cap_off, int N,
+                                                    float* __restrict__ cls) {
+    const int n = blockIdx.x;
+    if (n >= N) return;
+    const float* row = h + (size_t)cap_off[n] * kHid;
+    for (int k = threadIdx.x; k < kHid; k += 256) cls[(size_t)n * kHid + k] = row[k];
+}
+
+// F.normalize(x, dim=-1): x / max(||x||, 1e-12), one wave per row of 512.
+__global__ __launch_bounds__(256) void k_l2norm(const float* __restrict__ x, int N, float* __restrict__ y) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= N) return;
+    float v[kProj / 64], s = 0.f;
+#pragma unroll
+    for (int j = 0; j < kProj / 64; ++j) {
+        v[j] = x[(size_t)r * kProj + lane + 64 * j];
+        s += v[j] * v[j];
+    }
+    const float inv = 1.0f / fmaxf(sqrtf(wave_sum(s)), 1e-12f);
+#pragma unroll
+    for (int j = 0; j < kProj / 64; ++j) y[(size_t)r * kProj + lane + 64 * j] = v[j] * inv;
+}
+
+struct TRaw {
+    float* d = nullptr;
+    std::vector<int64_t> shape;
+};
+
+struct TLayer {
+    float *wqkv = nullptr, *bqkv = nullptr;  // fused (2304, 768) / (2304): query, key, value rows in that order
+    const float *wo, *bo, *g1, *b1, *wi, *bi, *w2, *b2, *g2, *b22;
+};
+
+// per-layer keys (HF RobertaLayer) and their shapes; 0 stands for "one dimension"
+struct LayerKey { const char* name; int d0, d1; };
+const LayerKey kLayerKeys[] = {
+    {"attention.self.query.weight", kHid, kHid},   {"attention.self.query.bias", kHid, 0},
+    {"attention.self.key.weight", kHid, kHid},     {"attention.self.key.bias", kHid, 0},
+    {"attention.self.value.weight", kHid, kHid},   {"attention.self.value.bias", kHid, 0},
+    {"attention.output.dense.weight", kHid, kHid}, {"attention.output.dense.bias", kHid, 0},
+    {"attention.output.LayerNorm.weight", kHid, 0}, {"attention.output.LayerNorm.bias", kHid, 0},
+    {"intermediate.dense.weight", kFF, kHid},      {"intermediate.dense.bias", kFF, 0},
+    {"output.dense.weight", kHid, kFF},            {"output.dense.bias", kHid, 0},
+    {"output.LayerNorm.weight", kHid, 0},          {"output.LayerNorm.bias", kHid, 0},
+};
+const LayerKey kFixedKeys[] = {
+    {"text_branch.embeddings.LayerNorm.weight", kHid, 0}, {"text_branch.embeddings.LayerNorm.bias", kHid, 0},
+    {"text_branch.pooler.dense.weight", kHid, kHid},      {"text_branch.pooler.dense.bias", kHid, 0},
+    {"text_projection.0.weight", kProj, kHid},            {"text_projection.0.bias", kProj, 0},
+    {"text_projection.2.weight", kProj, kProj},           {"text_projection.2.bias", kProj, 0},
+};
+const char* kLayerPrefix = "text_branch.encoder.layer.";
+
+thread_local std::string g_text_create_err;
+
+size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
+
+}  // namespace
+
+struct lass_text_ctx {
+    int device = 0;
+    std::string err;
+    std::map<std::string, TRaw> raw;
+    bool finalized = false;
+    int vocab = 0, npos = 0;
+    std::vector<TLayer> layers;
+    std::vector<void*> owned;  // fused QKV buffers
+    int* plan_host = nullptr;  // pinned staging of the packed-row plan
+    size_t plan_cap = 0;       // ints
+    hipEvent_t plan_ev = nullptr;
+    bool plan_pending = false;
+};
+
+namespace {
+
+#define TEXT_TRY(ctx, expr)                                                     \
+    do {                                                                        \
+        hipError_t _e = (expr);                                                 \
+        if (_e != hipSuccess) {                                                 \
+            (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(_e);     \
+            return LASS_ERR_HIP;                                                \
+        }                                                                       \
+    } while (0)
+
+int tfail(lass_text_ctx* c, int code, const std::string& msg) {
+    c->err = msg;
+    return code;
+}
+
+const float* tp(const lass_text_ctx* c, const std::string& k) {
+    auto it = c->raw.find(k);
+    return it == c->raw.end() ? nullptr : it->second.d;
+}
+
+// Expected shape of a key, or false if the name is not a text-tower parameter.  Vocabulary and position-table sizes
+// come from the tensors themselves; layer indices from the names.
+bool expected_shape(const std::string& name, const int64_t* shape, int ndim, std::string& why) {
+    auto want = [&](int d0, int d1) {
+        const int nd = d1 ? 2 : 1;
+        if (ndim != nd || shape[0] != d0 || (nd == 2 && shape[1] != d1)) {
+            why = name + ": expected shape (" + std::to_string(d0) + (d1 ? ", " + std::to_string(d1) : std::string(",")) + ")";
+            return false;
+        }
+        return true;
+    };
+    if (name == "text_branch.embeddings.word_embeddings.weight" || name == "text_branch.embeddings.position_embeddings.weight" ||
+        name == "text_branch.embeddings.token_type_embeddings.weight") {
+        if (ndim != 2 || shape[1] != kHid || shape[0] < 1) {
+            why = name + ": expected shape (rows, 768)";
+            return false;
+        }
+        return true;
+    }
+    for (const auto& k : kFixedKeys)
+        if (name == k.name) return want(k.d0, k.d1);
+    if (name.rfind(kLayerPrefix, 0) == 0) {
+        const std::string rest = name.substr(strlen(kLayerPrefix));
+        const size_t dot = rest.find('.');
+        if (dot != std::string::npos && dot > 0 && rest.find_first_not_of("0123456789") == dot) {
+            const std::string suffix = rest.substr(dot + 1);
+            for (const auto& k : kLayerKeys)
+                if (suffix == k.name) return want(k.d0, k.d1);
+        }
+    }
+    why = "unknown text-tower parameter '" + name + "'";
+    return false;
+}
+
+template <int EPI>
+void gemm(const float* X, const float* W, const float* b, float* Y, int M, int N, int K, hipStream_t st) {
+    hipLaunchKernelGGL(k_gemm<EPI>, dim3(N / BN, (M + BM - 1) / BM), dim3(256), 0, st, X, W, b, Y, M, N, K);
+}
+
+struct TPlan {  // workspace carve-up for (N, S): everything sized for M = N*S rows, the packed batch uses the first M_real
+    size_t src, cap, h, qkv, attn, ffn, cls, pool, p1, p2, total;
+};
+
+TPlan text_plan(int N, int S) {
+    const size_t M = (size_t)N * S;
+    TPlan p;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o += align256(bytes); return at; };
+    p.src = take(M * sizeof(int));
+    p.cap = take((N + 1) * sizeof(int));
+    p.h = take(M * kHid * sizeof(float));
+    p.qkv = take(M * 3 * kHid * sizeof(float));
+    p.attn = take(M * kHid * sizeof(float));
+    p.ffn = take(M * kFF * sizeof(float));
+    p.cls = take((size_t)N * kHid * sizeof(float));
+    p.pool = take((size_t)N * kHid * sizeof(float));
+    p.p1 = take((size_t)N * kProj * sizeof(float));
+    p.p2 = take((size_t)N * kProj * sizeof(float));
+    p.total = o;
+    return p;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lass_text_create(lass_text_ctx** out, int device_id) {
+    if (!out) return LASS_ERR_ARG;
+    *out = nullptr;
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0) {
+        g_text_create_err = std::string("no HIP device available: ") + hipGetErrorString(e) +
+                            " (liblass_hip has no CPU fallback)";
+        return LASS_ERR_HIP;
+    }
+    if (device_id < 0 || device_id >= ndev) {
+        g_text_create_err = "device_id out of range";
+        return LASS_ERR_ARG;
+    }
+    hipDeviceProp_t prop;
+    e = hipGetDeviceProperties(&prop, device_id);
+    if (e != hipSuccess) {
+        g_text_create_err = std::string("hipGetDeviceProperties: ") + hipGetErrorString(e);
+        return LASS_ERR_HIP;
+    }
+    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0) {
+        g_text_create_err = std::string("device is ") + prop.gcnArchName + "; liblass_hip is built for gfx950 only";
+        return LASS_ERR_HIP;
+    }
+    lass_text_ctx* c = new lass_text_ctx();
+    c->device = device_id;
+    if (hipSetDevice(device_id) != hipSuccess || hipEventCreateWithFlags(&c->plan_ev, hipEventDisableTiming) != hipSuccess) {
+        g_text_create_err = "hipSetDevice / hipEventCreate failed";
+        delete c;
+        return LASS_ERR_HIP;
+    }
+    *out = c;
+    return LASS_OK;
+}
+
+int lass_text_destroy(lass_text_ctx* c) {
+    if (!c) return LASS_OK;
+    (void)hipSetDevice(c->device);
+    (void)hipDeviceSynchronize();
+    for (auto& kv : c->raw) (void)hipFree(kv.second.d);
+    for (void* p : c->owned) (void)hipFree(p);
+    if (c->plan_host) (void)hipHostFree(c->plan_host);
+    if (c->plan_ev) (void)hipEventDestroy(c->plan_ev);
+    delete c;
+    return LASS_OK;
+}
+
+const char* lass_text_last_error(const lass_text_ctx* c) { return c ? c->err.c_str() : g_text_create_err.c_str(); }
+
+int lass_text_set_param(lass_text_ctx* c, const char* name, const void* data, const int64_t* shape, int ndim) {
+    if (!c) return LASS_ERR_ARG;
+    if (!name || !data || !shape || ndim < 1 || ndim > 2) return tfail(c, LASS_ERR_ARG, "lass_text_set_param: bad arguments");
+    std::string why;
+    if (!expected_shape(name, shape, ndim, why)) return tfail(c, LASS_ERR_ARG, why);
+    TEXT_TRY(c, hipSetDevice(c->device));
+    size_t n = 1;
+    for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
+    TRaw& r = c->raw[name];
+    if (r.d && r.shape != std::vector<int64_t>(shape, shape + ndim)) {
+        (void)hipFree(r.d);
+        r.d = nullptr;
+    }
+    if (!r.d) TEXT_TRY(c, hipMalloc(&r.d, n * sizeof(float)));
+    r.shape.assign(shape, shape + ndim);
+    TEXT_TRY(c, hipMemcpy(r.d, data, n * sizeof(float), hipMemcpyDefault));
+    c->finalized = false;
+    return LASS_OK;
+}
+
+int lass_text_finalize(lass_text_ctx* c) {
+    if (!c) return LASS_ERR_ARG;
+    TEXT_TRY(c, hipSetDevice(c->device));
+    TEXT_TRY(c, hipDeviceSynchronize());
+    for (void* p : c->owned) (void)hipFree(p);
+    c->owned.clear();
+    c->layers.clear();
+    c->finalized = false;
+    for (const char* k : {"text_branch.embeddings.word_embeddings.weight", "text_branch.embeddings.position_embeddings.weight",
+                          "text_branch.embeddings.token_type_embeddings.weight"})
+        if (!tp(c, k)) return tfail(c, LASS_ERR_STATE, std::string("missing parameter ") + k);
+    for (const auto& k : kFixedKeys)
+        if (!tp(c, k.name)) return tfail(c, LASS_ERR_STATE, std::string("missing parameter ") + k.name);
+    c->vocab = (int)c->raw["text_branch.embeddings.word_embeddings.weight"].shape[0];
+    c->npos = (int)c->raw["text_branch.embeddings.position_embeddings.weight"].shape[0];
+    if (c->npos < 3) return tfail(c, LASS_ERR_ARG, "position_embeddings needs at least 3 rows");
+    // layer count = number of distinct layer indices; they must be 0 .. L-1, each complete
+    int nl = 0;
+    for (const auto& kv : c->raw)
+        if (kv.first.rfind(kLayerPrefix, 0) == 0) nl = std::max(nl, atoi(kv.first.c_str() + strlen(kLayerPrefix)) + 1);
+    if (nl < 1) return tfail(c, LASS_ERR_STATE, "no encoder layer parameters (text_branch.encoder.layer.<i>.*)");
+    for (int l = 0; l < nl; ++l) {
+        const std::string pre = kLayerPrefix + std::to_string(l) + ".";
+        const float* p[16];
+        for (int i = 0; i < 16; ++i) {
+            p[i] = tp(c, pre + kLayerKeys[i].name);
+            if (!p[i]) return tfail(c, LASS_ERR_STATE, "missing parameter " + pre + kLayerKeys[i].name);
+        }
+        TLayer L;
+        TEXT_TRY(c, hipMalloc(&L.wqkv, (size_t)3 * kHid * kHid * sizeof(float)));
+        c->owned.push_back(L.wqkv);
+        TEXT_TRY(c, hipMalloc(&L.bqkv, (size_t)3 * kHid * sizeof(float)));
+        c->owned.push_back(L.bqkv);
+        for (int j = 0; j < 3; ++j) {
+            TEXT_TRY(c, hipMemcpy(L.wqkv + (size_t)j * kHid * kHid, p[2 * j], (size_t)kHid * kHid * sizeof(float),
+                                  hipMemcpyDeviceToDevice));
+            TEXT_TRY(c, hipMemcpy(L.bqkv + j * kHid, p[2 * j + 1], kHid * sizeof(float), hipMemcpyDeviceToDevice));
+        }
+        L.wo = p[6]; L.bo = p[7]; L.g1 = p[8]; L.b1 = p[9];
+        L.wi = p[10]; L.bi = p[11]; L.w2 = p[12]; L.b2 = p[13]; L.g2 = p[14]; L.b22 = p[15];
+        c->layers.push_back(L);
+    }
+    c->finalized = true;
+    return LASS_OK;
+}
+
+int lass_text_layers(const lass_text_ctx* c) { return c && c->finalized ? (int)c->layers.size() : 0; }
+
+int lass_text_workspace_bytes(const lass_text_ctx* c, int N, int S, size_t* bytes) {
+    if (!c || !bytes || N < 1 || S < 1 || S > kMaxLen) return LASS_ERR_ARG;
+    *bytes = text_plan(N, S).total;
+    return LASS_OK;
+}
+
+int lass_text_encode(lass_text_ctx* c, const int64_t* input_ids, const int64_t* attention_mask, int N, int S, float* out,
+                     float* pooler_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!c) return LASS_ERR_ARG;
+    if (!c->finalized) return tfail(c, LASS_ERR_STATE, "lass_text_finalize has not been called (or a parameter changed since)");
+    if (!input_ids || !attention_mask || !out || !workspace || N < 1 || S < 1 || S > kMaxLen)
+        return tfail(c, LASS_ERR_ARG, "lass_text_encode: bad arguments (N >= 1, 1 <= S <= 512, non-NULL buffers)");
+    if (S + 1 >= c->npos) return tfail(c, LASS_ERR_ARG, "S too long for the position table (needs S + 2 rows)");
+    const TPlan P = text_plan(N, S);
+    if (workspace_bytes < P.total) return tfail(c, LASS_ERR_ARG, "workspace too small (lass_text_workspace_bytes)");
+    TEXT_TRY(c, hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    // packed-row plan from the host mask: src[r] = n*S + s for every real token, cap_off[n] = first row of caption n
+    const size_t need = (size_t)N * S + N + 1;
+    if (c->plan_pending) TEXT_TRY(c, hipEventSynchronize(c->plan_ev));  // the previous call's upload has read the staging
+    c->plan_pending = false;
+    if (need > c->plan_cap) {
+        if (c->plan_host) (void)hipHostFree(c->plan_host);
+        c->plan_host = nullptr;
+        TEXT_TRY(c, hipHostMalloc((void**)&c->plan_host, need * sizeof(int), hipHostMallocDefault));
+        c->plan_cap = need;
+    }
+    int* src = c->plan_host;
+    int* cap = c->plan_host + (size_t)N * S;
+    int M = 0, maxlen = 0;
+    for (int n = 0; n < N; ++n) {
+        cap[n] = M;
+        if (attention_mask[(size_t)n * S] == 0)
+            return tfail(c, LASS_ERR_ARG, "attention_mask[:, 0] must be 1 (the <s> token of every caption is real)");
+        for (int s = 0; s < S; ++s)
+            if (attention_mask[(size_t)n * S + s] != 0) src[M++] = n * S + s;
+        maxlen = std::max(maxlen, M - cap[n]);
+    }
+    cap[N] = M;
+    char* ws = (char*)workspace;
+    int* d_src = (int*)(ws + P.src);
+    int* d_cap = (int*)(ws + P.cap);
+    TEXT_TRY(c, hipMemcpyAsync(d_src, src, (size_t)M * sizeof(int), hipMemcpyHostToDevice, st));
+    TEXT_TRY(c, hipMemcpyAsync(d_cap, cap, (N + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+    TEXT_TRY(c, hipEventRecord(c->plan_ev, st));
+    c->plan_pending = true;
+
+    float* h = (float*)(ws + P.h);
+    float* qkv = (float*)(ws + P.qkv);
+    float* attn = (float*)(ws + P.attn);
+    float* ffn = (float*)(ws + P.ffn);
+    const dim3 rows4((M + 3) / 4);
+    hipLaunchKernelGGL(k_embed_ln, rows4, dim3(256), 0, st, input_ids, S, d_src, M,
+                       tp(c, "text_branch.embeddings.word_embeddings.weight"), c->vocab,
+                       tp(c, "text_branch.embeddings.position_embeddings.weight"), c->npos,
+                       tp(c, "text_branch.embeddings.token_type_embeddings.weight"),
+                       tp(c, "text_branch.embeddings.LayerNorm.weight"), tp(c, "text_branch.embeddings.LayerNorm.bias"), h);
+    for (const TLayer& L : c->layers) {
+        gemm<EPI_BIAS>(h, L.wqkv, L.bqkv, qkv, M, 3 * kHid, kHid, st);
+        hipLaunchKernelGGL(k_attn, dim3((maxlen + AQ - 1) / AQ, kHeads, N), dim3(AQ), 0, st, qkv, d_cap, attn);
+        gemm<EPI_RESID>(attn, L.wo, L.bo, h, M, kHid, kHid, st);
+        hipLaunchKernelGGL(k_ln, rows4, dim3(256), 0, st, h, M, L.g1, L.b1);
+        gemm<EPI_GELU>(h, L.wi, L.bi, ffn, M, kFF, kHid, st);
+        gemm<EPI_RESID>(ffn, L.w2, L.b2, h, M, kHid, kFF, st);
+        hipLaunchKernelGGL(k_ln, rows4, dim3(256), 0, st, h, M, L.g2, L.b22);
+    }
+    float* cls = (float*)(ws + P.cls);
+    float* pool = pooler_out ? pooler_out : (float*)(ws + P.pool);
+    float* p1 = (float*)(ws + P.p1);
+    float* p2 = (float*)(ws + P.p2);
+    hipLaunchKernelGGL(k_gather_cls, dim3(N), dim3(256), 0, st, h, d_cap, N, cls);
+    gemm<EPI_TANH>(cls, tp(c, "text_branch.pooler.dense.weight"), tp(c, "text_branch.pooler.dense.bias"), pool, N, kHid, kHid, st);
+    gemm<EPI_RELU>(pool, tp(c, "text_projection.0.weight"), tp(c, "text_projection.0.bias"), p1, N, kProj, kHid, st);
+    gemm<EPI_BIAS>(p1, tp(c, "text_projection.2.weight"), tp(c, "text_projection.2.bias"), p2, N, kProj, kProj, st);
+    hipLaunchKernelGGL(k_l2norm, dim3((N + 3) / 4), dim3(256), 0, st, p2, N, out);
+    TEXT_TRY(c, hipGetLastError());
+    return LASS_OK;
+}
+
+}  // extern "C"

@@ -142,3 +142,18 @@ def write_validation_set(root: str, n_clips: int = 8, length: int = 160000, sr: 
     with open(csv_path, "w") as f:
         f.write("\n".join(rows) + "\n")
     return csv_path
+
+
+def make_clap_text_state_dict(seed: int = SEED + 8, layers: int = 12) -> Dict[str, np.ndarray]:
+    """Seeded weights of the CLAP text tower (RoBERTa-base + projection), keyed as lass_amd.clap_text.ClapTextEncoder's
+    state_dict (`model.text_branch.*`, `model.text_projection.{0,2}.*`): float32 from numpy PCG64, matrices and biases
+    N(0, 0.02), LayerNorm weights 1 + N(0, 0.1), LayerNorm biases N(0, 0.02).  Drawn tensor by tensor in the module's key
+    order, so every machine regenerates the same values."""
+    from .clap_text import param_specs
+
+    rng = np.random.Generator(np.random.PCG64(seed))
+    sd: Dict[str, np.ndarray] = {}
+    for name, shape, kind in param_specs(layers):
+        v = rng.standard_normal(shape, dtype=np.float32)
+        sd[name] = (1.0 + 0.1 * v if kind == "g" else 0.02 * v).astype(np.float32)
+    return sd

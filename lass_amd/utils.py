@@ -60,3 +60,14 @@ def load_ss_model(configs: Dict, checkpoint_path: str, query_encoder: nn.Module)
     ss_model.load_state_dict(ss_state_dict_from_checkpoint(checkpoint_path), strict=False)
     return AudioSep(ss_model=ss_model, waveform_mixer=None, query_encoder=query_encoder, loss_function=None,
                     optimizer_type=None, learning_rate=None, lr_lambda_func=None)
+
+
+def load_query_encoder(checkpoint_path: str, tokenizer=None, tokenizer_dir: str = None) -> nn.Module:
+    """The checkpoint's CLAP text tower as a query encoder (lass_amd.clap_text.ClapTextEncoder, HIP kernels) - the opt-in
+    replacement of the default PrecomputedQueryEncoder:
+        eval(evaluator, ckpt, query_encoder=load_query_encoder(ckpt, tokenizer_dir=<roberta-base vocab.json + merges.txt>))
+    Captions are tokenized by `tokenizer` (a callable with the transformers tokenizer signature) or by a
+    RobertaTokenizer built from `tokenizer_dir`.  It moves to the device together with the separator."""
+    from .clap_text import ClapTextEncoder
+
+    return ClapTextEncoder.from_checkpoint(checkpoint_path, tokenizer=tokenizer, tokenizer_dir=tokenizer_dir)
