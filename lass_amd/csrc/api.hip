@@ -52,7 +52,7 @@ struct ResBlock {  // one ConvBlockRes
     int width = 0;         // bins of the level the block runs at (fcrop >> level): known at finalize, the frame count is not
     int s1 = -1, s2 = -1;  // site indices
     float *w1 = nullptr, *w2 = nullptr, *wsc = nullptr;  // re-laid-out
-    float *u1 = nullptr, *u2 = nullptr, *usc = nullptr;  // Winograd-domain copies (when enabled)
+    float *u1 = nullptr, *u2 = nullptr, *usc = nullptr;  // Winograd-domain copies (f32 mode)
     float *u1f = nullptr, *u2f = nullptr;                   // conv1 / conv2 in the F(4x4,3x3) domain (wino4.hip), deep-K blocks
     void *b1 = nullptr, *b2 = nullptr, *bsc16 = nullptr;  // bf16 copies (LASS_COMPUTE_BF16 / _BF16X3)
     void *b1l = nullptr, *b2l = nullptr, *bscl = nullptr;  // lo halves of the hi+lo split (LASS_COMPUTE_BF16X3)
@@ -105,16 +105,12 @@ struct lass_ctx {
     std::vector<void*> owned;        // derived device buffers to free
     // profiling
     int compute_mode = LASS_COMPUTE_F32;
-    bool wino = true;          // Winograd F(2x2,3x3) kernels for the 3x3 convs at W >= 32 (LASS_WINO=0: direct only)
     int wino4_mincin = 32;     // 3x3 convs with at least that many input channels (and >= 32-wide images) run as Winograd
                                // F(4x4,3x3) (wino4.hip); LASS_WINO4=<min Cin>, 0 = off (F(2x2,3x3) everywhere)
-    bool fuse_preconv = true;  // LASS_FUSE_PRECONV=0 materialises pre_conv's output with its own kernel
-    bool fuse_pool = true;  // LASS_FUSE_POOL=0 selects the stand-alone pool kernel (A/B + parity of both paths)
     bool fuse_catb = true;  // bf16 mode: decoder concats as blocked bf16 copies (LASS_FUSE_CATB=0: f32 concat)
     bool fuse_block = true;  // bf16 mode: encoder_block1 as one kernel, intermediate in LDS (LASS_FUSE_BLOCK=0: two launches)
     bool fuse_up = true;    // bf16 mode: decoder_block6's transposed conv inside its fused kernel (LASS_FUSE_UP=0: its own launch)
     void* up_sc16 = nullptr;  // ... the 1x1 shortcut composed with that transposed conv, bf16 [4][2][128] units (lass_finalize)
-    bool fuse_mask = true;  // LASS_FUSE_MASK=0 keeps after_conv + mask as their own kernel behind decoder_block6
     // hipGraph replay of lass_separate (LASS_GRAPH=0 disables): the ~40 launches of one (pointers, shape) combination are
     // captured once on an internal stream and replayed on the caller's stream
     bool use_graph = true;
@@ -392,8 +388,6 @@ void prof_collect(lass_ctx* c) {
 
 // ---- one residual block ---------------------------------------------------------------------------------------------
 // x: (B,cin,H,W) batch stride x_bs; out: batch stride out_bs (may be a channel slice of a concat buffer).
-// pool_out (optional): the block's avg-pooled output (B,cout,H/pool_h,W/2), produced by conv2's epilogue.
-// x0 (optional, encoder_block1 only): the block input is pre_conv(x0) and is formed on the fly - x is then ignored.
 // bf16 mode: a decoder's concat input (transposed-conv output | encoder skip) kept as two blocked bf16 copies in the
 // concat buffer's storage - `act` (consumer prologue applied) for conv1, `raw` for the 1x1 shortcut (ConvArgs::out_bf16_act)
 struct CatCopies {
@@ -430,11 +424,25 @@ struct UpFuse {
     const void* wsc16;   // shortcut (up-sampled half) composed with the transposed conv, bf16
 };
 
+// What lass_separate fuses into one block beyond the plain ConvBlockRes; a default-constructed value fuses nothing.
+struct BlockFusions {
+    float* pool_out = nullptr;              // the block's avg-pooled output (B,cout,H/pool_h,W/2), from conv2's epilogue
+    int pool_h = 2;
+    long pool_bs = 0;                       // pool_out's batch stride (0: dense)
+    int cofs = 0;                           // this branch's channel offset inside the concatenated skip / pool
+    const PreConv* pre = nullptr;           // encoder_block1: the input is pre_conv(x0), formed on the fly - x is ignored
+    const MaskHead* head = nullptr;         // decoder_block6: after_conv + mask in conv2's epilogue, `out` is not written
+    const CatCopies* skip_out = nullptr;    // bf16: the skip output as the decoder concat's two blocked copies
+    const CatCopies* cat_in = nullptr;      // bf16: the concat input as two blocked copies
+    const Site* act_out = nullptr;          // bf16: the output as ONE blocked tensor with this site's prologue applied
+    const CatCopies* pool_copies = nullptr; // bf16: the pooled output as two blocked copies for the next encoder block
+    const UpFuse* up = nullptr;             // bf16, decoder_block6: its transposed conv inside the block's fused kernel
+};
+
 int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int B, int H, int W, const float* shift,
-                 float* a2, float* out, long out_bs, hipStream_t st, float* pool_out = nullptr, int pool_h = 2,
-                 const PreConv* pre = nullptr, const MaskHead* mh = nullptr, const CatCopies* skip_out = nullptr,
-                 const CatCopies* cat_in = nullptr, const Site* act_out = nullptr, const CatCopies* pool_copies = nullptr,
-                 long pool_bs = 0, const UpFuse* up = nullptr, int cofs = 0) {  // cofs: this branch's channel offset inside the concatenated skip / pool
+                 float* a2, float* out, long out_bs, hipStream_t st, const BlockFusions& f = BlockFusions()) {
+    const PreConv* pre = f.pre;
+    const CatCopies *skip_out = f.skip_out, *cat_in = f.cat_in, *pool_copies = f.pool_copies;
     const float* x0 = pre ? pre->x0 : nullptr;
     const Site& s1 = c->sites[rb.s1];
     const Site& s2 = c->sites[rb.s2];
@@ -459,25 +467,27 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
     if ((skip_out || cat_in) && (!bf1 || c->compute_mode != LASS_COMPUTE_BF16))
         return fail(c, LASS_ERR_STATE, "blocked bf16 concat copies need the bf16 kernels");
     if (cat_in) p.in_bf16 = cat_in->act;
-    const bool wino1 = !bf1 && c->wino && rb.u1 && lass_wino_supported(p);
+    // the direct f32 kernels (conv.hip) have no *_PRE kinds: they refuse them
+    const ConvKind k1 = x0 ? CONV1_ACT_PRE : CONV1_ACT, k2 = x0 ? CONV2_IDENT_PRE : CONV2_IDENT;
+    const bool wino1 = !bf1 && rb.u1 && lass_wino_supported(p);
     auto launch_conv1 = [&]() -> int {
         ProfScope ps(c, st, P_CONV3X3);
         if (bf1)
-            HIP_TRY(c, lass_launch_conv_bf16(x0 ? CONV1_ACT_PRE : CONV1_ACT, p, st));
-        else if (wino1 && rb.u1f && lass_wino4_supported(x0 ? CONV1_ACT_PRE : CONV1_ACT, p))
-            HIP_TRY(c, lass_launch_wino4(x0 ? CONV1_ACT_PRE : CONV1_ACT, p, st));
+            HIP_TRY(c, lass_launch_conv_bf16(k1, p, st));
+        else if (wino1 && rb.u1f && lass_wino4_supported(k1, p))
+            HIP_TRY(c, lass_launch_wino4(k1, p, st));
         else if (wino1)
-            HIP_TRY(c, lass_launch_wino(x0 ? CONV1_ACT_PRE : CONV1_ACT, p, st));
+            HIP_TRY(c, lass_launch_wino(k1, p, st));
         else
-            HIP_TRY(c, lass_launch_conv(x0 ? CONV1_ACT_PRE : CONV1_ACT, p, st));
+            HIP_TRY(c, lass_launch_conv(k1, p, st));
         return 0;
     };
     ConvArgs q;
     q.in = a2; q.in_bs = rb.cout * HW; q.Cin = rb.cout; q.w = rb.w2; q.Nw = rb.cout; q.N = rb.cout;
     q.out = out; q.out_bs = out_bs; q.B = B; q.H = H; q.W = W;
-    q.pool_out = pool_out; q.pool_h = pool_h; q.pool_bs = pool_bs;
+    q.pool_out = f.pool_out; q.pool_h = f.pool_h; q.pool_bs = f.pool_bs;
     q.w_wino = rb.u2; q.w2_wino = rb.usc; q.w_wino4 = rb.u2f;
-    if (mh) {  // the block output is consumed by the fused head and never written
+    if (const MaskHead* mh = f.head) {  // the block output is consumed by the fused head and never written
         q.out = nullptr;
         q.mask_w = rawp(c, "base.after_conv.weight"); q.mask_b = rawp(c, "base.after_conv.bias");
         q.mask_mag = mh->mag; q.mask_cos = mh->cosv; q.mask_sin = mh->sinv;
@@ -488,15 +498,16 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
     if (bf2) { q.in_bf16 = a2_hi; q.in_bf16_lo = a2_lo; }
     if (cat_in) q.in2_bf16 = cat_in->raw;
     if (pool_copies) {  // bf16 mode: the pooled output as blocked bf16 copies for the next encoder block
-        if (!bf2 || c->compute_mode != LASS_COMPUTE_BF16 || !pool_out || pool_h != 2)
+        if (!bf2 || c->compute_mode != LASS_COMPUTE_BF16 || !f.pool_out || f.pool_h != 2)
             return fail(c, LASS_ERR_STATE, "blocked bf16 pooled copies need the bf16 kernels and the fused 2x2 pool");
         q.pool_out = nullptr;
         q.pool_bf16 = pool_copies->raw; q.pool_bf16_act = pool_copies->act;
-        q.pool_oct0 = cofs / 8; q.pool_noct = pool_copies->noct;
-        q.pool_act_scale = pool_copies->scale + cofs; q.pool_act_shift = pool_copies->shift + cofs; q.act_shift_bs = c->n_shift;
+        q.pool_oct0 = f.cofs / 8; q.pool_noct = pool_copies->noct;
+        q.pool_act_scale = pool_copies->scale + f.cofs; q.pool_act_shift = pool_copies->shift + f.cofs; q.act_shift_bs = c->n_shift;
     }
-    if (act_out) {  // bf16 mode: the block output goes to the next transposed conv only - written as ONE blocked bf16
-                    // tensor with that conv's BN+FiLM+leaky prologue already applied (in `out`'s storage)
+    if (const Site* act_out = f.act_out) {  // bf16 mode: the block output goes to the next transposed conv only - written as
+                                            // ONE blocked bf16 tensor with that conv's BN+FiLM+leaky prologue already applied
+                                            // (in `out`'s storage)
         if (!bf2 || c->compute_mode != LASS_COMPUTE_BF16) return fail(c, LASS_ERR_STATE, "activated bf16 output needs the bf16 kernels");
         q.out_bf16 = out; q.out = nullptr; q.out_oct0 = 0; q.out_noct = 0;
         q.epi_scale = c->bn_scale + act_out->off; q.epi_shift = shift + act_out->off; q.epi_shift_bs = c->n_shift;
@@ -504,10 +515,10 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
     if (skip_out) {  // the skip goes out as the two blocked copies (concat channels [C, 2C)) instead of f32
         q.out = nullptr;
         q.out_bf16 = skip_out->raw; q.out_bf16_act = skip_out->act;
-        q.out_oct0 = (rb.cout + cofs) / 8; q.out_noct = skip_out->noct;
-        q.act_scale = skip_out->scale + rb.cout + cofs; q.act_shift = skip_out->shift + rb.cout + cofs; q.act_shift_bs = c->n_shift;
+        q.out_oct0 = (rb.cout + f.cofs) / 8; q.out_noct = skip_out->noct;
+        q.act_scale = skip_out->scale + rb.cout + f.cofs; q.act_shift = skip_out->shift + rb.cout + f.cofs; q.act_shift_bs = c->n_shift;
     }
-    const bool wino2 = !bf2 && c->wino && rb.u2 && lass_wino_supported(q);
+    const bool wino2 = !bf2 && rb.u2 && lass_wino_supported(q);
     if (rb.cin == rb.cout) {
         q.res = x; q.res_bs = x_bs;
         if (x0) {
@@ -526,18 +537,18 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
     if (rb.cin != rb.cout) { q.in2 = x; q.in2_bs = x_bs; q.Cin2 = rb.cin; q.w2 = rb.wsc; q.bias = rb.bsc; }
     // ... and decoder_block6's ConvBlockRes with the output head behind it (conv1 from the activated cat copy, the 1x1
     // shortcut from the raw one)
-    if (up) {  // the caller has NOT run the transposed conv: only the kernel that contains it will do
+    if (const UpFuse* up = f.up) {  // the caller has NOT run the transposed conv: only the kernel that contains it will do
         ConvArgs uq;
         uq.in_bf16 = up->x_act; uq.Cin = up->cin; uq.H = up->h; uq.W = up->w; uq.B = B;
         uq.w_bf16 = up->w16; uq.w2_bf16 = up->wsc16;
-        if (!(bf2 && !x0 && c->fuse_block && c->compute_mode == LASS_COMPUTE_BF16 && cat_in && mh && rb.cin != rb.cout &&
+        if (!(bf2 && !x0 && c->fuse_block && c->compute_mode == LASS_COMPUTE_BF16 && cat_in && f.head && rb.cin != rb.cout &&
               lass_dec6u_fused_bf16_supported(p, q, uq)))
             return fail(c, LASS_ERR_STATE, "decoder_block6 with its transposed conv inside needs the fused bf16 kernel");
         ProfScope ps(c, st, P_CONV3X3);
         HIP_TRY(c, lass_launch_dec6u_fused_bf16(p, q, uq, st));
         return 0;
     }
-    if (bf2 && !x0 && c->fuse_block && c->compute_mode == LASS_COMPUTE_BF16 && cat_in && mh && rb.cin != rb.cout &&
+    if (bf2 && !x0 && c->fuse_block && c->compute_mode == LASS_COMPUTE_BF16 && cat_in && f.head && rb.cin != rb.cout &&
         lass_dec6_fused_bf16_supported(p, q)) {
         ProfScope ps(c, st, P_CONV3X3);
         HIP_TRY(c, lass_launch_dec6_fused_bf16(p, q, st));
@@ -547,13 +558,13 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
     ProfScope ps(c, st, P_CONV3X3);
     if (rb.cin == rb.cout) {
         if (bf2)
-            HIP_TRY(c, lass_launch_conv_bf16(x0 ? CONV2_IDENT_PRE : CONV2_IDENT, q, st));
-        else if (wino2 && x0 && rb.u2f && lass_wino4_supported(CONV2_IDENT_PRE, q))
-            HIP_TRY(c, lass_launch_wino4(CONV2_IDENT_PRE, q, st));
+            HIP_TRY(c, lass_launch_conv_bf16(k2, q, st));
+        else if (wino2 && x0 && rb.u2f && lass_wino4_supported(k2, q))
+            HIP_TRY(c, lass_launch_wino4(k2, q, st));
         else if (wino2)
-            HIP_TRY(c, lass_launch_wino(x0 ? CONV2_IDENT_PRE : CONV2_IDENT, q, st));
+            HIP_TRY(c, lass_launch_wino(k2, q, st));
         else
-            HIP_TRY(c, lass_launch_conv(x0 ? CONV2_IDENT_PRE : CONV2_IDENT, q, st));
+            HIP_TRY(c, lass_launch_conv(k2, q, st));
     } else {
         if (bf2)
             HIP_TRY(c, lass_launch_conv_bf16(CONV2_SHORTCUT, q, st));
@@ -602,7 +613,7 @@ int run_upconv(lass_ctx* c, int di, const float* x, int B, int h, int w, const f
 struct Plan {
     int B, L, T, Tp;
     size_t total = 0;
-    size_t mag, cosv, sinv, x0[kMaxBranches], shift, xpre, a2, cat[6], pool[6], center, decout[6], oreal, oimag;
+    size_t mag, cosv, sinv, x0[kMaxBranches], shift, a2, cat[6], pool[6], center, decout[6], oreal, oimag;
     int eh[7], ew[7];  // encoder block spatial sizes
 };
 
@@ -613,10 +624,9 @@ size_t bump(size_t& total, size_t floats) {
 }
 
 // The conv kernels address one clip's tensors through 32-bit buffer descriptors and byte offsets, so the largest per-clip
-// tensor (decoder_block6's concat at full resolution, f32) bounds the clip length: below 4 GiB for the f32 Winograd
-// and the bf16 kernels (all offset arithmetic unsigned; both exercised by the 3.15-GB concat of the 30 s @ 32 kHz multi-STFT
-// clip), below 2 GiB for the direct f32 kernels (LASS_WINO=0).  ResUNet30 at 16 kHz: 131 072 B per frame -> 2^32 at 32 768
-// frames (327 s); the multi-STFT model (128 ch x 1024 bins): 524 288 B per frame ->
+// tensor (decoder_block6's concat at full resolution, f32) bounds the clip length: below 4 GiB (all offset arithmetic of
+// the f32 Winograd and the bf16 kernels is unsigned; both exercised by the 3.15-GB concat of the 30 s @ 32 kHz multi-STFT
+// clip).  ResUNet30 at 16 kHz: 131 072 B per frame -> 2^32 at 32 768 frames (327 s); the multi-STFT model (128 ch x 1024 bins): 524 288 B per frame ->
 // 2^32 at 8 192 frames (40.9 s at 32 kHz).  Longer inputs go through chunk_inference.
 int make_plan(const lass_ctx* c, int B, int L, Plan* pl) {
     const Geometry& g = c->g;
@@ -625,15 +635,13 @@ int make_plan(const lass_ctx* c, int B, int L, Plan* pl) {
     pl->T = 1 + L / LASS_HOP;
     pl->Tp = (pl->T + 31) / 32 * 32;
     const size_t clip_max = (size_t)c->dec_cat[5] * pl->Tp * g.fcrop * sizeof(float);
-    const size_t limit = (c->compute_mode != LASS_COMPUTE_F32 || c->wino) ? 0xFFFF0000ull : 0x7FFFFFFFull;
-    if (clip_max > limit) return LASS_ERR_ARG;
+    if (clip_max > 0xFFFF0000ull) return LASS_ERR_ARG;
     size_t& t = pl->total;
     t = 0;
     const size_t spec = (size_t)B * pl->T * g.nbins;
     pl->mag = bump(t, spec); pl->cosv = bump(t, spec); pl->sinv = bump(t, spec);
     for (int k = 0; k < g.nbr; ++k) pl->x0[k] = bump(t, (size_t)B * pl->Tp * g.fcrop);
     pl->shift = bump(t, (size_t)B * c->n_shift);
-    pl->xpre = bump(t, c->fuse_preconv ? 64 : (size_t)B * kPreCh * pl->Tp * g.fcrop);
     int h = pl->Tp, w = g.fcrop;
     size_t a2max = 0;
     for (int i = 0; i < 7; ++i) {
@@ -722,15 +730,11 @@ static int create_impl(lass_ctx** out, int device_id, const Geometry& geom) {
     lass_ctx* c = new lass_ctx();
     c->device = device_id;
     c->g = geom;
-    if (const char* e = getenv("LASS_WINO")) c->wino = atoi(e) != 0;
-    if (const char* e = getenv("LASS_FUSE_POOL")) c->fuse_pool = atoi(e) != 0;
-    if (const char* e = getenv("LASS_FUSE_MASK")) c->fuse_mask = atoi(e) != 0;
     if (const char* e = getenv("LASS_FUSE_CATB")) c->fuse_catb = atoi(e) != 0;
     if (const char* e = getenv("LASS_FUSE_BLOCK")) c->fuse_block = atoi(e) != 0;
     if (const char* e = getenv("LASS_FUSE_UP")) c->fuse_up = atoi(e) != 0;
     if (const char* e = getenv("LASS_WINO4")) c->wino4_mincin = atoi(e);
     if (const char* e = getenv("LASS_SPLIT")) c->split_batch = std::max(0, std::min(2, atoi(e)));
-    if (const char* e = getenv("LASS_FUSE_PRECONV")) c->fuse_preconv = atoi(e) != 0;
     if (const char* e = getenv("LASS_GRAPH")) c->use_graph = atoi(e) != 0;
     c->prof.resize(P_COUNT);
     for (int i = 0; i < P_COUNT; ++i) c->prof[i].name = kProfNames[i];
@@ -908,7 +912,7 @@ int lass_finalize(lass_ctx* c, int compute_mode) {
                 rb.b1l = l1; rb.b2l = l2;
             }
         }
-        if (c->wino && c->compute_mode == LASS_COMPUTE_F32) {
+        if (c->compute_mode == LASS_COMPUTE_F32) {
             if (dev_alloc(c, &rb.u1, (size_t)16 * rb.cout * rb.cin) || dev_alloc(c, &rb.u2, (size_t)16 * rb.cout * rb.cout))
                 return LASS_ERR_HIP;
             HIP_TRY(c, lass_launch_wino_weights(w1, rb.cout, rb.cin, rb.u1, st));
@@ -947,7 +951,7 @@ int lass_finalize(lass_ctx* c, int compute_mode) {
                     rb.bscl = l3;
                 }
             }
-            if (c->wino && c->compute_mode == LASS_COMPUTE_F32) {
+            if (c->compute_mode == LASS_COMPUTE_F32) {
                 if (dev_alloc(c, &rb.usc, (size_t)4 * rb.cout * rb.cin)) return LASS_ERR_HIP;
                 HIP_TRY(c, lass_launch_wino_shortcut_weights(ws, rb.cout, rb.cin, rb.usc, st));
             }
@@ -1129,9 +1133,11 @@ int lass_encoder_block(lass_ctx* c, const char* name, const float* x, int B, int
         const bool pooled = e.dw == 2;
         if (pooled && (!pool || W % 2 != 0)) return fail(c, LASS_ERR_ARG, "lass_encoder_block: pool output needed, W even");
         // same rule as lass_separate: the pool rides in conv2's epilogue when the rows divide, else its own kernel
-        const bool fuse = pooled && c->fuse_pool && (H % e.dh) == 0;
+        const bool fuse = pooled && (H % e.dh) == 0;
         hipStream_t st = (hipStream_t)stream;
-        r = run_resblock(c, rb, x, rb.cin * HW, B, H, W, shift, scratch, y, rb.cout * HW, st, fuse ? pool : nullptr, e.dh);
+        BlockFusions f;
+        if (fuse) { f.pool_out = pool; f.pool_h = e.dh; }
+        r = run_resblock(c, rb, x, rb.cin * HW, B, H, W, shift, scratch, y, rb.cout * HW, st, f);
         if (r) return r;
         if (pooled && !fuse) HIP_TRY(c, lass_launch_pool(y, rb.cout * HW, B, rb.cout, H, W, e.dh, e.dw, pool, st));
         return 0;
@@ -1272,9 +1278,8 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
     if (make_plan(c, B, L, &pl))
         return fail(c, LASS_ERR_ARG, std::string(who) + ": need B >= 1 and " + std::to_string(g.nfft / 2) +
                                          " < L, with decoder_block6's concat (" + std::to_string(c->dec_cat[5]) +
-                                         " ch x frames x " + std::to_string(g.fcrop) + " bins, f32) below " +
-                                         ((c->compute_mode != LASS_COMPUTE_F32 || c->wino) ? "4" : "2") +
-                                         " GiB per clip (longer clips: ResUNet30.chunk_inference)");
+                                         " ch x frames x " + std::to_string(g.fcrop) +
+                                         " bins, f32) below 4 GiB per clip (longer clips: ResUNet30.chunk_inference)");
     if (workspace_bytes < pl.total)
         return fail(c, LASS_ERR_WORKSPACE, "workspace too small: need " + std::to_string(pl.total) + " bytes");
     if (((uintptr_t)workspace & 255) != 0) return fail(c, LASS_ERR_ARG, "workspace must be 256-byte aligned");
@@ -1308,8 +1313,9 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
         ProfScope ps(c, st, P_FILM);
         HIP_TRY(c, lass_launch_film(condition, B, c->film_W, c->film_b, c->bn_base, c->n_shift, shift, st));
     }
-    // pre_conv (resunet.py:555) is normally never materialised: encoder_block1 forms it from x0 while staging
-    const bool fuse_pre = c->fuse_preconv || nbr > 1;
+    // Routes.  pre_conv (resunet.py:555) is never materialised: encoder_block1 forms it from x0 while staging.  Tp is a
+    // multiple of 32, so every pooled level has even rows and F.avg_pool2d (resunet.py:197) rides in conv2's epilogue.
+    // decoder_block6 runs at W = fcrop with 32 channels: after_conv + mask ride in its conv2's epilogue.
     // bf16 mode: decoders 2-6 (2x2 up-sampling) take their concat as blocked bf16 copies written by the
     // producers
     CatCopies cb[6];
@@ -1320,8 +1326,7 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
         const ResBlock& re = c->enc[nbr - 1 + e];
         const long hw = (long)pl.eh[e] * pl.ew[e];
         use_cb[d] = c->fuse_catb && c->compute_mode == LASS_COMPUTE_BF16 && c->D[d].uh == 2 && c->D[d].uw == 2 &&
-                    c->fuse_pool && (pl.eh[e] % c->E[e].dh) == 0 && rd.cout % 16 == 0 && rd.b1 && rd.b2 && rd.bsc16 &&
-                    c->up16[d] && re.b1 && re.b2 && (e != 0 || fuse_pre);
+                    rd.cout % 16 == 0 && rd.b1 && rd.b2 && rd.bsc16 && c->up16[d] && re.b1 && re.b2;
         cb[d].act = F(pl.cat[d]);
         cb[d].raw = (char*)F(pl.cat[d]) + (size_t)B * rd.cin * hw * 2;
         cb[d].noct = rd.cin / 8;
@@ -1334,9 +1339,8 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
     for (int i = 0; i < 4; ++i) {
         const ResBlock& nx = c->enc[nbr - 1 + i + 1];
         const long hwo = (long)pl.eh[i + 1] * pl.ew[i + 1];
-        use_pc[i] = c->fuse_catb && c->compute_mode == LASS_COMPUTE_BF16 && c->fuse_pool && c->E[i].dh == 2 &&
-                    (pl.eh[i] % 2) == 0 && pl.ew[i] % 32 == 0 && (i != 0 || fuse_pre) && use_cb[5 - i] && use_cb[5 - (i + 1)] &&
-                    nx.cin != nx.cout && nx.cin % 16 == 0 && nx.b1 && nx.b2 && nx.bsc16;
+        use_pc[i] = c->fuse_catb && c->compute_mode == LASS_COMPUTE_BF16 && c->E[i].dh == 2 && pl.ew[i] % 32 == 0 &&
+                    use_cb[5 - i] && use_cb[5 - (i + 1)] && nx.cin != nx.cout && nx.cin % 16 == 0 && nx.b1 && nx.b2 && nx.bsc16;
         pc[i].act = F(pl.pool[i]);
         pc[i].raw = (char*)F(pl.pool[i]) + (size_t)B * nx.cin * hwo * 2;
         pc[i].noct = nx.cin / 8;
@@ -1350,85 +1354,68 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
         const long HW = (long)H * W;
         const EncSpec& e = c->E[i];
         const int nb = i == 0 ? nbr : 1;  // encoder_block1 runs once per analysis branch
-        const bool fuse_pool = i < 6 && c->fuse_pool && (H % e.dh) == 0;
         float* o = nullptr;
         long o_bs = 0;
         for (int k = 0; k < nb; ++k) {
             const ResBlock& rb = c->enc[i == 0 ? k : nbr - 1 + i];
-            const int cofs = k * e.cout;  // channel offset of this branch inside the concatenated skip / pool
+            BlockFusions f;
+            f.cofs = k * e.cout;  // channel offset of this branch inside the concatenated skip / pool
             if (i < 6) {  // skip output lives behind the transposed-conv half of decoder (5-i)'s concat buffer
                 const int d = 5 - i;
-                o = F(pl.cat[d]) + (size_t)(c->D[d].cout + cofs) * HW;
+                o = F(pl.cat[d]) + (size_t)(c->D[d].cout + f.cofs) * HW;
                 o_bs = (long)c->dec_cat[d] * HW;
+                const long Ho = H / e.dh, Wo = W / e.dw;
+                f.pool_out = F(pl.pool[i]) + (size_t)f.cofs * Ho * Wo;
+                f.pool_h = e.dh;
+                f.pool_bs = (long)e.cout * nb * Ho * Wo;
             } else {
                 o = F(pl.center);
                 o_bs = rb.cout * HW;
             }
-            const long Ho = H / e.dh, Wo = W / e.dw;
-            float* pool_k = i < 6 ? F(pl.pool[i]) + (size_t)cofs * Ho * Wo : nullptr;
-            const long pool_bs = (long)e.cout * nb * Ho * Wo;
-            PreConv pre{nullptr, nullptr, nullptr};
-            const float* xin = x;
+            PreConv pre{};
             if (i == 0) {
-                if (fuse_pre) {
-                    pre = PreConv{F(pl.x0[k]), rawp(c, c->pre_name[k] + ".weight"), rawp(c, c->pre_name[k] + ".bias")};
-                } else {
-                    ProfScope ps(c, st, P_PRECONV);
-                    HIP_TRY(c, lass_launch_preconv(F(pl.x0[k]), rawp(c, c->pre_name[k] + ".weight"),
-                                                   rawp(c, c->pre_name[k] + ".bias"), B, kPreCh, HW, F(pl.xpre), st));
-                    xin = F(pl.xpre);
-                }
+                pre = PreConv{F(pl.x0[k]), rawp(c, c->pre_name[k] + ".weight"), rawp(c, c->pre_name[k] + ".bias")};
+                f.pre = &pre;
             }
-            // F.avg_pool2d (resunet.py:197) is fused into conv2's epilogue; W >= 16 at every pooled level
-            r = run_resblock(c, rb, xin, rb.cin * HW, B, H, W, shift, F(pl.a2), o, o_bs, st, fuse_pool ? pool_k : nullptr,
-                             e.dh, pre.x0 ? &pre : nullptr, nullptr, (i < 5 && use_cb[5 - i]) ? &cb[5 - i] : nullptr,
-                             (i >= 1 && i <= 4 && use_pc[i - 1]) ? &pc[i - 1] : nullptr, nullptr,
-                             (i < 4 && use_pc[i]) ? &pc[i] : nullptr, pool_bs, nullptr, cofs);
+            if (i < 5 && use_cb[5 - i]) f.skip_out = &cb[5 - i];
+            if (i >= 1 && i <= 4 && use_pc[i - 1]) f.cat_in = &pc[i - 1];
+            if (i < 4 && use_pc[i]) f.pool_copies = &pc[i];
+            r = run_resblock(c, rb, x, rb.cin * HW, B, H, W, shift, F(pl.a2), o, o_bs, st, f);
             if (r) return r;
-            if (i < 6 && !fuse_pool) {
-                ProfScope ps(c, st, P_POOL);
-                if (nb > 1) return fail(c, LASS_ERR_STATE, "the multi-STFT model needs the fused avg-pool (LASS_FUSE_POOL=1)");
-                HIP_TRY(c, lass_launch_pool(o, o_bs, B, rb.cout, H, W, e.dh, e.dw, F(pl.pool[i]), st));
-            }
         }
         x = i < 6 ? F(pl.pool[i]) : o;  // conv_block7a: downsample (1,1) is the identity (resunet.py:363-370)
     }
     // ---- decoder (resunet.py:563-568) -------------------------------------------------------------------------
     bool x_act = false;  // x (input of the next transposed conv) is an activated blocked bf16 tensor
-    bool fused_head = false;
     for (int d = 0; d < 6; ++d) {
         const int e = 5 - d;
         const int H = pl.eh[e], W = pl.ew[e];
         const long HW = (long)H * W;
         const int h = H / c->D[d].uh, w = W / c->D[d].uw;
         const ResBlock& rb = c->dec[d];
+        BlockFusions f;
         // decoder_block6 in the blocked bf16 pipeline: the transposed conv runs inside the block's fused kernel, its output
         // (half of the concat, at the full resolution) is never written
         const UpFuse upf{x, c->D[d].cin, h, w, c->up16[d], c->up_sc16};
-        const bool fuse_up = d == 5 && c->fuse_up && c->fuse_block && c->fuse_mask && use_cb[d] && x_act && c->up_sc16 &&
+        const bool fuse_up = d == 5 && c->fuse_up && c->fuse_block && use_cb[d] && x_act && c->up_sc16 &&
                              c->compute_mode == LASS_COMPUTE_BF16 && rb.cout == 32 && rb.cin == 64 && W == g.fcrop && W % 32 == 0 &&
                              H % 2 == 0 && (unsigned long long)H * W * 8ull < 0x10000000ull;
-        if (!fuse_up) {
+        if (fuse_up) {
+            f.up = &upf;
+        } else {
             r = run_upconv(c, d, x, B, h, w, shift, F(pl.cat[d]), rb.cin * HW, st, use_cb[d] ? &cb[d] : nullptr, x_act);
             if (r) return r;
         }
         // this decoder's output feeds only the next transposed conv: hand it over activated, as blocked bf16
-        const bool act_next = d < 5 && c->fuse_catb && c->compute_mode == LASS_COMPUTE_BF16 && rb.b1 && rb.b2 &&
-                              rb.bsc16 && rb.cout % 16 == 0 && c->up16[d + 1];
-        x_act = act_next;
-        // decoder_block6 (32 channels at the full resolution): after_conv + mask run in conv2's epilogue
+        x_act = d < 5 && c->fuse_catb && c->compute_mode == LASS_COMPUTE_BF16 && rb.b1 && rb.b2 && rb.bsc16 &&
+                rb.cout % 16 == 0 && c->up16[d + 1];
+        if (x_act) f.act_out = &c->sites[c->dec_site[d + 1]];
+        if (use_cb[d]) f.cat_in = &cb[d];
         const MaskHead head{mag_m, cos_m, sin_m, F(pl.oreal), F(pl.oimag), T, g.nbins};
-        fused_head = d == 5 && c->fuse_mask && rb.cout == 32 && rb.cin != rb.cout && W == g.fcrop;
-        r = run_resblock(c, rb, F(pl.cat[d]), rb.cin * HW, B, H, W, shift, F(pl.a2), F(pl.decout[d]), rb.cout * HW, st,
-                         nullptr, 2, nullptr, fused_head ? &head : nullptr, nullptr, use_cb[d] ? &cb[d] : nullptr,
-                         act_next ? &c->sites[c->dec_site[d + 1]] : nullptr, nullptr, 0, fuse_up ? &upf : nullptr);
+        if (d == 5) f.head = &head;
+        r = run_resblock(c, rb, F(pl.cat[d]), rb.cin * HW, B, H, W, shift, F(pl.a2), F(pl.decout[d]), rb.cout * HW, st, f);
         if (r) return r;
         x = F(pl.decout[d]);
-    }
-    if (!fused_head) {
-        ProfScope ps(c, st, P_MASK);
-        HIP_TRY(c, lass_launch_mask(x, rawp(c, "base.after_conv.weight"), rawp(c, "base.after_conv.bias"), mag_m, cos_m,
-                                    sin_m, B, T, Tp, g.fcrop, F(pl.oreal), F(pl.oimag), st));
     }
     {
         ProfScope ps(c, st, P_ISTFT);
@@ -1477,9 +1464,6 @@ int lass_separate(lass_ctx* c, const float* mixture, const float* condition, flo
     // over fresh buffers every time simply stay on the eager path; so does a profiled context.
     lass_ctx::GraphKey key;
     key.mix = mixture; key.cond = condition; key.out = out; key.ws = workspace; key.B = B; key.L = L; key.gen = c->gen;
-#ifdef LASS_CONV_DIAG
-    c->use_graph = false;  // the diagnostic launchers allocate and synchronise: not capturable
-#endif
     if (c->use_graph && !c->profiling && c->finalized) {
         ++c->g_tick;
         lass_ctx::GraphEntry* slot = nullptr;

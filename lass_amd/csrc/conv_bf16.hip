@@ -11,9 +11,6 @@
 //   weights [tap][cin-octet (2)][cout][8 x bf16]     lane (h, n): octet h, cout n
 // A chunk is 16 input channels = one MFMA K; per chunk a wave issues TAPS x NCO x NPX MFMAs.
 #include <hip/hip_runtime.h>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
 #include "conv_common.h"
 #include "kernels.h"
 #include "wino_common.h"  // make_rsrc_words, lds_dma_16B, wait_vmcnt
@@ -421,13 +418,6 @@ __global__ __launch_bounds__(NTHREADS, (half_slab_v<TAPS, NCO, NPX, FLAGS, SPLIT
         }
     }
 
-#ifdef LASS_CONV_DIAG
-    const int EXPF = p.exp;  // timing experiments (LASS_EXP; wrong results): 1 no weight DMA, 2 no image DMA, 8 no MFMA
-    const long long dg_t0 = clock64();
-    long long dg_t1 = dg_t0, dg_t2 = dg_t0, dg_t3 = dg_t0;
-#else
-    constexpr int EXPF = 0;
-#endif
     PA pa;
     PB pb;
     const auto rs = [](const void* ptr, long bytes) {
@@ -502,9 +492,6 @@ __global__ __launch_bounds__(NTHREADS, (half_slab_v<TAPS, NCO, NPX, FLAGS, SPLIT
         pa.issue_wdma(wd_rs, wdl_rs, 0u, p.Nw, wl0, wave);
         __syncthreads();  // epilogue tables visible
         init_acc();
-#ifdef LASS_CONV_DIAG
-        dg_t1 = clock64();
-#endif
         // RF_SC: shortcut chunks q*ch + s (s < q) ride with 3x3 chunk ch.  Their fragments are requested one chunk ahead
         // (ordinary loads the compiler tracks; the LDS-DMA is issued from asm and is invisible to it) and consumed right
         // behind the barrier, BEFORE the next chunk's DMA is issued: hipcc waits vmcnt(0) in front of their first use, which
@@ -563,12 +550,12 @@ __global__ __launch_bounds__(NTHREADS, (half_slab_v<TAPS, NCO, NPX, FLAGS, SPLIT
             __syncthreads();   // ... everyone's have, and everyone has finished contracting chunk ch-1
             if (fold) sc_mfma(ch);
             if (ch + 1 < nA) {
-                if (!(EXPF & 2)) pa.issue_dma(a_rs, al_rs, (unsigned)((ch + 1) * 2 * HW) * 16u, img0 + (unsigned)((cur ^ 1) * PA::IN_U4 * 16), wave);
-                if (!(EXPF & 1)) pa.issue_wdma(wd_rs, wdl_rs, (unsigned)((ch + 1) * TAPS * 2 * p.Nw) * 16u, p.Nw,
+                pa.issue_dma(a_rs, al_rs, (unsigned)((ch + 1) * 2 * HW) * 16u, img0 + (unsigned)((cur ^ 1) * PA::IN_U4 * 16), wave);
+                pa.issue_wdma(wd_rs, wdl_rs, (unsigned)((ch + 1) * TAPS * 2 * p.Nw) * 16u, p.Nw,
                               wl0 + (unsigned)((cur ^ 1) * PA::W_U4 * 16), wave);
                 if (fold) sc_load(ch + 1);
             }
-            if (!(EXPF & 8)) PA::compute(lds4 + cur * PA::IN_U4, lds4 + 2 * PA::IN_U4 + cur * PA::W_U4, acc, lane, wave);
+            PA::compute(lds4 + cur * PA::IN_U4, lds4 + 2 * PA::IN_U4 + cur * PA::W_U4, acc, lane, wave);
         }
         sc_folded = fold;
         }
@@ -617,9 +604,6 @@ __global__ __launch_bounds__(NTHREADS, (half_slab_v<TAPS, NCO, NPX, FLAGS, SPLIT
             __syncthreads();
         }
     }
-#ifdef LASS_CONV_DIAG
-    dg_t2 = clock64();
-#endif
     float rtmp[RES_PF ? NPX : 1][16];
     if (HASB) {
         if (!IN2BF) pb.init(tid, y0, x0, p.H, p.W);
@@ -727,21 +711,11 @@ __global__ __launch_bounds__(NTHREADS, (half_slab_v<TAPS, NCO, NPX, FLAGS, SPLIT
         }
         PB::compute(lds4, wl_b, acc, lane, wave);
     }
-#ifdef LASS_CONV_DIAG
-    dg_t3 = clock64();
-#endif
     if (FLAGS & F_TCONV)
         tconv_store<NCO, NPX, PW>(p, acc, b, n0, y0, x0, lane, wave, lds_tact);
     else
         store_tile<NCO, NPX, PW, FLAGS, RES_PF>(p, acc, rtmp, lds_es, lds_eh, b, n0, y0, x0, lane, wave,
                                                  MASK ? lds_mw : nullptr, OUTBF ? lds_act : nullptr);
-#ifdef LASS_CONV_DIAG
-    if (p.dbg && tid == 0) {
-        long long* d = p.dbg + 4 * (size_t)blockIdx.x;
-        const long long te = clock64();
-        d[0] = dg_t1 - dg_t0; d[1] = dg_t2 - dg_t1; d[2] = dg_t3 - dg_t2; d[3] = te - dg_t3;
-    }
-#endif
 }
 
 // dst[chunk][tap][octet][Cout][8] (bf16, RNE) = src[co][ci = chunk*16 + octet*8 + j][tap]   (taps = 9 or 1)
@@ -766,38 +740,10 @@ __global__ __launch_bounds__(256) void weights_bf16_kernel(const float* __restri
 template <int TAPS, int NCO, int NPX, int PW, int FLAGS>
 hipError_t launch_bf16_one(const ConvArgs& p0, hipStream_t stream) {
     ConvArgs p = p0;
-#ifdef LASS_CONV_DIAG
-    static const int exp_flags = [] { const char* e = getenv("LASS_EXP"); return e ? atoi(e) : 0; }();
-    p.exp = exp_flags;
-    static long long* dbuf = nullptr;
-    static size_t dcap = 0;
-    constexpr int PHTd = 4 * NPX * (32 / PW);
-    const size_t nblk = (size_t)(p.W / PW) * ((p.H + PHTd - 1) / PHTd) * (p.N / (32 * NCO)) * p.B;
-    if (nblk > dcap) {
-        if (dbuf) (void)hipFree(dbuf);
-        (void)hipMalloc((void**)&dbuf, nblk * 32);
-        dcap = nblk;
-    }
-    p.dbg = dbuf;
-    struct Report {
-        const ConvArgs& p; size_t nblk; long long* dbuf;
-        ~Report() {
-            std::vector<long long> h(nblk * 4);
-            (void)hipDeviceSynchronize();
-            (void)hipMemcpy(h.data(), dbuf, nblk * 32, hipMemcpyDeviceToHost);
-            double s[4] = {0, 0, 0, 0};
-            for (size_t i = 0; i < nblk; ++i) for (int k = 0; k < 4; ++k) s[k] += (double)h[i * 4 + k];
-            fprintf(stderr, "[bf16-diag] taps=%d NCO=%d NPX=%d flags=%d Cin=%d Cin2=%d N=%d %dx%d blocks=%zu | cycles per block: prologue %.0f  "
-                    "main %.0f (%.0f per chunk)  shortcut %.0f  epilogue %.0f\n", TAPS, NCO, NPX, FLAGS, p.Cin, p.Cin2, p.N, p.H, p.W, nblk,
-                    s[0] / nblk, s[1] / nblk, s[1] / nblk / (p.Cin / 16.0), s[2] / nblk, s[3] / nblk);
-        }
-    } report{p, nblk, dbuf};
-#endif
     constexpr int PHT = 4 * NPX * (32 / PW);
     p.gx = (p.W / PW) * ((p.H + PHT - 1) / PHT);
     p.gy = p.N / (32 * NCO);
-    static const int xcd = [] { const char* e = getenv("LASS_XCD_MAP"); return e ? atoi(e) : 2; }();  // 0 off, 1 tile by tile, 2 contiguous ranges
-    p.xcd_map = (xcd && ((long)p.gx * p.B) % 8 == 0 && (p.gy > 1 || xcd == 2)) ? xcd : 0;
+    p.xcd_map = ((long)p.gx * p.B) % 8 == 0;
     dim3 grid((unsigned)((long)p.gx * p.gy * p.B));
     if constexpr ((FLAGS & F_NOSPLIT) != 0) {
         if (p.w_bf16_lo) return hipErrorInvalidValue;

@@ -85,12 +85,12 @@ struct ConvArgs {
     long pool_bs = 0;            // elements between clips of pool_out; 0 = dense (N * H/pool_h * W/2).  A launch that
                                  // produces a channel slice of a wider pooled tensor passes the wide tensor's stride.
     int pool_h = 2;              // vertical pool factor (1 or 2); horizontal is 2
-    // XCD-aware block order (wino.hip, conv_bf16.hip): launched as a 1-D grid of gx * gy * B workgroups; set by the launcher
+    // XCD-aware block order (conv.hip, wino.hip, wino4.hip, conv_bf16.hip): launched as a 1-D grid of gx * gy * B workgroups;
+    // set by the launcher
     int gx = 0, gy = 0;        // spatial tiles per clip, cout blocks
-    int xcd_map = 0;           // 1, 2: the gy cout blocks of one (tile, clip) run on ONE XCD (they re-read the same input tile);
-                               // 2: and every XCD walks one contiguous range of tiles (block_coords, wino_common.h)
-    long long* dbg = nullptr;  // diagnostic builds (-DLASS_CONV_DIAG) only: 8 int64 per block
-    int exp = 0;  // diagnostic builds only: timing-experiment switches (env LASS_EXP, see wino.hip)
+    int xcd_map = 0;           // 1 (when gx * B is a multiple of 8): the gy cout blocks of one (tile, clip) run on ONE XCD (they
+                               // re-read the same input tile), and every XCD walks one contiguous range of tiles
+                               // (block_coords, wino_common.h)
 };
 
 enum ConvKind { CONV1_ACT = 0, CONV2_IDENT = 1, CONV2_SHORTCUT = 2, TCONV_ACT = 3, CONV1_ACT_PRE = 4, CONV2_IDENT_PRE = 5 };
@@ -158,9 +158,6 @@ hipError_t lass_launch_istft2(const float* real, const float* imag, int B, int T
 // film[b][j] = dot(cond[b], Wf[j]) + bf[j] (+ base[j] if base)   for j < n
 hipError_t lass_launch_film(const float* cond, int B, const float* Wf, const float* bf, const float* base, int n,
                             float* out, hipStream_t stream);
-// out[b][c][t][f] = w[c]*x0[b][t][f] + bias[c]
-hipError_t lass_launch_preconv(const float* x0, const float* w, const float* bias, int B, int C, long HW, float* out,
-                               hipStream_t stream);
 // average pool (ph x pw) of (B,C,H,W) with batch stride in_bs -> (B,C,H/ph,W/pw) dense
 hipError_t lass_launch_pool(const float* in, long in_bs, int B, int C, int H, int W, int ph, int pw, float* out,
                             hipStream_t stream);

@@ -2,7 +2,6 @@
 //
 // Replaces (reference: /root/reference):
 //   FiLM.forward                 models/resunet.py:59-81   (38 nn.Linear -> ONE pass over a concatenated matrix)
-//   pre_conv                     models/resunet.py:555
 //   F.avg_pool2d                 models/resunet.py:197
 //   after_conv + feature_maps_to_wav (mask part)  models/resunet.py:570-574, :469-495
 //   calculate_sdr / calculate_sisdr reductions    utils.py:148-200
@@ -43,18 +42,6 @@ __global__ __launch_bounds__(256) void film_kernel(const float* __restrict__ con
         s = wave_sum(s);
         if (lane == 0) out[(size_t)b * n + j] = s + add;
     }
-}
-
-__global__ __launch_bounds__(256) void preconv_kernel(const float* __restrict__ x0, const float* __restrict__ w,
-                                                      const float* __restrict__ bias, int C, long HW,
-                                                      float* __restrict__ out) {
-    const int b = blockIdx.z, c = blockIdx.y;
-    const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (i >= HW) return;
-    const float4 v = *reinterpret_cast<const float4*>(x0 + (size_t)b * HW + i);
-    const float wc = w[c], bc = bias[c];
-    float4 o = make_float4(v.x * wc + bc, v.y * wc + bc, v.z * wc + bc, v.w * wc + bc);
-    *reinterpret_cast<float4*>(out + ((size_t)b * C + c) * HW + i) = o;
 }
 
 template <int PH>
@@ -350,14 +337,6 @@ hipError_t lass_launch_film(const float* cond, int B, const float* Wf, const flo
                             float* out, hipStream_t stream) {
     if (B <= 0 || n <= 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL(film_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, cond, B, Wf, bf, base, n, out);
-    return hipGetLastError();
-}
-
-hipError_t lass_launch_preconv(const float* x0, const float* w, const float* bias, int B, int C, long HW, float* out,
-                               hipStream_t stream) {
-    if (B <= 0 || C <= 0 || HW <= 0 || (HW % 4) != 0) return hipErrorInvalidValue;
-    dim3 grid((unsigned)((HW / 4 + 255) / 256), C, B);
-    hipLaunchKernelGGL(preconv_kernel, grid, dim3(256), 0, stream, x0, w, bias, C, HW, out);
     return hipGetLastError();
 }
 

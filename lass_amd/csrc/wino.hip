@@ -17,10 +17,7 @@
 // The 1x1 shortcut is the same kernel family in the transform domain: a centre-only 3x3 kernel has G g G^T non-zero
 // at the four xi in {1,2}x{1,2} only, and its B^T d B there needs just the 2x2 centre of the patch.
 #include <hip/hip_runtime.h>
-#include <cstdio>
-#include <cstdlib>
 #include <type_traits>
-#include <vector>
 #include "kernels.h"
 #include "pixel_ops.h"
 #include "wino_common.h"
@@ -234,16 +231,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void wino_kernel(ConvArgs p) {
     }
     if (MASK && tid < 99) lds_mw[tid] = tid < 96 ? p.mask_w[tid] : p.mask_b[tid - 96];
 
-#ifdef LASS_CONV_DIAG
-    const int EXPF = p.exp;  // timing experiments (LASS_EXP; results are wrong when set): 1 no U DMA, 2 no transform,
-                             // 4 no raw staging, 8 no MFMA
-#else
-    constexpr int EXPF = 0;
-#endif
-#ifdef LASS_CONV_DIAG
-    const long long k_c0 = clock64(), k_r0 = wall_clock64();
-    long long dg[6] = {0, 0, 0, 0, 0, 0};
-#endif
     f32x4 acc[16][2];
 #pragma unroll
     for (int xi = 0; xi < 16; ++xi)
@@ -258,9 +245,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void wino_kernel(ConvArgs p) {
     const unsigned slab_pitch = (unsigned)(p.Nw / 32) * 16384u;  // bytes between the slabs of consecutive chunks
     const unsigned slab_n0 = (unsigned)(n0 / 32) * 16384u;
 
-#ifdef LASS_CONV_DIAG
-    const long long k_main0 = clock64();
-#endif
     // ---- main phase: 3x3 over p.in ------------------------------------------------------------------------------
     // Per chunk:  barrier | raw(ch) regs->LDS | issue U(ch) LDS-DMA | issue raw(ch+2) loads | barrier |
     //             transform raw->V | wait U(ch) (counted vmcnt: the raw(ch+2) loads stay in flight) | barrier |
@@ -384,40 +368,17 @@ __global__ __launch_bounds__(NTHREADS, 2) void wino_kernel(ConvArgs p) {
         lds_barrier();  // prologue tables visible
         auto chunk = [&](int ch, auto buf) {
             constexpr int BUF = decltype(buf)::value;
-#ifdef LASS_CONV_DIAG
-            const long long t0 = clock64();
-#endif
             lds_barrier();  // previous chunk's MFMAs have finished reading V / U
             prep_prio();
-#ifdef LASS_CONV_DIAG
-            const long long t1 = clock64();
-#endif
-            if (!(EXPF & 4)) ra.template store<BUF>(lraw, lds_sc + ch * KC, lds_sh + ch * KC, tid, lds_pw + ch * KC, lds_pb + ch * KC);
+            ra.template store<BUF>(lraw, lds_sc + ch * KC, lds_sh + ch * KC, tid, lds_pw + ch * KC, lds_pb + ch * KC);
             __builtin_amdgcn_sched_barrier(0);
-            if (!(EXPF & 1)) UA::issue(uw_n0, ulane, (unsigned)ch * slab_pitch + slab_n0, lu_addr, wave);
+            UA::issue(uw_n0, ulane, (unsigned)ch * slab_pitch + slab_n0, lu_addr, wave);
             __builtin_amdgcn_sched_barrier(0);
-            const bool pf = ch + 2 < nch && !(EXPF & 4);
+            const bool pf = ch + 2 < nch;
             if (pf) ra.template load<BUF>(in_rsrc, (unsigned)((ch + 2) * KC * HW) * 4u, HW);
             __builtin_amdgcn_sched_barrier(0);
-#ifdef LASS_CONV_DIAG
-            const long long t2 = clock64();
-#endif
             lds_barrier();  // raw tile visible
-#ifdef LASS_CONV_DIAG
-            const long long t3 = clock64();
-#endif
-#ifdef LASS_CONV_DIAG
-            if (EXPF & 48) {  // sensitivity probe: 16 (bit 4) / 32 (bit 5) extra dependent-free VALU instructions in the prep phase
-                float dv0 = (float)tid, dv1 = dv0 + 1.f, dv2 = dv0 + 2.f, dv3 = dv0 + 3.f;
-                const int nrep = ((EXPF & 16) ? 4 : 0) + ((EXPF & 32) ? 8 : 0);
-                for (int q = 0; q < nrep; ++q)
-                    asm volatile("v_add_f32 %0, %0, %0\n\tv_add_f32 %1, %1, %1\n\tv_add_f32 %2, %2, %2\n\tv_add_f32 %3, %3, %3"
-                                 : "+v"(dv0), "+v"(dv1), "+v"(dv2), "+v"(dv3));
-                if (dv0 + dv1 + dv2 + dv3 == 1.2345f) lraw[0] = dv0;
-            }
-#endif
             // input transform V = B^T d B: one (channel, tile) item per thread and pass
-            if (!(EXPF & 2))
 #pragma unroll
             for (int it = 0; it < (KC * NWT) / NTHREADS; ++it) {
                 const int item = tid + it * NTHREADS;
@@ -449,33 +410,20 @@ __global__ __launch_bounds__(NTHREADS, 2) void wino_kernel(ConvArgs p) {
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
-#ifdef LASS_CONV_DIAG
-            const long long t4 = clock64();
-#endif
             if (pf && !PRE)
                 wait_vmcnt<RA::NLOADS>();  // this wave's U(ch) rows have landed; raw(ch+2) may still be in flight
             else
                 wait_vmcnt<0>();
             lds_barrier();  // V visible, every wave's U rows landed
-#ifdef LASS_CONV_DIAG
-            const long long t5 = clock64();
-#endif
             // 16 GEMMs: M_xi += U_xi (32 couts x 8 cin) * V_xi (8 cin x 16 tiles)
             mfma_prio();
-            if (!(EXPF & 8)) gemm_steps<16, 256, 4 * VP>(afrag, bfrag, acc, [](int s) { return s; });
-#ifdef LASS_CONV_DIAG
-            dg[0] += t1 - t0; dg[1] += t2 - t1; dg[2] += t3 - t2; dg[3] += t4 - t3; dg[4] += t5 - t4;
-            dg[5] += clock64() - t5;
-#endif
+            gemm_steps<16, 256, 4 * VP>(afrag, bfrag, acc, [](int s) { return s; });
         };
         for (int ch = 0; ch < nch; ch += 2) {
             chunk(ch, std::integral_constant<int, 0>{});
             chunk(ch + 1, std::integral_constant<int, 1>{});
         }
     }
-#ifdef LASS_CONV_DIAG
-    const long long k_sc0 = clock64();
-#endif
     // ---- shortcut phase: 1x1 over p.in2, in the transform domain (xi in {5,6,9,10}) -------------------------------
     // Chunks of 32 channels: a thread owns one tile position and channels cb + i*CSTEP; it loads the 2x2 patch centres
     // straight from global (two aligned 8-byte loads per item, issued one chunk ahead: they land during the MFMAs) and
@@ -540,28 +488,12 @@ __global__ __launch_bounds__(NTHREADS, 2) void wino_kernel(ConvArgs p) {
         }
     }
 
-#ifdef LASS_CONV_DIAG
-    const long long k_epi0 = clock64();
-#endif
     // ---- output transform Y = A^T M A and epilogue (wino_epilogue.h) ---------------------------------------------------
     {
         const int wty = (wwt * 16 + l15) / PWT, wtx = (wwt * 16 + l15) % PWT;  // this lane's tile within the block
         wino_epilogue<FLAGS>(p, acc, b, n0, wco * 32, y0 + 2 * wty, x0 + 2 * wtx, lane, lds_bias, lds_es, lds_eh, lds_pw, lds_pb,
                              lds_mw);
     }
-#ifdef LASS_CONV_DIAG
-    if (p.dbg && tid == 0) {
-        long long* d = p.dbg + 12 * (size_t)blockIdx.x;
-        for (int i = 0; i < 6; ++i) d[i] = dg[i];
-        const long long k_end = clock64();
-        d[6] = k_end - k_c0;
-        d[7] = wall_clock64() - k_r0;
-        d[8] = k_main0 - k_c0;   // kernel prologue (tables, accumulator init)
-        d[9] = k_sc0 - k_main0;  // main phase incl. its own start-up (first loads)
-        d[10] = k_epi0 - k_sc0;  // shortcut phase
-        d[11] = k_end - k_epi0;  // output transform + epilogue
-    }
-#endif
 }
 
 // Transform-domain weights U_xi[cin][cout] = (G g G^T)[xi] for g = w[cout][cin][3][3], G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],
@@ -606,15 +538,10 @@ __global__ __launch_bounds__(256) void wino_shortcut_weights_kernel(const float*
 template <int FLAGS, bool PATCH>
 hipError_t launch_wino_v(const ConvArgs& p0, hipStream_t stream) {
     ConvArgs p = p0;
-#ifdef LASS_CONV_DIAG
-    static const int exp_flags = [] { const char* e = getenv("LASS_EXP"); return e ? atoi(e) : 0; }();
-    p.exp = exp_flags;
-#endif
     const bool wide = p.N % 64 == 0;  // 32-cout blocks on the >= 64-cout layers: measured 10 % slower (V work doubles)
-    static const int xcd = [] { const char* e = getenv("LASS_XCD_MAP"); return e ? atoi(e) : 2; }();  // 0 off, 1 tile by tile, 2 contiguous ranges
     auto set_grid = [&](int gx, int gy) {  // 1-D grid, decoded by block_coords()
         p.gx = gx; p.gy = gy;
-        p.xcd_map = (xcd && ((long)gx * p.B) % 8 == 0 && (gy > 1 || xcd == 2)) ? xcd : 0;
+        p.xcd_map = ((long)gx * p.B) % 8 == 0;
         return dim3((unsigned)((long)gx * gy * p.B));
     };
     if (p.W < 32) {  // 16- / 8-bin layers: 64-cout blocks of 8 x 16 or 16 x 8 output pixels
@@ -630,17 +557,6 @@ hipError_t launch_wino_v(const ConvArgs& p0, hipStream_t stream) {
         }
     }
     const dim3 grid = wide ? set_grid((p.W / 32) * ((p.H + 3) / 4), p.N / 64) : set_grid((p.W / 32) * ((p.H + 7) / 8), p.N / 32);
-#ifdef LASS_CONV_DIAG
-    static long long* dbuf = nullptr;
-    static size_t dcap = 0;
-    const size_t nblk = (size_t)grid.x * grid.y * grid.z;
-    if (nblk > dcap) {
-        if (dbuf) (void)hipFree(dbuf);
-        (void)hipMalloc((void**)&dbuf, nblk * 96);
-        dcap = nblk;
-    }
-    p.dbg = dbuf;
-#endif
     if constexpr ((FLAGS & F_MASK) != 0) {
         if (wide) return hipErrorInvalidValue;  // N == 32 only (host-checked)
         hipLaunchKernelGGL((wino_kernel<1, 4, FLAGS, 16, PATCH>), grid, dim3(NTHREADS), 0, stream, p);
@@ -650,24 +566,6 @@ hipError_t launch_wino_v(const ConvArgs& p0, hipStream_t stream) {
         else
             hipLaunchKernelGGL((wino_kernel<1, 4, FLAGS, 16, PATCH>), grid, dim3(NTHREADS), 0, stream, p);
     }
-#ifdef LASS_CONV_DIAG
-    {
-        std::vector<long long> h(nblk * 12);
-        (void)hipDeviceSynchronize();
-        (void)hipMemcpy(h.data(), dbuf, nblk * 96, hipMemcpyDeviceToHost);
-        double s[12] = {0};
-        for (size_t i = 0; i < nblk; ++i)
-            for (int k = 0; k < 12; ++k) s[k] += (double)h[i * 12 + k];
-        const double nch = p.Cin / 8.0;
-        for (double& v : s) v /= (double)nblk;
-        fprintf(stderr,
-                "[wino-diag] Cin=%d N=%d %dx%d blocks=%zu | per chunk: barA %.0f  store+issue %.0f  barB %.0f  transform %.0f  "
-                "waitU+barC %.0f  mfma %.0f | block total %.0f cycles = prologue %.0f + main %.0f + shortcut %.0f + epilogue %.0f, "
-                "clock %.3f GHz\n",
-                p.Cin, p.N, p.H, p.W, nblk, s[0] / nch, s[1] / nch, s[2] / nch, s[3] / nch, s[4] / nch, s[5] / nch, s[6], s[8],
-                s[9], s[10], s[11], s[6] / s[7] * 0.1);
-    }
-#endif
     return hipGetLastError();
 }
 

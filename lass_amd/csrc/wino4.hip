@@ -22,7 +22,6 @@
 // D layout, so the 1x1 conv is 16 more MFMAs per 4 input channels with B operands straight from global memory (this lane's
 // tile of channel 4 ks + kq: four 16-byte loads) and A = the shortcut weights - no transform, no LDS.
 #include <hip/hip_runtime.h>
-#include <cstdlib>
 #include "kernels.h"
 #include "pixel_ops.h"
 #include "wino_common.h"
@@ -467,8 +466,7 @@ hipError_t launch_wino4_tc(const ConvArgs& p0, hipStream_t stream) {
     constexpr int OR_ = 4 * (32 / TC), OC = 4 * TC;
     p.gx = (p.W / OC) * ((p.H + OR_ - 1) / OR_);
     p.gy = p.N / 32;
-    static const int xcd = [] { const char* e = getenv("LASS_XCD_MAP"); return e ? atoi(e) : 2; }();
-    p.xcd_map = (xcd && ((long)p.gx * p.B) % 8 == 0 && (p.gy > 1 || xcd == 2)) ? xcd : 0;
+    p.xcd_map = ((long)p.gx * p.B) % 8 == 0;
     hipLaunchKernelGGL((wino4_kernel<TC, FLAGS>), dim3((unsigned)((long)p.gx * p.gy * p.B)), dim3(NTHREADS), 0, stream, p);
     return hipGetLastError();
 }

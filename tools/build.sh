@@ -1,5 +1,5 @@
 #!/bin/bash
-# Build liblass_hip.so (and optionally the diagnostic variant / ISA) from anywhere.  Usage: tools/build.sh [diag] [asm FILE]
+# Build liblass_hip.so from anywhere, with the compiler's resource remarks (build.log).  Usage: tools/build.sh
 set -e
 cd "$(dirname "$0")/../lass_amd/csrc"
 SRC="api.hip conv.hip wino.hip wino4.hip conv_bf16.hip conv_bf16_fused.hip stft.hip misc.hip"
@@ -9,7 +9,6 @@ import sys; sys.path.insert(0, "../..")
 import __graft_entry__ as g
 open(g.STAMP, "w").write(g._src_hash())   # keep build()'s staleness stamp in step with this manual build
 PY
-if [ "$1" = "diag" ]; then hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -fno-slp-vectorize -shared -DLASS_CONV_DIAG -o liblass_hip_diag.so $SRC 2>&1 | grep -E "error" || true; fi
 python3 - <<'PY'
 import re
 txt=open('build.log').read()

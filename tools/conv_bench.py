@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-layer timing of the residual blocks / transposed convs at the BASELINE configs[1] shapes (B=16, T=1024).
-Usage (GPU box): LASS_CONV_VARIANT=n python tools/conv_bench.py [--iters 5] [--only enc1,dec6]"""
+Usage (GPU box): python tools/conv_bench.py [--iters 5] [--only enc1,dec6]"""
 import argparse, os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -46,4 +46,4 @@ for name, kind, prefix, cin, cout, H, W, up in jobs:
     res[name] = (ms, tf)
     print(f'{name:22s} cin={cin:4d} cout={cout:4d} {H:5d}x{W:<4d} {ms:8.3f} ms {tf:7.1f} TF', flush=True)
     del x
-print(f'TOTAL variant={os.environ.get("LASS_CONV_VARIANT","default")} {tot_ms:.3f} ms  {tot_fl/tot_ms/1e9:.1f} TF', flush=True)
+print(f'TOTAL {tot_ms:.3f} ms  {tot_fl/tot_ms/1e9:.1f} TF', flush=True)

@@ -17,17 +17,6 @@ done
 for p in "${pids[@]}"; do wait $p; done
 OBJS=""; for s in $SRC; do OBJS="$OBJS .obj/${s%.hip}.o"; done
 hipcc --offload-arch=gfx950 -shared -o liblass_hip.so $OBJS
-if [ "$1" = "diag" ]; then  # diagnostic library (-DLASS_CONV_DIAG in the files named in $2, default "api wino"): liblass_hip_diag.so
-  mkdir -p .obj/diag; DOBJS=""
-  for s in $SRC; do
-    b=${s%.hip}
-    if echo " ${2:-api wino} " | grep -q " $b "; then
-      hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -fno-slp-vectorize -DLASS_CONV_DIAG -c $s -o .obj/diag/$b.o 2> .obj/diag/$b.log || { grep error .obj/diag/$b.log | head; exit 1; }
-      DOBJS="$DOBJS .obj/diag/$b.o"
-    else DOBJS="$DOBJS .obj/$b.o"; fi
-  done
-  hipcc --offload-arch=gfx950 -shared -o liblass_hip_diag.so $DOBJS
-fi
 python3 - <<'PY'
 import sys; sys.path.insert(0, "../..")
 import __graft_entry__ as g
