@@ -439,6 +439,11 @@ struct BlockFusions {
     const UpFuse* up = nullptr;             // bf16, decoder_block6: its transposed conv inside the block's fused kernel
 };
 
+// f32: the shortcut layers with at least this many input channels run their 1x1 conv in pw_gemm.hip.  Shallower ones (K = 32 ...
+// 128: encoder_block2-4, decoder_block5-6) are byte-bound there - writing bias + Wsc x and reading it back costs more than
+// the re-fetches it saves (measured, profiles/r06)
+constexpr int kShortcutGemmMinCin = 256;
+
 int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int B, int H, int W, const float* shift,
                  float* a2, float* out, long out_bs, hipStream_t st, const BlockFusions& f = BlockFusions()) {
     const PreConv* pre = f.pre;
@@ -554,9 +559,30 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
         HIP_TRY(c, lass_launch_dec6_fused_bf16(p, q, st));
         return 0;
     }
+    // f32, the deep shortcut layers (encoder_block5, decoder_block2-4): the 1x1 shortcut as a GEMM of its own with a 128-cout
+    // tile (pw_gemm.hip), written into the block's output slot; conv2 then adds its result to that slot in place (wino4.hip,
+    // CONV2_IDENT).  Fused into conv2's 32-cout workgroups instead, every one of the Cout / 32 workgroups of a tile fetches the
+    // whole block input again.  The other shortcut layers (and decoder_block6's output head) keep the fused phase.
+    const bool sc_gemm = c->compute_mode == LASS_COMPUTE_F32 && !bf2 && rb.cin != rb.cout && !f.head && rb.cin >= kShortcutGemmMinCin &&
+                         wino2 && rb.u2f && lass_wino4_supported(CONV2_SHORTCUT, q) && lass_pw_gemm_supported(CONV2_SHORTCUT, q);
+    if (sc_gemm) {
+        const auto overlaps = [&](const float* a, long a_bs, long a_n, const float* b, long b_bs, long b_n) {
+            return a < b + (size_t)(B - 1) * b_bs + b_n && b < a + (size_t)(B - 1) * a_bs + a_n;
+        };
+        if (overlaps(out, out_bs, rb.cout * HW, x, x_bs, rb.cin * HW) || overlaps(out, out_bs, rb.cout * HW, a2, rb.cout * HW, rb.cout * HW))
+            return fail(c, LASS_ERR_STATE, "a block's output must not overlap its input or its intermediate");
+        ProfScope ps(c, st, P_CONV3X3);
+        HIP_TRY(c, lass_launch_pw_gemm(CONV2_SHORTCUT, q, st));
+    }
     if (int r1 = launch_conv1()) return r1;
     ProfScope ps(c, st, P_CONV3X3);
-    if (rb.cin == rb.cout) {
+    if (sc_gemm) {
+        ConvArgs r = q;
+        r.in2 = nullptr; r.in2_bs = 0; r.Cin2 = 0; r.w2 = nullptr; r.bias = nullptr;
+        r.res = out; r.res_bs = out_bs;
+        if (!lass_wino4_supported(CONV2_IDENT, r)) return fail(c, LASS_ERR_STATE, "conv2 with the shortcut as residual");
+        HIP_TRY(c, lass_launch_wino4(CONV2_IDENT, r, st));
+    } else if (rb.cin == rb.cout) {
         if (bf2)
             HIP_TRY(c, lass_launch_conv_bf16(k2, q, st));
         else if (wino2 && x0 && rb.u2f && lass_wino4_supported(k2, q))
@@ -577,6 +603,10 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
     }
     return 0;
 }
+
+// f32: transposed convs with at least this many input channels run in pw_gemm.hip; decoder_block6's (K = 64, 1 GB of output
+// per batch) is byte-bound and measured 7 % faster in the direct kernel
+constexpr int kTconvGemmMinCin = 128;
 
 int run_upconv(lass_ctx* c, int di, const float* x, int B, int h, int w, const float* shift, float* out, long out_bs,
                hipStream_t st, const CatCopies* cb = nullptr, bool x_is_act_bf16 = false) {
@@ -604,6 +634,8 @@ int run_upconv(lass_ctx* c, int di, const float* x, int B, int h, int w, const f
     ProfScope ps(c, st, P_TCONV);
     if (c->compute_mode != LASS_COMPUTE_F32 && p.w_bf16 && lass_bf16_supported(p))
         HIP_TRY(c, lass_launch_conv_bf16(TCONV_ACT, p, st));
+    else if (c->compute_mode == LASS_COMPUTE_F32 && d.cin >= kTconvGemmMinCin && lass_pw_gemm_supported(TCONV_ACT, p))
+        HIP_TRY(c, lass_launch_pw_gemm(TCONV_ACT, p, st));  // K = cin, N = 4 cout: one GEMM, the prologue applied once per element
     else
         HIP_TRY(c, lass_launch_conv(TCONV_ACT, p, st));
     return 0;

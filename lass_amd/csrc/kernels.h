@@ -103,10 +103,17 @@ hipError_t lass_launch_wino(ConvKind kind, const ConvArgs& p, hipStream_t stream
 hipError_t lass_launch_wino_weights(const float* w, int Cout, int Cin, float* U, hipStream_t stream);
 hipError_t lass_launch_wino_shortcut_weights(const float* w, int Cout, int Cin, float* U, hipStream_t stream);
 
-// ---- wino4.hip (Winograd F(4x4,3x3): 36 instead of 64 MFMA multiplies per 16 outputs; the conv1 kind, W % 32 == 0) ----------
+// ---- wino4.hip (Winograd F(4x4,3x3): 36 instead of 64 MFMA multiplies per 16 outputs; W % 32 == 0) ---------------------------
+// CONV2_IDENT: conv2 + a residual read from res (which may be `out` itself: every element is read and written by one lane)
 bool lass_wino4_supported(ConvKind kind, const ConvArgs& p);
 hipError_t lass_launch_wino4(ConvKind kind, const ConvArgs& p, hipStream_t stream);
 hipError_t lass_launch_wino4_weights(const float* w, int Cout, int Cin, float* U, hipStream_t stream);  // w (Cout, Cin, 3, 3)
+
+// ---- pw_gemm.hip (f32 pointwise GEMMs with a 128-cout workgroup tile; H*W % 4 == 0, N % 128 == 0, K % 32 == 0) ------------
+// CONV2_SHORTCUT: only the 1x1 shortcut, out = bias + Wsc x (in2, Cin2, w2, bias), for conv2 to read back as its residual;
+// TCONV_ACT: the kernel == stride transposed conv behind its BN+FiLM+leaky prologue (f32 output only)
+bool lass_pw_gemm_supported(ConvKind kind, const ConvArgs& p);
+hipError_t lass_launch_pw_gemm(ConvKind kind, const ConvArgs& p, hipStream_t stream);
 
 // ---- conv_bf16.hip (bf16-MFMA variant of the 3x3 kinds; W multiple of 32, Cin multiple of 16) ----------------------
 bool lass_bf16_supported(const ConvArgs& p);

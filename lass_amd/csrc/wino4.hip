@@ -16,8 +16,9 @@
 //      16-byte load + two 4-byte loads per row, requested one chunk ahead), gets the BN+FiLM+leaky prologue and the zero
 //      padding and is transformed in registers (144 add / fma), then written to V[36][4][32][2] in LDS;
 //   3. 72 MFMAs per wave (36 xi x 2 k-steps), A and B fragments one ds_read_b64 each.
-// Kinds: conv1 of a ConvBlockRes (prologue + epilogue activation) and conv2 with the 1x1 shortcut (resunet.py:122-128,163),
-// bias and the block's fused avg-pool (:197).  The shortcut is NOT taken through the transform domain: once the 36 xi are
+// Kinds: conv1 of a ConvBlockRes (prologue + epilogue activation), conv2 with the 1x1 shortcut (resunet.py:122-128,163),
+// bias and the block's fused avg-pool (:197), and conv2 + a residual read from memory (+ the pool) for the wide layers whose
+// shortcut runs as a GEMM of its own (pw_gemm.hip).  The shortcut is NOT taken through the transform domain: once the 36 xi are
 // folded into this lane's 4 couts x 16 pixels, accumulator tile s = [16 couts][16 tiles] of sub-pixel s has exactly the MFMA
 // D layout, so the 1x1 conv is 16 more MFMAs per 4 input channels with B operands straight from global memory (this lane's
 // tile of channel 4 ks + kq: four 16-byte loads) and A = the shortcut weights - no transform, no LDS.
@@ -68,10 +69,12 @@ __global__ __launch_bounds__(NTHREADS, 2) void wino4_kernel(ConvArgs p) {
     constexpr bool PRE = (FLAGS & F_PRECONV) != 0;   // the input is the 1-channel x0: channel c = pre_w[c] * x0 + pre_b[c] (resunet.py:555)
     constexpr bool RESPRE = (FLAGS & F_RESPRE) != 0; // identity residual = pre_conv(x0), never materialised (encoder_block1.conv2)
     constexpr bool MASK = (FLAGS & F_MASK) != 0;     // epilogue = after_conv + complex ratio mask; the block output is not written
+    constexpr bool RES = (FLAGS & F_RES) != 0;       // + residual: pre_conv(x0) (RESPRE) or read from p.res, possibly in place
     static_assert(!SC || (FLAGS & F_BIAS) != 0, "the shortcut conv has a bias");
     static_assert(!PRE || PRO, "pre_conv is folded into the prologue's affine");
     static_assert(!RESPRE || ((FLAGS & F_RES) != 0 && !SC && !EPI), "conv2 with the identity residual");
     static_assert(!MASK || SC, "the output head sits behind decoder_block6's conv2 + shortcut");
+    static_assert(!RES || (!SC && !EPI), "conv2 with a residual in place of the fused shortcut");
     constexpr int TR = 32 / TC;
     constexpr int OR_ = 4 * TR, OC = 4 * TC;
     constexpr int NCO = 32;  // output channels of the workgroup
@@ -321,6 +324,27 @@ __global__ __launch_bounds__(NTHREADS, 2) void wino4_kernel(ConvArgs p) {
             }
         }
     }
+    if constexpr (RES && !RESPRE) {
+        // + the residual at this lane's 4 couts x 16 pixels (resunet.py:165): for the routed shortcut layers bias + Wsc x, which
+        // pw_gemm.hip wrote into the output slot itself - read here and overwritten below by the same lane.  All 16 rows are
+        // fetched in one batch in front of the stores (a load behind a store to `out` cannot be hoisted over it).
+        float4 rv[4][4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float* rr = p.res + (size_t)b * p.res_bs + (size_t)(n0 + wco * 16 + kq * 4 + r) * HW + (size_t)min(oy, p.H - 4) * p.W + ox;
+#pragma unroll
+            for (int a = 0; a < 4; ++a) rv[r][a] = *reinterpret_cast<const float4*>(rr + (size_t)a * p.W);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                ysp[a * 4 + 0][r] += rv[r][a].x;
+                ysp[a * 4 + 1][r] += rv[r][a].y;
+                ysp[a * 4 + 2][r] += rv[r][a].z;
+                ysp[a * 4 + 3][r] += rv[r][a].w;
+            }
+    }
     if constexpr (SC) {
         // ---- 1x1 shortcut over the raw block input (resunet.py:163), direct: per 4 input channels 16 MFMAs, one per sub-pixel;
         // B[k = kq][col = l15] = x[channel 4 ks + kq][this lane's tile, sub-pixel s] (four 16-byte row loads),
@@ -417,7 +441,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void wino4_kernel(ConvArgs p) {
             const float4 o = make_float4(ysp[a * 4 + 0][r], ysp[a * 4 + 1][r], ysp[a * 4 + 2][r], ysp[a * 4 + 3][r]);
             if (oy + a < p.H) *reinterpret_cast<float4*>(dst + (size_t)a * p.W) = o;
         }
-        if ((SC || RESPRE) && p.pool_out) {  // wave-uniform; pool_h == 2 (host-checked): row-major summation order of F.avg_pool2d
+        if ((SC || RES) && p.pool_out) {  // wave-uniform; pool_h == 2 (host-checked): row-major summation order of F.avg_pool2d
             const int Ho = p.H / 2, Wo = p.W / 2;
             float* pd = p.pool_out + (size_t)b * (p.pool_bs ? (size_t)p.pool_bs : (size_t)p.N * Ho * Wo) + (size_t)n * Ho * Wo +
                         (size_t)(oy >> 1) * Wo + (ox >> 1);
@@ -491,6 +515,8 @@ bool lass_wino4_supported(ConvKind kind, const ConvArgs& p) {
             return p.pre_w && p.pre_b && p.Cin == 32;
         case CONV2_IDENT_PRE:  // encoder_block1.conv2: residual = pre_conv(x0), fused 2x2 avg-pool
             return p.res && p.pre_w && p.pre_b && p.N == 32 && p.Nw == 32 && (!p.pool_out || p.pool_h == 2);
+        case CONV2_IDENT:  // conv2 + residual from p.res (the shortcut layers whose 1x1 conv runs in pw_gemm.hip), fused 2x2 avg-pool
+            return p.res && !p.mask_re && (!p.pool_out || p.pool_h == 2);
         case CONV2_SHORTCUT:  // conv2 + 1x1 shortcut (+ fused 2x2 avg-pool, or decoder_block6's fused output head)
             if (!(p.in2 && p.w2 && p.bias && p.Cin2 % 16 == 0 && (!p.pool_out || p.pool_h == 2))) return false;
             if (p.mask_re)
@@ -509,6 +535,8 @@ hipError_t lass_launch_wino4(ConvKind kind, const ConvArgs& p, hipStream_t strea
         case CONV1_ACT_PRE:
             if (!p.pro_scale || !p.pro_shift || !p.epi_scale || !p.epi_shift) return hipErrorInvalidValue;
             return kind == CONV1_ACT ? launch_wino4<F_PRO | F_EPIACT>(p, stream) : launch_wino4<F_PRO | F_EPIACT | F_PRECONV>(p, stream);
+        case CONV2_IDENT:
+            return launch_wino4<F_RES>(p, stream);
         case CONV2_IDENT_PRE:
             return launch_wino4<F_RES | F_RESPRE>(p, stream);
         case CONV2_SHORTCUT:
