@@ -126,6 +126,11 @@ int lass_graph_stats(const lass_ctx* ctx, long* captures, long* replays);
 /* Turns graph replay off (0: every call launches its kernels eagerly) or back on (cached graphs are replayed again).
  * A measurement switch - bench.py times both forms of the same step - with no effect on results. */
 int lass_set_graph_replay(lass_ctx* ctx, int enabled);
+/* f32: the 3x3 convs at the 32-frame x 16-bin level run as split-K Winograd F(4x4,3x3) launches with a fixed number of
+ * splits (4, whatever the batch: a clip's bits do not depend on its batch).  An internal hook for the tests: splits = 1, 2
+ * or 4 forces that number on the stage calls and lass_separate alike (1 = the unsplit kernels), 0 restores the default.  Query lass_workspace_bytes again
+ * afterwards: the partial sums live in the workspace. */
+int lass_set_wino4_splits(lass_ctx* ctx, int splits);
 
 /* The same path from a PRECOMPUTED analysis of the mixtures, as the reference's multi-STFT wrapper takes it
  * (resunet_with_multistft.py:233-241: input_dict["stft_mixture_mag" / "_cos" / "_sin"][win]; producer:

@@ -175,20 +175,31 @@ def conv_layer_table(t_pad: int, f: int = F_CROP) -> List[Dict]:
 def wino4_routed(rows: List[Dict], min_cin: int = 32) -> set:
     """Names of the 3x3 rows of `conv_layer_table` that the f32 path runs as Winograd F(4x4,3x3) (csrc/wino4.hip; 36 instead
     of 144 MFMA multiplies per 4x4 output tile and (cin, cout) pair) - a mirror of the dispatch in csrc/api.hip
-    (run_resblock) and lass_wino4_supported: at least `min_cin` input channels (LASS_WINO4, default 32; 0 = none), images
-    whose width is a multiple of 32 and that tile into 8 x 64 or 16 x 32 pixel blocks; conv1 of every block, conv2 of the
-    blocks with a 1x1 shortcut (decoder_block6's with the fused output head) and of encoder_block1 (residual = pre_conv(x0)).
-    The identity blocks at 16 / 8 bins (encoder_block6, conv_block7a) and decoder_block1/2's narrow levels stay F(2x2,3x3)."""
+    (run_resblock, wino4_splits) and lass_wino4_supported: at least `min_cin` input channels (LASS_WINO4, default 32; 0 =
+    none).  Images whose width is a multiple of 32 and that tile into 8 x 64 or 16 x 32 pixel blocks: conv1 of every block,
+    conv2 of the blocks with a 1x1 shortcut (decoder_block6's with the fused output head) and of encoder_block1 (residual =
+    pre_conv(x0)).  Images that tile only into 32 x 16 blocks (16 bins under a 32-multiple of frames: encoder_block6 and
+    decoder_block1 of a 10 s clip): both convs of the block, split-K, the 1x1 shortcut then running in pw_gemm.hip.  At any
+    other frame count those two blocks, and always the 8-bin conv_block7a, stay F(2x2,3x3)."""
     if min_cin <= 0:
         return set()
     with_shortcut = {r["name"].rsplit(".", 1)[0] for r in rows if r["name"].endswith(".shortcut")}
+    block_cin = {r["name"].rsplit(".", 1)[0]: r["cin"] for r in rows if r["name"].endswith(".conv1")}
     out = set()
     for r in rows:
         if r["kind"] != "3x3":
             continue
         block, conv = r["name"].rsplit(".", 1)
         geom = r["w"] % 32 == 0 and ((r["w"] % 64 == 0 and r["h"] % 8 == 0) or r["h"] % 16 == 0)
-        if not (geom and r["cin"] >= min_cin and r["cin"] % 8 == 0 and r["cout"] % 32 == 0):
+        narrow = r["w"] % 32 == 16 and r["h"] % 32 == 0  # lass_wino4_narrow
+        if not ((geom or narrow) and r["cin"] >= min_cin and r["cin"] % 8 == 0 and r["cout"] % 32 == 0):
+            continue
+        if narrow:
+            # run_resblock takes this route from the F(2x2,3x3) one (lass_wino_supported: 16 bins, 64-cout groups, 16-channel
+            # chunks), for conv1 and conv2 of a block together (wino4_splits looks at the block's cin and cout)
+            cin1 = block_cin.get(block, r["cin"])
+            if r["w"] == 16 and r["cout"] % 64 == 0 and cin1 % 16 == 0 and min(cin1, r["cout"]) >= min_cin and not block.startswith("encoder_block1"):
+                out.add(r["name"])
             continue
         if conv == "conv1":
             out.add(r["name"])

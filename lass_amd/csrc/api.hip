@@ -107,6 +107,9 @@ struct lass_ctx {
     int compute_mode = LASS_COMPUTE_F32;
     int wino4_mincin = 32;     // 3x3 convs with at least that many input channels (and >= 32-wide images) run as Winograd
                                // F(4x4,3x3) (wino4.hip); LASS_WINO4=<min Cin>, 0 = off (F(2x2,3x3) everywhere)
+    int ksplit_force = 0;      // lass_set_wino4_splits: 0 = the route's split-K factor on the 32 x 16 Winograd blocks (kWino4Splits), else 1 / 2 / 4
+    float* stage_part = nullptr;   // split-K partials of the stage calls (lass_convblock, lass_encoder_block), grown on demand;
+    size_t stage_part_floats = 0;  // lass_separate takes its own from the caller's workspace (Plan::kpart)
     bool fuse_catb = true;  // bf16 mode: decoder concats as blocked bf16 copies (LASS_FUSE_CATB=0: f32 concat)
     bool fuse_block = true;  // bf16 mode: encoder_block1 as one kernel, intermediate in LDS (LASS_FUSE_BLOCK=0: two launches)
     bool fuse_up = true;    // bf16 mode: decoder_block6's transposed conv inside its fused kernel (LASS_FUSE_UP=0: its own launch)
@@ -437,7 +440,23 @@ struct BlockFusions {
     const Site* act_out = nullptr;          // bf16: the output as ONE blocked tensor with this site's prologue applied
     const CatCopies* pool_copies = nullptr; // bf16: the pooled output as two blocked copies for the next encoder block
     const UpFuse* up = nullptr;             // bf16, decoder_block6: its transposed conv inside the block's fused kernel
+    float* kpart = nullptr;                 // f32, the 32 x 16 Winograd blocks: split-K partials, wino4_split_floats() of them
 };
+
+// f32, the 3x3 convs of a block whose images tile only into 32-row x 16-column F(4x4,3x3) blocks (lass_wino4_narrow: the 16-bin
+// level under a 32-multiple of frames): a clip plane is ONE block, so a launch has B * cout / 32 workgroups for the 512 slots
+// (256 CUs x 2) - 96 per half-batch branch of the replayed B = 16 graph.  The input-channel loop is dealt to 4 workgroups each
+// (48-96 chunks -> 12-24).  The factor is a constant of the route and NOT a function of B: the summation order of a clip must not
+// depend on the batch it arrives in (half-batches, ragged tails and single clips are bit-identical - the suite pins that).
+// 0: the block does not take this route.
+constexpr int kWino4Splits = 4;
+int wino4_splits(const lass_ctx* c, const ResBlock& rb, int B, int H, int W) {
+    (void)B;
+    if (c->compute_mode != LASS_COMPUTE_F32 || c->wino4_mincin <= 0 || !lass_wino4_narrow(H, W) || rb.width % 32 != 16) return 0;
+    if (rb.cin < c->wino4_mincin || rb.cout < c->wino4_mincin || rb.cin % 8 != 0 || rb.cout % 32 != 0) return 0;
+    return c->ksplit_force ? c->ksplit_force : kWino4Splits;
+}
+size_t wino4_split_floats(const ResBlock& rb, int S, int B, int H, int W) { return S > 1 ? (size_t)S * B * rb.cout * H * W : 0; }
 
 // f32: the shortcut layers with at least this many input channels run their 1x1 conv in pw_gemm.hip.  Shallower ones (K = 32 ...
 // 128: encoder_block2-4, decoder_block5-6) are byte-bound there - writing bias + Wsc x and reading it back costs more than
@@ -475,12 +494,27 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
     // the direct f32 kernels (conv.hip) have no *_PRE kinds: they refuse them
     const ConvKind k1 = x0 ? CONV1_ACT_PRE : CONV1_ACT, k2 = x0 ? CONV2_IDENT_PRE : CONV2_IDENT;
     const bool wino1 = !bf1 && rb.u1 && lass_wino_supported(p);
+    // F(4x4,3x3) images of a 16-bin level serve the 32 x 16 blocks only, those of the wider levels the wider blocks only
+    const int ksplit = bf1 || x0 ? 0 : wino4_splits(c, rb, B, H, W);
+    const bool w4_geom = rb.width % 32 == 0 ? !lass_wino4_narrow(H, W) : ksplit > 0;
+    if (ksplit > 1) {
+        if (!f.kpart) return fail(c, LASS_ERR_STATE, "split-K needs its partial workspace");
+        const auto overlaps = [&](const float* a, size_t a_n, const float* b, long b_bs, long b_n) {
+            return a < b + (size_t)(B - 1) * b_bs + b_n && b < a + a_n;
+        };
+        const size_t kn = wino4_split_floats(rb, ksplit, B, H, W);
+        if (overlaps(f.kpart, kn, x, x_bs, rb.cin * HW) || overlaps(f.kpart, kn, a2, rb.cout * HW, rb.cout * HW) ||
+            overlaps(f.kpart, kn, out, out_bs, rb.cout * HW))
+            return fail(c, LASS_ERR_STATE, "the split-K partials must not overlap the block's input, intermediate or output");
+    }
+    Wino4Split sk;  // both convs of the block
+    if (ksplit > 1) { sk.n = ksplit; sk.part = f.kpart; }
     auto launch_conv1 = [&]() -> int {
         ProfScope ps(c, st, P_CONV3X3);
         if (bf1)
             HIP_TRY(c, lass_launch_conv_bf16(k1, p, st));
-        else if (wino1 && rb.u1f && lass_wino4_supported(k1, p))
-            HIP_TRY(c, lass_launch_wino4(k1, p, st));
+        else if (wino1 && rb.u1f && w4_geom && lass_wino4_supported(k1, p, sk))
+            HIP_TRY(c, lass_launch_wino4(k1, p, st, sk));
         else if (wino1)
             HIP_TRY(c, lass_launch_wino(k1, p, st));
         else
@@ -491,7 +525,7 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
     q.in = a2; q.in_bs = rb.cout * HW; q.Cin = rb.cout; q.w = rb.w2; q.Nw = rb.cout; q.N = rb.cout;
     q.out = out; q.out_bs = out_bs; q.B = B; q.H = H; q.W = W;
     q.pool_out = f.pool_out; q.pool_h = f.pool_h; q.pool_bs = f.pool_bs;
-    q.w_wino = rb.u2; q.w2_wino = rb.usc; q.w_wino4 = rb.u2f;
+    q.w_wino = rb.u2; q.w2_wino = rb.usc; q.w_wino4 = w4_geom ? rb.u2f : nullptr;
     if (const MaskHead* mh = f.head) {  // the block output is consumed by the fused head and never written
         q.out = nullptr;
         q.mask_w = rawp(c, "base.after_conv.weight"); q.mask_b = rawp(c, "base.after_conv.bias");
@@ -563,8 +597,9 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
     // tile (pw_gemm.hip), written into the block's output slot; conv2 then adds its result to that slot in place (wino4.hip,
     // CONV2_IDENT).  Fused into conv2's 32-cout workgroups instead, every one of the Cout / 32 workgroups of a tile fetches the
     // whole block input again.  The other shortcut layers (and decoder_block6's output head) keep the fused phase.
+    // (the 32 x 16 blocks have no fused shortcut phase at all - it would be serial work behind a split-K sum: decoder_block1)
     const bool sc_gemm = c->compute_mode == LASS_COMPUTE_F32 && !bf2 && rb.cin != rb.cout && !f.head && rb.cin >= kShortcutGemmMinCin &&
-                         wino2 && rb.u2f && lass_wino4_supported(CONV2_SHORTCUT, q) && lass_pw_gemm_supported(CONV2_SHORTCUT, q);
+                         wino2 && q.w_wino4 && (ksplit > 0 || lass_wino4_supported(CONV2_SHORTCUT, q)) && lass_pw_gemm_supported(CONV2_SHORTCUT, q);
     if (sc_gemm) {
         const auto overlaps = [&](const float* a, long a_bs, long a_n, const float* b, long b_bs, long b_n) {
             return a < b + (size_t)(B - 1) * b_bs + b_n && b < a + (size_t)(B - 1) * a_bs + a_n;
@@ -580,13 +615,13 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
         ConvArgs r = q;
         r.in2 = nullptr; r.in2_bs = 0; r.Cin2 = 0; r.w2 = nullptr; r.bias = nullptr;
         r.res = out; r.res_bs = out_bs;
-        if (!lass_wino4_supported(CONV2_IDENT, r)) return fail(c, LASS_ERR_STATE, "conv2 with the shortcut as residual");
-        HIP_TRY(c, lass_launch_wino4(CONV2_IDENT, r, st));
+        if (!lass_wino4_supported(CONV2_IDENT, r, sk)) return fail(c, LASS_ERR_STATE, "conv2 with the shortcut as residual");
+        HIP_TRY(c, lass_launch_wino4(CONV2_IDENT, r, st, sk));
     } else if (rb.cin == rb.cout) {
         if (bf2)
             HIP_TRY(c, lass_launch_conv_bf16(k2, q, st));
-        else if (wino2 && x0 && rb.u2f && lass_wino4_supported(k2, q))
-            HIP_TRY(c, lass_launch_wino4(k2, q, st));
+        else if (wino2 && (x0 || ksplit > 0) && q.w_wino4 && lass_wino4_supported(k2, q, sk))  // (ksplit: encoder_block6, 1 x 2 pool)
+            HIP_TRY(c, lass_launch_wino4(k2, q, st, sk));
         else if (wino2)
             HIP_TRY(c, lass_launch_wino(k2, q, st));
         else
@@ -594,7 +629,7 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
     } else {
         if (bf2)
             HIP_TRY(c, lass_launch_conv_bf16(CONV2_SHORTCUT, q, st));
-        else if (wino2 && rb.u2f && lass_wino4_supported(CONV2_SHORTCUT, q))
+        else if (wino2 && q.w_wino4 && lass_wino4_supported(CONV2_SHORTCUT, q))
             HIP_TRY(c, lass_launch_wino4(CONV2_SHORTCUT, q, st));
         else if (wino2)
             HIP_TRY(c, lass_launch_wino(CONV2_SHORTCUT, q, st));
@@ -646,6 +681,8 @@ struct Plan {
     int B, L, T, Tp;
     size_t total = 0;
     size_t mag, cosv, sinv, x0[kMaxBranches], shift, a2, cat[6], pool[6], center, decout[6], oreal, oimag;
+    size_t kpart = 0;  // split-K partials of the 32 x 16 Winograd blocks (one slot: the launches of a plan run in stream order)
+    bool has_kpart = false;
     int eh[7], ew[7];  // encoder block spatial sizes
 };
 
@@ -692,6 +729,18 @@ int make_plan(const lass_ctx* c, int B, int L, Plan* pl) {
     }
     pl->a2 = bump(t, a2max);
     pl->oreal = bump(t, spec); pl->oimag = bump(t, spec);
+    // (a half-batch plan has its own slot: the two branches of the replayed graph never share partials)
+    size_t kmax = 0;
+    for (int i = 1; i < 7; ++i) {
+        const ResBlock& rb = trunk_block(c, i);
+        kmax = std::max(kmax, wino4_split_floats(rb, wino4_splits(c, rb, B, pl->eh[i], pl->ew[i]), B, pl->eh[i], pl->ew[i]));
+    }
+    for (int d = 0; d < 6; ++d) {
+        const ResBlock& rb = c->dec[d];
+        kmax = std::max(kmax, wino4_split_floats(rb, wino4_splits(c, rb, B, pl->eh[5 - d], pl->ew[5 - d]), B, pl->eh[5 - d], pl->ew[5 - d]));
+    }
+    pl->has_kpart = kmax > 0;
+    if (kmax) pl->kpart = bump(t, kmax);
     return 0;
 }
 
@@ -720,6 +769,21 @@ void drop_graphs(lass_ctx* c) {
 
 // A batch is split into two overlapping half-batches when it is large enough for each half to fill the GPU on its own
 bool split_halves(const lass_ctx* c, int B) { return c->split_batch > 0 && !c->profiling && B >= 8 && (B % 2) == 0; }
+
+// Stage calls have no workspace plan: their split-K partials live in a buffer of the context that grows on demand (the call must
+// not be under stream capture when it does).  hipFree waits for the launches that still use the old buffer.
+int stage_kpart(lass_ctx* c, const ResBlock& rb, int B, int H, int W, BlockFusions* f) {
+    const size_t need = wino4_split_floats(rb, wino4_splits(c, rb, B, H, W), B, H, W);
+    if (need > c->stage_part_floats) {
+        if (c->stage_part) HIP_TRY(c, hipFree(c->stage_part));
+        c->stage_part = nullptr;
+        c->stage_part_floats = 0;
+        HIP_TRY(c, hipMalloc((void**)&c->stage_part, need * sizeof(float)));
+        c->stage_part_floats = need;
+    }
+    if (need) f->kpart = c->stage_part;
+    return 0;
+}
 
 const ResBlock* find_block(const lass_ctx* c, const std::string& prefix) {
     for (const auto& rb : c->enc) if (rb.prefix == prefix) return &rb;
@@ -840,6 +904,7 @@ int lass_destroy(lass_ctx* c) {
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     (void)hipFree(c->tw2k);
+    (void)hipFree(c->stage_part);
     delete c;
     return 0;
 }
@@ -949,16 +1014,17 @@ int lass_finalize(lass_ctx* c, int compute_mode) {
                 return LASS_ERR_HIP;
             HIP_TRY(c, lass_launch_wino_weights(w1, rb.cout, rb.cin, rb.u1, st));
             HIP_TRY(c, lass_launch_wino_weights(w2, rb.cout, rb.cout, rb.u2, st));
-            // (F(4x4,3x3) tiles need 32-bin multiples - lass_wino4_supported - so the 16-/8-bin levels get no images: 106 MB saved)
-            const bool w4_level = rb.width % 32 == 0;
-            if (w4_level && c->wino4_mincin > 0 && rb.cin >= c->wino4_mincin && rb.cin % 8 == 0 && rb.cout % 32 == 0) {
+            // (the 32 x 16 blocks of the 16-bin level run both convs of a block, identity residual or not: + 106 MB of images for
+            // encoder_block6 and decoder_block1; the 8-bin level tiles into no F(4x4,3x3) block and gets none)
+            const bool w4_level = rb.width % 32 == 0, w4_narrow = rb.width % 32 == 16;
+            if ((w4_level || w4_narrow) && c->wino4_mincin > 0 && rb.cin >= c->wino4_mincin && rb.cin % 8 == 0 && rb.cout % 32 == 0) {
                 if (dev_alloc(c, &rb.u1f, (size_t)36 * rb.cout * rb.cin)) return LASS_ERR_HIP;
                 HIP_TRY(c, lass_launch_wino4_weights(w1, rb.cout, rb.cin, rb.u1f, st));
             }
-            // conv2: the blocks with a 1x1 shortcut, and encoder_block1 (32 -> 32, residual = pre_conv(x0)); the identity blocks
-            // at the bottom of the U-Net (16 / 8 bins) stay with wino.hip
-            if (w4_level && c->wino4_mincin > 0 && rb.cout >= c->wino4_mincin && (rb.cin != rb.cout || rb.cout == kPreCh) && rb.cout % 32 == 0 &&
-                rb.cin % 8 == 0) {
+            // conv2: the blocks with a 1x1 shortcut, and encoder_block1 (32 -> 32, residual = pre_conv(x0)); at the 16-bin level
+            // every block (run_resblock uses these images only where wino4_splits admits the shape)
+            if (c->wino4_mincin > 0 && rb.cout >= c->wino4_mincin && rb.cout % 32 == 0 && rb.cin % 8 == 0 &&
+                (w4_level ? rb.cin != rb.cout || rb.cout == kPreCh : w4_narrow && rb.cin >= c->wino4_mincin)) {
                 if (dev_alloc(c, &rb.u2f, (size_t)36 * rb.cout * rb.cout)) return LASS_ERR_HIP;
                 HIP_TRY(c, lass_launch_wino4_weights(w2, rb.cout, rb.cout, rb.u2f, st));
             }
@@ -1148,7 +1214,9 @@ int lass_convblock(lass_ctx* c, const char* prefix, const float* x, int B, int H
     const ResBlock* rb = find_block(c, prefix);
     if (!rb) return fail(c, LASS_ERR_ARG, std::string("lass_convblock: unknown block '") + prefix + "'");
     const long HW = (long)H * W;
-    return run_resblock(c, *rb, x, rb->cin * HW, B, H, W, shift, scratch, y, rb->cout * HW, (hipStream_t)stream);
+    BlockFusions f;
+    if ((r = stage_kpart(c, *rb, B, H, W, &f))) return r;
+    return run_resblock(c, *rb, x, rb->cin * HW, B, H, W, shift, scratch, y, rb->cout * HW, (hipStream_t)stream, f);
 }
 
 int lass_encoder_block(lass_ctx* c, const char* name, const float* x, int B, int H, int W, const float* shift, float* y,
@@ -1169,6 +1237,7 @@ int lass_encoder_block(lass_ctx* c, const char* name, const float* x, int B, int
         hipStream_t st = (hipStream_t)stream;
         BlockFusions f;
         if (fuse) { f.pool_out = pool; f.pool_h = e.dh; }
+        if ((r = stage_kpart(c, rb, B, H, W, &f))) return r;
         r = run_resblock(c, rb, x, rb.cin * HW, B, H, W, shift, scratch, y, rb.cout * HW, st, f);
         if (r) return r;
         if (pooled && !fuse) HIP_TRY(c, lass_launch_pool(y, rb.cout * HW, B, rb.cout, H, W, e.dh, e.dw, pool, st));
@@ -1412,6 +1481,7 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
             if (i < 5 && use_cb[5 - i]) f.skip_out = &cb[5 - i];
             if (i >= 1 && i <= 4 && use_pc[i - 1]) f.cat_in = &pc[i - 1];
             if (i < 4 && use_pc[i]) f.pool_copies = &pc[i];
+            if (pl.has_kpart) f.kpart = F(pl.kpart);
             r = run_resblock(c, rb, x, rb.cin * HW, B, H, W, shift, F(pl.a2), o, o_bs, st, f);
             if (r) return r;
         }
@@ -1445,6 +1515,7 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
         if (use_cb[d]) f.cat_in = &cb[d];
         const MaskHead head{mag_m, cos_m, sin_m, F(pl.oreal), F(pl.oimag), T, g.nbins};
         if (d == 5) f.head = &head;
+        if (pl.has_kpart) f.kpart = F(pl.kpart);
         r = run_resblock(c, rb, F(pl.cat[d]), rb.cin * HW, B, H, W, shift, F(pl.a2), F(pl.decout[d]), rb.cout * HW, st, f);
         if (r) return r;
         x = F(pl.decout[d]);
@@ -1577,6 +1648,13 @@ int lass_separate(lass_ctx* c, const float* mixture, const float* condition, flo
 int lass_set_graph_replay(lass_ctx* c, int enabled) {
     if (!c) return LASS_ERR_ARG;
     c->use_graph = enabled != 0;  // captured graphs stay cached: switching back on replays them again
+    return 0;
+}
+
+int lass_set_wino4_splits(lass_ctx* c, int splits) {
+    if (!c || (splits != 0 && splits != 1 && splits != 2 && splits != 4)) return fail(c, LASS_ERR_ARG, "lass_set_wino4_splits: 0, 1, 2 or 4");
+    c->ksplit_force = splits;
+    ++c->gen;  // captured graphs hold the launches of the previous choice (and workspace sizes follow it)
     return 0;
 }
 

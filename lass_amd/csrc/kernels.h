@@ -93,6 +93,17 @@ struct ConvArgs {
                                // (block_coords, wino_common.h)
 };
 
+// wino4.hip: images that tile only into 32-row x 16-column blocks (the 16-bin level of a clip whose frame count at that level
+// is a multiple of 32); the 8 x 64 / 16 x 32 blocks take every geometry they fit
+inline bool lass_wino4_narrow(int H, int W) { return W % 32 == 16 && H % 32 == 0; }
+// Split-K on those blocks: the input-channel loop is dealt to n workgroups per (block, cout group, clip); each stores its partial
+// of the conv sum, [n][B][N][H][W] dense in part, and a combine launch sums them in split order and applies the epilogue.
+// (Not part of ConvArgs: the kernels that take only ConvArgs keep their argument block, and with it their compiled code.)
+struct Wino4Split {
+    int n = 1;
+    float* part = nullptr;
+};
+
 enum ConvKind { CONV1_ACT = 0, CONV2_IDENT = 1, CONV2_SHORTCUT = 2, TCONV_ACT = 3, CONV1_ACT_PRE = 4, CONV2_IDENT_PRE = 5 };
 
 hipError_t lass_launch_conv(ConvKind kind, const ConvArgs& p, hipStream_t stream);
@@ -105,8 +116,8 @@ hipError_t lass_launch_wino_shortcut_weights(const float* w, int Cout, int Cin, 
 
 // ---- wino4.hip (Winograd F(4x4,3x3): 36 instead of 64 MFMA multiplies per 16 outputs; W % 32 == 0) ---------------------------
 // CONV2_IDENT: conv2 + a residual read from res (which may be `out` itself: every element is read and written by one lane)
-bool lass_wino4_supported(ConvKind kind, const ConvArgs& p);
-hipError_t lass_launch_wino4(ConvKind kind, const ConvArgs& p, hipStream_t stream);
+bool lass_wino4_supported(ConvKind kind, const ConvArgs& p, const Wino4Split& sk = Wino4Split());
+hipError_t lass_launch_wino4(ConvKind kind, const ConvArgs& p, hipStream_t stream, const Wino4Split& sk = Wino4Split());
 hipError_t lass_launch_wino4_weights(const float* w, int Cout, int Cin, float* U, hipStream_t stream);  // w (Cout, Cin, 3, 3)
 
 // ---- pw_gemm.hip (f32 pointwise GEMMs with a 128-cout workgroup tile; H*W % 4 == 0, N % 128 == 0, K % 32 == 0) ------------
