@@ -291,6 +291,57 @@ int lass_text_workspace_bytes(const lass_text_ctx* ctx, int N, int S, size_t* by
 int lass_text_encode(lass_text_ctx* ctx, const int64_t* input_ids, const int64_t* attention_mask, int N, int S,
                      float* out, float* pooler_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- CLAP audio encoder (query by example) ------------------------------------------------------------------------ */
+
+/* The audio tower of the query encoder: clips -> (B,512) L2-normalised float32 embeddings.
+ * Replaces: CLAP_Encoder.get_query_embed(modality="audio") (models/clap_encoder.py:50-76) for amodel "HTSAT-base" without
+ * fusion: resample 32 -> 48 kHz (polyphase 3/2 FIR, torchaudio's published defaults), repeat-pad to 480 000 samples,
+ * log-mel (n_fft 1024, hop 480, periodic Hann, reflect; 64 slaney bands 50 .. 14000 Hz; 10 log10(max(p, 1e-10))), bn0,
+ * bicubic 1001 -> 1024 frames + fold to 256 x 256 + 4x4 patch embedding, the Swin stages (8 x 8 windows, shifted in odd
+ * blocks, relative-position bias, pre-LN, exact-erf GELU, PatchMerging), final LayerNorm, token mean ("embedding"),
+ * Linear -> ReLU -> Linear(512), F.normalize (CLAP/open_clip/htsat.py:1012-1149, model.py:566-570, 754-781).
+ * f32 throughout, contractions on the f32 MFMA.  Row n of the result is what the reference computes for clip n alone.
+ * A separate handle with the conventions of lass_text_*: return codes, caller's stream and workspace, no allocation in
+ * the encode calls, no CPU fallback (without a gfx950 device lass_audioq_create fails). */
+typedef struct lass_audioq_ctx lass_audioq_ctx;
+
+/* Optional device outputs of the encode calls; a NULL member is not written.  wave48k (B, ceil(1.5 L)) is written by
+ * lass_audioq_encode_wave32k only; logmel (B,1001,64) is after bn0; tokens (B,4096,128) after the patch embedding's
+ * LayerNorm; stage[i] is stage i's output (after its PatchMerging; the last stage's before the final LayerNorm);
+ * embedding (B, 128 * 2^(stages-1)) is the token mean. */
+typedef struct lass_audioq_taps {
+    float* wave48k;
+    float* logmel;
+    float* tokens;
+    float* stage[4];
+    float* embedding;
+} lass_audioq_taps;
+
+int lass_audioq_create(lass_audioq_ctx** out, int device_id);
+int lass_audioq_destroy(lass_audioq_ctx* ctx);
+/* Last error of this context (or of the failed lass_audioq_create when ctx == NULL).  Never NULL. */
+const char* lass_audioq_last_error(const lass_audioq_ctx* ctx);
+/* Upload one f32 tensor (host or device pointer), key relative to the CLAP model: "audio_branch.bn0.{weight,bias,
+ * running_mean,running_var}", "audio_branch.patch_embed.*", "audio_branch.layers.<i>.blocks.<j>.*",
+ * "audio_branch.layers.<i>.downsample.*", "audio_branch.norm.*", "audio_projection.{0,2}.*" - the checkpoint's
+ * `query_encoder.model.<key>`.  Any other key (the classification heads and the derived buffers included) is
+ * LASS_ERR_ARG.  Stage and block counts are taken from the indices present. */
+int lass_audioq_set_param(lass_audioq_ctx* ctx, const char* name, const void* data, const int64_t* shape, int ndim);
+/* Checks presence and shape of every parameter of the stages found (embedding width 128, doubling per stage), folds bn0,
+ * builds the resampler taps, window, twiddles, mel filter and bicubic table.  Call again after any lass_audioq_set_param. */
+int lass_audioq_finalize(lass_audioq_ctx* ctx);
+/* Stages of a finalized context (0 before lass_audioq_finalize). */
+int lass_audioq_stages(const lass_audioq_ctx* ctx);
+/* Workspace bytes either encode call needs for B clips. */
+int lass_audioq_workspace_bytes(const lass_audioq_ctx* ctx, int B, size_t* bytes);
+/* wave (B,L) f32 DEVICE pointer at 48 kHz, 1 <= L <= 480 000; lengths (B) int HOST pointer or NULL (every clip L samples):
+ * clip n is wave[n][0 .. lengths[n]) -> out (B,512) f32.  All argument checks run before anything is launched. */
+int lass_audioq_encode_wave48k(lass_audioq_ctx* ctx, const float* wave, const int* lengths, int B, int L, float* out,
+                               const lass_audioq_taps* taps, void* workspace, size_t workspace_bytes, void* stream);
+/* The same from 32 kHz input, 1 <= L <= 320 000 (10 s), with the resampler in front. */
+int lass_audioq_encode_wave32k(lass_audioq_ctx* ctx, const float* wave, const int* lengths, int B, int L, float* out,
+                               const lass_audioq_taps* taps, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- instrumentation ---------------------------------------------------------------------------------------- */
 
 /* When enabled, lass_separate brackets each kernel class with HIP events on `stream` (costs a few us per launch).

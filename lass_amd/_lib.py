@@ -61,6 +61,17 @@ SYMBOLS = [
     ("lass_text_workspace_bytes", c_int, [c_void_p, c_int, c_int, POINTER(c_size_t)]),
     ("lass_text_encode", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                  c_void_p]),
+    ("lass_audioq_create", c_int, [POINTER(c_void_p), c_int]),
+    ("lass_audioq_destroy", c_int, [c_void_p]),
+    ("lass_audioq_last_error", c_char_p, [c_void_p]),
+    ("lass_audioq_set_param", c_int, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int]),
+    ("lass_audioq_finalize", c_int, [c_void_p]),
+    ("lass_audioq_stages", c_int, [c_void_p]),
+    ("lass_audioq_workspace_bytes", c_int, [c_void_p, c_int, POINTER(c_size_t)]),
+    ("lass_audioq_encode_wave48k", c_int, [c_void_p, c_void_p, POINTER(c_int), c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                           c_size_t, c_void_p]),
+    ("lass_audioq_encode_wave32k", c_int, [c_void_p, c_void_p, POINTER(c_int), c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                           c_size_t, c_void_p]),
     ("lass_set_profiling", c_int, [c_void_p, c_int]),
     ("lass_profile_count", c_int, [c_void_p]),
     ("lass_profile_get", c_int, [c_void_p, c_int, POINTER(c_char_p), POINTER(c_double), POINTER(c_int)]),

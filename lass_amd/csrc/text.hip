@@ -28,14 +28,7 @@ namespace {
 constexpr int kHid = 768, kHeads = 12, kDh = 64, kFF = 3072, kProj = 512, kMaxLen = 512, kPad = 1;
 constexpr float kLnEps = 1e-5f;  // roberta-base config.json layer_norm_eps (HF RobertaConfig() defaults to 1e-12)
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ float wave_sum(float v) {
-    // xor butterfly: every lane ends with the same bits
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
+#include "f32_gemm.h"
 
 __device__ __forceinline__ int wave_isum(int v) {
 #pragma unroll
@@ -103,69 +96,6 @@ __global__ __launch_bounds__(256) void k_ln(float* __restrict__ h, int M, const 
 #pragma unroll
     for (int j = 0; j < 12; ++j) x[j] = row[lane + 64 * j];
     ln_row(x, g, b, row, lane);
-}
-
-enum Epi { EPI_BIAS = 0, EPI_GELU = 1, EPI_RESID = 2, EPI_TANH = 3, EPI_RELU = 4 };
-
-constexpr int BM = 64, BN = 64, BK = 16, LDT = BM + 32;  // +32: the two k rows one MFMA reads land in different banks
-
-// Y[M,N] = epi(X[M,K] . W[N,K]^T + bias), row-major, N % 64 == 0, K % 16 == 0.  EPI_RESID adds Y's previous value
-// (the residual stream, updated in place: each element is read and written by the same lane).  256 threads = 4 waves,
-// each a 32x32 quarter of the 64x64 tile on v_mfma_f32_32x32x2_f32 (exact f32, k-ordered FMA chain).  One tile shape for
-// every M, so a row's result does not depend on M or on where the row sits.
-template <int EPI>
-__global__ __launch_bounds__(256) void k_gemm(const float* __restrict__ X, const float* __restrict__ W,
-                                              const float* __restrict__ bias, float* Y, int M, int N, int K) {
-    __shared__ __attribute__((aligned(16))) float As[BK * LDT], Bs[BK * LDT];
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const int wm = w & 1, wn = w >> 1;
-    const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
-    const int lr = t >> 2, lc = (t & 3) * 4;  // this thread's staging row and k quad
-    const bool xrow = m0 + lr < M;
-    const float* xp = X + (size_t)(xrow ? m0 + lr : 0) * K + lc;
-    const float* wp = W + (size_t)(n0 + lr) * K + lc;
-    float4 ra = xrow ? *(const float4*)xp : make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 rb = *(const float4*)wp;
-    f32x16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    const int ai = wm * 32 + (lane & 31), bi = wn * 32 + (lane & 31), kh = lane >> 5;
-    for (int k0 = 0; k0 < K; k0 += BK) {
-        __syncthreads();
-        As[(lc + 0) * LDT + lr] = ra.x;
-        As[(lc + 1) * LDT + lr] = ra.y;
-        As[(lc + 2) * LDT + lr] = ra.z;
-        As[(lc + 3) * LDT + lr] = ra.w;
-        Bs[(lc + 0) * LDT + lr] = rb.x;
-        Bs[(lc + 1) * LDT + lr] = rb.y;
-        Bs[(lc + 2) * LDT + lr] = rb.z;
-        Bs[(lc + 3) * LDT + lr] = rb.w;
-        __syncthreads();
-        if (k0 + BK < K) {
-            ra = xrow ? *(const float4*)(xp + k0 + BK) : make_float4(0.f, 0.f, 0.f, 0.f);
-            rb = *(const float4*)(wp + k0 + BK);
-        }
-#pragma unroll
-        for (int kk = 0; kk < BK / 2; ++kk) {
-            const float a = As[(2 * kk + kh) * LDT + ai];
-            const float bb = Bs[(2 * kk + kh) * LDT + bi];
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bb, acc, 0, 0, 0);
-        }
-    }
-    const int n = n0 + wn * 32 + (lane & 31);
-    const float bn = bias[n];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const int m = m0 + wm * 32 + (i & 3) + 8 * (i >> 2) + 4 * kh;
-        if (m >= M) continue;
-        float v = acc[i] + bn;
-        float* yp = Y + (size_t)m * N + n;
-        if (EPI == EPI_GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
-        if (EPI == EPI_RESID) v = v + *yp;
-        if (EPI == EPI_TANH) v = tanhf(v);
-        if (EPI == EPI_RELU) v = fmaxf(v, 0.f);
-        *yp = v;
-    }
 }
 
 constexpr int AQ = 64;  // queries per workgroup (one per lane) and keys per LDS block

@@ -157,3 +157,48 @@ def make_clap_text_state_dict(seed: int = SEED + 8, layers: int = 12) -> Dict[st
         v = rng.standard_normal(shape, dtype=np.float32)
         sd[name] = (1.0 + 0.1 * v if kind == "g" else 0.02 * v).astype(np.float32)
     return sd
+
+
+def make_clap_audio_state_dict(seed: int = SEED + 10, depths=(2, 2, 12, 2)) -> Dict[str, np.ndarray]:
+    """Seeded weights of the CLAP audio tower (HTSAT + projection), keyed as lass_amd.clap_audio.ClapAudioEncoder's
+    state_dict (`model.audio_branch.*`, `model.audio_projection.{0,2}.*`; the derived buffers are left to the module):
+    float32 from numpy PCG64, matrices and biases N(0, 0.02), relative-position tables N(0, 0.5), norm weights
+    1 + N(0, 0.1), bn0.running_mean -15 + N(0, 3) (dB), bn0.running_var (10 (1 + N(0, 0.1)))^2 > 0.  Drawn tensor by
+    tensor in the module's key order, so every machine regenerates the same values."""
+    from .clap_audio import param_specs
+
+    rng = np.random.Generator(np.random.PCG64(seed))
+    sd: Dict[str, np.ndarray] = {}
+    for name, shape, kind in param_specs(depths):
+        if kind == "buf":
+            continue
+        v = rng.standard_normal(shape, dtype=np.float32)
+        if name.endswith("relative_position_bias_table"):
+            v = 0.5 * v
+        elif kind == "g":
+            v = 1.0 + 0.1 * v
+        elif kind == "m":
+            v = -15.0 + 3.0 * v
+        elif kind == "v":
+            v = (10.0 * (1.0 + 0.1 * v)) ** 2
+        else:
+            v = 0.02 * v
+        sd[name] = v.astype(np.float32)
+    return sd
+
+
+# (samples at 48 kHz, noise level, tones) of the CLAP audio fixture clips: 0.3 s .. exactly 10 s, one length that does
+# not divide 480 000, one all-zero clip, one of low level
+CLAP_AUDIO_CLIPS = [(14400, 0.1), (100003, 0.1), (48000, 0.0), (240000, 1e-3), (333333, 0.1), (480000, 0.05)]
+
+
+def make_clap_audio_clip(index: int, seed: int = SEED + 12, rate: int = 48000) -> np.ndarray:
+    """Fixture clip `index` (float32): white noise of the clip's level plus three tones of that amplitude - broadband,
+    so no mel band of a non-silent clip sits near the log floor."""
+    length, level = CLAP_AUDIO_CLIPS[index]
+    rng = np.random.Generator(np.random.PCG64(seed + index))
+    t = np.arange(length) / rate
+    x = level * rng.standard_normal(length)
+    for f in rng.uniform(100.0, 9000.0, 3):
+        x += level * np.sin(2 * np.pi * f * t + rng.uniform(0, 2 * np.pi))
+    return x.astype(np.float32)

@@ -62,12 +62,24 @@ def load_ss_model(configs: Dict, checkpoint_path: str, query_encoder: nn.Module)
                     optimizer_type=None, learning_rate=None, lr_lambda_func=None)
 
 
-def load_query_encoder(checkpoint_path: str, tokenizer=None, tokenizer_dir: str = None) -> nn.Module:
+def load_query_encoder(checkpoint_path: str, tokenizer=None, tokenizer_dir: str = None, modalities=("text",)) -> nn.Module:
     """The checkpoint's CLAP text tower as a query encoder (lass_amd.clap_text.ClapTextEncoder, HIP kernels) - the opt-in
     replacement of the default PrecomputedQueryEncoder:
         eval(evaluator, ckpt, query_encoder=load_query_encoder(ckpt, tokenizer_dir=<roberta-base vocab.json + merges.txt>))
     Captions are tokenized by `tokenizer` (a callable with the transformers tokenizer signature) or by a
-    RobertaTokenizer built from `tokenizer_dir`.  It moves to the device together with the separator."""
+    RobertaTokenizer built from `tokenizer_dir`.  It moves to the device together with the separator.
+    With "audio" among `modalities` the result is a lass_amd.clap_audio.ClapQueryEncoder holding both towers, which also
+    serves get_query_embed('audio' | 'hybird', audio=(B, L) at 32 kHz) - query by example; `modalities=("audio",)` gives
+    the ClapAudioEncoder alone (no text tower is read)."""
     from .clap_text import ClapTextEncoder
 
+    unknown = set(modalities) - {"text", "audio"}
+    if unknown:
+        raise ValueError(f"unknown modalities {sorted(unknown)} (expected 'text' and / or 'audio')")
+    if "audio" in modalities:
+        from .clap_audio import ClapAudioEncoder, ClapQueryEncoder
+
+        if "text" not in modalities:  # the audio tower alone: the text tower is neither needed nor loaded
+            return ClapAudioEncoder.from_checkpoint(checkpoint_path)
+        return ClapQueryEncoder.from_checkpoint(checkpoint_path, tokenizer=tokenizer, tokenizer_dir=tokenizer_dir)
     return ClapTextEncoder.from_checkpoint(checkpoint_path, tokenizer=tokenizer, tokenizer_dir=tokenizer_dir)
