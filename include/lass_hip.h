@@ -242,6 +242,32 @@ int lass_sdr_stats(lass_ctx* ctx, const float* ref, const float* est, int B, int
 int lass_mix_at_snr(lass_ctx* ctx, float* source, const float* noise, const float* snr_db, float* mixture, int B, int L,
                     double* scratch, void* stream);
 
+/* Evaluator load path: B rows of raw WAV payload -> B mono float32 clips at the target rate, in one launch.
+ * raw: row b = `frames` interleaved sample frames of `channels` samples at raw + b * row_stride_bytes (little-endian, as
+ * in the file's data chunk); encoding LASS_WAV_PCM16 (x/32768), LASS_WAV_PCM32 (round-to-nearest int -> float, then * 2^-31)
+ * or LASS_WAV_F32; channels (1 ... 8) are summed in ascending order in float32 and divided by their count, correctly rounded.
+ * Then the polyphase FIR of scipy.signal.resample_poly (padtype "constant"):
+ *   out[b][n] = sum_m x[b][m] * taps[n*down - m*up + (n_taps-1)/2],   x = 0 outside the clip,   n < L_out = ceil(frames*up/down)
+ * accumulated in float32 fmaf, in one fixed tap order per output (bit-identical whatever B, the row stride or the call);
+ * indices are 64-bit.  taps: the prototype filter (device, float32, natural order; lass_amd.resample.design_taps builds
+ * scipy's default).  up == down == 1 decodes and down-mixes only (taps may then be NULL, n_taps 1).
+ * Limits, checked before anything is launched (LASS_ERR_ARG): encoding one of the three, 1 <= channels <= 8,
+ * 1 <= up, down <= LASS_RESAMPLE_MAX_RATIO, n_taps odd and <= LASS_RESAMPLE_MAX_TAPS (the prototype filter is a 64 KiB table
+ * at most; the kernel keeps it in LDS phase by phase, up * (ceil(n_taps/up) | 1) floats, which must stay within
+ * LASS_RESAMPLE_MAX_TABLE floats = half of the CU's 160 KiB - true of every design_taps filter under the tap cap - so that
+ * the input span of at least one output always fits beside it), L_out equal to the ceiling above, row_stride_bytes a multiple
+ * of 4 and >= frames * channels * bytes per sample, raw 4-byte aligned, B <= 65535.  Stateless; out (B, L_out) is dense.
+ * Replaces: librosa.load(path, sr=16000, mono=True) (dcase_evaluator.py:73-74) behind the file read, for the encodings above;
+ * librosa resamples with soxr_hq, this is the project's scipy-style filter (parity unpinned against librosa, as on the host). */
+#define LASS_WAV_PCM16 0
+#define LASS_WAV_PCM32 1
+#define LASS_WAV_F32 2
+#define LASS_RESAMPLE_MAX_TAPS 16383
+#define LASS_RESAMPLE_MAX_TABLE 20480
+#define LASS_RESAMPLE_MAX_RATIO 65536
+int lass_decode_resample(lass_ctx* ctx, const void* raw, int64_t row_stride_bytes, int B, int frames, int channels, int encoding,
+                         int up, int down, const float* taps, int n_taps, float* out, int L_out, void* stream);
+
 /* Training-side data path ("next" row f4, mixer half; also the producer stage of the STFT pre-compute,
  * scripts/precompute_stfts.py:352-681): SegmentMixer.__call__ + dynamic_loudnorm (data/waveform_mixers.py:19-92) on the
  * device.  waveforms (B,L) -> mixture (B,L), segment (B,L).  For clip n:

@@ -1348,6 +1348,40 @@ int lass_mix_at_snr(lass_ctx* c, float* source, const float* noise, const float*
     return 0;
 }
 
+int lass_decode_resample(lass_ctx* c, const void* raw, int64_t row_stride_bytes, int B, int frames, int channels, int encoding,
+                         int up, int down, const float* taps, int n_taps, float* out, int L_out, void* stream) {
+    const char* w = "lass_decode_resample: ";
+    if (!c) return LASS_ERR_ARG;
+    if (!raw || !out || B <= 0 || B > 65535 || frames <= 0) return fail(c, LASS_ERR_ARG, std::string(w) + "raw, out non-NULL, 1 <= B <= 65535, frames >= 1");
+    if (encoding != LASS_WAV_PCM16 && encoding != LASS_WAV_PCM32 && encoding != LASS_WAV_F32)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "encoding must be LASS_WAV_PCM16, LASS_WAV_PCM32 or LASS_WAV_F32");
+    if (channels < 1 || channels > 8) return fail(c, LASS_ERR_ARG, std::string(w) + "1 ... 8 channels");
+    if (up < 1 || down < 1 || up > LASS_RESAMPLE_MAX_RATIO || down > LASS_RESAMPLE_MAX_RATIO)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "up and down must lie in 1 ... " + std::to_string(LASS_RESAMPLE_MAX_RATIO));
+    const bool fir = up != 1 || down != 1;
+    if (fir) {
+        if (!taps || n_taps < 1 || n_taps % 2 == 0) return fail(c, LASS_ERR_ARG, std::string(w) + "taps non-NULL, n_taps odd");
+        if (n_taps > LASS_RESAMPLE_MAX_TAPS)
+            return fail(c, LASS_ERR_ARG, std::string(w) + std::to_string(n_taps) + " taps exceed the cap of " +
+                        std::to_string(LASS_RESAMPLE_MAX_TAPS) + " (resample on the host)");
+        if (lass_resample_table_floats(up, n_taps) > LASS_RESAMPLE_MAX_TABLE)
+            return fail(c, LASS_ERR_ARG, std::string(w) + "the polyphase table up * (ceil(n_taps/up) | 1) exceeds " +
+                        std::to_string(LASS_RESAMPLE_MAX_TABLE) + " floats");
+    }
+    const long long want = ((long long)frames * up + down - 1) / down;
+    if (L_out <= 0 || want != (long long)L_out)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "L_out must be ceil(frames*up/down) = " + std::to_string(want));
+    const long long row_bytes = (long long)frames * channels * (encoding == LASS_WAV_PCM16 ? 2 : 4);
+    if (row_stride_bytes < row_bytes || row_stride_bytes % 4 != 0)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "row_stride_bytes must be a multiple of 4 and hold a row (" +
+                    std::to_string(row_bytes) + " bytes)");
+    if (reinterpret_cast<uintptr_t>(raw) % 4 != 0) return fail(c, LASS_ERR_ARG, std::string(w) + "raw must be 4-byte aligned");
+    if (int r = use_device(c)) return r;
+    HIP_TRY(c, lass_launch_decode_resample(raw, row_stride_bytes, B, frames, channels, encoding, up, down, taps, n_taps, out, L_out,
+                                           (hipStream_t)stream));
+    return 0;
+}
+
 int lass_segment_mix(lass_ctx* c, const float* waveforms, int B, int L, const int* mix_num, const float* comp_db, int max_comp,
                      const float* noise_db, float* mixture, float* segment, double* scratch, void* stream) {
     if (!c || !waveforms || !mix_num || !comp_db || !noise_db || !mixture || !segment || !scratch || B <= 0 || L <= 0)

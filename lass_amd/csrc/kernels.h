@@ -200,3 +200,11 @@ hipError_t lass_launch_relayout_conv(const float* src, int Cout, int Cin, int ta
 // scale[c] = g/sqrt(var+eps); base[c] = beta - mean*scale
 hipError_t lass_launch_bnfold(const float* g, const float* beta, const float* mean, const float* var, int C, float eps,
                               float* scale, float* base, hipStream_t stream);
+
+// ---- resample.hip -------------------------------------------------------------------------------------------------
+// raw (B rows of interleaved frames, row_stride bytes apart; enc = LASS_WAV_*) -> out (B, L_out) mono f32: decode, down-mix,
+// out[n] = sum_m x[m] * taps[n*down - m*up + (n_taps-1)/2].  up == down == 1: no FIR (taps unused).  The caller has checked
+// the arguments (lass_decode_resample); hipErrorInvalidValue for what the kernel's LDS plan cannot hold.
+size_t lass_resample_table_floats(int up, int n_taps);  // the polyphase table in LDS: up * (ceil(n_taps/up) | 1)
+hipError_t lass_launch_decode_resample(const void* raw, long long row_stride, int B, int frames, int ch, int enc, int up, int down,
+                                       const float* taps, int n_taps, float* out, int L_out, hipStream_t stream);

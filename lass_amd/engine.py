@@ -340,6 +340,49 @@ class Engine:
         _lib.check(self.ctx, rc, "lass_mix_at_snr")
         return mixture
 
+    def decode_resample(self, raw_u8: torch.Tensor, frames: int, channels: int, encoding: str, rate_in: int, rate_out: int,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """librosa.load(path, sr=rate_out, mono=True) behind the file read (dcase_evaluator.py:73-74), on the device: raw_u8
+        (B, row bytes) uint8 - each row a WAV data chunk of `frames` frames x `channels` samples, encoding "pcm16" / "pcm32" /
+        "f32", rows a multiple of 4 bytes apart - -> (B, ceil(frames * up / down)) float32 mono at rate_out (`out`: written
+        in place).  The filter is lass_amd.resample.design_taps; a ratio beyond the kernel's tap cap raises LassError
+        (resample.within_cap tells beforehand)."""
+        from . import resample as rs
+        if raw_u8.dim() == 1:
+            raw_u8 = raw_u8[None]
+        if raw_u8.device != self.device or raw_u8.dtype != torch.uint8 or raw_u8.dim() != 2 or raw_u8.stride(1) != 1:
+            raise _lib.LassError(f"raw_u8 must be a (B, bytes) uint8 tensor on {self.device} with contiguous rows")
+        if encoding not in rs.ENCODINGS:
+            raise _lib.LassError(f"encoding must be one of {sorted(rs.ENCODINGS)}")
+        B = raw_u8.shape[0]
+        if raw_u8.shape[1] < int(frames) * int(channels) * rs.SAMPLE_BYTES[encoding]:
+            raise _lib.LassError("raw_u8 rows are shorter than frames x channels samples")
+        up, down = rs.ratio(rate_in, rate_out)
+        L_out = rs.out_len(frames, up, down)
+        fir = (up, down) != (1, 1)
+        if fir and not rs.within_cap(up, down):
+            raise _lib.LassError(f"resampling {rate_in} -> {rate_out} Hz needs {rs.n_taps(up, down)} taps, over the device "
+                                 f"kernel's cap of {rs.MAX_TAPS}: resample on the host (wavio.read_wav)")
+        taps = rs.device_taps(up, down, self.device) if fir else None
+        if out is None:
+            out = torch.empty(B, L_out, dtype=torch.float32, device=self.device)
+        elif (tuple(out.shape) != (B, L_out) or out.dtype != torch.float32 or out.device != self.device
+              or not out.is_contiguous()):
+            raise _lib.LassError(f"out must be a contiguous float32 {(B, L_out)} tensor on {self.device}")
+        stride = raw_u8.stride(0) if B > 1 else (raw_u8.shape[1] + 3) // 4 * 4  # (one row: no stride to honour)
+        rc = self.lib.lass_decode_resample(self.ctx, _ptr(raw_u8), stride, B, int(frames), int(channels), rs.ENCODINGS[encoding], up, down, _ptr(taps),
+                                           taps.numel() if fir else 1, _ptr(out), L_out, _stream(self.device))
+        _lib.check(self.ctx, rc, "lass_decode_resample")
+        return out
+
+    def resample(self, x: torch.Tensor, rate_in: int, rate_out: int) -> torch.Tensor:
+        """(B, L) or (L,) float32 at rate_in -> float32 at rate_out: the mono float32 case of `decode_resample`."""
+        x = self._dev(x)
+        one = x.dim() == 1
+        x = x[None] if one else x
+        y = self.decode_resample(x.view(torch.uint8), x.shape[1], 1, "f32", rate_in, rate_out)
+        return y[0] if one else y
+
     def segment_mix(self, waveforms: torch.Tensor, mix_num: torch.Tensor, comp_db: torch.Tensor, noise_db: torch.Tensor):
         """data/waveform_mixers.py:19-62 on the device with the random draws given: waveforms (B,L), mix_num (B) int32,
         comp_db (B, max_mix_num - 1) f32, noise_db (B) f32 -> (mixture (B,L), segment (B,L))."""

@@ -17,6 +17,12 @@ definitions and the same printed line.  Differences are in execution only:
     overlapping half-batches (include/lass_hip.h) instead of launching ~40 kernels eagerly, and the loop allocates nothing per
     batch.  Any clip that does not fit a slot row (other length, rate, channels) sends its batch through the generic path
     below; results are identical either way (`resident=False` forces the generic path);
+  * (opt-in, `device_decode=True`) a validation set that is NOT mono at the evaluator's rate - another sample rate, several
+    channels - keeps the resident path: the slots then carry pinned and device BYTE rows, the decode threads only read each
+    file's data chunk into them (`read_wav_raw_into`), and PCM decode, mono down-mix and polyphase resampling run on the
+    device (`lass_decode_resample`, two launches per batch in front of `lass_mix_at_snr`).  Without it such a set is decoded and
+    resampled on the host (`read_wav`: scipy in float64, ~10 ms per clip) and every batch takes the generic path.  The filter
+    is the host's (lass_amd/resample.py), evaluated in float32; a set that is mono at the rate runs exactly as without the flag;
   * under torch.distributed the clip list is block-sharded over ranks and the per-clip metric rows are all-gathered
     once at the end (RCCL when the backend is "nccl").
 """
@@ -32,10 +38,11 @@ import numpy as np
 import torch
 
 from . import dist as ldist
+from . import resample as rs
 from .engine import get_engine
 from .metrics import stats_to_db
 from .utils import load_ss_model, parse_yaml
-from .wavio import read_wav, read_wav_into, wav_frames
+from .wavio import read_wav, read_wav_into, read_wav_raw_into, wav_frames, wav_info
 
 
 def _mix_on_host(source: np.ndarray, noise: np.ndarray, snr_db: int):
@@ -92,11 +99,19 @@ class _Stager:
 class _Slot:
     """One resident batch: pinned host rows for the decode threads and the device tensors lass_separate sees again and again."""
 
-    def __init__(self, B: int, L: int, device):
-        pin = lambda *shape: torch.empty(shape, dtype=torch.float32).pin_memory()  # noqa: E731
+    def __init__(self, B: int, L: int, device, raw_bytes: int = 0):
+        """raw_bytes > 0 (device_decode on a set that is not mono at the rate): the pinned rows hold the files' data chunks,
+        `raw_bytes` bytes each, next to device copies of them; the float32 rows exist on the device only."""
+        pin = lambda *shape, dtype=torch.float32: torch.empty(shape, dtype=dtype).pin_memory()  # noqa: E731
         dev = lambda *shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=device)  # noqa: E731
-        self.pin_src, self.pin_noise, self.pin_snr = pin(B, L), pin(B, L), pin(B)
-        self.np_src, self.np_noise, self.np_snr = self.pin_src.numpy(), self.pin_noise.numpy(), self.pin_snr.numpy()
+        self.pin_snr = pin(B)
+        self.np_snr = self.pin_snr.numpy()
+        if raw_bytes:
+            self.pin_src, self.pin_noise = pin(B, raw_bytes, dtype=torch.uint8), pin(B, raw_bytes, dtype=torch.uint8)
+            self.raw_src, self.raw_noise = dev(B, raw_bytes, dtype=torch.uint8), dev(B, raw_bytes, dtype=torch.uint8)
+        else:
+            self.pin_src, self.pin_noise = pin(B, L), pin(B, L)
+        self.np_src, self.np_noise = self.pin_src.numpy(), self.pin_noise.numpy()
         self.src, self.noise, self.snr, self.mix, self.out = dev(B, L), dev(B, L), dev(B), dev(B, L), dev(B, L)
         self.cond = dev(B, 512)
         self.scratch = dev(B, 4, dtype=torch.float64)
@@ -106,7 +121,8 @@ class _Slot:
 
 class DCASEEvaluator:
     def __init__(self, sampling_rate=16000, eval_indexes="lass_synthetic_validation.csv", audio_dir="lass_validation",
-                 batch_size: int = 16, device_mixing: bool = True, io_workers: int = 2, resident: bool = True) -> None:
+                 batch_size: int = 16, device_mixing: bool = True, io_workers: int = 2, resident: bool = True,
+                 device_decode: bool = False) -> None:
         r"""DCASE T9 LASS evaluator (dcase_evaluator.py:28-47)."""
         self.sampling_rate = sampling_rate
         with open(eval_indexes) as csv_file:
@@ -120,7 +136,8 @@ class DCASEEvaluator:
         self.last_rows = None  # (N,3) per-clip [sdr, sdri, sisdr] of the last call (all ranks)
         self._embed_cache: Dict[str, torch.Tensor] = {}
         self.resident = resident
-        self._slots = {}       # (B, L, device) -> [two _Slot]: kept across calls, so later calls replay graphs from their first batch
+        self.device_decode = device_decode  # module docstring: decode / down-mix / resample on the device (resident path only)
+        self._slots = {}       # (B, L, device, file format) -> [two _Slot]: kept across calls, so later calls replay graphs from their first batch
         self.last_path = None  # "resident" / "generic": which data path the last call took (tests, bench)
         self.resident_batches = self.generic_batches = 0
 
@@ -193,23 +210,44 @@ class DCASEEvaluator:
         B = self.batch_size
         items = self.eval_list[lo:hi]
         n = len(items)
-        L = wav_frames(os.path.join(self.audio_dir, f"{items[0][0]}.wav"))
-        if L <= 0:
-            return self._run_generic(pl_model, eng, device, items)
-        key = (B, L, str(device))
+        first = os.path.join(self.audio_dir, f"{items[0][0]}.wav")
+        sr = self.sampling_rate
+        fmt, raw_bytes = None, 0  # fmt: the (encoding, channels, rate, frames) every file must have for the device to decode it
+        if self.device_decode:
+            info = wav_info(first)
+            if info is not None and not (info[1] == 1 and info[2] == sr):
+                enc, nch, rate, frames = fmt = info[:4]
+                if nch > 8 or not rs.within_cap(*rs.ratio(rate, sr)):
+                    info = None
+            if info is None:  # nothing the device path takes: decided before any slot exists
+                self.last_path = "generic"
+                return self._run_generic(pl_model, eng, device, items)
+        if fmt is None:
+            L = wav_frames(first)
+            if L <= 0:
+                return self._run_generic(pl_model, eng, device, items)
+        else:
+            L = rs.out_len(frames, *rs.ratio(rate, sr))
+            raw_bytes = (frames * nch * rs.SAMPLE_BYTES[enc] + 3) // 4 * 4
+        key = (B, L, str(device)) + ((fmt,) if fmt else ())
         slots = self._slots.get(key)
         if slots is None:
             self._slots.clear()  # one shape at a time: 2 x (2 pinned + 5 device) x B x L floats
-            slots = self._slots[key] = [_Slot(B, L, device), _Slot(B, L, device)]
+            slots = self._slots[key] = [_Slot(B, L, device, raw_bytes), _Slot(B, L, device, raw_bytes)]
         nb = (n + B - 1) // B
         compute = torch.cuda.current_stream(device)
         copy_stream = torch.cuda.Stream(device)
-        sr = self.sampling_rate
 
         def decode(k: int):
             """-> None when both files went straight into the slot rows, else the generic loader's tuple for this clip."""
             source, noise, snr, _caption = items[k]
             slot, r = slots[(k // B) % 2], k % B
+            if fmt is not None:
+                if (read_wav_raw_into(os.path.join(self.audio_dir, f"{source}.wav"), fmt, slot.np_src[r])
+                        and read_wav_raw_into(os.path.join(self.audio_dir, f"{noise}.wav"), fmt, slot.np_noise[r])):
+                    slot.np_snr[r] = float(int(snr))
+                    return None
+                return self._read_pair(items[k])
             if (read_wav_into(os.path.join(self.audio_dir, f"{source}.wav"), sr, slot.np_src[r])
                     and read_wav_into(os.path.join(self.audio_dir, f"{noise}.wav"), sr, slot.np_noise[r])):
                 slot.np_snr[r] = float(int(snr))
@@ -246,13 +284,16 @@ class DCASEEvaluator:
                     with torch.cuda.stream(copy_stream):
                         if slot.compute_done is not None:
                             copy_stream.wait_event(slot.compute_done)  # batch j - 2 has finished with these device tensors
-                        slot.src[:m].copy_(slot.pin_src[:m], non_blocking=True)
-                        slot.noise[:m].copy_(slot.pin_noise[:m], non_blocking=True)
+                        (slot.src if fmt is None else slot.raw_src)[:m].copy_(slot.pin_src[:m], non_blocking=True)
+                        (slot.noise if fmt is None else slot.raw_noise)[:m].copy_(slot.pin_noise[:m], non_blocking=True)
                         slot.snr[:m].copy_(slot.pin_snr[:m], non_blocking=True)
                         slot.h2d_done = torch.cuda.Event()
                         slot.h2d_done.record(copy_stream)
                     compute.wait_event(slot.h2d_done)
                     src, mix, cond, out = slot.src[:m], slot.mix[:m], slot.cond[:m], slot.out[:m]
+                    if fmt is not None:
+                        eng.decode_resample(slot.raw_src[:m], frames, nch, enc, rate, sr, out=src)
+                        eng.decode_resample(slot.raw_noise[:m], frames, nch, enc, rate, sr, out=slot.noise[:m])
                     eng.mix_at_snr(src, slot.noise[:m], slot.snr[:m], out=mix, scratch=slot.scratch)
                     cond.copy_(self._conditions(pl_model, captions, device))
                     pl_model.ss_model.separate_into(mix, cond, out)
@@ -268,7 +309,9 @@ class DCASEEvaluator:
                     self.generic_batches += 1
                     group = []
                     for r_, k in zip(res, range(k0, k1)):
-                        if r_ is None:
+                        if r_ is None and fmt is not None:
+                            r_ = self._read_pair(items[k])  # (the slot row holds the file's bytes, not samples)
+                        elif r_ is None:
                             r_ = (slot.np_src[k % B].copy(), slot.np_noise[k % B].copy(), int(items[k][2]), items[k][3])
                         group.append(r_)
                     submit_ready(j + 3)

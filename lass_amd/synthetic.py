@@ -124,19 +124,32 @@ def make_mixtures(batch: int, length: int = 160000, first: int = 0, seed: int = 
     return np.stack(srcs).astype(np.float32), np.stack(mixes).astype(np.float32)
 
 
-def write_validation_set(root: str, n_clips: int = 8, length: int = 160000, sr: int = 16000, seed: int = SEED) -> str:
+def write_validation_set(root: str, n_clips: int = 8, length: int = 160000, sr: int = 16000, seed: int = SEED,
+                         file_rate: int | None = None, channels: int = 1, encoding: str = "f32") -> str:
     """Write `<root>/lass_validation/*.wav` + `<root>/lass_synthetic_validation.csv` in the DCASE layout
-    (header `source,noise,snr,caption`; dcase_evaluator.py:42-47,67-71).  Returns the csv path."""
+    (header `source,noise,snr,caption`; dcase_evaluator.py:42-47,67-71).  Returns the csv path.
+    file_rate / channels / encoding ("f32", "pcm16", "pcm32"): the files' own format when it is not mono float32 at `sr` -
+    the clips (still `length / sr` seconds) are then generated at `file_rate`, and channel c carries the clip times
+    1 - c / (2 * channels).  The defaults write the files this function always wrote."""
     import os
-    from .wavio import write_wav_f32
+    from . import wavio
+
+    write = {"f32": wavio.write_wav_f32, "pcm16": wavio.write_wav_pcm16, "pcm32": wavio.write_wav_pcm32}[encoding]
+    rate = sr if file_rate is None else int(file_rate)
+    frames = length if rate == sr else int(round(length * rate / sr))
+
+    def shaped(x):
+        if channels == 1:
+            return x
+        return np.stack([x * np.float32(1.0 - c / (2.0 * channels)) for c in range(channels)], axis=1)
 
     adir = os.path.join(root, "lass_validation")
     os.makedirs(adir, exist_ok=True)
     rows = ["source,noise,snr,caption"]
     for i in range(n_clips):
-        s, n, snr = make_clip(i, length, sr, seed)
-        write_wav_f32(os.path.join(adir, f"src_{i:04d}.wav"), s, sr)
-        write_wav_f32(os.path.join(adir, f"noise_{i:04d}.wav"), n, sr)
+        s, n, snr = make_clip(i, frames, rate, seed)
+        write(os.path.join(adir, f"src_{i:04d}.wav"), shaped(s), rate)
+        write(os.path.join(adir, f"noise_{i:04d}.wav"), shaped(n), rate)
         rows.append(f"src_{i:04d},noise_{i:04d},{snr},synthetic tone cluster {i % 4}")
     csv_path = os.path.join(root, "lass_synthetic_validation.csv")
     with open(csv_path, "w") as f:

@@ -1,5 +1,9 @@
 """Minimal RIFF/WAVE reader-writer (PCM16, PCM32, float32), mono down-mix.
 
+`wav_info` / `read_wav_raw_into` serve the evaluator's device load path: header parsing and the raw payload only, the decode,
+down-mix and resampling being `lass_decode_resample`'s (lass_amd/resample.py has the filter).
+
+
 Stands in for `librosa.load(path, sr=16000, mono=True)` (dcase_evaluator.py:73-74) for files that are ALREADY at the
 target rate: the load then reduces to PCM decode + mono down-mix + int->float scaling (x/32768 for int16, as
 soundfile/librosa do).  Whether the Zenodo validation audio is at 16 kHz is NOT established from the reference (its
@@ -128,6 +132,77 @@ def read_wav_into(path: str, sr: int, out: np.ndarray) -> bool:
     return False
 
 
+_EXT_PCM, _EXT_FLOAT = b"\x01\x00", b"\x03\x00"
+_EXT_TAIL = b"\x00\x00\x00\x00\x10\x00\x80\x00\x00\xaa\x00\x38\x9b\x71"  # KSDATAFORMAT_SUBTYPE_*: the tag + this
+
+
+def _parse_header(f):
+    """(encoding, channels, rate, frames, data_offset) from an open file positioned at 0, or None."""
+    import os
+    head = f.read(12)
+    if len(head) < 12 or head[:4] != b"RIFF" or head[8:12] != b"WAVE":
+        return None
+    fmt = None
+    while True:
+        ch = f.read(8)
+        if len(ch) < 8:
+            return None
+        cid, size = ch[:4], struct.unpack("<I", ch[4:])[0]
+        if cid == b"fmt ":
+            body = f.read(size + (size & 1))
+            if size < 16 or len(body) < size:
+                return None
+            tag, nch, rate, _, block, bits = struct.unpack("<HHIIHH", body[:16])
+            if tag == 0xFFFE:  # WAVE_FORMAT_EXTENSIBLE: the encoding is the sub-format GUID's first two bytes
+                if size < 40 or body[26:40] != _EXT_TAIL:
+                    return None
+                tag = struct.unpack("<H", body[24:26])[0]
+            fmt = (tag, nch, rate, block, bits)
+        elif cid == b"data":
+            break
+        else:
+            f.seek(size + (size & 1), 1)
+    if fmt is None:
+        return None
+    tag, nch, rate, block, bits = fmt
+    enc = {(1, 16): "pcm16", (1, 32): "pcm32", (3, 32): "f32"}.get((tag, bits))
+    offset = f.tell()
+    if (enc is None or nch < 1 or rate < 1 or block != nch * bits // 8 or size % block != 0 or size == 0
+            or os.fstat(f.fileno()).st_size < offset + size):
+        return None
+    return enc, nch, rate, size // block, offset
+
+
+def wav_info(path: str):
+    """(encoding, channels, rate, frames, data_offset) of a RIFF/WAVE file from its header alone - encoding "pcm16", "pcm32" or
+    "f32", data_offset the first payload byte - or None for any header this module does not fully understand: not RIFF/WAVE,
+    truncated, a `fmt ` chunk under 16 bytes, another encoding, a block size that is not channels x sample size, a data
+    chunk that is empty, not whole frames, or longer than the file."""
+    try:
+        with open(path, "rb") as f:
+            return _parse_header(f)
+    except (OSError, struct.error):
+        return None
+
+
+def read_wav_raw_into(path: str, info, out_u8: np.ndarray) -> bool:
+    """The file's data chunk, undecoded, into `out_u8` (a uint8 row of a pinned staging buffer, at least as long as the chunk) in
+    one `readinto`; decoding, down-mix and resampling are the device's (`Engine.decode_resample`).  True only if the file's
+    encoding, channels, rate and frame count equal `info`'s (a `wav_info` tuple; its data_offset is the file's own) and
+    every byte arrived."""
+    try:
+        with open(path, "rb") as f:
+            mine = _parse_header(f)
+            if mine is None or tuple(mine[:4]) != tuple(info[:4]):
+                return False
+            nbytes = mine[3] * mine[1] * (2 if mine[0] == "pcm16" else 4)
+            if out_u8.dtype != np.uint8 or out_u8.ndim != 1 or not out_u8.flags.c_contiguous or out_u8.shape[0] < nbytes:
+                return False
+            return f.readinto(memoryview(out_u8)[:nbytes]) == nbytes
+    except (OSError, struct.error):
+        return False
+
+
 def wav_frames(path: str) -> int:
     """Sample frames of a RIFF/WAVE file from its header alone (0 if the header is not understood)."""
     try:
@@ -152,19 +227,40 @@ def wav_frames(path: str) -> int:
         return 0
 
 
+def _frames_channels(x: np.ndarray):
+    """1-D = mono; 2-D = (frames, channels), written interleaved."""
+    if x.ndim == 1:
+        return 1
+    if x.ndim != 2 or x.shape[1] < 1:
+        raise ValueError("a (frames,) or (frames, channels) array expected")
+    return x.shape[1]
+
+
 def write_wav_f32(path: str, x: np.ndarray, sr: int) -> None:
     x = np.ascontiguousarray(x, dtype="<f4")
+    nch = _frames_channels(x)
     body = x.tobytes()
     hdr = b"RIFF" + struct.pack("<I", 36 + len(body)) + b"WAVE" + b"fmt " + struct.pack(
-        "<IHHIIHH", 16, 3, 1, sr, sr * 4, 4, 32) + b"data" + struct.pack("<I", len(body))
+        "<IHHIIHH", 16, 3, nch, sr, sr * 4 * nch, 4 * nch, 32) + b"data" + struct.pack("<I", len(body))
     with open(path, "wb") as f:
         f.write(hdr + body)
 
 
 def write_wav_pcm16(path: str, x: np.ndarray, sr: int) -> None:
-    q = np.clip(np.round(np.asarray(x, dtype=np.float64) * 32768.0), -32768, 32767).astype("<i2")
+    q = np.ascontiguousarray(np.clip(np.round(np.asarray(x, dtype=np.float64) * 32768.0), -32768, 32767).astype("<i2"))
+    nch = _frames_channels(q)
     body = q.tobytes()
     hdr = b"RIFF" + struct.pack("<I", 36 + len(body)) + b"WAVE" + b"fmt " + struct.pack(
-        "<IHHIIHH", 16, 1, 1, sr, sr * 2, 2, 16) + b"data" + struct.pack("<I", len(body))
+        "<IHHIIHH", 16, 1, nch, sr, sr * 2 * nch, 2 * nch, 16) + b"data" + struct.pack("<I", len(body))
+    with open(path, "wb") as f:
+        f.write(hdr + body)
+
+
+def write_wav_pcm32(path: str, x: np.ndarray, sr: int) -> None:
+    q = np.ascontiguousarray(np.clip(np.round(np.asarray(x, dtype=np.float64) * 2147483648.0), -2147483648, 2147483647).astype("<i4"))
+    nch = _frames_channels(q)
+    body = q.tobytes()
+    hdr = b"RIFF" + struct.pack("<I", 36 + len(body)) + b"WAVE" + b"fmt " + struct.pack(
+        "<IHHIIHH", 16, 1, nch, sr, sr * 4 * nch, 4 * nch, 32) + b"data" + struct.pack("<I", len(body))
     with open(path, "wb") as f:
         f.write(hdr + body)
