@@ -131,6 +131,17 @@ int lass_set_graph_replay(lass_ctx* ctx, int enabled);
  * or 4 forces that number on the stage calls and lass_separate alike (1 = the unsplit kernels), 0 restores the default.  Query lass_workspace_bytes again
  * afterwards: the partial sums live in the workspace. */
 int lass_set_wino4_splits(lass_ctx* ctx, int splits);
+/* f32: the F(4x4,3x3) layers with many output-channel groups read their transformed input from an image that one prep launch
+ * writes (into the workspace), instead of every group's workgroups transforming the same tiles again.  The rule looks at the
+ * layer's shape only, never at the batch.  mode 0 = off, 1 = the measured routing (default), 2 = every layer whose kind admits
+ * it (tests, A/B).  Query lass_workspace_bytes again afterwards. */
+int lass_set_wino4_vprep(lass_ctx* ctx, int mode);
+/* UNSTABLE, tests only - not part of the supported interface, and may change or go without notice; lass_separate never looks at
+ * it.  The stage calls (lass_convblock, lass_encoder_block) keep that image in `v` (`floats` f32 of device memory owned by the
+ * caller) instead of a buffer of the context; NULL restores the context's.  A buffer that is too small for a layer, or overlaps
+ * its tensors, makes the stage call return LASS_ERR_STATE without launching.  (The tests use it to place the image where the
+ * overlap check must refuse it, and to see that a layer's prep launch wrote it.) */
+int lass_set_wino4_vprep_buffer(lass_ctx* ctx, float* v, size_t floats);
 
 /* The same path from a PRECOMPUTED analysis of the mixtures, as the reference's multi-STFT wrapper takes it
  * (resunet_with_multistft.py:233-241: input_dict["stft_mixture_mag" / "_cos" / "_sin"][win]; producer:

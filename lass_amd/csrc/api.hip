@@ -108,6 +108,12 @@ struct lass_ctx {
     int wino4_mincin = 32;     // 3x3 convs with at least that many input channels (and >= 32-wide images) run as Winograd
                                // F(4x4,3x3) (wino4.hip); LASS_WINO4=<min Cin>, 0 = off (F(2x2,3x3) everywhere)
     int ksplit_force = 0;      // lass_set_wino4_splits: 0 = the route's split-K factor on the 32 x 16 Winograd blocks (kWino4Splits), else 1 / 2 / 4
+    int vprep_mode = 1;        // lass_set_wino4_vprep: 0 = every F(4x4,3x3) launch transforms its own input, 1 = the layers of
+                               // wino4_vprep_shape read it from a prep launch's image, 2 = every layer whose kind admits it (tests, A/B)
+    float* stage_v = nullptr;      // ... their V image in the stage calls, grown on demand like stage_part (Plan::vprep in lass_separate)
+    size_t stage_v_floats = 0;
+    float* stage_v_user = nullptr; // lass_set_wino4_vprep_buffer: a caller-owned image buffer for the stage calls instead
+    size_t stage_v_user_floats = 0;
     float* stage_part = nullptr;   // split-K partials of the stage calls (lass_convblock, lass_encoder_block), grown on demand;
     size_t stage_part_floats = 0;  // lass_separate takes its own from the caller's workspace (Plan::kpart)
     bool fuse_catb = true;  // bf16 mode: decoder concats as blocked bf16 copies (LASS_FUSE_CATB=0: f32 concat)
@@ -441,6 +447,8 @@ struct BlockFusions {
     const CatCopies* pool_copies = nullptr; // bf16: the pooled output as two blocked copies for the next encoder block
     const UpFuse* up = nullptr;             // bf16, decoder_block6: its transposed conv inside the block's fused kernel
     float* kpart = nullptr;                 // f32, the 32 x 16 Winograd blocks: split-K partials, wino4_split_floats() of them
+    float* vws = nullptr;                   // f32, the layers of wino4_vprep_shape: the transformed input image of one conv at a time,
+    size_t vws_floats = 0;                  // wino4_vprep_floats() of them
 };
 
 // f32, the 3x3 convs of a block whose images tile only into 32-row x 16-column F(4x4,3x3) blocks (lass_wino4_narrow: the 16-bin
@@ -462,6 +470,32 @@ size_t wino4_split_floats(const ResBlock& rb, int S, int B, int H, int W) { retu
 // 128: encoder_block2-4, decoder_block5-6) are byte-bound there - writing bias + Wsc x and reading it back costs more than
 // the re-fetches it saves (measured, profiles/r06)
 constexpr int kShortcutGemmMinCin = 256;
+
+// f32, F(4x4,3x3): the Cout / 32 workgroups of a 32-tile block each form the same transformed input V per chunk (prologue, zero
+// padding, 6x6 transform: 252 of a wave's ~460 non-MFMA instructions per chunk, on the datapath the f32 MFMA shares).  Layers with
+// at least this many cout groups have one prep launch write V to memory (2.25 x the input) and their conv kernels copy it in by
+// LDS-DMA like the weight slab.  Shape only, never a function of B.  The constant is the per-launch table of
+// profiles/r09/README.md (B = 16, prep + conv against the launch that transforms its own input): the 12-group layers (Cout 384,
+// the 64 x 32 and 32 x 16 levels) are 11-24 % below it; the 8-group layers (Cout 256, 128 x 64) only 1.5-5 % for a 0.6-GB image
+// and stay off; with 4 groups or fewer the prep launch costs more than it saves (+ 20-44 %).
+constexpr int kVprepMinCoutGroups = 12;
+// F(4x4,3x3) weight images of a 16-bin level serve the 32 x 16 blocks only (there ksplit > 0: wino4_splits), those of the wider
+// levels the wider blocks only
+bool wino4_level_geom(const ResBlock& rb, int H, int W, int ksplit) { return rb.width % 32 == 0 ? !lass_wino4_narrow(H, W) : ksplit > 0; }
+bool wino4_vprep_shape(const lass_ctx* c, const ResBlock& rb) {
+    if (c->compute_mode != LASS_COMPUTE_F32 || c->vprep_mode == 0 || c->wino4_mincin <= 0) return false;
+    return c->vprep_mode == 2 || rb.cout / 32 >= kVprepMinCoutGroups;
+}
+// floats of the V slot a block needs: the larger of conv1's image (cin channels) and conv2's (cout channels: only where conv2 runs
+// without a fused shortcut phase, i.e. the identity blocks and the layers whose shortcut is a GEMM of its own).  An upper bound
+// where run_resblock then finds a launch unsupported and leaves it off the route.
+size_t wino4_vprep_floats(const lass_ctx* c, const ResBlock& rb, int B, int H, int W) {
+    if (!wino4_vprep_shape(c, rb) || rb.cin % 8 != 0 || rb.cout % 32 != 0) return 0;
+    if (!lass_wino4_block_tc(H, W) || !wino4_level_geom(rb, H, W, wino4_splits(c, rb, B, H, W))) return 0;
+    int ch = rb.u1f ? rb.cin : 0;
+    if (rb.u2f && (rb.cin == rb.cout || rb.cin >= kShortcutGemmMinCin)) ch = std::max(ch, rb.cout);
+    return lass_wino4_vpre_floats(B, ch, H, W);
+}
 
 int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int B, int H, int W, const float* shift,
                  float* a2, float* out, long out_bs, hipStream_t st, const BlockFusions& f = BlockFusions()) {
@@ -494,9 +528,8 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
     // the direct f32 kernels (conv.hip) have no *_PRE kinds: they refuse them
     const ConvKind k1 = x0 ? CONV1_ACT_PRE : CONV1_ACT, k2 = x0 ? CONV2_IDENT_PRE : CONV2_IDENT;
     const bool wino1 = !bf1 && rb.u1 && lass_wino_supported(p);
-    // F(4x4,3x3) images of a 16-bin level serve the 32 x 16 blocks only, those of the wider levels the wider blocks only
     const int ksplit = bf1 || x0 ? 0 : wino4_splits(c, rb, B, H, W);
-    const bool w4_geom = rb.width % 32 == 0 ? !lass_wino4_narrow(H, W) : ksplit > 0;
+    const bool w4_geom = wino4_level_geom(rb, H, W, ksplit);
     if (ksplit > 1) {
         if (!f.kpart) return fail(c, LASS_ERR_STATE, "split-K needs its partial workspace");
         const auto overlaps = [&](const float* a, size_t a_n, const float* b, long b_bs, long b_n) {
@@ -509,12 +542,34 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
     }
     Wino4Split sk;  // both convs of the block
     if (ksplit > 1) { sk.n = ksplit; sk.part = f.kpart; }
+    // V from memory (wino4_vprep_shape): the slot holds one conv's image at a time, in stream order.  Checked here, in front of
+    // the block's first launch
+    const size_t vneed = !bf1 && !x0 && w4_geom ? wino4_vprep_floats(c, rb, B, H, W) : 0;
+    if (vneed) {
+        if (!f.vws || f.vws_floats < vneed) return fail(c, LASS_ERR_STATE, "the V-from-memory route needs its image workspace");
+        const auto overlaps = [&](const float* b, long b_bs, long b_n) {
+            return b && f.vws < b + (size_t)(B - 1) * b_bs + b_n && b < f.vws + vneed;
+        };
+        if (overlaps(x, x_bs, rb.cin * HW) || overlaps(a2, rb.cout * HW, rb.cout * HW) || overlaps(out, out_bs, rb.cout * HW) ||
+            (sk.part && overlaps(sk.part, 0, (long)wino4_split_floats(rb, ksplit, B, H, W))))
+            return fail(c, LASS_ERR_STATE, "the V image must not overlap the block's input, intermediate, output or split-K partials");
+    }
+    auto vprep_slot = [&](int cin, Wino4VPre* vp) -> int {
+        if (lass_wino4_vpre_floats(B, cin, H, W) > vneed) return fail(c, LASS_ERR_STATE, "the V image workspace is smaller than this layer's image");
+        vp->v = f.vws;
+        return 0;
+    };
+    const bool vshape = vneed > 0;
     auto launch_conv1 = [&]() -> int {
         ProfScope ps(c, st, P_CONV3X3);
         if (bf1)
             HIP_TRY(c, lass_launch_conv_bf16(k1, p, st));
-        else if (wino1 && rb.u1f && w4_geom && lass_wino4_supported(k1, p, sk))
-            HIP_TRY(c, lass_launch_wino4(k1, p, st, sk));
+        else if (wino1 && rb.u1f && w4_geom && lass_wino4_supported(k1, p, sk)) {
+            Wino4VPre vp;
+            if (vshape && lass_wino4_vpre_supported(k1, p, sk))
+                if (int rv = vprep_slot(rb.cin, &vp)) return rv;
+            HIP_TRY(c, lass_launch_wino4(k1, p, st, sk, vp));
+        }
         else if (wino1)
             HIP_TRY(c, lass_launch_wino(k1, p, st));
         else
@@ -616,12 +671,19 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
         r.in2 = nullptr; r.in2_bs = 0; r.Cin2 = 0; r.w2 = nullptr; r.bias = nullptr;
         r.res = out; r.res_bs = out_bs;
         if (!lass_wino4_supported(CONV2_IDENT, r, sk)) return fail(c, LASS_ERR_STATE, "conv2 with the shortcut as residual");
-        HIP_TRY(c, lass_launch_wino4(CONV2_IDENT, r, st, sk));
+        Wino4VPre vp;
+        if (vshape && lass_wino4_vpre_supported(CONV2_IDENT, r, sk))
+            if (int rv = vprep_slot(rb.cout, &vp)) return rv;
+        HIP_TRY(c, lass_launch_wino4(CONV2_IDENT, r, st, sk, vp));
     } else if (rb.cin == rb.cout) {
         if (bf2)
             HIP_TRY(c, lass_launch_conv_bf16(k2, q, st));
-        else if (wino2 && (x0 || ksplit > 0) && q.w_wino4 && lass_wino4_supported(k2, q, sk))  // (ksplit: encoder_block6, 1 x 2 pool)
-            HIP_TRY(c, lass_launch_wino4(k2, q, st, sk));
+        else if (wino2 && (x0 || ksplit > 0) && q.w_wino4 && lass_wino4_supported(k2, q, sk)) {  // (ksplit: encoder_block6, 1 x 2 pool)
+            Wino4VPre vp;
+            if (vshape && lass_wino4_vpre_supported(k2, q, sk))
+                if (int rv = vprep_slot(rb.cout, &vp)) return rv;
+            HIP_TRY(c, lass_launch_wino4(k2, q, st, sk, vp));
+        }
         else if (wino2)
             HIP_TRY(c, lass_launch_wino(k2, q, st));
         else
@@ -683,6 +745,7 @@ struct Plan {
     size_t mag, cosv, sinv, x0[kMaxBranches], shift, a2, cat[6], pool[6], center, decout[6], oreal, oimag;
     size_t kpart = 0;  // split-K partials of the 32 x 16 Winograd blocks (one slot: the launches of a plan run in stream order)
     bool has_kpart = false;
+    size_t vprep = 0, vprep_floats = 0;  // the V image of the V-from-memory layers: one slot, sized to the largest of them
     int eh[7], ew[7];  // encoder block spatial sizes
 };
 
@@ -730,17 +793,21 @@ int make_plan(const lass_ctx* c, int B, int L, Plan* pl) {
     pl->a2 = bump(t, a2max);
     pl->oreal = bump(t, spec); pl->oimag = bump(t, spec);
     // (a half-batch plan has its own slot: the two branches of the replayed graph never share partials)
-    size_t kmax = 0;
+    size_t kmax = 0, vmax = 0;
     for (int i = 1; i < 7; ++i) {
         const ResBlock& rb = trunk_block(c, i);
+        vmax = std::max(vmax, wino4_vprep_floats(c, rb, B, pl->eh[i], pl->ew[i]));
         kmax = std::max(kmax, wino4_split_floats(rb, wino4_splits(c, rb, B, pl->eh[i], pl->ew[i]), B, pl->eh[i], pl->ew[i]));
     }
     for (int d = 0; d < 6; ++d) {
         const ResBlock& rb = c->dec[d];
+        vmax = std::max(vmax, wino4_vprep_floats(c, rb, B, pl->eh[5 - d], pl->ew[5 - d]));
         kmax = std::max(kmax, wino4_split_floats(rb, wino4_splits(c, rb, B, pl->eh[5 - d], pl->ew[5 - d]), B, pl->eh[5 - d], pl->ew[5 - d]));
     }
     pl->has_kpart = kmax > 0;
     if (kmax) pl->kpart = bump(t, kmax);
+    pl->vprep_floats = vmax;
+    if (vmax) pl->vprep = bump(t, vmax);
     return 0;
 }
 
@@ -770,9 +837,9 @@ void drop_graphs(lass_ctx* c) {
 // A batch is split into two overlapping half-batches when it is large enough for each half to fill the GPU on its own
 bool split_halves(const lass_ctx* c, int B) { return c->split_batch > 0 && !c->profiling && B >= 8 && (B % 2) == 0; }
 
-// Stage calls have no workspace plan: their split-K partials live in a buffer of the context that grows on demand (the call must
-// not be under stream capture when it does).  hipFree waits for the launches that still use the old buffer.
-int stage_kpart(lass_ctx* c, const ResBlock& rb, int B, int H, int W, BlockFusions* f) {
+// Stage calls have no workspace plan: their split-K partials and their V image live in two buffers of the context that grow on
+// demand (the call must not be under stream capture when one does).  hipFree waits for the launches that still use the old buffer.
+int stage_scratch(lass_ctx* c, const ResBlock& rb, int B, int H, int W, BlockFusions* f) {
     const size_t need = wino4_split_floats(rb, wino4_splits(c, rb, B, H, W), B, H, W);
     if (need > c->stage_part_floats) {
         if (c->stage_part) HIP_TRY(c, hipFree(c->stage_part));
@@ -782,6 +849,20 @@ int stage_kpart(lass_ctx* c, const ResBlock& rb, int B, int H, int W, BlockFusio
         c->stage_part_floats = need;
     }
     if (need) f->kpart = c->stage_part;
+    // ... and the V image of the V-from-memory layers: the caller's buffer if one is set (lass_set_wino4_vprep_buffer), as it is
+    const size_t vneed = wino4_vprep_floats(c, rb, B, H, W);
+    if (c->stage_v_user) {
+        if (vneed) { f->vws = c->stage_v_user; f->vws_floats = c->stage_v_user_floats; }
+        return 0;
+    }
+    if (vneed > c->stage_v_floats) {
+        if (c->stage_v) HIP_TRY(c, hipFree(c->stage_v));
+        c->stage_v = nullptr;
+        c->stage_v_floats = 0;
+        HIP_TRY(c, hipMalloc((void**)&c->stage_v, vneed * sizeof(float)));
+        c->stage_v_floats = vneed;
+    }
+    if (vneed) { f->vws = c->stage_v; f->vws_floats = c->stage_v_floats; }
     return 0;
 }
 
@@ -830,6 +911,7 @@ static int create_impl(lass_ctx** out, int device_id, const Geometry& geom) {
     if (const char* e = getenv("LASS_FUSE_BLOCK")) c->fuse_block = atoi(e) != 0;
     if (const char* e = getenv("LASS_FUSE_UP")) c->fuse_up = atoi(e) != 0;
     if (const char* e = getenv("LASS_WINO4")) c->wino4_mincin = atoi(e);
+    if (const char* e = getenv("LASS_WINO4_VPREP")) c->vprep_mode = std::max(0, std::min(2, atoi(e)));  // A/B: lass_set_wino4_vprep
     if (const char* e = getenv("LASS_SPLIT")) c->split_batch = std::max(0, std::min(2, atoi(e)));
     if (const char* e = getenv("LASS_GRAPH")) c->use_graph = atoi(e) != 0;
     c->prof.resize(P_COUNT);
@@ -905,6 +987,7 @@ int lass_destroy(lass_ctx* c) {
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     (void)hipFree(c->tw2k);
     (void)hipFree(c->stage_part);
+    (void)hipFree(c->stage_v);
     delete c;
     return 0;
 }
@@ -1215,7 +1298,7 @@ int lass_convblock(lass_ctx* c, const char* prefix, const float* x, int B, int H
     if (!rb) return fail(c, LASS_ERR_ARG, std::string("lass_convblock: unknown block '") + prefix + "'");
     const long HW = (long)H * W;
     BlockFusions f;
-    if ((r = stage_kpart(c, *rb, B, H, W, &f))) return r;
+    if ((r = stage_scratch(c, *rb, B, H, W, &f))) return r;
     return run_resblock(c, *rb, x, rb->cin * HW, B, H, W, shift, scratch, y, rb->cout * HW, (hipStream_t)stream, f);
 }
 
@@ -1237,7 +1320,7 @@ int lass_encoder_block(lass_ctx* c, const char* name, const float* x, int B, int
         hipStream_t st = (hipStream_t)stream;
         BlockFusions f;
         if (fuse) { f.pool_out = pool; f.pool_h = e.dh; }
-        if ((r = stage_kpart(c, rb, B, H, W, &f))) return r;
+        if ((r = stage_scratch(c, rb, B, H, W, &f))) return r;
         r = run_resblock(c, rb, x, rb.cin * HW, B, H, W, shift, scratch, y, rb.cout * HW, st, f);
         if (r) return r;
         if (pooled && !fuse) HIP_TRY(c, lass_launch_pool(y, rb.cout * HW, B, rb.cout, H, W, e.dh, e.dw, pool, st));
@@ -1516,6 +1599,7 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
             if (i >= 1 && i <= 4 && use_pc[i - 1]) f.cat_in = &pc[i - 1];
             if (i < 4 && use_pc[i]) f.pool_copies = &pc[i];
             if (pl.has_kpart) f.kpart = F(pl.kpart);
+            if (pl.vprep_floats) { f.vws = F(pl.vprep); f.vws_floats = pl.vprep_floats; }
             r = run_resblock(c, rb, x, rb.cin * HW, B, H, W, shift, F(pl.a2), o, o_bs, st, f);
             if (r) return r;
         }
@@ -1550,6 +1634,7 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
         const MaskHead head{mag_m, cos_m, sin_m, F(pl.oreal), F(pl.oimag), T, g.nbins};
         if (d == 5) f.head = &head;
         if (pl.has_kpart) f.kpart = F(pl.kpart);
+        if (pl.vprep_floats) { f.vws = F(pl.vprep); f.vws_floats = pl.vprep_floats; }
         r = run_resblock(c, rb, F(pl.cat[d]), rb.cin * HW, B, H, W, shift, F(pl.a2), F(pl.decout[d]), rb.cout * HW, st, f);
         if (r) return r;
         x = F(pl.decout[d]);
@@ -1689,6 +1774,20 @@ int lass_set_wino4_splits(lass_ctx* c, int splits) {
     if (!c || (splits != 0 && splits != 1 && splits != 2 && splits != 4)) return fail(c, LASS_ERR_ARG, "lass_set_wino4_splits: 0, 1, 2 or 4");
     c->ksplit_force = splits;
     ++c->gen;  // captured graphs hold the launches of the previous choice (and workspace sizes follow it)
+    return 0;
+}
+
+int lass_set_wino4_vprep(lass_ctx* c, int mode) {
+    if (!c || mode < 0 || mode > 2) return fail(c, LASS_ERR_ARG, "lass_set_wino4_vprep: 0, 1 or 2");
+    c->vprep_mode = mode;
+    ++c->gen;  // as lass_set_wino4_splits: other launches, another workspace size
+    return 0;
+}
+
+int lass_set_wino4_vprep_buffer(lass_ctx* c, float* v, size_t floats) {
+    if (!c || (v && !floats)) return fail(c, LASS_ERR_ARG, "lass_set_wino4_vprep_buffer: a buffer and its size, or NULL");
+    c->stage_v_user = v;
+    c->stage_v_user_floats = v ? floats : 0;
     return 0;
 }
 

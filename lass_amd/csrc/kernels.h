@@ -96,12 +96,27 @@ struct ConvArgs {
 // wino4.hip: images that tile only into 32-row x 16-column blocks (the 16-bin level of a clip whose frame count at that level
 // is a multiple of 32); the 8 x 64 / 16 x 32 blocks take every geometry they fit
 inline bool lass_wino4_narrow(int H, int W) { return W % 32 == 16 && H % 32 == 0; }
+// The block geometry of an H x W image, as tile columns per block (TC; a block is 32 tiles of 4 x 4 outputs): 16 = 8 rows x 64
+// columns, 8 = 16 rows x 32 columns, 4 = 32 rows x 16 columns (narrow), 0 = none fits.  The one rule behind lass_wino4_supported,
+// the launchers and the sizing of the V image.
+inline int lass_wino4_block_tc(int H, int W) {
+    if (W % 64 == 0 && H % 8 == 0) return 16;
+    if (W % 32 == 0 && H % 16 == 0) return 8;
+    return lass_wino4_narrow(H, W) ? 4 : 0;
+}
 // Split-K on those blocks: the input-channel loop is dealt to n workgroups per (block, cout group, clip); each stores its partial
 // of the conv sum, [n][B][N][H][W] dense in part, and a combine launch sums them in split order and applies the epilogue.
 // (Not part of ConvArgs: the kernels that take only ConvArgs keep their argument block, and with it their compiled code.)
 struct Wino4Split {
     int n = 1;
     float* part = nullptr;
+};
+
+// The transformed input image of a layer, formed once by a prep launch instead of by every cout group's workgroups:
+// v[clip][block][chunk = cin / 8][36][256] f32, lass_wino4_vpre_floats() of them; null = the kernels transform their own input.
+// (Beside ConvArgs for the same reason as Wino4Split.)
+struct Wino4VPre {
+    float* v = nullptr;
 };
 
 enum ConvKind { CONV1_ACT = 0, CONV2_IDENT = 1, CONV2_SHORTCUT = 2, TCONV_ACT = 3, CONV1_ACT_PRE = 4, CONV2_IDENT_PRE = 5 };
@@ -117,7 +132,11 @@ hipError_t lass_launch_wino_shortcut_weights(const float* w, int Cout, int Cin, 
 // ---- wino4.hip (Winograd F(4x4,3x3): 36 instead of 64 MFMA multiplies per 16 outputs; W % 32 == 0) ---------------------------
 // CONV2_IDENT: conv2 + a residual read from res (which may be `out` itself: every element is read and written by one lane)
 bool lass_wino4_supported(ConvKind kind, const ConvArgs& p, const Wino4Split& sk = Wino4Split());
-hipError_t lass_launch_wino4(ConvKind kind, const ConvArgs& p, hipStream_t stream, const Wino4Split& sk = Wino4Split());
+hipError_t lass_launch_wino4(ConvKind kind, const ConvArgs& p, hipStream_t stream, const Wino4Split& sk = Wino4Split(),
+                             const Wino4VPre& vp = Wino4VPre());
+// V from memory (vp.v set): CONV1_ACT and CONV2_IDENT only, a prep launch in front of the conv launch
+bool lass_wino4_vpre_supported(ConvKind kind, const ConvArgs& p, const Wino4Split& sk = Wino4Split());
+size_t lass_wino4_vpre_floats(int B, int Cin, int H, int W);
 hipError_t lass_launch_wino4_weights(const float* w, int Cout, int Cin, float* U, hipStream_t stream);  // w (Cout, Cin, 3, 3)
 
 // ---- pw_gemm.hip (f32 pointwise GEMMs with a 128-cout workgroup tile; H*W % 4 == 0, N % 128 == 0, K % 32 == 0) ------------

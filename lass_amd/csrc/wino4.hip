@@ -32,6 +32,7 @@ namespace {
 
 constexpr int F_PRO = 1, F_PHASEB = 2, F_BIAS = 4, F_RES = 8, F_EPIACT = 16, F_PRECONV = 64, F_RESPRE = 128, F_MASK = 1024;  // as wino.hip
 constexpr int F_SPLITK = 2048;  // this workgroup runs one share of the input channels and stores its partial sums (Wino4Split)
+constexpr int F_VPRE = 4096;    // the transformed input V is read from memory (Wino4VPre): wino4_vprep_kernel wrote it, once per layer
 constexpr int NTHREADS = 256;
 constexpr int KC = 8;
 constexpr int NXI = 36;
@@ -68,13 +69,56 @@ __device__ __forceinline__ void at6(const float (&m)[6], float (&y)[4]) {
 template <int TC, int FLAGS>
 __global__ __launch_bounds__(NTHREADS, 2) void wino4_kernel(ConvArgs p) {
     const Wino4Split sk;  // (unsplit)
+    const Wino4VPre vp;   // (transforms its own input)
 #include "wino4_body.h"
 }
 // ... and one share of the input channels, partial sums out (FLAGS0: F_PRO or nothing)
 template <int TC, int FLAGS0>
 __global__ __launch_bounds__(NTHREADS, 2) void wino4_splitk_kernel(ConvArgs p, Wino4Split sk) {
     constexpr int FLAGS = FLAGS0 | F_SPLITK;
+    const Wino4VPre vp;
 #include "wino4_body.h"
+}
+// ... and both with the transformed input image V read from memory instead of formed here (FLAGS0: F_EPIACT, F_RES or F_SPLITK).
+// The Cout / 32 workgroups of a 32-tile block all need the same V: formed in the kernel, each of them repeats the prologue, the
+// padding and the 6x6 transform of its 32 tiles x 8 channels per chunk - 252 vector instructions per wave and chunk beside 72
+// MFMAs on the datapath the two share.  Here the chunk loop is 9 + 9 LDS-DMA pieces per wave, a wait and the same MFMA phase.
+template <int TC, int FLAGS0>
+__global__ __launch_bounds__(NTHREADS, 2) void wino4_vpre_kernel(ConvArgs p, Wino4Split sk, Wino4VPre vp) {
+    constexpr int FLAGS = FLAGS0 | F_VPRE;
+#include "wino4_body.h"
+}
+
+// The prep launch of those: one workgroup per (32-tile block, 8-channel chunk, clip), one (tile, channel) item per thread - the
+// item mapping, loads, prologue, padding rule and transform of the conv kernels (wino4_input.h, the same text).  The 36-KiB image
+// is staged in LDS exactly as the conv kernels lay it out (XOR swizzle included) and leaves as 16-byte rows, so the consumer's copy
+// is linear: Vg[clip][block][chunk][36][256].  FLAGS: F_PRO or 0.
+template <int TC, int FLAGS>
+__global__ __launch_bounds__(NTHREADS) void wino4_vprep_kernel(ConvArgs p, Wino4VPre vp) {
+    constexpr bool PRO = (FLAGS & F_PRO) != 0, PRE = false;
+    static_assert((FLAGS & ~F_PRO) == 0, "a prologue at most");
+    constexpr int TR = 32 / TC;
+    constexpr int OR_ = 4 * TR, OC = 4 * TC;
+    __shared__ __attribute__((aligned(16))) float lv[V_F];
+    const int tid = threadIdx.x;
+    const unsigned nchunk = (unsigned)(p.Cin / KC);
+    const unsigned lin = blockIdx.x;  // chunk fastest: neighbouring workgroups write neighbouring slabs
+    const int ch = (int)(lin % nchunk);
+    const int bx_ = (int)(lin / nchunk % (unsigned)p.gx), b = (int)(lin / nchunk / (unsigned)p.gx);
+    const int tiles_x = p.W / OC;
+    const int y0 = (bx_ / tiles_x) * OR_, x0 = (bx_ % tiles_x) * OC;
+    const int HW = p.H * p.W;
+    const float* in_b = p.in + (size_t)b * p.in_bs;
+    const float* sc = PRO ? p.pro_scale : nullptr;
+    const float* sh = PRO ? p.pro_shift + (size_t)b * p.pro_shift_bs : nullptr;
+#include "wino4_input.h"
+    pload(ch);
+    pprocess();
+    __syncthreads();
+    float4* dst = reinterpret_cast<float4*>(vp.v + (((size_t)b * p.gx + bx_) * nchunk + ch) * V_F);
+    const float4* src = reinterpret_cast<const float4*>(lv);
+#pragma unroll
+    for (int i = 0; i < V_F / 4 / NTHREADS; ++i) dst[i * NTHREADS + tid] = src[i * NTHREADS + tid];
 }
 
 // Combine of a split launch: out = epilogue(sum over the splits, in split order, of the partials wino4_splitk_kernel left in
@@ -170,11 +214,53 @@ hipError_t launch_wino4_tc(const ConvArgs& p0, hipStream_t stream) {
 
 template <int FLAGS>
 hipError_t launch_wino4(const ConvArgs& p, hipStream_t stream) {
-    if (p.W % 64 == 0 && p.H % 8 == 0) return launch_wino4_tc<16, FLAGS>(p, stream);  // 8 rows x 64 columns
-    if (p.W % 32 == 0 && p.H % 16 == 0) return launch_wino4_tc<8, FLAGS>(p, stream);  // 16 rows x 32 columns
+    const int tc = lass_wino4_block_tc(p.H, p.W);
+    if (tc == 16) return launch_wino4_tc<16, FLAGS>(p, stream);  // 8 rows x 64 columns
+    if (tc == 8) return launch_wino4_tc<8, FLAGS>(p, stream);    // 16 rows x 32 columns
     // 32 rows x 16 columns (lass_wino4_narrow): CONV1_ACT and CONV2_IDENT only (lass_wino4_supported)
     if constexpr (FLAGS == (F_PRO | F_EPIACT) || FLAGS == F_RES)
-        if (lass_wino4_narrow(p.H, p.W)) return launch_wino4_tc<4, FLAGS>(p, stream);
+        if (tc == 4) return launch_wino4_tc<4, FLAGS>(p, stream);
+    return hipErrorInvalidValue;
+}
+
+// V from memory: the prep launch (PRO: conv1's prologue), then the conv kernel of the same block geometry.  MAIN: F_EPIACT (conv1),
+// F_RES (identity conv2) or F_SPLITK; a split launch is followed by its combine (COMB), as in launch_wino4_split.
+template <int TC, int MAIN, int COMB>
+hipError_t launch_wino4_vpre_tc(const ConvArgs& p0, const Wino4Split& sk, const Wino4VPre& vp, bool pro, hipStream_t stream) {
+    ConvArgs p = p0;
+    constexpr int OR_ = 4 * (32 / TC), OC = 4 * TC;
+    constexpr bool SPLIT = (MAIN & F_SPLITK) != 0;
+    const int n = SPLIT ? sk.n : 1;
+    p.gx = (p.W / OC) * (p.H / OR_);
+    p.gy = p.N / 32;
+    p.xcd_map = ((long)p.gx * p.B * n) % 8 == 0;
+    const dim3 pgrid((unsigned)((long)p.gx * (p.Cin / KC) * p.B));
+    if (pro)
+        hipLaunchKernelGGL((wino4_vprep_kernel<TC, F_PRO>), pgrid, dim3(NTHREADS), 0, stream, p, vp);
+    else
+        hipLaunchKernelGGL((wino4_vprep_kernel<TC, 0>), pgrid, dim3(NTHREADS), 0, stream, p, vp);
+    if (hipError_t e = hipGetLastError()) return e;
+    Wino4Split s1 = sk;
+    if (!SPLIT) s1 = Wino4Split();
+    hipLaunchKernelGGL((wino4_vpre_kernel<TC, MAIN>), dim3((unsigned)((long)p.gx * p.gy * p.B * n)), dim3(NTHREADS), 0, stream, p, s1, vp);
+    if (hipError_t e = hipGetLastError()) return e;
+    if constexpr (SPLIT) {
+        const long items = (long)p.B * p.N * (p.H / 2) * (p.W / 4);
+        hipLaunchKernelGGL((wino4_combine_kernel<COMB>), dim3((unsigned)((items + 255) / 256)), dim3(256), 0, stream, p, sk);
+        return hipGetLastError();
+    }
+    return hipSuccess;
+}
+
+// EPI: F_EPIACT (conv1, prologue in the prep launch) or F_RES (identity conv2, none)
+template <int EPI>
+hipError_t launch_wino4_vpre(const ConvArgs& p, const Wino4Split& sk, const Wino4VPre& vp, hipStream_t stream) {
+    constexpr bool pro = EPI == F_EPIACT;
+    const int tc = lass_wino4_block_tc(p.H, p.W);
+    if (tc == 16) return launch_wino4_vpre_tc<16, EPI, 0>(p, sk, vp, pro, stream);
+    if (tc == 8) return launch_wino4_vpre_tc<8, EPI, 0>(p, sk, vp, pro, stream);
+    if (tc == 4)
+        return sk.n > 1 ? launch_wino4_vpre_tc<4, F_SPLITK, EPI>(p, sk, vp, pro, stream) : launch_wino4_vpre_tc<4, EPI, 0>(p, sk, vp, pro, stream);
     return hipErrorInvalidValue;
 }
 
@@ -197,8 +283,8 @@ hipError_t launch_wino4_split(const ConvArgs& p0, const Wino4Split& sk, hipStrea
 }  // namespace
 
 bool lass_wino4_supported(ConvKind kind, const ConvArgs& p, const Wino4Split& sk) {
-    const bool narrow = lass_wino4_narrow(p.H, p.W);  // (excludes the two wider geometries: W % 32 == 16)
-    if (!(p.w_wino4 && ((p.W % 64 == 0 && p.H % 8 == 0) || (p.W % 32 == 0 && p.H % 16 == 0) || narrow) && p.Cin % KC == 0 && p.N % 32 == 0 &&
+    const bool narrow = lass_wino4_block_tc(p.H, p.W) == 4;  // lass_wino4_narrow (excludes the two wider geometries: W % 32 == 16)
+    if (!(p.w_wino4 && lass_wino4_block_tc(p.H, p.W) != 0 && p.Cin % KC == 0 && p.N % 32 == 0 &&
           p.Nw % 32 == 0 && (unsigned long long)p.Cin * p.H * p.W * 4ull < 0xFFFF0000ull))
         return false;
     if (narrow) {  // conv1 and the identity conv2 (fused 2 x 2 or 1 x 2 pool), whole or split-K with the combine behind it
@@ -226,8 +312,25 @@ bool lass_wino4_supported(ConvKind kind, const ConvArgs& p, const Wino4Split& sk
     }
 }
 
-hipError_t lass_launch_wino4(ConvKind kind, const ConvArgs& p, hipStream_t stream, const Wino4Split& sk) {
+size_t lass_wino4_vpre_floats(int B, int Cin, int H, int W) { return (size_t)B * Cin * (size_t)(H * W / 16) * NXI; }
+
+bool lass_wino4_vpre_supported(ConvKind kind, const ConvArgs& p, const Wino4Split& sk) {
+    // conv1 and the identity conv2 (whole or split-K): the kinds without a fused shortcut phase or output head; the V image of one
+    // (clip, block) is addressed through a 32-bit buffer descriptor
+    return (kind == CONV1_ACT || kind == CONV2_IDENT) && lass_wino4_supported(kind, p, sk) && !p.mask_re &&
+           (unsigned long long)(p.Cin / KC) * V_F * 4ull < 0xFFFF0000ull;
+}
+
+hipError_t lass_launch_wino4(ConvKind kind, const ConvArgs& p, hipStream_t stream, const Wino4Split& sk, const Wino4VPre& vp) {
     if (!lass_wino4_supported(kind, p, sk) || !p.in || (!p.out && !p.mask_re)) return hipErrorInvalidValue;
+    if (vp.v) {
+        if (!lass_wino4_vpre_supported(kind, p, sk)) return hipErrorInvalidValue;
+        if (kind == CONV1_ACT) {
+            if (!p.pro_scale || !p.pro_shift || !p.epi_scale || !p.epi_shift) return hipErrorInvalidValue;
+            return launch_wino4_vpre<F_EPIACT>(p, sk, vp, stream);
+        }
+        return launch_wino4_vpre<F_RES>(p, sk, vp, stream);
+    }
     switch (kind) {
         case CONV1_ACT:
         case CONV1_ACT_PRE:

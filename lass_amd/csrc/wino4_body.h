@@ -1,5 +1,5 @@
 // wino4_body.h - the body of wino4.hip's conv kernels, included ONCE PER KERNEL inside the function braces: wino4_kernel
-// (ConvArgs alone) and wino4_splitk_kernel (ConvArgs + Wino4Split).  In scope: TC, FLAGS, `p`, `sk`.  Text inclusion and not an
+// (ConvArgs alone), wino4_splitk_kernel (ConvArgs + Wino4Split) and wino4_vpre_kernel (+ Wino4VPre).  In scope: TC, FLAGS, `p`, `sk`, `vp`.  Text inclusion and not an
 // inlined device function on purpose: hipcc schedules a kernel whose body arrives through a call differently, and the unsplit
 // kernels are to stay instruction for instruction what they were before the split-K variant existed.
     constexpr bool PRO = (FLAGS & F_PRO) != 0, EPI = (FLAGS & F_EPIACT) != 0, SC = (FLAGS & F_PHASEB) != 0;
@@ -13,7 +13,10 @@
     static_assert(!MASK || SC, "the output head sits behind decoder_block6's conv2 + shortcut");
     static_assert(!RES || (!SC && !EPI), "conv2 with a residual in place of the fused shortcut");
     constexpr bool SPLIT = (FLAGS & F_SPLITK) != 0;  // partial sums only: the epilogue runs in wino4_combine_kernel
-    static_assert(!SPLIT || (FLAGS & ~(F_SPLITK | F_PRO)) == 0, "a split launch has a prologue at most");
+    static_assert(!SPLIT || (FLAGS & ~(F_SPLITK | F_PRO | F_VPRE)) == 0, "a split launch has a prologue at most");
+    // the transformed input arrives from memory (Wino4VPre, written by wino4_vprep_kernel): no patch loads, prologue or transform here
+    constexpr bool VPRE = (FLAGS & F_VPRE) != 0;
+    static_assert(!VPRE || (FLAGS & ~(F_VPRE | F_SPLITK | F_EPIACT | F_RES)) == 0, "conv1 / identity conv2 / split share: the prologue ran in the prep launch");
     constexpr int TR = 32 / TC;
     constexpr int OR_ = 4 * TR, OC = 4 * TC;
     constexpr int NCO = 32;  // output channels of the workgroup
@@ -85,130 +88,54 @@
     const unsigned ulane = (unsigned)lane * 16u;
     const v4i32 uw = make_rsrc_words(p.w_wino4, (unsigned)(NXI * p.Cin * p.Nw) * 4u);
 
-    // ---- this thread's item: tile pt (0..31) and channel c8 (0..7) of the chunk; its 6x6 patch, top-left (gy0, gx0) ------
-    const int pt = tid & 31, c8 = (tid & 255) >> 5;  // (tid < 256: see afrag)
-    const int pty = pt / TC, ptx = pt % TC;
-    const int gy0 = y0 + 4 * pty - 1, gx0 = x0 + 4 * ptx - 1;
-    const bool left = gx0 < 0, right = gx0 + 5 >= p.W;
-    unsigned vo_c[6], vo_l[6], vo_r[6], rowok = 0;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        const int gy = gy0 + i;
-        const int row = (PRE ? 0 : c8 * HW) + min(max(gy, 0), p.H - 1) * p.W;
-        vo_c[i] = 4u * (unsigned)(row + gx0 + 1);                 // columns gx0+1 .. gx0+4: 16-byte aligned, always inside
-        vo_l[i] = 4u * (unsigned)(row + (left ? 0 : gx0));        // column gx0 (clamped at the left edge)
-        vo_r[i] = 4u * (unsigned)(row + (right ? p.W - 1 : gx0 + 5));
-        rowok |= (gy >= 0 && gy < p.H ? 1u : 0u) << i;
-    }
-    const __amdgpu_buffer_rsrc_t in_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in_b), 0, (int)((unsigned)(PRE ? 1 : p.Cin) * (unsigned)HW * 4u), 0x00020000);
-    const bool edge = left || right || rowok != 0x3fu;  // this item's patch reaches into the zero padding
-    float4 pc[6];
-    float pl[6], pr[6], ps = 1.f, ph = 0.f;
-    const unsigned tvo = (unsigned)c8 * 4u;  // this item's entry of a per-channel table, within the chunk
-    const auto tab_rsrc = [&](const float* t, int n) {
-        return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(t), 0, n * 4, 0x00020000);
-    };
-    const __amdgpu_buffer_rsrc_t sc_rsrc = tab_rsrc(PRO ? sc : p.in, p.Cin), sh_rsrc = tab_rsrc(PRO ? sh : p.in, p.Cin);
-    const __amdgpu_buffer_rsrc_t pw_rsrc = tab_rsrc(PRE ? p.pre_w : p.in, 32), pb_rsrc = tab_rsrc(PRE ? p.pre_b : p.in, 32);
-    auto pload = [&](int ch) {
-        const unsigned soff = PRE ? 0u : (unsigned)(ch * KC * HW) * 4u;
-        if (!PRE || ch == 0)  // PRE: every channel is an affine function of the one x0 patch, loaded once
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            pc[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, (int)vo_c[i], (int)soff, 0));
-            pl[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(in_rsrc, (int)vo_l[i], (int)soff, 0));
-            pr[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(in_rsrc, (int)vo_r[i], (int)soff, 0));
-        }
-        // The table reads are buffer loads as well (one vector-memory instruction each, by construction): wait_vmcnt<NLOAD> below
-        // counts them, and a plain C++ load could be merged, hoisted or scalarised by the compiler behind the count's back.
-        const unsigned toff = (unsigned)(ch * KC) * 4u;
-        if (PRO) {
-            ps = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(sc_rsrc, (int)tvo, (int)toff, 0));
-            ph = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(sh_rsrc, (int)tvo, (int)toff, 0));
-        }
-        if (PRE) {  // leaky(bn(pre_w x0 + pre_b) + beta) = leaky(x0 * (pre_w s) + (pre_b s + h))
-            const float pw = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(pw_rsrc, (int)tvo, (int)toff, 0));
-            const float pb = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(pb_rsrc, (int)tvo, (int)toff, 0));
-            ph = fmaf(pb, ps, ph);
-            ps = pw * ps;
-        }
-    };
-    constexpr int NLOAD = (PRE ? 0 : 6 * 3) + (PRO ? 2 : 0) + (PRE ? 2 : 0);  // vector-memory operations of one pload (chunks >= 1)
-    // V destination of this item: row (xi, kq = c8 % 4), column tile ^ swizzle, k-step c8 / 4; xi stride = 4 * 64 floats
-    float* vdst = lv + ((c8 & 3) * 32 + (pt ^ ((c8 & 1) << 4))) * 2 + (c8 >> 2);
-    auto pprocess = [&]() {
-        float d[6][6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            const float v[6] = {pl[i], pc[i].x, pc[i].y, pc[i].z, pc[i].w, pr[i]};
-#pragma unroll
-            for (int jx = 0; jx < 6; ++jx) d[i][jx] = PRO ? leaky(fmaf(v[jx], ps, ph)) : v[jx];
-        }
-        // zero padding comes AFTER the activation (resunet.py:150, conv padding) and touches only the outer ring of the patch
-        // (row 0 / 5, column 0 / 5) of the items at the image border: wave-uniform branch, skipped by interior waves
-        if (__builtin_amdgcn_ballot_w64(edge) != 0) {
-            const bool r0 = (rowok & 1u) != 0, r5 = (rowok & 32u) != 0;
-#pragma unroll
-            for (int jx = 0; jx < 6; ++jx) {
-                d[0][jx] = r0 ? d[0][jx] : 0.f;
-                d[5][jx] = r5 ? d[5][jx] : 0.f;
-            }
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-                d[i][0] = left ? 0.f : d[i][0];
-                d[i][5] = right ? 0.f : d[i][5];
-            }
-        }
-        float tt[6][6];  // B^T d: columns
-#pragma unroll
-        for (int jx = 0; jx < 6; ++jx) {
-            const float col[6] = {d[0][jx], d[1][jx], d[2][jx], d[3][jx], d[4][jx], d[5][jx]};
-            float r[6];
-            bt6(col, r);
-#pragma unroll
-            for (int i = 0; i < 6; ++i) tt[i][jx] = r[i];
-        }
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {  // (B^T d) B: rows
-            float r[6];
-            bt6(tt[i], r);
-#pragma unroll
-            for (int jx = 0; jx < 6; ++jx) vdst[(i * 6 + jx) * 256] = r[jx];
-        }
-    };
+#include "wino4_input.h"
+    // VPRE: the V slabs of this (clip, block), one per chunk, each the LDS image byte for byte
+    const unsigned lv_addr = (unsigned)(size_t)(__attribute__((address_space(3))) float*)lv;
+    const v4i32 vw = make_rsrc_words(VPRE ? vp.v + ((size_t)b * p.gx + bx_) * (size_t)(p.Cin / KC) * V_F : nullptr,
+                                     (unsigned)(p.Cin / KC) * (unsigned)(V_F * 4));
 
     // chunks [ch0, nch) of 8 input channels: all of them, or share ks of a split launch
     const int ch0 = SPLIT ? ks * (p.Cin / KC) / sk.n : 0;
     const int nch = SPLIT ? (ks + 1) * (p.Cin / KC) / sk.n : p.Cin / KC;
-    pload(ch0);
+    if constexpr (!VPRE) pload(ch0);
     lds_barrier();  // epilogue tables visible
     for (int ch = ch0; ch < nch; ++ch) {
         lds_barrier();  // previous chunk's MFMAs have finished reading V / U
         __builtin_amdgcn_s_setprio(2);
         // The patch of this chunk was requested a whole MFMA phase ago.  Pin it as arrived HERE: hipcc counts only its own
         // loads, so a wait placed behind the LDS-DMA below would be vmcnt(0) and drain the weight slab before the transform.
+        if constexpr (!VPRE) {
 #pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            asm volatile("" : "+v"(pc[i].x), "+v"(pc[i].y), "+v"(pc[i].z), "+v"(pc[i].w), "+v"(pl[i]), "+v"(pr[i]));
+            for (int i = 0; i < 6; ++i) {
+                asm volatile("" : "+v"(pc[i].x), "+v"(pc[i].y), "+v"(pc[i].z), "+v"(pc[i].w), "+v"(pl[i]), "+v"(pr[i]));
+            }
+            if (PRO) asm volatile("" : "+v"(ps), "+v"(ph));
         }
-        if (PRO) asm volatile("" : "+v"(ps), "+v"(ph));
         // weight slab of (chunk ch, cout group n0 / 32): 36 pieces of 1 KiB, 9 per wave
 #pragma unroll
         for (int i = 0; i < 9; ++i) {
             const unsigned piece = (unsigned)(wave * 9 + i) * 1024u;
             lds_dma_16B(uw, ulane, (unsigned)ch * slab_pitch + slab_n0 + piece, lu_addr + piece);
         }
-        __builtin_amdgcn_sched_barrier(0);
-        pprocess();
-        __builtin_amdgcn_sched_barrier(0);
-        const bool pf = ch + 1 < nch;
-        if (pf) pload(ch + 1);
-        __builtin_amdgcn_sched_barrier(0);
-        if (pf)
-            wait_vmcnt<NLOAD>();  // this wave's pieces of U(ch) have landed; the patch of chunk ch+1 stays in flight
-        else
+        if constexpr (VPRE) {  // ... and the V slab of (chunk ch, this block): 9 more pieces per wave, nothing else in flight
+#pragma unroll
+            for (int i = 0; i < 9; ++i) {
+                const unsigned piece = (unsigned)(wave * 9 + i) * 1024u;
+                lds_dma_16B(vw, ulane, (unsigned)ch * (unsigned)(V_F * 4) + piece, lv_addr + piece);
+            }
             wait_vmcnt<0>();
+        } else {
+            __builtin_amdgcn_sched_barrier(0);
+            pprocess();
+            __builtin_amdgcn_sched_barrier(0);
+            const bool pf = ch + 1 < nch;
+            if (pf) pload(ch + 1);
+            __builtin_amdgcn_sched_barrier(0);
+            if (pf)
+                wait_vmcnt<NLOAD>();  // this wave's pieces of U(ch) have landed; the patch of chunk ch+1 stays in flight
+            else
+                wait_vmcnt<0>();
+        }
         lds_barrier();  // V visible, every wave's U pieces landed
         __builtin_amdgcn_s_setprio(0);
         // 36 GEMM steps x 2 k-steps; two xi in flight so that no MFMA depends on its predecessor (40-cycle dependent latency)
