@@ -174,8 +174,8 @@ def conv_layer_table(t_pad: int, f: int = F_CROP) -> List[Dict]:
 
 def wino4_routed(rows: List[Dict], min_cin: int = 32) -> set:
     """Names of the 3x3 rows of `conv_layer_table` that the f32 path runs as Winograd F(4x4,3x3) (csrc/wino4.hip; 36 instead
-    of 144 MFMA multiplies per 4x4 output tile and (cin, cout) pair) - a mirror of the dispatch in csrc/api.hip
-    (run_resblock, wino4_splits) and lass_wino4_supported: at least `min_cin` input channels (LASS_WINO4, default 32; 0 =
+    of 144 MFMA multiplies per 4x4 output tile and (cin, cout) pair) - a mirror of the rule in
+    csrc/conv_route.h (plan_block; tests/test_wino4_routing_cpu.py compares the two): at least `min_cin` input channels (LASS_WINO4, default 32; 0 =
     none).  Images whose width is a multiple of 32 and that tile into 8 x 64 or 16 x 32 pixel blocks: conv1 of every block,
     conv2 of the blocks with a 1x1 shortcut (decoder_block6's with the fused output head) and of encoder_block1 (residual =
     pre_conv(x0)).  Images that tile only into 32 x 16 blocks (16 bins under a 32-multiple of frames: encoder_block6 and
@@ -195,8 +195,8 @@ def wino4_routed(rows: List[Dict], min_cin: int = 32) -> set:
         if not ((geom or narrow) and r["cin"] >= min_cin and r["cin"] % 8 == 0 and r["cout"] % 32 == 0):
             continue
         if narrow:
-            # run_resblock takes this route from the F(2x2,3x3) one (lass_wino_supported: 16 bins, 64-cout groups, 16-channel
-            # chunks), for conv1 and conv2 of a block together (wino4_splits looks at the block's cin and cout)
+            # plan_block takes this route from the F(2x2,3x3) one (lass_wino_shape: 16 bins, 64-cout groups, 16-channel
+            # chunks), for conv1 and conv2 of a block together (the split-K rule looks at the block's cin and cout)
             cin1 = block_cin.get(block, r["cin"])
             if r["w"] == 16 and r["cout"] % 64 == 0 and cin1 % 16 == 0 and min(cin1, r["cout"]) >= min_cin and not block.startswith("encoder_block1"):
                 out.add(r["name"])

@@ -29,7 +29,6 @@ const EncSpec kEnc[7] = {{"encoder_block1", 32, 32, 2, 2},   {"encoder_block2", 
 const DecSpec kDec[6] = {{"decoder_block1", 384, 384, 1, 2}, {"decoder_block2", 384, 384, 2, 2},
                          {"decoder_block3", 384, 256, 2, 2}, {"decoder_block4", 256, 128, 2, 2},
                          {"decoder_block5", 128, 64, 2, 2},  {"decoder_block6", 64, 32, 2, 2}};
-constexpr int kPreCh = 32;
 constexpr float kBnEps = 1e-5f;
 constexpr int kMaxBranches = LASS_MAX_STFT_WINDOWS;
 
@@ -109,7 +108,7 @@ struct lass_ctx {
                                // F(4x4,3x3) (wino4.hip); LASS_WINO4=<min Cin>, 0 = off (F(2x2,3x3) everywhere)
     int ksplit_force = 0;      // lass_set_wino4_splits: 0 = the route's split-K factor on the 32 x 16 Winograd blocks (kWino4Splits), else 1 / 2 / 4
     int vprep_mode = 1;        // lass_set_wino4_vprep: 0 = every F(4x4,3x3) launch transforms its own input, 1 = the layers of
-                               // wino4_vprep_shape read it from a prep launch's image, 2 = every layer whose kind admits it (tests, A/B)
+                               // kVprepMinCoutGroups read it from a prep launch's image, 2 = every layer whose kind admits it (tests, A/B)
     float* stage_v = nullptr;      // ... their V image in the stage calls, grown on demand like stage_part (Plan::vprep in lass_separate)
     size_t stage_v_floats = 0;
     float* stage_v_user = nullptr; // lass_set_wino4_vprep_buffer: a caller-owned image buffer for the stage calls instead
@@ -446,55 +445,98 @@ struct BlockFusions {
     const Site* act_out = nullptr;          // bf16: the output as ONE blocked tensor with this site's prologue applied
     const CatCopies* pool_copies = nullptr; // bf16: the pooled output as two blocked copies for the next encoder block
     const UpFuse* up = nullptr;             // bf16, decoder_block6: its transposed conv inside the block's fused kernel
-    float* kpart = nullptr;                 // f32, the 32 x 16 Winograd blocks: split-K partials, wino4_split_floats() of them
-    float* vws = nullptr;                   // f32, the layers of wino4_vprep_shape: the transformed input image of one conv at a time,
-    size_t vws_floats = 0;                  // wino4_vprep_floats() of them
+    float* kpart = nullptr;                 // f32: the block's split-K partials, BlockRoute::kpart_floats of them (conv_route.h)
+    float* vws = nullptr;                   // f32: the transformed input image of one conv at a time (the V-from-memory layers),
+    size_t vws_floats = 0;                  // at least BlockRoute::v_floats
 };
 
-// f32, the 3x3 convs of a block whose images tile only into 32-row x 16-column F(4x4,3x3) blocks (lass_wino4_narrow: the 16-bin
-// level under a 32-multiple of frames): a clip plane is ONE block, so a launch has B * cout / 32 workgroups for the 512 slots
-// (256 CUs x 2) - 96 per half-batch branch of the replayed B = 16 graph.  The input-channel loop is dealt to 4 workgroups each
-// (48-96 chunks -> 12-24).  The factor is a constant of the route and NOT a function of B: the summation order of a clip must not
-// depend on the batch it arrives in (half-batches, ragged tails and single clips are bit-identical - the suite pins that).
-// 0: the block does not take this route.
-constexpr int kWino4Splits = 4;
-int wino4_splits(const lass_ctx* c, const ResBlock& rb, int B, int H, int W) {
-    (void)B;
-    if (c->compute_mode != LASS_COMPUTE_F32 || c->wino4_mincin <= 0 || !lass_wino4_narrow(H, W) || rb.width % 32 != 16) return 0;
-    if (rb.cin < c->wino4_mincin || rb.cout < c->wino4_mincin || rb.cin % 8 != 0 || rb.cout % 32 != 0) return 0;
-    return c->ksplit_force ? c->ksplit_force : kWino4Splits;
+RouteCfg route_cfg(const lass_ctx* c) {
+    RouteCfg cfg;
+    cfg.f32 = c->compute_mode == LASS_COMPUTE_F32;
+    cfg.wino4_mincin = c->wino4_mincin; cfg.ksplit_force = c->ksplit_force; cfg.vprep_mode = c->vprep_mode;
+    return cfg;
 }
-size_t wino4_split_floats(const ResBlock& rb, int S, int B, int H, int W) { return S > 1 ? (size_t)S * B * rb.cout * H * W : 0; }
 
-// f32: the shortcut layers with at least this many input channels run their 1x1 conv in pw_gemm.hip.  Shallower ones (K = 32 ...
-// 128: encoder_block2-4, decoder_block5-6) are byte-bound there - writing bias + Wsc x and reading it back costs more than
-// the re-fetches it saves (measured, profiles/r06)
-constexpr int kShortcutGemmMinCin = 256;
-
-// f32, F(4x4,3x3): the Cout / 32 workgroups of a 32-tile block each form the same transformed input V per chunk (prologue, zero
-// padding, 6x6 transform: 252 of a wave's ~460 non-MFMA instructions per chunk, on the datapath the f32 MFMA shares).  Layers with
-// at least this many cout groups have one prep launch write V to memory (2.25 x the input) and their conv kernels copy it in by
-// LDS-DMA like the weight slab.  Shape only, never a function of B.  The constant is the per-launch table of
-// profiles/r09/README.md (B = 16, prep + conv against the launch that transforms its own input): the 12-group layers (Cout 384,
-// the 64 x 32 and 32 x 16 levels) are 11-24 % below it; the 8-group layers (Cout 256, 128 x 64) only 1.5-5 % for a 0.6-GB image
-// and stay off; with 4 groups or fewer the prep launch costs more than it saves (+ 20-44 %).
-constexpr int kVprepMinCoutGroups = 12;
-// F(4x4,3x3) weight images of a 16-bin level serve the 32 x 16 blocks only (there ksplit > 0: wino4_splits), those of the wider
-// levels the wider blocks only
-bool wino4_level_geom(const ResBlock& rb, int H, int W, int ksplit) { return rb.width % 32 == 0 ? !lass_wino4_narrow(H, W) : ksplit > 0; }
-bool wino4_vprep_shape(const lass_ctx* c, const ResBlock& rb) {
-    if (c->compute_mode != LASS_COMPUTE_F32 || c->vprep_mode == 0 || c->wino4_mincin <= 0) return false;
-    return c->vprep_mode == 2 || rb.cout / 32 >= kVprepMinCoutGroups;
+// The f32 route of one block call (conv_route.h holds the rule): the block, its images and what the call site fuses into it
+BlockRoute block_route(const lass_ctx* c, const ResBlock& rb, int B, int H, int W, const float* x, long x_bs, const BlockFusions& f) {
+    BlockIO io;
+    io.x0 = f.pre && f.pre->x0;
+    io.head = f.head != nullptr;
+    io.pool = f.pool_out != nullptr; io.pool_h = f.pool_h;
+    io.x_aligned = x && ((uintptr_t)x & 15u) == 0 && x_bs % 4 == 0;
+    return plan_block(route_cfg(c), BlockShape{rb.cin, rb.cout, rb.width}, B, H, W, io);
 }
-// floats of the V slot a block needs: the larger of conv1's image (cin channels) and conv2's (cout channels: only where conv2 runs
-// without a fused shortcut phase, i.e. the identity blocks and the layers whose shortcut is a GEMM of its own).  An upper bound
-// where run_resblock then finds a launch unsupported and leaves it off the route.
-size_t wino4_vprep_floats(const lass_ctx* c, const ResBlock& rb, int B, int H, int W) {
-    if (!wino4_vprep_shape(c, rb) || rb.cin % 8 != 0 || rb.cout % 32 != 0) return 0;
-    if (!lass_wino4_block_tc(H, W) || !wino4_level_geom(rb, H, W, wino4_splits(c, rb, B, H, W))) return 0;
-    int ch = rb.u1f ? rb.cin : 0;
-    if (rb.u2f && (rb.cin == rb.cout || rb.cin >= kShortcutGemmMinCin)) ch = std::max(ch, rb.cout);
-    return lass_wino4_vpre_floats(B, ch, H, W);
+
+// Do B clips of a_n floats, a_bs apart from a (a_bs = 0: one dense range), and the same of b share an element?
+bool overlaps(int B, const float* a, long a_bs, size_t a_n, const float* b, long b_bs, size_t b_n) {
+    return a && b && a_n && b_n && a < b + (size_t)(B - 1) * b_bs + b_n && b < a + (size_t)(B - 1) * a_bs + a_n;
+}
+
+// The bf16 modes, a block their kernels take (bf1 of run_resblock): p / q = the filled conv1 / conv2 arguments
+int run_resblock_bf16(lass_ctx* c, const ResBlock& rb, const ConvArgs& p, const ConvArgs& q, int B, hipStream_t st, const BlockFusions& f) {
+    const bool x0 = f.pre && f.pre->x0;
+    const bool bf16_blocked = c->fuse_block && c->compute_mode == LASS_COMPUTE_BF16;
+    // encoder_block1 in the blocked-copy pipeline: the whole block as ONE kernel, its 32-channel intermediate kept in LDS
+    // (conv_bf16_fused.hip; LASS_FUSE_BLOCK=0 restores the two launches)
+    if (x0 && bf16_blocked && f.skip_out && rb.cin == rb.cout && lass_enc1_fused_bf16_supported(p, q)) {
+        ProfScope ps(c, st, P_CONV3X3);
+        HIP_TRY(c, lass_launch_enc1_fused_bf16(p, q, st));
+        return 0;
+    }
+    // ... and decoder_block6's ConvBlockRes with the output head behind it (conv1 from the activated cat copy, the 1x1
+    // shortcut from the raw one)
+    const bool dec6 = !x0 && bf16_blocked && f.cat_in && f.head && rb.cin != rb.cout;
+    if (const UpFuse* up = f.up) {  // the caller has NOT run the transposed conv: only the kernel that contains it will do
+        ConvArgs uq;
+        uq.in_bf16 = up->x_act; uq.Cin = up->cin; uq.H = up->h; uq.W = up->w; uq.B = B;
+        uq.w_bf16 = up->w16; uq.w2_bf16 = up->wsc16;
+        if (!(dec6 && lass_dec6u_fused_bf16_supported(p, q, uq)))
+            return fail(c, LASS_ERR_STATE, "decoder_block6 with its transposed conv inside needs the fused bf16 kernel");
+        ProfScope ps(c, st, P_CONV3X3);
+        HIP_TRY(c, lass_launch_dec6u_fused_bf16(p, q, uq, st));
+        return 0;
+    }
+    if (dec6 && lass_dec6_fused_bf16_supported(p, q)) {
+        ProfScope ps(c, st, P_CONV3X3);
+        HIP_TRY(c, lass_launch_dec6_fused_bf16(p, q, st));
+        return 0;
+    }
+    {
+        ProfScope ps(c, st, P_CONV3X3);
+        HIP_TRY(c, lass_launch_conv_bf16(x0 ? CONV1_ACT_PRE : CONV1_ACT, p, st));
+    }
+    ProfScope ps(c, st, P_CONV3X3);
+    HIP_TRY(c, lass_launch_conv_bf16(rb.cin != rb.cout ? CONV2_SHORTCUT : x0 ? CONV2_IDENT_PRE : CONV2_IDENT, q, st));
+    return 0;
+}
+
+// One f32 conv launch of a block as its route says.  The pointer-taking predicate of the chosen family has the last word: where
+// it contradicts the route (which saw the shape and the call-site facts of BlockIO only) nothing is launched.
+int launch_routed(lass_ctx* c, const ResBlock& rb, const char* what, const ConvRoute& rt, const ConvArgs& a, const Wino4Split& sk,
+                  float* vws, hipStream_t st) {
+    ProfScope ps(c, st, P_CONV3X3);
+    bool ok = true;
+    switch (rt.family) {
+        case CONV_F4X4: {
+            const Wino4Split s = rt.splits > 1 ? sk : Wino4Split();
+            Wino4VPre vp;
+            if (rt.v_from_memory) vp.v = vws;
+            ok = rt.v_from_memory ? lass_wino4_vpre_supported(rt.kind, a, s) : lass_wino4_supported(rt.kind, a, s);
+            if (ok) HIP_TRY(c, lass_launch_wino4(rt.kind, a, st, s, vp));
+            break;
+        }
+        case CONV_F2X2:
+            ok = lass_wino_supported(a);
+            if (ok) HIP_TRY(c, lass_launch_wino(rt.kind, a, st));
+            break;
+        case CONV_DIRECT:
+            HIP_TRY(c, lass_launch_conv(rt.kind, a, st));
+            break;
+        case CONV_NONE:
+            ok = false;
+            break;
+    }
+    return ok ? 0 : fail(c, LASS_ERR_STATE, rb.prefix + " " + what + ": the launch arguments contradict the planned route");
 }
 
 int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int B, int H, int W, const float* shift,
@@ -516,71 +558,39 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
     }
     p.w_wino = rb.u1; p.w_wino4 = rb.u1f;
     p.w_bf16 = rb.b1; p.w_bf16_lo = rb.b1l;
+    // bf16 modes: both convs of a block run the bf16 kernels (they share shape and mode), or neither
     const bool bf1 = c->compute_mode != LASS_COMPUTE_F32 && rb.b1 && rb.b2 && lass_bf16_supported(p) &&
                      (!x0 || W % 32 == 0) && rb.cout % 16 == 0 && (rb.cin == rb.cout || (rb.bsc16 && rb.cin % 16 == 0));
-    // bf16 modes: the intermediate a2 is kept as blocked bf16 (hi, and lo for the split mode) in the same scratch
+    // ... the intermediate a2 is then kept as blocked bf16 (hi, and lo for the split mode) in the same scratch
     void* a2_hi = a2;
     void* a2_lo = c->compute_mode == LASS_COMPUTE_BF16X3 ? (void*)((char*)a2 + (size_t)B * rb.cout * HW * 2) : nullptr;
     if (bf1) { p.out_bf16 = a2_hi; p.out_bf16_lo = a2_lo; }
     if ((skip_out || cat_in) && (!bf1 || c->compute_mode != LASS_COMPUTE_BF16))
         return fail(c, LASS_ERR_STATE, "blocked bf16 concat copies need the bf16 kernels");
     if (cat_in) p.in_bf16 = cat_in->act;
-    // the direct f32 kernels (conv.hip) have no *_PRE kinds: they refuse them
-    const ConvKind k1 = x0 ? CONV1_ACT_PRE : CONV1_ACT, k2 = x0 ? CONV2_IDENT_PRE : CONV2_IDENT;
-    const bool wino1 = !bf1 && rb.u1 && lass_wino_supported(p);
-    const int ksplit = bf1 || x0 ? 0 : wino4_splits(c, rb, B, H, W);
-    const bool w4_geom = wino4_level_geom(rb, H, W, ksplit);
-    if (ksplit > 1) {
+    // f32: the route of both convs and of the shortcut, decided once (conv_route.h); its workspace is checked here, in front of the
+    // block's first launch
+    const BlockRoute rt = bf1 ? BlockRoute() : block_route(c, rb, B, H, W, x, x_bs, f);
+    const size_t xn = rb.cin * HW, on = rb.cout * HW;  // floats per clip of the input, and of the intermediate and the output
+    if (rt.kpart_floats) {
         if (!f.kpart) return fail(c, LASS_ERR_STATE, "split-K needs its partial workspace");
-        const auto overlaps = [&](const float* a, size_t a_n, const float* b, long b_bs, long b_n) {
-            return a < b + (size_t)(B - 1) * b_bs + b_n && b < a + a_n;
-        };
-        const size_t kn = wino4_split_floats(rb, ksplit, B, H, W);
-        if (overlaps(f.kpart, kn, x, x_bs, rb.cin * HW) || overlaps(f.kpart, kn, a2, rb.cout * HW, rb.cout * HW) ||
-            overlaps(f.kpart, kn, out, out_bs, rb.cout * HW))
+        if (overlaps(B, f.kpart, 0, rt.kpart_floats, x, x_bs, xn) || overlaps(B, f.kpart, 0, rt.kpart_floats, a2, on, on) ||
+            overlaps(B, f.kpart, 0, rt.kpart_floats, out, out_bs, on))
             return fail(c, LASS_ERR_STATE, "the split-K partials must not overlap the block's input, intermediate or output");
     }
-    Wino4Split sk;  // both convs of the block
-    if (ksplit > 1) { sk.n = ksplit; sk.part = f.kpart; }
-    // V from memory (wino4_vprep_shape): the slot holds one conv's image at a time, in stream order.  Checked here, in front of
-    // the block's first launch
-    const size_t vneed = !bf1 && !x0 && w4_geom ? wino4_vprep_floats(c, rb, B, H, W) : 0;
-    if (vneed) {
-        if (!f.vws || f.vws_floats < vneed) return fail(c, LASS_ERR_STATE, "the V-from-memory route needs its image workspace");
-        const auto overlaps = [&](const float* b, long b_bs, long b_n) {
-            return b && f.vws < b + (size_t)(B - 1) * b_bs + b_n && b < f.vws + vneed;
-        };
-        if (overlaps(x, x_bs, rb.cin * HW) || overlaps(a2, rb.cout * HW, rb.cout * HW) || overlaps(out, out_bs, rb.cout * HW) ||
-            (sk.part && overlaps(sk.part, 0, (long)wino4_split_floats(rb, ksplit, B, H, W))))
+    if (rt.v_floats) {  // the slot holds one conv's image at a time, in stream order
+        if (!f.vws || f.vws_floats < rt.v_floats) return fail(c, LASS_ERR_STATE, "the V-from-memory route needs its image workspace");
+        if (overlaps(B, f.vws, 0, rt.v_floats, x, x_bs, xn) || overlaps(B, f.vws, 0, rt.v_floats, a2, on, on) ||
+            overlaps(B, f.vws, 0, rt.v_floats, out, out_bs, on) || overlaps(B, f.vws, 0, rt.v_floats, f.kpart, 0, rt.kpart_floats))
             return fail(c, LASS_ERR_STATE, "the V image must not overlap the block's input, intermediate, output or split-K partials");
     }
-    auto vprep_slot = [&](int cin, Wino4VPre* vp) -> int {
-        if (lass_wino4_vpre_floats(B, cin, H, W) > vneed) return fail(c, LASS_ERR_STATE, "the V image workspace is smaller than this layer's image");
-        vp->v = f.vws;
-        return 0;
-    };
-    const bool vshape = vneed > 0;
-    auto launch_conv1 = [&]() -> int {
-        ProfScope ps(c, st, P_CONV3X3);
-        if (bf1)
-            HIP_TRY(c, lass_launch_conv_bf16(k1, p, st));
-        else if (wino1 && rb.u1f && w4_geom && lass_wino4_supported(k1, p, sk)) {
-            Wino4VPre vp;
-            if (vshape && lass_wino4_vpre_supported(k1, p, sk))
-                if (int rv = vprep_slot(rb.cin, &vp)) return rv;
-            HIP_TRY(c, lass_launch_wino4(k1, p, st, sk, vp));
-        }
-        else if (wino1)
-            HIP_TRY(c, lass_launch_wino(k1, p, st));
-        else
-            HIP_TRY(c, lass_launch_conv(k1, p, st));
-        return 0;
-    };
+    Wino4Split sk;  // both convs of the block
+    if (rt.kpart_floats) { sk.n = std::max(rt.conv1.splits, rt.conv2.splits); sk.part = f.kpart; }
     ConvArgs q;
     q.in = a2; q.in_bs = rb.cout * HW; q.Cin = rb.cout; q.w = rb.w2; q.Nw = rb.cout; q.N = rb.cout;
     q.out = out; q.out_bs = out_bs; q.B = B; q.H = H; q.W = W;
     q.pool_out = f.pool_out; q.pool_h = f.pool_h; q.pool_bs = f.pool_bs;
-    q.w_wino = rb.u2; q.w2_wino = rb.usc; q.w_wino4 = w4_geom ? rb.u2f : nullptr;
+    q.w_wino = rb.u2; q.w2_wino = rb.usc; q.w_wino4 = rb.u2f;
     if (const MaskHead* mh = f.head) {  // the block output is consumed by the fused head and never written
         q.out = nullptr;
         q.mask_w = rawp(c, "base.after_conv.weight"); q.mask_b = rawp(c, "base.after_conv.bias");
@@ -588,11 +598,10 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
         q.mask_re = mh->oreal; q.mask_im = mh->oimag; q.mask_T = mh->T; q.mask_nbins = mh->nbins;
     }
     q.w_bf16 = rb.b2; q.w2_bf16 = rb.bsc16; q.w_bf16_lo = rb.b2l; q.w2_bf16_lo = rb.bscl;
-    const bool bf2 = bf1;  // conv1 and conv2 of a block share shape and mode: both or neither
-    if (bf2) { q.in_bf16 = a2_hi; q.in_bf16_lo = a2_lo; }
+    if (bf1) { q.in_bf16 = a2_hi; q.in_bf16_lo = a2_lo; }
     if (cat_in) q.in2_bf16 = cat_in->raw;
     if (pool_copies) {  // bf16 mode: the pooled output as blocked bf16 copies for the next encoder block
-        if (!bf2 || c->compute_mode != LASS_COMPUTE_BF16 || !f.pool_out || f.pool_h != 2)
+        if (!bf1 || c->compute_mode != LASS_COMPUTE_BF16 || !f.pool_out || f.pool_h != 2)
             return fail(c, LASS_ERR_STATE, "blocked bf16 pooled copies need the bf16 kernels and the fused 2x2 pool");
         q.pool_out = nullptr;
         q.pool_bf16 = pool_copies->raw; q.pool_bf16_act = pool_copies->act;
@@ -602,7 +611,7 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
     if (const Site* act_out = f.act_out) {  // bf16 mode: the block output goes to the next transposed conv only - written as
                                             // ONE blocked bf16 tensor with that conv's BN+FiLM+leaky prologue already applied
                                             // (in `out`'s storage)
-        if (!bf2 || c->compute_mode != LASS_COMPUTE_BF16) return fail(c, LASS_ERR_STATE, "activated bf16 output needs the bf16 kernels");
+        if (!bf1 || c->compute_mode != LASS_COMPUTE_BF16) return fail(c, LASS_ERR_STATE, "activated bf16 output needs the bf16 kernels");
         q.out_bf16 = out; q.out = nullptr; q.out_oct0 = 0; q.out_noct = 0;
         q.epi_scale = c->bn_scale + act_out->off; q.epi_shift = shift + act_out->off; q.epi_shift_bs = c->n_shift;
     }
@@ -612,98 +621,34 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
         q.out_oct0 = (rb.cout + f.cofs) / 8; q.out_noct = skip_out->noct;
         q.act_scale = skip_out->scale + rb.cout + f.cofs; q.act_shift = skip_out->shift + rb.cout + f.cofs; q.act_shift_bs = c->n_shift;
     }
-    const bool wino2 = !bf2 && rb.u2 && lass_wino_supported(q);
     if (rb.cin == rb.cout) {
         q.res = x; q.res_bs = x_bs;
         if (x0) {
             q.res = x0; q.res_bs = HW;
             q.pre_w = pre->w; q.pre_b = pre->b;
         }
-    }
-    // bf16 mode, encoder_block1 in the blocked-copy pipeline: the whole block as ONE kernel, its 32-channel intermediate
-    // kept in LDS (conv_bf16_fused.hip; LASS_FUSE_BLOCK=0 restores the two launches)
-    if (bf2 && x0 && c->fuse_block && c->compute_mode == LASS_COMPUTE_BF16 && skip_out && rb.cin == rb.cout &&
-        lass_enc1_fused_bf16_supported(p, q)) {
-        ProfScope ps(c, st, P_CONV3X3);
-        HIP_TRY(c, lass_launch_enc1_fused_bf16(p, q, st));
-        return 0;
-    }
-    if (rb.cin != rb.cout) { q.in2 = x; q.in2_bs = x_bs; q.Cin2 = rb.cin; q.w2 = rb.wsc; q.bias = rb.bsc; }
-    // ... and decoder_block6's ConvBlockRes with the output head behind it (conv1 from the activated cat copy, the 1x1
-    // shortcut from the raw one)
-    if (const UpFuse* up = f.up) {  // the caller has NOT run the transposed conv: only the kernel that contains it will do
-        ConvArgs uq;
-        uq.in_bf16 = up->x_act; uq.Cin = up->cin; uq.H = up->h; uq.W = up->w; uq.B = B;
-        uq.w_bf16 = up->w16; uq.w2_bf16 = up->wsc16;
-        if (!(bf2 && !x0 && c->fuse_block && c->compute_mode == LASS_COMPUTE_BF16 && cat_in && f.head && rb.cin != rb.cout &&
-              lass_dec6u_fused_bf16_supported(p, q, uq)))
-            return fail(c, LASS_ERR_STATE, "decoder_block6 with its transposed conv inside needs the fused bf16 kernel");
-        ProfScope ps(c, st, P_CONV3X3);
-        HIP_TRY(c, lass_launch_dec6u_fused_bf16(p, q, uq, st));
-        return 0;
-    }
-    if (bf2 && !x0 && c->fuse_block && c->compute_mode == LASS_COMPUTE_BF16 && cat_in && f.head && rb.cin != rb.cout &&
-        lass_dec6_fused_bf16_supported(p, q)) {
-        ProfScope ps(c, st, P_CONV3X3);
-        HIP_TRY(c, lass_launch_dec6_fused_bf16(p, q, st));
-        return 0;
-    }
-    // f32, the deep shortcut layers (encoder_block5, decoder_block2-4): the 1x1 shortcut as a GEMM of its own with a 128-cout
-    // tile (pw_gemm.hip), written into the block's output slot; conv2 then adds its result to that slot in place (wino4.hip,
-    // CONV2_IDENT).  Fused into conv2's 32-cout workgroups instead, every one of the Cout / 32 workgroups of a tile fetches the
-    // whole block input again.  The other shortcut layers (and decoder_block6's output head) keep the fused phase.
-    // (the 32 x 16 blocks have no fused shortcut phase at all - it would be serial work behind a split-K sum: decoder_block1)
-    const bool sc_gemm = c->compute_mode == LASS_COMPUTE_F32 && !bf2 && rb.cin != rb.cout && !f.head && rb.cin >= kShortcutGemmMinCin &&
-                         wino2 && q.w_wino4 && (ksplit > 0 || lass_wino4_supported(CONV2_SHORTCUT, q)) && lass_pw_gemm_supported(CONV2_SHORTCUT, q);
-    if (sc_gemm) {
-        const auto overlaps = [&](const float* a, long a_bs, long a_n, const float* b, long b_bs, long b_n) {
-            return a < b + (size_t)(B - 1) * b_bs + b_n && b < a + (size_t)(B - 1) * a_bs + a_n;
-        };
-        if (overlaps(out, out_bs, rb.cout * HW, x, x_bs, rb.cin * HW) || overlaps(out, out_bs, rb.cout * HW, a2, rb.cout * HW, rb.cout * HW))
-            return fail(c, LASS_ERR_STATE, "a block's output must not overlap its input or its intermediate");
-        ProfScope ps(c, st, P_CONV3X3);
-        HIP_TRY(c, lass_launch_pw_gemm(CONV2_SHORTCUT, q, st));
-    }
-    if (int r1 = launch_conv1()) return r1;
-    ProfScope ps(c, st, P_CONV3X3);
-    if (sc_gemm) {
-        ConvArgs r = q;
-        r.in2 = nullptr; r.in2_bs = 0; r.Cin2 = 0; r.w2 = nullptr; r.bias = nullptr;
-        r.res = out; r.res_bs = out_bs;
-        if (!lass_wino4_supported(CONV2_IDENT, r, sk)) return fail(c, LASS_ERR_STATE, "conv2 with the shortcut as residual");
-        Wino4VPre vp;
-        if (vshape && lass_wino4_vpre_supported(CONV2_IDENT, r, sk))
-            if (int rv = vprep_slot(rb.cout, &vp)) return rv;
-        HIP_TRY(c, lass_launch_wino4(CONV2_IDENT, r, st, sk, vp));
-    } else if (rb.cin == rb.cout) {
-        if (bf2)
-            HIP_TRY(c, lass_launch_conv_bf16(k2, q, st));
-        else if (wino2 && (x0 || ksplit > 0) && q.w_wino4 && lass_wino4_supported(k2, q, sk)) {  // (ksplit: encoder_block6, 1 x 2 pool)
-            Wino4VPre vp;
-            if (vshape && lass_wino4_vpre_supported(k2, q, sk))
-                if (int rv = vprep_slot(rb.cout, &vp)) return rv;
-            HIP_TRY(c, lass_launch_wino4(k2, q, st, sk, vp));
-        }
-        else if (wino2)
-            HIP_TRY(c, lass_launch_wino(k2, q, st));
-        else
-            HIP_TRY(c, lass_launch_conv(k2, q, st));
     } else {
-        if (bf2)
-            HIP_TRY(c, lass_launch_conv_bf16(CONV2_SHORTCUT, q, st));
-        else if (wino2 && q.w_wino4 && lass_wino4_supported(CONV2_SHORTCUT, q))
-            HIP_TRY(c, lass_launch_wino4(CONV2_SHORTCUT, q, st));
-        else if (wino2)
-            HIP_TRY(c, lass_launch_wino(CONV2_SHORTCUT, q, st));
-        else
-            HIP_TRY(c, lass_launch_conv(CONV2_SHORTCUT, q, st));
+        q.in2 = x; q.in2_bs = x_bs; q.Cin2 = rb.cin; q.w2 = rb.wsc; q.bias = rb.bsc;
     }
-    return 0;
+    if (bf1) return run_resblock_bf16(c, rb, p, q, B, st, f);
+    if (f.up) return fail(c, LASS_ERR_STATE, "decoder_block6 with its transposed conv inside needs the fused bf16 kernel");
+    if (rt.shortcut_gemm) {
+        // the GEMM writes bias + Wsc x into the block's output slot; conv2 then adds its result to that slot in place
+        if (overlaps(B, out, out_bs, on, x, x_bs, xn) || overlaps(B, out, out_bs, on, a2, on, on))
+            return fail(c, LASS_ERR_STATE, "a block's output must not overlap its input or its intermediate");
+        if (rt.conv2.family == CONV_NONE) return fail(c, LASS_ERR_STATE, "conv2 with the shortcut as residual");
+        if (!lass_pw_gemm_supported(CONV2_SHORTCUT, q))
+            return fail(c, LASS_ERR_STATE, rb.prefix + " shortcut: the launch arguments contradict the planned route");
+        {
+            ProfScope ps(c, st, P_CONV3X3);
+            HIP_TRY(c, lass_launch_pw_gemm(CONV2_SHORTCUT, q, st));
+        }
+        q.in2 = nullptr; q.in2_bs = 0; q.Cin2 = 0; q.w2 = nullptr; q.bias = nullptr;
+        q.res = out; q.res_bs = out_bs;
+    }
+    if (int r = launch_routed(c, rb, "conv1", rt.conv1, p, sk, f.vws, st)) return r;
+    return launch_routed(c, rb, "conv2", rt.conv2, q, sk, f.vws, st);
 }
-
-// f32: transposed convs with at least this many input channels run in pw_gemm.hip; decoder_block6's (K = 64, 1 GB of output
-// per batch) is byte-bound and measured 7 % faster in the direct kernel
-constexpr int kTconvGemmMinCin = 128;
 
 int run_upconv(lass_ctx* c, int di, const float* x, int B, int h, int w, const float* shift, float* out, long out_bs,
                hipStream_t st, const CatCopies* cb = nullptr, bool x_is_act_bf16 = false) {
@@ -794,15 +739,22 @@ int make_plan(const lass_ctx* c, int B, int L, Plan* pl) {
     pl->oreal = bump(t, spec); pl->oimag = bump(t, spec);
     // (a half-batch plan has its own slot: the two branches of the replayed graph never share partials)
     size_t kmax = 0, vmax = 0;
+    // every block with a route of its own (conv_route.h), at its level's image size and with what lass_separate fuses into it
+    // (the workspace hands every block an aligned input)
+    const auto block = [&](const ResBlock& rb, int e, const BlockIO& io) {
+        const BlockRoute rt = plan_block(route_cfg(c), BlockShape{rb.cin, rb.cout, rb.width}, B, pl->eh[e], pl->ew[e], io);
+        kmax = std::max(kmax, rt.kpart_floats);
+        vmax = std::max(vmax, rt.v_floats);
+    };
     for (int i = 1; i < 7; ++i) {
-        const ResBlock& rb = trunk_block(c, i);
-        vmax = std::max(vmax, wino4_vprep_floats(c, rb, B, pl->eh[i], pl->ew[i]));
-        kmax = std::max(kmax, wino4_split_floats(rb, wino4_splits(c, rb, B, pl->eh[i], pl->ew[i]), B, pl->eh[i], pl->ew[i]));
+        BlockIO io;
+        io.pool = i < 6; io.pool_h = c->E[i].dh;
+        block(trunk_block(c, i), i, io);
     }
     for (int d = 0; d < 6; ++d) {
-        const ResBlock& rb = c->dec[d];
-        vmax = std::max(vmax, wino4_vprep_floats(c, rb, B, pl->eh[5 - d], pl->ew[5 - d]));
-        kmax = std::max(kmax, wino4_split_floats(rb, wino4_splits(c, rb, B, pl->eh[5 - d], pl->ew[5 - d]), B, pl->eh[5 - d], pl->ew[5 - d]));
+        BlockIO io;
+        io.head = d == 5;
+        block(c->dec[d], 5 - d, io);
     }
     pl->has_kpart = kmax > 0;
     if (kmax) pl->kpart = bump(t, kmax);
@@ -839,30 +791,26 @@ bool split_halves(const lass_ctx* c, int B) { return c->split_batch > 0 && !c->p
 
 // Stage calls have no workspace plan: their split-K partials and their V image live in two buffers of the context that grow on
 // demand (the call must not be under stream capture when one does).  hipFree waits for the launches that still use the old buffer.
-int stage_scratch(lass_ctx* c, const ResBlock& rb, int B, int H, int W, BlockFusions* f) {
-    const size_t need = wino4_split_floats(rb, wino4_splits(c, rb, B, H, W), B, H, W);
-    if (need > c->stage_part_floats) {
-        if (c->stage_part) HIP_TRY(c, hipFree(c->stage_part));
-        c->stage_part = nullptr;
-        c->stage_part_floats = 0;
-        HIP_TRY(c, hipMalloc((void**)&c->stage_part, need * sizeof(float)));
-        c->stage_part_floats = need;
-    }
-    if (need) f->kpart = c->stage_part;
-    // ... and the V image of the V-from-memory layers: the caller's buffer if one is set (lass_set_wino4_vprep_buffer), as it is
-    const size_t vneed = wino4_vprep_floats(c, rb, B, H, W);
-    if (c->stage_v_user) {
-        if (vneed) { f->vws = c->stage_v_user; f->vws_floats = c->stage_v_user_floats; }
+int stage_scratch(lass_ctx* c, const ResBlock& rb, int B, int H, int W, const float* x, BlockFusions* f) {
+    const BlockRoute rt = block_route(c, rb, B, H, W, x, (long)rb.cin * H * W, *f);
+    const auto grow = [&](float** buf, size_t* have, size_t need) -> int {
+        if (need <= *have) return 0;
+        if (*buf) HIP_TRY(c, hipFree(*buf));
+        *buf = nullptr;
+        *have = 0;
+        HIP_TRY(c, hipMalloc((void**)buf, need * sizeof(float)));
+        *have = need;
         return 0;
+    };
+    if (int r = grow(&c->stage_part, &c->stage_part_floats, rt.kpart_floats)) return r;
+    if (rt.kpart_floats) f->kpart = c->stage_part;
+    // ... and the V image of the V-from-memory layers: the caller's buffer if one is set (lass_set_wino4_vprep_buffer), as it is
+    if (!c->stage_v_user)
+        if (int r = grow(&c->stage_v, &c->stage_v_floats, rt.v_floats)) return r;
+    if (rt.v_floats) {
+        f->vws = c->stage_v_user ? c->stage_v_user : c->stage_v;
+        f->vws_floats = c->stage_v_user ? c->stage_v_user_floats : c->stage_v_floats;
     }
-    if (vneed > c->stage_v_floats) {
-        if (c->stage_v) HIP_TRY(c, hipFree(c->stage_v));
-        c->stage_v = nullptr;
-        c->stage_v_floats = 0;
-        HIP_TRY(c, hipMalloc((void**)&c->stage_v, vneed * sizeof(float)));
-        c->stage_v_floats = vneed;
-    }
-    if (vneed) { f->vws = c->stage_v; f->vws_floats = c->stage_v_floats; }
     return 0;
 }
 
@@ -1097,17 +1045,12 @@ int lass_finalize(lass_ctx* c, int compute_mode) {
                 return LASS_ERR_HIP;
             HIP_TRY(c, lass_launch_wino_weights(w1, rb.cout, rb.cin, rb.u1, st));
             HIP_TRY(c, lass_launch_wino_weights(w2, rb.cout, rb.cout, rb.u2, st));
-            // (the 32 x 16 blocks of the 16-bin level run both convs of a block, identity residual or not: + 106 MB of images for
-            // encoder_block6 and decoder_block1; the 8-bin level tiles into no F(4x4,3x3) block and gets none)
-            const bool w4_level = rb.width % 32 == 0, w4_narrow = rb.width % 32 == 16;
-            if ((w4_level || w4_narrow) && c->wino4_mincin > 0 && rb.cin >= c->wino4_mincin && rb.cin % 8 == 0 && rb.cout % 32 == 0) {
+            const Wino4Images im = wino4_images(route_cfg(c), rb.cin, rb.cout, rb.width);  // the routes plan_block can give the block
+            if (im.u1f) {
                 if (dev_alloc(c, &rb.u1f, (size_t)36 * rb.cout * rb.cin)) return LASS_ERR_HIP;
                 HIP_TRY(c, lass_launch_wino4_weights(w1, rb.cout, rb.cin, rb.u1f, st));
             }
-            // conv2: the blocks with a 1x1 shortcut, and encoder_block1 (32 -> 32, residual = pre_conv(x0)); at the 16-bin level
-            // every block (run_resblock uses these images only where wino4_splits admits the shape)
-            if (c->wino4_mincin > 0 && rb.cout >= c->wino4_mincin && rb.cout % 32 == 0 && rb.cin % 8 == 0 &&
-                (w4_level ? rb.cin != rb.cout || rb.cout == kPreCh : w4_narrow && rb.cin >= c->wino4_mincin)) {
+            if (im.u2f) {
                 if (dev_alloc(c, &rb.u2f, (size_t)36 * rb.cout * rb.cout)) return LASS_ERR_HIP;
                 HIP_TRY(c, lass_launch_wino4_weights(w2, rb.cout, rb.cout, rb.u2f, st));
             }
@@ -1298,7 +1241,7 @@ int lass_convblock(lass_ctx* c, const char* prefix, const float* x, int B, int H
     if (!rb) return fail(c, LASS_ERR_ARG, std::string("lass_convblock: unknown block '") + prefix + "'");
     const long HW = (long)H * W;
     BlockFusions f;
-    if ((r = stage_scratch(c, *rb, B, H, W, &f))) return r;
+    if ((r = stage_scratch(c, *rb, B, H, W, x, &f))) return r;
     return run_resblock(c, *rb, x, rb->cin * HW, B, H, W, shift, scratch, y, rb->cout * HW, (hipStream_t)stream, f);
 }
 
@@ -1320,7 +1263,7 @@ int lass_encoder_block(lass_ctx* c, const char* name, const float* x, int B, int
         hipStream_t st = (hipStream_t)stream;
         BlockFusions f;
         if (fuse) { f.pool_out = pool; f.pool_h = e.dh; }
-        if ((r = stage_scratch(c, rb, B, H, W, &f))) return r;
+        if ((r = stage_scratch(c, rb, B, H, W, x, &f))) return r;
         r = run_resblock(c, rb, x, rb.cin * HW, B, H, W, shift, scratch, y, rb.cout * HW, st, f);
         if (r) return r;
         if (pooled && !fuse) HIP_TRY(c, lass_launch_pool(y, rb.cout * HW, B, rb.cout, H, W, e.dh, e.dw, pool, st));
@@ -1506,6 +1449,10 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
     auto F = [&](size_t off) { return (float*)(ws + off); };
     const int T = pl.T, Tp = pl.Tp, nbr = g.nbr;
     float* shift = F(pl.shift);
+    const auto scratch = [&](BlockFusions& f) {  // the plan's split-K and V slots, for every block
+        if (pl.has_kpart) f.kpart = F(pl.kpart);
+        if (pl.vprep_floats) { f.vws = F(pl.vprep); f.vws_floats = pl.vprep_floats; }
+    };
     // ---- front end: STFT + magnitude / phase + bn0 / T-pad / F-crop (base.py:83-113, resunet.py:533-552) ------------
     const float *mag_m = F(pl.mag), *cos_m = F(pl.cosv), *sin_m = F(pl.sinv);  // of the mask branch
     if (mixture) {
@@ -1598,8 +1545,7 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
             if (i < 5 && use_cb[5 - i]) f.skip_out = &cb[5 - i];
             if (i >= 1 && i <= 4 && use_pc[i - 1]) f.cat_in = &pc[i - 1];
             if (i < 4 && use_pc[i]) f.pool_copies = &pc[i];
-            if (pl.has_kpart) f.kpart = F(pl.kpart);
-            if (pl.vprep_floats) { f.vws = F(pl.vprep); f.vws_floats = pl.vprep_floats; }
+            scratch(f);
             r = run_resblock(c, rb, x, rb.cin * HW, B, H, W, shift, F(pl.a2), o, o_bs, st, f);
             if (r) return r;
         }
@@ -1633,8 +1579,7 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
         if (use_cb[d]) f.cat_in = &cb[d];
         const MaskHead head{mag_m, cos_m, sin_m, F(pl.oreal), F(pl.oimag), T, g.nbins};
         if (d == 5) f.head = &head;
-        if (pl.has_kpart) f.kpart = F(pl.kpart);
-        if (pl.vprep_floats) { f.vws = F(pl.vprep); f.vws_floats = pl.vprep_floats; }
+        scratch(f);
         r = run_resblock(c, rb, F(pl.cat[d]), rb.cin * HW, B, H, W, shift, F(pl.a2), F(pl.decout[d]), rb.cout * HW, st, f);
         if (r) return r;
         x = F(pl.decout[d]);

@@ -1,0 +1,238 @@
+// conv_route.h - which kernel family runs the 3x3 convs of a residual block in f32, and the workspace that takes.  The ONE rule
+// behind the weight images of lass_finalize, the workspace plan, the launches of run_resblock (api.hip) and the shape halves of
+// the lass_*_supported predicates of wino.hip, wino4.hip and pw_gemm.hip.  Host only and free of HIP: any C++17 compiler builds
+// it.  tools/route_table.cpp prints the rule as a table; tests/test_wino4_routing_cpu.py holds lass_amd.arch.wino4_routed (the
+// Python mirror that bench.py's executed-FLOP accounting reads) against that table.
+#pragma once
+#include <stddef.h>
+
+enum ConvKind { CONV1_ACT = 0, CONV2_IDENT = 1, CONV2_SHORTCUT = 2, TCONV_ACT = 3, CONV1_ACT_PRE = 4, CONV2_IDENT_PRE = 5 };
+
+constexpr int kPreCh = 32;  // channels of pre_conv and of encoder_block1
+
+// ---- chunk and tile constants of the kernel files (each file names its own from these) ---------------------------------------
+constexpr int kWinoKC = 8;                              // wino.hip: input channels of a chunk
+constexpr int kWino4KC = 8;                             // wino4.hip: input channels of a chunk
+constexpr int kWino4NXI = 36;                           // wino4.hip: points of the 6 x 6 transform domain
+constexpr int kWino4VFloats = kWino4NXI * 4 * 32 * 2;   // wino4.hip: floats of one (block, chunk) of the transformed input
+constexpr int kPwGemmNB = 128;                          // pw_gemm.hip: couts of a workgroup
+constexpr int kPwGemmKC = 16;                           // pw_gemm.hip: k rows of a chunk
+
+// wino4.hip: images that tile only into 32-row x 16-column blocks (the 16-bin level of a clip whose frame count at that level
+// is a multiple of 32); the 8 x 64 / 16 x 32 blocks take every geometry they fit
+inline bool lass_wino4_narrow(int H, int W) { return W % 32 == 16 && H % 32 == 0; }
+// The block geometry of an H x W image, as tile columns per block (TC; a block is 32 tiles of 4 x 4 outputs): 16 = 8 rows x 64
+// columns, 8 = 16 rows x 32 columns, 4 = 32 rows x 16 columns (narrow), 0 = none fits.  The one rule behind lass_wino4_shape,
+// the launchers and the sizing of the V image.
+inline int lass_wino4_block_tc(int H, int W) {
+    if (W % 64 == 0 && H % 8 == 0) return 16;
+    if (W % 32 == 0 && H % 16 == 0) return 8;
+    return lass_wino4_narrow(H, W) ? 4 : 0;
+}
+
+// ---- shape halves of the support predicates ------------------------------------------------------------------------------------
+// One conv launch as the predicates see it: ConvArgs without its pointers (kernels.h: lass_conv_shape).  The kernel files'
+// lass_*_supported are "shape function && the pointers are there".
+struct ConvShape {
+    int Cin = 0, N = 0, Nw = 0, H = 0, W = 0;
+    int Cin2 = 0;       // CONV2_SHORTCUT: channels of the 1x1 shortcut's input
+    bool pool = false;  // fused avg-pool of the output, pool_h x 2
+    int pool_h = 2;
+    bool head = false;  // fused output head (after_conv + mask) instead of the output
+};
+
+// wino.hip, F(2x2,3x3): W a multiple of 32 (or 16 / 8 bins with 64-cout groups), H even
+inline bool lass_wino_shape(const ConvShape& s) {
+    const bool w_ok = (s.W >= 32 && (s.W % 32) == 0) || ((s.W == 16 || s.W == 8) && s.N % 64 == 0);
+    return w_ok && (s.H % 2) == 0 && s.Cin % (2 * kWinoKC) == 0 && s.N % 32 == 0 && (s.Nw % 32) == 0;
+}
+
+// wino4.hip, F(4x4,3x3), whole or split-K (splits workgroups per block, cout group and clip).  One clip's input is addressed
+// through a 32-bit buffer descriptor.
+inline bool lass_wino4_shape(ConvKind kind, const ConvShape& s, int splits = 1) {
+    const int tc = lass_wino4_block_tc(s.H, s.W);
+    if (!(tc != 0 && s.Cin % kWino4KC == 0 && s.N % 32 == 0 && s.Nw % 32 == 0 &&
+          (unsigned long long)s.Cin * s.H * s.W * 4ull < 0xFFFF0000ull))
+        return false;
+    const bool pool2 = !s.pool || s.pool_h == 2;
+    if (tc == 4) {  // narrow: conv1 and the identity conv2 (fused 2 x 2 or 1 x 2 pool), whole or split-K with the combine behind it
+        if (splits != 1 && !(splits >= 2 && splits <= s.Cin / kWino4KC && s.N == s.Nw)) return false;
+        return kind == CONV1_ACT || (kind == CONV2_IDENT && !s.head && (pool2 || s.pool_h == 1));
+    }
+    if (splits != 1) return false;
+    switch (kind) {
+        case CONV1_ACT:
+            return true;
+        case CONV1_ACT_PRE:  // encoder_block1.conv1: the 32 input channels are formed from x0
+            return s.Cin == kPreCh;
+        case CONV2_IDENT_PRE:  // encoder_block1.conv2: residual = pre_conv(x0), fused 2x2 avg-pool
+            return s.N == kPreCh && s.Nw == kPreCh && pool2;
+        case CONV2_IDENT:  // conv2 + residual from memory (the shortcut layers whose 1x1 conv runs in pw_gemm.hip), fused 2x2 avg-pool
+            return !s.head && pool2;
+        case CONV2_SHORTCUT:  // conv2 + 1x1 shortcut (+ fused 2x2 avg-pool, or decoder_block6's fused output head)
+            return s.Cin2 % 16 == 0 && pool2 && (!s.head || (s.N == 32 && s.Nw == 32 && !s.pool));
+        default:
+            return false;
+    }
+}
+
+// ... with V from memory: conv1 and the identity conv2 (whole or split-K), the kinds without a fused shortcut phase or output
+// head; the V image of one (clip, block) is addressed through a 32-bit buffer descriptor
+inline bool lass_wino4_vpre_shape(ConvKind kind, const ConvShape& s, int splits = 1) {
+    return (kind == CONV1_ACT || kind == CONV2_IDENT) && lass_wino4_shape(kind, s, splits) && !s.head &&
+           (unsigned long long)(s.Cin / kWino4KC) * kWino4VFloats * 4ull < 0xFFFF0000ull;
+}
+// floats of that image: v[clip][block][chunk = cin / 8][36][256]
+inline size_t lass_wino4_vpre_floats(int B, int Cin, int H, int W) { return (size_t)B * Cin * (size_t)(H * W / 16) * kWino4NXI; }
+
+// pw_gemm.hip: the 128-cout x 128-pixel tile of both kinds, and the 1x1 shortcut (K = Cin2 in pairs of chunks)
+inline bool lass_pw_gemm_tile_shape(const ConvShape& s) {
+    const long P = (long)s.H * s.W;
+    return P > 0 && P % 4 == 0 && s.N > 0 && s.N % kPwGemmNB == 0 && s.N <= s.Nw && s.Nw % 4 == 0;
+}
+inline bool lass_pw_gemm_shortcut_shape(const ConvShape& s) {
+    return lass_pw_gemm_tile_shape(s) && s.Cin2 > 0 && s.Cin2 % (2 * kPwGemmKC) == 0;
+}
+
+// ---- the route of a block ----------------------------------------------------------------------------------------------------
+// f32, the 3x3 convs of a block whose images tile only into 32-row x 16-column F(4x4,3x3) blocks (lass_wino4_narrow: the 16-bin
+// level under a 32-multiple of frames): a clip plane is ONE block, so a launch has B * cout / 32 workgroups for the 512 slots
+// (256 CUs x 2) - 96 per half-batch branch of the replayed B = 16 graph.  The input-channel loop is dealt to 4 workgroups each
+// (48-96 chunks -> 12-24).  The factor is a constant of the route and NOT a function of B: the summation order of a clip must not
+// depend on the batch it arrives in (half-batches, ragged tails and single clips are bit-identical - the suite pins that).
+constexpr int kWino4Splits = 4;
+
+// f32: the shortcut layers with at least this many input channels run their 1x1 conv in pw_gemm.hip.  Shallower ones (K = 32 ...
+// 128: encoder_block2-4, decoder_block5-6) are byte-bound there - writing bias + Wsc x and reading it back costs more than
+// the re-fetches it saves (measured, profiles/r06)
+constexpr int kShortcutGemmMinCin = 256;
+
+// f32, F(4x4,3x3): the Cout / 32 workgroups of a 32-tile block each form the same transformed input V per chunk (prologue, zero
+// padding, 6x6 transform: 252 of a wave's ~460 non-MFMA instructions per chunk, on the datapath the f32 MFMA shares).  Layers with
+// at least this many cout groups have one prep launch write V to memory (2.25 x the input) and their conv kernels copy it in by
+// LDS-DMA like the weight slab.  Shape only, never a function of B.  The constant is the per-launch table of
+// profiles/r09/README.md (B = 16, prep + conv against the launch that transforms its own input): the 12-group layers (Cout 384,
+// the 64 x 32 and 32 x 16 levels) are 11-24 % below it; the 8-group layers (Cout 256, 128 x 64) only 1.5-5 % for a 0.6-GB image
+// and stay off; with 4 groups or fewer the prep launch costs more than it saves (+ 20-44 %).
+constexpr int kVprepMinCoutGroups = 12;
+
+// f32: transposed convs with at least this many input channels run in pw_gemm.hip; decoder_block6's (K = 64, 1 GB of output
+// per batch) is byte-bound and measured 7 % faster in the direct kernel
+constexpr int kTconvGemmMinCin = 128;
+
+struct RouteCfg {
+    bool f32 = true;       // compute mode LASS_COMPUTE_F32.  The bf16 modes prepare no Winograd weights: a block their kernels
+                           // refuse runs the direct f32 kernels
+    int wino4_mincin = 32; // 3x3 convs with at least that many input channels run as F(4x4,3x3); 0 = off (F(2x2,3x3) everywhere)
+    int ksplit_force = 0;  // 0 = kWino4Splits on the 32 x 16 blocks, else 1 / 2 / 4
+    int vprep_mode = 1;    // V from memory: 0 = off, 1 = the layers of kVprepMinCoutGroups, 2 = every layer whose kind admits it
+};
+
+struct BlockShape {
+    int cin, cout;
+    int width;  // bins of the level the block runs at: known at finalize, the frame count is not
+};
+
+// What a call site adds to the shape
+struct BlockIO {
+    bool x0 = false;         // encoder_block1: the input is pre_conv(x0), formed on the fly (the *_PRE kinds)
+    bool head = false;       // decoder_block6: the output head in conv2's epilogue
+    bool pool = false;       // fused avg-pool in conv2's epilogue, pool_h x 2
+    int pool_h = 2;
+    bool x_aligned = true;   // the block input meets pw_gemm.hip's 16-byte alignment (pointer, and batch stride % 4 floats)
+};
+
+// Which of a block's F(4x4,3x3) weight images lass_finalize prepares: u1f (conv1) / u2f (conv2).  conv1 at every level that can
+// tile; conv2 of the blocks with a 1x1 shortcut and of encoder_block1 (32 -> 32, residual = pre_conv(x0)); at the 16-bin level
+// both convs of every block (the 32 x 16 blocks run them identity residual or not: + 106 MB of images for encoder_block6 and
+// decoder_block1).  The 8-bin level tiles into no F(4x4,3x3) block and gets none.
+struct Wino4Images {
+    bool u1f = false, u2f = false;
+};
+inline Wino4Images wino4_images(const RouteCfg& cfg, int cin, int cout, int width) {
+    Wino4Images im;
+    const int m = cfg.wino4_mincin;
+    if (!cfg.f32 || m <= 0 || cin % 8 != 0 || cout % 32 != 0) return im;
+    const bool level = width % 32 == 0, narrow = width % 32 == 16;
+    im.u1f = (level || narrow) && cin >= m;
+    im.u2f = cout >= m && (level ? cin != cout || cout == kPreCh : narrow && cin >= m);
+    return im;
+}
+
+enum ConvFamily {
+    CONV_DIRECT = 0,  // conv.hip
+    CONV_F2X2 = 1,    // wino.hip
+    CONV_F4X4 = 2,    // wino4.hip
+    CONV_NONE = 3     // conv2 behind a shortcut GEMM that no F(4x4,3x3) kernel takes: a state error, nothing is launched
+};
+
+struct ConvRoute {
+    ConvFamily family = CONV_DIRECT;
+    ConvKind kind = CONV1_ACT;
+    int splits = 1;               // F(4x4,3x3) split-K factor
+    bool v_from_memory = false;   // F(4x4,3x3): a prep launch writes the transformed input, the conv kernel reads it
+};
+
+struct BlockRoute {
+    ConvRoute conv1, conv2;
+    bool shortcut_gemm = false;  // the 1x1 shortcut is a pw_gemm.hip launch in front, into the block's output slot; conv2 is then
+                                 // CONV2_IDENT with that slot as its residual, in place
+    size_t kpart_floats = 0;     // split-K partials both convs share: [splits][B][cout][H][W]
+    size_t v_floats = 0;         // the V slot: the larger of the two convs' images (one at a time, in stream order)
+};
+
+inline BlockRoute plan_block(const RouteCfg& cfg, const BlockShape& b, int B, int H, int W, const BlockIO& io) {
+    BlockRoute r;
+    const bool ident = b.cin == b.cout;
+    r.conv1.kind = io.x0 ? CONV1_ACT_PRE : CONV1_ACT;  // (the direct kernels have no *_PRE kinds: they refuse them)
+    r.conv2.kind = !ident ? CONV2_SHORTCUT : io.x0 ? CONV2_IDENT_PRE : CONV2_IDENT;
+    if (!cfg.f32) return r;
+    ConvShape s1, s2;
+    s1.Cin = b.cin; s1.N = s1.Nw = b.cout; s1.H = H; s1.W = W;
+    s2.Cin = s2.N = s2.Nw = b.cout; s2.H = H; s2.W = W;
+    s2.Cin2 = ident ? 0 : b.cin; s2.pool = io.pool; s2.pool_h = io.pool_h; s2.head = io.head;
+    const Wino4Images im = wino4_images(cfg, b.cin, b.cout, b.width);
+    const int m = cfg.wino4_mincin;
+    // split-K: both convs of a 16-bin block on 32 x 16 images; 0 = the block does not take that route (never the x0 block)
+    int ksplit = 0;
+    if (!io.x0 && m > 0 && lass_wino4_narrow(H, W) && b.width % 32 == 16 && b.cin >= m && b.cout >= m && b.cin % 8 == 0 && b.cout % 32 == 0)
+        ksplit = cfg.ksplit_force ? cfg.ksplit_force : kWino4Splits;
+    const int n = ksplit > 1 ? ksplit : 1;
+    // the weight images of a 16-bin level serve the 32 x 16 blocks only, those of the wider levels the wider blocks only
+    const bool geom = b.width % 32 == 0 ? !lass_wino4_narrow(H, W) : ksplit > 0;
+    const bool vprep = !io.x0 && geom && m > 0 && (cfg.vprep_mode == 2 || (cfg.vprep_mode == 1 && b.cout / 32 >= kVprepMinCoutGroups));
+    // the F(4x4,3x3) routes are taken from the F(2x2,3x3) one: only where that shape test holds too
+    const bool wino1 = lass_wino_shape(s1), wino2 = lass_wino_shape(s2);
+    const auto f4 = [&](ConvRoute& c, ConvKind kind, const ConvShape& s, int splits) {
+        c.family = CONV_F4X4; c.kind = kind; c.splits = splits;
+        c.v_from_memory = vprep && lass_wino4_vpre_shape(kind, s, splits);
+    };
+    if (wino1 && im.u1f && geom && lass_wino4_shape(r.conv1.kind, s1, n))
+        f4(r.conv1, r.conv1.kind, s1, n);
+    else
+        r.conv1.family = wino1 ? CONV_F2X2 : CONV_DIRECT;
+    // The deep shortcut layers (encoder_block5, decoder_block2-4): the 1x1 shortcut as a GEMM of its own with a 128-cout tile.
+    // Fused into conv2's 32-cout workgroups instead, every one of the Cout / 32 workgroups of a tile fetches the whole block input
+    // again.  The other shortcut layers (and decoder_block6's output head) keep the fused phase.  The 32 x 16 blocks have no fused
+    // shortcut phase at all - it would be serial work behind a split-K sum (decoder_block1) - and without the GEMM fall to F(2x2,3x3).
+    const bool u2f = im.u2f && geom;
+    r.shortcut_gemm = !ident && !io.head && b.cin >= kShortcutGemmMinCin && wino2 && u2f &&
+                      (ksplit > 0 || lass_wino4_shape(CONV2_SHORTCUT, s2)) && lass_pw_gemm_shortcut_shape(s2) && io.x_aligned;
+    if (r.shortcut_gemm) {
+        s2.Cin2 = 0;
+        if (lass_wino4_shape(CONV2_IDENT, s2, n))
+            f4(r.conv2, CONV2_IDENT, s2, n);
+        else
+            r.conv2 = ConvRoute{CONV_NONE, CONV2_IDENT};
+    } else if (wino2 && u2f && (ident ? (io.x0 || ksplit > 0) && lass_wino4_shape(r.conv2.kind, s2, n)
+                                      : lass_wino4_shape(CONV2_SHORTCUT, s2))) {
+        // (identity: encoder_block1, and encoder_block6 with its 1 x 2 pool; the fused shortcut phase is never split)
+        f4(r.conv2, r.conv2.kind, s2, ident ? n : 1);
+    } else {
+        r.conv2.family = wino2 ? CONV_F2X2 : CONV_DIRECT;
+    }
+    if (r.conv1.splits > 1 || r.conv2.splits > 1) r.kpart_floats = (size_t)n * B * b.cout * H * W;
+    if (r.conv1.v_from_memory) r.v_floats = lass_wino4_vpre_floats(B, b.cin, H, W);
+    if (r.conv2.v_from_memory && lass_wino4_vpre_floats(B, b.cout, H, W) > r.v_floats) r.v_floats = lass_wino4_vpre_floats(B, b.cout, H, W);
+    return r;
+}

@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "conv_route.h"  // ConvKind, the shape rules of the f32 conv families and the route of a block (host only, HIP-free)
+
 constexpr int LASS_NFFT = 1024;
 constexpr int LASS_HOP = 160;
 constexpr int LASS_NBINS = 513;
@@ -93,19 +95,8 @@ struct ConvArgs {
                                // (block_coords, wino_common.h)
 };
 
-// wino4.hip: images that tile only into 32-row x 16-column blocks (the 16-bin level of a clip whose frame count at that level
-// is a multiple of 32); the 8 x 64 / 16 x 32 blocks take every geometry they fit
-inline bool lass_wino4_narrow(int H, int W) { return W % 32 == 16 && H % 32 == 0; }
-// The block geometry of an H x W image, as tile columns per block (TC; a block is 32 tiles of 4 x 4 outputs): 16 = 8 rows x 64
-// columns, 8 = 16 rows x 32 columns, 4 = 32 rows x 16 columns (narrow), 0 = none fits.  The one rule behind lass_wino4_supported,
-// the launchers and the sizing of the V image.
-inline int lass_wino4_block_tc(int H, int W) {
-    if (W % 64 == 0 && H % 8 == 0) return 16;
-    if (W % 32 == 0 && H % 16 == 0) return 8;
-    return lass_wino4_narrow(H, W) ? 4 : 0;
-}
-// Split-K on those blocks: the input-channel loop is dealt to n workgroups per (block, cout group, clip); each stores its partial
-// of the conv sum, [n][B][N][H][W] dense in part, and a combine launch sums them in split order and applies the epilogue.
+// Split-K on the 32 x 16 blocks of wino4.hip (conv_route.h: lass_wino4_narrow): the input-channel loop is dealt to n workgroups per
+// (block, cout group, clip); each stores its partial of the conv sum, [n][B][N][H][W] dense in part, and a combine launch sums them in split order and applies the epilogue.
 // (Not part of ConvArgs: the kernels that take only ConvArgs keep their argument block, and with it their compiled code.)
 struct Wino4Split {
     int n = 1;
@@ -119,7 +110,13 @@ struct Wino4VPre {
     float* v = nullptr;
 };
 
-enum ConvKind { CONV1_ACT = 0, CONV2_IDENT = 1, CONV2_SHORTCUT = 2, TCONV_ACT = 3, CONV1_ACT_PRE = 4, CONV2_IDENT_PRE = 5 };
+// The shape half of the predicates below (conv_route.h) reads a launch as its ConvShape; they add that the pointers are there.
+inline ConvShape lass_conv_shape(const ConvArgs& p) {
+    ConvShape s;
+    s.Cin = p.Cin; s.N = p.N; s.Nw = p.Nw; s.H = p.H; s.W = p.W;
+    s.Cin2 = p.Cin2; s.pool = p.pool_out != nullptr; s.pool_h = p.pool_h; s.head = p.mask_re != nullptr;
+    return s;
+}
 
 hipError_t lass_launch_conv(ConvKind kind, const ConvArgs& p, hipStream_t stream);
 
@@ -136,7 +133,6 @@ hipError_t lass_launch_wino4(ConvKind kind, const ConvArgs& p, hipStream_t strea
                              const Wino4VPre& vp = Wino4VPre());
 // V from memory (vp.v set): CONV1_ACT and CONV2_IDENT only, a prep launch in front of the conv launch
 bool lass_wino4_vpre_supported(ConvKind kind, const ConvArgs& p, const Wino4Split& sk = Wino4Split());
-size_t lass_wino4_vpre_floats(int B, int Cin, int H, int W);
 hipError_t lass_launch_wino4_weights(const float* w, int Cout, int Cin, float* U, hipStream_t stream);  // w (Cout, Cin, 3, 3)
 
 // ---- pw_gemm.hip (f32 pointwise GEMMs with a 128-cout workgroup tile; H*W % 4 == 0, N % 128 == 0, K % 32 == 0) ------------

@@ -18,9 +18,9 @@
 namespace {
 
 constexpr int NTHREADS = 256;
-constexpr int NB = 128;      // couts of a workgroup
+constexpr int NB = kPwGemmNB;  // couts of a workgroup
 constexpr int PB = 128;      // pixels of a workgroup
-constexpr int KC = 16;       // k rows of a chunk
+constexpr int KC = kPwGemmKC;  // k rows of a chunk
 constexpr int LP = NB + 32;  // LDS row pitch (floats) of both operand images
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -172,12 +172,11 @@ bool aligned16(const void* q) { return ((uintptr_t)q & 15u) == 0; }
 }  // namespace
 
 bool lass_pw_gemm_supported(ConvKind kind, const ConvArgs& p) {
-    const long P = (long)p.H * p.W;
-    if (!(p.out && !p.out_bf16 && p.B > 0 && P > 0 && P % 4 == 0 && p.N > 0 && p.N % NB == 0 && p.N <= p.Nw && p.Nw % 4 == 0))
-        return false;
+    const ConvShape s = lass_conv_shape(p);  // (the shape rules: conv_route.h)
+    if (!(p.out && !p.out_bf16 && p.B > 0 && lass_pw_gemm_tile_shape(s))) return false;
     switch (kind) {
         case CONV2_SHORTCUT:
-            return p.in2 && p.w2 && p.bias && p.Cin2 > 0 && p.Cin2 % (2 * KC) == 0 && p.in2_bs % 4 == 0 && aligned16(p.in2) && aligned16(p.w2);
+            return lass_pw_gemm_shortcut_shape(s) && p.in2 && p.w2 && p.bias && p.in2_bs % 4 == 0 && aligned16(p.in2) && aligned16(p.w2);
         case TCONV_ACT:
             return p.in && p.w && p.pro_scale && p.pro_shift && !p.in_bf16 && p.Cin > 0 && p.Cin % (2 * KC) == 0 && p.in_bs % 4 == 0 &&
                    (p.up_h == 1 || p.up_h == 2) && p.N % (2 * p.up_h) == 0 && p.out_bs % 2 == 0 && aligned16(p.in) && aligned16(p.w) &&

@@ -30,7 +30,7 @@ constexpr int F_MASK = 1024;    // epilogue = after_conv + complex ratio mask (C
 constexpr int F_PRECONV = 64;   // input is the 1-channel x0; channel c = pre_w[c]*x0 + pre_b[c] is formed while staging
 constexpr int F_RESPRE = 128;   // with F_RES: the residual is pre_w[n]*x0 + pre_b[n]
 constexpr int NTHREADS = 256;
-constexpr int KC = 8;
+constexpr int KC = kWinoKC;
 constexpr int KCB = 32;  // shortcut phase: 32 channels x 4 xi per chunk (the same 128 LDS rows and 64 MFMAs as a 3x3 chunk)
 
 // Wave priority by phase.  A wave's staging / transform chain (a few dozen VALU and LDS instructions strung between
@@ -579,10 +579,7 @@ hipError_t launch_wino(const ConvArgs& p, hipStream_t stream) {
 
 }  // namespace
 
-bool lass_wino_supported(const ConvArgs& p) {
-    const bool w_ok = (p.W >= 32 && (p.W % 32) == 0) || ((p.W == 16 || p.W == 8) && p.N % 64 == 0);
-    return w_ok && (p.H % 2) == 0 && p.Cin % (2 * KC) == 0 && p.N % 32 == 0 && (p.Nw % 32) == 0;
-}
+bool lass_wino_supported(const ConvArgs& p) { return lass_wino_shape(lass_conv_shape(p)); }
 
 hipError_t lass_launch_wino(ConvKind kind, const ConvArgs& p, hipStream_t stream) {
     if (!lass_wino_supported(p) || !p.w_wino || !p.in || (!p.out && !p.mask_re)) return hipErrorInvalidValue;

@@ -34,10 +34,10 @@ constexpr int F_PRO = 1, F_PHASEB = 2, F_BIAS = 4, F_RES = 8, F_EPIACT = 16, F_P
 constexpr int F_SPLITK = 2048;  // this workgroup runs one share of the input channels and stores its partial sums (Wino4Split)
 constexpr int F_VPRE = 4096;    // the transformed input V is read from memory (Wino4VPre): wino4_vprep_kernel wrote it, once per layer
 constexpr int NTHREADS = 256;
-constexpr int KC = 8;
-constexpr int NXI = 36;
+constexpr int KC = kWino4KC;
+constexpr int NXI = kWino4NXI;
 constexpr int U_F = NXI * 256;            // floats of one (8-channel chunk, 32-cout group) weight slab
-constexpr int V_F = NXI * 4 * 32 * 2;     // [xi][kq][tile][k-step]
+constexpr int V_F = kWino4VFloats;        // [xi][kq][tile][k-step]
 
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 
@@ -282,43 +282,29 @@ hipError_t launch_wino4_split(const ConvArgs& p0, const Wino4Split& sk, hipStrea
 
 }  // namespace
 
+// lass_wino4_shape (conv_route.h) && the pointers of the kind are there
 bool lass_wino4_supported(ConvKind kind, const ConvArgs& p, const Wino4Split& sk) {
-    const bool narrow = lass_wino4_block_tc(p.H, p.W) == 4;  // lass_wino4_narrow (excludes the two wider geometries: W % 32 == 16)
-    if (!(p.w_wino4 && lass_wino4_block_tc(p.H, p.W) != 0 && p.Cin % KC == 0 && p.N % 32 == 0 &&
-          p.Nw % 32 == 0 && (unsigned long long)p.Cin * p.H * p.W * 4ull < 0xFFFF0000ull))
-        return false;
-    if (narrow) {  // conv1 and the identity conv2 (fused 2 x 2 or 1 x 2 pool), whole or split-K with the combine behind it
-        if (sk.n != 1 && !(sk.n >= 2 && sk.n <= p.Cin / KC && sk.part && p.N == p.Nw)) return false;
-        return kind == CONV1_ACT || (kind == CONV2_IDENT && p.res && !p.mask_re && (!p.pool_out || p.pool_h == 2 || p.pool_h == 1));
-    }
-    if (sk.n != 1) return false;
+    if (!lass_wino4_shape(kind, lass_conv_shape(p), sk.n) || !p.w_wino4 || (sk.n != 1 && !sk.part)) return false;
     switch (kind) {
         case CONV1_ACT:
             return true;
-        case CONV1_ACT_PRE:  // encoder_block1.conv1: the 32 input channels are formed from x0
-            return p.pre_w && p.pre_b && p.Cin == 32;
-        case CONV2_IDENT_PRE:  // encoder_block1.conv2: residual = pre_conv(x0), fused 2x2 avg-pool
-            return p.res && p.pre_w && p.pre_b && p.N == 32 && p.Nw == 32 && (!p.pool_out || p.pool_h == 2);
-        case CONV2_IDENT:  // conv2 + residual from p.res (the shortcut layers whose 1x1 conv runs in pw_gemm.hip), fused 2x2 avg-pool
-            return p.res && !p.mask_re && (!p.pool_out || p.pool_h == 2);
-        case CONV2_SHORTCUT:  // conv2 + 1x1 shortcut (+ fused 2x2 avg-pool, or decoder_block6's fused output head)
-            if (!(p.in2 && p.w2 && p.bias && p.Cin2 % 16 == 0 && (!p.pool_out || p.pool_h == 2))) return false;
-            if (p.mask_re)
-                return p.N == 32 && p.Nw == 32 && p.W + 1 == p.mask_nbins && p.mask_w && p.mask_b && p.mask_mag && p.mask_cos && p.mask_sin &&
-                       p.mask_im && p.mask_T > 0 && p.mask_T <= p.H && !p.pool_out;
-            return true;
+        case CONV1_ACT_PRE:
+            return p.pre_w && p.pre_b;
+        case CONV2_IDENT_PRE:
+            return p.res && p.pre_w && p.pre_b;
+        case CONV2_IDENT:  // (res may be `out` itself)
+            return p.res != nullptr;
+        case CONV2_SHORTCUT:
+            if (!(p.in2 && p.w2 && p.bias)) return false;
+            return !p.mask_re || (p.W + 1 == p.mask_nbins && p.mask_w && p.mask_b && p.mask_mag && p.mask_cos && p.mask_sin && p.mask_im &&
+                                  p.mask_T > 0 && p.mask_T <= p.H);
         default:
             return false;
     }
 }
 
-size_t lass_wino4_vpre_floats(int B, int Cin, int H, int W) { return (size_t)B * Cin * (size_t)(H * W / 16) * NXI; }
-
 bool lass_wino4_vpre_supported(ConvKind kind, const ConvArgs& p, const Wino4Split& sk) {
-    // conv1 and the identity conv2 (whole or split-K): the kinds without a fused shortcut phase or output head; the V image of one
-    // (clip, block) is addressed through a 32-bit buffer descriptor
-    return (kind == CONV1_ACT || kind == CONV2_IDENT) && lass_wino4_supported(kind, p, sk) && !p.mask_re &&
-           (unsigned long long)(p.Cin / KC) * V_F * 4ull < 0xFFFF0000ull;
+    return lass_wino4_vpre_shape(kind, lass_conv_shape(p), sk.n) && lass_wino4_supported(kind, p, sk);
 }
 
 hipError_t lass_launch_wino4(ConvKind kind, const ConvArgs& p, hipStream_t stream, const Wino4Split& sk, const Wino4VPre& vp) {
