@@ -136,6 +136,12 @@ int lass_set_wino4_splits(lass_ctx* ctx, int splits);
  * layer's shape only, never at the batch.  mode 0 = off, 1 = the measured routing (default), 2 = every layer whose kind admits
  * it (tests, A/B).  Query lass_workspace_bytes again afterwards. */
 int lass_set_wino4_vprep(lass_ctx* ctx, int mode);
+/* f32: lass_separate's last launch (decoder_block6's conv2 + 1x1 shortcut with the output head in its epilogue) runs on weights
+ * that lass_finalize composed with after_conv - nothing non-linear sits between the two, so the 3 mask logits are one linear map
+ * of the launch's inputs and the block's 32 output channels are never formed.  1 = that route (default), 0 = the unfolded launch
+ * (A/B, tests; LASS_HEAD_FOLD at lass_create).  The two differ by f32 rounding only (the last linear layer is re-associated).  The
+ * stage calls, LASS_WINO4=0 and the bf16 modes have no folded form and ignore the switch. */
+int lass_set_head_fold(lass_ctx* ctx, int enabled);
 /* UNSTABLE, tests only - not part of the supported interface, and may change or go without notice; lass_separate never looks at
  * it.  The stage calls (lass_convblock, lass_encoder_block) keep that image in `v` (`floats` f32 of device memory owned by the
  * caller) instead of a buffer of the context; NULL restores the context's.  A buffer that is too small for a layer, or overlaps

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/lass_hip.h"
+#include "head_fold.h"
 #include "kernels.h"
 
 namespace {
@@ -56,6 +57,8 @@ struct ResBlock {  // one ConvBlockRes
     void *b1 = nullptr, *b2 = nullptr, *bsc16 = nullptr;  // bf16 copies (LASS_COMPUTE_BF16 / _BF16X3)
     void *b1l = nullptr, *b2l = nullptr, *bscl = nullptr;  // lo halves of the hi+lo split (LASS_COMPUTE_BF16X3)
     const float* bsc = nullptr;                         // raw shortcut bias
+    // decoder_block6, f32: conv2 and the shortcut composed with after_conv (head_fold.h) - U images, Wsc' [cin][16], b' [16]
+    float *u2h = nullptr, *wsch = nullptr, *bh = nullptr;
 };
 
 struct ProfEntry {
@@ -109,6 +112,7 @@ struct lass_ctx {
     int ksplit_force = 0;      // lass_set_wino4_splits: 0 = the route's split-K factor on the 32 x 16 Winograd blocks (kWino4Splits), else 1 / 2 / 4
     int vprep_mode = 1;        // lass_set_wino4_vprep: 0 = every F(4x4,3x3) launch transforms its own input, 1 = the layers of
                                // kVprepMinCoutGroups read it from a prep launch's image, 2 = every layer whose kind admits it (tests, A/B)
+    bool head_fold = true;     // lass_set_head_fold / LASS_HEAD_FOLD: lass_separate's fused output head runs on the composed images
     float* stage_v = nullptr;      // ... their V image in the stage calls, grown on demand like stage_part (Plan::vprep in lass_separate)
     size_t stage_v_floats = 0;
     float* stage_v_user = nullptr; // lass_set_wino4_vprep_buffer: a caller-owned image buffer for the stage calls instead
@@ -454,6 +458,7 @@ RouteCfg route_cfg(const lass_ctx* c) {
     RouteCfg cfg;
     cfg.f32 = c->compute_mode == LASS_COMPUTE_F32;
     cfg.wino4_mincin = c->wino4_mincin; cfg.ksplit_force = c->ksplit_force; cfg.vprep_mode = c->vprep_mode;
+    cfg.head_fold = c->head_fold;
     return cfg;
 }
 
@@ -521,6 +526,11 @@ int launch_routed(lass_ctx* c, const ResBlock& rb, const char* what, const ConvR
             const Wino4Split s = rt.splits > 1 ? sk : Wino4Split();
             Wino4VPre vp;
             if (rt.v_from_memory) vp.v = vws;
+            if (rt.head_fold) {
+                ok = lass_wino4_headfold_supported(a);
+                if (ok) HIP_TRY(c, lass_launch_wino4_headfold(a, st));
+                break;
+            }
             ok = rt.v_from_memory ? lass_wino4_vpre_supported(rt.kind, a, s) : lass_wino4_supported(rt.kind, a, s);
             if (ok) HIP_TRY(c, lass_launch_wino4(rt.kind, a, st, s, vp));
             break;
@@ -631,6 +641,10 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
         q.in2 = x; q.in2_bs = x_bs; q.Cin2 = rb.cin; q.w2 = rb.wsc; q.bias = rb.bsc;
     }
     if (bf1) return run_resblock_bf16(c, rb, p, q, B, st, f);
+    if (rt.conv2.head_fold) {  // the composed images in place of conv2's, the shortcut's and after_conv's (null: a state error below)
+        q.w_wino4 = rb.u2h; q.w2 = rb.wsch; q.bias = rb.bh;
+        q.mask_w = q.mask_b = nullptr;
+    }
     if (f.up) return fail(c, LASS_ERR_STATE, "decoder_block6 with its transposed conv inside needs the fused bf16 kernel");
     if (rt.shortcut_gemm) {
         // the GEMM writes bias + Wsc x into the block's output slot; conv2 then adds its result to that slot in place
@@ -860,6 +874,7 @@ static int create_impl(lass_ctx** out, int device_id, const Geometry& geom) {
     if (const char* e = getenv("LASS_FUSE_UP")) c->fuse_up = atoi(e) != 0;
     if (const char* e = getenv("LASS_WINO4")) c->wino4_mincin = atoi(e);
     if (const char* e = getenv("LASS_WINO4_VPREP")) c->vprep_mode = std::max(0, std::min(2, atoi(e)));  // A/B: lass_set_wino4_vprep
+    if (const char* e = getenv("LASS_HEAD_FOLD")) c->head_fold = atoi(e) != 0;  // A/B: lass_set_head_fold
     if (const char* e = getenv("LASS_SPLIT")) c->split_batch = std::max(0, std::min(2, atoi(e)));
     if (const char* e = getenv("LASS_GRAPH")) c->use_graph = atoi(e) != 0;
     c->prof.resize(P_COUNT);
@@ -1118,6 +1133,32 @@ int lass_finalize(lass_ctx* c, int compute_mode) {
             HIP_TRY(c, lass_launch_compose_up_shortcut(ws, wu, d.cin, d.cout, rb.cin, rb.cout, tmp, st));
             HIP_TRY(c, lass_launch_weights_bf16(tmp, 4 * rb.cout, d.cin, 1, t16, 0, 0, st));
             c->up_sc16 = t16;
+        }
+    }
+    // decoder_block6's conv2 and shortcut composed with after_conv, for the folded output head (head_fold.h): in double on the
+    // host, from the checkpoint alone
+    {
+        ResBlock& rb = c->dec[5];
+        rb.u2h = rb.wsch = rb.bh = nullptr;
+        const Raw& ra = c->raw["base.after_conv.weight"];
+        const int Q = ra.shape.empty() ? 0 : (int)ra.shape[0];
+        if (rb.u2f && rb.cin != rb.cout && Q > 0 && Q <= kHeadFoldRows && ra.n == (size_t)Q * rb.cout) {
+            const int N = rb.cout, K = rb.cin;
+            std::vector<float> w2((size_t)N * N * 9), ws((size_t)N * K), bs(N), wa((size_t)Q * N), ba(Q);
+            HIP_TRY(c, hipStreamSynchronize(st));
+            HIP_TRY(c, hipMemcpy(w2.data(), need(rb.prefix + ".conv2.weight"), w2.size() * sizeof(float), hipMemcpyDeviceToHost));
+            HIP_TRY(c, hipMemcpy(ws.data(), need(rb.prefix + ".shortcut.weight"), ws.size() * sizeof(float), hipMemcpyDeviceToHost));
+            HIP_TRY(c, hipMemcpy(bs.data(), rb.bsc, bs.size() * sizeof(float), hipMemcpyDeviceToHost));
+            HIP_TRY(c, hipMemcpy(wa.data(), ra.d, wa.size() * sizeof(float), hipMemcpyDeviceToHost));
+            HIP_TRY(c, hipMemcpy(ba.data(), need("base.after_conv.bias"), ba.size() * sizeof(float), hipMemcpyDeviceToHost));
+            HeadFold hf;
+            if (compose_head_fold(w2.data(), ws.data(), bs.data(), wa.data(), ba.data(), N, N, K, Q, &hf)) {
+                if (dev_alloc(c, &rb.u2h, hf.u.size()) || dev_alloc(c, &rb.wsch, hf.wsc.size()) || dev_alloc(c, &rb.bh, hf.bias.size()))
+                    return LASS_ERR_HIP;
+                HIP_TRY(c, hipMemcpy(rb.u2h, hf.u.data(), hf.u.size() * sizeof(float), hipMemcpyHostToDevice));
+                HIP_TRY(c, hipMemcpy(rb.wsch, hf.wsc.data(), hf.wsc.size() * sizeof(float), hipMemcpyHostToDevice));
+                HIP_TRY(c, hipMemcpy(rb.bh, hf.bias.data(), hf.bias.size() * sizeof(float), hipMemcpyHostToDevice));
+            }
         }
     }
     HIP_TRY(c, hipStreamSynchronize(st));
@@ -1726,6 +1767,13 @@ int lass_set_wino4_vprep(lass_ctx* c, int mode) {
     if (!c || mode < 0 || mode > 2) return fail(c, LASS_ERR_ARG, "lass_set_wino4_vprep: 0, 1 or 2");
     c->vprep_mode = mode;
     ++c->gen;  // as lass_set_wino4_splits: other launches, another workspace size
+    return 0;
+}
+
+int lass_set_head_fold(lass_ctx* c, int enabled) {
+    if (!c || (enabled != 0 && enabled != 1)) return fail(c, LASS_ERR_ARG, "lass_set_head_fold: 0 or 1");
+    c->head_fold = enabled != 0;
+    ++c->gen;  // captured graphs hold the launch of the previous choice
     return 0;
 }
 

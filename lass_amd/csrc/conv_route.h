@@ -15,6 +15,7 @@ constexpr int kWinoKC = 8;                              // wino.hip: input chann
 constexpr int kWino4KC = 8;                             // wino4.hip: input channels of a chunk
 constexpr int kWino4NXI = 36;                           // wino4.hip: points of the 6 x 6 transform domain
 constexpr int kWino4VFloats = kWino4NXI * 4 * 32 * 2;   // wino4.hip: floats of one (block, chunk) of the transformed input
+constexpr int kHeadFoldRows = 16;                       // wino4.hip, folded output head: rows of the one MFMA tile the 3 logits are padded to
 constexpr int kPwGemmNB = 128;                          // pw_gemm.hip: couts of a workgroup
 constexpr int kPwGemmKC = 16;                           // pw_gemm.hip: k rows of a chunk
 
@@ -76,6 +77,14 @@ inline bool lass_wino4_shape(ConvKind kind, const ConvShape& s, int splits = 1) 
     }
 }
 
+// wino4.hip, decoder_block6's conv2 with after_conv folded into its weights and its shortcut's (head_fold.h): the shape of the
+// unfolded launch - s.N = s.Nw = 32 names the conv that is folded, the images hold kHeadFoldRows rows - on the 8 x 64 blocks (the
+// head's rows are 512 or 1 024 bins wide and a plan's frame count is a multiple of 32: no other geometry reaches it); the two
+// k-step waves of the kernel take half of the shortcut's channels each, in groups of four k-steps
+inline bool lass_wino4_headfold_shape(const ConvShape& s) {
+    return s.head && lass_wino4_block_tc(s.H, s.W) == 16 && lass_wino4_shape(CONV2_SHORTCUT, s) && s.Cin2 % 32 == 0;
+}
+
 // ... with V from memory: conv1 and the identity conv2 (whole or split-K), the kinds without a fused shortcut phase or output
 // head; the V image of one (clip, block) is addressed through a 32-bit buffer descriptor
 inline bool lass_wino4_vpre_shape(ConvKind kind, const ConvShape& s, int splits = 1) {
@@ -126,6 +135,7 @@ struct RouteCfg {
     int wino4_mincin = 32; // 3x3 convs with at least that many input channels run as F(4x4,3x3); 0 = off (F(2x2,3x3) everywhere)
     int ksplit_force = 0;  // 0 = kWino4Splits on the 32 x 16 blocks, else 1 / 2 / 4
     int vprep_mode = 1;    // V from memory: 0 = off, 1 = the layers of kVprepMinCoutGroups, 2 = every layer whose kind admits it
+    bool head_fold = true; // the fused output head runs on weights composed with after_conv (3 logits instead of 32 channels)
 };
 
 struct BlockShape {
@@ -171,6 +181,7 @@ struct ConvRoute {
     ConvKind kind = CONV1_ACT;
     int splits = 1;               // F(4x4,3x3) split-K factor
     bool v_from_memory = false;   // F(4x4,3x3): a prep launch writes the transformed input, the conv kernel reads it
+    bool head_fold = false;       // F(4x4,3x3), CONV2_SHORTCUT with the output head: the folded kernel and its composed images
 };
 
 struct BlockRoute {
@@ -228,6 +239,7 @@ inline BlockRoute plan_block(const RouteCfg& cfg, const BlockShape& b, int B, in
                                       : lass_wino4_shape(CONV2_SHORTCUT, s2))) {
         // (identity: encoder_block1, and encoder_block6 with its 1 x 2 pool; the fused shortcut phase is never split)
         f4(r.conv2, r.conv2.kind, s2, ident ? n : 1);
+        r.conv2.head_fold = cfg.head_fold && !ident && io.head && lass_wino4_headfold_shape(s2);
     } else {
         r.conv2.family = wino2 ? CONV_F2X2 : CONV_DIRECT;
     }

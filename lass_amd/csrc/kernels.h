@@ -134,6 +134,10 @@ hipError_t lass_launch_wino4(ConvKind kind, const ConvArgs& p, hipStream_t strea
 // V from memory (vp.v set): CONV1_ACT and CONV2_IDENT only, a prep launch in front of the conv launch
 bool lass_wino4_vpre_supported(ConvKind kind, const ConvArgs& p, const Wino4Split& sk = Wino4Split());
 hipError_t lass_launch_wino4_weights(const float* w, int Cout, int Cin, float* U, hipStream_t stream);  // w (Cout, Cin, 3, 3)
+// decoder_block6.conv2 + shortcut + output head on weights composed with after_conv (head_fold.h): w_wino4 / w2 / bias hold the
+// composed images (U per 8-channel chunk, Wsc' [Cin2][16], b' [16]); N = Nw = 32 still name the conv that was folded
+bool lass_wino4_headfold_supported(const ConvArgs& p);
+hipError_t lass_launch_wino4_headfold(const ConvArgs& p, hipStream_t stream);
 
 // ---- pw_gemm.hip (f32 pointwise GEMMs with a 128-cout workgroup tile; H*W % 4 == 0, N % 128 == 0, K % 32 == 0) ------------
 // CONV2_SHORTCUT: only the 1x1 shortcut, out = bias + Wsc x (in2, Cin2, w2, bias), for conv2 to read back as its residual;

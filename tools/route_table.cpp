@@ -1,9 +1,10 @@
 // route_table.cpp - the f32 conv routes of the model as lass_amd/csrc/conv_route.h decides them, one line per 3x3 conv and one per
 // block.  Host only: g++ -std=c++17 -I lass_amd/csrc tools/route_table.cpp -o tools/bin/route_table
-// usage: route_table T_PAD [MIN_CIN=32] [VPREP_MODE=1] [FORCED_SPLITS=0] [X_ALIGNED=1] [STFT_WINDOWS=0] [B=1]
+// usage: route_table T_PAD [MIN_CIN=32] [VPREP_MODE=1] [FORCED_SPLITS=0] [X_ALIGNED=1] [STFT_WINDOWS=0] [B=1] [HEAD_FOLD=1] [HEAD=1]
+//   HEAD 1: decoder_block6 as lass_separate runs it, the output head in conv2's epilogue; 0: as the stage call runs it, without
 //   STFT_WINDOWS 0: ResUNet30 (512 bins); n > 0: the multi-STFT model with n analysis windows (1024 bins), rows named as
 //   lass_amd.arch.ms_conv_layer_table names them (encoder_block1s.<k> for window k).
-// conv <name> <direct|f2x2|f4x4|none> <kind> <splits> <v>     block <name> shortcut=<gemm|fused|-> kpart=<floats> v=<floats>
+// conv <name> <direct|f2x2|f4x4|none> <kind> <splits> <v> fold=<0|1>     block <name> shortcut=<gemm|fused|-> kpart=<floats> v=<floats>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -26,8 +27,8 @@ void print_block(const RouteCfg& cfg, const std::string& name, const BlockShape&
     const BlockRoute r = plan_block(cfg, b, B, H, W, io);
     const ConvRoute* cv[2] = {&r.conv1, &r.conv2};
     for (int k = 0; k < 2; ++k)
-        printf("conv %s.conv%d %s %s %d %d\n", name.c_str(), k + 1, kFamily[cv[k]->family], kKind[cv[k]->kind], cv[k]->splits,
-               (int)cv[k]->v_from_memory);
+        printf("conv %s.conv%d %s %s %d %d fold=%d\n", name.c_str(), k + 1, kFamily[cv[k]->family], kKind[cv[k]->kind], cv[k]->splits,
+               (int)cv[k]->v_from_memory, (int)cv[k]->head_fold);
     printf("block %s shortcut=%s kpart=%zu v=%zu\n", name.c_str(), b.cin == b.cout ? "-" : r.shortcut_gemm ? "gemm" : "fused",
            r.kpart_floats, r.v_floats);
 }
@@ -36,7 +37,8 @@ void print_block(const RouteCfg& cfg, const std::string& name, const BlockShape&
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        fprintf(stderr, "usage: %s T_PAD [MIN_CIN=32] [VPREP_MODE=1] [FORCED_SPLITS=0] [X_ALIGNED=1] [STFT_WINDOWS=0] [B=1]\n", argv[0]);
+        fprintf(stderr, "usage: %s T_PAD [MIN_CIN=32] [VPREP_MODE=1] [FORCED_SPLITS=0] [X_ALIGNED=1] [STFT_WINDOWS=0] [B=1] [HEAD_FOLD=1] [HEAD=1]\n",
+                argv[0]);
         return 2;
     }
     const auto arg = [&](int i, int dflt) { return argc > i ? atoi(argv[i]) : dflt; };
@@ -45,6 +47,8 @@ int main(int argc, char** argv) {
     cfg.wino4_mincin = arg(2, 32);
     cfg.vprep_mode = arg(3, 1);
     cfg.ksplit_force = arg(4, 0);
+    cfg.head_fold = arg(8, 1) != 0;
+    const bool head = arg(9, 1) != 0;
     const bool aligned = arg(5, 1) != 0;
     if (t_pad <= 0 || nwin < 0 || nwin > 4 || B <= 0) return 2;
     const int nbr = nwin ? nwin : 1, fcrop = nwin ? 1024 : 512;
@@ -67,7 +71,7 @@ int main(int argc, char** argv) {
     for (int d = 0; d < 6; ++d) {
         const int e = 5 - d;
         BlockIO io;
-        io.head = d == 5;
+        io.head = head && d == 5;
         io.x_aligned = aligned;
         const int cat = kDec[d].cout + kEnc[e].cout * (e == 0 ? nbr : 1);  // torch.cat((x, skip), 1)
         print_block(cfg, kDec[d].name, BlockShape{cat, kDec[d].cout, fcrop >> e}, B, eh[e], ew[e], io);
