@@ -142,6 +142,14 @@ int lass_set_wino4_vprep(lass_ctx* ctx, int mode);
  * (A/B, tests; LASS_HEAD_FOLD at lass_create).  The two differ by f32 rounding only (the last linear layer is re-associated).  The
  * stage calls, LASS_WINO4=0 and the bf16 modes have no folded form and ignore the switch. */
 int lass_set_head_fold(lass_ctx* ctx, int enabled);
+/* f32, under head_fold = 1, the single-window ResUNet30: that launch reads decoder_block6's concat only to apply the composed 1x1
+ * shortcut.  With this route the shortcut's 3 logits are formed where the two halves of the concat are produced - the skip in
+ * encoder_block1.conv2's epilogue, the up-sampled half as 12 more columns of decoder_block6's transposed conv - and handed to the
+ * head as two sets of planes (B, 3, frames, 512) in the workspace; the head then runs no shortcut phase.  1 = that route
+ * (default), 0 = the head forms the shortcut itself (A/B, tests; LASS_HEAD_SC_FOLD at lass_create).  The two differ by f32
+ * rounding only.  The multi-STFT model, the stage calls, LASS_WINO4=0, lass_set_head_fold(0) and the bf16 modes ignore the
+ * switch.  Query lass_workspace_bytes again afterwards. */
+int lass_set_head_sc_fold(lass_ctx* ctx, int enabled);
 /* UNSTABLE, tests only - not part of the supported interface, and may change or go without notice; lass_separate never looks at
  * it.  The stage calls (lass_convblock, lass_encoder_block) keep that image in `v` (`floats` f32 of device memory owned by the
  * caller) instead of a buffer of the context; NULL restores the context's.  A buffer that is too small for a layer, or overlaps

@@ -113,6 +113,9 @@ struct lass_ctx {
     int vprep_mode = 1;        // lass_set_wino4_vprep: 0 = every F(4x4,3x3) launch transforms its own input, 1 = the layers of
                                // kVprepMinCoutGroups read it from a prep launch's image, 2 = every layer whose kind admits it (tests, A/B)
     bool head_fold = true;     // lass_set_head_fold / LASS_HEAD_FOLD: lass_separate's fused output head runs on the composed images
+    bool head_sc_fold = true;  // lass_set_head_sc_fold / LASS_HEAD_SC_FOLD: ... and reads its shortcut's logits as planes that
+                               // encoder_block1.conv2 and decoder_block6's transposed conv write (conv_route.h: plan_head_sc_fold)
+    float *hs_wt = nullptr, *hs_wskip = nullptr;  // head_fold.h: Wt' [cin][64] for that transposed conv, Wsc'_skip [3][32] (lass_finalize)
     float* stage_v = nullptr;      // ... their V image in the stage calls, grown on demand like stage_part (Plan::vprep in lass_separate)
     size_t stage_v_floats = 0;
     float* stage_v_user = nullptr; // lass_set_wino4_vprep_buffer: a caller-owned image buffer for the stage calls instead
@@ -452,13 +455,15 @@ struct BlockFusions {
     float* kpart = nullptr;                 // f32: the block's split-K partials, BlockRoute::kpart_floats of them (conv_route.h)
     float* vws = nullptr;                   // f32: the transformed input image of one conv at a time (the V-from-memory layers),
     size_t vws_floats = 0;                  // at least BlockRoute::v_floats
+    const HeadScPlanes* planes = nullptr;   // f32, encoder_block1 / decoder_block6 of lass_separate: the head's shortcut logits as
+                                            // planes (Plan::sc_planes) - written by conv2's epilogue / read by the folded head
 };
 
 RouteCfg route_cfg(const lass_ctx* c) {
     RouteCfg cfg;
     cfg.f32 = c->compute_mode == LASS_COMPUTE_F32;
     cfg.wino4_mincin = c->wino4_mincin; cfg.ksplit_force = c->ksplit_force; cfg.vprep_mode = c->vprep_mode;
-    cfg.head_fold = c->head_fold;
+    cfg.head_fold = c->head_fold; cfg.head_sc_fold = c->head_sc_fold;
     return cfg;
 }
 
@@ -469,6 +474,7 @@ BlockRoute block_route(const lass_ctx* c, const ResBlock& rb, int B, int H, int 
     io.head = f.head != nullptr;
     io.pool = f.pool_out != nullptr; io.pool_h = f.pool_h;
     io.x_aligned = x && ((uintptr_t)x & 15u) == 0 && x_bs % 4 == 0;
+    io.sc_planes = f.planes != nullptr;
     return plan_block(route_cfg(c), BlockShape{rb.cin, rb.cout, rb.width}, B, H, W, io);
 }
 
@@ -518,7 +524,7 @@ int run_resblock_bf16(lass_ctx* c, const ResBlock& rb, const ConvArgs& p, const 
 // One f32 conv launch of a block as its route says.  The pointer-taking predicate of the chosen family has the last word: where
 // it contradicts the route (which saw the shape and the call-site facts of BlockIO only) nothing is launched.
 int launch_routed(lass_ctx* c, const ResBlock& rb, const char* what, const ConvRoute& rt, const ConvArgs& a, const Wino4Split& sk,
-                  float* vws, hipStream_t st) {
+                  float* vws, hipStream_t st, const HeadScPlanes* planes = nullptr) {
     ProfScope ps(c, st, P_CONV3X3);
     bool ok = true;
     switch (rt.family) {
@@ -526,6 +532,11 @@ int launch_routed(lass_ctx* c, const ResBlock& rb, const char* what, const ConvR
             const Wino4Split s = rt.splits > 1 ? sk : Wino4Split();
             Wino4VPre vp;
             if (rt.v_from_memory) vp.v = vws;
+            if (rt.head_sc_fold) {  // the folded head on the planes, or encoder_block1.conv2 that writes the skip's
+                ok = planes && (rt.head_fold ? lass_wino4_headfold_planes_supported(a, *planes) : lass_wino4_sclogit_supported(a, *planes));
+                if (ok) HIP_TRY(c, rt.head_fold ? lass_launch_wino4_headfold_planes(a, *planes, st) : lass_launch_wino4_sclogit(a, *planes, st));
+                break;
+            }
             if (rt.head_fold) {
                 ok = lass_wino4_headfold_supported(a);
                 if (ok) HIP_TRY(c, lass_launch_wino4_headfold(a, st));
@@ -594,6 +605,16 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
             overlaps(B, f.vws, 0, rt.v_floats, out, out_bs, on) || overlaps(B, f.vws, 0, rt.v_floats, f.kpart, 0, rt.kpart_floats))
             return fail(c, LASS_ERR_STATE, "the V image must not overlap the block's input, intermediate, output or split-K partials");
     }
+    if (f.planes) {  // the plan decided the route for three launches at once: a block that cannot follow it would leave the head
+                     // with planes nobody wrote
+        if (!rt.conv2.head_sc_fold) return fail(c, LASS_ERR_STATE, rb.prefix + ": the head's shortcut planes contradict the block's route");
+        const size_t pn = (size_t)3 * HW;
+        for (const float* pl : {(const float*)f.planes->skip, (const float*)f.planes->up})
+            if (overlaps(B, pl, pn, pn, x, x_bs, xn) || overlaps(B, pl, pn, pn, a2, on, on) || overlaps(B, pl, pn, pn, out, out_bs, on) ||
+                overlaps(B, pl, pn, pn, f.kpart, 0, rt.kpart_floats) || overlaps(B, pl, pn, pn, f.vws, 0, rt.v_floats))
+                return fail(c, LASS_ERR_STATE, "the head's shortcut planes must not overlap the block's tensors or workspaces");
+        if (overlaps(B, f.planes->skip, pn, pn, f.planes->up, pn, pn)) return fail(c, LASS_ERR_STATE, "the two sets of shortcut planes overlap");
+    }
     Wino4Split sk;  // both convs of the block
     if (rt.kpart_floats) { sk.n = std::max(rt.conv1.splits, rt.conv2.splits); sk.part = f.kpart; }
     ConvArgs q;
@@ -661,11 +682,11 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
         q.res = out; q.res_bs = out_bs;
     }
     if (int r = launch_routed(c, rb, "conv1", rt.conv1, p, sk, f.vws, st)) return r;
-    return launch_routed(c, rb, "conv2", rt.conv2, q, sk, f.vws, st);
+    return launch_routed(c, rb, "conv2", rt.conv2, q, sk, f.vws, st, f.planes);
 }
 
 int run_upconv(lass_ctx* c, int di, const float* x, int B, int h, int w, const float* shift, float* out, long out_bs,
-               hipStream_t st, const CatCopies* cb = nullptr, bool x_is_act_bf16 = false) {
+               hipStream_t st, const CatCopies* cb = nullptr, bool x_is_act_bf16 = false, const HeadScPlanes* planes = nullptr) {
     const DecSpec& d = c->D[di];
     const Site& s = c->sites[c->dec_site[di]];
     ConvArgs p;
@@ -688,6 +709,12 @@ int run_upconv(lass_ctx* c, int di, const float* x, int B, int h, int w, const f
         p.act_scale = cb->scale; p.act_shift = cb->shift; p.act_shift_bs = c->n_shift;
     }
     ProfScope ps(c, st, P_TCONV);
+    if (planes) {  // decoder_block6 of the head_sc_fold route: the launch also writes the head's shortcut logits of its output
+        if (c->compute_mode != LASS_COMPUTE_F32 || cb || x_is_act_bf16 || !lass_tconv_logits_supported(p, *planes))
+            return fail(c, LASS_ERR_STATE, std::string(d.name) + " transposed conv: the launch arguments contradict the planned route");
+        HIP_TRY(c, lass_launch_tconv_logits(p, *planes, st));
+        return 0;
+    }
     if (c->compute_mode != LASS_COMPUTE_F32 && p.w_bf16 && lass_bf16_supported(p))
         HIP_TRY(c, lass_launch_conv_bf16(TCONV_ACT, p, st));
     else if (c->compute_mode == LASS_COMPUTE_F32 && d.cin >= kTconvGemmMinCin && lass_pw_gemm_supported(TCONV_ACT, p))
@@ -705,6 +732,10 @@ struct Plan {
     size_t kpart = 0;  // split-K partials of the 32 x 16 Winograd blocks (one slot: the launches of a plan run in stream order)
     bool has_kpart = false;
     size_t vprep = 0, vprep_floats = 0;  // the V image of the V-from-memory layers: one slot, sized to the largest of them
+    // conv_route.h's head_sc_fold: the folded head's shortcut logits as two sets of planes [B][3][Tp][fcrop], one written by
+    // encoder_block1.conv2 and one by decoder_block6's transposed conv (last in the plan: no other offset depends on the switch)
+    bool sc_planes = false;
+    size_t lg_skip = 0, lg_up = 0;
     int eh[7], ew[7];  // encoder block spatial sizes
 };
 
@@ -712,6 +743,21 @@ size_t bump(size_t& total, size_t floats) {
     const size_t off = total;
     total += (floats * sizeof(float) + 255) / 256 * 256;
     return off;
+}
+
+// Does lass_separate take the head_sc_fold route (conv_route.h: plan_head_sc_fold) at this batch and image?  The call-site facts
+// are those of separate_impl: encoder_block1 with its fused 2 x 2 pool, decoder_block6 with the head, both on aligned workspace
+// tensors; the composed weights exist (lass_finalize made them for this checkpoint).
+bool head_sc_planned(const lass_ctx* c, int B, int H, int W) {
+    if (!c->hs_wt || !c->hs_wskip || c->enc.empty() || c->dec.size() < 6) return false;
+    const ResBlock &e1 = c->enc[0], &d6 = c->dec[5];
+    BlockIO eio, dio;
+    eio.x0 = true; eio.pool = true; eio.pool_h = c->E[0].dh;
+    dio.head = true;
+    HeadScSite site;
+    site.windows = c->g.variant == 0 ? 0 : c->g.nbr; site.tconv_cin = c->D[5].cin; site.up_h = c->D[5].uh; site.up_w = c->D[5].uw;
+    return c->E[0].dh == 2 && c->E[0].dw == 2 &&
+           plan_head_sc_fold(route_cfg(c), BlockShape{e1.cin, e1.cout, e1.width}, eio, BlockShape{d6.cin, d6.cout, d6.width}, dio, site, B, H, W);
 }
 
 // The conv kernels address one clip's tensors through 32-bit buffer descriptors and byte offsets, so the largest per-clip
@@ -774,6 +820,11 @@ int make_plan(const lass_ctx* c, int B, int L, Plan* pl) {
     if (kmax) pl->kpart = bump(t, kmax);
     pl->vprep_floats = vmax;
     if (vmax) pl->vprep = bump(t, vmax);
+    pl->sc_planes = head_sc_planned(c, B, pl->eh[0], pl->ew[0]);
+    if (pl->sc_planes) {
+        pl->lg_skip = bump(t, (size_t)B * 3 * pl->eh[0] * pl->ew[0]);
+        pl->lg_up = bump(t, (size_t)B * 3 * pl->eh[0] * pl->ew[0]);
+    }
     return 0;
 }
 
@@ -875,6 +926,7 @@ static int create_impl(lass_ctx** out, int device_id, const Geometry& geom) {
     if (const char* e = getenv("LASS_WINO4")) c->wino4_mincin = atoi(e);
     if (const char* e = getenv("LASS_WINO4_VPREP")) c->vprep_mode = std::max(0, std::min(2, atoi(e)));  // A/B: lass_set_wino4_vprep
     if (const char* e = getenv("LASS_HEAD_FOLD")) c->head_fold = atoi(e) != 0;  // A/B: lass_set_head_fold
+    if (const char* e = getenv("LASS_HEAD_SC_FOLD")) c->head_sc_fold = atoi(e) != 0;  // A/B: lass_set_head_sc_fold
     if (const char* e = getenv("LASS_SPLIT")) c->split_batch = std::max(0, std::min(2, atoi(e)));
     if (const char* e = getenv("LASS_GRAPH")) c->use_graph = atoi(e) != 0;
     c->prof.resize(P_COUNT);
@@ -1140,6 +1192,7 @@ int lass_finalize(lass_ctx* c, int compute_mode) {
     {
         ResBlock& rb = c->dec[5];
         rb.u2h = rb.wsch = rb.bh = nullptr;
+        c->hs_wt = c->hs_wskip = nullptr;
         const Raw& ra = c->raw["base.after_conv.weight"];
         const int Q = ra.shape.empty() ? 0 : (int)ra.shape[0];
         if (rb.u2f && rb.cin != rb.cout && Q > 0 && Q <= kHeadFoldRows && ra.n == (size_t)Q * rb.cout) {
@@ -1151,6 +1204,21 @@ int lass_finalize(lass_ctx* c, int compute_mode) {
             HIP_TRY(c, hipMemcpy(bs.data(), rb.bsc, bs.size() * sizeof(float), hipMemcpyDeviceToHost));
             HIP_TRY(c, hipMemcpy(wa.data(), ra.d, wa.size() * sizeof(float), hipMemcpyDeviceToHost));
             HIP_TRY(c, hipMemcpy(ba.data(), need("base.after_conv.bias"), ba.size() * sizeof(float), hipMemcpyDeviceToHost));
+            // ... and the shortcut's two halves for the launches that produce its inputs (ResUNet30: the skip is ONE encoder_block1's
+            // output): Wt' = Wsc'_up o Wt for the transposed conv, Wsc'_skip for encoder_block1.conv2's epilogue
+            const DecSpec& d6 = c->D[5];
+            const auto up = c->raw.find(std::string("base.") + d6.name + ".conv1.weight");
+            if (c->g.variant == 0 && c->g.nbr == 1 && Q == 3 && K == d6.cout + kPreCh && up != c->raw.end() && up->second.d &&
+                up->second.n == (size_t)d6.cin * d6.cout * d6.uh * d6.uw) {
+                std::vector<float> wt(up->second.n);
+                HIP_TRY(c, hipMemcpy(wt.data(), up->second.d, wt.size() * sizeof(float), hipMemcpyDeviceToHost));
+                HeadScFold hsf;
+                if (compose_head_sc_fold(ws.data(), wa.data(), wt.data(), N, d6.cout, kPreCh, Q, d6.cin, d6.uh, d6.uw, &hsf)) {
+                    if (dev_alloc(c, &c->hs_wt, hsf.wt.size()) || dev_alloc(c, &c->hs_wskip, hsf.wskip.size())) return LASS_ERR_HIP;
+                    HIP_TRY(c, hipMemcpy(c->hs_wt, hsf.wt.data(), hsf.wt.size() * sizeof(float), hipMemcpyHostToDevice));
+                    HIP_TRY(c, hipMemcpy(c->hs_wskip, hsf.wskip.data(), hsf.wskip.size() * sizeof(float), hipMemcpyHostToDevice));
+                }
+            }
             HeadFold hf;
             if (compose_head_fold(w2.data(), ws.data(), bs.data(), wa.data(), ba.data(), N, N, K, Q, &hf)) {
                 if (dev_alloc(c, &rb.u2h, hf.u.size()) || dev_alloc(c, &rb.wsch, hf.wsc.size()) || dev_alloc(c, &rb.bh, hf.bias.size()))
@@ -1368,6 +1436,9 @@ int lass_workspace_tensor(const lass_ctx* c, int B, int L, const char* name_c, s
         if (i < 6 && name == std::string(e.name) + ".pool")
             return put(pl.pool[i], C, H / e.dh, W / e.dw, C * (H / e.dh) * (W / e.dw));
     }
+    // the head's shortcut logits of the head_sc_fold route (only where the plan has them)
+    if (pl.sc_planes && name == "head_sc.skip") return put(pl.lg_skip, 3, pl.eh[0], pl.ew[0], (int64_t)3 * pl.eh[0] * pl.ew[0]);
+    if (pl.sc_planes && name == "head_sc.up") return put(pl.lg_up, 3, pl.eh[0], pl.ew[0], (int64_t)3 * pl.eh[0] * pl.ew[0]);
     for (int d = 0; d < 6; ++d) {
         const int64_t H = pl.eh[5 - d], W = pl.ew[5 - d], C = c->D[d].cout;
         if (name == std::string(c->D[d].name) + ".up") return put(pl.cat[d], C, H, W, (int64_t)c->dec_cat[d] * H * W);
@@ -1519,6 +1590,13 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
         ProfScope ps(c, st, P_FILM);
         HIP_TRY(c, lass_launch_film(condition, B, c->film_W, c->film_b, c->bn_base, c->n_shift, shift, st));
     }
+    // conv_route.h's head_sc_fold: one decision (make_plan) for encoder_block1.conv2, decoder_block6's transposed conv and the head
+    HeadScPlanes hs_skip, hs_up, hs_head;
+    if (pl.sc_planes) {
+        hs_skip.skip = hs_head.skip = F(pl.lg_skip); hs_skip.w = c->hs_wskip;
+        hs_up.up = hs_head.up = F(pl.lg_up); hs_up.w = c->hs_wt;
+        hs_skip.up = hs_head.up;  // (for run_resblock's overlap checks; the encoder launch does not touch it)
+    }
     // Routes.  pre_conv (resunet.py:555) is never materialised: encoder_block1 forms it from x0 while staging.  Tp is a
     // multiple of 32, so every pooled level has even rows and F.avg_pool2d (resunet.py:197) rides in conv2's epilogue.
     // decoder_block6 runs at W = fcrop with 32 channels: after_conv + mask ride in its conv2's epilogue.
@@ -1582,6 +1660,7 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
             if (i == 0) {
                 pre = PreConv{F(pl.x0[k]), rawp(c, c->pre_name[k] + ".weight"), rawp(c, c->pre_name[k] + ".bias")};
                 f.pre = &pre;
+                if (pl.sc_planes) f.planes = &hs_skip;
             }
             if (i < 5 && use_cb[5 - i]) f.skip_out = &cb[5 - i];
             if (i >= 1 && i <= 4 && use_pc[i - 1]) f.cat_in = &pc[i - 1];
@@ -1610,7 +1689,8 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
         if (fuse_up) {
             f.up = &upf;
         } else {
-            r = run_upconv(c, d, x, B, h, w, shift, F(pl.cat[d]), rb.cin * HW, st, use_cb[d] ? &cb[d] : nullptr, x_act);
+            r = run_upconv(c, d, x, B, h, w, shift, F(pl.cat[d]), rb.cin * HW, st, use_cb[d] ? &cb[d] : nullptr, x_act,
+                           d == 5 && pl.sc_planes ? &hs_up : nullptr);
             if (r) return r;
         }
         // this decoder's output feeds only the next transposed conv: hand it over activated, as blocked bf16
@@ -1620,6 +1700,7 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
         if (use_cb[d]) f.cat_in = &cb[d];
         const MaskHead head{mag_m, cos_m, sin_m, F(pl.oreal), F(pl.oimag), T, g.nbins};
         if (d == 5) f.head = &head;
+        if (d == 5 && pl.sc_planes) f.planes = &hs_head;
         scratch(f);
         r = run_resblock(c, rb, F(pl.cat[d]), rb.cin * HW, B, H, W, shift, F(pl.a2), F(pl.decout[d]), rb.cout * HW, st, f);
         if (r) return r;
@@ -1774,6 +1855,13 @@ int lass_set_head_fold(lass_ctx* c, int enabled) {
     if (!c || (enabled != 0 && enabled != 1)) return fail(c, LASS_ERR_ARG, "lass_set_head_fold: 0 or 1");
     c->head_fold = enabled != 0;
     ++c->gen;  // captured graphs hold the launch of the previous choice
+    return 0;
+}
+
+int lass_set_head_sc_fold(lass_ctx* c, int enabled) {
+    if (!c || (enabled != 0 && enabled != 1)) return fail(c, LASS_ERR_ARG, "lass_set_head_sc_fold: 0 or 1");
+    c->head_sc_fold = enabled != 0;
+    ++c->gen;  // as lass_set_wino4_splits: other launches, another workspace size
     return 0;
 }
 

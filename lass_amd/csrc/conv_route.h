@@ -136,6 +136,7 @@ struct RouteCfg {
     int ksplit_force = 0;  // 0 = kWino4Splits on the 32 x 16 blocks, else 1 / 2 / 4
     int vprep_mode = 1;    // V from memory: 0 = off, 1 = the layers of kVprepMinCoutGroups, 2 = every layer whose kind admits it
     bool head_fold = true; // the fused output head runs on weights composed with after_conv (3 logits instead of 32 channels)
+    bool head_sc_fold = true;  // ... and takes its shortcut's logits as planes from the launches that produce its inputs
 };
 
 struct BlockShape {
@@ -150,6 +151,8 @@ struct BlockIO {
     bool pool = false;       // fused avg-pool in conv2's epilogue, pool_h x 2
     int pool_h = 2;
     bool x_aligned = true;   // the block input meets pw_gemm.hip's 16-byte alignment (pointer, and batch stride % 4 floats)
+    bool sc_planes = false;  // encoder_block1 / decoder_block6 of one lass_separate: the call site hands over (takes) the head's
+                             // shortcut logits as planes - plan_head_sc_fold below has decided that for both ends at once
 };
 
 // Which of a block's F(4x4,3x3) weight images lass_finalize prepares: u1f (conv1) / u2f (conv2).  conv1 at every level that can
@@ -182,6 +185,8 @@ struct ConvRoute {
     int splits = 1;               // F(4x4,3x3) split-K factor
     bool v_from_memory = false;   // F(4x4,3x3): a prep launch writes the transformed input, the conv kernel reads it
     bool head_fold = false;       // F(4x4,3x3), CONV2_SHORTCUT with the output head: the folded kernel and its composed images
+    bool head_sc_fold = false;    // F(4x4,3x3) on 8 x 64 blocks: the folded head without its shortcut phase (it reads two sets of
+                                  // logit planes), or CONV2_IDENT_PRE that writes the skip's set from its epilogue
 };
 
 struct BlockRoute {
@@ -240,6 +245,8 @@ inline BlockRoute plan_block(const RouteCfg& cfg, const BlockShape& b, int B, in
         // (identity: encoder_block1, and encoder_block6 with its 1 x 2 pool; the fused shortcut phase is never split)
         f4(r.conv2, r.conv2.kind, s2, ident ? n : 1);
         r.conv2.head_fold = cfg.head_fold && !ident && io.head && lass_wino4_headfold_shape(s2);
+        r.conv2.head_sc_fold = io.sc_planes && cfg.head_fold && cfg.head_sc_fold && lass_wino4_block_tc(H, W) == 16 &&
+                               (r.conv2.head_fold || (io.x0 && r.conv2.kind == CONV2_IDENT_PRE));
     } else {
         r.conv2.family = wino2 ? CONV_F2X2 : CONV_DIRECT;
     }
@@ -247,4 +254,35 @@ inline BlockRoute plan_block(const RouteCfg& cfg, const BlockShape& b, int B, in
     if (r.conv1.v_from_memory) r.v_floats = lass_wino4_vpre_floats(B, b.cin, H, W);
     if (r.conv2.v_from_memory && lass_wino4_vpre_floats(B, b.cout, H, W) > r.v_floats) r.v_floats = lass_wino4_vpre_floats(B, b.cout, H, W);
     return r;
+}
+
+// ---- the head's shortcut logits at their producers ------------------------------------------------------------------------------
+// The folded head reads decoder_block6's concat only to apply the composed 1x1 shortcut Wsc' (head_fold.h).  Both halves of that
+// concat are in registers, or in a staged tile, in the launch that produces them: the skip x1 in encoder_block1.conv2's epilogue,
+// and up = Wt act(x11) as 12 more columns (3 logits x 4 sub-pixels) of the transposed conv's GEMM.  With both formed there the head
+// reads conv1's output and two sets of logit planes, and runs no shortcut phase.  One decision for three launches of one
+// lass_separate; the stage calls never take it.
+
+// conv.hip's transposed conv with the extra cout block: 2 x 2, K = cin in 16-channel chunks, 64-cout x 32-pixel wave tiles, below
+// the input-channel count from which transposed convs run in pw_gemm.hip
+inline bool lass_tconv_logits_shape(int cin, int cout, int up_h, int up_w, int h, int w) {
+    return up_h == 2 && up_w == 2 && cin > 0 && cin % 32 == 0 && cin < kTconvGemmMinCin && cout > 0 && (4 * cout) % 64 == 0 && h > 0 &&
+           w > 0 && w % 32 == 0;
+}
+
+struct HeadScSite {
+    int windows = 0;     // 0: ResUNet30; n: the multi-STFT model with n analysis windows - its skip is the concat of n branches, each
+                         // from a launch of its own, and it keeps its launches as they are for every n (n = 1 included)
+    int tconv_cin = 0;   // decoder_block6's transposed conv
+    int up_h = 0, up_w = 0;
+};
+
+// enc1 / dec6: encoder_block1 and decoder_block6 with what lass_separate fuses into them, B, H, W: decoder_block6's image
+inline bool plan_head_sc_fold(const RouteCfg& cfg, const BlockShape& enc1, BlockIO enc1_io, const BlockShape& dec6, BlockIO dec6_io,
+                              const HeadScSite& site, int B, int H, int W) {
+    if (!cfg.f32 || !cfg.head_fold || !cfg.head_sc_fold || site.windows != 0) return false;
+    if (enc1.cout != kPreCh || dec6.cin != dec6.cout + enc1.cout) return false;  // cat = (up, skip): api.hip's concat order
+    if (!lass_tconv_logits_shape(site.tconv_cin, dec6.cout, site.up_h, site.up_w, H / 2, W / 2)) return false;
+    enc1_io.sc_planes = dec6_io.sc_planes = true;
+    return plan_block(cfg, enc1, B, H, W, enc1_io).conv2.head_sc_fold && plan_block(cfg, dec6, B, H, W, dec6_io).conv2.head_sc_fold;
 }

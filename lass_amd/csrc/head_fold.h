@@ -70,3 +70,46 @@ inline bool compose_head_fold(const float* w2, const float* wsc, const float* bs
         }
     return true;
 }
+
+// ---- the composed shortcut at the producers of its inputs (conv_route.h: plan_head_sc_fold) ------------------------------------
+// cat = (up, skip) in api.hip's concat order, up = Wt act(x11) a kernel == stride transposed conv without a bias and with nothing
+// non-linear behind it.  So Wsc' cat = Wsc'_skip x1 + Wt' act(x11) with
+//      Wt'[k][q][a][bb] = sum_c Wsc'_up[q][c] Wt[k][c][a][bb]          (Wsc' = Wa Wsc, split at channel Cup)
+// again in double from the f32 checkpoint and rounded to f32 ONCE (Wsc' enters in double, not as HeadFold::wsc).  b' is untouched.
+constexpr int kHeadScCols = 64;   // columns of the slab the transposed conv's extra block stages (the pitch of its other blocks)
+constexpr int kHeadScLive = 32;   // ... of which it contracts the first 32-column tile: Q * uh * uw live columns, the rest zero
+
+struct HeadScFold {
+    int Q = 0, Cup = 0, Cskip = 0, Kt = 0;
+    std::vector<float> wt;     // Wt' [Kt][64], column (q * uh + a) * uw + bb as the transposed conv's own (co, a, bb); the rest zero
+    std::vector<float> wskip;  // Wsc'_skip [Q][Cskip]: the table of encoder_block1.conv2's epilogue
+};
+
+// wsc (N, Cup + Cskip), wa (Q, N), wt (Kt, Cup, uh, uw): PyTorch layouts (ConvTranspose2d: input channel first).  false: a shape
+// the extra block cannot hold.
+inline bool compose_head_sc_fold(const float* wsc, const float* wa, const float* wt, int N, int Cup, int Cskip, int Q, int Kt, int uh, int uw,
+                                 HeadScFold* out) {
+    if (!wsc || !wa || !wt || !out || N <= 0 || Cup <= 0 || Cskip <= 0 || Q <= 0 || Kt <= 0 || uh <= 0 || uw <= 0 || Q * uh * uw > kHeadScLive)
+        return false;
+    HeadScFold& f = *out;
+    f.Q = Q; f.Cup = Cup; f.Cskip = Cskip; f.Kt = Kt;
+    f.wt.assign((size_t)Kt * kHeadScCols, 0.f);
+    f.wskip.assign((size_t)Q * Cskip, 0.f);
+    const int K = Cup + Cskip, S = uh * uw;
+    std::vector<double> wq(K);  // row q of Wsc' = Wa Wsc, in double
+    for (int q = 0; q < Q; ++q) {
+        for (int k = 0; k < K; ++k) {
+            double s = 0;
+            for (int n = 0; n < N; ++n) s += (double)wa[q * N + n] * (double)wsc[(size_t)n * K + k];
+            wq[k] = s;
+        }
+        for (int c = 0; c < Cskip; ++c) f.wskip[(size_t)q * Cskip + c] = (float)wq[Cup + c];
+        for (int k = 0; k < Kt; ++k)
+            for (int s = 0; s < S; ++s) {
+                double t = 0;
+                for (int c = 0; c < Cup; ++c) t += wq[c] * (double)wt[((size_t)k * Cup + c) * S + s];
+                f.wt[(size_t)k * kHeadScCols + q * S + s] = (float)t;
+            }
+    }
+    return true;
+}

@@ -110,6 +110,16 @@ struct Wino4VPre {
     float* v = nullptr;
 };
 
+// The folded head's shortcut logits, formed where their inputs are produced (conv_route.h: head_sc_fold): Wsc' cat = Wsc'_skip x1 +
+// (Wsc'_up o Wt) act(x11), as two sets of planes [B][3][H][W] f32 at decoder_block6's resolution.  encoder_block1.conv2 writes
+// `skip` from its epilogue registers, the transposed conv's extra cout block writes `up`, the head adds (skip + up) to its conv
+// sum.  (Beside ConvArgs for the same reason as Wino4Split.)
+struct HeadScPlanes {
+    float* skip = nullptr;
+    float* up = nullptr;
+    const float* w = nullptr;  // the producer's composed weights (head_fold.h): Wsc'_skip [3][32], or Wt' [Cin][64]; the head reads none
+};
+
 // The shape half of the predicates below (conv_route.h) reads a launch as its ConvShape; they add that the pointers are there.
 inline ConvShape lass_conv_shape(const ConvArgs& p) {
     ConvShape s;
@@ -119,6 +129,10 @@ inline ConvShape lass_conv_shape(const ConvArgs& p) {
 }
 
 hipError_t lass_launch_conv(ConvKind kind, const ConvArgs& p, hipStream_t stream);
+// TCONV_ACT (2 x 2, f32 output) with one more cout block in the same launch: hs.w = Wt' [Cin][64], of whose first 32-column tile
+// the 12 live columns (3 logits x 4 sub-pixels) go to hs.up as three planes at the up-sampled resolution
+bool lass_tconv_logits_supported(const ConvArgs& p, const HeadScPlanes& hs);
+hipError_t lass_launch_tconv_logits(const ConvArgs& p, const HeadScPlanes& hs, hipStream_t stream);
 
 // ---- wino.hip (Winograd F(2x2,3x3) variant of the 3x3 kinds; W must be a multiple of 32, H even) -------------------
 bool lass_wino_supported(const ConvArgs& p);
@@ -138,6 +152,12 @@ hipError_t lass_launch_wino4_weights(const float* w, int Cout, int Cin, float* U
 // composed images (U per 8-channel chunk, Wsc' [Cin2][16], b' [16]); N = Nw = 32 still name the conv that was folded
 bool lass_wino4_headfold_supported(const ConvArgs& p);
 hipError_t lass_launch_wino4_headfold(const ConvArgs& p, hipStream_t stream);
+// ... with the shortcut's logits read from hs.skip / hs.up instead of formed from in2 (which is not read; Cin2 still names it)
+bool lass_wino4_headfold_planes_supported(const ConvArgs& p, const HeadScPlanes& hs);
+hipError_t lass_launch_wino4_headfold_planes(const ConvArgs& p, const HeadScPlanes& hs, hipStream_t stream);
+// CONV2_IDENT_PRE on the 8 x 64 blocks (encoder_block1.conv2) that also writes hs.skip = hs.w x1 from its epilogue
+bool lass_wino4_sclogit_supported(const ConvArgs& p, const HeadScPlanes& hs);
+hipError_t lass_launch_wino4_sclogit(const ConvArgs& p, const HeadScPlanes& hs, hipStream_t stream);
 
 // ---- pw_gemm.hip (f32 pointwise GEMMs with a 128-cout workgroup tile; H*W % 4 == 0, N % 128 == 0, K % 32 == 0) ------------
 // CONV2_SHORTCUT: only the 1x1 shortcut, out = bias + Wsc x (in2, Cin2, w2, bias), for conv2 to read back as its residual;

@@ -1,5 +1,5 @@
 // wino4_body.h - the body of wino4.hip's conv kernels, included ONCE PER KERNEL inside the function braces: wino4_kernel
-// (ConvArgs alone), wino4_splitk_kernel (ConvArgs + Wino4Split) and wino4_vpre_kernel (+ Wino4VPre).  In scope: TC, FLAGS, `p`, `sk`, `vp`.  Text inclusion and not an
+// (ConvArgs alone), wino4_splitk_kernel (ConvArgs + Wino4Split), wino4_vpre_kernel (+ Wino4VPre) and wino4_sclogit_kernel (ConvArgs + HeadScPlanes).  In scope: TC, FLAGS, `p`, `sk`, `vp`, `hs`.  Text inclusion and not an
 // inlined device function on purpose: hipcc schedules a kernel whose body arrives through a call differently, and the unsplit
 // kernels are to stay instruction for instruction what they were before the split-K variant existed.
     constexpr bool PRO = (FLAGS & F_PRO) != 0, EPI = (FLAGS & F_EPIACT) != 0, SC = (FLAGS & F_PHASEB) != 0;
@@ -17,15 +17,19 @@
     // the transformed input arrives from memory (Wino4VPre, written by wino4_vprep_kernel): no patch loads, prologue or transform here
     constexpr bool VPRE = (FLAGS & F_VPRE) != 0;
     static_assert(!VPRE || (FLAGS & ~(F_VPRE | F_SPLITK | F_EPIACT | F_RES)) == 0, "conv1 / identity conv2 / split share: the prologue ran in the prep launch");
+    // encoder_block1.conv2 of the head_sc_fold route (conv_route.h): the epilogue also forms the folded head's shortcut logits of the
+    // skip, hs.skip[b][q] = sum_c hs.w[q][c] x1[c], from the registers the skip is stored from
+    constexpr bool SCL = (FLAGS & F_SCLOGIT) != 0;
+    static_assert(!SCL || (FLAGS == (F_RES | F_RESPRE | F_SCLOGIT) && TC == 16), "the skip's logits: encoder_block1.conv2 on the 8 x 64 blocks");
     constexpr int TR = 32 / TC;
     constexpr int OR_ = 4 * TR, OC = 4 * TC;
     constexpr int NCO = 32;  // output channels of the workgroup
-    __shared__ __attribute__((aligned(16))) float lds[U_F + V_F + 2 * NCO + (MASK ? 100 : 0)];
+    __shared__ __attribute__((aligned(16))) float lds[U_F + V_F + 2 * NCO + (MASK ? 100 : 0) + (SCL ? 96 : 0)];
     float* lu = lds;
     float* lv = lds + U_F;
     float* lds_es = lv + V_F;
     float* lds_eh = lds_es + NCO;
-    float* lds_mw = lds_eh + NCO;  // MASK: after_conv weight [3][32] + bias [3]
+    float* lds_mw = lds_eh + NCO;  // MASK: after_conv weight [3][32] + bias [3]; SCL: Wsc'_skip [3][32]
 
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -69,6 +73,9 @@
         lds_eh[tid] = p.pre_b[n0 + tid];
     }
     if (MASK && tid < 99) lds_mw[tid] = tid < 96 ? p.mask_w[tid] : p.mask_b[tid - 96];
+    if constexpr (SCL) {
+        if (tid < 96) lds_mw[tid] = hs.w[tid];
+    }
 
     f32x4 acc[NXI];
 #pragma unroll
@@ -224,6 +231,31 @@
             }
         }
     }
+    if constexpr (SCL) {
+        // ---- the skip's share of the head's shortcut logits, in the shape of the F_MASK reduction below: the 32 channels of a
+        // pixel sit in the 4 kq lane groups of the 2 cout waves.  Every lane forms its partial logits (3 x 16 pixels over its 4
+        // channels, fixed order) and leaves them in the dead U / V region, [source = wco * 4 + kq][logit][pixel = tile * 16 + s];
+        // they are summed behind the skip's stores, which need no LDS.
+        float* part = lds;  // 8 * 3 * 512 floats = 48 KiB <= U_F + V_F
+        lds_barrier();      // every wave is past its last MFMA phase
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            float w4[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) w4[r] = lds_mw[q * 32 + wco * 16 + kq * 4 + r];
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                float4 o;
+                float* op = &o.x;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const f32x4 v = ysp[a * 4 + c];
+                    op[c] = fmaf(v[3], w4[3], fmaf(v[2], w4[2], fmaf(v[1], w4[1], v[0] * w4[0])));
+                }
+                *reinterpret_cast<float4*>(part + ((wco * 4 + kq) * 3 + q) * 512 + ot * 16 + a * 4) = o;
+            }
+        }
+    }
     if constexpr (RES && !RESPRE) {
         // + the residual at this lane's 4 couts x 16 pixels (resunet.py:165): for the routed shortcut layers bias + Wsc x, which
         // pw_gemm.hip wrote into the output slot itself - read here and overwritten below by the same lane.  All 16 rows are
@@ -373,5 +405,25 @@
                 o.y = s1 * 0.25f;
                 if (oy + 2 * i + 1 < p.H) *reinterpret_cast<float2*>(pd + (size_t)i * Wo) = o;
             }
+        }
+    }
+    if constexpr (SCL) {
+        // ---- every thread sums 2 pixels (same tile, same row) over the 8 sources, in source order: a clip's planes depend on
+        // nothing but the clip
+        const float* part = lds;
+        lds_barrier();
+        const int px = tid * 2;
+        const int mt = px >> 4, ms = px & 15;
+        const int my = y0 + 4 * (mt / TC) + (ms >> 2), mx = x0 + 4 * (mt % TC) + (ms & 3);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            float2 sum = *reinterpret_cast<const float2*>(part + q * 512 + px);
+#pragma unroll
+            for (int src = 1; src < 8; ++src) {
+                const float2 v = *reinterpret_cast<const float2*>(part + (src * 3 + q) * 512 + px);
+                sum.x += v.x;
+                sum.y += v.y;
+            }
+            if (my < p.H) *reinterpret_cast<float2*>(hs.skip + ((size_t)b * 3 + q) * HW + (size_t)my * p.W + mx) = sum;
         }
     }
