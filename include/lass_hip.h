@@ -118,6 +118,29 @@ int lass_workspace_bytes(const lass_ctx* ctx, int B, int L, size_t* bytes);
 int lass_separate(lass_ctx* ctx, const float* mixture, const float* condition, float* out, int B, int L,
                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- ragged batches: clips of different lengths in one call ------------------------------------------------------ */
+
+/* lass_separate for B clips of different lengths.  mixture and out are (B,L) with rows L samples apart; clip b is
+ * mixture[b][0 .. lengths[b]) and the rest of its row is never read.  lengths: DEVICE int32 (B).
+ * A clip of Lb samples has 1 + Lb/160 frames, zero-padded after bn0 to a multiple of 32 (resunet.py:543-548): the network sees
+ * one (padded frames, n_fft/2) image per clip, and clips whose padded frame counts agree can share every launch.  So every clip
+ * must lie in the bucket of L:  max(160*(Tp-32), n_fft/2+1) <= lengths[b] <= L,  Tp = 32*ceil((1 + L/160)/32)  - the interval
+ * lass_ragged_bucket returns.  Row b of `out` is then, bit for bit, what lass_separate gives for that clip alone at its own
+ * length (f32; in the bf16 modes as close as lass_separate's own batch-size dependence allows), in out[b][0 .. lengths[b]).
+ * The zero tail: out[b][lengths[b] .. L) is written as 0.0f.  With zero-padded rows on the input side too, lass_sdr_stats and
+ * lass_mix_at_snr work on the padded rows unchanged - their sums gain only exact zeros and the 1/L of their two means cancels.
+ * Bucket membership is the CALLER'S to check: the library never reads the array on the host.  The kernels clamp every entry
+ * into the interval above, so a wrong length gives a wrong clip and never an access out of range.
+ * Everything else is lass_separate's: both kinds of context, all compute modes, lass_workspace_bytes(B, L), the half-batch
+ * split (the second half reads lengths + B/2) and graph replay - the key includes the `lengths` POINTER, its contents are
+ * read when the graph runs, so a caller that keeps its buffers may rewrite the lengths between calls.
+ * NULL lengths: LASS_ERR_ARG. */
+int lass_separate_ragged(lass_ctx* ctx, const float* mixture, const int* lengths, const float* condition, float* out,
+                         int B, int L, void* workspace, size_t workspace_bytes, void* stream);
+/* Host helper, launches nothing: the closed interval [*lo, *hi] of lengths that may share a call whose rows are L samples long
+ * on this context (*hi == L).  <0 for L <= n_fft/2.  Either output may be NULL. */
+int lass_ragged_bucket(const lass_ctx* ctx, int L, int* lo, int* hi);
+
 /* Graph replay.  The third consecutive lass_separate call with the same pointers and shape is captured into a hipGraph
  * and replayed on the caller's stream from then on (one graph per context; a different combination is captured anew
  * after it, too, has been seen three times in a row).  Nothing else about the call changes; profiled
@@ -231,6 +254,17 @@ int lass_encoder_block(lass_ctx* ctx, const char* name, const float* x, int B, i
  * the mask window's. */
 int lass_front_end(lass_ctx* ctx, const float* wav, int B, int L, float* mag, float* cos_out, float* sin_out, float* x0,
                    void* stream);
+
+/* lass_front_end with a length per clip (lengths: DEVICE int32 (B), as in lass_separate_ragged; shapes as for B clips of L
+ * samples: T = 1 + L/160, Tpad = 32*ceil(T/32)).  With Tb = 1 + lengths[b]/160: rows t < Tb of clip b are what lass_front_end
+ * writes for that clip alone; rows Tb <= t < Tpad of x0 (every analysis window) and rows Tb <= t < T of mag/cos/sin are 0. */
+int lass_front_end_ragged(lass_ctx* ctx, const float* wav, const int* lengths, int B, int L, float* mag, float* cos_out,
+                          float* sin_out, float* x0, void* stream);
+/* lass_istft_nfft with a length per clip: real, imag (B,T,n_fft/2+1) with T = 1 + L/160 -> wav (B,L).  Only frames
+ * t < 1 + lengths[b]/160 of clip b are overlap-added; wav[b][0 .. lengths[b]) is what lass_istft_nfft gives for the clip
+ * alone, wav[b][lengths[b] .. L) is 0. */
+int lass_istft_ragged(lass_ctx* ctx, const float* real, const float* imag, const int* lengths, int B, int T, int L, int n_fft,
+                      int win_length, float* wav, void* stream);
 
 /* Where lass_separate(B, L) leaves a named intermediate inside the caller's workspace (f32 compute mode; in the bf16
  * modes several of these hold blocked bf16 data instead): byte offset, shape (B,C,H,W) and element strides.  Names:

@@ -21,6 +21,13 @@ SYMBOLS = [
     ("lass_finalize", c_int, [c_void_p, c_int]),
     ("lass_workspace_bytes", c_int, [c_void_p, c_int, c_int, POINTER(c_size_t)]),
     ("lass_separate", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    ("lass_separate_ragged", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t,
+                                     c_void_p]),
+    ("lass_ragged_bucket", c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_int)]),
+    ("lass_front_end_ragged", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p]),
+    ("lass_istft_ragged", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                  c_void_p]),
     ("lass_stft_magphase", c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_void_p]),
     ("lass_mix_at_snr", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),

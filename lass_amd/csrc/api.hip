@@ -131,10 +131,12 @@ struct lass_ctx {
     bool use_graph = true;
     struct GraphKey {
         const void *mix = nullptr, *cond = nullptr, *out = nullptr, *ws = nullptr;
+        const void* lens = nullptr;  // lass_separate_ragged's lengths (the pointer: its contents are read at replay time)
         int B = 0, L = 0;
         unsigned long gen = 0;
         bool operator==(const GraphKey& o) const {
-            return mix == o.mix && cond == o.cond && out == o.out && ws == o.ws && B == o.B && L == o.L && gen == o.gen;
+            return mix == o.mix && cond == o.cond && out == o.out && ws == o.ws && lens == o.lens && B == o.B && L == o.L &&
+                   gen == o.gen;
         }
     };
     // A small cache of instantiated graphs: the evaluator alternates between its common batch and a ragged tail, long-form
@@ -889,7 +891,7 @@ const ResBlock* find_block(const lass_ctx* c, const std::string& prefix) {
 
 extern "C" {
 
-int lass_version(void) { return 10300; }  // 1.3.0: CLAP text tower (lass_text_*, text.hip); 1.2.0: F(4x4,3x3) kernels, lass_set_graph_replay (1.1.0: multi-STFT model, fused iSTFT, graph replay)
+int lass_version(void) { return 10400; }  // 1.4.0: per-clip lengths (lass_separate_ragged & co); 1.3.0: CLAP text tower (lass_text_*, text.hip); 1.2.0: F(4x4,3x3) kernels, lass_set_graph_replay (1.1.0: multi-STFT model, fused iSTFT, graph replay)
 
 const char* lass_last_error(const lass_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_err.c_str(); }
 
@@ -1399,6 +1401,35 @@ int lass_front_end(lass_ctx* c, const float* wav, int B, int L, float* mag, floa
     return 0;
 }
 
+int lass_front_end_ragged(lass_ctx* c, const float* wav, const int* lengths, int B, int L, float* mag, float* cos_out,
+                          float* sin_out, float* x0, void* stream) {
+    int r = check_ready(c);
+    if (r) return r;
+    const Geometry& g = c->g;
+    if (!wav || !lengths || !x0 || B <= 0 || L <= g.nfft / 2) return fail(c, LASS_ERR_ARG, "lass_front_end_ragged: bad argument");
+    const int T = 1 + L / LASS_HOP, Tp = (T + 31) / 32 * 32;
+    StftBranch br[kMaxBranches];
+    for (int k = 0; k < g.nbr; ++k) {  // as lass_front_end
+        br[k].wlen = g.wins[k];
+        br[k].x0 = x0 + (size_t)k * B * Tp * g.fcrop;
+        if (k == g.mask_br) { br[k].mag = mag; br[k].cosv = cos_out; br[k].sinv = sin_out; }
+    }
+    HIP_TRY(c, lass_launch_stft2_ragged(wav, lengths, B, L, g.nfft, LASS_HOP, T, Tp, g.nbr, br, g.magphase_sem, c->bn0_s,
+                                        c->bn0_h, c->tw2k, (hipStream_t)stream));
+    return 0;
+}
+
+int lass_istft_ragged(lass_ctx* c, const float* real, const float* imag, const int* lengths, int B, int T, int L, int n_fft,
+                      int win_length, float* wav, void* stream) {
+    if (!c || !real || !imag || !lengths || !wav || B <= 0 || (n_fft != 1024 && n_fft != 2048) || L <= n_fft / 2 ||
+        T != 1 + L / LASS_HOP || win_length < 32 || win_length > n_fft || (2048 % win_length) != 0)
+        return fail(c, LASS_ERR_ARG, "lass_istft_ragged: bad argument (T = 1 + L/160 frames per clip, L > n_fft/2)");
+    if (int r = use_device(c)) return r;
+    HIP_TRY(c, lass_launch_istft2_ragged(real, imag, lengths, B, T, L, n_fft, win_length, LASS_HOP, c->tw2k, wav,
+                                         (hipStream_t)stream));
+    return 0;
+}
+
 int lass_workspace_tensor(const lass_ctx* c, int B, int L, const char* name_c, size_t* offset, int64_t shape[4],
                           int64_t strides[4]) {
     if (!c || !name_c || !offset || !shape || !strides) return LASS_ERR_ARG;
@@ -1541,8 +1572,10 @@ struct Components {
     const float* sinv;
 };
 
+// lengths: nullptr, or one length per clip (device): the two ends of the network then run their per-clip-length forms
 static int separate_impl(lass_ctx* c, const float* mixture, const Components* comp, const float* condition, float* out,
-                         int B, int L, void* workspace, size_t workspace_bytes, void* stream, const char* who) {
+                         int B, int L, void* workspace, size_t workspace_bytes, void* stream, const char* who,
+                         const int* lengths = nullptr) {
     int r = check_ready(c);
     if (r) return r;
     const Geometry& g = c->g;
@@ -1575,8 +1608,12 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
             br[k].x0 = F(pl.x0[k]);
             if (k == g.mask_br) { br[k].mag = F(pl.mag); br[k].cosv = F(pl.cosv); br[k].sinv = F(pl.sinv); }
         }
-        HIP_TRY(c, lass_launch_stft2(mixture, B, L, g.nfft, LASS_HOP, T, Tp, nbr, br, g.magphase_sem, c->bn0_s, c->bn0_h,
-                                     c->tw2k, st));
+        if (lengths)
+            HIP_TRY(c, lass_launch_stft2_ragged(mixture, lengths, B, L, g.nfft, LASS_HOP, T, Tp, nbr, br, g.magphase_sem,
+                                                c->bn0_s, c->bn0_h, c->tw2k, st));
+        else
+            HIP_TRY(c, lass_launch_stft2(mixture, B, L, g.nfft, LASS_HOP, T, Tp, nbr, br, g.magphase_sem, c->bn0_s, c->bn0_h,
+                                         c->tw2k, st));
     } else {
         ProfScope ps(c, st, P_STFT);
         for (int k = 0; k < nbr; ++k) {
@@ -1708,20 +1745,24 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
     }
     {
         ProfScope ps(c, st, P_ISTFT);
-        HIP_TRY(c, lass_launch_istft2(F(pl.oreal), F(pl.oimag), B, T, L, g.nfft, g.wins[g.mask_br], LASS_HOP, c->tw2k, out, st));
+        if (lengths)
+            HIP_TRY(c, lass_launch_istft2_ragged(F(pl.oreal), F(pl.oimag), lengths, B, T, L, g.nfft, g.wins[g.mask_br], LASS_HOP,
+                                                 c->tw2k, out, st));
+        else
+            HIP_TRY(c, lass_launch_istft2(F(pl.oreal), F(pl.oimag), B, T, L, g.nfft, g.wins[g.mask_br], LASS_HOP, c->tw2k, out, st));
     }
     return 0;
 }
 
 // lass_separate's launches, whole or as two overlapping half-batches (lass_ctx::split_batch).  Capture-safe: under stream
 // capture the event pair makes `s2` a parallel branch of the same graph.
-static int separate_any(lass_ctx* c, const float* mixture, const float* condition, float* out, int B, int L, void* workspace,
-                        size_t workspace_bytes, hipStream_t stream, bool capturing) {
+static int separate_any(lass_ctx* c, const float* mixture, const int* lengths, const float* condition, float* out, int B, int L,
+                        void* workspace, size_t workspace_bytes, hipStream_t stream, bool capturing, const char* who) {
     Plan ph;
     if (!c->finalized || !split_halves(c, B) || !mixture || !condition || !out || !workspace || (!capturing && c->split_batch < 2) ||
         make_plan(c, B / 2, L, &ph) || 2 * ((ph.total + 255) / 256 * 256) > workspace_bytes) {
         c->last_split[{B, L}] = false;
-        return separate_impl(c, mixture, nullptr, condition, out, B, L, workspace, workspace_bytes, stream, "lass_separate");
+        return separate_impl(c, mixture, nullptr, condition, out, B, L, workspace, workspace_bytes, stream, who, lengths);
     }
     c->last_split[{B, L}] = true;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1734,9 +1775,9 @@ static int separate_any(lass_ctx* c, const float* mixture, const float* conditio
     const size_t half_ws = (ph.total + 255) / 256 * 256;
     HIP_TRY(c, hipEventRecord(c->ev_fork, stream));
     HIP_TRY(c, hipStreamWaitEvent(c->s2, c->ev_fork, 0));
-    int r = separate_impl(c, mixture, nullptr, condition, out, h, L, workspace, half_ws, stream, "lass_separate");
+    int r = separate_impl(c, mixture, nullptr, condition, out, h, L, workspace, half_ws, stream, who, lengths);
     const int r2 = separate_impl(c, mixture + (size_t)h * L, nullptr, condition + (size_t)h * LASS_COND, out + (size_t)h * L, h, L,
-                                 (char*)workspace + half_ws, half_ws, c->s2, "lass_separate");
+                                 (char*)workspace + half_ws, half_ws, c->s2, who, lengths ? lengths + h : nullptr);
     if (!r) r = r2;
     // the join is recorded even after a failure: a capturing stream must get its branch back
     HIP_TRY(c, hipEventRecord(c->ev_join, c->s2));
@@ -1744,15 +1785,16 @@ static int separate_any(lass_ctx* c, const float* mixture, const float* conditio
     return r;
 }
 
-int lass_separate(lass_ctx* c, const float* mixture, const float* condition, float* out, int B, int L, void* workspace,
-                  size_t workspace_bytes, void* stream) {
-    if (!c) return LASS_ERR_ARG;
-    if (!mixture) return fail(c, LASS_ERR_ARG, "lass_separate: null pointer");
+// lass_separate (lengths == nullptr) and lass_separate_ragged: one call, eager or through the graph cache
+static int separate_call(lass_ctx* c, const float* mixture, const int* lengths, const float* condition, float* out, int B, int L,
+                         void* workspace, size_t workspace_bytes, void* stream, const char* who) {
+    if (!mixture) return fail(c, LASS_ERR_ARG, std::string(who) + ": null pointer");
     // Graph replay: the third call that presents the same (pointers, shape) key is captured once (on an internal stream; the
     // caller's may be the legacy default stream, which cannot be captured) and replayed from then on.  Callers that hand
     // over fresh buffers every time simply stay on the eager path; so does a profiled context.
     lass_ctx::GraphKey key;
-    key.mix = mixture; key.cond = condition; key.out = out; key.ws = workspace; key.B = B; key.L = L; key.gen = c->gen;
+    key.mix = mixture; key.cond = condition; key.out = out; key.ws = workspace; key.lens = lengths; key.B = B; key.L = L;
+    key.gen = c->gen;
     if (c->use_graph && !c->profiling && c->finalized) {
         ++c->g_tick;
         lass_ctx::GraphEntry* slot = nullptr;
@@ -1793,7 +1835,7 @@ int lass_separate(lass_ctx* c, const float* mixture, const float* condition, flo
                 Plan pl0;
                 if (!condition || !out || !workspace || make_plan(c, B, L, &pl0) || workspace_bytes < pl0.total ||
                     ((uintptr_t)workspace & 255) != 0)
-                    return separate_any(c, mixture, condition, out, B, L, workspace, workspace_bytes, (hipStream_t)stream, false);
+                    return separate_any(c, mixture, lengths, condition, out, B, L, workspace, workspace_bytes, (hipStream_t)stream, false, who);
                 slot->need = pl0.total;
                 if (split_halves(c, B)) {  // (checked again at capture time by separate_any: smaller workspaces run unsplit)
                     Plan ph0;
@@ -1805,7 +1847,7 @@ int lass_separate(lass_ctx* c, const float* mixture, const float* condition, flo
             if (!c->g_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->g_stream, hipStreamNonBlocking));
             bool ok = false;
             if (hipStreamBeginCapture(c->g_stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                const int r = separate_any(c, mixture, condition, out, B, L, workspace, workspace_bytes, c->g_stream, true);
+                const int r = separate_any(c, mixture, lengths, condition, out, B, L, workspace, workspace_bytes, c->g_stream, true, who);
                 hipGraph_t graph = nullptr;
                 const hipError_t e = hipStreamEndCapture(c->g_stream, &graph);  // always ends the capture, also after a failure
                 if (r == 0 && e == hipSuccess && graph && hipGraphInstantiate(&slot->exec, graph, nullptr, nullptr, 0) == hipSuccess) {
@@ -1828,7 +1870,28 @@ int lass_separate(lass_ctx* c, const float* mixture, const float* condition, flo
             c->err.clear();
         }
     }
-    return separate_any(c, mixture, condition, out, B, L, workspace, workspace_bytes, (hipStream_t)stream, false);
+    return separate_any(c, mixture, lengths, condition, out, B, L, workspace, workspace_bytes, (hipStream_t)stream, false, who);
+}
+
+int lass_separate(lass_ctx* c, const float* mixture, const float* condition, float* out, int B, int L, void* workspace,
+                  size_t workspace_bytes, void* stream) {
+    if (!c) return LASS_ERR_ARG;
+    return separate_call(c, mixture, nullptr, condition, out, B, L, workspace, workspace_bytes, stream, "lass_separate");
+}
+
+int lass_ragged_bucket(const lass_ctx* c, int L, int* lo, int* hi) {
+    if (!c || L <= c->g.nfft / 2) return LASS_ERR_ARG;
+    const int T = 1 + L / LASS_HOP, Tp = (T + 31) / 32 * 32;
+    if (lo) *lo = std::max(LASS_HOP * (Tp - 32), c->g.nfft / 2 + 1);
+    if (hi) *hi = L;  // a row holds L samples
+    return 0;
+}
+
+int lass_separate_ragged(lass_ctx* c, const float* mixture, const int* lengths, const float* condition, float* out, int B, int L,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+    if (!c) return LASS_ERR_ARG;
+    if (!lengths) return fail(c, LASS_ERR_ARG, "lass_separate_ragged: null lengths");
+    return separate_call(c, mixture, lengths, condition, out, B, L, workspace, workspace_bytes, stream, "lass_separate_ragged");
 }
 
 int lass_set_graph_replay(lass_ctx* c, int enabled) {

@@ -210,6 +210,14 @@ hipError_t lass_launch_stft2(const float* wav, int B, int L, int n_fft, int hop,
 // Fused inverse STFT (inverse transforms + overlap-add + envelope + trim in one kernel, no frame scratch).
 hipError_t lass_launch_istft2(const float* real, const float* imag, int B, int T, int L, int n_fft, int wlen, int hop,
                               const float2* tw2k, float* wav, hipStream_t stream);
+// The same two kernels with a length per clip (lengths: device int32 (B), clamped into the 32-frame bucket of L by the kernels):
+// rows L samples / T = 1 + L / hop frames apart, Tpad = 32 * ceil(T / 32).  Beyond a clip's own frames x0 and the spectra are 0;
+// beyond its own samples the waveform is 0.
+hipError_t lass_launch_stft2_ragged(const float* wav, const int* lengths, int B, int L, int n_fft, int hop, int T, int Tpad,
+                                    int nbr, const StftBranch* br, int magphase_sem, const float* s0, const float* h0,
+                                    const float2* tw2k, hipStream_t stream);
+hipError_t lass_launch_istft2_ragged(const float* real, const float* imag, const int* lengths, int B, int T, int L, int n_fft,
+                                     int wlen, int hop, const float2* tw2k, float* wav, hipStream_t stream);
 
 // ---- misc.hip -----------------------------------------------------------------------------------------------------
 // film[b][j] = dot(cond[b], Wf[j]) + bf[j] (+ base[j] if base)   for j < n

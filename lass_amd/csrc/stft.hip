@@ -338,6 +338,166 @@ __global__ __launch_bounds__(256) void istft2_kernel(const float* __restrict__ r
     }
 }
 
+// ---- per-clip lengths (lass_separate_ragged) -------------------------------------------------------------------------
+// Clips whose lengths fall in one 32-frame bucket share every launch between the two ends of the network: the U-Net sees a
+// (Tpad, n_fft/2) image per clip whatever its length.  What differs per clip is where the reflect padding turns round, how
+// many rows of x0 are real, and what the iSTFT overlap-adds and trims - the two kernels below, siblings of stft2_kernel and
+// istft2_kernel that read a clip's length from `lengths` (device, int32) and are otherwise the same arithmetic in the same
+// order: clip b of a ragged call is bit-identical to that clip run alone at its own length.  Rows are L samples apart, T =
+// 1 + L / hop frames apart; `lo` is the smallest length of L's bucket.  A length outside [lo, L] is clamped into it, so a
+// wrong entry gives a wrong clip, never an access out of range.
+__device__ __forceinline__ int ragged_len(const int* __restrict__ lengths, int b, int lo, int L) {
+    const int v = lengths[b];
+    return v < lo ? lo : (v > L ? L : v);
+}
+
+// Rows t < Tb = 1 + Lb / hop as stft2_kernel writes them for a clip of Lb samples; rows Tb <= t < Tpad of x0 and rows
+// Tb <= t < T of mag / cos / sin / real / imag are 0.  Nothing of a clip's row is read at or beyond Lb.
+template <int N, bool MAGPHASE>
+__global__ __launch_bounds__(256) void stft2_ragged_kernel(const float* __restrict__ wav, const int* __restrict__ lengths,
+                                                           int lo, int L, int hop, int T, int Tpad,
+                                                           const float2* __restrict__ tw2k, Stft2Args a,
+                                                           const float* __restrict__ s0, const float* __restrict__ h0) {
+    __shared__ float2 A[N], Bf[N], TW[2048];
+    constexpr int NB = N / 2 + 1, FC = N / 2;
+    const int ta = 2 * blockIdx.x, b = blockIdx.y, z = blockIdx.z, tid = threadIdx.x;
+    const int Lb = ragged_len(lengths, b, lo, L), Tb = 1 + Lb / hop;
+    float* x0 = a.x0[z];
+    float *mag = a.mag[z], *cosv = a.cosv[z], *sinv = a.sinv[z], *real = a.real[z], *imag = a.imag[z];
+    // rows from `from` of this frame pair lie beyond the clip: zeros in the network input and in the spectra
+    const auto zero_rows = [&](int from) {
+        for (int t = from; t < ta + 2; ++t) {
+            if (x0 && t < Tpad)
+                for (int f = tid; f < FC; f += 256) x0[((size_t)b * Tpad + t) * FC + f] = 0.f;
+            if (t < T)
+                for (int f = tid; f < NB; f += 256) {
+                    const size_t row = ((size_t)b * T + t) * NB + f;
+                    if (real) real[row] = 0.f;
+                    if (imag) imag[row] = 0.f;
+                    if (mag) mag[row] = 0.f;
+                    if (cosv) cosv[row] = 0.f;
+                    if (sinv) sinv[row] = 0.f;
+                }
+        }
+    };
+    if (ta >= Tb) {
+        zero_rows(ta);
+        return;
+    }
+    for (int i = tid; i < 2048; i += 256) TW[i] = tw2k[i];
+    __syncthreads();
+    const int wlen = a.wlen[z], woff = (N - wlen) / 2, wstride = 2048 / wlen;
+    const float* w = wav + (size_t)b * L;
+    const bool have_b = ta + 1 < Tb;
+    for (int idx = tid; idx < N; idx += 256) {
+        float2 v = make_float2(0.f, 0.f);
+        const int j = idx - woff;
+        if (j >= 0 && j < wlen) {
+            const float wn = 0.5f - 0.5f * TW[j * wstride].x;  // periodic Hann of wlen
+            int n = ta * hop + idx - N / 2;                     // centre=True, reflect padding of n_fft/2 about Lb - 1
+            int n2 = n + hop;
+            if (n < 0) n = -n;
+            if (n >= Lb) n = 2 * (Lb - 1) - n;
+            if (n2 < 0) n2 = -n2;
+            if (n2 >= Lb) n2 = 2 * (Lb - 1) - n2;
+            v = make_float2(w[n] * wn, have_b ? w[n2] * wn : 0.f);
+        }
+        A[idx] = v;
+    }
+    __syncthreads();
+    const float2* Z = fft_c<N, false>(A, Bf, TW, tid);
+    for (int f = tid; f < NB; f += 256) {
+        const float2 z1 = Z[f], z2 = Z[(N - f) & (N - 1)];
+        const float re[2] = {0.5f * (z1.x + z2.x), 0.5f * (z1.y + z2.y)};
+        const float im[2] = {0.5f * (z1.y - z2.y), -0.5f * (z1.x - z2.x)};
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            if (r == 1 && !have_b) break;
+            const size_t row = ((size_t)b * T + ta + r) * NB + f;
+            float m, c, s;
+            if (MAGPHASE) {
+                m = sqrtf(re[r] * re[r] + im[r] * im[r]);
+                const float den = fmaxf(m, 1e-10f);
+                c = re[r] / den; s = im[r] / den;
+            } else {
+                m = sqrtf(fmaxf(re[r] * re[r] + im[r] * im[r], 1e-10f));
+                c = re[r] / m; s = im[r] / m;
+            }
+            if (real) real[row] = re[r];
+            if (imag) imag[row] = im[r];
+            if (mag) mag[row] = m;
+            if (cosv) cosv[row] = c;
+            if (sinv) sinv[row] = s;
+            if (x0 && f < FC) x0[((size_t)b * Tpad + ta + r) * FC + f] = m * s0[f] + h0[f];
+        }
+    }
+    if (!have_b) zero_rows(ta + 1);
+}
+
+// istft2_kernel over the frames t < Tb of a clip of Lb samples: samples n < Lb as that kernel writes them for the clip alone,
+// samples Lb <= n < L are 0 (the zero tail: sums over a padded row gain only exact zeros).
+template <int N>
+__global__ __launch_bounds__(256) void istft2_ragged_kernel(const float* __restrict__ real, const float* __restrict__ imag,
+                                                            const int* __restrict__ lengths, int lo, int T, int L, int hop,
+                                                            int wlen, const float2* __restrict__ tw2k,
+                                                            float* __restrict__ wav) {
+    __shared__ float2 A[N], Bf[N], TW[2048];
+    __shared__ float acc[ISTFT_SPAN], env[ISTFT_SPAN];
+    constexpr int NB = N / 2 + 1;
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int m0 = blockIdx.x * ISTFT_SPAN;  // first padded position of this span
+    const int Lb = ragged_len(lengths, b, lo, L), Tb = 1 + Lb / hop;
+    if (m0 - N / 2 >= Lb) {  // the whole span lies beyond the clip's end
+        for (int i = tid; i < ISTFT_SPAN; i += 256) {
+            const int n = m0 + i - N / 2;
+            if (n < L) wav[(size_t)b * L + n] = 0.f;
+        }
+        return;
+    }
+    const int woff = (N - wlen) / 2, wstride = 2048 / wlen;
+    for (int i = tid; i < 2048; i += 256) TW[i] = tw2k[i];
+    for (int i = tid; i < ISTFT_SPAN; i += 256) { acc[i] = 0.f; env[i] = 0.f; }
+    // frames whose window support [t*hop + woff, t*hop + woff + wlen) meets [m0, m0 + SPAN)
+    int t_lo = m0 - woff - wlen + 1;
+    t_lo = t_lo <= 0 ? 0 : (t_lo + hop - 1) / hop;
+    int t_hi = (m0 + ISTFT_SPAN - 1 - woff) / hop;
+    if (m0 + ISTFT_SPAN - 1 - woff < 0) t_hi = -1;
+    if (t_hi > Tb - 1) t_hi = Tb - 1;
+    __syncthreads();
+    for (int ta = t_lo; ta <= t_hi; ta += 2) {
+        const bool have_b = ta + 1 <= t_hi;
+        const size_t rowa = ((size_t)b * T + ta) * NB, rowb = rowa + NB;
+        for (int k = tid; k < N; k += 256) {  // Z = Xa + i Xb, Hermitian-extended (see istft2_kernel)
+            const int kk = k <= N / 2 ? k : N - k;
+            const float sg = (kk == 0 || kk == N / 2) ? 0.f : (k <= N / 2 ? 1.f : -1.f);
+            const float ar = real[rowa + kk], ai = sg * imag[rowa + kk];
+            const float br = have_b ? real[rowb + kk] : 0.f, bi = have_b ? sg * imag[rowb + kk] : 0.f;
+            A[k] = make_float2(ar - bi, ai + br);
+        }
+        __syncthreads();
+        const float2* X = fft_c<N, true>(A, Bf, TW, tid);  // (xa, xb) * N
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            if (r == 1 && !have_b) break;
+            const int base = (ta + r) * hop + woff - m0;  // span position of window sample 0
+            for (int j = tid; j < wlen; j += 256) {
+                const int pos = base + j;
+                if (pos >= 0 && pos < ISTFT_SPAN) {
+                    const float wn = 0.5f - 0.5f * TW[j * wstride].x;
+                    const float2 x = X[woff + j];
+                    acc[pos] += (r == 0 ? x.x : x.y) * (wn * (1.0f / N));
+                    env[pos] += wn * wn;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (int i = tid; i < ISTFT_SPAN; i += 256) {
+        const int n = m0 + i - N / 2;
+        if (n >= 0 && n < L) wav[(size_t)b * L + n] = n < Lb ? acc[i] / fmaxf(env[i], 1e-11f) : 0.f;
+    }
+}
+
 }  // namespace
 
 hipError_t lass_launch_multi_stft(const float* wav, int B, int L, int hop, int nwin, const int* n_fft,
@@ -392,6 +552,53 @@ hipError_t lass_launch_istft2(const float* real, const float* imag, int B, int T
         hipLaunchKernelGGL(istft2_kernel<1024>, grid, dim3(256), 0, stream, real, imag, T, L, hop, wlen, tw2k, wav);
     else
         hipLaunchKernelGGL(istft2_kernel<2048>, grid, dim3(256), 0, stream, real, imag, T, L, hop, wlen, tw2k, wav);
+    return hipGetLastError();
+}
+
+// The smallest length that shares a 32-frame bucket with L: max(hop * (Tpad - 32), n_fft / 2 + 1).
+static int ragged_lo(int L, int n_fft, int hop) {
+    const int T = 1 + L / hop, Tpad = (T + 31) / 32 * 32;
+    const int a = hop * (Tpad - 32), b = n_fft / 2 + 1;
+    return a > b ? a : b;
+}
+
+hipError_t lass_launch_stft2_ragged(const float* wav, const int* lengths, int B, int L, int n_fft, int hop, int T, int Tpad,
+                                    int nbr, const StftBranch* br, int magphase_sem, const float* s0, const float* h0,
+                                    const float2* tw2k, hipStream_t stream) {
+    if (!lengths || B <= 0 || hop <= 0 || nbr <= 0 || nbr > LASS_MAX_STFT_WINDOWS || (n_fft != 1024 && n_fft != 2048) ||
+        L <= n_fft / 2 || T != 1 + L / hop || Tpad != (T + 31) / 32 * 32)
+        return hipErrorInvalidValue;
+    Stft2Args a;
+    a.nbr = nbr;
+    bool any_x0 = false;
+    for (int i = 0; i < nbr; ++i) {
+        const int wl = br[i].wlen;
+        if (wl <= 0 || wl > n_fft || (2048 % wl) != 0 || ((n_fft - wl) & 1)) return hipErrorInvalidValue;
+        if (br[i].x0 && (!s0 || !h0)) return hipErrorInvalidValue;
+        any_x0 |= br[i].x0 != nullptr;
+        a.wlen[i] = wl; a.mag[i] = br[i].mag; a.cosv[i] = br[i].cosv; a.sinv[i] = br[i].sinv;
+        a.real[i] = br[i].real; a.imag[i] = br[i].imag; a.x0[i] = br[i].x0;
+    }
+    const int lo = ragged_lo(L, n_fft, hop);
+    dim3 grid(((any_x0 ? Tpad : T) + 1) / 2, B, nbr);
+#define LASS_STFT2R(NN, MP) hipLaunchKernelGGL((stft2_ragged_kernel<NN, MP>), grid, dim3(256), 0, stream, wav, lengths, lo, L, hop, T, Tpad, tw2k, a, s0, h0)
+    if (n_fft == 1024) { if (magphase_sem) LASS_STFT2R(1024, true); else LASS_STFT2R(1024, false); }
+    else               { if (magphase_sem) LASS_STFT2R(2048, true); else LASS_STFT2R(2048, false); }
+#undef LASS_STFT2R
+    return hipGetLastError();
+}
+
+hipError_t lass_launch_istft2_ragged(const float* real, const float* imag, const int* lengths, int B, int T, int L, int n_fft,
+                                     int wlen, int hop, const float2* tw2k, float* wav, hipStream_t stream) {
+    if (!lengths || B <= 0 || L <= n_fft / 2 || hop != LASS_HOP || T != 1 + L / hop || (n_fft != 1024 && n_fft != 2048) ||
+        wlen <= 0 || wlen > n_fft || (2048 % wlen) != 0 || ((n_fft - wlen) & 1))
+        return hipErrorInvalidValue;
+    const int lo = ragged_lo(L, n_fft, hop);
+    dim3 grid((n_fft / 2 + L + ISTFT_SPAN - 1) / ISTFT_SPAN, B);
+    if (n_fft == 1024)
+        hipLaunchKernelGGL(istft2_ragged_kernel<1024>, grid, dim3(256), 0, stream, real, imag, lengths, lo, T, L, hop, wlen, tw2k, wav);
+    else
+        hipLaunchKernelGGL(istft2_ragged_kernel<2048>, grid, dim3(256), 0, stream, real, imag, lengths, lo, T, L, hop, wlen, tw2k, wav);
     return hipGetLastError();
 }
 

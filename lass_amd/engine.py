@@ -125,6 +125,55 @@ class Engine:
         _lib.check(self.ctx, rc, "lass_separate")
         return out
 
+    def ragged_bucket(self, L: int):
+        """(lo, hi): the lengths that may share a `separate_ragged` call with rows of L samples (lass_ragged_bucket)."""
+        lo, hi = c_int(), c_int()
+        if self.lib.lass_ragged_bucket(self.ctx, int(L), byref(lo), byref(hi)) < 0:
+            raise _lib.LassError(f"lass_ragged_bucket: L = {L} is not longer than the reflect padding ({self.n_fft // 2})")
+        return lo.value, hi.value
+
+    def _ragged_lengths(self, lengths, B: int, L: int, checked: bool, what: str) -> torch.Tensor:
+        """The lengths of a ragged call as a device int32 (B) tensor.  A Python sequence, numpy array or CPU tensor is checked
+        against the bucket of L here and uploaded; a device tensor is taken as it is, and only with `checked=True` - the
+        caller's word that it did the check (the library never reads the array; the kernels clamp)."""
+        if torch.is_tensor(lengths) and lengths.is_cuda:
+            if not checked:
+                raise _lib.LassError(f"{what}: device lengths cannot be checked without a copy to the host: pass host "
+                                     "lengths, or checked=True once you have checked them (Engine.ragged_bucket)")
+            if lengths.device != self.device or lengths.dtype != torch.int32 or lengths.shape != (B,) or not lengths.is_contiguous():
+                raise _lib.LassError(f"{what}: device lengths must be a contiguous int32 ({B},) tensor on {self.device}")
+            return lengths
+        host = np.asarray(lengths.numpy() if torch.is_tensor(lengths) else lengths)
+        if host.shape != (B,) or not np.issubdtype(host.dtype, np.integer):
+            raise _lib.LassError(f"{what}: lengths must be {B} integers")
+        lo, hi = self.ragged_bucket(L)
+        if host.min() < lo or host.max() > hi:
+            raise _lib.LassError(f"{what}: lengths {int(host.min())} .. {int(host.max())} leave the bucket [{lo}, {hi}] of rows "
+                                 f"of {L} samples: sort the clips into buckets first (lass_amd.ragged.plan_batches)")
+        return torch.from_numpy(host.astype(np.int32)).to(self.device)
+
+    def separate_ragged(self, mixture: torch.Tensor, lengths, condition: torch.Tensor, out: Optional[torch.Tensor] = None,
+                        checked: bool = False):
+        """Clips of different lengths in one call: mixture (B,L) f32 with clip b in mixture[b, :lengths[b]] (the rest of the
+        row is never read), condition (B,512) -> (B,L) f32 with out[b, :lengths[b]] what `separate` gives for the clip alone
+        and out[b, lengths[b]:] zero.  All lengths must lie in the bucket of L (`ragged_bucket`); see `_ragged_lengths` for
+        how they are checked."""
+        assert mixture.dim() == 2 and condition.dim() == 2 and condition.shape == (mixture.shape[0], arch_cond())
+        mixture = self._dev(mixture)
+        condition = self._dev(condition)
+        B, L = mixture.shape
+        lens = self._ragged_lengths(lengths, B, L, checked, "separate_ragged")
+        if out is None:
+            out = torch.empty_like(mixture)
+        elif (out.shape != mixture.shape or out.dtype != torch.float32 or out.device != self.device
+              or not out.is_contiguous()):
+            raise _lib.LassError(f"out must be a contiguous float32 {tuple(mixture.shape)} tensor on {self.device}")
+        ws = self._workspace(B, L)
+        rc = self.lib.lass_separate_ragged(self.ctx, _ptr(mixture), _ptr(lens), _ptr(condition), _ptr(out), B, L, _ptr(ws),
+                                           ws.numel(), _stream(self.device))
+        _lib.check(self.ctx, rc, "lass_separate_ragged")
+        return out
+
     def _dev(self, t: torch.Tensor) -> torch.Tensor:
         if t.device != self.device:
             raise _lib.LassError(f"tensor on {t.device}, engine on {self.device}")
@@ -229,6 +278,41 @@ class Engine:
                                      _stream(self.device))
         _lib.check(self.ctx, rc, "lass_front_end")
         return mag, cos, sin, x0
+
+    def front_end_ragged(self, wav: torch.Tensor, lengths, checked: bool = False):
+        """`front_end` with a length per clip (lass_front_end_ragged): same shapes as for B clips of L samples; beyond clip b's
+        own 1 + lengths[b] // 160 frames x0 and mag / cos / sin are zero."""
+        wav = self._dev(wav)
+        B, L = wav.shape
+        lens = self._ragged_lengths(lengths, B, L, checked, "front_end_ragged")
+        T = arch.frames_for(L)
+        nb = self.n_fft // 2 + 1
+        shape = (B, arch.padded_frames(T), nb - 1)
+        mk = lambda: torch.empty(B, T, nb, dtype=torch.float32, device=self.device)  # noqa: E731
+        mag, cos, sin = mk(), mk(), mk()
+        x0 = torch.empty((self.n_branches,) + shape if self.multistft else shape, dtype=torch.float32, device=self.device)
+        rc = self.lib.lass_front_end_ragged(self.ctx, _ptr(wav), _ptr(lens), B, L, _ptr(mag), _ptr(cos), _ptr(sin), _ptr(x0),
+                                            _stream(self.device))
+        _lib.check(self.ctx, rc, "lass_front_end_ragged")
+        return mag, cos, sin, x0
+
+    def istft_ragged(self, real: torch.Tensor, imag: torch.Tensor, lengths, length: int, n_fft: Optional[int] = None,
+                     win_length: Optional[int] = None, checked: bool = False):
+        """`istft_nfft` with a length per clip (lass_istft_ragged): real, imag (B, 1 + length // 160, n_fft/2+1) -> (B, length),
+        clip b from its own first 1 + lengths[b] // 160 frames, zero from lengths[b] on."""
+        real, imag = self._dev(real), self._dev(imag)
+        n_fft = self.n_fft if n_fft is None else int(n_fft)
+        win_length = n_fft if win_length is None else int(win_length)
+        B, T, F = real.shape
+        assert F == n_fft // 2 + 1 and imag.shape == real.shape
+        if n_fft != self.n_fft:
+            raise _lib.LassError("istft_ragged: the bucket is the context's (n_fft must be the engine's)")
+        lens = self._ragged_lengths(lengths, B, length, checked, "istft_ragged")
+        wav = torch.empty(B, length, dtype=torch.float32, device=self.device)
+        rc = self.lib.lass_istft_ragged(self.ctx, _ptr(real), _ptr(imag), _ptr(lens), B, T, length, n_fft, win_length, _ptr(wav),
+                                        _stream(self.device))
+        _lib.check(self.ctx, rc, "lass_istft_ragged")
+        return wav
 
     def stft_components(self, wav: torch.Tensor, n_fft: int, win_lengths, hop: int = arch.HOP):
         """(B,L) -> {win: (mag, cos, sin)} each (B,1,T,n_fft//2+1): `calculate_stft_components` at a COMMON n_fft for

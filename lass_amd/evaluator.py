@@ -23,6 +23,11 @@ definitions and the same printed line.  Differences are in execution only:
     device (`lass_decode_resample`, two launches per batch in front of `lass_mix_at_snr`).  Without it such a set is decoded and
     resampled on the host (`read_wav`: scipy in float64, ~10 ms per clip) and every batch takes the generic path.  The filter
     is the host's (lass_amd/resample.py), evaluated in float32; a set that is mono at the rate runs exactly as without the flag;
+  * (opt-in, `ragged=True`) a set whose clips DIFFER in length: the generic path below batches only consecutive clips of
+    identical length, so such a set runs as batch-1 launches.  With the flag it decodes a window of clips, sorts them into
+    32-frame buckets (lass_amd/ragged.py), stages each batch as zero-padded rows and separates it with one
+    `lass_separate_ragged` launch set; mixing and the SDR sums run on the padded rows unchanged (the padding adds exact zeros)
+    and the dB figures use each clip's own length.  Waveforms are bit-equal to the clip-by-clip run; rows come back in csv order;
   * under torch.distributed the clip list is block-sharded over ranks and the per-clip metric rows are all-gathered
     once at the end (RCCL when the backend is "nccl").
 """
@@ -41,6 +46,7 @@ from . import dist as ldist
 from . import resample as rs
 from .engine import get_engine
 from .metrics import stats_to_db
+from .ragged import plan_batches
 from .utils import load_ss_model, parse_yaml
 from .wavio import read_wav, read_wav_into, read_wav_raw_into, wav_frames, wav_info
 
@@ -122,7 +128,7 @@ class _Slot:
 class DCASEEvaluator:
     def __init__(self, sampling_rate=16000, eval_indexes="lass_synthetic_validation.csv", audio_dir="lass_validation",
                  batch_size: int = 16, device_mixing: bool = True, io_workers: int = 2, resident: bool = True,
-                 device_decode: bool = False) -> None:
+                 device_decode: bool = False, ragged: bool = False) -> None:
         r"""DCASE T9 LASS evaluator (dcase_evaluator.py:28-47)."""
         self.sampling_rate = sampling_rate
         with open(eval_indexes) as csv_file:
@@ -137,6 +143,9 @@ class DCASEEvaluator:
         self._embed_cache: Dict[str, torch.Tensor] = {}
         self.resident = resident
         self.device_decode = device_decode  # module docstring: decode / down-mix / resample on the device (resident path only)
+        self.ragged = ragged   # module docstring: bucketed batches of clips of different lengths (generic path only)
+        if ragged and not device_mixing:
+            raise ValueError("ragged=True mixes on the device (zero-padded rows): it needs device_mixing=True")
         self._slots = {}       # (B, L, device, file format) -> [two _Slot]: kept across calls, so later calls replay graphs from their first batch
         self.last_path = None  # "resident" / "generic": which data path the last call took (tests, bench)
         self.resident_batches = self.generic_batches = 0
@@ -324,6 +333,8 @@ class DCASEEvaluator:
     def _run_generic(self, pl_model, eng, device, items, decoded=None) -> List[np.ndarray]:
         """The generic data path: clips of any length, grouped into batches of consecutive equal-length clips, fresh device
         tensors per batch (eager launches).  `decoded`: already decoded (source, noise, snr, caption) tuples instead of csv rows."""
+        if self.ragged:
+            return self._run_ragged(pl_model, eng, device, items, decoded)
         rows: List[np.ndarray] = []
         loader = self._read_pair if self.device_mixing else self._load_clip
         if decoded is not None:
@@ -370,6 +381,49 @@ class DCASEEvaluator:
                 pending_stats.append((eng.sdr_stats(src, sep.contiguous()), eng.sdr_stats(src, mix), src.shape[1]))
             rows.extend(self._rows_from_stats(pending_stats))
         return rows
+
+
+    def _run_ragged(self, pl_model, eng, device, items, decoded=None) -> List[np.ndarray]:
+        """`ragged=True` (module docstring): windows of 4 batches' worth of clips, each planned into one-bucket batches."""
+        ss = pl_model.ss_model
+        if not hasattr(ss, "separate_ragged"):
+            raise TypeError("ragged=True needs a separator with separate_ragged (lass_amd.ResUNet30)")
+        loader = self._read_pair
+        if decoded is not None:
+            items, loader = decoded, (lambda t: t)
+        n = len(items)
+        n_fft = getattr(getattr(ss, "engine", None), "n_fft", 1024)
+        window = 4 * self.batch_size
+        order: List[int] = []
+        pending_stats = []
+        with torch.no_grad(), ThreadPoolExecutor(max_workers=self.io_workers) as pool:
+            stager = _Stager(device)
+            jobs = deque(pool.submit(loader, items[k]) for k in range(min(n, window)))
+            submitted = len(jobs)
+            for w0 in range(0, n, window):
+                clips = [jobs.popleft().result() for _ in range(min(window, n - w0))]
+                while submitted < min(n, w0 + 2 * window):  # the next window decodes while this one is on the GPU
+                    jobs.append(pool.submit(loader, items[submitted]))
+                    submitted += 1
+                lengths = [int(c[0].shape[0]) for c in clips]
+                if any(c[1].shape[0] != m for c, m in zip(clips, lengths)):
+                    raise ValueError("a source and its noise clip differ in length")
+                for idx, row in plan_batches(lengths, self.batch_size, n_fft):
+                    pad = lambda x: np.pad(x, (0, row - x.shape[0]))  # noqa: E731
+                    snr_col = [np.full(1, float(clips[i][2]), dtype=np.float32) for i in idx]
+                    src, noise, snr = stager.put([[pad(clips[i][0]) for i in idx], [pad(clips[i][1]) for i in idx], snr_col])
+                    mix = eng.mix_at_snr(src, noise, snr[:, 0])  # zero tails stay zero; the two means share their 1/row
+                    cond = self._conditions(pl_model, [clips[i][3] for i in idx], device)
+                    lens = np.asarray([lengths[i] for i in idx], dtype=np.int64)
+                    sep = ss.separate_ragged(mix, lens, cond)
+                    pending_stats.append((eng.sdr_stats(src, sep), eng.sdr_stats(src, mix), lens))
+                    order.extend(w0 + i for i in idx)
+        rows = self._rows_from_stats(pending_stats)
+        if not rows:
+            return rows
+        out = np.empty((n, 3))
+        out[np.asarray(order)] = np.concatenate(rows, axis=0)
+        return [out]
 
 
 def eval(evaluator, checkpoint_path, config_yaml="config/audiosep_base.yaml", device="cuda", query_encoder=None):

@@ -8,13 +8,13 @@ BatchNorm uses running statistics (dcase_evaluator.py:57).
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-from . import arch
+from . import arch, ragged
 from ._lib import LassError
 from .engine import Engine
 
@@ -145,6 +145,43 @@ class ResUNet30(nn.Module):
         if self.training:
             raise LassError("lass_amd.ResUNet30 is inference-only (call .eval()); training is out of scope")
         return self._ensure_engine().separate(mixture, condition, out)
+
+    @torch.no_grad()
+    def separate_ragged(self, mixture: torch.Tensor, lengths, condition: torch.Tensor, out: Optional[torch.Tensor] = None,
+                        checked: bool = False) -> torch.Tensor:
+        """Clips of different lengths of ONE 32-frame bucket in one call (Engine.separate_ragged): mixture (B,L) zero-padded
+        rows, lengths (B), condition (B,512) -> (B,L), row b the clip's own separation followed by zeros."""
+        if self.training:
+            raise LassError("lass_amd.ResUNet30 is inference-only (call .eval()); training is out of scope")
+        return self._ensure_engine().separate_ragged(mixture, lengths, condition, out, checked=checked)
+
+    @torch.no_grad()
+    def separate_list(self, waveforms: Sequence[torch.Tensor], conditions, max_batch: int = 16) -> List[torch.Tensor]:
+        """Separate clips of ANY lengths: waveforms = 1-D float32 tensors, conditions (N,512) (or N tensors of 512) ->
+        N 1-D tensors on the model's device, in input order, each of its clip's length and equal to separating that clip
+        alone.  The clips are sorted into 32-frame buckets (lass_amd.ragged.plan_batches); each batch of up to `max_batch`
+        clips of one bucket is staged as zero-padded rows and runs as one launch set."""
+        if self.training:
+            raise LassError("lass_amd.ResUNet30 is inference-only (call .eval()); training is out of scope")
+        eng = self._ensure_engine()
+        dev = eng.device
+        n = len(waveforms)
+        if any(w.dim() != 1 for w in waveforms):
+            raise ValueError("separate_list takes 1-D waveforms")
+        cond = conditions if torch.is_tensor(conditions) else torch.stack(list(conditions))
+        cond = cond.to(device=dev, dtype=torch.float32)
+        if cond.shape != (n, self.condition_size):
+            raise ValueError(f"conditions must be ({n}, {self.condition_size})")
+        lengths = [int(w.shape[0]) for w in waveforms]
+        results: List[Optional[torch.Tensor]] = [None] * n
+        for idx, row_length in ragged.plan_batches(lengths, max_batch, eng.n_fft):
+            mix = torch.zeros(len(idx), row_length, dtype=torch.float32, device=dev)
+            for r, i in enumerate(idx):
+                mix[r, :lengths[i]].copy_(waveforms[i], non_blocking=True)
+            sep = eng.separate_ragged(mix, [lengths[i] for i in idx], cond[idx].contiguous())
+            for r, i in enumerate(idx):
+                results[i] = sep[r, :lengths[i]]
+        return results
 
     @torch.no_grad()
     def forward(self, input_dict: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
