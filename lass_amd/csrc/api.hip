@@ -20,16 +20,6 @@
 
 namespace {
 
-struct EncSpec { const char* name; int cin, cout, dh, dw; };
-struct DecSpec { const char* name; int cin, cout, uh, uw; };
-// resunet.py:315-418
-const EncSpec kEnc[7] = {{"encoder_block1", 32, 32, 2, 2},   {"encoder_block2", 32, 64, 2, 2},
-                         {"encoder_block3", 64, 128, 2, 2},  {"encoder_block4", 128, 256, 2, 2},
-                         {"encoder_block5", 256, 384, 2, 2}, {"encoder_block6", 384, 384, 1, 2},
-                         {"conv_block7a", 384, 384, 1, 1}};
-const DecSpec kDec[6] = {{"decoder_block1", 384, 384, 1, 2}, {"decoder_block2", 384, 384, 2, 2},
-                         {"decoder_block3", 384, 256, 2, 2}, {"decoder_block4", 256, 128, 2, 2},
-                         {"decoder_block5", 128, 64, 2, 2},  {"decoder_block6", 64, 32, 2, 2}};
 constexpr float kBnEps = 1e-5f;
 constexpr int kMaxBranches = LASS_MAX_STFT_WINDOWS;
 
@@ -88,9 +78,7 @@ struct lass_ctx {
     int device = 0;
     std::string err;
     Geometry g;
-    EncSpec E[7];  // encoder table of THIS model: E[0] is one analysis branch's block; E[1].cin = 32 * nbr
-    DecSpec D[6];
-    int dec_cat[6] = {0};              // concat channels of decoder d = D[d].cout + skip channels
+    ModelTable m;  // encoder / decoder table of THIS model (conv_route.h)
     std::string pre_name[kMaxBranches];  // "base.pre_conv" / "base.pre_convs.<win>"
     std::map<std::string, Raw> raw;
     bool finalized = false;
@@ -105,16 +93,10 @@ struct lass_ctx {
     void* up16[6] = {nullptr};       // bf16 transposed-conv weights (hi) per decoder, bf16 modes only
     void* up16l[6] = {nullptr};      // lo halves (LASS_COMPUTE_BF16X3)
     std::vector<void*> owned;        // derived device buffers to free
-    // profiling
-    int compute_mode = LASS_COMPUTE_F32;
-    int wino4_mincin = 32;     // 3x3 convs with at least that many input channels (and >= 32-wide images) run as Winograd
-                               // F(4x4,3x3) (wino4.hip); LASS_WINO4=<min Cin>, 0 = off (F(2x2,3x3) everywhere)
-    int ksplit_force = 0;      // lass_set_wino4_splits: 0 = the route's split-K factor on the 32 x 16 Winograd blocks (kWino4Splits), else 1 / 2 / 4
-    int vprep_mode = 1;        // lass_set_wino4_vprep: 0 = every F(4x4,3x3) launch transforms its own input, 1 = the layers of
-                               // kVprepMinCoutGroups read it from a prep launch's image, 2 = every layer whose kind admits it (tests, A/B)
-    bool head_fold = true;     // lass_set_head_fold / LASS_HEAD_FOLD: lass_separate's fused output head runs on the composed images
-    bool head_sc_fold = true;  // lass_set_head_sc_fold / LASS_HEAD_SC_FOLD: ... and reads its shortcut's logits as planes that
-                               // encoder_block1.conv2 and decoder_block6's transposed conv write (conv_route.h: plan_head_sc_fold)
+    // the compute mode (lass_finalize) and every switch a route depends on, as the value conv_route.h's rules read: LASS_WINO4,
+    // lass_set_wino4_splits, lass_set_wino4_vprep / LASS_WINO4_VPREP, lass_set_head_fold / LASS_HEAD_FOLD, lass_set_head_sc_fold /
+    // LASS_HEAD_SC_FOLD, LASS_FUSE_CATB / _BLOCK / _UP
+    RouteCfg cfg;
     float *hs_wt = nullptr, *hs_wskip = nullptr;  // head_fold.h: Wt' [cin][64] for that transposed conv, Wsc'_skip [3][32] (lass_finalize)
     float* stage_v = nullptr;      // ... their V image in the stage calls, grown on demand like stage_part (Plan::vprep in lass_separate)
     size_t stage_v_floats = 0;
@@ -122,10 +104,7 @@ struct lass_ctx {
     size_t stage_v_user_floats = 0;
     float* stage_part = nullptr;   // split-K partials of the stage calls (lass_convblock, lass_encoder_block), grown on demand;
     size_t stage_part_floats = 0;  // lass_separate takes its own from the caller's workspace (Plan::kpart)
-    bool fuse_catb = true;  // bf16 mode: decoder concats as blocked bf16 copies (LASS_FUSE_CATB=0: f32 concat)
-    bool fuse_block = true;  // bf16 mode: encoder_block1 as one kernel, intermediate in LDS (LASS_FUSE_BLOCK=0: two launches)
-    bool fuse_up = true;    // bf16 mode: decoder_block6's transposed conv inside its fused kernel (LASS_FUSE_UP=0: its own launch)
-    void* up_sc16 = nullptr;  // ... the 1x1 shortcut composed with that transposed conv, bf16 [4][2][128] units (lass_finalize)
+    void* up_sc16 = nullptr;  // bf16 mode: decoder_block6's 1x1 shortcut composed with its transposed conv, bf16 [4][2][128] units (lass_finalize)
     // hipGraph replay of lass_separate (LASS_GRAPH=0 disables): the ~40 launches of one (pointers, shape) combination are
     // captured once on an internal stream and replayed on the caller's stream
     bool use_graph = true;
@@ -238,9 +217,7 @@ void build_arch(lass_ctx* c) {
     c->n_shift = 0;
     c->enc.clear();
     c->dec.clear();
-    for (int i = 0; i < 7; ++i) c->E[i] = kEnc[i];
-    for (int i = 0; i < 6; ++i) c->D[i] = kDec[i];
-    c->E[1].cin = kPreCh * g.nbr;
+    c->m = model_table(g.variant == 0 ? 0 : g.nbr);
     for (int k = 0; k < g.nbr; ++k) {  // analysis branches
         ResBlock rb;
         std::string film;
@@ -261,7 +238,7 @@ void build_arch(lass_ctx* c) {
         c->enc.push_back(rb);
     }
     for (int i = 1; i < 7; ++i) {
-        const EncSpec& e = c->E[i];
+        const EncSpec& e = c->m.E[i];
         ResBlock rb;
         rb.prefix = std::string("base.") + e.name + ".conv_block1";
         rb.cin = e.cin;
@@ -272,13 +249,12 @@ void build_arch(lass_ctx* c) {
         c->enc.push_back(rb);
     }
     for (int i = 0; i < 6; ++i) {
-        const auto& d = c->D[i];
+        const auto& d = c->m.D[i];
         const int e = 5 - i;
-        c->dec_cat[i] = d.cout + c->E[e].cout * (e == 0 ? g.nbr : 1);  // torch.cat((x, skip), 1)
         c->dec_site[i] = add_site(c, std::string(d.name) + "->beta1", d.cin);
         ResBlock rb;
         rb.prefix = std::string("base.") + d.name + ".conv_block2";
-        rb.cin = c->dec_cat[i];
+        rb.cin = c->m.dec_cat[i];
         rb.cout = d.cout;
         rb.width = g.fcrop >> e;  // decoder i runs at its skip's level: 16, 32, ..., 512 bins
         rb.s1 = add_site(c, std::string(d.name) + "->conv_block2->beta1", rb.cin);
@@ -319,7 +295,7 @@ std::vector<int64_t> expected_shape(const lass_ctx* c, const std::string& name) 
     for (int i = 0; i < 6; ++i) {
         auto s = res_block(c->dec[i]);
         if (!s.empty()) return s;
-        const DecSpec& d = c->D[i];
+        const DecSpec& d = c->m.D[i];
         const std::string p = std::string("base.") + d.name;
         if (name == p + ".conv1.weight") return {d.cin, d.cout, d.uh, d.uw};
         if (starts_with(name, (p + ".bn1.").c_str()) && bn_field(name)) return {d.cin};
@@ -435,7 +411,7 @@ struct PreConv {
 
 // bf16 mode, decoder_block6: the transposed conv in front of the block runs inside the fused kernel (conv_bf16_fused.hip)
 struct UpFuse {
-    const void* x_act;   // previous decoder's output, that conv's prologue applied, blocked bf16 (B, cin/8, h, w, 8)
+    const void* xin;     // previous decoder's output, that conv's prologue applied, blocked bf16 (B, cin/8, h, w, 8)
     int cin, h, w;
     const void* w16;     // transposed-conv weights, bf16
     const void* wsc16;   // shortcut (up-sampled half) composed with the transposed conv, bf16
@@ -461,23 +437,22 @@ struct BlockFusions {
                                             // planes (Plan::sc_planes) - written by conv2's epilogue / read by the folded head
 };
 
-RouteCfg route_cfg(const lass_ctx* c) {
-    RouteCfg cfg;
-    cfg.f32 = c->compute_mode == LASS_COMPUTE_F32;
-    cfg.wino4_mincin = c->wino4_mincin; cfg.ksplit_force = c->ksplit_force; cfg.vprep_mode = c->vprep_mode;
-    cfg.head_fold = c->head_fold; cfg.head_sc_fold = c->head_sc_fold;
-    return cfg;
-}
-
-// The f32 route of one block call (conv_route.h holds the rule): the block, its images and what the call site fuses into it
-BlockRoute block_route(const lass_ctx* c, const ResBlock& rb, int B, int H, int W, const float* x, long x_bs, const BlockFusions& f) {
+// What one block call's site adds to the block's shape (conv_route.h holds the rules that read it)
+BlockIO block_io(const float* x, long x_bs, const BlockFusions& f) {
     BlockIO io;
     io.x0 = f.pre && f.pre->x0;
     io.head = f.head != nullptr;
     io.pool = f.pool_out != nullptr; io.pool_h = f.pool_h;
     io.x_aligned = x && ((uintptr_t)x & 15u) == 0 && x_bs % 4 == 0;
     io.sc_planes = f.planes != nullptr;
-    return plan_block(route_cfg(c), BlockShape{rb.cin, rb.cout, rb.width}, B, H, W, io);
+    io.cat_in = f.cat_in != nullptr; io.skip_out = f.skip_out != nullptr; io.pool_copies = f.pool_copies != nullptr;
+    io.act_out = f.act_out != nullptr; io.up_cin = f.up ? f.up->cin : 0;
+    return io;
+}
+
+// The f32 route of one block call: the block, its images and what the call site fuses into it
+BlockRoute block_route(const lass_ctx* c, const ResBlock& rb, int B, int H, int W, const float* x, long x_bs, const BlockFusions& f) {
+    return plan_block(c->cfg, BlockShape{rb.cin, rb.cout, rb.width}, B, H, W, block_io(x, x_bs, f));
 }
 
 // Do B clips of a_n floats, a_bs apart from a (a_bs = 0: one dense range), and the same of b share an element?
@@ -485,41 +460,34 @@ bool overlaps(int B, const float* a, long a_bs, size_t a_n, const float* b, long
     return a && b && a_n && b_n && a < b + (size_t)(B - 1) * b_bs + b_n && b < a + (size_t)(B - 1) * a_bs + a_n;
 }
 
-// The bf16 modes, a block their kernels take (bf1 of run_resblock): p / q = the filled conv1 / conv2 arguments
-int run_resblock_bf16(lass_ctx* c, const ResBlock& rb, const ConvArgs& p, const ConvArgs& q, int B, hipStream_t st, const BlockFusions& f) {
-    const bool x0 = f.pre && f.pre->x0;
-    const bool bf16_blocked = c->fuse_block && c->compute_mode == LASS_COMPUTE_BF16;
-    // encoder_block1 in the blocked-copy pipeline: the whole block as ONE kernel, its 32-channel intermediate kept in LDS
-    // (conv_bf16_fused.hip; LASS_FUSE_BLOCK=0 restores the two launches)
-    if (x0 && bf16_blocked && f.skip_out && rb.cin == rb.cout && lass_enc1_fused_bf16_supported(p, q)) {
+// The bf16 modes, a block their kernels take, in its planned form (conv_route.h: plan_bf16_block): p / q = the filled conv1 /
+// conv2 arguments.  As in launch_routed, the pointer-taking predicate of a fused kernel has the last word.
+int run_resblock_bf16(lass_ctx* c, const ResBlock& rb, Bf16Form form, const ConvArgs& p, const ConvArgs& q, int B, hipStream_t st,
+                      const BlockFusions& f) {
+    if (form == BF16_TWO) {
+        const bool x0 = f.pre && f.pre->x0;
+        {
+            ProfScope ps(c, st, P_CONV3X3);
+            HIP_TRY(c, lass_launch_conv_bf16(x0 ? CONV1_ACT_PRE : CONV1_ACT, p, st));
+        }
         ProfScope ps(c, st, P_CONV3X3);
-        HIP_TRY(c, lass_launch_enc1_fused_bf16(p, q, st));
+        HIP_TRY(c, lass_launch_conv_bf16(rb.cin != rb.cout ? CONV2_SHORTCUT : x0 ? CONV2_IDENT_PRE : CONV2_IDENT, q, st));
         return 0;
     }
-    // ... and decoder_block6's ConvBlockRes with the output head behind it (conv1 from the activated cat copy, the 1x1
-    // shortcut from the raw one)
-    const bool dec6 = !x0 && bf16_blocked && f.cat_in && f.head && rb.cin != rb.cout;
-    if (const UpFuse* up = f.up) {  // the caller has NOT run the transposed conv: only the kernel that contains it will do
-        ConvArgs uq;
-        uq.in_bf16 = up->x_act; uq.Cin = up->cin; uq.H = up->h; uq.W = up->w; uq.B = B;
+    // conv_bf16_fused.hip: encoder_block1 as ONE kernel, its 32-channel intermediate kept in LDS; decoder_block6 with the output
+    // head behind it (conv1 from the activated cat copy, the 1x1 shortcut from the raw one), behind its transposed conv's launch
+    // or - the caller has NOT run it - with that conv inside
+    ConvArgs uq;
+    if (const UpFuse* up = f.up) {
+        uq.in_bf16 = up->xin; uq.Cin = up->cin; uq.H = up->h; uq.W = up->w; uq.B = B;
         uq.w_bf16 = up->w16; uq.w2_bf16 = up->wsc16;
-        if (!(dec6 && lass_dec6u_fused_bf16_supported(p, q, uq)))
-            return fail(c, LASS_ERR_STATE, "decoder_block6 with its transposed conv inside needs the fused bf16 kernel");
-        ProfScope ps(c, st, P_CONV3X3);
-        HIP_TRY(c, lass_launch_dec6u_fused_bf16(p, q, uq, st));
-        return 0;
     }
-    if (dec6 && lass_dec6_fused_bf16_supported(p, q)) {
-        ProfScope ps(c, st, P_CONV3X3);
-        HIP_TRY(c, lass_launch_dec6_fused_bf16(p, q, st));
-        return 0;
-    }
-    {
-        ProfScope ps(c, st, P_CONV3X3);
-        HIP_TRY(c, lass_launch_conv_bf16(x0 ? CONV1_ACT_PRE : CONV1_ACT, p, st));
-    }
+    if (!(form == BF16_ENC1 ? lass_enc1_fused_bf16_supported(p, q) : form == BF16_DEC6 ? lass_dec6_fused_bf16_supported(p, q)
+                            : form == BF16_DEC6U && f.up && lass_dec6u_fused_bf16_supported(p, q, uq)))
+        return fail(c, LASS_ERR_STATE, rb.prefix + ": the launch arguments contradict the planned route");
     ProfScope ps(c, st, P_CONV3X3);
-    HIP_TRY(c, lass_launch_conv_bf16(rb.cin != rb.cout ? CONV2_SHORTCUT : x0 ? CONV2_IDENT_PRE : CONV2_IDENT, q, st));
+    HIP_TRY(c, form == BF16_ENC1 ? lass_launch_enc1_fused_bf16(p, q, st) : form == BF16_DEC6 ? lass_launch_dec6_fused_bf16(p, q, st)
+                                 : lass_launch_dec6u_fused_bf16(p, q, uq, st));
     return 0;
 }
 
@@ -581,19 +549,24 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
     }
     p.w_wino = rb.u1; p.w_wino4 = rb.u1f;
     p.w_bf16 = rb.b1; p.w_bf16_lo = rb.b1l;
-    // bf16 modes: both convs of a block run the bf16 kernels (they share shape and mode), or neither
-    const bool bf1 = c->compute_mode != LASS_COMPUTE_F32 && rb.b1 && rb.b2 && lass_bf16_supported(p) &&
-                     (!x0 || W % 32 == 0) && rb.cout % 16 == 0 && (rb.cin == rb.cout || (rb.bsc16 && rb.cin % 16 == 0));
+    // bf16 modes: the block's form, and which of the call site's hand-overs it admits (conv_route.h).  lass_separate planned
+    // them for producer and consumer at once; one that the block does not admit would have a launch read f32 storage as bf16
+    // units, or the reverse
+    const BlockIO io = block_io(x, x_bs, f);
+    const BlockShape shape{rb.cin, rb.cout, rb.width};
+    const Bf16Block bb = plan_bf16_block(c->cfg, shape, H, W, io);
+    if (bb.cat_in != io.cat_in || bb.skip_out != io.skip_out || bb.pool_copies != io.pool_copies || bb.act_out != io.act_out ||
+        (bb.form == BF16_DEC6U) != (io.up_cin != 0))
+        return fail(c, LASS_ERR_STATE, rb.prefix + ": the launch arguments contradict the planned route");
+    const bool bf1 = bb.form != BF16_NONE;
     // ... the intermediate a2 is then kept as blocked bf16 (hi, and lo for the split mode) in the same scratch
     void* a2_hi = a2;
-    void* a2_lo = c->compute_mode == LASS_COMPUTE_BF16X3 ? (void*)((char*)a2 + (size_t)B * rb.cout * HW * 2) : nullptr;
+    void* a2_lo = c->cfg.mode == MODE_BF16X3 ? (void*)((char*)a2 + (size_t)B * rb.cout * HW * 2) : nullptr;
     if (bf1) { p.out_bf16 = a2_hi; p.out_bf16_lo = a2_lo; }
-    if ((skip_out || cat_in) && (!bf1 || c->compute_mode != LASS_COMPUTE_BF16))
-        return fail(c, LASS_ERR_STATE, "blocked bf16 concat copies need the bf16 kernels");
     if (cat_in) p.in_bf16 = cat_in->act;
     // f32: the route of both convs and of the shortcut, decided once (conv_route.h); its workspace is checked here, in front of the
     // block's first launch
-    const BlockRoute rt = bf1 ? BlockRoute() : block_route(c, rb, B, H, W, x, x_bs, f);
+    const BlockRoute rt = bf1 ? BlockRoute() : plan_block(c->cfg, shape, B, H, W, io);
     const size_t xn = rb.cin * HW, on = rb.cout * HW;  // floats per clip of the input, and of the intermediate and the output
     if (rt.kpart_floats) {
         if (!f.kpart) return fail(c, LASS_ERR_STATE, "split-K needs its partial workspace");
@@ -634,8 +607,6 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
     if (bf1) { q.in_bf16 = a2_hi; q.in_bf16_lo = a2_lo; }
     if (cat_in) q.in2_bf16 = cat_in->raw;
     if (pool_copies) {  // bf16 mode: the pooled output as blocked bf16 copies for the next encoder block
-        if (!bf1 || c->compute_mode != LASS_COMPUTE_BF16 || !f.pool_out || f.pool_h != 2)
-            return fail(c, LASS_ERR_STATE, "blocked bf16 pooled copies need the bf16 kernels and the fused 2x2 pool");
         q.pool_out = nullptr;
         q.pool_bf16 = pool_copies->raw; q.pool_bf16_act = pool_copies->act;
         q.pool_oct0 = f.cofs / 8; q.pool_noct = pool_copies->noct;
@@ -644,7 +615,6 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
     if (const Site* act_out = f.act_out) {  // bf16 mode: the block output goes to the next transposed conv only - written as
                                             // ONE blocked bf16 tensor with that conv's BN+FiLM+leaky prologue already applied
                                             // (in `out`'s storage)
-        if (!bf1 || c->compute_mode != LASS_COMPUTE_BF16) return fail(c, LASS_ERR_STATE, "activated bf16 output needs the bf16 kernels");
         q.out_bf16 = out; q.out = nullptr; q.out_oct0 = 0; q.out_noct = 0;
         q.epi_scale = c->bn_scale + act_out->off; q.epi_shift = shift + act_out->off; q.epi_shift_bs = c->n_shift;
     }
@@ -663,12 +633,11 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
     } else {
         q.in2 = x; q.in2_bs = x_bs; q.Cin2 = rb.cin; q.w2 = rb.wsc; q.bias = rb.bsc;
     }
-    if (bf1) return run_resblock_bf16(c, rb, p, q, B, st, f);
+    if (bf1) return run_resblock_bf16(c, rb, bb.form, p, q, B, st, f);
     if (rt.conv2.head_fold) {  // the composed images in place of conv2's, the shortcut's and after_conv's (null: a state error below)
         q.w_wino4 = rb.u2h; q.w2 = rb.wsch; q.bias = rb.bh;
         q.mask_w = q.mask_b = nullptr;
     }
-    if (f.up) return fail(c, LASS_ERR_STATE, "decoder_block6 with its transposed conv inside needs the fused bf16 kernel");
     if (rt.shortcut_gemm) {
         // the GEMM writes bias + Wsc x into the block's output slot; conv2 then adds its result to that slot in place
         if (overlaps(B, out, out_bs, on, x, x_bs, xn) || overlaps(B, out, out_bs, on, a2, on, on))
@@ -689,7 +658,7 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
 
 int run_upconv(lass_ctx* c, int di, const float* x, int B, int h, int w, const float* shift, float* out, long out_bs,
                hipStream_t st, const CatCopies* cb = nullptr, bool x_is_act_bf16 = false, const HeadScPlanes* planes = nullptr) {
-    const DecSpec& d = c->D[di];
+    const DecSpec& d = c->m.D[di];
     const Site& s = c->sites[c->dec_site[di]];
     ConvArgs p;
     p.in = x; p.in_bs = (long)d.cin * h * w; p.Cin = d.cin;
@@ -698,31 +667,37 @@ int run_upconv(lass_ctx* c, int di, const float* x, int B, int h, int w, const f
     p.pro_scale = c->bn_scale + s.off; p.pro_shift = shift + s.off; p.pro_shift_bs = c->n_shift;
     p.out = out; p.out_bs = out_bs; p.B = B; p.H = h; p.W = w; p.up_h = d.uh;
     p.w_bf16 = c->up16[di]; p.w_bf16_lo = c->up16l[di];
-    if (x_is_act_bf16) {  // the producer already applied this conv's prologue and wrote blocked bf16
-        if (c->compute_mode != LASS_COMPUTE_BF16 || !p.w_bf16 || !lass_bf16_supported(p))
-            return fail(c, LASS_ERR_STATE, "activated bf16 input needs the bf16 kernels");
-        p.in_bf16 = x;
-    }
-    if (cb) {  // concat channels [0, C) as the two blocked copies instead of f32
-        if (c->compute_mode != LASS_COMPUTE_BF16 || !p.w_bf16 || !lass_bf16_supported(p))
-            return fail(c, LASS_ERR_STATE, "blocked bf16 concat copies need the bf16 kernels");
+    // the family, and which of the call site's hand-overs it admits (conv_route.h: plan_upconv)
+    UpSite site;
+    site.in_act = x_is_act_bf16; site.out_copies = cb != nullptr; site.logits = planes != nullptr;
+    site.aligned = p.in_bs % 4 == 0 && p.out_bs % 2 == 0 && ((uintptr_t)p.in & 15u) == 0 && ((uintptr_t)p.w & 15u) == 0 && ((uintptr_t)p.out & 7u) == 0;
+    const UpRoute rt = plan_upconv(c->cfg, d, h, w, site);
+    bool ok = rt.in_act == site.in_act && rt.out_copies == site.out_copies && (rt.family == UP_LOGITS) == site.logits;
+    if (rt.in_act) p.in_bf16 = x;  // the producer already applied this conv's prologue and wrote blocked bf16
+    if (rt.out_copies) {           // concat channels [0, C) as the two blocked copies instead of f32
         p.out = nullptr;
         p.out_bf16 = cb->raw; p.out_bf16_act = cb->act; p.out_oct0 = 0; p.out_noct = cb->noct;
         p.act_scale = cb->scale; p.act_shift = cb->shift; p.act_shift_bs = c->n_shift;
     }
+    if (ok && rt.family == UP_LOGITS) ok = lass_tconv_logits_supported(p, *planes);
+    if (ok && rt.family == UP_GEMM) ok = lass_pw_gemm_supported(TCONV_ACT, p);
+    if (!ok || rt.family == UP_INSIDE)
+        return fail(c, LASS_ERR_STATE, std::string(d.name) + " transposed conv: the launch arguments contradict the planned route");
     ProfScope ps(c, st, P_TCONV);
-    if (planes) {  // decoder_block6 of the head_sc_fold route: the launch also writes the head's shortcut logits of its output
-        if (c->compute_mode != LASS_COMPUTE_F32 || cb || x_is_act_bf16 || !lass_tconv_logits_supported(p, *planes))
-            return fail(c, LASS_ERR_STATE, std::string(d.name) + " transposed conv: the launch arguments contradict the planned route");
-        HIP_TRY(c, lass_launch_tconv_logits(p, *planes, st));
-        return 0;
+    switch (rt.family) {
+        case UP_LOGITS:  // decoder_block6 of the head_sc_fold route: the launch also writes the head's shortcut logits of its output
+            HIP_TRY(c, lass_launch_tconv_logits(p, *planes, st));
+            break;
+        case UP_BF16:
+            HIP_TRY(c, lass_launch_conv_bf16(TCONV_ACT, p, st));
+            break;
+        case UP_GEMM:
+            HIP_TRY(c, lass_launch_pw_gemm(TCONV_ACT, p, st));
+            break;
+        default:
+            HIP_TRY(c, lass_launch_conv(TCONV_ACT, p, st));
+            break;
     }
-    if (c->compute_mode != LASS_COMPUTE_F32 && p.w_bf16 && lass_bf16_supported(p))
-        HIP_TRY(c, lass_launch_conv_bf16(TCONV_ACT, p, st));
-    else if (c->compute_mode == LASS_COMPUTE_F32 && d.cin >= kTconvGemmMinCin && lass_pw_gemm_supported(TCONV_ACT, p))
-        HIP_TRY(c, lass_launch_pw_gemm(TCONV_ACT, p, st));  // K = cin, N = 4 cout: one GEMM, the prologue applied once per element
-    else
-        HIP_TRY(c, lass_launch_conv(TCONV_ACT, p, st));
     return 0;
 }
 
@@ -738,7 +713,8 @@ struct Plan {
     // encoder_block1.conv2 and one by decoder_block6's transposed conv (last in the plan: no other offset depends on the switch)
     bool sc_planes = false;
     size_t lg_skip = 0, lg_up = 0;
-    int eh[7], ew[7];  // encoder block spatial sizes
+    Levels lv;         // encoder block spatial sizes
+    SeparatePlan sp;   // the bf16 forms and hand-overs, the transposed convs' families (conv_route.h)
 };
 
 size_t bump(size_t& total, size_t floats) {
@@ -754,12 +730,12 @@ bool head_sc_planned(const lass_ctx* c, int B, int H, int W) {
     if (!c->hs_wt || !c->hs_wskip || c->enc.empty() || c->dec.size() < 6) return false;
     const ResBlock &e1 = c->enc[0], &d6 = c->dec[5];
     BlockIO eio, dio;
-    eio.x0 = true; eio.pool = true; eio.pool_h = c->E[0].dh;
+    eio.x0 = true; eio.pool = true; eio.pool_h = c->m.E[0].dh;
     dio.head = true;
     HeadScSite site;
-    site.windows = c->g.variant == 0 ? 0 : c->g.nbr; site.tconv_cin = c->D[5].cin; site.up_h = c->D[5].uh; site.up_w = c->D[5].uw;
-    return c->E[0].dh == 2 && c->E[0].dw == 2 &&
-           plan_head_sc_fold(route_cfg(c), BlockShape{e1.cin, e1.cout, e1.width}, eio, BlockShape{d6.cin, d6.cout, d6.width}, dio, site, B, H, W);
+    site.windows = c->g.variant == 0 ? 0 : c->g.nbr; site.tconv_cin = c->m.D[5].cin; site.up_h = c->m.D[5].uh; site.up_w = c->m.D[5].uw;
+    return c->m.E[0].dh == 2 && c->m.E[0].dw == 2 &&
+           plan_head_sc_fold(c->cfg, BlockShape{e1.cin, e1.cout, e1.width}, eio, BlockShape{d6.cin, d6.cout, d6.width}, dio, site, B, H, W);
 }
 
 // The conv kernels address one clip's tensors through 32-bit buffer descriptors and byte offsets, so the largest per-clip
@@ -773,7 +749,7 @@ int make_plan(const lass_ctx* c, int B, int L, Plan* pl) {
     pl->B = B; pl->L = L;
     pl->T = 1 + L / LASS_HOP;
     pl->Tp = (pl->T + 31) / 32 * 32;
-    const size_t clip_max = (size_t)c->dec_cat[5] * pl->Tp * g.fcrop * sizeof(float);
+    const size_t clip_max = (size_t)c->m.dec_cat[5] * pl->Tp * g.fcrop * sizeof(float);
     if (clip_max > 0xFFFF0000ull) return LASS_ERR_ARG;
     size_t& t = pl->total;
     t = 0;
@@ -781,21 +757,19 @@ int make_plan(const lass_ctx* c, int B, int L, Plan* pl) {
     pl->mag = bump(t, spec); pl->cosv = bump(t, spec); pl->sinv = bump(t, spec);
     for (int k = 0; k < g.nbr; ++k) pl->x0[k] = bump(t, (size_t)B * pl->Tp * g.fcrop);
     pl->shift = bump(t, (size_t)B * c->n_shift);
-    int h = pl->Tp, w = g.fcrop;
+    pl->lv = model_levels(c->m, pl->Tp);
     size_t a2max = 0;
     for (int i = 0; i < 7; ++i) {
-        pl->eh[i] = h; pl->ew[i] = w;
-        const size_t o = (size_t)B * c->E[i].cout * h * w;
+        const size_t o = (size_t)B * c->m.E[i].cout * pl->lv.eh[i] * pl->lv.ew[i];
         if (o > a2max) a2max = o;
-        h /= c->E[i].dh; w /= c->E[i].dw;
-        if (i < 6) pl->pool[i] = bump(t, (size_t)B * c->E[i].cout * (i == 0 ? g.nbr : 1) * h * w);
+        if (i < 6) pl->pool[i] = bump(t, (size_t)B * c->m.E[i].cout * (i == 0 ? g.nbr : 1) * pl->lv.eh[i + 1] * pl->lv.ew[i + 1]);
     }
-    pl->center = bump(t, (size_t)B * c->E[6].cout * pl->eh[6] * pl->ew[6]);
+    pl->center = bump(t, (size_t)B * c->m.E[6].cout * pl->lv.eh[6] * pl->lv.ew[6]);
     for (int d = 0; d < 6; ++d) {
         const int e = 5 - d;  // decoder d concatenates the skip of encoder e
-        const size_t hw = (size_t)pl->eh[e] * pl->ew[e];
-        pl->cat[d] = bump(t, (size_t)B * c->dec_cat[d] * hw);
-        pl->decout[d] = bump(t, (size_t)B * c->D[d].cout * hw);
+        const size_t hw = (size_t)pl->lv.eh[e] * pl->lv.ew[e];
+        pl->cat[d] = bump(t, (size_t)B * c->m.dec_cat[d] * hw);
+        pl->decout[d] = bump(t, (size_t)B * c->m.D[d].cout * hw);
     }
     pl->a2 = bump(t, a2max);
     pl->oreal = bump(t, spec); pl->oimag = bump(t, spec);
@@ -804,13 +778,13 @@ int make_plan(const lass_ctx* c, int B, int L, Plan* pl) {
     // every block with a route of its own (conv_route.h), at its level's image size and with what lass_separate fuses into it
     // (the workspace hands every block an aligned input)
     const auto block = [&](const ResBlock& rb, int e, const BlockIO& io) {
-        const BlockRoute rt = plan_block(route_cfg(c), BlockShape{rb.cin, rb.cout, rb.width}, B, pl->eh[e], pl->ew[e], io);
+        const BlockRoute rt = plan_block(c->cfg, BlockShape{rb.cin, rb.cout, rb.width}, B, pl->lv.eh[e], pl->lv.ew[e], io);
         kmax = std::max(kmax, rt.kpart_floats);
         vmax = std::max(vmax, rt.v_floats);
     };
     for (int i = 1; i < 7; ++i) {
         BlockIO io;
-        io.pool = i < 6; io.pool_h = c->E[i].dh;
+        io.pool = i < 6; io.pool_h = c->m.E[i].dh;
         block(trunk_block(c, i), i, io);
     }
     for (int d = 0; d < 6; ++d) {
@@ -822,10 +796,11 @@ int make_plan(const lass_ctx* c, int B, int L, Plan* pl) {
     if (kmax) pl->kpart = bump(t, kmax);
     pl->vprep_floats = vmax;
     if (vmax) pl->vprep = bump(t, vmax);
-    pl->sc_planes = head_sc_planned(c, B, pl->eh[0], pl->ew[0]);
+    pl->sc_planes = head_sc_planned(c, B, pl->lv.eh[0], pl->lv.ew[0]);
+    pl->sp = plan_separate(c->cfg, c->m, pl->lv, pl->sc_planes);
     if (pl->sc_planes) {
-        pl->lg_skip = bump(t, (size_t)B * 3 * pl->eh[0] * pl->ew[0]);
-        pl->lg_up = bump(t, (size_t)B * 3 * pl->eh[0] * pl->ew[0]);
+        pl->lg_skip = bump(t, (size_t)B * 3 * pl->lv.eh[0] * pl->lv.ew[0]);
+        pl->lg_up = bump(t, (size_t)B * 3 * pl->lv.eh[0] * pl->lv.ew[0]);
     }
     return 0;
 }
@@ -922,13 +897,13 @@ static int create_impl(lass_ctx** out, int device_id, const Geometry& geom) {
     lass_ctx* c = new lass_ctx();
     c->device = device_id;
     c->g = geom;
-    if (const char* e = getenv("LASS_FUSE_CATB")) c->fuse_catb = atoi(e) != 0;
-    if (const char* e = getenv("LASS_FUSE_BLOCK")) c->fuse_block = atoi(e) != 0;
-    if (const char* e = getenv("LASS_FUSE_UP")) c->fuse_up = atoi(e) != 0;
-    if (const char* e = getenv("LASS_WINO4")) c->wino4_mincin = atoi(e);
-    if (const char* e = getenv("LASS_WINO4_VPREP")) c->vprep_mode = std::max(0, std::min(2, atoi(e)));  // A/B: lass_set_wino4_vprep
-    if (const char* e = getenv("LASS_HEAD_FOLD")) c->head_fold = atoi(e) != 0;  // A/B: lass_set_head_fold
-    if (const char* e = getenv("LASS_HEAD_SC_FOLD")) c->head_sc_fold = atoi(e) != 0;  // A/B: lass_set_head_sc_fold
+    if (const char* e = getenv("LASS_FUSE_CATB")) c->cfg.fuse_catb = atoi(e) != 0;
+    if (const char* e = getenv("LASS_FUSE_BLOCK")) c->cfg.fuse_block = atoi(e) != 0;
+    if (const char* e = getenv("LASS_FUSE_UP")) c->cfg.fuse_up = atoi(e) != 0;
+    if (const char* e = getenv("LASS_WINO4")) c->cfg.wino4_mincin = atoi(e);
+    if (const char* e = getenv("LASS_WINO4_VPREP")) c->cfg.vprep_mode = std::max(0, std::min(2, atoi(e)));  // A/B: lass_set_wino4_vprep
+    if (const char* e = getenv("LASS_HEAD_FOLD")) c->cfg.head_fold = atoi(e) != 0;  // A/B: lass_set_head_fold
+    if (const char* e = getenv("LASS_HEAD_SC_FOLD")) c->cfg.head_sc_fold = atoi(e) != 0;  // A/B: lass_set_head_sc_fold
     if (const char* e = getenv("LASS_SPLIT")) c->split_batch = std::max(0, std::min(2, atoi(e)));
     if (const char* e = getenv("LASS_GRAPH")) c->use_graph = atoi(e) != 0;
     c->prof.resize(P_COUNT);
@@ -1043,7 +1018,7 @@ int lass_finalize(lass_ctx* c, int compute_mode) {
     if (compute_mode != LASS_COMPUTE_F32 && compute_mode != LASS_COMPUTE_BF16 && compute_mode != LASS_COMPUTE_BF16X3)
         return fail(c, LASS_ERR_ARG, "unsupported compute mode");
     c->last_split.clear();
-    c->compute_mode = compute_mode;
+    c->cfg.mode = (ComputeMode)compute_mode;
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipDeviceSynchronize());  // replays of graphs that hold the old derived buffers have drained
     drop_graphs(c);
@@ -1091,16 +1066,15 @@ int lass_finalize(lass_ctx* c, int compute_mode) {
         rb.u1 = rb.u2 = rb.usc = nullptr;
         rb.u1f = rb.u2f = nullptr;
         rb.b1 = rb.b2 = rb.bsc16 = rb.b1l = rb.b2l = rb.bscl = nullptr;
-        const bool bfm = c->compute_mode == LASS_COMPUTE_BF16 || c->compute_mode == LASS_COMPUTE_BF16X3;
-        const bool split = c->compute_mode == LASS_COMPUTE_BF16X3;
-        if (bfm && rb.cin % 16 == 0 && rb.cout % 16 == 0) {
+        const Bf16Weights wt = bf16_block_weights(c->cfg, rb.cin, rb.cout);  // the copies the bf16 plan counts on
+        if (wt.pair) {
             unsigned short *t1 = nullptr, *t2 = nullptr;
             if (dev_alloc(c, &t1, (size_t)rb.cout * rb.cin * 9) || dev_alloc(c, &t2, (size_t)rb.cout * rb.cout * 9))
                 return LASS_ERR_HIP;
             HIP_TRY(c, lass_launch_weights_bf16(w1, rb.cout, rb.cin, 9, t1, 0, 0, st));
             HIP_TRY(c, lass_launch_weights_bf16(w2, rb.cout, rb.cout, 9, t2, 0, 0, st));
             rb.b1 = t1; rb.b2 = t2;
-            if (split) {
+            if (wt.pair_lo) {
                 unsigned short *l1 = nullptr, *l2 = nullptr;
                 if (dev_alloc(c, &l1, (size_t)rb.cout * rb.cin * 9) || dev_alloc(c, &l2, (size_t)rb.cout * rb.cout * 9))
                     return LASS_ERR_HIP;
@@ -1109,12 +1083,12 @@ int lass_finalize(lass_ctx* c, int compute_mode) {
                 rb.b1l = l1; rb.b2l = l2;
             }
         }
-        if (c->compute_mode == LASS_COMPUTE_F32) {
+        if (c->cfg.f32()) {
             if (dev_alloc(c, &rb.u1, (size_t)16 * rb.cout * rb.cin) || dev_alloc(c, &rb.u2, (size_t)16 * rb.cout * rb.cout))
                 return LASS_ERR_HIP;
             HIP_TRY(c, lass_launch_wino_weights(w1, rb.cout, rb.cin, rb.u1, st));
             HIP_TRY(c, lass_launch_wino_weights(w2, rb.cout, rb.cout, rb.u2, st));
-            const Wino4Images im = wino4_images(route_cfg(c), rb.cin, rb.cout, rb.width);  // the routes plan_block can give the block
+            const Wino4Images im = wino4_images(c->cfg, rb.cin, rb.cout, rb.width);  // the routes plan_block can give the block
             if (im.u1f) {
                 if (dev_alloc(c, &rb.u1f, (size_t)36 * rb.cout * rb.cin)) return LASS_ERR_HIP;
                 HIP_TRY(c, lass_launch_wino4_weights(w1, rb.cout, rb.cin, rb.u1f, st));
@@ -1132,19 +1106,19 @@ int lass_finalize(lass_ctx* c, int compute_mode) {
             if (dev_alloc(c, &rb.wsc, (size_t)rb.cout * rb.cin)) return LASS_ERR_HIP;
             HIP_TRY(c, lass_launch_relayout_conv(ws, rb.cout, rb.cin, 1, rb.wsc, st));
             rb.bsc = bs;
-            if (bfm && rb.b1) {
+            if (wt.shortcut) {
                 unsigned short* t3 = nullptr;
                 if (dev_alloc(c, &t3, (size_t)rb.cout * rb.cin)) return LASS_ERR_HIP;
                 HIP_TRY(c, lass_launch_weights_bf16(ws, rb.cout, rb.cin, 1, t3, 0, 0, st));
                 rb.bsc16 = t3;
-                if (split) {
+                if (wt.shortcut_lo) {
                     unsigned short* l3 = nullptr;
                     if (dev_alloc(c, &l3, (size_t)rb.cout * rb.cin)) return LASS_ERR_HIP;
                     HIP_TRY(c, lass_launch_weights_bf16(ws, rb.cout, rb.cin, 1, l3, 1, 0, st));
                     rb.bscl = l3;
                 }
             }
-            if (c->compute_mode == LASS_COMPUTE_F32) {
+            if (c->cfg.f32()) {
                 if (dev_alloc(c, &rb.usc, (size_t)4 * rb.cout * rb.cin)) return LASS_ERR_HIP;
                 HIP_TRY(c, lass_launch_wino_shortcut_weights(ws, rb.cout, rb.cin, rb.usc, st));
             }
@@ -1154,17 +1128,17 @@ int lass_finalize(lass_ctx* c, int compute_mode) {
     for (auto& rb : c->enc) { int r = prep(rb); if (r) return r; }
     for (auto& rb : c->dec) { int r = prep(rb); if (r) return r; }
     for (int i = 0; i < 6; ++i) {
-        const auto& d = c->D[i];
+        const auto& d = c->m.D[i];
         const float* wu = need(std::string("base.") + d.name + ".conv1.weight");
         if (!wu) return LASS_ERR_STATE;
         c->up16[i] = c->up16l[i] = nullptr;
-        if (c->compute_mode != LASS_COMPUTE_F32 && d.cin % 16 == 0) {
+        if (bf16_tconv_weights(c->cfg, d)) {
             const int N = d.cout * d.uh * d.uw;
             unsigned short *t = nullptr, *l = nullptr;
             if (dev_alloc(c, &t, (size_t)N * d.cin)) return LASS_ERR_HIP;
             HIP_TRY(c, lass_launch_weights_bf16(wu, N, d.cin, 1, t, 0, 1, st));
             c->up16[i] = t;
-            if (c->compute_mode == LASS_COMPUTE_BF16X3) {
+            if (c->cfg.mode == MODE_BF16X3) {
                 if (dev_alloc(c, &l, (size_t)N * d.cin)) return LASS_ERR_HIP;
                 HIP_TRY(c, lass_launch_weights_bf16(wu, N, d.cin, 1, l, 1, 1, st));
                 c->up16l[i] = l;
@@ -1174,10 +1148,9 @@ int lass_finalize(lass_ctx* c, int compute_mode) {
     // decoder_block6's shortcut over the up-sampled half of its concat, composed with the transposed conv (dec6u_fused_bf16_kernel)
     c->up_sc16 = nullptr;
     {
-        const DecSpec& d = c->D[5];
+        const DecSpec& d = c->m.D[5];
         const ResBlock& rb = c->dec[5];
-        if (c->compute_mode == LASS_COMPUTE_BF16 && c->g.variant == 0 && d.cin == 64 && d.cout == 32 && d.uh == 2 && d.uw == 2 &&
-            rb.cin == 64 && rb.cout == 32 && c->up16[5]) {
+        if (bf16_up_sc_weights(c->cfg, c->m)) {
             const float* wu = need(std::string("base.") + d.name + ".conv1.weight");
             const float* ws = need(rb.prefix + ".shortcut.weight");
             if (!wu || !ws) return LASS_ERR_STATE;
@@ -1208,7 +1181,7 @@ int lass_finalize(lass_ctx* c, int compute_mode) {
             HIP_TRY(c, hipMemcpy(ba.data(), need("base.after_conv.bias"), ba.size() * sizeof(float), hipMemcpyDeviceToHost));
             // ... and the shortcut's two halves for the launches that produce its inputs (ResUNet30: the skip is ONE encoder_block1's
             // output): Wt' = Wsc'_up o Wt for the transposed conv, Wsc'_skip for encoder_block1.conv2's epilogue
-            const DecSpec& d6 = c->D[5];
+            const DecSpec& d6 = c->m.D[5];
             const auto up = c->raw.find(std::string("base.") + d6.name + ".conv1.weight");
             if (c->g.variant == 0 && c->g.nbr == 1 && Q == 3 && K == d6.cout + kPreCh && up != c->raw.end() && up->second.d &&
                 up->second.n == (size_t)d6.cin * d6.cout * d6.uh * d6.uw) {
@@ -1365,7 +1338,7 @@ int lass_encoder_block(lass_ctx* c, const char* name, const float* x, int B, int
     for (size_t bi = 0; bi < c->enc.size(); ++bi) {
         const ResBlock& rb = c->enc[bi];
         if (rb.prefix != std::string(name) + ".conv_block1") continue;
-        const EncSpec& e = c->E[bi < (size_t)c->g.nbr ? 0 : bi - c->g.nbr + 1];
+        const EncSpec& e = c->m.E[bi < (size_t)c->g.nbr ? 0 : bi - c->g.nbr + 1];
         const long HW = (long)H * W;
         const bool pooled = e.dw == 2;
         if (pooled && (!pool || W % 2 != 0)) return fail(c, LASS_ERR_ARG, "lass_encoder_block: pool output needed, W even");
@@ -1456,24 +1429,24 @@ int lass_workspace_tensor(const lass_ctx* c, int B, int L, const char* name_c, s
         if (name == (g.variant == 0 ? std::string("x0") : "x0." + std::to_string(g.wins[k])))
             return put(pl.x0[k], 1, pl.Tp, g.fcrop, (int64_t)pl.Tp * g.fcrop);
     for (int i = 0; i < 7; ++i) {
-        const EncSpec& e = c->E[i];
-        const int64_t H = pl.eh[i], W = pl.ew[i];
+        const EncSpec& e = c->m.E[i];
+        const int64_t H = pl.lv.eh[i], W = pl.lv.ew[i];
         const int64_t C = (int64_t)e.cout * (i == 0 ? g.nbr : 1);  // encoder_block1: all branches, channel-concatenated
         if (name == e.name) {
             if (i == 6) return put(pl.center, C, H, W, C * H * W);
             const int d = 5 - i;  // the skip lives in place behind the transposed-conv half of decoder d's concat
-            return put(pl.cat[d] + (size_t)c->D[d].cout * H * W * sizeof(float), C, H, W, (int64_t)c->dec_cat[d] * H * W);
+            return put(pl.cat[d] + (size_t)c->m.D[d].cout * H * W * sizeof(float), C, H, W, (int64_t)c->m.dec_cat[d] * H * W);
         }
         if (i < 6 && name == std::string(e.name) + ".pool")
             return put(pl.pool[i], C, H / e.dh, W / e.dw, C * (H / e.dh) * (W / e.dw));
     }
     // the head's shortcut logits of the head_sc_fold route (only where the plan has them)
-    if (pl.sc_planes && name == "head_sc.skip") return put(pl.lg_skip, 3, pl.eh[0], pl.ew[0], (int64_t)3 * pl.eh[0] * pl.ew[0]);
-    if (pl.sc_planes && name == "head_sc.up") return put(pl.lg_up, 3, pl.eh[0], pl.ew[0], (int64_t)3 * pl.eh[0] * pl.ew[0]);
+    if (pl.sc_planes && name == "head_sc.skip") return put(pl.lg_skip, 3, pl.lv.eh[0], pl.lv.ew[0], (int64_t)3 * pl.lv.eh[0] * pl.lv.ew[0]);
+    if (pl.sc_planes && name == "head_sc.up") return put(pl.lg_up, 3, pl.lv.eh[0], pl.lv.ew[0], (int64_t)3 * pl.lv.eh[0] * pl.lv.ew[0]);
     for (int d = 0; d < 6; ++d) {
-        const int64_t H = pl.eh[5 - d], W = pl.ew[5 - d], C = c->D[d].cout;
-        if (name == std::string(c->D[d].name) + ".up") return put(pl.cat[d], C, H, W, (int64_t)c->dec_cat[d] * H * W);
-        if (name == c->D[d].name) return put(pl.decout[d], C, H, W, C * H * W);
+        const int64_t H = pl.lv.eh[5 - d], W = pl.lv.ew[5 - d], C = c->m.D[d].cout;
+        if (name == std::string(c->m.D[d].name) + ".up") return put(pl.cat[d], C, H, W, (int64_t)c->m.dec_cat[d] * H * W);
+        if (name == c->m.D[d].name) return put(pl.decout[d], C, H, W, C * H * W);
     }
     return LASS_ERR_ARG;
 }
@@ -1484,8 +1457,8 @@ int lass_upconv(lass_ctx* c, const char* name, const float* x, int B, int h, int
     if (r) return r;
     if (!name || !x || !shift || !y) return fail(c, LASS_ERR_ARG, "lass_upconv: bad argument");
     for (int i = 0; i < 6; ++i)
-        if (std::string("base.") + c->D[i].name == name)
-            return run_upconv(c, i, x, B, h, w, shift, y, (long)c->D[i].cout * h * c->D[i].uh * w * c->D[i].uw,
+        if (std::string("base.") + c->m.D[i].name == name)
+            return run_upconv(c, i, x, B, h, w, shift, y, (long)c->m.D[i].cout * h * c->m.D[i].uh * w * c->m.D[i].uw,
                               (hipStream_t)stream);
     return fail(c, LASS_ERR_ARG, std::string("lass_upconv: unknown decoder '") + name + "'");
 }
@@ -1583,7 +1556,7 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
     Plan pl;
     if (make_plan(c, B, L, &pl))
         return fail(c, LASS_ERR_ARG, std::string(who) + ": need B >= 1 and " + std::to_string(g.nfft / 2) +
-                                         " < L, with decoder_block6's concat (" + std::to_string(c->dec_cat[5]) +
+                                         " < L, with decoder_block6's concat (" + std::to_string(c->m.dec_cat[5]) +
                                          " ch x frames x " + std::to_string(g.fcrop) +
                                          " bins, f32) below 4 GiB per clip (longer clips: ResUNet30.chunk_inference)");
     if (workspace_bytes < pl.total)
@@ -1637,31 +1610,25 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
     // Routes.  pre_conv (resunet.py:555) is never materialised: encoder_block1 forms it from x0 while staging.  Tp is a
     // multiple of 32, so every pooled level has even rows and F.avg_pool2d (resunet.py:197) rides in conv2's epilogue.
     // decoder_block6 runs at W = fcrop with 32 channels: after_conv + mask ride in its conv2's epilogue.
-    // bf16 mode: decoders 2-6 (2x2 up-sampling) take their concat as blocked bf16 copies written by the
-    // producers
+    // bf16 mode: which tensors travel as blocked bf16 copies, and which blocks run fused, is pl.sp (conv_route.h: plan_separate).
+    // Where decoders 2-6 take their concat that way the copies live in the concat's storage
+    const SeparatePlan& sp = pl.sp;
     CatCopies cb[6];
-    bool use_cb[6] = {false, false, false, false, false, false};
     for (int d = 1; d < 6; ++d) {
         const int e = 5 - d;
         const ResBlock& rd = c->dec[d];
-        const ResBlock& re = c->enc[nbr - 1 + e];
-        const long hw = (long)pl.eh[e] * pl.ew[e];
-        use_cb[d] = c->fuse_catb && c->compute_mode == LASS_COMPUTE_BF16 && c->D[d].uh == 2 && c->D[d].uw == 2 &&
-                    rd.cout % 16 == 0 && rd.b1 && rd.b2 && rd.bsc16 && c->up16[d] && re.b1 && re.b2;
+        const long hw = (long)pl.lv.eh[e] * pl.lv.ew[e];
         cb[d].act = F(pl.cat[d]);
         cb[d].raw = (char*)F(pl.cat[d]) + (size_t)B * rd.cin * hw * 2;
         cb[d].noct = rd.cin / 8;
         cb[d].scale = c->bn_scale + c->sites[rd.s1].off;
         cb[d].shift = shift + c->sites[rd.s1].off;
     }
-    // ... and encoder blocks 2-5 take their (pooled) input the same way, from the previous block's fused pool
+    // ... and encoder blocks 2-5 their (pooled) input, from the previous block's fused pool, in the pooled tensor's
     CatCopies pc[4];
-    bool use_pc[4] = {false, false, false, false};
     for (int i = 0; i < 4; ++i) {
         const ResBlock& nx = c->enc[nbr - 1 + i + 1];
-        const long hwo = (long)pl.eh[i + 1] * pl.ew[i + 1];
-        use_pc[i] = c->fuse_catb && c->compute_mode == LASS_COMPUTE_BF16 && c->E[i].dh == 2 && pl.ew[i] % 32 == 0 &&
-                    use_cb[5 - i] && use_cb[5 - (i + 1)] && nx.cin != nx.cout && nx.cin % 16 == 0 && nx.b1 && nx.b2 && nx.bsc16;
+        const long hwo = (long)pl.lv.eh[i + 1] * pl.lv.ew[i + 1];
         pc[i].act = F(pl.pool[i]);
         pc[i].raw = (char*)F(pl.pool[i]) + (size_t)B * nx.cin * hwo * 2;
         pc[i].noct = nx.cin / 8;
@@ -1671,9 +1638,9 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
     // ---- encoder (resunet.py:556-562; resunet_with_multistft.py:151-179) -----------------------------------------------
     const float* x = nullptr;
     for (int i = 0; i < 7; ++i) {
-        const int H = pl.eh[i], W = pl.ew[i];
+        const int H = pl.lv.eh[i], W = pl.lv.ew[i];
         const long HW = (long)H * W;
-        const EncSpec& e = c->E[i];
+        const EncSpec& e = c->m.E[i];
         const int nb = i == 0 ? nbr : 1;  // encoder_block1 runs once per analysis branch
         float* o = nullptr;
         long o_bs = 0;
@@ -1683,8 +1650,8 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
             f.cofs = k * e.cout;  // channel offset of this branch inside the concatenated skip / pool
             if (i < 6) {  // skip output lives behind the transposed-conv half of decoder (5-i)'s concat buffer
                 const int d = 5 - i;
-                o = F(pl.cat[d]) + (size_t)(c->D[d].cout + f.cofs) * HW;
-                o_bs = (long)c->dec_cat[d] * HW;
+                o = F(pl.cat[d]) + (size_t)(c->m.D[d].cout + f.cofs) * HW;
+                o_bs = (long)c->m.dec_cat[d] * HW;
                 const long Ho = H / e.dh, Wo = W / e.dw;
                 f.pool_out = F(pl.pool[i]) + (size_t)f.cofs * Ho * Wo;
                 f.pool_h = e.dh;
@@ -1699,9 +1666,9 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
                 f.pre = &pre;
                 if (pl.sc_planes) f.planes = &hs_skip;
             }
-            if (i < 5 && use_cb[5 - i]) f.skip_out = &cb[5 - i];
-            if (i >= 1 && i <= 4 && use_pc[i - 1]) f.cat_in = &pc[i - 1];
-            if (i < 4 && use_pc[i]) f.pool_copies = &pc[i];
+            if (sp.enc[i].skip_out) f.skip_out = &cb[5 - i];
+            if (sp.enc[i].cat_in) f.cat_in = &pc[i - 1];
+            if (sp.enc[i].pool_copies) f.pool_copies = &pc[i];
             scratch(f);
             r = run_resblock(c, rb, x, rb.cin * HW, B, H, W, shift, F(pl.a2), o, o_bs, st, f);
             if (r) return r;
@@ -1709,32 +1676,26 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
         x = i < 6 ? F(pl.pool[i]) : o;  // conv_block7a: downsample (1,1) is the identity (resunet.py:363-370)
     }
     // ---- decoder (resunet.py:563-568) -------------------------------------------------------------------------
-    bool x_act = false;  // x (input of the next transposed conv) is an activated blocked bf16 tensor
     for (int d = 0; d < 6; ++d) {
         const int e = 5 - d;
-        const int H = pl.eh[e], W = pl.ew[e];
+        const int H = pl.lv.eh[e], W = pl.lv.ew[e];
         const long HW = (long)H * W;
-        const int h = H / c->D[d].uh, w = W / c->D[d].uw;
+        const int h = H / c->m.D[d].uh, w = W / c->m.D[d].uw;
         const ResBlock& rb = c->dec[d];
         BlockFusions f;
         // decoder_block6 in the blocked bf16 pipeline: the transposed conv runs inside the block's fused kernel, its output
         // (half of the concat, at the full resolution) is never written
-        const UpFuse upf{x, c->D[d].cin, h, w, c->up16[d], c->up_sc16};
-        const bool fuse_up = d == 5 && c->fuse_up && c->fuse_block && use_cb[d] && x_act && c->up_sc16 &&
-                             c->compute_mode == LASS_COMPUTE_BF16 && rb.cout == 32 && rb.cin == 64 && W == g.fcrop && W % 32 == 0 &&
-                             H % 2 == 0 && (unsigned long long)H * W * 8ull < 0x10000000ull;
-        if (fuse_up) {
+        const UpFuse upf{x, c->m.D[d].cin, h, w, c->up16[d], c->up_sc16};
+        if (sp.up[d].family == UP_INSIDE) {
             f.up = &upf;
         } else {
-            r = run_upconv(c, d, x, B, h, w, shift, F(pl.cat[d]), rb.cin * HW, st, use_cb[d] ? &cb[d] : nullptr, x_act,
+            r = run_upconv(c, d, x, B, h, w, shift, F(pl.cat[d]), rb.cin * HW, st, sp.up[d].out_copies ? &cb[d] : nullptr, sp.up[d].in_act,
                            d == 5 && pl.sc_planes ? &hs_up : nullptr);
             if (r) return r;
         }
-        // this decoder's output feeds only the next transposed conv: hand it over activated, as blocked bf16
-        x_act = d < 5 && c->fuse_catb && c->compute_mode == LASS_COMPUTE_BF16 && rb.b1 && rb.b2 && rb.bsc16 &&
-                rb.cout % 16 == 0 && c->up16[d + 1];
-        if (x_act) f.act_out = &c->sites[c->dec_site[d + 1]];
-        if (use_cb[d]) f.cat_in = &cb[d];
+        // a decoder output that feeds only the next transposed conv is handed over activated, as blocked bf16
+        if (sp.dec[d].act_out) f.act_out = &c->sites[c->dec_site[d + 1]];
+        if (sp.dec[d].cat_in) f.cat_in = &cb[d];
         const MaskHead head{mag_m, cos_m, sin_m, F(pl.oreal), F(pl.oimag), T, g.nbins};
         if (d == 5) f.head = &head;
         if (d == 5 && pl.sc_planes) f.planes = &hs_head;
@@ -1902,28 +1863,28 @@ int lass_set_graph_replay(lass_ctx* c, int enabled) {
 
 int lass_set_wino4_splits(lass_ctx* c, int splits) {
     if (!c || (splits != 0 && splits != 1 && splits != 2 && splits != 4)) return fail(c, LASS_ERR_ARG, "lass_set_wino4_splits: 0, 1, 2 or 4");
-    c->ksplit_force = splits;
+    c->cfg.ksplit_force = splits;
     ++c->gen;  // captured graphs hold the launches of the previous choice (and workspace sizes follow it)
     return 0;
 }
 
 int lass_set_wino4_vprep(lass_ctx* c, int mode) {
     if (!c || mode < 0 || mode > 2) return fail(c, LASS_ERR_ARG, "lass_set_wino4_vprep: 0, 1 or 2");
-    c->vprep_mode = mode;
+    c->cfg.vprep_mode = mode;
     ++c->gen;  // as lass_set_wino4_splits: other launches, another workspace size
     return 0;
 }
 
 int lass_set_head_fold(lass_ctx* c, int enabled) {
     if (!c || (enabled != 0 && enabled != 1)) return fail(c, LASS_ERR_ARG, "lass_set_head_fold: 0 or 1");
-    c->head_fold = enabled != 0;
+    c->cfg.head_fold = enabled != 0;
     ++c->gen;  // captured graphs hold the launch of the previous choice
     return 0;
 }
 
 int lass_set_head_sc_fold(lass_ctx* c, int enabled) {
     if (!c || (enabled != 0 && enabled != 1)) return fail(c, LASS_ERR_ARG, "lass_set_head_sc_fold: 0 or 1");
-    c->head_sc_fold = enabled != 0;
+    c->cfg.head_sc_fold = enabled != 0;
     ++c->gen;  // as lass_set_wino4_splits: other launches, another workspace size
     return 0;
 }

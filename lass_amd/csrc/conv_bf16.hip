@@ -779,9 +779,7 @@ hipError_t launch_bf16(const ConvArgs& p, hipStream_t stream) {
 
 }  // namespace
 
-bool lass_bf16_supported(const ConvArgs& p) {
-    return (p.W == 8 || p.W == 16 || (p.W % 32) == 0) && p.Cin % 16 == 0 && p.N % 32 == 0;
-}
+bool lass_bf16_supported(const ConvArgs& p) { return lass_bf16_shape(p.Cin, p.N, p.W); }  // (the shape rule: conv_route.h)
 
 hipError_t lass_launch_conv_bf16(ConvKind kind, const ConvArgs& p, hipStream_t stream) {
     if (!lass_bf16_supported(p) || !p.w_bf16 || (!p.in && !p.in_bf16) || (!p.out && !p.out_bf16 && !p.mask_re))

@@ -27,7 +27,7 @@ __device__ __forceinline__ unsigned fused_tile_index() {
     return (gridDim.x & 7u) == 0 ? (lin & 7u) * (gridDim.x >> 3) + (lin >> 3) : lin;
 }
 
-constexpr int FPW = 32, FPHT = 8;                           // output tile: 8 rows x 32 columns, 4 waves x 2 rows
+constexpr int FPW = kBf16FusedTileW, FPHT = 8;                           // output tile: 8 rows x 32 columns, 4 waves x 2 rows
 constexpr int IRI = FPHT + 4, IPI = FPW + 4, NPI = IRI * IPI;  // input image (halo 2): 12 x 36 pixels
 constexpr int IRM = FPHT + 2, IPM = FPW + 2, NPM = IRM * IPM;  // conv1 output = conv2 input (halo 1): 10 x 34 pixels
 constexpr int NPPI = (NPI + NTHREADS - 1) / NTHREADS;          // input pixels per thread
@@ -775,11 +775,11 @@ __global__ __launch_bounds__(256) void compose_up_shortcut_kernel(const float* _
 
 }  // namespace
 
+// lass_*_fused_bf16_shape (conv_route.h) && the pointers are there
 bool lass_enc1_fused_bf16_supported(const ConvArgs& p, const ConvArgs& q) {
-    return p.Cin == 32 && p.N == 32 && p.Nw == 32 && q.Cin == 32 && q.N == 32 && q.Nw == 32 && p.W % FPW == 0 && p.W >= FPW &&
-           p.w_bf16 && q.w_bf16 && !p.w_bf16_lo && !q.w_bf16_lo && p.pre_w && p.pre_b && p.pro_scale && p.pro_shift && p.epi_scale &&
-           p.epi_shift && q.res && q.pre_w && q.pre_b && q.out_bf16 && !q.out_bf16_lo && q.out_noct > 0 && (!q.pool_out) &&
-           (!q.pool_bf16 || (q.pool_h == 2 && q.pool_bf16_act && q.H % 2 == 0)) && q.H == p.H && q.W == p.W && q.B == p.B;
+    return lass_enc1_fused_bf16_shape(lass_conv_shape(p), lass_conv_shape(q), q.pool_bf16 != nullptr) && p.w_bf16 && q.w_bf16 &&
+           !p.w_bf16_lo && !q.w_bf16_lo && p.pre_w && p.pre_b && p.pro_scale && p.pro_shift && p.epi_scale && p.epi_shift && q.res &&
+           q.pre_w && q.pre_b && q.out_bf16 && !q.out_bf16_lo && q.out_noct > 0 && (!q.pool_bf16 || q.pool_bf16_act) && q.B == p.B;
 }
 
 hipError_t lass_launch_enc1_fused_bf16(const ConvArgs& p, const ConvArgs& q, hipStream_t stream) {
@@ -790,11 +790,10 @@ hipError_t lass_launch_enc1_fused_bf16(const ConvArgs& p, const ConvArgs& q, hip
 }
 
 bool lass_dec6_fused_bf16_supported(const ConvArgs& p, const ConvArgs& q) {
-    return p.Cin == 64 && p.N == 32 && p.Nw == 32 && q.Cin == 32 && q.N == 32 && q.Nw == 32 && q.Cin2 == 64 && p.W % FPW == 0 &&
-           p.W >= FPW && p.in_bf16 && !p.in_bf16_lo && p.w_bf16 && q.w_bf16 && !p.w_bf16_lo && !q.w_bf16_lo && p.epi_scale &&
-           p.epi_shift && q.in2_bf16 && q.w2_bf16 && !q.w2_bf16_lo && q.bias && q.mask_re && q.mask_im && q.mask_w && q.mask_b &&
-           q.mask_mag && q.mask_cos && q.mask_sin && q.W + 1 == q.mask_nbins && q.mask_T > 0 && q.mask_T <= q.H && !q.pool_out &&
-           !q.pool_bf16 && q.H == p.H && q.W == p.W && q.B == p.B && (unsigned long long)p.H * p.W * 8ull < 0x10000000ull;
+    return lass_dec6_fused_bf16_shape(lass_conv_shape(p), lass_conv_shape(q)) && p.in_bf16 && !p.in_bf16_lo && p.w_bf16 && q.w_bf16 &&
+           !p.w_bf16_lo && !q.w_bf16_lo && p.epi_scale && p.epi_shift && q.in2_bf16 && q.w2_bf16 && !q.w2_bf16_lo && q.bias &&
+           q.mask_im && q.mask_w && q.mask_b && q.mask_mag && q.mask_cos && q.mask_sin && q.W + 1 == q.mask_nbins && q.mask_T > 0 &&
+           q.mask_T <= q.H && !q.pool_bf16 && q.B == p.B;
 }
 
 hipError_t lass_launch_dec6_fused_bf16(const ConvArgs& p, const ConvArgs& q, hipStream_t stream) {
@@ -805,8 +804,8 @@ hipError_t lass_launch_dec6_fused_bf16(const ConvArgs& p, const ConvArgs& q, hip
 }
 
 bool lass_dec6u_fused_bf16_supported(const ConvArgs& p, const ConvArgs& q, const ConvArgs& u) {
-    return lass_dec6_fused_bf16_supported(p, q) && p.pro_scale && p.pro_shift && u.in_bf16 && u.w_bf16 && u.w2_bf16 && u.Cin == 64 &&
-           u.H * 2 == p.H && u.W * 2 == p.W && u.B == p.B && p.H % 2 == 0 && (unsigned long long)u.H * u.W * 8ull < 0x10000000ull;
+    return lass_dec6_fused_bf16_supported(p, q) && lass_dec6u_fused_bf16_shape(lass_conv_shape(p), lass_conv_shape(q), u.Cin, u.H, u.W) &&
+           p.pro_scale && p.pro_shift && u.in_bf16 && u.w_bf16 && u.w2_bf16 && u.B == p.B;
 }
 
 hipError_t lass_launch_dec6u_fused_bf16(const ConvArgs& p, const ConvArgs& q, const ConvArgs& u, hipStream_t stream) {

@@ -1,8 +1,12 @@
-// conv_route.h - which kernel family runs the 3x3 convs of a residual block in f32, and the workspace that takes.  The ONE rule
-// behind the weight images of lass_finalize, the workspace plan, the launches of run_resblock (api.hip) and the shape halves of
-// the lass_*_supported predicates of wino.hip, wino4.hip and pw_gemm.hip.  Host only and free of HIP: any C++17 compiler builds
-// it.  tools/route_table.cpp prints the rule as a table; tests/test_wino4_routing_cpu.py holds lass_amd.arch.wino4_routed (the
-// Python mirror that bench.py's executed-FLOP accounting reads) against that table.
+// conv_route.h - which kernel family runs the 3x3 convs of a residual block in f32, and the workspace that takes; in the bf16
+// modes which blocks run the bf16 kernels, in which form (two launches or one fused kernel), and which tensors travel between
+// launches as blocked bf16 copies; in every mode the family of each transposed conv; and the model table with its level walk.
+// The ONE rule behind the weight images and bf16 copies of lass_finalize, the workspace plan, the launches of run_resblock and
+// run_upconv, the hand-overs of lass_separate (api.hip) and the shape halves of the lass_*_supported predicates of wino.hip,
+// wino4.hip, pw_gemm.hip, conv_bf16.hip and conv_bf16_fused.hip.  Host only and free of HIP: any C++17 compiler builds it.
+// tools/route_table.cpp prints the rule as a table; tests/test_wino4_routing_cpu.py holds lass_amd.arch.wino4_routed (the Python
+// mirror that bench.py's executed-FLOP accounting reads) against that table, tests/test_bf16_routing_cpu.py pins the bf16 plan
+// and tests/test_gpu_bf16_routes.py ties the printed launch counts to what a lass_separate runs.
 #pragma once
 #include <stddef.h>
 
@@ -18,6 +22,7 @@ constexpr int kWino4VFloats = kWino4NXI * 4 * 32 * 2;   // wino4.hip: floats of 
 constexpr int kHeadFoldRows = 16;                       // wino4.hip, folded output head: rows of the one MFMA tile the 3 logits are padded to
 constexpr int kPwGemmNB = 128;                          // pw_gemm.hip: couts of a workgroup
 constexpr int kPwGemmKC = 16;                           // pw_gemm.hip: k rows of a chunk
+constexpr int kBf16FusedTileW = 32;                     // conv_bf16_fused.hip: columns of an output tile
 
 // wino4.hip: images that tile only into 32-row x 16-column blocks (the 16-bin level of a clip whose frame count at that level
 // is a multiple of 32); the 8 x 64 / 16 x 32 blocks take every geometry they fit
@@ -102,6 +107,33 @@ inline bool lass_pw_gemm_tile_shape(const ConvShape& s) {
 inline bool lass_pw_gemm_shortcut_shape(const ConvShape& s) {
     return lass_pw_gemm_tile_shape(s) && s.Cin2 > 0 && s.Cin2 % (2 * kPwGemmKC) == 0;
 }
+// ... and the kernel == stride transposed conv (up_h x 2; K = Cin in pairs of chunks)
+inline bool lass_pw_gemm_tconv_shape(const ConvShape& s, int up_h) {
+    return lass_pw_gemm_tile_shape(s) && s.Cin > 0 && s.Cin % (2 * kPwGemmKC) == 0 && (up_h == 1 || up_h == 2) && s.N % (2 * up_h) == 0;
+}
+
+// conv_bf16.hip: 8 or 16 bins, or a multiple of 32; K in 16-channel chunks, 32-cout wave tiles
+inline bool lass_bf16_shape(int Cin, int N, int W) { return (W == 8 || W == 16 || (W % 32) == 0) && Cin % 16 == 0 && N % 32 == 0; }
+
+// conv_bf16_fused.hip addresses one clip's blocked tensors (8-channel octets of bf16) through byte offsets below 2^28
+inline bool lass_bf16_fused_addressable(int H, int W) { return (unsigned long long)H * W * 8ull < 0x10000000ull; }
+// ... encoder_block1 as one kernel: p = conv1 (CONV1_ACT_PRE), q = conv2 (CONV2_IDENT_PRE; q.pool: an f32 pooled output, which
+// the kernel does not write); pool_copies: the pooled output as the two blocked copies instead
+inline bool lass_enc1_fused_bf16_shape(const ConvShape& p, const ConvShape& q, bool pool_copies) {
+    return p.Cin == 32 && p.N == 32 && p.Nw == 32 && q.Cin == 32 && q.N == 32 && q.Nw == 32 && p.W % kBf16FusedTileW == 0 &&
+           p.W >= kBf16FusedTileW && !q.pool && (!pool_copies || (q.pool_h == 2 && q.H % 2 == 0)) && q.H == p.H && q.W == p.W;
+}
+// ... decoder_block6 with the output head: conv1 64 -> 32, conv2 + the 1x1 shortcut over 64 channels
+inline bool lass_dec6_fused_bf16_shape(const ConvShape& p, const ConvShape& q) {
+    return p.Cin == 64 && p.N == 32 && p.Nw == 32 && q.Cin == 32 && q.N == 32 && q.Nw == 32 && q.Cin2 == 64 &&
+           p.W % kBf16FusedTileW == 0 && p.W >= kBf16FusedTileW && q.head && !q.pool && q.H == p.H && q.W == p.W &&
+           lass_bf16_fused_addressable(p.H, p.W);
+}
+// ... with its 2 x 2 transposed conv inside: u_cin channels at u_h x u_w
+inline bool lass_dec6u_fused_bf16_shape(const ConvShape& p, const ConvShape& q, int u_cin, int u_h, int u_w) {
+    return lass_dec6_fused_bf16_shape(p, q) && u_cin == 64 && u_h * 2 == p.H && u_w * 2 == p.W && p.H % 2 == 0 &&
+           lass_bf16_fused_addressable(u_h, u_w);
+}
 
 // ---- the route of a block ----------------------------------------------------------------------------------------------------
 // f32, the 3x3 convs of a block whose images tile only into 32-row x 16-column F(4x4,3x3) blocks (lass_wino4_narrow: the 16-bin
@@ -129,14 +161,21 @@ constexpr int kVprepMinCoutGroups = 12;
 // per batch) is byte-bound and measured 7 % faster in the direct kernel
 constexpr int kTconvGemmMinCin = 128;
 
+enum ComputeMode { MODE_F32 = 0, MODE_BF16 = 1, MODE_BF16X3 = 2 };  // the values of LASS_COMPUTE_* (include/lass_hip.h)
+
 struct RouteCfg {
-    bool f32 = true;       // compute mode LASS_COMPUTE_F32.  The bf16 modes prepare no Winograd weights: a block their kernels
-                           // refuse runs the direct f32 kernels
+    ComputeMode mode = MODE_F32;  // the bf16 modes prepare no Winograd weights: a block their kernels refuse runs the direct f32 kernels
+    bool f32() const { return mode == MODE_F32; }
     int wino4_mincin = 32; // 3x3 convs with at least that many input channels run as F(4x4,3x3); 0 = off (F(2x2,3x3) everywhere)
     int ksplit_force = 0;  // 0 = kWino4Splits on the 32 x 16 blocks, else 1 / 2 / 4
     int vprep_mode = 1;    // V from memory: 0 = off, 1 = the layers of kVprepMinCoutGroups, 2 = every layer whose kind admits it
     bool head_fold = true; // the fused output head runs on weights composed with after_conv (3 logits instead of 32 channels)
     bool head_sc_fold = true;  // ... and takes its shortcut's logits as planes from the launches that produce its inputs
+    // bf16 mode (MODE_BF16 only: the hi+lo split of bf16x3 has no blocked hand-overs and no fused kernels)
+    bool fuse_catb = true;   // tensors between launches travel as blocked bf16 copies (LASS_FUSE_CATB)
+    bool fuse_block = true;  // encoder_block1 and decoder_block6 as one kernel each (LASS_FUSE_BLOCK)
+    bool fuse_up = true;     // decoder_block6's transposed conv inside that kernel (LASS_FUSE_UP; needs fuse_block)
+    bool blocked() const { return mode == MODE_BF16 && fuse_catb; }
 };
 
 struct BlockShape {
@@ -153,6 +192,14 @@ struct BlockIO {
     bool x_aligned = true;   // the block input meets pw_gemm.hip's 16-byte alignment (pointer, and batch stride % 4 floats)
     bool sc_planes = false;  // encoder_block1 / decoder_block6 of one lass_separate: the call site hands over (takes) the head's
                              // shortcut logits as planes - plan_head_sc_fold below has decided that for both ends at once
+    // bf16 mode, lass_separate only (plan_separate below decides them for producer and consumer at once): tensors the call site
+    // hands over as blocked bf16 copies instead of f32
+    bool cat_in = false;       // the input: two copies, one with conv1's prologue applied, one raw for the 1x1 shortcut
+    bool skip_out = false;     // an encoder's skip output: the same two copies inside the decoder's concat
+    bool pool_copies = false;  // the pooled output: the two copies that are the next encoder's cat_in
+    bool act_out = false;      // a decoder's output: ONE copy with the next transposed conv's prologue applied
+    int up_cin = 0;            // decoder_block6: the call site has NOT run the 2 x 2 transposed conv in front (up_cin channels at
+                               // H/2 x W/2) - only the kernel that contains it will do; 0: it has
 };
 
 // Which of a block's F(4x4,3x3) weight images lass_finalize prepares: u1f (conv1) / u2f (conv2).  conv1 at every level that can
@@ -165,7 +212,7 @@ struct Wino4Images {
 inline Wino4Images wino4_images(const RouteCfg& cfg, int cin, int cout, int width) {
     Wino4Images im;
     const int m = cfg.wino4_mincin;
-    if (!cfg.f32 || m <= 0 || cin % 8 != 0 || cout % 32 != 0) return im;
+    if (!cfg.f32() || m <= 0 || cin % 8 != 0 || cout % 32 != 0) return im;
     const bool level = width % 32 == 0, narrow = width % 32 == 16;
     im.u1f = (level || narrow) && cin >= m;
     im.u2f = cout >= m && (level ? cin != cout || cout == kPreCh : narrow && cin >= m);
@@ -202,7 +249,7 @@ inline BlockRoute plan_block(const RouteCfg& cfg, const BlockShape& b, int B, in
     const bool ident = b.cin == b.cout;
     r.conv1.kind = io.x0 ? CONV1_ACT_PRE : CONV1_ACT;  // (the direct kernels have no *_PRE kinds: they refuse them)
     r.conv2.kind = !ident ? CONV2_SHORTCUT : io.x0 ? CONV2_IDENT_PRE : CONV2_IDENT;
-    if (!cfg.f32) return r;
+    if (!cfg.f32()) return r;
     ConvShape s1, s2;
     s1.Cin = b.cin; s1.N = s1.Nw = b.cout; s1.H = H; s1.W = W;
     s2.Cin = s2.N = s2.Nw = b.cout; s2.H = H; s2.W = W;
@@ -280,9 +327,234 @@ struct HeadScSite {
 // enc1 / dec6: encoder_block1 and decoder_block6 with what lass_separate fuses into them, B, H, W: decoder_block6's image
 inline bool plan_head_sc_fold(const RouteCfg& cfg, const BlockShape& enc1, BlockIO enc1_io, const BlockShape& dec6, BlockIO dec6_io,
                               const HeadScSite& site, int B, int H, int W) {
-    if (!cfg.f32 || !cfg.head_fold || !cfg.head_sc_fold || site.windows != 0) return false;
+    if (!cfg.f32() || !cfg.head_fold || !cfg.head_sc_fold || site.windows != 0) return false;
     if (enc1.cout != kPreCh || dec6.cin != dec6.cout + enc1.cout) return false;  // cat = (up, skip): api.hip's concat order
     if (!lass_tconv_logits_shape(site.tconv_cin, dec6.cout, site.up_h, site.up_w, H / 2, W / 2)) return false;
     enc1_io.sc_planes = dec6_io.sc_planes = true;
     return plan_block(cfg, enc1, B, H, W, enc1_io).conv2.head_sc_fold && plan_block(cfg, dec6, B, H, W, dec6_io).conv2.head_sc_fold;
+}
+
+// ---- the model table ------------------------------------------------------------------------------------------------------------
+struct EncSpec { const char* name; int cin, cout, dh, dw; };  // a ConvBlockRes and the (dh, dw) avg-pool behind it
+struct DecSpec { const char* name; int cin, cout, uh, uw; };  // the (uh, uw) transposed conv of a decoder; its ConvBlockRes reads the concat
+// ResUNet30 (resunet.py:315-418)
+constexpr EncSpec kEnc[7] = {{"encoder_block1", 32, 32, 2, 2},   {"encoder_block2", 32, 64, 2, 2},   {"encoder_block3", 64, 128, 2, 2},
+                             {"encoder_block4", 128, 256, 2, 2}, {"encoder_block5", 256, 384, 2, 2}, {"encoder_block6", 384, 384, 1, 2},
+                             {"conv_block7a", 384, 384, 1, 1}};
+constexpr DecSpec kDec[6] = {{"decoder_block1", 384, 384, 1, 2}, {"decoder_block2", 384, 384, 2, 2}, {"decoder_block3", 384, 256, 2, 2},
+                             {"decoder_block4", 256, 128, 2, 2}, {"decoder_block5", 128, 64, 2, 2},  {"decoder_block6", 64, 32, 2, 2}};
+
+struct ModelTable {
+    EncSpec E[7];  // E[0] is ONE analysis branch's block (there are nbr of them); E[1].cin = 32 * nbr
+    DecSpec D[6];
+    int windows = 0;  // 0: ResUNet30; n: the multi-STFT model with n analysis windows
+    int nbr = 1;      // analysis branches
+    int fcrop = 512;  // bins of the full-resolution level
+    int dec_cat[6];   // concat channels of decoder d = D[d].cout + its skip's channels: torch.cat((x, skip), 1)
+    BlockShape enc_shape(int i) const { return BlockShape{E[i].cin, E[i].cout, fcrop >> i}; }  // behind i frequency halvings
+    BlockShape dec_shape(int d) const { return BlockShape{dec_cat[d], D[d].cout, fcrop >> (5 - d)}; }  // at its skip's level
+};
+inline ModelTable model_table(int windows) {
+    ModelTable m;
+    for (int i = 0; i < 7; ++i) m.E[i] = kEnc[i];
+    for (int d = 0; d < 6; ++d) m.D[d] = kDec[d];
+    m.windows = windows;
+    m.nbr = windows ? windows : 1;
+    m.fcrop = windows ? 1024 : 512;
+    m.E[1].cin = kPreCh * m.nbr;  // the branches' pools, channel-concatenated
+    for (int d = 0; d < 6; ++d) m.dec_cat[d] = m.D[d].cout + m.E[5 - d].cout * (d == 5 ? m.nbr : 1);
+    return m;
+}
+
+// The image of encoder level i at t_pad padded frames; decoder d runs at level 5 - d, its transposed conv reads (eh / uh, ew / uw)
+struct Levels {
+    int eh[7], ew[7];
+};
+inline Levels model_levels(const ModelTable& m, int t_pad) {
+    Levels lv;
+    int h = t_pad, w = m.fcrop;
+    for (int i = 0; i < 7; ++i) {
+        lv.eh[i] = h; lv.ew[i] = w;
+        h /= m.E[i].dh; w /= m.E[i].dw;
+    }
+    return lv;
+}
+
+// ---- the bf16 modes: weights, transposed convs, blocks --------------------------------------------------------------------------
+// Which bf16 copies lass_finalize prepares.  The plans below ask these functions, not the pointers: finalize allocates by
+// exactly this rule or fails.
+struct Bf16Weights {
+    bool pair = false, pair_lo = false;          // conv1 and conv2 (hi), and their lo halves (bf16x3)
+    bool shortcut = false, shortcut_lo = false;  // the 1x1 shortcut of a block that has one
+};
+inline Bf16Weights bf16_block_weights(const RouteCfg& cfg, int cin, int cout) {
+    Bf16Weights wt;
+    wt.pair = !cfg.f32() && cin % 16 == 0 && cout % 16 == 0;
+    wt.pair_lo = wt.pair && cfg.mode == MODE_BF16X3;
+    wt.shortcut = cin != cout && wt.pair;
+    wt.shortcut_lo = wt.shortcut && cfg.mode == MODE_BF16X3;
+    return wt;
+}
+// a decoder's transposed conv (hi; the lo half in bf16x3)
+inline bool bf16_tconv_weights(const RouteCfg& cfg, const DecSpec& d) { return !cfg.f32() && d.cin % 16 == 0; }
+// decoder_block6's 1x1 shortcut over the up-sampled half of its concat, composed with its transposed conv (dec6u_fused_bf16_kernel)
+inline bool bf16_up_sc_weights(const RouteCfg& cfg, const ModelTable& m) {
+    const DecSpec& d = m.D[5];
+    const BlockShape rb = m.dec_shape(5);
+    return cfg.mode == MODE_BF16 && m.windows == 0 && d.cin == 64 && d.cout == 32 && d.uh == 2 && d.uw == 2 && rb.cin == 64 &&
+           rb.cout == 32 && bf16_tconv_weights(cfg, d);
+}
+
+// The transposed conv of a decoder, every mode: h x w is its input image
+enum UpFamily {
+    UP_DIRECT = 0,  // conv.hip
+    UP_GEMM = 1,    // pw_gemm.hip (f32)
+    UP_BF16 = 2,    // conv_bf16.hip
+    UP_LOGITS = 3,  // tconv_logits.hip: f32, with the head's shortcut logits as one more cout block (plan_head_sc_fold)
+    UP_INSIDE = 4   // no launch: decoder_block6's fused bf16 kernel contains it (BF16_DEC6U)
+};
+struct UpSite {
+    bool in_act = false;      // bf16: the input arrives as ONE blocked copy with this conv's prologue applied (the producer's act_out)
+    bool out_copies = false;  // bf16: the output goes out as the concat's two blocked copies (the block's cat_in)
+    bool logits = false;      // f32: the call site takes the head's shortcut logits from this launch
+    bool aligned = true;      // input, weights and output meet pw_gemm.hip's alignment
+};
+struct UpRoute {
+    UpFamily family = UP_DIRECT;
+    bool in_act = false, out_copies = false;  // the site's, where the family admits them
+};
+inline UpRoute plan_upconv(const RouteCfg& cfg, const DecSpec& d, int h, int w, const UpSite& site = UpSite()) {
+    UpRoute r;
+    ConvShape s;
+    s.Cin = d.cin; s.N = s.Nw = d.cout * d.uh * d.uw; s.H = h; s.W = w;
+    if (site.logits && cfg.f32() && lass_tconv_logits_shape(d.cin, d.cout, d.uh, d.uw, h, w)) {
+        r.family = UP_LOGITS;
+    } else if (!cfg.f32() && bf16_tconv_weights(cfg, d) && lass_bf16_shape(s.Cin, s.N, w)) {
+        r.family = UP_BF16;
+        // (the blocked copies are written by the 2 x 2 kernels only)
+        r.in_act = site.in_act && cfg.blocked();
+        r.out_copies = site.out_copies && cfg.blocked() && d.uh == 2 && d.uw == 2;
+    } else if (cfg.f32() && d.cin >= kTconvGemmMinCin && site.aligned && lass_pw_gemm_tconv_shape(s, d.uh)) {
+        r.family = UP_GEMM;  // K = cin, N = 4 cout: one GEMM, the prologue applied once per element
+    }
+    return r;
+}
+
+// One block in the bf16 modes
+enum Bf16Form {
+    BF16_NONE = 0,  // the bf16 kernels do not take the block (or the mode is f32): plan_block's route, f32 hand-overs
+    BF16_TWO = 1,   // conv1 and conv2 as two launches of conv_bf16.hip, the intermediate as blocked bf16
+    BF16_ENC1 = 2,  // conv_bf16_fused.hip: encoder_block1 as one kernel, the intermediate in LDS
+    BF16_DEC6 = 3,  // ... decoder_block6 with the output head
+    BF16_DEC6U = 4  // ... and with its transposed conv inside
+};
+struct Bf16Block {
+    Bf16Form form = BF16_NONE;
+    bool cat_in = false, skip_out = false, pool_copies = false, act_out = false;  // BlockIO's, where the block admits them
+    int launches() const { return form == BF16_NONE || form == BF16_TWO ? 2 : 1; }
+};
+// both convs of a block run the bf16 kernels (they share shape and mode), or neither
+inline bool bf16_block_runs(const RouteCfg& cfg, const BlockShape& b, int W, bool x0) {
+    const Bf16Weights wt = bf16_block_weights(cfg, b.cin, b.cout);
+    return wt.pair && lass_bf16_shape(b.cin, b.cout, W) && (!x0 || W % 32 == 0) && (b.cin == b.cout || wt.shortcut);
+}
+inline Bf16Block plan_bf16_block(const RouteCfg& cfg, const BlockShape& b, int H, int W, const BlockIO& io) {
+    Bf16Block r;
+    if (!bf16_block_runs(cfg, b, W, io.x0)) return r;
+    r.form = BF16_TWO;
+    if (cfg.blocked()) {
+        r.cat_in = io.cat_in; r.skip_out = io.skip_out; r.act_out = io.act_out;
+        r.pool_copies = io.pool_copies && io.pool && io.pool_h == 2;  // written by the fused 2 x 2 pool only
+    }
+    if (cfg.mode != MODE_BF16 || !cfg.fuse_block) return r;
+    const bool ident = b.cin == b.cout;
+    ConvShape p, q;
+    p.Cin = b.cin; p.N = p.Nw = b.cout; p.H = H; p.W = W;
+    q.Cin = q.N = q.Nw = b.cout; q.H = H; q.W = W;
+    q.Cin2 = ident ? 0 : b.cin; q.pool = io.pool && !r.pool_copies; q.pool_h = io.pool_h; q.head = io.head;
+    if (io.x0) {  // in the blocked-copy pipeline only: the kernel writes its output as the skip's two copies
+        if (r.skip_out && ident && lass_enc1_fused_bf16_shape(p, q, r.pool_copies)) r.form = BF16_ENC1;
+    } else if (r.cat_in && io.head && !ident && W == b.width) {  // conv1 from the activated copy, the shortcut from the raw one
+        if (io.up_cin) {
+            if (lass_dec6u_fused_bf16_shape(p, q, io.up_cin, H / 2, W / 2)) r.form = BF16_DEC6U;
+        } else if (lass_dec6_fused_bf16_shape(p, q)) {
+            r.form = BF16_DEC6;
+        }
+    }
+    return r;
+}
+
+// One lass_separate: every block's form and every hand-over between two launches, decided for producer and consumer at once -
+// a consumer that read f32 storage as bf16 units, or the reverse, would read garbage.  enc[0] stands for all nbr branch blocks.
+// The stage calls (lass_convblock, lass_encoder_block, lass_upconv) have no hand-overs: plan_bf16_block and plan_upconv on a
+// default-constructed site.
+struct SeparatePlan {
+    Bf16Block enc[7], dec[6];
+    UpRoute up[6];
+    // P_CONV3X3 / P_TCONV profiler scopes of the run: one per launch (f32: the prep launch of a V image shares its conv's)
+    int conv_scopes = 0, tconv_scopes = 0;
+};
+// sc_planes: plan_head_sc_fold's decision (f32).  (The f32 scope count plans each block at B = 1: B only sizes its workspaces.)
+inline SeparatePlan plan_separate(const RouteCfg& cfg, const ModelTable& m, const Levels& lv, bool sc_planes) {
+    SeparatePlan sp;
+    const auto enc_runs = [&](int i) { return bf16_block_runs(cfg, m.enc_shape(i), lv.ew[i], i == 0); };
+    const auto dec_runs = [&](int d) { return bf16_block_runs(cfg, m.dec_shape(d), lv.ew[5 - d], false); };
+    const auto has_sc = [&](const BlockShape& b) { return b.cin != b.cout; };
+    const auto up = [&](int d, bool in_act, bool out_copies) {
+        UpSite site;
+        site.in_act = in_act; site.out_copies = out_copies; site.logits = d == 5 && sc_planes;
+        return plan_upconv(cfg, m.D[d], lv.eh[5 - d] / m.D[d].uh, lv.ew[5 - d] / m.D[d].uw, site);
+    };
+    for (int d = 0; d < 6; ++d) sp.up[d] = up(d, false, false);  // the family does not depend on the hand-overs
+    // decoders 2-6 (2 x 2 up-sampling) take their concat as the two blocked copies: half from the transposed conv, half from the
+    // encoder whose skip it is
+    bool cb[6] = {false, false, false, false, false, false};
+    for (int d = 1; d < 6; ++d)
+        cb[d] = cfg.blocked() && m.D[d].uh == 2 && m.D[d].uw == 2 && dec_runs(d) && has_sc(m.dec_shape(d)) &&
+                sp.up[d].family == UP_BF16 && enc_runs(5 - d);
+    // ... and encoder blocks 2-5 their input, from the previous block's fused 2 x 2 pool - both blocks are then in the pipeline
+    bool pc[4] = {false, false, false, false};
+    for (int i = 0; i < 4; ++i)
+        pc[i] = cfg.blocked() && m.E[i].dh == 2 && lv.ew[i] % 32 == 0 && cb[5 - i] && cb[4 - i] && has_sc(m.enc_shape(i + 1)) && enc_runs(i + 1);
+    for (int i = 0; i < 7; ++i) {
+        BlockIO io;
+        io.x0 = i == 0;
+        io.pool = i < 6; io.pool_h = m.E[i].dh;
+        io.skip_out = i < 5 && cb[5 - i];
+        io.cat_in = i >= 1 && i <= 4 && pc[i - 1];
+        io.pool_copies = i < 4 && pc[i];
+        sp.enc[i] = plan_bf16_block(cfg, m.enc_shape(i), lv.eh[i], lv.ew[i], io);
+    }
+    for (int d = 0; d < 6; ++d) {
+        const int e = 5 - d;
+        BlockIO io;
+        io.head = d == 5;
+        io.cat_in = cb[d];
+        // the output feeds only the next transposed conv: handed over activated
+        io.act_out = d < 5 && cfg.blocked() && dec_runs(d) && has_sc(m.dec_shape(d)) && sp.up[d + 1].family == UP_BF16;
+        sp.dec[d] = plan_bf16_block(cfg, m.dec_shape(d), lv.eh[e], lv.ew[e], io);
+        // decoder_block6: its transposed conv inside the fused kernel, if the kernel takes the block that way
+        if (d == 5 && cfg.fuse_up && cb[d] && sp.dec[4].act_out && bf16_up_sc_weights(cfg, m)) {
+            io.up_cin = m.D[d].cin;
+            const Bf16Block in = plan_bf16_block(cfg, m.dec_shape(d), lv.eh[e], lv.ew[e], io);
+            if (in.form == BF16_DEC6U) {
+                sp.dec[d] = in;
+                sp.up[d] = UpRoute{UP_INSIDE, true, false};
+            }
+        }
+        if (sp.up[d].family != UP_INSIDE) sp.up[d] = up(d, d > 0 && sp.dec[d - 1].act_out, sp.dec[d].cat_in);
+    }
+    for (int i = 0; i < 7; ++i) {
+        BlockIO io;  // (f32: the GEMM shortcuts are decided by shape, pool and head alone; lass_separate's inputs are aligned)
+        io.x0 = i == 0; io.pool = i < 6; io.pool_h = m.E[i].dh;
+        const int n = cfg.f32() ? 2 + plan_block(cfg, m.enc_shape(i), 1, lv.eh[i], lv.ew[i], io).shortcut_gemm : sp.enc[i].launches();
+        sp.conv_scopes += n * (i == 0 ? m.nbr : 1);
+    }
+    for (int d = 0; d < 6; ++d) {
+        BlockIO io;
+        io.head = d == 5;
+        sp.conv_scopes += cfg.f32() ? 2 + plan_block(cfg, m.dec_shape(d), 1, lv.eh[5 - d], lv.ew[5 - d], io).shortcut_gemm : sp.dec[d].launches();
+        sp.tconv_scopes += sp.up[d].family != UP_INSIDE;
+    }
+    return sp;
 }

@@ -1,12 +1,18 @@
-// route_table.cpp - the f32 conv routes of the model as lass_amd/csrc/conv_route.h decides them, one line per 3x3 conv and one per
-// block.  Host only: g++ -std=c++17 -I lass_amd/csrc tools/route_table.cpp -o tools/bin/route_table
+// route_table.cpp - the routes of one lass_separate as lass_amd/csrc/conv_route.h decides them: one line per 3x3 conv and one per
+// block (the f32 rule), one per transposed conv, in the bf16 modes one per block (form and hand-overs), and the profiler scopes.
+// Host only: g++ -std=c++17 -I lass_amd/csrc tools/route_table.cpp -o tools/bin/route_table
 // usage: route_table T_PAD [MIN_CIN=32] [VPREP_MODE=1] [FORCED_SPLITS=0] [X_ALIGNED=1] [STFT_WINDOWS=0] [B=1] [HEAD_FOLD=1] [HEAD=1]
-//                    [HEAD_SC_FOLD=1]
+//                    [HEAD_SC_FOLD=1] [MODE=0] [FUSE_CATB=1] [FUSE_BLOCK=1] [FUSE_UP=1]
+//   MODE 0: f32, 1: bf16, 2: bf16x3; FUSE_*: the LASS_FUSE_* switches of the bf16 mode.  With MODE given (any value) the up,
+//   bf16 and scopes lines follow the conv and block lines; without it the output is the conv and block lines alone.
 //   HEAD 1: decoder_block6 as lass_separate runs it, the output head in conv2's epilogue; 0: as the stage call runs it, without
 //   HEAD_SC_FOLD: the switch of the head_sc_fold route (plan_head_sc_fold); the route itself needs HEAD = 1 as well
 //   STFT_WINDOWS 0: ResUNet30 (512 bins); n > 0: the multi-STFT model with n analysis windows (1024 bins), rows named as
 //   lass_amd.arch.ms_conv_layer_table names them (encoder_block1s.<k> for window k).
 // conv <name> <direct|f2x2|f4x4|none> <kind> <splits> <v> fold=<0|1> scfold=<0|1>     block <name> shortcut=<gemm|fused|-> kpart=<floats> v=<floats>
+// up <decoder> <direct|gemm|bf16|tconv_logits|inside> in_act=<0|1> out_copies=<0|1>
+// bf16 <block> form=<f32|two|enc1|dec6|dec6u> cat_in=<0|1> skip_out=<0|1> pool_copies=<0|1> act_out=<0|1>      (MODE 1, 2)
+// scopes conv3x3=<n> tconv=<n>      the P_CONV3X3 / P_TCONV profiler scopes of the run (HEAD = 1: a lass_separate)
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -15,14 +21,9 @@
 
 namespace {
 
-struct Enc { const char* name; int cin, cout, dh, dw; };
-struct Dec { const char* name; int cout, uh, uw; };
-const Enc kEnc[7] = {{"encoder_block1", 32, 32, 2, 2},   {"encoder_block2", 32, 64, 2, 2},   {"encoder_block3", 64, 128, 2, 2},
-                     {"encoder_block4", 128, 256, 2, 2}, {"encoder_block5", 256, 384, 2, 2}, {"encoder_block6", 384, 384, 1, 2},
-                     {"conv_block7a", 384, 384, 1, 1}};
-const Dec kDec[6] = {{"decoder_block1", 384, 1, 2}, {"decoder_block2", 384, 2, 2}, {"decoder_block3", 256, 2, 2},
-                     {"decoder_block4", 128, 2, 2}, {"decoder_block5", 64, 2, 2},  {"decoder_block6", 32, 2, 2}};
 const char* kFamily[] = {"direct", "f2x2", "f4x4", "none"};
+const char* kUpFamily[] = {"direct", "gemm", "bf16", "tconv_logits", "inside"};
+const char* kForm[] = {"f32", "two", "enc1", "dec6", "dec6u"};
 const char* kKind[] = {"CONV1_ACT", "CONV2_IDENT", "CONV2_SHORTCUT", "TCONV_ACT", "CONV1_ACT_PRE", "CONV2_IDENT_PRE"};
 
 void print_block(const RouteCfg& cfg, const std::string& name, const BlockShape& b, int B, int H, int W, const BlockIO& io) {
@@ -35,12 +36,17 @@ void print_block(const RouteCfg& cfg, const std::string& name, const BlockShape&
            r.kpart_floats, r.v_floats);
 }
 
+void print_bf16(const std::string& name, const Bf16Block& b) {
+    printf("bf16 %s form=%s cat_in=%d skip_out=%d pool_copies=%d act_out=%d\n", name.c_str(), kForm[b.form], (int)b.cat_in, (int)b.skip_out,
+           (int)b.pool_copies, (int)b.act_out);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
     if (argc < 2) {
         fprintf(stderr, "usage: %s T_PAD [MIN_CIN=32] [VPREP_MODE=1] [FORCED_SPLITS=0] [X_ALIGNED=1] [STFT_WINDOWS=0] [B=1] [HEAD_FOLD=1] [HEAD=1] "
-                        "[HEAD_SC_FOLD=1]\n", argv[0]);
+                        "[HEAD_SC_FOLD=1] [MODE=0] [FUSE_CATB=1] [FUSE_BLOCK=1] [FUSE_UP=1]\n", argv[0]);
         return 2;
     }
     const auto arg = [&](int i, int dflt) { return argc > i ? atoi(argv[i]) : dflt; };
@@ -51,37 +57,37 @@ int main(int argc, char** argv) {
     cfg.ksplit_force = arg(4, 0);
     cfg.head_fold = arg(8, 1) != 0;
     cfg.head_sc_fold = arg(10, 1) != 0;
+    const int mode = arg(11, 0);
+    cfg.fuse_catb = arg(12, 1) != 0;
+    cfg.fuse_block = arg(13, 1) != 0;
+    cfg.fuse_up = arg(14, 1) != 0;
     const bool head = arg(9, 1) != 0;
     const bool aligned = arg(5, 1) != 0;
-    if (t_pad <= 0 || nwin < 0 || nwin > 4 || B <= 0) return 2;
-    const int nbr = nwin ? nwin : 1, fcrop = nwin ? 1024 : 512;
-    // the image of encoder level i, as the workspace plan walks it
-    int eh[7], ew[7], h = t_pad, w = fcrop;
-    for (int i = 0; i < 7; ++i) {
-        eh[i] = h; ew[i] = w;
-        h /= kEnc[i].dh; w /= kEnc[i].dw;
-    }
+    if (t_pad <= 0 || nwin < 0 || nwin > 4 || B <= 0 || mode < 0 || mode > 2) return 2;
+    cfg.mode = (ComputeMode)mode;
+    const ModelTable m = model_table(nwin);
+    const int nbr = m.nbr, fcrop = m.fcrop;
+    const Levels lv = model_levels(m, t_pad);
+    const int *eh = lv.eh, *ew = lv.ew;
     // the head's shortcut logits at their producers: one decision for encoder_block1 and decoder_block6 of a lass_separate (HEAD = 1)
     bool sc_planes = false;
     if (head) {
         BlockIO eio, dio;
-        eio.x0 = true; eio.pool = true; eio.pool_h = kEnc[0].dh; eio.x_aligned = aligned;
+        eio.x0 = true; eio.pool = true; eio.pool_h = m.E[0].dh; eio.x_aligned = aligned;
         dio.head = true; dio.x_aligned = aligned;
         HeadScSite site;
-        site.windows = nwin; site.tconv_cin = kDec[4].cout; site.up_h = kDec[5].uh; site.up_w = kDec[5].uw;
-        sc_planes = plan_head_sc_fold(cfg, BlockShape{kEnc[0].cin, kEnc[0].cout, fcrop}, eio,
-                                      BlockShape{kDec[5].cout + kEnc[0].cout * nbr, kDec[5].cout, fcrop}, dio, site, B, t_pad, fcrop);
+        site.windows = nwin; site.tconv_cin = m.D[5].cin; site.up_h = m.D[5].uh; site.up_w = m.D[5].uw;
+        sc_planes = plan_head_sc_fold(cfg, m.enc_shape(0), eio, m.dec_shape(5), dio, site, B, t_pad, fcrop);
     }
     for (int i = 0; i < 7; ++i)
         for (int k = 0; k < (i == 0 ? nbr : 1); ++k) {
             BlockIO io;
             io.x0 = i == 0;
-            io.pool = i < 6; io.pool_h = kEnc[i].dh;
+            io.pool = i < 6; io.pool_h = m.E[i].dh;
             io.x_aligned = aligned;
             io.sc_planes = i == 0 && sc_planes;
-            const int cin = i == 1 ? kPreCh * nbr : kEnc[i].cin;
-            const std::string name = i == 0 && nwin ? "encoder_block1s." + std::to_string(k) : kEnc[i].name;
-            print_block(cfg, name, BlockShape{cin, kEnc[i].cout, fcrop >> i}, B, eh[i], ew[i], io);
+            const std::string name = i == 0 && nwin ? "encoder_block1s." + std::to_string(k) : m.E[i].name;
+            print_block(cfg, name, m.enc_shape(i), B, eh[i], ew[i], io);
         }
     for (int d = 0; d < 6; ++d) {
         const int e = 5 - d;
@@ -89,8 +95,20 @@ int main(int argc, char** argv) {
         io.head = head && d == 5;
         io.x_aligned = aligned;
         io.sc_planes = d == 5 && sc_planes;
-        const int cat = kDec[d].cout + kEnc[e].cout * (e == 0 ? nbr : 1);  // torch.cat((x, skip), 1)
-        print_block(cfg, kDec[d].name, BlockShape{cat, kDec[d].cout, fcrop >> e}, B, eh[e], ew[e], io);
+        print_block(cfg, m.D[d].name, m.dec_shape(d), B, eh[e], ew[e], io);
     }
+    // The lines below come with the MODE argument only: a command line of up to ten arguments prints what it always printed.
+    if (argc <= 11) return 0;
+    // one lass_separate (the stage calls have no hand-overs and no fused forms)
+    const SeparatePlan sp = plan_separate(cfg, m, lv, sc_planes);
+    for (int d = 0; d < 6; ++d)
+        printf("up %s %s in_act=%d out_copies=%d\n", m.D[d].name, kUpFamily[sp.up[d].family], (int)sp.up[d].in_act, (int)sp.up[d].out_copies);
+    if (!cfg.f32()) {
+        for (int i = 0; i < 7; ++i)
+            for (int k = 0; k < (i == 0 ? nbr : 1); ++k)
+                print_bf16(i == 0 && nwin ? "encoder_block1s." + std::to_string(k) : m.E[i].name, sp.enc[i]);
+        for (int d = 0; d < 6; ++d) print_bf16(m.D[d].name, sp.dec[d]);
+    }
+    printf("scopes conv3x3=%d tconv=%d\n", sp.conv_scopes, sp.tconv_scopes);
     return 0;
 }
