@@ -141,6 +141,29 @@ int lass_separate_ragged(lass_ctx* ctx, const float* mixture, const int* lengths
  * on this context (*hi == L).  <0 for L <= n_fft/2.  Either output may be NULL. */
 int lass_ragged_bucket(const lass_ctx* ctx, int L, int* lo, int* hi);
 
+/* ---- long recordings: windows of one long row, stitched on the device --------------------------------------------- */
+
+/* lass_separate for B windows of ONE recording.  recording and out are rows of `total` floats; window b is the W-sample clip
+ * recording[s_b .. s_b + W) with s_b = starts[b], separated exactly as lass_separate separates that clip alone (reflect padding
+ * at the window's own two ends, as the reference does for its chunks).  Of its W output samples only lo_b <= n < hi_b are
+ * stored, at out[s_b + n], with (lo_b, hi_b) = (keep[2b], keep[2b+1]).  NO OTHER SAMPLE OF out IS TOUCHED: it keeps its previous
+ * value, so consecutive calls on the same `out` stitch a recording of any length in place.  A window with lo_b == hi_b stores
+ * nothing (planners pad a group of windows with such rows).
+ * starts: DEVICE int64 (B); keep: DEVICE int32 (2B).  The library never reads either array on the host; the kernels clamp
+ * instead - s_b into [0, total - W], lo_b into [0, W], hi_b into [lo_b, W] - so a wrong entry gives wrong audio and never an
+ * access out of range.  The kept ranges [s_b + lo_b, s_b + hi_b) of one call must be DISJOINT (the two half-batches store from
+ * two streams): the caller's duty.  recording and out must not overlap (LASS_ERR_ARG).
+ * f32: a kept sample is bit-identical to the gathered window's through lass_separate (any batch size, any position); the bf16
+ * modes: as lass_separate at the same B and row positions.
+ * Everything else is lass_separate's: both kinds of context, all compute modes, lass_workspace_bytes(B, W), the half-batch
+ * split (the second half reads starts + B/2 and keep + 2*(B/2), the same recording and out) and graph replay - the key includes
+ * the two POINTERS and total, their contents are read when the graph runs, so a caller that keeps its buffers rewrites the
+ * arrays between calls and every group of windows from the third on is one graph launch.
+ * LASS_ERR_ARG: a null pointer, B <= 0, W <= n_fft/2, total < W, overlapping recording / out. */
+int lass_separate_windows(lass_ctx* ctx, const float* recording, int64_t total, const int64_t* starts, const int* keep,
+                          const float* condition /* (B,512) */, float* out /* total floats */, int B, int W,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* Graph replay.  The third consecutive lass_separate call with the same pointers and shape is captured into a hipGraph
  * and replayed on the caller's stream from then on (one graph per context; a different combination is captured anew
  * after it, too, has been seen three times in a row).  Nothing else about the call changes; profiled
@@ -265,6 +288,17 @@ int lass_front_end_ragged(lass_ctx* ctx, const float* wav, const int* lengths, i
  * alone, wav[b][lengths[b] .. L) is 0. */
 int lass_istft_ragged(lass_ctx* ctx, const float* real, const float* imag, const int* lengths, int B, int T, int L, int n_fft,
                       int win_length, float* wav, void* stream);
+
+/* lass_front_end for the windows recording[starts[b] .. starts[b] + W) of one row of `total` floats (starts: DEVICE int64 (B),
+ * clamped as in lass_separate_windows): shapes as for B clips of W samples, row b what lass_front_end writes for the gathered
+ * window, bit for bit. */
+int lass_front_end_windows(lass_ctx* ctx, const float* recording, int64_t total, const int64_t* starts, int B, int W, float* mag,
+                           float* cos_out, float* sin_out, float* x0, void* stream);
+/* lass_istft_nfft for windows: real, imag (B,T,n_fft/2+1) with T = 1 + W/160 -> out (total floats).  Of window b only samples
+ * keep[2b] <= n < keep[2b+1] are stored, at out[starts[b] + n], each what lass_istft_nfft gives for a clip of W samples; the
+ * rest of `out` is not touched.  16-hop spans of a window that do not meet its kept range run no transform. */
+int lass_istft_windows(lass_ctx* ctx, const float* real, const float* imag, const int64_t* starts, const int* keep, int64_t total,
+                       int B, int T, int W, int n_fft, int win_length, float* out, void* stream);
 
 /* Where lass_separate(B, L) leaves a named intermediate inside the caller's workspace (f32 compute mode; in the bf16
  * modes several of these hold blocked bf16 data instead): byte offset, shape (B,C,H,W) and element strides.  Names:

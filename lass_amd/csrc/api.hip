@@ -111,11 +111,13 @@ struct lass_ctx {
     struct GraphKey {
         const void *mix = nullptr, *cond = nullptr, *out = nullptr, *ws = nullptr;
         const void* lens = nullptr;  // lass_separate_ragged's lengths (the pointer: its contents are read at replay time)
+        const void *starts = nullptr, *keep = nullptr;  // lass_separate_windows' index arrays (pointers, as `lens`)
+        int64_t total = 0;                              // ... and the length of its long rows
         int B = 0, L = 0;
         unsigned long gen = 0;
         bool operator==(const GraphKey& o) const {
-            return mix == o.mix && cond == o.cond && out == o.out && ws == o.ws && lens == o.lens && B == o.B && L == o.L &&
-                   gen == o.gen;
+            return mix == o.mix && cond == o.cond && out == o.out && ws == o.ws && lens == o.lens && starts == o.starts &&
+                   keep == o.keep && total == o.total && B == o.B && L == o.L && gen == o.gen;
         }
     };
     // A small cache of instantiated graphs: the evaluator alternates between its common batch and a ragged tail, long-form
@@ -866,7 +868,7 @@ const ResBlock* find_block(const lass_ctx* c, const std::string& prefix) {
 
 extern "C" {
 
-int lass_version(void) { return 10400; }  // 1.4.0: per-clip lengths (lass_separate_ragged & co); 1.3.0: CLAP text tower (lass_text_*, text.hip); 1.2.0: F(4x4,3x3) kernels, lass_set_graph_replay (1.1.0: multi-STFT model, fused iSTFT, graph replay)
+int lass_version(void) { return 10500; }  // 1.5.0: windows of one long row (lass_separate_windows & co); 1.4.0: per-clip lengths (lass_separate_ragged & co); 1.3.0: CLAP text tower (lass_text_*, text.hip); 1.2.0: F(4x4,3x3) kernels, lass_set_graph_replay (1.1.0: multi-STFT model, fused iSTFT, graph replay)
 
 const char* lass_last_error(const lass_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_err.c_str(); }
 
@@ -1403,6 +1405,36 @@ int lass_istft_ragged(lass_ctx* c, const float* real, const float* imag, const i
     return 0;
 }
 
+int lass_front_end_windows(lass_ctx* c, const float* recording, int64_t total, const int64_t* starts, int B, int W, float* mag,
+                           float* cos_out, float* sin_out, float* x0, void* stream) {
+    int r = check_ready(c);
+    if (r) return r;
+    const Geometry& g = c->g;
+    if (!recording || !starts || !x0 || B <= 0 || W <= g.nfft / 2 || total < W)
+        return fail(c, LASS_ERR_ARG, "lass_front_end_windows: bad argument (n_fft/2 < W <= total)");
+    const int T = 1 + W / LASS_HOP, Tp = (T + 31) / 32 * 32;
+    StftBranch br[kMaxBranches];
+    for (int k = 0; k < g.nbr; ++k) {  // as lass_front_end
+        br[k].wlen = g.wins[k];
+        br[k].x0 = x0 + (size_t)k * B * Tp * g.fcrop;
+        if (k == g.mask_br) { br[k].mag = mag; br[k].cosv = cos_out; br[k].sinv = sin_out; }
+    }
+    HIP_TRY(c, lass_launch_stft2_windows(recording, total, starts, B, W, g.nfft, LASS_HOP, T, Tp, g.nbr, br, g.magphase_sem, c->bn0_s,
+                                         c->bn0_h, c->tw2k, (hipStream_t)stream));
+    return 0;
+}
+
+int lass_istft_windows(lass_ctx* c, const float* real, const float* imag, const int64_t* starts, const int* keep, int64_t total,
+                       int B, int T, int W, int n_fft, int win_length, float* out, void* stream) {
+    if (!c || !real || !imag || !starts || !keep || !out || B <= 0 || (n_fft != 1024 && n_fft != 2048) || W <= n_fft / 2 ||
+        total < W || T != 1 + W / LASS_HOP || win_length < 32 || win_length > n_fft || (2048 % win_length) != 0)
+        return fail(c, LASS_ERR_ARG, "lass_istft_windows: bad argument (T = 1 + W/160 frames per window, n_fft/2 < W <= total)");
+    if (int r = use_device(c)) return r;
+    HIP_TRY(c, lass_launch_istft2_windows(real, imag, starts, keep, total, B, T, W, n_fft, win_length, LASS_HOP, c->tw2k, out,
+                                          (hipStream_t)stream));
+    return 0;
+}
+
 int lass_workspace_tensor(const lass_ctx* c, int B, int L, const char* name_c, size_t* offset, int64_t shape[4],
                           int64_t strides[4]) {
     if (!c || !name_c || !offset || !shape || !strides) return LASS_ERR_ARG;
@@ -1545,10 +1577,19 @@ struct Components {
     const float* sinv;
 };
 
+// lass_separate_windows: B windows of L samples of ONE row of `total` samples (`mixture`), their kept parts stored into one row of
+// `total` samples (`out`); see stft.hip
+struct WindowArgs {
+    const int64_t* starts;  // device (B)
+    const int* keep;        // device (2B)
+    int64_t total;
+};
+
 // lengths: nullptr, or one length per clip (device): the two ends of the network then run their per-clip-length forms
+// win: nullptr, or the window form: the two ends read and write windows of one long row (never together with lengths)
 static int separate_impl(lass_ctx* c, const float* mixture, const Components* comp, const float* condition, float* out,
                          int B, int L, void* workspace, size_t workspace_bytes, void* stream, const char* who,
-                         const int* lengths = nullptr) {
+                         const int* lengths = nullptr, const WindowArgs* win = nullptr) {
     int r = check_ready(c);
     if (r) return r;
     const Geometry& g = c->g;
@@ -1581,7 +1622,10 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
             br[k].x0 = F(pl.x0[k]);
             if (k == g.mask_br) { br[k].mag = F(pl.mag); br[k].cosv = F(pl.cosv); br[k].sinv = F(pl.sinv); }
         }
-        if (lengths)
+        if (win)
+            HIP_TRY(c, lass_launch_stft2_windows(mixture, win->total, win->starts, B, L, g.nfft, LASS_HOP, T, Tp, nbr, br,
+                                                 g.magphase_sem, c->bn0_s, c->bn0_h, c->tw2k, st));
+        else if (lengths)
             HIP_TRY(c, lass_launch_stft2_ragged(mixture, lengths, B, L, g.nfft, LASS_HOP, T, Tp, nbr, br, g.magphase_sem,
                                                 c->bn0_s, c->bn0_h, c->tw2k, st));
         else
@@ -1706,7 +1750,10 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
     }
     {
         ProfScope ps(c, st, P_ISTFT);
-        if (lengths)
+        if (win)
+            HIP_TRY(c, lass_launch_istft2_windows(F(pl.oreal), F(pl.oimag), win->starts, win->keep, win->total, B, T, L, g.nfft,
+                                                  g.wins[g.mask_br], LASS_HOP, c->tw2k, out, st));
+        else if (lengths)
             HIP_TRY(c, lass_launch_istft2_ragged(F(pl.oreal), F(pl.oimag), lengths, B, T, L, g.nfft, g.wins[g.mask_br], LASS_HOP,
                                                  c->tw2k, out, st));
         else
@@ -1718,12 +1765,13 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
 // lass_separate's launches, whole or as two overlapping half-batches (lass_ctx::split_batch).  Capture-safe: under stream
 // capture the event pair makes `s2` a parallel branch of the same graph.
 static int separate_any(lass_ctx* c, const float* mixture, const int* lengths, const float* condition, float* out, int B, int L,
-                        void* workspace, size_t workspace_bytes, hipStream_t stream, bool capturing, const char* who) {
+                        void* workspace, size_t workspace_bytes, hipStream_t stream, bool capturing, const char* who,
+                        const WindowArgs* win = nullptr) {
     Plan ph;
     if (!c->finalized || !split_halves(c, B) || !mixture || !condition || !out || !workspace || (!capturing && c->split_batch < 2) ||
         make_plan(c, B / 2, L, &ph) || 2 * ((ph.total + 255) / 256 * 256) > workspace_bytes) {
         c->last_split[{B, L}] = false;
-        return separate_impl(c, mixture, nullptr, condition, out, B, L, workspace, workspace_bytes, stream, who, lengths);
+        return separate_impl(c, mixture, nullptr, condition, out, B, L, workspace, workspace_bytes, stream, who, lengths, win);
     }
     c->last_split[{B, L}] = true;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1736,9 +1784,13 @@ static int separate_any(lass_ctx* c, const float* mixture, const int* lengths, c
     const size_t half_ws = (ph.total + 255) / 256 * 256;
     HIP_TRY(c, hipEventRecord(c->ev_fork, stream));
     HIP_TRY(c, hipStreamWaitEvent(c->s2, c->ev_fork, 0));
-    int r = separate_impl(c, mixture, nullptr, condition, out, h, L, workspace, half_ws, stream, who, lengths);
-    const int r2 = separate_impl(c, mixture + (size_t)h * L, nullptr, condition + (size_t)h * LASS_COND, out + (size_t)h * L, h, L,
-                                 (char*)workspace + half_ws, half_ws, c->s2, who, lengths ? lengths + h : nullptr);
+    // the window form's second half reads its own entries of the index arrays and the SAME two long rows
+    const WindowArgs win2 = win ? WindowArgs{win->starts + h, win->keep + 2 * h, win->total} : WindowArgs{};
+    const size_t row2 = win ? 0 : (size_t)h * L;
+    int r = separate_impl(c, mixture, nullptr, condition, out, h, L, workspace, half_ws, stream, who, lengths, win);
+    const int r2 = separate_impl(c, mixture + row2, nullptr, condition + (size_t)h * LASS_COND, out + row2, h, L,
+                                 (char*)workspace + half_ws, half_ws, c->s2, who, lengths ? lengths + h : nullptr,
+                                 win ? &win2 : nullptr);
     if (!r) r = r2;
     // the join is recorded even after a failure: a capturing stream must get its branch back
     HIP_TRY(c, hipEventRecord(c->ev_join, c->s2));
@@ -1746,9 +1798,10 @@ static int separate_any(lass_ctx* c, const float* mixture, const int* lengths, c
     return r;
 }
 
-// lass_separate (lengths == nullptr) and lass_separate_ragged: one call, eager or through the graph cache
+// lass_separate (lengths == nullptr), lass_separate_ragged and lass_separate_windows (win): one call, eager or through the graph
+// cache
 static int separate_call(lass_ctx* c, const float* mixture, const int* lengths, const float* condition, float* out, int B, int L,
-                         void* workspace, size_t workspace_bytes, void* stream, const char* who) {
+                         void* workspace, size_t workspace_bytes, void* stream, const char* who, const WindowArgs* win = nullptr) {
     if (!mixture) return fail(c, LASS_ERR_ARG, std::string(who) + ": null pointer");
     // Graph replay: the third call that presents the same (pointers, shape) key is captured once (on an internal stream; the
     // caller's may be the legacy default stream, which cannot be captured) and replayed from then on.  Callers that hand
@@ -1756,6 +1809,7 @@ static int separate_call(lass_ctx* c, const float* mixture, const int* lengths, 
     lass_ctx::GraphKey key;
     key.mix = mixture; key.cond = condition; key.out = out; key.ws = workspace; key.lens = lengths; key.B = B; key.L = L;
     key.gen = c->gen;
+    if (win) { key.starts = win->starts; key.keep = win->keep; key.total = win->total; }
     if (c->use_graph && !c->profiling && c->finalized) {
         ++c->g_tick;
         lass_ctx::GraphEntry* slot = nullptr;
@@ -1796,7 +1850,7 @@ static int separate_call(lass_ctx* c, const float* mixture, const int* lengths, 
                 Plan pl0;
                 if (!condition || !out || !workspace || make_plan(c, B, L, &pl0) || workspace_bytes < pl0.total ||
                     ((uintptr_t)workspace & 255) != 0)
-                    return separate_any(c, mixture, lengths, condition, out, B, L, workspace, workspace_bytes, (hipStream_t)stream, false, who);
+                    return separate_any(c, mixture, lengths, condition, out, B, L, workspace, workspace_bytes, (hipStream_t)stream, false, who, win);
                 slot->need = pl0.total;
                 if (split_halves(c, B)) {  // (checked again at capture time by separate_any: smaller workspaces run unsplit)
                     Plan ph0;
@@ -1808,7 +1862,7 @@ static int separate_call(lass_ctx* c, const float* mixture, const int* lengths, 
             if (!c->g_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->g_stream, hipStreamNonBlocking));
             bool ok = false;
             if (hipStreamBeginCapture(c->g_stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                const int r = separate_any(c, mixture, lengths, condition, out, B, L, workspace, workspace_bytes, c->g_stream, true, who);
+                const int r = separate_any(c, mixture, lengths, condition, out, B, L, workspace, workspace_bytes, c->g_stream, true, who, win);
                 hipGraph_t graph = nullptr;
                 const hipError_t e = hipStreamEndCapture(c->g_stream, &graph);  // always ends the capture, also after a failure
                 if (r == 0 && e == hipSuccess && graph && hipGraphInstantiate(&slot->exec, graph, nullptr, nullptr, 0) == hipSuccess) {
@@ -1831,7 +1885,7 @@ static int separate_call(lass_ctx* c, const float* mixture, const int* lengths, 
             c->err.clear();
         }
     }
-    return separate_any(c, mixture, lengths, condition, out, B, L, workspace, workspace_bytes, (hipStream_t)stream, false, who);
+    return separate_any(c, mixture, lengths, condition, out, B, L, workspace, workspace_bytes, (hipStream_t)stream, false, who, win);
 }
 
 int lass_separate(lass_ctx* c, const float* mixture, const float* condition, float* out, int B, int L, void* workspace,
@@ -1853,6 +1907,21 @@ int lass_separate_ragged(lass_ctx* c, const float* mixture, const int* lengths, 
     if (!c) return LASS_ERR_ARG;
     if (!lengths) return fail(c, LASS_ERR_ARG, "lass_separate_ragged: null lengths");
     return separate_call(c, mixture, lengths, condition, out, B, L, workspace, workspace_bytes, stream, "lass_separate_ragged");
+}
+
+int lass_separate_windows(lass_ctx* c, const float* recording, int64_t total, const int64_t* starts, const int* keep,
+                          const float* condition, float* out, int B, int W, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!c) return LASS_ERR_ARG;
+    const std::string who = "lass_separate_windows";
+    if (!recording || !starts || !keep || !condition || !out || !workspace) return fail(c, LASS_ERR_ARG, who + ": null pointer");
+    if (B <= 0) return fail(c, LASS_ERR_ARG, who + ": need B >= 1");
+    if (W <= c->g.nfft / 2)
+        return fail(c, LASS_ERR_ARG, who + ": a window must be longer than the reflect padding (W > " + std::to_string(c->g.nfft / 2) + ")");
+    if (total < W) return fail(c, LASS_ERR_ARG, who + ": the recording is shorter than one window (total < W)");
+    const uintptr_t r0 = (uintptr_t)recording, o0 = (uintptr_t)out, bytes = (uintptr_t)total * sizeof(float);
+    if (r0 < o0 + bytes && o0 < r0 + bytes) return fail(c, LASS_ERR_ARG, who + ": recording and out overlap");
+    const WindowArgs win{starts, keep, total};
+    return separate_call(c, recording, nullptr, condition, out, B, W, workspace, workspace_bytes, stream, who.c_str(), &win);
 }
 
 int lass_set_graph_replay(lass_ctx* c, int enabled) {

@@ -218,6 +218,15 @@ hipError_t lass_launch_stft2_ragged(const float* wav, const int* lengths, int B,
                                     const float2* tw2k, hipStream_t stream);
 hipError_t lass_launch_istft2_ragged(const float* real, const float* imag, const int* lengths, int B, int T, int L, int n_fft,
                                      int wlen, int hop, const float2* tw2k, float* wav, hipStream_t stream);
+// The same two kernels for windows of one long row (lass_separate_windows): window b is recording[starts[b], starts[b] + W) with
+// T = 1 + W / hop frames, and of its W output samples only keep[2b] <= n < keep[2b+1] are stored, at out[starts[b] + n].  starts:
+// device int64 (B), keep: device int32 (2B); the kernels clamp starts into [0, total - W], lo into [0, W], hi into [lo, W].
+hipError_t lass_launch_stft2_windows(const float* recording, int64_t total, const int64_t* starts, int B, int W, int n_fft, int hop,
+                                     int T, int Tpad, int nbr, const StftBranch* br, int magphase_sem, const float* s0,
+                                     const float* h0, const float2* tw2k, hipStream_t stream);
+hipError_t lass_launch_istft2_windows(const float* real, const float* imag, const int64_t* starts, const int* keep, int64_t total,
+                                      int B, int T, int W, int n_fft, int wlen, int hop, const float2* tw2k, float* out,
+                                      hipStream_t stream);
 
 // ---- misc.hip -----------------------------------------------------------------------------------------------------
 // film[b][j] = dot(cond[b], Wf[j]) + bf[j] (+ base[j] if base)   for j < n

@@ -498,6 +498,150 @@ __global__ __launch_bounds__(256) void istft2_ragged_kernel(const float* __restr
     }
 }
 
+// ---- windows of one long row (lass_separate_windows) -----------------------------------------------------------------
+// Long-form separation: window b of a call is recording[s_b, s_b + W), a clip that starts at an arbitrary offset of ONE long row
+// instead of at b * L, and of its W output samples only [lo_b, hi_b) are wanted, at the same offset of one long output row.  The
+// two kernels below are siblings of stft2_kernel and istft2_kernel that read s_b from `starts` (device, int64) and (lo_b, hi_b)
+// from `keep` (device, int32 pairs) and are otherwise the same arithmetic in the same order: a kept sample is bit-identical to
+// the gathered window run through lass_separate.  Entries are clamped - s_b into [0, total - W], lo_b into [0, W], hi_b into
+// [lo_b, W] - so a wrong entry gives wrong audio, never an access out of range.
+__device__ __forceinline__ int64_t window_start(const int64_t* __restrict__ starts, int b, int64_t total, int W) {
+    const int64_t v = starts[b], last = total - W;
+    return v < 0 ? 0 : (v > last ? last : v);
+}
+
+// stft2_kernel for the clip recording[s_b, s_b + W): reflect padding at the window's own two ends.
+template <int N, bool MAGPHASE>
+__global__ __launch_bounds__(256) void stft2_windows_kernel(const float* __restrict__ recording, int64_t total,
+                                                            const int64_t* __restrict__ starts, int W, int hop, int T, int Tpad,
+                                                            const float2* __restrict__ tw2k, Stft2Args a,
+                                                            const float* __restrict__ s0, const float* __restrict__ h0) {
+    __shared__ float2 A[N], Bf[N], TW[2048];
+    constexpr int NB = N / 2 + 1, FC = N / 2;
+    const int ta = 2 * blockIdx.x, b = blockIdx.y, z = blockIdx.z, tid = threadIdx.x;
+    const int L = W;
+    float* x0 = a.x0[z];
+    if (ta >= T) {  // rows T..Tpad-1 of the network input are zeros AFTER bn0
+        if (x0)
+            for (int r = 0; r < 2; ++r)
+                if (ta + r < Tpad)
+                    for (int f = tid; f < FC; f += 256) x0[((size_t)b * Tpad + ta + r) * FC + f] = 0.f;
+        return;
+    }
+    for (int i = tid; i < 2048; i += 256) TW[i] = tw2k[i];
+    __syncthreads();
+    const int wlen = a.wlen[z], woff = (N - wlen) / 2, wstride = 2048 / wlen;
+    const float* w = recording + window_start(starts, b, total, W);
+    const bool have_b = ta + 1 < T;
+    for (int idx = tid; idx < N; idx += 256) {
+        float2 v = make_float2(0.f, 0.f);
+        const int j = idx - woff;
+        if (j >= 0 && j < wlen) {
+            const float wn = 0.5f - 0.5f * TW[j * wstride].x;  // periodic Hann of wlen
+            int n = ta * hop + idx - N / 2;                     // centre=True, reflect padding of n_fft/2
+            int n2 = n + hop;
+            if (n < 0) n = -n;
+            if (n >= L) n = 2 * (L - 1) - n;
+            if (n2 < 0) n2 = -n2;
+            if (n2 >= L) n2 = 2 * (L - 1) - n2;
+            v = make_float2(w[n] * wn, have_b ? w[n2] * wn : 0.f);
+        }
+        A[idx] = v;
+    }
+    __syncthreads();
+    const float2* Z = fft_c<N, false>(A, Bf, TW, tid);
+    float *mag = a.mag[z], *cosv = a.cosv[z], *sinv = a.sinv[z], *real = a.real[z], *imag = a.imag[z];
+    for (int f = tid; f < NB; f += 256) {
+        const float2 z1 = Z[f], z2 = Z[(N - f) & (N - 1)];
+        const float re[2] = {0.5f * (z1.x + z2.x), 0.5f * (z1.y + z2.y)};
+        const float im[2] = {0.5f * (z1.y - z2.y), -0.5f * (z1.x - z2.x)};
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            if (r == 1 && !have_b) break;
+            const size_t row = ((size_t)b * T + ta + r) * NB + f;
+            float m, c, s;
+            if (MAGPHASE) {
+                m = sqrtf(re[r] * re[r] + im[r] * im[r]);
+                const float den = fmaxf(m, 1e-10f);
+                c = re[r] / den; s = im[r] / den;
+            } else {
+                m = sqrtf(fmaxf(re[r] * re[r] + im[r] * im[r], 1e-10f));
+                c = re[r] / m; s = im[r] / m;
+            }
+            if (real) real[row] = re[r];
+            if (imag) imag[row] = im[r];
+            if (mag) mag[row] = m;
+            if (cosv) cosv[row] = c;
+            if (sinv) sinv[row] = s;
+            if (x0 && f < FC) x0[((size_t)b * Tpad + ta + r) * FC + f] = m * s0[f] + h0[f];
+        }
+    }
+    if (x0 && !have_b && ta + 1 < Tpad)
+        for (int f = tid; f < FC; f += 256) x0[((size_t)b * Tpad + ta + 1) * FC + f] = 0.f;
+}
+
+// istft2_kernel for a clip of W samples whose samples lo <= n < hi alone are stored, at out[s_b + n].  A span that does not meet
+// [lo, hi) returns before it loads a twiddle: with a second of context either side of a five-second window that is two spans in
+// five.  Inside a span the overlap-add runs over the same frames in the same order as istft2_kernel.
+template <int N>
+__global__ __launch_bounds__(256) void istft2_windows_kernel(const float* __restrict__ real, const float* __restrict__ imag,
+                                                             const int64_t* __restrict__ starts, const int* __restrict__ keep,
+                                                             int64_t total, int T, int W, int hop, int wlen,
+                                                             const float2* __restrict__ tw2k, float* __restrict__ out) {
+    __shared__ float2 A[N], Bf[N], TW[2048];
+    __shared__ float acc[ISTFT_SPAN], env[ISTFT_SPAN];
+    constexpr int NB = N / 2 + 1;
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int m0 = blockIdx.x * ISTFT_SPAN;  // first padded position of this span
+    int lo = keep[2 * b], hi = keep[2 * b + 1];
+    lo = lo < 0 ? 0 : (lo > W ? W : lo);
+    hi = hi < lo ? lo : (hi > W ? W : hi);
+    if (m0 - N / 2 >= hi || m0 + ISTFT_SPAN - N / 2 <= lo) return;  // (an empty keep meets no span)
+    float* wav = out + window_start(starts, b, total, W);
+    const int woff = (N - wlen) / 2, wstride = 2048 / wlen;
+    for (int i = tid; i < 2048; i += 256) TW[i] = tw2k[i];
+    for (int i = tid; i < ISTFT_SPAN; i += 256) { acc[i] = 0.f; env[i] = 0.f; }
+    // frames whose window support [t*hop + woff, t*hop + woff + wlen) meets [m0, m0 + SPAN)
+    int t_lo = m0 - woff - wlen + 1;
+    t_lo = t_lo <= 0 ? 0 : (t_lo + hop - 1) / hop;
+    int t_hi = (m0 + ISTFT_SPAN - 1 - woff) / hop;
+    if (m0 + ISTFT_SPAN - 1 - woff < 0) t_hi = -1;
+    if (t_hi > T - 1) t_hi = T - 1;
+    __syncthreads();
+    for (int ta = t_lo; ta <= t_hi; ta += 2) {
+        const bool have_b = ta + 1 <= t_hi;
+        const size_t rowa = ((size_t)b * T + ta) * NB, rowb = rowa + NB;
+        for (int k = tid; k < N; k += 256) {  // Z = Xa + i Xb, Hermitian-extended (see istft2_kernel)
+            const int kk = k <= N / 2 ? k : N - k;
+            const float sg = (kk == 0 || kk == N / 2) ? 0.f : (k <= N / 2 ? 1.f : -1.f);
+            const float ar = real[rowa + kk], ai = sg * imag[rowa + kk];
+            const float br = have_b ? real[rowb + kk] : 0.f, bi = have_b ? sg * imag[rowb + kk] : 0.f;
+            A[k] = make_float2(ar - bi, ai + br);
+        }
+        __syncthreads();
+        const float2* X = fft_c<N, true>(A, Bf, TW, tid);  // (xa, xb) * N
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            if (r == 1 && !have_b) break;
+            const int base = (ta + r) * hop + woff - m0;  // span position of window sample 0
+            for (int j = tid; j < wlen; j += 256) {
+                const int pos = base + j;
+                if (pos >= 0 && pos < ISTFT_SPAN) {
+                    const float wn = 0.5f - 0.5f * TW[j * wstride].x;
+                    const float2 x = X[woff + j];
+                    acc[pos] += (r == 0 ? x.x : x.y) * (wn * (1.0f / N));
+                    env[pos] += wn * wn;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (int i = tid; i < ISTFT_SPAN; i += 256) {
+        const int n = m0 + i - N / 2;
+        if (n >= lo && n < hi) wav[n] = acc[i] / fmaxf(env[i], 1e-11f);  // 0 <= lo, hi <= W
+    }
+}
+
 }  // namespace
 
 hipError_t lass_launch_multi_stft(const float* wav, int B, int L, int hop, int nwin, const int* n_fft,
@@ -599,6 +743,45 @@ hipError_t lass_launch_istft2_ragged(const float* real, const float* imag, const
         hipLaunchKernelGGL(istft2_ragged_kernel<1024>, grid, dim3(256), 0, stream, real, imag, lengths, lo, T, L, hop, wlen, tw2k, wav);
     else
         hipLaunchKernelGGL(istft2_ragged_kernel<2048>, grid, dim3(256), 0, stream, real, imag, lengths, lo, T, L, hop, wlen, tw2k, wav);
+    return hipGetLastError();
+}
+
+hipError_t lass_launch_stft2_windows(const float* recording, int64_t total, const int64_t* starts, int B, int W, int n_fft, int hop,
+                                     int T, int Tpad, int nbr, const StftBranch* br, int magphase_sem, const float* s0,
+                                     const float* h0, const float2* tw2k, hipStream_t stream) {
+    if (!recording || !starts || B <= 0 || hop <= 0 || nbr <= 0 || nbr > LASS_MAX_STFT_WINDOWS || (n_fft != 1024 && n_fft != 2048) ||
+        W <= n_fft / 2 || total < W || T != 1 + W / hop || Tpad < T)
+        return hipErrorInvalidValue;
+    Stft2Args a;
+    a.nbr = nbr;
+    bool any_x0 = false;
+    for (int i = 0; i < nbr; ++i) {
+        const int wl = br[i].wlen;
+        if (wl <= 0 || wl > n_fft || (2048 % wl) != 0 || ((n_fft - wl) & 1)) return hipErrorInvalidValue;
+        if (br[i].x0 && (!s0 || !h0)) return hipErrorInvalidValue;
+        any_x0 |= br[i].x0 != nullptr;
+        a.wlen[i] = wl; a.mag[i] = br[i].mag; a.cosv[i] = br[i].cosv; a.sinv[i] = br[i].sinv;
+        a.real[i] = br[i].real; a.imag[i] = br[i].imag; a.x0[i] = br[i].x0;
+    }
+    dim3 grid(((any_x0 ? Tpad : T) + 1) / 2, B, nbr);
+#define LASS_STFT2W(NN, MP) hipLaunchKernelGGL((stft2_windows_kernel<NN, MP>), grid, dim3(256), 0, stream, recording, total, starts, W, hop, T, Tpad, tw2k, a, s0, h0)
+    if (n_fft == 1024) { if (magphase_sem) LASS_STFT2W(1024, true); else LASS_STFT2W(1024, false); }
+    else               { if (magphase_sem) LASS_STFT2W(2048, true); else LASS_STFT2W(2048, false); }
+#undef LASS_STFT2W
+    return hipGetLastError();
+}
+
+hipError_t lass_launch_istft2_windows(const float* real, const float* imag, const int64_t* starts, const int* keep, int64_t total,
+                                      int B, int T, int W, int n_fft, int wlen, int hop, const float2* tw2k, float* out,
+                                      hipStream_t stream) {
+    if (!starts || !keep || !out || B <= 0 || W <= n_fft / 2 || total < W || hop != LASS_HOP || T != 1 + W / hop ||
+        (n_fft != 1024 && n_fft != 2048) || wlen <= 0 || wlen > n_fft || (2048 % wlen) != 0 || ((n_fft - wlen) & 1))
+        return hipErrorInvalidValue;
+    dim3 grid((n_fft / 2 + W + ISTFT_SPAN - 1) / ISTFT_SPAN, B);
+    if (n_fft == 1024)
+        hipLaunchKernelGGL(istft2_windows_kernel<1024>, grid, dim3(256), 0, stream, real, imag, starts, keep, total, T, W, hop, wlen, tw2k, out);
+    else
+        hipLaunchKernelGGL(istft2_windows_kernel<2048>, grid, dim3(256), 0, stream, real, imag, starts, keep, total, T, W, hop, wlen, tw2k, out);
     return hipGetLastError();
 }
 

@@ -8,7 +8,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from . import _lib, arch
+from . import _lib, arch, longform
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -49,6 +49,7 @@ class Engine:
         self._ws_buf: Optional[torch.Tensor] = None  # ONE workspace, as large as the largest (B, L) seen so far
         self._ws_last = None                         # (B, L) of the last call that used it (its intermediates live there)
         self.ws_allocations = 0
+        self._win_bufs: Dict[int, tuple] = {}        # B -> (starts int64 (B), keep int32 (B,2), condition (B,512)): persistent
         self.finalized = False
 
     def __del__(self):
@@ -172,6 +173,83 @@ class Engine:
         rc = self.lib.lass_separate_ragged(self.ctx, _ptr(mixture), _ptr(lens), _ptr(condition), _ptr(out), B, L, _ptr(ws),
                                            ws.numel(), _stream(self.device))
         _lib.check(self.ctx, rc, "lass_separate_ragged")
+        return out
+
+    # ---- long recordings: windows of one long row ----------------------------------------------------------------
+    def window_buffers(self, B: int):
+        """The engine's persistent index and condition buffers of a B-window call: (starts int64 (B), keep int32 (B,2),
+        condition f32 (B,512)).  `separate_windows` stages host indices and a single condition here, so consecutive calls present
+        the same pointers (and reach graph replay); a caller may also fill them itself with stream-ordered copies."""
+        B = int(B)
+        if B not in self._win_bufs:
+            self._win_bufs[B] = (torch.zeros(B, dtype=torch.int64, device=self.device),
+                                 torch.zeros(B, 2, dtype=torch.int32, device=self.device),
+                                 torch.zeros(B, arch_cond(), dtype=torch.float32, device=self.device))
+        return self._win_bufs[B]
+
+    def _window_index(self, starts, keep, total: int, W: int, checked: bool, what: str):
+        """starts / keep of a window call as device tensors (int64 (B), int32 (B,2)).  Python sequences (or numpy arrays, CPU
+        tensors) are checked here - every window inside the recording, every keep inside its window, kept ranges disjoint
+        (ValueError) - and staged into the engine's persistent buffers; device tensors are taken as they are, and only with
+        `checked=True` (the library never reads them; the kernels clamp).  keep None (the front end keeps nothing): empty keeps."""
+        if keep is None:
+            on_device = torch.is_tensor(starts) and starts.is_cuda
+            keep = torch.zeros(len(starts), 2, dtype=torch.int32, device=self.device) if on_device else [(0, 0)] * len(starts)
+        dev_s, dev_k = torch.is_tensor(starts) and starts.is_cuda, torch.is_tensor(keep) and keep.is_cuda
+        if dev_s or dev_k:
+            if not (dev_s and dev_k):
+                raise _lib.LassError(f"{what}: starts and keep must both be device tensors or both host sequences")
+            if not checked:
+                raise _lib.LassError(f"{what}: device indices cannot be checked without a copy to the host: pass host "
+                                     "sequences, or checked=True once you have checked them (lass_amd.longform.check_keeps)")
+            B = starts.numel()
+            if (starts.device != self.device or starts.dtype != torch.int64 or starts.dim() != 1 or not starts.is_contiguous()
+                    or keep.device != self.device or keep.dtype != torch.int32 or keep.numel() != 2 * B or not keep.is_contiguous()):
+                raise _lib.LassError(f"{what}: device indices must be contiguous int64 (B,) starts and int32 (B,2) keeps on "
+                                     f"{self.device}")
+            return starts, keep
+        hs = np.asarray(starts.numpy() if torch.is_tensor(starts) else starts)
+        hk = np.asarray(keep.numpy() if torch.is_tensor(keep) else keep)
+        B = hs.shape[0] if hs.ndim == 1 else 0
+        if B < 1 or hk.size != 2 * B or not np.issubdtype(hs.dtype, np.integer) or not np.issubdtype(hk.dtype, np.integer):
+            raise ValueError(f"{what}: starts must be B >= 1 integers and keep B (lo, hi) pairs of integers")
+        hk = hk.reshape(B, 2)
+        longform.check_keeps([(int(a), int(lo), int(hi)) for a, (lo, hi) in zip(hs, hk)], W, total)
+        buf_s, buf_k, _ = self.window_buffers(B)
+        buf_s.copy_(torch.from_numpy(hs.astype(np.int64)))
+        buf_k.copy_(torch.from_numpy(hk.astype(np.int32)))
+        return buf_s, buf_k
+
+    def separate_windows(self, recording: torch.Tensor, starts, keep, condition: torch.Tensor, window: int,
+                         out: Optional[torch.Tensor] = None, checked: bool = False) -> torch.Tensor:
+        """B windows of ONE recording in one call (lass_separate_windows): recording (total,) f32; window b is
+        recording[starts[b] : starts[b] + window], separated as that clip alone, and of its output only [lo_b, hi_b) =
+        keep[b] is stored, at out[starts[b] + lo_b : starts[b] + hi_b].  Nothing else of `out` (total,) is touched: a fresh `out`
+        is zero-filled, one passed in keeps its other samples.  condition (B,512), or (1,512) / (512,) for all windows (expanded
+        into a persistent buffer).  See `_window_index` for how starts / keep are checked."""
+        if recording.dim() != 1:
+            raise ValueError("separate_windows takes a 1-D recording")
+        recording = self._dev(recording)
+        total, W = recording.shape[0], int(window)
+        idx_s, idx_k = self._window_index(starts, keep, total, W, checked, "separate_windows")
+        B = idx_s.numel()
+        condition = self._dev(condition)
+        if condition.numel() == arch_cond() and (B > 1 or condition.dim() == 1):
+            cond = self.window_buffers(B)[2]
+            cond.copy_(condition.reshape(1, -1).expand(B, -1))
+        elif condition.shape == (B, arch_cond()):
+            cond = condition
+        else:
+            raise ValueError(f"condition must be ({B}, {arch_cond()}), (1, {arch_cond()}) or ({arch_cond()},)")
+        if out is None:
+            out = torch.zeros_like(recording)
+        elif (out.shape != recording.shape or out.dtype != torch.float32 or out.device != self.device
+              or not out.is_contiguous()):
+            raise _lib.LassError(f"out must be a contiguous float32 {tuple(recording.shape)} tensor on {self.device}")
+        ws = self._workspace(B, W)
+        rc = self.lib.lass_separate_windows(self.ctx, _ptr(recording), total, _ptr(idx_s), _ptr(idx_k), _ptr(cond), _ptr(out), B, W,
+                                            _ptr(ws), ws.numel(), _stream(self.device))
+        _lib.check(self.ctx, rc, "lass_separate_windows")
         return out
 
     def _dev(self, t: torch.Tensor) -> torch.Tensor:
@@ -313,6 +391,42 @@ class Engine:
                                         _stream(self.device))
         _lib.check(self.ctx, rc, "lass_istft_ragged")
         return wav
+
+    def front_end_windows(self, recording: torch.Tensor, starts, window: int, checked: bool = False):
+        """`front_end` of the windows recording[starts[b] : starts[b] + window] of a 1-D recording (lass_front_end_windows):
+        shapes as for B clips of `window` samples, row b what `front_end` gives for the gathered window."""
+        recording = self._dev(recording)
+        total, W = recording.shape[0], int(window)
+        B = len(starts)
+        idx_s, _ = self._window_index(starts, None, total, W, checked, "front_end_windows")
+        T = arch.frames_for(W)
+        nb = self.n_fft // 2 + 1
+        shape = (B, arch.padded_frames(T), nb - 1)
+        mk = lambda: torch.empty(B, T, nb, dtype=torch.float32, device=self.device)  # noqa: E731
+        mag, cos, sin = mk(), mk(), mk()
+        x0 = torch.empty((self.n_branches,) + shape if self.multistft else shape, dtype=torch.float32, device=self.device)
+        rc = self.lib.lass_front_end_windows(self.ctx, _ptr(recording), total, _ptr(idx_s), B, W, _ptr(mag), _ptr(cos), _ptr(sin),
+                                             _ptr(x0), _stream(self.device))
+        _lib.check(self.ctx, rc, "lass_front_end_windows")
+        return mag, cos, sin, x0
+
+    def istft_windows(self, real: torch.Tensor, imag: torch.Tensor, starts, keep, window: int, out: torch.Tensor,
+                      n_fft: Optional[int] = None, win_length: Optional[int] = None, checked: bool = False) -> torch.Tensor:
+        """`istft_nfft` for windows (lass_istft_windows): real, imag (B, 1 + window // 160, n_fft/2+1); of window b's `window`
+        samples only keep[b] = [lo, hi) is stored, at out[starts[b] + lo : starts[b] + hi] of the 1-D `out`."""
+        real, imag, out = self._dev(real), self._dev(imag), self._dev(out)
+        n_fft = self.n_fft if n_fft is None else int(n_fft)
+        win_length = n_fft if win_length is None else int(win_length)
+        B, T, F = real.shape
+        assert F == n_fft // 2 + 1 and imag.shape == real.shape and out.dim() == 1
+        total, W = out.shape[0], int(window)
+        idx_s, idx_k = self._window_index(starts, keep, total, W, checked, "istft_windows")
+        if idx_s.numel() != B:
+            raise ValueError(f"istft_windows: {B} spectra, {idx_s.numel()} windows")
+        rc = self.lib.lass_istft_windows(self.ctx, _ptr(real), _ptr(imag), _ptr(idx_s), _ptr(idx_k), total, B, T, W, n_fft,
+                                         win_length, _ptr(out), _stream(self.device))
+        _lib.check(self.ctx, rc, "lass_istft_windows")
+        return out
 
     def stft_components(self, wav: torch.Tensor, n_fft: int, win_lengths, hop: int = arch.HOP):
         """(B,L) -> {win: (mag, cos, sin)} each (B,1,T,n_fft//2+1): `calculate_stft_components` at a COMMON n_fft for

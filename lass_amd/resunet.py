@@ -14,7 +14,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import arch, ragged
+from . import arch, longform, ragged
 from ._lib import LassError
 from .engine import Engine
 
@@ -184,18 +184,64 @@ class ResUNet30(nn.Module):
         return results
 
     @torch.no_grad()
+    def separate_long(self, waveform: torch.Tensor, condition: torch.Tensor, window: int = 160000, context: int = 16000,
+                      max_batch: int = 16, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Separate a recording of ANY length (> n_fft/2): 1-D waveform, condition (512,) or (1,512) -> 1-D float32 tensor of
+        the same length on the model's device.  The recording is cut into overlapping windows of `window` samples of which
+        only the inner part is kept (`context` samples discarded towards each neighbour: lass_amd.longform.plan_windows) and
+        stays on the device throughout: groups of `max_batch` windows run as one Engine.separate_windows each, all on the same
+        recording, output, index buffers and workspace, so from the third group on a group is one replayed hipGraph.  The index
+        buffers are rewritten by stream-ordered device copies between groups: no host synchronisation, no copy to the host.
+        total <= window: one plain `separate`."""
+        if self.training:
+            raise LassError("lass_amd.ResUNet30 is inference-only (call .eval()); training is out of scope")
+        if waveform.dim() != 1:
+            raise ValueError("separate_long takes a 1-D waveform")
+        eng = self._ensure_engine()
+        dev = eng.device
+        total = int(waveform.shape[0])
+        plan = longform.plan_windows(total, window, context, eng.n_fft)
+        rec = waveform.to(device=dev, dtype=torch.float32).contiguous()
+        cond = condition.to(device=dev, dtype=torch.float32).reshape(1, -1).contiguous()
+        if cond.shape != (1, self.condition_size):
+            raise ValueError(f"condition must be ({self.condition_size},) or (1, {self.condition_size})")
+        if out is not None and (out.shape != rec.shape or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous()):
+            raise LassError(f"out must be a contiguous float32 {tuple(rec.shape)} tensor on {dev}")
+        if total <= window:
+            sep = eng.separate(rec[None], cond)[0]
+            return sep if out is None else out.copy_(sep)
+        if out is None:
+            out = torch.empty_like(rec)  # the kept ranges tile it exactly once
+        groups = longform.group_windows(plan, max_batch)
+        B = len(groups[0])
+        # the whole plan goes up in two copies; each group's rows then reach the engine's index buffers device to device
+        all_starts = torch.tensor([[w[0] for w in g] for g in groups], dtype=torch.int64).to(dev)
+        all_keeps = torch.tensor([[w[1:] for w in g] for g in groups], dtype=torch.int32).to(dev)
+        idx_s, idx_k, cond_b = eng.window_buffers(B)
+        cond_b.copy_(cond.expand(B, -1))
+        for gi in range(len(groups)):
+            idx_s.copy_(all_starts[gi])
+            idx_k.copy_(all_keeps[gi])
+            eng.separate_windows(rec, idx_s, idx_k, cond_b, window, out=out, checked=True)
+        return out
+
+    @torch.no_grad()
     def forward(self, input_dict: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         """resunet.py:640-653."""
         return {"waveform": self._separate(input_dict["mixture"], input_dict["condition"])}
 
     @torch.no_grad()
-    def chunk_inference(self, input_dict: Dict[str, torch.Tensor], max_batch: int = 16) -> np.ndarray:
+    def chunk_inference(self, input_dict: Dict[str, torch.Tensor], max_batch: int = 16, resident: bool = False) -> np.ndarray:
         """resunet.py:655-714, including its quirks: RATE hard-coded to 32000, batch 1, float64 result, zeros when
         the input is not longer than one window.  The reference runs a second, overlapping forward inside each loop
         iteration whose write is overwritten by the next iteration except at the tail; the same writes are made here in
         the same order, so outputs are identical sample for sample.  Execution differs: the windows are independent
         (eval-mode BatchNorm), so every DISTINCT window is separated once, `max_batch` windows per launch, instead of
-        two batch-1 forwards per iteration (the second forward of iteration i is the first of iteration i+1)."""
+        two batch-1 forwards per iteration (the second forward of iteration i is the first of iteration i+1).
+        resident=True: the same result, sample for sample, with the recording and the output kept on the device
+        (`_chunk_inference_resident`)."""
+        if resident:
+            return self._chunk_inference_resident(input_dict, max_batch)
         mixtures, conditions = input_dict["mixture"], input_dict["condition"]
         rate = 32000
         nl, nc, nr = int(1.0 * rate), int(3.0 * rate), int(1.0 * rate)
@@ -233,3 +279,34 @@ class ResUNet30(nn.Module):
         for seg, dst, src in writes:
             out_np[:, dst] = results[seg][:, src]
         return out_np
+
+    def _chunk_inference_resident(self, input_dict: Dict[str, torch.Tensor], max_batch: int) -> np.ndarray:
+        """chunk_inference's result through Engine.separate_windows: what survives of the reference's writes is one range per
+        distinct window (lass_amd.longform.reference_plan), so every window stores its range straight into one output row on
+        the device - one call per `max_batch` windows of equal length (the shorter tail window is a call of its own length), the
+        same batches in the same order as the default path - and ONE copy to the host at the end fills the reference's (1, L)
+        float64 array, zero where the reference never writes."""
+        if self.training:
+            raise LassError("lass_amd.ResUNet30 is inference-only (call .eval()); training is out of scope")
+        mixtures, conditions = input_dict["mixture"], input_dict["condition"]
+        if mixtures.dim() != 3 or mixtures.shape[1] != 1:
+            raise ValueError("mixture must be (batch_size, 1, segment_samples)")
+        rate = 32000
+        nl, nc, nr = int(1.0 * rate), int(3.0 * rate), int(1.0 * rate)
+        length = mixtures.shape[2]
+        _, ranges = longform.reference_plan(length, nl, nc, nr)
+        if not ranges:
+            return np.zeros([1, length])
+        eng = self._ensure_engine()
+        dev = eng.device
+        rec = mixtures[0, 0].to(device=dev, dtype=torch.float32).contiguous()
+        cond = conditions[:1].to(device=dev, dtype=torch.float32).contiguous()
+        out = torch.zeros_like(rec)
+        by_len: Dict[int, list] = {}
+        for a, b, lo, hi in ranges:
+            by_len.setdefault(b - a, []).append((a, lo, hi))
+        for w, wins in by_len.items():
+            for i in range(0, len(wins), max_batch):
+                group = wins[i:i + max_batch]
+                eng.separate_windows(rec, [g[0] for g in group], [g[1:] for g in group], cond, w, out=out)
+        return out.cpu().numpy().astype(np.float64)[None, :]
