@@ -196,6 +196,13 @@ int lass_set_head_fold(lass_ctx* ctx, int enabled);
  * rounding only.  The multi-STFT model, the stage calls, LASS_WINO4=0, lass_set_head_fold(0) and the bf16 modes ignore the
  * switch.  Query lass_workspace_bytes again afterwards. */
 int lass_set_head_sc_fold(lass_ctx* ctx, int enabled);
+/* f32: the pointwise GEMMs (the 1x1 shortcuts of the deep blocks, the transposed convs from 128 input channels up) multiply on the
+ * bf16 matrix unit at f32 accuracy: each f32 operand is split exactly into three bf16 pieces and six of the nine piece products
+ * are summed in f32 in one fixed order (the three dropped ones are ~2^-24 of the product).  1 = that kernel (default), 0 = the
+ * f32-MFMA kernel (A/B, tests; LASS_PW_SPLIT at lass_create).  The switch picks the kernel of those launches and nothing else:
+ * which layers they are, and every workspace size, stay as they were.  The two differ by f32 rounding only.  Non-finite
+ * activations are outside the split's contract.  The bf16 modes run no such launch and ignore the switch. */
+int lass_set_pw_split(lass_ctx* ctx, int enabled);
 /* UNSTABLE, tests only - not part of the supported interface, and may change or go without notice; lass_separate never looks at
  * it.  The stage calls (lass_convblock, lass_encoder_block) keep that image in `v` (`floats` f32 of device memory owned by the
  * caller) instead of a buffer of the context; NULL restores the context's.  A buffer that is too small for a layer, or overlaps

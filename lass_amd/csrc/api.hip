@@ -49,6 +49,7 @@ struct ResBlock {  // one ConvBlockRes
     const float* bsc = nullptr;                         // raw shortcut bias
     // decoder_block6, f32: conv2 and the shortcut composed with after_conv (head_fold.h) - U images, Wsc' [cin][16], b' [16]
     float *u2h = nullptr, *wsch = nullptr, *bh = nullptr;
+    void* wsc3 = nullptr;  // f32: wsc as the three bf16 pieces of pw_gemm.hip's split kernel (the shortcut-GEMM layers)
 };
 
 struct ProfEntry {
@@ -92,10 +93,11 @@ struct lass_ctx {
     int dec_site[6] = {0};           // decoder_blockN->beta1
     void* up16[6] = {nullptr};       // bf16 transposed-conv weights (hi) per decoder, bf16 modes only
     void* up16l[6] = {nullptr};      // lo halves (LASS_COMPUTE_BF16X3)
+    void* up3[6] = {nullptr};        // f32: the transposed-conv weights as the three bf16 pieces of pw_gemm.hip's split kernel
     std::vector<void*> owned;        // derived device buffers to free
     // the compute mode (lass_finalize) and every switch a route depends on, as the value conv_route.h's rules read: LASS_WINO4,
     // lass_set_wino4_splits, lass_set_wino4_vprep / LASS_WINO4_VPREP, lass_set_head_fold / LASS_HEAD_FOLD, lass_set_head_sc_fold /
-    // LASS_HEAD_SC_FOLD, LASS_FUSE_CATB / _BLOCK / _UP
+    // LASS_HEAD_SC_FOLD, lass_set_pw_split / LASS_PW_SPLIT, LASS_FUSE_CATB / _BLOCK / _UP
     RouteCfg cfg;
     float *hs_wt = nullptr, *hs_wskip = nullptr;  // head_fold.h: Wt' [cin][64] for that transposed conv, Wsc'_skip [3][32] (lass_finalize)
     float* stage_v = nullptr;      // ... their V image in the stage calls, grown on demand like stage_part (Plan::vprep in lass_separate)
@@ -647,9 +649,12 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
         if (rt.conv2.family == CONV_NONE) return fail(c, LASS_ERR_STATE, "conv2 with the shortcut as residual");
         if (!lass_pw_gemm_supported(CONV2_SHORTCUT, q))
             return fail(c, LASS_ERR_STATE, rb.prefix + " shortcut: the launch arguments contradict the planned route");
+        PwSplitW sw;
+        if (rt.pw_split) sw.w = rb.wsc3;
+        if (rt.pw_split && !sw.w) return fail(c, LASS_ERR_STATE, rb.prefix + " shortcut: the split weights of the planned route are missing");
         {
             ProfScope ps(c, st, P_CONV3X3);
-            HIP_TRY(c, lass_launch_pw_gemm(CONV2_SHORTCUT, q, st));
+            HIP_TRY(c, lass_launch_pw_gemm(CONV2_SHORTCUT, q, st, sw));
         }
         q.in2 = nullptr; q.in2_bs = 0; q.Cin2 = 0; q.w2 = nullptr; q.bias = nullptr;
         q.res = out; q.res_bs = out_bs;
@@ -682,7 +687,9 @@ int run_upconv(lass_ctx* c, int di, const float* x, int B, int h, int w, const f
         p.act_scale = cb->scale; p.act_shift = cb->shift; p.act_shift_bs = c->n_shift;
     }
     if (ok && rt.family == UP_LOGITS) ok = lass_tconv_logits_supported(p, *planes);
-    if (ok && rt.family == UP_GEMM) ok = lass_pw_gemm_supported(TCONV_ACT, p);
+    PwSplitW sw;
+    if (rt.pw_split) sw.w = c->up3[di];
+    if (ok && rt.family == UP_GEMM) ok = lass_pw_gemm_supported(TCONV_ACT, p) && (!rt.pw_split || sw.w);
     if (!ok || rt.family == UP_INSIDE)
         return fail(c, LASS_ERR_STATE, std::string(d.name) + " transposed conv: the launch arguments contradict the planned route");
     ProfScope ps(c, st, P_TCONV);
@@ -694,7 +701,7 @@ int run_upconv(lass_ctx* c, int di, const float* x, int B, int h, int w, const f
             HIP_TRY(c, lass_launch_conv_bf16(TCONV_ACT, p, st));
             break;
         case UP_GEMM:
-            HIP_TRY(c, lass_launch_pw_gemm(TCONV_ACT, p, st));
+            HIP_TRY(c, lass_launch_pw_gemm(TCONV_ACT, p, st, sw));
             break;
         default:
             HIP_TRY(c, lass_launch_conv(TCONV_ACT, p, st));
@@ -906,6 +913,7 @@ static int create_impl(lass_ctx** out, int device_id, const Geometry& geom) {
     if (const char* e = getenv("LASS_WINO4_VPREP")) c->cfg.vprep_mode = std::max(0, std::min(2, atoi(e)));  // A/B: lass_set_wino4_vprep
     if (const char* e = getenv("LASS_HEAD_FOLD")) c->cfg.head_fold = atoi(e) != 0;  // A/B: lass_set_head_fold
     if (const char* e = getenv("LASS_HEAD_SC_FOLD")) c->cfg.head_sc_fold = atoi(e) != 0;  // A/B: lass_set_head_sc_fold
+    if (const char* e = getenv("LASS_PW_SPLIT")) c->cfg.pw_split = atoi(e) != 0;  // A/B: lass_set_pw_split
     if (const char* e = getenv("LASS_SPLIT")) c->split_batch = std::max(0, std::min(2, atoi(e)));
     if (const char* e = getenv("LASS_GRAPH")) c->use_graph = atoi(e) != 0;
     c->prof.resize(P_COUNT);
@@ -1102,6 +1110,7 @@ int lass_finalize(lass_ctx* c, int compute_mode) {
         }
         rb.wsc = nullptr;
         rb.bsc = nullptr;
+        rb.wsc3 = nullptr;
         if (rb.cin != rb.cout) {
             const float *ws = need(rb.prefix + ".shortcut.weight"), *bs = need(rb.prefix + ".shortcut.bias");
             if (!ws || !bs) return LASS_ERR_STATE;
@@ -1124,6 +1133,12 @@ int lass_finalize(lass_ctx* c, int compute_mode) {
                 if (dev_alloc(c, &rb.usc, (size_t)4 * rb.cout * rb.cin)) return LASS_ERR_HIP;
                 HIP_TRY(c, lass_launch_wino_shortcut_weights(ws, rb.cout, rb.cin, rb.usc, st));
             }
+            if (lass_pw_split_shortcut_weights(c->cfg.f32(), rb.cin, rb.cout)) {  // from wsc [cin][cout], the f32 kernel's matrix
+                unsigned short* t = nullptr;
+                if (dev_alloc(c, &t, (size_t)3 * rb.cout * rb.cin)) return LASS_ERR_HIP;
+                HIP_TRY(c, lass_launch_pw_split_weights(rb.wsc, rb.cin, rb.cout, t, st));
+                rb.wsc3 = t;
+            }
         }
         return 0;
     };
@@ -1133,7 +1148,13 @@ int lass_finalize(lass_ctx* c, int compute_mode) {
         const auto& d = c->m.D[i];
         const float* wu = need(std::string("base.") + d.name + ".conv1.weight");
         if (!wu) return LASS_ERR_STATE;
-        c->up16[i] = c->up16l[i] = nullptr;
+        c->up16[i] = c->up16l[i] = c->up3[i] = nullptr;
+        if (lass_pw_split_tconv_weights(c->cfg.f32(), d.cin, d.cout * d.uh * d.uw, d.uh)) {  // (cin, cout, uh, uw) == [cin][n]
+            unsigned short* t = nullptr;
+            if (dev_alloc(c, &t, (size_t)3 * d.cin * d.cout * d.uh * d.uw)) return LASS_ERR_HIP;
+            HIP_TRY(c, lass_launch_pw_split_weights(wu, d.cin, d.cout * d.uh * d.uw, t, st));
+            c->up3[i] = t;
+        }
         if (bf16_tconv_weights(c->cfg, d)) {
             const int N = d.cout * d.uh * d.uw;
             unsigned short *t = nullptr, *l = nullptr;
@@ -1955,6 +1976,13 @@ int lass_set_head_sc_fold(lass_ctx* c, int enabled) {
     if (!c || (enabled != 0 && enabled != 1)) return fail(c, LASS_ERR_ARG, "lass_set_head_sc_fold: 0 or 1");
     c->cfg.head_sc_fold = enabled != 0;
     ++c->gen;  // as lass_set_wino4_splits: other launches, another workspace size
+    return 0;
+}
+
+int lass_set_pw_split(lass_ctx* c, int enabled) {
+    if (!c || (enabled != 0 && enabled != 1)) return fail(c, LASS_ERR_ARG, "lass_set_pw_split: 0 or 1");
+    c->cfg.pw_split = enabled != 0;
+    ++c->gen;  // captured graphs hold the launches of the previous choice
     return 0;
 }
 

@@ -161,6 +161,16 @@ constexpr int kVprepMinCoutGroups = 12;
 // per batch) is byte-bound and measured 7 % faster in the direct kernel
 constexpr int kTconvGemmMinCin = 128;
 
+// Which weight matrices lass_finalize also keeps as the three bf16 pieces of pw_gemm.hip's split kernel (6 K N bytes each): every
+// one that plan_block / plan_upconv can send there at some image size (the channel half of their rules).  Kept whatever
+// RouteCfg::pw_split says at that moment: the switch can be thrown afterwards.
+inline bool lass_pw_split_shortcut_weights(bool f32, int cin, int cout) {
+    return f32 && cin != cout && cin >= kShortcutGemmMinCin && cin % (2 * kPwGemmKC) == 0 && cout % kPwGemmNB == 0;
+}
+inline bool lass_pw_split_tconv_weights(bool f32, int cin, int N, int up_h) {
+    return f32 && cin >= kTconvGemmMinCin && cin % (2 * kPwGemmKC) == 0 && N % kPwGemmNB == 0 && (up_h == 1 || up_h == 2) && N % (2 * up_h) == 0;
+}
+
 enum ComputeMode { MODE_F32 = 0, MODE_BF16 = 1, MODE_BF16X3 = 2 };  // the values of LASS_COMPUTE_* (include/lass_hip.h)
 
 struct RouteCfg {
@@ -171,6 +181,7 @@ struct RouteCfg {
     int vprep_mode = 1;    // V from memory: 0 = off, 1 = the layers of kVprepMinCoutGroups, 2 = every layer whose kind admits it
     bool head_fold = true; // the fused output head runs on weights composed with after_conv (3 logits instead of 32 channels)
     bool head_sc_fold = true;  // ... and takes its shortcut's logits as planes from the launches that produce its inputs
+    bool pw_split = true;  // the pw_gemm.hip launches contract on the bf16 MFMA over three exact bf16 pieces per operand (f32 accuracy)
     // bf16 mode (MODE_BF16 only: the hi+lo split of bf16x3 has no blocked hand-overs and no fused kernels)
     bool fuse_catb = true;   // tensors between launches travel as blocked bf16 copies (LASS_FUSE_CATB)
     bool fuse_block = true;  // encoder_block1 and decoder_block6 as one kernel each (LASS_FUSE_BLOCK)
@@ -240,6 +251,7 @@ struct BlockRoute {
     ConvRoute conv1, conv2;
     bool shortcut_gemm = false;  // the 1x1 shortcut is a pw_gemm.hip launch in front, into the block's output slot; conv2 is then
                                  // CONV2_IDENT with that slot as its residual, in place
+    bool pw_split = false;       // ... by pw_gemm.hip's split-bf16 kernel (RouteCfg::pw_split: the switch picks the kernel, never the route)
     size_t kpart_floats = 0;     // split-K partials both convs share: [splits][B][cout][H][W]
     size_t v_floats = 0;         // the V slot: the larger of the two convs' images (one at a time, in stream order)
 };
@@ -281,6 +293,7 @@ inline BlockRoute plan_block(const RouteCfg& cfg, const BlockShape& b, int B, in
     const bool u2f = im.u2f && geom;
     r.shortcut_gemm = !ident && !io.head && b.cin >= kShortcutGemmMinCin && wino2 && u2f &&
                       (ksplit > 0 || lass_wino4_shape(CONV2_SHORTCUT, s2)) && lass_pw_gemm_shortcut_shape(s2) && io.x_aligned;
+    r.pw_split = r.shortcut_gemm && cfg.pw_split;
     if (r.shortcut_gemm) {
         s2.Cin2 = 0;
         if (lass_wino4_shape(CONV2_IDENT, s2, n))
@@ -422,6 +435,7 @@ struct UpSite {
 struct UpRoute {
     UpFamily family = UP_DIRECT;
     bool in_act = false, out_copies = false;  // the site's, where the family admits them
+    bool pw_split = false;                    // UP_GEMM: pw_gemm.hip's split-bf16 kernel (RouteCfg::pw_split)
 };
 inline UpRoute plan_upconv(const RouteCfg& cfg, const DecSpec& d, int h, int w, const UpSite& site = UpSite()) {
     UpRoute r;
@@ -436,6 +450,7 @@ inline UpRoute plan_upconv(const RouteCfg& cfg, const DecSpec& d, int h, int w, 
         r.out_copies = site.out_copies && cfg.blocked() && d.uh == 2 && d.uw == 2;
     } else if (cfg.f32() && d.cin >= kTconvGemmMinCin && site.aligned && lass_pw_gemm_tconv_shape(s, d.uh)) {
         r.family = UP_GEMM;  // K = cin, N = 4 cout: one GEMM, the prologue applied once per element
+        r.pw_split = cfg.pw_split;
     }
     return r;
 }

@@ -162,8 +162,15 @@ hipError_t lass_launch_wino4_sclogit(const ConvArgs& p, const HeadScPlanes& hs, 
 // ---- pw_gemm.hip (f32 pointwise GEMMs with a 128-cout workgroup tile; H*W % 4 == 0, N % 128 == 0, K % 32 == 0) ------------
 // CONV2_SHORTCUT: only the 1x1 shortcut, out = bias + Wsc x (in2, Cin2, w2, bias), for conv2 to read back as its residual;
 // TCONV_ACT: the kernel == stride transposed conv behind its BN+FiLM+leaky prologue (f32 output only)
+// sw.w set: the split-bf16 kernel (six v_mfma_f32_32x32x16_bf16 products of three exact bf16 pieces per operand, f32 accuracy)
+// on weights that lass_launch_pw_split_weights formed from the same [K][Nw] f32 matrix: [3][K / 8][Nw][8] bf16, 6 K Nw bytes.
+// (Beside ConvArgs for the same reason as Wino4Split.)
+struct PwSplitW {
+    const void* w = nullptr;
+};
 bool lass_pw_gemm_supported(ConvKind kind, const ConvArgs& p);
-hipError_t lass_launch_pw_gemm(ConvKind kind, const ConvArgs& p, hipStream_t stream);
+hipError_t lass_launch_pw_gemm(ConvKind kind, const ConvArgs& p, hipStream_t stream, const PwSplitW& sw = PwSplitW());
+hipError_t lass_launch_pw_split_weights(const float* w, int K, int Nw, void* dst, hipStream_t stream);
 
 // ---- conv_bf16.hip (bf16-MFMA variant of the 3x3 kinds; W multiple of 32, Cin multiple of 16) ----------------------
 bool lass_bf16_supported(const ConvArgs& p);
