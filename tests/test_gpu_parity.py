@@ -218,7 +218,8 @@ def test_separate_tiny_vs_oracle_and_golden(model, oracle_sd, golden_dir):
 def test_separate_10s_vs_golden(synthetic_sd, golden_dir, mode):
     """G2 = the reference's own output and SDR / SDRi / SI-SDR triple on a 10 s clip (tools/gen_golden.py).  Every compute
     mode is pinned to it: the triple within north_star's 0.05 dB (f32: 0.01), the waveform within 3e-6 RMS for f32,
-    1e-5 RMS for the split-operand mode (f32 tolerance class), 5 % relative for plain bf16 (8-bit mantissa operands)."""
+    1e-5 RMS for the split-operand mode (f32 tolerance class), 0.69 % relative for plain bf16 (8-bit mantissa operands: 3 x the
+    0.227 % measured; tests/test_gpu_bf16_exact.py holds every launch to its own model)."""
     from lass_amd.resunet import ResUNet30
     from oracle import metrics as om
     g = np.load(os.path.join(golden_dir, "g2_clip10s.npz"))
@@ -239,7 +240,7 @@ def test_separate_10s_vs_golden(synthetic_sd, golden_dir, mode):
     elif mode == "bf16x3":
         assert err <= 1e-5
     else:
-        assert 1e-7 < err < 5e-2 * ref_rms   # really the bf16 kernels, and sane
+        assert 1e-7 < err < 6.9e-3 * ref_rms   # really the bf16 kernels; 3 x the 2.27e-3 measured (was 5e-2)
     sdr = om.calculate_sdr(src[0], out)
     sdr0 = om.calculate_sdr(src[0], mix[0])
     sisdr = om.calculate_sisdr(src[0], out)
@@ -638,7 +639,8 @@ def test_bf16_mode_convblock_and_waveform(synthetic_sd, oracle_sd, monkeypatch):
         ref = orr.conv_block_res(oracle_sd, prefix, x, orr.film(oracle_sd, cond, stem + "->beta1"),
                                  orr.film(oracle_sd, cond, stem + "->beta2"))
         rel = _relerr(y, ref)
-        assert 1e-5 < rel < 2e-2, (prefix, rel)   # > 1e-5: make sure the bf16 kernels really ran
+        print("bf16", prefix, "relative RMS error vs the f32 oracle", rel)
+        assert 1e-5 < rel < 8.1e-3, (prefix, rel)   # > 1e-5: the bf16 kernels really ran; 3 x the largest measured, 2.67e-3 (was 2e-2)
     m = ResUNet30(1, 1, 512)
     m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in synthetic_sd.items()})
     m = m.to(DEV).eval().set_compute_dtype("bf16")
@@ -649,7 +651,7 @@ def test_bf16_mode_convblock_and_waveform(synthetic_sd, oracle_sd, monkeypatch):
         "waveform"]
     rel = _relerr(out, ref)
     print("bf16 waveform relative RMS error", rel)
-    assert rel < 5e-2, rel
+    assert rel < 7.4e-3, rel   # 3 x the 2.46e-3 measured (was 5e-2)
     # decoder_block6's transposed conv inside its fused kernel (default) composes the shortcut with it - weights rounded once,
     # bf16 noise apart from the three-launch form (test_bf16_fused_upconv_vs_separate_launch); the exact A/B pairs below are
     # taken against the three-launch form
@@ -670,7 +672,8 @@ def test_bf16_mode_convblock_and_waveform(synthetic_sd, oracle_sd, monkeypatch):
     monkeypatch.delenv("LASS_FUSE_CATB")
     # (round 5: with the blocked copies the 1x1 shortcut is contracted INSIDE the 3x3 chunk loop, with f32 tensors behind it -
     # another f32 summation order, so roundings of the bf16 hand-overs flip here and there: bf16 noise, not 1e-5 any more)
-    assert _relerr(out2, out) < 2e-3
+    print("blocked bf16 hand-overs vs f32 hand-overs (bf16): relative RMS difference", _relerr(out2, out))
+    assert _relerr(out2, out) < 2e-3   # measured 8.9e-4: 3 x that would be looser than this bar, which stays
     # encoder_block1 and decoder_block6 as ONE kernel each (conv_bf16_fused.hip: the 32-channel intermediate stays in LDS) is the default; the
     # two-launch form rounds the same f32 accumulators to the same bf16 intermediate: same waveform
     monkeypatch.setenv("LASS_FUSE_BLOCK", "0")
@@ -783,7 +786,7 @@ def test_bf16_modes_full_size_metrics_vs_f32(synthetic_sd):
     for mode in ("bf16", "bf16x3"):
         d = np.abs(rows[mode] - rows["f32"]).max()
         print(mode, "max |dB difference| vs f32 over 16 clips x (SDR, SDRi, SI-SDR):", d)
-        assert d < 0.05, (mode, d)
+        assert d < (0.0434 if mode == "bf16" else 1.3e-4), (mode, d)   # 3 x the 1.444e-2 / 4.14e-5 dB measured (was 0.05 for both)
     assert _rms(outs["bf16x3"] - outs["f32"]) <= 1e-5
     assert 1e-6 < _rms(outs["bf16"] - outs["f32"]) < 5e-2 * _rms(outs["f32"])   # really the bf16 kernels, and sane
 
