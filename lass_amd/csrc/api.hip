@@ -1278,7 +1278,7 @@ int lass_stft_magphase(lass_ctx* c, const float* wav, int B, int L, float* mag, 
     const int T = 1 + L / LASS_HOP;
     StftBranch br;
     br.wlen = LASS_NFFT; br.mag = mag; br.cosv = cos_out; br.sinv = sin_out; br.real = real_out; br.imag = imag_out;
-    HIP_TRY(c, lass_launch_stft2(wav, B, L, LASS_NFFT, LASS_HOP, T, T, 1, &br, 0, nullptr, nullptr, c->tw2k,
+    HIP_TRY(c, lass_launch_stft2(wav, ClipForm{B, L}, LASS_NFFT, LASS_HOP, T, T, 1, &br, 0, nullptr, nullptr, c->tw2k,
                                  (hipStream_t)stream));
     return 0;
 }
@@ -1299,7 +1299,7 @@ int lass_stft_components(lass_ctx* c, const float* wav, int B, int L, int n_fft,
     }
     if (int r = use_device(c)) return r;
     const int T = 1 + L / hop;
-    HIP_TRY(c, lass_launch_stft2(wav, B, L, n_fft, hop, T, T, n_windows, br, 1, nullptr, nullptr, c->tw2k,
+    HIP_TRY(c, lass_launch_stft2(wav, ClipForm{B, L}, n_fft, hop, T, T, n_windows, br, 1, nullptr, nullptr, c->tw2k,
                                  (hipStream_t)stream));
     return 0;
 }
@@ -1335,7 +1335,7 @@ int lass_istft_nfft(lass_ctx* c, const float* real, const float* imag, int B, in
         (long)L + n_fft / 2 > (long)(T - 1) * LASS_HOP + n_fft)
         return fail(c, LASS_ERR_ARG, "lass_istft: bad argument");
     if (int r = use_device(c)) return r;
-    HIP_TRY(c, lass_launch_istft2(real, imag, B, T, L, n_fft, win_length, LASS_HOP, c->tw2k, wav, (hipStream_t)stream));
+    HIP_TRY(c, lass_launch_istft2(real, imag, ClipForm{B, L}, T, n_fft, win_length, LASS_HOP, c->tw2k, wav, (hipStream_t)stream));
     return 0;
 }
 
@@ -1379,40 +1379,45 @@ int lass_encoder_block(lass_ctx* c, const char* name, const float* x, int B, int
     return fail(c, LASS_ERR_ARG, std::string("lass_encoder_block: unknown encoder '") + name + "'");
 }
 
+// The front end of the network for the clips of cf, one launch for all analysis branches: x0[k] (B, Tp, fcrop) of branch k,
+// mag / cos / sin of the mask branch alone.
+static hipError_t launch_front_end(lass_ctx* c, const float* wav, const ClipForm& cf, float* const* x0, float* mag, float* cosv,
+                                   float* sinv, hipStream_t st) {
+    const Geometry& g = c->g;
+    const int T = 1 + cf.L / LASS_HOP, Tp = (T + 31) / 32 * 32;
+    StftBranch br[kMaxBranches];
+    for (int k = 0; k < g.nbr; ++k) {
+        br[k].wlen = g.wins[k];
+        br[k].x0 = x0[k];
+        if (k == g.mask_br) { br[k].mag = mag; br[k].cosv = cosv; br[k].sinv = sinv; }
+    }
+    return lass_launch_stft2(wav, cf, g.nfft, LASS_HOP, T, Tp, g.nbr, br, g.magphase_sem, c->bn0_s, c->bn0_h, c->tw2k, st);
+}
+
+// lass_front_end, lass_front_end_ragged and lass_front_end_windows behind their argument checks: x0 is (nbr, B, Tp, fcrop)
+static int front_end(lass_ctx* c, const float* wav, const ClipForm& cf, float* mag, float* cos_out, float* sin_out, float* x0,
+                     void* stream) {
+    const int T = 1 + cf.L / LASS_HOP, Tp = (T + 31) / 32 * 32;
+    float* x0k[kMaxBranches];
+    for (int k = 0; k < c->g.nbr; ++k) x0k[k] = x0 + (size_t)k * cf.B * Tp * c->g.fcrop;
+    HIP_TRY(c, launch_front_end(c, wav, cf, x0k, mag, cos_out, sin_out, (hipStream_t)stream));
+    return 0;
+}
+
 int lass_front_end(lass_ctx* c, const float* wav, int B, int L, float* mag, float* cos_out, float* sin_out, float* x0,
                    void* stream) {
     int r = check_ready(c);
     if (r) return r;
-    const Geometry& g = c->g;
-    if (!wav || !x0 || B <= 0 || L <= g.nfft / 2) return fail(c, LASS_ERR_ARG, "lass_front_end: bad argument");
-    const int T = 1 + L / LASS_HOP, Tp = (T + 31) / 32 * 32;
-    StftBranch br[kMaxBranches];
-    for (int k = 0; k < g.nbr; ++k) {  // x0 (nbr, B, Tp, fcrop); mag / cos / sin of the mask branch
-        br[k].wlen = g.wins[k];
-        br[k].x0 = x0 + (size_t)k * B * Tp * g.fcrop;
-        if (k == g.mask_br) { br[k].mag = mag; br[k].cosv = cos_out; br[k].sinv = sin_out; }
-    }
-    HIP_TRY(c, lass_launch_stft2(wav, B, L, g.nfft, LASS_HOP, T, Tp, g.nbr, br, g.magphase_sem, c->bn0_s, c->bn0_h,
-                                 c->tw2k, (hipStream_t)stream));
-    return 0;
+    if (!wav || !x0 || B <= 0 || L <= c->g.nfft / 2) return fail(c, LASS_ERR_ARG, "lass_front_end: bad argument");
+    return front_end(c, wav, ClipForm{B, L}, mag, cos_out, sin_out, x0, stream);
 }
 
 int lass_front_end_ragged(lass_ctx* c, const float* wav, const int* lengths, int B, int L, float* mag, float* cos_out,
                           float* sin_out, float* x0, void* stream) {
     int r = check_ready(c);
     if (r) return r;
-    const Geometry& g = c->g;
-    if (!wav || !lengths || !x0 || B <= 0 || L <= g.nfft / 2) return fail(c, LASS_ERR_ARG, "lass_front_end_ragged: bad argument");
-    const int T = 1 + L / LASS_HOP, Tp = (T + 31) / 32 * 32;
-    StftBranch br[kMaxBranches];
-    for (int k = 0; k < g.nbr; ++k) {  // as lass_front_end
-        br[k].wlen = g.wins[k];
-        br[k].x0 = x0 + (size_t)k * B * Tp * g.fcrop;
-        if (k == g.mask_br) { br[k].mag = mag; br[k].cosv = cos_out; br[k].sinv = sin_out; }
-    }
-    HIP_TRY(c, lass_launch_stft2_ragged(wav, lengths, B, L, g.nfft, LASS_HOP, T, Tp, g.nbr, br, g.magphase_sem, c->bn0_s,
-                                        c->bn0_h, c->tw2k, (hipStream_t)stream));
-    return 0;
+    if (!wav || !lengths || !x0 || B <= 0 || L <= c->g.nfft / 2) return fail(c, LASS_ERR_ARG, "lass_front_end_ragged: bad argument");
+    return front_end(c, wav, ClipForm{B, L, lengths}, mag, cos_out, sin_out, x0, stream);
 }
 
 int lass_istft_ragged(lass_ctx* c, const float* real, const float* imag, const int* lengths, int B, int T, int L, int n_fft,
@@ -1421,8 +1426,8 @@ int lass_istft_ragged(lass_ctx* c, const float* real, const float* imag, const i
         T != 1 + L / LASS_HOP || win_length < 32 || win_length > n_fft || (2048 % win_length) != 0)
         return fail(c, LASS_ERR_ARG, "lass_istft_ragged: bad argument (T = 1 + L/160 frames per clip, L > n_fft/2)");
     if (int r = use_device(c)) return r;
-    HIP_TRY(c, lass_launch_istft2_ragged(real, imag, lengths, B, T, L, n_fft, win_length, LASS_HOP, c->tw2k, wav,
-                                         (hipStream_t)stream));
+    HIP_TRY(c, lass_launch_istft2(real, imag, ClipForm{B, L, lengths}, T, n_fft, win_length, LASS_HOP, c->tw2k, wav,
+                                  (hipStream_t)stream));
     return 0;
 }
 
@@ -1430,19 +1435,9 @@ int lass_front_end_windows(lass_ctx* c, const float* recording, int64_t total, c
                            float* cos_out, float* sin_out, float* x0, void* stream) {
     int r = check_ready(c);
     if (r) return r;
-    const Geometry& g = c->g;
-    if (!recording || !starts || !x0 || B <= 0 || W <= g.nfft / 2 || total < W)
+    if (!recording || !starts || !x0 || B <= 0 || W <= c->g.nfft / 2 || total < W)
         return fail(c, LASS_ERR_ARG, "lass_front_end_windows: bad argument (n_fft/2 < W <= total)");
-    const int T = 1 + W / LASS_HOP, Tp = (T + 31) / 32 * 32;
-    StftBranch br[kMaxBranches];
-    for (int k = 0; k < g.nbr; ++k) {  // as lass_front_end
-        br[k].wlen = g.wins[k];
-        br[k].x0 = x0 + (size_t)k * B * Tp * g.fcrop;
-        if (k == g.mask_br) { br[k].mag = mag; br[k].cosv = cos_out; br[k].sinv = sin_out; }
-    }
-    HIP_TRY(c, lass_launch_stft2_windows(recording, total, starts, B, W, g.nfft, LASS_HOP, T, Tp, g.nbr, br, g.magphase_sem, c->bn0_s,
-                                         c->bn0_h, c->tw2k, (hipStream_t)stream));
-    return 0;
+    return front_end(c, recording, ClipForm{B, W, nullptr, starts, nullptr, total}, mag, cos_out, sin_out, x0, stream);
 }
 
 int lass_istft_windows(lass_ctx* c, const float* real, const float* imag, const int64_t* starts, const int* keep, int64_t total,
@@ -1451,8 +1446,8 @@ int lass_istft_windows(lass_ctx* c, const float* real, const float* imag, const 
         total < W || T != 1 + W / LASS_HOP || win_length < 32 || win_length > n_fft || (2048 % win_length) != 0)
         return fail(c, LASS_ERR_ARG, "lass_istft_windows: bad argument (T = 1 + W/160 frames per window, n_fft/2 < W <= total)");
     if (int r = use_device(c)) return r;
-    HIP_TRY(c, lass_launch_istft2_windows(real, imag, starts, keep, total, B, T, W, n_fft, win_length, LASS_HOP, c->tw2k, out,
-                                          (hipStream_t)stream));
+    HIP_TRY(c, lass_launch_istft2(real, imag, ClipForm{B, W, nullptr, starts, keep, total}, T, n_fft, win_length, LASS_HOP,
+                                  c->tw2k, out, (hipStream_t)stream));
     return 0;
 }
 
@@ -1598,19 +1593,12 @@ struct Components {
     const float* sinv;
 };
 
-// lass_separate_windows: B windows of L samples of ONE row of `total` samples (`mixture`), their kept parts stored into one row of
-// `total` samples (`out`); see stft.hip
-struct WindowArgs {
-    const int64_t* starts;  // device (B)
-    const int* keep;        // device (2B)
-    int64_t total;
-};
-
-// lengths: nullptr, or one length per clip (device): the two ends of the network then run their per-clip-length forms
-// win: nullptr, or the window form: the two ends read and write windows of one long row (never together with lengths)
+// cf: the clips of the call (kernels.h) - B rows of L samples, dense or with a length per clip, or B windows of L samples of ONE
+// row of cf.total samples (`mixture`), their kept parts stored into one row of as many samples (`out`).  The two ends of the
+// network run in cf's form; everything between them sees B images of (Tp, fcrop) whatever the form.
 static int separate_impl(lass_ctx* c, const float* mixture, const Components* comp, const float* condition, float* out,
-                         int B, int L, void* workspace, size_t workspace_bytes, void* stream, const char* who,
-                         const int* lengths = nullptr, const WindowArgs* win = nullptr) {
+                         const ClipForm& cf, void* workspace, size_t workspace_bytes, void* stream, const char* who) {
+    const int B = cf.B, L = cf.L;
     int r = check_ready(c);
     if (r) return r;
     const Geometry& g = c->g;
@@ -1637,21 +1625,9 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
     const float *mag_m = F(pl.mag), *cos_m = F(pl.cosv), *sin_m = F(pl.sinv);  // of the mask branch
     if (mixture) {
         ProfScope ps(c, st, P_STFT);
-        StftBranch br[kMaxBranches];
-        for (int k = 0; k < nbr; ++k) {
-            br[k].wlen = g.wins[k];
-            br[k].x0 = F(pl.x0[k]);
-            if (k == g.mask_br) { br[k].mag = F(pl.mag); br[k].cosv = F(pl.cosv); br[k].sinv = F(pl.sinv); }
-        }
-        if (win)
-            HIP_TRY(c, lass_launch_stft2_windows(mixture, win->total, win->starts, B, L, g.nfft, LASS_HOP, T, Tp, nbr, br,
-                                                 g.magphase_sem, c->bn0_s, c->bn0_h, c->tw2k, st));
-        else if (lengths)
-            HIP_TRY(c, lass_launch_stft2_ragged(mixture, lengths, B, L, g.nfft, LASS_HOP, T, Tp, nbr, br, g.magphase_sem,
-                                                c->bn0_s, c->bn0_h, c->tw2k, st));
-        else
-            HIP_TRY(c, lass_launch_stft2(mixture, B, L, g.nfft, LASS_HOP, T, Tp, nbr, br, g.magphase_sem, c->bn0_s, c->bn0_h,
-                                         c->tw2k, st));
+        float* x0k[kMaxBranches];
+        for (int k = 0; k < nbr; ++k) x0k[k] = F(pl.x0[k]);
+        HIP_TRY(c, launch_front_end(c, mixture, cf, x0k, F(pl.mag), F(pl.cosv), F(pl.sinv), st));
     } else {
         ProfScope ps(c, st, P_STFT);
         for (int k = 0; k < nbr; ++k) {
@@ -1771,28 +1747,33 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
     }
     {
         ProfScope ps(c, st, P_ISTFT);
-        if (win)
-            HIP_TRY(c, lass_launch_istft2_windows(F(pl.oreal), F(pl.oimag), win->starts, win->keep, win->total, B, T, L, g.nfft,
-                                                  g.wins[g.mask_br], LASS_HOP, c->tw2k, out, st));
-        else if (lengths)
-            HIP_TRY(c, lass_launch_istft2_ragged(F(pl.oreal), F(pl.oimag), lengths, B, T, L, g.nfft, g.wins[g.mask_br], LASS_HOP,
-                                                 c->tw2k, out, st));
-        else
-            HIP_TRY(c, lass_launch_istft2(F(pl.oreal), F(pl.oimag), B, T, L, g.nfft, g.wins[g.mask_br], LASS_HOP, c->tw2k, out, st));
+        HIP_TRY(c, lass_launch_istft2(F(pl.oreal), F(pl.oimag), cf, T, g.nfft, g.wins[g.mask_br], LASS_HOP, c->tw2k, out, st));
     }
     return 0;
 }
 
 // lass_separate's launches, whole or as two overlapping half-batches (lass_ctx::split_batch).  Capture-safe: under stream
 // capture the event pair makes `s2` a parallel branch of the same graph.
-static int separate_any(lass_ctx* c, const float* mixture, const int* lengths, const float* condition, float* out, int B, int L,
-                        void* workspace, size_t workspace_bytes, hipStream_t stream, bool capturing, const char* who,
-                        const WindowArgs* win = nullptr) {
+// Clips [h, B) of cf as a call of their own.  *row: how far into the mixture and the output their rows begin - the window form's
+// second half reads its own entries of the index arrays and the SAME two long rows.
+static ClipForm upper_clips(const ClipForm& cf, int h, size_t* row) {
+    ClipForm u = cf;
+    u.B = cf.B - h;
+    if (cf.lengths) u.lengths = cf.lengths + h;
+    if (cf.starts) u.starts = cf.starts + h;
+    if (cf.keep) u.keep = cf.keep + 2 * h;
+    *row = cf.starts ? 0 : (size_t)h * cf.L;
+    return u;
+}
+
+static int separate_any(lass_ctx* c, const float* mixture, const float* condition, float* out, const ClipForm& cf, void* workspace,
+                        size_t workspace_bytes, hipStream_t stream, bool capturing, const char* who) {
+    const int B = cf.B, L = cf.L;
     Plan ph;
     if (!c->finalized || !split_halves(c, B) || !mixture || !condition || !out || !workspace || (!capturing && c->split_batch < 2) ||
         make_plan(c, B / 2, L, &ph) || 2 * ((ph.total + 255) / 256 * 256) > workspace_bytes) {
         c->last_split[{B, L}] = false;
-        return separate_impl(c, mixture, nullptr, condition, out, B, L, workspace, workspace_bytes, stream, who, lengths, win);
+        return separate_impl(c, mixture, nullptr, condition, out, cf, workspace, workspace_bytes, stream, who);
     }
     c->last_split[{B, L}] = true;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1805,13 +1786,13 @@ static int separate_any(lass_ctx* c, const float* mixture, const int* lengths, c
     const size_t half_ws = (ph.total + 255) / 256 * 256;
     HIP_TRY(c, hipEventRecord(c->ev_fork, stream));
     HIP_TRY(c, hipStreamWaitEvent(c->s2, c->ev_fork, 0));
-    // the window form's second half reads its own entries of the index arrays and the SAME two long rows
-    const WindowArgs win2 = win ? WindowArgs{win->starts + h, win->keep + 2 * h, win->total} : WindowArgs{};
-    const size_t row2 = win ? 0 : (size_t)h * L;
-    int r = separate_impl(c, mixture, nullptr, condition, out, h, L, workspace, half_ws, stream, who, lengths, win);
-    const int r2 = separate_impl(c, mixture + row2, nullptr, condition + (size_t)h * LASS_COND, out + row2, h, L,
-                                 (char*)workspace + half_ws, half_ws, c->s2, who, lengths ? lengths + h : nullptr,
-                                 win ? &win2 : nullptr);
+    ClipForm lower = cf;
+    lower.B = h;
+    size_t row2;
+    const ClipForm upper = upper_clips(cf, h, &row2);  // (split_halves: B is even)
+    int r = separate_impl(c, mixture, nullptr, condition, out, lower, workspace, half_ws, stream, who);
+    const int r2 = separate_impl(c, mixture + row2, nullptr, condition + (size_t)h * LASS_COND, out + row2, upper,
+                                 (char*)workspace + half_ws, half_ws, c->s2, who);
     if (!r) r = r2;
     // the join is recorded even after a failure: a capturing stream must get its branch back
     HIP_TRY(c, hipEventRecord(c->ev_join, c->s2));
@@ -1819,18 +1800,18 @@ static int separate_any(lass_ctx* c, const float* mixture, const int* lengths, c
     return r;
 }
 
-// lass_separate (lengths == nullptr), lass_separate_ragged and lass_separate_windows (win): one call, eager or through the graph
-// cache
-static int separate_call(lass_ctx* c, const float* mixture, const int* lengths, const float* condition, float* out, int B, int L,
-                         void* workspace, size_t workspace_bytes, void* stream, const char* who, const WindowArgs* win = nullptr) {
+// lass_separate, lass_separate_ragged and lass_separate_windows (cf says which): one call, eager or through the graph cache
+static int separate_call(lass_ctx* c, const float* mixture, const float* condition, float* out, const ClipForm& cf, void* workspace,
+                         size_t workspace_bytes, void* stream, const char* who) {
+    const int B = cf.B, L = cf.L;
     if (!mixture) return fail(c, LASS_ERR_ARG, std::string(who) + ": null pointer");
     // Graph replay: the third call that presents the same (pointers, shape) key is captured once (on an internal stream; the
     // caller's may be the legacy default stream, which cannot be captured) and replayed from then on.  Callers that hand
     // over fresh buffers every time simply stay on the eager path; so does a profiled context.
     lass_ctx::GraphKey key;
-    key.mix = mixture; key.cond = condition; key.out = out; key.ws = workspace; key.lens = lengths; key.B = B; key.L = L;
+    key.mix = mixture; key.cond = condition; key.out = out; key.ws = workspace; key.lens = cf.lengths; key.B = B; key.L = L;
     key.gen = c->gen;
-    if (win) { key.starts = win->starts; key.keep = win->keep; key.total = win->total; }
+    key.starts = cf.starts; key.keep = cf.keep; key.total = cf.total;
     if (c->use_graph && !c->profiling && c->finalized) {
         ++c->g_tick;
         lass_ctx::GraphEntry* slot = nullptr;
@@ -1871,7 +1852,7 @@ static int separate_call(lass_ctx* c, const float* mixture, const int* lengths, 
                 Plan pl0;
                 if (!condition || !out || !workspace || make_plan(c, B, L, &pl0) || workspace_bytes < pl0.total ||
                     ((uintptr_t)workspace & 255) != 0)
-                    return separate_any(c, mixture, lengths, condition, out, B, L, workspace, workspace_bytes, (hipStream_t)stream, false, who, win);
+                    return separate_any(c, mixture, condition, out, cf, workspace, workspace_bytes, (hipStream_t)stream, false, who);
                 slot->need = pl0.total;
                 if (split_halves(c, B)) {  // (checked again at capture time by separate_any: smaller workspaces run unsplit)
                     Plan ph0;
@@ -1883,7 +1864,7 @@ static int separate_call(lass_ctx* c, const float* mixture, const int* lengths, 
             if (!c->g_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->g_stream, hipStreamNonBlocking));
             bool ok = false;
             if (hipStreamBeginCapture(c->g_stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                const int r = separate_any(c, mixture, lengths, condition, out, B, L, workspace, workspace_bytes, c->g_stream, true, who, win);
+                const int r = separate_any(c, mixture, condition, out, cf, workspace, workspace_bytes, c->g_stream, true, who);
                 hipGraph_t graph = nullptr;
                 const hipError_t e = hipStreamEndCapture(c->g_stream, &graph);  // always ends the capture, also after a failure
                 if (r == 0 && e == hipSuccess && graph && hipGraphInstantiate(&slot->exec, graph, nullptr, nullptr, 0) == hipSuccess) {
@@ -1906,13 +1887,13 @@ static int separate_call(lass_ctx* c, const float* mixture, const int* lengths, 
             c->err.clear();
         }
     }
-    return separate_any(c, mixture, lengths, condition, out, B, L, workspace, workspace_bytes, (hipStream_t)stream, false, who, win);
+    return separate_any(c, mixture, condition, out, cf, workspace, workspace_bytes, (hipStream_t)stream, false, who);
 }
 
 int lass_separate(lass_ctx* c, const float* mixture, const float* condition, float* out, int B, int L, void* workspace,
                   size_t workspace_bytes, void* stream) {
     if (!c) return LASS_ERR_ARG;
-    return separate_call(c, mixture, nullptr, condition, out, B, L, workspace, workspace_bytes, stream, "lass_separate");
+    return separate_call(c, mixture, condition, out, ClipForm{B, L}, workspace, workspace_bytes, stream, "lass_separate");
 }
 
 int lass_ragged_bucket(const lass_ctx* c, int L, int* lo, int* hi) {
@@ -1927,7 +1908,7 @@ int lass_separate_ragged(lass_ctx* c, const float* mixture, const int* lengths, 
                          void* workspace, size_t workspace_bytes, void* stream) {
     if (!c) return LASS_ERR_ARG;
     if (!lengths) return fail(c, LASS_ERR_ARG, "lass_separate_ragged: null lengths");
-    return separate_call(c, mixture, lengths, condition, out, B, L, workspace, workspace_bytes, stream, "lass_separate_ragged");
+    return separate_call(c, mixture, condition, out, ClipForm{B, L, lengths}, workspace, workspace_bytes, stream, "lass_separate_ragged");
 }
 
 int lass_separate_windows(lass_ctx* c, const float* recording, int64_t total, const int64_t* starts, const int* keep,
@@ -1941,8 +1922,8 @@ int lass_separate_windows(lass_ctx* c, const float* recording, int64_t total, co
     if (total < W) return fail(c, LASS_ERR_ARG, who + ": the recording is shorter than one window (total < W)");
     const uintptr_t r0 = (uintptr_t)recording, o0 = (uintptr_t)out, bytes = (uintptr_t)total * sizeof(float);
     if (r0 < o0 + bytes && o0 < r0 + bytes) return fail(c, LASS_ERR_ARG, who + ": recording and out overlap");
-    const WindowArgs win{starts, keep, total};
-    return separate_call(c, recording, nullptr, condition, out, B, W, workspace, workspace_bytes, stream, who.c_str(), &win);
+    return separate_call(c, recording, condition, out, ClipForm{B, W, nullptr, starts, keep, total}, workspace, workspace_bytes, stream,
+                         who.c_str());
 }
 
 int lass_set_graph_replay(lass_ctx* c, int enabled) {
@@ -2008,7 +1989,7 @@ int lass_separate_components(lass_ctx* c, const float* const* mag, const float* 
     Components comp;
     for (int k = 0; k < kMaxBranches; ++k) comp.mag[k] = k < c->g.nbr ? mag[k] : nullptr;
     comp.cosv = cos_mask; comp.sinv = sin_mask;
-    return separate_impl(c, nullptr, &comp, condition, out, B, L, workspace, workspace_bytes, stream,
+    return separate_impl(c, nullptr, &comp, condition, out, ClipForm{B, L}, workspace, workspace_bytes, stream,
                          "lass_separate_components");
 }
 

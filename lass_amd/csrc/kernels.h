@@ -211,29 +211,27 @@ struct StftBranch {
     int wlen = 0;
     float *mag = nullptr, *cosv = nullptr, *sinv = nullptr, *real = nullptr, *imag = nullptr, *x0 = nullptr;
 };
-hipError_t lass_launch_stft2(const float* wav, int B, int L, int n_fft, int hop, int T, int Tpad, int nbr,
+// The clips of one launch of the two kernels below (host side; stft.hip turns it into the kernel's form when it instantiates):
+//   dense   (lengths == starts == nullptr): clip b is wav[b * L, (b + 1) * L), T = 1 + L / hop frames.
+//   ragged  (lengths: device int32 (B), clamped into the 32-frame bucket of L by the kernels): the same rows, Tpad = 32 *
+//           ceil(T / 32).  Beyond a clip's own frames x0 and the spectra are 0; beyond its own samples the waveform is 0.
+//   windows (starts: device int64 (B); lass_separate_windows): window b is wav[starts[b], starts[b] + L) of ONE row of `total`
+//           samples, and of its L output samples only keep[2b] <= n < keep[2b+1] (device int32 (2B), needed by the iSTFT alone)
+//           are stored, at out[starts[b] + n].  The kernels clamp starts into [0, total - L], lo into [0, L], hi into [lo, L].
+struct ClipForm {
+    int B = 0;
+    int L = 0;  // samples per row, or per window
+    const int* lengths = nullptr;
+    const int64_t* starts = nullptr;
+    const int* keep = nullptr;
+    int64_t total = 0;
+};
+hipError_t lass_launch_stft2(const float* wav, const ClipForm& cf, int n_fft, int hop, int T, int Tpad, int nbr,
                              const StftBranch* br, int magphase_sem, const float* s0, const float* h0,
                              const float2* tw2k, hipStream_t stream);
 // Fused inverse STFT (inverse transforms + overlap-add + envelope + trim in one kernel, no frame scratch).
-hipError_t lass_launch_istft2(const float* real, const float* imag, int B, int T, int L, int n_fft, int wlen, int hop,
+hipError_t lass_launch_istft2(const float* real, const float* imag, const ClipForm& cf, int T, int n_fft, int wlen, int hop,
                               const float2* tw2k, float* wav, hipStream_t stream);
-// The same two kernels with a length per clip (lengths: device int32 (B), clamped into the 32-frame bucket of L by the kernels):
-// rows L samples / T = 1 + L / hop frames apart, Tpad = 32 * ceil(T / 32).  Beyond a clip's own frames x0 and the spectra are 0;
-// beyond its own samples the waveform is 0.
-hipError_t lass_launch_stft2_ragged(const float* wav, const int* lengths, int B, int L, int n_fft, int hop, int T, int Tpad,
-                                    int nbr, const StftBranch* br, int magphase_sem, const float* s0, const float* h0,
-                                    const float2* tw2k, hipStream_t stream);
-hipError_t lass_launch_istft2_ragged(const float* real, const float* imag, const int* lengths, int B, int T, int L, int n_fft,
-                                     int wlen, int hop, const float2* tw2k, float* wav, hipStream_t stream);
-// The same two kernels for windows of one long row (lass_separate_windows): window b is recording[starts[b], starts[b] + W) with
-// T = 1 + W / hop frames, and of its W output samples only keep[2b] <= n < keep[2b+1] are stored, at out[starts[b] + n].  starts:
-// device int64 (B), keep: device int32 (2B); the kernels clamp starts into [0, total - W], lo into [0, W], hi into [lo, W].
-hipError_t lass_launch_stft2_windows(const float* recording, int64_t total, const int64_t* starts, int B, int W, int n_fft, int hop,
-                                     int T, int Tpad, int nbr, const StftBranch* br, int magphase_sem, const float* s0,
-                                     const float* h0, const float2* tw2k, hipStream_t stream);
-hipError_t lass_launch_istft2_windows(const float* real, const float* imag, const int64_t* starts, const int* keep, int64_t total,
-                                      int B, int T, int W, int n_fft, int wlen, int hop, const float2* tw2k, float* out,
-                                      hipStream_t stream);
 
 // ---- misc.hip -----------------------------------------------------------------------------------------------------
 // film[b][j] = dot(cond[b], Wf[j]) + bf[j] (+ base[j] if base)   for j < n

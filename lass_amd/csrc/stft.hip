@@ -25,100 +25,11 @@ __device__ __forceinline__ float2 ctw(float2 u, float2 w) {
     return make_float2(u.x * w.x + u.y * w.y, u.y * w.x - u.x * w.y);
 }
 
-// N-point complex forward FFT for N in {256, 512, 1024, 2048}: radix-4 Stockham passes plus one radix-2 pass when log2 N
-// is odd; 256 threads, each taking (N/4)/256 butterflies per pass (or idling).  tw2k[m] = (cos, sin)(2*pi*m/2048).
-template <int N>
-__device__ __forceinline__ float2* fft_fwd(float2* a, float2* b, const float2* tw2k, int tid) {
-    constexpr int LOG2 = N == 256 ? 8 : N == 512 ? 9 : N == 1024 ? 10 : 11;
-    constexpr int NP4 = LOG2 / 2;
-    constexpr int TWS = 2048 / N;  // stride into the 2048-entry table
-    float2* src = a;
-    float2* dst = b;
-#pragma unroll
-    for (int pass = 0; pass < NP4; ++pass) {
-        const int p = 1 << (2 * pass);
-        for (int i = tid; i < N / 4; i += 256) {
-            const int k = i & (p - 1);
-            const int j = ((i - k) << 2) + k;
-            const int ts = (N / 4 / p) * TWS;
-            float2 u0 = src[i], u1 = src[i + N / 4], u2 = src[i + N / 2], u3 = src[i + 3 * N / 4];
-            if (pass > 0) {
-                u1 = ctw<false>(u1, tw2k[k * ts]);
-                u2 = ctw<false>(u2, tw2k[2 * k * ts]);
-                u3 = ctw<false>(u3, tw2k[3 * k * ts]);
-            }
-            const float2 a0 = cadd(u0, u2), a1 = csub(u0, u2), a2 = cadd(u1, u3);
-            float2 a3 = csub(u1, u3);
-            a3 = make_float2(a3.y, -a3.x);  // * (-i)
-            dst[j] = cadd(a0, a2);
-            dst[j + p] = cadd(a1, a3);
-            dst[j + 2 * p] = csub(a0, a2);
-            dst[j + 3 * p] = csub(a1, a3);
-        }
-        __syncthreads();
-        float2* t = src; src = dst; dst = t;
-    }
-    if (LOG2 & 1) {  // final radix-2 pass, p = N/2
-        for (int i = tid; i < N / 2; i += 256) {
-            const float2 u0 = src[i];
-            const float2 u1 = ctw<false>(src[i + N / 2], tw2k[i * TWS]);
-            dst[i] = cadd(u0, u1);
-            dst[i + N / 2] = csub(u0, u1);
-        }
-        __syncthreads();
-        float2* t = src; src = dst; dst = t;
-    }
-    return src;  // natural-order spectrum
-}
-
-struct MultiStftArgs {
-    int nwin;
-    int n_fft[LASS_MAX_STFT_WINDOWS];
-    float* mag[LASS_MAX_STFT_WINDOWS];
-    float* cosv[LASS_MAX_STFT_WINDOWS];
-    float* sinv[LASS_MAX_STFT_WINDOWS];
-};
-
-template <int N>
-__device__ __forceinline__ void stft_frame(const float* __restrict__ w, int L, int hop, int t, size_t row,
-                                           const float2* TW, float2* A, float2* Bf, float* __restrict__ mag,
-                                           float* __restrict__ cosv, float* __restrict__ sinv, int tid) {
-    constexpr int TWS = 2048 / N;
-    for (int idx = tid; idx < N; idx += 256) {
-        int n = t * hop + idx - N / 2;  // centre=True, reflect padding of n_fft/2
-        if (n < 0) n = -n;
-        if (n >= L) n = 2 * (L - 1) - n;
-        const float wn = 0.5f - 0.5f * TW[idx * TWS].x;  // periodic Hann
-        A[idx] = make_float2(w[n] * wn, 0.f);
-    }
-    __syncthreads();
-    const float2* X = fft_fwd<N>(A, Bf, TW, tid);
-    for (int f = tid; f <= N / 2; f += 256) {
-        const float re = X[f].x, im = X[f].y;
-        const float m = sqrtf(re * re + im * im);
-        const float den = fmaxf(m, 1e-10f);  // torchlibrosa magphase: the clamp is on |X| (precompute_stfts.py:51)
-        mag[row + f] = m;
-        cosv[row + f] = re / den;
-        sinv[row + f] = im / den;
-    }
-}
-
-// One launch for all analysis windows (they share the hop, hence T): blockIdx.z selects the window.
-__global__ __launch_bounds__(256) void multi_stft_kernel(const float* __restrict__ wav, int L, int T, int hop,
-                                                         const float2* __restrict__ tw2k, MultiStftArgs a) {
-    __shared__ float2 A[2048], Bf[2048], TW[2048];
-    const int t = blockIdx.x, b = blockIdx.y, z = blockIdx.z, tid = threadIdx.x;
-    for (int i = tid; i < 2048; i += 256) TW[i] = tw2k[i];
-    __syncthreads();
-    const int N = a.n_fft[z];
-    const float* w = wav + (size_t)b * L;
-    const size_t row = ((size_t)b * T + t) * (N / 2 + 1);
-    switch (N) {
-        case 256: stft_frame<256>(w, L, hop, t, row, TW, A, Bf, a.mag[z], a.cosv[z], a.sinv[z], tid); break;
-        case 512: stft_frame<512>(w, L, hop, t, row, TW, A, Bf, a.mag[z], a.cosv[z], a.sinv[z], tid); break;
-        case 1024: stft_frame<1024>(w, L, hop, t, row, TW, A, Bf, a.mag[z], a.cosv[z], a.sinv[z], tid); break;
-        default: stft_frame<2048>(w, L, hop, t, row, TW, A, Bf, a.mag[z], a.cosv[z], a.sinv[z], tid); break;
-    }
+// centre=True: sample n of a clip of L samples under reflect padding of n_fft/2 (< L) at either end
+__device__ __forceinline__ int reflect(int n, int L) {
+    if (n < 0) n = -n;
+    if (n >= L) n = 2 * (L - 1) - n;
+    return n;
 }
 
 #ifdef LASS_STFT_DBG
@@ -133,16 +44,13 @@ __device__ float2* g_stft_dbg = nullptr;
 #define STFT_DBG_REC(kind, slot, val)
 #endif
 
-// ---- generic pair-packed transforms (n_fft in {1024, 2048}, window length <= n_fft) ---------------------------------
-// A real frame needs only half a complex transform: two frames ride in one complex FFT (frame a in the real part, frame b
-// in the imaginary part) and are separated by the Hermitian symmetry of their spectra:
-//     Z = FFT(xa + i xb):   Xa[k] = (Z[k] + conj(Z[N-k])) / 2,   Xb[k] = (Z[k] - conj(Z[N-k])) / (2i)
-// and the other way round for the inverse.  Twiddles and the periodic Hann window come from the 2048-entry table.
+// N-point complex FFT, forward or inverse, for N in {256, 512, 1024, 2048}: radix-4 Stockham passes plus one radix-2 pass
+// when log2 N is odd; 256 threads, each taking (N/4)/256 butterflies per pass (or idling).  tw2k[m] = (cos, sin)(2*pi*m/2048).
 template <int N, bool INV>
 __device__ __forceinline__ float2* fft_c(float2* a, float2* b, const float2* tw2k, int tid, float2* dbg = nullptr) {
-    constexpr int LOG2 = N == 1024 ? 10 : 11;
+    constexpr int LOG2 = N == 256 ? 8 : N == 512 ? 9 : N == 1024 ? 10 : 11;
     constexpr int NP4 = LOG2 / 2;
-    constexpr int TWS = 2048 / N;
+    constexpr int TWS = 2048 / N;  // stride into the 2048-entry table
     float2* src = a;
     float2* dst = b;
 #pragma unroll
@@ -189,6 +97,121 @@ __device__ __forceinline__ float2* fft_c(float2* a, float2* b, const float2* tw2
     return src;  // natural order
 }
 
+struct MultiStftArgs {
+    int nwin;
+    int n_fft[LASS_MAX_STFT_WINDOWS];
+    float* mag[LASS_MAX_STFT_WINDOWS];
+    float* cosv[LASS_MAX_STFT_WINDOWS];
+    float* sinv[LASS_MAX_STFT_WINDOWS];
+};
+
+template <int N>
+__device__ __forceinline__ void stft_frame(const float* __restrict__ w, int L, int hop, int t, size_t row,
+                                           const float2* TW, float2* A, float2* Bf, float* __restrict__ mag,
+                                           float* __restrict__ cosv, float* __restrict__ sinv, int tid) {
+    constexpr int TWS = 2048 / N;
+    for (int idx = tid; idx < N; idx += 256) {
+        const int n = reflect(t * hop + idx - N / 2, L);
+        const float wn = 0.5f - 0.5f * TW[idx * TWS].x;  // periodic Hann
+        A[idx] = make_float2(w[n] * wn, 0.f);
+    }
+    __syncthreads();
+    const float2* X = fft_c<N, false>(A, Bf, TW, tid);
+    for (int f = tid; f <= N / 2; f += 256) {
+        const float re = X[f].x, im = X[f].y;
+        const float m = sqrtf(re * re + im * im);
+        const float den = fmaxf(m, 1e-10f);  // torchlibrosa magphase: the clamp is on |X| (precompute_stfts.py:51)
+        mag[row + f] = m;
+        cosv[row + f] = re / den;
+        sinv[row + f] = im / den;
+    }
+}
+
+// One launch for all analysis windows (they share the hop, hence T): blockIdx.z selects the window.
+__global__ __launch_bounds__(256) void multi_stft_kernel(const float* __restrict__ wav, int L, int T, int hop,
+                                                         const float2* __restrict__ tw2k, MultiStftArgs a) {
+    __shared__ float2 A[2048], Bf[2048], TW[2048];
+    const int t = blockIdx.x, b = blockIdx.y, z = blockIdx.z, tid = threadIdx.x;
+    for (int i = tid; i < 2048; i += 256) TW[i] = tw2k[i];
+    __syncthreads();
+    const int N = a.n_fft[z];
+    const float* w = wav + (size_t)b * L;
+    const size_t row = ((size_t)b * T + t) * (N / 2 + 1);
+    switch (N) {
+        case 256: stft_frame<256>(w, L, hop, t, row, TW, A, Bf, a.mag[z], a.cosv[z], a.sinv[z], tid); break;
+        case 512: stft_frame<512>(w, L, hop, t, row, TW, A, Bf, a.mag[z], a.cosv[z], a.sinv[z], tid); break;
+        case 1024: stft_frame<1024>(w, L, hop, t, row, TW, A, Bf, a.mag[z], a.cosv[z], a.sinv[z], tid); break;
+        default: stft_frame<2048>(w, L, hop, t, row, TW, A, Bf, a.mag[z], a.cosv[z], a.sinv[z], tid); break;
+    }
+}
+
+// ---- clip forms -----------------------------------------------------------------------------------------------------------
+// The two ends of the network, stft2_kernel and istft2_kernel below, are each ONE body.  What a launch's clips are is a type,
+// resolved when the kernel is instantiated, that answers the few questions in which the forms differ: where clip b's row is,
+// how many samples and frames it has, and which of its output samples the iSTFT stores.  Every form therefore runs the same
+// arithmetic in the same order, and a clip of any form is bit-identical to that clip run alone through the dense form.
+//   DenseClips  (lass_separate): rows L samples apart, every clip L samples and the launch's T frames long.
+//   RaggedClips (lass_separate_ragged): the same rows with a length per clip (`lengths`, device int32).  Clips whose lengths
+//       fall in one 32-frame bucket share every launch between the two ends: the U-Net sees a (Tpad, n_fft/2) image per clip
+//       whatever its length.  What differs per clip is where the reflect padding turns round, how many rows of x0 are real,
+//       and what the iSTFT overlap-adds and trims; beyond a clip's frames x0 and the spectra are 0, beyond its samples the
+//       waveform is 0.  `lo` is the smallest length of L's bucket: a length outside [lo, L] is clamped into it, so a wrong
+//       entry gives a wrong clip, never an access out of range.
+//   WindowClips (lass_separate_windows): window b is recording[s_b, s_b + W), a clip that starts at an arbitrary offset of ONE
+//       long row, and of its W output samples only [lo_b, hi_b) are stored, at the same offset of one long output row; s_b
+//       from `starts` (device int64), (lo_b, hi_b) from `keep` (device int32 pairs, read by the iSTFT alone).  Entries are
+//       clamped - s_b into [0, total - W], lo_b into [0, W], hi_b into [lo_b, W] - so a wrong entry gives wrong audio, never
+//       an access out of range.
+struct Kept { int lo, hi, zend; };  // of a clip's output row the iSTFT stores samples [lo, hi) and writes [hi, zend) as 0
+
+struct DenseClips {
+    int L;
+    static constexpr bool kShort = false;    // may a clip have fewer frames than the launch's T?
+    static constexpr bool kPartial = false;  // may a span of the iSTFT lie wholly outside what its clip stores?
+    template <class P> __device__ P* row(P* base, int b) const { return base + (size_t)b * L; }
+    __device__ int len(int) const { return L; }
+    __device__ int frames(int, int T, int) const { return T; }
+    __device__ Kept kept(int, int) const { return {0, L, L}; }
+};
+
+struct RaggedClips {
+    const int* __restrict__ lengths;
+    int lo, L;
+    static constexpr bool kShort = true, kPartial = true;
+    template <class P> __device__ P* row(P* base, int b) const { return base + (size_t)b * L; }
+    __device__ int len(int b) const {
+        const int v = lengths[b];
+        return v < lo ? lo : (v > L ? L : v);
+    }
+    __device__ int frames(int Lb, int, int hop) const { return 1 + Lb / hop; }
+    __device__ Kept kept(int, int Lb) const { return {0, Lb, L}; }
+};
+
+struct WindowClips {
+    const int64_t* __restrict__ starts;
+    const int* __restrict__ keep;
+    int64_t total;
+    int W;
+    static constexpr bool kShort = false, kPartial = true;  // (an empty keep meets no span)
+    template <class P> __device__ P* row(P* base, int b) const {
+        const int64_t v = starts[b], last = total - W;
+        return base + (v < 0 ? 0 : (v > last ? last : v));
+    }
+    __device__ int len(int) const { return W; }
+    __device__ int frames(int, int T, int) const { return T; }
+    __device__ Kept kept(int b, int) const {
+        int lo = keep[2 * b], hi = keep[2 * b + 1];
+        lo = lo < 0 ? 0 : (lo > W ? W : lo);
+        hi = hi < lo ? lo : (hi > W ? W : hi);
+        return {lo, hi, hi};
+    }
+};
+
+// ---- generic pair-packed transforms (n_fft in {1024, 2048}, window length <= n_fft) ---------------------------------
+// A real frame needs only half a complex transform: two frames ride in one complex FFT (frame a in the real part, frame b
+// in the imaginary part) and are separated by the Hermitian symmetry of their spectra:
+//     Z = FFT(xa + i xb):   Xa[k] = (Z[k] + conj(Z[N-k])) / 2,   Xb[k] = (Z[k] - conj(Z[N-k])) / (2i)
+// and the other way round for the inverse.  Twiddles and the periodic Hann window come from the 2048-entry table.
 struct Stft2Args {
     int nbr;
     int wlen[LASS_MAX_STFT_WINDOWS];
@@ -202,46 +225,59 @@ struct Stft2Args {
 
 // Centred, reflect-padded STFT of frames (2*blockIdx.x, 2*blockIdx.x + 1) of clip blockIdx.y for branch blockIdx.z
 // (periodic Hann of wlen samples zero-padded to N, centred), fused with magnitude / phase and the network-input prologue
-// x0 = bn0(mag) with T zero-padded to Tpad and the Nyquist bin dropped (resunet.py:533-552).
+// x0 = bn0(mag) with T zero-padded to Tpad and the Nyquist bin dropped (resunet.py:533-552).  Of a clip of Tb <= T frames,
+// rows Tb <= t < Tpad of x0 and rows Tb <= t < T of mag / cos / sin / real / imag are 0 (no such spectrum rows where the form
+// gives Tb = T), and nothing of the clip's row is read at or beyond its length.
 // MAGPHASE: torchlibrosa magphase (clamp on |X|, precompute_stfts.py:51) instead of base.py:83-88 (clamp on |X|^2).
-template <int N, bool MAGPHASE>
-__global__ __launch_bounds__(256) void stft2_kernel(const float* __restrict__ wav, int L, int hop, int T, int Tpad,
+template <int N, bool MAGPHASE, class Clips>
+__global__ __launch_bounds__(256) void stft2_kernel(const float* __restrict__ wav, Clips clips, int hop, int T, int Tpad,
                                                     const float2* __restrict__ tw2k, Stft2Args a,
                                                     const float* __restrict__ s0, const float* __restrict__ h0) {
     __shared__ float2 A[N], Bf[N], TW[2048];
     constexpr int NB = N / 2 + 1, FC = N / 2;
     const int ta = 2 * blockIdx.x, b = blockIdx.y, z = blockIdx.z, tid = threadIdx.x;
+    const int Lb = clips.len(b), Tb = clips.frames(Lb, T, hop);
     float* x0 = a.x0[z];
-    if (ta >= T) {  // rows T..Tpad-1 of the network input are zeros AFTER bn0
-        if (x0)
-            for (int r = 0; r < 2; ++r)
-                if (ta + r < Tpad)
-                    for (int f = tid; f < FC; f += 256) x0[((size_t)b * Tpad + ta + r) * FC + f] = 0.f;
+    // rows from `from` of this frame pair lie beyond the clip: zeros in the network input (AFTER bn0) and in the spectra
+    const auto zero_rows = [&](int from) {
+        for (int t = from; t < ta + 2; ++t) {
+            if (x0 && t < Tpad)
+                for (int f = tid; f < FC; f += 256) x0[((size_t)b * Tpad + t) * FC + f] = 0.f;
+            if (Clips::kShort && t < T) {
+                float *mag = a.mag[z], *cosv = a.cosv[z], *sinv = a.sinv[z], *real = a.real[z], *imag = a.imag[z];
+                for (int f = tid; f < NB; f += 256) {
+                    const size_t row = ((size_t)b * T + t) * NB + f;
+                    if (real) real[row] = 0.f;
+                    if (imag) imag[row] = 0.f;
+                    if (mag) mag[row] = 0.f;
+                    if (cosv) cosv[row] = 0.f;
+                    if (sinv) sinv[row] = 0.f;
+                }
+            }
+        }
+    };
+    if (ta >= Tb) {
+        zero_rows(ta);
         return;
     }
     for (int i = tid; i < 2048; i += 256) TW[i] = tw2k[i];
     __syncthreads();
     const int wlen = a.wlen[z], woff = (N - wlen) / 2, wstride = 2048 / wlen;
-    const float* w = wav + (size_t)b * L;
-    const bool have_b = ta + 1 < T;
+    const float* w = clips.row(wav, b);
+    const bool have_b = ta + 1 < Tb;
     for (int idx = tid; idx < N; idx += 256) {
         float2 v = make_float2(0.f, 0.f);
         const int j = idx - woff;
         if (j >= 0 && j < wlen) {
             const float wn = 0.5f - 0.5f * TW[j * wstride].x;  // periodic Hann of wlen
-            int n = ta * hop + idx - N / 2;                     // centre=True, reflect padding of n_fft/2
-            int n2 = n + hop;
-            if (n < 0) n = -n;
-            if (n >= L) n = 2 * (L - 1) - n;
-            if (n2 < 0) n2 = -n2;
-            if (n2 >= L) n2 = 2 * (L - 1) - n2;
-            v = make_float2(w[n] * wn, have_b ? w[n2] * wn : 0.f);
+            const int n = ta * hop + idx - N / 2;
+            v = make_float2(w[reflect(n, Lb)] * wn, have_b ? w[reflect(n + hop, Lb)] * wn : 0.f);
         }
         A[idx] = v;
     }
     __syncthreads();
 #ifdef LASS_STFT_DBG
-    float2* dbg = g_stft_dbg ? g_stft_dbg + (size_t)((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * (N == 1024 ? 5 : 5) * 3 * N : nullptr;
+    float2* dbg = g_stft_dbg ? g_stft_dbg + (size_t)((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 5 * 3 * N : nullptr;
     const float2* Z = fft_c<N, false>(A, Bf, TW, tid, dbg);
 #else
     const float2* Z = fft_c<N, false>(A, Bf, TW, tid);
@@ -272,25 +308,37 @@ __global__ __launch_bounds__(256) void stft2_kernel(const float* __restrict__ wa
             if (x0 && f < FC) x0[((size_t)b * Tpad + ta + r) * FC + f] = m * s0[f] + h0[f];
         }
     }
-    if (x0 && !have_b && ta + 1 < Tpad)
-        for (int f = tid; f < FC; f += 256) x0[((size_t)b * Tpad + ta + 1) * FC + f] = 0.f;
+    if (!have_b) zero_rows(ta + 1);
 }
 
 // Inverse STFT, fused: a workgroup owns SPAN consecutive samples of the (n_fft/2-padded) output, runs the inverse
-// transforms of every frame whose window reaches into that span (two frames per complex transform) and overlap-adds
-// them in LDS in ascending frame order, then divides by the window-sum-square envelope of the same frames (clamped at
-// 1e-11) and writes the trimmed samples [n_fft/2, n_fft/2 + L).  No frame scratch in HBM.
+// transforms of every frame of the clip whose window reaches into that span (two frames per complex transform) and
+// overlap-adds them in LDS in ascending frame order, then divides by the window-sum-square envelope of the same frames
+// (clamped at 1e-11) and writes the samples the form keeps, n_fft/2 trimmed (zeros where it says so: sums over a padded
+// ragged row gain only exact zeros).  No frame scratch in HBM.  A span that meets nothing its clip stores writes its zeros
+// and returns before it loads a twiddle: with a second of context either side of a five-second window that is two spans in
+// five.
 constexpr int ISTFT_SPAN = 16 * LASS_HOP;
 
-template <int N>
+template <int N, class Clips>
 __global__ __launch_bounds__(256) void istft2_kernel(const float* __restrict__ real, const float* __restrict__ imag,
-                                                     int T, int L, int hop, int wlen,
-                                                     const float2* __restrict__ tw2k, float* __restrict__ wav) {
+                                                     Clips clips, int T, int hop, int wlen,
+                                                     const float2* __restrict__ tw2k, float* __restrict__ out) {
     __shared__ float2 A[N], Bf[N], TW[2048];
     __shared__ float acc[ISTFT_SPAN], env[ISTFT_SPAN];
     constexpr int NB = N / 2 + 1;
     const int b = blockIdx.y, tid = threadIdx.x;
     const int m0 = blockIdx.x * ISTFT_SPAN;  // first padded position of this span
+    const int Lb = clips.len(b), Tb = clips.frames(Lb, T, hop);
+    const Kept kp = clips.kept(b, Lb);
+    float* wav = clips.row(out, b);
+    if (Clips::kPartial && (m0 - N / 2 >= kp.hi || m0 + ISTFT_SPAN - N / 2 <= kp.lo)) {
+        for (int i = tid; i < ISTFT_SPAN; i += 256) {
+            const int n = m0 + i - N / 2;
+            if (n >= kp.hi && n < kp.zend) wav[n] = 0.f;
+        }
+        return;
+    }
     const int woff = (N - wlen) / 2, wstride = 2048 / wlen;
     for (int i = tid; i < 2048; i += 256) TW[i] = tw2k[i];
     for (int i = tid; i < ISTFT_SPAN; i += 256) { acc[i] = 0.f; env[i] = 0.f; }
@@ -299,7 +347,7 @@ __global__ __launch_bounds__(256) void istft2_kernel(const float* __restrict__ r
     t_lo = t_lo <= 0 ? 0 : (t_lo + hop - 1) / hop;
     int t_hi = (m0 + ISTFT_SPAN - 1 - woff) / hop;
     if (m0 + ISTFT_SPAN - 1 - woff < 0) t_hi = -1;
-    if (t_hi > T - 1) t_hi = T - 1;
+    if (t_hi > Tb - 1) t_hi = Tb - 1;
     __syncthreads();
     for (int ta = t_lo; ta <= t_hi; ta += 2) {
         const bool have_b = ta + 1 <= t_hi;
@@ -334,312 +382,28 @@ __global__ __launch_bounds__(256) void istft2_kernel(const float* __restrict__ r
     }
     for (int i = tid; i < ISTFT_SPAN; i += 256) {
         const int n = m0 + i - N / 2;
-        if (n >= 0 && n < L) wav[(size_t)b * L + n] = acc[i] / fmaxf(env[i], 1e-11f);
+        if (n >= kp.lo && n < kp.hi) wav[n] = acc[i] / fmaxf(env[i], 1e-11f);
+        else if (n >= kp.hi && n < kp.zend) wav[n] = 0.f;
     }
 }
 
-// ---- per-clip lengths (lass_separate_ragged) -------------------------------------------------------------------------
-// Clips whose lengths fall in one 32-frame bucket share every launch between the two ends of the network: the U-Net sees a
-// (Tpad, n_fft/2) image per clip whatever its length.  What differs per clip is where the reflect padding turns round, how
-// many rows of x0 are real, and what the iSTFT overlap-adds and trims - the two kernels below, siblings of stft2_kernel and
-// istft2_kernel that read a clip's length from `lengths` (device, int32) and are otherwise the same arithmetic in the same
-// order: clip b of a ragged call is bit-identical to that clip run alone at its own length.  Rows are L samples apart, T =
-// 1 + L / hop frames apart; `lo` is the smallest length of L's bucket.  A length outside [lo, L] is clamped into it, so a
-// wrong entry gives a wrong clip, never an access out of range.
-__device__ __forceinline__ int ragged_len(const int* __restrict__ lengths, int b, int lo, int L) {
-    const int v = lengths[b];
-    return v < lo ? lo : (v > L ? L : v);
+// The smallest length that shares a 32-frame bucket with L: max(hop * (Tpad - 32), n_fft / 2 + 1).
+int ragged_lo(int L, int n_fft, int hop) {
+    const int T = 1 + L / hop, Tpad = (T + 31) / 32 * 32;
+    const int a = hop * (Tpad - 32), b = n_fft / 2 + 1;
+    return a > b ? a : b;
 }
 
-// Rows t < Tb = 1 + Lb / hop as stft2_kernel writes them for a clip of Lb samples; rows Tb <= t < Tpad of x0 and rows
-// Tb <= t < T of mag / cos / sin / real / imag are 0.  Nothing of a clip's row is read at or beyond Lb.
-template <int N, bool MAGPHASE>
-__global__ __launch_bounds__(256) void stft2_ragged_kernel(const float* __restrict__ wav, const int* __restrict__ lengths,
-                                                           int lo, int L, int hop, int T, int Tpad,
-                                                           const float2* __restrict__ tw2k, Stft2Args a,
-                                                           const float* __restrict__ s0, const float* __restrict__ h0) {
-    __shared__ float2 A[N], Bf[N], TW[2048];
-    constexpr int NB = N / 2 + 1, FC = N / 2;
-    const int ta = 2 * blockIdx.x, b = blockIdx.y, z = blockIdx.z, tid = threadIdx.x;
-    const int Lb = ragged_len(lengths, b, lo, L), Tb = 1 + Lb / hop;
-    float* x0 = a.x0[z];
-    float *mag = a.mag[z], *cosv = a.cosv[z], *sinv = a.sinv[z], *real = a.real[z], *imag = a.imag[z];
-    // rows from `from` of this frame pair lie beyond the clip: zeros in the network input and in the spectra
-    const auto zero_rows = [&](int from) {
-        for (int t = from; t < ta + 2; ++t) {
-            if (x0 && t < Tpad)
-                for (int f = tid; f < FC; f += 256) x0[((size_t)b * Tpad + t) * FC + f] = 0.f;
-            if (t < T)
-                for (int f = tid; f < NB; f += 256) {
-                    const size_t row = ((size_t)b * T + t) * NB + f;
-                    if (real) real[row] = 0.f;
-                    if (imag) imag[row] = 0.f;
-                    if (mag) mag[row] = 0.f;
-                    if (cosv) cosv[row] = 0.f;
-                    if (sinv) sinv[row] = 0.f;
-                }
-        }
-    };
-    if (ta >= Tb) {
-        zero_rows(ta);
-        return;
-    }
-    for (int i = tid; i < 2048; i += 256) TW[i] = tw2k[i];
-    __syncthreads();
-    const int wlen = a.wlen[z], woff = (N - wlen) / 2, wstride = 2048 / wlen;
-    const float* w = wav + (size_t)b * L;
-    const bool have_b = ta + 1 < Tb;
-    for (int idx = tid; idx < N; idx += 256) {
-        float2 v = make_float2(0.f, 0.f);
-        const int j = idx - woff;
-        if (j >= 0 && j < wlen) {
-            const float wn = 0.5f - 0.5f * TW[j * wstride].x;  // periodic Hann of wlen
-            int n = ta * hop + idx - N / 2;                     // centre=True, reflect padding of n_fft/2 about Lb - 1
-            int n2 = n + hop;
-            if (n < 0) n = -n;
-            if (n >= Lb) n = 2 * (Lb - 1) - n;
-            if (n2 < 0) n2 = -n2;
-            if (n2 >= Lb) n2 = 2 * (Lb - 1) - n2;
-            v = make_float2(w[n] * wn, have_b ? w[n2] * wn : 0.f);
-        }
-        A[idx] = v;
-    }
-    __syncthreads();
-    const float2* Z = fft_c<N, false>(A, Bf, TW, tid);
-    for (int f = tid; f < NB; f += 256) {
-        const float2 z1 = Z[f], z2 = Z[(N - f) & (N - 1)];
-        const float re[2] = {0.5f * (z1.x + z2.x), 0.5f * (z1.y + z2.y)};
-        const float im[2] = {0.5f * (z1.y - z2.y), -0.5f * (z1.x - z2.x)};
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            if (r == 1 && !have_b) break;
-            const size_t row = ((size_t)b * T + ta + r) * NB + f;
-            float m, c, s;
-            if (MAGPHASE) {
-                m = sqrtf(re[r] * re[r] + im[r] * im[r]);
-                const float den = fmaxf(m, 1e-10f);
-                c = re[r] / den; s = im[r] / den;
-            } else {
-                m = sqrtf(fmaxf(re[r] * re[r] + im[r] * im[r], 1e-10f));
-                c = re[r] / m; s = im[r] / m;
-            }
-            if (real) real[row] = re[r];
-            if (imag) imag[row] = im[r];
-            if (mag) mag[row] = m;
-            if (cosv) cosv[row] = c;
-            if (sinv) sinv[row] = s;
-            if (x0 && f < FC) x0[((size_t)b * Tpad + ta + r) * FC + f] = m * s0[f] + h0[f];
-        }
-    }
-    if (!have_b) zero_rows(ta + 1);
+// f(clips) with the device-side form of cf: the window form where it has starts, the ragged form where it has lengths
+template <class F>
+void with_clips(const ClipForm& cf, int n_fft, int hop, F f) {
+    if (cf.starts) f(WindowClips{cf.starts, cf.keep, cf.total, cf.L});
+    else if (cf.lengths) f(RaggedClips{cf.lengths, ragged_lo(cf.L, n_fft, hop), cf.L});
+    else f(DenseClips{cf.L});
 }
 
-// istft2_kernel over the frames t < Tb of a clip of Lb samples: samples n < Lb as that kernel writes them for the clip alone,
-// samples Lb <= n < L are 0 (the zero tail: sums over a padded row gain only exact zeros).
-template <int N>
-__global__ __launch_bounds__(256) void istft2_ragged_kernel(const float* __restrict__ real, const float* __restrict__ imag,
-                                                            const int* __restrict__ lengths, int lo, int T, int L, int hop,
-                                                            int wlen, const float2* __restrict__ tw2k,
-                                                            float* __restrict__ wav) {
-    __shared__ float2 A[N], Bf[N], TW[2048];
-    __shared__ float acc[ISTFT_SPAN], env[ISTFT_SPAN];
-    constexpr int NB = N / 2 + 1;
-    const int b = blockIdx.y, tid = threadIdx.x;
-    const int m0 = blockIdx.x * ISTFT_SPAN;  // first padded position of this span
-    const int Lb = ragged_len(lengths, b, lo, L), Tb = 1 + Lb / hop;
-    if (m0 - N / 2 >= Lb) {  // the whole span lies beyond the clip's end
-        for (int i = tid; i < ISTFT_SPAN; i += 256) {
-            const int n = m0 + i - N / 2;
-            if (n < L) wav[(size_t)b * L + n] = 0.f;
-        }
-        return;
-    }
-    const int woff = (N - wlen) / 2, wstride = 2048 / wlen;
-    for (int i = tid; i < 2048; i += 256) TW[i] = tw2k[i];
-    for (int i = tid; i < ISTFT_SPAN; i += 256) { acc[i] = 0.f; env[i] = 0.f; }
-    // frames whose window support [t*hop + woff, t*hop + woff + wlen) meets [m0, m0 + SPAN)
-    int t_lo = m0 - woff - wlen + 1;
-    t_lo = t_lo <= 0 ? 0 : (t_lo + hop - 1) / hop;
-    int t_hi = (m0 + ISTFT_SPAN - 1 - woff) / hop;
-    if (m0 + ISTFT_SPAN - 1 - woff < 0) t_hi = -1;
-    if (t_hi > Tb - 1) t_hi = Tb - 1;
-    __syncthreads();
-    for (int ta = t_lo; ta <= t_hi; ta += 2) {
-        const bool have_b = ta + 1 <= t_hi;
-        const size_t rowa = ((size_t)b * T + ta) * NB, rowb = rowa + NB;
-        for (int k = tid; k < N; k += 256) {  // Z = Xa + i Xb, Hermitian-extended (see istft2_kernel)
-            const int kk = k <= N / 2 ? k : N - k;
-            const float sg = (kk == 0 || kk == N / 2) ? 0.f : (k <= N / 2 ? 1.f : -1.f);
-            const float ar = real[rowa + kk], ai = sg * imag[rowa + kk];
-            const float br = have_b ? real[rowb + kk] : 0.f, bi = have_b ? sg * imag[rowb + kk] : 0.f;
-            A[k] = make_float2(ar - bi, ai + br);
-        }
-        __syncthreads();
-        const float2* X = fft_c<N, true>(A, Bf, TW, tid);  // (xa, xb) * N
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            if (r == 1 && !have_b) break;
-            const int base = (ta + r) * hop + woff - m0;  // span position of window sample 0
-            for (int j = tid; j < wlen; j += 256) {
-                const int pos = base + j;
-                if (pos >= 0 && pos < ISTFT_SPAN) {
-                    const float wn = 0.5f - 0.5f * TW[j * wstride].x;
-                    const float2 x = X[woff + j];
-                    acc[pos] += (r == 0 ? x.x : x.y) * (wn * (1.0f / N));
-                    env[pos] += wn * wn;
-                }
-            }
-            __syncthreads();
-        }
-    }
-    for (int i = tid; i < ISTFT_SPAN; i += 256) {
-        const int n = m0 + i - N / 2;
-        if (n >= 0 && n < L) wav[(size_t)b * L + n] = n < Lb ? acc[i] / fmaxf(env[i], 1e-11f) : 0.f;
-    }
-}
-
-// ---- windows of one long row (lass_separate_windows) -----------------------------------------------------------------
-// Long-form separation: window b of a call is recording[s_b, s_b + W), a clip that starts at an arbitrary offset of ONE long row
-// instead of at b * L, and of its W output samples only [lo_b, hi_b) are wanted, at the same offset of one long output row.  The
-// two kernels below are siblings of stft2_kernel and istft2_kernel that read s_b from `starts` (device, int64) and (lo_b, hi_b)
-// from `keep` (device, int32 pairs) and are otherwise the same arithmetic in the same order: a kept sample is bit-identical to
-// the gathered window run through lass_separate.  Entries are clamped - s_b into [0, total - W], lo_b into [0, W], hi_b into
-// [lo_b, W] - so a wrong entry gives wrong audio, never an access out of range.
-__device__ __forceinline__ int64_t window_start(const int64_t* __restrict__ starts, int b, int64_t total, int W) {
-    const int64_t v = starts[b], last = total - W;
-    return v < 0 ? 0 : (v > last ? last : v);
-}
-
-// stft2_kernel for the clip recording[s_b, s_b + W): reflect padding at the window's own two ends.
-template <int N, bool MAGPHASE>
-__global__ __launch_bounds__(256) void stft2_windows_kernel(const float* __restrict__ recording, int64_t total,
-                                                            const int64_t* __restrict__ starts, int W, int hop, int T, int Tpad,
-                                                            const float2* __restrict__ tw2k, Stft2Args a,
-                                                            const float* __restrict__ s0, const float* __restrict__ h0) {
-    __shared__ float2 A[N], Bf[N], TW[2048];
-    constexpr int NB = N / 2 + 1, FC = N / 2;
-    const int ta = 2 * blockIdx.x, b = blockIdx.y, z = blockIdx.z, tid = threadIdx.x;
-    const int L = W;
-    float* x0 = a.x0[z];
-    if (ta >= T) {  // rows T..Tpad-1 of the network input are zeros AFTER bn0
-        if (x0)
-            for (int r = 0; r < 2; ++r)
-                if (ta + r < Tpad)
-                    for (int f = tid; f < FC; f += 256) x0[((size_t)b * Tpad + ta + r) * FC + f] = 0.f;
-        return;
-    }
-    for (int i = tid; i < 2048; i += 256) TW[i] = tw2k[i];
-    __syncthreads();
-    const int wlen = a.wlen[z], woff = (N - wlen) / 2, wstride = 2048 / wlen;
-    const float* w = recording + window_start(starts, b, total, W);
-    const bool have_b = ta + 1 < T;
-    for (int idx = tid; idx < N; idx += 256) {
-        float2 v = make_float2(0.f, 0.f);
-        const int j = idx - woff;
-        if (j >= 0 && j < wlen) {
-            const float wn = 0.5f - 0.5f * TW[j * wstride].x;  // periodic Hann of wlen
-            int n = ta * hop + idx - N / 2;                     // centre=True, reflect padding of n_fft/2
-            int n2 = n + hop;
-            if (n < 0) n = -n;
-            if (n >= L) n = 2 * (L - 1) - n;
-            if (n2 < 0) n2 = -n2;
-            if (n2 >= L) n2 = 2 * (L - 1) - n2;
-            v = make_float2(w[n] * wn, have_b ? w[n2] * wn : 0.f);
-        }
-        A[idx] = v;
-    }
-    __syncthreads();
-    const float2* Z = fft_c<N, false>(A, Bf, TW, tid);
-    float *mag = a.mag[z], *cosv = a.cosv[z], *sinv = a.sinv[z], *real = a.real[z], *imag = a.imag[z];
-    for (int f = tid; f < NB; f += 256) {
-        const float2 z1 = Z[f], z2 = Z[(N - f) & (N - 1)];
-        const float re[2] = {0.5f * (z1.x + z2.x), 0.5f * (z1.y + z2.y)};
-        const float im[2] = {0.5f * (z1.y - z2.y), -0.5f * (z1.x - z2.x)};
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            if (r == 1 && !have_b) break;
-            const size_t row = ((size_t)b * T + ta + r) * NB + f;
-            float m, c, s;
-            if (MAGPHASE) {
-                m = sqrtf(re[r] * re[r] + im[r] * im[r]);
-                const float den = fmaxf(m, 1e-10f);
-                c = re[r] / den; s = im[r] / den;
-            } else {
-                m = sqrtf(fmaxf(re[r] * re[r] + im[r] * im[r], 1e-10f));
-                c = re[r] / m; s = im[r] / m;
-            }
-            if (real) real[row] = re[r];
-            if (imag) imag[row] = im[r];
-            if (mag) mag[row] = m;
-            if (cosv) cosv[row] = c;
-            if (sinv) sinv[row] = s;
-            if (x0 && f < FC) x0[((size_t)b * Tpad + ta + r) * FC + f] = m * s0[f] + h0[f];
-        }
-    }
-    if (x0 && !have_b && ta + 1 < Tpad)
-        for (int f = tid; f < FC; f += 256) x0[((size_t)b * Tpad + ta + 1) * FC + f] = 0.f;
-}
-
-// istft2_kernel for a clip of W samples whose samples lo <= n < hi alone are stored, at out[s_b + n].  A span that does not meet
-// [lo, hi) returns before it loads a twiddle: with a second of context either side of a five-second window that is two spans in
-// five.  Inside a span the overlap-add runs over the same frames in the same order as istft2_kernel.
-template <int N>
-__global__ __launch_bounds__(256) void istft2_windows_kernel(const float* __restrict__ real, const float* __restrict__ imag,
-                                                             const int64_t* __restrict__ starts, const int* __restrict__ keep,
-                                                             int64_t total, int T, int W, int hop, int wlen,
-                                                             const float2* __restrict__ tw2k, float* __restrict__ out) {
-    __shared__ float2 A[N], Bf[N], TW[2048];
-    __shared__ float acc[ISTFT_SPAN], env[ISTFT_SPAN];
-    constexpr int NB = N / 2 + 1;
-    const int b = blockIdx.y, tid = threadIdx.x;
-    const int m0 = blockIdx.x * ISTFT_SPAN;  // first padded position of this span
-    int lo = keep[2 * b], hi = keep[2 * b + 1];
-    lo = lo < 0 ? 0 : (lo > W ? W : lo);
-    hi = hi < lo ? lo : (hi > W ? W : hi);
-    if (m0 - N / 2 >= hi || m0 + ISTFT_SPAN - N / 2 <= lo) return;  // (an empty keep meets no span)
-    float* wav = out + window_start(starts, b, total, W);
-    const int woff = (N - wlen) / 2, wstride = 2048 / wlen;
-    for (int i = tid; i < 2048; i += 256) TW[i] = tw2k[i];
-    for (int i = tid; i < ISTFT_SPAN; i += 256) { acc[i] = 0.f; env[i] = 0.f; }
-    // frames whose window support [t*hop + woff, t*hop + woff + wlen) meets [m0, m0 + SPAN)
-    int t_lo = m0 - woff - wlen + 1;
-    t_lo = t_lo <= 0 ? 0 : (t_lo + hop - 1) / hop;
-    int t_hi = (m0 + ISTFT_SPAN - 1 - woff) / hop;
-    if (m0 + ISTFT_SPAN - 1 - woff < 0) t_hi = -1;
-    if (t_hi > T - 1) t_hi = T - 1;
-    __syncthreads();
-    for (int ta = t_lo; ta <= t_hi; ta += 2) {
-        const bool have_b = ta + 1 <= t_hi;
-        const size_t rowa = ((size_t)b * T + ta) * NB, rowb = rowa + NB;
-        for (int k = tid; k < N; k += 256) {  // Z = Xa + i Xb, Hermitian-extended (see istft2_kernel)
-            const int kk = k <= N / 2 ? k : N - k;
-            const float sg = (kk == 0 || kk == N / 2) ? 0.f : (k <= N / 2 ? 1.f : -1.f);
-            const float ar = real[rowa + kk], ai = sg * imag[rowa + kk];
-            const float br = have_b ? real[rowb + kk] : 0.f, bi = have_b ? sg * imag[rowb + kk] : 0.f;
-            A[k] = make_float2(ar - bi, ai + br);
-        }
-        __syncthreads();
-        const float2* X = fft_c<N, true>(A, Bf, TW, tid);  // (xa, xb) * N
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            if (r == 1 && !have_b) break;
-            const int base = (ta + r) * hop + woff - m0;  // span position of window sample 0
-            for (int j = tid; j < wlen; j += 256) {
-                const int pos = base + j;
-                if (pos >= 0 && pos < ISTFT_SPAN) {
-                    const float wn = 0.5f - 0.5f * TW[j * wstride].x;
-                    const float2 x = X[woff + j];
-                    acc[pos] += (r == 0 ? x.x : x.y) * (wn * (1.0f / N));
-                    env[pos] += wn * wn;
-                }
-            }
-            __syncthreads();
-        }
-    }
-    for (int i = tid; i < ISTFT_SPAN; i += 256) {
-        const int n = m0 + i - N / 2;
-        if (n >= lo && n < hi) wav[n] = acc[i] / fmaxf(env[i], 1e-11f);  // 0 <= lo, hi <= W
-    }
+bool bad_transform(int n_fft, int wlen) {
+    return (n_fft != 1024 && n_fft != 2048) || wlen <= 0 || wlen > n_fft || (2048 % wlen) != 0 || ((n_fft - wlen) & 1);
 }
 
 }  // namespace
@@ -661,127 +425,47 @@ hipError_t lass_launch_multi_stft(const float* wav, int B, int L, int hop, int n
     return hipGetLastError();
 }
 
-hipError_t lass_launch_stft2(const float* wav, int B, int L, int n_fft, int hop, int T, int Tpad, int nbr,
+hipError_t lass_launch_stft2(const float* wav, const ClipForm& cf, int n_fft, int hop, int T, int Tpad, int nbr,
                              const StftBranch* br, int magphase_sem, const float* s0, const float* h0,
                              const float2* tw2k, hipStream_t stream) {
+    const int B = cf.B, L = cf.L;
     if (B <= 0 || hop <= 0 || nbr <= 0 || nbr > LASS_MAX_STFT_WINDOWS || (n_fft != 1024 && n_fft != 2048) ||
-        L <= n_fft / 2 || T != 1 + L / hop || Tpad < T)
+        L <= n_fft / 2 || T != 1 + L / hop)
+        return hipErrorInvalidValue;
+    if (cf.starts ? (!wav || cf.total < L || Tpad < T) : cf.lengths ? Tpad != (T + 31) / 32 * 32 : Tpad < T)
         return hipErrorInvalidValue;
     Stft2Args a;
     a.nbr = nbr;
     bool any_x0 = false;
     for (int i = 0; i < nbr; ++i) {
-        const int wl = br[i].wlen;
-        if (wl <= 0 || wl > n_fft || (2048 % wl) != 0 || ((n_fft - wl) & 1)) return hipErrorInvalidValue;
+        if (bad_transform(n_fft, br[i].wlen)) return hipErrorInvalidValue;
         if (br[i].x0 && (!s0 || !h0)) return hipErrorInvalidValue;
         any_x0 |= br[i].x0 != nullptr;
-        a.wlen[i] = wl; a.mag[i] = br[i].mag; a.cosv[i] = br[i].cosv; a.sinv[i] = br[i].sinv;
+        a.wlen[i] = br[i].wlen; a.mag[i] = br[i].mag; a.cosv[i] = br[i].cosv; a.sinv[i] = br[i].sinv;
         a.real[i] = br[i].real; a.imag[i] = br[i].imag; a.x0[i] = br[i].x0;
     }
     dim3 grid(((any_x0 ? Tpad : T) + 1) / 2, B, nbr);
-#define LASS_STFT2(NN, MP) hipLaunchKernelGGL((stft2_kernel<NN, MP>), grid, dim3(256), 0, stream, wav, L, hop, T, Tpad, tw2k, a, s0, h0)
-    if (n_fft == 1024) { if (magphase_sem) LASS_STFT2(1024, true); else LASS_STFT2(1024, false); }
-    else               { if (magphase_sem) LASS_STFT2(2048, true); else LASS_STFT2(2048, false); }
-#undef LASS_STFT2
+    with_clips(cf, n_fft, hop, [&](auto clips) {
+        using C = decltype(clips);
+        const auto kernel = n_fft == 1024 ? (magphase_sem ? stft2_kernel<1024, true, C> : stft2_kernel<1024, false, C>)
+                                          : (magphase_sem ? stft2_kernel<2048, true, C> : stft2_kernel<2048, false, C>);
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, wav, clips, hop, T, Tpad, tw2k, a, s0, h0);
+    });
     return hipGetLastError();
 }
 
-hipError_t lass_launch_istft2(const float* real, const float* imag, int B, int T, int L, int n_fft, int wlen, int hop,
+hipError_t lass_launch_istft2(const float* real, const float* imag, const ClipForm& cf, int T, int n_fft, int wlen, int hop,
                               const float2* tw2k, float* wav, hipStream_t stream) {
-    if (B <= 0 || T <= 0 || L <= 0 || hop != LASS_HOP || (n_fft != 1024 && n_fft != 2048) || wlen <= 0 || wlen > n_fft ||
-        (2048 % wlen) != 0 || ((n_fft - wlen) & 1))
-        return hipErrorInvalidValue;
+    const int B = cf.B, L = cf.L;
+    if (B <= 0 || hop != LASS_HOP || bad_transform(n_fft, wlen)) return hipErrorInvalidValue;
+    if (cf.starts || cf.lengths ? (L <= n_fft / 2 || T != 1 + L / hop) : (T <= 0 || L <= 0)) return hipErrorInvalidValue;
+    if (cf.starts && (!cf.keep || !wav || cf.total < L)) return hipErrorInvalidValue;
     dim3 grid((n_fft / 2 + L + ISTFT_SPAN - 1) / ISTFT_SPAN, B);
-    if (n_fft == 1024)
-        hipLaunchKernelGGL(istft2_kernel<1024>, grid, dim3(256), 0, stream, real, imag, T, L, hop, wlen, tw2k, wav);
-    else
-        hipLaunchKernelGGL(istft2_kernel<2048>, grid, dim3(256), 0, stream, real, imag, T, L, hop, wlen, tw2k, wav);
-    return hipGetLastError();
-}
-
-// The smallest length that shares a 32-frame bucket with L: max(hop * (Tpad - 32), n_fft / 2 + 1).
-static int ragged_lo(int L, int n_fft, int hop) {
-    const int T = 1 + L / hop, Tpad = (T + 31) / 32 * 32;
-    const int a = hop * (Tpad - 32), b = n_fft / 2 + 1;
-    return a > b ? a : b;
-}
-
-hipError_t lass_launch_stft2_ragged(const float* wav, const int* lengths, int B, int L, int n_fft, int hop, int T, int Tpad,
-                                    int nbr, const StftBranch* br, int magphase_sem, const float* s0, const float* h0,
-                                    const float2* tw2k, hipStream_t stream) {
-    if (!lengths || B <= 0 || hop <= 0 || nbr <= 0 || nbr > LASS_MAX_STFT_WINDOWS || (n_fft != 1024 && n_fft != 2048) ||
-        L <= n_fft / 2 || T != 1 + L / hop || Tpad != (T + 31) / 32 * 32)
-        return hipErrorInvalidValue;
-    Stft2Args a;
-    a.nbr = nbr;
-    bool any_x0 = false;
-    for (int i = 0; i < nbr; ++i) {
-        const int wl = br[i].wlen;
-        if (wl <= 0 || wl > n_fft || (2048 % wl) != 0 || ((n_fft - wl) & 1)) return hipErrorInvalidValue;
-        if (br[i].x0 && (!s0 || !h0)) return hipErrorInvalidValue;
-        any_x0 |= br[i].x0 != nullptr;
-        a.wlen[i] = wl; a.mag[i] = br[i].mag; a.cosv[i] = br[i].cosv; a.sinv[i] = br[i].sinv;
-        a.real[i] = br[i].real; a.imag[i] = br[i].imag; a.x0[i] = br[i].x0;
-    }
-    const int lo = ragged_lo(L, n_fft, hop);
-    dim3 grid(((any_x0 ? Tpad : T) + 1) / 2, B, nbr);
-#define LASS_STFT2R(NN, MP) hipLaunchKernelGGL((stft2_ragged_kernel<NN, MP>), grid, dim3(256), 0, stream, wav, lengths, lo, L, hop, T, Tpad, tw2k, a, s0, h0)
-    if (n_fft == 1024) { if (magphase_sem) LASS_STFT2R(1024, true); else LASS_STFT2R(1024, false); }
-    else               { if (magphase_sem) LASS_STFT2R(2048, true); else LASS_STFT2R(2048, false); }
-#undef LASS_STFT2R
-    return hipGetLastError();
-}
-
-hipError_t lass_launch_istft2_ragged(const float* real, const float* imag, const int* lengths, int B, int T, int L, int n_fft,
-                                     int wlen, int hop, const float2* tw2k, float* wav, hipStream_t stream) {
-    if (!lengths || B <= 0 || L <= n_fft / 2 || hop != LASS_HOP || T != 1 + L / hop || (n_fft != 1024 && n_fft != 2048) ||
-        wlen <= 0 || wlen > n_fft || (2048 % wlen) != 0 || ((n_fft - wlen) & 1))
-        return hipErrorInvalidValue;
-    const int lo = ragged_lo(L, n_fft, hop);
-    dim3 grid((n_fft / 2 + L + ISTFT_SPAN - 1) / ISTFT_SPAN, B);
-    if (n_fft == 1024)
-        hipLaunchKernelGGL(istft2_ragged_kernel<1024>, grid, dim3(256), 0, stream, real, imag, lengths, lo, T, L, hop, wlen, tw2k, wav);
-    else
-        hipLaunchKernelGGL(istft2_ragged_kernel<2048>, grid, dim3(256), 0, stream, real, imag, lengths, lo, T, L, hop, wlen, tw2k, wav);
-    return hipGetLastError();
-}
-
-hipError_t lass_launch_stft2_windows(const float* recording, int64_t total, const int64_t* starts, int B, int W, int n_fft, int hop,
-                                     int T, int Tpad, int nbr, const StftBranch* br, int magphase_sem, const float* s0,
-                                     const float* h0, const float2* tw2k, hipStream_t stream) {
-    if (!recording || !starts || B <= 0 || hop <= 0 || nbr <= 0 || nbr > LASS_MAX_STFT_WINDOWS || (n_fft != 1024 && n_fft != 2048) ||
-        W <= n_fft / 2 || total < W || T != 1 + W / hop || Tpad < T)
-        return hipErrorInvalidValue;
-    Stft2Args a;
-    a.nbr = nbr;
-    bool any_x0 = false;
-    for (int i = 0; i < nbr; ++i) {
-        const int wl = br[i].wlen;
-        if (wl <= 0 || wl > n_fft || (2048 % wl) != 0 || ((n_fft - wl) & 1)) return hipErrorInvalidValue;
-        if (br[i].x0 && (!s0 || !h0)) return hipErrorInvalidValue;
-        any_x0 |= br[i].x0 != nullptr;
-        a.wlen[i] = wl; a.mag[i] = br[i].mag; a.cosv[i] = br[i].cosv; a.sinv[i] = br[i].sinv;
-        a.real[i] = br[i].real; a.imag[i] = br[i].imag; a.x0[i] = br[i].x0;
-    }
-    dim3 grid(((any_x0 ? Tpad : T) + 1) / 2, B, nbr);
-#define LASS_STFT2W(NN, MP) hipLaunchKernelGGL((stft2_windows_kernel<NN, MP>), grid, dim3(256), 0, stream, recording, total, starts, W, hop, T, Tpad, tw2k, a, s0, h0)
-    if (n_fft == 1024) { if (magphase_sem) LASS_STFT2W(1024, true); else LASS_STFT2W(1024, false); }
-    else               { if (magphase_sem) LASS_STFT2W(2048, true); else LASS_STFT2W(2048, false); }
-#undef LASS_STFT2W
-    return hipGetLastError();
-}
-
-hipError_t lass_launch_istft2_windows(const float* real, const float* imag, const int64_t* starts, const int* keep, int64_t total,
-                                      int B, int T, int W, int n_fft, int wlen, int hop, const float2* tw2k, float* out,
-                                      hipStream_t stream) {
-    if (!starts || !keep || !out || B <= 0 || W <= n_fft / 2 || total < W || hop != LASS_HOP || T != 1 + W / hop ||
-        (n_fft != 1024 && n_fft != 2048) || wlen <= 0 || wlen > n_fft || (2048 % wlen) != 0 || ((n_fft - wlen) & 1))
-        return hipErrorInvalidValue;
-    dim3 grid((n_fft / 2 + W + ISTFT_SPAN - 1) / ISTFT_SPAN, B);
-    if (n_fft == 1024)
-        hipLaunchKernelGGL(istft2_windows_kernel<1024>, grid, dim3(256), 0, stream, real, imag, starts, keep, total, T, W, hop, wlen, tw2k, out);
-    else
-        hipLaunchKernelGGL(istft2_windows_kernel<2048>, grid, dim3(256), 0, stream, real, imag, starts, keep, total, T, W, hop, wlen, tw2k, out);
+    with_clips(cf, n_fft, hop, [&](auto clips) {
+        using C = decltype(clips);
+        const auto kernel = n_fft == 1024 ? istft2_kernel<1024, C> : istft2_kernel<2048, C>;
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, real, imag, clips, T, hop, wlen, tw2k, wav);
+    });
     return hipGetLastError();
 }
 
