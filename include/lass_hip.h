@@ -64,6 +64,21 @@ int lass_version(void);
  * 621-637 is written for target_sources_num x output_channels x 3 mask channels, and the Python mirror raises
  * NotImplementedError for anything else (lass_amd/resunet.py). */
 int lass_create(lass_ctx** out, int device_id);
+/* lass_create at a given STFT geometry (n_fft = window length, hop).  Two pairs are accepted:
+ *   (1024, 160): exactly lass_create - the reference's 16 kHz layout (resunet.py:271-276), 513-bin bn0, 512-bin images.
+ *   (2048, 320): the same network at 32 kHz - 64 ms windows every 10 ms as before, `base.bn0.*` with 1025 entries, images of
+ *                1024 bins, the same K = 3 mask head.  These two numbers are those of upstream AudioSep's released 32 kHz
+ *                ResUNet30, from which the reference was trimmed; nothing in the reference states them (it keeps only that
+ *                model's RATE = 32000 in chunk_inference, resunet.py:657), so they are the specification here.
+ * Any other pair: LASS_ERR_ARG, the message names the two.  Everything below works on such a context with hop and n_fft
+ * read as the context's: a clip of L samples has 1 + L/hop frames, a ragged bucket is 32*hop samples wide (10 240 at hop 320),
+ * L and window lengths must exceed n_fft/2, all three compute modes.  The weight-free stage calls lass_stft_magphase and
+ * lass_istft transform at the context's geometry too.  Per-clip limit at (2048, 320): 64 ch x padded frames x 1024 bins x 4 B
+ * below 4 GiB = fewer than 16 384 padded frames, 163 s at 32 kHz (LASS_ERR_ARG beyond, as at the default geometry). */
+int lass_create_stft(lass_ctx** out, int device_id, int n_fft, int hop);
+/* The STFT geometry of a context (either pointer may be NULL): (1024, 160) or (2048, 320) for ResUNet30, (n_fft, 160) for the
+ * multi-STFT model. */
+int lass_stft_geometry(const lass_ctx* ctx, int* n_fft, int* hop);
 /* Context for the multi-resolution-STFT separator (BASELINE configs[4]; reference intent:
  * models/resunet_with_multistft.py:40-118,137-216 - not runnable as shipped, see DESIGN.md section 9 for the authored
  * spec): `n_windows` periodic-Hann analysis windows (`win_lengths`, e.g. {256, 512, 2048}) at a common n_fft (2048),
@@ -94,7 +109,7 @@ int lass_finalize(lass_ctx* ctx, int compute_mode);
 
 /* Bytes of workspace `lass_separate` needs for B clips of L samples.
  * Limits: B >= 1, L > n_fft/2, and the largest per-clip tensor - decoder_block6's concat, (32 + 32*n_windows) channels x
- * padded frames x n_fft/2 bins, f32 - below 4 GiB: the kernels address one clip's tensors with unsigned 32-bit byte offsets.  ResUNet30: 327 s at 16 kHz; multi-STFT model: 40.9 s at 32 kHz.  Longer clips are an LASS_ERR_ARG here and in lass_separate; the reference's own long-form route,
+ * padded frames x n_fft/2 bins, f32 - below 4 GiB: the kernels address one clip's tensors with unsigned 32-bit byte offsets.  ResUNet30: 327 s at 16 kHz, 163 s at 32 kHz with the (2048, 320) geometry (lass_create_stft); multi-STFT model: 40.9 s at 32 kHz.  Longer clips are an LASS_ERR_ARG here and in lass_separate; the reference's own long-form route,
  * chunk_inference (resunet.py:655-714), stays available. */
 int lass_workspace_bytes(const lass_ctx* ctx, int B, int L, size_t* bytes);
 
@@ -122,6 +137,7 @@ int lass_separate(lass_ctx* ctx, const float* mixture, const float* condition, f
 
 /* lass_separate for B clips of different lengths.  mixture and out are (B,L) with rows L samples apart; clip b is
  * mixture[b][0 .. lengths[b]) and the rest of its row is never read.  lengths: DEVICE int32 (B).
+ * (160 below is the context's hop: read 320 on a (2048, 320) context of lass_create_stft, whose buckets are 10 240 samples wide.)
  * A clip of Lb samples has 1 + Lb/160 frames, zero-padded after bn0 to a multiple of 32 (resunet.py:543-548): the network sees
  * one (padded frames, n_fft/2) image per clip, and clips whose padded frame counts agree can share every launch.  So every clip
  * must lie in the bucket of L:  max(160*(Tp-32), n_fft/2+1) <= lengths[b] <= L,  Tp = 32*ceil((1 + L/160)/32)  - the interval
@@ -220,8 +236,8 @@ int lass_separate_components(lass_ctx* ctx, const float* const* mag, const float
 
 /* ---- stage entry points (used by the parity tests; same kernels lass_separate launches) --------------------- */
 
-/* Centred STFT (n_fft=win=1024, hop 160, reflect pad, periodic Hann) fused with magnitude/phase.
- * wav (B,L) -> mag, cos, sin (B,T,513), T = 1 + L/160.  Any of mag/cos/sin/real/imag may be NULL.
+/* Centred STFT (n_fft=win=1024, hop 160, reflect pad, periodic Hann; on a lass_create_stft context its (n_fft, hop)) fused with
+ * magnitude/phase.  wav (B,L) -> mag, cos, sin (B,T,n_fft/2+1 = 513), T = 1 + L/hop.  Any of mag/cos/sin/real/imag may be NULL.
  * mag = sqrt(max(re^2+im^2, 1e-10)), cos = re/mag, sin = im/mag.
  * Replaces: Base.wav_to_spectrogram_phase (base.py:83-113) + torchlibrosa STFT.forward. */
 int lass_stft_magphase(lass_ctx* ctx, const float* wav, int B, int L, float* mag, float* cos_out, float* sin_out,
@@ -249,7 +265,8 @@ int lass_stft_components(lass_ctx* ctx, const float* wav, int B, int L, int n_ff
  * Replaces: torchlibrosa ISTFT.forward as called at resunet.py:510. */
 int lass_istft(lass_ctx* ctx, const float* real, const float* imag, int B, int T, int L, float* wav,
                float* frames_ws, void* stream);
-/* The same for n_fft in {1024, 2048} and a synthesis window of win_length <= n_fft (zero-padded, centred), hop 160:
+/* The same for n_fft in {1024, 2048} and a synthesis window of win_length <= n_fft (zero-padded, centred), at the context's
+ * hop (160; a (2048, 320) context of lass_create_stft: hop 320, n_fft 2048 only):
  * real, imag (B,T,n_fft/2+1) -> wav (B,L).  Replaces: ISTFT(n_fft, hop, win_length) of resunet_with_multistft.py:36-44. */
 int lass_istft_nfft(lass_ctx* ctx, const float* real, const float* imag, int B, int T, int L, int n_fft, int win_length,
                     float* wav, void* stream);
@@ -303,7 +320,8 @@ int lass_front_end_windows(lass_ctx* ctx, const float* recording, int64_t total,
                            float* cos_out, float* sin_out, float* x0, void* stream);
 /* lass_istft_nfft for windows: real, imag (B,T,n_fft/2+1) with T = 1 + W/160 -> out (total floats).  Of window b only samples
  * keep[2b] <= n < keep[2b+1] are stored, at out[starts[b] + n], each what lass_istft_nfft gives for a clip of W samples; the
- * rest of `out` is not touched.  16-hop spans of a window that do not meet its kept range run no transform. */
+ * rest of `out` is not touched.  2 560-sample spans of a window that do not meet its kept range run no transform.  (T = 1 + W/hop
+ * with the context's hop, as everywhere.) */
 int lass_istft_windows(lass_ctx* ctx, const float* real, const float* imag, const int64_t* starts, const int* keep, int64_t total,
                        int B, int T, int W, int n_fft, int win_length, float* out, void* stream);
 

@@ -14,6 +14,8 @@ _lib = None
 SYMBOLS = [
     ("lass_version", c_int, []),
     ("lass_create", c_int, [POINTER(c_void_p), c_int]),
+    ("lass_create_stft", c_int, [POINTER(c_void_p), c_int, c_int, c_int]),
+    ("lass_stft_geometry", c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),
     ("lass_create_multistft", c_int, [POINTER(c_void_p), c_int, c_int, c_int, POINTER(c_int), c_int]),
     ("lass_destroy", c_int, [c_void_p]),
     ("lass_last_error", c_char_p, [c_void_p]),

@@ -63,9 +63,24 @@ DECODERS: Tuple[DecSpec, ...] = (
 )
 
 
-def frames_for(length: int) -> int:
+# The two STFT geometries (n_fft, hop) a ResUNet30 context takes (include/lass_hip.h: lass_create_stft).  (1024, 160) is the
+# reference's 16 kHz layout; (2048, 320) is the same network at 32 kHz - 64 ms / 10 ms again, 1025-bin bn0, 1024-bin images - as
+# upstream AudioSep released it.  Nothing in the reference states the second pair: it is this package's specification.
+STFT_GEOMETRIES: Tuple[Tuple[int, int], ...] = ((N_FFT, HOP), (2048, 320))
+
+
+def check_stft(n_fft: int, hop: int) -> Tuple[int, int]:
+    """(n_fft, hop) as ints if it is one of STFT_GEOMETRIES, ValueError naming both keywords otherwise."""
+    pair = (int(n_fft), int(hop))
+    if pair not in STFT_GEOMETRIES:
+        raise ValueError(f"n_fft={n_fft}, hop={hop} is not a supported STFT geometry: (n_fft, hop) must be one of "
+                         f"{', '.join(map(str, STFT_GEOMETRIES))}")
+    return pair
+
+
+def frames_for(length: int, hop: int = HOP) -> int:
     """Centred STFT frame count (torchlibrosa STFT with center=True)."""
-    return 1 + length // HOP
+    return 1 + length // hop
 
 
 def padded_frames(t: int) -> int:
@@ -112,14 +127,16 @@ def film_sites() -> List[Tuple[str, int, bool]]:
     return sites
 
 
-def param_specs(input_channels: int = 1, output_channels: int = 1, condition_size: int = 512):
+def param_specs(input_channels: int = 1, output_channels: int = 1, condition_size: int = 512, n_fft: int = N_FFT):
     """Ordered [(state_dict key, shape, kind)] for `ResUNet30(input_channels, output_channels, condition_size)`.
+    n_fft: the STFT size of the model - it sets the entries of `base.bn0.*` (n_fft/2 + 1: 513, or 1025 at n_fft 2048) and
+    nothing else; every other tensor is a channel count.
 
     Keys carry the `base.` / `film.` prefixes of resunet.py:625-637.  torchlibrosa's frozen conv buffers
     (`base.stft.*`, `base.istft.*`) are deliberately absent: they are constants of the STFT geometry, not weights.
     """
     specs: List[Tuple[str, Tuple[int, ...], str]] = []
-    specs += _bn("base.bn0", N_BINS)
+    specs += _bn("base.bn0", n_fft // 2 + 1)
     specs.append(("base.pre_conv.weight", (PRE_CH, input_channels, 1, 1), "conv_w"))
     specs.append(("base.pre_conv.bias", (PRE_CH,), "bias"))
     for e in ENCODERS:

@@ -62,15 +62,18 @@ thread_local std::string g_create_err;
 
 }  // namespace
 
-// Model geometry.  variant 0 = ResUNet30 (models/resunet.py): one analysis branch, n_fft = win = 1024.
+// Model geometry.  variant 0 = ResUNet30 (models/resunet.py): one analysis branch, n_fft = win, at one of two STFT geometries -
+// (1024, hop 160), the reference's 16 kHz layout (lass_create), or (2048, hop 320), the 32 kHz layout of the same network
+// (lass_create_stft: 1025-bin bn0, 1024-bin images, the same durations of 64 ms / 10 ms).
 // variant 1 = the multi-resolution-STFT separator (models/resunet_with_multistft.py under the authored spec of
 // DESIGN.md / lass_amd/arch.py): nbr analysis windows at a common n_fft, one pre_conv + encoder_block1 per window,
-// channel-concatenated pools / skips, shared trunk, mask and iSTFT on the branch `mask_br`.
+// channel-concatenated pools / skips, shared trunk, mask and iSTFT on the branch `mask_br`; always hop 160.
 struct Geometry {
     int variant = 0;
     int nbr = 1;
     int wins[kMaxBranches] = {1024, 0, 0, 0};
     int nfft = 1024, nbins = 513, fcrop = 512;
+    int hop = LASS_HOP;  // frames are 1 + L / hop; a ragged bucket is 32 * hop samples wide
     int mask_br = 0;
     int magphase_sem = 0;  // 0: base.py:83-88 clamp on |X|^2; 1: torchlibrosa magphase (precomputed-STFT wire format)
 };
@@ -221,7 +224,7 @@ void build_arch(lass_ctx* c) {
     c->n_shift = 0;
     c->enc.clear();
     c->dec.clear();
-    c->m = model_table(g.variant == 0 ? 0 : g.nbr);
+    c->m = model_table(g.variant == 0 ? 0 : g.nbr, g.fcrop);
     for (int k = 0; k < g.nbr; ++k) {  // analysis branches
         ResBlock rb;
         std::string film;
@@ -247,7 +250,7 @@ void build_arch(lass_ctx* c) {
         rb.prefix = std::string("base.") + e.name + ".conv_block1";
         rb.cin = e.cin;
         rb.cout = e.cout;
-        rb.width = g.fcrop >> i;  // encoder i (0-based) runs behind i frequency halvings: 512, 256, ..., 16, 8 bins
+        rb.width = g.fcrop >> i;  // encoder i (0-based) runs behind i frequency halvings: 512, 256, ..., 16, 8 bins at n_fft 1024
         rb.s1 = add_site(c, std::string(e.name) + "->conv_block1->beta1", e.cin);
         rb.s2 = add_site(c, std::string(e.name) + "->conv_block1->beta2", e.cout);
         c->enc.push_back(rb);
@@ -750,13 +753,14 @@ bool head_sc_planned(const lass_ctx* c, int B, int H, int W) {
 // The conv kernels address one clip's tensors through 32-bit buffer descriptors and byte offsets, so the largest per-clip
 // tensor (decoder_block6's concat at full resolution, f32) bounds the clip length: below 4 GiB (all offset arithmetic of
 // the f32 Winograd and the bf16 kernels is unsigned; both exercised by the 3.15-GB concat of the 30 s @ 32 kHz multi-STFT
-// clip).  ResUNet30 at 16 kHz: 131 072 B per frame -> 2^32 at 32 768 frames (327 s); the multi-STFT model (128 ch x 1024 bins): 524 288 B per frame ->
-// 2^32 at 8 192 frames (40.9 s at 32 kHz).  Longer inputs go through chunk_inference.
+// clip).  ResUNet30 at 16 kHz: 131 072 B per frame -> 2^32 at 32 768 frames (327 s); ResUNet30 at the 32 kHz geometry (64 ch x 1024
+// bins): 262 144 B per frame -> 2^32 at 16 384 frames (163 s at hop 320); the multi-STFT model (128 ch x 1024 bins): 524 288 B per
+// frame -> 2^32 at 8 192 frames (40.9 s at 32 kHz).  Longer inputs go through chunk_inference / separate_long.
 int make_plan(const lass_ctx* c, int B, int L, Plan* pl) {
     const Geometry& g = c->g;
     if (B <= 0 || L <= g.nfft / 2) return LASS_ERR_ARG;
     pl->B = B; pl->L = L;
-    pl->T = 1 + L / LASS_HOP;
+    pl->T = 1 + L / g.hop;
     pl->Tp = (pl->T + 31) / 32 * 32;
     const size_t clip_max = (size_t)c->m.dec_cat[5] * pl->Tp * g.fcrop * sizeof(float);
     if (clip_max > 0xFFFF0000ull) return LASS_ERR_ARG;
@@ -865,6 +869,13 @@ int stage_scratch(lass_ctx* c, const ResBlock& rb, int B, int H, int W, const fl
     return 0;
 }
 
+// The transform size of the weight-free stage calls (lass_stft_magphase, lass_istft): a ResUNet30 context's own; the multi-STFT
+// model's context keeps the reference layout's 1024 there (its own transforms go through the *_nfft / *_components calls)
+int stage_nfft(const lass_ctx* c) { return c->g.variant == 0 ? c->g.nfft : LASS_NFFT; }
+
+// iSTFT transform sizes of a context: 1024 or 2048 at hop 160, 2048 alone at hop 320 (stft.hip instantiates no other pair)
+bool istft_nfft_ok(const lass_ctx* c, int n_fft) { return n_fft == 2048 || (n_fft == 1024 && c->g.hop == LASS_HOP); }
+
 const ResBlock* find_block(const lass_ctx* c, const std::string& prefix) {
     for (const auto& rb : c->enc) if (rb.prefix == prefix) return &rb;
     for (const auto& rb : c->dec) if (rb.prefix == prefix) return &rb;
@@ -875,7 +886,7 @@ const ResBlock* find_block(const lass_ctx* c, const std::string& prefix) {
 
 extern "C" {
 
-int lass_version(void) { return 10500; }  // 1.5.0: windows of one long row (lass_separate_windows & co); 1.4.0: per-clip lengths (lass_separate_ragged & co); 1.3.0: CLAP text tower (lass_text_*, text.hip); 1.2.0: F(4x4,3x3) kernels, lass_set_graph_replay (1.1.0: multi-STFT model, fused iSTFT, graph replay)
+int lass_version(void) { return 10600; }  // 1.6.0: ResUNet30 at the (2048, 320) STFT geometry (lass_create_stft, lass_stft_geometry); 1.5.0: windows of one long row (lass_separate_windows & co); 1.4.0: per-clip lengths (lass_separate_ragged & co); 1.3.0: CLAP text tower (lass_text_*, text.hip); 1.2.0: F(4x4,3x3) kernels, lass_set_graph_replay (1.1.0: multi-STFT model, fused iSTFT, graph replay)
 
 const char* lass_last_error(const lass_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_err.c_str(); }
 
@@ -941,6 +952,27 @@ static int create_impl(lass_ctx** out, int device_id, const Geometry& geom) {
 }
 
 int lass_create(lass_ctx** out, int device_id) { return create_impl(out, device_id, Geometry()); }
+
+int lass_create_stft(lass_ctx** out, int device_id, int n_fft, int hop) {
+    if (!out) return LASS_ERR_ARG;
+    *out = nullptr;
+    Geometry g;  // (1024, 160): exactly lass_create
+    if (n_fft == 2048 && hop == 320) {
+        g.nfft = 2048; g.nbins = 1025; g.fcrop = 1024; g.hop = 320; g.wins[0] = 2048;
+    } else if (n_fft != LASS_NFFT || hop != LASS_HOP) {
+        g_create_err = "lass_create_stft: (n_fft, hop) must be (1024, 160) or (2048, 320), got (" + std::to_string(n_fft) + ", " +
+                       std::to_string(hop) + ")";
+        return LASS_ERR_ARG;
+    }
+    return create_impl(out, device_id, g);
+}
+
+int lass_stft_geometry(const lass_ctx* c, int* n_fft, int* hop) {
+    if (!c) return LASS_ERR_ARG;
+    if (n_fft) *n_fft = c->g.nfft;
+    if (hop) *hop = c->g.hop;
+    return 0;
+}
 
 int lass_create_multistft(lass_ctx** out, int device_id, int n_fft, int n_windows, const int* win_lengths,
                           int mask_window) {
@@ -1273,12 +1305,14 @@ int lass_film_raw(lass_ctx* c, const float* cond, int B, float* film, void* stre
 
 int lass_stft_magphase(lass_ctx* c, const float* wav, int B, int L, float* mag, float* cos_out, float* sin_out,
                        float* real_out, float* imag_out, void* stream) {
-    if (!c || !wav || B <= 0 || L <= LASS_NFFT / 2) return fail(c, LASS_ERR_ARG, "lass_stft_magphase: bad argument");
+    if (!c) return LASS_ERR_ARG;
+    const int n_fft = stage_nfft(c), hop = c->g.hop;  // a ResUNet30 context analyses at its own geometry
+    if (!wav || B <= 0 || L <= n_fft / 2) return fail(c, LASS_ERR_ARG, "lass_stft_magphase: bad argument");
     if (int r = use_device(c)) return r;
-    const int T = 1 + L / LASS_HOP;
+    const int T = 1 + L / hop;
     StftBranch br;
-    br.wlen = LASS_NFFT; br.mag = mag; br.cosv = cos_out; br.sinv = sin_out; br.real = real_out; br.imag = imag_out;
-    HIP_TRY(c, lass_launch_stft2(wav, ClipForm{B, L}, LASS_NFFT, LASS_HOP, T, T, 1, &br, 0, nullptr, nullptr, c->tw2k,
+    br.wlen = n_fft; br.mag = mag; br.cosv = cos_out; br.sinv = sin_out; br.real = real_out; br.imag = imag_out;
+    HIP_TRY(c, lass_launch_stft2(wav, ClipForm{B, L}, n_fft, hop, T, T, 1, &br, 0, nullptr, nullptr, c->tw2k,
                                  (hipStream_t)stream));
     return 0;
 }
@@ -1325,17 +1359,18 @@ int lass_multi_stft(lass_ctx* c, const float* wav, int B, int L, int hop, int n_
 int lass_istft(lass_ctx* c, const float* real, const float* imag, int B, int T, int L, float* wav, float* frames_ws,
                void* stream) {
     (void)frames_ws;  // the fused kernel needs no frame scratch (kept in the signature for ABI stability; may be NULL)
-    return lass_istft_nfft(c, real, imag, B, T, L, LASS_NFFT, LASS_NFFT, wav, stream);
+    if (!c) return LASS_ERR_ARG;
+    return lass_istft_nfft(c, real, imag, B, T, L, stage_nfft(c), stage_nfft(c), wav, stream);
 }
 
 int lass_istft_nfft(lass_ctx* c, const float* real, const float* imag, int B, int T, int L, int n_fft, int win_length,
                     float* wav, void* stream) {
     if (!c || !real || !imag || !wav || B <= 0 || T <= 0 || L <= 0 || (n_fft != 1024 && n_fft != 2048) ||
-        win_length < 32 || win_length > n_fft || (2048 % win_length) != 0 ||
-        (long)L + n_fft / 2 > (long)(T - 1) * LASS_HOP + n_fft)
-        return fail(c, LASS_ERR_ARG, "lass_istft: bad argument");
+        !istft_nfft_ok(c, n_fft) || win_length < 32 || win_length > n_fft || (2048 % win_length) != 0 ||
+        (long)L + n_fft / 2 > (long)(T - 1) * c->g.hop + n_fft)
+        return fail(c, LASS_ERR_ARG, "lass_istft: bad argument (n_fft 1024 or 2048 - 2048 alone at hop 320 -, the frames must cover L)");
     if (int r = use_device(c)) return r;
-    HIP_TRY(c, lass_launch_istft2(real, imag, ClipForm{B, L}, T, n_fft, win_length, LASS_HOP, c->tw2k, wav, (hipStream_t)stream));
+    HIP_TRY(c, lass_launch_istft2(real, imag, ClipForm{B, L}, T, n_fft, win_length, c->g.hop, c->tw2k, wav, (hipStream_t)stream));
     return 0;
 }
 
@@ -1384,20 +1419,20 @@ int lass_encoder_block(lass_ctx* c, const char* name, const float* x, int B, int
 static hipError_t launch_front_end(lass_ctx* c, const float* wav, const ClipForm& cf, float* const* x0, float* mag, float* cosv,
                                    float* sinv, hipStream_t st) {
     const Geometry& g = c->g;
-    const int T = 1 + cf.L / LASS_HOP, Tp = (T + 31) / 32 * 32;
+    const int T = 1 + cf.L / g.hop, Tp = (T + 31) / 32 * 32;
     StftBranch br[kMaxBranches];
     for (int k = 0; k < g.nbr; ++k) {
         br[k].wlen = g.wins[k];
         br[k].x0 = x0[k];
         if (k == g.mask_br) { br[k].mag = mag; br[k].cosv = cosv; br[k].sinv = sinv; }
     }
-    return lass_launch_stft2(wav, cf, g.nfft, LASS_HOP, T, Tp, g.nbr, br, g.magphase_sem, c->bn0_s, c->bn0_h, c->tw2k, st);
+    return lass_launch_stft2(wav, cf, g.nfft, g.hop, T, Tp, g.nbr, br, g.magphase_sem, c->bn0_s, c->bn0_h, c->tw2k, st);
 }
 
 // lass_front_end, lass_front_end_ragged and lass_front_end_windows behind their argument checks: x0 is (nbr, B, Tp, fcrop)
 static int front_end(lass_ctx* c, const float* wav, const ClipForm& cf, float* mag, float* cos_out, float* sin_out, float* x0,
                      void* stream) {
-    const int T = 1 + cf.L / LASS_HOP, Tp = (T + 31) / 32 * 32;
+    const int T = 1 + cf.L / c->g.hop, Tp = (T + 31) / 32 * 32;
     float* x0k[kMaxBranches];
     for (int k = 0; k < c->g.nbr; ++k) x0k[k] = x0 + (size_t)k * cf.B * Tp * c->g.fcrop;
     HIP_TRY(c, launch_front_end(c, wav, cf, x0k, mag, cos_out, sin_out, (hipStream_t)stream));
@@ -1422,11 +1457,12 @@ int lass_front_end_ragged(lass_ctx* c, const float* wav, const int* lengths, int
 
 int lass_istft_ragged(lass_ctx* c, const float* real, const float* imag, const int* lengths, int B, int T, int L, int n_fft,
                       int win_length, float* wav, void* stream) {
-    if (!c || !real || !imag || !lengths || !wav || B <= 0 || (n_fft != 1024 && n_fft != 2048) || L <= n_fft / 2 ||
-        T != 1 + L / LASS_HOP || win_length < 32 || win_length > n_fft || (2048 % win_length) != 0)
-        return fail(c, LASS_ERR_ARG, "lass_istft_ragged: bad argument (T = 1 + L/160 frames per clip, L > n_fft/2)");
+    if (!c || !real || !imag || !lengths || !wav || B <= 0 || !istft_nfft_ok(c, n_fft) || L <= n_fft / 2 ||
+        T != 1 + L / c->g.hop || win_length < 32 || win_length > n_fft || (2048 % win_length) != 0)
+        return fail(c, LASS_ERR_ARG, "lass_istft_ragged: bad argument (T = 1 + L/" + std::to_string(c ? c->g.hop : LASS_HOP) +
+                                         " frames per clip, L > n_fft/2)");
     if (int r = use_device(c)) return r;
-    HIP_TRY(c, lass_launch_istft2(real, imag, ClipForm{B, L, lengths}, T, n_fft, win_length, LASS_HOP, c->tw2k, wav,
+    HIP_TRY(c, lass_launch_istft2(real, imag, ClipForm{B, L, lengths}, T, n_fft, win_length, c->g.hop, c->tw2k, wav,
                                   (hipStream_t)stream));
     return 0;
 }
@@ -1442,11 +1478,12 @@ int lass_front_end_windows(lass_ctx* c, const float* recording, int64_t total, c
 
 int lass_istft_windows(lass_ctx* c, const float* real, const float* imag, const int64_t* starts, const int* keep, int64_t total,
                        int B, int T, int W, int n_fft, int win_length, float* out, void* stream) {
-    if (!c || !real || !imag || !starts || !keep || !out || B <= 0 || (n_fft != 1024 && n_fft != 2048) || W <= n_fft / 2 ||
-        total < W || T != 1 + W / LASS_HOP || win_length < 32 || win_length > n_fft || (2048 % win_length) != 0)
-        return fail(c, LASS_ERR_ARG, "lass_istft_windows: bad argument (T = 1 + W/160 frames per window, n_fft/2 < W <= total)");
+    if (!c || !real || !imag || !starts || !keep || !out || B <= 0 || !istft_nfft_ok(c, n_fft) || W <= n_fft / 2 ||
+        total < W || T != 1 + W / c->g.hop || win_length < 32 || win_length > n_fft || (2048 % win_length) != 0)
+        return fail(c, LASS_ERR_ARG, "lass_istft_windows: bad argument (T = 1 + W/" + std::to_string(c ? c->g.hop : LASS_HOP) +
+                                         " frames per window, n_fft/2 < W <= total)");
     if (int r = use_device(c)) return r;
-    HIP_TRY(c, lass_launch_istft2(real, imag, ClipForm{B, W, nullptr, starts, keep, total}, T, n_fft, win_length, LASS_HOP,
+    HIP_TRY(c, lass_launch_istft2(real, imag, ClipForm{B, W, nullptr, starts, keep, total}, T, n_fft, win_length, c->g.hop,
                                   c->tw2k, out, (hipStream_t)stream));
     return 0;
 }
@@ -1747,7 +1784,7 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
     }
     {
         ProfScope ps(c, st, P_ISTFT);
-        HIP_TRY(c, lass_launch_istft2(F(pl.oreal), F(pl.oimag), cf, T, g.nfft, g.wins[g.mask_br], LASS_HOP, c->tw2k, out, st));
+        HIP_TRY(c, lass_launch_istft2(F(pl.oreal), F(pl.oimag), cf, T, g.nfft, g.wins[g.mask_br], g.hop, c->tw2k, out, st));
     }
     return 0;
 }
@@ -1898,8 +1935,8 @@ int lass_separate(lass_ctx* c, const float* mixture, const float* condition, flo
 
 int lass_ragged_bucket(const lass_ctx* c, int L, int* lo, int* hi) {
     if (!c || L <= c->g.nfft / 2) return LASS_ERR_ARG;
-    const int T = 1 + L / LASS_HOP, Tp = (T + 31) / 32 * 32;
-    if (lo) *lo = std::max(LASS_HOP * (Tp - 32), c->g.nfft / 2 + 1);
+    const int T = 1 + L / c->g.hop, Tp = (T + 31) / 32 * 32;
+    if (lo) *lo = std::max(c->g.hop * (Tp - 32), c->g.nfft / 2 + 1);
     if (hi) *hi = L;  // a row holds L samples
     return 0;
 }

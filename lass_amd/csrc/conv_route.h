@@ -367,13 +367,14 @@ struct ModelTable {
     BlockShape enc_shape(int i) const { return BlockShape{E[i].cin, E[i].cout, fcrop >> i}; }  // behind i frequency halvings
     BlockShape dec_shape(int d) const { return BlockShape{dec_cat[d], D[d].cout, fcrop >> (5 - d)}; }  // at its skip's level
 };
-inline ModelTable model_table(int windows) {
+// fcrop: n_fft / 2 of the context's STFT geometry - 512 (n_fft 1024) or 1024 (n_fft 2048: ResUNet30 at 32 kHz, and every multi-STFT model)
+inline ModelTable model_table(int windows, int fcrop) {
     ModelTable m;
     for (int i = 0; i < 7; ++i) m.E[i] = kEnc[i];
     for (int d = 0; d < 6; ++d) m.D[d] = kDec[d];
     m.windows = windows;
     m.nbr = windows ? windows : 1;
-    m.fcrop = windows ? 1024 : 512;
+    m.fcrop = fcrop;
     m.E[1].cin = kPreCh * m.nbr;  // the branches' pools, channel-concatenated
     for (int d = 0; d < 6; ++d) m.dec_cat[d] = m.D[d].cout + m.E[5 - d].cout * (d == 5 ? m.nbr : 1);
     return m;

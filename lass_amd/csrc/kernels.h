@@ -6,6 +6,8 @@
 
 #include "conv_route.h"  // ConvKind, the shape rules of the f32 conv families and the route of a block (host only, HIP-free)
 
+// The default STFT geometry (lass_create).  A context carries its own (api.hip: Geometry - n_fft, hop, bins), and every launch
+// interface below takes them as arguments: these four name the default's values, nothing reads them as "the" geometry.
 constexpr int LASS_NFFT = 1024;
 constexpr int LASS_HOP = 160;
 constexpr int LASS_NBINS = 513;
@@ -72,7 +74,7 @@ struct ConvArgs {
     const float* pool_act_shift = nullptr;  // [B][act_shift_bs]
     const float* pre_w = nullptr;  // pre_conv (1x1, 1 -> 32) weight / bias for the *_PRE kinds
     const float* pre_b = nullptr;
-    // fused output head (decoder_block6.conv2 only, N == 32, W == 512): after_conv (1x1, 32 -> 3, + bias) and the complex
+    // fused output head (decoder_block6.conv2 only, N == 32, W == mask_nbins - 1: 512 or 1024 bins, the kernels read W): after_conv (1x1, 32 -> 3, + bias) and the complex
     // ratio mask (resunet.py:570-574,436-519) in the epilogue; the block's own output is then not written at all
     const float* mask_w = nullptr;    // after_conv.weight [3][32]
     const float* mask_b = nullptr;    // after_conv.bias [3]
@@ -82,7 +84,7 @@ struct ConvArgs {
     float* mask_re = nullptr;         // (B, mask_T, 513) separated spectrum
     float* mask_im = nullptr;
     int mask_T = 0;                   // frames (rows y >= mask_T are the T padding: dropped)
-    int mask_nbins = LASS_NBINS;      // bins per spectrum row = W + 1 (513; 1025 for the multi-STFT model)
+    int mask_nbins = LASS_NBINS;      // bins per spectrum row = W + 1 (513; 1025 at n_fft 2048: ResUNet30 at 32 kHz, the multi-STFT model)
     float* pool_out = nullptr;  // fused avg-pool of the output: (B, N, H/pool_h, W/2), batch stride pool_bs
     long pool_bs = 0;            // elements between clips of pool_out; 0 = dense (N * H/pool_h * W/2).  A launch that
                                  // produces a channel slice of a wider pooled tensor passes the wide tensor's stride.

@@ -318,9 +318,24 @@ __global__ __launch_bounds__(256) void stft2_kernel(const float* __restrict__ wa
 // ragged row gain only exact zeros).  No frame scratch in HBM.  A span that meets nothing its clip stores writes its zeros
 // and returns before it loads a twiddle: with a second of context either side of a five-second window that is two spans in
 // five.
-constexpr int ISTFT_SPAN = 16 * LASS_HOP;
+// SPAN is a property of the STFT geometry (its hop): the LDS of a workgroup is A + Bf + TW = 24 * N bytes plus acc + env = 8 bytes
+// per span sample, and a span of S samples runs the (S + wlen) / hop frames that reach into it for the S / hop that start in it.
+//   hop 160: 16 hops = 2 560 samples - 44 KiB at N = 1024 (three workgroups per CU), 68 KiB at N = 2048 (two).
+//   hop 320: kIstftSpanHops320 hops.  8 hops = the same 2 560 samples and 68 KiB: two workgroups per CU, (8 + 6.4) / 8 = 1.8 x
+//            redundant transforms.  16 hops = 5 120 samples and 88 KiB: one workgroup per CU, 1.4 x.  Measured on an MI355X at
+//            B = 16, L = 320 000 (tools/geometry_bench.py --istft): 8 hops 0.214 ms, 16 hops 0.293 ms -
+//            8 ships; the build-time override below exists for that measurement alone.
+// The frames of a span are visited in ascending order whatever the span, and a sample's sum never leaves its span: the value of
+// a sample does not depend on the clip form, only (through the pairing of frames) on the span constant.
+#ifndef LASS_ISTFT_SPAN_HOPS_320
+#define LASS_ISTFT_SPAN_HOPS_320 8
+#endif
+constexpr int kIstftSpanHops320 = LASS_ISTFT_SPAN_HOPS_320;
+constexpr int kIstftSpan160 = 16 * LASS_HOP;
+constexpr int kIstftSpan320 = kIstftSpanHops320 * 320;
+static_assert(kIstftSpanHops320 == 8 || kIstftSpanHops320 == 16, "8 or 16 hops per span at hop 320");
 
-template <int N, class Clips>
+template <int N, int ISTFT_SPAN, class Clips>
 __global__ __launch_bounds__(256) void istft2_kernel(const float* __restrict__ real, const float* __restrict__ imag,
                                                      Clips clips, int T, int hop, int wlen,
                                                      const float2* __restrict__ tw2k, float* __restrict__ out) {
@@ -457,13 +472,17 @@ hipError_t lass_launch_stft2(const float* wav, const ClipForm& cf, int n_fft, in
 hipError_t lass_launch_istft2(const float* real, const float* imag, const ClipForm& cf, int T, int n_fft, int wlen, int hop,
                               const float2* tw2k, float* wav, hipStream_t stream) {
     const int B = cf.B, L = cf.L;
-    if (B <= 0 || hop != LASS_HOP || bad_transform(n_fft, wlen)) return hipErrorInvalidValue;
+    // the two geometries: hop 160 at either transform size, hop 320 at n_fft 2048
+    if (B <= 0 || (hop != LASS_HOP && !(hop == 320 && n_fft == 2048)) || bad_transform(n_fft, wlen)) return hipErrorInvalidValue;
     if (cf.starts || cf.lengths ? (L <= n_fft / 2 || T != 1 + L / hop) : (T <= 0 || L <= 0)) return hipErrorInvalidValue;
     if (cf.starts && (!cf.keep || !wav || cf.total < L)) return hipErrorInvalidValue;
-    dim3 grid((n_fft / 2 + L + ISTFT_SPAN - 1) / ISTFT_SPAN, B);
+    const int span = hop == LASS_HOP ? kIstftSpan160 : kIstftSpan320;
+    dim3 grid((n_fft / 2 + L + span - 1) / span, B);
     with_clips(cf, n_fft, hop, [&](auto clips) {
         using C = decltype(clips);
-        const auto kernel = n_fft == 1024 ? istft2_kernel<1024, C> : istft2_kernel<2048, C>;
+        const auto kernel = n_fft == 1024      ? istft2_kernel<1024, kIstftSpan160, C>
+                            : hop == LASS_HOP ? istft2_kernel<2048, kIstftSpan160, C>
+                                              : istft2_kernel<2048, kIstftSpan320, C>;
         hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, real, imag, clips, T, hop, wlen, tw2k, wav);
     });
     return hipGetLastError();

@@ -22,9 +22,15 @@ def _stream(device) -> c_void_p:
 class Engine:
     """One context per (process, device)."""
 
-    def __init__(self, device="cuda:0", multistft=None):
+    def __init__(self, device="cuda:0", multistft=None, stft=None):
         """multistft: None = ResUNet30 (models/resunet.py); (n_fft, win_lengths, mask_window) = the multi-resolution-STFT
-        separator (lass_create_multistft)."""
+        separator (lass_create_multistft).  stft: ResUNet30's STFT geometry (n_fft, hop) - None or (1024, 160) = the reference's
+        16 kHz layout, (2048, 320) = the same network at 32 kHz (lass_create_stft; arch.STFT_GEOMETRIES).  Every method takes
+        its frame counts, bucket and length limits from it (`n_fft`, `hop`)."""
+        if stft is not None:
+            if multistft is not None:
+                raise ValueError("stft=(n_fft, hop) is ResUNet30's geometry: the multi-STFT model has its own (n_fft, hop 160)")
+            stft = arch.check_stft(*stft)
         self.lib = _lib.load()
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -36,7 +42,7 @@ class Engine:
         h = c_void_p()
         self.multistft = None
         if multistft is None:
-            rc = self.lib.lass_create(byref(h), idx)
+            rc = self.lib.lass_create(byref(h), idx) if stft is None else self.lib.lass_create_stft(byref(h), idx, stft[0], stft[1])
         else:
             n_fft, wins, mask_window = int(multistft[0]), [int(w) for w in multistft[1]], int(multistft[2])
             rc = self.lib.lass_create_multistft(byref(h), idx, n_fft, len(wins), (c_int * len(wins))(*wins), mask_window)
@@ -44,7 +50,10 @@ class Engine:
         if rc < 0:
             raise _lib.LassError(f"lass_create failed ({rc}): {self.lib.lass_last_error(None).decode()}")
         self.ctx = h
-        self.n_fft = 1024 if multistft is None else self.multistft[0]
+        n_fft, hop = c_int(), c_int()
+        _lib.check(self.ctx, self.lib.lass_stft_geometry(self.ctx, byref(n_fft), byref(hop)), "lass_stft_geometry")
+        self.n_fft, self.hop = n_fft.value, hop.value  # the context's word: (1024, 160), (2048, 320), or the multi-STFT model's
+        self._stage_n_fft = self.n_fft if multistft is None else arch.N_FFT  # stft_magphase / istft (lass_stft_magphase)
         self.n_branches = 1 if multistft is None else len(self.multistft[1])
         self._ws_buf: Optional[torch.Tensor] = None  # ONE workspace, as large as the largest (B, L) seen so far
         self._ws_last = None                         # (B, L) of the last call that used it (its intermediates live there)
@@ -263,8 +272,8 @@ class Engine:
     def stft_magphase(self, wav: torch.Tensor, want_complex: bool = False):
         wav = self._dev(wav)
         B, L = wav.shape
-        T = arch.frames_for(L)
-        mk = lambda: torch.empty(B, T, arch.N_BINS, dtype=torch.float32, device=self.device)  # noqa: E731
+        T = arch.frames_for(L, self.hop)
+        mk = lambda: torch.empty(B, T, self._stage_n_fft // 2 + 1, dtype=torch.float32, device=self.device)  # noqa: E731
         mag, cos, sin = mk(), mk(), mk()
         re, im = (mk(), mk()) if want_complex else (None, None)
         rc = self.lib.lass_stft_magphase(self.ctx, _ptr(wav), B, L, _ptr(mag), _ptr(cos), _ptr(sin), _ptr(re),
@@ -290,7 +299,7 @@ class Engine:
     def istft(self, real: torch.Tensor, imag: torch.Tensor, length: int):
         real, imag = self._dev(real), self._dev(imag)
         B, T, F = real.shape
-        assert F == arch.N_BINS and imag.shape == real.shape
+        assert F == self._stage_n_fft // 2 + 1 and imag.shape == real.shape
         wav = torch.empty(B, length, dtype=torch.float32, device=self.device)
         rc = self.lib.lass_istft(self.ctx, _ptr(real), _ptr(imag), B, T, length, _ptr(wav), None, _stream(self.device))
         _lib.check(self.ctx, rc, "lass_istft")
@@ -335,11 +344,11 @@ class Engine:
 
     def front_end(self, wav: torch.Tensor, out=None):
         """(B,L) -> (mag, cos, sin (B,T,n_fft/2+1), x0): STFT + bn0 + T-pad + F-crop (resunet.py:533-552).
-        x0 is (B,Tpad,512) for ResUNet30 and (n_windows,B,Tpad,1024) for the multi-STFT model (mag/cos/sin are then the
+        x0 is (B,Tpad,n_fft/2) for ResUNet30 (512 bins, 1024 at the (2048, 320) geometry) and (n_windows,B,Tpad,1024) for the multi-STFT model (mag/cos/sin are then the
         mask window's).  `out` = a (mag, cos, sin, x0) tuple of an earlier call to write into (no allocation in this call)."""
         wav = self._dev(wav)
         B, L = wav.shape
-        T = arch.frames_for(L)
+        T = arch.frames_for(L, self.hop)
         nb = self.n_fft // 2 + 1
         shape = (B, arch.padded_frames(T), nb - 1)
         x0_shape = (self.n_branches,) + shape if self.multistft else shape
@@ -359,11 +368,11 @@ class Engine:
 
     def front_end_ragged(self, wav: torch.Tensor, lengths, checked: bool = False):
         """`front_end` with a length per clip (lass_front_end_ragged): same shapes as for B clips of L samples; beyond clip b's
-        own 1 + lengths[b] // 160 frames x0 and mag / cos / sin are zero."""
+        own 1 + lengths[b] // hop frames x0 and mag / cos / sin are zero."""
         wav = self._dev(wav)
         B, L = wav.shape
         lens = self._ragged_lengths(lengths, B, L, checked, "front_end_ragged")
-        T = arch.frames_for(L)
+        T = arch.frames_for(L, self.hop)
         nb = self.n_fft // 2 + 1
         shape = (B, arch.padded_frames(T), nb - 1)
         mk = lambda: torch.empty(B, T, nb, dtype=torch.float32, device=self.device)  # noqa: E731
@@ -376,8 +385,8 @@ class Engine:
 
     def istft_ragged(self, real: torch.Tensor, imag: torch.Tensor, lengths, length: int, n_fft: Optional[int] = None,
                      win_length: Optional[int] = None, checked: bool = False):
-        """`istft_nfft` with a length per clip (lass_istft_ragged): real, imag (B, 1 + length // 160, n_fft/2+1) -> (B, length),
-        clip b from its own first 1 + lengths[b] // 160 frames, zero from lengths[b] on."""
+        """`istft_nfft` with a length per clip (lass_istft_ragged): real, imag (B, 1 + length // hop, n_fft/2+1) -> (B, length),
+        clip b from its own first 1 + lengths[b] // hop frames, zero from lengths[b] on."""
         real, imag = self._dev(real), self._dev(imag)
         n_fft = self.n_fft if n_fft is None else int(n_fft)
         win_length = n_fft if win_length is None else int(win_length)
@@ -399,7 +408,7 @@ class Engine:
         total, W = recording.shape[0], int(window)
         B = len(starts)
         idx_s, _ = self._window_index(starts, None, total, W, checked, "front_end_windows")
-        T = arch.frames_for(W)
+        T = arch.frames_for(W, self.hop)
         nb = self.n_fft // 2 + 1
         shape = (B, arch.padded_frames(T), nb - 1)
         mk = lambda: torch.empty(B, T, nb, dtype=torch.float32, device=self.device)  # noqa: E731
@@ -412,7 +421,7 @@ class Engine:
 
     def istft_windows(self, real: torch.Tensor, imag: torch.Tensor, starts, keep, window: int, out: torch.Tensor,
                       n_fft: Optional[int] = None, win_length: Optional[int] = None, checked: bool = False) -> torch.Tensor:
-        """`istft_nfft` for windows (lass_istft_windows): real, imag (B, 1 + window // 160, n_fft/2+1); of window b's `window`
+        """`istft_nfft` for windows (lass_istft_windows): real, imag (B, 1 + window // hop, n_fft/2+1); of window b's `window`
         samples only keep[b] = [lo, hi) is stored, at out[starts[b] + lo : starts[b] + hi] of the 1-D `out`."""
         real, imag, out = self._dev(real), self._dev(imag), self._dev(out)
         n_fft = self.n_fft if n_fft is None else int(n_fft)
@@ -462,7 +471,7 @@ class Engine:
         cos_mask, sin_mask, condition = self._dev(cos_mask), self._dev(sin_mask), self._dev(condition)
         B, T, F = mags[0].shape
         if len(mags) != self.n_branches or any(m.shape != (B, T, F) for m in mags) or F != self.n_fft // 2 + 1 \
-                or cos_mask.shape != (B, T, F) or sin_mask.shape != (B, T, F) or T != arch.frames_for(length) \
+                or cos_mask.shape != (B, T, F) or sin_mask.shape != (B, T, F) or T != arch.frames_for(length, self.hop) \
                 or condition.shape != (B, arch_cond()):
             raise _lib.LassError("separate_components: inconsistent shapes")
         out = torch.empty(B, length, dtype=torch.float32, device=self.device)
@@ -504,7 +513,7 @@ class Engine:
         x12, mag, cos, sin = map(self._dev, (x12, mag, cos, sin))
         B, C, Tp, F = x12.shape
         T = mag.shape[1]
-        assert C == 32 and F == arch.F_CROP
+        assert C == 32 and F == self.n_fft // 2
         o_re = torch.empty_like(mag)
         o_im = torch.empty_like(mag)
         rc = self.lib.lass_mask_apply(self.ctx, _ptr(x12), _ptr(mag), _ptr(cos), _ptr(sin), B, T, Tp, _ptr(o_re),

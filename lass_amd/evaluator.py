@@ -393,6 +393,7 @@ class DCASEEvaluator:
             items, loader = decoded, (lambda t: t)
         n = len(items)
         n_fft = getattr(getattr(ss, "engine", None), "n_fft", 1024)
+        hop = getattr(getattr(ss, "engine", None), "hop", 160)
         window = 4 * self.batch_size
         order: List[int] = []
         pending_stats = []
@@ -408,7 +409,7 @@ class DCASEEvaluator:
                 lengths = [int(c[0].shape[0]) for c in clips]
                 if any(c[1].shape[0] != m for c, m in zip(clips, lengths)):
                     raise ValueError("a source and its noise clip differ in length")
-                for idx, row in plan_batches(lengths, self.batch_size, n_fft):
+                for idx, row in plan_batches(lengths, self.batch_size, n_fft, hop):
                     pad = lambda x: np.pad(x, (0, row - x.shape[0]))  # noqa: E731
                     snr_col = [np.full(1, float(clips[i][2]), dtype=np.float32) for i in idx]
                     src, noise, snr = stager.put([[pad(clips[i][0]) for i in idx], [pad(clips[i][1]) for i in idx], snr_col])

@@ -41,8 +41,13 @@ def _init_tensor(kind: str, shape) -> torch.Tensor:
 
 
 class ResUNet30(nn.Module):
-    def __init__(self, input_channels: int = 1, output_channels: int = 1, condition_size: int = 512):
+    def __init__(self, input_channels: int = 1, output_channels: int = 1, condition_size: int = 512, *, n_fft: int = arch.N_FFT,
+                 hop: int = arch.HOP):
+        """n_fft, hop: the model's STFT geometry - (1024, 160), the reference's 16 kHz layout, or (2048, 320), the same network
+        at 32 kHz with a 1025-bin bn0 (arch.STFT_GEOMETRIES; upstream AudioSep's released model).  Every method below takes
+        its frame counts, bucket width and length limits from it, through the engine."""
         super().__init__()
+        self.n_fft, self.hop = arch.check_stft(n_fft, hop)
         if (input_channels, output_channels, condition_size) != (1, 1, 512):
             # config/audiosep_base.yaml:23-30 is the only configuration the reference ships or evaluates
             raise NotImplementedError("lass_amd.ResUNet30 supports input_channels=1, output_channels=1, "
@@ -68,13 +73,13 @@ class ResUNet30(nn.Module):
 
     # ---- what a variant of the model overrides (lass_amd/resunet_with_multistft.py) ---------------------------------
     def _param_specs(self):
-        return arch.param_specs(self.input_channels, self.output_channels, self.condition_size)
+        return arch.param_specs(self.input_channels, self.output_channels, self.condition_size, n_fft=self.n_fft)
 
     def _film_sites(self):
         return arch.film_sites()
 
     def _make_engine(self, dev) -> Engine:
-        return Engine(dev)
+        return Engine(dev, stft=(self.n_fft, self.hop))
 
     def _film_meta(self) -> Dict:
         """Nested {module: {'beta1': C, 'beta2': C}} as get_film_meta returns (resunet.py:598-618)."""
@@ -90,9 +95,26 @@ class ResUNet30(nn.Module):
     # ---- state handling ------------------------------------------------------------------------------------------
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
         sd = {k: v for k, v in state_dict.items() if not k.startswith(_IGNORED_PREFIXES)}
+        self._check_geometry(sd)
         r = super().load_state_dict(sd, strict=strict, **kw)
         self._uploaded_sig = None
         return r
+
+    def _check_geometry(self, sd) -> None:
+        """A checkpoint of the other STFT geometry differs in `base.bn0.*` alone (n_fft/2 + 1 entries): say which model it
+        needs instead of leaving a bare shape mismatch."""
+        own = getattr(getattr(self, "base", None), "bn0", None)
+        w = sd.get("base.bn0.weight")
+        if own is None or w is None or getattr(w, "ndim", 0) != 1:
+            return
+        have, got = int(own.weight.shape[0]), int(w.shape[0])
+        if got == have:
+            return
+        match = [g for g in arch.STFT_GEOMETRIES if g[0] // 2 + 1 == got]
+        hint = (f"it belongs to ResUNet30(..., n_fft={match[0][0]}, hop={match[0][1]})" if match else
+                "no supported (n_fft, hop) has that many bins")
+        raise ValueError(f"base.bn0 of this state dict has {got} entries, this model was built with n_fft={self.n_fft}, "
+                         f"hop={self.hop} ({have} bins): {hint}")
 
     def set_compute_dtype(self, compute_dtype: str) -> "ResUNet30":
         if compute_dtype not in Engine.COMPUTE_MODES:
@@ -174,7 +196,7 @@ class ResUNet30(nn.Module):
             raise ValueError(f"conditions must be ({n}, {self.condition_size})")
         lengths = [int(w.shape[0]) for w in waveforms]
         results: List[Optional[torch.Tensor]] = [None] * n
-        for idx, row_length in ragged.plan_batches(lengths, max_batch, eng.n_fft):
+        for idx, row_length in ragged.plan_batches(lengths, max_batch, eng.n_fft, eng.hop):
             mix = torch.zeros(len(idx), row_length, dtype=torch.float32, device=dev)
             for r, i in enumerate(idx):
                 mix[r, :lengths[i]].copy_(waveforms[i], non_blocking=True)

@@ -34,6 +34,7 @@ class ResUNet30(_ResUNet30):
             raise NotImplementedError("the mask / re-synthesis window (512, resunet_with_multistft.py:36-44,185-188) "
                                       "must be one of win_lengths")
         super().__init__(input_channels, output_channels, condition_size)
+        self.n_fft = arch.MS_N_FFT  # every window at the common transform size, hop 160 (the engine's geometry)
 
     def _param_specs(self):
         return arch.ms_param_specs(self.input_channels, self.output_channels, self.condition_size, self.win_lengths)

@@ -30,13 +30,14 @@ def _xavier_bound(shape: Tuple[int, ...], kind: str) -> float:
 
 
 def make_state_dict(seed: int = SEED, input_channels: int = 1, output_channels: int = 1,
-                    condition_size: int = 512, specs=None) -> Dict[str, np.ndarray]:
+                    condition_size: int = 512, specs=None, n_fft: int = arch.N_FFT) -> Dict[str, np.ndarray]:
     """Seeded numpy state_dict with the reference's keys (float32; num_batches_tracked int64).  `specs` defaults to
-    arch.param_specs(...) (ResUNet30); pass arch.ms_param_specs(...) for the multi-STFT model."""
+    arch.param_specs(..., n_fft=n_fft) (ResUNet30; n_fft=2048: the 32 kHz geometry's 1025-entry bn0, which is drawn first, so
+    that model's stream differs from the default's from the start); pass arch.ms_param_specs(...) for the multi-STFT model."""
     rng = np.random.Generator(np.random.PCG64(seed))
     sd: Dict[str, np.ndarray] = {}
     if specs is None:
-        specs = arch.param_specs(input_channels, output_channels, condition_size)
+        specs = arch.param_specs(input_channels, output_channels, condition_size, n_fft=n_fft)
     for name, shape, kind in specs:
         if kind in ("conv_w", "tconv_w", "linear_w"):
             b = _xavier_bound(shape, kind)

@@ -34,9 +34,11 @@ def parse_yaml(config_yaml: str) -> Dict:
 
 def _build(configs: Dict) -> nn.Module:
     m = configs["model"]
+    # optional `model.n_fft` / `model.hop`: the separator's STFT geometry (config/audiosep_32k.yaml); absent = the class default
+    stft = {k: int(m[k]) for k in ("n_fft", "hop") if m.get(k) is not None}
     return get_model_class(model_type=m["model_type"])(input_channels=m["input_channels"],
                                                       output_channels=m["output_channels"],
-                                                      condition_size=m["condition_size"])
+                                                      condition_size=m["condition_size"], **stft)
 
 
 def get_ss_model(config_yaml) -> nn.Module:

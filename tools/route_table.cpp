@@ -2,13 +2,15 @@
 // block (the f32 rule), one per transposed conv, in the bf16 modes one per block (form and hand-overs), and the profiler scopes.
 // Host only: g++ -std=c++17 -I lass_amd/csrc tools/route_table.cpp -o tools/bin/route_table
 // usage: route_table T_PAD [MIN_CIN=32] [VPREP_MODE=1] [FORCED_SPLITS=0] [X_ALIGNED=1] [STFT_WINDOWS=0] [B=1] [HEAD_FOLD=1] [HEAD=1]
-//                    [HEAD_SC_FOLD=1] [MODE=0] [FUSE_CATB=1] [FUSE_BLOCK=1] [FUSE_UP=1]
+//                    [HEAD_SC_FOLD=1] [MODE=0] [FUSE_CATB=1] [FUSE_BLOCK=1] [FUSE_UP=1] [N_FFT=0]
 //   MODE 0: f32, 1: bf16, 2: bf16x3; FUSE_*: the LASS_FUSE_* switches of the bf16 mode.  With MODE given (any value) the up,
 //   bf16 and scopes lines follow the conv and block lines; without it the output is the conv and block lines alone.
 //   HEAD 1: decoder_block6 as lass_separate runs it, the output head in conv2's epilogue; 0: as the stage call runs it, without
 //   HEAD_SC_FOLD: the switch of the head_sc_fold route (plan_head_sc_fold); the route itself needs HEAD = 1 as well
 //   STFT_WINDOWS 0: ResUNet30 (512 bins); n > 0: the multi-STFT model with n analysis windows (1024 bins), rows named as
 //   lass_amd.arch.ms_conv_layer_table names them (encoder_block1s.<k> for window k).
+//   N_FFT 0: the model's own (1024 for ResUNet30, 2048 for the multi-STFT model); 2048 with STFT_WINDOWS 0: ResUNet30 at the
+//   32 kHz geometry (1024 bins).
 // conv <name> <direct|f2x2|f4x4|none> <kind> <splits> <v> fold=<0|1> scfold=<0|1>     block <name> shortcut=<gemm|fused|-> kpart=<floats> v=<floats>
 // up <decoder> <direct|gemm|bf16|tconv_logits|inside> in_act=<0|1> out_copies=<0|1>
 // bf16 <block> form=<f32|two|enc1|dec6|dec6u> cat_in=<0|1> skip_out=<0|1> pool_copies=<0|1> act_out=<0|1>      (MODE 1, 2)
@@ -46,7 +48,7 @@ void print_bf16(const std::string& name, const Bf16Block& b) {
 int main(int argc, char** argv) {
     if (argc < 2) {
         fprintf(stderr, "usage: %s T_PAD [MIN_CIN=32] [VPREP_MODE=1] [FORCED_SPLITS=0] [X_ALIGNED=1] [STFT_WINDOWS=0] [B=1] [HEAD_FOLD=1] [HEAD=1] "
-                        "[HEAD_SC_FOLD=1] [MODE=0] [FUSE_CATB=1] [FUSE_BLOCK=1] [FUSE_UP=1]\n", argv[0]);
+                        "[HEAD_SC_FOLD=1] [MODE=0] [FUSE_CATB=1] [FUSE_BLOCK=1] [FUSE_UP=1] [N_FFT=0]\n", argv[0]);
         return 2;
     }
     const auto arg = [&](int i, int dflt) { return argc > i ? atoi(argv[i]) : dflt; };
@@ -65,7 +67,9 @@ int main(int argc, char** argv) {
     const bool aligned = arg(5, 1) != 0;
     if (t_pad <= 0 || nwin < 0 || nwin > 4 || B <= 0 || mode < 0 || mode > 2) return 2;
     cfg.mode = (ComputeMode)mode;
-    const ModelTable m = model_table(nwin);
+    const int n_fft = arg(15, 0) ? arg(15, 0) : nwin ? 2048 : 1024;
+    if ((n_fft != 1024 && n_fft != 2048) || (nwin && n_fft != 2048)) return 2;
+    const ModelTable m = model_table(nwin, n_fft / 2);
     const int nbr = m.nbr, fcrop = m.fcrop;
     const Levels lv = model_levels(m, t_pad);
     const int *eh = lv.eh, *ew = lv.ew;
