@@ -219,6 +219,14 @@ int lass_set_head_sc_fold(lass_ctx* ctx, int enabled);
  * which layers they are, and every workspace size, stay as they were.  The two differ by f32 rounding only.  Non-finite
  * activations are outside the split's contract.  The bf16 modes run no such launch and ignore the switch. */
 int lass_set_pw_split(lass_ctx* ctx, int enabled);
+/* f32: the F(4x4,3x3) convs with 384 output channels that read their transformed input from memory (both convs of encoder_block5-6
+ * and decoder_block1-2) run as three launches - a scatter that writes the transformed input in GEMM layout, 36 batched GEMMs on the
+ * bf16 matrix unit at f32 accuracy (the split of lass_set_pw_split, on weight images lass_finalize keeps: 216 bytes per (cin, cout)
+ * pair), and a gather that applies the output transform and the epilogue.  1 = that route (default), 0 = the prep + conv (+ combine)
+ * launches (A/B, tests; LASS_WINO4_GEMM at lass_create).  The two differ by f32 rounding only; a clip's result never depends on its
+ * batch on either.  The rule looks at the layer's shape only.  The bf16 modes, LASS_WINO4=0, lass_set_wino4_vprep(0) and a forced
+ * split factor (lass_set_wino4_splits) never take the route.  Query lass_workspace_bytes again afterwards. */
+int lass_set_wino4_gemm(lass_ctx* ctx, int enabled);
 /* UNSTABLE, tests only - not part of the supported interface, and may change or go without notice; lass_separate never looks at
  * it.  The stage calls (lass_convblock, lass_encoder_block) keep that image in `v` (`floats` f32 of device memory owned by the
  * caller) instead of a buffer of the context; NULL restores the context's.  A buffer that is too small for a layer, or overlaps

@@ -53,6 +53,7 @@ SYMBOLS = [
     ("lass_set_head_fold", c_int, [c_void_p, c_int]),
     ("lass_set_head_sc_fold", c_int, [c_void_p, c_int]),
     ("lass_set_pw_split", c_int, [c_void_p, c_int]),
+    ("lass_set_wino4_gemm", c_int, [c_void_p, c_int]),
     ("lass_separate_components", c_int, [c_void_p, POINTER(c_void_p), c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                          c_int, c_void_p, c_size_t, c_void_p]),
     ("lass_stft_components", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, POINTER(c_int),

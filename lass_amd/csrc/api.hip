@@ -50,6 +50,7 @@ struct ResBlock {  // one ConvBlockRes
     // decoder_block6, f32: conv2 and the shortcut composed with after_conv (head_fold.h) - U images, Wsc' [cin][16], b' [16]
     float *u2h = nullptr, *wsch = nullptr, *bh = nullptr;
     void* wsc3 = nullptr;  // f32: wsc as the three bf16 pieces of pw_gemm.hip's split kernel (the shortcut-GEMM layers)
+    void *u1g = nullptr, *u2g = nullptr;  // f32: u1f / u2f as the three bf16 pieces of wino4_gemm.hip's GEMMs (conv_route.h: lass_wino4_gemm_weights)
 };
 
 struct ProfEntry {
@@ -105,6 +106,8 @@ struct lass_ctx {
     float *hs_wt = nullptr, *hs_wskip = nullptr;  // head_fold.h: Wt' [cin][64] for that transposed conv, Wsc'_skip [3][32] (lass_finalize)
     float* stage_v = nullptr;      // ... their V image in the stage calls, grown on demand like stage_part (Plan::vprep in lass_separate)
     size_t stage_v_floats = 0;
+    float* stage_m = nullptr;      // ... and the product image of the gemm route, grown on demand (Plan::mgemm in lass_separate)
+    size_t stage_m_floats = 0;
     float* stage_v_user = nullptr; // lass_set_wino4_vprep_buffer: a caller-owned image buffer for the stage calls instead
     size_t stage_v_user_floats = 0;
     float* stage_part = nullptr;   // split-K partials of the stage calls (lass_convblock, lass_encoder_block), grown on demand;
@@ -440,6 +443,8 @@ struct BlockFusions {
     float* kpart = nullptr;                 // f32: the block's split-K partials, BlockRoute::kpart_floats of them (conv_route.h)
     float* vws = nullptr;                   // f32: the transformed input image of one conv at a time (the V-from-memory layers),
     size_t vws_floats = 0;                  // at least BlockRoute::v_floats
+    float* mws = nullptr;                   // f32: the product image of one conv at a time on the gemm route (wino4_gemm.hip),
+    size_t mws_floats = 0;                  // at least BlockRoute::m_floats
     const HeadScPlanes* planes = nullptr;   // f32, encoder_block1 / decoder_block6 of lass_separate: the head's shortcut logits as
                                             // planes (Plan::sc_planes) - written by conv2's epilogue / read by the folded head
 };
@@ -501,7 +506,7 @@ int run_resblock_bf16(lass_ctx* c, const ResBlock& rb, Bf16Form form, const Conv
 // One f32 conv launch of a block as its route says.  The pointer-taking predicate of the chosen family has the last word: where
 // it contradicts the route (which saw the shape and the call-site facts of BlockIO only) nothing is launched.
 int launch_routed(lass_ctx* c, const ResBlock& rb, const char* what, const ConvRoute& rt, const ConvArgs& a, const Wino4Split& sk,
-                  float* vws, hipStream_t st, const HeadScPlanes* planes = nullptr) {
+                  float* vws, const Wino4Gemm& wg, hipStream_t st, const HeadScPlanes* planes = nullptr) {
     ProfScope ps(c, st, P_CONV3X3);
     bool ok = true;
     switch (rt.family) {
@@ -517,6 +522,11 @@ int launch_routed(lass_ctx* c, const ResBlock& rb, const char* what, const ConvR
             if (rt.head_fold) {
                 ok = lass_wino4_headfold_supported(a);
                 if (ok) HIP_TRY(c, lass_launch_wino4_headfold(a, st));
+                break;
+            }
+            if (rt.gemm) {  // scatter, 36 GEMMs, gather: three launches under this conv's scope, as the prep launch shares it
+                ok = lass_wino4_gemm_supported(rt.kind, a, vp, wg);
+                if (ok) HIP_TRY(c, lass_launch_wino4_gemm(rt.kind, a, vp, wg, st));
                 break;
             }
             ok = rt.v_from_memory ? lass_wino4_vpre_supported(rt.kind, a, s) : lass_wino4_supported(rt.kind, a, s);
@@ -586,6 +596,18 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
         if (overlaps(B, f.vws, 0, rt.v_floats, x, x_bs, xn) || overlaps(B, f.vws, 0, rt.v_floats, a2, on, on) ||
             overlaps(B, f.vws, 0, rt.v_floats, out, out_bs, on) || overlaps(B, f.vws, 0, rt.v_floats, f.kpart, 0, rt.kpart_floats))
             return fail(c, LASS_ERR_STATE, "the V image must not overlap the block's input, intermediate, output or split-K partials");
+    }
+    if (rt.m_floats) {  // ... and so does the M slot of the gemm route
+        if (!f.mws || f.mws_floats < rt.m_floats) return fail(c, LASS_ERR_STATE, "the gemm route needs its product-image workspace");
+        if (overlaps(B, f.mws, 0, rt.m_floats, x, x_bs, xn) || overlaps(B, f.mws, 0, rt.m_floats, a2, on, on) ||
+            overlaps(B, f.mws, 0, rt.m_floats, out, out_bs, on) || overlaps(B, f.mws, 0, rt.m_floats, f.kpart, 0, rt.kpart_floats) ||
+            overlaps(B, f.mws, 0, rt.m_floats, f.vws, 0, rt.v_floats))
+            return fail(c, LASS_ERR_STATE, "the product image must not overlap the block's input, intermediate, output or other workspaces");
+        if (f.pool_out) {
+            const size_t pn = on / ((size_t)f.pool_h * 2);
+            if (overlaps(B, f.mws, 0, rt.m_floats, f.pool_out, f.pool_bs ? f.pool_bs : (long)pn, pn))
+                return fail(c, LASS_ERR_STATE, "the product image must not overlap the block's pooled output");
+        }
     }
     if (f.planes) {  // the plan decided the route for three launches at once: a block that cannot follow it would leave the head
                      // with planes nobody wrote
@@ -662,8 +684,11 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
         q.in2 = nullptr; q.in2_bs = 0; q.Cin2 = 0; q.w2 = nullptr; q.bias = nullptr;
         q.res = out; q.res_bs = out_bs;
     }
-    if (int r = launch_routed(c, rb, "conv1", rt.conv1, p, sk, f.vws, st)) return r;
-    return launch_routed(c, rb, "conv2", rt.conv2, q, sk, f.vws, st, f.planes);
+    Wino4Gemm g1, g2;
+    g1.w3 = rb.u1g; g2.w3 = rb.u2g;
+    g1.m = g2.m = f.mws;
+    if (int r = launch_routed(c, rb, "conv1", rt.conv1, p, sk, f.vws, g1, st)) return r;
+    return launch_routed(c, rb, "conv2", rt.conv2, q, sk, f.vws, g2, st, f.planes);
 }
 
 int run_upconv(lass_ctx* c, int di, const float* x, int B, int h, int w, const float* shift, float* out, long out_bs,
@@ -721,6 +746,7 @@ struct Plan {
     size_t kpart = 0;  // split-K partials of the 32 x 16 Winograd blocks (one slot: the launches of a plan run in stream order)
     bool has_kpart = false;
     size_t vprep = 0, vprep_floats = 0;  // the V image of the V-from-memory layers: one slot, sized to the largest of them
+    size_t mgemm = 0, mgemm_floats = 0;  // the product image of the gemm-route layers (wino4_gemm.hip): one slot, the largest of them
     // conv_route.h's head_sc_fold: the folded head's shortcut logits as two sets of planes [B][3][Tp][fcrop], one written by
     // encoder_block1.conv2 and one by decoder_block6's transposed conv (last in the plan: no other offset depends on the switch)
     bool sc_planes = false;
@@ -787,13 +813,14 @@ int make_plan(const lass_ctx* c, int B, int L, Plan* pl) {
     pl->a2 = bump(t, a2max);
     pl->oreal = bump(t, spec); pl->oimag = bump(t, spec);
     // (a half-batch plan has its own slot: the two branches of the replayed graph never share partials)
-    size_t kmax = 0, vmax = 0;
+    size_t kmax = 0, vmax = 0, mmax = 0;
     // every block with a route of its own (conv_route.h), at its level's image size and with what lass_separate fuses into it
     // (the workspace hands every block an aligned input)
     const auto block = [&](const ResBlock& rb, int e, const BlockIO& io) {
         const BlockRoute rt = plan_block(c->cfg, BlockShape{rb.cin, rb.cout, rb.width}, B, pl->lv.eh[e], pl->lv.ew[e], io);
         kmax = std::max(kmax, rt.kpart_floats);
         vmax = std::max(vmax, rt.v_floats);
+        mmax = std::max(mmax, rt.m_floats);
     };
     for (int i = 1; i < 7; ++i) {
         BlockIO io;
@@ -809,6 +836,8 @@ int make_plan(const lass_ctx* c, int B, int L, Plan* pl) {
     if (kmax) pl->kpart = bump(t, kmax);
     pl->vprep_floats = vmax;
     if (vmax) pl->vprep = bump(t, vmax);
+    pl->mgemm_floats = mmax;
+    if (mmax) pl->mgemm = bump(t, mmax);
     pl->sc_planes = head_sc_planned(c, B, pl->lv.eh[0], pl->lv.ew[0]);
     pl->sp = plan_separate(c->cfg, c->m, pl->lv, pl->sc_planes);
     if (pl->sc_planes) {
@@ -866,6 +895,8 @@ int stage_scratch(lass_ctx* c, const ResBlock& rb, int B, int H, int W, const fl
         f->vws = c->stage_v_user ? c->stage_v_user : c->stage_v;
         f->vws_floats = c->stage_v_user ? c->stage_v_user_floats : c->stage_v_floats;
     }
+    if (int r = grow(&c->stage_m, &c->stage_m_floats, rt.m_floats)) return r;
+    if (rt.m_floats) { f->mws = c->stage_m; f->mws_floats = c->stage_m_floats; }
     return 0;
 }
 
@@ -925,6 +956,7 @@ static int create_impl(lass_ctx** out, int device_id, const Geometry& geom) {
     if (const char* e = getenv("LASS_HEAD_FOLD")) c->cfg.head_fold = atoi(e) != 0;  // A/B: lass_set_head_fold
     if (const char* e = getenv("LASS_HEAD_SC_FOLD")) c->cfg.head_sc_fold = atoi(e) != 0;  // A/B: lass_set_head_sc_fold
     if (const char* e = getenv("LASS_PW_SPLIT")) c->cfg.pw_split = atoi(e) != 0;  // A/B: lass_set_pw_split
+    if (const char* e = getenv("LASS_WINO4_GEMM")) c->cfg.wino4_gemm = atoi(e) != 0;  // A/B: lass_set_wino4_gemm
     if (const char* e = getenv("LASS_SPLIT")) c->split_batch = std::max(0, std::min(2, atoi(e)));
     if (const char* e = getenv("LASS_GRAPH")) c->use_graph = atoi(e) != 0;
     c->prof.resize(P_COUNT);
@@ -1022,6 +1054,7 @@ int lass_destroy(lass_ctx* c) {
     (void)hipFree(c->tw2k);
     (void)hipFree(c->stage_part);
     (void)hipFree(c->stage_v);
+    (void)hipFree(c->stage_m);
     delete c;
     return 0;
 }
@@ -1107,6 +1140,7 @@ int lass_finalize(lass_ctx* c, int compute_mode) {
         HIP_TRY(c, lass_launch_relayout_conv(w2, rb.cout, rb.cout, 9, rb.w2, st));
         rb.u1 = rb.u2 = rb.usc = nullptr;
         rb.u1f = rb.u2f = nullptr;
+        rb.u1g = rb.u2g = nullptr;
         rb.b1 = rb.b2 = rb.bsc16 = rb.b1l = rb.b2l = rb.bscl = nullptr;
         const Bf16Weights wt = bf16_block_weights(c->cfg, rb.cin, rb.cout);  // the copies the bf16 plan counts on
         if (wt.pair) {
@@ -1138,6 +1172,20 @@ int lass_finalize(lass_ctx* c, int compute_mode) {
             if (im.u2f) {
                 if (dev_alloc(c, &rb.u2f, (size_t)36 * rb.cout * rb.cout)) return LASS_ERR_HIP;
                 HIP_TRY(c, lass_launch_wino4_weights(w2, rb.cout, rb.cout, rb.u2f, st));
+            }
+            // ... and, for the convs plan_block can route through wino4_gemm.hip, the split of exactly those f32 images (216 K N
+            // bytes each, kept beside them whatever RouteCfg::wino4_gemm says at that moment: the switch can be thrown afterwards)
+            if (rb.u1f && lass_wino4_gemm_weights(true, rb.cin, rb.cout)) {
+                unsigned short* t = nullptr;
+                if (dev_alloc(c, &t, (size_t)3 * 36 * rb.cout * rb.cin)) return LASS_ERR_HIP;
+                HIP_TRY(c, lass_launch_wino4_gemm_weights(rb.u1f, rb.cout, rb.cin, t, st));
+                rb.u1g = t;
+            }
+            if (rb.u2f && lass_wino4_gemm_weights(true, rb.cout, rb.cout)) {
+                unsigned short* t = nullptr;
+                if (dev_alloc(c, &t, (size_t)3 * 36 * rb.cout * rb.cout)) return LASS_ERR_HIP;
+                HIP_TRY(c, lass_launch_wino4_gemm_weights(rb.u2f, rb.cout, rb.cout, t, st));
+                rb.u2g = t;
             }
         }
         rb.wsc = nullptr;
@@ -1657,6 +1705,7 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
     const auto scratch = [&](BlockFusions& f) {  // the plan's split-K and V slots, for every block
         if (pl.has_kpart) f.kpart = F(pl.kpart);
         if (pl.vprep_floats) { f.vws = F(pl.vprep); f.vws_floats = pl.vprep_floats; }
+        if (pl.mgemm_floats) { f.mws = F(pl.mgemm); f.mws_floats = pl.mgemm_floats; }
     };
     // ---- front end: STFT + magnitude / phase + bn0 / T-pad / F-crop (base.py:83-113, resunet.py:533-552) ------------
     const float *mag_m = F(pl.mag), *cos_m = F(pl.cosv), *sin_m = F(pl.sinv);  // of the mask branch
@@ -2001,6 +2050,13 @@ int lass_set_pw_split(lass_ctx* c, int enabled) {
     if (!c || (enabled != 0 && enabled != 1)) return fail(c, LASS_ERR_ARG, "lass_set_pw_split: 0 or 1");
     c->cfg.pw_split = enabled != 0;
     ++c->gen;  // captured graphs hold the launches of the previous choice
+    return 0;
+}
+
+int lass_set_wino4_gemm(lass_ctx* c, int enabled) {
+    if (!c || (enabled != 0 && enabled != 1)) return fail(c, LASS_ERR_ARG, "lass_set_wino4_gemm: 0 or 1");
+    c->cfg.wino4_gemm = enabled != 0;
+    ++c->gen;  // as lass_set_wino4_splits: other launches, another workspace size
     return 0;
 }
 

@@ -3,9 +3,10 @@
 // launches as blocked bf16 copies; in every mode the family of each transposed conv; and the model table with its level walk.
 // The ONE rule behind the weight images and bf16 copies of lass_finalize, the workspace plan, the launches of run_resblock and
 // run_upconv, the hand-overs of lass_separate (api.hip) and the shape halves of the lass_*_supported predicates of wino.hip,
-// wino4.hip, pw_gemm.hip, conv_bf16.hip and conv_bf16_fused.hip.  Host only and free of HIP: any C++17 compiler builds it.
+// wino4.hip, wino4_gemm.hip, pw_gemm.hip, conv_bf16.hip and conv_bf16_fused.hip.  Host only and free of HIP: any C++17 compiler builds it.
 // tools/route_table.cpp prints the rule as a table; tests/test_wino4_routing_cpu.py holds lass_amd.arch.wino4_routed (the Python
-// mirror that bench.py's executed-FLOP accounting reads) against that table, tests/test_bf16_routing_cpu.py pins the bf16 plan
+// mirror that bench.py's executed-FLOP accounting reads) against that table, tests/test_wino4_gemm_routing_cpu.py pins the gemm
+// route (ConvRoute::gemm), tests/test_bf16_routing_cpu.py pins the bf16 plan
 // and tests/test_gpu_bf16_routes.py ties the printed launch counts to what a lass_separate runs.
 #pragma once
 #include <stddef.h>
@@ -99,6 +100,14 @@ inline bool lass_wino4_vpre_shape(ConvKind kind, const ConvShape& s, int splits 
 // floats of that image: v[clip][block][chunk = cin / 8][36][256]
 inline size_t lass_wino4_vpre_floats(int B, int Cin, int H, int W) { return (size_t)B * Cin * (size_t)(H * W / 16) * kWino4NXI; }
 
+// wino4_gemm.hip, F(4x4,3x3) as scatter - 36 batched GEMMs - gather: the V-from-memory kinds, unsplit, with the split-bf16 GEMM's
+// tile (128 couts; K = Cin in pairs of 16-row chunks).  The tiles of all clips of a launch are the GEMM's one column index p.
+inline bool lass_wino4_gemm_shape(ConvKind kind, const ConvShape& s) {
+    return lass_wino4_vpre_shape(kind, s, 1) && s.N == s.Nw && s.N % kPwGemmNB == 0 && s.Cin % (2 * kPwGemmKC) == 0;
+}
+// floats of its product image m[36][cout][p]: 2.25 x the output
+inline size_t lass_wino4_gemm_m_floats(int B, int N, int H, int W) { return (size_t)B * N * (size_t)(H * W / 16) * kWino4NXI; }
+
 // pw_gemm.hip: the 128-cout x 128-pixel tile of both kinds, and the 1x1 shortcut (K = Cin2 in pairs of chunks)
 inline bool lass_pw_gemm_tile_shape(const ConvShape& s) {
     const long P = (long)s.H * s.W;
@@ -181,6 +190,7 @@ struct RouteCfg {
     int vprep_mode = 1;    // V from memory: 0 = off, 1 = the layers of kVprepMinCoutGroups, 2 = every layer whose kind admits it
     bool head_fold = true; // the fused output head runs on weights composed with after_conv (3 logits instead of 32 channels)
     bool head_sc_fold = true;  // ... and takes its shortcut's logits as planes from the launches that produce its inputs
+    bool wino4_gemm = true;  // the 384-cout F(4x4,3x3) convs with V from memory contract as 36 batched split-bf16 GEMMs (wino4_gemm.hip)
     bool pw_split = true;  // the pw_gemm.hip launches contract on the bf16 MFMA over three exact bf16 pieces per operand (f32 accuracy)
     // bf16 mode (MODE_BF16 only: the hi+lo split of bf16x3 has no blocked hand-overs and no fused kernels)
     bool fuse_catb = true;   // tensors between launches travel as blocked bf16 copies (LASS_FUSE_CATB)
@@ -242,6 +252,8 @@ struct ConvRoute {
     ConvKind kind = CONV1_ACT;
     int splits = 1;               // F(4x4,3x3) split-K factor
     bool v_from_memory = false;   // F(4x4,3x3): a prep launch writes the transformed input, the conv kernel reads it
+    bool gemm = false;            // F(4x4,3x3) with V from memory: scatter, 36 batched split-bf16 GEMMs, gather (wino4_gemm.hip) in
+                                  // place of the prep, conv (and combine) launches that the fields above describe
     bool head_fold = false;       // F(4x4,3x3), CONV2_SHORTCUT with the output head: the folded kernel and its composed images
     bool head_sc_fold = false;    // F(4x4,3x3) on 8 x 64 blocks: the folded head without its shortcut phase (it reads two sets of
                                   // logit planes), or CONV2_IDENT_PRE that writes the skip's set from its epilogue
@@ -254,7 +266,23 @@ struct BlockRoute {
     bool pw_split = false;       // ... by pw_gemm.hip's split-bf16 kernel (RouteCfg::pw_split: the switch picks the kernel, never the route)
     size_t kpart_floats = 0;     // split-K partials both convs share: [splits][B][cout][H][W]
     size_t v_floats = 0;         // the V slot: the larger of the two convs' images (one at a time, in stream order)
+    size_t m_floats = 0;         // the M slot of the gemm route: the product image [36][cout][tiles of the batch], one conv at a time
 };
+
+// f32, F(4x4,3x3) with V from memory and at least kVprepMinCoutGroups cout groups (Cout 384: both convs of encoder_block5-6 and
+// decoder_block1-2): the conv kernel there is 36 independent contractions M_xi = U_xi V_xi and an output transform, on the f32
+// MFMA with a 16 x 16 wave tile that re-reads both operands from LDS per 16 MACs.  As GEMMs of their own they take pw_gemm.hip's
+// split-bf16 body (128 x 128 tile, three exact bf16 pieces per operand, f32 accuracy).  Shape and switches only, never a
+// function of B: a column's sum over K does not depend on the tile or the batch it sits in.
+inline bool lass_wino4_gemm_routed(const RouteCfg& cfg, const ConvRoute& c, const ConvShape& s) {
+    return cfg.f32() && cfg.wino4_gemm && cfg.ksplit_force == 0 && c.family == CONV_F4X4 && c.v_from_memory &&
+           (c.kind == CONV1_ACT || c.kind == CONV2_IDENT) && s.N / 32 >= kVprepMinCoutGroups && s.Cin % 32 == 0 &&
+           lass_wino4_gemm_shape(c.kind, s);
+}
+// ... and which convs lass_finalize keeps the split images of: the channel half of that rule, whatever the switch says then
+inline bool lass_wino4_gemm_weights(bool f32, int cin, int cout) {
+    return f32 && cout % kPwGemmNB == 0 && cout / 32 >= kVprepMinCoutGroups && cin % 32 == 0;
+}
 
 inline BlockRoute plan_block(const RouteCfg& cfg, const BlockShape& b, int B, int H, int W, const BlockIO& io) {
     BlockRoute r;
@@ -313,6 +341,11 @@ inline BlockRoute plan_block(const RouteCfg& cfg, const BlockShape& b, int B, in
     if (r.conv1.splits > 1 || r.conv2.splits > 1) r.kpart_floats = (size_t)n * B * b.cout * H * W;
     if (r.conv1.v_from_memory) r.v_floats = lass_wino4_vpre_floats(B, b.cin, H, W);
     if (r.conv2.v_from_memory && lass_wino4_vpre_floats(B, b.cout, H, W) > r.v_floats) r.v_floats = lass_wino4_vpre_floats(B, b.cout, H, W);
+    // The gemm route replaces the launches of a V-from-memory conv; every field above stays what the switch falls back to.  A
+    // forced split factor asks for the split-K kernels and keeps them.
+    r.conv1.gemm = lass_wino4_gemm_routed(cfg, r.conv1, s1);
+    r.conv2.gemm = lass_wino4_gemm_routed(cfg, r.conv2, s2);
+    if (r.conv1.gemm || r.conv2.gemm) r.m_floats = lass_wino4_gemm_m_floats(B, b.cout, H, W);
     return r;
 }
 

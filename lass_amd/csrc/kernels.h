@@ -161,6 +161,20 @@ hipError_t lass_launch_wino4_headfold_planes(const ConvArgs& p, const HeadScPlan
 bool lass_wino4_sclogit_supported(const ConvArgs& p, const HeadScPlanes& hs);
 hipError_t lass_launch_wino4_sclogit(const ConvArgs& p, const HeadScPlanes& hs, hipStream_t stream);
 
+// ---- wino4_gemm.hip (F(4x4,3x3) as scatter - 36 batched split-bf16 GEMMs - gather: the V-from-memory convs with 128-multiples of
+// couts; conv_route.h: ConvRoute::gemm) -------------------------------------------------------------------------------------------
+// w3 = the layer's U split into three bf16 pieces, [36][3][Cin / 8][N][8] (lass_launch_wino4_gemm_weights, from the w_wino4 image:
+// 216 Cin N bytes); m = the product image M[36][N][tiles of the batch] f32, lass_wino4_gemm_m_floats() of them.  vp.v takes V in GEMM
+// layout [36][Cin][tiles]: lass_wino4_vpre_floats() floats, as the prep launch's image.  (Beside ConvArgs for Wino4Split's reason.)
+struct Wino4Gemm {
+    const void* w3 = nullptr;
+    float* m = nullptr;
+};
+// CONV1_ACT and CONV2_IDENT (res may be `out` itself); three launches: scatter, GEMMs, gather
+bool lass_wino4_gemm_supported(ConvKind kind, const ConvArgs& p, const Wino4VPre& vp, const Wino4Gemm& g);
+hipError_t lass_launch_wino4_gemm(ConvKind kind, const ConvArgs& p, const Wino4VPre& vp, const Wino4Gemm& g, hipStream_t stream);
+hipError_t lass_launch_wino4_gemm_weights(const float* U, int Cout, int Cin, void* dst, hipStream_t stream);
+
 // ---- pw_gemm.hip (f32 pointwise GEMMs with a 128-cout workgroup tile; H*W % 4 == 0, N % 128 == 0, K % 32 == 0) ------------
 // CONV2_SHORTCUT: only the 1x1 shortcut, out = bias + Wsc x (in2, Cin2, w2, bias), for conv2 to read back as its residual;
 // TCONV_ACT: the kernel == stride transposed conv behind its BN+FiLM+leaky prologue (f32 output only)

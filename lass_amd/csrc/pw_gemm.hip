@@ -23,69 +23,11 @@
 // share a group).  The staging thread owns one k octet of one column.  48 KiB of LDS, two workgroups per CU.
 // Non-finite inputs are outside the split's contract (inf - inf): h = inf gives m = NaN where the f32 kernel gives inf.
 #include <hip/hip_runtime.h>
-#include "kernels.h"
-#include "pixel_ops.h"
-#include "wino_common.h"
+#include "pw_gemm_split.h"  // the tile constants, acc_init, store_tile and split3: shared with wino4_gemm.hip
 
 namespace {
 
-constexpr int NTHREADS = 256;
-constexpr int NB = kPwGemmNB;  // couts of a workgroup
-constexpr int PB = 128;      // pixels of a workgroup
-constexpr int KC = kPwGemmKC;  // k rows of a chunk
 constexpr int LP = NB + 32;  // LDS row pitch (floats) of both operand images
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// accumulators start at the shortcut's bias (loaded in the shadow of the first chunk: read in the epilogue, every load would wait
-// behind the store before it)
-template <bool TCONV>
-__device__ __forceinline__ void acc_init(const ConvArgs& p, f32x16 (&acc)[2][2], int n0, int wn, int lane) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float v = TCONV ? 0.f : p.bias[n0 + wn * 64 + i * 32 + 4 * (lane >> 5) + (r & 3) + 8 * (r >> 2)];
-            acc[i][0][r] = v;
-            acc[i][1][r] = v;
-        }
-}
-
-// Both kernels' epilogue: D row (cout) = tile * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5), column (pixel) = lane & 31
-template <bool TCONV>
-__device__ __forceinline__ void store_tile(const ConvArgs& p, const f32x16 (&acc)[2][2], int b, int n0, unsigned p0, unsigned P, int wn,
-                                           int wp, int lane) {
-#pragma unroll
-    for (int tp = 0; tp < 2; ++tp) {
-        const unsigned pj = p0 + (unsigned)(wp * 64 + tp * 32 + (lane & 31));
-        if (pj >= P) continue;
-#pragma unroll
-        for (int tn = 0; tn < 2; ++tn) {
-            const int nb = n0 + wn * 64 + tn * 32 + 4 * (lane >> 5);
-            if (!TCONV) {
-                float* dst = p.out + (size_t)b * p.out_bs + pj;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int n = nb + (r & 3) + 8 * (r >> 2);
-                    dst[(size_t)n * P] = acc[tn][tp][r];
-                }
-            } else {
-                // n = co * (2 up_h) + a * 2 + bb: registers (r, r + 1), r even, are bb = 0 / 1 of one (co, a) - 8 contiguous bytes
-                const unsigned y = pj / (unsigned)p.W, x = pj - y * (unsigned)p.W;
-                const int uhw = p.up_h * 2;
-                const size_t oHW = (size_t)P * uhw;
-                const unsigned oW = 2u * (unsigned)p.W;
-                float* ob = p.out + (size_t)b * p.out_bs + (size_t)(y * p.up_h) * oW + 2u * x;
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) {
-                    const int n = nb + (r & 3) + 8 * (r >> 2);
-                    const int co = n / uhw, a = (n % uhw) >> 1;
-                    *reinterpret_cast<float2*>(ob + (size_t)co * oHW + (size_t)a * oW) = make_float2(acc[tn][tp][r], acc[tn][tp][r + 1]);
-                }
-            }
-        }
-    }
-}
 
 template <bool TCONV>
 __global__ __launch_bounds__(NTHREADS, 2) void pw_gemm_kernel(ConvArgs p) {
@@ -189,38 +131,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void pw_gemm_kernel(ConvArgs p) {
     store_tile<TCONV>(p, acc, b, n0, p0, P, wn, wp, lane);
 }
 
-// ---- the split-bf16 form ---------------------------------------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-constexpr int SPLANE = (KC / 8) * NB;  // 16-byte units of one piece's LDS plane: [k octet][column]  (NB == PB)
-static_assert(NB == PB, "both operand images have 128 columns");
-
-// x[i] = h[i] + m[i] + l[i] exactly, 8 mantissa bits each.  The conversions are gfx950's packed round-to-nearest-even, one per
-// pair; a piece goes back to f32 as its 16 bits in the upper half of a dword.
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned cvt_pair(float a, float b, float& fa, float& fb) {
-    const f32x2 v = {a, b};
-    const unsigned u = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-    fa = __uint_as_float(u << 16);
-    fb = __uint_as_float(u & 0xffff0000u);
-    return u;
-}
-__device__ __forceinline__ void split3(const float (&x)[8], bf16x8& h, bf16x8& m, bf16x8& l) {
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    u32x4 hu, mu, lu;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        float f0, f1, g0, g1;
-        hu[i] = cvt_pair(x[2 * i], x[2 * i + 1], f0, f1);
-        const float r0 = x[2 * i] - f0, r1 = x[2 * i + 1] - f1;
-        mu[i] = cvt_pair(r0, r1, g0, g1);
-        lu[i] = cvt_pair(r0 - g0, r1 - g1, f0, f1);
-    }
-    h = __builtin_bit_cast(bf16x8, hu);
-    m = __builtin_bit_cast(bf16x8, mu);
-    l = __builtin_bit_cast(bf16x8, lu);
-}
-
+// ---- the split-bf16 form (its helpers: pw_gemm_split.h) ------------------------------------------------------------------------
 // w [K][Nw] f32 -> dst [3 pieces h, m, l][K / 8][Nw][8] bf16: what a staging thread of the kernel below copies as one 16-byte load
 // per piece.  One thread per (k octet, column).
 __global__ __launch_bounds__(256) void pw_split_weights_kernel(const float* __restrict__ w, int K, int Nw, bf16x8* __restrict__ dst) {
@@ -239,122 +150,8 @@ __global__ __launch_bounds__(256) void pw_split_weights_kernel(const float* __re
 
 template <bool TCONV>
 __global__ __launch_bounds__(NTHREADS, 2) void pw_gemm_split_kernel(ConvArgs p, PwSplitW sw) {
-    __shared__ __attribute__((aligned(16))) bf16x8 lds[2][2][3][SPLANE];  // [buffer][0 = W, 1 = X][piece][k octet][column]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wn = wave >> 1, wp = wave & 1;  // this wave's 64 couts / 64 pixels of the workgroup tile
-    int bx, by, b;
-    block_coords(p, bx, by, b);
-    const int n0 = by * NB;
-    const unsigned P = (unsigned)p.H * (unsigned)p.W;  // pixels per channel
-    const unsigned p0 = (unsigned)bx * PB;
-    const int K = TCONV ? p.Cin : p.Cin2;
-    const unsigned Nw = (unsigned)p.Nw;
-
-    // staging: thread = (k octet so of the chunk, column sc) of both operands; so is the same for a whole wave, so the prologue's
-    // per-channel scale and shift are scalar loads.  Past the last pixel the column is clamped to the last one (loaded, never
-    // stored to memory)
-    const int sc = tid & (NB - 1), so = __builtin_amdgcn_readfirstlane(tid >> 7);
-    const float* xs = (TCONV ? p.in + (size_t)b * p.in_bs : p.in2 + (size_t)b * p.in2_bs) + min(p0 + (unsigned)sc, P - 1u) +
-                      (size_t)(so * 8) * P;
-    const size_t wplane = (size_t)(K / 8) * Nw;  // 16-byte units of one piece of W
-    const bf16x8* ws = reinterpret_cast<const bf16x8*>(sw.w) + (size_t)so * Nw + n0 + sc;
-    const float* psc = TCONV ? p.pro_scale + so * 8 : nullptr;
-    const float* psh = TCONV ? p.pro_shift + (size_t)b * p.pro_shift_bs + so * 8 : nullptr;
-    // Two register stages, as in the f32 kernel (indexed only statically: the chunk loop is unrolled by two).  One chunk is 768
-    // MFMA cycles per wave: shorter still against a memory round trip
-    struct Act {  // scale and shift of a stage's 8 channels: wave-uniform, in scalar registers
-        float s[8], h[8];
-    };
-    struct Stage {
-        float x[8];
-        bf16x8 w[3];
-        Act a;
-    };
-    Stage S0, S1;
-    Act T;
-    // The scalar loads of a stage are issued in FRONT of a chunk's MFMAs, into T, and handed to the stage behind them: issued
-    // with the vector loads they would sit right in front of the barrier's lgkmcnt(0), their latency exposed in every chunk
-    const auto aload = [&](Act& a, int ch) {
-        if (TCONV) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                a.s[j] = psc[(size_t)ch * KC + j];
-                a.h[j] = psh[(size_t)ch * KC + j];
-            }
-        }
-    };
-    const auto gload = [&](Stage& st, int ch) {
-        const size_t k = (size_t)ch * KC;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) st.x[j] = xs[(k + j) * P];
-#pragma unroll
-        for (int pc = 0; pc < 3; ++pc) st.w[pc] = ws[pc * wplane + (size_t)ch * (KC / 8) * Nw];
-    };
-    const auto sstore = [&](const Stage& st, int buf) {  // the prologue and the split are applied here, once per staged element
-        float x[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) x[j] = TCONV ? leaky(fmaf(st.x[j], st.a.s[j], st.a.h[j])) : st.x[j];  // (resunet.py:247)
-        bf16x8 xp[3];
-        split3(x, xp[0], xp[1], xp[2]);
-#pragma unroll
-        for (int pc = 0; pc < 3; ++pc) {
-            lds[buf][0][pc][so * NB + sc] = st.w[pc];
-            lds[buf][1][pc][so * PB + sc] = xp[pc];
-        }
-    };
-
-    f32x16 acc[2][2];
-    acc_init<TCONV>(p, acc, n0, wn, lane);
-
-    // fragments: A[i = lane & 31][k = 8 (lane >> 5) ... + 7] = W[k][n], B[k = 8 (lane >> 5) ... + 7][j = lane & 31] = X[k][pixel]
-    const int fo = (lane >> 5) * NB + (lane & 31);
-    const auto mma = [&](int buf) {
-        bf16x8 fa[3][2], fb[3][2];  // [piece][tile]: all fragments of the chunk requested up front
-#pragma unroll
-        for (int pc = 0; pc < 3; ++pc)
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                fa[pc][t] = lds[buf][0][pc][fo + wn * 64 + t * 32];
-                fb[pc][t] = lds[buf][1][pc][fo + wp * 64 + t * 32];
-            }
-        __builtin_amdgcn_sched_barrier(0);  // (pinned, as in the f32 kernel)
-        // the six products in ONE fixed order, smallest first; every accumulator sees the same order whatever the batch
-        constexpr int WP[6] = {2, 0, 1, 1, 0, 0}, XP[6] = {0, 2, 1, 0, 1, 0};  // (lh, hl, mm, mh, hm, hh): 0 = h, 1 = m, 2 = l
-#pragma unroll
-        for (int t = 0; t < 6; ++t) {
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[WP[t]][0], fb[XP[t]][0], acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[WP[t]][0], fb[XP[t]][1], acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[WP[t]][1], fb[XP[t]][0], acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[WP[t]][1], fb[XP[t]][1], acc[1][1], 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    // The f32 kernel's pipeline: chunk c in stage c % 2 and LDS buffer c % 2, nch even, one barrier per chunk, unconditional
-    // loads (past the end: the last chunk again, never used)
-    const int nch = K / KC;
-    aload(S0.a, 0);
-    aload(S1.a, 1);
-    gload(S0, 0);
-    gload(S1, 1);
-    sstore(S0, 0);
-    aload(S0.a, min(2, nch - 1));
-    gload(S0, min(2, nch - 1));
-    __syncthreads();
-    for (int ch = 0; ch < nch; ch += 2) {
-        aload(T, min(ch + 3, nch - 1));
-        mma(0);  // chunk ch
-        sstore(S1, 1);
-        S1.a = T;
-        gload(S1, min(ch + 3, nch - 1));
-        __syncthreads();
-        aload(T, min(ch + 4, nch - 1));
-        mma(1);  // chunk ch + 1
-        sstore(S0, 0);  // (behind the last chunk: unused)
-        S0.a = T;
-        gload(S0, min(ch + 4, nch - 1));
-        __syncthreads();
-    }
-    store_tile<TCONV>(p, acc, b, n0, p0, P, wn, wp, lane);
+    constexpr bool XI = false, ACC2 = false;  // (one weight matrix for every clip, accumulators start at the bias, one set of them)
+#include "pw_gemm_split_body.h"
 }
 
 bool aligned16(const void* q) { return ((uintptr_t)q & 15u) == 0; }

@@ -2,7 +2,7 @@
 // block (the f32 rule), one per transposed conv, in the bf16 modes one per block (form and hand-overs), and the profiler scopes.
 // Host only: g++ -std=c++17 -I lass_amd/csrc tools/route_table.cpp -o tools/bin/route_table
 // usage: route_table T_PAD [MIN_CIN=32] [VPREP_MODE=1] [FORCED_SPLITS=0] [X_ALIGNED=1] [STFT_WINDOWS=0] [B=1] [HEAD_FOLD=1] [HEAD=1]
-//                    [HEAD_SC_FOLD=1] [MODE=0] [FUSE_CATB=1] [FUSE_BLOCK=1] [FUSE_UP=1] [N_FFT=0]
+//                    [HEAD_SC_FOLD=1] [MODE=0] [FUSE_CATB=1] [FUSE_BLOCK=1] [FUSE_UP=1] [N_FFT=0] [WINO4_GEMM=1]
 //   MODE 0: f32, 1: bf16, 2: bf16x3; FUSE_*: the LASS_FUSE_* switches of the bf16 mode.  With MODE given (any value) the up,
 //   bf16 and scopes lines follow the conv and block lines; without it the output is the conv and block lines alone.
 //   HEAD 1: decoder_block6 as lass_separate runs it, the output head in conv2's epilogue; 0: as the stage call runs it, without
@@ -11,7 +11,9 @@
 //   lass_amd.arch.ms_conv_layer_table names them (encoder_block1s.<k> for window k).
 //   N_FFT 0: the model's own (1024 for ResUNet30, 2048 for the multi-STFT model); 2048 with STFT_WINDOWS 0: ResUNet30 at the
 //   32 kHz geometry (1024 bins).
-// conv <name> <direct|f2x2|f4x4|none> <kind> <splits> <v> fold=<0|1> scfold=<0|1>     block <name> shortcut=<gemm|fused|-> kpart=<floats> v=<floats>
+//   WINO4_GEMM: the switch of the gemm route (wino4_gemm.hip).  With it given (any value) the conv and block lines end in gemm= / m=;
+//   the fields in front describe the launches the switch falls back to.  Without it the lines are what they always were.
+// conv <name> <direct|f2x2|f4x4|none> <kind> <splits> <v> fold=<0|1> scfold=<0|1> [gemm=<0|1>]     block <name> shortcut=<gemm|fused|-> kpart=<floats> v=<floats> [m=<floats>]
 // up <decoder> <direct|gemm|bf16|tconv_logits|inside> in_act=<0|1> out_copies=<0|1>
 // bf16 <block> form=<f32|two|enc1|dec6|dec6u> cat_in=<0|1> skip_out=<0|1> pool_copies=<0|1> act_out=<0|1>      (MODE 1, 2)
 // scopes conv3x3=<n> tconv=<n>      the P_CONV3X3 / P_TCONV profiler scopes of the run (HEAD = 1: a lass_separate)
@@ -28,14 +30,21 @@ const char* kUpFamily[] = {"direct", "gemm", "bf16", "tconv_logits", "inside"};
 const char* kForm[] = {"f32", "two", "enc1", "dec6", "dec6u"};
 const char* kKind[] = {"CONV1_ACT", "CONV2_IDENT", "CONV2_SHORTCUT", "TCONV_ACT", "CONV1_ACT_PRE", "CONV2_IDENT_PRE"};
 
+bool g_gemm_cols = false;  // the WINO4_GEMM argument was given: gemm= and m= trail the conv and block lines
+
 void print_block(const RouteCfg& cfg, const std::string& name, const BlockShape& b, int B, int H, int W, const BlockIO& io) {
     const BlockRoute r = plan_block(cfg, b, B, H, W, io);
     const ConvRoute* cv[2] = {&r.conv1, &r.conv2};
-    for (int k = 0; k < 2; ++k)
-        printf("conv %s.conv%d %s %s %d %d fold=%d scfold=%d\n", name.c_str(), k + 1, kFamily[cv[k]->family], kKind[cv[k]->kind],
+    for (int k = 0; k < 2; ++k) {
+        printf("conv %s.conv%d %s %s %d %d fold=%d scfold=%d", name.c_str(), k + 1, kFamily[cv[k]->family], kKind[cv[k]->kind],
                cv[k]->splits, (int)cv[k]->v_from_memory, (int)cv[k]->head_fold, (int)cv[k]->head_sc_fold);
-    printf("block %s shortcut=%s kpart=%zu v=%zu\n", name.c_str(), b.cin == b.cout ? "-" : r.shortcut_gemm ? "gemm" : "fused",
+        if (g_gemm_cols) printf(" gemm=%d", (int)cv[k]->gemm);
+        printf("\n");
+    }
+    printf("block %s shortcut=%s kpart=%zu v=%zu", name.c_str(), b.cin == b.cout ? "-" : r.shortcut_gemm ? "gemm" : "fused",
            r.kpart_floats, r.v_floats);
+    if (g_gemm_cols) printf(" m=%zu", r.m_floats);
+    printf("\n");
 }
 
 void print_bf16(const std::string& name, const Bf16Block& b) {
@@ -48,7 +57,7 @@ void print_bf16(const std::string& name, const Bf16Block& b) {
 int main(int argc, char** argv) {
     if (argc < 2) {
         fprintf(stderr, "usage: %s T_PAD [MIN_CIN=32] [VPREP_MODE=1] [FORCED_SPLITS=0] [X_ALIGNED=1] [STFT_WINDOWS=0] [B=1] [HEAD_FOLD=1] [HEAD=1] "
-                        "[HEAD_SC_FOLD=1] [MODE=0] [FUSE_CATB=1] [FUSE_BLOCK=1] [FUSE_UP=1] [N_FFT=0]\n", argv[0]);
+                        "[HEAD_SC_FOLD=1] [MODE=0] [FUSE_CATB=1] [FUSE_BLOCK=1] [FUSE_UP=1] [N_FFT=0] [WINO4_GEMM=1]\n", argv[0]);
         return 2;
     }
     const auto arg = [&](int i, int dflt) { return argc > i ? atoi(argv[i]) : dflt; };
@@ -63,6 +72,8 @@ int main(int argc, char** argv) {
     cfg.fuse_catb = arg(12, 1) != 0;
     cfg.fuse_block = arg(13, 1) != 0;
     cfg.fuse_up = arg(14, 1) != 0;
+    cfg.wino4_gemm = arg(16, 1) != 0;
+    g_gemm_cols = argc > 16;
     const bool head = arg(9, 1) != 0;
     const bool aligned = arg(5, 1) != 0;
     if (t_pad <= 0 || nwin < 0 || nwin > 4 || B <= 0 || mode < 0 || mode > 2) return 2;
