@@ -15,8 +15,10 @@
 #include <vector>
 
 #include "../../include/lass_hip.h"
+#include "graph_cache.h"
 #include "head_fold.h"
 #include "kernels.h"
+#include "workspace_plan.h"
 
 namespace {
 
@@ -63,22 +65,6 @@ thread_local std::string g_create_err;
 
 }  // namespace
 
-// Model geometry.  variant 0 = ResUNet30 (models/resunet.py): one analysis branch, n_fft = win, at one of two STFT geometries -
-// (1024, hop 160), the reference's 16 kHz layout (lass_create), or (2048, hop 320), the 32 kHz layout of the same network
-// (lass_create_stft: 1025-bin bn0, 1024-bin images, the same durations of 64 ms / 10 ms).
-// variant 1 = the multi-resolution-STFT separator (models/resunet_with_multistft.py under the authored spec of
-// DESIGN.md / lass_amd/arch.py): nbr analysis windows at a common n_fft, one pre_conv + encoder_block1 per window,
-// channel-concatenated pools / skips, shared trunk, mask and iSTFT on the branch `mask_br`; always hop 160.
-struct Geometry {
-    int variant = 0;
-    int nbr = 1;
-    int wins[kMaxBranches] = {1024, 0, 0, 0};
-    int nfft = 1024, nbins = 513, fcrop = 512;
-    int hop = LASS_HOP;  // frames are 1 + L / hop; a ragged bucket is 32 * hop samples wide
-    int mask_br = 0;
-    int magphase_sem = 0;  // 0: base.py:83-88 clamp on |X|^2; 1: torchlibrosa magphase (precomputed-STFT wire format)
-};
-
 struct lass_ctx {
     int device = 0;
     std::string err;
@@ -116,36 +102,12 @@ struct lass_ctx {
     // hipGraph replay of lass_separate (LASS_GRAPH=0 disables): the ~40 launches of one (pointers, shape) combination are
     // captured once on an internal stream and replayed on the caller's stream
     bool use_graph = true;
-    struct GraphKey {
-        const void *mix = nullptr, *cond = nullptr, *out = nullptr, *ws = nullptr;
-        const void* lens = nullptr;  // lass_separate_ragged's lengths (the pointer: its contents are read at replay time)
-        const void *starts = nullptr, *keep = nullptr;  // lass_separate_windows' index arrays (pointers, as `lens`)
-        int64_t total = 0;                              // ... and the length of its long rows
-        int B = 0, L = 0;
-        unsigned long gen = 0;
-        bool operator==(const GraphKey& o) const {
-            return mix == o.mix && cond == o.cond && out == o.out && ws == o.ws && lens == o.lens && starts == o.starts &&
-                   keep == o.keep && total == o.total && B == o.B && L == o.L && gen == o.gen;
-        }
-    };
-    // A small cache of instantiated graphs: the evaluator alternates between its common batch and a ragged tail, long-form
-    // callers between a few window counts.  An entry is captured on the third call that presents its key.
-    struct GraphEntry {
-        GraphKey key;
-        hipGraphExec_t exec = nullptr;
-        size_t need = 0;         // workspace bytes the captured plan addresses (re-checked on every replay)
-        int seen = 0;            // calls with this key so far
-        unsigned long used = 0;  // g_tick of the last call (LRU)
-        bool split = false;      // the captured launch sequence runs half-batches (their layouts are what the workspace holds)
-    };
+    // A key is captured on the third call that presents it; the bookkeeping is graph_cache.h's.  Replaced execs may still be
+    // replaying on some stream: they are destroyed only behind a device synchronisation (separate_call / lass_finalize / lass_destroy)
+    GraphCache<hipGraphExec_t> graphs;
     // (B, L) -> did the LAST lass_separate of that shape run as half-batches?  lass_workspace_tensor refuses only then: eager
     // calls (the first calls of a key, LASS_GRAPH=0, changing pointers) leave the whole-batch layout, taps stay readable.
     std::map<std::pair<int, int>, bool> last_split;
-    static constexpr int kGraphSlots = 4;
-    GraphEntry g_slots[kGraphSlots];
-    unsigned long g_tick = 0;
-    std::vector<hipGraphExec_t> g_retired;  // replaced execs: a replay may still be in flight on some stream, so they are
-                                            // destroyed only behind a device synchronisation (lass_finalize / lass_destroy)
     hipStream_t g_stream = nullptr;
     // Half-batch overlap: an even batch of >= 8 clips runs as two independent half-batches on two streams (clips are
     // independent: eval-mode BN) - the second on `s2`, forked from / joined to the caller's stream by events - so that one
@@ -159,7 +121,7 @@ struct lass_ctx {
     int split_batch = 1;
     hipStream_t s2 = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    unsigned long gen = 0;         // bumped by lass_finalize: a graph holds weight pointers
+    unsigned long gen = 0;         // bumped by lass_finalize: a graph holds weight pointers (GraphKey::gen)
     long g_replays = 0, g_captures = 0;
     bool profiling = false;
     std::vector<ProfEntry> prof;
@@ -217,8 +179,6 @@ int add_site(lass_ctx* c, const std::string& film, int C) {
     c->sites.push_back(s);
     return (int)c->sites.size() - 1;
 }
-
-const ResBlock& trunk_block(const lass_ctx* c, int i) { return c->enc[c->g.nbr - 1 + i]; }  // i = 1..6 (E[i])
 
 void build_arch(lass_ctx* c) {
     const Geometry& g = c->g;
@@ -446,7 +406,7 @@ struct BlockFusions {
     float* mws = nullptr;                   // f32: the product image of one conv at a time on the gemm route (wino4_gemm.hip),
     size_t mws_floats = 0;                  // at least BlockRoute::m_floats
     const HeadScPlanes* planes = nullptr;   // f32, encoder_block1 / decoder_block6 of lass_separate: the head's shortcut logits as
-                                            // planes (Plan::sc_planes) - written by conv2's epilogue / read by the folded head
+                                            // planes (Plan::lg_skip / lg_up) - written by conv2's epilogue / read by the folded head
 };
 
 // What one block call's site adds to the block's shape (conv_route.h holds the rules that read it)
@@ -460,11 +420,6 @@ BlockIO block_io(const float* x, long x_bs, const BlockFusions& f) {
     io.cat_in = f.cat_in != nullptr; io.skip_out = f.skip_out != nullptr; io.pool_copies = f.pool_copies != nullptr;
     io.act_out = f.act_out != nullptr; io.up_cin = f.up ? f.up->cin : 0;
     return io;
-}
-
-// The f32 route of one block call: the block, its images and what the call site fuses into it
-BlockRoute block_route(const lass_ctx* c, const ResBlock& rb, int B, int H, int W, const float* x, long x_bs, const BlockFusions& f) {
-    return plan_block(c->cfg, BlockShape{rb.cin, rb.cout, rb.width}, B, H, W, block_io(x, x_bs, f));
 }
 
 // Do B clips of a_n floats, a_bs apart from a (a_bs = 0: one dense range), and the same of b share an element?
@@ -739,112 +694,11 @@ int run_upconv(lass_ctx* c, int di, const float* x, int B, int h, int w, const f
 }
 
 // ---- workspace plan ---------------------------------------------------------------------------------------------
-struct Plan {
-    int B, L, T, Tp;
-    size_t total = 0;
-    size_t mag, cosv, sinv, x0[kMaxBranches], shift, a2, cat[6], pool[6], center, decout[6], oreal, oimag;
-    size_t kpart = 0;  // split-K partials of the 32 x 16 Winograd blocks (one slot: the launches of a plan run in stream order)
-    bool has_kpart = false;
-    size_t vprep = 0, vprep_floats = 0;  // the V image of the V-from-memory layers: one slot, sized to the largest of them
-    size_t mgemm = 0, mgemm_floats = 0;  // the product image of the gemm-route layers (wino4_gemm.hip): one slot, the largest of them
-    // conv_route.h's head_sc_fold: the folded head's shortcut logits as two sets of planes [B][3][Tp][fcrop], one written by
-    // encoder_block1.conv2 and one by decoder_block6's transposed conv (last in the plan: no other offset depends on the switch)
-    bool sc_planes = false;
-    size_t lg_skip = 0, lg_up = 0;
-    Levels lv;         // encoder block spatial sizes
-    SeparatePlan sp;   // the bf16 forms and hand-overs, the transposed convs' families (conv_route.h)
-};
-
-size_t bump(size_t& total, size_t floats) {
-    const size_t off = total;
-    total += (floats * sizeof(float) + 255) / 256 * 256;
-    return off;
-}
-
-// Does lass_separate take the head_sc_fold route (conv_route.h: plan_head_sc_fold) at this batch and image?  The call-site facts
-// are those of separate_impl: encoder_block1 with its fused 2 x 2 pool, decoder_block6 with the head, both on aligned workspace
-// tensors; the composed weights exist (lass_finalize made them for this checkpoint).
-bool head_sc_planned(const lass_ctx* c, int B, int H, int W) {
-    if (!c->hs_wt || !c->hs_wskip || c->enc.empty() || c->dec.size() < 6) return false;
-    const ResBlock &e1 = c->enc[0], &d6 = c->dec[5];
-    BlockIO eio, dio;
-    eio.x0 = true; eio.pool = true; eio.pool_h = c->m.E[0].dh;
-    dio.head = true;
-    HeadScSite site;
-    site.windows = c->g.variant == 0 ? 0 : c->g.nbr; site.tconv_cin = c->m.D[5].cin; site.up_h = c->m.D[5].uh; site.up_w = c->m.D[5].uw;
-    return c->m.E[0].dh == 2 && c->m.E[0].dw == 2 &&
-           plan_head_sc_fold(c->cfg, BlockShape{e1.cin, e1.cout, e1.width}, eio, BlockShape{d6.cin, d6.cout, d6.width}, dio, site, B, H, W);
-}
-
-// The conv kernels address one clip's tensors through 32-bit buffer descriptors and byte offsets, so the largest per-clip
-// tensor (decoder_block6's concat at full resolution, f32) bounds the clip length: below 4 GiB (all offset arithmetic of
-// the f32 Winograd and the bf16 kernels is unsigned; both exercised by the 3.15-GB concat of the 30 s @ 32 kHz multi-STFT
-// clip).  ResUNet30 at 16 kHz: 131 072 B per frame -> 2^32 at 32 768 frames (327 s); ResUNet30 at the 32 kHz geometry (64 ch x 1024
-// bins): 262 144 B per frame -> 2^32 at 16 384 frames (163 s at hop 320); the multi-STFT model (128 ch x 1024 bins): 524 288 B per
-// frame -> 2^32 at 8 192 frames (40.9 s at 32 kHz).  Longer inputs go through chunk_inference / separate_long.
-int make_plan(const lass_ctx* c, int B, int L, Plan* pl) {
-    const Geometry& g = c->g;
-    if (B <= 0 || L <= g.nfft / 2) return LASS_ERR_ARG;
-    pl->B = B; pl->L = L;
-    pl->T = 1 + L / g.hop;
-    pl->Tp = (pl->T + 31) / 32 * 32;
-    const size_t clip_max = (size_t)c->m.dec_cat[5] * pl->Tp * g.fcrop * sizeof(float);
-    if (clip_max > 0xFFFF0000ull) return LASS_ERR_ARG;
-    size_t& t = pl->total;
-    t = 0;
-    const size_t spec = (size_t)B * pl->T * g.nbins;
-    pl->mag = bump(t, spec); pl->cosv = bump(t, spec); pl->sinv = bump(t, spec);
-    for (int k = 0; k < g.nbr; ++k) pl->x0[k] = bump(t, (size_t)B * pl->Tp * g.fcrop);
-    pl->shift = bump(t, (size_t)B * c->n_shift);
-    pl->lv = model_levels(c->m, pl->Tp);
-    size_t a2max = 0;
-    for (int i = 0; i < 7; ++i) {
-        const size_t o = (size_t)B * c->m.E[i].cout * pl->lv.eh[i] * pl->lv.ew[i];
-        if (o > a2max) a2max = o;
-        if (i < 6) pl->pool[i] = bump(t, (size_t)B * c->m.E[i].cout * (i == 0 ? g.nbr : 1) * pl->lv.eh[i + 1] * pl->lv.ew[i + 1]);
-    }
-    pl->center = bump(t, (size_t)B * c->m.E[6].cout * pl->lv.eh[6] * pl->lv.ew[6]);
-    for (int d = 0; d < 6; ++d) {
-        const int e = 5 - d;  // decoder d concatenates the skip of encoder e
-        const size_t hw = (size_t)pl->lv.eh[e] * pl->lv.ew[e];
-        pl->cat[d] = bump(t, (size_t)B * c->m.dec_cat[d] * hw);
-        pl->decout[d] = bump(t, (size_t)B * c->m.D[d].cout * hw);
-    }
-    pl->a2 = bump(t, a2max);
-    pl->oreal = bump(t, spec); pl->oimag = bump(t, spec);
-    // (a half-batch plan has its own slot: the two branches of the replayed graph never share partials)
-    size_t kmax = 0, vmax = 0, mmax = 0;
-    // every block with a route of its own (conv_route.h), at its level's image size and with what lass_separate fuses into it
-    // (the workspace hands every block an aligned input)
-    const auto block = [&](const ResBlock& rb, int e, const BlockIO& io) {
-        const BlockRoute rt = plan_block(c->cfg, BlockShape{rb.cin, rb.cout, rb.width}, B, pl->lv.eh[e], pl->lv.ew[e], io);
-        kmax = std::max(kmax, rt.kpart_floats);
-        vmax = std::max(vmax, rt.v_floats);
-        mmax = std::max(mmax, rt.m_floats);
-    };
-    for (int i = 1; i < 7; ++i) {
-        BlockIO io;
-        io.pool = i < 6; io.pool_h = c->m.E[i].dh;
-        block(trunk_block(c, i), i, io);
-    }
-    for (int d = 0; d < 6; ++d) {
-        BlockIO io;
-        io.head = d == 5;
-        block(c->dec[d], 5 - d, io);
-    }
-    pl->has_kpart = kmax > 0;
-    if (kmax) pl->kpart = bump(t, kmax);
-    pl->vprep_floats = vmax;
-    if (vmax) pl->vprep = bump(t, vmax);
-    pl->mgemm_floats = mmax;
-    if (mmax) pl->mgemm = bump(t, mmax);
-    pl->sc_planes = head_sc_planned(c, B, pl->lv.eh[0], pl->lv.ew[0]);
-    pl->sp = plan_separate(c->cfg, c->m, pl->lv, pl->sc_planes);
-    if (pl->sc_planes) {
-        pl->lg_skip = bump(t, (size_t)B * 3 * pl->lv.eh[0] * pl->lv.ew[0]);
-        pl->lg_up = bump(t, (size_t)B * 3 * pl->lv.eh[0] * pl->lv.ew[0]);
-    }
-    return 0;
+// What workspace_plan.h's rules read of a context
+PlanInputs plan_inputs(const lass_ctx* c) { return PlanInputs{c->g, c->m, c->cfg, c->n_shift, c->hs_wt && c->hs_wskip}; }
+Plan make_plan(const lass_ctx* c, int B, int L) { return make_plan(plan_inputs(c), B, L); }
+CallPlan plan_call(const lass_ctx* c, int B, int L, bool capturing, size_t workspace_bytes) {
+    return plan_call(plan_inputs(c), B, L, c->split_batch, c->profiling, capturing, workspace_bytes);
 }
 
 // Every entry that launches or allocates runs on the context's device, whatever the caller's current device is.
@@ -862,21 +716,13 @@ int check_ready(lass_ctx* c) {
 
 // Destroys every instantiated graph (live and retired).  Caller has synchronised the device.
 void drop_graphs(lass_ctx* c) {
-    for (auto& e : c->g_slots) {
-        if (e.exec) (void)hipGraphExecDestroy(e.exec);
-        e = lass_ctx::GraphEntry();
-    }
-    for (hipGraphExec_t x : c->g_retired) (void)hipGraphExecDestroy(x);
-    c->g_retired.clear();
+    for (hipGraphExec_t x : c->graphs.take_all()) (void)hipGraphExecDestroy(x);
 }
-
-// A batch is split into two overlapping half-batches when it is large enough for each half to fill the GPU on its own
-bool split_halves(const lass_ctx* c, int B) { return c->split_batch > 0 && !c->profiling && B >= 8 && (B % 2) == 0; }
 
 // Stage calls have no workspace plan: their split-K partials and their V image live in two buffers of the context that grow on
 // demand (the call must not be under stream capture when one does).  hipFree waits for the launches that still use the old buffer.
 int stage_scratch(lass_ctx* c, const ResBlock& rb, int B, int H, int W, const float* x, BlockFusions* f) {
-    const BlockRoute rt = block_route(c, rb, B, H, W, x, (long)rb.cin * H * W, *f);
+    const BlockRoute rt = plan_block(c->cfg, BlockShape{rb.cin, rb.cout, rb.width}, B, H, W, block_io(x, (long)rb.cin * H * W, *f));
     const auto grow = [&](float** buf, size_t* have, size_t need) -> int {
         if (need <= *have) return 0;
         if (*buf) HIP_TRY(c, hipFree(*buf));
@@ -1315,15 +1161,10 @@ int lass_finalize(lass_ctx* c, int compute_mode) {
 
 int lass_workspace_bytes(const lass_ctx* c, int B, int L, size_t* bytes) {
     if (!c || !bytes) return LASS_ERR_ARG;
-    Plan pl;
-    if (make_plan(c, B, L, &pl)) return LASS_ERR_ARG;  // B < 1, L <= 512 or L beyond the 32-bit per-clip addressing limit
-    *bytes = pl.total;
-    if (split_halves(c, B)) {  // the half-batch plans side by side (they differ from the whole plan by alignment padding only)
-        Plan ph;
-        if (make_plan(c, B / 2, L, &ph)) return LASS_ERR_ARG;
-        const size_t both = 2 * ((ph.total + 255) / 256 * 256);
-        if (both > *bytes) *bytes = both;
-    }
+    // (the half-batch plans side by side differ from the whole plan by alignment padding only)
+    const CallPlan cp = plan_call(c, B, L, false, kNoWorkspaceLimit);
+    if (!cp.whole.valid) return LASS_ERR_ARG;  // B < 1, L <= n_fft / 2 or L beyond the 32-bit per-clip addressing limit
+    *bytes = cp.need;
     return 0;
 }
 
@@ -1542,45 +1383,16 @@ int lass_workspace_tensor(const lass_ctx* c, int B, int L, const char* name_c, s
     // a batch whose LAST separation ran as half-batches (B >= 8, LASS_SPLIT: the replayed graph by default) holds their layouts
     // in its workspace, not this one; after an eager, unsplit call - or before any call - the whole-batch layout is what is there
     if (auto it = c->last_split.find({B, L}); it != c->last_split.end() && it->second) return LASS_ERR_STATE;
-    Plan pl;
-    if (make_plan(c, B, L, &pl)) return LASS_ERR_ARG;
-    const Geometry& g = c->g;
+    const Plan pl = make_plan(c, B, L);
+    if (!pl.valid) return LASS_ERR_ARG;
     const std::string name(name_c);
-    auto put = [&](size_t off, int64_t C, int64_t H, int64_t W, int64_t bs) {
-        *offset = off;
-        shape[0] = B; shape[1] = C; shape[2] = H; shape[3] = W;
-        strides[0] = bs; strides[1] = H * W; strides[2] = W; strides[3] = 1;
-        return 0;
-    };
-    const int64_t spec = (int64_t)pl.T * g.nbins;
-    if (name == "mag") return put(pl.mag, 1, pl.T, g.nbins, spec);
-    if (name == "cos") return put(pl.cosv, 1, pl.T, g.nbins, spec);
-    if (name == "sin") return put(pl.sinv, 1, pl.T, g.nbins, spec);
-    if (name == "out_real") return put(pl.oreal, 1, pl.T, g.nbins, spec);
-    if (name == "out_imag") return put(pl.oimag, 1, pl.T, g.nbins, spec);
-    for (int k = 0; k < g.nbr; ++k)
-        if (name == (g.variant == 0 ? std::string("x0") : "x0." + std::to_string(g.wins[k])))
-            return put(pl.x0[k], 1, pl.Tp, g.fcrop, (int64_t)pl.Tp * g.fcrop);
-    for (int i = 0; i < 7; ++i) {
-        const EncSpec& e = c->m.E[i];
-        const int64_t H = pl.lv.eh[i], W = pl.lv.ew[i];
-        const int64_t C = (int64_t)e.cout * (i == 0 ? g.nbr : 1);  // encoder_block1: all branches, channel-concatenated
-        if (name == e.name) {
-            if (i == 6) return put(pl.center, C, H, W, C * H * W);
-            const int d = 5 - i;  // the skip lives in place behind the transposed-conv half of decoder d's concat
-            return put(pl.cat[d] + (size_t)c->m.D[d].cout * H * W * sizeof(float), C, H, W, (int64_t)c->m.dec_cat[d] * H * W);
+    for (const PlanTensor& t : plan_tensors(plan_inputs(c), pl))
+        if (t.name == name) {
+            *offset = t.offset;
+            std::copy(t.shape, t.shape + 4, shape);
+            std::copy(t.strides, t.strides + 4, strides);
+            return 0;
         }
-        if (i < 6 && name == std::string(e.name) + ".pool")
-            return put(pl.pool[i], C, H / e.dh, W / e.dw, C * (H / e.dh) * (W / e.dw));
-    }
-    // the head's shortcut logits of the head_sc_fold route (only where the plan has them)
-    if (pl.sc_planes && name == "head_sc.skip") return put(pl.lg_skip, 3, pl.lv.eh[0], pl.lv.ew[0], (int64_t)3 * pl.lv.eh[0] * pl.lv.ew[0]);
-    if (pl.sc_planes && name == "head_sc.up") return put(pl.lg_up, 3, pl.lv.eh[0], pl.lv.ew[0], (int64_t)3 * pl.lv.eh[0] * pl.lv.ew[0]);
-    for (int d = 0; d < 6; ++d) {
-        const int64_t H = pl.lv.eh[5 - d], W = pl.lv.ew[5 - d], C = c->m.D[d].cout;
-        if (name == std::string(c->m.D[d].name) + ".up") return put(pl.cat[d], C, H, W, (int64_t)c->m.dec_cat[d] * H * W);
-        if (name == c->m.D[d].name) return put(pl.decout[d], C, H, W, C * H * W);
-    }
     return LASS_ERR_ARG;
 }
 
@@ -1680,16 +1492,16 @@ struct Components {
 
 // cf: the clips of the call (kernels.h) - B rows of L samples, dense or with a length per clip, or B windows of L samples of ONE
 // row of cf.total samples (`mixture`), their kept parts stored into one row of as many samples (`out`).  The two ends of the
-// network run in cf's form; everything between them sees B images of (Tp, fcrop) whatever the form.
+// network run in cf's form; everything between them sees B images of (Tp, fcrop) whatever the form.  pl: the plan of (cf.B, cf.L) -
+// the caller made it, once per call (an invalid one is refused here, behind the checks that come first).
 static int separate_impl(lass_ctx* c, const float* mixture, const Components* comp, const float* condition, float* out,
-                         const ClipForm& cf, void* workspace, size_t workspace_bytes, void* stream, const char* who) {
-    const int B = cf.B, L = cf.L;
+                         const ClipForm& cf, const Plan& pl, void* workspace, size_t workspace_bytes, void* stream, const char* who) {
+    const int B = cf.B;
     int r = check_ready(c);
     if (r) return r;
     const Geometry& g = c->g;
     if ((!mixture && !comp) || !condition || !out || !workspace) return fail(c, LASS_ERR_ARG, std::string(who) + ": null pointer");
-    Plan pl;
-    if (make_plan(c, B, L, &pl))
+    if (!pl.valid)
         return fail(c, LASS_ERR_ARG, std::string(who) + ": need B >= 1 and " + std::to_string(g.nfft / 2) +
                                          " < L, with decoder_block6's concat (" + std::to_string(c->m.dec_cat[5]) +
                                          " ch x frames x " + std::to_string(g.fcrop) +
@@ -1702,10 +1514,13 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
     auto F = [&](size_t off) { return (float*)(ws + off); };
     const int T = pl.T, Tp = pl.Tp, nbr = g.nbr;
     float* shift = F(pl.shift);
+    // What each block is called with - its BlockIO, its bf16 form, each transposed conv's family - is decided once, in
+    // conv_route.h's plan_separate; the fusions below follow it, and run_resblock / run_upconv refuse a contradiction
+    const SeparatePlan& sp = pl.sp;
     const auto scratch = [&](BlockFusions& f) {  // the plan's split-K and V slots, for every block
-        if (pl.has_kpart) f.kpart = F(pl.kpart);
-        if (pl.vprep_floats) { f.vws = F(pl.vprep); f.vws_floats = pl.vprep_floats; }
-        if (pl.mgemm_floats) { f.mws = F(pl.mgemm); f.mws_floats = pl.mgemm_floats; }
+        if (sp.kpart_floats) f.kpart = F(pl.kpart);
+        if (sp.v_floats) { f.vws = F(pl.vprep); f.vws_floats = sp.v_floats; }
+        if (sp.m_floats) { f.mws = F(pl.mgemm); f.mws_floats = sp.m_floats; }
     };
     // ---- front end: STFT + magnitude / phase + bn0 / T-pad / F-crop (base.py:83-113, resunet.py:533-552) ------------
     const float *mag_m = F(pl.mag), *cos_m = F(pl.cosv), *sin_m = F(pl.sinv);  // of the mask branch
@@ -1727,9 +1542,9 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
         ProfScope ps(c, st, P_FILM);
         HIP_TRY(c, lass_launch_film(condition, B, c->film_W, c->film_b, c->bn_base, c->n_shift, shift, st));
     }
-    // conv_route.h's head_sc_fold: one decision (make_plan) for encoder_block1.conv2, decoder_block6's transposed conv and the head
+    // conv_route.h's head_sc_fold: one decision for encoder_block1.conv2, decoder_block6's transposed conv and the head
     HeadScPlanes hs_skip, hs_up, hs_head;
-    if (pl.sc_planes) {
+    if (sp.head_sc_fold) {
         hs_skip.skip = hs_head.skip = F(pl.lg_skip); hs_skip.w = c->hs_wskip;
         hs_up.up = hs_head.up = F(pl.lg_up); hs_up.w = c->hs_wt;
         hs_skip.up = hs_head.up;  // (for run_resblock's overlap checks; the encoder launch does not touch it)
@@ -1737,31 +1552,16 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
     // Routes.  pre_conv (resunet.py:555) is never materialised: encoder_block1 forms it from x0 while staging.  Tp is a
     // multiple of 32, so every pooled level has even rows and F.avg_pool2d (resunet.py:197) rides in conv2's epilogue.
     // decoder_block6 runs at W = fcrop with 32 channels: after_conv + mask ride in its conv2's epilogue.
-    // bf16 mode: which tensors travel as blocked bf16 copies, and which blocks run fused, is pl.sp (conv_route.h: plan_separate).
+    // bf16 mode: which tensors travel as blocked bf16 copies, and which blocks run fused, is sp.
     // Where decoders 2-6 take their concat that way the copies live in the concat's storage
-    const SeparatePlan& sp = pl.sp;
-    CatCopies cb[6];
-    for (int d = 1; d < 6; ++d) {
-        const int e = 5 - d;
-        const ResBlock& rd = c->dec[d];
-        const long hw = (long)pl.lv.eh[e] * pl.lv.ew[e];
-        cb[d].act = F(pl.cat[d]);
-        cb[d].raw = (char*)F(pl.cat[d]) + (size_t)B * rd.cin * hw * 2;
-        cb[d].noct = rd.cin / 8;
-        cb[d].scale = c->bn_scale + c->sites[rd.s1].off;
-        cb[d].shift = shift + c->sites[rd.s1].off;
-    }
+    const auto copies = [&](float* store, const ResBlock& rb, int e) {  // the two copies of rb's input (level e) in `store`
+        const Site& s = c->sites[rb.s1];
+        return CatCopies{store, (char*)store + (size_t)B * rb.cin * pl.lv.eh[e] * pl.lv.ew[e] * 2, rb.cin / 8, c->bn_scale + s.off, shift + s.off};
+    };
+    CatCopies cb[6], pc[4];
+    for (int d = 1; d < 6; ++d) cb[d] = copies(F(pl.cat[d]), c->dec[d], 5 - d);
     // ... and encoder blocks 2-5 their (pooled) input, from the previous block's fused pool, in the pooled tensor's
-    CatCopies pc[4];
-    for (int i = 0; i < 4; ++i) {
-        const ResBlock& nx = c->enc[nbr - 1 + i + 1];
-        const long hwo = (long)pl.lv.eh[i + 1] * pl.lv.ew[i + 1];
-        pc[i].act = F(pl.pool[i]);
-        pc[i].raw = (char*)F(pl.pool[i]) + (size_t)B * nx.cin * hwo * 2;
-        pc[i].noct = nx.cin / 8;
-        pc[i].scale = c->bn_scale + c->sites[nx.s1].off;
-        pc[i].shift = shift + c->sites[nx.s1].off;
-    }
+    for (int i = 0; i < 4; ++i) pc[i] = copies(F(pl.pool[i]), c->enc[nbr + i], i + 1);
     // ---- encoder (resunet.py:556-562; resunet_with_multistft.py:151-179) -----------------------------------------------
     const float* x = nullptr;
     for (int i = 0; i < 7; ++i) {
@@ -1773,29 +1573,32 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
         long o_bs = 0;
         for (int k = 0; k < nb; ++k) {
             const ResBlock& rb = c->enc[i == 0 ? k : nbr - 1 + i];
+            const BlockIO& io = sp.enc_io[i];
             BlockFusions f;
             f.cofs = k * e.cout;  // channel offset of this branch inside the concatenated skip / pool
             if (i < 6) {  // skip output lives behind the transposed-conv half of decoder (5-i)'s concat buffer
                 const int d = 5 - i;
                 o = F(pl.cat[d]) + (size_t)(c->m.D[d].cout + f.cofs) * HW;
                 o_bs = (long)c->m.dec_cat[d] * HW;
-                const long Ho = H / e.dh, Wo = W / e.dw;
-                f.pool_out = F(pl.pool[i]) + (size_t)f.cofs * Ho * Wo;
-                f.pool_h = e.dh;
-                f.pool_bs = (long)e.cout * nb * Ho * Wo;
             } else {
                 o = F(pl.center);
                 o_bs = rb.cout * HW;
             }
+            if (io.pool) {
+                const long Ho = H / e.dh, Wo = W / e.dw;
+                f.pool_out = F(pl.pool[i]) + (size_t)f.cofs * Ho * Wo;
+                f.pool_h = e.dh;
+                f.pool_bs = (long)e.cout * nb * Ho * Wo;
+            }
             PreConv pre{};
-            if (i == 0) {
+            if (io.x0) {
                 pre = PreConv{F(pl.x0[k]), rawp(c, c->pre_name[k] + ".weight"), rawp(c, c->pre_name[k] + ".bias")};
                 f.pre = &pre;
-                if (pl.sc_planes) f.planes = &hs_skip;
             }
-            if (sp.enc[i].skip_out) f.skip_out = &cb[5 - i];
-            if (sp.enc[i].cat_in) f.cat_in = &pc[i - 1];
-            if (sp.enc[i].pool_copies) f.pool_copies = &pc[i];
+            if (io.sc_planes) f.planes = &hs_skip;
+            if (io.skip_out) f.skip_out = &cb[5 - i];
+            if (io.cat_in) f.cat_in = &pc[i - 1];
+            if (io.pool_copies) f.pool_copies = &pc[i];
             scratch(f);
             r = run_resblock(c, rb, x, rb.cin * HW, B, H, W, shift, F(pl.a2), o, o_bs, st, f);
             if (r) return r;
@@ -1809,23 +1612,24 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
         const long HW = (long)H * W;
         const int h = H / c->m.D[d].uh, w = W / c->m.D[d].uw;
         const ResBlock& rb = c->dec[d];
+        const BlockIO& io = sp.dec_io[d];
         BlockFusions f;
         // decoder_block6 in the blocked bf16 pipeline: the transposed conv runs inside the block's fused kernel, its output
         // (half of the concat, at the full resolution) is never written
         const UpFuse upf{x, c->m.D[d].cin, h, w, c->up16[d], c->up_sc16};
-        if (sp.up[d].family == UP_INSIDE) {
+        if (io.up_cin) {
             f.up = &upf;
         } else {
             r = run_upconv(c, d, x, B, h, w, shift, F(pl.cat[d]), rb.cin * HW, st, sp.up[d].out_copies ? &cb[d] : nullptr, sp.up[d].in_act,
-                           d == 5 && pl.sc_planes ? &hs_up : nullptr);
+                           sp.up[d].family == UP_LOGITS ? &hs_up : nullptr);
             if (r) return r;
         }
         // a decoder output that feeds only the next transposed conv is handed over activated, as blocked bf16
-        if (sp.dec[d].act_out) f.act_out = &c->sites[c->dec_site[d + 1]];
-        if (sp.dec[d].cat_in) f.cat_in = &cb[d];
+        if (io.act_out) f.act_out = &c->sites[c->dec_site[d + 1]];
+        if (io.cat_in) f.cat_in = &cb[d];
         const MaskHead head{mag_m, cos_m, sin_m, F(pl.oreal), F(pl.oimag), T, g.nbins};
-        if (d == 5) f.head = &head;
-        if (d == 5 && pl.sc_planes) f.planes = &hs_head;
+        if (io.head) f.head = &head;
+        if (io.sc_planes) f.planes = &hs_head;
         scratch(f);
         r = run_resblock(c, rb, F(pl.cat[d]), rb.cin * HW, B, H, W, shift, F(pl.a2), F(pl.decout[d]), rb.cout * HW, st, f);
         if (r) return r;
@@ -1838,8 +1642,6 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
     return 0;
 }
 
-// lass_separate's launches, whole or as two overlapping half-batches (lass_ctx::split_batch).  Capture-safe: under stream
-// capture the event pair makes `s2` a parallel branch of the same graph.
 // Clips [h, B) of cf as a call of their own.  *row: how far into the mixture and the output their rows begin - the window form's
 // second half reads its own entries of the index arrays and the SAME two long rows.
 static ClipForm upper_clips(const ClipForm& cf, int h, size_t* row) {
@@ -1852,32 +1654,31 @@ static ClipForm upper_clips(const ClipForm& cf, int h, size_t* row) {
     return u;
 }
 
-static int separate_any(lass_ctx* c, const float* mixture, const float* condition, float* out, const ClipForm& cf, void* workspace,
-                        size_t workspace_bytes, hipStream_t stream, bool capturing, const char* who) {
-    const int B = cf.B, L = cf.L;
-    Plan ph;
-    if (!c->finalized || !split_halves(c, B) || !mixture || !condition || !out || !workspace || (!capturing && c->split_batch < 2) ||
-        make_plan(c, B / 2, L, &ph) || 2 * ((ph.total + 255) / 256 * 256) > workspace_bytes) {
-        c->last_split[{B, L}] = false;
-        return separate_impl(c, mixture, nullptr, condition, out, cf, workspace, workspace_bytes, stream, who);
-    }
-    c->last_split[{B, L}] = true;
+// lass_separate's launches, whole or as two overlapping half-batches, as cp (plan_call) says.  Capture-safe: under stream capture
+// the event pair makes `s2` a parallel branch of the same graph.  The one place that records, for lass_workspace_tensor, which
+// layout the workspace is left in.
+static int separate_any(lass_ctx* c, const float* mixture, const float* condition, float* out, const ClipForm& cf, const CallPlan& cp,
+                        void* workspace, size_t workspace_bytes, hipStream_t stream, const char* who) {
+    // (a call that separate_impl is going to refuse - not finalized, a null pointer - reaches it whole, for its error text)
+    const bool split = cp.split && c->finalized && mixture && condition && out && workspace;
+    c->last_split[{cf.B, cf.L}] = split;
+    if (!split) return separate_impl(c, mixture, nullptr, condition, out, cf, cp.whole, workspace, workspace_bytes, stream, who);
     HIP_TRY(c, hipSetDevice(c->device));
     if (!c->ev_fork) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
     if (!c->s2) {
         HIP_TRY(c, hipStreamCreateWithFlags(&c->s2, hipStreamNonBlocking));
         HIP_TRY(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
     }
-    const int h = B / 2;
-    const size_t half_ws = (ph.total + 255) / 256 * 256;
+    const int h = cf.B / 2;
+    const size_t half_ws = cp.half_bytes();
     HIP_TRY(c, hipEventRecord(c->ev_fork, stream));
     HIP_TRY(c, hipStreamWaitEvent(c->s2, c->ev_fork, 0));
     ClipForm lower = cf;
     lower.B = h;
     size_t row2;
     const ClipForm upper = upper_clips(cf, h, &row2);  // (split_halves: B is even)
-    int r = separate_impl(c, mixture, nullptr, condition, out, lower, workspace, half_ws, stream, who);
-    const int r2 = separate_impl(c, mixture + row2, nullptr, condition + (size_t)h * LASS_COND, out + row2, upper,
+    int r = separate_impl(c, mixture, nullptr, condition, out, lower, cp.half, workspace, half_ws, stream, who);
+    const int r2 = separate_impl(c, mixture + row2, nullptr, condition + (size_t)h * LASS_COND, out + row2, upper, cp.half,
                                  (char*)workspace + half_ws, half_ws, c->s2, who);
     if (!r) r = r2;
     // the join is recorded even after a failure: a capturing stream must get its branch back
@@ -1894,86 +1695,62 @@ static int separate_call(lass_ctx* c, const float* mixture, const float* conditi
     // Graph replay: the third call that presents the same (pointers, shape) key is captured once (on an internal stream; the
     // caller's may be the legacy default stream, which cannot be captured) and replayed from then on.  Callers that hand
     // over fresh buffers every time simply stay on the eager path; so does a profiled context.
-    lass_ctx::GraphKey key;
-    key.mix = mixture; key.cond = condition; key.out = out; key.ws = workspace; key.lens = cf.lengths; key.B = B; key.L = L;
-    key.gen = c->gen;
-    key.starts = cf.starts; key.keep = cf.keep; key.total = cf.total;
     if (c->use_graph && !c->profiling && c->finalized) {
-        ++c->g_tick;
-        lass_ctx::GraphEntry* slot = nullptr;
-        for (auto& e : c->g_slots)
-            if (e.seen > 0 && e.key == key) slot = &e;
-        if (!slot) {  // take the least recently used slot, preferring one without a graph
-            for (auto& e : c->g_slots)
-                if (!slot || (!e.exec && slot->exec) || (!e.exec == !slot->exec && e.used < slot->used)) slot = &e;
-            if (slot->exec) {  // may still be replaying on some stream: destroyed only behind a device synchronisation
-                c->g_retired.push_back(slot->exec);
-                if (c->g_retired.size() > 8) {  // a caller cycling through many recurring keys: bound the list here
-                    HIP_TRY(c, hipSetDevice(c->device));
-                    HIP_TRY(c, hipDeviceSynchronize());
-                    for (hipGraphExec_t x : c->g_retired) (void)hipGraphExecDestroy(x);
-                    c->g_retired.clear();
-                }
-            }
-            *slot = lass_ctx::GraphEntry();
-            slot->key = key;
-        }
-        slot->used = c->g_tick;
-        ++slot->seen;
-        if (slot->exec) {
-            if (workspace_bytes < slot->need)
-                return fail(c, LASS_ERR_WORKSPACE, "workspace too small: need " + std::to_string(slot->need) + " bytes");
+        GraphKey key;
+        key.mix = mixture; key.cond = condition; key.out = out; key.ws = workspace; key.lens = cf.lengths; key.B = B; key.L = L;
+        key.gen = c->gen;
+        key.starts = cf.starts; key.keep = cf.keep; key.total = cf.total;
+        auto& slot = c->graphs.touch(key);
+        if (c->graphs.drain_due()) {  // a caller cycling through many recurring keys: bound the list of evicted execs here
             HIP_TRY(c, hipSetDevice(c->device));
-            HIP_TRY(c, hipGraphLaunch(slot->exec, (hipStream_t)stream));
+            HIP_TRY(c, hipDeviceSynchronize());
+            for (hipGraphExec_t x : c->graphs.take_retired()) (void)hipGraphExecDestroy(x);
+        }
+        if (slot.exec()) {  // (no planning on a replay: the slot holds what the captured plan said)
+            if (workspace_bytes < slot.need)
+                return fail(c, LASS_ERR_WORKSPACE, "workspace too small: need " + std::to_string(slot.need) + " bytes");
+            HIP_TRY(c, hipSetDevice(c->device));
+            HIP_TRY(c, hipGraphLaunch(slot.exec(), (hipStream_t)stream));
             ++c->g_replays;
-            c->last_split[{B, L}] = slot->split;
+            c->last_split[{B, L}] = slot.split;
             return 0;
         }
-        if (slot->seen >= 3) {  // worth a capture
-            // argument errors are reported as such, before any capture starts: only a failure of the capture machinery
-            // itself (begin / end / instantiate, or a launch refused under capture) turns graph replay off
-            {
-                int r0 = check_ready(c);
-                if (r0) return r0;
-                Plan pl0;
-                if (!condition || !out || !workspace || make_plan(c, B, L, &pl0) || workspace_bytes < pl0.total ||
-                    ((uintptr_t)workspace & 255) != 0)
-                    return separate_any(c, mixture, condition, out, cf, workspace, workspace_bytes, (hipStream_t)stream, false, who);
-                slot->need = pl0.total;
-                if (split_halves(c, B)) {  // (checked again at capture time by separate_any: smaller workspaces run unsplit)
-                    Plan ph0;
-                    if (!make_plan(c, B / 2, L, &ph0) && 2 * ((ph0.total + 255) / 256 * 256) <= workspace_bytes)
-                        slot->need = std::max(slot->need, 2 * ((ph0.total + 255) / 256 * 256));
+        if (c->graphs.capture_due(slot)) {
+            // argument errors are reported as such, before any capture starts, by the eager run below: only a failure of the
+            // capture machinery itself (begin / end / instantiate, or a launch refused under capture) turns graph replay off
+            int r0 = check_ready(c);
+            if (r0) return r0;
+            const CallPlan cp = plan_call(c, B, L, true, workspace_bytes);
+            if (condition && out && workspace && cp.whole.valid && workspace_bytes >= cp.whole.total && ((uintptr_t)workspace & 255) == 0) {
+                slot.need = cp.need;
+                slot.split = cp.split;
+                HIP_TRY(c, hipSetDevice(c->device));
+                if (!c->g_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->g_stream, hipStreamNonBlocking));
+                hipGraphExec_t exec = nullptr;
+                if (hipStreamBeginCapture(c->g_stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+                    const int r = separate_any(c, mixture, condition, out, cf, cp, workspace, workspace_bytes, c->g_stream, who);
+                    hipGraph_t graph = nullptr;
+                    const hipError_t e = hipStreamEndCapture(c->g_stream, &graph);  // always ends the capture, also after a failure
+                    if (!(r == 0 && e == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess))
+                        exec = nullptr;
+                    if (graph) (void)hipGraphDestroy(graph);
                 }
-            }
-            HIP_TRY(c, hipSetDevice(c->device));
-            if (!c->g_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->g_stream, hipStreamNonBlocking));
-            bool ok = false;
-            if (hipStreamBeginCapture(c->g_stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                const int r = separate_any(c, mixture, condition, out, cf, workspace, workspace_bytes, c->g_stream, true, who);
-                hipGraph_t graph = nullptr;
-                const hipError_t e = hipStreamEndCapture(c->g_stream, &graph);  // always ends the capture, also after a failure
-                if (r == 0 && e == hipSuccess && graph && hipGraphInstantiate(&slot->exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-                    ok = true;
-                    if (auto it = c->last_split.find({B, L}); it != c->last_split.end()) slot->split = it->second;
-                } else {
-                    slot->exec = nullptr;
+                if (exec) {
+                    c->graphs.set_exec(slot, exec);
+                    ++c->g_captures;
+                    HIP_TRY(c, hipGraphLaunch(exec, (hipStream_t)stream));
+                    return 0;
                 }
-                if (graph) (void)hipGraphDestroy(graph);
+                // A launch failed inside the capture, or the runtime refused it: nothing has run yet.  Stay eager from now on and
+                // run this call eagerly below (an error is reported only if the eager run fails too).
+                (void)hipGetLastError();
+                c->use_graph = false;
+                c->err.clear();
             }
-            if (ok) {
-                ++c->g_captures;
-                HIP_TRY(c, hipGraphLaunch(slot->exec, (hipStream_t)stream));
-                return 0;
-            }
-            // A launch failed inside the capture, or the runtime refused it: nothing has run yet.  Stay eager from now on and
-            // run this call eagerly below (an error is reported only if the eager run fails too).
-            (void)hipGetLastError();
-            c->use_graph = false;
-            c->err.clear();
         }
     }
-    return separate_any(c, mixture, condition, out, cf, workspace, workspace_bytes, (hipStream_t)stream, false, who);
+    const CallPlan cp = plan_call(c, B, L, false, workspace_bytes);
+    return separate_any(c, mixture, condition, out, cf, cp, workspace, workspace_bytes, (hipStream_t)stream, who);
 }
 
 int lass_separate(lass_ctx* c, const float* mixture, const float* condition, float* out, int B, int L, void* workspace,
@@ -2082,7 +1859,7 @@ int lass_separate_components(lass_ctx* c, const float* const* mag, const float* 
     Components comp;
     for (int k = 0; k < kMaxBranches; ++k) comp.mag[k] = k < c->g.nbr ? mag[k] : nullptr;
     comp.cosv = cos_mask; comp.sinv = sin_mask;
-    return separate_impl(c, nullptr, &comp, condition, out, ClipForm{B, L}, workspace, workspace_bytes, stream,
+    return separate_impl(c, nullptr, &comp, condition, out, ClipForm{B, L}, make_plan(c, B, L), workspace, workspace_bytes, stream,
                          "lass_separate_components");
 }
 

@@ -1,9 +1,13 @@
 // conv_route.h - which kernel family runs the 3x3 convs of a residual block in f32, and the workspace that takes; in the bf16
 // modes which blocks run the bf16 kernels, in which form (two launches or one fused kernel), and which tensors travel between
 // launches as blocked bf16 copies; in every mode the family of each transposed conv; and the model table with its level walk.
-// The ONE rule behind the weight images and bf16 copies of lass_finalize, the workspace plan, the launches of run_resblock and
-// run_upconv, the hand-overs of lass_separate (api.hip) and the shape halves of the lass_*_supported predicates of wino.hip,
-// wino4.hip, wino4_gemm.hip, pw_gemm.hip, conv_bf16.hip and conv_bf16_fused.hip.  Host only and free of HIP: any C++17 compiler builds it.
+// The ONE rule behind the weight images and bf16 copies of lass_finalize, the launches of run_resblock and run_upconv (api.hip),
+// and the shape halves of the lass_*_supported predicates of wino.hip, wino4.hip, wino4_gemm.hip, pw_gemm.hip, conv_bf16.hip and
+// conv_bf16_fused.hip; and, as plan_separate, the ONE walk over the blocks of a lass_separate: what each block is called with, its
+// route and hand-overs, the head_sc_fold decision and the workspace the routes take.  workspace_plan.h sizes the workspace from that
+// walk (make_plan) and lass_separate sets each block's fusions from it (api.hip: separate_impl); run_resblock and run_upconv derive
+// the route again from the pointers they are handed and refuse a contradiction (the stage calls come the same way, on a default
+// site).  Host only and free of HIP: any C++17 compiler builds it.
 // tools/route_table.cpp prints the rule as a table; tests/test_wino4_routing_cpu.py holds lass_amd.arch.wino4_routed (the Python
 // mirror that bench.py's executed-FLOP accounting reads) against that table, tests/test_wino4_gemm_routing_cpu.py pins the gemm
 // route (ConvRoute::gemm), tests/test_bf16_routing_cpu.py pins the bf16 plan
@@ -381,6 +385,15 @@ inline bool plan_head_sc_fold(const RouteCfg& cfg, const BlockShape& enc1, Block
 }
 
 // ---- the model table ------------------------------------------------------------------------------------------------------------
+// The default STFT geometry (lass_create).  A context carries its own (workspace_plan.h: Geometry - n_fft, hop, bins), and every
+// launch interface of kernels.h takes them as arguments: these four name the default's values, nothing reads them as "the" geometry.
+constexpr int LASS_NFFT = 1024;
+constexpr int LASS_HOP = 160;
+constexpr int LASS_NBINS = 513;
+constexpr int LASS_FCROP = 512;
+constexpr int LASS_COND = 512;
+constexpr int LASS_MAX_STFT_WINDOWS = 4;
+
 struct EncSpec { const char* name; int cin, cout, dh, dw; };  // a ConvBlockRes and the (dh, dw) avg-pool behind it
 struct DecSpec { const char* name; int cin, cout, uh, uw; };  // the (uh, uw) transposed conv of a decoder; its ConvBlockRes reads the concat
 // ResUNet30 (resunet.py:315-418)
@@ -533,26 +546,48 @@ inline Bf16Block plan_bf16_block(const RouteCfg& cfg, const BlockShape& b, int H
     return r;
 }
 
-// One lass_separate: every block's form and every hand-over between two launches, decided for producer and consumer at once -
-// a consumer that read f32 storage as bf16 units, or the reverse, would read garbage.  enc[0] stands for all nbr branch blocks.
-// The stage calls (lass_convblock, lass_encoder_block, lass_upconv) have no hand-overs: plan_bf16_block and plan_upconv on a
-// default-constructed site.
+// One lass_separate, the ONE walk over its blocks: the BlockIO every block is called with, every block's form and every hand-over
+// between two launches, decided for producer and consumer at once - a consumer that read f32 storage as bf16 units, or the reverse,
+// would read garbage - the head_sc_fold decision for its three launches, and in f32 every block's route with the workspace the
+// routes take.  enc[0] stands for all nbr branch blocks.  The stage calls (lass_convblock, lass_encoder_block, lass_upconv) have no
+// hand-overs: plan_block, plan_bf16_block and plan_upconv on a default-constructed site.
 struct SeparatePlan {
+    BlockIO enc_io[7], dec_io[6];  // complete: the bf16 hand-overs are the ones the block admits; inputs are workspace tensors (x_aligned)
     Bf16Block enc[7], dec[6];
     UpRoute up[6];
+    bool head_sc_fold = false;     // plan_head_sc_fold's decision: enc_io[0].sc_planes, dec_io[5].sc_planes and up[5] = UP_LOGITS
+    BlockRoute enc_rt[7], dec_rt[6];  // f32: plan_block at the call's B (the bf16 modes: the kinds alone)
+    size_t kpart_floats = 0, v_floats = 0, m_floats = 0;  // ... and their largest slots over the trunk and decoder blocks
     // P_CONV3X3 / P_TCONV profiler scopes of the run: one per launch (f32: the prep launch of a V image shares its conv's)
     int conv_scopes = 0, tconv_scopes = 0;
 };
-// sc_planes: plan_head_sc_fold's decision (f32).  (The f32 scope count plans each block at B = 1: B only sizes its workspaces.)
-inline SeparatePlan plan_separate(const RouteCfg& cfg, const ModelTable& m, const Levels& lv, bool sc_planes) {
+// B sizes the workspace slots of the routes and nothing else: forms, hand-overs, families and scope counts do not depend on it.
+// head_sc_weights: lass_finalize composed the head's shortcut with its two producers (head_fold.h) for this checkpoint.
+inline SeparatePlan plan_separate(const RouteCfg& cfg, const ModelTable& m, const Levels& lv, int B, bool head_sc_weights) {
     SeparatePlan sp;
+    // encoder_block1 forms pre_conv(x0), the encoders pool in conv2's epilogue, decoder_block6 carries the output head
+    for (int i = 0; i < 7; ++i) {
+        sp.enc_io[i].x0 = i == 0;
+        sp.enc_io[i].pool = i < 6; sp.enc_io[i].pool_h = m.E[i].dh;
+    }
+    sp.dec_io[5].head = true;
+    HeadScSite hs;
+    hs.windows = m.windows; hs.tconv_cin = m.D[5].cin; hs.up_h = m.D[5].uh; hs.up_w = m.D[5].uw;
+    sp.head_sc_fold = head_sc_weights && m.E[0].dh == 2 && m.E[0].dw == 2 &&
+                      plan_head_sc_fold(cfg, m.enc_shape(0), sp.enc_io[0], m.dec_shape(5), sp.dec_io[5], hs, B, lv.eh[0], lv.ew[0]);
+    sp.enc_io[0].sc_planes = sp.dec_io[5].sc_planes = sp.head_sc_fold;
     const auto enc_runs = [&](int i) { return bf16_block_runs(cfg, m.enc_shape(i), lv.ew[i], i == 0); };
     const auto dec_runs = [&](int d) { return bf16_block_runs(cfg, m.dec_shape(d), lv.ew[5 - d], false); };
     const auto has_sc = [&](const BlockShape& b) { return b.cin != b.cout; };
     const auto up = [&](int d, bool in_act, bool out_copies) {
         UpSite site;
-        site.in_act = in_act; site.out_copies = out_copies; site.logits = d == 5 && sc_planes;
+        site.in_act = in_act; site.out_copies = out_copies; site.logits = d == 5 && sp.head_sc_fold;
         return plan_upconv(cfg, m.D[d], lv.eh[5 - d] / m.D[d].uh, lv.ew[5 - d] / m.D[d].uw, site);
+    };
+    // the hand-overs a block admits, back into the BlockIO it is called with
+    const auto admit = [](BlockIO& io, const Bf16Block& b, int up_cin) {
+        io.cat_in = b.cat_in; io.skip_out = b.skip_out; io.pool_copies = b.pool_copies; io.act_out = b.act_out;
+        io.up_cin = b.form == BF16_DEC6U ? up_cin : 0;
     };
     for (int d = 0; d < 6; ++d) sp.up[d] = up(d, false, false);  // the family does not depend on the hand-overs
     // decoders 2-6 (2 x 2 up-sampling) take their concat as the two blocked copies: half from the transposed conv, half from the
@@ -566,18 +601,16 @@ inline SeparatePlan plan_separate(const RouteCfg& cfg, const ModelTable& m, cons
     for (int i = 0; i < 4; ++i)
         pc[i] = cfg.blocked() && m.E[i].dh == 2 && lv.ew[i] % 32 == 0 && cb[5 - i] && cb[4 - i] && has_sc(m.enc_shape(i + 1)) && enc_runs(i + 1);
     for (int i = 0; i < 7; ++i) {
-        BlockIO io;
-        io.x0 = i == 0;
-        io.pool = i < 6; io.pool_h = m.E[i].dh;
+        BlockIO io = sp.enc_io[i];
         io.skip_out = i < 5 && cb[5 - i];
         io.cat_in = i >= 1 && i <= 4 && pc[i - 1];
         io.pool_copies = i < 4 && pc[i];
         sp.enc[i] = plan_bf16_block(cfg, m.enc_shape(i), lv.eh[i], lv.ew[i], io);
+        admit(sp.enc_io[i], sp.enc[i], 0);
     }
     for (int d = 0; d < 6; ++d) {
         const int e = 5 - d;
-        BlockIO io;
-        io.head = d == 5;
+        BlockIO io = sp.dec_io[d];
         io.cat_in = cb[d];
         // the output feeds only the next transposed conv: handed over activated
         io.act_out = d < 5 && cfg.blocked() && dec_runs(d) && has_sc(m.dec_shape(d)) && sp.up[d + 1].family == UP_BF16;
@@ -591,18 +624,21 @@ inline SeparatePlan plan_separate(const RouteCfg& cfg, const ModelTable& m, cons
                 sp.up[d] = UpRoute{UP_INSIDE, true, false};
             }
         }
+        admit(sp.dec_io[d], sp.dec[d], m.D[d].cin);
         if (sp.up[d].family != UP_INSIDE) sp.up[d] = up(d, d > 0 && sp.dec[d - 1].act_out, sp.dec[d].cat_in);
     }
-    for (int i = 0; i < 7; ++i) {
-        BlockIO io;  // (f32: the GEMM shortcuts are decided by shape, pool and head alone; lass_separate's inputs are aligned)
-        io.x0 = i == 0; io.pool = i < 6; io.pool_h = m.E[i].dh;
-        const int n = cfg.f32() ? 2 + plan_block(cfg, m.enc_shape(i), 1, lv.eh[i], lv.ew[i], io).shortcut_gemm : sp.enc[i].launches();
-        sp.conv_scopes += n * (i == 0 ? m.nbr : 1);
-    }
+    // the routes and the launches they make (f32: the GEMM shortcut is a launch of its own)
+    const auto route = [&](BlockRoute& rt, const BlockShape& b, int e, const BlockIO& io, const Bf16Block& bf, int times, bool slots) {
+        rt = plan_block(cfg, b, B, lv.eh[e], lv.ew[e], io);
+        sp.conv_scopes += (cfg.f32() ? 2 + rt.shortcut_gemm : bf.launches()) * times;
+        if (!slots) return;
+        if (rt.kpart_floats > sp.kpart_floats) sp.kpart_floats = rt.kpart_floats;
+        if (rt.v_floats > sp.v_floats) sp.v_floats = rt.v_floats;
+        if (rt.m_floats > sp.m_floats) sp.m_floats = rt.m_floats;
+    };
+    for (int i = 0; i < 7; ++i) route(sp.enc_rt[i], m.enc_shape(i), i, sp.enc_io[i], sp.enc[i], i == 0 ? m.nbr : 1, i > 0);
     for (int d = 0; d < 6; ++d) {
-        BlockIO io;
-        io.head = d == 5;
-        sp.conv_scopes += cfg.f32() ? 2 + plan_block(cfg, m.dec_shape(d), 1, lv.eh[5 - d], lv.ew[5 - d], io).shortcut_gemm : sp.dec[d].launches();
+        route(sp.dec_rt[d], m.dec_shape(d), 5 - d, sp.dec_io[d], sp.dec[d], 1, true);
         sp.tconv_scopes += sp.up[d].family != UP_INSIDE;
     }
     return sp;

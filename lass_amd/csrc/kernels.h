@@ -4,16 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "conv_route.h"  // ConvKind, the shape rules of the f32 conv families and the route of a block (host only, HIP-free)
-
-// The default STFT geometry (lass_create).  A context carries its own (api.hip: Geometry - n_fft, hop, bins), and every launch
-// interface below takes them as arguments: these four name the default's values, nothing reads them as "the" geometry.
-constexpr int LASS_NFFT = 1024;
-constexpr int LASS_HOP = 160;
-constexpr int LASS_NBINS = 513;
-constexpr int LASS_FCROP = 512;
-constexpr int LASS_COND = 512;
-constexpr int LASS_MAX_STFT_WINDOWS = 4;
+#include "conv_route.h"  // ConvKind, the shape rules of the f32 conv families and the route of a block, LASS_NFFT & co (host only, HIP-free)
 
 // ---- conv.hip -----------------------------------------------------------------------------------------------------
 struct ConvArgs {

@@ -32,8 +32,7 @@ const char* kKind[] = {"CONV1_ACT", "CONV2_IDENT", "CONV2_SHORTCUT", "TCONV_ACT"
 
 bool g_gemm_cols = false;  // the WINO4_GEMM argument was given: gemm= and m= trail the conv and block lines
 
-void print_block(const RouteCfg& cfg, const std::string& name, const BlockShape& b, int B, int H, int W, const BlockIO& io) {
-    const BlockRoute r = plan_block(cfg, b, B, H, W, io);
+void print_block(const std::string& name, const BlockShape& b, const BlockRoute& r) {
     const ConvRoute* cv[2] = {&r.conv1, &r.conv2};
     for (int k = 0; k < 2; ++k) {
         printf("conv %s.conv%d %s %s %d %d fold=%d scfold=%d", name.c_str(), k + 1, kFamily[cv[k]->family], kKind[cv[k]->kind],
@@ -81,41 +80,30 @@ int main(int argc, char** argv) {
     const int n_fft = arg(15, 0) ? arg(15, 0) : nwin ? 2048 : 1024;
     if ((n_fft != 1024 && n_fft != 2048) || (nwin && n_fft != 2048)) return 2;
     const ModelTable m = model_table(nwin, n_fft / 2);
-    const int nbr = m.nbr, fcrop = m.fcrop;
+    const int nbr = m.nbr;
     const Levels lv = model_levels(m, t_pad);
-    const int *eh = lv.eh, *ew = lv.ew;
-    // the head's shortcut logits at their producers: one decision for encoder_block1 and decoder_block6 of a lass_separate (HEAD = 1)
-    bool sc_planes = false;
-    if (head) {
-        BlockIO eio, dio;
-        eio.x0 = true; eio.pool = true; eio.pool_h = m.E[0].dh; eio.x_aligned = aligned;
-        dio.head = true; dio.x_aligned = aligned;
-        HeadScSite site;
-        site.windows = nwin; site.tconv_cin = m.D[5].cin; site.up_h = m.D[5].uh; site.up_w = m.D[5].uw;
-        sc_planes = plan_head_sc_fold(cfg, m.enc_shape(0), eio, m.dec_shape(5), dio, site, B, t_pad, fcrop);
-    }
+    // One lass_separate as the library plans it (HEAD = 1; the composed head-shortcut weights exist).  HEAD = 0 takes the head
+    // off: no head_sc_fold, and decoder_block6 on a default site, as the stage call runs it.
+    const SeparatePlan sp = plan_separate(cfg, m, lv, B, head);
+    // The planned route of each block; computed here only for X_ALIGNED = 0 (the same site with an input that misses pw_gemm.hip's
+    // alignment, as a stage call can be handed one) and for HEAD = 0's decoder_block6
+    const auto route = [&](const BlockShape& b, int e, BlockIO io, const BlockRoute* planned) {
+        if (planned && aligned) return *planned;
+        io.x_aligned = aligned;
+        return plan_block(cfg, b, B, lv.eh[e], lv.ew[e], io);
+    };
     for (int i = 0; i < 7; ++i)
         for (int k = 0; k < (i == 0 ? nbr : 1); ++k) {
-            BlockIO io;
-            io.x0 = i == 0;
-            io.pool = i < 6; io.pool_h = m.E[i].dh;
-            io.x_aligned = aligned;
-            io.sc_planes = i == 0 && sc_planes;
             const std::string name = i == 0 && nwin ? "encoder_block1s." + std::to_string(k) : m.E[i].name;
-            print_block(cfg, name, m.enc_shape(i), B, eh[i], ew[i], io);
+            print_block(name, m.enc_shape(i), route(m.enc_shape(i), i, sp.enc_io[i], &sp.enc_rt[i]));
         }
     for (int d = 0; d < 6; ++d) {
-        const int e = 5 - d;
-        BlockIO io;
-        io.head = head && d == 5;
-        io.x_aligned = aligned;
-        io.sc_planes = d == 5 && sc_planes;
-        print_block(cfg, m.D[d].name, m.dec_shape(d), B, eh[e], ew[e], io);
+        const bool stage = d == 5 && !head;
+        print_block(m.D[d].name, m.dec_shape(d), route(m.dec_shape(d), 5 - d, stage ? BlockIO() : sp.dec_io[d], stage ? nullptr : &sp.dec_rt[d]));
     }
     // The lines below come with the MODE argument only: a command line of up to ten arguments prints what it always printed.
     if (argc <= 11) return 0;
-    // one lass_separate (the stage calls have no hand-overs and no fused forms)
-    const SeparatePlan sp = plan_separate(cfg, m, lv, sc_planes);
+    // (the stage calls have no hand-overs and no fused forms)
     for (int d = 0; d < 6; ++d)
         printf("up %s %s in_act=%d out_copies=%d\n", m.D[d].name, kUpFamily[sp.up[d].family], (int)sp.up[d].in_act, (int)sp.up[d].out_copies);
     if (!cfg.f32()) {
