@@ -36,9 +36,6 @@
         Act a;
     };
     Stage S0, S1;
-    Act T;
-    // The scalar loads of a stage are issued in FRONT of a chunk's MFMAs, into T, and handed to the stage behind them: issued
-    // with the vector loads they would sit right in front of the barrier's lgkmcnt(0), their latency exposed in every chunk
     const auto aload = [&](Act& a, int ch) {
         if (TCONV) {
 #pragma unroll
@@ -55,12 +52,15 @@
 #pragma unroll
         for (int pc = 0; pc < 3; ++pc) st.w[pc] = ws[pc * wplane + (size_t)ch * (KC / 8) * Nw];
     };
-    const auto sstore = [&](const Stage& st, int buf) {  // the prologue and the split are applied here, once per staged element
+    // Staging in two halves, so that each can sit under its own part of a chunk's MFMAs: the prologue and the split, applied once
+    // per staged element (vector arithmetic alone), and the six LDS writes
+    const auto sprep = [&](const Stage& st, bf16x8 (&xp)[3]) {
         float x[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) x[j] = TCONV ? leaky(fmaf(st.x[j], st.a.s[j], st.a.h[j])) : st.x[j];  // (resunet.py:247)
-        bf16x8 xp[3];
         split3(x, xp[0], xp[1], xp[2]);
+    };
+    const auto swrite = [&](const Stage& st, const bf16x8 (&xp)[3], int buf) {
 #pragma unroll
         for (int pc = 0; pc < 3; ++pc) {
             lds[buf][0][pc][so * NB + sc] = st.w[pc];
@@ -78,33 +78,60 @@
 
     // fragments: A[i = lane & 31][k = 8 (lane >> 5) ... + 7] = W[k][n], B[k = 8 (lane >> 5) ... + 7][j = lane & 31] = X[k][pixel]
     const int fo = (lane >> 5) * NB + (lane & 31);
-    const auto mma = [&](int buf) {
-        bf16x8 fa[3][2], fb[3][2];  // [piece][tile]: all fragments of the chunk requested up front
+    // the six products in ONE fixed order, smallest first; every accumulator sees the same order whatever the batch
+    constexpr int WP[6] = {2, 0, 1, 1, 0, 0}, XP[6] = {0, 2, 1, 0, 1, 0};  // (lh, hl, mm, mh, hm, hh): 0 = h, 1 = m, 2 = l
+    const auto prod = [&](const bf16x8 (&fa)[3][2], const bf16x8 (&fb)[3][2], int t) {
+        f32x16(&d)[2][2] = (ACC2 && t < 5) ? accs : acc;  // (the small products: their own accumulators)
+        d[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[WP[t]][0], fb[XP[t]][0], d[0][0], 0, 0, 0);
+        d[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[WP[t]][0], fb[XP[t]][1], d[0][1], 0, 0, 0);
+        d[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[WP[t]][1], fb[XP[t]][0], d[1][0], 0, 0, 0);
+        d[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[WP[t]][1], fb[XP[t]][1], d[1][1], 0, 0, 0);
+    };
+    // One chunk of one wave: the 24 MFMAs of LDS buffer `buf`, and between them the staging of the other buffer from stage `st`,
+    // whose registers then take chunk `chn`.  Nothing in a chunk waits for anything else in it, so nothing is fenced off (round 21):
+    //   - the twelve fragment reads leave in the order the products take them - (W l, X h) for lh, (W h, X l) for hl, both m
+    //     pieces for mm - and LDS returns them in order: hipcc's counted lgkmcnt lets lh start behind the first three reads, the
+    //     others land under the MFMAs (lgkmcnt 9, 8, 5, 4, 1, 0);
+    //   - lh, hl and mm carry the prologue and the split of the staged X, a few vector instructions behind each MFMA;
+    //   - mh, hm and hh carry the six LDS writes and the global loads.  The scalar loads of the next scale and shift are issued
+    //     HERE and not earlier: scalar memory shares lgkmcnt with LDS and returns out of order, so with one of them in flight every
+    //     wait for a fragment is lgkmcnt(0).  Here the fragments have all landed; the barrier's own lgkmcnt(0) takes the loads.
+    // The MFMAs, their operands and their order per accumulator are those of the plain sequence: every sum keeps its bits.
+    constexpr int NV = TCONV ? 9 : 7;  // vector instructions behind each of the first twelve MFMAs: all of sprep's, spread
+    const auto phase = [&](int buf, Stage& st, int chn) {
+        bf16x8 fa[3][2], fb[3][2];  // [piece][tile]
+        bf16x8 xp[3];
+        constexpr int RW[3] = {2, 0, 1}, RX[3] = {0, 2, 1};
 #pragma unroll
-        for (int pc = 0; pc < 3; ++pc)
+        for (int g = 0; g < 3; ++g) {
 #pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                fa[pc][t] = lds[buf][0][pc][fo + wn * 64 + t * 32];
-                fb[pc][t] = lds[buf][1][pc][fo + wp * 64 + t * 32];
-            }
-        __builtin_amdgcn_sched_barrier(0);  // (pinned, as in the f32 kernel)
-        // the six products in ONE fixed order, smallest first; every accumulator sees the same order whatever the batch
-        constexpr int WP[6] = {2, 0, 1, 1, 0, 0}, XP[6] = {0, 2, 1, 0, 1, 0};  // (lh, hl, mm, mh, hm, hh): 0 = h, 1 = m, 2 = l
+            for (int t = 0; t < 2; ++t) fa[RW[g]][t] = lds[buf][0][RW[g]][fo + wn * 64 + t * 32];
 #pragma unroll
-        for (int t = 0; t < 6; ++t) {
-            if constexpr (ACC2) {
-                if (t < 5) {  // the small products: their own accumulators
-                    accs[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[WP[t]][0], fb[XP[t]][0], accs[0][0], 0, 0, 0);
-                    accs[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[WP[t]][0], fb[XP[t]][1], accs[0][1], 0, 0, 0);
-                    accs[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[WP[t]][1], fb[XP[t]][0], accs[1][0], 0, 0, 0);
-                    accs[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[WP[t]][1], fb[XP[t]][1], accs[1][1], 0, 0, 0);
-                    continue;
-                }
-            }
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[WP[t]][0], fb[XP[t]][0], acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[WP[t]][0], fb[XP[t]][1], acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[WP[t]][1], fb[XP[t]][0], acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[WP[t]][1], fb[XP[t]][1], acc[1][1], 0, 0, 0);
+            for (int t = 0; t < 2; ++t) fb[RX[g]][t] = lds[buf][1][RX[g]][fo + wp * 64 + t * 32];
+            __builtin_amdgcn_sched_barrier(0);  // (pinned: the counted waits count on this order)
+        }
+        prod(fa, fb, 0);
+        prod(fa, fb, 1);
+        prod(fa, fb, 2);
+        sprep(st, xp);
+#pragma unroll
+        for (int i = 0; i < 12; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // one MFMA
+            __builtin_amdgcn_sched_group_barrier(0x002, NV, 0);  // vector instructions
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        aload(st.a, chn);
+        __builtin_amdgcn_sched_barrier(0);  // (issued here: hipcc sinks them to the barrier otherwise, their latency exposed)
+        prod(fa, fb, 3);
+        prod(fa, fb, 4);
+        prod(fa, fb, 5);
+        swrite(st, xp, buf ^ 1);
+        gload(st, chn);
+#pragma unroll
+        for (int i = 0; i < 12; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);
+            if (i < 6) __builtin_amdgcn_sched_group_barrier(0x200, 1, 1);   // one LDS write
+            if (i >= 1) __builtin_amdgcn_sched_group_barrier(0x020, 1, 1);  // one global load
         }
         __builtin_amdgcn_sched_barrier(0);
     };
@@ -115,24 +142,24 @@
     aload(S1.a, 1);
     gload(S0, 0);
     gload(S1, 1);
-    sstore(S0, 0);
+    {
+        bf16x8 xp[3];
+        sprep(S0, xp);
+        swrite(S0, xp, 0);
+    }
     aload(S0.a, min(2, nch - 1));
     gload(S0, min(2, nch - 1));
     __syncthreads();
-    for (int ch = 0; ch < nch; ch += 2) {
-        aload(T, min(ch + 3, nch - 1));
-        mma(0);  // chunk ch
-        sstore(S1, 1);
-        S1.a = T;
-        gload(S1, min(ch + 3, nch - 1));
+    // Entered without a guard (nch >= 2, host-checked): behind a guard hipcc sinks the scalar loads above into the loop's
+    // preheader, past the barrier, and the first fragment wait of every other chunk becomes lgkmcnt(0)
+    int ch = 0;
+    do {
+        phase(0, S1, min(ch + 3, nch - 1));  // chunk ch
         __syncthreads();
-        aload(T, min(ch + 4, nch - 1));
-        mma(1);  // chunk ch + 1
-        sstore(S0, 0);  // (behind the last chunk: unused)
-        S0.a = T;
-        gload(S0, min(ch + 4, nch - 1));
+        phase(1, S0, min(ch + 4, nch - 1));  // chunk ch + 1 (behind the last chunk its staging is unused)
         __syncthreads();
-    }
+        ch += 2;
+    } while (ch < nch);
     if constexpr (ACC2) {
 #pragma unroll
         for (int i = 0; i < 2; ++i)
