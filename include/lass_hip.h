@@ -180,6 +180,33 @@ int lass_separate_windows(lass_ctx* ctx, const float* recording, int64_t total, 
                           const float* condition /* (B,512) */, float* out /* total floats */, int B, int W,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* lass_separate_windows with cross-faded seams.  Everything of lass_separate_windows holds - clamping of starts / keep, both kinds
+ * of context, both STFT geometries, all compute modes, lass_workspace_bytes(B, W), the split, graph replay - and the kept range of
+ * a window may begin and / or end with a FADE REGION whose samples are not stored but weighted and ADDED to `out`.
+ * fade: DEVICE int32 (2B), (fade-in flag, fade-out flag) of window b, any non-zero value meaning set; ramp: DEVICE f32 (F), the
+ * fade-in weights in ascending order (the fade-out reads the table backwards).  With (lo, hi) the clamped keep of window b and y
+ * its W output samples:
+ *   fade-in region,  if fade[2b]   != 0: n in [lo, min(lo + F, hi)),                                 weight ramp[n - lo];
+ *   fade-out region, if fade[2b+1] != 0: n in [max(hi - F, end of the fade-in region), hi),          weight ramp[hi - 1 - n].
+ * Both table indices lie in [0, F) by construction: a wrong entry gives wrong audio and never an access out of range, and the
+ * library never reads either array on the host.  A sample of [lo, hi) in neither region is stored as by lass_separate_windows,
+ * bit for bit; a sample of a region contributes the f32 product w * y[n], rounded once, ADDED to out[starts[b] + n] (one
+ * hardware f32 atomic add per sample).
+ * PRECONDITION: every sample that any window reaches through a fade region holds 0.0f before the first call that reaches it
+ * (zero-fill `out` once).  POSTCONDITION: once every window that reaches a sample has run, the sample equals
+ * fl(fl(w_a * y_a) + fl(w_b * y_b)) - in any grouping of the windows into calls, at any batch size, on either half-batch, eager
+ * or replayed: f32 addition commutes and 0 + a is exact, so two adds onto a zero give the same bits in either order.  (Products
+ * below the smallest normal f32 may be flushed to zero by the hardware add.)
+ * THE CALLER'S DUTY, across all the calls that stitch one `out`: a plainly stored range overlaps nothing, and a fade region
+ * coincides with at most ONE other fade region (the neighbouring window's complementary one).  lass_amd.longform plans and checks
+ * such calls.
+ * Graph replay: the key gains the fade and ramp POINTERS and F; their contents are read when the graph runs.  The second
+ * half-batch reads fade + 2*(B/2).
+ * LASS_ERR_ARG, nothing launched: whatever lass_separate_windows refuses, a null fade or ramp, F < 1, F > W. */
+int lass_separate_windows_faded(lass_ctx* ctx, const float* recording, int64_t total, const int64_t* starts, const int* keep,
+                                const int* fade, const float* ramp, int F, const float* condition /* (B,512) */,
+                                float* out /* total floats */, int B, int W, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Graph replay.  The third consecutive lass_separate call with the same pointers and shape is captured into a hipGraph
  * and replayed on the caller's stream from then on (one graph per context; a different combination is captured anew
  * after it, too, has been seen three times in a row).  Nothing else about the call changes; profiled
@@ -332,6 +359,11 @@ int lass_front_end_windows(lass_ctx* ctx, const float* recording, int64_t total,
  * with the context's hop, as everywhere.) */
 int lass_istft_windows(lass_ctx* ctx, const float* real, const float* imag, const int64_t* starts, const int* keep, int64_t total,
                        int B, int T, int W, int n_fft, int win_length, float* out, void* stream);
+/* lass_istft_windows with the fade regions of lass_separate_windows_faded (fade: DEVICE int32 (2B), ramp: DEVICE f32 (F),
+ * 1 <= F <= W): samples of a region are weighted and ADDED to `out`, which must hold 0 there beforehand. */
+int lass_istft_windows_faded(lass_ctx* ctx, const float* real, const float* imag, const int64_t* starts, const int* keep,
+                             const int* fade, const float* ramp, int F, int64_t total, int B, int T, int W, int n_fft,
+                             int win_length, float* out, void* stream);
 
 /* Where lass_separate(B, L) leaves a named intermediate inside the caller's workspace (f32 compute mode; in the bf16
  * modes several of these hold blocked bf16 data instead): byte offset, shape (B,C,H,W) and element strides.  Names:

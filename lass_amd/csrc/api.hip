@@ -763,7 +763,7 @@ const ResBlock* find_block(const lass_ctx* c, const std::string& prefix) {
 
 extern "C" {
 
-int lass_version(void) { return 10600; }  // 1.6.0: ResUNet30 at the (2048, 320) STFT geometry (lass_create_stft, lass_stft_geometry); 1.5.0: windows of one long row (lass_separate_windows & co); 1.4.0: per-clip lengths (lass_separate_ragged & co); 1.3.0: CLAP text tower (lass_text_*, text.hip); 1.2.0: F(4x4,3x3) kernels, lass_set_graph_replay (1.1.0: multi-STFT model, fused iSTFT, graph replay)
+int lass_version(void) { return 10700; }  // 1.7.0: cross-faded window seams (lass_separate_windows_faded, lass_istft_windows_faded); 1.6.0: ResUNet30 at the (2048, 320) STFT geometry (lass_create_stft, lass_stft_geometry); 1.5.0: windows of one long row (lass_separate_windows & co); 1.4.0: per-clip lengths (lass_separate_ragged & co); 1.3.0: CLAP text tower (lass_text_*, text.hip); 1.2.0: F(4x4,3x3) kernels, lass_set_graph_replay (1.1.0: multi-STFT model, fused iSTFT, graph replay)
 
 const char* lass_last_error(const lass_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_err.c_str(); }
 
@@ -1377,6 +1377,19 @@ int lass_istft_windows(lass_ctx* c, const float* real, const float* imag, const 
     return 0;
 }
 
+int lass_istft_windows_faded(lass_ctx* c, const float* real, const float* imag, const int64_t* starts, const int* keep,
+                             const int* fade, const float* ramp, int F, int64_t total, int B, int T, int W, int n_fft,
+                             int win_length, float* out, void* stream) {
+    if (!c || !real || !imag || !starts || !keep || !fade || !ramp || !out || B <= 0 || !istft_nfft_ok(c, n_fft) || W <= n_fft / 2 ||
+        total < W || T != 1 + W / c->g.hop || win_length < 32 || win_length > n_fft || (2048 % win_length) != 0 || F < 1 || F > W)
+        return fail(c, LASS_ERR_ARG, "lass_istft_windows_faded: bad argument (T = 1 + W/" + std::to_string(c ? c->g.hop : LASS_HOP) +
+                                         " frames per window, n_fft/2 < W <= total, 1 <= F <= W)");
+    if (int r = use_device(c)) return r;
+    HIP_TRY(c, lass_launch_istft2(real, imag, ClipForm{B, W, nullptr, starts, keep, total, fade, ramp, F}, T, n_fft, win_length,
+                                  c->g.hop, c->tw2k, out, (hipStream_t)stream));
+    return 0;
+}
+
 int lass_workspace_tensor(const lass_ctx* c, int B, int L, const char* name_c, size_t* offset, int64_t shape[4],
                           int64_t strides[4]) {
     if (!c || !name_c || !offset || !shape || !strides) return LASS_ERR_ARG;
@@ -1650,6 +1663,7 @@ static ClipForm upper_clips(const ClipForm& cf, int h, size_t* row) {
     if (cf.lengths) u.lengths = cf.lengths + h;
     if (cf.starts) u.starts = cf.starts + h;
     if (cf.keep) u.keep = cf.keep + 2 * h;
+    if (cf.fade) u.fade = cf.fade + 2 * h;
     *row = cf.starts ? 0 : (size_t)h * cf.L;
     return u;
 }
@@ -1700,6 +1714,7 @@ static int separate_call(lass_ctx* c, const float* mixture, const float* conditi
         key.mix = mixture; key.cond = condition; key.out = out; key.ws = workspace; key.lens = cf.lengths; key.B = B; key.L = L;
         key.gen = c->gen;
         key.starts = cf.starts; key.keep = cf.keep; key.total = cf.total;
+        key.fade = cf.fade; key.ramp = cf.ramp; key.F = cf.F;
         auto& slot = c->graphs.touch(key);
         if (c->graphs.drain_due()) {  // a caller cycling through many recurring keys: bound the list of evicted execs here
             HIP_TRY(c, hipSetDevice(c->device));
@@ -1774,10 +1789,10 @@ int lass_separate_ragged(lass_ctx* c, const float* mixture, const int* lengths, 
     return separate_call(c, mixture, condition, out, ClipForm{B, L, lengths}, workspace, workspace_bytes, stream, "lass_separate_ragged");
 }
 
-int lass_separate_windows(lass_ctx* c, const float* recording, int64_t total, const int64_t* starts, const int* keep,
-                          const float* condition, float* out, int B, int W, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!c) return LASS_ERR_ARG;
-    const std::string who = "lass_separate_windows";
+// lass_separate_windows and lass_separate_windows_faded behind the checks that only the latter has (fade == nullptr: the former)
+static int separate_windows(lass_ctx* c, const std::string& who, const float* recording, int64_t total, const int64_t* starts,
+                            const int* keep, const int* fade, const float* ramp, int F, const float* condition, float* out, int B,
+                            int W, void* workspace, size_t workspace_bytes, void* stream) {
     if (!recording || !starts || !keep || !condition || !out || !workspace) return fail(c, LASS_ERR_ARG, who + ": null pointer");
     if (B <= 0) return fail(c, LASS_ERR_ARG, who + ": need B >= 1");
     if (W <= c->g.nfft / 2)
@@ -1785,8 +1800,26 @@ int lass_separate_windows(lass_ctx* c, const float* recording, int64_t total, co
     if (total < W) return fail(c, LASS_ERR_ARG, who + ": the recording is shorter than one window (total < W)");
     const uintptr_t r0 = (uintptr_t)recording, o0 = (uintptr_t)out, bytes = (uintptr_t)total * sizeof(float);
     if (r0 < o0 + bytes && o0 < r0 + bytes) return fail(c, LASS_ERR_ARG, who + ": recording and out overlap");
-    return separate_call(c, recording, condition, out, ClipForm{B, W, nullptr, starts, keep, total}, workspace, workspace_bytes, stream,
-                         who.c_str());
+    return separate_call(c, recording, condition, out, ClipForm{B, W, nullptr, starts, keep, total, fade, ramp, F}, workspace,
+                         workspace_bytes, stream, who.c_str());
+}
+
+int lass_separate_windows(lass_ctx* c, const float* recording, int64_t total, const int64_t* starts, const int* keep,
+                          const float* condition, float* out, int B, int W, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!c) return LASS_ERR_ARG;
+    return separate_windows(c, "lass_separate_windows", recording, total, starts, keep, nullptr, nullptr, 0, condition, out, B, W,
+                            workspace, workspace_bytes, stream);
+}
+
+int lass_separate_windows_faded(lass_ctx* c, const float* recording, int64_t total, const int64_t* starts, const int* keep,
+                                const int* fade, const float* ramp, int F, const float* condition, float* out, int B, int W,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    if (!c) return LASS_ERR_ARG;
+    const std::string who = "lass_separate_windows_faded";
+    if (!fade || !ramp) return fail(c, LASS_ERR_ARG, who + ": null pointer");
+    if (F < 1 || F > W) return fail(c, LASS_ERR_ARG, who + ": the fade length must lie in [1, W]");
+    return separate_windows(c, who, recording, total, starts, keep, fade, ramp, F, condition, out, B, W, workspace, workspace_bytes,
+                            stream);
 }
 
 int lass_set_graph_replay(lass_ctx* c, int enabled) {

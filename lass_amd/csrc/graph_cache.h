@@ -13,11 +13,14 @@ struct GraphKey {
     const void* lens = nullptr;  // lass_separate_ragged's lengths (the pointer: its contents are read at replay time)
     const void *starts = nullptr, *keep = nullptr;  // lass_separate_windows' index arrays (pointers, as `lens`)
     int64_t total = 0;                              // ... and the length of its long rows
+    const void *fade = nullptr, *ramp = nullptr;    // lass_separate_windows_faded's flags and ramp (pointers again) ...
+    int F = 0;                                      // ... and its fade length
     int B = 0, L = 0;
     unsigned long gen = 0;  // bumped by lass_finalize: a graph holds weight pointers
     bool operator==(const GraphKey& o) const {
         return mix == o.mix && cond == o.cond && out == o.out && ws == o.ws && lens == o.lens && starts == o.starts &&
-               keep == o.keep && total == o.total && B == o.B && L == o.L && gen == o.gen;
+               keep == o.keep && total == o.total && fade == o.fade && ramp == o.ramp && F == o.F && B == o.B && L == o.L &&
+               gen == o.gen;
     }
 };
 

@@ -225,6 +225,10 @@ struct StftBranch {
 //   windows (starts: device int64 (B); lass_separate_windows): window b is wav[starts[b], starts[b] + L) of ONE row of `total`
 //           samples, and of its L output samples only keep[2b] <= n < keep[2b+1] (device int32 (2B), needed by the iSTFT alone)
 //           are stored, at out[starts[b] + n].  The kernels clamp starts into [0, total - L], lo into [0, L], hi into [lo, L].
+//   faded windows (windows with fade: device int32 (2B) flag pairs, ramp: device f32 (F), 1 <= F <= L;
+//           lass_separate_windows_faded): the first min(F, hi - lo) kept samples of a window whose fade[2b] is set, and the last
+//           F (cut where they would reach into the former) of one whose fade[2b+1] is set, are multiplied by ramp[n - lo] /
+//           ramp[hi - 1 - n] and ADDED to out[starts[b] + n].  Read by the iSTFT alone.
 struct ClipForm {
     int B = 0;
     int L = 0;  // samples per row, or per window
@@ -232,6 +236,9 @@ struct ClipForm {
     const int64_t* starts = nullptr;
     const int* keep = nullptr;
     int64_t total = 0;
+    const int* fade = nullptr;
+    const float* ramp = nullptr;
+    int F = 0;
 };
 hipError_t lass_launch_stft2(const float* wav, const ClipForm& cf, int n_fft, int hop, int T, int Tpad, int nbr,
                              const StftBranch* br, int magphase_sem, const float* s0, const float* h0,

@@ -162,12 +162,20 @@ __global__ __launch_bounds__(256) void multi_stft_kernel(const float* __restrict
 //       from `starts` (device int64), (lo_b, hi_b) from `keep` (device int32 pairs, read by the iSTFT alone).  Entries are
 //       clamped - s_b into [0, total - W], lo_b into [0, W], hi_b into [lo_b, W] - so a wrong entry gives wrong audio, never
 //       an access out of range.
+//   FadedWindowClips (lass_separate_windows_faded): WindowClips whose kept range may begin with a fade-in region and end with a
+//       fade-out region of up to F samples (`fade`: device int32 flag pairs; `ramp`: device f32 (F), ascending).  A sample of
+//       a region is not stored: its product with the ramp weight is ADDED to the output row, where the neighbouring window's
+//       complementary region adds the other half of the cross-fade.  The output holds 0 there beforehand, and two adds onto a
+//       zero give the same bits in either order, so the result does not depend on which window arrives first.  The regions
+//       are cut to the (clamped) kept range and to each other, so both table indices lie in [0, F) whatever the entries say.
+//       The forward side has no such form: a faded window reads its input as WindowClips does.
 struct Kept { int lo, hi, zend; };  // of a clip's output row the iSTFT stores samples [lo, hi) and writes [hi, zend) as 0
 
 struct DenseClips {
     int L;
     static constexpr bool kShort = false;    // may a clip have fewer frames than the launch's T?
     static constexpr bool kPartial = false;  // may a span of the iSTFT lie wholly outside what its clip stores?
+    static constexpr bool kFaded = false;    // are some kept samples added, weighted, instead of stored?
     template <class P> __device__ P* row(P* base, int b) const { return base + (size_t)b * L; }
     __device__ int len(int) const { return L; }
     __device__ int frames(int, int T, int) const { return T; }
@@ -177,7 +185,7 @@ struct DenseClips {
 struct RaggedClips {
     const int* __restrict__ lengths;
     int lo, L;
-    static constexpr bool kShort = true, kPartial = true;
+    static constexpr bool kShort = true, kPartial = true, kFaded = false;
     template <class P> __device__ P* row(P* base, int b) const { return base + (size_t)b * L; }
     __device__ int len(int b) const {
         const int v = lengths[b];
@@ -192,7 +200,7 @@ struct WindowClips {
     const int* __restrict__ keep;
     int64_t total;
     int W;
-    static constexpr bool kShort = false, kPartial = true;  // (an empty keep meets no span)
+    static constexpr bool kShort = false, kPartial = true, kFaded = false;  // (an empty keep meets no span)
     template <class P> __device__ P* row(P* base, int b) const {
         const int64_t v = starts[b], last = total - W;
         return base + (v < 0 ? 0 : (v > last ? last : v));
@@ -204,6 +212,22 @@ struct WindowClips {
         lo = lo < 0 ? 0 : (lo > W ? W : lo);
         hi = hi < lo ? lo : (hi > W ? W : hi);
         return {lo, hi, hi};
+    }
+};
+
+// of a kept range [lo, hi): [lo, in_end) fades in with ramp[n - lo], [out_begin, hi) fades out with ramp[hi - 1 - n]
+struct Fades { int in_end, out_begin; };
+
+struct FadedWindowClips : WindowClips {
+    const int* __restrict__ fade;
+    const float* __restrict__ ramp;
+    int F;  // 1 <= F <= W (the launcher refuses anything else)
+    static constexpr bool kFaded = true;
+    __device__ Fades fades(int b, const Kept& kp) const {
+        const int in_end = fade[2 * b] != 0 ? (kp.hi - kp.lo < F ? kp.hi : kp.lo + F) : kp.lo;
+        int out_begin = kp.hi;
+        if (fade[2 * b + 1] != 0) out_begin = kp.hi - F < in_end ? in_end : kp.hi - F;
+        return {in_end, out_begin};
     }
 };
 
@@ -395,10 +419,23 @@ __global__ __launch_bounds__(256) void istft2_kernel(const float* __restrict__ r
             __syncthreads();
         }
     }
-    for (int i = tid; i < ISTFT_SPAN; i += 256) {
-        const int n = m0 + i - N / 2;
-        if (n >= kp.lo && n < kp.hi) wav[n] = acc[i] / fmaxf(env[i], 1e-11f);
-        else if (n >= kp.hi && n < kp.zend) wav[n] = 0.f;
+    if constexpr (Clips::kFaded) {
+        // (the span early-out above stands: both regions lie inside [lo, hi).)  __fmul_rn: nothing contracts into the product
+        const Fades fd = clips.fades(b, kp);
+        for (int i = tid; i < ISTFT_SPAN; i += 256) {
+            const int n = m0 + i - N / 2;
+            if (n < kp.lo || n >= kp.hi) continue;
+            const float y = acc[i] / fmaxf(env[i], 1e-11f);
+            if (n < fd.in_end) atomicAdd(wav + n, __fmul_rn(clips.ramp[n - kp.lo], y));
+            else if (n >= fd.out_begin) atomicAdd(wav + n, __fmul_rn(clips.ramp[kp.hi - 1 - n], y));
+            else wav[n] = y;
+        }
+    } else {
+        for (int i = tid; i < ISTFT_SPAN; i += 256) {
+            const int n = m0 + i - N / 2;
+            if (n >= kp.lo && n < kp.hi) wav[n] = acc[i] / fmaxf(env[i], 1e-11f);
+            else if (n >= kp.hi && n < kp.zend) wav[n] = 0.f;
+        }
     }
 }
 
@@ -409,9 +446,17 @@ int ragged_lo(int L, int n_fft, int hop) {
     return a > b ? a : b;
 }
 
-// f(clips) with the device-side form of cf: the window form where it has starts, the ragged form where it has lengths
-template <class F>
+// f(clips) with the device-side form of cf: the window form where it has starts, the ragged form where it has lengths.  kFades:
+// the faded window form where cf has flags as well - the iSTFT's; what a window stores or adds is no business of the forward
+// side, which reads a faded window as WindowClips (and instantiates nothing new).
+template <bool kFades, class F>
 void with_clips(const ClipForm& cf, int n_fft, int hop, F f) {
+    if constexpr (kFades) {
+        if (cf.starts && cf.fade) {
+            f(FadedWindowClips{{cf.starts, cf.keep, cf.total, cf.L}, cf.fade, cf.ramp, cf.F});
+            return;
+        }
+    }
     if (cf.starts) f(WindowClips{cf.starts, cf.keep, cf.total, cf.L});
     else if (cf.lengths) f(RaggedClips{cf.lengths, ragged_lo(cf.L, n_fft, hop), cf.L});
     else f(DenseClips{cf.L});
@@ -460,7 +505,7 @@ hipError_t lass_launch_stft2(const float* wav, const ClipForm& cf, int n_fft, in
         a.real[i] = br[i].real; a.imag[i] = br[i].imag; a.x0[i] = br[i].x0;
     }
     dim3 grid(((any_x0 ? Tpad : T) + 1) / 2, B, nbr);
-    with_clips(cf, n_fft, hop, [&](auto clips) {
+    with_clips<false>(cf, n_fft, hop, [&](auto clips) {
         using C = decltype(clips);
         const auto kernel = n_fft == 1024 ? (magphase_sem ? stft2_kernel<1024, true, C> : stft2_kernel<1024, false, C>)
                                           : (magphase_sem ? stft2_kernel<2048, true, C> : stft2_kernel<2048, false, C>);
@@ -476,9 +521,10 @@ hipError_t lass_launch_istft2(const float* real, const float* imag, const ClipFo
     if (B <= 0 || (hop != LASS_HOP && !(hop == 320 && n_fft == 2048)) || bad_transform(n_fft, wlen)) return hipErrorInvalidValue;
     if (cf.starts || cf.lengths ? (L <= n_fft / 2 || T != 1 + L / hop) : (T <= 0 || L <= 0)) return hipErrorInvalidValue;
     if (cf.starts && (!cf.keep || !wav || cf.total < L)) return hipErrorInvalidValue;
+    if (cf.fade && (!cf.starts || !cf.ramp || cf.F < 1 || cf.F > L)) return hipErrorInvalidValue;
     const int span = hop == LASS_HOP ? kIstftSpan160 : kIstftSpan320;
     dim3 grid((n_fft / 2 + L + span - 1) / span, B);
-    with_clips(cf, n_fft, hop, [&](auto clips) {
+    with_clips<true>(cf, n_fft, hop, [&](auto clips) {
         using C = decltype(clips);
         const auto kernel = n_fft == 1024      ? istft2_kernel<1024, kIstftSpan160, C>
                             : hop == LASS_HOP ? istft2_kernel<2048, kIstftSpan160, C>

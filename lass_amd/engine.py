@@ -58,6 +58,7 @@ class Engine:
         self._ws_buf: Optional[torch.Tensor] = None  # ONE workspace, as large as the largest (B, L) seen so far
         self._ws_last = None                         # (B, L) of the last call that used it (its intermediates live there)
         self.ws_allocations = 0
+        self._fade_bufs: Dict[int, torch.Tensor] = {}  # B -> fade flags int32 (B,2), beside _win_bufs
         self._win_bufs: Dict[int, tuple] = {}        # B -> (starts int64 (B), keep int32 (B,2), condition (B,512)): persistent
         self.finalized = False
 
@@ -196,18 +197,40 @@ class Engine:
                                  torch.zeros(B, arch_cond(), dtype=torch.float32, device=self.device))
         return self._win_bufs[B]
 
-    def _window_index(self, starts, keep, total: int, W: int, checked: bool, what: str):
+    def fade_buffer(self, B: int) -> torch.Tensor:
+        """The engine's persistent fade flags of a B-window call, int32 (B,2), beside `window_buffers`: groups that stage their
+        flags here present the same pointer."""
+        B = int(B)
+        if B not in self._fade_bufs:
+            self._fade_bufs[B] = torch.zeros(B, 2, dtype=torch.int32, device=self.device)
+        return self._fade_bufs[B]
+
+    def _fade_ramp(self, fade, ramp, W: int, what: str) -> torch.Tensor:
+        """The ramp of a faded window call on the device, f32 (F) with 1 <= F <= W.  Keep it there between calls: a fresh upload
+        is a fresh pointer, and no graph replay."""
+        if fade is None or ramp is None:
+            raise ValueError(f"{what}: fade and ramp go together")
+        ramp = self._dev(torch.as_tensor(ramp))
+        if ramp.dtype != torch.float32 or ramp.dim() != 1 or not ramp.is_contiguous() or not 1 <= ramp.numel() <= W:
+            raise ValueError(f"{what}: ramp must be a contiguous 1-D float32 table of 1 to {W} weights")
+        return ramp
+
+    def _window_index(self, starts, keep, total: int, W: int, checked: bool, what: str, fade=None, F: int = 0):
         """starts / keep of a window call as device tensors (int64 (B), int32 (B,2)).  Python sequences (or numpy arrays, CPU
         tensors) are checked here - every window inside the recording, every keep inside its window, kept ranges disjoint
         (ValueError) - and staged into the engine's persistent buffers; device tensors are taken as they are, and only with
-        `checked=True` (the library never reads them; the kernels clamp).  keep None (the front end keeps nothing): empty keeps."""
+        `checked=True` (the library never reads them; the kernels clamp).  keep None (the front end keeps nothing): empty keeps.
+        fade (a faded call with a ramp of F weights): B (fade_in, fade_out) pairs, given the way starts and keep are and returned
+        as a third tensor, int32 (B,2); host flags are checked with the keeps (lass_amd.longform.check_keeps_faded: fade regions
+        may meet in pairs) and staged into `fade_buffer`."""
         if keep is None:
             on_device = torch.is_tensor(starts) and starts.is_cuda
             keep = torch.zeros(len(starts), 2, dtype=torch.int32, device=self.device) if on_device else [(0, 0)] * len(starts)
         dev_s, dev_k = torch.is_tensor(starts) and starts.is_cuda, torch.is_tensor(keep) and keep.is_cuda
-        if dev_s or dev_k:
-            if not (dev_s and dev_k):
-                raise _lib.LassError(f"{what}: starts and keep must both be device tensors or both host sequences")
+        dev_f = torch.is_tensor(fade) and fade.is_cuda
+        if dev_s or dev_k or dev_f:
+            if not (dev_s and dev_k and (dev_f or fade is None)):
+                raise _lib.LassError(f"{what}: starts and keep (and fade) must all be device tensors or all host sequences")
             if not checked:
                 raise _lib.LassError(f"{what}: device indices cannot be checked without a copy to the host: pass host "
                                      "sequences, or checked=True once you have checked them (lass_amd.longform.check_keeps)")
@@ -216,31 +239,56 @@ class Engine:
                     or keep.device != self.device or keep.dtype != torch.int32 or keep.numel() != 2 * B or not keep.is_contiguous()):
                 raise _lib.LassError(f"{what}: device indices must be contiguous int64 (B,) starts and int32 (B,2) keeps on "
                                      f"{self.device}")
-            return starts, keep
+            if fade is None:
+                return starts, keep
+            if fade.device != self.device or fade.dtype != torch.int32 or fade.numel() != 2 * B or not fade.is_contiguous():
+                raise _lib.LassError(f"{what}: device fade flags must be a contiguous int32 (B,2) tensor on {self.device}")
+            return starts, keep, fade
         hs = np.asarray(starts.numpy() if torch.is_tensor(starts) else starts)
         hk = np.asarray(keep.numpy() if torch.is_tensor(keep) else keep)
         B = hs.shape[0] if hs.ndim == 1 else 0
         if B < 1 or hk.size != 2 * B or not np.issubdtype(hs.dtype, np.integer) or not np.issubdtype(hk.dtype, np.integer):
             raise ValueError(f"{what}: starts must be B >= 1 integers and keep B (lo, hi) pairs of integers")
         hk = hk.reshape(B, 2)
-        longform.check_keeps([(int(a), int(lo), int(hi)) for a, (lo, hi) in zip(hs, hk)], W, total)
+        if fade is None:
+            longform.check_keeps([(int(a), int(lo), int(hi)) for a, (lo, hi) in zip(hs, hk)], W, total)
+        else:
+            hf = np.asarray(fade.numpy() if torch.is_tensor(fade) else fade)
+            if hf.size != 2 * B or not (np.issubdtype(hf.dtype, np.integer) or hf.dtype == np.bool_):
+                raise ValueError(f"{what}: fade must be B (fade_in, fade_out) pairs of integers")
+            hf = hf.reshape(B, 2).astype(np.int32)
+            longform.check_keeps_faded([(int(a), int(lo), int(hi), int(fi), int(fo)) for a, (lo, hi), (fi, fo) in zip(hs, hk, hf)],
+                                       W, total, F)
         buf_s, buf_k, _ = self.window_buffers(B)
         buf_s.copy_(torch.from_numpy(hs.astype(np.int64)))
         buf_k.copy_(torch.from_numpy(hk.astype(np.int32)))
-        return buf_s, buf_k
+        if fade is None:
+            return buf_s, buf_k
+        buf_f = self.fade_buffer(B)
+        buf_f.copy_(torch.from_numpy(hf))
+        return buf_s, buf_k, buf_f
 
     def separate_windows(self, recording: torch.Tensor, starts, keep, condition: torch.Tensor, window: int,
-                         out: Optional[torch.Tensor] = None, checked: bool = False) -> torch.Tensor:
+                         out: Optional[torch.Tensor] = None, checked: bool = False, fade=None, ramp=None) -> torch.Tensor:
         """B windows of ONE recording in one call (lass_separate_windows): recording (total,) f32; window b is
         recording[starts[b] : starts[b] + window], separated as that clip alone, and of its output only [lo_b, hi_b) =
         keep[b] is stored, at out[starts[b] + lo_b : starts[b] + hi_b].  Nothing else of `out` (total,) is touched: a fresh `out`
         is zero-filled, one passed in keeps its other samples.  condition (B,512), or (1,512) / (512,) for all windows (expanded
-        into a persistent buffer).  See `_window_index` for how starts / keep are checked."""
+        into a persistent buffer).  See `_window_index` for how starts / keep are checked.
+        fade, ramp (both or neither; lass_separate_windows_faded): B (fade_in, fade_out) flag pairs and the F ascending fade-in
+        weights (`_window_index`, `_fade_ramp`).  The first F kept samples of a window that fades in and the last F of one that fades out are
+        not stored but weighted and ADDED to `out`, which must hold 0 there before the first window reaches them (a fresh `out`
+        does); everything else is stored as without fades, bit for bit."""
         if recording.dim() != 1:
             raise ValueError("separate_windows takes a 1-D recording")
         recording = self._dev(recording)
         total, W = recording.shape[0], int(window)
-        idx_s, idx_k = self._window_index(starts, keep, total, W, checked, "separate_windows")
+        faded = fade is not None or ramp is not None
+        if faded:
+            ramp = self._fade_ramp(fade, ramp, W, "separate_windows")
+            idx_s, idx_k, idx_f = self._window_index(starts, keep, total, W, checked, "separate_windows", fade, ramp.numel())
+        else:
+            idx_s, idx_k = self._window_index(starts, keep, total, W, checked, "separate_windows")
         B = idx_s.numel()
         condition = self._dev(condition)
         if condition.numel() == arch_cond() and (B > 1 or condition.dim() == 1):
@@ -256,6 +304,12 @@ class Engine:
               or not out.is_contiguous()):
             raise _lib.LassError(f"out must be a contiguous float32 {tuple(recording.shape)} tensor on {self.device}")
         ws = self._workspace(B, W)
+        if faded:
+            rc = self.lib.lass_separate_windows_faded(self.ctx, _ptr(recording), total, _ptr(idx_s), _ptr(idx_k), _ptr(idx_f), _ptr(ramp),
+                                                      ramp.numel(), _ptr(cond), _ptr(out), B, W, _ptr(ws), ws.numel(),
+                                                      _stream(self.device))
+            _lib.check(self.ctx, rc, "lass_separate_windows_faded")
+            return out
         rc = self.lib.lass_separate_windows(self.ctx, _ptr(recording), total, _ptr(idx_s), _ptr(idx_k), _ptr(cond), _ptr(out), B, W,
                                             _ptr(ws), ws.numel(), _stream(self.device))
         _lib.check(self.ctx, rc, "lass_separate_windows")
@@ -420,18 +474,30 @@ class Engine:
         return mag, cos, sin, x0
 
     def istft_windows(self, real: torch.Tensor, imag: torch.Tensor, starts, keep, window: int, out: torch.Tensor,
-                      n_fft: Optional[int] = None, win_length: Optional[int] = None, checked: bool = False) -> torch.Tensor:
+                      n_fft: Optional[int] = None, win_length: Optional[int] = None, checked: bool = False, fade=None,
+                      ramp=None) -> torch.Tensor:
         """`istft_nfft` for windows (lass_istft_windows): real, imag (B, 1 + window // hop, n_fft/2+1); of window b's `window`
-        samples only keep[b] = [lo, hi) is stored, at out[starts[b] + lo : starts[b] + hi] of the 1-D `out`."""
+        samples only keep[b] = [lo, hi) is stored, at out[starts[b] + lo : starts[b] + hi] of the 1-D `out`.  fade, ramp: as for
+        `separate_windows` (lass_istft_windows_faded); `out` holds 0 in the fade regions beforehand."""
         real, imag, out = self._dev(real), self._dev(imag), self._dev(out)
         n_fft = self.n_fft if n_fft is None else int(n_fft)
         win_length = n_fft if win_length is None else int(win_length)
         B, T, F = real.shape
         assert F == n_fft // 2 + 1 and imag.shape == real.shape and out.dim() == 1
         total, W = out.shape[0], int(window)
-        idx_s, idx_k = self._window_index(starts, keep, total, W, checked, "istft_windows")
+        faded = fade is not None or ramp is not None
+        if faded:
+            ramp = self._fade_ramp(fade, ramp, W, "istft_windows")
+            idx_s, idx_k, idx_f = self._window_index(starts, keep, total, W, checked, "istft_windows", fade, ramp.numel())
+        else:
+            idx_s, idx_k = self._window_index(starts, keep, total, W, checked, "istft_windows")
         if idx_s.numel() != B:
             raise ValueError(f"istft_windows: {B} spectra, {idx_s.numel()} windows")
+        if faded:
+            rc = self.lib.lass_istft_windows_faded(self.ctx, _ptr(real), _ptr(imag), _ptr(idx_s), _ptr(idx_k), _ptr(idx_f), _ptr(ramp),
+                                                   ramp.numel(), total, B, T, W, n_fft, win_length, _ptr(out), _stream(self.device))
+            _lib.check(self.ctx, rc, "lass_istft_windows_faded")
+            return out
         rc = self.lib.lass_istft_windows(self.ctx, _ptr(real), _ptr(imag), _ptr(idx_s), _ptr(idx_k), total, B, T, W, n_fft,
                                          win_length, _ptr(out), _stream(self.device))
         _lib.check(self.ctx, rc, "lass_istft_windows")

@@ -207,14 +207,19 @@ class ResUNet30(nn.Module):
 
     @torch.no_grad()
     def separate_long(self, waveform: torch.Tensor, condition: torch.Tensor, window: int = 160000, context: int = 16000,
-                      max_batch: int = 16, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                      max_batch: int = 16, out: Optional[torch.Tensor] = None, fade: int = 0,
+                      fade_shape: str = "linear") -> torch.Tensor:
         """Separate a recording of ANY length (> n_fft/2): 1-D waveform, condition (512,) or (1,512) -> 1-D float32 tensor of
         the same length on the model's device.  The recording is cut into overlapping windows of `window` samples of which
         only the inner part is kept (`context` samples discarded towards each neighbour: lass_amd.longform.plan_windows) and
         stays on the device throughout: groups of `max_batch` windows run as one Engine.separate_windows each, all on the same
         recording, output, index buffers and workspace, so from the third group on a group is one replayed hipGraph.  The index
         buffers are rewritten by stream-ordered device copies between groups: no host synchronisation, no copy to the host.
-        total <= window: one plain `separate`."""
+        total <= window: one plain `separate`.
+        fade > 0 (even, <= 2 * context and <= window - 2 * context: lass_amd.longform.plan_windows_faded): neighbouring windows are
+        cross-faded over the `fade` samples around each seam, with complementary "linear" or "hann" weights
+        (lass_amd.longform.fade_ramp), instead of switched between.  Both windows' samples of a zone are ADDED into the output,
+        which is therefore zero-filled first - a caller-passed `out` too, whatever it held.  fade = 0: hard seams."""
         if self.training:
             raise LassError("lass_amd.ResUNet30 is inference-only (call .eval()); training is out of scope")
         if waveform.dim() != 1:
@@ -222,7 +227,15 @@ class ResUNet30(nn.Module):
         eng = self._ensure_engine()
         dev = eng.device
         total = int(waveform.shape[0])
-        plan = longform.plan_windows(total, window, context, eng.n_fft)
+        fade = int(fade)
+        if fade < 0:
+            raise ValueError("fade must not be negative")
+        if fade:
+            plan = longform.plan_windows_faded(total, window, context, fade, eng.n_fft)
+            ramp = longform.fade_ramp(fade, fade_shape)
+        else:
+            plan = longform.plan_windows(total, window, context, eng.n_fft)
+            ramp = None
         rec = waveform.to(device=dev, dtype=torch.float32).contiguous()
         cond = condition.to(device=dev, dtype=torch.float32).reshape(1, -1).contiguous()
         if cond.shape != (1, self.condition_size):
@@ -232,20 +245,103 @@ class ResUNet30(nn.Module):
         if total <= window:
             sep = eng.separate(rec[None], cond)[0]
             return sep if out is None else out.copy_(sep)
-        if out is None:
-            out = torch.empty_like(rec)  # the kept ranges tile it exactly once
-        groups = longform.group_windows(plan, max_batch)
-        B = len(groups[0])
-        # the whole plan goes up in two copies; each group's rows then reach the engine's index buffers device to device
+        if fade:
+            out = torch.zeros_like(rec) if out is None else out.zero_()
+            groups = longform.group_windows_faded(plan, max_batch)
+        else:
+            if out is None:
+                out = torch.empty_like(rec)  # the kept ranges tile it exactly once
+            groups = longform.group_windows(plan, max_batch)
+        self._run_windows(eng, rec, out, window, groups, cond, None, ramp)
+        return out
+
+    @staticmethod
+    def _run_windows(eng: Engine, rec: torch.Tensor, out: torch.Tensor, window: int, groups, cond: torch.Tensor, cond_rows, ramp) -> None:
+        """Groups of equally many windows of ONE row - (start, lo, hi) or, with a `ramp`, (start, lo, hi, fade_in, fade_out) - as
+        one Engine.separate_windows each, on the engine's persistent index buffers.  cond_rows None: row 0 of `cond` for every
+        window; else the row of `cond` per window, grouped as `groups`.  The whole plan goes up in a few copies; each group's rows
+        reach the index buffers by stream-ordered device copies: no host synchronisation."""
+        dev, B = eng.device, len(groups[0])
         all_starts = torch.tensor([[w[0] for w in g] for g in groups], dtype=torch.int64).to(dev)
-        all_keeps = torch.tensor([[w[1:] for w in g] for g in groups], dtype=torch.int32).to(dev)
+        all_keeps = torch.tensor([[w[1:3] for w in g] for g in groups], dtype=torch.int32).to(dev)
         idx_s, idx_k, cond_b = eng.window_buffers(B)
-        cond_b.copy_(cond.expand(B, -1))
+        idx_f = ramp_d = None
+        if ramp is not None:
+            all_fades = torch.tensor([[w[3:5] for w in g] for g in groups], dtype=torch.int32).to(dev)
+            idx_f, ramp_d = eng.fade_buffer(B), torch.from_numpy(ramp).to(dev)  # (the ramp is uploaded once)
+        if cond_rows is None:
+            cond_b.copy_(cond.expand(B, -1))
+        else:
+            all_rows = torch.tensor(cond_rows, dtype=torch.int64).to(dev)
         for gi in range(len(groups)):
             idx_s.copy_(all_starts[gi])
             idx_k.copy_(all_keeps[gi])
-            eng.separate_windows(rec, idx_s, idx_k, cond_b, window, out=out, checked=True)
-        return out
+            if idx_f is not None:
+                idx_f.copy_(all_fades[gi])
+            if cond_rows is not None:
+                torch.index_select(cond, 0, all_rows[gi], out=cond_b)
+            eng.separate_windows(rec, idx_s, idx_k, cond_b, window, out=out, checked=True, fade=idx_f, ramp=ramp_d)
+
+    @torch.no_grad()
+    def separate_long_list(self, waveforms: Sequence[torch.Tensor], conditions, window: int = 160000, context: int = 16000,
+                           max_batch: int = 16, fade: int = 0, fade_shape: str = "linear") -> List[torch.Tensor]:
+        """`separate_long` for several recordings in one pass: waveforms = 1-D float32 tensors of ANY lengths, conditions (N,512)
+        (or N tensors of 512) -> N 1-D tensors on the model's device, in input order, each what `separate_long` gives for that
+        recording alone (f32: bit for bit).  The recordings longer than `window` are laid end to end in one device row and each
+        is planned on its own (lass_amd.longform.plan_windows / plan_windows_faded, the starts offset by its position): no
+        window straddles two recordings and no fade crosses a boundary.  The windows of all of them are then grouped together,
+        each with its own recording's condition, and run as Engine.separate_windows calls on that one row, one output and one
+        set of index buffers - so a folder of short files fills every group and reaches graph replay, which one `separate_long`
+        per file does not.  The results are views of the one output row.  Recordings not longer than `window` go through
+        `separate_list`."""
+        if self.training:
+            raise LassError("lass_amd.ResUNet30 is inference-only (call .eval()); training is out of scope")
+        eng = self._ensure_engine()
+        dev = eng.device
+        n = len(waveforms)
+        if any(w.dim() != 1 for w in waveforms):
+            raise ValueError("separate_long_list takes 1-D waveforms")
+        cond = conditions if torch.is_tensor(conditions) else torch.stack(list(conditions))
+        cond = cond.to(device=dev, dtype=torch.float32).contiguous()
+        if cond.shape != (n, self.condition_size):
+            raise ValueError(f"conditions must be ({n}, {self.condition_size})")
+        window, fade = int(window), int(fade)
+        if fade < 0:
+            raise ValueError("fade must not be negative")
+        lengths = [int(w.shape[0]) for w in waveforms]
+        long_ids = [i for i in range(n) if lengths[i] > window]
+        short_ids = [i for i in range(n) if lengths[i] <= window]
+        results: List[Optional[torch.Tensor]] = [None] * n
+        if short_ids:
+            for i, sep in zip(short_ids, self.separate_list([waveforms[i] for i in short_ids], cond[short_ids], max_batch)):
+                results[i] = sep
+        if not long_ids:
+            return results
+        rows, cond_rows, offsets, at = [], [], {}, 0
+        for i in long_ids:
+            if fade:
+                plan = longform.plan_windows_faded(lengths[i], window, context, fade, eng.n_fft)
+            else:
+                plan = longform.plan_windows(lengths[i], window, context, eng.n_fft)
+            rows += [(w[0] + at,) + tuple(w[1:]) for w in plan]
+            cond_rows += [i] * len(plan)
+            offsets[i] = at
+            at += lengths[i]
+        rec = torch.empty(at, dtype=torch.float32, device=dev)
+        for i in long_ids:
+            rec[offsets[i]:offsets[i] + lengths[i]].copy_(waveforms[i], non_blocking=True)
+        if fade:
+            out, ramp = torch.zeros_like(rec), longform.fade_ramp(fade, fade_shape)
+            groups = longform.group_windows_faded(rows, max_batch)
+        else:
+            out, ramp = torch.empty_like(rec), None  # the kept ranges tile it exactly once
+            groups = longform.group_windows(rows, max_batch)
+        B = len(groups[0])
+        cond_rows += [cond_rows[-1]] * (len(groups) * B - len(cond_rows))  # (the padding rows store nothing)
+        self._run_windows(eng, rec, out, window, groups, cond, [cond_rows[g * B:(g + 1) * B] for g in range(len(groups))], ramp)
+        for i in long_ids:
+            results[i] = out[offsets[i]:offsets[i] + lengths[i]]
+        return results
 
     @torch.no_grad()
     def forward(self, input_dict: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
