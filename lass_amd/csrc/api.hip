@@ -1144,10 +1144,10 @@ int lass_finalize(lass_ctx* c, int compute_mode) {
                 }
             }
             HeadFold hf;
-            if (compose_head_fold(w2.data(), ws.data(), bs.data(), wa.data(), ba.data(), N, N, K, Q, &hf)) {
-                if (dev_alloc(c, &rb.u2h, hf.u.size()) || dev_alloc(c, &rb.wsch, hf.wsc.size()) || dev_alloc(c, &rb.bh, hf.bias.size()))
+            if (compose_head_fold(w2.data(), ws.data(), bs.data(), wa.data(), ba.data(), N, N, K, Q, &hf) && !hf.u4.empty()) {
+                if (dev_alloc(c, &rb.u2h, hf.u4.size()) || dev_alloc(c, &rb.wsch, hf.wsc.size()) || dev_alloc(c, &rb.bh, hf.bias.size()))
                     return LASS_ERR_HIP;
-                HIP_TRY(c, hipMemcpy(rb.u2h, hf.u.data(), hf.u.size() * sizeof(float), hipMemcpyHostToDevice));
+                HIP_TRY(c, hipMemcpy(rb.u2h, hf.u4.data(), hf.u4.size() * sizeof(float), hipMemcpyHostToDevice));
                 HIP_TRY(c, hipMemcpy(rb.wsch, hf.wsc.data(), hf.wsc.size() * sizeof(float), hipMemcpyHostToDevice));
                 HIP_TRY(c, hipMemcpy(rb.bh, hf.bias.data(), hf.bias.size() * sizeof(float), hipMemcpyHostToDevice));
             }

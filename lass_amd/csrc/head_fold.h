@@ -2,9 +2,10 @@
 // sits between x12 = shortcut(cat) + conv2(h) and after_conv(x12), so the Q = 3 mask logits are one linear map of h and cat:
 //      logit[q] = sum_{c,tap} W2'[q][c][tap] h[c] + sum_k Wsc'[q][k] cat[k] + b'[q]
 //      W2' = Wa W2,   Wsc' = Wa Wsc,   b' = Wa bsc + ba
-// formed here in double from the f32 checkpoint, rounded to f32 ONCE and zero-padded to the 16 rows of one MFMA tile; W2' then
+// formed here in double from the f32 checkpoint, rounded to f32 ONCE and zero-padded to 16 rows (Wsc': one 16x16x4 MFMA tile); W2' then
 // goes through the F(4x4,3x3) weight transform G g G^T (double, as wino4_weights_kernel) into the LDS images that
-// wino4_headfold_kernel copies in by LDS-DMA.  The images depend on the checkpoint only: lass_finalize prepares them once.
+// wino4_headfold_kernel copies in by LDS-DMA (the compact 4-row form, u4; the 16-row form holds the same values).  The images
+// depend on the checkpoint only: lass_finalize prepares them once.
 // Host only and free of HIP, as conv_route.h: tools/head_fold_check.cpp holds the algebra and the padding on the CPU.
 #pragma once
 #include <stddef.h>
@@ -22,12 +23,26 @@ inline size_t head_fold_u_index(int cin, int xi, int row) {
     return (size_t)(cin / kWino4KC) * kHeadFoldUFloats + (size_t)(((xi >> 1) * 2 + k) * 64 + kq * kHeadFoldRows + row) * 2 + (xi & 1);
 }
 
+// The compact image of the same values, which the folded-head kernels copy in: their contraction runs on 4-row MFMA blocks
+// (v_mfma_f32_4x4x1_16b_f32: rows = the 3 logits and ONE zero row), so only rows 0 .. 3 of the 16 exist here.  One 8-channel
+// chunk: [k-step 2][row 4][xi 36][kq = cin % 4] - a lane's A operands of one chunk, the 9 xi of its wave x 4 channels of its
+// k-step, are 36 consecutive floats (9 16-byte reads) - followed by zeros up to a whole number of 1-KiB LDS-DMA pieces.
+constexpr int kHeadFoldRows4 = 4;
+constexpr int kHeadFoldU4Live = kWino4NXI * kWino4KC * kHeadFoldRows4;      // 1 152 floats addressed by head_fold_u4_index
+constexpr int kHeadFoldU4Floats = (kHeadFoldU4Live + 255) / 256 * 256;      // 1 280: five pieces
+
+inline size_t head_fold_u4_index(int cin, int xi, int row) {
+    const int k = (cin & 7) >> 2, kq = cin & 3;
+    return (size_t)(cin / kWino4KC) * kHeadFoldU4Floats + (size_t)((k * kHeadFoldRows4 + row) * kWino4NXI + xi) * 4 + kq;
+}
+
 struct HeadFold {
     int Q = 0, C = 0, K = 0;
     std::vector<float> w2;    // W2'  [16][C][3][3], rows >= Q zero
     std::vector<float> wsc;   // Wsc' [K][16], columns >= Q zero (the kernel's A operand of input channel k is one row)
     std::vector<float> bias;  // b'   [16]
     std::vector<float> u;     // G W2' G^T as LDS images: C / 8 chunks of kHeadFoldUFloats (head_fold_u_index)
+    std::vector<float> u4;    // ... rows 0 .. 3 of it, compact: C / 8 chunks of kHeadFoldU4Floats (head_fold_u4_index); empty if Q > 3
 };
 
 // w2 (N, C, 3, 3), wsc (N, K), bsc (N), wa (Q, N), ba (Q): PyTorch layouts.  false: a shape the images cannot hold.
@@ -41,6 +56,8 @@ inline bool compose_head_fold(const float* w2, const float* wsc, const float* bs
     f.wsc.assign((size_t)K * kHeadFoldRows, 0.f);
     f.bias.assign(kHeadFoldRows, 0.f);
     f.u.assign((size_t)(C / kWino4KC) * kHeadFoldUFloats, 0.f);
+    f.u4.clear();
+    if (Q < kHeadFoldRows4) f.u4.assign((size_t)(C / kWino4KC) * kHeadFoldU4Floats, 0.f);  // (row 3 stays the zero row)
     for (int q = 0; q < Q; ++q) {
         for (int i = 0; i < C * 9; ++i) {
             double s = 0;
@@ -67,6 +84,8 @@ inline bool compose_head_fold(const float* w2, const float* wsc, const float* bs
             for (int a = 0; a < 6; ++a)
                 for (int c = 0; c < 6; ++c)
                     f.u[head_fold_u_index(ci, a * 6 + c, q)] = (float)(t[a][0] * G[c][0] + t[a][1] * G[c][1] + t[a][2] * G[c][2]);
+            if (!f.u4.empty())  // the same rounded values, not a second rounding
+                for (int xi = 0; xi < kWino4NXI; ++xi) f.u4[head_fold_u4_index(ci, xi, q)] = f.u[head_fold_u_index(ci, xi, q)];
         }
     return true;
 }
@@ -76,8 +95,8 @@ inline bool compose_head_fold(const float* w2, const float* wsc, const float* bs
 // non-linear behind it.  So Wsc' cat = Wsc'_skip x1 + Wt' act(x11) with
 //      Wt'[k][q][a][bb] = sum_c Wsc'_up[q][c] Wt[k][c][a][bb]          (Wsc' = Wa Wsc, split at channel Cup)
 // again in double from the f32 checkpoint and rounded to f32 ONCE (Wsc' enters in double, not as HeadFold::wsc).  b' is untouched.
-constexpr int kHeadScCols = 64;   // columns of the slab the transposed conv's extra block stages (the pitch of its other blocks)
-constexpr int kHeadScLive = 32;   // ... of which it contracts the first 32-column tile: Q * uh * uw live columns, the rest zero
+constexpr int kHeadScCols = 64;   // columns (the pitch) of the slab, as a cout block of the transposed conv has
+constexpr int kHeadScLive = 32;   // ... of which at most the first 32 are live: Q * uh * uw columns, the rest zero (the kernel reads 16)
 
 struct HeadScFold {
     int Q = 0, Cup = 0, Cskip = 0, Kt = 0;
@@ -86,7 +105,7 @@ struct HeadScFold {
 };
 
 // wsc (N, Cup + Cskip), wa (Q, N), wt (Kt, Cup, uh, uw): PyTorch layouts (ConvTranspose2d: input channel first).  false: a shape
-// the extra block cannot hold.
+// the slab cannot hold.
 inline bool compose_head_sc_fold(const float* wsc, const float* wa, const float* wt, int N, int Cup, int Cskip, int Q, int Kt, int uh, int uw,
                                  HeadScFold* out) {
     if (!wsc || !wa || !wt || !out || N <= 0 || Cup <= 0 || Cskip <= 0 || Q <= 0 || Kt <= 0 || uh <= 0 || uw <= 0 || Q * uh * uw > kHeadScLive)

@@ -105,7 +105,7 @@ struct Wino4VPre {
 
 // The folded head's shortcut logits, formed where their inputs are produced (conv_route.h: head_sc_fold): Wsc' cat = Wsc'_skip x1 +
 // (Wsc'_up o Wt) act(x11), as two sets of planes [B][3][H][W] f32 at decoder_block6's resolution.  encoder_block1.conv2 writes
-// `skip` from its epilogue registers, the transposed conv's extra cout block writes `up`, the head adds (skip + up) to its conv
+// `skip` from its epilogue registers, the transposed conv's two cout blocks write `up` (12 more columns), the head adds (skip + up) to its conv
 // sum.  (Beside ConvArgs for the same reason as Wino4Split.)
 struct HeadScPlanes {
     float* skip = nullptr;
@@ -122,8 +122,8 @@ inline ConvShape lass_conv_shape(const ConvArgs& p) {
 }
 
 hipError_t lass_launch_conv(ConvKind kind, const ConvArgs& p, hipStream_t stream);
-// TCONV_ACT (2 x 2, f32 output) with one more cout block in the same launch: hs.w = Wt' [Cin][64], of whose first 32-column tile
-// the 12 live columns (3 logits x 4 sub-pixels) go to hs.up as three planes at the up-sampled resolution
+// TCONV_ACT (2 x 2, f32 output, two cout blocks) with 12 more columns in the same launch: hs.w = Wt' [Cin][64], whose 12 live
+// columns (3 logits x 4 sub-pixels) go to hs.up as three planes at the up-sampled resolution
 bool lass_tconv_logits_supported(const ConvArgs& p, const HeadScPlanes& hs);
 hipError_t lass_launch_tconv_logits(const ConvArgs& p, const HeadScPlanes& hs, hipStream_t stream);
 

@@ -86,15 +86,17 @@ __global__ __launch_bounds__(NTHREADS, 2) void wino4_sclogit_kernel(ConvArgs p, 
 }
 
 // decoder_block6.conv2 with the output head, on weights composed with after_conv (head_fold.h): the 3 mask logits are one linear
-// map of the conv input h and the shortcut input cat, so only 3 output rows are formed - padded to ONE 16-row MFMA tile where
-// wino4_kernel<.., F_MASK> forms 32 channels on two and then reduces them 32 -> 3 through 48 KiB of LDS.  Same workgroup (4 waves,
-// 32 tiles, 8-channel chunks), same V image and input transform (wino4_input.h).  The two waves that own the two cout tiles there
-// own the two K-STEPS of a chunk here (wk): 36 MFMAs per wave and chunk into the same 36 accumulators, then the shortcut's
-// k-steps half and half.  Each wave ends with a partial logit set over its half of the channels; the two are summed through LDS
-// in a fixed order (k-step 0 + k-step 1, then b'), so a clip's result depends on nothing but the clip.
-// p: w_wino4 = the composed U images (kHeadFoldUFloats per chunk), w2 = Wsc' [Cin2][16], bias = b' [16]; mask_w / mask_b unused.
+// map of the conv input h and the shortcut input cat, so only 3 output rows are formed - padded to the 4 rows of the multi-block
+// MFMA form (wino4_head_body.h) where wino4_kernel<.., F_MASK> forms 32 channels on two 16-row tiles and then reduces them 32 -> 3
+// through 48 KiB of LDS.  Same workgroup (4 waves, 32 tiles, 8-channel chunks), same V image and input transform (wino4_input.h).
+// A wave owns 9 of the 36 xi, for all tiles and both K-STEPS of a chunk: 36 MFMAs of 8 cycles per wave and chunk into 9
+// accumulators (36 registers; 42 KiB of LDS: three workgroups per CU).  Behind the chunk loop the accumulators change hands once
+// through LDS, every lane transforms one (k-step, logit, tile), and the shortcut's k-steps run half and half.  Each k-step ends
+// with a partial logit set over its half of the channels; the two are summed through LDS in a fixed order (k-step 0 + k-step 1,
+// then b'), so a clip's result depends on nothing but the clip.
+// p: w_wino4 = the composed compact U images (kHeadFoldU4Floats per chunk), w2 = Wsc' [Cin2][16], bias = b' [16]; mask_w / mask_b unused.
 template <int TC>
-__global__ __launch_bounds__(NTHREADS, 2) void wino4_headfold_kernel(ConvArgs p) {
+__global__ __launch_bounds__(NTHREADS, 3) void wino4_headfold_kernel(ConvArgs p) {
     constexpr bool PLANES = false;
     const HeadScPlanes hs;
 #include "wino4_head_body.h"
@@ -102,7 +104,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void wino4_headfold_kernel(ConvArgs p)
 // ... with the shortcut's logits read as planes (hs.skip + hs.up) that encoder_block1.conv2 and the transposed conv wrote: no shortcut
 // phase, in2 / w2 are not read.  Final sum per pixel: (k-step 0 + k-step 1) + (skip + up) + b', in that order.
 template <int TC>
-__global__ __launch_bounds__(NTHREADS, 2) void wino4_headfold_planes_kernel(ConvArgs p, HeadScPlanes hs) {
+__global__ __launch_bounds__(NTHREADS, 3) void wino4_headfold_planes_kernel(ConvArgs p, HeadScPlanes hs) {
     constexpr bool PLANES = true;
 #include "wino4_head_body.h"
 }

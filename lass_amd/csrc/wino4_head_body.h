@@ -2,11 +2,25 @@
 // wino4_body.h, and for its reason): wino4_headfold_kernel (ConvArgs alone: the composed shortcut runs here, over in2) and
 // wino4_headfold_planes_kernel (ConvArgs + HeadScPlanes: the shortcut's logits arrive as two sets of planes, conv_route.h's
 // head_sc_fold).  In scope: TC, PLANES, `p`, `hs`.
+//
+// The chunk loop contracts on v_mfma_f32_4x4x1_16b_f32: 16 independent 4 x 4 blocks with K = 1, lane 4 b + i holding A row i and
+// B column i of block b and, in D register r, element (r, i).  A block's rows are the 3 logits and one zero row, its columns 4
+// tiles; the 16 blocks of one instruction are (k-step 2) x (8 groups of 4 tiles) at ONE xi and ONE input channel of the k-step, so
+// the 64 B values of an instruction are one whole 256-byte row of the V image.  Wave w owns xi 9 w .. 9 w + 8: per chunk 4
+// channels x 9 xi = 36 instructions into 9 accumulators, the channel outermost (9 independent instructions between two on one
+// accumulator), each accumulator summing its k-step's channels in ascending order, chunk by chunk - the order of the 16x16x4 form
+// this replaces, whose 16 rows held the same 3 logits.
     constexpr bool PRO = false, PRE = false;  // conv2 reads conv1's activated output as it is
     constexpr int TR = 32 / TC;
     constexpr int OR_ = 4 * TR, OC = 4 * TC;
-    constexpr int UH_F = kHeadFoldUFloats;      // 18 KiB: [xi pair][k-step][kq][row 16][xi & 1]
+    constexpr int UH_F = kHeadFoldU4Floats;     // 5 KiB: [k-step][row 4][xi][kq], 4.5 KiB of it live (head_fold_u4_index)
     constexpr int NQ = 3;                       // logits
+    constexpr int NXW = NXI / 4;                // xi of a wave
+    // the hand-over of the accumulators behind the chunk loop, in the dead U / V region: [k-step][logit][xi][tile], the strides
+    // padded so that neither its writers (lanes = k-step x tile) nor its readers (lanes = logit x 16 tiles) meet in a bank ...
+    constexpr int XQ_F = NXI * 32 + 16, XK_F = NQ * XQ_F + 48, X_F = 2 * XK_F;
+    // ... and behind it the partial logits [k-step][logit][pixel = tile * 16 + s] (2 x 3 x 512 floats)
+    static_assert(X_F % 4 == 0 && X_F + 2 * NQ * 512 <= UH_F + V_F, "the hand-over images fit into the dead U / V region");
     __shared__ __attribute__((aligned(16))) float lds[UH_F + V_F + kHeadFoldRows];
     float* lu = lds;
     float* lv = lds + UH_F;
@@ -14,27 +28,33 @@
 
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wk = wave >> 1, wwt = wave & 1;  // k-step of a chunk (and half of the shortcut's channels) / tile group of this wave
+    const int wk = wave >> 1, wwt = wave & 1;  // behind the chunk loop: k-step (and half of the shortcut's channels) / tile group of this wave
     int bx_, by_, b;
     block_coords(p, bx_, by_, b);  // (gy = 1)
     const int tiles_x = p.W / OC;
     const int y0 = (bx_ / tiles_x) * OR_, x0 = (bx_ % tiles_x) * OC;
+    // Every row of this block lies at or beyond mask_T: mask_pixel is skipped for all of them below, nothing is written.  (The
+    // head only: another conv's padded rows feed valid rows further down.)
+    if (y0 >= p.mask_T) return;
     const int HW = p.H * p.W;
     const float* in_b = p.in + (size_t)b * p.in_bs;
     const float* sc = nullptr;
     const float* sh = nullptr;
     if (tid < kHeadFoldRows) lds_b[tid] = p.bias[tid];
 
-    f32x4 acc[NXI];
+    f32x4 acc[NXW];  // [xi - 9 wave][logit]: k-step lane >> 5, tile lane & 31
 #pragma unroll
-    for (int xi = 0; xi < NXI; ++xi)
+    for (int g = 0; g < NXW; ++g)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) acc[xi][r] = 0.f;
+        for (int r = 0; r < 4; ++r) acc[g][r] = 0.f;
 
     const int kq = lane >> 4, l15 = lane & 15;
-    // fragments of this wave's k-step: A = {xi, xi + 1}[row l15][channel kq] in one 8-byte read; B = V[xi][kq][tile ^ swz][wk]
-    const float* afrag = lu + (wk * 64 + kq * 16 + l15) * 2;
-    const float* bfrag = lv + (kq * 32 + ((wwt * 16 + l15) ^ ((kq & 1) << 4))) * 2 + wk;
+    const int l31 = lane & 31, lks = lane >> 5;
+    // fragments: A = U[k-step lks][row lane & 3][xi 9 wave + g][channel 0 .. 3] in one 16-byte read per xi;
+    // B = V[xi][channel c][tile l31 ^ swz(c)][lks], the two swizzles of even and odd c as two bases
+    const float* afrag = lu + ((lks * kHeadFoldRows4 + (lane & 3)) * NXI + wave * NXW) * 4;
+    const float* bfrag0 = lv + wave * NXW * 256 + l31 * 2 + lks;
+    const float* bfrag1 = lv + wave * NXW * 256 + (l31 ^ 16) * 2 + lks;
     const unsigned lu_addr = (unsigned)(size_t)(__attribute__((address_space(3))) float*)lu;
     const unsigned ulane = (unsigned)lane * 16u;
     const v4i32 uw = make_rsrc_words(p.w_wino4, (unsigned)(p.Cin / KC) * (unsigned)(UH_F * 4));
@@ -52,18 +72,14 @@
         for (int i = 0; i < 6; ++i) {
             asm volatile("" : "+v"(pc[i].x), "+v"(pc[i].y), "+v"(pc[i].z), "+v"(pc[i].w), "+v"(pl[i]), "+v"(pr[i]));
         }
-        // weight image of chunk ch: 18 pieces of 1 KiB, 4 per wave and the last two to waves 0 and 1
-        static_assert(UH_F == 18 * 256, "18 pieces");
+        // weight image of chunk ch: 5 pieces of 1 KiB, one per wave and the last one to wave 0
+        static_assert(UH_F == 5 * 256, "5 pieces");
         const unsigned slab = (unsigned)ch * (unsigned)(UH_F * 4);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const unsigned piece = (unsigned)(wave * 4 + i) * 1024u;
+        {
+            const unsigned piece = (unsigned)wave * 1024u;
             lds_dma_16B(uw, ulane, slab + piece, lu_addr + piece);
         }
-        if (wave < 2) {
-            const unsigned piece = (unsigned)(16 + wave) * 1024u;
-            lds_dma_16B(uw, ulane, slab + piece, lu_addr + piece);
-        }
+        if (wave == 0) lds_dma_16B(uw, ulane, slab + 4096u, lu_addr + 4096u);
         __builtin_amdgcn_sched_barrier(0);
         pprocess();
         __builtin_amdgcn_sched_barrier(0);
@@ -76,24 +92,23 @@
             wait_vmcnt<0>();
         lds_barrier();  // V visible, every wave's U pieces landed
         __builtin_amdgcn_s_setprio(0);
-        // 36 GEMM steps of ONE k-step: every MFMA has an accumulator of its own
-        constexpr int PFD = 3;  // pairs of fragment reads ahead
-        f32x2v av[PFD + 1];
-        float bv[PFD + 1][2];
-        auto rd = [&](int s) {  // step s = xi pair (2s, 2s+1)
-            av[s % (PFD + 1)] = *reinterpret_cast<const f32x2v*>(afrag + s * 256);
+        // A stays in registers for the chunk; the B values of channel c + 1 are requested in front of the MFMAs of channel c
+        f32x4 av[NXW];
+        float bv[2][NXW];
+        auto rdb = [&](int c) {
+            const float* bp = ((c & 1) ? bfrag1 : bfrag0) + c * 64;
 #pragma unroll
-            for (int q = 0; q < 2; ++q) bv[s % (PFD + 1)][q] = bfrag[(2 * s + q) * 256];
+            for (int g = 0; g < NXW; ++g) bv[c & 1][g] = bp[g * 256];
         };
 #pragma unroll
-        for (int s = 0; s < PFD; ++s) rd(s);
+        for (int g = 0; g < NXW; ++g) av[g] = *reinterpret_cast<const f32x4*>(afrag + g * 4);
+        rdb(0);
 #pragma unroll
-        for (int s = 0; s < NXI / 2; ++s) {
-            if (s + PFD < NXI / 2) rd(s + PFD);
+        for (int c = 0; c < 4; ++c) {
+            if (c + 1 < 4) rdb(c + 1);
             __builtin_amdgcn_sched_barrier(0);
-            const f32x2v a = av[s % (PFD + 1)];
-            acc[2 * s] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, bv[s % (PFD + 1)][0], acc[2 * s], 0, 0, 0);
-            acc[2 * s + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, bv[s % (PFD + 1)][1], acc[2 * s + 1], 0, 0, 0);
+#pragma unroll
+            for (int g = 0; g < NXW; ++g) acc[g] = __builtin_amdgcn_mfma_f32_4x4x1f32(av[g][c], bv[c & 1][g], acc[g], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
         }
     }
@@ -110,35 +125,64 @@
             lup[q] = *reinterpret_cast<const float2*>(hs.up + po + (size_t)q * HW);
         }
     }
-    // ---- output transform Y = A^T M A of D rows kq * 4 + r, r < 3: the logits are rows 0 .. 2 (the kq = 0 lanes); the other
-    // rows of the tile are the zero padding of the images -----------------------------------------------------------------
+    // ---- the accumulators change hands ONCE per workgroup: a lane holds 9 of the 36 xi of (k-step, tile) for all logits, the output
+    // transform wants all 36 of one (k-step, logit, tile).  Lane (kq, l15) of wave (wk, wwt) then transforms logit kq of tile
+    // wwt * 16 + l15 for k-step wk (the kq = 3 lanes run along on logit 2 and store nothing) --------------------------------------
+    float* xh = lds;
+    float* part = lds + X_F;
+    lds_barrier();  // every wave is past its last MFMA phase: U / V are dead
+#pragma unroll
+    for (int g = 0; g < NXW; ++g)
+#pragma unroll
+        for (int r = 0; r < NQ; ++r) xh[lks * XK_F + r * XQ_F + (wave * NXW + g) * 32 + l31] = acc[g][r];
+    lds_barrier();
     const int ot = wwt * 16 + l15;  // this lane's tile
     const int oy = y0 + 4 * (ot / TC), ox = x0 + 4 * (ot % TC);
-    f32x4 ysp[16];  // [sub-pixel a * 4 + c][r]
+    {
+        const float* xs = xh + wk * XK_F + min(kq, NQ - 1) * XQ_F + ot;
+        float mm[NXI];
 #pragma unroll
-    for (int s = 0; s < 16; ++s) ysp[s][3] = 0.f;
-#pragma unroll
-    for (int r = 0; r < NQ; ++r) {
+        for (int xi = 0; xi < NXI; ++xi) mm[xi] = xs[xi * 32];
+        // output transform Y = A^T M A
         float tmp[4][6];
 #pragma unroll
         for (int jx = 0; jx < 6; ++jx) {
-            const float m[6] = {acc[0 + jx][r], acc[6 + jx][r], acc[12 + jx][r], acc[18 + jx][r], acc[24 + jx][r], acc[30 + jx][r]};
+            const float m[6] = {mm[0 + jx], mm[6 + jx], mm[12 + jx], mm[18 + jx], mm[24 + jx], mm[30 + jx]};
             float y[4];
             at6(m, y);
 #pragma unroll
             for (int a = 0; a < 4; ++a) tmp[a][jx] = y[a];
         }
+        // ---- the two waves of a tile group hold the logits of their half of the channels: left as [wk][logit][pixel = tile * 16 + s]
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
             float y[4];
             at6(tmp[a], y);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) ysp[a * 4 + c][r] = y[c];
+            if (kq < NQ) *reinterpret_cast<float4*>(part + (wk * NQ + kq) * 512 + ot * 16 + a * 4) = make_float4(y[0], y[1], y[2], y[3]);
         }
     }
     if constexpr (!PLANES) {
         // ---- the composed 1x1 shortcut over the raw block input, as wino4_body.h's: 16 MFMAs per 4 input channels, B straight
-        // from global memory.  This wave runs k-steps [wk, wk + 1) * nks / 2 and loads only those channels.
+        // from global memory, on top of the transformed logits in the 16x16x4 D layout (rows 0 .. 2 = the kq = 0 lanes' registers
+        // 0 .. 2 at column l15; the other rows are the zero padding of Wsc').  This wave runs k-steps [wk, wk + 1) * nks / 2 and
+        // loads only those channels.
+        lds_barrier();
+        f32x4 ysp[16];  // [sub-pixel a * 4 + c][r]
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            float4 yq[NQ];
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) yq[q] = *reinterpret_cast<const float4*>(part + (wk * NQ + q) * 512 + ot * 16 + a * 4);
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                ysp[a * 4 + 0][q] = kq == 0 ? yq[q].x : 0.f;
+                ysp[a * 4 + 1][q] = kq == 0 ? yq[q].y : 0.f;
+                ysp[a * 4 + 2][q] = kq == 0 ? yq[q].z : 0.f;
+                ysp[a * 4 + 3][q] = kq == 0 ? yq[q].w : 0.f;
+            }
+#pragma unroll
+            for (int c = 0; c < 4; ++c) ysp[a * 4 + c][3] = 0.f;
+        }
         const float* x2 = p.in2 + (size_t)b * p.in2_bs + (size_t)min(oy, p.H - 4) * p.W + ox;
         const float* wsc = p.w2 + l15;  // [Cin2][16]
         const int nks = p.Cin2 / 8, k0 = wk * nks;  // Cin2 % 32 == 0 (host-checked): whole groups of NSB k-steps per wave
@@ -172,19 +216,17 @@
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-    }
-    // ---- the two waves of a tile group hold the logits of their half of the channels, 3 x 16 pixels per kq = 0 lane: left in the
-    // dead U / V region as [wk][logit][pixel = tile * 16 + s] (2 x 3 x 512 floats), then every thread finishes 2 pixels ----------
-    float* part = lds;
-    lds_barrier();  // every wave is past its last MFMA phase
-    if (kq == 0) {
+        // (the kq = 0 lanes wrote and read these very addresses themselves: no barrier between the read above and this)
+        if (kq == 0) {
 #pragma unroll
-        for (int q = 0; q < NQ; ++q)
+            for (int q = 0; q < NQ; ++q)
 #pragma unroll
-            for (int a = 0; a < 4; ++a)
-                *reinterpret_cast<float4*>(part + (wk * NQ + q) * 512 + ot * 16 + a * 4) =
-                    make_float4(ysp[a * 4 + 0][q], ysp[a * 4 + 1][q], ysp[a * 4 + 2][q], ysp[a * 4 + 3][q]);
+                for (int a = 0; a < 4; ++a)
+                    *reinterpret_cast<float4*>(part + (wk * NQ + q) * 512 + ot * 16 + a * 4) =
+                        make_float4(ysp[a * 4 + 0][q], ysp[a * 4 + 1][q], ysp[a * 4 + 2][q], ysp[a * 4 + 3][q]);
+        }
     }
+    // ---- then every thread finishes 2 pixels ------------------------------------------------------------------------------------
     lds_barrier();
     const int px = tid * 2;  // pixels px, px + 1: same tile, same row
     const int mt = px >> 4, ms = px & 15;

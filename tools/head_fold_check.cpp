@@ -1,6 +1,7 @@
 // head_fold_check.cpp - the composition of lass_amd/csrc/head_fold.h on the CPU: decoder_block6's conv2 + 1x1 shortcut composed
 // with after_conv must give after_conv(conv2(h) + shortcut(cat)) on random small weights, in double, and the padded images
-// must be zero outside the 3 logit rows.  Host only:
+// must be zero outside the 3 logit rows; the compact 4-row image the kernels copy in must hold the 16-row image's rows 0 .. 3, value
+// for value.  Host only:
 //   g++ -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -I lass_amd/csrc tools/head_fold_check.cpp -o tools/bin/head_fold_check
 // Prints one line per check and "ok"; exit status 1 on the first failure.
 #include <cmath>
@@ -159,6 +160,33 @@ int check(int N, int C, int K, int Q) {
             if (f.u[head_fold_u_index(c, 0, q)] != (float)((double)g[0] / 16.0) || f.u[head_fold_u_index(c, 35, q)] != g[8])
                 return fail("the U image is not G g G^T of W2'");
         }
+    // ---- the compact image the kernels copy in: rows 0 .. 3 of the U image, the SAME f32 values (not a second rounding), every
+    // live element addressed exactly once, row 3 (and every row >= Q) zero, the tail of each chunk up to whole DMA pieces zero;
+    // with more than 3 logits there is no zero row and no compact image ---------------------------------------------------------
+    if (Q >= kHeadFoldRows4) {
+        if (!f.u4.empty()) return fail("a compact image without a zero row");
+        printf("N=%d C=%d K=%d Q=%d: no compact image\n", N, C, K, Q);
+        return 0;
+    }
+    if (f.u4.size() != (size_t)(C / kWino4KC) * kHeadFoldU4Floats) return fail("compact image size");
+    std::vector<int> hit4(f.u4.size(), 0);
+    size_t same = 0;
+    for (int c = 0; c < C; ++c)
+        for (int xi = 0; xi < kWino4NXI; ++xi)
+            for (int r = 0; r < kHeadFoldRows4; ++r) {
+                const size_t i = head_fold_u4_index(c, xi, r), chunk = (size_t)(c / kWino4KC) * kHeadFoldU4Floats;
+                if (i < chunk || i >= chunk + kHeadFoldU4Live) return fail("head_fold_u4_index leaves its chunk's live part");
+                ++hit4[i];
+                if (f.u4[i] != f.u[head_fold_u_index(c, xi, r)]) return fail("the compact image differs from the U image");
+                if (r >= Q && f.u4[i] != 0.f) return fail("the compact image has a non-zero padding row");
+                ++same;
+            }
+    for (size_t i = 0; i < f.u4.size(); ++i) {
+        const bool live = i % kHeadFoldU4Floats < (size_t)kHeadFoldU4Live;
+        if (hit4[i] != (live ? 1 : 0)) return fail("head_fold_u4_index is not a bijection onto the live part");
+        if (!live && f.u4[i] != 0.f) return fail("the compact image's tail is not zero");
+    }
+    printf("N=%d C=%d K=%d Q=%d: compact image: %zu values equal to the U image's rows 0..3, row 3 zero\n", N, C, K, Q, same);
     return 0;
 }
 
