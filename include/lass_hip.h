@@ -426,6 +426,35 @@ int lass_mix_at_snr(lass_ctx* ctx, float* source, const float* noise, const floa
 int lass_decode_resample(lass_ctx* ctx, const void* raw, int64_t row_stride_bytes, int B, int frames, int channels, int encoding,
                          int up, int down, const float* taps, int n_taps, float* out, int L_out, void* stream);
 
+/* The same load without the down-mix: out (B, channels, L_out) float32, dense, one plane per channel.  Arguments and limits are
+ * lass_decode_resample's.  Plane c of row b is bit-identical to what lass_decode_resample writes for a mono payload holding
+ * channel c of that row alone (the same decode rule, tap order and fmaf chain), whatever B, the row stride or the call.  For
+ * callers that separate every channel of a recording on its own and keep the channel layout. */
+int lass_decode_resample_planar(lass_ctx* ctx, const void* raw, int64_t row_stride_bytes, int B, int frames, int channels,
+                                int encoding, int up, int down, const float* taps, int n_taps, float* out, int L_out, void* stream);
+
+/* Export path, the mirror of lass_decode_resample: B recordings as planar float32 at the model rate -> B WAV data chunks at the
+ * file's rate, in one launch.  planes: plane c of recording b = L_in floats at planes + b*row_stride + c*plane_stride (strides
+ * in floats; channels 1 ... 8).  For every plane
+ *   y[n] = sum_m x[m] * taps[n*down - m*up + (n_taps-1)/2],   x = 0 outside the plane,   n < frames_out <= ceil(L_in*up/down)
+ * which is lass_decode_resample's formula for a mono LASS_WAV_F32 payload in the same accumulation order: y is bit-identical to
+ * what that entry point writes for the plane, whatever B, the strides or the call.  frames_out below the ceiling truncates (a
+ * file decoded from F frames comes back at F frames: ceil(ceil(F*u/d)*d/u) >= F).  up == down == 1: no filter (taps may be
+ * NULL, n_taps 1).  Then row b = frames_out frames of `channels` interleaved samples at out_bytes + b*out_row_stride_bytes,
+ * little-endian, as a WAV data chunk holds them:
+ *   LASS_WAV_PCM16  clip(rintf(y * 32768), -32768, 32767), ties to even   (wavio.write_wav_pcm16, for every finite float32)
+ *   LASS_WAV_PCM32  rintf(y * 2^31) clipped to [-2^31, 2^31 - 1]          (wavio.write_wav_pcm32)
+ *   LASS_WAV_F32    y as is                                               (wavio.write_wav_f32)
+ * A NaN encodes as PCM 0.  clipped (optional, device, B unsigned counters zero-filled by the caller): counter b grows by the
+ * number of PCM samples of row b that the clip changed (integer atomics: order-independent); LASS_WAV_F32 adds nothing.
+ * Limits, checked before anything is launched (LASS_ERR_ARG): those of lass_decode_resample on encoding, channels, up, down,
+ * taps, n_taps, the polyphase table and B; L_in >= 1; 1 <= frames_out <= the ceiling above; plane_stride >= L_in and
+ * row_stride >= (channels-1)*plane_stride + L_in; out_bytes 4-byte aligned, out_row_stride_bytes a multiple of 4 and
+ * >= frames_out * channels * bytes per sample.  Stateless; bytes of a row past its frames_out frames are left alone. */
+int lass_resample_encode(lass_ctx* ctx, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels, int L_in,
+                         int up, int down, const float* taps, int n_taps, int encoding, void* out_bytes,
+                         int64_t out_row_stride_bytes, int frames_out, unsigned* clipped, void* stream);
+
 /* Training-side data path ("next" row f4, mixer half; also the producer stage of the STFT pre-compute,
  * scripts/precompute_stfts.py:352-681): SegmentMixer.__call__ + dynamic_loudnorm (data/waveform_mixers.py:19-92) on the
  * device.  waveforms (B,L) -> mixture (B,L), segment (B,L).  For clip n:

@@ -1482,6 +1482,75 @@ int lass_decode_resample(lass_ctx* c, const void* raw, int64_t row_stride_bytes,
     return 0;
 }
 
+// What lass_decode_resample asks of encoding, channels, up, down and the filter, for the entry points that share its limits
+// (w: the caller's "name: ").  0, or LASS_ERR_ARG with the message set.
+static int check_resample_args(lass_ctx* c, const char* w, int channels, int encoding, int up, int down, const float* taps,
+                               int n_taps) {
+    if (encoding != LASS_WAV_PCM16 && encoding != LASS_WAV_PCM32 && encoding != LASS_WAV_F32)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "encoding must be LASS_WAV_PCM16, LASS_WAV_PCM32 or LASS_WAV_F32");
+    if (channels < 1 || channels > 8) return fail(c, LASS_ERR_ARG, std::string(w) + "1 ... 8 channels");
+    if (up < 1 || down < 1 || up > LASS_RESAMPLE_MAX_RATIO || down > LASS_RESAMPLE_MAX_RATIO)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "up and down must lie in 1 ... " + std::to_string(LASS_RESAMPLE_MAX_RATIO));
+    if (up != 1 || down != 1) {
+        if (!taps || n_taps < 1 || n_taps % 2 == 0) return fail(c, LASS_ERR_ARG, std::string(w) + "taps non-NULL, n_taps odd");
+        if (n_taps > LASS_RESAMPLE_MAX_TAPS)
+            return fail(c, LASS_ERR_ARG, std::string(w) + std::to_string(n_taps) + " taps exceed the cap of " +
+                        std::to_string(LASS_RESAMPLE_MAX_TAPS) + " (resample on the host)");
+        if (lass_resample_table_floats(up, n_taps) > LASS_RESAMPLE_MAX_TABLE)
+            return fail(c, LASS_ERR_ARG, std::string(w) + "the polyphase table up * (ceil(n_taps/up) | 1) exceeds " +
+                        std::to_string(LASS_RESAMPLE_MAX_TABLE) + " floats");
+    }
+    return 0;
+}
+
+int lass_decode_resample_planar(lass_ctx* c, const void* raw, int64_t row_stride_bytes, int B, int frames, int channels,
+                                int encoding, int up, int down, const float* taps, int n_taps, float* out, int L_out, void* stream) {
+    const char* w = "lass_decode_resample_planar: ";
+    if (!c) return LASS_ERR_ARG;
+    if (!raw || !out || B <= 0 || B > 65535 || frames <= 0) return fail(c, LASS_ERR_ARG, std::string(w) + "raw, out non-NULL, 1 <= B <= 65535, frames >= 1");
+    if (int r = check_resample_args(c, w, channels, encoding, up, down, taps, n_taps)) return r;
+    const long long want = ((long long)frames * up + down - 1) / down;
+    if (L_out <= 0 || want != (long long)L_out)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "L_out must be ceil(frames*up/down) = " + std::to_string(want));
+    const long long row_bytes = (long long)frames * channels * (encoding == LASS_WAV_PCM16 ? 2 : 4);
+    if (row_stride_bytes < row_bytes || row_stride_bytes % 4 != 0)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "row_stride_bytes must be a multiple of 4 and hold a row (" +
+                    std::to_string(row_bytes) + " bytes)");
+    if (reinterpret_cast<uintptr_t>(raw) % 4 != 0) return fail(c, LASS_ERR_ARG, std::string(w) + "raw must be 4-byte aligned");
+    if (int r = use_device(c)) return r;
+    HIP_TRY(c, lass_launch_decode_resample_planar(raw, row_stride_bytes, B, frames, channels, encoding, up, down, taps, n_taps, out,
+                                                  L_out, (hipStream_t)stream));
+    return 0;
+}
+
+int lass_resample_encode(lass_ctx* c, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels, int L_in,
+                         int up, int down, const float* taps, int n_taps, int encoding, void* out_bytes,
+                         int64_t out_row_stride_bytes, int frames_out, unsigned* clipped, void* stream) {
+    const char* w = "lass_resample_encode: ";
+    if (!c) return LASS_ERR_ARG;
+    if (!planes || !out_bytes || B <= 0 || B > 65535 || L_in <= 0)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "planes, out_bytes non-NULL, 1 <= B <= 65535, L_in >= 1");
+    if (int r = check_resample_args(c, w, channels, encoding, up, down, taps, n_taps)) return r;
+    const long long ceiling = ((long long)L_in * up + down - 1) / down;
+    if (frames_out < 1 || (long long)frames_out > ceiling)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "frames_out must lie in 1 ... ceil(L_in*up/down) = " + std::to_string(ceiling));
+    const long long row_floats = (long long)(channels - 1) * plane_stride + L_in;
+    if (plane_stride < L_in || row_stride < row_floats)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "plane_stride must hold a plane (" + std::to_string(L_in) +
+                    " floats) and row_stride a recording (" + std::to_string(row_floats) + " floats)");
+    const long long row_bytes = (long long)frames_out * channels * (encoding == LASS_WAV_PCM16 ? 2 : 4);
+    if (out_row_stride_bytes < row_bytes || out_row_stride_bytes % 4 != 0)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "out_row_stride_bytes must be a multiple of 4 and hold a row (" +
+                    std::to_string(row_bytes) + " bytes)");
+    if (reinterpret_cast<uintptr_t>(out_bytes) % 4 != 0) return fail(c, LASS_ERR_ARG, std::string(w) + "out_bytes must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(planes) % 4 != 0 || reinterpret_cast<uintptr_t>(clipped) % 4 != 0)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "planes and clipped must be 4-byte aligned");
+    if (int r = use_device(c)) return r;
+    HIP_TRY(c, lass_launch_resample_encode(planes, row_stride, plane_stride, B, channels, L_in, up, down, taps, n_taps, encoding,
+                                           out_bytes, out_row_stride_bytes, frames_out, clipped, (hipStream_t)stream));
+    return 0;
+}
+
 int lass_segment_mix(lass_ctx* c, const float* waveforms, int B, int L, const int* mix_num, const float* comp_db, int max_comp,
                      const float* noise_db, float* mixture, float* segment, double* scratch, void* stream) {
     if (!c || !waveforms || !mix_num || !comp_db || !noise_db || !mixture || !segment || !scratch || B <= 0 || L <= 0)

@@ -283,3 +283,16 @@ hipError_t lass_launch_bnfold(const float* g, const float* beta, const float* me
 size_t lass_resample_table_floats(int up, int n_taps);  // the polyphase table in LDS: up * (ceil(n_taps/up) | 1)
 hipError_t lass_launch_decode_resample(const void* raw, long long row_stride, int B, int frames, int ch, int enc, int up, int down,
                                        const float* taps, int n_taps, float* out, int L_out, hipStream_t stream);
+// the same arguments -> out (B, ch, L_out): one plane per channel, each bit-identical to the mono call on that channel alone
+hipError_t lass_launch_decode_resample_planar(const void* raw, long long row_stride, int B, int frames, int ch, int enc, int up,
+                                              int down, const float* taps, int n_taps, float* out, int L_out, hipStream_t stream);
+size_t lass_resample_span_floats(int up, int down, int n_taps, int tile);  // the input frames `tile` outputs reach, in LDS
+
+// ---- export.hip ---------------------------------------------------------------------------------------------------
+// planes (B recordings x ch planes of L_in floats; strides in floats) -> out (B rows of frames_out interleaved frames, enc =
+// LASS_WAV_*, out_row_stride bytes apart): the FIR above per plane, truncated to frames_out, quantised as wavio's writers do.
+// clipped (B counters, may be NULL): += the PCM samples of the row that the clip changed.  The caller has checked the arguments
+// (lass_resample_encode).
+hipError_t lass_launch_resample_encode(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L_in,
+                                       int up, int down, const float* taps, int n_taps, int enc, void* out, long long out_row_stride,
+                                       int frames_out, unsigned* clipped, hipStream_t stream);

@@ -12,6 +12,9 @@
 //   span[s]   = the decoded, down-mixed frame (first frame of the tile's reach) + s, zero outside the clip.
 // Every output is one f32 fmaf chain over j = 0 ... J-1 in that order, whatever the batch, the row stride or the tile it falls in:
 // results are bit-identical per clip.  No atomics.
+//
+// k_decode_planar / k_decode_resample_planar are the same two kernels without the down-mix: one output plane per channel, for
+// callers that separate every channel on its own (export.hip is the way back out).
 #include "../../include/lass_hip.h"
 #include "kernels.h"
 
@@ -87,11 +90,102 @@ __global__ __launch_bounds__(kThreads) void k_decode_resample(const unsigned cha
     }
 }
 
+// The planar siblings: one plane per channel instead of their average, out (B, ch, L_out).  Plane c is what the kernels above
+// make of a mono payload holding channel c alone - frame_at with one channel IS sample_at, and the tap order and the fmaf chain
+// are theirs - so it is bit-identical to them.
+__global__ __launch_bounds__(kThreads) void k_decode_planar(const unsigned char* __restrict__ raw, long long row_stride, int frames,
+                                                            int ch, int enc, float* __restrict__ out) {
+    const int n = blockIdx.x * kThreads + threadIdx.x;
+    if (n >= frames) return;
+    const unsigned char* row = raw + (size_t)blockIdx.y * row_stride;
+    float* o = out + (size_t)blockIdx.y * ch * frames + n;
+    for (int c = 0; c < ch; ++c) o[(size_t)c * frames] = sample_at(row, (long long)n * ch + c, enc);
+}
+
+// The table is staged once per workgroup, the span once per channel (the same LDS plan as k_decode_resample: one span).
+__global__ __launch_bounds__(kThreads) void k_decode_resample_planar(const unsigned char* __restrict__ raw, long long row_stride,
+                                                                     int frames, int ch, int enc, int up, int down,
+                                                                     const float* __restrict__ taps, int n_taps, int J, int tile,
+                                                                     float* __restrict__ out, int L_out) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int Jp = J | 1;
+    float* tab = lds;                        // [up][Jp]
+    float* span = lds + (size_t)up * Jp;     // [(up - 1 + (tile - 1) * down) / up + J]
+    const int tid = threadIdx.x;
+    const unsigned char* row = raw + (size_t)blockIdx.y * row_stride;
+
+    const long long n0 = (long long)blockIdx.x * tile;
+    const long long t0 = n0 * down + (n_taps - 1) / 2;
+    const long long q0 = t0 / up;
+    const unsigned r0 = (unsigned)(t0 - q0 * up);
+    const int nout = (int)(L_out - n0 < tile ? L_out - n0 : tile);
+    const int S = (int)((r0 + (unsigned)(nout - 1) * (unsigned)down) / (unsigned)up) + J;
+    const long long mlo = q0 - (J - 1);
+
+    for (int p = tid; p < up; p += kThreads) tab[p * Jp + J - 1] = 0.f;
+    __syncthreads();
+    for (int k = tid; k < n_taps; k += kThreads) tab[(k % up) * Jp + k / up] = taps[k];
+
+    for (int c = 0; c < ch; ++c) {
+        if (c) __syncthreads();              // the previous channel's reads of the span
+        for (int s = tid; s < S; s += kThreads) {
+            const long long m = mlo + s;
+            span[s] = (m >= 0 && m < frames) ? sample_at(row, m * ch + c, enc) : 0.f;
+        }
+        __syncthreads();
+        float* o = out + ((size_t)blockIdx.y * ch + c) * L_out + n0;
+        for (int i = tid; i < nout; i += kThreads) {
+            const unsigned t = r0 + (unsigned)i * (unsigned)down;
+            const unsigned q = t / (unsigned)up;
+            const float* g = tab + (t - q * (unsigned)up) * Jp;
+            const float* x = span + q + (J - 1);
+            float acc = 0.f;
+            for (int j = 0; j < J; ++j) acc = fmaf(x[-j], g[j], acc);
+            o[i] = acc;
+        }
+    }
+}
+
 }  // namespace
 
 size_t lass_resample_table_floats(int up, int n_taps) {
     const int J = (n_taps + up - 1) / up;
     return (size_t)up * (size_t)(J | 1);
+}
+
+size_t lass_resample_span_floats(int up, int down, int n_taps, int tile) {
+    const int J = (n_taps + up - 1) / up;
+    return ((size_t)(up - 1) + (size_t)(tile - 1) * down) / up + J;
+}
+
+hipError_t lass_launch_decode_resample_planar(const void* raw, long long row_stride, int B, int frames, int ch, int enc, int up,
+                                              int down, const float* taps, int n_taps, float* out, int L_out, hipStream_t stream) {
+    if (B <= 0 || B > 65535 || frames <= 0 || L_out <= 0 || up < 1 || down < 1 || ch < 1) return hipErrorInvalidValue;
+    const unsigned char* r = static_cast<const unsigned char*>(raw);
+    if (up == 1 && down == 1) {
+        hipLaunchKernelGGL(k_decode_planar, dim3((frames + kThreads - 1) / kThreads, B), dim3(kThreads), 0, stream, r, row_stride,
+                           frames, ch, enc, out);
+        return hipGetLastError();
+    }
+    const int J = (n_taps + up - 1) / up;
+    const size_t table = lass_resample_table_floats(up, n_taps);
+    if (up > LASS_RESAMPLE_MAX_RATIO || down > LASS_RESAMPLE_MAX_RATIO || n_taps > LASS_RESAMPLE_MAX_TAPS || table > LASS_RESAMPLE_MAX_TABLE)
+        return hipErrorInvalidValue;
+    // k_decode_resample's plan: the largest tile whose input span fits beside the table
+    int tile = kTileMax;
+    while (tile > 1 && table + lass_resample_span_floats(up, down, n_taps, tile) > (size_t)kLdsFloats) tile /= 2;
+    const size_t lds = (table + lass_resample_span_floats(up, down, n_taps, tile)) * sizeof(float);
+    if (lds > (size_t)kLdsFloats * sizeof(float)) return hipErrorInvalidValue;
+    if (lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_decode_resample_planar),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLdsFloats * (int)sizeof(float));
+        if (e != hipSuccess) return e;
+    }
+    const long long nblk = ((long long)L_out + tile - 1) / tile;
+    if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_decode_resample_planar, dim3((unsigned)nblk, B), dim3(kThreads), lds, stream, r, row_stride, frames, ch, enc,
+                       up, down, taps, n_taps, J, tile, out, L_out);
+    return hipGetLastError();
 }
 
 hipError_t lass_launch_decode_resample(const void* raw, long long row_stride, int B, int frames, int ch, int enc, int up, int down,

@@ -620,6 +620,15 @@ class Engine:
         "f32", rows a multiple of 4 bytes apart - -> (B, ceil(frames * up / down)) float32 mono at rate_out (`out`: written
         in place).  The filter is lass_amd.resample.design_taps; a ratio beyond the kernel's tap cap raises LassError
         (resample.within_cap tells beforehand)."""
+        return self._decode_resample(raw_u8, frames, channels, encoding, rate_in, rate_out, out, False)
+
+    def decode_resample_planar(self, raw_u8: torch.Tensor, frames: int, channels: int, encoding: str, rate_in: int, rate_out: int,
+                               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`decode_resample` without the down-mix: -> (B, channels, ceil(frames * up / down)) float32, plane c of row b bit-identical
+        to `decode_resample` of a mono payload holding that channel alone (lass_decode_resample_planar)."""
+        return self._decode_resample(raw_u8, frames, channels, encoding, rate_in, rate_out, out, True)
+
+    def _decode_resample(self, raw_u8, frames, channels, encoding, rate_in, rate_out, out, planar: bool) -> torch.Tensor:
         from . import resample as rs
         if raw_u8.dim() == 1:
             raw_u8 = raw_u8[None]
@@ -637,15 +646,17 @@ class Engine:
             raise _lib.LassError(f"resampling {rate_in} -> {rate_out} Hz needs {rs.n_taps(up, down)} taps, over the device "
                                  f"kernel's cap of {rs.MAX_TAPS}: resample on the host (wavio.read_wav)")
         taps = rs.device_taps(up, down, self.device) if fir else None
+        shape = (B, int(channels), L_out) if planar else (B, L_out)
         if out is None:
-            out = torch.empty(B, L_out, dtype=torch.float32, device=self.device)
-        elif (tuple(out.shape) != (B, L_out) or out.dtype != torch.float32 or out.device != self.device
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        elif (tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != self.device
               or not out.is_contiguous()):
-            raise _lib.LassError(f"out must be a contiguous float32 {(B, L_out)} tensor on {self.device}")
+            raise _lib.LassError(f"out must be a contiguous float32 {shape} tensor on {self.device}")
         stride = raw_u8.stride(0) if B > 1 else (raw_u8.shape[1] + 3) // 4 * 4  # (one row: no stride to honour)
-        rc = self.lib.lass_decode_resample(self.ctx, _ptr(raw_u8), stride, B, int(frames), int(channels), rs.ENCODINGS[encoding], up, down, _ptr(taps),
-                                           taps.numel() if fir else 1, _ptr(out), L_out, _stream(self.device))
-        _lib.check(self.ctx, rc, "lass_decode_resample")
+        name = "lass_decode_resample_planar" if planar else "lass_decode_resample"
+        rc = getattr(self.lib, name)(self.ctx, _ptr(raw_u8), stride, B, int(frames), int(channels), rs.ENCODINGS[encoding], up, down,
+                                     _ptr(taps), taps.numel() if fir else 1, _ptr(out), L_out, _stream(self.device))
+        _lib.check(self.ctx, rc, name)
         return out
 
     def resample(self, x: torch.Tensor, rate_in: int, rate_out: int) -> torch.Tensor:
@@ -655,6 +666,51 @@ class Engine:
         x = x[None] if one else x
         y = self.decode_resample(x.view(torch.uint8), x.shape[1], 1, "f32", rate_in, rate_out)
         return y[0] if one else y
+
+    def resample_encode(self, planes: torch.Tensor, rate_in: int, rate_out: int, encoding: str, frames_out: Optional[int] = None,
+                        out: Optional[torch.Tensor] = None, clipped: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The export side of `decode_resample_planar`, on the device: planes (B, C, L) or (C, L) float32 at rate_in (any strides
+        with contiguous samples; C 1 ... 8) -> (B, frames_out * C * sample bytes) uint8, each row a WAV data chunk at rate_out
+        ("pcm16" / "pcm32" / "f32", frames interleaved) as wavio.write_wav_* would write the resampled planes.  frames_out (default
+        and at most ceil(L * up / down)) truncates.  `out`: a (B, >= row bytes) uint8 tensor written in place, rows a multiple of 4
+        bytes apart, bytes past a row's end left alone; `clipped`: (B,) int32 counters, zero-filled by the caller, that receive
+        the number of PCM samples the clip changed.  The filter is lass_amd.resample.design_taps; a ratio beyond the kernel's tap
+        cap raises LassError (resample.within_cap tells beforehand)."""
+        from . import resample as rs
+        if planes.dim() == 2:
+            planes = planes[None]
+        if planes.device != self.device or planes.dtype != torch.float32 or planes.dim() != 3 or planes.stride(2) != 1:
+            raise _lib.LassError(f"planes must be a (B, C, L) or (C, L) float32 tensor on {self.device} with contiguous samples")
+        if encoding not in rs.ENCODINGS:
+            raise _lib.LassError(f"encoding must be one of {sorted(rs.ENCODINGS)}")
+        B, C, L = planes.shape
+        up, down = rs.ratio(rate_in, rate_out)
+        ceiling = rs.out_len(L, up, down)
+        frames_out = ceiling if frames_out is None else int(frames_out)
+        if not 1 <= frames_out <= ceiling:
+            raise _lib.LassError(f"frames_out must lie in 1 ... ceil(L * up / down) = {ceiling}")
+        fir = (up, down) != (1, 1)
+        if fir and not rs.within_cap(up, down):
+            raise _lib.LassError(f"resampling {rate_in} -> {rate_out} Hz needs {rs.n_taps(up, down)} taps, over the device "
+                                 f"kernel's cap of {rs.MAX_TAPS}: resample on the host (wavio.write_wav_*)")
+        taps = rs.device_taps(up, down, self.device) if fir else None
+        row_bytes = frames_out * C * rs.SAMPLE_BYTES[encoding]
+        if out is None:
+            out = torch.empty(B, (row_bytes + 3) // 4 * 4, dtype=torch.uint8, device=self.device)
+        elif (out.dim() != 2 or out.shape[0] != B or out.shape[1] < row_bytes or out.dtype != torch.uint8 or out.device != self.device
+              or out.stride(1) != 1):
+            raise _lib.LassError(f"out must be a ({B}, >= {row_bytes}) uint8 tensor on {self.device} with contiguous rows")
+        if clipped is not None and (tuple(clipped.shape) != (B,) or clipped.dtype != torch.int32 or clipped.device != self.device
+                                    or not clipped.is_contiguous()):
+            raise _lib.LassError(f"clipped must be a contiguous int32 ({B},) tensor on {self.device}")
+        plane_stride = planes.stride(1) if C > 1 else L                      # (one plane, one row: no stride to honour)
+        row_stride = planes.stride(0) if B > 1 else (C - 1) * plane_stride + L
+        out_stride = out.stride(0) if B > 1 else (row_bytes + 3) // 4 * 4
+        rc = self.lib.lass_resample_encode(self.ctx, _ptr(planes), row_stride, plane_stride, B, C, L, up, down, _ptr(taps),
+                                           taps.numel() if fir else 1, rs.ENCODINGS[encoding], _ptr(out), out_stride, frames_out,
+                                           _ptr(clipped), _stream(self.device))
+        _lib.check(self.ctx, rc, "lass_resample_encode")
+        return out[:, :row_bytes]
 
     def segment_mix(self, waveforms: torch.Tensor, mix_num: torch.Tensor, comp_db: torch.Tensor, noise_db: torch.Tensor):
         """data/waveform_mixers.py:19-62 on the device with the random draws given: waveforms (B,L), mix_num (B) int32,

@@ -1,0 +1,331 @@
+"""File in, file out: separate WAV files by caption and write WAV files, with everything between the two file accesses on the
+device.
+
+Neither `separate_files` nor `inference` exists in the reference in this form: upstream AudioSep's `pipeline.inference(model,
+audio_file, text, output_file)` loads one file with librosa at 32 kHz mono, runs one forward (or `chunk_inference`) and writes
+int16 with scipy.  What the two functions below do - channel by channel, at the file's own rate, encoding and frame count, many
+files per pass, hard or cross-faded seams - is THIS PACKAGE'S SPECIFICATION, pinned by tests/test_export_gpu.py against a
+composition of the package's public pieces, not by a reference fixture (as DESIGN.md sections 14 and 15 say of the long-form
+calls).
+
+One pass over a group of files:
+
+    WAV bytes -> pinned row -> H2D -> Engine.decode_resample_planar (or decode_resample for channels="mono")
+              -> every plane one recording of ResUNet30.separate_long_list, with its file's condition
+              -> Engine.resample_encode back to the file's rate, encoding and frame count -> D2H into a pinned row
+              -> wavio.wav_header + payload written
+
+Files are read on one thread and written on another while the device works.  Only the encoded payload leaves the device.  A
+file the device kernels do not take - a header `wavio.wav_info` does not fully understand, more than 8 channels, a rate pair
+beyond `resample.within_cap` in either direction - is decoded, resampled and written on the host (`wavio._resample`,
+`wavio.write_wav_*`); its separation still runs on the device, in the same pass, and its record says `path == "host"`.
+"""
+from __future__ import annotations
+
+import threading
+import time
+from concurrent.futures import ThreadPoolExecutor
+from contextlib import contextmanager
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import resample as rs
+from . import wavio
+
+MAX_CHANNELS = 8                     # include/lass_hip.h: lass_decode_resample, lass_resample_encode
+DEFAULT_MAX_SAMPLES = 1 << 26        # model-rate samples per pass, all planes counted: 256 MiB per float32 buffer of the pass
+_WRITERS = {"pcm16": wavio.write_wav_pcm16, "pcm32": wavio.write_wav_pcm32, "f32": wavio.write_wav_f32}
+
+
+# ---- planning (host only) ---------------------------------------------------------------------------------------------------
+def route(info, sampling_rate: int, out_rate: Optional[int] = None) -> str:
+    """"device" if the two device kernels take the file - `info` a `wavio.wav_info` tuple, at most 8 channels, and both rate
+    pairs (file -> model, model -> output) within the kernels' tap cap - else "host"."""
+    if info is None:
+        return "host"
+    _, nch, rate, _, _ = info
+    if nch > MAX_CHANNELS:
+        return "host"
+    out_rate = rate if out_rate is None else int(out_rate)
+    if not rs.within_cap(*rs.ratio(rate, sampling_rate)) or not rs.within_cap(*rs.ratio(sampling_rate, out_rate)):
+        return "host"
+    return "device"
+
+
+def model_samples(nch: int, rate: int, frames: int, sampling_rate: int, channels: str) -> Tuple[int, int]:
+    """(planes, model-rate samples per plane) a file puts into a pass: its channels or 1, ceil(frames * up / down)."""
+    return (nch if channels == "each" else 1), rs.out_len(frames, *rs.ratio(rate, sampling_rate))
+
+
+def plan_passes(samples: Sequence[int], max_samples: int) -> List[List[int]]:
+    """Consecutive jobs grouped into passes of at most `max_samples` model-rate samples; a job over the bound on its own is a
+    pass of its own.  Every job is in exactly one pass, in input order."""
+    max_samples = int(max_samples)
+    if max_samples < 1:
+        raise ValueError("max_samples must be at least 1")
+    passes, cur, held = [], [], 0
+    for i, n in enumerate(samples):
+        if cur and held + n > max_samples:
+            passes.append(cur)
+            cur, held = [], 0
+        cur.append(i)
+        held += int(n)
+    if cur:
+        passes.append(cur)
+    return passes
+
+
+def dedup_captions(queries) -> Tuple[List[str], List[Optional[int]]]:
+    """(the distinct captions in first-seen order, per query its index into them - None for a query that is an embedding)."""
+    captions, where, index = [], {}, []
+    for q in queries:
+        if isinstance(q, str):
+            if q not in where:
+                where[q] = len(captions)
+                captions.append(q)
+            index.append(where[q])
+        else:
+            index.append(None)
+    return captions, index
+
+
+def _host_info(path: str):
+    """(encoding or None, channels, rate, frames) of a file `wavio.wav_info` refuses, through `wavio.read_wav`'s own parser (which
+    raises ValueError for what it cannot read either); the channel layout is then unknown and the file counts as mono."""
+    x, rate = wavio.read_wav(path)
+    return None, 1, rate, int(x.shape[0])
+
+
+# ---- host route -------------------------------------------------------------------------------------------------------------
+def _host_decode(path: str, info, channels: str) -> np.ndarray:
+    """(planes, frames) float32 at the file's rate: `wavio.read_wav`'s decode rules, per channel ("each") or down-mixed."""
+    if info is None or channels == "mono":
+        return wavio.read_wav(path)[0][None]
+    enc, nch, _, frames, offset = info
+    with open(path, "rb") as f:
+        f.seek(offset)
+        raw = f.read(frames * nch * rs.SAMPLE_BYTES[enc])
+    if enc == "pcm16":
+        x = np.frombuffer(raw, dtype="<i2").astype(np.float32) / 32768.0
+    elif enc == "pcm32":
+        x = (np.frombuffer(raw, dtype="<i4").astype(np.float64) / 2147483648.0).astype(np.float32)
+    else:
+        x = np.frombuffer(raw, dtype="<f4").astype(np.float32)
+    return np.ascontiguousarray(x.reshape(frames, nch).T)
+
+
+def _host_resample(x: np.ndarray, rate_in: int, rate_out: int) -> np.ndarray:
+    return x if rate_in == rate_out else np.stack([wavio._resample(p, rate_in, rate_out) for p in x])
+
+
+def host_clip_count(x: np.ndarray, encoding: str) -> int:
+    """PCM samples of x that `wavio.write_wav_pcm16` / `write_wav_pcm32` clip (0 for "f32"; a NaN is not counted)."""
+    if encoding == "f32":
+        return 0
+    scale, lo, hi = (32768.0, -32768, 32767) if encoding == "pcm16" else (2147483648.0, -2147483648, 2147483647)
+    r = np.round(np.asarray(x, dtype=np.float64) * scale)
+    return int(np.count_nonzero((r < lo) | (r > hi)))
+
+
+# ---- the pass ---------------------------------------------------------------------------------------------------------------
+class _Clock:
+    """Seconds per stage into `profile` (synchronising the device at each stage's end); nothing at all without one."""
+
+    def __init__(self, profile: Optional[Dict[str, float]], device):
+        self.profile, self.device = profile, device
+
+    @contextmanager
+    def __call__(self, stage: str):
+        if self.profile is None:
+            yield
+            return
+        import torch
+        t0 = time.perf_counter()
+        yield
+        torch.cuda.synchronize(self.device)
+        self.profile[stage] = self.profile.get(stage, 0.0) + time.perf_counter() - t0
+
+
+class _Pinned:
+    """Pinned uint8 rows, reused across files and passes instead of page-locking a fresh one per file."""
+
+    def __init__(self):
+        self.free: List = []
+        self.lock = threading.Lock()     # the reader thread takes rows while the main thread takes and gives
+
+    def take(self, nbytes: int):
+        import torch
+        with self.lock:
+            fit = [b for b in self.free if b.numel() >= nbytes]
+            if fit:
+                buf = min(fit, key=lambda b: b.numel())
+                self.free = [b for b in self.free if b is not buf]   # (list.remove would compare tensors)
+                return buf
+        return torch.empty(max(4, (nbytes + 3) // 4 * 4), dtype=torch.uint8).pin_memory()
+
+    def give(self, buf) -> None:
+        with self.lock:
+            self.free.append(buf)
+
+
+def _read_job(path: str, info, how: str, channels: str, pool: _Pinned, profile):
+    """Reader thread: the raw payload in a pinned row (device route) or the decoded planes (host route)."""
+    t0 = time.perf_counter()
+    if how == "device":
+        nbytes = info[3] * info[1] * rs.SAMPLE_BYTES[info[0]]
+        buf = pool.take(nbytes)
+        if not wavio.read_wav_raw_into(path, info, buf.numpy()[:nbytes]):
+            raise OSError(f"{path}: the file changed or could not be read")
+        got = buf
+    else:
+        got = _host_decode(path, info, channels)
+    if profile is not None:
+        profile["read"] = profile.get("read", 0.0) + time.perf_counter() - t0
+    return got
+
+
+def _write_device(path: str, header: bytes, buf, nbytes: int, event, profile) -> None:
+    """Writer thread: the payload has arrived in the pinned row once `event` has passed."""
+    event.synchronize()
+    t0 = time.perf_counter()
+    with open(path, "wb") as f:
+        f.write(header)
+        f.write(memoryview(buf.numpy())[:nbytes])
+    if profile is not None:
+        profile["write"] = profile.get("write", 0.0) + time.perf_counter() - t0
+
+
+def _write_host(path: str, encoding: str, x: np.ndarray, rate: int, profile) -> None:
+    t0 = time.perf_counter()
+    _WRITERS[encoding](path, x.T if x.shape[0] > 1 else x[0], rate)
+    if profile is not None:
+        profile["write"] = profile.get("write", 0.0) + time.perf_counter() - t0
+
+
+def separate_files(model, jobs, sampling_rate: int, channels: str = "each", encoding: Optional[str] = None,
+                   out_rate: Optional[int] = None, window: int = 160000, context: int = 16000, fade: int = 0,
+                   fade_shape: str = "linear", max_batch: int = 16, max_samples: int = DEFAULT_MAX_SAMPLES,
+                   profile: Optional[Dict[str, float]] = None) -> List[dict]:
+    """Separate WAV files by caption, file in and file out.  model: an `AudioSep`-shaped holder (`.ss_model` a ResUNet30 on the
+    device working at `sampling_rate`, `.query_encoder` with `get_query_embed`); jobs: a sequence of (in_path, query, out_path),
+    query a caption or a (512,) embedding.  channels "each": every channel of a file is separated on its own with the file's
+    query and the output keeps the channel layout; "mono": the channels are averaged first (as `librosa.load(mono=True)` does) and
+    the output is mono.  encoding / out_rate None: the input file's own; the output then has the input's frame count, else
+    ceil(model-rate samples * up / down).  window, context, fade, fade_shape, max_batch: `ResUNet30.separate_long_list`'s.  Files
+    are taken in passes of at most `max_samples` model-rate samples (all planes counted), which bounds the memory; the captions
+    of a pass are embedded in one `get_query_embed` call, each distinct caption once.  profile: a dict that receives seconds per
+    stage (read, h2d, decode, separate, encode, d2h, write), with the device synchronised after each stage - for measurement.
+    Returns one record per job, in order: {"rate", "channels", "frames", "clipped", "path"} of the file written - "clipped" the
+    number of PCM samples the writer clipped, "path" "device" or "host" (module docstring).
+    A file not longer than n_fft/2 samples at the model rate raises ValueError before anything is written."""
+    import torch
+
+    if channels not in ("each", "mono"):
+        raise ValueError('channels must be "each" or "mono"')
+    if encoding is not None and encoding not in rs.ENCODINGS:
+        raise ValueError(f"encoding must be one of {sorted(rs.ENCODINGS)} or None")
+    jobs = [tuple(j) for j in jobs]
+    ss = model.ss_model
+    eng = ss.engine
+    dev, sr = eng.device, int(sampling_rate)
+
+    # plan: header, route and size of every job
+    infos, hows, sizes = [], [], []
+    for in_path, _, _ in jobs:
+        info = wavio.wav_info(in_path)
+        how = route(info, sr, out_rate)
+        meta = info[:4] if info is not None else _host_info(in_path)
+        n_planes, length = model_samples(meta[1], meta[2], meta[3], sr, channels)
+        if length <= eng.n_fft // 2:   # longform.plan_windows' refusal, with the file's name, before anything is written
+            raise ValueError(f"{in_path}: a recording of {length} samples is not longer than the reflect padding "
+                             f"(n_fft/2 = {eng.n_fft // 2})")
+        infos.append((info, meta))
+        hows.append(how)
+        sizes.append(n_planes * length)
+
+    clock, pool = _Clock(profile, dev), _Pinned()
+    records: List[Optional[dict]] = [None] * len(jobs)
+    passes = plan_passes(sizes, max_samples)
+    with ThreadPoolExecutor(1) as reader, ThreadPoolExecutor(1) as writer:
+        def submit_reads(ids):
+            return [reader.submit(_read_job, jobs[i][0], infos[i][0], hows[i], channels, pool, profile) for i in ids]
+
+        written, uploaded = [], []
+        reads = submit_reads(passes[0]) if passes else []
+        for pi, ids in enumerate(passes):
+            ahead = submit_reads(passes[pi + 1]) if pi + 1 < len(passes) else []   # the next pass is read while this one runs
+            captions, cap_of = dedup_captions([jobs[i][1] for i in ids])
+            emb = (model.query_encoder.get_query_embed(modality="text", text=captions, device=dev).to(torch.float32)
+                   if captions else None)
+            planes, conds, counts = [], [], []
+            for k, (i, fut) in enumerate(zip(ids, reads)):
+                (info, meta), got = infos[i], fut.result()
+                enc_in, nch, rate, frames = meta
+                if hows[i] == "device":
+                    nbytes = frames * nch * rs.SAMPLE_BYTES[enc_in]
+                    with clock("h2d"):
+                        raw = got[None, :(nbytes + 3) // 4 * 4].to(dev, non_blocking=True)
+                    with clock("decode"):
+                        if channels == "each":
+                            mine = list(eng.decode_resample_planar(raw, frames, nch, enc_in, rate, sr)[0])
+                        else:
+                            mine = [eng.decode_resample(raw, frames, nch, enc_in, rate, sr)[0]]
+                    uploaded.append(got)
+                else:
+                    mine = [torch.from_numpy(p).to(dev) for p in _host_resample(got, rate, sr)]
+                cond = emb[cap_of[k]] if cap_of[k] is not None else torch.as_tensor(jobs[i][1]).to(device=dev, dtype=torch.float32).reshape(-1)
+                planes += mine
+                conds += [cond] * len(mine)
+                counts.append(len(mine))
+            with clock("separate"):
+                seps = ss.separate_long_list(planes, torch.stack(conds), window=window, context=context, max_batch=max_batch,
+                                             fade=fade, fade_shape=fade_shape)
+            at = 0
+            for i, n in zip(ids, counts):
+                (info, meta), mine = infos[i], seps[at:at + n]
+                at += n
+                enc_in, nch, rate, frames = meta
+                rate_o = rate if out_rate is None else int(out_rate)
+                enc_o = encoding or enc_in or "f32"
+                L = int(mine[0].shape[0])
+                frames_o = frames if rate_o == rate else rs.out_len(L, *rs.ratio(sr, rate_o))
+                rec = {"rate": rate_o, "channels": n, "frames": frames_o, "path": hows[i]}
+                if hows[i] == "device":
+                    with clock("encode"):
+                        clipped = torch.zeros(1, dtype=torch.int32, device=dev)
+                        payload = eng.resample_encode(torch.stack(mine), sr, rate_o, enc_o, frames_out=frames_o, clipped=clipped)
+                    nbytes = payload.shape[1]
+                    tail = (nbytes + 3) // 4 * 4                   # the clip counter travels behind the payload
+                    buf = pool.take(tail + 4)
+                    with clock("d2h"):
+                        buf[:nbytes].copy_(payload[0], non_blocking=True)
+                        buf[tail:tail + 4].view(torch.int32).copy_(clipped, non_blocking=True)
+                        done = torch.cuda.Event()
+                        done.record(torch.cuda.current_stream(dev))
+                    written.append((i, buf, tail, writer.submit(_write_device, jobs[i][2], wavio.wav_header(enc_o, n, rate_o, frames_o),
+                                                                buf, nbytes, done, profile)))
+                else:
+                    with clock("d2h"):
+                        x = torch.stack(mine).cpu().numpy()
+                    y = _host_resample(x, sr, rate_o)[:, :frames_o]
+                    rec["clipped"] = host_clip_count(y, enc_o)
+                    written.append((i, None, 0, writer.submit(_write_host, jobs[i][2], enc_o, y, rate_o, profile)))
+                records[i] = rec
+            reads = ahead
+            # the pass's files are on disk (so its uploads are long done) and its counters read before its pinned rows go back
+            for i, buf, tail, fut in written:
+                fut.result()
+                if buf is not None:
+                    records[i]["clipped"] = int(buf[tail:tail + 4].view(torch.int32)[0])
+                    pool.give(buf)
+            for buf in uploaded:
+                pool.give(buf)
+            written, uploaded = [], []
+    return records
+
+
+def inference(model, audio_file: str, text, output_file: str, sampling_rate: int = 32000, **kw) -> dict:
+    """One file through `separate_files`: the single-file shape of upstream AudioSep's `pipeline.inference`.  Returns the job's
+    record."""
+    return separate_files(model, [(audio_file, text, output_file)], sampling_rate, **kw)[0]

@@ -1,7 +1,8 @@
 """Minimal RIFF/WAVE reader-writer (PCM16, PCM32, float32), mono down-mix.
 
 `wav_info` / `read_wav_raw_into` serve the evaluator's device load path: header parsing and the raw payload only, the decode,
-down-mix and resampling being `lass_decode_resample`'s (lass_amd/resample.py has the filter).
+down-mix and resampling being `lass_decode_resample`'s (lass_amd/resample.py has the filter).  `wav_header` serves the way back
+out: the 44 bytes in front of a payload the device encoded (`lass_resample_encode`, lass_amd/pipeline.py).
 
 
 Stands in for `librosa.load(path, sr=16000, mono=True)` (dcase_evaluator.py:73-74) for files that are ALREADY at the
@@ -236,31 +237,37 @@ def _frames_channels(x: np.ndarray):
     return x.shape[1]
 
 
-def write_wav_f32(path: str, x: np.ndarray, sr: int) -> None:
-    x = np.ascontiguousarray(x, dtype="<f4")
-    nch = _frames_channels(x)
-    body = x.tobytes()
-    hdr = b"RIFF" + struct.pack("<I", 36 + len(body)) + b"WAVE" + b"fmt " + struct.pack(
-        "<IHHIIHH", 16, 3, nch, sr, sr * 4 * nch, 4 * nch, 32) + b"data" + struct.pack("<I", len(body))
+_WAV_FORMATS = {"pcm16": (1, 2), "pcm32": (1, 4), "f32": (3, 4)}  # encoding -> (format tag, bytes per sample)
+
+
+def wav_header(encoding: str, channels: int, rate: int, frames: int) -> bytes:
+    """The 44-byte RIFF/WAVE header (`fmt ` chunk of 16 bytes, then `data`) in front of `frames` interleaved frames of
+    `channels` samples, encoding "pcm16", "pcm32" or "f32": what the three writers below put in front of their payload, for
+    callers that hold the payload already (lass_amd.pipeline writes the device's `Engine.resample_encode` rows behind it)."""
+    if encoding not in _WAV_FORMATS:
+        raise ValueError(f"encoding must be one of {sorted(_WAV_FORMATS)}")
+    tag, size = _WAV_FORMATS[encoding]
+    channels, rate, frames = int(channels), int(rate), int(frames)
+    nbytes = frames * channels * size
+    if channels < 1 or rate < 1 or frames < 0 or 36 + nbytes >= 2 ** 32:
+        raise ValueError("channels and rate must be positive and the payload must stay below 4 GiB")
+    return b"RIFF" + struct.pack("<I", 36 + nbytes) + b"WAVE" + b"fmt " + struct.pack(
+        "<IHHIIHH", 16, tag, channels, rate, rate * size * channels, size * channels, 8 * size) + b"data" + struct.pack("<I", nbytes)
+
+
+def _write(path: str, encoding: str, q: np.ndarray, sr: int) -> None:
+    nch = _frames_channels(q)
     with open(path, "wb") as f:
-        f.write(hdr + body)
+        f.write(wav_header(encoding, nch, sr, q.shape[0]) + q.tobytes())
+
+
+def write_wav_f32(path: str, x: np.ndarray, sr: int) -> None:
+    _write(path, "f32", np.ascontiguousarray(x, dtype="<f4"), sr)
 
 
 def write_wav_pcm16(path: str, x: np.ndarray, sr: int) -> None:
-    q = np.ascontiguousarray(np.clip(np.round(np.asarray(x, dtype=np.float64) * 32768.0), -32768, 32767).astype("<i2"))
-    nch = _frames_channels(q)
-    body = q.tobytes()
-    hdr = b"RIFF" + struct.pack("<I", 36 + len(body)) + b"WAVE" + b"fmt " + struct.pack(
-        "<IHHIIHH", 16, 1, nch, sr, sr * 2 * nch, 2 * nch, 16) + b"data" + struct.pack("<I", len(body))
-    with open(path, "wb") as f:
-        f.write(hdr + body)
+    _write(path, "pcm16", np.ascontiguousarray(np.clip(np.round(np.asarray(x, dtype=np.float64) * 32768.0), -32768, 32767).astype("<i2")), sr)
 
 
 def write_wav_pcm32(path: str, x: np.ndarray, sr: int) -> None:
-    q = np.ascontiguousarray(np.clip(np.round(np.asarray(x, dtype=np.float64) * 2147483648.0), -2147483648, 2147483647).astype("<i4"))
-    nch = _frames_channels(q)
-    body = q.tobytes()
-    hdr = b"RIFF" + struct.pack("<I", 36 + len(body)) + b"WAVE" + b"fmt " + struct.pack(
-        "<IHHIIHH", 16, 1, nch, sr, sr * 4 * nch, 4 * nch, 32) + b"data" + struct.pack("<I", len(body))
-    with open(path, "wb") as f:
-        f.write(hdr + body)
+    _write(path, "pcm32", np.ascontiguousarray(np.clip(np.round(np.asarray(x, dtype=np.float64) * 2147483648.0), -2147483648, 2147483647).astype("<i4")), sr)

@@ -1,0 +1,145 @@
+"""File in, file out on one MI355X: `pipeline.separate_files` against the same jobs done with the pieces the package had before
+it, on 32 seeded one-minute 44.1 kHz stereo PCM16 files (synthetic ResUNet30 weights, 16 kHz, f32 unless --compute-dtype).
+
+    python tools/separate_files_bench.py [--files 32] [--seconds 60] [--reps 5] [--compute-dtype f32]
+
+Leg A: `separate_files(channels="each")` - decode, resample, separate, resample back, encode and interleave on the device.
+Leg B: host decode + de-interleave + `wavio._resample` (scipy, float64), `separate_long_list`, `.cpu()`, host `_resample` back
+and `wavio.write_wav_pcm16`.  The legs alternate A B A B ..., `--reps` runs each, every run in a child process of its own under
+`timeout -k 10` (a failing run ends the whole); a child separates one file as a warm-up before its timed pass.  Prints one JSON
+line per run and a summary line: median seconds, files/s and x real time per leg, and leg A's time split from one further run
+with `profile=` (which synchronises after every stage, so its parts add up to more than an unprofiled pass).
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SR, FILE_RATE, CHANNELS = 16000, 44100, 2
+
+
+def make_files(d: str, n: int, seconds: float):
+    import numpy as np
+    from lass_amd import wavio
+    frames = int(seconds * FILE_RATE)
+    t = np.arange(frames)[:, None] / FILE_RATE
+    for i in range(n):
+        rng = np.random.Generator(np.random.PCG64([24, i]))
+        x = 0.1 * rng.standard_normal((frames, CHANNELS)) + 0.3 * np.sin(2 * np.pi * rng.uniform(100, 4000, CHANNELS) * t)
+        wavio.write_wav_pcm16(os.path.join(d, f"in_{i:03d}.wav"), x.astype(np.float32), FILE_RATE)
+
+
+def _model(mode: str):
+    import numpy as np
+    import torch
+    from lass_amd import synthetic
+    from lass_amd.audiosep import AudioSep, PrecomputedQueryEncoder
+    from lass_amd.resunet import ResUNet30
+    m = ResUNet30(1, 1, 512)
+    m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in synthetic.make_state_dict().items()})
+    return AudioSep(ss_model=m.to("cuda:0").eval().set_compute_dtype(mode), query_encoder=PrecomputedQueryEncoder())
+
+
+def _jobs(d: str, n: int, tag: str):
+    return [(os.path.join(d, f"in_{i:03d}.wav"), f"caption {i % 4}", os.path.join(d, f"out_{tag}_{i:03d}.wav")) for i in range(n)]
+
+
+def host_pieces(model, jobs):
+    """Leg B: what a caller did before `separate_files` existed."""
+    import numpy as np
+    import torch
+    from lass_amd import wavio
+    captions = sorted({q for _, q, _ in jobs})
+    emb = model.query_encoder.get_query_embed(modality="text", text=captions, device="cuda:0")
+    planes, conds, metas = [], [], []
+    for path, q, _ in jobs:
+        enc, nch, rate, frames, offset = wavio.wav_info(path)
+        with open(path, "rb") as f:
+            f.seek(offset)
+            x = np.frombuffer(f.read(frames * nch * 2), dtype="<i2").astype(np.float32).reshape(frames, nch) / 32768.0
+        for c in range(nch):
+            planes.append(torch.from_numpy(wavio._resample(x[:, c], rate, SR)).to("cuda:0"))
+            conds.append(emb[captions.index(q)])
+        metas.append((nch, rate, frames))
+    seps = model.ss_model.separate_long_list(planes, torch.stack(conds))
+    at = 0
+    for (_, _, out), (nch, rate, frames) in zip(jobs, metas):
+        y = np.stack([wavio._resample(s.cpu().numpy(), SR, rate)[:frames] for s in seps[at:at + nch]], axis=1)
+        at += nch
+        wavio.write_wav_pcm16(out, y, rate)
+
+
+def leg(name: str, d: str, n: int, mode: str):
+    import torch
+    from lass_amd import pipeline
+    model = _model(mode)
+    profile = {} if name == "A-profile" else None
+
+    def run(jobs, profile=None):
+        if name == "B":
+            host_pieces(model, jobs)
+        else:
+            pipeline.separate_files(model, jobs, SR, channels="each", profile=profile)
+
+    run(_jobs(d, 1, "warm"))
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    run(_jobs(d, n, name), profile)
+    torch.cuda.synchronize()
+    res = {"leg": name, "seconds": round(time.perf_counter() - t0, 4)}
+    if profile is not None:
+        res["split_s"] = {k: round(v, 4) for k, v in profile.items()}
+    print(json.dumps(res), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--files", type=int, default=32)
+    ap.add_argument("--seconds", type=float, default=60.0)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--compute-dtype", default="f32")
+    ap.add_argument("--timeout", type=int, default=300, help="seconds per run")
+    ap.add_argument("--leg", choices=["A", "B", "A-profile"])
+    ap.add_argument("--dir")
+    a = ap.parse_args()
+    if a.leg:
+        leg(a.leg, a.dir, a.files, a.compute_dtype)
+        return 0
+    with tempfile.TemporaryDirectory() as d:
+        make_files(d, a.files, a.seconds)
+        times = {"A": [], "B": []}
+        split = None
+        for name in ["A", "B"] * a.reps + ["A-profile"]:
+            cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--leg", name, "--dir", d,
+                   "--files", str(a.files), "--compute-dtype", a.compute_dtype]
+            pr = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, text=True)
+            sys.stdout.write(pr.stdout)
+            sys.stdout.flush()
+            if pr.returncode != 0:
+                print(json.dumps({"leg": name, "failed": pr.returncode}), flush=True)
+                return pr.returncode
+            res = json.loads(pr.stdout.strip().split("\n")[-1])
+            if name == "A-profile":
+                split = res["split_s"]
+            else:
+                times[name].append(res["seconds"])
+        audio = a.files * a.seconds
+        summary = {"files": a.files, "seconds_each": a.seconds, "compute_dtype": a.compute_dtype, "A_split_s": split}
+        for name, ts in times.items():
+            med = statistics.median(ts)
+            summary[name] = {"median_s": round(med, 4), "files_per_s": round(a.files / med, 2), "x_real_time": round(audio / med, 1),
+                             "runs_s": ts}
+        summary["B_over_A"] = round(summary["B"]["median_s"] / summary["A"]["median_s"], 2)
+        print(json.dumps(summary), flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
