@@ -139,3 +139,58 @@ def check(ctx, rc: int, what: str):
         msg = load().lass_last_error(ctx)
         raise LassError(f"{what} failed ({rc}): {msg.decode() if msg else '?'}")
     return rc
+
+
+class TowerContext:
+    """Owns one context of a CLAP tower with its weights uploaded: the lass_text_ctx / lass_audioq_ctx behind the symbols
+    <family>_create, _destroy, _last_error, _set_param and _finalize (family "lass_text" or "lass_audioq")."""
+
+    def __init__(self, family: str, dev, tensors):
+        """tensors: the (name, tensor) pairs the tower's kernels read, on the torch device `dev`."""
+        import torch
+
+        self.lib, self.family = load(), family
+        h = c_void_p()
+        rc = self.fn("create")(ctypes.byref(h), dev.index if dev.index is not None else torch.cuda.current_device())
+        if rc < 0:
+            raise LassError(f"{family}_create failed ({rc}): {self.fn('last_error')(None).decode()}")
+        self.ctx = h
+        self.key = self.key_of(dev, tensors)
+        torch.cuda.current_stream(dev).synchronize()  # <family>_set_param copies on the NULL stream
+        for name, p in tensors:
+            t = p.detach().to(torch.float32).contiguous()
+            shape = (c_int64 * t.dim())(*t.shape)
+            self.check(self.fn("set_param")(self.ctx, name.encode(), c_void_p(t.data_ptr()), shape, t.dim()),
+                       f"{family}_set_param({name})")
+        self.check(self.fn("finalize")(self.ctx), f"{family}_finalize")
+
+    @staticmethod
+    def key_of(dev, tensors):
+        """What an upload is valid for: the device, and every tensor's storage and version."""
+        return (dev, tuple((p.data_ptr(), p._version) for _, p in tensors))
+
+    def fn(self, name: str):
+        return getattr(self.lib, f"{self.family}_{name}")
+
+    def check(self, rc: int, what: str) -> int:
+        if rc < 0:
+            raise LassError(f"{what} failed ({rc}): {self.fn('last_error')(self.ctx).decode()}")
+        return rc
+
+    def __del__(self):
+        try:
+            if getattr(self, "ctx", None):
+                self.fn("destroy")(self.ctx)
+                self.ctx = None
+        except Exception:
+            pass
+
+
+def grow_workspace(owner, nbytes: int, dev):
+    """owner._ws: a uint8 tensor of at least nbytes on `dev`; a smaller one is released before the larger one is allocated."""
+    import torch
+
+    if owner._ws is None or owner._ws.device != dev or owner._ws.numel() < nbytes:
+        owner._ws = None
+        owner._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    return owner._ws

@@ -18,7 +18,7 @@ from __future__ import annotations
 import ctypes
 import math
 import random
-from ctypes import POINTER, byref, c_int, c_int64, c_size_t, c_void_p
+from ctypes import POINTER, byref, c_int, c_size_t, c_void_p
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -153,31 +153,6 @@ class lass_audioq_taps(ctypes.Structure):
                 ("embedding", c_void_p)]
 
 
-class _AudioContext:
-    """Owns one lass_audioq_ctx."""
-
-    def __init__(self, device_index: int):
-        self.lib = _lib.load()
-        h = c_void_p()
-        rc = self.lib.lass_audioq_create(byref(h), device_index)
-        if rc < 0:
-            raise _lib.LassError(f"lass_audioq_create failed ({rc}): {self.lib.lass_audioq_last_error(None).decode()}")
-        self.ctx = h
-
-    def check(self, rc: int, what: str) -> int:
-        if rc < 0:
-            raise _lib.LassError(f"{what} failed ({rc}): {self.lib.lass_audioq_last_error(self.ctx).decode()}")
-        return rc
-
-    def __del__(self):
-        try:
-            if getattr(self, "ctx", None):
-                self.lib.lass_audioq_destroy(self.ctx)
-                self.ctx = None
-        except Exception:
-            pass
-
-
 def _block(C: int, heads: int, res: int, shifted: bool) -> nn.Module:
     attn = _module(qkv=nn.Linear(C, 3 * C), proj=nn.Linear(C, C))
     attn.relative_position_bias_table = nn.Parameter(torch.zeros((2 * WINDOW - 1) ** 2, heads))
@@ -225,8 +200,7 @@ class ClapAudioEncoder(nn.Module):
                 p.zero_()
         self.eval()
         self.depths, self.embed_dim, self.features = depths, embed_dim, F
-        self._ctx: Optional[_AudioContext] = None
-        self._ctx_key = None
+        self._ctx: Optional[_lib.TowerContext] = None
         self._ws: Optional[torch.Tensor] = None
 
     # ---- weights ---------------------------------------------------------------------------------------------
@@ -292,26 +266,16 @@ class ClapAudioEncoder(nn.Module):
             if not any(u in name for u in _UNUSED):
                 yield name, t
 
-    def _context(self) -> _AudioContext:
+    def _context(self) -> _lib.TowerContext:
         dev = self.device
         if dev.type != "cuda":
             raise _lib.LassError("ClapAudioEncoder computes on an MI355X only: move it to a cuda/HIP device first "
                                  "(lass_amd has no CPU fallback)")
         params = list(self._uploaded())
-        key = (dev, tuple((p.data_ptr(), p._version) for _, p in params))
-        if self._ctx is not None and self._ctx_key == key:
-            return self._ctx
-        self._ctx = None
-        ctx = _AudioContext(dev.index if dev.index is not None else torch.cuda.current_device())
-        torch.cuda.current_stream(dev).synchronize()  # lass_audioq_set_param copies on the NULL stream
-        for name, p in params:
-            t = p.detach().to(torch.float32).contiguous()
-            shape = (c_int64 * t.dim())(*t.shape)
-            ctx.check(ctx.lib.lass_audioq_set_param(ctx.ctx, name.encode(), c_void_p(t.data_ptr()), shape, t.dim()),
-                      f"lass_audioq_set_param({name})")
-        ctx.check(ctx.lib.lass_audioq_finalize(ctx.ctx), "lass_audioq_finalize")
-        self._ctx, self._ctx_key = ctx, key
-        return ctx
+        if self._ctx is None or self._ctx.key != _lib.TowerContext.key_of(dev, params):
+            self._ctx = None  # the previous upload is freed before the new one is made
+            self._ctx = _lib.TowerContext("lass_audioq", dev, params)
+        return self._ctx
 
     # ---- compute ---------------------------------------------------------------------------------------------
     @staticmethod
@@ -347,9 +311,7 @@ class ClapAudioEncoder(nn.Module):
         B, L = wave.shape
         n = c_size_t()
         ctx.check(ctx.lib.lass_audioq_workspace_bytes(ctx.ctx, B, byref(n)), "lass_audioq_workspace_bytes")
-        if self._ws is None or self._ws.device != dev or self._ws.numel() < n.value:
-            self._ws = None
-            self._ws = torch.empty(n.value, dtype=torch.uint8, device=dev)
+        ws = _lib.grow_workspace(self, n.value, dev)
         out = torch.empty(B, PROJ, dtype=torch.float32, device=dev)
         t = lass_audioq_taps()
         res = {}
@@ -368,7 +330,7 @@ class ClapAudioEncoder(nn.Module):
                 t.stage[i] = res["stages"][-1].data_ptr()
         fn = ctx.lib.lass_audioq_encode_wave32k if rate32k else ctx.lib.lass_audioq_encode_wave48k
         rc = fn(ctx.ctx, c_void_p(wave.data_ptr()), lens.ctypes.data_as(POINTER(c_int)), B, L, c_void_p(out.data_ptr()),
-                byref(t) if taps else None, c_void_p(self._ws.data_ptr()), self._ws.numel(),
+                byref(t) if taps else None, c_void_p(ws.data_ptr()), ws.numel(),
                 c_void_p(torch.cuda.current_stream(dev).cuda_stream))
         ctx.check(rc, fn.__name__)
         return (out, res) if taps else out

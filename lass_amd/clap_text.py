@@ -11,7 +11,7 @@ There is no CPU fallback and no tokenizer implementation: captions are tokenized
 from __future__ import annotations
 
 import os
-from ctypes import byref, c_int64, c_size_t, c_void_p
+from ctypes import byref, c_size_t, c_void_p
 from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
@@ -70,31 +70,6 @@ def _layer() -> nn.Module:
                    output=_module(dense=nn.Linear(FFN, HIDDEN), LayerNorm=ln()))
 
 
-class _TextContext:
-    """Owns one lass_text_ctx."""
-
-    def __init__(self, device_index: int):
-        self.lib = _lib.load()
-        h = c_void_p()
-        rc = self.lib.lass_text_create(byref(h), device_index)
-        if rc < 0:
-            raise _lib.LassError(f"lass_text_create failed ({rc}): {self.lib.lass_text_last_error(None).decode()}")
-        self.ctx = h
-
-    def check(self, rc: int, what: str) -> int:
-        if rc < 0:
-            raise _lib.LassError(f"{what} failed ({rc}): {self.lib.lass_text_last_error(self.ctx).decode()}")
-        return rc
-
-    def __del__(self):
-        try:
-            if getattr(self, "ctx", None):
-                self.lib.lass_text_destroy(self.ctx)
-                self.ctx = None
-        except Exception:
-            pass
-
-
 class ClapTextEncoder(nn.Module):
     """Drop-in query encoder (`get_query_embed` signature of models/clap_encoder.py:93-106) for the text modality."""
 
@@ -119,8 +94,7 @@ class ClapTextEncoder(nn.Module):
         self.layers, self.vocab_size, self.max_positions = layers, vocab_size, max_positions
         self.tokenizer = tokenizer
         self.tokenizer_dir = tokenizer_dir
-        self._ctx: Optional[_TextContext] = None
-        self._ctx_key = None
+        self._ctx: Optional[_lib.TowerContext] = None
         self._ws: Optional[torch.Tensor] = None
 
     # ---- weights ---------------------------------------------------------------------------------------------
@@ -175,26 +149,16 @@ class ClapTextEncoder(nn.Module):
     def device(self) -> torch.device:
         return self.model.text_projection[0].weight.device
 
-    def _context(self) -> _TextContext:
+    def _context(self) -> _lib.TowerContext:
         dev = self.device
         if dev.type != "cuda":
             raise _lib.LassError("ClapTextEncoder computes on an MI355X only: move it to a cuda/HIP device first "
                                  "(lass_amd has no CPU fallback)")
         params = list(self.model.named_parameters())  # keys relative to the CLAP model: text_branch.*, text_projection.*
-        key = (dev, tuple((p.data_ptr(), p._version) for _, p in params))
-        if self._ctx is not None and self._ctx_key == key:
-            return self._ctx
-        self._ctx = None
-        ctx = _TextContext(dev.index if dev.index is not None else torch.cuda.current_device())
-        torch.cuda.current_stream(dev).synchronize()  # lass_text_set_param copies on the NULL stream
-        for name, p in params:
-            t = p.detach().to(torch.float32).contiguous()
-            shape = (c_int64 * t.dim())(*t.shape)
-            ctx.check(ctx.lib.lass_text_set_param(ctx.ctx, name.encode(), c_void_p(t.data_ptr()), shape,
-                                                  t.dim()), f"lass_text_set_param({name})")
-        ctx.check(ctx.lib.lass_text_finalize(ctx.ctx), "lass_text_finalize")
-        self._ctx, self._ctx_key = ctx, key
-        return ctx
+        if self._ctx is None or self._ctx.key != _lib.TowerContext.key_of(dev, params):
+            self._ctx = None  # the previous upload is freed before the new one is made
+            self._ctx = _lib.TowerContext("lass_text", dev, params)
+        return self._ctx
 
     # ---- compute ---------------------------------------------------------------------------------------------
     def _validate(self, input_ids, attention_mask) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -229,15 +193,13 @@ class ClapTextEncoder(nn.Module):
         N, S = ids.shape
         n = c_size_t()
         ctx.check(ctx.lib.lass_text_workspace_bytes(ctx.ctx, N, S, byref(n)), "lass_text_workspace_bytes")
-        if self._ws is None or self._ws.device != dev or self._ws.numel() < n.value:
-            self._ws = None
-            self._ws = torch.empty(n.value, dtype=torch.uint8, device=dev)
+        ws = _lib.grow_workspace(self, n.value, dev)
         ids_dev = ids.to(dev)
         out = torch.empty(N, PROJ, dtype=torch.float32, device=dev)
         pool = torch.empty(N, HIDDEN, dtype=torch.float32, device=dev) if return_pooler else None
         rc = ctx.lib.lass_text_encode(ctx.ctx, c_void_p(ids_dev.data_ptr()), c_void_p(mask.data_ptr()), N, S,
                                       c_void_p(out.data_ptr()), c_void_p(pool.data_ptr() if pool is not None else 0),
-                                      c_void_p(self._ws.data_ptr()), self._ws.numel(),
+                                      c_void_p(ws.data_ptr()), ws.numel(),
                                       c_void_p(torch.cuda.current_stream(dev).cuda_stream))
         ctx.check(rc, "lass_text_encode")
         return (out, pool) if return_pooler else out

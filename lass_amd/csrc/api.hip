@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/lass_hip.h"
+#include "ctx_parts.h"
 #include "graph_cache.h"
 #include "head_fold.h"
 #include "kernels.h"
@@ -24,12 +25,6 @@ namespace {
 
 constexpr float kBnEps = 1e-5f;
 constexpr int kMaxBranches = LASS_MAX_STFT_WINDOWS;
-
-struct Raw {
-    float* d = nullptr;
-    std::vector<int64_t> shape;
-    size_t n = 0;
-};
 
 struct Site {
     std::string film;  // "encoder_block1->conv_block1->beta1"
@@ -71,7 +66,7 @@ struct lass_ctx {
     Geometry g;
     ModelTable m;  // encoder / decoder table of THIS model (conv_route.h)
     std::string pre_name[kMaxBranches];  // "base.pre_conv" / "base.pre_convs.<win>"
-    std::map<std::string, Raw> raw;
+    ParamStore raw;
     bool finalized = false;
     float2* tw2k = nullptr;  // (cos, sin)(2 pi k / 2048): twiddles of every transform size + the Hann windows
     std::vector<Site> sites;
@@ -132,20 +127,6 @@ struct lass_ctx {
 };
 
 namespace {
-
-#define HIP_TRY(ctx, expr)                                                                                     \
-    do {                                                                                                       \
-        hipError_t _e = (expr);                                                                                \
-        if (_e != hipSuccess) {                                                                                \
-            (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(_e);                                     \
-            return LASS_ERR_HIP;                                                                               \
-        }                                                                                                      \
-    } while (0)
-
-int fail(lass_ctx* ctx, int code, const std::string& msg) {
-    if (ctx) ctx->err = msg;
-    return code;
-}
 
 bool starts_with(const std::string& s, const char* p) { return s.rfind(p, 0) == 0; }
 bool ends_with(const std::string& s, const char* p) {
@@ -289,10 +270,7 @@ bool ignorable(const std::string& name) {
     return false;
 }
 
-const float* rawp(const lass_ctx* c, const std::string& name) {
-    auto it = c->raw.find(name);
-    return it == c->raw.end() ? nullptr : it->second.d;
-}
+const float* rawp(const lass_ctx* c, const std::string& name) { return c->raw.get(name); }
 
 template <typename T>
 int dev_alloc(lass_ctx* c, T** p, size_t count) {
@@ -770,27 +748,7 @@ const char* lass_last_error(const lass_ctx* ctx) { return ctx ? ctx->err.c_str()
 static int create_impl(lass_ctx** out, int device_id, const Geometry& geom) {
     if (!out) return LASS_ERR_ARG;
     *out = nullptr;
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) {
-        g_create_err = std::string("no HIP device available: ") + hipGetErrorString(e) +
-                       " (liblass_hip has no CPU fallback)";
-        return LASS_ERR_HIP;
-    }
-    if (device_id < 0 || device_id >= ndev) {
-        g_create_err = "device_id out of range";
-        return LASS_ERR_ARG;
-    }
-    hipDeviceProp_t prop;
-    e = hipGetDeviceProperties(&prop, device_id);
-    if (e != hipSuccess) {
-        g_create_err = std::string("hipGetDeviceProperties: ") + hipGetErrorString(e);
-        return LASS_ERR_HIP;
-    }
-    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0) {
-        g_create_err = std::string("device is ") + prop.gcnArchName + "; liblass_hip is built for gfx950 only";
-        return LASS_ERR_HIP;
-    }
+    if (int rc = open_device(device_id, g_create_err)) return rc;
     lass_ctx* c = new lass_ctx();
     c->device = device_id;
     c->g = geom;
@@ -889,7 +847,7 @@ int lass_destroy(lass_ctx* c) {
     if (!c) return LASS_ERR_ARG;
     (void)hipSetDevice(c->device);
     free_owned(c);
-    for (auto& kv : c->raw) (void)hipFree(kv.second.d);
+    c->raw.free_all();
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     (void)hipDeviceSynchronize();  // no replay of a graph below is in flight any more
     drop_graphs(c);
@@ -922,14 +880,8 @@ int lass_set_param(lass_ctx* c, const char* name_c, const void* data, const int6
         for (auto v : want) m += std::to_string(v) + ",";
         return fail(c, LASS_ERR_ARG, m + ")");
     }
-    size_t n = 1;
-    for (auto v : want) n *= (size_t)v;
     HIP_TRY(c, hipSetDevice(c->device));
-    Raw& r = c->raw[name];
-    if (!r.d) HIP_TRY(c, hipMalloc((void**)&r.d, n * sizeof(float)));
-    r.shape = want;
-    r.n = n;
-    HIP_TRY(c, hipMemcpy(r.d, data, n * sizeof(float), hipMemcpyDefault));
+    if (int rc = c->raw.put(c, name, data, shape, ndim)) return rc;
     c->finalized = false;
     return 0;
 }
@@ -1117,7 +1069,7 @@ int lass_finalize(lass_ctx* c, int compute_mode) {
         ResBlock& rb = c->dec[5];
         rb.u2h = rb.wsch = rb.bh = nullptr;
         c->hs_wt = c->hs_wskip = nullptr;
-        const Raw& ra = c->raw["base.after_conv.weight"];
+        const Param& ra = c->raw.by_name["base.after_conv.weight"];
         const int Q = ra.shape.empty() ? 0 : (int)ra.shape[0];
         if (rb.u2f && rb.cin != rb.cout && Q > 0 && Q <= kHeadFoldRows && ra.n == (size_t)Q * rb.cout) {
             const int N = rb.cout, K = rb.cin;
@@ -1131,11 +1083,11 @@ int lass_finalize(lass_ctx* c, int compute_mode) {
             // ... and the shortcut's two halves for the launches that produce its inputs (ResUNet30: the skip is ONE encoder_block1's
             // output): Wt' = Wsc'_up o Wt for the transposed conv, Wsc'_skip for encoder_block1.conv2's epilogue
             const DecSpec& d6 = c->m.D[5];
-            const auto up = c->raw.find(std::string("base.") + d6.name + ".conv1.weight");
-            if (c->g.variant == 0 && c->g.nbr == 1 && Q == 3 && K == d6.cout + kPreCh && up != c->raw.end() && up->second.d &&
-                up->second.n == (size_t)d6.cin * d6.cout * d6.uh * d6.uw) {
-                std::vector<float> wt(up->second.n);
-                HIP_TRY(c, hipMemcpy(wt.data(), up->second.d, wt.size() * sizeof(float), hipMemcpyDeviceToHost));
+            const Param* up = c->raw.find(std::string("base.") + d6.name + ".conv1.weight");
+            if (c->g.variant == 0 && c->g.nbr == 1 && Q == 3 && K == d6.cout + kPreCh && up && up->d &&
+                up->n == (size_t)d6.cin * d6.cout * d6.uh * d6.uw) {
+                std::vector<float> wt(up->n);
+                HIP_TRY(c, hipMemcpy(wt.data(), up->d, wt.size() * sizeof(float), hipMemcpyDeviceToHost));
                 HeadScFold hsf;
                 if (compose_head_sc_fold(ws.data(), wa.data(), wt.data(), N, d6.cout, kPreCh, Q, d6.cin, d6.uh, d6.uw, &hsf)) {
                     if (dev_alloc(c, &c->hs_wt, hsf.wt.size()) || dev_alloc(c, &c->hs_wskip, hsf.wskip.size())) return LASS_ERR_HIP;
@@ -1448,40 +1400,6 @@ int lass_mix_at_snr(lass_ctx* c, float* source, const float* noise, const float*
     return 0;
 }
 
-int lass_decode_resample(lass_ctx* c, const void* raw, int64_t row_stride_bytes, int B, int frames, int channels, int encoding,
-                         int up, int down, const float* taps, int n_taps, float* out, int L_out, void* stream) {
-    const char* w = "lass_decode_resample: ";
-    if (!c) return LASS_ERR_ARG;
-    if (!raw || !out || B <= 0 || B > 65535 || frames <= 0) return fail(c, LASS_ERR_ARG, std::string(w) + "raw, out non-NULL, 1 <= B <= 65535, frames >= 1");
-    if (encoding != LASS_WAV_PCM16 && encoding != LASS_WAV_PCM32 && encoding != LASS_WAV_F32)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "encoding must be LASS_WAV_PCM16, LASS_WAV_PCM32 or LASS_WAV_F32");
-    if (channels < 1 || channels > 8) return fail(c, LASS_ERR_ARG, std::string(w) + "1 ... 8 channels");
-    if (up < 1 || down < 1 || up > LASS_RESAMPLE_MAX_RATIO || down > LASS_RESAMPLE_MAX_RATIO)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "up and down must lie in 1 ... " + std::to_string(LASS_RESAMPLE_MAX_RATIO));
-    const bool fir = up != 1 || down != 1;
-    if (fir) {
-        if (!taps || n_taps < 1 || n_taps % 2 == 0) return fail(c, LASS_ERR_ARG, std::string(w) + "taps non-NULL, n_taps odd");
-        if (n_taps > LASS_RESAMPLE_MAX_TAPS)
-            return fail(c, LASS_ERR_ARG, std::string(w) + std::to_string(n_taps) + " taps exceed the cap of " +
-                        std::to_string(LASS_RESAMPLE_MAX_TAPS) + " (resample on the host)");
-        if (lass_resample_table_floats(up, n_taps) > LASS_RESAMPLE_MAX_TABLE)
-            return fail(c, LASS_ERR_ARG, std::string(w) + "the polyphase table up * (ceil(n_taps/up) | 1) exceeds " +
-                        std::to_string(LASS_RESAMPLE_MAX_TABLE) + " floats");
-    }
-    const long long want = ((long long)frames * up + down - 1) / down;
-    if (L_out <= 0 || want != (long long)L_out)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "L_out must be ceil(frames*up/down) = " + std::to_string(want));
-    const long long row_bytes = (long long)frames * channels * (encoding == LASS_WAV_PCM16 ? 2 : 4);
-    if (row_stride_bytes < row_bytes || row_stride_bytes % 4 != 0)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "row_stride_bytes must be a multiple of 4 and hold a row (" +
-                    std::to_string(row_bytes) + " bytes)");
-    if (reinterpret_cast<uintptr_t>(raw) % 4 != 0) return fail(c, LASS_ERR_ARG, std::string(w) + "raw must be 4-byte aligned");
-    if (int r = use_device(c)) return r;
-    HIP_TRY(c, lass_launch_decode_resample(raw, row_stride_bytes, B, frames, channels, encoding, up, down, taps, n_taps, out, L_out,
-                                           (hipStream_t)stream));
-    return 0;
-}
-
 // What lass_decode_resample asks of encoding, channels, up, down and the filter, for the entry points that share its limits
 // (w: the caller's "name: ").  0, or LASS_ERR_ARG with the message set.
 static int check_resample_args(lass_ctx* c, const char* w, int channels, int encoding, int up, int down, const float* taps,
@@ -1503,9 +1421,10 @@ static int check_resample_args(lass_ctx* c, const char* w, int channels, int enc
     return 0;
 }
 
-int lass_decode_resample_planar(lass_ctx* c, const void* raw, int64_t row_stride_bytes, int B, int frames, int channels,
-                                int encoding, int up, int down, const float* taps, int n_taps, float* out, int L_out, void* stream) {
-    const char* w = "lass_decode_resample_planar: ";
+// The two decode entries: one checked body (w: the entry's "name: "; planar: one output plane per channel, no down-mix).
+static int decode_resample(lass_ctx* c, const char* w, const void* raw, int64_t row_stride_bytes, int B, int frames, int channels,
+                           int encoding, int up, int down, const float* taps, int n_taps, bool planar, float* out, int L_out,
+                           void* stream) {
     if (!c) return LASS_ERR_ARG;
     if (!raw || !out || B <= 0 || B > 65535 || frames <= 0) return fail(c, LASS_ERR_ARG, std::string(w) + "raw, out non-NULL, 1 <= B <= 65535, frames >= 1");
     if (int r = check_resample_args(c, w, channels, encoding, up, down, taps, n_taps)) return r;
@@ -1518,9 +1437,21 @@ int lass_decode_resample_planar(lass_ctx* c, const void* raw, int64_t row_stride
                     std::to_string(row_bytes) + " bytes)");
     if (reinterpret_cast<uintptr_t>(raw) % 4 != 0) return fail(c, LASS_ERR_ARG, std::string(w) + "raw must be 4-byte aligned");
     if (int r = use_device(c)) return r;
-    HIP_TRY(c, lass_launch_decode_resample_planar(raw, row_stride_bytes, B, frames, channels, encoding, up, down, taps, n_taps, out,
-                                                  L_out, (hipStream_t)stream));
+    HIP_TRY(c, lass_launch_decode_resample(raw, row_stride_bytes, B, frames, channels, encoding, up, down, taps, n_taps, planar, out,
+                                           L_out, (hipStream_t)stream));
     return 0;
+}
+
+int lass_decode_resample(lass_ctx* c, const void* raw, int64_t row_stride_bytes, int B, int frames, int channels, int encoding,
+                         int up, int down, const float* taps, int n_taps, float* out, int L_out, void* stream) {
+    return decode_resample(c, "lass_decode_resample: ", raw, row_stride_bytes, B, frames, channels, encoding, up, down, taps, n_taps,
+                           false, out, L_out, stream);
+}
+
+int lass_decode_resample_planar(lass_ctx* c, const void* raw, int64_t row_stride_bytes, int B, int frames, int channels,
+                                int encoding, int up, int down, const float* taps, int n_taps, float* out, int L_out, void* stream) {
+    return decode_resample(c, "lass_decode_resample_planar: ", raw, row_stride_bytes, B, frames, channels, encoding, up, down, taps,
+                           n_taps, true, out, L_out, stream);
 }
 
 int lass_resample_encode(lass_ctx* c, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels, int L_in,

@@ -1,7 +1,7 @@
 // audio_clap.hip - the CLAP audio tower on the device: 32 -> 48 kHz resampler, repeat-pad + log-mel front end, HTSAT (a Swin
 // transformer over the 256 x 256 fold of the spectrogram, CLAP/open_clip/htsat.py:1012-1149) + audio projection + L2
 // normalisation (CLAP/open_clip/model.py:566-570, 754-781), behind its own lass_audioq_ctx.  f32 throughout; every
-// contraction of the tower runs on v_mfma_f32_32x32x2_f32 (the GEMM of f32_gemm.h, shared with text.hip, and the two
+// contraction of the tower runs on v_mfma_f32_32x32x2_f32 (the GEMM of tower_parts.h, shared with text.hip, and the two
 // products of the window attention).
 //
 // Batch invariance: every kernel computes a frame, a token row, a window or a clip from that unit's inputs alone in a fixed
@@ -19,15 +19,15 @@
 #include <vector>
 
 #include "../../include/lass_hip.h"
+#include "ctx_parts.h"
 
 namespace {
 
-#include "f32_gemm.h"
+#include "tower_parts.h"
 
 constexpr int kClip = 480000, kFft = 1024, kHop = 480, kFrames = 1001, kBins = 513, kMel = 64, kMelTaps = 32;
-constexpr int kGrid = 64, kWin = 8, kTok = 64, kDh = 32, kEmbed = 128, kProj = 512, kMaxStages = 4;
+constexpr int kGrid = 64, kWin = 8, kTok = 64, kDh = 32, kEmbed = 128, kMaxStages = 4;
 constexpr int kMax32k = 320000, kRsTaps = 16;
-constexpr float kLnEps = 1e-5f;
 constexpr double kBnEps = 1e-5;
 
 // ---- resampler: y[3i + p] = sum_k taps[p][k] x[2i + k - 7], zero outside the clip; rows past a clip's end are zero -------
@@ -101,28 +101,6 @@ __global__ __launch_bounds__(256) void k_logmel(const float* __restrict__ wave, 
             const float scaled = db * bscale[tid];
             out[((size_t)b * kFrames + t) * kMel + tid] = scaled + bbase[tid];
         }
-    }
-}
-
-template <int NPL>  // LayerNorm of a row of 64 * NPL values held as element lane + 64 j
-__device__ __forceinline__ void ln_row(float (&x)[NPL], const float* __restrict__ g, const float* __restrict__ b,
-                                       float* __restrict__ y, int lane) {
-    constexpr float inv = 1.0f / (64 * NPL);
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < NPL; ++j) s += x[j];
-    const float mean = wave_sum(s) * inv;
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < NPL; ++j) {
-        const float d = x[j] - mean;
-        q += d * d;
-    }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) * inv + kLnEps);
-#pragma unroll
-    for (int j = 0; j < NPL; ++j) {
-        const int k = lane + 64 * j;
-        y[k] = (x[j] - mean) * rstd * g[k] + b[k];
     }
 }
 
@@ -293,27 +271,6 @@ __global__ __launch_bounds__(256) void k_token_mean(const float* __restrict__ x,
     y[(size_t)b * C + c] = s / (float)T;
 }
 
-// F.normalize(x, dim=-1): x / max(||x||, 1e-12), one wave per row of 512.
-__global__ __launch_bounds__(256) void k_l2norm(const float* __restrict__ x, int N, float* __restrict__ y) {
-    const int lane = threadIdx.x & 63;
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= N) return;
-    float v[kProj / 64], s = 0.f;
-#pragma unroll
-    for (int j = 0; j < kProj / 64; ++j) {
-        v[j] = x[(size_t)r * kProj + lane + 64 * j];
-        s += v[j] * v[j];
-    }
-    const float inv = 1.0f / fmaxf(sqrtf(wave_sum(s)), 1e-12f);
-#pragma unroll
-    for (int j = 0; j < kProj / 64; ++j) y[(size_t)r * kProj + lane + 64 * j] = v[j] * inv;
-}
-
-struct ARaw {
-    float* d = nullptr;
-    std::vector<int64_t> shape;
-};
-
 struct ABlock {
     const float *g1, *b1, *table, *wqkv, *bqkv, *wo, *bo, *g2, *b2, *w1, *bb1, *w2, *bb2;
 };
@@ -333,8 +290,6 @@ struct AConst {
 };
 
 thread_local std::string g_audioq_create_err;
-
-size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
 const char* kBlockKeys[] = {"norm1.weight", "norm1.bias", "attn.relative_position_bias_table", "attn.qkv.weight", "attn.qkv.bias",
                             "attn.proj.weight", "attn.proj.bias", "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias",
@@ -372,38 +327,16 @@ bool known_key(const std::string& name) {
 struct lass_audioq_ctx {
     int device = 0;
     std::string err;
-    std::map<std::string, ARaw> raw;
+    ParamStore raw;
     bool finalized = false;
     std::vector<AStage> stages;
     int features = 0;
     void* consts = nullptr;
     AConst K{};
-    int* len_host = nullptr;  // pinned staging of the clip lengths and their 48 kHz lengths (2 B ints)
-    size_t len_cap = 0;
-    hipEvent_t len_ev = nullptr;
-    bool len_pending = false;
+    PinnedInts len;  // staging of the clip lengths and their 48 kHz lengths (2 B ints)
 };
 
 namespace {
-
-#define AQ_TRY(ctx, expr)                                                       \
-    do {                                                                        \
-        hipError_t _e = (expr);                                                 \
-        if (_e != hipSuccess) {                                                 \
-            (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(_e);     \
-            return LASS_ERR_HIP;                                                \
-        }                                                                       \
-    } while (0)
-
-int afail(lass_audioq_ctx* c, int code, const std::string& msg) {
-    c->err = msg;
-    return code;
-}
-
-template <int EPI>
-void gemm(const float* X, const float* W, const float* b, float* Y, int M, int N, int K, hipStream_t st) {
-    hipLaunchKernelGGL(k_gemm<EPI>, dim3(N / BN, (M + BM - 1) / BM), dim3(256), 0, st, X, W, b, Y, M, N, K);
-}
 
 void layer_norm(const float* x, float* y, int M, int C, const float* g, const float* b, hipStream_t st) {
     const dim3 grid((M + 3) / 4), blk(256);
@@ -457,7 +390,7 @@ double mel_to_hz(double m) { return m >= 15.0 ? 1000.0 * std::exp(std::log(6.4) 
 int encode48(lass_audioq_ctx* c, const float* wave, int stride, const int* d_len, int B, float* out,
              const lass_audioq_taps* taps, char* ws, const APlan& P, hipStream_t st) {
     const AConst& K = c->K;
-    auto tp = [&](const char* k) { return (const float*)c->raw[k].d; };
+    auto tp = [&](const char* k) { return c->raw.get(k); };
     float* logmel = (float*)(ws + P.logmel);
     float* x = (float*)(ws + P.x);
     float* ln = (float*)(ws + P.ln);
@@ -471,9 +404,9 @@ int encode48(lass_audioq_ctx* c, const float* wave, int stride, const int* d_len
                        tp("audio_branch.patch_embed.proj.weight"), tp("audio_branch.patch_embed.proj.bias"),
                        tp("audio_branch.patch_embed.norm.weight"), tp("audio_branch.patch_embed.norm.bias"), x, rows);
     if (taps && taps->logmel)
-        AQ_TRY(c, hipMemcpyAsync(taps->logmel, logmel, (size_t)B * kFrames * kMel * sizeof(float), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(c, hipMemcpyAsync(taps->logmel, logmel, (size_t)B * kFrames * kMel * sizeof(float), hipMemcpyDeviceToDevice, st));
     if (taps && taps->tokens)
-        AQ_TRY(c, hipMemcpyAsync(taps->tokens, x, (size_t)rows * kEmbed * sizeof(float), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(c, hipMemcpyAsync(taps->tokens, x, (size_t)rows * kEmbed * sizeof(float), hipMemcpyDeviceToDevice, st));
     int res = kGrid, C = kEmbed;
     for (size_t si = 0; si < c->stages.size(); ++si) {
         const AStage& S = c->stages[si];
@@ -499,7 +432,7 @@ int encode48(lass_audioq_ctx* c, const float* wave, int stride, const int* d_len
             C *= 2;
         }
         if (taps && taps->stage[si])
-            AQ_TRY(c, hipMemcpyAsync(taps->stage[si], x, (size_t)rows * C * sizeof(float), hipMemcpyDeviceToDevice, st));
+            HIP_TRY(c, hipMemcpyAsync(taps->stage[si], x, (size_t)rows * C * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
     float* emb = taps && taps->embedding ? taps->embedding : (float*)(ws + P.emb);
     float* p1 = (float*)(ws + P.p1);
@@ -509,7 +442,7 @@ int encode48(lass_audioq_ctx* c, const float* wave, int stride, const int* d_len
     gemm<EPI_RELU>(emb, tp("audio_projection.0.weight"), tp("audio_projection.0.bias"), p1, B, kProj, C, st);
     gemm<EPI_BIAS>(p1, tp("audio_projection.2.weight"), tp("audio_projection.2.bias"), p2, B, kProj, kProj, st);
     hipLaunchKernelGGL(k_l2norm, dim3((B + 3) / 4), dim3(256), 0, st, p2, B, out);
-    AQ_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipGetLastError());
     return LASS_OK;
 }
 
@@ -517,33 +450,25 @@ int encode48(lass_audioq_ctx* c, const float* wave, int stride, const int* d_len
 int begin_encode(lass_audioq_ctx* c, const char* what, const float* wave, const int* lengths, int B, int L, int maxL, float* out,
                  void* ws, size_t ws_bytes, hipStream_t st, int** d_len) {
     const std::string w(what);
-    if (!c->finalized) return afail(c, LASS_ERR_STATE, "lass_audioq_finalize has not been called (or a parameter changed since)");
-    if (!wave || !out || !ws) return afail(c, LASS_ERR_ARG, w + ": wave, out and workspace must be non-NULL");
-    if (B < 1) return afail(c, LASS_ERR_ARG, w + ": B must be >= 1");
-    if (L < 1 || L > maxL) return afail(c, LASS_ERR_ARG, w + ": clips hold 1 .. " + std::to_string(maxL) + " samples (10 s)");
+    if (!c->finalized) return fail(c, LASS_ERR_STATE, "lass_audioq_finalize has not been called (or a parameter changed since)");
+    if (!wave || !out || !ws) return fail(c, LASS_ERR_ARG, w + ": wave, out and workspace must be non-NULL");
+    if (B < 1) return fail(c, LASS_ERR_ARG, w + ": B must be >= 1");
+    if (L < 1 || L > maxL) return fail(c, LASS_ERR_ARG, w + ": clips hold 1 .. " + std::to_string(maxL) + " samples (10 s)");
     if (lengths)
         for (int n = 0; n < B; ++n)
-            if (lengths[n] < 1 || lengths[n] > L) return afail(c, LASS_ERR_ARG, w + ": lengths must lie in [1, L]");
+            if (lengths[n] < 1 || lengths[n] > L) return fail(c, LASS_ERR_ARG, w + ": lengths must lie in [1, L]");
     const APlan P = audio_plan(B);
-    if (ws_bytes < P.total) return afail(c, LASS_ERR_ARG, w + ": workspace too small (lass_audioq_workspace_bytes)");
-    AQ_TRY(c, hipSetDevice(c->device));
-    if (c->len_pending) AQ_TRY(c, hipEventSynchronize(c->len_ev));  // the previous call's upload has read the staging
-    c->len_pending = false;
-    if ((size_t)B > c->len_cap) {
-        if (c->len_host) (void)hipHostFree(c->len_host);
-        c->len_host = nullptr;
-        AQ_TRY(c, hipHostMalloc((void**)&c->len_host, 2 * (size_t)B * sizeof(int), hipHostMallocDefault));
-        c->len_cap = B;
-    }
+    if (ws_bytes < P.total) return fail(c, LASS_ERR_ARG, w + ": workspace too small (lass_audioq_workspace_bytes)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = c->len.reserve(c, 2 * (size_t)B)) return rc;
+    int* len = c->len.host;
     for (int n = 0; n < B; ++n) {
-        c->len_host[n] = lengths ? lengths[n] : L;
-        c->len_host[B + n] = (3 * c->len_host[n] + 1) / 2;
+        len[n] = lengths ? lengths[n] : L;
+        len[B + n] = (3 * len[n] + 1) / 2;
     }
     *d_len = (int*)((char*)ws + P.lens);
-    AQ_TRY(c, hipMemcpyAsync(*d_len, c->len_host, 2 * (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
-    AQ_TRY(c, hipEventRecord(c->len_ev, st));
-    c->len_pending = true;
-    return LASS_OK;
+    HIP_TRY(c, hipMemcpyAsync(*d_len, len, 2 * (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
+    return c->len.record(c, st);
 }
 
 }  // namespace
@@ -553,30 +478,10 @@ extern "C" {
 int lass_audioq_create(lass_audioq_ctx** out, int device_id) {
     if (!out) return LASS_ERR_ARG;
     *out = nullptr;
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) {
-        g_audioq_create_err = std::string("no HIP device available: ") + hipGetErrorString(e) +
-                              " (liblass_hip has no CPU fallback)";
-        return LASS_ERR_HIP;
-    }
-    if (device_id < 0 || device_id >= ndev) {
-        g_audioq_create_err = "device_id out of range";
-        return LASS_ERR_ARG;
-    }
-    hipDeviceProp_t prop;
-    e = hipGetDeviceProperties(&prop, device_id);
-    if (e != hipSuccess) {
-        g_audioq_create_err = std::string("hipGetDeviceProperties: ") + hipGetErrorString(e);
-        return LASS_ERR_HIP;
-    }
-    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0) {
-        g_audioq_create_err = std::string("device is ") + prop.gcnArchName + "; liblass_hip is built for gfx950 only";
-        return LASS_ERR_HIP;
-    }
+    if (int rc = open_device(device_id, g_audioq_create_err)) return rc;
     lass_audioq_ctx* c = new lass_audioq_ctx();
     c->device = device_id;
-    if (hipSetDevice(device_id) != hipSuccess || hipEventCreateWithFlags(&c->len_ev, hipEventDisableTiming) != hipSuccess) {
+    if (hipSetDevice(device_id) != hipSuccess || c->len.create() != hipSuccess) {
         g_audioq_create_err = "hipSetDevice / hipEventCreate failed";
         delete c;
         return LASS_ERR_HIP;
@@ -589,10 +494,9 @@ int lass_audioq_destroy(lass_audioq_ctx* c) {
     if (!c) return LASS_OK;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    for (auto& kv : c->raw) (void)hipFree(kv.second.d);
+    c->raw.free_all();
     if (c->consts) (void)hipFree(c->consts);
-    if (c->len_host) (void)hipHostFree(c->len_host);
-    if (c->len_ev) (void)hipEventDestroy(c->len_ev);
+    c->len.destroy();
     delete c;
     return LASS_OK;
 }
@@ -601,61 +505,51 @@ const char* lass_audioq_last_error(const lass_audioq_ctx* c) { return c ? c->err
 
 int lass_audioq_set_param(lass_audioq_ctx* c, const char* name, const void* data, const int64_t* shape, int ndim) {
     if (!c) return LASS_ERR_ARG;
-    if (!name || !data || !shape || ndim < 1 || ndim > 4) return afail(c, LASS_ERR_ARG, "lass_audioq_set_param: bad arguments");
-    if (!known_key(name)) return afail(c, LASS_ERR_ARG, std::string("unknown audio-tower parameter '") + name + "'");
-    size_t n = 1;
-    for (int i = 0; i < ndim; ++i) {
-        if (shape[i] < 1) return afail(c, LASS_ERR_ARG, std::string(name) + ": empty dimension");
-        n *= (size_t)shape[i];
-    }
-    AQ_TRY(c, hipSetDevice(c->device));
-    ARaw& r = c->raw[name];
-    if (r.d && r.shape != std::vector<int64_t>(shape, shape + ndim)) {
-        (void)hipFree(r.d);
-        r.d = nullptr;
-    }
-    if (!r.d) AQ_TRY(c, hipMalloc(&r.d, n * sizeof(float)));
-    r.shape.assign(shape, shape + ndim);
-    AQ_TRY(c, hipMemcpy(r.d, data, n * sizeof(float), hipMemcpyDefault));
+    if (!name || !data || !shape || ndim < 1 || ndim > 4) return fail(c, LASS_ERR_ARG, "lass_audioq_set_param: bad arguments");
+    if (!known_key(name)) return fail(c, LASS_ERR_ARG, std::string("unknown audio-tower parameter '") + name + "'");
+    for (int i = 0; i < ndim; ++i)
+        if (shape[i] < 1) return fail(c, LASS_ERR_ARG, std::string(name) + ": empty dimension");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = c->raw.put(c, name, data, shape, ndim)) return rc;
     c->finalized = false;
     return LASS_OK;
 }
 
 int lass_audioq_finalize(lass_audioq_ctx* c) {
     if (!c) return LASS_ERR_ARG;
-    AQ_TRY(c, hipSetDevice(c->device));
-    AQ_TRY(c, hipDeviceSynchronize());
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipDeviceSynchronize());
     c->stages.clear();
     c->finalized = false;
     std::string bad;
     // a present key with the expected shape, or nullptr with `bad` set
     auto need = [&](const std::string& k, std::vector<int64_t> shape) -> const float* {
-        auto it = c->raw.find(k);
-        if (it == c->raw.end()) {
+        const Param* p = c->raw.find(k);
+        if (!p) {
             if (bad.empty()) bad = "missing parameter " + k;
             return nullptr;
         }
-        if (it->second.shape != shape) {
+        if (p->shape != shape) {
             std::string s;
             for (int64_t d : shape) s += (s.empty() ? "" : ", ") + std::to_string(d);
             if (bad.empty()) bad = k + ": expected shape (" + s + ")";
             return nullptr;
         }
-        return it->second.d;
+        return p->d;
     };
     int nstage = 0;
     std::vector<int> depth(kMaxStages, 0);
-    for (const auto& kv : c->raw) {
+    for (const auto& kv : c->raw.by_name) {
         int i = -1, j = -1;
         if (kv.first.rfind(kLayers, 0) == 0 && sscanf(kv.first.c_str() + strlen(kLayers), "%d.blocks.%d.", &i, &j) == 2) {
             nstage = std::max(nstage, i + 1);
             depth[i] = std::max(depth[i], j + 1);
         }
     }
-    if (nstage < 1) return afail(c, LASS_ERR_STATE, "no block parameters (audio_branch.layers.<i>.blocks.<j>.*)");
+    if (nstage < 1) return fail(c, LASS_ERR_STATE, "no block parameters (audio_branch.layers.<i>.blocks.<j>.*)");
     int C = kEmbed;
     for (int i = 0; i < nstage; ++i, C *= 2) {
-        if (depth[i] < 1) return afail(c, LASS_ERR_STATE, "missing parameter audio_branch.layers." + std::to_string(i) + ".blocks.0.*");
+        if (depth[i] < 1) return fail(c, LASS_ERR_STATE, "missing parameter audio_branch.layers." + std::to_string(i) + ".blocks.0.*");
         AStage S;
         const int heads = C / kDh;
         for (int j = 0; j < depth[i]; ++j) {
@@ -698,7 +592,7 @@ int lass_audioq_finalize(lass_audioq_ctx* c) {
     need("audio_projection.2.bias", {kProj});
     if (!bad.empty()) {
         c->stages.clear();
-        return afail(c, bad.rfind("missing", 0) == 0 ? LASS_ERR_STATE : LASS_ERR_ARG, bad);
+        return fail(c, bad.rfind("missing", 0) == 0 ? LASS_ERR_STATE : LASS_ERR_ARG, bad);
     }
     c->features = F;
 
@@ -733,7 +627,7 @@ int lass_audioq_finalize(lass_audioq_ctx* c) {
                 const double v = std::max(0.0, std::min((f - edge[m]) / (edge[m + 1] - edge[m]), (edge[m + 2] - f) / (edge[m + 2] - edge[m + 1])));
                 if (v > 0) {
                     if (first < 0) first = k;
-                    if (k - first >= kMelTaps) return afail(c, LASS_ERR_STATE, "mel band wider than its tap run");
+                    if (k - first >= kMelTaps) return fail(c, LASS_ERR_STATE, "mel band wider than its tap run");
                     mw[m * kMelTaps + (k - first)] = (float)(v * 2.0 / (edge[m + 2] - edge[m]));
                     count = k - first + 1;
                 }
@@ -744,12 +638,12 @@ int lass_audioq_finalize(lass_audioq_ctx* c) {
     }
     {   // bn0 (eval) folded to scale / base
         std::vector<float> w(kMel), b(kMel), mu(kMel), var(kMel);
-        AQ_TRY(c, hipMemcpy(w.data(), c->raw["audio_branch.bn0.weight"].d, kMel * sizeof(float), hipMemcpyDeviceToHost));
-        AQ_TRY(c, hipMemcpy(b.data(), c->raw["audio_branch.bn0.bias"].d, kMel * sizeof(float), hipMemcpyDeviceToHost));
-        AQ_TRY(c, hipMemcpy(mu.data(), c->raw["audio_branch.bn0.running_mean"].d, kMel * sizeof(float), hipMemcpyDeviceToHost));
-        AQ_TRY(c, hipMemcpy(var.data(), c->raw["audio_branch.bn0.running_var"].d, kMel * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(w.data(), c->raw.get("audio_branch.bn0.weight"), kMel * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(b.data(), c->raw.get("audio_branch.bn0.bias"), kMel * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(mu.data(), c->raw.get("audio_branch.bn0.running_mean"), kMel * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(var.data(), c->raw.get("audio_branch.bn0.running_var"), kMel * sizeof(float), hipMemcpyDeviceToHost));
         for (int m = 0; m < kMel; ++m) {
-            if (!(var[m] + kBnEps > 0)) return afail(c, LASS_ERR_ARG, "audio_branch.bn0.running_var must be positive");
+            if (!(var[m] + kBnEps > 0)) return fail(c, LASS_ERR_ARG, "audio_branch.bn0.running_var must be positive");
             const double s = (double)w[m] / std::sqrt((double)var[m] + kBnEps);
             bscale[m] = (float)s;
             bbase[m] = (float)((double)b[m] - (double)mu[m] * s);
@@ -773,19 +667,19 @@ int lass_audioq_finalize(lass_audioq_ctx* c) {
     const size_t o_taps = take(taps.size() * 4), o_win = take(win.size() * 4), o_tw = take(twf.size() * 4), o_mw = take(mw.size() * 4),
                  o_ms = take(mstart.size() * 4), o_mc = take(mcount.size() * 4), o_bs = take(bscale.size() * 4),
                  o_bb = take(bbase.size() * 4), o_bi = take(bidx.size() * 4), o_bw = take(bwf.size() * 4), o_zero = take(2048 * 4);
-    AQ_TRY(c, hipMalloc(&c->consts, o));
+    HIP_TRY(c, hipMalloc(&c->consts, o));
     char* d = (char*)c->consts;
-    AQ_TRY(c, hipMemset(d, 0, o));
-    AQ_TRY(c, hipMemcpy(d + o_taps, taps.data(), taps.size() * 4, hipMemcpyHostToDevice));
-    AQ_TRY(c, hipMemcpy(d + o_win, win.data(), win.size() * 4, hipMemcpyHostToDevice));
-    AQ_TRY(c, hipMemcpy(d + o_tw, twf.data(), twf.size() * 4, hipMemcpyHostToDevice));
-    AQ_TRY(c, hipMemcpy(d + o_mw, mw.data(), mw.size() * 4, hipMemcpyHostToDevice));
-    AQ_TRY(c, hipMemcpy(d + o_ms, mstart.data(), mstart.size() * 4, hipMemcpyHostToDevice));
-    AQ_TRY(c, hipMemcpy(d + o_mc, mcount.data(), mcount.size() * 4, hipMemcpyHostToDevice));
-    AQ_TRY(c, hipMemcpy(d + o_bs, bscale.data(), bscale.size() * 4, hipMemcpyHostToDevice));
-    AQ_TRY(c, hipMemcpy(d + o_bb, bbase.data(), bbase.size() * 4, hipMemcpyHostToDevice));
-    AQ_TRY(c, hipMemcpy(d + o_bi, bidx.data(), bidx.size() * 4, hipMemcpyHostToDevice));
-    AQ_TRY(c, hipMemcpy(d + o_bw, bwf.data(), bwf.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemset(d, 0, o));
+    HIP_TRY(c, hipMemcpy(d + o_taps, taps.data(), taps.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d + o_win, win.data(), win.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d + o_tw, twf.data(), twf.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d + o_mw, mw.data(), mw.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d + o_ms, mstart.data(), mstart.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d + o_mc, mcount.data(), mcount.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d + o_bs, bscale.data(), bscale.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d + o_bb, bbase.data(), bbase.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d + o_bi, bidx.data(), bidx.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d + o_bw, bwf.data(), bwf.size() * 4, hipMemcpyHostToDevice));
     c->K.taps = (float*)(d + o_taps);
     c->K.win = (float*)(d + o_win);
     c->K.tw = (float2*)(d + o_tw);
@@ -833,7 +727,7 @@ int lass_audioq_encode_wave32k(lass_audioq_ctx* c, const float* wave, const int*
     int* d_len48 = d_len + B;
     hipLaunchKernelGGL(k_resample32, dim3((L48 + 255) / 256, B), dim3(256), 0, st, wave, L, d_len, c->K.taps, wave48, L48);
     if (taps && taps->wave48k)
-        AQ_TRY(c, hipMemcpyAsync(taps->wave48k, wave48, (size_t)B * L48 * sizeof(float), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(c, hipMemcpyAsync(taps->wave48k, wave48, (size_t)B * L48 * sizeof(float), hipMemcpyDeviceToDevice, st));
     return encode48(c, wave48, L48, d_len48, B, out, taps, ws, P, st);
 }
 

@@ -1,9 +1,9 @@
 // export.hip - planar float32 at the model rate -> a WAV data chunk at the file's rate in one launch: the polyphase FIR of
-// resample.hip (y[n] = sum_m x[m] * h[n*down - m*up + half], zeros outside the plane, the same tap order and fmaf chain, so the
+// polyphase.h (y[n] = sum_m x[m] * h[n*down - m*up + half], zeros outside the plane; resample.hip's tap chain, so the
 // value before quantisation is bit-identical to lass_decode_resample's for that plane), truncation to frames_out, PCM
 // quantisation and channel interleave.  The mirror of resample.hip; DESIGN.md section 16.
 //
-// One workgroup makes `tile` consecutive output frames of one recording.  Beside resample.hip's table and span (the table staged
+// One workgroup makes `tile` consecutive output frames of one recording.  Beside polyphase.h's table and span (the table staged
 // once per workgroup, the span once per channel) it keeps in LDS
 //   stage = the tile's encoded bytes, frame-major and interleaved as they go to memory, at the byte offset (first byte & 3), so
 //           that LDS and global dwords line up.
@@ -14,10 +14,9 @@
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kTileMax = 2048;          // output frames per workgroup (fewer when table + span + stage would not fit in LDS)
+#include "polyphase.h"
+
 constexpr int kTilePlain = 1024;        // k_encode: 1024 frames x 8 channels x 4 bytes = 32 KiB of stage
-constexpr int kLdsFloats = 160 * 256;   // 160 KiB per CU
 
 // wavio.write_wav_pcm16 / write_wav_pcm32 on a float32: y * 2^15 (2^31) is exact, rintf rounds ties to even as numpy.round does,
 // the clip is the writers'.  NaN -> 0.  *clips counts the samples the clip changed.
@@ -89,51 +88,25 @@ __global__ __launch_bounds__(kThreads) void k_resample_encode(const float* __res
                                                               long long out_row_stride, int frames_out,
                                                               unsigned* __restrict__ clipped) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int Jp = J | 1;
-    float* tab = lds;                                     // [up][Jp]
-    float* span = lds + (size_t)up * Jp;                  // [span_floats] = [(up - 1 + (tile - 1) * down) / up + J]
-    unsigned char* stage0 = reinterpret_cast<unsigned char*>(lds + (((size_t)up * Jp + span_floats + 3) & ~(size_t)3));
     const int tid = threadIdx.x;
     const int bps = sample_bytes(enc);
     const float* rec = planes + (size_t)blockIdx.y * row_stride;
-
-    // 64-bit: n*down passes 2^31 on long recordings (16 -> 44.1 kHz: after 304 s)
-    const long long n0 = (long long)blockIdx.x * tile;
-    const long long t0 = n0 * down + (n_taps - 1) / 2;
-    const long long q0 = t0 / up;
-    const unsigned r0 = (unsigned)(t0 - q0 * up);
-    const int nout = (int)(frames_out - n0 < tile ? frames_out - n0 : tile);
-    const int S = (int)((r0 + (unsigned)(nout - 1) * (unsigned)down) / (unsigned)up) + J;
-    const long long mlo = q0 - (J - 1);
-    const size_t a = (size_t)n0 * ch * bps;
+    const FirTile T = fir_tile(lds, up, down, n_taps, J, tile, frames_out);
+    unsigned char* stage0 = reinterpret_cast<unsigned char*>(lds + (((size_t)up * T.Jp + span_floats + 3) & ~(size_t)3));
+    const size_t a = (size_t)T.n0 * ch * bps;
     unsigned char* stage = stage0 + (a & 3);
-
-    // only the last tap of a phase can lie past the filter's end
-    for (int p = tid; p < up; p += kThreads) tab[p * Jp + J - 1] = 0.f;
-    __syncthreads();
-    for (int k = tid; k < n_taps; k += kThreads) tab[(k % up) * Jp + k / up] = taps[k];
+    fir_table(T, taps, n_taps);
 
     unsigned clips = 0;
     for (int c = 0; c < ch; ++c) {
         const float* x0 = rec + (size_t)c * plane_stride;
         if (c) __syncthreads();                           // the previous channel's reads of the span
-        for (int s = tid; s < S; s += kThreads) {
-            const long long m = mlo + s;
-            span[s] = (m >= 0 && m < L_in) ? x0[m] : 0.f;
-        }
+        fir_fill(T, L_in, [&](long long m) { return x0[m]; });
         __syncthreads();
-        for (int i = tid; i < nout; i += kThreads) {
-            const unsigned t = r0 + (unsigned)i * (unsigned)down;
-            const unsigned q = t / (unsigned)up;
-            const float* g = tab + (t - q * (unsigned)up) * Jp;
-            const float* x = span + q + (J - 1);
-            float acc = 0.f;
-            for (int j = 0; j < J; ++j) acc = fmaf(x[-j], g[j], acc);
-            stage_put(stage, i * ch + c, acc, enc, &clips);
-        }
+        for (int i = tid; i < T.nout; i += kThreads) stage_put(stage, i * ch + c, fir_output(T, i), enc, &clips);
     }
     __syncthreads();
-    store_tile(stage0, out + (size_t)blockIdx.y * out_row_stride, a, (size_t)nout * ch * bps, tid);
+    store_tile(stage0, out + (size_t)blockIdx.y * out_row_stride, a, (size_t)T.nout * ch * bps, tid);
     if (clipped && clips) atomicAdd(clipped + blockIdx.y, clips);
 }
 
@@ -151,29 +124,16 @@ hipError_t lass_launch_resample_encode(const float* planes, long long row_stride
                            row_stride, plane_stride, ch, enc, o, out_row_stride, frames_out, clipped);
         return hipGetLastError();
     }
-    const int J = (n_taps + up - 1) / up;
-    const size_t table = lass_resample_table_floats(up, n_taps);
-    if (up > LASS_RESAMPLE_MAX_RATIO || down > LASS_RESAMPLE_MAX_RATIO || n_taps > LASS_RESAMPLE_MAX_TAPS || table > LASS_RESAMPLE_MAX_TABLE)
-        return hipErrorInvalidValue;
     // the largest tile whose span and stage fit beside the table (one frame needs J floats of span and at most 9 of stage: it
-    // always fits under the caps above); the stage starts on a multiple of four floats
-    auto floats_of = [&](int t) {
-        const size_t head = (table + lass_resample_span_floats(up, down, n_taps, t) + 3) & ~(size_t)3;
+    // always fits under the caps); the stage starts on a multiple of four floats
+    FirPlan P;
+    hipError_t e = fir_plan(reinterpret_cast<const void*>(k_resample_encode), up, down, n_taps, frames_out, [&](int t) {
+        const size_t head = (lass_resample_table_floats(up, n_taps) + lass_resample_span_floats(up, down, n_taps, t) + 3) & ~(size_t)3;
         return head + ((size_t)t * ch * bps + 4 + 3) / 4;
-    };
-    int tile = kTileMax;
-    while (tile > 1 && floats_of(tile) > (size_t)kLdsFloats) tile /= 2;
-    const size_t lds = floats_of(tile) * sizeof(float);
-    if (lds > (size_t)kLdsFloats * sizeof(float)) return hipErrorInvalidValue;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_resample_encode),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLdsFloats * (int)sizeof(float));
-        if (e != hipSuccess) return e;
-    }
-    const long long nblk = ((long long)frames_out + tile - 1) / tile;
-    if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_resample_encode, dim3((unsigned)nblk, B), dim3(kThreads), lds, stream, planes, row_stride, plane_stride, L_in,
-                       ch, enc, up, down, taps, n_taps, J, tile, (int)lass_resample_span_floats(up, down, n_taps, tile), o,
+    }, &P);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_resample_encode, dim3(P.nblk, B), dim3(kThreads), P.lds, stream, planes, row_stride, plane_stride, L_in, ch,
+                       enc, up, down, taps, n_taps, P.J, P.tile, (int)lass_resample_span_floats(up, down, n_taps, P.tile), o,
                        out_row_stride, frames_out, clipped);
     return hipGetLastError();
 }

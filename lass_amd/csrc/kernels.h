@@ -281,11 +281,9 @@ hipError_t lass_launch_bnfold(const float* g, const float* beta, const float* me
 // out[n] = sum_m x[m] * taps[n*down - m*up + (n_taps-1)/2].  up == down == 1: no FIR (taps unused).  The caller has checked
 // the arguments (lass_decode_resample); hipErrorInvalidValue for what the kernel's LDS plan cannot hold.
 size_t lass_resample_table_floats(int up, int n_taps);  // the polyphase table in LDS: up * (ceil(n_taps/up) | 1)
+// planar: out (B, ch, L_out) instead, one plane per channel, each bit-identical to the mono call on that channel alone
 hipError_t lass_launch_decode_resample(const void* raw, long long row_stride, int B, int frames, int ch, int enc, int up, int down,
-                                       const float* taps, int n_taps, float* out, int L_out, hipStream_t stream);
-// the same arguments -> out (B, ch, L_out): one plane per channel, each bit-identical to the mono call on that channel alone
-hipError_t lass_launch_decode_resample_planar(const void* raw, long long row_stride, int B, int frames, int ch, int enc, int up,
-                                              int down, const float* taps, int n_taps, float* out, int L_out, hipStream_t stream);
+                                       const float* taps, int n_taps, bool planar, float* out, int L_out, hipStream_t stream);
 size_t lass_resample_span_floats(int up, int down, int n_taps, int tile);  // the input frames `tile` outputs reach, in LDS
 
 // ---- export.hip ---------------------------------------------------------------------------------------------------

@@ -3,26 +3,18 @@
 // librosa.load(path, sr=16000, mono=True) (dcase_evaluator.py:73-74) on files that are not mono at the target rate; DESIGN.md
 // section 12 has the filter, the indexing and what is pinned to what.
 //
-// One workgroup makes `tile` consecutive outputs of one clip.  With t = n*down + half, output n reads the input frames
-// m0 - j (m0 = t / up, j = 0 ... J-1, J = ceil(n_taps / up)) against the taps h[p + j*up] of its phase p = t % up, so the workgroup
-// keeps in LDS
-//   tab[p][j] = h[p + j*up] (0 past the filter's end), row pitch J | 1: the lanes of a wave sit on different phases, and an odd
-//               pitch spreads their rows over the banks; with up == 1 there is one row, which every lane reads at the same j (a
-//               broadcast);
-//   span[s]   = the decoded, down-mixed frame (first frame of the tile's reach) + s, zero outside the clip.
-// Every output is one f32 fmaf chain over j = 0 ... J-1 in that order, whatever the batch, the row stride or the tile it falls in:
-// results are bit-identical per clip.  No atomics.
+// One workgroup makes `tile` consecutive outputs of one clip with the FIR of polyphase.h (the table, the span and the tap chain
+// are there); its span holds the decoded, down-mixed frames of the tile's reach.  Results are bit-identical per clip, whatever the
+// batch, the row stride or the tile an output falls in.  No atomics.
 //
-// k_decode_planar / k_decode_resample_planar are the same two kernels without the down-mix: one output plane per channel, for
-// callers that separate every channel on its own (export.hip is the way back out).
+// The PLANAR instances are the same two kernels without the down-mix: one output plane per channel, for callers that separate
+// every channel on its own (export.hip is the way back out).
 #include "../../include/lass_hip.h"
 #include "kernels.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kTileMax = 2048;          // outputs per workgroup (fewer when the input span would not fit in LDS)
-constexpr int kLdsFloats = 160 * 256;   // 160 KiB per CU
+#include "polyphase.h"
 
 // One frame of the clip as read_wav makes it: x/32768 (PCM16), round-to-nearest int -> float then * 2^-31 (PCM32: equal to
 // read_wav's float64 division rounded once, the scaling being exact), the float itself (float32); channels summed in ascending
@@ -40,110 +32,63 @@ __device__ __forceinline__ float frame_at(const unsigned char* __restrict__ row,
     return __fdiv_rn(s, (float)ch);
 }
 
-// up == down == 1: decode + down-mix only (a stereo or PCM file already at the target rate)
+// Plane c of frame m.  PLANAR: channel c as it stands (out holds ch planes); otherwise the down-mix (one plane, c == 0).  frame_at
+// with one channel IS sample_at, and the tap order and the fmaf chain are polyphase.h's for both, so a planar plane is
+// bit-identical to the mono result of a payload holding that channel alone.
+template <bool PLANAR>
+__device__ __forceinline__ float plane_at(const unsigned char* __restrict__ row, long long m, int c, int ch, int enc) {
+    return PLANAR ? sample_at(row, m * ch + c, enc) : frame_at(row, m, ch, enc);
+}
+
+// up == down == 1: decode (+ down-mix) only (a stereo or PCM file already at the target rate)
+template <bool PLANAR>
 __global__ __launch_bounds__(kThreads) void k_decode(const unsigned char* __restrict__ raw, long long row_stride, int frames,
                                                      int ch, int enc, float* __restrict__ out) {
     const int n = blockIdx.x * kThreads + threadIdx.x;
     if (n >= frames) return;
     const unsigned char* row = raw + (size_t)blockIdx.y * row_stride;
-    out[(size_t)blockIdx.y * frames + n] = frame_at(row, n, ch, enc);
+    const int planes = PLANAR ? ch : 1;
+    float* o = out + (size_t)blockIdx.y * planes * frames + n;
+    for (int c = 0; c < planes; ++c) o[(size_t)c * frames] = plane_at<PLANAR>(row, n, c, ch, enc);
 }
 
+// The table is staged once per workgroup, the span once per plane (one span in LDS whatever the plane count).
+template <bool PLANAR>
 __global__ __launch_bounds__(kThreads) void k_decode_resample(const unsigned char* __restrict__ raw, long long row_stride,
                                                               int frames, int ch, int enc, int up, int down,
                                                               const float* __restrict__ taps, int n_taps, int J, int tile,
                                                               float* __restrict__ out, int L_out) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int Jp = J | 1;
-    float* tab = lds;                        // [up][Jp]
-    float* span = lds + (size_t)up * Jp;     // [(up - 1 + (tile - 1) * down) / up + J]
-    const int tid = threadIdx.x;
     const unsigned char* row = raw + (size_t)blockIdx.y * row_stride;
-
-    // 64-bit: n*down and m*up pass 2^31 on long clips (44.1 -> 16 kHz: after 304 s)
-    const long long n0 = (long long)blockIdx.x * tile;
-    const long long t0 = n0 * down + (n_taps - 1) / 2;
-    const long long q0 = t0 / up;
-    const unsigned r0 = (unsigned)(t0 - q0 * up);
-    const int nout = (int)(L_out - n0 < tile ? L_out - n0 : tile);
-    const int S = (int)((r0 + (unsigned)(nout - 1) * (unsigned)down) / (unsigned)up) + J;
-    const long long mlo = q0 - (J - 1);
-
-    // only the last tap of a phase can lie past the filter's end
-    for (int p = tid; p < up; p += kThreads) tab[p * Jp + J - 1] = 0.f;
-    __syncthreads();
-    for (int k = tid; k < n_taps; k += kThreads) tab[(k % up) * Jp + k / up] = taps[k];
-    for (int s = tid; s < S; s += kThreads) {
-        const long long m = mlo + s;
-        span[s] = (m >= 0 && m < frames) ? frame_at(row, m, ch, enc) : 0.f;
-    }
-    __syncthreads();
-
-    for (int i = tid; i < nout; i += kThreads) {
-        const unsigned t = r0 + (unsigned)i * (unsigned)down;
-        const unsigned q = t / (unsigned)up;
-        const float* g = tab + (t - q * (unsigned)up) * Jp;
-        const float* x = span + q + (J - 1);
-        float acc = 0.f;
-        for (int j = 0; j < J; ++j) acc = fmaf(x[-j], g[j], acc);
-        out[(size_t)blockIdx.y * L_out + n0 + i] = acc;
-    }
-}
-
-// The planar siblings: one plane per channel instead of their average, out (B, ch, L_out).  Plane c is what the kernels above
-// make of a mono payload holding channel c alone - frame_at with one channel IS sample_at, and the tap order and the fmaf chain
-// are theirs - so it is bit-identical to them.
-__global__ __launch_bounds__(kThreads) void k_decode_planar(const unsigned char* __restrict__ raw, long long row_stride, int frames,
-                                                            int ch, int enc, float* __restrict__ out) {
-    const int n = blockIdx.x * kThreads + threadIdx.x;
-    if (n >= frames) return;
-    const unsigned char* row = raw + (size_t)blockIdx.y * row_stride;
-    float* o = out + (size_t)blockIdx.y * ch * frames + n;
-    for (int c = 0; c < ch; ++c) o[(size_t)c * frames] = sample_at(row, (long long)n * ch + c, enc);
-}
-
-// The table is staged once per workgroup, the span once per channel (the same LDS plan as k_decode_resample: one span).
-__global__ __launch_bounds__(kThreads) void k_decode_resample_planar(const unsigned char* __restrict__ raw, long long row_stride,
-                                                                     int frames, int ch, int enc, int up, int down,
-                                                                     const float* __restrict__ taps, int n_taps, int J, int tile,
-                                                                     float* __restrict__ out, int L_out) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int Jp = J | 1;
-    float* tab = lds;                        // [up][Jp]
-    float* span = lds + (size_t)up * Jp;     // [(up - 1 + (tile - 1) * down) / up + J]
-    const int tid = threadIdx.x;
-    const unsigned char* row = raw + (size_t)blockIdx.y * row_stride;
-
-    const long long n0 = (long long)blockIdx.x * tile;
-    const long long t0 = n0 * down + (n_taps - 1) / 2;
-    const long long q0 = t0 / up;
-    const unsigned r0 = (unsigned)(t0 - q0 * up);
-    const int nout = (int)(L_out - n0 < tile ? L_out - n0 : tile);
-    const int S = (int)((r0 + (unsigned)(nout - 1) * (unsigned)down) / (unsigned)up) + J;
-    const long long mlo = q0 - (J - 1);
-
-    for (int p = tid; p < up; p += kThreads) tab[p * Jp + J - 1] = 0.f;
-    __syncthreads();
-    for (int k = tid; k < n_taps; k += kThreads) tab[(k % up) * Jp + k / up] = taps[k];
-
-    for (int c = 0; c < ch; ++c) {
-        if (c) __syncthreads();              // the previous channel's reads of the span
-        for (int s = tid; s < S; s += kThreads) {
-            const long long m = mlo + s;
-            span[s] = (m >= 0 && m < frames) ? sample_at(row, m * ch + c, enc) : 0.f;
-        }
+    const FirTile T = fir_tile(lds, up, down, n_taps, J, tile, L_out);
+    fir_table(T, taps, n_taps);
+    const int planes = PLANAR ? ch : 1;
+    for (int c = 0; c < planes; ++c) {
+        if (c) __syncthreads();              // the previous plane's reads of the span
+        fir_fill(T, frames, [&](long long m) { return plane_at<PLANAR>(row, m, c, ch, enc); });
         __syncthreads();
-        float* o = out + ((size_t)blockIdx.y * ch + c) * L_out + n0;
-        for (int i = tid; i < nout; i += kThreads) {
-            const unsigned t = r0 + (unsigned)i * (unsigned)down;
-            const unsigned q = t / (unsigned)up;
-            const float* g = tab + (t - q * (unsigned)up) * Jp;
-            const float* x = span + q + (J - 1);
-            float acc = 0.f;
-            for (int j = 0; j < J; ++j) acc = fmaf(x[-j], g[j], acc);
-            o[i] = acc;
-        }
+        float* o = out + ((size_t)blockIdx.y * planes + c) * L_out + T.n0;
+        for (int i = threadIdx.x; i < T.nout; i += kThreads) o[i] = fir_output(T, i);
     }
+}
+
+template <bool PLANAR>
+hipError_t launch(const unsigned char* raw, long long row_stride, int B, int frames, int ch, int enc, int up, int down,
+                  const float* taps, int n_taps, float* out, int L_out, hipStream_t stream) {
+    if (up == 1 && down == 1) {
+        hipLaunchKernelGGL(k_decode<PLANAR>, dim3((frames + kThreads - 1) / kThreads, B), dim3(kThreads), 0, stream, raw, row_stride,
+                           frames, ch, enc, out);
+        return hipGetLastError();
+    }
+    // the largest tile whose input span fits beside the table (one output needs J frames: always fits under the caps)
+    FirPlan P;
+    hipError_t e = fir_plan(reinterpret_cast<const void*>(k_decode_resample<PLANAR>), up, down, n_taps, L_out, [&](int t) {
+        return lass_resample_table_floats(up, n_taps) + lass_resample_span_floats(up, down, n_taps, t);
+    }, &P);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_decode_resample<PLANAR>, dim3(P.nblk, B), dim3(kThreads), P.lds, stream, raw, row_stride, frames, ch, enc,
+                       up, down, taps, n_taps, P.J, P.tile, out, L_out);
+    return hipGetLastError();
 }
 
 }  // namespace
@@ -158,63 +103,10 @@ size_t lass_resample_span_floats(int up, int down, int n_taps, int tile) {
     return ((size_t)(up - 1) + (size_t)(tile - 1) * down) / up + J;
 }
 
-hipError_t lass_launch_decode_resample_planar(const void* raw, long long row_stride, int B, int frames, int ch, int enc, int up,
-                                              int down, const float* taps, int n_taps, float* out, int L_out, hipStream_t stream) {
+hipError_t lass_launch_decode_resample(const void* raw, long long row_stride, int B, int frames, int ch, int enc, int up, int down,
+                                       const float* taps, int n_taps, bool planar, float* out, int L_out, hipStream_t stream) {
     if (B <= 0 || B > 65535 || frames <= 0 || L_out <= 0 || up < 1 || down < 1 || ch < 1) return hipErrorInvalidValue;
     const unsigned char* r = static_cast<const unsigned char*>(raw);
-    if (up == 1 && down == 1) {
-        hipLaunchKernelGGL(k_decode_planar, dim3((frames + kThreads - 1) / kThreads, B), dim3(kThreads), 0, stream, r, row_stride,
-                           frames, ch, enc, out);
-        return hipGetLastError();
-    }
-    const int J = (n_taps + up - 1) / up;
-    const size_t table = lass_resample_table_floats(up, n_taps);
-    if (up > LASS_RESAMPLE_MAX_RATIO || down > LASS_RESAMPLE_MAX_RATIO || n_taps > LASS_RESAMPLE_MAX_TAPS || table > LASS_RESAMPLE_MAX_TABLE)
-        return hipErrorInvalidValue;
-    // k_decode_resample's plan: the largest tile whose input span fits beside the table
-    int tile = kTileMax;
-    while (tile > 1 && table + lass_resample_span_floats(up, down, n_taps, tile) > (size_t)kLdsFloats) tile /= 2;
-    const size_t lds = (table + lass_resample_span_floats(up, down, n_taps, tile)) * sizeof(float);
-    if (lds > (size_t)kLdsFloats * sizeof(float)) return hipErrorInvalidValue;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_decode_resample_planar),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLdsFloats * (int)sizeof(float));
-        if (e != hipSuccess) return e;
-    }
-    const long long nblk = ((long long)L_out + tile - 1) / tile;
-    if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_decode_resample_planar, dim3((unsigned)nblk, B), dim3(kThreads), lds, stream, r, row_stride, frames, ch, enc,
-                       up, down, taps, n_taps, J, tile, out, L_out);
-    return hipGetLastError();
-}
-
-hipError_t lass_launch_decode_resample(const void* raw, long long row_stride, int B, int frames, int ch, int enc, int up, int down,
-                                       const float* taps, int n_taps, float* out, int L_out, hipStream_t stream) {
-    if (B <= 0 || B > 65535 || frames <= 0 || L_out <= 0 || up < 1 || down < 1) return hipErrorInvalidValue;
-    const unsigned char* r = static_cast<const unsigned char*>(raw);
-    if (up == 1 && down == 1) {
-        hipLaunchKernelGGL(k_decode, dim3((frames + kThreads - 1) / kThreads, B), dim3(kThreads), 0, stream, r, row_stride, frames,
-                           ch, enc, out);
-        return hipGetLastError();
-    }
-    const int J = (n_taps + up - 1) / up;
-    const size_t table = lass_resample_table_floats(up, n_taps);
-    if (up > LASS_RESAMPLE_MAX_RATIO || down > LASS_RESAMPLE_MAX_RATIO || n_taps > LASS_RESAMPLE_MAX_TAPS || table > LASS_RESAMPLE_MAX_TABLE)
-        return hipErrorInvalidValue;
-    // the largest tile whose input span fits beside the table (one output needs J frames: always fits under the caps above)
-    int tile = kTileMax;
-    auto span_of = [&](int t) { return ((size_t)(up - 1) + (size_t)(t - 1) * down) / up + J; };
-    while (tile > 1 && table + span_of(tile) > (size_t)kLdsFloats) tile /= 2;
-    const size_t lds = (table + span_of(tile)) * sizeof(float);
-    if (lds > (size_t)kLdsFloats * sizeof(float)) return hipErrorInvalidValue;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_decode_resample),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLdsFloats * (int)sizeof(float));
-        if (e != hipSuccess) return e;
-    }
-    const long long nblk = ((long long)L_out + tile - 1) / tile;
-    if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_decode_resample, dim3((unsigned)nblk, B), dim3(kThreads), lds, stream, r, row_stride, frames, ch, enc, up,
-                       down, taps, n_taps, J, tile, out, L_out);
-    return hipGetLastError();
+    return planar ? launch<true>(r, row_stride, B, frames, ch, enc, up, down, taps, n_taps, out, L_out, stream)
+                  : launch<false>(r, row_stride, B, frames, ch, enc, up, down, taps, n_taps, out, L_out, stream);
 }

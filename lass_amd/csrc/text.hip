@@ -22,39 +22,18 @@
 #include <vector>
 
 #include "../../include/lass_hip.h"
+#include "ctx_parts.h"
 
 namespace {
 
-constexpr int kHid = 768, kHeads = 12, kDh = 64, kFF = 3072, kProj = 512, kMaxLen = 512, kPad = 1;
-constexpr float kLnEps = 1e-5f;  // roberta-base config.json layer_norm_eps (HF RobertaConfig() defaults to 1e-12)
+constexpr int kHid = 768, kHeads = 12, kDh = 64, kFF = 3072, kMaxLen = 512, kPad = 1;
 
-#include "f32_gemm.h"
+#include "tower_parts.h"
 
 __device__ __forceinline__ int wave_isum(int v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
-}
-
-// LayerNorm of one 768-wide row held as 12 values per lane (element lane + 64 j), written to y.
-__device__ __forceinline__ void ln_row(float (&x)[12], const float* __restrict__ g, const float* __restrict__ b,
-                                       float* __restrict__ y, int lane) {
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < 12; ++j) s += x[j];
-    const float mean = wave_sum(s) * (1.0f / kHid);
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < 12; ++j) {
-        const float d = x[j] - mean;
-        q += d * d;
-    }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) * (1.0f / kHid) + kLnEps);
-#pragma unroll
-    for (int j = 0; j < 12; ++j) {
-        const int k = lane + 64 * j;
-        y[k] = (x[j] - mean) * rstd * g[k] + b[k];
-    }
 }
 
 // Embeddings (RobertaEmbeddings.forward): word[id] + token_type[0] + position[pos], then LayerNorm.  One wave per packed
@@ -82,7 +61,7 @@ __global__ __launch_bounds__(256) void k_embed_ln(const int64_t* __restrict__ id
         const int k = lane + 64 * j;
         x[j] = (we[(size_t)id * kHid + k] + te[k]) + pe[(size_t)pos * kHid + k];
     }
-    ln_row(x, g, b, h + (size_t)r * kHid, lane);
+    ln_row<12>(x, g, b, h + (size_t)r * kHid, lane);
 }
 
 // In-place LayerNorm of M rows of 768 (the residual sum was added by the GEMM epilogue).
@@ -95,7 +74,7 @@ __global__ __launch_bounds__(256) void k_ln(float* __restrict__ h, int M, const 
     float x[12];
 #pragma unroll
     for (int j = 0; j < 12; ++j) x[j] = row[lane + 64 * j];
-    ln_row(x, g, b, row, lane);
+    ln_row<12>(x, g, b, row, lane);
 }
 
 constexpr int AQ = 64;  // queries per workgroup (one per lane) and keys per LDS block
@@ -192,27 +171,6 @@ __global__ __launch_bounds__(256) void k_gather_cls(const float* __restrict__ h,
     for (int k = threadIdx.x; k < kHid; k += 256) cls[(size_t)n * kHid + k] = row[k];
 }
 
-// F.normalize(x, dim=-1): x / max(||x||, 1e-12), one wave per row of 512.
-__global__ __launch_bounds__(256) void k_l2norm(const float* __restrict__ x, int N, float* __restrict__ y) {
-    const int lane = threadIdx.x & 63;
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= N) return;
-    float v[kProj / 64], s = 0.f;
-#pragma unroll
-    for (int j = 0; j < kProj / 64; ++j) {
-        v[j] = x[(size_t)r * kProj + lane + 64 * j];
-        s += v[j] * v[j];
-    }
-    const float inv = 1.0f / fmaxf(sqrtf(wave_sum(s)), 1e-12f);
-#pragma unroll
-    for (int j = 0; j < kProj / 64; ++j) y[(size_t)r * kProj + lane + 64 * j] = v[j] * inv;
-}
-
-struct TRaw {
-    float* d = nullptr;
-    std::vector<int64_t> shape;
-};
-
 struct TLayer {
     float *wqkv = nullptr, *bqkv = nullptr;  // fused (2304, 768) / (2304): query, key, value rows in that order
     const float *wo, *bo, *g1, *b1, *wi, *bi, *w2, *b2, *g2, *b22;
@@ -240,44 +198,22 @@ const char* kLayerPrefix = "text_branch.encoder.layer.";
 
 thread_local std::string g_text_create_err;
 
-size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-
 }  // namespace
 
 struct lass_text_ctx {
     int device = 0;
     std::string err;
-    std::map<std::string, TRaw> raw;
+    ParamStore raw;
     bool finalized = false;
     int vocab = 0, npos = 0;
     std::vector<TLayer> layers;
     std::vector<void*> owned;  // fused QKV buffers
-    int* plan_host = nullptr;  // pinned staging of the packed-row plan
-    size_t plan_cap = 0;       // ints
-    hipEvent_t plan_ev = nullptr;
-    bool plan_pending = false;
+    PinnedInts plan;  // staging of the packed-row plan
 };
 
 namespace {
 
-#define TEXT_TRY(ctx, expr)                                                     \
-    do {                                                                        \
-        hipError_t _e = (expr);                                                 \
-        if (_e != hipSuccess) {                                                 \
-            (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(_e);     \
-            return LASS_ERR_HIP;                                                \
-        }                                                                       \
-    } while (0)
-
-int tfail(lass_text_ctx* c, int code, const std::string& msg) {
-    c->err = msg;
-    return code;
-}
-
-const float* tp(const lass_text_ctx* c, const std::string& k) {
-    auto it = c->raw.find(k);
-    return it == c->raw.end() ? nullptr : it->second.d;
-}
+const float* tp(const lass_text_ctx* c, const std::string& k) { return c->raw.get(k); }
 
 // Expected shape of a key, or false if the name is not a text-tower parameter.  Vocabulary and position-table sizes
 // come from the tensors themselves; layer indices from the names.
@@ -313,11 +249,6 @@ bool expected_shape(const std::string& name, const int64_t* shape, int ndim, std
     return false;
 }
 
-template <int EPI>
-void gemm(const float* X, const float* W, const float* b, float* Y, int M, int N, int K, hipStream_t st) {
-    hipLaunchKernelGGL(k_gemm<EPI>, dim3(N / BN, (M + BM - 1) / BM), dim3(256), 0, st, X, W, b, Y, M, N, K);
-}
-
 struct TPlan {  // workspace carve-up for (N, S): everything sized for M = N*S rows, the packed batch uses the first M_real
     size_t src, cap, h, qkv, attn, ffn, cls, pool, p1, p2, total;
 };
@@ -348,30 +279,10 @@ extern "C" {
 int lass_text_create(lass_text_ctx** out, int device_id) {
     if (!out) return LASS_ERR_ARG;
     *out = nullptr;
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) {
-        g_text_create_err = std::string("no HIP device available: ") + hipGetErrorString(e) +
-                            " (liblass_hip has no CPU fallback)";
-        return LASS_ERR_HIP;
-    }
-    if (device_id < 0 || device_id >= ndev) {
-        g_text_create_err = "device_id out of range";
-        return LASS_ERR_ARG;
-    }
-    hipDeviceProp_t prop;
-    e = hipGetDeviceProperties(&prop, device_id);
-    if (e != hipSuccess) {
-        g_text_create_err = std::string("hipGetDeviceProperties: ") + hipGetErrorString(e);
-        return LASS_ERR_HIP;
-    }
-    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0) {
-        g_text_create_err = std::string("device is ") + prop.gcnArchName + "; liblass_hip is built for gfx950 only";
-        return LASS_ERR_HIP;
-    }
+    if (int rc = open_device(device_id, g_text_create_err)) return rc;
     lass_text_ctx* c = new lass_text_ctx();
     c->device = device_id;
-    if (hipSetDevice(device_id) != hipSuccess || hipEventCreateWithFlags(&c->plan_ev, hipEventDisableTiming) != hipSuccess) {
+    if (hipSetDevice(device_id) != hipSuccess || c->plan.create() != hipSuccess) {
         g_text_create_err = "hipSetDevice / hipEventCreate failed";
         delete c;
         return LASS_ERR_HIP;
@@ -384,10 +295,9 @@ int lass_text_destroy(lass_text_ctx* c) {
     if (!c) return LASS_OK;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    for (auto& kv : c->raw) (void)hipFree(kv.second.d);
+    c->raw.free_all();
     for (void* p : c->owned) (void)hipFree(p);
-    if (c->plan_host) (void)hipHostFree(c->plan_host);
-    if (c->plan_ev) (void)hipEventDestroy(c->plan_ev);
+    c->plan.destroy();
     delete c;
     return LASS_OK;
 }
@@ -396,61 +306,52 @@ const char* lass_text_last_error(const lass_text_ctx* c) { return c ? c->err.c_s
 
 int lass_text_set_param(lass_text_ctx* c, const char* name, const void* data, const int64_t* shape, int ndim) {
     if (!c) return LASS_ERR_ARG;
-    if (!name || !data || !shape || ndim < 1 || ndim > 2) return tfail(c, LASS_ERR_ARG, "lass_text_set_param: bad arguments");
+    if (!name || !data || !shape || ndim < 1 || ndim > 2) return fail(c, LASS_ERR_ARG, "lass_text_set_param: bad arguments");
     std::string why;
-    if (!expected_shape(name, shape, ndim, why)) return tfail(c, LASS_ERR_ARG, why);
-    TEXT_TRY(c, hipSetDevice(c->device));
-    size_t n = 1;
-    for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
-    TRaw& r = c->raw[name];
-    if (r.d && r.shape != std::vector<int64_t>(shape, shape + ndim)) {
-        (void)hipFree(r.d);
-        r.d = nullptr;
-    }
-    if (!r.d) TEXT_TRY(c, hipMalloc(&r.d, n * sizeof(float)));
-    r.shape.assign(shape, shape + ndim);
-    TEXT_TRY(c, hipMemcpy(r.d, data, n * sizeof(float), hipMemcpyDefault));
+    if (!expected_shape(name, shape, ndim, why)) return fail(c, LASS_ERR_ARG, why);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = c->raw.put(c, name, data, shape, ndim)) return rc;
     c->finalized = false;
     return LASS_OK;
 }
 
 int lass_text_finalize(lass_text_ctx* c) {
     if (!c) return LASS_ERR_ARG;
-    TEXT_TRY(c, hipSetDevice(c->device));
-    TEXT_TRY(c, hipDeviceSynchronize());
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipDeviceSynchronize());
     for (void* p : c->owned) (void)hipFree(p);
     c->owned.clear();
     c->layers.clear();
     c->finalized = false;
     for (const char* k : {"text_branch.embeddings.word_embeddings.weight", "text_branch.embeddings.position_embeddings.weight",
                           "text_branch.embeddings.token_type_embeddings.weight"})
-        if (!tp(c, k)) return tfail(c, LASS_ERR_STATE, std::string("missing parameter ") + k);
+        if (!tp(c, k)) return fail(c, LASS_ERR_STATE, std::string("missing parameter ") + k);
     for (const auto& k : kFixedKeys)
-        if (!tp(c, k.name)) return tfail(c, LASS_ERR_STATE, std::string("missing parameter ") + k.name);
-    c->vocab = (int)c->raw["text_branch.embeddings.word_embeddings.weight"].shape[0];
-    c->npos = (int)c->raw["text_branch.embeddings.position_embeddings.weight"].shape[0];
-    if (c->npos < 3) return tfail(c, LASS_ERR_ARG, "position_embeddings needs at least 3 rows");
+        if (!tp(c, k.name)) return fail(c, LASS_ERR_STATE, std::string("missing parameter ") + k.name);
+    c->vocab = (int)c->raw.by_name["text_branch.embeddings.word_embeddings.weight"].shape[0];
+    c->npos = (int)c->raw.by_name["text_branch.embeddings.position_embeddings.weight"].shape[0];
+    if (c->npos < 3) return fail(c, LASS_ERR_ARG, "position_embeddings needs at least 3 rows");
     // layer count = number of distinct layer indices; they must be 0 .. L-1, each complete
     int nl = 0;
-    for (const auto& kv : c->raw)
+    for (const auto& kv : c->raw.by_name)
         if (kv.first.rfind(kLayerPrefix, 0) == 0) nl = std::max(nl, atoi(kv.first.c_str() + strlen(kLayerPrefix)) + 1);
-    if (nl < 1) return tfail(c, LASS_ERR_STATE, "no encoder layer parameters (text_branch.encoder.layer.<i>.*)");
+    if (nl < 1) return fail(c, LASS_ERR_STATE, "no encoder layer parameters (text_branch.encoder.layer.<i>.*)");
     for (int l = 0; l < nl; ++l) {
         const std::string pre = kLayerPrefix + std::to_string(l) + ".";
         const float* p[16];
         for (int i = 0; i < 16; ++i) {
             p[i] = tp(c, pre + kLayerKeys[i].name);
-            if (!p[i]) return tfail(c, LASS_ERR_STATE, "missing parameter " + pre + kLayerKeys[i].name);
+            if (!p[i]) return fail(c, LASS_ERR_STATE, "missing parameter " + pre + kLayerKeys[i].name);
         }
         TLayer L;
-        TEXT_TRY(c, hipMalloc(&L.wqkv, (size_t)3 * kHid * kHid * sizeof(float)));
+        HIP_TRY(c, hipMalloc(&L.wqkv, (size_t)3 * kHid * kHid * sizeof(float)));
         c->owned.push_back(L.wqkv);
-        TEXT_TRY(c, hipMalloc(&L.bqkv, (size_t)3 * kHid * sizeof(float)));
+        HIP_TRY(c, hipMalloc(&L.bqkv, (size_t)3 * kHid * sizeof(float)));
         c->owned.push_back(L.bqkv);
         for (int j = 0; j < 3; ++j) {
-            TEXT_TRY(c, hipMemcpy(L.wqkv + (size_t)j * kHid * kHid, p[2 * j], (size_t)kHid * kHid * sizeof(float),
+            HIP_TRY(c, hipMemcpy(L.wqkv + (size_t)j * kHid * kHid, p[2 * j], (size_t)kHid * kHid * sizeof(float),
                                   hipMemcpyDeviceToDevice));
-            TEXT_TRY(c, hipMemcpy(L.bqkv + j * kHid, p[2 * j + 1], kHid * sizeof(float), hipMemcpyDeviceToDevice));
+            HIP_TRY(c, hipMemcpy(L.bqkv + j * kHid, p[2 * j + 1], kHid * sizeof(float), hipMemcpyDeviceToDevice));
         }
         L.wo = p[6]; L.bo = p[7]; L.g1 = p[8]; L.b1 = p[9];
         L.wi = p[10]; L.bi = p[11]; L.w2 = p[12]; L.b2 = p[13]; L.g2 = p[14]; L.b22 = p[15];
@@ -471,31 +372,23 @@ int lass_text_workspace_bytes(const lass_text_ctx* c, int N, int S, size_t* byte
 int lass_text_encode(lass_text_ctx* c, const int64_t* input_ids, const int64_t* attention_mask, int N, int S, float* out,
                      float* pooler_out, void* workspace, size_t workspace_bytes, void* stream) {
     if (!c) return LASS_ERR_ARG;
-    if (!c->finalized) return tfail(c, LASS_ERR_STATE, "lass_text_finalize has not been called (or a parameter changed since)");
+    if (!c->finalized) return fail(c, LASS_ERR_STATE, "lass_text_finalize has not been called (or a parameter changed since)");
     if (!input_ids || !attention_mask || !out || !workspace || N < 1 || S < 1 || S > kMaxLen)
-        return tfail(c, LASS_ERR_ARG, "lass_text_encode: bad arguments (N >= 1, 1 <= S <= 512, non-NULL buffers)");
-    if (S + 1 >= c->npos) return tfail(c, LASS_ERR_ARG, "S too long for the position table (needs S + 2 rows)");
+        return fail(c, LASS_ERR_ARG, "lass_text_encode: bad arguments (N >= 1, 1 <= S <= 512, non-NULL buffers)");
+    if (S + 1 >= c->npos) return fail(c, LASS_ERR_ARG, "S too long for the position table (needs S + 2 rows)");
     const TPlan P = text_plan(N, S);
-    if (workspace_bytes < P.total) return tfail(c, LASS_ERR_ARG, "workspace too small (lass_text_workspace_bytes)");
-    TEXT_TRY(c, hipSetDevice(c->device));
+    if (workspace_bytes < P.total) return fail(c, LASS_ERR_ARG, "workspace too small (lass_text_workspace_bytes)");
+    HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
     // packed-row plan from the host mask: src[r] = n*S + s for every real token, cap_off[n] = first row of caption n
-    const size_t need = (size_t)N * S + N + 1;
-    if (c->plan_pending) TEXT_TRY(c, hipEventSynchronize(c->plan_ev));  // the previous call's upload has read the staging
-    c->plan_pending = false;
-    if (need > c->plan_cap) {
-        if (c->plan_host) (void)hipHostFree(c->plan_host);
-        c->plan_host = nullptr;
-        TEXT_TRY(c, hipHostMalloc((void**)&c->plan_host, need * sizeof(int), hipHostMallocDefault));
-        c->plan_cap = need;
-    }
-    int* src = c->plan_host;
-    int* cap = c->plan_host + (size_t)N * S;
+    if (int rc = c->plan.reserve(c, (size_t)N * S + N + 1)) return rc;
+    int* src = c->plan.host;
+    int* cap = c->plan.host + (size_t)N * S;
     int M = 0, maxlen = 0;
     for (int n = 0; n < N; ++n) {
         cap[n] = M;
         if (attention_mask[(size_t)n * S] == 0)
-            return tfail(c, LASS_ERR_ARG, "attention_mask[:, 0] must be 1 (the <s> token of every caption is real)");
+            return fail(c, LASS_ERR_ARG, "attention_mask[:, 0] must be 1 (the <s> token of every caption is real)");
         for (int s = 0; s < S; ++s)
             if (attention_mask[(size_t)n * S + s] != 0) src[M++] = n * S + s;
         maxlen = std::max(maxlen, M - cap[n]);
@@ -504,10 +397,9 @@ int lass_text_encode(lass_text_ctx* c, const int64_t* input_ids, const int64_t* 
     char* ws = (char*)workspace;
     int* d_src = (int*)(ws + P.src);
     int* d_cap = (int*)(ws + P.cap);
-    TEXT_TRY(c, hipMemcpyAsync(d_src, src, (size_t)M * sizeof(int), hipMemcpyHostToDevice, st));
-    TEXT_TRY(c, hipMemcpyAsync(d_cap, cap, (N + 1) * sizeof(int), hipMemcpyHostToDevice, st));
-    TEXT_TRY(c, hipEventRecord(c->plan_ev, st));
-    c->plan_pending = true;
+    HIP_TRY(c, hipMemcpyAsync(d_src, src, (size_t)M * sizeof(int), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(d_cap, cap, (N + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+    if (int rc = c->plan.record(c, st)) return rc;
 
     float* h = (float*)(ws + P.h);
     float* qkv = (float*)(ws + P.qkv);
@@ -537,7 +429,7 @@ int lass_text_encode(lass_text_ctx* c, const int64_t* input_ids, const int64_t* 
     gemm<EPI_RELU>(pool, tp(c, "text_projection.0.weight"), tp(c, "text_projection.0.bias"), p1, N, kProj, kHid, st);
     gemm<EPI_BIAS>(p1, tp(c, "text_projection.2.weight"), tp(c, "text_projection.2.bias"), p2, N, kProj, kProj, st);
     hipLaunchKernelGGL(k_l2norm, dim3((N + 3) / 4), dim3(256), 0, st, p2, N, out);
-    TEXT_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipGetLastError());
     return LASS_OK;
 }
 

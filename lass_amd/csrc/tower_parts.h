@@ -1,8 +1,12 @@
-// f32_gemm.h - the exact-f32 MFMA GEMM of the CLAP towers (text.hip, audio_clap.hip), shared by inclusion so that both
-// translation units compile the same kernel text.  Include inside an anonymous namespace, after <hip/hip_runtime.h>.
+// tower_parts.h - the device parts the CLAP towers (text.hip, audio_clap.hip) share: the exact-f32 MFMA GEMM and its launcher, the
+// row LayerNorm and the final L2 normalisation.  Shared by inclusion so that both translation units compile the same kernel
+// text.  Include inside an anonymous namespace, after <hip/hip_runtime.h>.
 #pragma once
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int kProj = 512;       // width of the joint embedding both towers project to
+constexpr float kLnEps = 1e-5f;  // roberta-base config.json layer_norm_eps (HF RobertaConfig() defaults to 1e-12); HTSAT: nn.LayerNorm's default
 
 __device__ __forceinline__ float wave_sum(float v) {
     // xor butterfly: every lane ends with the same bits
@@ -72,4 +76,47 @@ __global__ __launch_bounds__(256) void k_gemm(const float* __restrict__ X, const
         if (EPI == EPI_RELU) v = fmaxf(v, 0.f);
         *yp = v;
     }
+}
+
+template <int EPI>
+void gemm(const float* X, const float* W, const float* b, float* Y, int M, int N, int K, hipStream_t st) {
+    hipLaunchKernelGGL(k_gemm<EPI>, dim3(N / BN, (M + BM - 1) / BM), dim3(256), 0, st, X, W, b, Y, M, N, K);
+}
+
+template <int NPL>  // LayerNorm of a row of 64 * NPL values held as element lane + 64 j, written to y
+__device__ __forceinline__ void ln_row(float (&x)[NPL], const float* __restrict__ g, const float* __restrict__ b,
+                                       float* __restrict__ y, int lane) {
+    constexpr float inv = 1.0f / (64 * NPL);
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < NPL; ++j) s += x[j];
+    const float mean = wave_sum(s) * inv;
+    float q = 0.f;
+#pragma unroll
+    for (int j = 0; j < NPL; ++j) {
+        const float d = x[j] - mean;
+        q += d * d;
+    }
+    const float rstd = 1.0f / sqrtf(wave_sum(q) * inv + kLnEps);
+#pragma unroll
+    for (int j = 0; j < NPL; ++j) {
+        const int k = lane + 64 * j;
+        y[k] = (x[j] - mean) * rstd * g[k] + b[k];
+    }
+}
+
+// F.normalize(x, dim=-1): x / max(||x||, 1e-12), one wave per row of 512.
+__global__ __launch_bounds__(256) void k_l2norm(const float* __restrict__ x, int N, float* __restrict__ y) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= N) return;
+    float v[kProj / 64], s = 0.f;
+#pragma unroll
+    for (int j = 0; j < kProj / 64; ++j) {
+        v[j] = x[(size_t)r * kProj + lane + 64 * j];
+        s += v[j] * v[j];
+    }
+    const float inv = 1.0f / fmaxf(sqrtf(wave_sum(s)), 1e-12f);
+#pragma unroll
+    for (int j = 0; j < kProj / 64; ++j) y[(size_t)r * kProj + lane + 64 * j] = v[j] * inv;
 }
