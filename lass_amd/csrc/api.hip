@@ -19,6 +19,7 @@
 #include "graph_cache.h"
 #include "head_fold.h"
 #include "kernels.h"
+#include "weight_plan.h"
 #include "workspace_plan.h"
 
 namespace {
@@ -38,16 +39,7 @@ struct ResBlock {  // one ConvBlockRes
     int cin = 0, cout = 0;
     int width = 0;         // bins of the level the block runs at (fcrop >> level): known at finalize, the frame count is not
     int s1 = -1, s2 = -1;  // site indices
-    float *w1 = nullptr, *w2 = nullptr, *wsc = nullptr;  // re-laid-out
-    float *u1 = nullptr, *u2 = nullptr, *usc = nullptr;  // Winograd-domain copies (f32 mode)
-    float *u1f = nullptr, *u2f = nullptr;                   // conv1 / conv2 in the F(4x4,3x3) domain (wino4.hip), deep-K blocks
-    void *b1 = nullptr, *b2 = nullptr, *bsc16 = nullptr;  // bf16 copies (LASS_COMPUTE_BF16 / _BF16X3)
-    void *b1l = nullptr, *b2l = nullptr, *bscl = nullptr;  // lo halves of the hi+lo split (LASS_COMPUTE_BF16X3)
-    const float* bsc = nullptr;                         // raw shortcut bias
-    // decoder_block6, f32: conv2 and the shortcut composed with after_conv (head_fold.h) - U images, Wsc' [cin][16], b' [16]
-    float *u2h = nullptr, *wsch = nullptr, *bh = nullptr;
-    void* wsc3 = nullptr;  // f32: wsc as the three bf16 pieces of pw_gemm.hip's split kernel (the shortcut-GEMM layers)
-    void *u1g = nullptr, *u2g = nullptr;  // f32: u1f / u2f as the three bf16 pieces of wino4_gemm.hip's GEMMs (conv_route.h: lass_wino4_gemm_weights)
+    WeightImages img;      // the block slots of weight_plan.h, as lass_finalize made them
 };
 
 struct ProfEntry {
@@ -76,16 +68,14 @@ struct lass_ctx {
     float *bn0_s = nullptr, *bn0_h = nullptr;
     std::vector<ResBlock> enc, dec;  // enc: nbr branch blocks (encoder_block1[s]) then the 6 trunk blocks; dec: 6
     int dec_site[6] = {0};           // decoder_blockN->beta1
-    void* up16[6] = {nullptr};       // bf16 transposed-conv weights (hi) per decoder, bf16 modes only
-    void* up16l[6] = {nullptr};      // lo halves (LASS_COMPUTE_BF16X3)
-    void* up3[6] = {nullptr};        // f32: the transposed-conv weights as the three bf16 pieces of pw_gemm.hip's split kernel
+    WeightImages up_img[6], img;     // the decoder slots of weight_plan.h per transposed conv, and the context's (lass_finalize)
+    int head_rows = 0;               // rows of after_conv as lass_finalize saw them: the Q of weight_plan.h's head rules
     std::vector<void*> owned;        // derived device buffers to free
     // the compute mode (lass_finalize) and every switch a route depends on, as the value conv_route.h's rules read: LASS_WINO4,
     // lass_set_wino4_splits, lass_set_wino4_vprep / LASS_WINO4_VPREP, lass_set_head_fold / LASS_HEAD_FOLD, lass_set_head_sc_fold /
     // LASS_HEAD_SC_FOLD, lass_set_pw_split / LASS_PW_SPLIT, LASS_FUSE_CATB / _BLOCK / _UP
     RouteCfg cfg;
-    float *hs_wt = nullptr, *hs_wskip = nullptr;  // head_fold.h: Wt' [cin][64] for that transposed conv, Wsc'_skip [3][32] (lass_finalize)
-    float* stage_v = nullptr;      // ... their V image in the stage calls, grown on demand like stage_part (Plan::vprep in lass_separate)
+    float* stage_v = nullptr;      // the V image of the V-from-memory layers in the stage calls, grown on demand like stage_part (Plan::vprep in lass_separate)
     size_t stage_v_floats = 0;
     float* stage_m = nullptr;      // ... and the product image of the gemm route, grown on demand (Plan::mgemm in lass_separate)
     size_t stage_m_floats = 0;
@@ -93,7 +83,6 @@ struct lass_ctx {
     size_t stage_v_user_floats = 0;
     float* stage_part = nullptr;   // split-K partials of the stage calls (lass_convblock, lass_encoder_block), grown on demand;
     size_t stage_part_floats = 0;  // lass_separate takes its own from the caller's workspace (Plan::kpart)
-    void* up_sc16 = nullptr;  // bf16 mode: decoder_block6's 1x1 shortcut composed with its transposed conv, bf16 [4][2][128] units (lass_finalize)
     // hipGraph replay of lass_separate (LASS_GRAPH=0 disables): the ~40 launches of one (pointers, shape) combination are
     // captured once on an internal stream and replayed on the caller's stream
     bool use_graph = true;
@@ -284,6 +273,17 @@ int dev_alloc(lass_ctx* c, T** p, size_t count) {
 void free_owned(lass_ctx* c) {
     for (void* p : c->owned) (void)hipFree(p);
     c->owned.clear();
+}
+
+// The slots of `want` (weight_plan.h: route_images) that lass_finalize has not made: the block's in `blk`, its decoder's in `up`
+// (either may be null: such a slot counts as missing), the context's in c->img
+SlotSet missing_images(const lass_ctx* c, const WeightImages* blk, const WeightImages* up, SlotSet want) {
+    SlotSet miss = 0;
+    for (int s = 0; s < kWeightSlots; ++s) {
+        const WeightImages* im = s < kBlockSlots ? blk : s < kDecoderSlotsEnd ? up : &c->img;
+        if ((want >> s & 1) && !(im && im->p[s])) miss |= SlotSet(1) << s;
+    }
+    return miss;
 }
 
 // ---- profiling ----------------------------------------------------------------------------------------------------
@@ -483,13 +483,14 @@ int launch_routed(lass_ctx* c, const ResBlock& rb, const char* what, const ConvR
 int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int B, int H, int W, const float* shift,
                  float* a2, float* out, long out_bs, hipStream_t st, const BlockFusions& f = BlockFusions()) {
     const PreConv* pre = f.pre;
+    const WeightImages& im = rb.img;
     const CatCopies *skip_out = f.skip_out, *cat_in = f.cat_in, *pool_copies = f.pool_copies;
     const float* x0 = pre ? pre->x0 : nullptr;
     const Site& s1 = c->sites[rb.s1];
     const Site& s2 = c->sites[rb.s2];
     const long HW = (long)H * W;
     ConvArgs p;
-    p.in = x; p.in_bs = x_bs; p.Cin = rb.cin; p.w = rb.w1; p.Nw = rb.cout; p.N = rb.cout;
+    p.in = x; p.in_bs = x_bs; p.Cin = rb.cin; p.w = im.f32(W1); p.Nw = rb.cout; p.N = rb.cout;
     p.pro_scale = c->bn_scale + s1.off; p.pro_shift = shift + s1.off; p.pro_shift_bs = c->n_shift;
     p.epi_scale = c->bn_scale + s2.off; p.epi_shift = shift + s2.off; p.epi_shift_bs = c->n_shift;
     p.out = a2; p.out_bs = rb.cout * HW; p.B = B; p.H = H; p.W = W;
@@ -497,8 +498,8 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
         p.in = x0; p.in_bs = HW;
         p.pre_w = pre->w; p.pre_b = pre->b;
     }
-    p.w_wino = rb.u1; p.w_wino4 = rb.u1f;
-    p.w_bf16 = rb.b1; p.w_bf16_lo = rb.b1l;
+    p.w_wino = im.f32(U1); p.w_wino4 = im.f32(U1F);
+    p.w_bf16 = im.p[B1]; p.w_bf16_lo = im.p[B1L];
     // bf16 modes: the block's form, and which of the call site's hand-overs it admits (conv_route.h).  lass_separate planned
     // them for producer and consumer at once; one that the block does not admit would have a launch read f32 storage as bf16
     // units, or the reverse
@@ -517,6 +518,11 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
     // f32: the route of both convs and of the shortcut, decided once (conv_route.h); its workspace is checked here, in front of the
     // block's first launch
     const BlockRoute rt = bf1 ? BlockRoute() : plan_block(c->cfg, shape, B, H, W, io);
+    // ... and so are the images the route reads (weight_plan.h), once for the block
+    if (const SlotSet miss = missing_images(c, &im, bb.form == BF16_DEC6U ? &c->up_img[5] : nullptr,  // (decoder_block6's own)
+                                            bf1 ? route_images(bb, bf16_block_weights(c->cfg, rb.cin, rb.cout)) : route_images(rt)))
+        return fail(c, LASS_ERR_STATE, rb.prefix + (miss == slots(WSC3) ? " shortcut: the split weights of the planned route are missing"
+                                                                        : ": the launch arguments contradict the planned route"));
     const size_t xn = rb.cin * HW, on = rb.cout * HW;  // floats per clip of the input, and of the intermediate and the output
     if (rt.kpart_floats) {
         if (!f.kpart) return fail(c, LASS_ERR_STATE, "split-K needs its partial workspace");
@@ -555,17 +561,17 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
     Wino4Split sk;  // both convs of the block
     if (rt.kpart_floats) { sk.n = std::max(rt.conv1.splits, rt.conv2.splits); sk.part = f.kpart; }
     ConvArgs q;
-    q.in = a2; q.in_bs = rb.cout * HW; q.Cin = rb.cout; q.w = rb.w2; q.Nw = rb.cout; q.N = rb.cout;
+    q.in = a2; q.in_bs = rb.cout * HW; q.Cin = rb.cout; q.w = im.f32(W2); q.Nw = rb.cout; q.N = rb.cout;
     q.out = out; q.out_bs = out_bs; q.B = B; q.H = H; q.W = W;
     q.pool_out = f.pool_out; q.pool_h = f.pool_h; q.pool_bs = f.pool_bs;
-    q.w_wino = rb.u2; q.w2_wino = rb.usc; q.w_wino4 = rb.u2f;
+    q.w_wino = im.f32(U2); q.w2_wino = im.f32(USC); q.w_wino4 = im.f32(U2F);
     if (const MaskHead* mh = f.head) {  // the block output is consumed by the fused head and never written
         q.out = nullptr;
         q.mask_w = rawp(c, "base.after_conv.weight"); q.mask_b = rawp(c, "base.after_conv.bias");
         q.mask_mag = mh->mag; q.mask_cos = mh->cosv; q.mask_sin = mh->sinv;
         q.mask_re = mh->oreal; q.mask_im = mh->oimag; q.mask_T = mh->T; q.mask_nbins = mh->nbins;
     }
-    q.w_bf16 = rb.b2; q.w2_bf16 = rb.bsc16; q.w_bf16_lo = rb.b2l; q.w2_bf16_lo = rb.bscl;
+    q.w_bf16 = im.p[B2]; q.w2_bf16 = im.p[BSC16]; q.w_bf16_lo = im.p[B2L]; q.w2_bf16_lo = im.p[BSCL];
     if (bf1) { q.in_bf16 = a2_hi; q.in_bf16_lo = a2_lo; }
     if (cat_in) q.in2_bf16 = cat_in->raw;
     if (pool_copies) {  // bf16 mode: the pooled output as blocked bf16 copies for the next encoder block
@@ -593,11 +599,11 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
             q.pre_w = pre->w; q.pre_b = pre->b;
         }
     } else {
-        q.in2 = x; q.in2_bs = x_bs; q.Cin2 = rb.cin; q.w2 = rb.wsc; q.bias = rb.bsc;
+        q.in2 = x; q.in2_bs = x_bs; q.Cin2 = rb.cin; q.w2 = im.f32(WSC); q.bias = rawp(c, rb.prefix + ".shortcut.bias");
     }
     if (bf1) return run_resblock_bf16(c, rb, bb.form, p, q, B, st, f);
-    if (rt.conv2.head_fold) {  // the composed images in place of conv2's, the shortcut's and after_conv's (null: a state error below)
-        q.w_wino4 = rb.u2h; q.w2 = rb.wsch; q.bias = rb.bh;
+    if (rt.conv2.head_fold) {  // the composed images in place of conv2's, the shortcut's and after_conv's
+        q.w_wino4 = im.f32(U2H); q.w2 = im.f32(WSCH); q.bias = im.f32(BH);
         q.mask_w = q.mask_b = nullptr;
     }
     if (rt.shortcut_gemm) {
@@ -608,8 +614,7 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
         if (!lass_pw_gemm_supported(CONV2_SHORTCUT, q))
             return fail(c, LASS_ERR_STATE, rb.prefix + " shortcut: the launch arguments contradict the planned route");
         PwSplitW sw;
-        if (rt.pw_split) sw.w = rb.wsc3;
-        if (rt.pw_split && !sw.w) return fail(c, LASS_ERR_STATE, rb.prefix + " shortcut: the split weights of the planned route are missing");
+        if (rt.pw_split) sw.w = im.p[WSC3];
         {
             ProfScope ps(c, st, P_CONV3X3);
             HIP_TRY(c, lass_launch_pw_gemm(CONV2_SHORTCUT, q, st, sw));
@@ -618,7 +623,7 @@ int run_resblock(lass_ctx* c, const ResBlock& rb, const float* x, long x_bs, int
         q.res = out; q.res_bs = out_bs;
     }
     Wino4Gemm g1, g2;
-    g1.w3 = rb.u1g; g2.w3 = rb.u2g;
+    g1.w3 = im.p[U1G]; g2.w3 = im.p[U2G];
     g1.m = g2.m = f.mws;
     if (int r = launch_routed(c, rb, "conv1", rt.conv1, p, sk, f.vws, g1, st)) return r;
     return launch_routed(c, rb, "conv2", rt.conv2, q, sk, f.vws, g2, st, f.planes);
@@ -634,7 +639,7 @@ int run_upconv(lass_ctx* c, int di, const float* x, int B, int h, int w, const f
     p.N = p.Nw = d.cout * d.uh * d.uw;
     p.pro_scale = c->bn_scale + s.off; p.pro_shift = shift + s.off; p.pro_shift_bs = c->n_shift;
     p.out = out; p.out_bs = out_bs; p.B = B; p.H = h; p.W = w; p.up_h = d.uh;
-    p.w_bf16 = c->up16[di]; p.w_bf16_lo = c->up16l[di];
+    p.w_bf16 = c->up_img[di].p[UP16]; p.w_bf16_lo = c->up_img[di].p[UP16L];
     // the family, and which of the call site's hand-overs it admits (conv_route.h: plan_upconv)
     UpSite site;
     site.in_act = x_is_act_bf16; site.out_copies = cb != nullptr; site.logits = planes != nullptr;
@@ -647,10 +652,11 @@ int run_upconv(lass_ctx* c, int di, const float* x, int B, int h, int w, const f
         p.out_bf16 = cb->raw; p.out_bf16_act = cb->act; p.out_oct0 = 0; p.out_noct = cb->noct;
         p.act_scale = cb->scale; p.act_shift = cb->shift; p.act_shift_bs = c->n_shift;
     }
+    ok = ok && !missing_images(c, nullptr, &c->up_img[di], route_images(rt, c->cfg));  // the images the route reads (weight_plan.h)
     if (ok && rt.family == UP_LOGITS) ok = lass_tconv_logits_supported(p, *planes);
     PwSplitW sw;
-    if (rt.pw_split) sw.w = c->up3[di];
-    if (ok && rt.family == UP_GEMM) ok = lass_pw_gemm_supported(TCONV_ACT, p) && (!rt.pw_split || sw.w);
+    if (rt.pw_split) sw.w = c->up_img[di].p[UP3];
+    if (ok && rt.family == UP_GEMM) ok = lass_pw_gemm_supported(TCONV_ACT, p);
     if (!ok || rt.family == UP_INSIDE)
         return fail(c, LASS_ERR_STATE, std::string(d.name) + " transposed conv: the launch arguments contradict the planned route");
     ProfScope ps(c, st, P_TCONV);
@@ -673,7 +679,11 @@ int run_upconv(lass_ctx* c, int di, const float* x, int B, int h, int w, const f
 
 // ---- workspace plan ---------------------------------------------------------------------------------------------
 // What workspace_plan.h's rules read of a context
-PlanInputs plan_inputs(const lass_ctx* c) { return PlanInputs{c->g, c->m, c->cfg, c->n_shift, c->hs_wt && c->hs_wskip}; }
+// (head_sc_weights: the rule, and - a composition can decline - the images are really there)
+PlanInputs plan_inputs(const lass_ctx* c) {
+    const bool head_sc = head_sc_weights(c->cfg, c->m, c->head_rows) && !missing_images(c, nullptr, nullptr, slots(HS_WT, HS_WSKIP));
+    return PlanInputs{c->g, c->m, c->cfg, c->n_shift, head_sc};
+}
 Plan make_plan(const lass_ctx* c, int B, int L) { return make_plan(plan_inputs(c), B, L); }
 CallPlan plan_call(const lass_ctx* c, int B, int L, bool capturing, size_t workspace_bytes) {
     return plan_call(plan_inputs(c), B, L, c->split_batch, c->profiling, capturing, workspace_bytes);
@@ -735,6 +745,51 @@ const ResBlock* find_block(const lass_ctx* c, const std::string& prefix) {
     for (const auto& rb : c->enc) if (rb.prefix == prefix) return &rb;
     for (const auto& rb : c->dec) if (rb.prefix == prefix) return &rb;
     return nullptr;
+}
+
+// scale[c] = g / sqrt(var + eps), base[c] = beta - mean * scale of the BatchNorm `bn` of the checkpoint
+hipError_t launch_bnfold(const lass_ctx* c, const std::string& bn, int C, float* scale, float* base, hipStream_t st) {
+    return lass_launch_bnfold(rawp(c, bn + ".weight"), rawp(c, bn + ".bias"), rawp(c, bn + ".running_mean"), rawp(c, bn + ".running_var"), C,
+                              kBnEps, scale, base, st);
+}
+
+int upload(lass_ctx* c, const std::vector<float>& v, void** slot) {
+    float* d = nullptr;
+    if (dev_alloc(c, &d, v.size())) return LASS_ERR_HIP;
+    HIP_TRY(c, hipMemcpy(d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
+    *slot = d;
+    return 0;
+}
+
+// The folded head's images (weight_plan.h: WF_HEAD_*): decoder_block6's conv2 and shortcut composed with after_conv, and (sc) the
+// shortcut's two halves for the launches that produce its inputs - Wt' = Wsc'_up o Wt for the transposed conv, Wsc'_skip for
+// encoder_block1.conv2's epilogue (head_fold.h).  A composition that declines leaves its vectors empty.
+struct HeadHost {
+    HeadFold hf;
+    HeadScFold hsf;
+    const std::vector<float>& of(WeightForm f) const {
+        return f == WF_HEAD_U4 ? hf.u4 : f == WF_HEAD_WSC ? hf.wsc : f == WF_HEAD_BIAS ? hf.bias : f == WF_HEAD_SC_WT ? hsf.wt : hsf.wskip;
+    }
+};
+int compose_head(lass_ctx* c, int Q, bool sc, HeadHost* h) {
+    const ResBlock& rb = c->dec[5];
+    const DecSpec& d6 = c->m.D[5];
+    const int N = rb.cout, K = rb.cin;
+    std::vector<float> w2, ws, bs, wa, ba, wt;
+    const auto host = [&](std::vector<float>& v, const std::string& name, size_t n) -> int {
+        v.resize(n);
+        HIP_TRY(c, hipMemcpy(v.data(), rawp(c, name), n * sizeof(float), hipMemcpyDeviceToHost));
+        return 0;
+    };
+    HIP_TRY(c, hipStreamSynchronize(nullptr));  // lass_finalize's stream: the one wait in front of the host reads
+    if (host(w2, rb.prefix + ".conv2.weight", (size_t)N * N * 9) || host(ws, rb.prefix + ".shortcut.weight", (size_t)N * K) ||
+        host(bs, rb.prefix + ".shortcut.bias", N) || host(wa, "base.after_conv.weight", (size_t)Q * N) ||
+        host(ba, "base.after_conv.bias", Q) ||
+        (sc && host(wt, std::string("base.") + d6.name + ".conv1.weight", (size_t)d6.cin * d6.cout * d6.uh * d6.uw)))
+        return LASS_ERR_HIP;
+    if (sc) compose_head_sc_fold(ws.data(), wa.data(), wt.data(), N, d6.cout, kPreCh, Q, d6.cin, d6.uh, d6.uw, &h->hsf);
+    if (!compose_head_fold(w2.data(), ws.data(), bs.data(), wa.data(), ba.data(), N, N, K, Q, &h->hf) || h->hf.u4.empty()) h->hf = HeadFold();
+    return 0;
 }
 
 }  // namespace
@@ -895,215 +950,87 @@ int lass_finalize(lass_ctx* c, int compute_mode) {
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipDeviceSynchronize());  // replays of graphs that hold the old derived buffers have drained
     drop_graphs(c);
-    free_owned(c);
+    free_owned(c);  // ... and with the storage goes every pointer to it: a second finalize in another mode starts from no image
+    for (auto* blocks : {&c->enc, &c->dec})
+        for (ResBlock& rb : *blocks) rb.img = WeightImages();
+    for (WeightImages& u : c->up_img) u = WeightImages();
+    c->img = WeightImages();
+    c->head_rows = 0;
     c->finalized = false;
-    hipStream_t st = nullptr;
-    auto need = [&](const std::string& n) -> const float* {
-        const float* p = rawp(c, n);
-        if (!p && c->err.empty()) c->err = "missing parameter '" + n + "'";
-        return p;
-    };
     c->err.clear();
+    hipStream_t st = nullptr;
+    // -- every parameter is there: the first one missing, in this order, is the error
+    const auto need = [&](const std::string& p, std::initializer_list<const char*> fields) {
+        for (const char* f : fields)
+            if (!rawp(c, p + f) && c->err.empty()) c->err = "missing parameter '" + p + f + "'";
+    };
+    const auto bn = {".weight", ".bias", ".running_mean", ".running_var"}, wb = {".weight", ".bias"};
+    for (const Site& s : c->sites) { need(s.bn, bn); need("film." + s.film, wb); }
+    need("base.bn0", bn);
+    for (int k = 0; k < c->g.nbr; ++k) need(c->pre_name[k], wb);
+    need("base.after_conv", wb);
+    for (const auto* blocks : {&c->enc, &c->dec})
+        for (const ResBlock& rb : *blocks) {
+            need(rb.prefix, {".conv1.weight", ".conv2.weight"});
+            if (rb.cin != rb.cout) need(rb.prefix, {".shortcut.weight", ".shortcut.bias"});
+        }
+    for (const DecSpec& d : c->m.D) need(std::string("base.") + d.name, {".conv1.weight"});
+    if (!c->err.empty()) return LASS_ERR_STATE;
     // -- BN folding for the 32 live sites + bn0, FiLM concatenation
     if (dev_alloc(c, &c->bn_scale, c->n_shift) || dev_alloc(c, &c->bn_base, c->n_shift) ||
         dev_alloc(c, &c->film_W, (size_t)c->n_shift * LASS_COND) || dev_alloc(c, &c->film_b, c->n_shift) ||
         dev_alloc(c, &c->bn0_s, c->g.nbins) || dev_alloc(c, &c->bn0_h, c->g.nbins))
         return LASS_ERR_HIP;
-    for (const auto& s : c->sites) {
-        const float *g = need(s.bn + ".weight"), *b = need(s.bn + ".bias"), *m = need(s.bn + ".running_mean"),
-                    *v = need(s.bn + ".running_var"), *fw = need("film." + s.film + ".weight"),
-                    *fb = need("film." + s.film + ".bias");
-        if (!g || !b || !m || !v || !fw || !fb) return LASS_ERR_STATE;
-        HIP_TRY(c, lass_launch_bnfold(g, b, m, v, s.C, kBnEps, c->bn_scale + s.off, c->bn_base + s.off, st));
-        HIP_TRY(c, hipMemcpyAsync(c->film_W + (size_t)s.off * LASS_COND, fw, (size_t)s.C * LASS_COND * sizeof(float),
-                                  hipMemcpyDeviceToDevice, st));
-        HIP_TRY(c, hipMemcpyAsync(c->film_b + s.off, fb, s.C * sizeof(float), hipMemcpyDeviceToDevice, st));
+    for (const Site& s : c->sites) {
+        HIP_TRY(c, launch_bnfold(c, s.bn, s.C, c->bn_scale + s.off, c->bn_base + s.off, st));
+        HIP_TRY(c, hipMemcpyAsync(c->film_W + (size_t)s.off * LASS_COND, rawp(c, "film." + s.film + ".weight"),
+                                  (size_t)s.C * LASS_COND * sizeof(float), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(c, hipMemcpyAsync(c->film_b + s.off, rawp(c, "film." + s.film + ".bias"), s.C * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
-    {
-        const float *g = need("base.bn0.weight"), *b = need("base.bn0.bias"), *m = need("base.bn0.running_mean"),
-                    *v = need("base.bn0.running_var");
-        if (!g || !b || !m || !v) return LASS_ERR_STATE;
-        HIP_TRY(c, lass_launch_bnfold(g, b, m, v, c->g.nbins, kBnEps, c->bn0_s, c->bn0_h, st));
-    }
-    for (int k = 0; k < c->g.nbr; ++k)
-        if (!need(c->pre_name[k] + ".weight") || !need(c->pre_name[k] + ".bias")) return LASS_ERR_STATE;
-    if (!need("base.after_conv.weight") || !need("base.after_conv.bias")) return LASS_ERR_STATE;
-    // -- conv weights -> [cin][tap][cout]
-    auto prep = [&](ResBlock& rb) -> int {
-        const float *w1 = need(rb.prefix + ".conv1.weight"), *w2 = need(rb.prefix + ".conv2.weight");
-        if (!w1 || !w2) return LASS_ERR_STATE;
-        if (dev_alloc(c, &rb.w1, (size_t)rb.cout * rb.cin * 9) || dev_alloc(c, &rb.w2, (size_t)rb.cout * rb.cout * 9))
-            return LASS_ERR_HIP;
-        HIP_TRY(c, lass_launch_relayout_conv(w1, rb.cout, rb.cin, 9, rb.w1, st));
-        HIP_TRY(c, lass_launch_relayout_conv(w2, rb.cout, rb.cout, 9, rb.w2, st));
-        rb.u1 = rb.u2 = rb.usc = nullptr;
-        rb.u1f = rb.u2f = nullptr;
-        rb.u1g = rb.u2g = nullptr;
-        rb.b1 = rb.b2 = rb.bsc16 = rb.b1l = rb.b2l = rb.bscl = nullptr;
-        const Bf16Weights wt = bf16_block_weights(c->cfg, rb.cin, rb.cout);  // the copies the bf16 plan counts on
-        if (wt.pair) {
-            unsigned short *t1 = nullptr, *t2 = nullptr;
-            if (dev_alloc(c, &t1, (size_t)rb.cout * rb.cin * 9) || dev_alloc(c, &t2, (size_t)rb.cout * rb.cout * 9))
-                return LASS_ERR_HIP;
-            HIP_TRY(c, lass_launch_weights_bf16(w1, rb.cout, rb.cin, 9, t1, 0, 0, st));
-            HIP_TRY(c, lass_launch_weights_bf16(w2, rb.cout, rb.cout, 9, t2, 0, 0, st));
-            rb.b1 = t1; rb.b2 = t2;
-            if (wt.pair_lo) {
-                unsigned short *l1 = nullptr, *l2 = nullptr;
-                if (dev_alloc(c, &l1, (size_t)rb.cout * rb.cin * 9) || dev_alloc(c, &l2, (size_t)rb.cout * rb.cout * 9))
-                    return LASS_ERR_HIP;
-                HIP_TRY(c, lass_launch_weights_bf16(w1, rb.cout, rb.cin, 9, l1, 1, 0, st));
-                HIP_TRY(c, lass_launch_weights_bf16(w2, rb.cout, rb.cout, 9, l2, 1, 0, st));
-                rb.b1l = l1; rb.b2l = l2;
-            }
+    HIP_TRY(c, launch_bnfold(c, "base.bn0", c->g.nbins, c->bn0_s, c->bn0_h, st));
+    // -- the weight images: weight_plan.h says which, in which form and from what; every launcher below writes `count` elements
+    const Param* ra = c->raw.find("base.after_conv.weight");
+    if (!ra->shape.empty() && ra->n == (size_t)ra->shape[0] * c->dec[5].cout) c->head_rows = (int)ra->shape[0];
+    const ResBlock& rb6 = c->dec[5];
+    const DecSpec& d6 = c->m.D[5];
+    HeadHost head;
+    bool composed = false;
+    for (const WeightItem& it : plan_weights(c->cfg, c->m, c->head_rows)) {
+        ResBlock* rb = it.owner != OWN_BLOCK ? nullptr : it.index < (int)c->enc.size() ? &c->enc[it.index] : &c->dec[it.index - c->enc.size()];
+        WeightImages& im = rb ? rb->img : it.owner == OWN_DECODER ? c->up_img[it.index] : c->img;
+        // the owner's prefix of checkpoint names: the block's, or its decoder's (the context's images are decoder_block6's)
+        const std::string prefix = rb ? rb->prefix + "." : std::string("base.") + c->m.D[it.owner == OWN_DECODER ? it.index : 5].name + ".";
+        const float* src = it.param ? rawp(c, prefix + it.param) : it.from >= 0 ? im.f32((WeightSlot)it.from) : nullptr;
+        if (weight_form_on_host(it.form)) {  // in double on the host, from the checkpoint alone
+            if (!composed && compose_head(c, c->head_rows, head_sc_weights(c->cfg, c->m, c->head_rows), &head)) return LASS_ERR_HIP;
+            composed = true;
+            const std::vector<float>& v = head.of(it.form);
+            if (v.empty()) continue;  // the composition declined: no image, and the route is off
+            if (v.size() != it.count) return fail(c, LASS_ERR_STATE, "lass_finalize: a head composition contradicts the weight plan");
+            if (int r = upload(c, v, &im.p[it.slot])) return r;
+            continue;
         }
-        if (c->cfg.f32()) {
-            if (dev_alloc(c, &rb.u1, (size_t)16 * rb.cout * rb.cin) || dev_alloc(c, &rb.u2, (size_t)16 * rb.cout * rb.cout))
-                return LASS_ERR_HIP;
-            HIP_TRY(c, lass_launch_wino_weights(w1, rb.cout, rb.cin, rb.u1, st));
-            HIP_TRY(c, lass_launch_wino_weights(w2, rb.cout, rb.cout, rb.u2, st));
-            const Wino4Images im = wino4_images(c->cfg, rb.cin, rb.cout, rb.width);  // the routes plan_block can give the block
-            if (im.u1f) {
-                if (dev_alloc(c, &rb.u1f, (size_t)36 * rb.cout * rb.cin)) return LASS_ERR_HIP;
-                HIP_TRY(c, lass_launch_wino4_weights(w1, rb.cout, rb.cin, rb.u1f, st));
-            }
-            if (im.u2f) {
-                if (dev_alloc(c, &rb.u2f, (size_t)36 * rb.cout * rb.cout)) return LASS_ERR_HIP;
-                HIP_TRY(c, lass_launch_wino4_weights(w2, rb.cout, rb.cout, rb.u2f, st));
-            }
-            // ... and, for the convs plan_block can route through wino4_gemm.hip, the split of exactly those f32 images (216 K N
-            // bytes each, kept beside them whatever RouteCfg::wino4_gemm says at that moment: the switch can be thrown afterwards)
-            if (rb.u1f && lass_wino4_gemm_weights(true, rb.cin, rb.cout)) {
-                unsigned short* t = nullptr;
-                if (dev_alloc(c, &t, (size_t)3 * 36 * rb.cout * rb.cin)) return LASS_ERR_HIP;
-                HIP_TRY(c, lass_launch_wino4_gemm_weights(rb.u1f, rb.cout, rb.cin, t, st));
-                rb.u1g = t;
-            }
-            if (rb.u2f && lass_wino4_gemm_weights(true, rb.cout, rb.cout)) {
-                unsigned short* t = nullptr;
-                if (dev_alloc(c, &t, (size_t)3 * 36 * rb.cout * rb.cout)) return LASS_ERR_HIP;
-                HIP_TRY(c, lass_launch_wino4_gemm_weights(rb.u2f, rb.cout, rb.cout, t, st));
-                rb.u2g = t;
-            }
+        char* dst = nullptr;
+        if (dev_alloc(c, &dst, it.count * it.elem_bytes)) return LASS_ERR_HIP;
+        float* dstf = (float*)dst;
+        switch (it.form) {
+            case WF_RELAYOUT: HIP_TRY(c, lass_launch_relayout_conv(src, it.rows, it.cols, it.taps, dstf, st)); break;
+            case WF_F2X2: HIP_TRY(c, lass_launch_wino_weights(src, it.rows, it.cols, dstf, st)); break;
+            case WF_F2X2_SC: HIP_TRY(c, lass_launch_wino_shortcut_weights(src, it.rows, it.cols, dstf, st)); break;
+            case WF_F4X4: HIP_TRY(c, lass_launch_wino4_weights(src, it.rows, it.cols, dstf, st)); break;
+            case WF_F4X4_SPLIT3: HIP_TRY(c, lass_launch_wino4_gemm_weights(src, it.rows, it.cols, dst, st)); break;
+            case WF_PW_SPLIT3: HIP_TRY(c, lass_launch_pw_split_weights(src, it.rows, it.cols, dst, st)); break;
+            case WF_UP_SC:
+                HIP_TRY(c, lass_launch_compose_up_shortcut(rawp(c, rb6.prefix + ".shortcut.weight"), rawp(c, prefix + "conv1.weight"), d6.cin,
+                                                           d6.cout, rb6.cin, rb6.cout, dstf, st));
+                break;
+            case WF_BF16: case WF_BF16_LO: case WF_BF16_T: case WF_BF16_T_LO:
+                HIP_TRY(c, lass_launch_weights_bf16(src, it.rows, it.cols, it.taps, dst, it.form == WF_BF16_LO || it.form == WF_BF16_T_LO,
+                                                    it.form >= WF_BF16_T, st));
+                break;
+            default: return fail(c, LASS_ERR_STATE, "lass_finalize: a weight form without a launcher");
         }
-        rb.wsc = nullptr;
-        rb.bsc = nullptr;
-        rb.wsc3 = nullptr;
-        if (rb.cin != rb.cout) {
-            const float *ws = need(rb.prefix + ".shortcut.weight"), *bs = need(rb.prefix + ".shortcut.bias");
-            if (!ws || !bs) return LASS_ERR_STATE;
-            if (dev_alloc(c, &rb.wsc, (size_t)rb.cout * rb.cin)) return LASS_ERR_HIP;
-            HIP_TRY(c, lass_launch_relayout_conv(ws, rb.cout, rb.cin, 1, rb.wsc, st));
-            rb.bsc = bs;
-            if (wt.shortcut) {
-                unsigned short* t3 = nullptr;
-                if (dev_alloc(c, &t3, (size_t)rb.cout * rb.cin)) return LASS_ERR_HIP;
-                HIP_TRY(c, lass_launch_weights_bf16(ws, rb.cout, rb.cin, 1, t3, 0, 0, st));
-                rb.bsc16 = t3;
-                if (wt.shortcut_lo) {
-                    unsigned short* l3 = nullptr;
-                    if (dev_alloc(c, &l3, (size_t)rb.cout * rb.cin)) return LASS_ERR_HIP;
-                    HIP_TRY(c, lass_launch_weights_bf16(ws, rb.cout, rb.cin, 1, l3, 1, 0, st));
-                    rb.bscl = l3;
-                }
-            }
-            if (c->cfg.f32()) {
-                if (dev_alloc(c, &rb.usc, (size_t)4 * rb.cout * rb.cin)) return LASS_ERR_HIP;
-                HIP_TRY(c, lass_launch_wino_shortcut_weights(ws, rb.cout, rb.cin, rb.usc, st));
-            }
-            if (lass_pw_split_shortcut_weights(c->cfg.f32(), rb.cin, rb.cout)) {  // from wsc [cin][cout], the f32 kernel's matrix
-                unsigned short* t = nullptr;
-                if (dev_alloc(c, &t, (size_t)3 * rb.cout * rb.cin)) return LASS_ERR_HIP;
-                HIP_TRY(c, lass_launch_pw_split_weights(rb.wsc, rb.cin, rb.cout, t, st));
-                rb.wsc3 = t;
-            }
-        }
-        return 0;
-    };
-    for (auto& rb : c->enc) { int r = prep(rb); if (r) return r; }
-    for (auto& rb : c->dec) { int r = prep(rb); if (r) return r; }
-    for (int i = 0; i < 6; ++i) {
-        const auto& d = c->m.D[i];
-        const float* wu = need(std::string("base.") + d.name + ".conv1.weight");
-        if (!wu) return LASS_ERR_STATE;
-        c->up16[i] = c->up16l[i] = c->up3[i] = nullptr;
-        if (lass_pw_split_tconv_weights(c->cfg.f32(), d.cin, d.cout * d.uh * d.uw, d.uh)) {  // (cin, cout, uh, uw) == [cin][n]
-            unsigned short* t = nullptr;
-            if (dev_alloc(c, &t, (size_t)3 * d.cin * d.cout * d.uh * d.uw)) return LASS_ERR_HIP;
-            HIP_TRY(c, lass_launch_pw_split_weights(wu, d.cin, d.cout * d.uh * d.uw, t, st));
-            c->up3[i] = t;
-        }
-        if (bf16_tconv_weights(c->cfg, d)) {
-            const int N = d.cout * d.uh * d.uw;
-            unsigned short *t = nullptr, *l = nullptr;
-            if (dev_alloc(c, &t, (size_t)N * d.cin)) return LASS_ERR_HIP;
-            HIP_TRY(c, lass_launch_weights_bf16(wu, N, d.cin, 1, t, 0, 1, st));
-            c->up16[i] = t;
-            if (c->cfg.mode == MODE_BF16X3) {
-                if (dev_alloc(c, &l, (size_t)N * d.cin)) return LASS_ERR_HIP;
-                HIP_TRY(c, lass_launch_weights_bf16(wu, N, d.cin, 1, l, 1, 1, st));
-                c->up16l[i] = l;
-            }
-        }
-    }
-    // decoder_block6's shortcut over the up-sampled half of its concat, composed with the transposed conv (dec6u_fused_bf16_kernel)
-    c->up_sc16 = nullptr;
-    {
-        const DecSpec& d = c->m.D[5];
-        const ResBlock& rb = c->dec[5];
-        if (bf16_up_sc_weights(c->cfg, c->m)) {
-            const float* wu = need(std::string("base.") + d.name + ".conv1.weight");
-            const float* ws = need(rb.prefix + ".shortcut.weight");
-            if (!wu || !ws) return LASS_ERR_STATE;
-            float* tmp = nullptr;
-            unsigned short* t16 = nullptr;
-            if (dev_alloc(c, &tmp, (size_t)4 * rb.cout * d.cin) || dev_alloc(c, &t16, (size_t)4 * rb.cout * d.cin)) return LASS_ERR_HIP;
-            HIP_TRY(c, lass_launch_compose_up_shortcut(ws, wu, d.cin, d.cout, rb.cin, rb.cout, tmp, st));
-            HIP_TRY(c, lass_launch_weights_bf16(tmp, 4 * rb.cout, d.cin, 1, t16, 0, 0, st));
-            c->up_sc16 = t16;
-        }
-    }
-    // decoder_block6's conv2 and shortcut composed with after_conv, for the folded output head (head_fold.h): in double on the
-    // host, from the checkpoint alone
-    {
-        ResBlock& rb = c->dec[5];
-        rb.u2h = rb.wsch = rb.bh = nullptr;
-        c->hs_wt = c->hs_wskip = nullptr;
-        const Param& ra = c->raw.by_name["base.after_conv.weight"];
-        const int Q = ra.shape.empty() ? 0 : (int)ra.shape[0];
-        if (rb.u2f && rb.cin != rb.cout && Q > 0 && Q <= kHeadFoldRows && ra.n == (size_t)Q * rb.cout) {
-            const int N = rb.cout, K = rb.cin;
-            std::vector<float> w2((size_t)N * N * 9), ws((size_t)N * K), bs(N), wa((size_t)Q * N), ba(Q);
-            HIP_TRY(c, hipStreamSynchronize(st));
-            HIP_TRY(c, hipMemcpy(w2.data(), need(rb.prefix + ".conv2.weight"), w2.size() * sizeof(float), hipMemcpyDeviceToHost));
-            HIP_TRY(c, hipMemcpy(ws.data(), need(rb.prefix + ".shortcut.weight"), ws.size() * sizeof(float), hipMemcpyDeviceToHost));
-            HIP_TRY(c, hipMemcpy(bs.data(), rb.bsc, bs.size() * sizeof(float), hipMemcpyDeviceToHost));
-            HIP_TRY(c, hipMemcpy(wa.data(), ra.d, wa.size() * sizeof(float), hipMemcpyDeviceToHost));
-            HIP_TRY(c, hipMemcpy(ba.data(), need("base.after_conv.bias"), ba.size() * sizeof(float), hipMemcpyDeviceToHost));
-            // ... and the shortcut's two halves for the launches that produce its inputs (ResUNet30: the skip is ONE encoder_block1's
-            // output): Wt' = Wsc'_up o Wt for the transposed conv, Wsc'_skip for encoder_block1.conv2's epilogue
-            const DecSpec& d6 = c->m.D[5];
-            const Param* up = c->raw.find(std::string("base.") + d6.name + ".conv1.weight");
-            if (c->g.variant == 0 && c->g.nbr == 1 && Q == 3 && K == d6.cout + kPreCh && up && up->d &&
-                up->n == (size_t)d6.cin * d6.cout * d6.uh * d6.uw) {
-                std::vector<float> wt(up->n);
-                HIP_TRY(c, hipMemcpy(wt.data(), up->d, wt.size() * sizeof(float), hipMemcpyDeviceToHost));
-                HeadScFold hsf;
-                if (compose_head_sc_fold(ws.data(), wa.data(), wt.data(), N, d6.cout, kPreCh, Q, d6.cin, d6.uh, d6.uw, &hsf)) {
-                    if (dev_alloc(c, &c->hs_wt, hsf.wt.size()) || dev_alloc(c, &c->hs_wskip, hsf.wskip.size())) return LASS_ERR_HIP;
-                    HIP_TRY(c, hipMemcpy(c->hs_wt, hsf.wt.data(), hsf.wt.size() * sizeof(float), hipMemcpyHostToDevice));
-                    HIP_TRY(c, hipMemcpy(c->hs_wskip, hsf.wskip.data(), hsf.wskip.size() * sizeof(float), hipMemcpyHostToDevice));
-                }
-            }
-            HeadFold hf;
-            if (compose_head_fold(w2.data(), ws.data(), bs.data(), wa.data(), ba.data(), N, N, K, Q, &hf) && !hf.u4.empty()) {
-                if (dev_alloc(c, &rb.u2h, hf.u4.size()) || dev_alloc(c, &rb.wsch, hf.wsc.size()) || dev_alloc(c, &rb.bh, hf.bias.size()))
-                    return LASS_ERR_HIP;
-                HIP_TRY(c, hipMemcpy(rb.u2h, hf.u4.data(), hf.u4.size() * sizeof(float), hipMemcpyHostToDevice));
-                HIP_TRY(c, hipMemcpy(rb.wsch, hf.wsc.data(), hf.wsc.size() * sizeof(float), hipMemcpyHostToDevice));
-                HIP_TRY(c, hipMemcpy(rb.bh, hf.bias.data(), hf.bias.size() * sizeof(float), hipMemcpyHostToDevice));
-            }
-        }
+        im.p[it.slot] = dst;
     }
     HIP_TRY(c, hipStreamSynchronize(st));
     c->finalized = true;
@@ -1558,8 +1485,8 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
     // conv_route.h's head_sc_fold: one decision for encoder_block1.conv2, decoder_block6's transposed conv and the head
     HeadScPlanes hs_skip, hs_up, hs_head;
     if (sp.head_sc_fold) {
-        hs_skip.skip = hs_head.skip = F(pl.lg_skip); hs_skip.w = c->hs_wskip;
-        hs_up.up = hs_head.up = F(pl.lg_up); hs_up.w = c->hs_wt;
+        hs_skip.skip = hs_head.skip = F(pl.lg_skip); hs_skip.w = c->img.f32(HS_WSKIP);
+        hs_up.up = hs_head.up = F(pl.lg_up); hs_up.w = c->img.f32(HS_WT);
         hs_skip.up = hs_head.up;  // (for run_resblock's overlap checks; the encoder launch does not touch it)
     }
     // Routes.  pre_conv (resunet.py:555) is never materialised: encoder_block1 forms it from x0 while staging.  Tp is a
@@ -1629,7 +1556,7 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
         BlockFusions f;
         // decoder_block6 in the blocked bf16 pipeline: the transposed conv runs inside the block's fused kernel, its output
         // (half of the concat, at the full resolution) is never written
-        const UpFuse upf{x, c->m.D[d].cin, h, w, c->up16[d], c->up_sc16};
+        const UpFuse upf{x, c->m.D[d].cin, h, w, c->up_img[d].p[UP16], c->img.p[UP_SC16]};
         if (io.up_cin) {
             f.up = &upf;
         } else {

@@ -1,7 +1,8 @@
 // conv_route.h - which kernel family runs the 3x3 convs of a residual block in f32, and the workspace that takes; in the bf16
 // modes which blocks run the bf16 kernels, in which form (two launches or one fused kernel), and which tensors travel between
 // launches as blocked bf16 copies; in every mode the family of each transposed conv; and the model table with its level walk.
-// The ONE rule behind the weight images and bf16 copies of lass_finalize, the launches of run_resblock and run_upconv (api.hip),
+// The ONE rule behind the launches of run_resblock and run_upconv (api.hip), the predicates that weight_plan.h lists the weight
+// images and bf16 copies of lass_finalize by (wino4_images, lass_wino4_gemm_weights, lass_pw_split_*_weights, bf16_*_weights),
 // and the shape halves of the lass_*_supported predicates of wino.hip, wino4.hip, wino4_gemm.hip, pw_gemm.hip, conv_bf16.hip and
 // conv_bf16_fused.hip; and, as plan_separate, the ONE walk over the blocks of a lass_separate: what each block is called with, its
 // route and hand-overs, the head_sc_fold decision and the workspace the routes take.  workspace_plan.h sizes the workspace from that
@@ -176,7 +177,8 @@ constexpr int kTconvGemmMinCin = 128;
 
 // Which weight matrices lass_finalize also keeps as the three bf16 pieces of pw_gemm.hip's split kernel (6 K N bytes each): every
 // one that plan_block / plan_upconv can send there at some image size (the channel half of their rules).  Kept whatever
-// RouteCfg::pw_split says at that moment: the switch can be thrown afterwards.
+// RouteCfg::pw_split says at that moment: the switch can be thrown afterwards (weight_plan.h reads no such switch, and
+// tests/test_weight_plan_cpu.py holds every route of every switch setting inside the list it makes).
 inline bool lass_pw_split_shortcut_weights(bool f32, int cin, int cout) {
     return f32 && cin != cout && cin >= kShortcutGemmMinCin && cin % (2 * kPwGemmKC) == 0 && cout % kPwGemmNB == 0;
 }
@@ -441,8 +443,8 @@ inline Levels model_levels(const ModelTable& m, int t_pad) {
 }
 
 // ---- the bf16 modes: weights, transposed convs, blocks --------------------------------------------------------------------------
-// Which bf16 copies lass_finalize prepares.  The plans below ask these functions, not the pointers: finalize allocates by
-// exactly this rule or fails.
+// Which bf16 copies lass_finalize prepares (weight_plan.h: plan_weights).  The plans below ask these functions, not the pointers:
+// finalize allocates by exactly this rule or fails.
 struct Bf16Weights {
     bool pair = false, pair_lo = false;          // conv1 and conv2 (hi), and their lo halves (bf16x3)
     bool shortcut = false, shortcut_lo = false;  // the 1x1 shortcut of a block that has one
@@ -562,7 +564,8 @@ struct SeparatePlan {
     int conv_scopes = 0, tconv_scopes = 0;
 };
 // B sizes the workspace slots of the routes and nothing else: forms, hand-overs, families and scope counts do not depend on it.
-// head_sc_weights: lass_finalize composed the head's shortcut with its two producers (head_fold.h) for this checkpoint.
+// head_sc_weights: lass_finalize composed the head's shortcut with its two producers (head_fold.h) for this checkpoint
+// (weight_plan.h: head_sc_weights is the rule, and the images are there).
 inline SeparatePlan plan_separate(const RouteCfg& cfg, const ModelTable& m, const Levels& lv, int B, bool head_sc_weights) {
     SeparatePlan sp;
     // encoder_block1 forms pre_conv(x0), the encoders pool in conv2's epilogue, decoder_block6 carries the output head

@@ -18,6 +18,7 @@
 #include <cstring>
 #include <string>
 
+#include "weight_plan.h"
 #include "workspace_plan.h"
 
 // The FiLM width of a model (lass_film_width): two sites per ConvBlockRes (cin, cout) and one per transposed conv (its cin)
@@ -69,9 +70,7 @@ int main(int argc, char** argv) {
         else return 2;
     }
     const ModelTable m = model_table(g.variant == 0 ? 0 : g.nbr, g.fcrop);
-    // lass_finalize composes the head's shortcut weights where decoder_block6.conv2 has its F(4x4,3x3) image, for ResUNet30
-    const BlockShape d6 = m.dec_shape(5);
-    if (weights < 0) weights = g.variant == 0 && wino4_images(cfg, d6.cin, d6.cout, d6.width).u2f;
+    if (weights < 0) weights = head_sc_weights(cfg, m, 3);  // weight_plan.h: what lass_finalize composes (after_conv has 3 rows)
     const PlanInputs in{g, m, cfg, film_width(m), weights != 0};
     const int B = atoi(argv[5]), L = atoi(argv[6]);
     const long long ws = atoll(argv[9]);
