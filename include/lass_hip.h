@@ -455,6 +455,58 @@ int lass_resample_encode(lass_ctx* ctx, const float* planes, int64_t row_stride,
                          int up, int down, const float* taps, int n_taps, int encoding, void* out_bytes,
                          int64_t out_row_stride_bytes, int frames_out, unsigned* clipped, void* stream);
 
+/* ---- levelled export: loudness meter, peak, gain (opt-in; lass_amd.pipeline.separate_files(loudness=, peak_ceiling_db=)) ---- */
+
+/* The ITU-R BS.1770-4 gated integrated loudness of B recordings, on the device.  planes, row_stride, plane_stride, channels:
+ * as lass_resample_encode addresses its planes, L floats each; lengths (device, B int32, or NULL: every recording L samples):
+ * recording b is the first lengths[b] samples of its planes (values outside 0 ... L are clamped).  hop = rate / 10 samples
+ * (100 ms; the rate must be a multiple of 10).  coef (HOST, 10 doubles): the K-weighting biquads for that rate, b0 b1 b2 a1 a2
+ * of the high shelf, then of the high-pass, a0 == 1 (lass_amd.loudness.coefficients).  weights (device, `channels` floats, or
+ * NULL: all 1): the channel weights G_i.  For every recording:
+ *   y_c = the cascade on plane c, direct form II transposed, zero initial state, state and products in float64;
+ *   p_j = sum_c G_c * mean(y_c[j*hop .. j*hop + 4*hop)^2),   j < nb = (len - 4*hop) / hop + 1  (0 if len < 4*hop): whole blocks only;
+ *   l_j = -0.691 + 10 log10 p_j;  absolute gate l_j > -70;  relative gate l_j > (-0.691 + 10 log10 mean of the abs-gated p) - 10;
+ *   out[b] = { -0.691 + 10 log10 (mean of the doubly gated p), or -inf when no block survives;  nb;  surviving blocks }
+ * out: (B,3) doubles.  blocks (optional, (B, nb_max) doubles): row b receives p_0 ... p_{nb-1}, then zeros.
+ * The recurrence is cut into hop bins (one wave each, its lanes on consecutive sub-runs), carried over the cuts with powers of
+ * the cascade's state matrix formed here on the host in float64; every cut is a multiple of hop from the plane's first sample and
+ * every sum has one fixed order, so a recording's three numbers and its blocks are bit-identical whatever B, its row, the
+ * strides or the call.  No floating-point atomics; nothing is read back.
+ * scratch: 5 * B * channels * (L / hop) doubles (device, 8-byte aligned), scratch_bytes its size.
+ * Limits, checked before anything is launched (LASS_ERR_ARG): 1 <= channels <= 8, B * channels <= 65535,
+ * 1 <= hop <= LASS_LOUDNESS_MAX_HOP, plane_stride >= L, row_stride >= (channels-1)*plane_stride + L, coef finite with both pole
+ * pairs inside the unit circle, nb_max >= the blocks of L samples when blocks is given, scratch large enough.  Stateless.
+ * Replaces: pyloudnorm.Meter(rate).integrated_loudness (data/waveform_mixers.py:119-120) for the export path; written from the
+ * recommendation and pinned by the EBU Tech 3341 tones and the float64 host definition, not by a reference fixture. */
+#define LASS_LOUDNESS_MAX_HOP 38400
+int lass_loudness(lass_ctx* ctx, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels, int L,
+                  const int* lengths, int hop, const double* coef, const float* weights, double* out, double* blocks, int nb_max,
+                  void* scratch, size_t scratch_bytes, void* stream);
+
+/* The sample peak of what lass_resample_encode would quantise: peak[b] (device, B floats, written here) = max |y[n]| over the
+ * channels of recording b and n < frames_out, y that entry point's value before quantisation (one kernel body with it: the same
+ * formula, tap order and fmaf chain).  Raised by integer atomic max on the bits of |y|: exact and order-independent; a NaN is
+ * skipped, an infinity is a peak.  Arguments and limits: lass_resample_encode's up to frames_out, peak 4-byte aligned. */
+int lass_resample_peak(lass_ctx* ctx, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels, int L_in,
+                       int up, int down, const float* taps, int n_taps, int frames_out, float* peak, void* stream);
+
+/* One gain per recording from its loudness and peak (utils.py:293 gives the dB rule; the ceiling is scripts/process_audio.sh's
+ * peak normalisation turned into a bound).  loudness (device, B doubles, -inf allowed), peak (device, B floats, may be NULL
+ * without a ceiling), target_lufs (NaN: none), ceiling (linear, 0: none) -> gain (device, B floats):
+ *   g = (float)10^((target_lufs - loudness[b]) / 20) if a target is given and loudness[b] is finite, else 1;
+ *   if a ceiling is given and fl(g * peak[b]) > ceiling:  g = fl(ceiling / peak[b]), then one float32 ulp down while
+ *   fl(g * peak[b]) > ceiling.   x -> fl(g * x) is monotone in |x|: no sample of the row, gained, exceeds the ceiling.
+ * limited (optional, device, B int32): 1 where the ceiling bit, else 0.  lass_amd.loudness.gain_for is the same rule on the host. */
+int lass_loudness_gain(lass_ctx* ctx, const double* loudness, const float* peak, int B, double target_lufs, float ceiling,
+                       float* gain, int* limited, void* stream);
+
+/* lass_resample_encode with a gain per recording: every y of recording b becomes fl(gain[b] * y) - one float32 multiplication,
+ * rounded once - and is then quantised by lass_resample_encode's rule (gain: device, B floats).  The same kernel body:
+ * gain[b] == 1 gives lass_resample_encode's bytes.  The other arguments and limits are that entry point's. */
+int lass_resample_encode_gain(lass_ctx* ctx, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels,
+                              int L_in, int up, int down, const float* taps, int n_taps, int encoding, const float* gain,
+                              void* out_bytes, int64_t out_row_stride_bytes, int frames_out, unsigned* clipped, void* stream);
+
 /* Training-side data path ("next" row f4, mixer half; also the producer stage of the STFT pre-compute,
  * scripts/precompute_stfts.py:352-681): SegmentMixer.__call__ + dynamic_loudnorm (data/waveform_mixers.py:19-92) on the
  * device.  waveforms (B,L) -> mixture (B,L), segment (B,L).  For clip n:

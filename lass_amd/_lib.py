@@ -3,7 +3,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_int, c_int64, c_long, c_size_t, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_long, c_size_t, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LASS_HIP_LIB") or os.path.join(_HERE, "csrc", "liblass_hip.so")  # env: another build (A/B)
@@ -49,6 +49,13 @@ SYMBOLS = [
                                             c_void_p, c_int, c_void_p]),
     ("lass_resample_encode", c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int,
                                      c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    ("lass_loudness", c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_int, POINTER(c_double), c_void_p,
+                              c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    ("lass_resample_peak", c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int,
+                                   c_void_p, c_void_p]),
+    ("lass_loudness_gain", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_float, c_void_p, c_void_p, c_void_p]),
+    ("lass_resample_encode_gain", c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
+                                          c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     ("lass_segment_mix", c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p]),
     ("lass_multi_stft", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_void_p),

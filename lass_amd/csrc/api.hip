@@ -796,7 +796,7 @@ int compose_head(lass_ctx* c, int Q, bool sc, HeadHost* h) {
 
 extern "C" {
 
-int lass_version(void) { return 10700; }  // 1.7.0: cross-faded window seams (lass_separate_windows_faded, lass_istft_windows_faded); 1.6.0: ResUNet30 at the (2048, 320) STFT geometry (lass_create_stft, lass_stft_geometry); 1.5.0: windows of one long row (lass_separate_windows & co); 1.4.0: per-clip lengths (lass_separate_ragged & co); 1.3.0: CLAP text tower (lass_text_*, text.hip); 1.2.0: F(4x4,3x3) kernels, lass_set_graph_replay (1.1.0: multi-STFT model, fused iSTFT, graph replay)
+int lass_version(void) { return 10800; }  // 1.8.0: levelled export (lass_loudness, lass_resample_peak, lass_loudness_gain, lass_resample_encode_gain); 1.7.0: cross-faded window seams (lass_separate_windows_faded, lass_istft_windows_faded); 1.6.0: ResUNet30 at the (2048, 320) STFT geometry (lass_create_stft, lass_stft_geometry); 1.5.0: windows of one long row (lass_separate_windows & co); 1.4.0: per-clip lengths (lass_separate_ragged & co); 1.3.0: CLAP text tower (lass_text_*, text.hip); 1.2.0: F(4x4,3x3) kernels, lass_set_graph_replay (1.1.0: multi-STFT model, fused iSTFT, graph replay)
 
 const char* lass_last_error(const lass_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_err.c_str(); }
 
@@ -1381,14 +1381,9 @@ int lass_decode_resample_planar(lass_ctx* c, const void* raw, int64_t row_stride
                            n_taps, true, out, L_out, stream);
 }
 
-int lass_resample_encode(lass_ctx* c, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels, int L_in,
-                         int up, int down, const float* taps, int n_taps, int encoding, void* out_bytes,
-                         int64_t out_row_stride_bytes, int frames_out, unsigned* clipped, void* stream) {
-    const char* w = "lass_resample_encode: ";
-    if (!c) return LASS_ERR_ARG;
-    if (!planes || !out_bytes || B <= 0 || B > 65535 || L_in <= 0)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "planes, out_bytes non-NULL, 1 <= B <= 65535, L_in >= 1");
-    if (int r = check_resample_args(c, w, channels, encoding, up, down, taps, n_taps)) return r;
+// What the export entries ask of the planes and frames_out, after check_resample_args (w: the entry's "name: ").
+static int check_export_planes(lass_ctx* c, const char* w, const float* planes, int64_t row_stride, int64_t plane_stride, int channels,
+                               int L_in, int up, int down, int frames_out) {
     const long long ceiling = ((long long)L_in * up + down - 1) / down;
     if (frames_out < 1 || (long long)frames_out > ceiling)
         return fail(c, LASS_ERR_ARG, std::string(w) + "frames_out must lie in 1 ... ceil(L_in*up/down) = " + std::to_string(ceiling));
@@ -1396,6 +1391,18 @@ int lass_resample_encode(lass_ctx* c, const float* planes, int64_t row_stride, i
     if (plane_stride < L_in || row_stride < row_floats)
         return fail(c, LASS_ERR_ARG, std::string(w) + "plane_stride must hold a plane (" + std::to_string(L_in) +
                     " floats) and row_stride a recording (" + std::to_string(row_floats) + " floats)");
+    return 0;
+}
+
+// The two encode entries: one checked body (gain NULL: lass_resample_encode).
+static int resample_encode(lass_ctx* c, const char* w, const float* planes, int64_t row_stride, int64_t plane_stride, int B,
+                           int channels, int L_in, int up, int down, const float* taps, int n_taps, int encoding, void* out_bytes,
+                           int64_t out_row_stride_bytes, int frames_out, unsigned* clipped, const float* gain, void* stream) {
+    if (!c) return LASS_ERR_ARG;
+    if (!planes || !out_bytes || B <= 0 || B > 65535 || L_in <= 0)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "planes, out_bytes non-NULL, 1 <= B <= 65535, L_in >= 1");
+    if (int r = check_resample_args(c, w, channels, encoding, up, down, taps, n_taps)) return r;
+    if (int r = check_export_planes(c, w, planes, row_stride, plane_stride, channels, L_in, up, down, frames_out)) return r;
     const long long row_bytes = (long long)frames_out * channels * (encoding == LASS_WAV_PCM16 ? 2 : 4);
     if (out_row_stride_bytes < row_bytes || out_row_stride_bytes % 4 != 0)
         return fail(c, LASS_ERR_ARG, std::string(w) + "out_row_stride_bytes must be a multiple of 4 and hold a row (" +
@@ -1404,8 +1411,95 @@ int lass_resample_encode(lass_ctx* c, const float* planes, int64_t row_stride, i
     if (reinterpret_cast<uintptr_t>(planes) % 4 != 0 || reinterpret_cast<uintptr_t>(clipped) % 4 != 0)
         return fail(c, LASS_ERR_ARG, std::string(w) + "planes and clipped must be 4-byte aligned");
     if (int r = use_device(c)) return r;
-    HIP_TRY(c, lass_launch_resample_encode(planes, row_stride, plane_stride, B, channels, L_in, up, down, taps, n_taps, encoding,
-                                           out_bytes, out_row_stride_bytes, frames_out, clipped, (hipStream_t)stream));
+    if (gain)
+        HIP_TRY(c, lass_launch_resample_encode_gain(planes, row_stride, plane_stride, B, channels, L_in, up, down, taps, n_taps,
+                                                    encoding, out_bytes, out_row_stride_bytes, frames_out, clipped, gain,
+                                                    (hipStream_t)stream));
+    else
+        HIP_TRY(c, lass_launch_resample_encode(planes, row_stride, plane_stride, B, channels, L_in, up, down, taps, n_taps, encoding,
+                                               out_bytes, out_row_stride_bytes, frames_out, clipped, (hipStream_t)stream));
+    return 0;
+}
+
+int lass_resample_encode(lass_ctx* c, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels, int L_in,
+                         int up, int down, const float* taps, int n_taps, int encoding, void* out_bytes,
+                         int64_t out_row_stride_bytes, int frames_out, unsigned* clipped, void* stream) {
+    return resample_encode(c, "lass_resample_encode: ", planes, row_stride, plane_stride, B, channels, L_in, up, down, taps, n_taps,
+                           encoding, out_bytes, out_row_stride_bytes, frames_out, clipped, nullptr, stream);
+}
+
+int lass_resample_encode_gain(lass_ctx* c, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels,
+                              int L_in, int up, int down, const float* taps, int n_taps, int encoding, const float* gain,
+                              void* out_bytes, int64_t out_row_stride_bytes, int frames_out, unsigned* clipped, void* stream) {
+    const char* w = "lass_resample_encode_gain: ";
+    if (!c) return LASS_ERR_ARG;
+    if (!gain || reinterpret_cast<uintptr_t>(gain) % 4 != 0) return fail(c, LASS_ERR_ARG, std::string(w) + "gain non-NULL, 4-byte aligned");
+    return resample_encode(c, w, planes, row_stride, plane_stride, B, channels, L_in, up, down, taps, n_taps, encoding, out_bytes,
+                           out_row_stride_bytes, frames_out, clipped, gain, stream);
+}
+
+int lass_resample_peak(lass_ctx* c, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels, int L_in,
+                       int up, int down, const float* taps, int n_taps, int frames_out, float* peak, void* stream) {
+    const char* w = "lass_resample_peak: ";
+    if (!c) return LASS_ERR_ARG;
+    if (!planes || !peak || B <= 0 || B > 65535 || L_in <= 0)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "planes, peak non-NULL, 1 <= B <= 65535, L_in >= 1");
+    if (int r = check_resample_args(c, w, channels, LASS_WAV_F32, up, down, taps, n_taps)) return r;
+    if (int r = check_export_planes(c, w, planes, row_stride, plane_stride, channels, L_in, up, down, frames_out)) return r;
+    if (reinterpret_cast<uintptr_t>(planes) % 4 != 0 || reinterpret_cast<uintptr_t>(peak) % 4 != 0)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "planes and peak must be 4-byte aligned");
+    if (int r = use_device(c)) return r;
+    HIP_TRY(c, lass_launch_resample_peak(planes, row_stride, plane_stride, B, channels, L_in, up, down, taps, n_taps, frames_out, peak,
+                                         (hipStream_t)stream));
+    return 0;
+}
+
+int lass_loudness(lass_ctx* c, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels, int L,
+                  const int* lengths, int hop, const double* coef, const float* weights, double* out, double* blocks, int nb_max,
+                  void* scratch, size_t scratch_bytes, void* stream) {
+    const char* w = "lass_loudness: ";
+    if (!c) return LASS_ERR_ARG;
+    if (!planes || !coef || !out || B <= 0 || L <= 0) return fail(c, LASS_ERR_ARG, std::string(w) + "planes, coef, out non-NULL, B >= 1, L >= 1");
+    if (channels < 1 || channels > 8 || (long long)B * channels > 65535)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "1 ... 8 channels, B * channels <= 65535");
+    if (hop < 1 || hop > LASS_LOUDNESS_MAX_HOP)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "hop (rate / 10) must lie in 1 ... " + std::to_string(LASS_LOUDNESS_MAX_HOP));
+    const long long row_floats = (long long)(channels - 1) * plane_stride + L;
+    if (plane_stride < L || row_stride < row_floats)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "plane_stride must hold a plane (" + std::to_string(L) +
+                    " floats) and row_stride a recording (" + std::to_string(row_floats) + " floats)");
+    const long long bins = L / hop, nb = bins >= 4 ? bins - 3 : 0;
+    if (blocks && (long long)nb_max < nb)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "nb_max must hold the blocks of L samples (" + std::to_string(nb) + ")");
+    const size_t need = (size_t)5 * B * channels * bins * sizeof(double);
+    if (need && (!scratch || scratch_bytes < need))
+        return fail(c, LASS_ERR_ARG, std::string(w) + "scratch must hold 5 * B * channels * (L / hop) doubles (" + std::to_string(need) + " bytes)");
+    if (reinterpret_cast<uintptr_t>(planes) % 4 != 0 || reinterpret_cast<uintptr_t>(lengths) % 4 != 0 ||
+        reinterpret_cast<uintptr_t>(weights) % 4 != 0 || reinterpret_cast<uintptr_t>(out) % 8 != 0 ||
+        reinterpret_cast<uintptr_t>(blocks) % 8 != 0 || reinterpret_cast<uintptr_t>(scratch) % 8 != 0)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "planes, lengths, weights 4-byte aligned; out, blocks, scratch 8-byte aligned");
+    LoudnessFilter f;
+    if (!lass_loudness_filter(coef, hop, &f))
+        return fail(c, LASS_ERR_ARG, std::string(w) + "coef must be finite, both biquads with their poles inside the unit circle");
+    if (int r = use_device(c)) return r;
+    HIP_TRY(c, lass_launch_loudness(planes, row_stride, plane_stride, B, channels, L, lengths, hop, f, weights, out, blocks, nb_max,
+                                    static_cast<double*>(scratch), (hipStream_t)stream));
+    return 0;
+}
+
+int lass_loudness_gain(lass_ctx* c, const double* loudness, const float* peak, int B, double target_lufs, float ceiling, float* gain,
+                       int* limited, void* stream) {
+    const char* w = "lass_loudness_gain: ";
+    if (!c) return LASS_ERR_ARG;
+    if (!loudness || !gain || B <= 0) return fail(c, LASS_ERR_ARG, std::string(w) + "loudness, gain non-NULL, B >= 1");
+    if (!(ceiling >= 0.0f) || std::isinf(ceiling)) return fail(c, LASS_ERR_ARG, std::string(w) + "ceiling must be finite and >= 0 (0: none)");
+    if (ceiling > 0.0f && !peak) return fail(c, LASS_ERR_ARG, std::string(w) + "a ceiling needs peak");
+    if (std::isinf(target_lufs)) return fail(c, LASS_ERR_ARG, std::string(w) + "target_lufs must be finite, or NaN for none");
+    if (reinterpret_cast<uintptr_t>(loudness) % 8 != 0 || reinterpret_cast<uintptr_t>(peak) % 4 != 0 ||
+        reinterpret_cast<uintptr_t>(gain) % 4 != 0 || reinterpret_cast<uintptr_t>(limited) % 4 != 0)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "loudness 8-byte aligned; peak, gain, limited 4-byte aligned");
+    if (int r = use_device(c)) return r;
+    HIP_TRY(c, lass_launch_loudness_gain(loudness, peak, B, target_lufs, ceiling, gain, limited, (hipStream_t)stream));
     return 0;
 }
 

@@ -9,6 +9,10 @@
 //           that LDS and global dwords line up.
 // The stage is then written out as contiguous dwords; a 2-byte store is made only where the tile's byte range starts or ends off
 // a 4-byte boundary (PCM16 alone, and with an even tile the end of the row alone).
+//
+// Both kernels are templates over where an output y goes (Sink): quantised into the stage (kEncode, lass_resample_encode), the
+// same after one multiplication by the row's gain (kEncodeGain, lass_resample_encode_gain), or into the row's peak |y| with no
+// stage and no store (kPeak, lass_resample_peak).  Up to that point the three are one body, so they see the same y.
 #include "../../include/lass_hip.h"
 #include "kernels.h"
 
@@ -60,10 +64,51 @@ __device__ __forceinline__ void store_tile(const unsigned char* stage0, unsigned
 
 __device__ __forceinline__ int sample_bytes(int enc) { return enc == LASS_WAV_PCM16 ? 2 : 4; }
 
+enum Sink { kEncode, kEncodeGain, kPeak };
+
+// the row's gain (1 where the sink takes none)
+template <Sink kSink>
+__device__ __forceinline__ float row_gain(const float* __restrict__ gain) {
+    if constexpr (kSink == kEncodeGain) return gain[blockIdx.y];
+    return 1.0f;
+}
+
+// output y, sample k of the tile: into the stage (times g, rounded once, for kEncodeGain), or its |y| bits into pk (NaN skipped)
+template <Sink kSink>
+__device__ __forceinline__ void emit(unsigned char* stage, int k, float y, float g, int enc, unsigned* clips, unsigned* pk) {
+    if constexpr (kSink == kPeak) {
+        const unsigned a = __float_as_uint(y) & 0x7fffffffu;
+        if (a <= 0x7f800000u && a > *pk) *pk = a;
+    } else {
+        if constexpr (kSink == kEncodeGain) y = __fmul_rn(g, y);
+        stage_put(stage, k, y, enc, clips);
+    }
+}
+
+// the tile's end: the stage to memory and the clip count, or the workgroup's peak, to the row's counter
+template <Sink kSink>
+__device__ __forceinline__ void finish(const unsigned char* stage0, unsigned char* __restrict__ out, long long out_row_stride, size_t a,
+                                       size_t nbytes, int tid, unsigned clips, unsigned* __restrict__ clipped, unsigned pk,
+                                       unsigned* __restrict__ peak) {
+    if constexpr (kSink == kPeak) {
+        for (int w = 32; w > 0; w >>= 1) {
+            const unsigned o = (unsigned)__shfl_xor((int)pk, w);
+            pk = o > pk ? o : pk;
+        }
+        if ((tid & 63) == 0 && pk) atomicMax(peak + blockIdx.y, pk);
+    } else {
+        __syncthreads();
+        store_tile(stage0, out + (size_t)blockIdx.y * out_row_stride, a, nbytes, tid);
+        if (clipped && clips) atomicAdd(clipped + blockIdx.y, clips);
+    }
+}
+
 // up == down == 1: quantise and interleave only
+template <Sink kSink>
 __global__ __launch_bounds__(kThreads) void k_encode(const float* __restrict__ planes, long long row_stride, long long plane_stride,
                                                      int ch, int enc, unsigned char* __restrict__ out, long long out_row_stride,
-                                                     int frames_out, unsigned* __restrict__ clipped) {
+                                                     int frames_out, unsigned* __restrict__ clipped, const float* __restrict__ gain,
+                                                     unsigned* __restrict__ peak) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     unsigned char* stage0 = reinterpret_cast<unsigned char*>(lds);
     const int tid = threadIdx.x;
@@ -73,20 +118,21 @@ __global__ __launch_bounds__(kThreads) void k_encode(const float* __restrict__ p
     const size_t a = (size_t)n0 * ch * bps;
     unsigned char* stage = stage0 + (a & 3);
     const float* x = planes + (size_t)blockIdx.y * row_stride + n0;
-    unsigned clips = 0;
+    const float g = row_gain<kSink>(gain);
+    unsigned clips = 0, pk = 0;
     for (int c = 0; c < ch; ++c)
-        for (int i = tid; i < nout; i += kThreads) stage_put(stage, i * ch + c, x[(size_t)c * plane_stride + i], enc, &clips);
-    __syncthreads();
-    store_tile(stage0, out + (size_t)blockIdx.y * out_row_stride, a, (size_t)nout * ch * bps, tid);
-    if (clipped && clips) atomicAdd(clipped + blockIdx.y, clips);
+        for (int i = tid; i < nout; i += kThreads) emit<kSink>(stage, i * ch + c, x[(size_t)c * plane_stride + i], g, enc, &clips, &pk);
+    finish<kSink>(stage0, out, out_row_stride, a, (size_t)nout * ch * bps, tid, clips, clipped, pk, peak);
 }
 
+template <Sink kSink>
 __global__ __launch_bounds__(kThreads) void k_resample_encode(const float* __restrict__ planes, long long row_stride,
                                                               long long plane_stride, int L_in, int ch, int enc, int up, int down,
                                                               const float* __restrict__ taps, int n_taps, int J, int tile,
                                                               int span_floats, unsigned char* __restrict__ out,
                                                               long long out_row_stride, int frames_out,
-                                                              unsigned* __restrict__ clipped) {
+                                                              unsigned* __restrict__ clipped, const float* __restrict__ gain,
+                                                              unsigned* __restrict__ peak) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x;
     const int bps = sample_bytes(enc);
@@ -97,43 +143,67 @@ __global__ __launch_bounds__(kThreads) void k_resample_encode(const float* __res
     unsigned char* stage = stage0 + (a & 3);
     fir_table(T, taps, n_taps);
 
-    unsigned clips = 0;
+    const float g = row_gain<kSink>(gain);
+    unsigned clips = 0, pk = 0;
     for (int c = 0; c < ch; ++c) {
         const float* x0 = rec + (size_t)c * plane_stride;
         if (c) __syncthreads();                           // the previous channel's reads of the span
         fir_fill(T, L_in, [&](long long m) { return x0[m]; });
         __syncthreads();
-        for (int i = tid; i < T.nout; i += kThreads) stage_put(stage, i * ch + c, fir_output(T, i), enc, &clips);
+        for (int i = tid; i < T.nout; i += kThreads) emit<kSink>(stage, i * ch + c, fir_output(T, i), g, enc, &clips, &pk);
     }
-    __syncthreads();
-    store_tile(stage0, out + (size_t)blockIdx.y * out_row_stride, a, (size_t)T.nout * ch * bps, tid);
-    if (clipped && clips) atomicAdd(clipped + blockIdx.y, clips);
+    finish<kSink>(stage0, out, out_row_stride, a, (size_t)T.nout * ch * bps, tid, clips, clipped, pk, peak);
 }
 
 }  // namespace
 
-hipError_t lass_launch_resample_encode(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L_in,
-                                       int up, int down, const float* taps, int n_taps, int enc, void* out, long long out_row_stride,
-                                       int frames_out, unsigned* clipped, hipStream_t stream) {
+// One launch for the three sinks.  kPeak keeps no stage (enc, out and clipped unused), so its tiles are as large as the span allows.
+template <Sink kSink>
+static hipError_t launch(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L_in, int up, int down,
+                         const float* taps, int n_taps, int enc, unsigned char* o, long long out_row_stride, int frames_out,
+                         unsigned* clipped, const float* gain, unsigned* peak, hipStream_t stream) {
     if (B <= 0 || B > 65535 || ch < 1 || ch > 8 || L_in <= 0 || frames_out <= 0 || up < 1 || down < 1) return hipErrorInvalidValue;
-    unsigned char* o = static_cast<unsigned char*>(out);
     const int bps = enc == LASS_WAV_PCM16 ? 2 : 4;
     if (up == 1 && down == 1) {
-        const size_t lds = (size_t)kTilePlain * ch * bps + 4;
-        hipLaunchKernelGGL(k_encode, dim3((frames_out + kTilePlain - 1) / kTilePlain, B), dim3(kThreads), lds, stream, planes,
-                           row_stride, plane_stride, ch, enc, o, out_row_stride, frames_out, clipped);
+        const size_t lds = kSink == kPeak ? 0 : (size_t)kTilePlain * ch * bps + 4;
+        hipLaunchKernelGGL(k_encode<kSink>, dim3((frames_out + kTilePlain - 1) / kTilePlain, B), dim3(kThreads), lds, stream, planes,
+                           row_stride, plane_stride, ch, enc, o, out_row_stride, frames_out, clipped, gain, peak);
         return hipGetLastError();
     }
     // the largest tile whose span and stage fit beside the table (one frame needs J floats of span and at most 9 of stage: it
     // always fits under the caps); the stage starts on a multiple of four floats
     FirPlan P;
-    hipError_t e = fir_plan(reinterpret_cast<const void*>(k_resample_encode), up, down, n_taps, frames_out, [&](int t) {
+    hipError_t e = fir_plan(reinterpret_cast<const void*>(k_resample_encode<kSink>), up, down, n_taps, frames_out, [&](int t) {
         const size_t head = (lass_resample_table_floats(up, n_taps) + lass_resample_span_floats(up, down, n_taps, t) + 3) & ~(size_t)3;
-        return head + ((size_t)t * ch * bps + 4 + 3) / 4;
+        return kSink == kPeak ? head : head + ((size_t)t * ch * bps + 4 + 3) / 4;
     }, &P);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_resample_encode, dim3(P.nblk, B), dim3(kThreads), P.lds, stream, planes, row_stride, plane_stride, L_in, ch,
-                       enc, up, down, taps, n_taps, P.J, P.tile, (int)lass_resample_span_floats(up, down, n_taps, P.tile), o,
-                       out_row_stride, frames_out, clipped);
+    hipLaunchKernelGGL(k_resample_encode<kSink>, dim3(P.nblk, B), dim3(kThreads), P.lds, stream, planes, row_stride, plane_stride, L_in,
+                       ch, enc, up, down, taps, n_taps, P.J, P.tile, (int)lass_resample_span_floats(up, down, n_taps, P.tile), o,
+                       out_row_stride, frames_out, clipped, gain, peak);
     return hipGetLastError();
+}
+
+hipError_t lass_launch_resample_encode(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L_in,
+                                       int up, int down, const float* taps, int n_taps, int enc, void* out, long long out_row_stride,
+                                       int frames_out, unsigned* clipped, hipStream_t stream) {
+    return launch<kEncode>(planes, row_stride, plane_stride, B, ch, L_in, up, down, taps, n_taps, enc, static_cast<unsigned char*>(out),
+                           out_row_stride, frames_out, clipped, nullptr, nullptr, stream);
+}
+
+hipError_t lass_launch_resample_encode_gain(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L_in,
+                                            int up, int down, const float* taps, int n_taps, int enc, void* out,
+                                            long long out_row_stride, int frames_out, unsigned* clipped, const float* gain,
+                                            hipStream_t stream) {
+    return launch<kEncodeGain>(planes, row_stride, plane_stride, B, ch, L_in, up, down, taps, n_taps, enc,
+                               static_cast<unsigned char*>(out), out_row_stride, frames_out, clipped, gain, nullptr, stream);
+}
+
+hipError_t lass_launch_resample_peak(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L_in, int up,
+                                     int down, const float* taps, int n_taps, int frames_out, float* peak, hipStream_t stream) {
+    if (B <= 0) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(peak, 0, (size_t)B * sizeof(float), stream);
+    if (e != hipSuccess) return e;
+    return launch<kPeak>(planes, row_stride, plane_stride, B, ch, L_in, up, down, taps, n_taps, LASS_WAV_F32, nullptr, 0, frames_out,
+                         nullptr, nullptr, reinterpret_cast<unsigned*>(peak), stream);
 }

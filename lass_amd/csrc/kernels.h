@@ -294,3 +294,34 @@ size_t lass_resample_span_floats(int up, int down, int n_taps, int tile);  // th
 hipError_t lass_launch_resample_encode(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L_in,
                                        int up, int down, const float* taps, int n_taps, int enc, void* out, long long out_row_stride,
                                        int frames_out, unsigned* clipped, hipStream_t stream);
+// The same with a gain: every y of row b becomes fl(gain[b] * y) before it is quantised (gain: B device floats).  One kernel body
+// with the entry above; gain[b] == 1 gives its bytes.
+hipError_t lass_launch_resample_encode_gain(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L_in,
+                                            int up, int down, const float* taps, int n_taps, int enc, void* out,
+                                            long long out_row_stride, int frames_out, unsigned* clipped, const float* gain,
+                                            hipStream_t stream);
+// peak[b] = max |y| over the planes of row b and n < frames_out, y the value the two entries above quantise (the same kernel body
+// up to where y goes); a NaN is skipped.  peak (B floats) is zero-filled here, then raised by integer atomic max on |y|'s bits.
+hipError_t lass_launch_resample_peak(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L_in, int up,
+                                     int down, const float* taps, int n_taps, int frames_out, float* peak, hipStream_t stream);
+
+// ---- loudness.hip -------------------------------------------------------------------------------------------------
+// K-weighting as the kernels take it: the two biquads (b0 b1 b2 a1 a2 of the shelf, then of the high-pass) and the powers of the
+// cascade's 4 x 4 state matrix that carry a state over one lane's samples and over one hop bin, row-major.
+struct LoudnessFilter {
+    double coef[10];
+    double lane_step[16];
+    double bin_step[16];
+};
+int lass_loudness_lanes(int hop);  // lanes of the wave that share a hop bin: the largest divisor of hop up to 64
+// f <- coef and the two powers for `hop`; false for a coefficient that is not finite or a pole on or outside the unit circle
+bool lass_loudness_filter(const double* coef, int hop, LoudnessFilter* f);
+// BS.1770-4 gated loudness of B recordings of ch planes (addressed as lass_launch_resample_encode's), lengths[b] <= L samples
+// each (NULL: L; clamped to 0 ... L): out (B,3) = {LUFS or -inf, blocks, blocks past both gates}; blocks (B, nb_max), optional:
+// the block powers, 0 past a recording's own count.  scratch: 5 * B * ch * (L / hop) doubles.
+hipError_t lass_launch_loudness(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L,
+                                const int* lengths, int hop, const LoudnessFilter& f, const float* weights, double* out,
+                                double* blocks, int nb_max, double* scratch, hipStream_t stream);
+// lass_loudness_gain's rule, one thread per row
+hipError_t lass_launch_loudness_gain(const double* loudness, const float* peak, int B, double target, float ceiling, float* gain,
+                                     int* limited, hipStream_t stream);

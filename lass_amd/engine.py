@@ -668,19 +668,19 @@ class Engine:
         return y[0] if one else y
 
     def resample_encode(self, planes: torch.Tensor, rate_in: int, rate_out: int, encoding: str, frames_out: Optional[int] = None,
-                        out: Optional[torch.Tensor] = None, clipped: Optional[torch.Tensor] = None) -> torch.Tensor:
+                        out: Optional[torch.Tensor] = None, clipped: Optional[torch.Tensor] = None,
+                        gain: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The export side of `decode_resample_planar`, on the device: planes (B, C, L) or (C, L) float32 at rate_in (any strides
         with contiguous samples; C 1 ... 8) -> (B, frames_out * C * sample bytes) uint8, each row a WAV data chunk at rate_out
         ("pcm16" / "pcm32" / "f32", frames interleaved) as wavio.write_wav_* would write the resampled planes.  frames_out (default
         and at most ceil(L * up / down)) truncates.  `out`: a (B, >= row bytes) uint8 tensor written in place, rows a multiple of 4
         bytes apart, bytes past a row's end left alone; `clipped`: (B,) int32 counters, zero-filled by the caller, that receive
-        the number of PCM samples the clip changed.  The filter is lass_amd.resample.design_taps; a ratio beyond the kernel's tap
-        cap raises LassError (resample.within_cap tells beforehand)."""
+        the number of PCM samples the clip changed.  `gain`: (B,) float32 on the device; every resampled sample of row b is
+        multiplied by gain[b] (one float32 rounding) before it is quantised (lass_resample_encode_gain; without it
+        lass_resample_encode, as ever).  The filter is lass_amd.resample.design_taps; a ratio beyond the kernel's tap cap raises
+        LassError (resample.within_cap tells beforehand)."""
         from . import resample as rs
-        if planes.dim() == 2:
-            planes = planes[None]
-        if planes.device != self.device or planes.dtype != torch.float32 or planes.dim() != 3 or planes.stride(2) != 1:
-            raise _lib.LassError(f"planes must be a (B, C, L) or (C, L) float32 tensor on {self.device} with contiguous samples")
+        planes, row_stride, plane_stride = self._planes(planes)
         if encoding not in rs.ENCODINGS:
             raise _lib.LassError(f"encoding must be one of {sorted(rs.ENCODINGS)}")
         B, C, L = planes.shape
@@ -703,14 +703,101 @@ class Engine:
         if clipped is not None and (tuple(clipped.shape) != (B,) or clipped.dtype != torch.int32 or clipped.device != self.device
                                     or not clipped.is_contiguous()):
             raise _lib.LassError(f"clipped must be a contiguous int32 ({B},) tensor on {self.device}")
-        plane_stride = planes.stride(1) if C > 1 else L                      # (one plane, one row: no stride to honour)
-        row_stride = planes.stride(0) if B > 1 else (C - 1) * plane_stride + L
         out_stride = out.stride(0) if B > 1 else (row_bytes + 3) // 4 * 4
+        if gain is not None:
+            if tuple(gain.shape) != (B,) or gain.dtype != torch.float32 or gain.device != self.device or not gain.is_contiguous():
+                raise _lib.LassError(f"gain must be a contiguous float32 ({B},) tensor on {self.device}")
+            rc = self.lib.lass_resample_encode_gain(self.ctx, _ptr(planes), row_stride, plane_stride, B, C, L, up, down, _ptr(taps),
+                                                    taps.numel() if fir else 1, rs.ENCODINGS[encoding], _ptr(gain), _ptr(out),
+                                                    out_stride, frames_out, _ptr(clipped), _stream(self.device))
+            _lib.check(self.ctx, rc, "lass_resample_encode_gain")
+            return out[:, :row_bytes]
         rc = self.lib.lass_resample_encode(self.ctx, _ptr(planes), row_stride, plane_stride, B, C, L, up, down, _ptr(taps),
                                            taps.numel() if fir else 1, rs.ENCODINGS[encoding], _ptr(out), out_stride, frames_out,
                                            _ptr(clipped), _stream(self.device))
         _lib.check(self.ctx, rc, "lass_resample_encode")
         return out[:, :row_bytes]
+
+    def _planes(self, planes: torch.Tensor):
+        """(planes as (B, C, L), row stride, plane stride) of a (B, C, L) or (C, L) float32 tensor with contiguous samples."""
+        if planes.dim() == 2:
+            planes = planes[None]
+        if planes.device != self.device or planes.dtype != torch.float32 or planes.dim() != 3 or planes.stride(2) != 1:
+            raise _lib.LassError(f"planes must be a (B, C, L) or (C, L) float32 tensor on {self.device} with contiguous samples")
+        B, C, L = planes.shape
+        plane_stride = planes.stride(1) if C > 1 else L                      # (one plane, one row: no stride to honour)
+        row_stride = planes.stride(0) if B > 1 else (C - 1) * plane_stride + L
+        return planes, row_stride, plane_stride
+
+    def resample_peak(self, planes: torch.Tensor, rate_in: int, rate_out: int, frames_out: Optional[int] = None) -> torch.Tensor:
+        """(B,) float32: max |y| over the channels and the first frames_out frames of each recording, y the very float32 values
+        `resample_encode` of the same arguments quantises (lass_resample_peak); a NaN is skipped."""
+        from . import resample as rs
+        planes, row_stride, plane_stride = self._planes(planes)
+        B, C, L = planes.shape
+        up, down = rs.ratio(rate_in, rate_out)
+        ceiling = rs.out_len(L, up, down)
+        frames_out = ceiling if frames_out is None else int(frames_out)
+        if not 1 <= frames_out <= ceiling:
+            raise _lib.LassError(f"frames_out must lie in 1 ... ceil(L * up / down) = {ceiling}")
+        fir = (up, down) != (1, 1)
+        if fir and not rs.within_cap(up, down):
+            raise _lib.LassError(f"resampling {rate_in} -> {rate_out} Hz needs {rs.n_taps(up, down)} taps, over the device "
+                                 f"kernel's cap of {rs.MAX_TAPS}")
+        taps = rs.device_taps(up, down, self.device) if fir else None
+        peak = torch.empty(B, dtype=torch.float32, device=self.device)
+        rc = self.lib.lass_resample_peak(self.ctx, _ptr(planes), row_stride, plane_stride, B, C, L, up, down, _ptr(taps),
+                                         taps.numel() if fir else 1, frames_out, _ptr(peak), _stream(self.device))
+        _lib.check(self.ctx, rc, "lass_resample_peak")
+        return peak
+
+    def loudness(self, planes: torch.Tensor, rate: int, lengths=None, weights=None, return_blocks: bool = False,
+                 return_counts: bool = False):
+        """ITU-R BS.1770-4 gated integrated loudness on the device (lass_loudness; lass_amd.loudness is its float64 definition):
+        planes (B, C, L) or (C, L) float32 at `rate` (any strides with contiguous samples; C 1 ... 8), lengths (B,) int32 (each
+        <= L; default L), weights (C,) float32 channel weights (default ones) -> (B,) float64 LUFS, -inf where no block survives.
+        return_blocks: also the (B, nb) float64 block powers (zeros past a recording's own count); return_counts: also a (B, 2)
+        float64 tensor of (blocks, blocks past both gates).  Order of the extras: blocks, counts."""
+        from . import loudness as ld
+        planes, row_stride, plane_stride = self._planes(planes)
+        B, C, L = planes.shape
+        coef = ld.coefficients(rate)
+        hop = int(rate) // 10
+        if lengths is not None:
+            lengths = torch.as_tensor(lengths).to(device=self.device, dtype=torch.int32).contiguous()
+            if tuple(lengths.shape) != (B,):
+                raise _lib.LassError(f"lengths must have shape ({B},)")
+        if weights is not None:
+            weights = torch.as_tensor(weights).to(device=self.device, dtype=torch.float32).contiguous()
+            if tuple(weights.shape) != (C,):
+                raise _lib.LassError(f"weights must have shape ({C},)")
+        nb = max(ld.n_blocks(L, rate), 0)
+        out = torch.empty(B, 3, dtype=torch.float64, device=self.device)
+        blocks = torch.empty(B, nb, dtype=torch.float64, device=self.device) if return_blocks else None
+        scratch = torch.empty(max(5 * B * C * (L // hop), 1), dtype=torch.float64, device=self.device)
+        rc = self.lib.lass_loudness(self.ctx, _ptr(planes), row_stride, plane_stride, B, C, L, _ptr(lengths), hop,
+                                    (c_double * 10)(*coef.tolist()), _ptr(weights), _ptr(out), _ptr(blocks), nb, _ptr(scratch),
+                                    scratch.numel() * 8, _stream(self.device))
+        _lib.check(self.ctx, rc, "lass_loudness")
+        res = (out[:, 0],) + ((blocks,) if return_blocks else ()) + ((out[:, 1:],) if return_counts else ())
+        return res[0] if len(res) == 1 else res
+
+    def loudness_gain(self, loudness: torch.Tensor, peak: Optional[torch.Tensor] = None, target: Optional[float] = None,
+                      ceiling: Optional[float] = None):
+        """((B,) float32 gain, (B,) int32 flags of the rows the ceiling bit) from (B,) float64 loudness and (B,) float32 peak, on
+        the device: lass_amd.loudness.gain_for's rule (lass_loudness_gain).  target in LUFS or None, ceiling linear or None."""
+        loudness = loudness.to(device=self.device, dtype=torch.float64).contiguous()
+        B = loudness.shape[0]
+        if peak is not None:
+            peak = peak.to(device=self.device, dtype=torch.float32).contiguous()
+            if tuple(peak.shape) != (B,):
+                raise _lib.LassError(f"peak must have shape ({B},)")
+        gain = torch.empty(B, dtype=torch.float32, device=self.device)
+        limited = torch.empty(B, dtype=torch.int32, device=self.device)
+        rc = self.lib.lass_loudness_gain(self.ctx, _ptr(loudness), _ptr(peak), B, float("nan") if target is None else float(target),
+                                         0.0 if ceiling is None else float(ceiling), _ptr(gain), _ptr(limited), _stream(self.device))
+        _lib.check(self.ctx, rc, "lass_loudness_gain")
+        return gain, limited
 
     def segment_mix(self, waveforms: torch.Tensor, mix_num: torch.Tensor, comp_db: torch.Tensor, noise_db: torch.Tensor):
         """data/waveform_mixers.py:19-62 on the device with the random draws given: waveforms (B,L), mix_num (B) int32,

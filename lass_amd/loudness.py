@@ -1,0 +1,206 @@
+"""Programme loudness, host side: the K-weighting filter design, the float64 definition of the gated ITU-R BS.1770-4 integrated
+loudness that the device meter (csrc/loudness.hip) is held to, and the scalar gain rule of the levelled export.
+
+Nothing of this is ported: the reference measures with `pyloudnorm` (data/waveform_mixers.py) and applies `utils.loudness`'s
+gain by hand; the meter here is written from the recommendation.  Its pins are the EBU Tech 3341 tones (tests/test_loudness_cpu.py)
+and, for the kernels, this module.
+
+K-weighting is two biquads: a high shelf (+4 dB above 1.5 kHz) and a high-pass (the RLB curve, 38 Hz).  The recommendation
+tabulates them at 48 kHz only; `k_weighting` redesigns both for the rate asked from the analogue prototypes behind that table,
+with the audio-EQ-cookbook bilinear forms (shelf: G = 4 dB, Q = 1/sqrt 2, fc = 1500 Hz; high-pass: Q = 0.5, fc = 38 Hz).  At
+48 kHz they differ from the table in the fourth digit, which is 0.04 LU on the EBU tones.
+
+The cascade runs in direct form II transposed with zero initial state,
+
+    y1 = b0 x + z1;  z1 = b1 x - a1 y1 + z2;  z2 = b2 x - a2 y1          (stage 1, then the same on y1 for stage 2)
+
+which is a 4-state affine recurrence s[n+1] = M s[n] + v x[n].  Both this module and the kernels cut the time axis into chunks,
+run every chunk from a zero state, carry the true states over the chunk ends with a power of M, and add each chunk's response
+to its true initial state - here with numpy over all chunks at once, because a Python loop over millions of samples is not an
+option.  In float64 the split changes the result by rounding only (1e-15 relative).
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import numpy as np
+
+ABSOLUTE_GATE = -70.0     # LUFS
+RELATIVE_GATE = -10.0     # LU under the absolute-gated loudness
+OFFSET = -0.691
+
+
+def k_weighting(rate: int):
+    """((b, a) of the high shelf, (b, a) of the high-pass) for `rate`, float64 arrays of 3 with a[0] == 1."""
+    rate = int(rate)
+    if rate % 10 != 0 or rate < 8000:
+        raise ValueError("the meter needs a rate of at least 8000 Hz that is a multiple of 10 (100 ms hops of whole samples)")
+
+    def shelf(gain_db, q, fc):
+        A = 10.0 ** (gain_db / 40.0)
+        w0 = 2.0 * np.pi * fc / rate
+        alpha, c = np.sin(w0) / (2.0 * q), np.cos(w0)
+        s = 2.0 * np.sqrt(A) * alpha
+        b = np.array([A * ((A + 1) + (A - 1) * c + s), -2 * A * ((A - 1) + (A + 1) * c), A * ((A + 1) + (A - 1) * c - s)])
+        a = np.array([(A + 1) - (A - 1) * c + s, 2 * ((A - 1) - (A + 1) * c), (A + 1) - (A - 1) * c - s])
+        return b / a[0], a / a[0]
+
+    def highpass(q, fc):
+        w0 = 2.0 * np.pi * fc / rate
+        alpha, c = np.sin(w0) / (2.0 * q), np.cos(w0)
+        b = np.array([(1 + c) / 2, -(1 + c), (1 + c) / 2])
+        a = np.array([1 + alpha, -2 * c, 1 - alpha])
+        return b / a[0], a / a[0]
+
+    return shelf(4.0, 1.0 / np.sqrt(2.0), 1500.0), highpass(0.5, 38.0)
+
+
+def coefficients(rate: int) -> np.ndarray:
+    """`k_weighting(rate)` as the ten float64 the C-ABI takes: b0 b1 b2 a1 a2 of stage 1, then of stage 2."""
+    (b1, a1), (b2, a2) = k_weighting(rate)
+    return np.array([b1[0], b1[1], b1[2], a1[1], a1[2], b2[0], b2[1], b2[2], a2[1], a2[2]], dtype=np.float64)
+
+
+def _biquad(x: np.ndarray, b, a, chunk: int) -> np.ndarray:
+    """One stage over the last axis of x (P, N), in x's dtype, the time axis cut into chunks of `chunk` samples."""
+    dt = x.dtype.type
+    b0, b1, b2, a1, a2 = dt(b[0]), dt(b[1]), dt(b[2]), dt(a[1]), dt(a[2])
+    P, N = x.shape
+    K = max(1, min(int(chunk), N))
+    nc = -(-N // K)
+    xp = np.zeros((P, nc * K), dtype=x.dtype)
+    xp[:, :N] = x
+    xp = xp.reshape(P, nc, K)
+    y = np.empty_like(xp)
+    z1, z2 = np.zeros((P, nc), dtype=x.dtype), np.zeros((P, nc), dtype=x.dtype)
+    for k in range(K):                                  # every chunk from a zero state, all chunks at once
+        xk = xp[:, :, k]
+        yk = b0 * xk + z1
+        z1 = b1 * xk - a1 * yk + z2
+        z2 = b2 * xk - a2 * yk
+        y[:, :, k] = yk
+    if nc > 1:
+        # the response of a chunk to its initial state: outputs R (K, 2) and end state E (2, 2), from the unit states
+        R, u1, u2 = np.empty((K, 2), dtype=x.dtype), np.array([1, 0], dtype=x.dtype), np.array([0, 1], dtype=x.dtype)
+        for k in range(K):
+            R[k] = u1
+            u1, u2 = -a1 * R[k] + u2, -a2 * R[k]
+        E = np.stack([u1, u2])
+        s = np.zeros((P, 2), dtype=x.dtype)
+        S0 = np.empty((P, nc, 2), dtype=x.dtype)
+        for j in range(nc):                             # the carry: one short serial pass
+            S0[:, j] = s
+            s = s @ E.T + np.stack([z1[:, j], z2[:, j]], axis=1)
+        y += np.einsum("pjs,ks->pjk", S0, R)
+    return y.reshape(P, nc * K)[:, :N]
+
+
+def k_weighted(x, rate: int, dtype=np.float64, chunk: Optional[int] = None) -> np.ndarray:
+    """The K-weighted signal of x (C, N) or (N,), zero initial state, evaluated in `dtype` (signal, coefficients, state).  chunk:
+    samples per chunk of the split evaluation (module docstring); the default is about sqrt(N) in float64 and the whole signal -
+    the plain sample-by-sample recurrence - in any other dtype."""
+    dtype = np.dtype(dtype)
+    x = np.asarray(x, dtype=dtype)
+    one = x.ndim == 1
+    y = np.atleast_2d(x)
+    if y.shape[1] == 0:
+        return x.copy()
+    if chunk is None:
+        chunk = max(256, int(np.sqrt(y.shape[1]))) if dtype == np.float64 else y.shape[1]
+    for b, a in k_weighting(rate):
+        y = _biquad(y, b, a, chunk)
+    return y[0] if one else y
+
+
+def n_blocks(n: int, rate: int) -> int:
+    """Whole 400 ms blocks, 100 ms apart, in n samples."""
+    H = int(rate) // 10
+    return (int(n) - 4 * H) // H + 1 if n >= 4 * H else 0
+
+
+def powers_of_weighted(y, rate: int, weights=None, dtype=np.float64) -> np.ndarray:
+    """(nb,) channel-weighted mean squares of an already K-weighted y (C, N) over blocks of T = 4H samples, H = rate // 10 apart,
+    whole blocks only."""
+    y = np.atleast_2d(np.asarray(y, dtype=dtype))
+    C, N = y.shape
+    H = int(rate) // 10
+    nb = n_blocks(N, rate)
+    w = np.ones(C, dtype=dtype) if weights is None else np.asarray(weights, dtype=dtype).reshape(C)
+    p = np.zeros(nb, dtype=dtype)
+    if nb:
+        idx = np.arange(nb)[:, None] * H + np.arange(4 * H)[None, :]
+        for c in range(C):
+            p += w[c] * np.mean(np.square(y[c][idx]), axis=1, dtype=dtype)
+    return p
+
+
+def block_powers(x, rate: int, weights=None, dtype=np.float64) -> np.ndarray:
+    """(nb,) block powers of x (C, N): `powers_of_weighted` of `k_weighted(x)`, everything in `dtype`."""
+    x = np.atleast_2d(np.asarray(x, dtype=dtype))
+    k_weighting(rate)                                   # (the refusals, also for a signal too short to be filtered)
+    if n_blocks(x.shape[1], rate) == 0:
+        return np.zeros(0, dtype=dtype)
+    return powers_of_weighted(k_weighted(x, rate, dtype), rate, weights, dtype)
+
+
+def gate(p: np.ndarray) -> Tuple[float, int]:
+    """(integrated loudness, blocks that pass both gates) of block powers p; (-inf, 0) when none passes."""
+    p = np.asarray(p, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        l = OFFSET + 10.0 * np.log10(p)
+        keep = l > ABSOLUTE_GATE
+        if not keep.any():
+            return float("-inf"), 0
+        rel = OFFSET + 10.0 * np.log10(np.mean(p[keep])) + RELATIVE_GATE
+        keep &= l > rel
+        if not keep.any():
+            return float("-inf"), 0
+        return float(OFFSET + 10.0 * np.log10(np.mean(p[keep]))), int(np.count_nonzero(keep))
+
+
+def integrated_loudness(x, rate: int, weights=None) -> float:
+    """Gated integrated loudness of x (C, N) in LUFS (BS.1770-4: 400 ms blocks at 75 % overlap, absolute gate -70 LUFS, relative
+    gate -10 LU); -inf when no block survives (shorter than one block, silent)."""
+    return gate(block_powers(x, rate, weights))[0]
+
+
+def gain_for(loudness: float, peak: Optional[float], target: Optional[float], ceiling: Optional[float]) -> Tuple[np.float32, bool]:
+    """(float32 gain, whether the ceiling bit): lass_loudness_gain's rule.  g = 10^((target - loudness) / 20), computed in float64
+    and rounded to float32, if a target is given and the loudness is finite, else 1; with a ceiling (linear, > 0) and a float32
+    peak with fl(g * peak) > ceiling, g = fl(ceiling / peak), stepped down one float32 ulp while fl(g * peak) > ceiling.  Since
+    x -> fl(g * x) is monotone in |x|, no sample at or under the peak then lands over the ceiling."""
+    g = np.float32(1.0)
+    if target is not None and not np.isnan(target) and np.isfinite(loudness):
+        with np.errstate(over="ignore"):
+            g = np.float32(10.0 ** ((float(target) - float(loudness)) / 20.0))
+    limited = False
+    if ceiling is not None and ceiling > 0 and peak is not None:
+        pk, ce = np.float32(peak), np.float32(ceiling)
+        with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+            if g * pk > ce:
+                limited = True
+                g = np.float32(ce / pk)
+                while g * pk > ce:
+                    g = np.nextafter(g, np.float32(0.0))
+    return g, limited
+
+
+def ceiling_for(peak_ceiling_db: Optional[float], encoding: str) -> Optional[np.float32]:
+    """The linear float32 ceiling of a level in dBFS (<= 0), capped at the largest value `encoding` holds without clipping:
+    32767/32768 for "pcm16", the largest float32 below 1 for "pcm32"; None for None."""
+    if peak_ceiling_db is None:
+        return None
+    c = np.float32(10.0 ** (float(peak_ceiling_db) / 20.0))
+    cap = {"pcm16": np.float32(32767.0 / 32768.0), "pcm32": np.nextafter(np.float32(1.0), np.float32(0.0))}.get(encoding)
+    return c if cap is None else min(c, cap)
+
+
+def check_level_args(loudness, peak_ceiling_db) -> None:
+    """ValueError for a target that is not a finite number or a ceiling that is not a number <= 0 dBFS."""
+    for name, v in (("loudness", loudness), ("peak_ceiling_db", peak_ceiling_db)):
+        if v is None:
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise ValueError(f"{name} must be a finite number or None")
+    if peak_ceiling_db is not None and peak_ceiling_db > 0:
+        raise ValueError("peak_ceiling_db must be <= 0 dBFS")

@@ -15,8 +15,16 @@ One pass over a group of files:
               -> Engine.resample_encode back to the file's rate, encoding and frame count -> D2H into a pinned row
               -> wavio.wav_header + payload written
 
-Files are read on one thread and written on another while the device works.  Only the encoded payload leaves the device.  A
-file the device kernels do not take - a header `wavio.wav_info` does not fully understand, more than 8 channels, a rate pair
+Files are read on one thread and written on another while the device works.  Only the encoded payload leaves the device.
+
+With a level asked for (`loudness=` in LUFS, `peak_ceiling_db=` in dBFS) three more launches stand between the separation and
+the encoder, per file: `Engine.loudness` over all of the file's planes at the model rate (a gain commutes with the linear
+resampler, so no file-rate float plane is made), `Engine.resample_peak` of the samples the encoder is about to quantise, and
+`Engine.loudness_gain`, whose one gain per file - the channel balance is kept - stays on the device and goes into
+`Engine.resample_encode(gain=)`.  Loudness, gain and the limited flag travel to the host behind the payload, with the clip
+counter.  Without a level none of this runs: the pass is the one above.
+
+A file the device kernels do not take - a header `wavio.wav_info` does not fully understand, more than 8 channels, a rate pair
 beyond `resample.within_cap` in either direction - is decoded, resampled and written on the host (`wavio._resample`,
 `wavio.write_wav_*`); its separation still runs on the device, in the same pass, and its record says `path == "host"`.
 """
@@ -30,6 +38,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import loudness as ld
 from . import resample as rs
 from . import wavio
 
@@ -203,10 +212,17 @@ def _write_host(path: str, encoding: str, x: np.ndarray, rate: int, profile) -> 
         profile["write"] = profile.get("write", 0.0) + time.perf_counter() - t0
 
 
+def _level_record(measured: float, gain, limited: bool) -> dict:
+    with np.errstate(divide="ignore"):
+        return {"loudness_out": float(measured), "gain": float(gain), "gain_db": float(20.0 * np.log10(np.float64(gain))),
+                "peak_limited": bool(limited)}
+
+
 def separate_files(model, jobs, sampling_rate: int, channels: str = "each", encoding: Optional[str] = None,
                    out_rate: Optional[int] = None, window: int = 160000, context: int = 16000, fade: int = 0,
                    fade_shape: str = "linear", max_batch: int = 16, max_samples: int = DEFAULT_MAX_SAMPLES,
-                   profile: Optional[Dict[str, float]] = None) -> List[dict]:
+                   profile: Optional[Dict[str, float]] = None, loudness: Optional[float] = None,
+                   peak_ceiling_db: Optional[float] = None) -> List[dict]:
     """Separate WAV files by caption, file in and file out.  model: an `AudioSep`-shaped holder (`.ss_model` a ResUNet30 on the
     device working at `sampling_rate`, `.query_encoder` with `get_query_embed`); jobs: a sequence of (in_path, query, out_path),
     query a caption or a (512,) embedding.  channels "each": every channel of a file is separated on its own with the file's
@@ -215,9 +231,14 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
     ceil(model-rate samples * up / down).  window, context, fade, fade_shape, max_batch: `ResUNet30.separate_long_list`'s.  Files
     are taken in passes of at most `max_samples` model-rate samples (all planes counted), which bounds the memory; the captions
     of a pass are embedded in one `get_query_embed` call, each distinct caption once.  profile: a dict that receives seconds per
-    stage (read, h2d, decode, separate, encode, d2h, write), with the device synchronised after each stage - for measurement.
+    stage (read, h2d, decode, separate, level, encode, d2h, write), with the device synchronised after each stage - for measurement.
     Returns one record per job, in order: {"rate", "channels", "frames", "clipped", "path"} of the file written - "clipped" the
     number of PCM samples the writer clipped, "path" "device" or "host" (module docstring).
+    loudness: the integrated loudness (ITU-R BS.1770-4, LUFS) every file is brought to; peak_ceiling_db: the level in dBFS (<= 0)
+    no written sample exceeds - the gain is lowered where it would, and with "pcm16" / "pcm32" the ceiling is capped at the
+    largest value that does not clip, so "clipped" is then 0.  One gain per file.  With either, a record also has "loudness_out"
+    (measured on the separated planes before the gain; -inf for a file shorter than 400 ms or silent, which gets gain 1 or the
+    ceiling's gain alone), "gain" (linear, the float32 applied), "gain_db" and "peak_limited" (whether the ceiling lowered it).
     A file not longer than n_fft/2 samples at the model rate raises ValueError before anything is written."""
     import torch
 
@@ -225,6 +246,8 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
         raise ValueError('channels must be "each" or "mono"')
     if encoding is not None and encoding not in rs.ENCODINGS:
         raise ValueError(f"encoding must be one of {sorted(rs.ENCODINGS)} or None")
+    ld.check_level_args(loudness, peak_ceiling_db)
+    level = loudness is not None or peak_ceiling_db is not None
     jobs = [tuple(j) for j in jobs]
     ss = model.ss_model
     eng = ss.engine
@@ -292,15 +315,25 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
                 frames_o = frames if rate_o == rate else rs.out_len(L, *rs.ratio(sr, rate_o))
                 rec = {"rate": rate_o, "channels": n, "frames": frames_o, "path": hows[i]}
                 if hows[i] == "device":
+                    stacked, gain = torch.stack(mine), None
+                    if level:
+                        with clock("level"):
+                            measured = eng.loudness(stacked, sr)
+                            peak = eng.resample_peak(stacked, sr, rate_o, frames_out=frames_o) if peak_ceiling_db is not None else None
+                            gain, limited = eng.loudness_gain(measured, peak, loudness, ld.ceiling_for(peak_ceiling_db, enc_o))
                     with clock("encode"):
                         clipped = torch.zeros(1, dtype=torch.int32, device=dev)
-                        payload = eng.resample_encode(torch.stack(mine), sr, rate_o, enc_o, frames_out=frames_o, clipped=clipped)
+                        payload = eng.resample_encode(stacked, sr, rate_o, enc_o, frames_out=frames_o, clipped=clipped, gain=gain)
                     nbytes = payload.shape[1]
-                    tail = (nbytes + 3) // 4 * 4                   # the clip counter travels behind the payload
-                    buf = pool.take(tail + 4)
+                    tail = (nbytes + 7) // 8 * 8 if level else (nbytes + 3) // 4 * 4   # the clip counter travels behind the payload
+                    buf = pool.take(tail + (24 if level else 4))
                     with clock("d2h"):
                         buf[:nbytes].copy_(payload[0], non_blocking=True)
                         buf[tail:tail + 4].view(torch.int32).copy_(clipped, non_blocking=True)
+                        if level:                                  # ... and with it the file's limited flag, gain and loudness
+                            buf[tail + 4:tail + 8].view(torch.int32).copy_(limited, non_blocking=True)
+                            buf[tail + 8:tail + 12].view(torch.float32).copy_(gain, non_blocking=True)
+                            buf[tail + 16:tail + 24].view(torch.float64).copy_(measured, non_blocking=True)
                         done = torch.cuda.Event()
                         done.record(torch.cuda.current_stream(dev))
                     written.append((i, buf, tail, writer.submit(_write_device, jobs[i][2], wavio.wav_header(enc_o, n, rate_o, frames_o),
@@ -309,6 +342,12 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
                     with clock("d2h"):
                         x = torch.stack(mine).cpu().numpy()
                     y = _host_resample(x, sr, rate_o)[:, :frames_o]
+                    if level:                                      # the device's rule with lass_amd.loudness and numpy
+                        measured = ld.integrated_loudness(x, sr)
+                        g, bit = ld.gain_for(measured, float(np.nanmax(np.abs(y))) if y.size else 0.0, loudness,
+                                             ld.ceiling_for(peak_ceiling_db, enc_o))
+                        y = (g * y.astype(np.float32)).astype(np.float32)
+                        rec.update(_level_record(measured, g, bit))
                     rec["clipped"] = host_clip_count(y, enc_o)
                     written.append((i, None, 0, writer.submit(_write_host, jobs[i][2], enc_o, y, rate_o, profile)))
                 records[i] = rec
@@ -318,6 +357,10 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
                 fut.result()
                 if buf is not None:
                     records[i]["clipped"] = int(buf[tail:tail + 4].view(torch.int32)[0])
+                    if level:
+                        records[i].update(_level_record(float(buf[tail + 16:tail + 24].view(torch.float64)[0]),
+                                                        np.float32(buf[tail + 8:tail + 12].view(torch.float32)[0].item()),
+                                                        bool(buf[tail + 4:tail + 8].view(torch.int32)[0])))
                     pool.give(buf)
             for buf in uploaded:
                 pool.give(buf)
@@ -325,7 +368,9 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
     return records
 
 
-def inference(model, audio_file: str, text, output_file: str, sampling_rate: int = 32000, **kw) -> dict:
-    """One file through `separate_files`: the single-file shape of upstream AudioSep's `pipeline.inference`.  Returns the job's
-    record."""
-    return separate_files(model, [(audio_file, text, output_file)], sampling_rate, **kw)[0]
+def inference(model, audio_file: str, text, output_file: str, sampling_rate: int = 32000, loudness: Optional[float] = None,
+              peak_ceiling_db: Optional[float] = None, **kw) -> dict:
+    """One file through `separate_files`: the single-file shape of upstream AudioSep's `pipeline.inference`.  loudness, peak_ceiling_db and the
+    other keywords are `separate_files`'s.  Returns the job's record."""
+    return separate_files(model, [(audio_file, text, output_file)], sampling_rate, loudness=loudness, peak_ceiling_db=peak_ceiling_db,
+                          **kw)[0]

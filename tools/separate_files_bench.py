@@ -1,7 +1,7 @@
 """File in, file out on one MI355X: `pipeline.separate_files` against the same jobs done with the pieces the package had before
 it, on 32 seeded one-minute 44.1 kHz stereo PCM16 files (synthetic ResUNet30 weights, 16 kHz, f32 unless --compute-dtype).
 
-    python tools/separate_files_bench.py [--files 32] [--seconds 60] [--reps 5] [--compute-dtype f32]
+    python tools/separate_files_bench.py [--files 32] [--seconds 60] [--reps 5] [--compute-dtype f32] [--loudness]
 
 Leg A: `separate_files(channels="each")` - decode, resample, separate, resample back, encode and interleave on the device.
 Leg B: host decode + de-interleave + `wavio._resample` (scipy, float64), `separate_long_list`, `.cpu()`, host `_resample` back
@@ -9,6 +9,10 @@ and `wavio.write_wav_pcm16`.  The legs alternate A B A B ..., `--reps` runs each
 `timeout -k 10` (a failing run ends the whole); a child separates one file as a warm-up before its timed pass.  Prints one JSON
 line per run and a summary line: median seconds, files/s and x real time per leg, and leg A's time split from one further run
 with `profile=` (which synchronises after every stage, so its parts add up to more than an unprofiled pass).
+
+--loudness: leg A against leg L, the same call with `loudness=-23.0, peak_ceiling_db=-1.0` (meter, peak and gain on the device, per
+file), alternating A L A L ...; no leg B, and the profiled run is leg L's, whose split has the `level` stage.  Leg A with this flag
+is the number to hold against the same tool's leg A on the parent commit: it launches the same kernels.
 """
 import argparse
 import json
@@ -80,13 +84,14 @@ def leg(name: str, d: str, n: int, mode: str):
     import torch
     from lass_amd import pipeline
     model = _model(mode)
-    profile = {} if name == "A-profile" else None
+    profile = {} if name.endswith("-profile") else None
+    level = dict(loudness=-23.0, peak_ceiling_db=-1.0) if name.startswith("L") else {}
 
     def run(jobs, profile=None):
         if name == "B":
             host_pieces(model, jobs)
         else:
-            pipeline.separate_files(model, jobs, SR, channels="each", profile=profile)
+            pipeline.separate_files(model, jobs, SR, channels="each", profile=profile, **level)
 
     run(_jobs(d, 1, "warm"))
     torch.cuda.synchronize()
@@ -106,7 +111,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--compute-dtype", default="f32")
     ap.add_argument("--timeout", type=int, default=300, help="seconds per run")
-    ap.add_argument("--leg", choices=["A", "B", "A-profile"])
+    ap.add_argument("--loudness", action="store_true", help="leg A against leg L (loudness=-23, peak_ceiling_db=-1) instead of leg B")
+    ap.add_argument("--leg", choices=["A", "B", "L", "A-profile", "L-profile"])
     ap.add_argument("--dir")
     a = ap.parse_args()
     if a.leg:
@@ -114,9 +120,11 @@ def main():
         return 0
     with tempfile.TemporaryDirectory() as d:
         make_files(d, a.files, a.seconds)
-        times = {"A": [], "B": []}
+        other = "L" if a.loudness else "B"
+        prof = "L-profile" if a.loudness else "A-profile"
+        times = {"A": [], other: []}
         split = None
-        for name in ["A", "B"] * a.reps + ["A-profile"]:
+        for name in ["A", other] * a.reps + [prof]:
             cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--leg", name, "--dir", d,
                    "--files", str(a.files), "--compute-dtype", a.compute_dtype]
             pr = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, text=True)
@@ -126,17 +134,17 @@ def main():
                 print(json.dumps({"leg": name, "failed": pr.returncode}), flush=True)
                 return pr.returncode
             res = json.loads(pr.stdout.strip().split("\n")[-1])
-            if name == "A-profile":
+            if name == prof:
                 split = res["split_s"]
             else:
                 times[name].append(res["seconds"])
         audio = a.files * a.seconds
-        summary = {"files": a.files, "seconds_each": a.seconds, "compute_dtype": a.compute_dtype, "A_split_s": split}
+        summary = {"files": a.files, "seconds_each": a.seconds, "compute_dtype": a.compute_dtype, prof[0] + "_split_s": split}
         for name, ts in times.items():
             med = statistics.median(ts)
             summary[name] = {"median_s": round(med, 4), "files_per_s": round(a.files / med, 2), "x_real_time": round(audio / med, 1),
                              "runs_s": ts}
-        summary["B_over_A"] = round(summary["B"]["median_s"] / summary["A"]["median_s"], 2)
+        summary[other + "_over_A"] = round(summary[other]["median_s"] / summary["A"]["median_s"], 2)
         print(json.dumps(summary), flush=True)
     return 0
 
