@@ -507,6 +507,44 @@ int lass_resample_encode_gain(lass_ctx* ctx, const float* planes, int64_t row_st
                               int L_in, int up, int down, const float* taps, int n_taps, int encoding, const float* gain,
                               void* out_bytes, int64_t out_row_stride_bytes, int frames_out, unsigned* clipped, void* stream);
 
+/* ---- EBU R 128 delivery: true peak, loudness range and maxima (opt-in; separate_files(peak="true", meter=True)) ---- */
+
+/* The true peak of what lass_resample_encode would quantise: lass_resample_peak with the signal between the samples.  With y_c[n]
+ * that entry point's float32 value before quantisation for n < frames_out, and zero outside,
+ *   z_c[k] = sum_m y_c[m] * os_taps[k - m*os + 10*os],   k < os * frames_out
+ * evaluated as lass_decode_resample evaluates an (up, down) = (os, 1) filter - one float32 fmaf chain over the 21 taps of the
+ * output's phase, in that entry point's order - and
+ *   peak[b] = max over c of max( max_n |y_c[n]| , max over k % os != 0 of |z_c[k]| ).
+ * Phase 0 is the samples themselves and not the filtered samples, so a true peak is never under the sample peak.  peak[b] is
+ * bit-identical to composing the public pieces (lass_decode_resample of the float32 plane, cut to frames_out, then of the result
+ * at (os, 1)), whatever B, the row, the strides, the tile or the call; raised by integer atomic max on the bits, a NaN skipped.
+ * os: 2 or 4 (lass_amd.loudness.oversampling; 1 is lass_resample_peak); os_taps: device, n_os_taps = 20*os + 1 floats, the float32
+ * of lass_amd.resample.design_taps(os, 1); peak: device, B floats, written here.  One launch: a workgroup keeps the y of its tile
+ * and of the 10 frames on either side of it that the 21 taps reach in LDS; no scratch, no float plane at the file's rate in memory.
+ * Arguments and limits otherwise: lass_resample_peak's.  In addition a ratio at which the 21 first-stage frames of one
+ * interpolated value no longer fit the CU's LDS beside the filter table (lass_amd.resample.true_peak_fits tells beforehand; far
+ * down-sampling ratios such as 1:800) is refused with LASS_ERR_ARG before anything is launched. */
+int lass_resample_true_peak(lass_ctx* ctx, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels,
+                            int L_in, int up, int down, const float* taps, int n_taps, int frames_out, int os, const float* os_taps,
+                            int n_os_taps, float* peak, void* stream);
+
+/* lass_loudness with the other figures an R 128 delivery is checked against.  Arguments: lass_loudness's, except that out is (B,10)
+ * doubles and that short_term (optional, device, (B, ns_max) doubles, ns_max >= the short-term blocks of L samples) receives the
+ * short-term powers, zeros past a recording's own count.  With S_c[i] the sum of the squared K-weighted samples of hop bin i,
+ *   q_j = sum_c G_c * (S_c[j] + S_c[j+1] + ... + S_c[j+29]) / (30 hop),  j < ns = bins - 29 (0 under 30 bins): 3 s blocks, 100 ms apart.
+ * out[b] = { columns 0 ... 2: what lass_loudness writes, bit for bit (the same kernels);
+ *            3: maximum momentary loudness, -0.691 + 10 log10 max_j p_j, ungated;   4: maximum short-term loudness, the same of q;
+ *            5: loudness range in LU (EBU Tech 3342): absolute gate l > -70, relative gate l > (loudness of the mean of the abs-gated
+ *               q) - 20; of the n survivors sorted ascending p10 = v[floor((n-1)*0.10 + 0.5)], p95 = v[floor((n-1)*0.95 + 0.5)],
+ *               LRA = 10 log10(p95 / p10);
+ *            6: ns;   7: n;   8: p10;   9: p95 (powers) }
+ * and -inf, -inf, 0, 0, 0, 0, 0 where there is nothing to measure.  The two order statistics are selected exactly (a radix select
+ * on the bit patterns, integer atomics, any count); no floating-point atomics and one order per sum: a recording's ten numbers are
+ * bit-identical alone and as any row of any batch.  scratch: (5 * channels + 1) * B * (L / hop) doubles. */
+int lass_loudness_stats(lass_ctx* ctx, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels, int L,
+                        const int* lengths, int hop, const double* coef, const float* weights, double* out, double* blocks,
+                        int nb_max, double* short_term, int ns_max, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Training-side data path ("next" row f4, mixer half; also the producer stage of the STFT pre-compute,
  * scripts/precompute_stfts.py:352-681): SegmentMixer.__call__ + dynamic_loudnorm (data/waveform_mixers.py:19-92) on the
  * device.  waveforms (B,L) -> mixture (B,L), segment (B,L).  For clip n:

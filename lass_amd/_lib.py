@@ -56,6 +56,10 @@ SYMBOLS = [
     ("lass_loudness_gain", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_float, c_void_p, c_void_p, c_void_p]),
     ("lass_resample_encode_gain", c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
                                           c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    ("lass_resample_true_peak", c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int,
+                                        c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    ("lass_loudness_stats", c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_int, POINTER(c_double),
+                                    c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     ("lass_segment_mix", c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p]),
     ("lass_multi_stft", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_void_p),

@@ -796,7 +796,7 @@ int compose_head(lass_ctx* c, int Q, bool sc, HeadHost* h) {
 
 extern "C" {
 
-int lass_version(void) { return 10800; }  // 1.8.0: levelled export (lass_loudness, lass_resample_peak, lass_loudness_gain, lass_resample_encode_gain); 1.7.0: cross-faded window seams (lass_separate_windows_faded, lass_istft_windows_faded); 1.6.0: ResUNet30 at the (2048, 320) STFT geometry (lass_create_stft, lass_stft_geometry); 1.5.0: windows of one long row (lass_separate_windows & co); 1.4.0: per-clip lengths (lass_separate_ragged & co); 1.3.0: CLAP text tower (lass_text_*, text.hip); 1.2.0: F(4x4,3x3) kernels, lass_set_graph_replay (1.1.0: multi-STFT model, fused iSTFT, graph replay)
+int lass_version(void) { return 10900; }  // 1.9.0: EBU R 128 figures (lass_resample_true_peak, lass_loudness_stats); 1.8.0: levelled export (lass_loudness, lass_resample_peak, lass_loudness_gain, lass_resample_encode_gain); 1.7.0: cross-faded window seams (lass_separate_windows_faded, lass_istft_windows_faded); 1.6.0: ResUNet30 at the (2048, 320) STFT geometry (lass_create_stft, lass_stft_geometry); 1.5.0: windows of one long row (lass_separate_windows & co); 1.4.0: per-clip lengths (lass_separate_ragged & co); 1.3.0: CLAP text tower (lass_text_*, text.hip); 1.2.0: F(4x4,3x3) kernels, lass_set_graph_replay (1.1.0: multi-STFT model, fused iSTFT, graph replay)
 
 const char* lass_last_error(const lass_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_err.c_str(); }
 
@@ -1454,11 +1454,37 @@ int lass_resample_peak(lass_ctx* c, const float* planes, int64_t row_stride, int
     return 0;
 }
 
-int lass_loudness(lass_ctx* c, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels, int L,
-                  const int* lengths, int hop, const double* coef, const float* weights, double* out, double* blocks, int nb_max,
-                  void* scratch, size_t scratch_bytes, void* stream) {
-    const char* w = "lass_loudness: ";
+int lass_resample_true_peak(lass_ctx* c, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels, int L_in,
+                            int up, int down, const float* taps, int n_taps, int frames_out, int os, const float* os_taps,
+                            int n_os_taps, float* peak, void* stream) {
+    const char* w = "lass_resample_true_peak: ";
     if (!c) return LASS_ERR_ARG;
+    if (!planes || !peak || B <= 0 || B > 65535 || L_in <= 0)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "planes, peak non-NULL, 1 <= B <= 65535, L_in >= 1");
+    if (int r = check_resample_args(c, w, channels, LASS_WAV_F32, up, down, taps, n_taps)) return r;
+    if (int r = check_export_planes(c, w, planes, row_stride, plane_stride, channels, L_in, up, down, frames_out)) return r;
+    if (os != 2 && os != 4) return fail(c, LASS_ERR_ARG, std::string(w) + "os must be 2 or 4 (1 is lass_resample_peak)");
+    if (!os_taps || n_os_taps != 20 * os + 1)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "os_taps non-NULL, n_os_taps = 20 * os + 1 = " + std::to_string(20 * os + 1));
+    if (reinterpret_cast<uintptr_t>(planes) % 4 != 0 || reinterpret_cast<uintptr_t>(peak) % 4 != 0 ||
+        reinterpret_cast<uintptr_t>(os_taps) % 4 != 0)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "planes, os_taps and peak must be 4-byte aligned");
+    if (!lass_resample_true_peak_fits(up, down, (up == 1 && down == 1) ? 1 : n_taps, os))
+        return fail(c, LASS_ERR_ARG, std::string(w) + "at up = " + std::to_string(up) + ", down = " + std::to_string(down) +
+                    " the 21 frames one interpolated value reaches do not fit the CU's LDS beside the filter table (take the "
+                    "true peak on the host)");
+    if (int r = use_device(c)) return r;
+    HIP_TRY(c, lass_launch_resample_true_peak(planes, row_stride, plane_stride, B, channels, L_in, up, down, taps, n_taps, frames_out,
+                                              os, os_taps, n_os_taps, peak, (hipStream_t)stream));
+    return 0;
+}
+
+// What the two meter entries ask before the filter is formed (w: the entry's "name: "; scratch_per_bin: doubles of scratch per
+// recording and hop bin beyond the 5 per plane).
+static int check_loudness_args(lass_ctx* c, const char* w, const float* planes, int64_t row_stride, int64_t plane_stride, int B,
+                               int channels, int L, const int* lengths, int hop, const double* coef, const float* weights,
+                               const double* out, const double* blocks, int nb_max, const void* scratch, size_t scratch_bytes,
+                               int scratch_per_bin) {
     if (!planes || !coef || !out || B <= 0 || L <= 0) return fail(c, LASS_ERR_ARG, std::string(w) + "planes, coef, out non-NULL, B >= 1, L >= 1");
     if (channels < 1 || channels > 8 || (long long)B * channels > 65535)
         return fail(c, LASS_ERR_ARG, std::string(w) + "1 ... 8 channels, B * channels <= 65535");
@@ -1471,13 +1497,46 @@ int lass_loudness(lass_ctx* c, const float* planes, int64_t row_stride, int64_t 
     const long long bins = L / hop, nb = bins >= 4 ? bins - 3 : 0;
     if (blocks && (long long)nb_max < nb)
         return fail(c, LASS_ERR_ARG, std::string(w) + "nb_max must hold the blocks of L samples (" + std::to_string(nb) + ")");
-    const size_t need = (size_t)5 * B * channels * bins * sizeof(double);
+    const size_t need = ((size_t)5 * B * channels + (size_t)scratch_per_bin * B) * bins * sizeof(double);
     if (need && (!scratch || scratch_bytes < need))
-        return fail(c, LASS_ERR_ARG, std::string(w) + "scratch must hold 5 * B * channels * (L / hop) doubles (" + std::to_string(need) + " bytes)");
+        return fail(c, LASS_ERR_ARG, std::string(w) + "scratch must hold " + (scratch_per_bin ? "(5 * channels + 1) * B" : "5 * B * channels") +
+                    " * (L / hop) doubles (" + std::to_string(need) + " bytes)");
     if (reinterpret_cast<uintptr_t>(planes) % 4 != 0 || reinterpret_cast<uintptr_t>(lengths) % 4 != 0 ||
         reinterpret_cast<uintptr_t>(weights) % 4 != 0 || reinterpret_cast<uintptr_t>(out) % 8 != 0 ||
         reinterpret_cast<uintptr_t>(blocks) % 8 != 0 || reinterpret_cast<uintptr_t>(scratch) % 8 != 0)
         return fail(c, LASS_ERR_ARG, std::string(w) + "planes, lengths, weights 4-byte aligned; out, blocks, scratch 8-byte aligned");
+    return 0;
+}
+
+int lass_loudness_stats(lass_ctx* c, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels, int L,
+                        const int* lengths, int hop, const double* coef, const float* weights, double* out, double* blocks,
+                        int nb_max, double* short_term, int ns_max, void* scratch, size_t scratch_bytes, void* stream) {
+    const char* w = "lass_loudness_stats: ";
+    if (!c) return LASS_ERR_ARG;
+    if (int r = check_loudness_args(c, w, planes, row_stride, plane_stride, B, channels, L, lengths, hop, coef, weights, out, blocks,
+                                    nb_max, scratch, scratch_bytes, 1))
+        return r;
+    const long long bins = L / hop, ns = bins >= 30 ? bins - 29 : 0;
+    if (short_term && ((long long)ns_max < ns || reinterpret_cast<uintptr_t>(short_term) % 8 != 0))
+        return fail(c, LASS_ERR_ARG, std::string(w) + "short_term 8-byte aligned, ns_max must hold the short-term blocks of L samples (" +
+                    std::to_string(ns) + ")");
+    LoudnessFilter f;
+    if (!lass_loudness_filter(coef, hop, &f))
+        return fail(c, LASS_ERR_ARG, std::string(w) + "coef must be finite, both biquads with their poles inside the unit circle");
+    if (int r = use_device(c)) return r;
+    HIP_TRY(c, lass_launch_loudness_stats(planes, row_stride, plane_stride, B, channels, L, lengths, hop, f, weights, out, blocks, nb_max,
+                                          short_term, ns_max, static_cast<double*>(scratch), (hipStream_t)stream));
+    return 0;
+}
+
+int lass_loudness(lass_ctx* c, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels, int L,
+                  const int* lengths, int hop, const double* coef, const float* weights, double* out, double* blocks, int nb_max,
+                  void* scratch, size_t scratch_bytes, void* stream) {
+    const char* w = "lass_loudness: ";
+    if (!c) return LASS_ERR_ARG;
+    if (int r = check_loudness_args(c, w, planes, row_stride, plane_stride, B, channels, L, lengths, hop, coef, weights, out, blocks,
+                                    nb_max, scratch, scratch_bytes, 0))
+        return r;
     LoudnessFilter f;
     if (!lass_loudness_filter(coef, hop, &f))
         return fail(c, LASS_ERR_ARG, std::string(w) + "coef must be finite, both biquads with their poles inside the unit circle");

@@ -13,6 +13,9 @@
 // Both kernels are templates over where an output y goes (Sink): quantised into the stage (kEncode, lass_resample_encode), the
 // same after one multiplication by the row's gain (kEncodeGain, lass_resample_encode_gain), or into the row's peak |y| with no
 // stage and no store (kPeak, lass_resample_peak).  Up to that point the three are one body, so they see the same y.
+//
+// k_true_peak (lass_resample_true_peak) is a fourth use of the same chain: it keeps the y of its tile and a halo as floats in LDS
+// and runs polyphase.h's chain once more over them, at (os, 1), for the peak between the samples.  DESIGN.md section 19.
 #include "../../include/lass_hip.h"
 #include "kernels.h"
 
@@ -155,6 +158,80 @@ __global__ __launch_bounds__(kThreads) void k_resample_encode(const float* __res
     finish<kSink>(stage0, out, out_row_stride, a, (size_t)T.nout * ch * bps, tid, clips, clipped, pk, peak);
 }
 
+// ---- the true-peak sink (lass_resample_true_peak) --------------------------------------------------------
+// The peak of y and of y interpolated os times: z[k] = sum_m y[m] * g[k - m*os + 10*os], g the 20*os + 1 taps of the (os, 1)
+// filter, which polyphase.h evaluates as J2 = 21 taps per phase over the frames n - 10 ... n + 10 of output k = n*os + p.  One
+// workgroup makes the y of its tile and of kOsHalo frames on either side (J2 - 1 = 20 frames of reach in all, zeros outside the
+// row's frames_out frames) into a float stage in LDS, one channel at a time, and runs the os - 1 interpolated phases of its own
+// frames over the stage with polyphase.h's fir_output itself: the stage is the span and the second table the table of a
+// FirTile of (up, down) = (os, 1) whose first output is the stage's frame kOsHalo.  Phase 0 is y itself.
+constexpr int kOsJ = 21;                // taps per phase of the second filter: ceil((20*os + 1) / os)
+constexpr int kOsHalo = (kOsJ - 1) / 2;
+
+__host__ __device__ __forceinline__ size_t true_peak_stage_floats(int tile) { return ((size_t)tile + 2 * kOsHalo + 3) & ~(size_t)3; }
+
+// kFir false: up == down == 1, the planes go straight into the stage (no first table, no span)
+template <bool kFir>
+__global__ __launch_bounds__(kThreads) void k_true_peak(const float* __restrict__ planes, long long row_stride, long long plane_stride,
+                                                        int L_in, int ch, int up, int down, const float* __restrict__ taps, int n_taps,
+                                                        int J, int tile, int span_floats, int frames_out, int os,
+                                                        const float* __restrict__ os_taps, int n_os_taps, unsigned* __restrict__ peak) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x;
+    const float* rec = planes + (size_t)blockIdx.y * row_stride;
+    const long long n0 = (long long)blockIdx.x * tile;
+    const int nout = (int)(frames_out - n0 < tile ? frames_out - n0 : tile);
+    const long long lo = n0 - kOsHalo;                                          // the frame stage[0] holds
+    const long long first = lo < 0 ? 0 : lo;                                    // the frames of the row among the stage's
+    const long long last = n0 + nout + kOsHalo < frames_out ? n0 + nout + kOsHalo : frames_out;
+    float* stage = lds + (kFir ? (((size_t)up * (J | 1) + span_floats + 3) & ~(size_t)3) : 0);
+    FirTile T, T2;
+    if constexpr (kFir) {
+        T = fir_tile_at(lds, up, down, n_taps, J, first, (int)(last - first));
+        fir_table(T, taps, n_taps);
+    }
+    T2.J = kOsJ;
+    T2.Jp = kOsJ | 1;
+    T2.up = os;
+    T2.down = 1;
+    T2.tab = stage + true_peak_stage_floats(tile);
+    T2.span = stage;
+    T2.r0 = 0;
+    fir_table(T2, os_taps, n_os_taps);
+
+    unsigned pk = 0;
+    for (int c = 0; c < ch; ++c) {
+        const float* x0 = rec + (size_t)c * plane_stride;
+        if (c) __syncthreads();                           // the previous channel's reads of the stage
+        if constexpr (kFir) {
+            fir_fill(T, L_in, [&](long long m) { return x0[m]; });
+            __syncthreads();
+        }
+        for (int s = tid; s < nout + 2 * kOsHalo; s += kThreads) {
+            const long long f = lo + s;
+            float y = 0.f;
+            if (f >= first && f < last) {
+                if constexpr (kFir) y = fir_output(T, (int)(f - first));
+                else y = x0[f];
+            }
+            stage[s] = y;
+        }
+        __syncthreads();
+        for (int i = tid; i < nout; i += kThreads) {
+            emit<kPeak>(nullptr, 0, stage[i + kOsHalo], 1.0f, 0, nullptr, &pk);
+            for (int p = 1; p < os; ++p) emit<kPeak>(nullptr, 0, fir_output(T2, i * os + p), 1.0f, 0, nullptr, &pk);
+        }
+    }
+    finish<kPeak>(nullptr, nullptr, 0, 0, 0, tid, 0, nullptr, pk, peak);
+}
+
+// floats of LDS a tile of t frames needs: table and span of t + 2 * kOsHalo first-stage outputs, the stage, the second table
+size_t true_peak_floats(int up, int down, int n_taps, int os, int t) {
+    const size_t head = (up == 1 && down == 1) ? 0
+        : (lass_resample_table_floats(up, n_taps) + lass_resample_span_floats(up, down, n_taps, t + 2 * kOsHalo) + 3) & ~(size_t)3;
+    return head + true_peak_stage_floats(t) + (size_t)os * (kOsJ | 1);
+}
+
 }  // namespace
 
 // One launch for the three sinks.  kPeak keeps no stage (enc, out and clipped unused), so its tiles are as large as the span allows.
@@ -206,4 +283,34 @@ hipError_t lass_launch_resample_peak(const float* planes, long long row_stride, 
     if (e != hipSuccess) return e;
     return launch<kPeak>(planes, row_stride, plane_stride, B, ch, L_in, up, down, taps, n_taps, LASS_WAV_F32, nullptr, 0, frames_out,
                          nullptr, nullptr, reinterpret_cast<unsigned*>(peak), stream);
+}
+
+bool lass_resample_true_peak_fits(int up, int down, int n_taps, int os) {
+    return true_peak_floats(up, down, n_taps, os, 1) <= (size_t)kLdsFloats;
+}
+
+hipError_t lass_launch_resample_true_peak(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L_in,
+                                          int up, int down, const float* taps, int n_taps, int frames_out, int os, const float* os_taps,
+                                          int n_os_taps, float* peak, hipStream_t stream) {
+    if (B <= 0 || B > 65535 || ch < 1 || ch > 8 || L_in <= 0 || frames_out <= 0 || up < 1 || down < 1 || (os != 2 && os != 4) ||
+        n_os_taps != 20 * os + 1)
+        return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(peak, 0, (size_t)B * sizeof(float), stream);
+    if (e != hipSuccess) return e;
+    unsigned* pk = reinterpret_cast<unsigned*>(peak);
+    if (up == 1 && down == 1) {
+        const size_t lds = true_peak_floats(1, 1, 1, os, kTileMax) * sizeof(float);
+        hipLaunchKernelGGL(k_true_peak<false>, dim3((frames_out + kTileMax - 1) / kTileMax, B), dim3(kThreads), lds, stream, planes,
+                           row_stride, plane_stride, L_in, ch, 1, 1, nullptr, 1, 1, kTileMax, 0, frames_out, os, os_taps, n_os_taps, pk);
+        return hipGetLastError();
+    }
+    // the stage costs LDS beside table and span, and the span reaches 2 * kOsHalo outputs further: never a larger tile than kPeak's
+    FirPlan P;
+    e = fir_plan(reinterpret_cast<const void*>(k_true_peak<true>), up, down, n_taps, frames_out,
+                 [&](int t) { return true_peak_floats(up, down, n_taps, os, t); }, &P);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_true_peak<true>, dim3(P.nblk, B), dim3(kThreads), P.lds, stream, planes, row_stride, plane_stride, L_in, ch, up,
+                       down, taps, n_taps, P.J, P.tile, (int)lass_resample_span_floats(up, down, n_taps, P.tile + 2 * kOsHalo),
+                       frames_out, os, os_taps, n_os_taps, pk);
+    return hipGetLastError();
 }

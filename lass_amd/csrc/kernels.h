@@ -304,6 +304,15 @@ hipError_t lass_launch_resample_encode_gain(const float* planes, long long row_s
 // up to where y goes); a NaN is skipped.  peak (B floats) is zero-filled here, then raised by integer atomic max on |y|'s bits.
 hipError_t lass_launch_resample_peak(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L_in, int up,
                                      int down, const float* taps, int n_taps, int frames_out, float* peak, hipStream_t stream);
+// peak[b] = the larger of max |y| (the entry above) and max |z[k]|, k % os != 0, z[k] = sum_m y[m] * os_taps[k - m*os + 10*os] for
+// k < os * frames_out (y = 0 outside its frames_out frames): y interpolated os times by polyphase.h's chain of (os, 1), phase 0
+// left out.  os in {2, 4}, os_taps: 20*os + 1 device floats.  One launch, the y of a tile and its halo in LDS.
+// hipErrorInvalidValue where lass_resample_true_peak_fits is false.
+hipError_t lass_launch_resample_true_peak(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L_in,
+                                          int up, int down, const float* taps, int n_taps, int frames_out, int os, const float* os_taps,
+                                          int n_os_taps, float* peak, hipStream_t stream);
+// whether a tile of one frame - table, the span of its 21 first-stage outputs, stage, second table - fits the CU's 160 KiB
+bool lass_resample_true_peak_fits(int up, int down, int n_taps, int os);
 
 // ---- loudness.hip -------------------------------------------------------------------------------------------------
 // K-weighting as the kernels take it: the two biquads (b0 b1 b2 a1 a2 of the shelf, then of the high-pass) and the powers of the
@@ -322,6 +331,13 @@ bool lass_loudness_filter(const double* coef, int hop, LoudnessFilter* f);
 hipError_t lass_launch_loudness(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L,
                                 const int* lengths, int hop, const LoudnessFilter& f, const float* weights, double* out,
                                 double* blocks, int nb_max, double* scratch, hipStream_t stream);
+// The same into columns 0 ... 2 of out (B,10) by the same kernels, then one more kernel, one workgroup per recording: columns
+// 3 ... 9 = {max momentary LUFS, max short-term LUFS, LRA, ns, short-term blocks past both gates, p10, p95} (EBU Tech 3342 on 3 s
+// blocks of 30 bin sums; the two order statistics by an exact radix select).  short_term (B, ns_max), optional: the short-term
+// powers, 0 past a recording's own count.  scratch: (5 * ch + 1) * B * (L / hop) doubles.
+hipError_t lass_launch_loudness_stats(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L,
+                                      const int* lengths, int hop, const LoudnessFilter& f, const float* weights, double* out,
+                                      double* blocks, int nb_max, double* short_term, int ns_max, double* scratch, hipStream_t stream);
 // lass_loudness_gain's rule, one thread per row
 hipError_t lass_launch_loudness_gain(const double* loudness, const float* peak, int B, double target, float ceiling, float* gain,
                                      int* limited, hipStream_t stream);

@@ -12,6 +12,9 @@
 //                and sums y^2; lane 0 adds the lane sums in lane order.
 // k_gate:        one workgroup per recording: block powers from four consecutive bin sums, then the two gates, each one
 //                strided sum per thread and one LDS tree.
+// k_range:       (lass_loudness_stats alone) one workgroup per recording: short-term powers from thirty consecutive bin sums, the
+//                maxima of both kinds of block, EBU Tech 3342's two gates, and the 10th and 95th percentile by an exact radix
+//                select on the powers' bit patterns.  DESIGN.md section 19.
 // A wave reads its bin into LDS with consecutive lanes on consecutive floats (the lanes' own runs lie S floats apart, which no
 // load instruction coalesces); a lane's run sits at pitch S | 1 so the lanes spread over the banks.  State, products and sums
 // are float64.  Every chunk boundary is a multiple of H from the plane's first sample and every sum has one order, so a
@@ -144,10 +147,10 @@ __device__ __forceinline__ double tree_sum(double v, double* red) {
     return red[0];
 }
 
-// one workgroup per recording.  out[b] = {integrated loudness, blocks, blocks that pass both gates}
+// one workgroup per recording.  out[b * out_pitch] ... = {integrated loudness, blocks, blocks that pass both gates}
 __global__ __launch_bounds__(kGateThreads) void k_gate(const double* __restrict__ sums, int ch, int L, const int* __restrict__ lengths,
                                                        int H, int bins_max, const float* __restrict__ weights,
-                                                       double* __restrict__ out, double* __restrict__ blocks, int nb_max) {
+                                                       double* __restrict__ out, int out_pitch, double* __restrict__ blocks, int nb_max) {
     __shared__ double red[kGateThreads];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int bins = clamp_len(lengths, b, L) / H;
@@ -185,9 +188,127 @@ __global__ __launch_bounds__(kGateThreads) void k_gate(const double* __restrict_
         if (kept > 0.0) loud = lufs(sum2 / kept);
     }
     if (tid == 0) {
-        out[3 * b] = loud;
-        out[3 * b + 1] = (double)nb;
-        out[3 * b + 2] = kept;
+        out[(size_t)out_pitch * b] = loud;
+        out[(size_t)out_pitch * b + 1] = (double)nb;
+        out[(size_t)out_pitch * b + 2] = kept;
+    }
+}
+
+// ---- EBU R 128 beside the integrated loudness (lass_loudness_stats) --------------------------------------
+constexpr int kShortBins = 30;          // a 3 s short-term block in hop bins
+
+// maximum over the workgroup; every thread gets the result (exact whatever the order)
+__device__ __forceinline__ double tree_max(double v, double* red) {
+    __syncthreads();
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int w = kGateThreads / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] = red[threadIdx.x + w] > red[threadIdx.x] ? red[threadIdx.x + w] : red[threadIdx.x];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+// The k-th smallest (k from 0) of the n doubles of row v, by their bit patterns (non-negative doubles order as unsigned 64-bit
+// integers; a dropped block holds all ones and sorts behind every power): a radix select, most significant byte first, each pass
+// one 256-bin histogram of the values that share the bytes found so far.  Integer LDS atomics: exact and order-independent.
+__device__ __forceinline__ unsigned long long radix_select(const double* v, int n, unsigned k, unsigned* hist, unsigned long long* found) {
+    unsigned long long prefix = 0;
+    for (int pass = 7; pass >= 0; --pass) {
+        const int shift = 8 * pass;
+        const unsigned long long mask = pass == 7 ? 0ull : ~0ull << (shift + 8);
+        __syncthreads();
+        hist[threadIdx.x] = 0;
+        __syncthreads();
+        for (int j = threadIdx.x; j < n; j += kGateThreads) {
+            const unsigned long long bits = (unsigned long long)__double_as_longlong(v[j]);
+            if ((bits & mask) == prefix) atomicAdd(hist + (unsigned)((bits >> shift) & 255u), 1u);
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            unsigned below = 0, d = 0;
+            while (d < 255u && k >= below + hist[d]) below += hist[d++];
+            found[0] = prefix | ((unsigned long long)d << shift);
+            found[1] = k - below;
+        }
+        __syncthreads();
+        prefix = found[0];
+        k = (unsigned)found[1];
+    }
+    return prefix;
+}
+
+// one workgroup per recording, after k_gate.  out[b * 10 + 3 ...] = {max momentary, max short-term, LRA, ns, short-term blocks past
+// both gates, p10, p95}; st (B, bins_max): the recording's short-term powers, a dropped one replaced by all ones; short_term
+// (optional, (B, ns_max)): the powers themselves, 0 past the recording's own count.
+__global__ __launch_bounds__(kGateThreads) void k_range(const double* __restrict__ sums, int ch, int L, const int* __restrict__ lengths,
+                                                        int H, int bins_max, const float* __restrict__ weights,
+                                                        double* __restrict__ out, double* __restrict__ st_all,
+                                                        double* __restrict__ short_term, int ns_max) {
+    __shared__ double red[kGateThreads];
+    __shared__ unsigned hist[kGateThreads];
+    __shared__ unsigned long long found[2];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int bins = clamp_len(lengths, b, L) / H;
+    const int nb = bins >= 4 ? bins - 3 : 0, ns = bins >= kShortBins ? bins - (kShortBins - 1) : 0;
+    double* st = st_all + (size_t)b * bins_max;
+    // the channel-weighted mean square of the n bins from bin j on, the bin sums added left to right
+    auto power = [&](int j, int n) {
+        double p = 0.0;
+        for (int c = 0; c < ch; ++c) {
+            const double* s = sums + ((size_t)b * ch + c) * bins_max + j;
+            double acc = s[0];
+            for (int i = 1; i < n; ++i) acc += s[i];
+            p += (weights ? (double)weights[c] : 1.0) * (acc / ((double)n * (double)H));
+        }
+        return p;
+    };
+    auto lufs = [](double p) { return -0.691 + 10.0 * log10(p); };
+    double mom = 0.0, shr = 0.0, sum = 0.0, cnt = 0.0;
+    for (int j = tid; j < nb; j += kGateThreads) {
+        const double p = power(j, 4);
+        mom = p > mom ? p : mom;
+    }
+    for (int j = tid; j < ns; j += kGateThreads) {           // (thread tid alone touches st[tid + 256 i], here and below)
+        const double q = power(j, kShortBins);
+        st[j] = q;
+        shr = q > shr ? q : shr;
+        if (lufs(q) > -70.0) { sum += q; cnt += 1.0; }
+    }
+    if (short_term)
+        for (int j = tid; j < ns_max; j += kGateThreads) short_term[(size_t)b * ns_max + j] = j < ns ? st[j] : 0.0;
+    mom = tree_max(mom, red);
+    shr = tree_max(shr, red);
+    sum = tree_sum(sum, red);
+    cnt = tree_sum(cnt, red);
+    double kept = 0.0, p10 = 0.0, p95 = 0.0, lra = 0.0;
+    if (cnt > 0.0) {                                         // (uniform over the workgroup)
+        const double rel = lufs(sum / cnt) - 20.0;
+        double cnt2 = 0.0;
+        for (int j = tid; j < ns; j += kGateThreads) {
+            const double l = lufs(st[j]);
+            if (l > -70.0 && l > rel) cnt2 += 1.0;
+            else st[j] = __longlong_as_double(-1ll);
+        }
+        kept = tree_sum(cnt2, red);
+        if (kept > 0.0) {
+            // floor((n - 1) * 0.10 + 0.5) and the same at 0.95, rounded as the host rounds them (no fused multiply-add)
+            const unsigned k10 = (unsigned)floor(__dadd_rn(__dmul_rn(kept - 1.0, 0.10), 0.5));
+            const unsigned k95 = (unsigned)floor(__dadd_rn(__dmul_rn(kept - 1.0, 0.95), 0.5));
+            p10 = __longlong_as_double((long long)radix_select(st, ns, k10, hist, found));
+            p95 = __longlong_as_double((long long)radix_select(st, ns, k95, hist, found));
+            lra = 10.0 * log10(p95 / p10);
+        }
+    }
+    if (tid == 0) {
+        double* o = out + (size_t)10 * b;
+        o[3] = nb ? lufs(mom) : -INFINITY;
+        o[4] = ns ? lufs(shr) : -INFINITY;
+        o[5] = lra;
+        o[6] = (double)ns;
+        o[7] = kept;
+        o[8] = p10;
+        o[9] = p95;
     }
 }
 
@@ -263,9 +384,10 @@ int lass_loudness_lanes(int hop) {
     return nl;
 }
 
-hipError_t lass_launch_loudness(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L,
-                                const int* lengths, int hop, const LoudnessFilter& f, const float* weights, double* out,
-                                double* blocks, int nb_max, double* scratch, hipStream_t stream) {
+// The meter up to and including k_gate; out: rows of out_pitch doubles.
+static hipError_t launch_meter(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L,
+                               const int* lengths, int hop, const LoudnessFilter& f, const float* weights, double* out, int out_pitch,
+                               double* blocks, int nb_max, double* scratch, hipStream_t stream) {
     const int bins_max = L / hop;
     if (B <= 0 || ch < 1 || ch > 8 || (long long)B * ch > 65535 || hop < 1 || L < 1) return hipErrorInvalidValue;
     State* states = reinterpret_cast<State*>(scratch);
@@ -291,7 +413,26 @@ hipError_t lass_launch_loudness(const float* planes, long long row_stride, long 
                            bins_max, f, states, sums);
     }
     hipLaunchKernelGGL(k_gate, dim3(B), dim3(kGateThreads), 0, stream, sums, ch, L, lengths, hop, bins_max > 0 ? bins_max : 1, weights,
-                       out, blocks, nb_max);
+                       out, out_pitch, blocks, nb_max);
+    return hipGetLastError();
+}
+
+hipError_t lass_launch_loudness(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L,
+                                const int* lengths, int hop, const LoudnessFilter& f, const float* weights, double* out,
+                                double* blocks, int nb_max, double* scratch, hipStream_t stream) {
+    return launch_meter(planes, row_stride, plane_stride, B, ch, L, lengths, hop, f, weights, out, 3, blocks, nb_max, scratch, stream);
+}
+
+hipError_t lass_launch_loudness_stats(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L,
+                                      const int* lengths, int hop, const LoudnessFilter& f, const float* weights, double* out,
+                                      double* blocks, int nb_max, double* short_term, int ns_max, double* scratch, hipStream_t stream) {
+    hipError_t e = launch_meter(planes, row_stride, plane_stride, B, ch, L, lengths, hop, f, weights, out, 10, blocks, nb_max, scratch,
+                                stream);
+    if (e != hipSuccess) return e;
+    const int bins_max = L / hop;
+    const double* sums = scratch + (size_t)4 * B * ch * bins_max;
+    hipLaunchKernelGGL(k_range, dim3(B), dim3(kGateThreads), 0, stream, sums, ch, L, lengths, hop, bins_max > 0 ? bins_max : 1, weights,
+                       out, scratch + (size_t)5 * B * ch * bins_max, short_term, ns_max);
     return hipGetLastError();
 }
 

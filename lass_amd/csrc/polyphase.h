@@ -47,6 +47,26 @@ __device__ __forceinline__ FirTile fir_tile(float* lds, int up, int down, int n_
     return T;
 }
 
+// The same for a tile that does not start at blockIdx.x * tile: the `count` outputs from output `first` >= 0 on (a tile with a
+// halo, export.hip's true-peak sink).  A sibling and not a generalisation, so that fir_tile's callers compile to what they did.
+__device__ __forceinline__ FirTile fir_tile_at(float* lds, int up, int down, int n_taps, int J, long long first, int count) {
+    FirTile T;
+    T.J = J;
+    T.Jp = J | 1;
+    T.up = up;
+    T.down = down;
+    T.tab = lds;
+    T.span = lds + (size_t)up * T.Jp;
+    T.n0 = first;
+    const long long t0 = first * down + (n_taps - 1) / 2;
+    const long long q0 = t0 / up;
+    T.r0 = (unsigned)(t0 - q0 * up);
+    T.nout = count;
+    T.S = (int)((T.r0 + (unsigned)(count - 1) * (unsigned)down) / (unsigned)up) + J;
+    T.mlo = q0 - (J - 1);
+    return T;
+}
+
 // tab <- taps.  The caller's first span fill may follow at once; one __syncthreads() after it covers both.
 __device__ __forceinline__ void fir_table(const FirTile& T, const float* __restrict__ taps, int n_taps) {
     // only the last tap of a phase can lie past the filter's end

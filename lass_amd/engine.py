@@ -751,6 +751,77 @@ class Engine:
         _lib.check(self.ctx, rc, "lass_resample_peak")
         return peak
 
+    def resample_true_peak(self, planes: torch.Tensor, rate_in: int, rate_out: int, frames_out: Optional[int] = None) -> torch.Tensor:
+        """(B,) float32: the true peak of what `resample_encode` of the same arguments quantises - the larger of `resample_peak`
+        and the peak of those samples interpolated os = loudness.oversampling(rate_out) times, phase 0 left out
+        (lass_resample_true_peak; lass_amd.loudness.true_peak is its float64 definition).  Bit-identical to `resample` of
+        `resample`'s own output at (os, 1); a NaN is skipped.  With os == 1 it is `resample_peak`.  A ratio
+        `resample.true_peak_fits` refuses raises LassError."""
+        from . import loudness as ld
+        from . import resample as rs
+        os_ = ld.oversampling(rate_out)
+        if os_ == 1:
+            return self.resample_peak(planes, rate_in, rate_out, frames_out)
+        planes, row_stride, plane_stride = self._planes(planes)
+        B, C, L = planes.shape
+        up, down = rs.ratio(rate_in, rate_out)
+        ceiling = rs.out_len(L, up, down)
+        frames_out = ceiling if frames_out is None else int(frames_out)
+        if not 1 <= frames_out <= ceiling:
+            raise _lib.LassError(f"frames_out must lie in 1 ... ceil(L * up / down) = {ceiling}")
+        fir = (up, down) != (1, 1)
+        if fir and not rs.within_cap(up, down):
+            raise _lib.LassError(f"resampling {rate_in} -> {rate_out} Hz needs {rs.n_taps(up, down)} taps, over the device "
+                                 f"kernel's cap of {rs.MAX_TAPS}")
+        taps = rs.device_taps(up, down, self.device) if fir else None
+        os_taps = rs.device_taps(os_, 1, self.device)
+        peak = torch.empty(B, dtype=torch.float32, device=self.device)
+        rc = self.lib.lass_resample_true_peak(self.ctx, _ptr(planes), row_stride, plane_stride, B, C, L, up, down, _ptr(taps),
+                                              taps.numel() if fir else 1, frames_out, os_, _ptr(os_taps), os_taps.numel(), _ptr(peak),
+                                              _stream(self.device))
+        _lib.check(self.ctx, rc, "lass_resample_true_peak")
+        return peak
+
+    STATS_COLUMNS = ("loudness", "blocks", "blocks_kept", "max_momentary", "max_short_term", "loudness_range", "short_term_blocks",
+                     "short_term_kept", "p10", "p95")
+
+    def loudness_stats(self, planes: torch.Tensor, rate: int, lengths=None, weights=None, return_short_term: bool = False):
+        """`loudness` with the other EBU R 128 figures, on the device (lass_loudness_stats; lass_amd.loudness is the float64
+        definition): a dict of (B,) float64 tensors - "loudness" (as `loudness`, bit for bit), "blocks", "blocks_kept",
+        "max_momentary" and "max_short_term" (LUFS, ungated), "loudness_range" (LU, EBU Tech 3342), "short_term_blocks",
+        "short_term_kept", "p10", "p95" (the two percentile powers) - views of one (B, 10) tensor, which is "all".
+        return_short_term: also "short_term", the (B, ns) short-term powers (zeros past a recording's own count)."""
+        from . import loudness as ld
+        planes, row_stride, plane_stride = self._planes(planes)
+        B, C, L = planes.shape
+        coef = ld.coefficients(rate)
+        hop = int(rate) // 10
+        lengths, weights = self._meter_args(lengths, weights, B, C)
+        out = torch.empty(B, 10, dtype=torch.float64, device=self.device)
+        ns = ld.n_short_term(L, rate)
+        short = torch.empty(B, ns, dtype=torch.float64, device=self.device) if return_short_term else None
+        scratch = torch.empty(max((5 * C + 1) * B * (L // hop), 1), dtype=torch.float64, device=self.device)
+        rc = self.lib.lass_loudness_stats(self.ctx, _ptr(planes), row_stride, plane_stride, B, C, L, _ptr(lengths), hop,
+                                          (c_double * 10)(*coef.tolist()), _ptr(weights), _ptr(out), None, 0, _ptr(short), ns,
+                                          _ptr(scratch), scratch.numel() * 8, _stream(self.device))
+        _lib.check(self.ctx, rc, "lass_loudness_stats")
+        res = {name: out[:, k] for k, name in enumerate(self.STATS_COLUMNS)}
+        res["all"] = out
+        if return_short_term:
+            res["short_term"] = short
+        return res
+
+    def _meter_args(self, lengths, weights, B: int, C: int):
+        if lengths is not None:
+            lengths = torch.as_tensor(lengths).to(device=self.device, dtype=torch.int32).contiguous()
+            if tuple(lengths.shape) != (B,):
+                raise _lib.LassError(f"lengths must have shape ({B},)")
+        if weights is not None:
+            weights = torch.as_tensor(weights).to(device=self.device, dtype=torch.float32).contiguous()
+            if tuple(weights.shape) != (C,):
+                raise _lib.LassError(f"weights must have shape ({C},)")
+        return lengths, weights
+
     def loudness(self, planes: torch.Tensor, rate: int, lengths=None, weights=None, return_blocks: bool = False,
                  return_counts: bool = False):
         """ITU-R BS.1770-4 gated integrated loudness on the device (lass_loudness; lass_amd.loudness is its float64 definition):
@@ -763,14 +834,7 @@ class Engine:
         B, C, L = planes.shape
         coef = ld.coefficients(rate)
         hop = int(rate) // 10
-        if lengths is not None:
-            lengths = torch.as_tensor(lengths).to(device=self.device, dtype=torch.int32).contiguous()
-            if tuple(lengths.shape) != (B,):
-                raise _lib.LassError(f"lengths must have shape ({B},)")
-        if weights is not None:
-            weights = torch.as_tensor(weights).to(device=self.device, dtype=torch.float32).contiguous()
-            if tuple(weights.shape) != (C,):
-                raise _lib.LassError(f"weights must have shape ({C},)")
+        lengths, weights = self._meter_args(lengths, weights, B, C)
         nb = max(ld.n_blocks(L, rate), 0)
         out = torch.empty(B, 3, dtype=torch.float64, device=self.device)
         blocks = torch.empty(B, nb, dtype=torch.float64, device=self.device) if return_blocks else None

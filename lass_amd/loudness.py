@@ -18,6 +18,11 @@ which is a 4-state affine recurrence s[n+1] = M s[n] + v x[n].  Both this module
 run every chunk from a zero state, carry the true states over the chunk ends with a power of M, and add each chunk's response
 to its true initial state - here with numpy over all chunks at once, because a Python loop over millions of samples is not an
 option.  In float64 the split changes the result by rounding only (1e-15 relative).
+
+The second half of the module is what an EBU R 128 delivery is checked against beside the integrated loudness, again written
+from the recommendations (BS.1770-4 Annex 2, EBU Tech 3341 and 3342) and pinned by their test signals (tests/test_r128_cpu.py):
+`true_peak` with its `oversampling`, `short_term_powers`, `loudness_range`, `max_momentary` and `max_short_term` - the float64
+definitions of `lass_resample_true_peak` (csrc/export.hip) and `lass_loudness_stats` (csrc/loudness.hip); DESIGN.md section 19.
 """
 from __future__ import annotations
 
@@ -162,6 +167,114 @@ def integrated_loudness(x, rate: int, weights=None) -> float:
     """Gated integrated loudness of x (C, N) in LUFS (BS.1770-4: 400 ms blocks at 75 % overlap, absolute gate -70 LUFS, relative
     gate -10 LU); -inf when no block survives (shorter than one block, silent)."""
     return gate(block_powers(x, rate, weights))[0]
+
+
+# ---- EBU R 128: true peak, short-term and momentary maxima, loudness range (DESIGN.md section 19) -----------------------------
+RANGE_GATE = -20.0        # LU under the absolute-gated short-term loudness (EBU Tech 3342)
+SHORT_TERM_BINS = 30      # a 3 s short-term block in 100 ms hop bins
+
+
+def oversampling(rate: int) -> int:
+    """The true-peak meter's oversampling factor: 4 up to 48 kHz, 2 at 88.2 and 96 kHz, 1 (the sample peak) from 176.4 kHz
+    (BS.1770-4 Annex 2 asks 4x at 48 kHz and proportionally less above; an N x meter's under-read depends on f/fs alone)."""
+    return max(1, min(4, 192000 // int(rate)))
+
+
+def true_peak(y, rate: int, dtype=np.float64) -> float:
+    """The true peak (linear) of y (C, N) or (N,): with os = oversampling(rate), the larger of the sample peak and the peak of the
+    os - 1 interpolated phases of `resample.resample_host(y_c, os, 1, dtype)`, over the channels.  Phase 0 is the samples
+    themselves, not the filtered samples, so a true peak is never under the sample peak.  NaNs are skipped."""
+    from . import resample as rs
+    dtype = np.dtype(dtype)
+    y = np.atleast_2d(np.asarray(y, dtype=dtype))
+    os_ = oversampling(rate)
+    peak = 0.0
+    for c in range(y.shape[0]):
+        if y.shape[1] == 0:
+            continue
+        a = np.abs(y[c])
+        if os_ > 1:
+            with np.errstate(invalid="ignore"):
+                z = np.abs(rs.resample_host(y[c], os_, 1, dtype)).reshape(-1, os_)[:, 1:]
+            a = np.concatenate([a, z.reshape(-1)])
+        a = a[~np.isnan(a)]
+        if a.size:
+            peak = max(peak, float(a.max()))
+    return peak
+
+
+def n_short_term(n: int, rate: int) -> int:
+    """Whole 3 s blocks, 100 ms apart, in n samples."""
+    bins = int(n) // (int(rate) // 10)
+    return bins - (SHORT_TERM_BINS - 1) if bins >= SHORT_TERM_BINS else 0
+
+
+def short_term_powers_of_weighted(y, rate: int, weights=None, dtype=np.float64) -> np.ndarray:
+    """(ns,) short-term powers of an already K-weighted y (C, N): with H = rate // 10 and S_c[i] the sum of the squares of bin i
+    (summed as `powers_of_weighted` sums a block), q_j = sum_c G_c * (S_c[j] + ... + S_c[j+29]) / (30 H), added left to right."""
+    dtype = np.dtype(dtype)
+    y = np.atleast_2d(np.asarray(y, dtype=dtype))
+    C, N = y.shape
+    H = int(rate) // 10
+    ns = n_short_term(N, rate)
+    w = np.ones(C, dtype=dtype) if weights is None else np.asarray(weights, dtype=dtype).reshape(C)
+    q = np.zeros(ns, dtype=dtype)
+    if ns:
+        bins = N // H
+        for c in range(C):
+            S = np.sum(np.square(y[c, :bins * H]).reshape(bins, H), axis=1, dtype=dtype)
+            acc = S[0:ns].copy()
+            for i in range(1, SHORT_TERM_BINS):
+                acc += S[i:i + ns]
+            q += w[c] * (acc / dtype.type(SHORT_TERM_BINS * H))
+    return q
+
+
+def short_term_powers(x, rate: int, weights=None, dtype=np.float64) -> np.ndarray:
+    """(ns,) short-term powers of x (C, N): `short_term_powers_of_weighted` of `k_weighted(x)`, everything in `dtype`."""
+    x = np.atleast_2d(np.asarray(x, dtype=dtype))
+    k_weighting(rate)
+    if n_short_term(x.shape[1], rate) == 0:
+        return np.zeros(0, dtype=dtype)
+    return short_term_powers_of_weighted(k_weighted(x, rate, dtype), rate, weights, dtype)
+
+
+def loudness_range(q) -> Tuple[float, float, float, int]:
+    """(LRA in LU, p10, p95, blocks kept) of short-term powers q (EBU Tech 3342): absolute gate l > -70 LUFS, relative gate
+    l > (loudness of the mean of the abs-gated q) - 20; of the n survivors sorted ascending, p10 = v[floor((n-1) * 0.10 + 0.5)],
+    p95 = v[floor((n-1) * 0.95 + 0.5)], LRA = 10 log10(p95 / p10).  (0, 0, 0, 0) when none survives."""
+    q = np.asarray(q, dtype=np.float64).reshape(-1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        l = OFFSET + 10.0 * np.log10(q)
+        keep = l > ABSOLUTE_GATE
+        if not keep.any():
+            return 0.0, 0.0, 0.0, 0
+        keep &= l > OFFSET + 10.0 * np.log10(np.mean(q[keep])) + RANGE_GATE
+    v = np.sort(q[keep])
+    n = v.shape[0]
+    if n == 0:
+        return 0.0, 0.0, 0.0, 0
+    p10 = float(v[int(np.floor((n - 1) * 0.10 + 0.5))])
+    p95 = float(v[int(np.floor((n - 1) * 0.95 + 0.5))])
+    return float(10.0 * np.log10(p95 / p10)), p10, p95, n
+
+
+def _max_loudness(p) -> float:
+    p = np.asarray(p, dtype=np.float64).reshape(-1)
+    if p.size == 0:
+        return float("-inf")
+    with np.errstate(divide="ignore"):
+        return float(OFFSET + 10.0 * np.log10(np.max(p)))
+
+
+def max_momentary(p) -> float:
+    """The maximum momentary loudness (LUFS, ungated) of the 400 ms block powers p; -inf for none."""
+    return _max_loudness(p)
+
+
+def max_short_term(q) -> float:
+    """The maximum short-term loudness (LUFS, ungated) of the 3 s block powers q; -inf for none."""
+    return _max_loudness(q)
 
 
 def gain_for(loudness: float, peak: Optional[float], target: Optional[float], ceiling: Optional[float]) -> Tuple[np.float32, bool]:

@@ -24,6 +24,11 @@ resampler, so no file-rate float plane is made), `Engine.resample_peak` of the s
 `Engine.resample_encode(gain=)`.  Loudness, gain and the limited flag travel to the host behind the payload, with the clip
 counter.  Without a level none of this runs: the pass is the one above.
 
+For an EBU R 128 delivery (-23 LUFS, -1 dBTP) `peak="true"` puts `Engine.resample_true_peak` - the peak of the signal between
+the samples the encoder is about to quantise - where `Engine.resample_peak` stood, and `meter=True` puts `Engine.loudness_stats`
+where `Engine.loudness` stood: loudness range, maximum momentary and maximum short-term loudness travel to the host with the
+rest.  At their defaults neither launches anything and no record gains a key.
+
 A file the device kernels do not take - a header `wavio.wav_info` does not fully understand, more than 8 channels, a rate pair
 beyond `resample.within_cap` in either direction - is decoded, resampled and written on the host (`wavio._resample`,
 `wavio.write_wav_*`); its separation still runs on the device, in the same pass, and its record says `path == "host"`.
@@ -48,9 +53,10 @@ _WRITERS = {"pcm16": wavio.write_wav_pcm16, "pcm32": wavio.write_wav_pcm32, "f32
 
 
 # ---- planning (host only) ---------------------------------------------------------------------------------------------------
-def route(info, sampling_rate: int, out_rate: Optional[int] = None) -> str:
+def route(info, sampling_rate: int, out_rate: Optional[int] = None, true_peak: bool = False) -> str:
     """"device" if the two device kernels take the file - `info` a `wavio.wav_info` tuple, at most 8 channels, and both rate
-    pairs (file -> model, model -> output) within the kernels' tap cap - else "host"."""
+    pairs (file -> model, model -> output) within the kernels' tap cap - else "host".  true_peak: a true peak is asked for, and
+    the output pair must also be one `Engine.resample_true_peak` takes (`resample.true_peak_fits`)."""
     if info is None:
         return "host"
     _, nch, rate, _, _ = info
@@ -58,6 +64,8 @@ def route(info, sampling_rate: int, out_rate: Optional[int] = None) -> str:
         return "host"
     out_rate = rate if out_rate is None else int(out_rate)
     if not rs.within_cap(*rs.ratio(rate, sampling_rate)) or not rs.within_cap(*rs.ratio(sampling_rate, out_rate)):
+        return "host"
+    if true_peak and not rs.true_peak_fits(*rs.ratio(sampling_rate, out_rate), ld.oversampling(out_rate)):
         return "host"
     return "device"
 
@@ -212,17 +220,33 @@ def _write_host(path: str, encoding: str, x: np.ndarray, rate: int, profile) -> 
         profile["write"] = profile.get("write", 0.0) + time.perf_counter() - t0
 
 
-def _level_record(measured: float, gain, limited: bool) -> dict:
+def _level_record(measured: float, gain, limited: bool, true_peak=None) -> dict:
+    """true_peak: the float32 true peak before the gain, with peak="true"."""
     with np.errstate(divide="ignore"):
-        return {"loudness_out": float(measured), "gain": float(gain), "gain_db": float(20.0 * np.log10(np.float64(gain))),
-                "peak_limited": bool(limited)}
+        rec = {"loudness_out": float(measured), "gain": float(gain), "gain_db": float(20.0 * np.log10(np.float64(gain))),
+               "peak_limited": bool(limited)}
+        if true_peak is not None:
+            rec["true_peak_db"] = float(20.0 * np.log10(np.float64(gain) * np.float64(true_peak)))
+    return rec
+
+
+def _meter_record(loudness_range: float, max_momentary: float, max_short_term: float) -> dict:
+    return {"loudness_range": float(loudness_range), "max_momentary": float(max_momentary), "max_short_term": float(max_short_term)}
+
+
+def check_peak_arg(peak, peak_ceiling_db) -> None:
+    """ValueError for a `peak` that is neither "sample" nor "true", or "true" without a ceiling to hold it to."""
+    if peak not in ("sample", "true"):
+        raise ValueError('peak must be "sample" or "true"')
+    if peak == "true" and peak_ceiling_db is None:
+        raise ValueError('peak="true" needs a peak_ceiling_db')
 
 
 def separate_files(model, jobs, sampling_rate: int, channels: str = "each", encoding: Optional[str] = None,
                    out_rate: Optional[int] = None, window: int = 160000, context: int = 16000, fade: int = 0,
                    fade_shape: str = "linear", max_batch: int = 16, max_samples: int = DEFAULT_MAX_SAMPLES,
                    profile: Optional[Dict[str, float]] = None, loudness: Optional[float] = None,
-                   peak_ceiling_db: Optional[float] = None) -> List[dict]:
+                   peak_ceiling_db: Optional[float] = None, peak: str = "sample", meter: bool = False) -> List[dict]:
     """Separate WAV files by caption, file in and file out.  model: an `AudioSep`-shaped holder (`.ss_model` a ResUNet30 on the
     device working at `sampling_rate`, `.query_encoder` with `get_query_embed`); jobs: a sequence of (in_path, query, out_path),
     query a caption or a (512,) embedding.  channels "each": every channel of a file is separated on its own with the file's
@@ -239,6 +263,12 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
     largest value that does not clip, so "clipped" is then 0.  One gain per file.  With either, a record also has "loudness_out"
     (measured on the separated planes before the gain; -inf for a file shorter than 400 ms or silent, which gets gain 1 or the
     ceiling's gain alone), "gain" (linear, the float32 applied), "gain_db" and "peak_limited" (whether the ceiling lowered it).
+    peak "true" (it needs a peak_ceiling_db): the ceiling holds the true peak - the peak of the written signal between its samples,
+    4 x oversampled up to 48 kHz (`loudness.true_peak`, `Engine.resample_true_peak`) - instead of the sample peak, as EBU R 128's
+    -1 dBTP asks; a true peak is never under the sample peak, so "clipped" stays 0, and the record gains "true_peak_db", the true
+    peak of what was written (20 log10 of gain x true peak).  meter: the record gains "loudness_range" (LU, EBU Tech 3342),
+    "max_momentary" and "max_short_term" (LUFS), measured like "loudness_out" on the separated planes at the model rate before
+    the gain (`Engine.loudness_stats` in the place of `Engine.loudness`); with or without a level.
     A file not longer than n_fft/2 samples at the model rate raises ValueError before anything is written."""
     import torch
 
@@ -247,7 +277,10 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
     if encoding is not None and encoding not in rs.ENCODINGS:
         raise ValueError(f"encoding must be one of {sorted(rs.ENCODINGS)} or None")
     ld.check_level_args(loudness, peak_ceiling_db)
+    check_peak_arg(peak, peak_ceiling_db)
     level = loudness is not None or peak_ceiling_db is not None
+    true_peak, meter = peak == "true", bool(meter)
+    extra = level or meter               # whether anything travels behind the payload beside the clip counter
     jobs = [tuple(j) for j in jobs]
     ss = model.ss_model
     eng = ss.engine
@@ -257,7 +290,7 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
     infos, hows, sizes = [], [], []
     for in_path, _, _ in jobs:
         info = wavio.wav_info(in_path)
-        how = route(info, sr, out_rate)
+        how = route(info, sr, out_rate, true_peak)
         meta = info[:4] if info is not None else _host_info(in_path)
         n_planes, length = model_samples(meta[1], meta[2], meta[3], sr, channels)
         if length <= eng.n_fft // 2:   # longform.plan_windows' refusal, with the file's name, before anything is written
@@ -315,18 +348,24 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
                 frames_o = frames if rate_o == rate else rs.out_len(L, *rs.ratio(sr, rate_o))
                 rec = {"rate": rate_o, "channels": n, "frames": frames_o, "path": hows[i]}
                 if hows[i] == "device":
-                    stacked, gain = torch.stack(mine), None
-                    if level:
+                    stacked, gain, pk, stats = torch.stack(mine), None, None, None
+                    if extra:
                         with clock("level"):
-                            measured = eng.loudness(stacked, sr)
-                            peak = eng.resample_peak(stacked, sr, rate_o, frames_out=frames_o) if peak_ceiling_db is not None else None
-                            gain, limited = eng.loudness_gain(measured, peak, loudness, ld.ceiling_for(peak_ceiling_db, enc_o))
+                            if meter:
+                                stats = eng.loudness_stats(stacked, sr)["all"]
+                                measured = stats[:, 0]
+                            else:
+                                measured = eng.loudness(stacked, sr)
+                            if peak_ceiling_db is not None:
+                                pk = (eng.resample_true_peak if true_peak else eng.resample_peak)(stacked, sr, rate_o, frames_out=frames_o)
+                            if level:
+                                gain, limited = eng.loudness_gain(measured, pk, loudness, ld.ceiling_for(peak_ceiling_db, enc_o))
                     with clock("encode"):
                         clipped = torch.zeros(1, dtype=torch.int32, device=dev)
                         payload = eng.resample_encode(stacked, sr, rate_o, enc_o, frames_out=frames_o, clipped=clipped, gain=gain)
                     nbytes = payload.shape[1]
-                    tail = (nbytes + 7) // 8 * 8 if level else (nbytes + 3) // 4 * 4   # the clip counter travels behind the payload
-                    buf = pool.take(tail + (24 if level else 4))
+                    tail = (nbytes + 7) // 8 * 8 if extra else (nbytes + 3) // 4 * 4   # the clip counter travels behind the payload
+                    buf = pool.take(tail + (24 if extra else 4) + (80 if meter else 0))
                     with clock("d2h"):
                         buf[:nbytes].copy_(payload[0], non_blocking=True)
                         buf[tail:tail + 4].view(torch.int32).copy_(clipped, non_blocking=True)
@@ -334,6 +373,10 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
                             buf[tail + 4:tail + 8].view(torch.int32).copy_(limited, non_blocking=True)
                             buf[tail + 8:tail + 12].view(torch.float32).copy_(gain, non_blocking=True)
                             buf[tail + 16:tail + 24].view(torch.float64).copy_(measured, non_blocking=True)
+                            if true_peak:
+                                buf[tail + 12:tail + 16].view(torch.float32).copy_(pk, non_blocking=True)
+                        if meter:                                  # ... and the ten numbers of Engine.loudness_stats
+                            buf[tail + 24:tail + 104].view(torch.float64).copy_(stats[0], non_blocking=True)
                         done = torch.cuda.Event()
                         done.record(torch.cuda.current_stream(dev))
                     written.append((i, buf, tail, writer.submit(_write_device, jobs[i][2], wavio.wav_header(enc_o, n, rate_o, frames_o),
@@ -342,12 +385,20 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
                     with clock("d2h"):
                         x = torch.stack(mine).cpu().numpy()
                     y = _host_resample(x, sr, rate_o)[:, :frames_o]
-                    if level:                                      # the device's rule with lass_amd.loudness and numpy
-                        measured = ld.integrated_loudness(x, sr)
-                        g, bit = ld.gain_for(measured, float(np.nanmax(np.abs(y))) if y.size else 0.0, loudness,
-                                             ld.ceiling_for(peak_ceiling_db, enc_o))
+                    if extra:                                      # the device's rule with lass_amd.loudness and numpy
+                        p = ld.block_powers(x, sr)
+                    if level:
+                        measured = ld.gate(p)[0]
+                        if true_peak:
+                            pk = np.float32(ld.true_peak(y, rate_o))
+                        else:
+                            pk = float(np.nanmax(np.abs(y))) if y.size else 0.0
+                        g, bit = ld.gain_for(measured, pk, loudness, ld.ceiling_for(peak_ceiling_db, enc_o))
                         y = (g * y.astype(np.float32)).astype(np.float32)
-                        rec.update(_level_record(measured, g, bit))
+                        rec.update(_level_record(measured, g, bit, pk if true_peak else None))
+                    if meter:
+                        q = ld.short_term_powers(x, sr)
+                        rec.update(_meter_record(ld.loudness_range(q)[0], ld.max_momentary(p), ld.max_short_term(q)))
                     rec["clipped"] = host_clip_count(y, enc_o)
                     written.append((i, None, 0, writer.submit(_write_host, jobs[i][2], enc_o, y, rate_o, profile)))
                 records[i] = rec
@@ -360,7 +411,11 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
                     if level:
                         records[i].update(_level_record(float(buf[tail + 16:tail + 24].view(torch.float64)[0]),
                                                         np.float32(buf[tail + 8:tail + 12].view(torch.float32)[0].item()),
-                                                        bool(buf[tail + 4:tail + 8].view(torch.int32)[0])))
+                                                        bool(buf[tail + 4:tail + 8].view(torch.int32)[0]),
+                                                        np.float32(buf[tail + 12:tail + 16].view(torch.float32)[0].item()) if true_peak else None))
+                    if meter:
+                        ten = buf[tail + 24:tail + 104].view(torch.float64)
+                        records[i].update(_meter_record(float(ten[5]), float(ten[3]), float(ten[4])))
                     pool.give(buf)
             for buf in uploaded:
                 pool.give(buf)
@@ -369,8 +424,8 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
 
 
 def inference(model, audio_file: str, text, output_file: str, sampling_rate: int = 32000, loudness: Optional[float] = None,
-              peak_ceiling_db: Optional[float] = None, **kw) -> dict:
-    """One file through `separate_files`: the single-file shape of upstream AudioSep's `pipeline.inference`.  loudness, peak_ceiling_db and the
-    other keywords are `separate_files`'s.  Returns the job's record."""
+              peak_ceiling_db: Optional[float] = None, peak: str = "sample", meter: bool = False, **kw) -> dict:
+    """One file through `separate_files`: the single-file shape of upstream AudioSep's `pipeline.inference`.  loudness, peak_ceiling_db,
+    peak, meter and the other keywords are `separate_files`'s.  Returns the job's record."""
     return separate_files(model, [(audio_file, text, output_file)], sampling_rate, loudness=loudness, peak_ceiling_db=peak_ceiling_db,
-                          **kw)[0]
+                          peak=peak, meter=meter, **kw)[0]

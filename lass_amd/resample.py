@@ -42,6 +42,27 @@ def within_cap(up: int, down: int) -> bool:
     return n_taps(up, down) <= MAX_TAPS
 
 
+LDS_FLOATS = 160 * 256      # csrc/polyphase.h: kLdsFloats, the CU's 160 KiB
+OS_TAPS_PER_PHASE = 21      # csrc/export.hip: kOsJ, ceil((20 * os + 1) / os)
+
+
+def true_peak_fits(up: int, down: int, os: int) -> bool:
+    """Whether `lass_resample_true_peak` takes this ratio at oversampling `os`: the ratio is within the tap cap, and a tile of one
+    frame - the filter table, the input span of the 21 first-stage outputs one interpolated value reaches, the stage that holds
+    them and the second table - fits the CU's LDS (the launcher's formula, csrc/export.hip: true_peak_floats at t = 1)."""
+    up, down, os = int(up), int(down), int(os)
+    stage = (1 + OS_TAPS_PER_PHASE - 1 + 3) // 4 * 4 + os * (OS_TAPS_PER_PHASE | 1)
+    if up == down:
+        return True
+    if not within_cap(up, down):
+        return False
+    nt = n_taps(up, down)
+    J = -(-nt // up)
+    table = up * (J | 1)
+    span = ((up - 1) + (1 + OS_TAPS_PER_PHASE - 1 - 1) * down) // up + J
+    return (table + span + 3) // 4 * 4 + stage <= LDS_FLOATS
+
+
 def out_len(frames: int, up: int, down: int) -> int:
     return -(-int(frames) * int(up) // int(down))
 

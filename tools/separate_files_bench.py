@@ -1,7 +1,7 @@
 """File in, file out on one MI355X: `pipeline.separate_files` against the same jobs done with the pieces the package had before
 it, on 32 seeded one-minute 44.1 kHz stereo PCM16 files (synthetic ResUNet30 weights, 16 kHz, f32 unless --compute-dtype).
 
-    python tools/separate_files_bench.py [--files 32] [--seconds 60] [--reps 5] [--compute-dtype f32] [--loudness]
+    python tools/separate_files_bench.py [--files 32] [--seconds 60] [--reps 5] [--compute-dtype f32] [--loudness [--true-peak] [--meter]]
 
 Leg A: `separate_files(channels="each")` - decode, resample, separate, resample back, encode and interleave on the device.
 Leg B: host decode + de-interleave + `wavio._resample` (scipy, float64), `separate_long_list`, `.cpu()`, host `_resample` back
@@ -13,6 +13,10 @@ with `profile=` (which synchronises after every stage, so its parts add up to mo
 --loudness: leg A against leg L, the same call with `loudness=-23.0, peak_ceiling_db=-1.0` (meter, peak and gain on the device, per
 file), alternating A L A L ...; no leg B, and the profiled run is leg L's, whose split has the `level` stage.  Leg A with this flag
 is the number to hold against the same tool's leg A on the parent commit: it launches the same kernels.
+
+--true-peak / --meter (with --loudness): a third leg R, leg L's call with `peak="true"` and / or `meter=True` (EBU R 128: the
+ceiling holds the true peak; loudness range and the two maxima beside the loudness), alternating A L R A L R ...; the profiled run
+is then leg R's.  Leg L is the number to hold against the parent's leg L; R over L is what the two arguments add.
 """
 import argparse
 import json
@@ -80,12 +84,14 @@ def host_pieces(model, jobs):
         wavio.write_wav_pcm16(out, y, rate)
 
 
-def leg(name: str, d: str, n: int, mode: str):
+def leg(name: str, d: str, n: int, mode: str, true_peak: bool = False, meter: bool = False):
     import torch
     from lass_amd import pipeline
     model = _model(mode)
     profile = {} if name.endswith("-profile") else None
-    level = dict(loudness=-23.0, peak_ceiling_db=-1.0) if name.startswith("L") else {}
+    level = dict(loudness=-23.0, peak_ceiling_db=-1.0) if name[0] in "LR" else {}
+    if name.startswith("R"):
+        level.update(peak="true" if true_peak else "sample", meter=meter)
 
     def run(jobs, profile=None):
         if name == "B":
@@ -112,21 +118,27 @@ def main():
     ap.add_argument("--compute-dtype", default="f32")
     ap.add_argument("--timeout", type=int, default=300, help="seconds per run")
     ap.add_argument("--loudness", action="store_true", help="leg A against leg L (loudness=-23, peak_ceiling_db=-1) instead of leg B")
-    ap.add_argument("--leg", choices=["A", "B", "L", "A-profile", "L-profile"])
+    ap.add_argument("--true-peak", action="store_true", help="with --loudness: a leg R with peak=\"true\"")
+    ap.add_argument("--meter", action="store_true", help="with --loudness: a leg R with meter=True")
+    ap.add_argument("--leg", choices=["A", "B", "L", "R", "A-profile", "L-profile", "R-profile"])
     ap.add_argument("--dir")
     a = ap.parse_args()
     if a.leg:
-        leg(a.leg, a.dir, a.files, a.compute_dtype)
+        leg(a.leg, a.dir, a.files, a.compute_dtype, a.true_peak, a.meter)
         return 0
+    r128 = a.true_peak or a.meter
+    if r128 and not a.loudness:
+        ap.error("--true-peak and --meter go with --loudness")
     with tempfile.TemporaryDirectory() as d:
         make_files(d, a.files, a.seconds)
         other = "L" if a.loudness else "B"
-        prof = "L-profile" if a.loudness else "A-profile"
-        times = {"A": [], other: []}
+        legs = ["A", other] + (["R"] if r128 else [])
+        prof = legs[-1] + "-profile" if a.loudness else "A-profile"
+        times = {name: [] for name in legs}
         split = None
-        for name in ["A", other] * a.reps + [prof]:
+        for name in legs * a.reps + [prof]:
             cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--leg", name, "--dir", d,
-                   "--files", str(a.files), "--compute-dtype", a.compute_dtype]
+                   "--files", str(a.files), "--compute-dtype", a.compute_dtype] + ["--true-peak"] * a.true_peak + ["--meter"] * a.meter
             pr = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, text=True)
             sys.stdout.write(pr.stdout)
             sys.stdout.flush()
@@ -145,6 +157,9 @@ def main():
             summary[name] = {"median_s": round(med, 4), "files_per_s": round(a.files / med, 2), "x_real_time": round(audio / med, 1),
                              "runs_s": ts}
         summary[other + "_over_A"] = round(summary[other]["median_s"] / summary["A"]["median_s"], 2)
+        if r128:
+            summary["R"]["true_peak"], summary["R"]["meter"] = a.true_peak, a.meter
+            summary["R_over_L"] = round(summary["R"]["median_s"] / summary["L"]["median_s"], 2)
         print(json.dumps(summary), flush=True)
     return 0
 
