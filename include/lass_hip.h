@@ -15,6 +15,15 @@
  *   - kernels are enqueued on the caller's `stream` (a hipStream_t passed as void*) and never synchronise.
  *   - the caller owns inputs, outputs and the workspace; the context owns re-laid-out weights and constant tables.
  *     `lass_separate` allocates nothing.
+ *   - workspaces and scratch buffers need no initialisation, and no result depends on their prior content: every kernel writes
+ *     what a later one reads, padding included.  (They may hold anything afterwards.)
+ *   - outputs are written in full unless their entry says otherwise.  The entries that say otherwise:
+ *       `clipped` of lass_resample_encode / lass_resample_encode_gain: counters the call ADDS to, zero-filled by the caller;
+ *       the fade regions of lass_separate_windows_faded / lass_istft_windows_faded: weighted and ADDED to `out`, which holds 0
+ *         there before the first window reaches them;
+ *       bytes past a row's end in the encoders (lass_resample_encode*, `out_stride` beyond the row's bytes): left alone;
+ *       samples outside `keep` in lass_separate_windows / lass_istft_windows and their faded forms: left alone.
+ *     tests/test_gpu_poison.py holds both rules, on buffers filled with 0x00, 0xFF (a NaN as f32 and as bf16) and 0x7F (3.39e38).
  *   - one context per (process, device); not re-entrant per context.  Every entry point makes the context's device
  *     current (hipSetDevice) before it launches or allocates, so the caller's current device does not matter.
  *   - there is NO CPU fallback: without a gfx950 device `lass_create` fails.

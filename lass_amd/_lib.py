@@ -198,10 +198,15 @@ class TowerContext:
 
 
 def grow_workspace(owner, nbytes: int, dev):
-    """owner._ws: a uint8 tensor of at least nbytes on `dev`; a smaller one is released before the larger one is allocated."""
+    """owner._ws: a uint8 tensor of at least nbytes on `dev`; a smaller one is released before the larger one is allocated.
+    Under poison (lass_amd._alloc) a cached one is filled again, on the current stream of `dev`."""
     import torch
+
+    from . import _alloc
 
     if owner._ws is None or owner._ws.device != dev or owner._ws.numel() < nbytes:
         owner._ws = None
-        owner._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        owner._ws = _alloc.empty(nbytes, dtype=torch.uint8, device=dev)
+    else:
+        _alloc.refill(owner._ws)
     return owner._ws

@@ -25,7 +25,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _alloc, _lib
 from .clap_text import ClapTextEncoder, _module
 
 EMBED_DIM, DEPTHS, HEADS0, WINDOW, PROJ = 128, (2, 2, 12, 2), 4, 8, 512
@@ -312,11 +312,11 @@ class ClapAudioEncoder(nn.Module):
         n = c_size_t()
         ctx.check(ctx.lib.lass_audioq_workspace_bytes(ctx.ctx, B, byref(n)), "lass_audioq_workspace_bytes")
         ws = _lib.grow_workspace(self, n.value, dev)
-        out = torch.empty(B, PROJ, dtype=torch.float32, device=dev)
+        out = _alloc.empty(B, PROJ, dtype=torch.float32, device=dev)
         t = lass_audioq_taps()
         res = {}
         if taps:
-            new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
+            new = lambda *s: _alloc.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
             if rate32k:
                 res["wave48k"] = new(B, (3 * L + 1) // 2)
                 t.wave48k = res["wave48k"].data_ptr()

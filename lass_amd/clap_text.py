@@ -17,7 +17,7 @@ from typing import Callable, Dict, List, Optional, Tuple
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _alloc, _lib
 
 HIDDEN, HEADS, FFN, PROJ = 768, 12, 3072, 512
 VOCAB, MAX_POSITIONS, TYPE_VOCAB = 50265, 514, 1  # roberta-base config.json
@@ -195,8 +195,8 @@ class ClapTextEncoder(nn.Module):
         ctx.check(ctx.lib.lass_text_workspace_bytes(ctx.ctx, N, S, byref(n)), "lass_text_workspace_bytes")
         ws = _lib.grow_workspace(self, n.value, dev)
         ids_dev = ids.to(dev)
-        out = torch.empty(N, PROJ, dtype=torch.float32, device=dev)
-        pool = torch.empty(N, HIDDEN, dtype=torch.float32, device=dev) if return_pooler else None
+        out = _alloc.empty(N, PROJ, dtype=torch.float32, device=dev)
+        pool = _alloc.empty(N, HIDDEN, dtype=torch.float32, device=dev) if return_pooler else None
         rc = ctx.lib.lass_text_encode(ctx.ctx, c_void_p(ids_dev.data_ptr()), c_void_p(mask.data_ptr()), N, S,
                                       c_void_p(out.data_ptr()), c_void_p(pool.data_ptr() if pool is not None else 0),
                                       c_void_p(ws.data_ptr()), ws.numel(),

@@ -8,7 +8,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from . import _lib, arch, longform
+from . import _alloc, _lib, arch, longform
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -114,8 +114,10 @@ class Engine:
         need = self.workspace_bytes(B, L)
         if self._ws_buf is None or self._ws_buf.numel() < need:
             self._ws_buf = None
-            self._ws_buf = torch.empty(need, dtype=torch.uint8, device=self.device)
+            self._ws_buf = _alloc.empty(need, dtype=torch.uint8, device=self.device)
             self.ws_allocations += 1
+        else:
+            _alloc.refill(self._ws_buf)  # under poison only, on the call's stream: a replayed graph meets fresh poison too
         self._ws_last = (B, L)
         return self._ws_buf
 
@@ -126,7 +128,7 @@ class Engine:
         condition = self._dev(condition)
         B, L = mixture.shape
         if out is None:
-            out = torch.empty_like(mixture)
+            out = _alloc.empty_like(mixture)
         elif (out.shape != mixture.shape or out.dtype != torch.float32 or out.device != self.device
               or not out.is_contiguous()):
             raise _lib.LassError(f"out must be a contiguous float32 {tuple(mixture.shape)} tensor on {self.device}")
@@ -175,7 +177,7 @@ class Engine:
         B, L = mixture.shape
         lens = self._ragged_lengths(lengths, B, L, checked, "separate_ragged")
         if out is None:
-            out = torch.empty_like(mixture)
+            out = _alloc.empty_like(mixture)
         elif (out.shape != mixture.shape or out.dtype != torch.float32 or out.device != self.device
               or not out.is_contiguous()):
             raise _lib.LassError(f"out must be a contiguous float32 {tuple(mixture.shape)} tensor on {self.device}")
@@ -327,7 +329,7 @@ class Engine:
         wav = self._dev(wav)
         B, L = wav.shape
         T = arch.frames_for(L, self.hop)
-        mk = lambda: torch.empty(B, T, self._stage_n_fft // 2 + 1, dtype=torch.float32, device=self.device)  # noqa: E731
+        mk = lambda: _alloc.empty(B, T, self._stage_n_fft // 2 + 1, dtype=torch.float32, device=self.device)  # noqa: E731
         mag, cos, sin = mk(), mk(), mk()
         re, im = (mk(), mk()) if want_complex else (None, None)
         rc = self.lib.lass_stft_magphase(self.ctx, _ptr(wav), B, L, _ptr(mag), _ptr(cos), _ptr(sin), _ptr(re),
@@ -342,7 +344,7 @@ class Engine:
         T = 1 + L // hop
         wins = [int(w) for w in win_lengths]
         n = len(wins)
-        outs = {w: tuple(torch.empty(B, 1, T, w // 2 + 1, dtype=torch.float32, device=self.device) for _ in range(3))
+        outs = {w: tuple(_alloc.empty(B, 1, T, w // 2 + 1, dtype=torch.float32, device=self.device) for _ in range(3))
                 for w in wins}
         arr = lambda i: (c_void_p * n)(*[outs[w][i].data_ptr() for w in wins])  # noqa: E731
         rc = self.lib.lass_multi_stft(self.ctx, _ptr(wav), B, L, hop, n, (c_int * n)(*wins), arr(0), arr(1), arr(2),
@@ -354,7 +356,7 @@ class Engine:
         real, imag = self._dev(real), self._dev(imag)
         B, T, F = real.shape
         assert F == self._stage_n_fft // 2 + 1 and imag.shape == real.shape
-        wav = torch.empty(B, length, dtype=torch.float32, device=self.device)
+        wav = _alloc.empty(B, length, dtype=torch.float32, device=self.device)
         rc = self.lib.lass_istft(self.ctx, _ptr(real), _ptr(imag), B, T, length, _ptr(wav), None, _stream(self.device))
         _lib.check(self.ctx, rc, "lass_istft")
         return wav
@@ -368,7 +370,7 @@ class Engine:
     def film(self, cond: torch.Tensor, raw: bool = False) -> torch.Tensor:
         cond = self._dev(cond)
         B = cond.shape[0]
-        out = torch.empty(B, self.film_width(), dtype=torch.float32, device=self.device)
+        out = _alloc.empty(B, self.film_width(), dtype=torch.float32, device=self.device)
         fn = self.lib.lass_film_raw if raw else self.lib.lass_film
         _lib.check(self.ctx, fn(self.ctx, _ptr(cond), B, _ptr(out), _stream(self.device)), "lass_film")
         return out
@@ -376,8 +378,8 @@ class Engine:
     def convblock(self, prefix: str, x: torch.Tensor, shift: torch.Tensor, cout: int) -> torch.Tensor:
         x = self._dev(x)
         B, _cin, H, W = x.shape
-        y = torch.empty(B, cout, H, W, dtype=torch.float32, device=self.device)
-        scratch = torch.empty_like(y)
+        y = _alloc.empty(B, cout, H, W, dtype=torch.float32, device=self.device)
+        scratch = _alloc.empty_like(y)
         rc = self.lib.lass_convblock(self.ctx, prefix.encode(), _ptr(x), B, H, W, _ptr(shift), _ptr(y), _ptr(scratch),
                                      _stream(self.device))
         _lib.check(self.ctx, rc, "lass_convblock")
@@ -387,10 +389,10 @@ class Engine:
         """One encoder block incl. its (fused) avg-pool: x (B,Cin,H,W) -> (y (B,Cout,H,W), pool or None)."""
         x = self._dev(x)
         B, _cin, H, W = x.shape
-        y = torch.empty(B, cout, H, W, dtype=torch.float32, device=self.device)
-        pool = (torch.empty(B, cout, H // down[0], W // down[1], dtype=torch.float32, device=self.device)
+        y = _alloc.empty(B, cout, H, W, dtype=torch.float32, device=self.device)
+        pool = (_alloc.empty(B, cout, H // down[0], W // down[1], dtype=torch.float32, device=self.device)
                 if tuple(down) != (1, 1) else None)
-        scratch = torch.empty_like(y)
+        scratch = _alloc.empty_like(y)
         rc = self.lib.lass_encoder_block(self.ctx, name.encode(), _ptr(x), B, H, W, _ptr(shift), _ptr(y), _ptr(pool),
                                          _ptr(scratch), _stream(self.device))
         _lib.check(self.ctx, rc, "lass_encoder_block")
@@ -412,9 +414,9 @@ class Engine:
                     and all(t.dtype == torch.float32 and t.is_contiguous() for t in (mag, cos, sin, x0))):
                 raise ValueError("front_end: `out` does not match this input's shapes")
         else:
-            mk = lambda: torch.empty(B, T, nb, dtype=torch.float32, device=self.device)  # noqa: E731
+            mk = lambda: _alloc.empty(B, T, nb, dtype=torch.float32, device=self.device)  # noqa: E731
             mag, cos, sin = mk(), mk(), mk()
-            x0 = torch.empty(x0_shape, dtype=torch.float32, device=self.device)
+            x0 = _alloc.empty(x0_shape, dtype=torch.float32, device=self.device)
         rc = self.lib.lass_front_end(self.ctx, _ptr(wav), B, L, _ptr(mag), _ptr(cos), _ptr(sin), _ptr(x0),
                                      _stream(self.device))
         _lib.check(self.ctx, rc, "lass_front_end")
@@ -429,9 +431,9 @@ class Engine:
         T = arch.frames_for(L, self.hop)
         nb = self.n_fft // 2 + 1
         shape = (B, arch.padded_frames(T), nb - 1)
-        mk = lambda: torch.empty(B, T, nb, dtype=torch.float32, device=self.device)  # noqa: E731
+        mk = lambda: _alloc.empty(B, T, nb, dtype=torch.float32, device=self.device)  # noqa: E731
         mag, cos, sin = mk(), mk(), mk()
-        x0 = torch.empty((self.n_branches,) + shape if self.multistft else shape, dtype=torch.float32, device=self.device)
+        x0 = _alloc.empty((self.n_branches,) + shape if self.multistft else shape, dtype=torch.float32, device=self.device)
         rc = self.lib.lass_front_end_ragged(self.ctx, _ptr(wav), _ptr(lens), B, L, _ptr(mag), _ptr(cos), _ptr(sin), _ptr(x0),
                                             _stream(self.device))
         _lib.check(self.ctx, rc, "lass_front_end_ragged")
@@ -449,7 +451,7 @@ class Engine:
         if n_fft != self.n_fft:
             raise _lib.LassError("istft_ragged: the bucket is the context's (n_fft must be the engine's)")
         lens = self._ragged_lengths(lengths, B, length, checked, "istft_ragged")
-        wav = torch.empty(B, length, dtype=torch.float32, device=self.device)
+        wav = _alloc.empty(B, length, dtype=torch.float32, device=self.device)
         rc = self.lib.lass_istft_ragged(self.ctx, _ptr(real), _ptr(imag), _ptr(lens), B, T, length, n_fft, win_length, _ptr(wav),
                                         _stream(self.device))
         _lib.check(self.ctx, rc, "lass_istft_ragged")
@@ -465,9 +467,9 @@ class Engine:
         T = arch.frames_for(W, self.hop)
         nb = self.n_fft // 2 + 1
         shape = (B, arch.padded_frames(T), nb - 1)
-        mk = lambda: torch.empty(B, T, nb, dtype=torch.float32, device=self.device)  # noqa: E731
+        mk = lambda: _alloc.empty(B, T, nb, dtype=torch.float32, device=self.device)  # noqa: E731
         mag, cos, sin = mk(), mk(), mk()
-        x0 = torch.empty((self.n_branches,) + shape if self.multistft else shape, dtype=torch.float32, device=self.device)
+        x0 = _alloc.empty((self.n_branches,) + shape if self.multistft else shape, dtype=torch.float32, device=self.device)
         rc = self.lib.lass_front_end_windows(self.ctx, _ptr(recording), total, _ptr(idx_s), B, W, _ptr(mag), _ptr(cos), _ptr(sin),
                                              _ptr(x0), _stream(self.device))
         _lib.check(self.ctx, rc, "lass_front_end_windows")
@@ -511,7 +513,7 @@ class Engine:
         T = 1 + L // hop
         wins = [int(w) for w in win_lengths]
         n = len(wins)
-        outs = {w: tuple(torch.empty(B, 1, T, n_fft // 2 + 1, dtype=torch.float32, device=self.device) for _ in range(3))
+        outs = {w: tuple(_alloc.empty(B, 1, T, n_fft // 2 + 1, dtype=torch.float32, device=self.device) for _ in range(3))
                 for w in wins}
         arr = lambda i: (c_void_p * n)(*[outs[w][i].data_ptr() for w in wins])  # noqa: E731
         rc = self.lib.lass_stft_components(self.ctx, _ptr(wav), B, L, n_fft, hop, n, (c_int * n)(*wins), arr(0), arr(1),
@@ -523,7 +525,7 @@ class Engine:
         real, imag = self._dev(real), self._dev(imag)
         B, T, F = real.shape
         assert F == n_fft // 2 + 1 and imag.shape == real.shape
-        wav = torch.empty(B, length, dtype=torch.float32, device=self.device)
+        wav = _alloc.empty(B, length, dtype=torch.float32, device=self.device)
         rc = self.lib.lass_istft_nfft(self.ctx, _ptr(real), _ptr(imag), B, T, length, n_fft, win_length, _ptr(wav),
                                       _stream(self.device))
         _lib.check(self.ctx, rc, "lass_istft_nfft")
@@ -540,7 +542,7 @@ class Engine:
                 or cos_mask.shape != (B, T, F) or sin_mask.shape != (B, T, F) or T != arch.frames_for(length, self.hop) \
                 or condition.shape != (B, arch_cond()):
             raise _lib.LassError("separate_components: inconsistent shapes")
-        out = torch.empty(B, length, dtype=torch.float32, device=self.device)
+        out = _alloc.empty(B, length, dtype=torch.float32, device=self.device)
         ws = self._workspace(B, length)
         arr = (c_void_p * len(mags))(*[m.data_ptr() for m in mags])
         rc = self.lib.lass_separate_components(self.ctx, arr, _ptr(cos_mask), _ptr(sin_mask), _ptr(condition), _ptr(out),
@@ -569,7 +571,7 @@ class Engine:
     def upconv(self, name: str, x: torch.Tensor, shift: torch.Tensor, cout: int, up) -> torch.Tensor:
         x = self._dev(x)
         B, _cin, h, w = x.shape
-        y = torch.empty(B, cout, h * up[0], w * up[1], dtype=torch.float32, device=self.device)
+        y = _alloc.empty(B, cout, h * up[0], w * up[1], dtype=torch.float32, device=self.device)
         rc = self.lib.lass_upconv(self.ctx, name.encode(), _ptr(x), B, h, w, _ptr(shift), _ptr(y),
                                   _stream(self.device))
         _lib.check(self.ctx, rc, "lass_upconv")
@@ -580,8 +582,8 @@ class Engine:
         B, C, Tp, F = x12.shape
         T = mag.shape[1]
         assert C == 32 and F == self.n_fft // 2
-        o_re = torch.empty_like(mag)
-        o_im = torch.empty_like(mag)
+        o_re = _alloc.empty_like(mag)
+        o_im = _alloc.empty_like(mag)
         rc = self.lib.lass_mask_apply(self.ctx, _ptr(x12), _ptr(mag), _ptr(cos), _ptr(sin), B, T, Tp, _ptr(o_re),
                                       _ptr(o_im), _stream(self.device))
         _lib.check(self.ctx, rc, "lass_mask_apply")
@@ -591,7 +593,7 @@ class Engine:
         """(B,L),(B,L) f32 -> (B,6) f64 sums (see include/lass_hip.h)."""
         ref, est = self._dev(ref), self._dev(est)
         B, L = ref.shape
-        stats = torch.empty(B, 6, dtype=torch.float64, device=self.device)
+        stats = _alloc.empty(B, 6, dtype=torch.float64, device=self.device)
         rc = self.lib.lass_sdr_stats(self.ctx, _ptr(ref), _ptr(est), B, L, _ptr(stats), _stream(self.device))
         _lib.check(self.ctx, rc, "lass_sdr_stats")
         return stats
@@ -603,10 +605,10 @@ class Engine:
         source, noise, snr_db = self._dev(source), self._dev(noise), self._dev(snr_db)
         B, L = source.shape
         assert noise.shape == source.shape and snr_db.shape == (B,)
-        mixture = torch.empty_like(source) if out is None else self._dev(out)
+        mixture = _alloc.empty_like(source) if out is None else self._dev(out)
         assert mixture.shape == source.shape and mixture.is_contiguous() and mixture.dtype == torch.float32
         if scratch is None:
-            scratch = torch.empty(B, 4, dtype=torch.float64, device=self.device)
+            scratch = _alloc.empty(B, 4, dtype=torch.float64, device=self.device)
         assert scratch.dtype == torch.float64 and scratch.numel() >= 4 * B and scratch.is_contiguous()
         rc = self.lib.lass_mix_at_snr(self.ctx, _ptr(source), _ptr(noise), _ptr(snr_db), _ptr(mixture), B, L,
                                       _ptr(scratch), _stream(self.device))
@@ -648,7 +650,7 @@ class Engine:
         taps = rs.device_taps(up, down, self.device) if fir else None
         shape = (B, int(channels), L_out) if planar else (B, L_out)
         if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+            out = _alloc.empty(shape, dtype=torch.float32, device=self.device)
         elif (tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != self.device
               or not out.is_contiguous()):
             raise _lib.LassError(f"out must be a contiguous float32 {shape} tensor on {self.device}")
@@ -696,7 +698,7 @@ class Engine:
         taps = rs.device_taps(up, down, self.device) if fir else None
         row_bytes = frames_out * C * rs.SAMPLE_BYTES[encoding]
         if out is None:
-            out = torch.empty(B, (row_bytes + 3) // 4 * 4, dtype=torch.uint8, device=self.device)
+            out = _alloc.empty(B, (row_bytes + 3) // 4 * 4, dtype=torch.uint8, device=self.device)
         elif (out.dim() != 2 or out.shape[0] != B or out.shape[1] < row_bytes or out.dtype != torch.uint8 or out.device != self.device
               or out.stride(1) != 1):
             raise _lib.LassError(f"out must be a ({B}, >= {row_bytes}) uint8 tensor on {self.device} with contiguous rows")
@@ -745,7 +747,7 @@ class Engine:
             raise _lib.LassError(f"resampling {rate_in} -> {rate_out} Hz needs {rs.n_taps(up, down)} taps, over the device "
                                  f"kernel's cap of {rs.MAX_TAPS}")
         taps = rs.device_taps(up, down, self.device) if fir else None
-        peak = torch.empty(B, dtype=torch.float32, device=self.device)
+        peak = _alloc.empty(B, dtype=torch.float32, device=self.device)
         rc = self.lib.lass_resample_peak(self.ctx, _ptr(planes), row_stride, plane_stride, B, C, L, up, down, _ptr(taps),
                                          taps.numel() if fir else 1, frames_out, _ptr(peak), _stream(self.device))
         _lib.check(self.ctx, rc, "lass_resample_peak")
@@ -775,7 +777,7 @@ class Engine:
                                  f"kernel's cap of {rs.MAX_TAPS}")
         taps = rs.device_taps(up, down, self.device) if fir else None
         os_taps = rs.device_taps(os_, 1, self.device)
-        peak = torch.empty(B, dtype=torch.float32, device=self.device)
+        peak = _alloc.empty(B, dtype=torch.float32, device=self.device)
         rc = self.lib.lass_resample_true_peak(self.ctx, _ptr(planes), row_stride, plane_stride, B, C, L, up, down, _ptr(taps),
                                               taps.numel() if fir else 1, frames_out, os_, _ptr(os_taps), os_taps.numel(), _ptr(peak),
                                               _stream(self.device))
@@ -797,10 +799,10 @@ class Engine:
         coef = ld.coefficients(rate)
         hop = int(rate) // 10
         lengths, weights = self._meter_args(lengths, weights, B, C)
-        out = torch.empty(B, 10, dtype=torch.float64, device=self.device)
+        out = _alloc.empty(B, 10, dtype=torch.float64, device=self.device)
         ns = ld.n_short_term(L, rate)
-        short = torch.empty(B, ns, dtype=torch.float64, device=self.device) if return_short_term else None
-        scratch = torch.empty(max((5 * C + 1) * B * (L // hop), 1), dtype=torch.float64, device=self.device)
+        short = _alloc.empty(B, ns, dtype=torch.float64, device=self.device) if return_short_term else None
+        scratch = _alloc.empty(max((5 * C + 1) * B * (L // hop), 1), dtype=torch.float64, device=self.device)
         rc = self.lib.lass_loudness_stats(self.ctx, _ptr(planes), row_stride, plane_stride, B, C, L, _ptr(lengths), hop,
                                           (c_double * 10)(*coef.tolist()), _ptr(weights), _ptr(out), None, 0, _ptr(short), ns,
                                           _ptr(scratch), scratch.numel() * 8, _stream(self.device))
@@ -836,9 +838,9 @@ class Engine:
         hop = int(rate) // 10
         lengths, weights = self._meter_args(lengths, weights, B, C)
         nb = max(ld.n_blocks(L, rate), 0)
-        out = torch.empty(B, 3, dtype=torch.float64, device=self.device)
-        blocks = torch.empty(B, nb, dtype=torch.float64, device=self.device) if return_blocks else None
-        scratch = torch.empty(max(5 * B * C * (L // hop), 1), dtype=torch.float64, device=self.device)
+        out = _alloc.empty(B, 3, dtype=torch.float64, device=self.device)
+        blocks = _alloc.empty(B, nb, dtype=torch.float64, device=self.device) if return_blocks else None
+        scratch = _alloc.empty(max(5 * B * C * (L // hop), 1), dtype=torch.float64, device=self.device)
         rc = self.lib.lass_loudness(self.ctx, _ptr(planes), row_stride, plane_stride, B, C, L, _ptr(lengths), hop,
                                     (c_double * 10)(*coef.tolist()), _ptr(weights), _ptr(out), _ptr(blocks), nb, _ptr(scratch),
                                     scratch.numel() * 8, _stream(self.device))
@@ -856,8 +858,8 @@ class Engine:
             peak = peak.to(device=self.device, dtype=torch.float32).contiguous()
             if tuple(peak.shape) != (B,):
                 raise _lib.LassError(f"peak must have shape ({B},)")
-        gain = torch.empty(B, dtype=torch.float32, device=self.device)
-        limited = torch.empty(B, dtype=torch.int32, device=self.device)
+        gain = _alloc.empty(B, dtype=torch.float32, device=self.device)
+        limited = _alloc.empty(B, dtype=torch.int32, device=self.device)
         rc = self.lib.lass_loudness_gain(self.ctx, _ptr(loudness), _ptr(peak), B, float("nan") if target is None else float(target),
                                          0.0 if ceiling is None else float(ceiling), _ptr(gain), _ptr(limited), _stream(self.device))
         _lib.check(self.ctx, rc, "lass_loudness_gain")
@@ -873,8 +875,8 @@ class Engine:
         noise_db = noise_db.to(device=self.device, dtype=torch.float32).contiguous()
         if mix_num.shape != (B,) or noise_db.shape != (B,) or comp_db.dim() != 2 or comp_db.shape[0] != B:
             raise ValueError("segment_mix: mix_num (B), comp_db (B, max_mix_num - 1), noise_db (B) expected")
-        mixture, segment = torch.empty_like(waveforms), torch.empty_like(waveforms)
-        scratch = torch.empty(B, 4, dtype=torch.float64, device=self.device)
+        mixture, segment = _alloc.empty_like(waveforms), _alloc.empty_like(waveforms)
+        scratch = _alloc.empty(B, 4, dtype=torch.float64, device=self.device)
         rc = self.lib.lass_segment_mix(self.ctx, _ptr(waveforms), B, L, _ptr(mix_num), _ptr(comp_db), int(comp_db.shape[1]),
                                        _ptr(noise_db), _ptr(mixture), _ptr(segment), _ptr(scratch), _stream(self.device))
         _lib.check(self.ctx, rc, "lass_segment_mix")

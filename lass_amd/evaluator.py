@@ -42,6 +42,7 @@ from typing import Dict, List
 import numpy as np
 import torch
 
+from . import _alloc
 from . import dist as ldist
 from . import resample as rs
 from .engine import get_engine
@@ -109,7 +110,7 @@ class _Slot:
         """raw_bytes > 0 (device_decode on a set that is not mono at the rate): the pinned rows hold the files' data chunks,
         `raw_bytes` bytes each, next to device copies of them; the float32 rows exist on the device only."""
         pin = lambda *shape, dtype=torch.float32: torch.empty(shape, dtype=dtype).pin_memory()  # noqa: E731
-        dev = lambda *shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=device)  # noqa: E731
+        dev = lambda *shape, dtype=torch.float32: _alloc.empty(shape, dtype=dtype, device=device)  # noqa: E731
         self.pin_snr = pin(B)
         self.np_snr = self.pin_snr.numpy()
         if raw_bytes:

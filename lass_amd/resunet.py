@@ -14,7 +14,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import arch, longform, ragged
+from . import _alloc, arch, longform, ragged
 from ._lib import LassError
 from .engine import Engine
 
@@ -250,7 +250,7 @@ class ResUNet30(nn.Module):
             groups = longform.group_windows_faded(plan, max_batch)
         else:
             if out is None:
-                out = torch.empty_like(rec)  # the kept ranges tile it exactly once
+                out = _alloc.empty_like(rec)  # the kept ranges tile it exactly once
             groups = longform.group_windows(plan, max_batch)
         self._run_windows(eng, rec, out, window, groups, cond, None, ramp)
         return out
@@ -334,7 +334,7 @@ class ResUNet30(nn.Module):
             out, ramp = torch.zeros_like(rec), longform.fade_ramp(fade, fade_shape)
             groups = longform.group_windows_faded(rows, max_batch)
         else:
-            out, ramp = torch.empty_like(rec), None  # the kept ranges tile it exactly once
+            out, ramp = _alloc.empty_like(rec), None  # the kept ranges tile it exactly once
             groups = longform.group_windows(rows, max_batch)
         B = len(groups[0])
         cond_rows += [cond_rows[-1]] * (len(groups) * B - len(cond_rows))  # (the padding rows store nothing)
