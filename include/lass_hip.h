@@ -592,7 +592,8 @@ int lass_text_set_param(lass_text_ctx* ctx, const char* name, const void* data, 
 int lass_text_finalize(lass_text_ctx* ctx);
 /* Encoder layers of a finalized context (0 before lass_text_finalize). */
 int lass_text_layers(const lass_text_ctx* ctx);
-/* Workspace bytes lass_text_encode needs for N captions padded to S tokens (1 <= S <= 512). */
+/* Workspace bytes lass_text_encode needs for N captions padded to S tokens (1 <= S <= 512); anything else is LASS_ERR_ARG
+ * with its message in lass_text_last_error. */
 int lass_text_workspace_bytes(const lass_text_ctx* ctx, int N, int S, size_t* bytes);
 /* input_ids (N,S) int64 DEVICE pointer, attention_mask (N,S) int64 HOST pointer (it decides which rows are computed and
  * sizes every launch, so no device-to-host read is needed) -> out (N,512) f32, and pooler_output (N,768) f32 into

@@ -7,9 +7,9 @@
 // softmax, so no real row ever depends on a padded one.  No work is spent on padding.
 //
 // Batch invariance: every kernel computes a row (a token, or a caption in the head) from that row's inputs alone in a
-// fixed order - the GEMM tile is one shape for all M and each output element is a k-ordered chain of f32 MFMA FMAs,
-// reductions are per row, attention is per (caption, head, query) - so a caption's embedding is bit-identical whatever
-// batch, padding length or packed position it comes with.
+// fixed order - the GEMM tile is one shape for all M and each output element is the in-order sum of k-ordered chains of
+// f32 MFMA FMAs, one per 64 of k, reductions are per row, attention is per (caption, head, query) - so a caption's
+// embedding is bit-identical whatever batch, padding length or packed position it comes with.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -202,7 +202,7 @@ thread_local std::string g_text_create_err;
 
 struct lass_text_ctx {
     int device = 0;
-    std::string err;
+    mutable std::string err;  // mutable: lass_text_workspace_bytes takes a const context and still reports why it refused
     ParamStore raw;
     bool finalized = false;
     int vocab = 0, npos = 0;
@@ -364,7 +364,9 @@ int lass_text_finalize(lass_text_ctx* c) {
 int lass_text_layers(const lass_text_ctx* c) { return c && c->finalized ? (int)c->layers.size() : 0; }
 
 int lass_text_workspace_bytes(const lass_text_ctx* c, int N, int S, size_t* bytes) {
-    if (!c || !bytes || N < 1 || S < 1 || S > kMaxLen) return LASS_ERR_ARG;
+    if (!c) return LASS_ERR_ARG;
+    if (!bytes || N < 1 || S < 1 || S > kMaxLen)
+        return fail(c, LASS_ERR_ARG, "lass_text_workspace_bytes: bad arguments (N >= 1, 1 <= S <= 512, non-NULL bytes)");
     *bytes = text_plan(N, S).total;
     return LASS_OK;
 }
