@@ -554,6 +554,40 @@ int lass_loudness_stats(lass_ctx* ctx, const float* planes, int64_t row_stride, 
                         const int* lengths, int hop, const double* coef, const float* weights, double* out, double* blocks,
                         int nb_max, double* short_term, int ns_max, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- look-ahead limiter of the levelled export (opt-in; separate_files(limiter=True)) ---- */
+
+/* One gain curve per recording, linked across the channels, that holds gain x envelope under the ceiling, so that a ceiling that binds
+ * no longer costs the whole recording its loudness.  planes: lass_resample_peak's (B recordings of `channels` planes of L floats at
+ * the model rate, strides in floats); gain (device, B floats, finite, >= 0); ceiling (linear, > 0, finite); H: the reach in frames,
+ * 1 ... LASS_LIMITER_MAX_H (lass_amd.loudness.reach); window (device, 2H + 1 floats: lass_amd.loudness.limiter_window); os: 1, 2 or 4
+ * with os_taps (device, n_os_taps = 20*os + 1 floats, lass_resample_true_peak's) or NULL and 0 at os == 1.  For recording b, in
+ * float32 with every operation rounded once:
+ *   e[n] = max_c max( |x_c[n]| , max_{p=1..os-1} |z_c[n*os + p]| ),  z_c as lass_resample_true_peak forms it from a plane (one fmaf
+ *          chain over the 21 taps of the phase: bit-identical to lass_decode_resample of the plane at (os, 1)); a NaN counts as 0;
+ *   r[n] = 1 if a = fl(g * e[n]) <= ceiling, else fl(ceiling / a);
+ *   m[n] = min r[k] over |k - n| <= H, 0 <= k < L;
+ *   G[n] = sum_{j=-H..H} window[j+H] * m'[n+j] (m' = m inside the row, 1 outside), one fmaf chain in that order onto 0; G[n] = 1
+ *          exactly where every m' in reach is 1; then G[n] = min(G[n], r[n]);
+ *   out_c[n] = fl( fl(g * G[n]) * x_c[n] ).
+ * out: addressed as planes with its own strides; it must not overlap planes (a tile's halo reads what a neighbour would write).
+ * Optional outputs: curve and envelope ((B, L) floats, rows curve_row_stride >= L floats apart) receive G and e; min_gain (B floats,
+ * written here) the smallest G of the row, lowered by integer atomic min on the bits; frames (B int32, written here) the number of
+ * n with m[n] < 1, by integer atomic add.  lass_amd.loudness.limit is the float64 definition.
+ * One launch, one workgroup per tile of LASS_LIMITER_TILE frames and recording, no scratch, no floating-point atomics: a tile keeps
+ * the plane over tile +- (2H + 10), e over tile +- 2H and m over tile +- H in LDS and makes its neighbours' share again; the
+ * minimum is a doubling scheme (O(log H) per frame), and the smoothing chain runs only in waves with some m' < 1 in reach.  A row's
+ * outputs are bit-identical whatever B, the row, the strides or the call.  Nothing is read back.
+ * Limits, checked before anything is launched (LASS_ERR_ARG): 1 <= B <= 65535, 1 <= channels <= 8, L >= 1, 1 <= H <=
+ * LASS_LIMITER_MAX_H, os in {1, 2, 4} with its taps, ceiling > 0 and finite, plane_stride >= L and row_stride >=
+ * (channels-1)*plane_stride + L for planes and for out, curve_row_stride >= L with curve or envelope, out disjoint from planes,
+ * every pointer 4-byte aligned.  Stateless.  Not ported: the reference has no limiter (scripts/process_audio.sh peak-normalises). */
+#define LASS_LIMITER_MAX_H 512
+#define LASS_LIMITER_TILE 1024
+int lass_limit(lass_ctx* ctx, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels, int L, int os,
+               const float* os_taps, int n_os_taps, const float* gain, float ceiling, int H, const float* window, float* out,
+               int64_t out_row_stride, int64_t out_plane_stride, float* curve, float* envelope, int64_t curve_row_stride,
+               float* min_gain, int* frames, void* stream);
+
 /* Training-side data path ("next" row f4, mixer half; also the producer stage of the STFT pre-compute,
  * scripts/precompute_stfts.py:352-681): SegmentMixer.__call__ + dynamic_loudnorm (data/waveform_mixers.py:19-92) on the
  * device.  waveforms (B,L) -> mixture (B,L), segment (B,L).  For clip n:

@@ -1562,6 +1562,50 @@ int lass_loudness_gain(lass_ctx* c, const double* loudness, const float* peak, i
     return 0;
 }
 
+int lass_limit(lass_ctx* c, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels, int L, int os,
+               const float* os_taps, int n_os_taps, const float* gain, float ceiling, int H, const float* window, float* out,
+               int64_t out_row_stride, int64_t out_plane_stride, float* curve, float* envelope, int64_t curve_row_stride,
+               float* min_gain, int* frames, void* stream) {
+    const char* w = "lass_limit: ";
+    if (!c) return LASS_ERR_ARG;
+    if (!planes || !gain || !window || !out || B <= 0 || B > 65535)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "planes, gain, window, out non-NULL, 1 <= B <= 65535");
+    if (channels < 1 || channels > 8) return fail(c, LASS_ERR_ARG, std::string(w) + "1 ... 8 channels");
+    if (L < 1) return fail(c, LASS_ERR_ARG, std::string(w) + "L >= 1");
+    if (H < 1 || H > LASS_LIMITER_MAX_H)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "H must lie in 1 ... " + std::to_string(LASS_LIMITER_MAX_H));
+    if (os != 1 && os != 2 && os != 4) return fail(c, LASS_ERR_ARG, std::string(w) + "os must be 1, 2 or 4");
+    if (os == 1 ? (os_taps ? n_os_taps != 21 : n_os_taps != 0) : (!os_taps || n_os_taps != 20 * os + 1))
+        return fail(c, LASS_ERR_ARG, std::string(w) + "os_taps non-NULL with n_os_taps = 20 * os + 1 = " + std::to_string(20 * os + 1) +
+                    " (or NULL and 0 at os == 1)");
+    if (!(ceiling > 0.0f) || std::isinf(ceiling)) return fail(c, LASS_ERR_ARG, std::string(w) + "ceiling must be finite and > 0");
+    const long long row_floats = (long long)(channels - 1) * plane_stride + L;
+    if (plane_stride < L || row_stride < row_floats)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "plane_stride must hold a plane (" + std::to_string(L) +
+                    " floats) and row_stride a recording (" + std::to_string(row_floats) + " floats)");
+    const long long out_row_floats = (long long)(channels - 1) * out_plane_stride + L;
+    if (out_plane_stride < L || out_row_stride < out_row_floats)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "out_plane_stride must hold a plane (" + std::to_string(L) +
+                    " floats) and out_row_stride a recording (" + std::to_string(out_row_floats) + " floats)");
+    if ((curve || envelope) && curve_row_stride < L)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "curve_row_stride must hold a row (" + std::to_string(L) + " floats)");
+    const uintptr_t p0 = reinterpret_cast<uintptr_t>(planes), o0 = reinterpret_cast<uintptr_t>(out);
+    const uintptr_t p1 = p0 + ((uintptr_t)(B - 1) * (uintptr_t)row_stride + (uintptr_t)row_floats) * sizeof(float);
+    const uintptr_t o1 = o0 + ((uintptr_t)(B - 1) * (uintptr_t)out_row_stride + (uintptr_t)out_row_floats) * sizeof(float);
+    if (p0 < o1 && o0 < p1)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "out must not overlap planes (a tile's halo reads what a neighbour would write)");
+    for (const void* q : {(const void*)planes, (const void*)os_taps, (const void*)gain, (const void*)window, (const void*)out,
+                          (const void*)curve, (const void*)envelope, (const void*)min_gain, (const void*)frames})
+        if (reinterpret_cast<uintptr_t>(q) % 4 != 0)
+            return fail(c, LASS_ERR_ARG, std::string(w) + "planes, os_taps, gain, window, out, curve, envelope, min_gain and frames "
+                        "must be 4-byte aligned");
+    if (int r = use_device(c)) return r;
+    HIP_TRY(c, lass_launch_limit(planes, row_stride, plane_stride, B, channels, L, os, os > 1 ? os_taps : nullptr,
+                                 os > 1 ? n_os_taps : 0, gain, ceiling, H, window, out, out_row_stride, out_plane_stride, curve, envelope,
+                                 curve_row_stride, min_gain, frames, (hipStream_t)stream));
+    return 0;
+}
+
 int lass_segment_mix(lass_ctx* c, const float* waveforms, int B, int L, const int* mix_num, const float* comp_db, int max_comp,
                      const float* noise_db, float* mixture, float* segment, double* scratch, void* stream) {
     if (!c || !waveforms || !mix_num || !comp_db || !noise_db || !mixture || !segment || !scratch || B <= 0 || L <= 0)

@@ -314,6 +314,15 @@ hipError_t lass_launch_resample_true_peak(const float* planes, long long row_str
 // whether a tile of one frame - table, the span of its 21 first-stage outputs, stage, second table - fits the CU's 160 KiB
 bool lass_resample_true_peak_fits(int up, int down, int n_taps, int os);
 
+// ---- limiter.hip --------------------------------------------------------------------------------------------------
+// lass_limit's kernel (include/lass_hip.h has the arithmetic): out = fl(fl(g * G) * x) with G the smoothed minimum of the gain
+// that holds g x envelope under `ceiling`; one launch, LASS_LIMITER_TILE frames per workgroup.  min_gain (1) and frames (0) are
+// filled here, on the stream.  The caller has checked the arguments (lass_limit).
+hipError_t lass_launch_limit(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L, int os,
+                             const float* os_taps, int n_os_taps, const float* gain, float ceiling, int H, const float* window,
+                             float* out, long long out_row_stride, long long out_plane_stride, float* curve, float* envelope,
+                             long long curve_row_stride, float* min_gain, int* frames, hipStream_t stream);
+
 // ---- loudness.hip -------------------------------------------------------------------------------------------------
 // K-weighting as the kernels take it: the two biquads (b0 b1 b2 a1 a2 of the shelf, then of the high-pass) and the powers of the
 // cascade's 4 x 4 state matrix that carry a state over one lane's samples and over one hop bin, row-major.

@@ -865,6 +865,47 @@ class Engine:
         _lib.check(self.ctx, rc, "lass_loudness_gain")
         return gain, limited
 
+    def limit(self, planes: torch.Tensor, rate: int, gain: torch.Tensor, ceiling: float, lookahead: int, peak: str = "true",
+              return_curve: bool = False):
+        """The look-ahead limiter on the device (lass_limit; lass_amd.loudness.limit is its float64 definition): planes (B, C, L) or
+        (C, L) float32 at `rate` (any strides with contiguous samples; C 1 ... 8), gain (B,) float32 on the device, ceiling linear
+        (> 0), lookahead the reach H in frames (`loudness.reach`; 1 ... 512) -> (limited, info): limited (B, C, L) float32 with
+        limited[b, c, n] = (gain[b] * G_b[n]) * planes[b, c, n], G_b the one gain curve of recording b, which holds gain x envelope
+        under the ceiling and is 1 wherever no frame within 2H needs a reduction.  peak "true": the envelope holds the signal
+        between the samples too, loudness.oversampling(rate) times oversampled; "sample": |x| alone.  info: "min_gain" (B,) float32,
+        the smallest G of each recording, and "frames" (B,) int32, the frames whose look-ahead minimum is below 1; with
+        return_curve also "curve" and "envelope", (B, L) float32.  Everything stays on the device; nothing is read back."""
+        from . import loudness as ld
+        from . import resample as rs
+        if peak not in ("sample", "true"):
+            raise _lib.LassError('peak must be "sample" or "true"')
+        planes, row_stride, plane_stride = self._planes(planes)
+        B, C, L = planes.shape
+        H = int(lookahead)
+        if not 1 <= H <= ld.LIMITER_MAX_REACH:
+            raise _lib.LassError(f"lookahead must lie in 1 ... {ld.LIMITER_MAX_REACH} frames")
+        if tuple(gain.shape) != (B,) or gain.dtype != torch.float32 or gain.device != self.device or not gain.is_contiguous():
+            raise _lib.LassError(f"gain must be a contiguous float32 ({B},) tensor on {self.device}")
+        os_ = ld.oversampling(rate) if peak == "true" else 1
+        os_taps = rs.device_taps(os_, 1, self.device) if os_ > 1 else None
+        key = (H, str(self.device))
+        window = _LIMITER_WINDOWS.get(key)
+        if window is None:
+            window = _LIMITER_WINDOWS[key] = torch.from_numpy(ld.limiter_window(H)).to(self.device)
+        out = _alloc.empty(B, C, L, dtype=torch.float32, device=self.device)
+        min_gain = _alloc.empty(B, dtype=torch.float32, device=self.device)
+        frames = _alloc.empty(B, dtype=torch.int32, device=self.device)
+        curve = _alloc.empty(B, L, dtype=torch.float32, device=self.device) if return_curve else None
+        envelope = _alloc.empty(B, L, dtype=torch.float32, device=self.device) if return_curve else None
+        rc = self.lib.lass_limit(self.ctx, _ptr(planes), row_stride, plane_stride, B, C, L, os_, _ptr(os_taps),
+                                 os_taps.numel() if os_ > 1 else 0, _ptr(gain), float(ceiling), H, _ptr(window), _ptr(out), C * L, L,
+                                 _ptr(curve), _ptr(envelope), L, _ptr(min_gain), _ptr(frames), _stream(self.device))
+        _lib.check(self.ctx, rc, "lass_limit")
+        info = {"min_gain": min_gain, "frames": frames}
+        if return_curve:
+            info["curve"], info["envelope"] = curve, envelope
+        return out, info
+
     def segment_mix(self, waveforms: torch.Tensor, mix_num: torch.Tensor, comp_db: torch.Tensor, noise_db: torch.Tensor):
         """data/waveform_mixers.py:19-62 on the device with the random draws given: waveforms (B,L), mix_num (B) int32,
         comp_db (B, max_mix_num - 1) f32, noise_db (B) f32 -> (mixture (B,L), segment (B,L))."""
@@ -914,6 +955,7 @@ def arch_cond() -> int:
 
 
 _ENGINES: Dict[int, Engine] = {}
+_LIMITER_WINDOWS: Dict[tuple, torch.Tensor] = {}   # (H, device) -> loudness.limiter_window(H) on the device, uploaded once
 
 
 def get_engine(device) -> Engine:

@@ -23,6 +23,10 @@ The second half of the module is what an EBU R 128 delivery is checked against b
 from the recommendations (BS.1770-4 Annex 2, EBU Tech 3341 and 3342) and pinned by their test signals (tests/test_r128_cpu.py):
 `true_peak` with its `oversampling`, `short_term_powers`, `loudness_range`, `max_momentary` and `max_short_term` - the float64
 definitions of `lass_resample_true_peak` (csrc/export.hip) and `lass_loudness_stats` (csrc/loudness.hip); DESIGN.md section 19.
+
+The last part is the look-ahead limiter of the levelled export (`limit` and its pieces: `limiter_envelope`, `limiter_window`,
+`reach`), the float64 definition of `lass_limit` (csrc/limiter.hip): one gain curve per recording, linked across the channels,
+that holds gain x envelope under the ceiling so that the ceiling stops costing loudness; DESIGN.md section 20.
 """
 from __future__ import annotations
 
@@ -317,3 +321,98 @@ def check_level_args(loudness, peak_ceiling_db) -> None:
             raise ValueError(f"{name} must be a finite number or None")
     if peak_ceiling_db is not None and peak_ceiling_db > 0:
         raise ValueError("peak_ceiling_db must be <= 0 dBFS")
+
+
+# ---- the look-ahead limiter ------------------------------------------------------------------------
+LIMITER_MAX_REACH = 512   # include/lass_hip.h: LASS_LIMITER_MAX_H
+
+
+def reach(lookahead_ms: float, rate: int) -> int:
+    """The limiter's reach H in frames for a look-ahead in milliseconds: max(1, round(lookahead_ms * rate / 1000))."""
+    if isinstance(lookahead_ms, bool) or not isinstance(lookahead_ms, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(lookahead_ms) or lookahead_ms < 0:
+        raise ValueError("lookahead_ms must be a finite number >= 0")
+    return max(1, int(round(float(lookahead_ms) * int(rate) / 1000.0)))
+
+
+def limiter_window(H: int) -> np.ndarray:
+    """The 2H + 1 float32 smoothing taps: np.hanning(2H + 3) without its two zero ends, normalised in float64, then cast."""
+    H = int(H)
+    if H < 1:
+        raise ValueError("H must be at least 1")
+    w = np.hanning(2 * H + 3)[1:-1].astype(np.float64)
+    return (w / w.sum()).astype(np.float32)
+
+
+def limiter_envelope(x, rate: int, true: bool = True, dtype=np.float64) -> np.ndarray:
+    """(L,) e[n] = max over the channels of x (C, L) or (L,) of max(|x_c[n]|, |z_c[n*os + p]| for p = 1 ... os-1), with
+    z_c = `resample.resample_host(x_c, os, 1, dtype)` as `true_peak` forms it and os = oversampling(rate) with `true`, else 1.
+    A NaN counts as 0; max_n e[n] is `true_peak(x, rate)`."""
+    from . import resample as rs
+    dtype = np.dtype(dtype)
+    x = np.atleast_2d(np.asarray(x, dtype=dtype))
+    os_ = oversampling(rate) if true else 1
+    e = np.zeros(x.shape[1], dtype=dtype)
+    for c in range(x.shape[0]):
+        a = np.abs(x[c])
+        if os_ > 1 and x.shape[1]:
+            with np.errstate(invalid="ignore"):
+                z = np.abs(rs.resample_host(x[c], os_, 1, dtype)).reshape(-1, os_)[:, 1:]
+            z = np.where(np.isnan(z), dtype.type(0), z)
+            a = np.maximum(np.where(np.isnan(a), dtype.type(0), a), z.max(axis=1))
+        e = np.maximum(e, np.where(np.isnan(a), dtype.type(0), a))
+    return e
+
+
+def limiter_required(e, gain, ceiling, dtype=np.float64) -> np.ndarray:
+    """r[n]: 1 where gain * e[n] <= ceiling, else ceiling / (gain * e[n]); every operation rounded once in `dtype`."""
+    dt = np.dtype(dtype).type
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        a = dt(gain) * np.asarray(e, dtype=dtype)
+        return np.where(a <= dt(ceiling), dt(1), dt(ceiling) / np.where(a <= dt(ceiling), dt(1), a))
+
+
+def _running_min(r: np.ndarray, H: int, fill) -> np.ndarray:
+    """min r[k] over |k - n| <= H, r continued with `fill`: minima of 2^i neighbours doubled up to the largest power of two in
+    2H + 1, then two of them overlapped (min is exact: the scheme cannot change a bit)."""
+    L, W = r.shape[0], 2 * H + 1
+    A = np.concatenate([np.full(H, fill, dtype=r.dtype), r, np.full(H, fill, dtype=r.dtype)])
+    p = 1
+    while 2 * p <= W:
+        A = np.minimum(A[:A.shape[0] - p], A[p:])
+        p *= 2
+    return np.minimum(A[:L], A[W - p:W - p + L])
+
+
+def limiter_curve(e, gain, ceiling, H: int, window=None, dtype=np.float64):
+    """(G, r, m) of an envelope e (L,): the required gain r (`limiter_required`), its minimum m over |k - n| <= H inside the row,
+    and G[n] = sum_{j=-H..H} w[j+H] * m'[n+j] (m' = m inside the row, 1 outside; added in that order) with the two rules that
+    make it exact where it matters: G[n] = 1 where every m' in reach is 1, and G[n] := min(G[n], r[n])."""
+    dtype = np.dtype(dtype)
+    H = int(H)
+    if H < 1:
+        raise ValueError("H must be at least 1")
+    r = limiter_required(e, gain, ceiling, dtype)
+    L = r.shape[0]
+    one = dtype.type(1)
+    m = _running_min(r, H, one)
+    w = (limiter_window(H) if window is None else np.asarray(window)).astype(dtype)
+    mp = np.concatenate([np.ones(H, dtype=dtype), m, np.ones(H, dtype=dtype)])
+    G = np.zeros(L, dtype=dtype)
+    for j in range(2 * H + 1):
+        G += w[j] * mp[j:j + L]
+    G = np.where(_running_min(m, H, one) == one, one, G)
+    return np.minimum(G, r), r, m
+
+
+def limit(x, rate: int, gain, ceiling, H: int, true: bool = True, dtype=np.float64):
+    """The look-ahead limiter: (v, G, e) for planes x (C, L) or (L,) - e = `limiter_envelope(x, rate, true)`, G the gain curve of
+    `limiter_curve(e, gain, ceiling, H)`, one per recording, and v_c[n] = (gain * G[n]) * x_c[n].  gain * G[n] * e[n] <= ceiling
+    up to the rounding of the two products, and a stretch whose envelope needs no reduction within 2H frames is gain * x."""
+    dtype = np.dtype(dtype)
+    xs = np.asarray(x, dtype=dtype)
+    e = limiter_envelope(xs, rate, true, dtype)
+    G = limiter_curve(e, gain, ceiling, H, None, dtype)[0]
+    with np.errstate(invalid="ignore", over="ignore"):
+        v = (dtype.type(gain) * G) * xs
+    return v, G, e

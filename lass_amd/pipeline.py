@@ -29,6 +29,14 @@ the samples the encoder is about to quantise - where `Engine.resample_peak` stoo
 where `Engine.loudness` stood: loudness range, maximum momentary and maximum short-term loudness travel to the host with the
 rest.  At their defaults neither launches anything and no record gains a key.
 
+One gain per file misses its loudness target by the whole overshoot whenever the ceiling binds, which a separated sound event - a
+high crest factor - makes the usual case.  `limiter=True` puts `Engine.limit` in front of the level stage: the separated planes
+are measured, brought to the target by a gain without a ceiling and limited to the ceiling by a look-ahead gain curve, one per
+file, at the model rate, `limiter_passes` times with the gain corrected by the loudness the limited planes measure between the
+passes - a fixed count, all on the device.  The limited planes then go through the level stage above unchanged, which still
+guarantees the ceiling on what is written; its gain is now a static trim - thousandths of a dB where the limiter takes a few dB
+off rare peaks, tenths where it takes 25 dB off most of the file.  DESIGN.md section 20.
+
 A file the device kernels do not take - a header `wavio.wav_info` does not fully understand, more than 8 channels, a rate pair
 beyond `resample.within_cap` in either direction - is decoded, resampled and written on the host (`wavio._resample`,
 `wavio.write_wav_*`); its separation still runs on the device, in the same pass, and its record says `path == "host"`.
@@ -234,6 +242,41 @@ def _meter_record(loudness_range: float, max_momentary: float, max_short_term: f
     return {"loudness_range": float(loudness_range), "max_momentary": float(max_momentary), "max_short_term": float(max_short_term)}
 
 
+def _limiter_record(loudness_in: float, gain, min_gain, frames: int) -> dict:
+    with np.errstate(divide="ignore"):
+        return {"loudness_in": float(loudness_in), "limiter_gain_db": float(20.0 * np.log10(np.float64(gain))),
+                "limiter_reduction_db": float(20.0 * np.log10(np.float64(min_gain))), "limiter_frames": int(frames)}
+
+
+def check_limiter_args(limiter, limiter_lookahead_ms, limiter_passes, peak_ceiling_db, sampling_rate: int) -> None:
+    """ValueError for a limiter without a ceiling to hold, a look-ahead that is no finite number >= 0 or reaches further than
+    the kernel's `loudness.LIMITER_MAX_REACH` frames at the model rate, or a pass count that is no integer >= 1."""
+    if not limiter:
+        return
+    if peak_ceiling_db is None:
+        raise ValueError("limiter=True needs a peak_ceiling_db")
+    if isinstance(limiter_passes, bool) or not isinstance(limiter_passes, (int, np.integer)) or limiter_passes < 1:
+        raise ValueError("limiter_passes must be an integer >= 1")
+    H = ld.reach(limiter_lookahead_ms, sampling_rate)
+    if H > ld.LIMITER_MAX_REACH:
+        raise ValueError(f"limiter_lookahead_ms reaches {H} frames at {sampling_rate} Hz, over the limiter's {ld.LIMITER_MAX_REACH}")
+
+
+def _host_limit(x: np.ndarray, rate: int, target: Optional[float], ceiling, H: int, true: bool, passes: int):
+    """The device route's limiter loop with lass_amd.loudness and numpy: (limited float32 planes, loudness of x, the gain of the
+    last pass, the smallest value of its curve, the frames whose look-ahead minimum is below 1)."""
+    l_in = ld.integrated_loudness(x, rate)
+    g = ld.gain_for(l_in, None, target, None)[0]
+    passes = passes if target is not None else 1
+    for k in range(passes):
+        e = ld.limiter_envelope(x, rate, true)
+        G, _, m = ld.limiter_curve(e, g, ceiling, H)
+        v = ((np.float64(g) * G) * x.astype(np.float64)).astype(np.float32)
+        if k + 1 < passes:
+            g = np.float32(g * ld.gain_for(ld.integrated_loudness(v, rate), None, target, None)[0])
+    return v, l_in, g, (float(G.min()) if G.size else 1.0), int(np.count_nonzero(m < 1.0))
+
+
 def check_peak_arg(peak, peak_ceiling_db) -> None:
     """ValueError for a `peak` that is neither "sample" nor "true", or "true" without a ceiling to hold it to."""
     if peak not in ("sample", "true"):
@@ -246,7 +289,8 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
                    out_rate: Optional[int] = None, window: int = 160000, context: int = 16000, fade: int = 0,
                    fade_shape: str = "linear", max_batch: int = 16, max_samples: int = DEFAULT_MAX_SAMPLES,
                    profile: Optional[Dict[str, float]] = None, loudness: Optional[float] = None,
-                   peak_ceiling_db: Optional[float] = None, peak: str = "sample", meter: bool = False) -> List[dict]:
+                   peak_ceiling_db: Optional[float] = None, peak: str = "sample", meter: bool = False, limiter: bool = False,
+                   limiter_lookahead_ms: float = 1.5, limiter_passes: int = 2) -> List[dict]:
     """Separate WAV files by caption, file in and file out.  model: an `AudioSep`-shaped holder (`.ss_model` a ResUNet30 on the
     device working at `sampling_rate`, `.query_encoder` with `get_query_embed`); jobs: a sequence of (in_path, query, out_path),
     query a caption or a (512,) embedding.  channels "each": every channel of a file is separated on its own with the file's
@@ -269,6 +313,14 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
     peak of what was written (20 log10 of gain x true peak).  meter: the record gains "loudness_range" (LU, EBU Tech 3342),
     "max_momentary" and "max_short_term" (LUFS), measured like "loudness_out" on the separated planes at the model rate before
     the gain (`Engine.loudness_stats` in the place of `Engine.loudness`); with or without a level.
+    limiter (it needs a peak_ceiling_db): a look-ahead limiter (`Engine.limit`, `loudness.limit`) in front of the level stage, so
+    that a ceiling that binds no longer costs the file its loudness: the separated planes are brought to `loudness` by a gain
+    without a ceiling (1 without a target) and held under the ceiling by one gain curve per file that reaches
+    `limiter_lookahead_ms` to either side of a peak, `limiter_passes` (>= 1) times, the gain corrected between the passes by the
+    loudness of the limited planes (one pass without a target).  The record gains "loudness_in" (the separated planes),
+    "limiter_gain_db" (the last pass's gain), "limiter_reduction_db" (20 log10 of the curve's smallest value, <= 0) and
+    "limiter_frames" (frames the curve was asked to lower); "loudness_out" and the `meter` figures then describe the LIMITED planes,
+    "gain" is the static trim the level stage applies to them, and the loudness written is loudness_out + gain_db.
     A file not longer than n_fft/2 samples at the model rate raises ValueError before anything is written."""
     import torch
 
@@ -278,6 +330,9 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
         raise ValueError(f"encoding must be one of {sorted(rs.ENCODINGS)} or None")
     ld.check_level_args(loudness, peak_ceiling_db)
     check_peak_arg(peak, peak_ceiling_db)
+    check_limiter_args(limiter, limiter_lookahead_ms, limiter_passes, peak_ceiling_db, int(sampling_rate))
+    limiter = bool(limiter)
+    reach = ld.reach(limiter_lookahead_ms, int(sampling_rate)) if limiter else 0
     level = loudness is not None or peak_ceiling_db is not None
     true_peak, meter = peak == "true", bool(meter)
     extra = level or meter               # whether anything travels behind the payload beside the clip counter
@@ -351,6 +406,15 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
                     stacked, gain, pk, stats = torch.stack(mine), None, None, None
                     if extra:
                         with clock("level"):
+                            if limiter:
+                                loud_in = eng.loudness(stacked, sr)
+                                lim_gain = eng.loudness_gain(loud_in, None, loudness, None)[0]
+                                n_pass = int(limiter_passes) if loudness is not None else 1
+                                for k in range(n_pass):
+                                    held, lim = eng.limit(stacked, sr, lim_gain, ld.ceiling_for(peak_ceiling_db, enc_o), reach, peak)
+                                    if k + 1 < n_pass:
+                                        lim_gain = lim_gain * eng.loudness_gain(eng.loudness(held, sr), None, loudness, None)[0]
+                                stacked = held[0]
                             if meter:
                                 stats = eng.loudness_stats(stacked, sr)["all"]
                                 measured = stats[:, 0]
@@ -365,7 +429,8 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
                         payload = eng.resample_encode(stacked, sr, rate_o, enc_o, frames_out=frames_o, clipped=clipped, gain=gain)
                     nbytes = payload.shape[1]
                     tail = (nbytes + 7) // 8 * 8 if extra else (nbytes + 3) // 4 * 4   # the clip counter travels behind the payload
-                    buf = pool.take(tail + (24 if extra else 4) + (80 if meter else 0))
+                    lim_at = tail + 24 + (80 if meter else 0)       # the limiter's four numbers come last
+                    buf = pool.take(tail + (24 if extra else 4) + (80 if meter else 0) + (24 if limiter else 0))
                     with clock("d2h"):
                         buf[:nbytes].copy_(payload[0], non_blocking=True)
                         buf[tail:tail + 4].view(torch.int32).copy_(clipped, non_blocking=True)
@@ -377,13 +442,22 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
                                 buf[tail + 12:tail + 16].view(torch.float32).copy_(pk, non_blocking=True)
                         if meter:                                  # ... and the ten numbers of Engine.loudness_stats
                             buf[tail + 24:tail + 104].view(torch.float64).copy_(stats[0], non_blocking=True)
+                        if limiter:
+                            buf[lim_at:lim_at + 8].view(torch.float64).copy_(loud_in, non_blocking=True)
+                            buf[lim_at + 8:lim_at + 12].view(torch.float32).copy_(lim_gain, non_blocking=True)
+                            buf[lim_at + 12:lim_at + 16].view(torch.float32).copy_(lim["min_gain"], non_blocking=True)
+                            buf[lim_at + 16:lim_at + 20].view(torch.int32).copy_(lim["frames"], non_blocking=True)
                         done = torch.cuda.Event()
                         done.record(torch.cuda.current_stream(dev))
-                    written.append((i, buf, tail, writer.submit(_write_device, jobs[i][2], wavio.wav_header(enc_o, n, rate_o, frames_o),
+                    written.append((i, buf, (tail, lim_at), writer.submit(_write_device, jobs[i][2], wavio.wav_header(enc_o, n, rate_o, frames_o),
                                                                 buf, nbytes, done, profile)))
                 else:
                     with clock("d2h"):
                         x = torch.stack(mine).cpu().numpy()
+                    if limiter:
+                        x, *lim = _host_limit(x, sr, loudness, ld.ceiling_for(peak_ceiling_db, enc_o), reach, true_peak,
+                                              int(limiter_passes))
+                        rec.update(_limiter_record(*lim))
                     y = _host_resample(x, sr, rate_o)[:, :frames_o]
                     if extra:                                      # the device's rule with lass_amd.loudness and numpy
                         p = ld.block_powers(x, sr)
@@ -400,11 +474,11 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
                         q = ld.short_term_powers(x, sr)
                         rec.update(_meter_record(ld.loudness_range(q)[0], ld.max_momentary(p), ld.max_short_term(q)))
                     rec["clipped"] = host_clip_count(y, enc_o)
-                    written.append((i, None, 0, writer.submit(_write_host, jobs[i][2], enc_o, y, rate_o, profile)))
+                    written.append((i, None, (0, 0), writer.submit(_write_host, jobs[i][2], enc_o, y, rate_o, profile)))
                 records[i] = rec
             reads = ahead
             # the pass's files are on disk (so its uploads are long done) and its counters read before its pinned rows go back
-            for i, buf, tail, fut in written:
+            for i, buf, (tail, lim_at), fut in written:
                 fut.result()
                 if buf is not None:
                     records[i]["clipped"] = int(buf[tail:tail + 4].view(torch.int32)[0])
@@ -416,6 +490,11 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
                     if meter:
                         ten = buf[tail + 24:tail + 104].view(torch.float64)
                         records[i].update(_meter_record(float(ten[5]), float(ten[3]), float(ten[4])))
+                    if limiter:
+                        records[i].update(_limiter_record(float(buf[lim_at:lim_at + 8].view(torch.float64)[0]),
+                                                          np.float32(buf[lim_at + 8:lim_at + 12].view(torch.float32)[0].item()),
+                                                          np.float32(buf[lim_at + 12:lim_at + 16].view(torch.float32)[0].item()),
+                                                          int(buf[lim_at + 16:lim_at + 20].view(torch.int32)[0])))
                     pool.give(buf)
             for buf in uploaded:
                 pool.give(buf)
@@ -424,8 +503,10 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
 
 
 def inference(model, audio_file: str, text, output_file: str, sampling_rate: int = 32000, loudness: Optional[float] = None,
-              peak_ceiling_db: Optional[float] = None, peak: str = "sample", meter: bool = False, **kw) -> dict:
+              peak_ceiling_db: Optional[float] = None, peak: str = "sample", meter: bool = False, limiter: bool = False,
+              limiter_lookahead_ms: float = 1.5, limiter_passes: int = 2, **kw) -> dict:
     """One file through `separate_files`: the single-file shape of upstream AudioSep's `pipeline.inference`.  loudness, peak_ceiling_db,
-    peak, meter and the other keywords are `separate_files`'s.  Returns the job's record."""
+    peak, meter, limiter, limiter_lookahead_ms, limiter_passes and the other keywords are `separate_files`'s.  Returns the job's record."""
     return separate_files(model, [(audio_file, text, output_file)], sampling_rate, loudness=loudness, peak_ceiling_db=peak_ceiling_db,
-                          peak=peak, meter=meter, **kw)[0]
+                          peak=peak, meter=meter, limiter=limiter, limiter_lookahead_ms=limiter_lookahead_ms,
+                          limiter_passes=limiter_passes, **kw)[0]

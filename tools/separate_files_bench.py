@@ -1,7 +1,7 @@
 """File in, file out on one MI355X: `pipeline.separate_files` against the same jobs done with the pieces the package had before
 it, on 32 seeded one-minute 44.1 kHz stereo PCM16 files (synthetic ResUNet30 weights, 16 kHz, f32 unless --compute-dtype).
 
-    python tools/separate_files_bench.py [--files 32] [--seconds 60] [--reps 5] [--compute-dtype f32] [--loudness [--true-peak] [--meter]]
+    python tools/separate_files_bench.py [--files 32] [--seconds 60] [--reps 5] [--compute-dtype f32] [--loudness [--true-peak] [--meter] [--limiter]]
 
 Leg A: `separate_files(channels="each")` - decode, resample, separate, resample back, encode and interleave on the device.
 Leg B: host decode + de-interleave + `wavio._resample` (scipy, float64), `separate_long_list`, `.cpu()`, host `_resample` back
@@ -17,6 +17,11 @@ is the number to hold against the same tool's leg A on the parent commit: it lau
 --true-peak / --meter (with --loudness): a third leg R, leg L's call with `peak="true"` and / or `meter=True` (EBU R 128: the
 ceiling holds the true peak; loudness range and the two maxima beside the loudness), alternating A L R A L R ...; the profiled run
 is then leg R's.  Leg L is the number to hold against the parent's leg L; R over L is what the two arguments add.
+
+--limiter (with --loudness): one more leg M, the call of the leg before it (R, or L without the two flags above) with
+`limiter=True` - the look-ahead limiter in front of the level stage - alternating ... M ...; the profiled run is then leg M's, and
+it also prints, per file, the limiter's reduction beside the static trim the level stage still applied ("gain_db"): the
+limiter's own overshoot.  The legs before M launch what they launched without the flag.
 """
 import argparse
 import json
@@ -85,19 +90,23 @@ def host_pieces(model, jobs):
 
 
 def leg(name: str, d: str, n: int, mode: str, true_peak: bool = False, meter: bool = False):
+    """One run of leg `name` (A, B, L, R or M, or one of them with "-profile") in this process."""
     import torch
     from lass_amd import pipeline
     model = _model(mode)
     profile = {} if name.endswith("-profile") else None
-    level = dict(loudness=-23.0, peak_ceiling_db=-1.0) if name[0] in "LR" else {}
-    if name.startswith("R"):
+    level = dict(loudness=-23.0, peak_ceiling_db=-1.0) if name[0] in "LRM" else {}
+    if name[0] in "RM":
         level.update(peak="true" if true_peak else "sample", meter=meter)
+    if name.startswith("M"):
+        level.update(limiter=True)
+    records = []
 
     def run(jobs, profile=None):
         if name == "B":
             host_pieces(model, jobs)
         else:
-            pipeline.separate_files(model, jobs, SR, channels="each", profile=profile, **level)
+            records[:] = pipeline.separate_files(model, jobs, SR, channels="each", profile=profile, **level)
 
     run(_jobs(d, 1, "warm"))
     torch.cuda.synchronize()
@@ -107,6 +116,9 @@ def leg(name: str, d: str, n: int, mode: str, true_peak: bool = False, meter: bo
     res = {"leg": name, "seconds": round(time.perf_counter() - t0, 4)}
     if profile is not None:
         res["split_s"] = {k: round(v, 4) for k, v in profile.items()}
+        if name.startswith("M"):
+            keys = ("loudness_in", "limiter_gain_db", "limiter_reduction_db", "limiter_frames", "loudness_out", "gain_db")
+            res["per_file"] = [{k: round(r[k], 4) for k in keys} for r in records]
     print(json.dumps(res), flush=True)
 
 
@@ -120,22 +132,23 @@ def main():
     ap.add_argument("--loudness", action="store_true", help="leg A against leg L (loudness=-23, peak_ceiling_db=-1) instead of leg B")
     ap.add_argument("--true-peak", action="store_true", help="with --loudness: a leg R with peak=\"true\"")
     ap.add_argument("--meter", action="store_true", help="with --loudness: a leg R with meter=True")
-    ap.add_argument("--leg", choices=["A", "B", "L", "R", "A-profile", "L-profile", "R-profile"])
+    ap.add_argument("--limiter", action="store_true", help="with --loudness: a leg M, the last leg's call with limiter=True")
+    ap.add_argument("--leg", choices=["A", "B", "L", "R", "M", "A-profile", "L-profile", "R-profile", "M-profile"])
     ap.add_argument("--dir")
     a = ap.parse_args()
     if a.leg:
         leg(a.leg, a.dir, a.files, a.compute_dtype, a.true_peak, a.meter)
         return 0
     r128 = a.true_peak or a.meter
-    if r128 and not a.loudness:
-        ap.error("--true-peak and --meter go with --loudness")
+    if (r128 or a.limiter) and not a.loudness:
+        ap.error("--true-peak, --meter and --limiter go with --loudness")
     with tempfile.TemporaryDirectory() as d:
         make_files(d, a.files, a.seconds)
         other = "L" if a.loudness else "B"
-        legs = ["A", other] + (["R"] if r128 else [])
+        legs = ["A", other] + (["R"] if r128 else []) + (["M"] if a.limiter else [])
         prof = legs[-1] + "-profile" if a.loudness else "A-profile"
         times = {name: [] for name in legs}
-        split = None
+        split = per_file = None
         for name in legs * a.reps + [prof]:
             cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--leg", name, "--dir", d,
                    "--files", str(a.files), "--compute-dtype", a.compute_dtype] + ["--true-peak"] * a.true_peak + ["--meter"] * a.meter
@@ -147,7 +160,7 @@ def main():
                 return pr.returncode
             res = json.loads(pr.stdout.strip().split("\n")[-1])
             if name == prof:
-                split = res["split_s"]
+                split, per_file = res["split_s"], res.get("per_file")
             else:
                 times[name].append(res["seconds"])
         audio = a.files * a.seconds
@@ -160,6 +173,9 @@ def main():
         if r128:
             summary["R"]["true_peak"], summary["R"]["meter"] = a.true_peak, a.meter
             summary["R_over_L"] = round(summary["R"]["median_s"] / summary["L"]["median_s"], 2)
+        if a.limiter:
+            summary["M_over_" + legs[-2]] = round(summary["M"]["median_s"] / summary[legs[-2]]["median_s"], 2)
+            summary["M_per_file"] = per_file
         print(json.dumps(summary), flush=True)
     return 0
 
