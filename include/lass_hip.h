@@ -588,6 +588,36 @@ int lass_limit(lass_ctx* ctx, const float* planes, int64_t row_stride, int64_t p
                int64_t out_row_stride, int64_t out_plane_stride, float* curve, float* envelope, int64_t curve_row_stride,
                float* min_gain, int* frames, void* stream);
 
+/* ---- remix export: the original with the target removed, ducked or boosted (opt-in; separate_files(target_gain_db=)) ---- */
+
+/* lass_resample_encode (gain NULL) or lass_resample_encode_gain (gain: device, B floats) of a remix: with y that entry point's
+ * float32 value before quantisation for frame n and channel c of recording b (the same kernel body, tile plan, tap order and fmaf
+ * chain: bit-identical to lass_decode_resample of the plane), the value that is quantised (after fl(gain[b] * v) with a gain) is
+ *   v = fl( x + fl( amount[b] * y ) )
+ * - two float32 roundings, never an fma - where x is sample n*channels + c of row b of `dry`, decoded by lass_decode_resample's
+ * rule: s / 32768 (LASS_WAV_PCM16), (float)s * 2^-31 (LASS_WAV_PCM32, the conversion rounded to nearest), the float itself
+ * (LASS_WAV_F32).  dry: device, B rows of at least frames_out interleaved frames of `channels` samples, dry_row_stride_bytes
+ * apart, encoding dry_encoding - independent of the output's `encoding`; amount: device, B floats.  The original is read at the
+ * file's rate from its own samples, so everything the model did not touch keeps its full band; only y is band-limited.
+ * Identities: amount[b] == 0 and a finite y give v == x, hence a PCM16 payload encoded as PCM16 comes back byte for byte, a float32
+ * payload comes back equal as values (x + (+0) turns -0.0 into +0.0), and a PCM32 payload comes back as its float32 rounding; an
+ * all-zero float32 dry payload with amount[b] == 1 gives lass_resample_encode's values.
+ * Limits, checked before anything is launched (LASS_ERR_ARG): lass_resample_encode's, and dry non-NULL and 4-byte aligned,
+ * dry_encoding one of the three, dry_row_stride_bytes a multiple of 4 and >= frames_out * channels * bytes per sample, amount
+ * non-NULL (and, as gain, 4-byte aligned).  Stateless, no floating-point atomics: a row's bytes are bit-identical alone and as any
+ * row of any batch.  Not ported: the reference writes the separated target only. */
+int lass_remix_encode(lass_ctx* ctx, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels, int L_in,
+                      int up, int down, const float* taps, int n_taps, const void* dry, int64_t dry_row_stride_bytes,
+                      int dry_encoding, const float* amount, int encoding, const float* gain, void* out_bytes,
+                      int64_t out_row_stride_bytes, int frames_out, unsigned* clipped, void* stream);
+
+/* The sample peak of what lass_remix_encode (without a gain) would quantise: peak[b] = max |v| over the channels of recording b and
+ * n < frames_out, v as above - lass_resample_peak with the dry source, by the same integer atomic max; a NaN is skipped.
+ * Arguments and limits: lass_remix_encode's up to amount, then lass_resample_peak's. */
+int lass_remix_peak(lass_ctx* ctx, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels, int L_in,
+                    int up, int down, const float* taps, int n_taps, const void* dry, int64_t dry_row_stride_bytes, int dry_encoding,
+                    const float* amount, int frames_out, float* peak, void* stream);
+
 /* Training-side data path ("next" row f4, mixer half; also the producer stage of the STFT pre-compute,
  * scripts/precompute_stfts.py:352-681): SegmentMixer.__call__ + dynamic_loudnorm (data/waveform_mixers.py:19-92) on the
  * device.  waveforms (B,L) -> mixture (B,L), segment (B,L).  For clip n:

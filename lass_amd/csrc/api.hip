@@ -1454,6 +1454,65 @@ int lass_resample_peak(lass_ctx* c, const float* planes, int64_t row_stride, int
     return 0;
 }
 
+// What the two remix entries ask of the dry source, after check_export_planes (w: the entry's "name: ").
+static int check_dry(lass_ctx* c, const char* w, const void* dry, int64_t dry_row_stride_bytes, int dry_encoding, const float* amount,
+                     int channels, int frames_out) {
+    if (!dry || !amount) return fail(c, LASS_ERR_ARG, std::string(w) + "dry and amount non-NULL");
+    if (dry_encoding != LASS_WAV_PCM16 && dry_encoding != LASS_WAV_PCM32 && dry_encoding != LASS_WAV_F32)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "dry_encoding must be LASS_WAV_PCM16, LASS_WAV_PCM32 or LASS_WAV_F32");
+    const long long row_bytes = (long long)frames_out * channels * (dry_encoding == LASS_WAV_PCM16 ? 2 : 4);
+    if (dry_row_stride_bytes < row_bytes || dry_row_stride_bytes % 4 != 0)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "dry_row_stride_bytes must be a multiple of 4 and hold frames_out frames (" +
+                    std::to_string(row_bytes) + " bytes)");
+    if (reinterpret_cast<uintptr_t>(dry) % 4 != 0 || reinterpret_cast<uintptr_t>(amount) % 4 != 0)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "dry and amount must be 4-byte aligned");
+    return 0;
+}
+
+int lass_remix_encode(lass_ctx* c, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels, int L_in, int up,
+                      int down, const float* taps, int n_taps, const void* dry, int64_t dry_row_stride_bytes, int dry_encoding,
+                      const float* amount, int encoding, const float* gain, void* out_bytes, int64_t out_row_stride_bytes,
+                      int frames_out, unsigned* clipped, void* stream) {
+    const char* w = "lass_remix_encode: ";
+    if (!c) return LASS_ERR_ARG;
+    if (!planes || !out_bytes || B <= 0 || B > 65535 || L_in <= 0)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "planes, out_bytes non-NULL, 1 <= B <= 65535, L_in >= 1");
+    if (int r = check_resample_args(c, w, channels, encoding, up, down, taps, n_taps)) return r;
+    if (int r = check_export_planes(c, w, planes, row_stride, plane_stride, channels, L_in, up, down, frames_out)) return r;
+    if (int r = check_dry(c, w, dry, dry_row_stride_bytes, dry_encoding, amount, channels, frames_out)) return r;
+    const long long row_bytes = (long long)frames_out * channels * (encoding == LASS_WAV_PCM16 ? 2 : 4);
+    if (out_row_stride_bytes < row_bytes || out_row_stride_bytes % 4 != 0)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "out_row_stride_bytes must be a multiple of 4 and hold a row (" +
+                    std::to_string(row_bytes) + " bytes)");
+    if (reinterpret_cast<uintptr_t>(out_bytes) % 4 != 0) return fail(c, LASS_ERR_ARG, std::string(w) + "out_bytes must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(planes) % 4 != 0 || reinterpret_cast<uintptr_t>(clipped) % 4 != 0 ||
+        reinterpret_cast<uintptr_t>(gain) % 4 != 0)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "planes, gain and clipped must be 4-byte aligned");
+    if (int r = use_device(c)) return r;
+    HIP_TRY(c, lass_launch_remix_encode(planes, row_stride, plane_stride, B, channels, L_in, up, down, taps, n_taps, dry,
+                                        dry_row_stride_bytes, dry_encoding, amount, encoding, gain, out_bytes, out_row_stride_bytes,
+                                        frames_out, clipped, (hipStream_t)stream));
+    return 0;
+}
+
+int lass_remix_peak(lass_ctx* c, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels, int L_in, int up,
+                    int down, const float* taps, int n_taps, const void* dry, int64_t dry_row_stride_bytes, int dry_encoding,
+                    const float* amount, int frames_out, float* peak, void* stream) {
+    const char* w = "lass_remix_peak: ";
+    if (!c) return LASS_ERR_ARG;
+    if (!planes || !peak || B <= 0 || B > 65535 || L_in <= 0)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "planes, peak non-NULL, 1 <= B <= 65535, L_in >= 1");
+    if (int r = check_resample_args(c, w, channels, LASS_WAV_F32, up, down, taps, n_taps)) return r;
+    if (int r = check_export_planes(c, w, planes, row_stride, plane_stride, channels, L_in, up, down, frames_out)) return r;
+    if (int r = check_dry(c, w, dry, dry_row_stride_bytes, dry_encoding, amount, channels, frames_out)) return r;
+    if (reinterpret_cast<uintptr_t>(planes) % 4 != 0 || reinterpret_cast<uintptr_t>(peak) % 4 != 0)
+        return fail(c, LASS_ERR_ARG, std::string(w) + "planes and peak must be 4-byte aligned");
+    if (int r = use_device(c)) return r;
+    HIP_TRY(c, lass_launch_remix_peak(planes, row_stride, plane_stride, B, channels, L_in, up, down, taps, n_taps, dry,
+                                      dry_row_stride_bytes, dry_encoding, amount, frames_out, peak, (hipStream_t)stream));
+    return 0;
+}
+
 int lass_resample_true_peak(lass_ctx* c, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels, int L_in,
                             int up, int down, const float* taps, int n_taps, int frames_out, int os, const float* os_taps,
                             int n_os_taps, float* peak, void* stream) {

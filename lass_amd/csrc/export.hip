@@ -14,6 +14,11 @@
 // same after one multiplication by the row's gain (kEncodeGain, lass_resample_encode_gain), or into the row's peak |y| with no
 // stage and no store (kPeak, lass_resample_peak).  Up to that point the three are one body, so they see the same y.
 //
+// They are templates, too, over a dry source (Dry...: none, or one DryRows): with one, the value that goes to the sink is
+//   v = fl(x + fl(amount[b] * y)),  x the sample of the original payload row at the same frame and channel (wav_sample.h)
+// - the remix of lass_remix_encode and lass_remix_peak.  y, the tile plan, the stage and the sinks are the
+// same code; without a dry source a kernel takes no further argument and is the instantiation it was.
+//
 // k_true_peak (lass_resample_true_peak) is a fourth use of the same chain: it keeps the y of its tile and a halo as floats in LDS
 // and runs polyphase.h's chain once more over them, at (os, 1), for the peak between the samples.  DESIGN.md section 19.
 #include "../../include/lass_hip.h"
@@ -22,6 +27,7 @@
 namespace {
 
 #include "polyphase.h"
+#include "wav_sample.h"
 
 constexpr int kTilePlain = 1024;        // k_encode: 1024 frames x 8 channels x 4 bytes = 32 KiB of stage
 
@@ -88,6 +94,37 @@ __device__ __forceinline__ void emit(unsigned char* stage, int k, float y, float
     }
 }
 
+// The dry source of a remix: B payload rows (enc = LASS_WAV_*, row_stride bytes apart) and one amount per row.
+struct DryRows {
+    const unsigned char* rows;
+    long long row_stride;
+    const float* amount;
+    int enc;
+};
+
+// What a workgroup with a dry source makes of an output y, sample idx (frame-major, interleaved; 64-bit: a row's samples pass 2^31
+// before a plane's do) of its row, before the sink has it: fl(x + fl(k * y)) with x = sample idx of the payload row and k the row's
+// amount - two roundings, so numpy float32 restates them.  (__fadd_rn(x, __fmul_rn(k, y)) does not say so here: the toolchain's
+// header defines the two as plain + and *, and under HIP's default -ffp-contract=fast they inline to one v_fmac_f32.  The pragma
+// takes the contract flag off both operations instead.)  x is read straight from memory: consecutive lanes are on consecutive
+// frames and the channel loop comes back to the same lines, so the stage and the tile plan are those of a launch without a dry
+// source.  Without one (the empty pack) the kernels, which ask `if constexpr`, make the call they always made and compile to the
+// instructions they were.
+template <class... Dry>
+struct Mix {};
+template <>
+struct Mix<DryRows> {
+    const unsigned char* row;
+    float k;
+    int enc;
+    __device__ __forceinline__ Mix(DryRows d) : row(d.rows + (size_t)blockIdx.y * d.row_stride), k(d.amount[blockIdx.y]), enc(d.enc) {}
+    __device__ __forceinline__ float operator()(long long idx, float y) const {
+#pragma clang fp contract(off)
+        const float p = k * y;
+        return sample_at(row, idx, enc) + p;
+    }
+};
+
 // the tile's end: the stage to memory and the clip count, or the workgroup's peak, to the row's counter
 template <Sink kSink>
 __device__ __forceinline__ void finish(const unsigned char* stage0, unsigned char* __restrict__ out, long long out_row_stride, size_t a,
@@ -107,11 +144,11 @@ __device__ __forceinline__ void finish(const unsigned char* stage0, unsigned cha
 }
 
 // up == down == 1: quantise and interleave only
-template <Sink kSink>
+template <Sink kSink, class... Dry>
 __global__ __launch_bounds__(kThreads) void k_encode(const float* __restrict__ planes, long long row_stride, long long plane_stride,
                                                      int ch, int enc, unsigned char* __restrict__ out, long long out_row_stride,
                                                      int frames_out, unsigned* __restrict__ clipped, const float* __restrict__ gain,
-                                                     unsigned* __restrict__ peak) {
+                                                     unsigned* __restrict__ peak, Dry... dry) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     unsigned char* stage0 = reinterpret_cast<unsigned char*>(lds);
     const int tid = threadIdx.x;
@@ -122,20 +159,24 @@ __global__ __launch_bounds__(kThreads) void k_encode(const float* __restrict__ p
     unsigned char* stage = stage0 + (a & 3);
     const float* x = planes + (size_t)blockIdx.y * row_stride + n0;
     const float g = row_gain<kSink>(gain);
+    const Mix<Dry...> mix{dry...};
     unsigned clips = 0, pk = 0;
     for (int c = 0; c < ch; ++c)
-        for (int i = tid; i < nout; i += kThreads) emit<kSink>(stage, i * ch + c, x[(size_t)c * plane_stride + i], g, enc, &clips, &pk);
+        for (int i = tid; i < nout; i += kThreads) {
+            if constexpr (sizeof...(Dry) == 0) emit<kSink>(stage, i * ch + c, x[(size_t)c * plane_stride + i], g, enc, &clips, &pk);
+            else emit<kSink>(stage, i * ch + c, mix((n0 + i) * ch + c, x[(size_t)c * plane_stride + i]), g, enc, &clips, &pk);
+        }
     finish<kSink>(stage0, out, out_row_stride, a, (size_t)nout * ch * bps, tid, clips, clipped, pk, peak);
 }
 
-template <Sink kSink>
+template <Sink kSink, class... Dry>
 __global__ __launch_bounds__(kThreads) void k_resample_encode(const float* __restrict__ planes, long long row_stride,
                                                               long long plane_stride, int L_in, int ch, int enc, int up, int down,
                                                               const float* __restrict__ taps, int n_taps, int J, int tile,
                                                               int span_floats, unsigned char* __restrict__ out,
                                                               long long out_row_stride, int frames_out,
                                                               unsigned* __restrict__ clipped, const float* __restrict__ gain,
-                                                              unsigned* __restrict__ peak) {
+                                                              unsigned* __restrict__ peak, Dry... dry) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x;
     const int bps = sample_bytes(enc);
@@ -147,13 +188,17 @@ __global__ __launch_bounds__(kThreads) void k_resample_encode(const float* __res
     fir_table(T, taps, n_taps);
 
     const float g = row_gain<kSink>(gain);
+    const Mix<Dry...> mix{dry...};
     unsigned clips = 0, pk = 0;
     for (int c = 0; c < ch; ++c) {
         const float* x0 = rec + (size_t)c * plane_stride;
         if (c) __syncthreads();                           // the previous channel's reads of the span
         fir_fill(T, L_in, [&](long long m) { return x0[m]; });
         __syncthreads();
-        for (int i = tid; i < T.nout; i += kThreads) emit<kSink>(stage, i * ch + c, fir_output(T, i), g, enc, &clips, &pk);
+        for (int i = tid; i < T.nout; i += kThreads) {
+            if constexpr (sizeof...(Dry) == 0) emit<kSink>(stage, i * ch + c, fir_output(T, i), g, enc, &clips, &pk);
+            else emit<kSink>(stage, i * ch + c, mix((T.n0 + i) * ch + c, fir_output(T, i)), g, enc, &clips, &pk);
+        }
     }
     finish<kSink>(stage0, out, out_row_stride, a, (size_t)T.nout * ch * bps, tid, clips, clipped, pk, peak);
 }
@@ -234,30 +279,33 @@ size_t true_peak_floats(int up, int down, int n_taps, int os, int t) {
 
 }  // namespace
 
-// One launch for the three sinks.  kPeak keeps no stage (enc, out and clipped unused), so its tiles are as large as the span allows.
-template <Sink kSink>
+// One launch for the three sinks, with or without a dry source.  kPeak keeps no stage (enc, out and clipped unused), so its tiles
+// are as large as the span allows.
+template <Sink kSink, class... Dry>
 static hipError_t launch(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L_in, int up, int down,
                          const float* taps, int n_taps, int enc, unsigned char* o, long long out_row_stride, int frames_out,
-                         unsigned* clipped, const float* gain, unsigned* peak, hipStream_t stream) {
+                         unsigned* clipped, const float* gain, unsigned* peak, hipStream_t stream, Dry... dry) {
     if (B <= 0 || B > 65535 || ch < 1 || ch > 8 || L_in <= 0 || frames_out <= 0 || up < 1 || down < 1) return hipErrorInvalidValue;
     const int bps = enc == LASS_WAV_PCM16 ? 2 : 4;
     if (up == 1 && down == 1) {
         const size_t lds = kSink == kPeak ? 0 : (size_t)kTilePlain * ch * bps + 4;
-        hipLaunchKernelGGL(k_encode<kSink>, dim3((frames_out + kTilePlain - 1) / kTilePlain, B), dim3(kThreads), lds, stream, planes,
-                           row_stride, plane_stride, ch, enc, o, out_row_stride, frames_out, clipped, gain, peak);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_encode<kSink, Dry...>), dim3((frames_out + kTilePlain - 1) / kTilePlain, B), dim3(kThreads),
+                           lds, stream, planes, row_stride, plane_stride, ch, enc, o, out_row_stride, frames_out, clipped, gain, peak,
+                           dry...);
         return hipGetLastError();
     }
     // the largest tile whose span and stage fit beside the table (one frame needs J floats of span and at most 9 of stage: it
     // always fits under the caps); the stage starts on a multiple of four floats
     FirPlan P;
-    hipError_t e = fir_plan(reinterpret_cast<const void*>(k_resample_encode<kSink>), up, down, n_taps, frames_out, [&](int t) {
+    hipError_t e = fir_plan(reinterpret_cast<const void*>(k_resample_encode<kSink, Dry...>), up, down, n_taps, frames_out, [&](int t) {
         const size_t head = (lass_resample_table_floats(up, n_taps) + lass_resample_span_floats(up, down, n_taps, t) + 3) & ~(size_t)3;
         return kSink == kPeak ? head : head + ((size_t)t * ch * bps + 4 + 3) / 4;
     }, &P);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_resample_encode<kSink>, dim3(P.nblk, B), dim3(kThreads), P.lds, stream, planes, row_stride, plane_stride, L_in,
-                       ch, enc, up, down, taps, n_taps, P.J, P.tile, (int)lass_resample_span_floats(up, down, n_taps, P.tile), o,
-                       out_row_stride, frames_out, clipped, gain, peak);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_resample_encode<kSink, Dry...>), dim3(P.nblk, B), dim3(kThreads), P.lds, stream, planes,
+                       row_stride, plane_stride, L_in, ch, enc, up, down, taps, n_taps, P.J, P.tile,
+                       (int)lass_resample_span_floats(up, down, n_taps, P.tile), o, out_row_stride, frames_out, clipped, gain, peak,
+                       dry...);
     return hipGetLastError();
 }
 
@@ -283,6 +331,29 @@ hipError_t lass_launch_resample_peak(const float* planes, long long row_stride, 
     if (e != hipSuccess) return e;
     return launch<kPeak>(planes, row_stride, plane_stride, B, ch, L_in, up, down, taps, n_taps, LASS_WAV_F32, nullptr, 0, frames_out,
                          nullptr, nullptr, reinterpret_cast<unsigned*>(peak), stream);
+}
+
+hipError_t lass_launch_remix_encode(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L_in, int up,
+                                    int down, const float* taps, int n_taps, const void* dry, long long dry_row_stride, int dry_enc,
+                                    const float* amount, int enc, const float* gain, void* out, long long out_row_stride,
+                                    int frames_out, unsigned* clipped, hipStream_t stream) {
+    const DryRows d{static_cast<const unsigned char*>(dry), dry_row_stride, amount, dry_enc};
+    unsigned char* o = static_cast<unsigned char*>(out);
+    return gain ? launch<kEncodeGain>(planes, row_stride, plane_stride, B, ch, L_in, up, down, taps, n_taps, enc, o, out_row_stride,
+                                      frames_out, clipped, gain, nullptr, stream, d)
+                : launch<kEncode>(planes, row_stride, plane_stride, B, ch, L_in, up, down, taps, n_taps, enc, o, out_row_stride,
+                                  frames_out, clipped, nullptr, nullptr, stream, d);
+}
+
+hipError_t lass_launch_remix_peak(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L_in, int up,
+                                  int down, const float* taps, int n_taps, const void* dry, long long dry_row_stride, int dry_enc,
+                                  const float* amount, int frames_out, float* peak, hipStream_t stream) {
+    if (B <= 0) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(peak, 0, (size_t)B * sizeof(float), stream);
+    if (e != hipSuccess) return e;
+    const DryRows d{static_cast<const unsigned char*>(dry), dry_row_stride, amount, dry_enc};
+    return launch<kPeak>(planes, row_stride, plane_stride, B, ch, L_in, up, down, taps, n_taps, LASS_WAV_F32, nullptr, 0, frames_out,
+                         nullptr, nullptr, reinterpret_cast<unsigned*>(peak), stream, d);
 }
 
 bool lass_resample_true_peak_fits(int up, int down, int n_taps, int os) {

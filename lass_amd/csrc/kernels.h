@@ -313,6 +313,18 @@ hipError_t lass_launch_resample_true_peak(const float* planes, long long row_str
                                           int n_os_taps, float* peak, hipStream_t stream);
 // whether a tile of one frame - table, the span of its 21 first-stage outputs, stage, second table - fits the CU's 160 KiB
 bool lass_resample_true_peak_fits(int up, int down, int n_taps, int os);
+// The remix of lass_launch_resample_encode[_gain] and lass_launch_resample_peak (lass_remix_encode, lass_remix_peak): the value
+// that is quantised (times gain[b] first where gain is not NULL) or goes into the peak is v = fl(x + fl(amount[b] * y)), x sample
+// n*ch + c of row b of `dry` (B payload rows of at least frames_out frames, dry_enc = LASS_WAV_*, dry_row_stride bytes apart;
+// amount: B device floats), y the value those entries quantise.  The same kernel bodies and tile plans with one more read stream.
+// The caller has checked the arguments.
+hipError_t lass_launch_remix_encode(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L_in, int up,
+                                    int down, const float* taps, int n_taps, const void* dry, long long dry_row_stride, int dry_enc,
+                                    const float* amount, int enc, const float* gain, void* out, long long out_row_stride,
+                                    int frames_out, unsigned* clipped, hipStream_t stream);
+hipError_t lass_launch_remix_peak(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L_in, int up,
+                                  int down, const float* taps, int n_taps, const void* dry, long long dry_row_stride, int dry_enc,
+                                  const float* amount, int frames_out, float* peak, hipStream_t stream);
 
 // ---- limiter.hip --------------------------------------------------------------------------------------------------
 // lass_limit's kernel (include/lass_hip.h has the arithmetic): out = fl(fl(g * G) * x) with G the smoothed minimum of the gain

@@ -15,16 +15,10 @@
 namespace {
 
 #include "polyphase.h"
+#include "wav_sample.h"     // sample_at: one sample of the payload, by read_wav's rule
 
-// One frame of the clip as read_wav makes it: x/32768 (PCM16), round-to-nearest int -> float then * 2^-31 (PCM32: equal to
-// read_wav's float64 division rounded once, the scaling being exact), the float itself (float32); channels summed in ascending
-// order in f32 and divided by their count, correctly rounded (numpy's mean over the channel axis).
-__device__ __forceinline__ float sample_at(const unsigned char* __restrict__ row, long long idx, int enc) {
-    if (enc == LASS_WAV_PCM16) return (float)reinterpret_cast<const short*>(row)[idx] * (1.0f / 32768.0f);
-    if (enc == LASS_WAV_PCM32) return __int2float_rn(reinterpret_cast<const int*>(row)[idx]) * (1.0f / 2147483648.0f);
-    return reinterpret_cast<const float*>(row)[idx];
-}
-
+// One frame of the clip as read_wav makes it: its samples (sample_at) summed in ascending channel order in f32 and divided by
+// their count, correctly rounded (numpy's mean over the channel axis).
 __device__ __forceinline__ float frame_at(const unsigned char* __restrict__ row, long long m, int ch, int enc) {
     float s = sample_at(row, m * ch, enc);
     if (ch == 1) return s;

@@ -753,6 +753,85 @@ class Engine:
         _lib.check(self.ctx, rc, "lass_resample_peak")
         return peak
 
+    def _remix_args(self, planes, rate_in, rate_out, dry, dry_encoding, amount, frames_out):
+        """What `remix_encode` and `remix_peak` share: (planes, row stride, plane stride, up, down, taps or None, frames_out, dry
+        stride), with `resample_encode`'s refusals and those of the dry source."""
+        from . import resample as rs
+        planes, row_stride, plane_stride = self._planes(planes)
+        B, C, L = planes.shape
+        up, down = rs.ratio(rate_in, rate_out)
+        ceiling = rs.out_len(L, up, down)
+        frames_out = ceiling if frames_out is None else int(frames_out)
+        if not 1 <= frames_out <= ceiling:
+            raise _lib.LassError(f"frames_out must lie in 1 ... ceil(L * up / down) = {ceiling}")
+        fir = (up, down) != (1, 1)
+        if fir and not rs.within_cap(up, down):
+            raise _lib.LassError(f"resampling {rate_in} -> {rate_out} Hz needs {rs.n_taps(up, down)} taps, over the device "
+                                 f"kernel's cap of {rs.MAX_TAPS}: resample on the host (wavio.write_wav_*)")
+        if dry_encoding not in rs.ENCODINGS:
+            raise _lib.LassError(f"dry_encoding must be one of {sorted(rs.ENCODINGS)}")
+        dry_bytes = frames_out * C * rs.SAMPLE_BYTES[dry_encoding]
+        if dry.dim() == 1:
+            dry = dry[None]
+        if (dry.dim() != 2 or dry.shape[0] != B or dry.shape[1] < dry_bytes or dry.dtype != torch.uint8 or dry.device != self.device
+                or dry.stride(1) != 1):
+            raise _lib.LassError(f"dry must be a ({B}, >= {dry_bytes}) uint8 tensor on {self.device} with contiguous rows")
+        if tuple(amount.shape) != (B,) or amount.dtype != torch.float32 or amount.device != self.device or not amount.is_contiguous():
+            raise _lib.LassError(f"amount must be a contiguous float32 ({B},) tensor on {self.device}")
+        dry_stride = dry.stride(0) if B > 1 else (dry_bytes + 3) // 4 * 4     # (one row: no stride to honour)
+        return planes, row_stride, plane_stride, up, down, (rs.device_taps(up, down, self.device) if fir else None), frames_out, dry, dry_stride
+
+    def remix_encode(self, planes: torch.Tensor, rate_in: int, rate_out: int, encoding: str, dry: torch.Tensor, dry_encoding: str,
+                     amount: torch.Tensor, frames_out: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                     clipped: Optional[torch.Tensor] = None, gain: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`resample_encode` of a remix, on the device (lass_remix_encode): what is quantised for frame n, channel c of row b is
+        v = fl(x + fl(amount[b] * y)) - times gain[b], rounded once more, with a `gain` - where y is the float32 `resample_encode`
+        quantises (bit-identical to `resample` of the plane) and x sample n * C + c of row b of `dry`, decoded as
+        `decode_resample_planar` decodes it.  dry: a (B, >= frames_out * C * sample bytes) uint8 tensor on the device, each row a
+        WAV data chunk at rate_out ("pcm16" / "pcm32" / "f32", whatever `encoding` is), rows a multiple of 4 bytes apart; amount:
+        (B,) float32 on the device (`pipeline.remix_coefficient`: -1 removes the target, 0 gives the original back).  The other
+        arguments, the result and the refusals are `resample_encode`'s; `pipeline.remix_host` is the numpy restatement of v."""
+        from . import resample as rs
+        if encoding not in rs.ENCODINGS:
+            raise _lib.LassError(f"encoding must be one of {sorted(rs.ENCODINGS)}")
+        planes, row_stride, plane_stride, up, down, taps, frames_out, dry, dry_stride = self._remix_args(
+            planes, rate_in, rate_out, dry, dry_encoding, amount, frames_out)
+        B, C, L = planes.shape
+        row_bytes = frames_out * C * rs.SAMPLE_BYTES[encoding]
+        if out is None:
+            out = _alloc.empty(B, (row_bytes + 3) // 4 * 4, dtype=torch.uint8, device=self.device)
+        elif (out.dim() != 2 or out.shape[0] != B or out.shape[1] < row_bytes or out.dtype != torch.uint8 or out.device != self.device
+              or out.stride(1) != 1):
+            raise _lib.LassError(f"out must be a ({B}, >= {row_bytes}) uint8 tensor on {self.device} with contiguous rows")
+        if clipped is not None and (tuple(clipped.shape) != (B,) or clipped.dtype != torch.int32 or clipped.device != self.device
+                                    or not clipped.is_contiguous()):
+            raise _lib.LassError(f"clipped must be a contiguous int32 ({B},) tensor on {self.device}")
+        if gain is not None and (tuple(gain.shape) != (B,) or gain.dtype != torch.float32 or gain.device != self.device
+                                 or not gain.is_contiguous()):
+            raise _lib.LassError(f"gain must be a contiguous float32 ({B},) tensor on {self.device}")
+        out_stride = out.stride(0) if B > 1 else (row_bytes + 3) // 4 * 4
+        rc = self.lib.lass_remix_encode(self.ctx, _ptr(planes), row_stride, plane_stride, B, C, L, up, down, _ptr(taps),
+                                        taps.numel() if taps is not None else 1, _ptr(dry), dry_stride, rs.ENCODINGS[dry_encoding],
+                                        _ptr(amount), rs.ENCODINGS[encoding], _ptr(gain), _ptr(out), out_stride, frames_out,
+                                        _ptr(clipped), _stream(self.device))
+        _lib.check(self.ctx, rc, "lass_remix_encode")
+        return out[:, :row_bytes]
+
+    def remix_peak(self, planes: torch.Tensor, rate_in: int, rate_out: int, dry: torch.Tensor, dry_encoding: str, amount: torch.Tensor,
+                   frames_out: Optional[int] = None) -> torch.Tensor:
+        """(B,) float32: max |v| over the channels and the first frames_out frames of each recording, v the very float32 values
+        `remix_encode` of the same arguments (without a gain) quantises (lass_remix_peak); a NaN is skipped."""
+        from . import resample as rs
+        planes, row_stride, plane_stride, up, down, taps, frames_out, dry, dry_stride = self._remix_args(
+            planes, rate_in, rate_out, dry, dry_encoding, amount, frames_out)
+        B, C, L = planes.shape
+        peak = _alloc.empty(B, dtype=torch.float32, device=self.device)
+        rc = self.lib.lass_remix_peak(self.ctx, _ptr(planes), row_stride, plane_stride, B, C, L, up, down, _ptr(taps),
+                                      taps.numel() if taps is not None else 1, _ptr(dry), dry_stride, rs.ENCODINGS[dry_encoding],
+                                      _ptr(amount), frames_out, _ptr(peak), _stream(self.device))
+        _lib.check(self.ctx, rc, "lass_remix_peak")
+        return peak
+
     def resample_true_peak(self, planes: torch.Tensor, rate_in: int, rate_out: int, frames_out: Optional[int] = None) -> torch.Tensor:
         """(B,) float32: the true peak of what `resample_encode` of the same arguments quantises - the larger of `resample_peak`
         and the peak of those samples interpolated os = loudness.oversampling(rate_out) times, phase 0 left out

@@ -37,6 +37,14 @@ passes - a fixed count, all on the device.  The limited planes then go through t
 guarantees the ceiling on what is written; its gain is now a static trim - thousandths of a dB where the limiter takes a few dB
 off rare peaks, tenths where it takes 25 dB off most of the file.  DESIGN.md section 20.
 
+With `target_gain_db=` the file written is a REMIX: the original with the target's level changed by that many dB (-inf takes the
+target out, -12 ducks it, +6 brings it up), v = original + k * target with k = 10^(dB/20) - 1, formed at the file's own rate
+from the original's own samples.  The device copy of a file's raw row is kept until that file's encode, which is
+`Engine.remix_encode` with the row as its dry source in the place of `Engine.resample_encode`: one more read stream in the
+same launch.  Only the estimate is band-limited to the model's rate; what the model did not touch keeps its full band, and at
+0 dB the file comes back as it went in.  A job of four, (in, query, out, remix_out), writes both the target and the remix from
+one separation.  DESIGN.md section 21.
+
 A file the device kernels do not take - a header `wavio.wav_info` does not fully understand, more than 8 channels, a rate pair
 beyond `resample.within_cap` in either direction - is decoded, resampled and written on the host (`wavio._resample`,
 `wavio.write_wav_*`); its separation still runs on the device, in the same pass, and its record says `path == "host"`.
@@ -151,6 +159,80 @@ def host_clip_count(x: np.ndarray, encoding: str) -> int:
     scale, lo, hi = (32768.0, -32768, 32767) if encoding == "pcm16" else (2147483648.0, -2147483648, 2147483647)
     r = np.round(np.asarray(x, dtype=np.float64) * scale)
     return int(np.count_nonzero((r < lo) | (r > hi)))
+
+
+# ---- remix -------------------------------------------------------------------------------------------
+def remix_coefficient(db) -> np.float32:
+    """k of `original + k * target` for a change of the target's level by `db` dB: float32(10^(db/20) - 1), formed in float64
+    and rounded once.  Exactly -1 for -inf (the target is removed) and exactly 0 for 0 (the file comes back).  ValueError for a
+    NaN, for +inf and for a boost beyond float32."""
+    try:
+        db = float(db)
+    except (TypeError, ValueError):
+        raise ValueError("target_gain_db must be a number of dB (-inf removes the target)") from None
+    if np.isnan(db) or db == np.inf:
+        raise ValueError("target_gain_db must be a number of dB below +inf (-inf removes the target)")
+    with np.errstate(over="ignore"):
+        k = np.float32(np.power(10.0, np.float64(db) / 20.0) - 1.0)
+    if not np.isfinite(k):
+        raise ValueError(f"target_gain_db = {db} dB is beyond float32")
+    return k
+
+
+def remix_host(x: np.ndarray, y: np.ndarray, k, gain=None) -> np.ndarray:
+    """lass_remix_encode's value before quantisation, restated in numpy float32: v = fl(x + fl(k * y)) - two roundings, as the
+    kernel makes them - and fl(gain * v) with a gain.  x: the decoded original, y: the estimate resampled to the file's rate."""
+    x, y = np.asarray(x, dtype=np.float32), np.asarray(y, dtype=np.float32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        p = np.float32(k) * y
+        v = x + p
+        return v if gain is None else np.float32(gain) * v
+
+
+def check_remix_args(target_gain_db, jobs, channels: str, out_rate, loudness, meter, limiter, peak) -> Optional[List[float]]:
+    """The dB of every job, or None without a `target_gain_db`.  ValueError for a job that is no (in, query, out) or (in, query,
+    out, remix_out), a job of four without a target_gain_db, a target_gain_db that is neither one number nor one per job
+    (`remix_coefficient`'s refusals), and in remix mode for channels="mono" (there is no mono original to mix into), an out_rate
+    that differs from a file's own rate (the original exists at its own rate alone), and loudness=, meter=True, limiter=True and
+    peak="true": those measure the separated planes at the model rate, which a remix does not write.  Reads the files' headers,
+    nothing else: it runs before the model is touched."""
+    for j in jobs:
+        if len(j) not in (3, 4):
+            raise ValueError("a job is (in_path, query, out_path) or (in_path, query, out_path, remix_out_path)")
+    if target_gain_db is None:
+        if any(len(j) == 4 for j in jobs):
+            raise ValueError("a job (in_path, query, out_path, remix_out_path) needs a target_gain_db")
+        return None
+    if isinstance(target_gain_db, (list, tuple, np.ndarray)):
+        dbs = list(target_gain_db)
+        if len(dbs) != len(jobs):
+            raise ValueError(f"target_gain_db holds {len(dbs)} values for {len(jobs)} jobs")
+    else:
+        dbs = [target_gain_db] * len(jobs)
+    for d in dbs:
+        remix_coefficient(d)
+    dbs = [float(d) for d in dbs]
+    if channels == "mono":
+        raise ValueError('target_gain_db needs channels="each": a remix keeps the original\'s channels')
+    for name, on in (("loudness", loudness is not None), ("meter", bool(meter)), ("limiter", bool(limiter)), ('peak="true"', peak == "true")):
+        if on:
+            raise ValueError(f"{name} measures the separated planes at the model rate, which a remix (target_gain_db) does not "
+                             "write; peak_ceiling_db with peak=\"sample\" is what a remix takes")
+    if out_rate is not None:
+        for j in jobs:
+            info = wavio.wav_info(j[0])
+            rate = info[2] if info is not None else _host_info(j[0])[2]
+            if int(out_rate) != rate:
+                raise ValueError(f"{j[0]}: a remix is written at the file's own rate ({rate} Hz), not out_rate = {int(out_rate)}")
+    return dbs
+
+
+def _remix_record(rec: dict, db: float, gain=None, limited=None) -> dict:
+    rec["target_gain_db"] = float(db)
+    if gain is not None:
+        with np.errstate(divide="ignore"):
+            rec.update({"gain": float(gain), "gain_db": float(20.0 * np.log10(np.float64(gain))), "peak_limited": bool(limited)})
+    return rec
 
 
 # ---- the pass ---------------------------------------------------------------------------------------------------------------
@@ -290,7 +372,7 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
                    fade_shape: str = "linear", max_batch: int = 16, max_samples: int = DEFAULT_MAX_SAMPLES,
                    profile: Optional[Dict[str, float]] = None, loudness: Optional[float] = None,
                    peak_ceiling_db: Optional[float] = None, peak: str = "sample", meter: bool = False, limiter: bool = False,
-                   limiter_lookahead_ms: float = 1.5, limiter_passes: int = 2) -> List[dict]:
+                   limiter_lookahead_ms: float = 1.5, limiter_passes: int = 2, target_gain_db=None) -> List[dict]:
     """Separate WAV files by caption, file in and file out.  model: an `AudioSep`-shaped holder (`.ss_model` a ResUNet30 on the
     device working at `sampling_rate`, `.query_encoder` with `get_query_embed`); jobs: a sequence of (in_path, query, out_path),
     query a caption or a (512,) embedding.  channels "each": every channel of a file is separated on its own with the file's
@@ -321,6 +403,19 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
     "limiter_gain_db" (the last pass's gain), "limiter_reduction_db" (20 log10 of the curve's smallest value, <= 0) and
     "limiter_frames" (frames the curve was asked to lower); "loudness_out" and the `meter` figures then describe the LIMITED planes,
     "gain" is the static trim the level stage applies to them, and the loudness written is loudness_out + gain_db.
+    target_gain_db (None: all of the above, bit for bit): a number of dB (-inf allowed), or one per job, turns on REMIX MODE - the
+    file written to out_path is the original with the target's level changed by that many dB, original + k * target with k =
+    `remix_coefficient(dB)`, at the file's own rate, channels and frame count (`Engine.remix_encode`; `remix_host` on the host
+    route): -inf removes the target, 0 gives the file back.  A job may then be (in_path, query, out_path, remix_out_path): out_path
+    is written exactly as without target_gain_db, the separated target, and remix_out_path is the remix, from the same separated
+    planes with one more encode launch; the record describes out_path as ever and carries "remix", the remix file's record.  The
+    record of a remix has "target_gain_db" beside the five keys.  A boost can clip, so peak_ceiling_db (with peak="sample") holds
+    for the remix too: `Engine.remix_peak` of what is about to be quantised, `Engine.loudness_gain` for the ceiling's gain alone,
+    `Engine.remix_encode(gain=)`; its record gains "gain", "gain_db" and "peak_limited" (no "loudness_out": nothing is metered),
+    and with PCM output "clipped" is 0.  Remix mode refuses (`check_remix_args`, ValueError) channels="mono", an out_rate other than
+    a file's own rate, loudness=, meter=True, limiter=True and peak="true".  The raw rows of a pass stay on the device until their
+    files are encoded, BESIDE the `max_samples` bound: about 5.5 bytes per model-rate sample for 44.1 kHz PCM16 at a 16 kHz model
+    (2 bytes x 44100 / 16000), up to 12 for 48 kHz float32.
     A file not longer than n_fft/2 samples at the model rate raises ValueError before anything is written."""
     import torch
 
@@ -337,13 +432,14 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
     true_peak, meter = peak == "true", bool(meter)
     extra = level or meter               # whether anything travels behind the payload beside the clip counter
     jobs = [tuple(j) for j in jobs]
+    dbs = check_remix_args(target_gain_db, jobs, channels, out_rate, loudness, meter, limiter, peak)
     ss = model.ss_model
     eng = ss.engine
     dev, sr = eng.device, int(sampling_rate)
 
     # plan: header, route and size of every job
     infos, hows, sizes = [], [], []
-    for in_path, _, _ in jobs:
+    for in_path in (j[0] for j in jobs):
         info = wavio.wav_info(in_path)
         how = route(info, sr, out_rate, true_peak)
         meta = info[:4] if info is not None else _host_info(in_path)
@@ -362,14 +458,58 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
         def submit_reads(ids):
             return [reader.submit(_read_job, jobs[i][0], infos[i][0], hows[i], channels, pool, profile) for i in ids]
 
-        written, uploaded = [], []
+        def write_remix(i, rec, mine, stacked, dry, amount):
+            """Job i's remix from its separated planes (`mine`, `stacked` on the device route) and its original (`dry`: the raw
+            row on the device, the decoded planes on the host route), written to the job's last path; -> its record, which is
+            complete once the pass's files are on disk."""
+            enc_in, rate, frames = infos[i][1][0], infos[i][1][2], infos[i][1][3]
+            enc_o, path_out = encoding or enc_in or "f32", jobs[i][-1]
+            rec = _remix_record(dict(rec), dbs[i])
+            ceiling = ld.ceiling_for(peak_ceiling_db, enc_o)
+            if hows[i] == "device":
+                gain = limited = None
+                if ceiling is not None:
+                    with clock("level"):
+                        pk = eng.remix_peak(stacked, sr, rate, dry, enc_in, amount, frames_out=frames)
+                        gain, limited = eng.loudness_gain(torch.full((1,), -np.inf, dtype=torch.float64, device=dev), pk, None, ceiling)
+                with clock("encode"):
+                    clipped = torch.zeros(1, dtype=torch.int32, device=dev)
+                    payload = eng.remix_encode(stacked, sr, rate, enc_o, dry, enc_in, amount, frames_out=frames, clipped=clipped, gain=gain)
+                nbytes = payload.shape[1]
+                tail = (nbytes + 3) // 4 * 4                   # clip counter, limited flag and gain travel behind the payload
+                buf = pool.take(tail + 12)
+                with clock("d2h"):
+                    buf[:nbytes].copy_(payload[0], non_blocking=True)
+                    buf[tail:tail + 4].view(torch.int32).copy_(clipped, non_blocking=True)
+                    if gain is not None:
+                        buf[tail + 4:tail + 8].view(torch.int32).copy_(limited, non_blocking=True)
+                        buf[tail + 8:tail + 12].view(torch.float32).copy_(gain, non_blocking=True)
+                    done = torch.cuda.Event()
+                    done.record(torch.cuda.current_stream(dev))
+                remixed.append((rec, buf, tail, gain is not None, writer.submit(
+                    _write_device, path_out, wavio.wav_header(enc_o, len(mine), rate, frames), buf, nbytes, done, profile)))
+            else:
+                with clock("d2h"):
+                    x = torch.stack(mine).cpu().numpy()
+                v = remix_host(dry, _host_resample(x, sr, rate)[:, :frames], remix_coefficient(dbs[i]))
+                if ceiling is not None:                        # the device's rule with numpy and loudness.gain_for
+                    pk = np.float32(np.nanmax(np.abs(v))) if v.size else np.float32(0.0)
+                    g, bit = ld.gain_for(-np.inf, pk, None, ceiling)
+                    v = (g * v).astype(np.float32)
+                    _remix_record(rec, dbs[i], g, bit)
+                rec["clipped"] = host_clip_count(v, enc_o)
+                remixed.append((rec, None, 0, False, writer.submit(_write_host, path_out, enc_o, v, rate, profile)))
+            return rec
+
+        written, uploaded, remixed = [], [], []
         reads = submit_reads(passes[0]) if passes else []
         for pi, ids in enumerate(passes):
             ahead = submit_reads(passes[pi + 1]) if pi + 1 < len(passes) else []   # the next pass is read while this one runs
             captions, cap_of = dedup_captions([jobs[i][1] for i in ids])
             emb = (model.query_encoder.get_query_embed(modality="text", text=captions, device=dev).to(torch.float32)
                    if captions else None)
-            planes, conds, counts = [], [], []
+            planes, conds, counts, dry = [], [], [], {}
+            amounts = None if dbs is None else torch.tensor([float(remix_coefficient(dbs[i])) for i in ids], dtype=torch.float32).to(dev)
             for k, (i, fut) in enumerate(zip(ids, reads)):
                 (info, meta), got = infos[i], fut.result()
                 enc_in, nch, rate, frames = meta
@@ -383,8 +523,12 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
                         else:
                             mine = [eng.decode_resample(raw, frames, nch, enc_in, rate, sr)[0]]
                     uploaded.append(got)
+                    if dbs is not None:
+                        dry[i] = raw                       # kept until the file's encode: the remix's dry source
                 else:
                     mine = [torch.from_numpy(p).to(dev) for p in _host_resample(got, rate, sr)]
+                    if dbs is not None:
+                        dry[i] = got
                 cond = emb[cap_of[k]] if cap_of[k] is not None else torch.as_tensor(jobs[i][1]).to(device=dev, dtype=torch.float32).reshape(-1)
                 planes += mine
                 conds += [cond] * len(mine)
@@ -393,7 +537,7 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
                 seps = ss.separate_long_list(planes, torch.stack(conds), window=window, context=context, max_batch=max_batch,
                                              fade=fade, fade_shape=fade_shape)
             at = 0
-            for i, n in zip(ids, counts):
+            for j, (i, n) in enumerate(zip(ids, counts)):
                 (info, meta), mine = infos[i], seps[at:at + n]
                 at += n
                 enc_in, nch, rate, frames = meta
@@ -402,8 +546,15 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
                 L = int(mine[0].shape[0])
                 frames_o = frames if rate_o == rate else rs.out_len(L, *rs.ratio(sr, rate_o))
                 rec = {"rate": rate_o, "channels": n, "frames": frames_o, "path": hows[i]}
+                stacked = torch.stack(mine) if hows[i] == "device" else None
+                if dbs is not None:
+                    remix = write_remix(i, rec, mine, stacked, dry.pop(i), amounts[j:j + 1])
+                    if len(jobs[i]) == 3:                          # the remix is the job's one file
+                        records[i] = remix
+                        continue
+                    rec["remix"] = remix                           # ... or goes beside the target, which is written as ever
                 if hows[i] == "device":
-                    stacked, gain, pk, stats = torch.stack(mine), None, None, None
+                    gain, pk, stats = None, None, None
                     if extra:
                         with clock("level"):
                             if limiter:
@@ -496,17 +647,26 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
                                                           np.float32(buf[lim_at + 12:lim_at + 16].view(torch.float32)[0].item()),
                                                           int(buf[lim_at + 16:lim_at + 20].view(torch.int32)[0])))
                     pool.give(buf)
+            for rec, buf, tail, gained, fut in remixed:
+                fut.result()
+                if buf is not None:
+                    rec["clipped"] = int(buf[tail:tail + 4].view(torch.int32)[0])
+                    if gained:
+                        _remix_record(rec, rec["target_gain_db"], np.float32(buf[tail + 8:tail + 12].view(torch.float32)[0].item()),
+                                      bool(buf[tail + 4:tail + 8].view(torch.int32)[0]))
+                    pool.give(buf)
             for buf in uploaded:
                 pool.give(buf)
-            written, uploaded = [], []
+            written, uploaded, remixed = [], [], []
     return records
 
 
 def inference(model, audio_file: str, text, output_file: str, sampling_rate: int = 32000, loudness: Optional[float] = None,
               peak_ceiling_db: Optional[float] = None, peak: str = "sample", meter: bool = False, limiter: bool = False,
-              limiter_lookahead_ms: float = 1.5, limiter_passes: int = 2, **kw) -> dict:
+              limiter_lookahead_ms: float = 1.5, limiter_passes: int = 2, target_gain_db=None, **kw) -> dict:
     """One file through `separate_files`: the single-file shape of upstream AudioSep's `pipeline.inference`.  loudness, peak_ceiling_db,
-    peak, meter, limiter, limiter_lookahead_ms, limiter_passes and the other keywords are `separate_files`'s.  Returns the job's record."""
+    peak, meter, limiter, limiter_lookahead_ms, limiter_passes, target_gain_db (with which `output_file` is the remix) and the other
+    keywords are `separate_files`'s.  Returns the job's record."""
     return separate_files(model, [(audio_file, text, output_file)], sampling_rate, loudness=loudness, peak_ceiling_db=peak_ceiling_db,
                           peak=peak, meter=meter, limiter=limiter, limiter_lookahead_ms=limiter_lookahead_ms,
-                          limiter_passes=limiter_passes, **kw)[0]
+                          limiter_passes=limiter_passes, target_gain_db=target_gain_db, **kw)[0]

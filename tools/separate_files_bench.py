@@ -2,6 +2,7 @@
 it, on 32 seeded one-minute 44.1 kHz stereo PCM16 files (synthetic ResUNet30 weights, 16 kHz, f32 unless --compute-dtype).
 
     python tools/separate_files_bench.py [--files 32] [--seconds 60] [--reps 5] [--compute-dtype f32] [--loudness [--true-peak] [--meter] [--limiter]]
+    python tools/separate_files_bench.py --remix DB
 
 Leg A: `separate_files(channels="each")` - decode, resample, separate, resample back, encode and interleave on the device.
 Leg B: host decode + de-interleave + `wavio._resample` (scipy, float64), `separate_long_list`, `.cpu()`, host `_resample` back
@@ -22,6 +23,10 @@ is then leg R's.  Leg L is the number to hold against the parent's leg L; R over
 `limiter=True` - the look-ahead limiter in front of the level stage - alternating ... M ...; the profiled run is then leg M's, and
 it also prints, per file, the limiter's reduction beside the static trim the level stage still applied ("gain_db"): the
 limiter's own overshoot.  The legs before M launch what they launched without the flag.
+
+--remix DB: leg A against leg X, the same call with `target_gain_db=DB` (the remix: the raw rows stay on the device and the encode
+reads them as its dry source), alternating A X A X ...; no leg B, and BOTH legs are profiled once at the end, so that the two
+`encode` stages stand side by side.
 """
 import argparse
 import json
@@ -89,8 +94,8 @@ def host_pieces(model, jobs):
         wavio.write_wav_pcm16(out, y, rate)
 
 
-def leg(name: str, d: str, n: int, mode: str, true_peak: bool = False, meter: bool = False):
-    """One run of leg `name` (A, B, L, R or M, or one of them with "-profile") in this process."""
+def leg(name: str, d: str, n: int, mode: str, true_peak: bool = False, meter: bool = False, remix_db=None):
+    """One run of leg `name` (A, B, L, R, M or X, or one of them with "-profile") in this process."""
     import torch
     from lass_amd import pipeline
     model = _model(mode)
@@ -100,6 +105,8 @@ def leg(name: str, d: str, n: int, mode: str, true_peak: bool = False, meter: bo
         level.update(peak="true" if true_peak else "sample", meter=meter)
     if name.startswith("M"):
         level.update(limiter=True)
+    if name.startswith("X"):
+        level.update(target_gain_db=remix_db)
     records = []
 
     def run(jobs, profile=None):
@@ -133,25 +140,30 @@ def main():
     ap.add_argument("--true-peak", action="store_true", help="with --loudness: a leg R with peak=\"true\"")
     ap.add_argument("--meter", action="store_true", help="with --loudness: a leg R with meter=True")
     ap.add_argument("--limiter", action="store_true", help="with --loudness: a leg M, the last leg's call with limiter=True")
-    ap.add_argument("--leg", choices=["A", "B", "L", "R", "M", "A-profile", "L-profile", "R-profile", "M-profile"])
+    ap.add_argument("--remix", type=float, metavar="DB", help="leg A against leg X (target_gain_db=DB) instead of leg B")
+    ap.add_argument("--leg", choices=["A", "B", "L", "R", "M", "X", "A-profile", "L-profile", "R-profile", "M-profile", "X-profile"])
     ap.add_argument("--dir")
     a = ap.parse_args()
     if a.leg:
-        leg(a.leg, a.dir, a.files, a.compute_dtype, a.true_peak, a.meter)
+        leg(a.leg, a.dir, a.files, a.compute_dtype, a.true_peak, a.meter, a.remix)
         return 0
     r128 = a.true_peak or a.meter
     if (r128 or a.limiter) and not a.loudness:
         ap.error("--true-peak, --meter and --limiter go with --loudness")
+    if a.remix is not None and a.loudness:
+        ap.error("--remix stands alone: a remix is not levelled")
     with tempfile.TemporaryDirectory() as d:
         make_files(d, a.files, a.seconds)
-        other = "L" if a.loudness else "B"
+        other = "L" if a.loudness else "X" if a.remix is not None else "B"
         legs = ["A", other] + (["R"] if r128 else []) + (["M"] if a.limiter else [])
-        prof = legs[-1] + "-profile" if a.loudness else "A-profile"
+        prof = legs[-1] + "-profile" if a.loudness or a.remix is not None else "A-profile"
         times = {name: [] for name in legs}
-        split = per_file = None
-        for name in legs * a.reps + [prof]:
+        split = per_file = a_split = None
+        for name in legs * a.reps + (["A-profile"] if a.remix is not None else []) + [prof]:
             cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--leg", name, "--dir", d,
                    "--files", str(a.files), "--compute-dtype", a.compute_dtype] + ["--true-peak"] * a.true_peak + ["--meter"] * a.meter
+            if a.remix is not None:
+                cmd += [f"--remix={a.remix}"]
             pr = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, text=True)
             sys.stdout.write(pr.stdout)
             sys.stdout.flush()
@@ -161,10 +173,14 @@ def main():
             res = json.loads(pr.stdout.strip().split("\n")[-1])
             if name == prof:
                 split, per_file = res["split_s"], res.get("per_file")
+            elif name == "A-profile":
+                a_split = res["split_s"]
             else:
                 times[name].append(res["seconds"])
         audio = a.files * a.seconds
         summary = {"files": a.files, "seconds_each": a.seconds, "compute_dtype": a.compute_dtype, prof[0] + "_split_s": split}
+        if a.remix is not None:
+            summary.update(remix_db=a.remix, A_split_s=a_split)
         for name, ts in times.items():
             med = statistics.median(ts)
             summary[name] = {"median_s": round(med, 4), "files_per_s": round(a.files / med, 2), "x_real_time": round(audio / med, 1),
