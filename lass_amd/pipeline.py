@@ -22,7 +22,7 @@ the encoder, per file: `Engine.loudness` over all of the file's planes at the mo
 resampler, so no file-rate float plane is made), `Engine.resample_peak` of the samples the encoder is about to quantise, and
 `Engine.loudness_gain`, whose one gain per file - the channel balance is kept - stays on the device and goes into
 `Engine.resample_encode(gain=)`.  Loudness, gain and the limited flag travel to the host behind the payload, with the clip
-counter.  Without a level none of this runs: the pass is the one above.
+counter, in the layout `Tail` alone knows.  Without a level none of this runs: the pass is the one above.
 
 For an EBU R 128 delivery (-23 LUFS, -1 dBTP) `peak="true"` puts `Engine.resample_true_peak` - the peak of the signal between
 the samples the encoder is about to quantise - where `Engine.resample_peak` stood, and `meter=True` puts `Engine.loudness_stats`
@@ -48,6 +48,10 @@ one separation.  DESIGN.md section 21.
 A file the device kernels do not take - a header `wavio.wav_info` does not fully understand, more than 8 channels, a rate pair
 beyond `resample.within_cap` in either direction - is decoded, resampled and written on the host (`wavio._resample`,
 `wavio.write_wav_*`); its separation still runs on the device, in the same pass, and its record says `path == "host"`.
+
+What the arguments and a file's header decide is decided before the first pass, host only: `Options` for the call and one
+`FilePlan` per job (`plan_files`).  A pass reads them and calls one function per stage of a file: `_device_level`,
+`_device_remix_level`, `_send` and `_collect`, `host_target` and `host_remix` on the host route.  DESIGN.md section 22.
 """
 from __future__ import annotations
 
@@ -55,7 +59,8 @@ import threading
 import time
 from concurrent.futures import ThreadPoolExecutor
 from contextlib import contextmanager
-from typing import Dict, List, Optional, Sequence, Tuple
+from dataclasses import dataclass
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -128,6 +133,69 @@ def _host_info(path: str):
     raises ValueError for what it cannot read either); the channel layout is then unknown and the file counts as mono."""
     x, rate = wavio.read_wav(path)
     return None, 1, rate, int(x.shape[0])
+
+
+@dataclass(frozen=True)
+class Options:
+    """What a `separate_files` call asks of every file, after its checks."""
+    loudness: Optional[float]        # LUFS target
+    ceiling_db: Optional[float]      # peak_ceiling_db
+    true_peak: bool                  # peak == "true"
+    meter: bool
+    limiter: bool
+    reach: int                       # the limiter's look-ahead in model-rate frames (0 without one)
+    passes: int                      # limiter_passes (0 without a limiter)
+    remix: bool                      # a target_gain_db was given
+
+    @property
+    def level(self) -> bool:
+        return self.loudness is not None or self.ceiling_db is not None
+
+    @property
+    def extra(self) -> bool:         # whether a target sends anything to the host beside its payload and clip counter
+        return self.level or self.meter
+
+
+@dataclass(frozen=True)
+class FilePlan:
+    """Everything about one job that its header and the call's arguments decide (`plan_files`); the pass derives none of it."""
+    info: Optional[tuple]            # `wavio.wav_info`'s tuple, None for a header it refuses
+    meta: tuple                      # (encoding or None, channels, rate, frames) of the input
+    how: str                         # `route`: "device" or "host"
+    n_planes: int                    # recordings the file puts into a pass, and channels of what is written
+    length: int                      # model-rate samples per plane
+    enc_o: str
+    rate_o: int
+    frames_o: int
+    ceiling: Optional[np.float32]    # `loudness.ceiling_for`: linear, capped for PCM
+    in_path: str
+    out_path: Optional[str]          # the separated target's file; None where the job's one file is the remix
+    remix_path: Optional[str]
+    db: Optional[float]              # the job's target_gain_db
+    amount: Optional[np.float32]     # `remix_coefficient(db)`
+
+
+def plan_files(jobs, dbs, o: Options, sampling_rate: int, n_fft: int, channels: str = "each", encoding: Optional[str] = None,
+               out_rate: Optional[int] = None) -> List[FilePlan]:
+    """One FilePlan per job, from the files' headers alone.  dbs: `check_remix_args`' list or None.  The output has the input's
+    frame count at the input's rate, else ceil(model-rate samples * up / down).  ValueError, with the file's name, for a file not
+    longer than the reflect padding n_fft/2 at the model rate (`longform.plan_windows`' refusal, before anything is written)."""
+    sr, plans = int(sampling_rate), []
+    for k, job in enumerate(jobs):
+        info = wavio.wav_info(job[0])
+        how = route(info, sr, out_rate, o.true_peak)
+        enc_in, nch, rate, frames = meta = info[:4] if info is not None else _host_info(job[0])
+        n_planes, length = model_samples(nch, rate, frames, sr, channels)
+        if length <= n_fft // 2:
+            raise ValueError(f"{job[0]}: a recording of {length} samples is not longer than the reflect padding "
+                             f"(n_fft/2 = {n_fft // 2})")
+        rate_o, enc_o = rate if out_rate is None else int(out_rate), encoding or enc_in or "f32"
+        plans.append(FilePlan(
+            info, meta, how, n_planes, length, enc_o, rate_o,
+            frames if rate_o == rate else rs.out_len(length, *rs.ratio(sr, rate_o)), ld.ceiling_for(o.ceiling_db, enc_o), job[0],
+            job[2] if dbs is None or len(job) == 4 else None, job[-1] if dbs is not None else None,
+            None if dbs is None else dbs[k], None if dbs is None else remix_coefficient(dbs[k])))
+    return plans
 
 
 # ---- host route -------------------------------------------------------------------------------------------------------------
@@ -367,6 +435,237 @@ def check_peak_arg(peak, peak_ceiling_db) -> None:
         raise ValueError('peak="true" needs a peak_ceiling_db')
 
 
+# ---- what travels to the host behind a payload ------------------------------------------------------------------------------
+_ITEM = {"uint8": 1, "int32": 4, "float32": 4, "float64": 8}
+_LEVEL = (("limited", "int32", 1), ("gain", "float32", 1))
+_STATS = {"max_momentary": 3, "max_short_term": 4, "loudness_range": 5}   # columns of Engine.loudness_stats' ten (STATS_COLUMNS)
+
+
+class Tail:
+    """One pinned row's layout: the encoded payload, then the file's numbers as named fields.  The fields start at the payload's
+    end rounded up to the largest item among them and each starts on a multiple of its own item size, in the order given.  The
+    only place that knows an offset: `size` is what to take from the pinned pool, `put` packs on the device's stream (one copy
+    per field), `get` unpacks once the row has arrived."""
+
+    def __init__(self, nbytes: int, fields):
+        self.nbytes, self.where = int(nbytes), {"payload": (0, int(nbytes), "uint8")}
+        widest = max(_ITEM[dtype] for _, dtype, _ in fields)
+        at = (self.nbytes + widest - 1) // widest * widest
+        for name, dtype, count in fields:
+            at = (at + _ITEM[dtype] - 1) // _ITEM[dtype] * _ITEM[dtype]
+            self.where[name] = (at, at + count * _ITEM[dtype], dtype)
+            at += count * _ITEM[dtype]
+        self.size = at
+
+    @classmethod
+    def target(cls, nbytes: int, o: Options) -> "Tail":
+        """A separated target's: the clip counter; with a level the limited flag, the gain, the true peak where one is held and
+        the loudness; the meter's ten numbers; the limiter's four."""
+        fields = [("clipped", "int32", 1)]
+        if o.level:
+            fields += _LEVEL + ((("peak", "float32", 1),) if o.true_peak else ()) + (("loudness", "float64", 1),)
+        if o.meter:
+            fields += [("stats", "float64", 10)]
+        if o.limiter:
+            fields += [("loudness_in", "float64", 1), ("limiter_gain", "float32", 1), ("min_gain", "float32", 1), ("limiter_frames", "int32", 1)]
+        return cls(nbytes, fields)
+
+    @classmethod
+    def remix(cls, nbytes: int, gained: bool) -> "Tail":
+        """A remix's: the clip counter, and under a ceiling the limited flag and the gain."""
+        return cls(nbytes, (("clipped", "int32", 1),) + (_LEVEL if gained else ()))
+
+    def __contains__(self, name: str) -> bool:
+        return name in self.where
+
+    def _view(self, buf, name: str):
+        import torch
+        lo, hi, dtype = self.where[name]
+        return buf[lo:hi].view(getattr(torch, dtype))
+
+    def put(self, buf, name: str, tensor) -> None:
+        self._view(buf, name).copy_(tensor, non_blocking=True)
+
+    def get(self, buf, name: str):
+        """The field's value: a Python number for a field of one item, else the view."""
+        v = self._view(buf, name)
+        return v[0].item() if v.numel() == 1 and name != "payload" else v
+
+    def record(self, buf, rec: dict) -> dict:
+        """rec with what the row holds beside the payload, under the record's keys."""
+        rec["clipped"] = int(self.get(buf, "clipped"))
+        gain, limited = (np.float32(self.get(buf, "gain")), bool(self.get(buf, "limited"))) if "gain" in self else (None, None)
+        if "loudness" in self:
+            rec.update(_level_record(self.get(buf, "loudness"), gain, limited, np.float32(self.get(buf, "peak")) if "peak" in self else None))
+        elif gain is not None:
+            _remix_record(rec, rec["target_gain_db"], gain, limited)
+        if "stats" in self:
+            ten = self.get(buf, "stats")
+            rec.update(_meter_record(*(float(ten[_STATS[k]]) for k in ("loudness_range", "max_momentary", "max_short_term"))))
+        if "loudness_in" in self:
+            rec.update(_limiter_record(self.get(buf, "loudness_in"), np.float32(self.get(buf, "limiter_gain")),
+                                       np.float32(self.get(buf, "min_gain")), self.get(buf, "limiter_frames")))
+        return rec
+
+
+# ---- a file's stages (DESIGN.md section 22) ---------------------------------------------------------------------------------
+class _Ctx(NamedTuple):
+    """What every stage of a call needs beside the file's plan."""
+    eng: object
+    sr: int
+    o: Options
+    clock: _Clock
+    pool: _Pinned
+    writer: ThreadPoolExecutor
+    profile: Optional[Dict[str, float]]
+
+
+def host_target(x: np.ndarray, plan: FilePlan, o: Options, sr: int) -> Tuple[np.ndarray, dict]:
+    """The host route's target: x the separated planes at the model rate -> (the samples to write, the record's entries).  The
+    device's rule with lass_amd.loudness and numpy."""
+    rec = {}
+    if o.limiter:
+        x, *lim = _host_limit(x, sr, o.loudness, plan.ceiling, o.reach, o.true_peak, o.passes)
+        rec.update(_limiter_record(*lim))
+    y = _host_resample(x, sr, plan.rate_o)[:, :plan.frames_o]
+    if o.extra:
+        p = ld.block_powers(x, sr)
+    if o.level:
+        measured = ld.gate(p)[0]
+        if o.true_peak:
+            pk = np.float32(ld.true_peak(y, plan.rate_o))
+        else:
+            pk = float(np.nanmax(np.abs(y))) if y.size else 0.0
+        g, bit = ld.gain_for(measured, pk, o.loudness, plan.ceiling)
+        y = (g * y.astype(np.float32)).astype(np.float32)
+        rec.update(_level_record(measured, g, bit, pk if o.true_peak else None))
+    if o.meter:
+        q = ld.short_term_powers(x, sr)
+        rec.update(_meter_record(ld.loudness_range(q)[0], ld.max_momentary(p), ld.max_short_term(q)))
+    rec["clipped"] = host_clip_count(y, plan.enc_o)
+    return y, rec
+
+
+def host_remix(x: np.ndarray, dry: np.ndarray, plan: FilePlan, sr: int) -> Tuple[np.ndarray, dict]:
+    """The host route's remix: x the separated planes at the model rate, dry the decoded original -> (samples, entries)."""
+    v = remix_host(dry, _host_resample(x, sr, plan.rate_o)[:, :plan.frames_o], plan.amount)
+    rec = {}
+    if plan.ceiling is not None:
+        pk = np.float32(np.nanmax(np.abs(v))) if v.size else np.float32(0.0)
+        g, bit = ld.gain_for(-np.inf, pk, None, plan.ceiling)
+        v = (g * v).astype(np.float32)
+        _remix_record(rec, plan.db, g, bit)
+    rec["clipped"] = host_clip_count(v, plan.enc_o)
+    return v, rec
+
+
+def _device_level(eng, o: Options, plan: FilePlan, sr: int, stacked):
+    """The limiter loop, the meter or the loudness, the sample or true peak, the gain -> (the planes to encode, the gain or
+    None, the tensors of `Tail.target`'s fields).  Everything stays on the device."""
+    fields, gain, pk = {}, None, None
+    if o.limiter:
+        loud_in = eng.loudness(stacked, sr)
+        lim_gain = eng.loudness_gain(loud_in, None, o.loudness, None)[0]
+        n_pass = o.passes if o.loudness is not None else 1
+        for k in range(n_pass):
+            held, lim = eng.limit(stacked, sr, lim_gain, plan.ceiling, o.reach, "true" if o.true_peak else "sample")
+            if k + 1 < n_pass:
+                lim_gain = lim_gain * eng.loudness_gain(eng.loudness(held, sr), None, o.loudness, None)[0]
+        stacked = held[0]
+        fields.update(loudness_in=loud_in, limiter_gain=lim_gain, min_gain=lim["min_gain"], limiter_frames=lim["frames"])
+    if o.meter:
+        stats = eng.loudness_stats(stacked, sr)["all"]
+        measured, fields["stats"] = stats[:, 0], stats[0]
+    else:
+        measured = eng.loudness(stacked, sr)
+    if o.ceiling_db is not None:
+        pk = (eng.resample_true_peak if o.true_peak else eng.resample_peak)(stacked, sr, plan.rate_o, frames_out=plan.frames_o)
+    if o.level:
+        gain, limited = eng.loudness_gain(measured, pk, o.loudness, plan.ceiling)
+        fields.update(limited=limited, gain=gain, loudness=measured, **({"peak": pk} if o.true_peak else {}))
+    return stacked, gain, fields
+
+
+def _device_remix_level(eng, plan: FilePlan, sr: int, stacked, dry, amount):
+    """The peak of the remix about to be quantised and the ceiling's gain alone -> (the gain, `Tail.remix`'s fields)."""
+    import torch
+    pk = eng.remix_peak(stacked, sr, plan.rate_o, dry, plan.meta[0], amount, frames_out=plan.frames_o)
+    gain, limited = eng.loudness_gain(torch.full((1,), -np.inf, dtype=torch.float64, device=eng.device), pk, None, plan.ceiling)
+    return gain, {"limited": limited, "gain": gain}
+
+
+def _send(ctx: _Ctx, plan: FilePlan, rec: dict, path: str, stacked, gain, fields: dict, dry=None, amount=None):
+    """Encode (`Engine.remix_encode` with a dry source, else `Engine.resample_encode`), copy payload and fields into a pinned row
+    and hand the row to the writer thread -> the pass's pending entry (remix?, record, tail, row, the write)."""
+    import torch
+    eng = ctx.eng
+    with ctx.clock("encode"):
+        clipped = torch.zeros(1, dtype=torch.int32, device=eng.device)
+        if dry is None:
+            payload = eng.resample_encode(stacked, ctx.sr, plan.rate_o, plan.enc_o, frames_out=plan.frames_o, clipped=clipped, gain=gain)
+        else:
+            payload = eng.remix_encode(stacked, ctx.sr, plan.rate_o, plan.enc_o, dry, plan.meta[0], amount, frames_out=plan.frames_o,
+                                       clipped=clipped, gain=gain)
+    tail = Tail.target(payload.shape[1], ctx.o) if dry is None else Tail.remix(payload.shape[1], gain is not None)
+    buf = ctx.pool.take(tail.size)
+    with ctx.clock("d2h"):
+        values = dict(payload=payload[0], clipped=clipped, **fields)
+        assert set(values) == set(tail.where), (sorted(values), sorted(tail.where))
+        for name in tail.where:
+            tail.put(buf, name, values[name])
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream(eng.device))
+    header = wavio.wav_header(plan.enc_o, plan.n_planes, plan.rate_o, plan.frames_o)
+    return dry is not None, rec, tail, buf, ctx.writer.submit(_write_device, path, header, buf, tail.nbytes, done, ctx.profile)
+
+
+def _to_host(ctx: _Ctx, mine) -> np.ndarray:
+    import torch
+    with ctx.clock("d2h"):
+        return torch.stack(mine).cpu().numpy()
+
+
+def _write_target(ctx: _Ctx, plan: FilePlan, rec: dict, mine, stacked):
+    """The separated target of one file, levelled as the call asks -> its pending entry; `rec` is complete once collected."""
+    if plan.how == "device":
+        gain, fields = None, {}
+        if ctx.o.extra:
+            with ctx.clock("level"):
+                stacked, gain, fields = _device_level(ctx.eng, ctx.o, plan, ctx.sr, stacked)
+        return _send(ctx, plan, rec, plan.out_path, stacked, gain, fields)
+    y, entries = host_target(_to_host(ctx, mine), plan, ctx.o, ctx.sr)
+    rec.update(entries)
+    return False, rec, None, None, ctx.writer.submit(_write_host, plan.out_path, plan.enc_o, y, plan.rate_o, ctx.profile)
+
+
+def _write_remix(ctx: _Ctx, plan: FilePlan, rec: dict, mine, stacked, dry, amount):
+    """The remix of one file from its separated planes and its original (`dry`: the raw row on the device, the decoded planes on
+    the host route) -> its pending entry."""
+    if plan.how == "device":
+        gain, fields = None, {}
+        if plan.ceiling is not None:
+            with ctx.clock("level"):
+                gain, fields = _device_remix_level(ctx.eng, plan, ctx.sr, stacked, dry, amount)
+        return _send(ctx, plan, rec, plan.remix_path, stacked, gain, fields, dry, amount)
+    v, entries = host_remix(_to_host(ctx, mine), dry, plan, ctx.sr)
+    rec.update(entries)
+    return True, rec, None, None, ctx.writer.submit(_write_host, plan.remix_path, plan.enc_o, v, plan.rate_o, ctx.profile)
+
+
+def _collect(pending, pool: _Pinned) -> None:
+    """Wait for every file of the pass, the targets first, and read each device row's numbers into its record before the row
+    goes back to the pool."""
+    for _, rec, tail, buf, fut in sorted(pending, key=lambda entry: entry[0]):
+        fut.result()
+        if buf is not None:
+            tail.record(buf, rec)
+            pool.give(buf)
+
+
+def _submit_reads(reader, plans, ids, channels: str, pool: _Pinned, profile):
+    return [reader.submit(_read_job, plans[i].in_path, plans[i].info, plans[i].how, channels, pool, profile) for i in ids]
+
+
 def separate_files(model, jobs, sampling_rate: int, channels: str = "each", encoding: Optional[str] = None,
                    out_rate: Optional[int] = None, window: int = 160000, context: int = 16000, fade: int = 0,
                    fade_shape: str = "linear", max_batch: int = 16, max_samples: int = DEFAULT_MAX_SAMPLES,
@@ -426,94 +725,33 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
     ld.check_level_args(loudness, peak_ceiling_db)
     check_peak_arg(peak, peak_ceiling_db)
     check_limiter_args(limiter, limiter_lookahead_ms, limiter_passes, peak_ceiling_db, int(sampling_rate))
-    limiter = bool(limiter)
-    reach = ld.reach(limiter_lookahead_ms, int(sampling_rate)) if limiter else 0
-    level = loudness is not None or peak_ceiling_db is not None
-    true_peak, meter = peak == "true", bool(meter)
-    extra = level or meter               # whether anything travels behind the payload beside the clip counter
     jobs = [tuple(j) for j in jobs]
-    dbs = check_remix_args(target_gain_db, jobs, channels, out_rate, loudness, meter, limiter, peak)
+    dbs = check_remix_args(target_gain_db, jobs, channels, out_rate, loudness, bool(meter), bool(limiter), peak)
+    o = Options(loudness, peak_ceiling_db, peak == "true", bool(meter), bool(limiter),
+                ld.reach(limiter_lookahead_ms, int(sampling_rate)) if limiter else 0, int(limiter_passes) if limiter else 0, dbs is not None)
     ss = model.ss_model
     eng = ss.engine
     dev, sr = eng.device, int(sampling_rate)
-
-    # plan: header, route and size of every job
-    infos, hows, sizes = [], [], []
-    for in_path in (j[0] for j in jobs):
-        info = wavio.wav_info(in_path)
-        how = route(info, sr, out_rate, true_peak)
-        meta = info[:4] if info is not None else _host_info(in_path)
-        n_planes, length = model_samples(meta[1], meta[2], meta[3], sr, channels)
-        if length <= eng.n_fft // 2:   # longform.plan_windows' refusal, with the file's name, before anything is written
-            raise ValueError(f"{in_path}: a recording of {length} samples is not longer than the reflect padding "
-                             f"(n_fft/2 = {eng.n_fft // 2})")
-        infos.append((info, meta))
-        hows.append(how)
-        sizes.append(n_planes * length)
+    plans = plan_files(jobs, dbs, o, sr, eng.n_fft, channels, encoding, out_rate)
 
     clock, pool = _Clock(profile, dev), _Pinned()
     records: List[Optional[dict]] = [None] * len(jobs)
-    passes = plan_passes(sizes, max_samples)
+    passes = plan_passes([p.n_planes * p.length for p in plans], max_samples)
     with ThreadPoolExecutor(1) as reader, ThreadPoolExecutor(1) as writer:
-        def submit_reads(ids):
-            return [reader.submit(_read_job, jobs[i][0], infos[i][0], hows[i], channels, pool, profile) for i in ids]
-
-        def write_remix(i, rec, mine, stacked, dry, amount):
-            """Job i's remix from its separated planes (`mine`, `stacked` on the device route) and its original (`dry`: the raw
-            row on the device, the decoded planes on the host route), written to the job's last path; -> its record, which is
-            complete once the pass's files are on disk."""
-            enc_in, rate, frames = infos[i][1][0], infos[i][1][2], infos[i][1][3]
-            enc_o, path_out = encoding or enc_in or "f32", jobs[i][-1]
-            rec = _remix_record(dict(rec), dbs[i])
-            ceiling = ld.ceiling_for(peak_ceiling_db, enc_o)
-            if hows[i] == "device":
-                gain = limited = None
-                if ceiling is not None:
-                    with clock("level"):
-                        pk = eng.remix_peak(stacked, sr, rate, dry, enc_in, amount, frames_out=frames)
-                        gain, limited = eng.loudness_gain(torch.full((1,), -np.inf, dtype=torch.float64, device=dev), pk, None, ceiling)
-                with clock("encode"):
-                    clipped = torch.zeros(1, dtype=torch.int32, device=dev)
-                    payload = eng.remix_encode(stacked, sr, rate, enc_o, dry, enc_in, amount, frames_out=frames, clipped=clipped, gain=gain)
-                nbytes = payload.shape[1]
-                tail = (nbytes + 3) // 4 * 4                   # clip counter, limited flag and gain travel behind the payload
-                buf = pool.take(tail + 12)
-                with clock("d2h"):
-                    buf[:nbytes].copy_(payload[0], non_blocking=True)
-                    buf[tail:tail + 4].view(torch.int32).copy_(clipped, non_blocking=True)
-                    if gain is not None:
-                        buf[tail + 4:tail + 8].view(torch.int32).copy_(limited, non_blocking=True)
-                        buf[tail + 8:tail + 12].view(torch.float32).copy_(gain, non_blocking=True)
-                    done = torch.cuda.Event()
-                    done.record(torch.cuda.current_stream(dev))
-                remixed.append((rec, buf, tail, gain is not None, writer.submit(
-                    _write_device, path_out, wavio.wav_header(enc_o, len(mine), rate, frames), buf, nbytes, done, profile)))
-            else:
-                with clock("d2h"):
-                    x = torch.stack(mine).cpu().numpy()
-                v = remix_host(dry, _host_resample(x, sr, rate)[:, :frames], remix_coefficient(dbs[i]))
-                if ceiling is not None:                        # the device's rule with numpy and loudness.gain_for
-                    pk = np.float32(np.nanmax(np.abs(v))) if v.size else np.float32(0.0)
-                    g, bit = ld.gain_for(-np.inf, pk, None, ceiling)
-                    v = (g * v).astype(np.float32)
-                    _remix_record(rec, dbs[i], g, bit)
-                rec["clipped"] = host_clip_count(v, enc_o)
-                remixed.append((rec, None, 0, False, writer.submit(_write_host, path_out, enc_o, v, rate, profile)))
-            return rec
-
-        written, uploaded, remixed = [], [], []
-        reads = submit_reads(passes[0]) if passes else []
+        ctx = _Ctx(eng, sr, o, clock, pool, writer, profile)
+        reads = _submit_reads(reader, plans, passes[0], channels, pool, profile) if passes else []
         for pi, ids in enumerate(passes):
-            ahead = submit_reads(passes[pi + 1]) if pi + 1 < len(passes) else []   # the next pass is read while this one runs
+            # the next pass is read while this one runs
+            ahead = _submit_reads(reader, plans, passes[pi + 1], channels, pool, profile) if pi + 1 < len(passes) else []
             captions, cap_of = dedup_captions([jobs[i][1] for i in ids])
             emb = (model.query_encoder.get_query_embed(modality="text", text=captions, device=dev).to(torch.float32)
                    if captions else None)
-            planes, conds, counts, dry = [], [], [], {}
-            amounts = None if dbs is None else torch.tensor([float(remix_coefficient(dbs[i])) for i in ids], dtype=torch.float32).to(dev)
+            planes, conds, uploaded, dry, pending = [], [], [], {}, []
+            amounts = torch.tensor([float(plans[i].amount) for i in ids], dtype=torch.float32).to(dev) if o.remix else None
             for k, (i, fut) in enumerate(zip(ids, reads)):
-                (info, meta), got = infos[i], fut.result()
-                enc_in, nch, rate, frames = meta
-                if hows[i] == "device":
+                plan, got = plans[i], fut.result()
+                enc_in, nch, rate, frames = plan.meta
+                if plan.how == "device":
                     nbytes = frames * nch * rs.SAMPLE_BYTES[enc_in]
                     with clock("h2d"):
                         raw = got[None, :(nbytes + 3) // 4 * 4].to(dev, non_blocking=True)
@@ -523,150 +761,43 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
                         else:
                             mine = [eng.decode_resample(raw, frames, nch, enc_in, rate, sr)[0]]
                     uploaded.append(got)
-                    if dbs is not None:
-                        dry[i] = raw                       # kept until the file's encode: the remix's dry source
                 else:
                     mine = [torch.from_numpy(p).to(dev) for p in _host_resample(got, rate, sr)]
-                    if dbs is not None:
-                        dry[i] = got
+                if o.remix:
+                    dry[i] = raw if plan.how == "device" else got   # kept until the file's encode: the remix's dry source
                 cond = emb[cap_of[k]] if cap_of[k] is not None else torch.as_tensor(jobs[i][1]).to(device=dev, dtype=torch.float32).reshape(-1)
                 planes += mine
                 conds += [cond] * len(mine)
-                counts.append(len(mine))
             with clock("separate"):
                 seps = ss.separate_long_list(planes, torch.stack(conds), window=window, context=context, max_batch=max_batch,
                                              fade=fade, fade_shape=fade_shape)
             at = 0
-            for j, (i, n) in enumerate(zip(ids, counts)):
-                (info, meta), mine = infos[i], seps[at:at + n]
-                at += n
-                enc_in, nch, rate, frames = meta
-                rate_o = rate if out_rate is None else int(out_rate)
-                enc_o = encoding or enc_in or "f32"
-                L = int(mine[0].shape[0])
-                frames_o = frames if rate_o == rate else rs.out_len(L, *rs.ratio(sr, rate_o))
-                rec = {"rate": rate_o, "channels": n, "frames": frames_o, "path": hows[i]}
-                stacked = torch.stack(mine) if hows[i] == "device" else None
-                if dbs is not None:
-                    remix = write_remix(i, rec, mine, stacked, dry.pop(i), amounts[j:j + 1])
-                    if len(jobs[i]) == 3:                          # the remix is the job's one file
+            for j, i in enumerate(ids):
+                plan, mine = plans[i], seps[at:at + plans[i].n_planes]
+                at += plan.n_planes
+                if any(int(m.shape[0]) != plan.length for m in mine):
+                    raise RuntimeError(f"{plan.in_path}: separated planes of {[int(m.shape[0]) for m in mine]} samples, planned {plan.length}")
+                rec = {"rate": plan.rate_o, "channels": plan.n_planes, "frames": plan.frames_o, "path": plan.how}
+                stacked = torch.stack(mine) if plan.how == "device" else None
+                if o.remix:
+                    remix = _remix_record(dict(rec), plan.db)
+                    pending.append(_write_remix(ctx, plan, remix, mine, stacked, dry.pop(i), amounts[j:j + 1]))
+                    if plan.out_path is None:                      # the remix is the job's one file
                         records[i] = remix
                         continue
                     rec["remix"] = remix                           # ... or goes beside the target, which is written as ever
-                if hows[i] == "device":
-                    gain, pk, stats = None, None, None
-                    if extra:
-                        with clock("level"):
-                            if limiter:
-                                loud_in = eng.loudness(stacked, sr)
-                                lim_gain = eng.loudness_gain(loud_in, None, loudness, None)[0]
-                                n_pass = int(limiter_passes) if loudness is not None else 1
-                                for k in range(n_pass):
-                                    held, lim = eng.limit(stacked, sr, lim_gain, ld.ceiling_for(peak_ceiling_db, enc_o), reach, peak)
-                                    if k + 1 < n_pass:
-                                        lim_gain = lim_gain * eng.loudness_gain(eng.loudness(held, sr), None, loudness, None)[0]
-                                stacked = held[0]
-                            if meter:
-                                stats = eng.loudness_stats(stacked, sr)["all"]
-                                measured = stats[:, 0]
-                            else:
-                                measured = eng.loudness(stacked, sr)
-                            if peak_ceiling_db is not None:
-                                pk = (eng.resample_true_peak if true_peak else eng.resample_peak)(stacked, sr, rate_o, frames_out=frames_o)
-                            if level:
-                                gain, limited = eng.loudness_gain(measured, pk, loudness, ld.ceiling_for(peak_ceiling_db, enc_o))
-                    with clock("encode"):
-                        clipped = torch.zeros(1, dtype=torch.int32, device=dev)
-                        payload = eng.resample_encode(stacked, sr, rate_o, enc_o, frames_out=frames_o, clipped=clipped, gain=gain)
-                    nbytes = payload.shape[1]
-                    tail = (nbytes + 7) // 8 * 8 if extra else (nbytes + 3) // 4 * 4   # the clip counter travels behind the payload
-                    lim_at = tail + 24 + (80 if meter else 0)       # the limiter's four numbers come last
-                    buf = pool.take(tail + (24 if extra else 4) + (80 if meter else 0) + (24 if limiter else 0))
-                    with clock("d2h"):
-                        buf[:nbytes].copy_(payload[0], non_blocking=True)
-                        buf[tail:tail + 4].view(torch.int32).copy_(clipped, non_blocking=True)
-                        if level:                                  # ... and with it the file's limited flag, gain and loudness
-                            buf[tail + 4:tail + 8].view(torch.int32).copy_(limited, non_blocking=True)
-                            buf[tail + 8:tail + 12].view(torch.float32).copy_(gain, non_blocking=True)
-                            buf[tail + 16:tail + 24].view(torch.float64).copy_(measured, non_blocking=True)
-                            if true_peak:
-                                buf[tail + 12:tail + 16].view(torch.float32).copy_(pk, non_blocking=True)
-                        if meter:                                  # ... and the ten numbers of Engine.loudness_stats
-                            buf[tail + 24:tail + 104].view(torch.float64).copy_(stats[0], non_blocking=True)
-                        if limiter:
-                            buf[lim_at:lim_at + 8].view(torch.float64).copy_(loud_in, non_blocking=True)
-                            buf[lim_at + 8:lim_at + 12].view(torch.float32).copy_(lim_gain, non_blocking=True)
-                            buf[lim_at + 12:lim_at + 16].view(torch.float32).copy_(lim["min_gain"], non_blocking=True)
-                            buf[lim_at + 16:lim_at + 20].view(torch.int32).copy_(lim["frames"], non_blocking=True)
-                        done = torch.cuda.Event()
-                        done.record(torch.cuda.current_stream(dev))
-                    written.append((i, buf, (tail, lim_at), writer.submit(_write_device, jobs[i][2], wavio.wav_header(enc_o, n, rate_o, frames_o),
-                                                                buf, nbytes, done, profile)))
-                else:
-                    with clock("d2h"):
-                        x = torch.stack(mine).cpu().numpy()
-                    if limiter:
-                        x, *lim = _host_limit(x, sr, loudness, ld.ceiling_for(peak_ceiling_db, enc_o), reach, true_peak,
-                                              int(limiter_passes))
-                        rec.update(_limiter_record(*lim))
-                    y = _host_resample(x, sr, rate_o)[:, :frames_o]
-                    if extra:                                      # the device's rule with lass_amd.loudness and numpy
-                        p = ld.block_powers(x, sr)
-                    if level:
-                        measured = ld.gate(p)[0]
-                        if true_peak:
-                            pk = np.float32(ld.true_peak(y, rate_o))
-                        else:
-                            pk = float(np.nanmax(np.abs(y))) if y.size else 0.0
-                        g, bit = ld.gain_for(measured, pk, loudness, ld.ceiling_for(peak_ceiling_db, enc_o))
-                        y = (g * y.astype(np.float32)).astype(np.float32)
-                        rec.update(_level_record(measured, g, bit, pk if true_peak else None))
-                    if meter:
-                        q = ld.short_term_powers(x, sr)
-                        rec.update(_meter_record(ld.loudness_range(q)[0], ld.max_momentary(p), ld.max_short_term(q)))
-                    rec["clipped"] = host_clip_count(y, enc_o)
-                    written.append((i, None, (0, 0), writer.submit(_write_host, jobs[i][2], enc_o, y, rate_o, profile)))
+                pending.append(_write_target(ctx, plan, rec, mine, stacked))
                 records[i] = rec
             reads = ahead
-            # the pass's files are on disk (so its uploads are long done) and its counters read before its pinned rows go back
-            for i, buf, (tail, lim_at), fut in written:
-                fut.result()
-                if buf is not None:
-                    records[i]["clipped"] = int(buf[tail:tail + 4].view(torch.int32)[0])
-                    if level:
-                        records[i].update(_level_record(float(buf[tail + 16:tail + 24].view(torch.float64)[0]),
-                                                        np.float32(buf[tail + 8:tail + 12].view(torch.float32)[0].item()),
-                                                        bool(buf[tail + 4:tail + 8].view(torch.int32)[0]),
-                                                        np.float32(buf[tail + 12:tail + 16].view(torch.float32)[0].item()) if true_peak else None))
-                    if meter:
-                        ten = buf[tail + 24:tail + 104].view(torch.float64)
-                        records[i].update(_meter_record(float(ten[5]), float(ten[3]), float(ten[4])))
-                    if limiter:
-                        records[i].update(_limiter_record(float(buf[lim_at:lim_at + 8].view(torch.float64)[0]),
-                                                          np.float32(buf[lim_at + 8:lim_at + 12].view(torch.float32)[0].item()),
-                                                          np.float32(buf[lim_at + 12:lim_at + 16].view(torch.float32)[0].item()),
-                                                          int(buf[lim_at + 16:lim_at + 20].view(torch.int32)[0])))
-                    pool.give(buf)
-            for rec, buf, tail, gained, fut in remixed:
-                fut.result()
-                if buf is not None:
-                    rec["clipped"] = int(buf[tail:tail + 4].view(torch.int32)[0])
-                    if gained:
-                        _remix_record(rec, rec["target_gain_db"], np.float32(buf[tail + 8:tail + 12].view(torch.float32)[0].item()),
-                                      bool(buf[tail + 4:tail + 8].view(torch.int32)[0]))
-                    pool.give(buf)
+            # the pass's files are on disk (so its uploads are long done) and its numbers read before its pinned rows go back
+            _collect(pending, pool)
             for buf in uploaded:
                 pool.give(buf)
-            written, uploaded, remixed = [], [], []
     return records
 
 
-def inference(model, audio_file: str, text, output_file: str, sampling_rate: int = 32000, loudness: Optional[float] = None,
-              peak_ceiling_db: Optional[float] = None, peak: str = "sample", meter: bool = False, limiter: bool = False,
-              limiter_lookahead_ms: float = 1.5, limiter_passes: int = 2, target_gain_db=None, **kw) -> dict:
+def inference(model, audio_file: str, text, output_file: str, sampling_rate: int = 32000, **kw) -> dict:
     """One file through `separate_files`: the single-file shape of upstream AudioSep's `pipeline.inference`.  loudness, peak_ceiling_db,
     peak, meter, limiter, limiter_lookahead_ms, limiter_passes, target_gain_db (with which `output_file` is the remix) and the other
     keywords are `separate_files`'s.  Returns the job's record."""
-    return separate_files(model, [(audio_file, text, output_file)], sampling_rate, loudness=loudness, peak_ceiling_db=peak_ceiling_db,
-                          peak=peak, meter=meter, limiter=limiter, limiter_lookahead_ms=limiter_lookahead_ms,
-                          limiter_passes=limiter_passes, target_gain_db=target_gain_db, **kw)[0]
+    return separate_files(model, [(audio_file, text, output_file)], sampling_rate, **kw)[0]

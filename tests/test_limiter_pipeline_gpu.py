@@ -23,6 +23,7 @@ KW = dict(loudness=TARGET, peak_ceiling_db=CEILING_DB, peak="true")
 CAPS = ["a dog barking", "a door slamming", "a bell"]
 LEVEL_KEYS = ["rate", "channels", "frames", "path", "clipped", "loudness_out", "gain", "gain_db", "peak_limited", "true_peak_db"]
 LIMITER_KEYS = ["loudness_in", "limiter_gain_db", "limiter_reduction_db", "limiter_frames"]
+METER_KEYS = ["loudness_range", "max_momentary", "max_short_term"]
 SHAPES = [("pcm16", 1, 16000, 32000), ("pcm16", 2, 44100, 88200), ("pcm16", 2, 44101, 88202)]
 
 
@@ -86,18 +87,19 @@ def true_peak_bound(ceiling, enc, rate):
 
 @pytest.fixture(scope="module")
 def runs(holder, files):
-    """The same jobs four times: the separated planes (a float32 export at the model rate), with the limiter, with limiter=False
-    and without the argument."""
+    """The same jobs five times: the separated planes (a float32 export at the model rate), with the limiter, with the limiter and
+    the meter, with limiter=False and without the argument."""
     d, paths = files
-    model, lim, off, bare = ([str(d / f"{name}{k}.wav") for k in range(3)] for name in ("model", "lim", "off", "bare"))
+    model, lim, met, off, bare = ([str(d / f"{name}{k}.wav") for k in range(3)] for name in ("model", "lim", "met", "off", "bare"))
     import warnings
     with warnings.catch_warnings():
         warnings.filterwarnings("ignore", message=".*parity with the reference is unpinned.*", category=UserWarning)
         pipeline.separate_files(holder, list(zip(paths, CAPS, model)), SR, encoding="f32", out_rate=SR)
         recs = pipeline.separate_files(holder, list(zip(paths, CAPS, lim)), SR, limiter=True, **KW)
+        recs_met = pipeline.separate_files(holder, list(zip(paths, CAPS, met)), SR, limiter=True, meter=True, **KW)
         recs_off = pipeline.separate_files(holder, list(zip(paths, CAPS, off)), SR, limiter=False, **KW)
         recs_bare = pipeline.separate_files(holder, list(zip(paths, CAPS, bare)), SR, **KW)
-    return dict(model=model, lim=lim, off=off, bare=bare, recs=recs, recs_off=recs_off, recs_bare=recs_bare)
+    return dict(model=model, lim=lim, met=met, off=off, bare=bare, recs=recs, recs_met=recs_met, recs_off=recs_off, recs_bare=recs_bare)
 
 
 def test_records_and_ceiling(runs):
@@ -118,33 +120,22 @@ def test_records_and_ceiling(runs):
         assert tp <= true_peak_bound(ceiling, enc, rate)
 
 
-def test_device_files_are_the_public_pieces_by_hand(eng, runs):
-    for k, (enc, nch, rate, frames) in enumerate(SHAPES[:2]):
-        rec = runs["recs"][k]
-        x = torch.from_numpy(np.frombuffer(_payload(runs["model"][k]), dtype="<f4").reshape(-1, nch).T.copy()).to(DEV)
-        ceiling, H = ld.ceiling_for(CEILING_DB, enc), ld.reach(1.5, SR)
-        loud_in = eng.loudness(x, SR)
-        g = eng.loudness_gain(loud_in, None, TARGET, None)[0]
-        v, info = eng.limit(x, SR, g, ceiling, H, "true")
-        g = g * eng.loudness_gain(eng.loudness(v, SR), None, TARGET, None)[0]
-        v, info = eng.limit(x, SR, g, ceiling, H, "true")
-        measured = eng.loudness(v[0], SR)
-        pk = eng.resample_true_peak(v[0], SR, rate, frames_out=frames)
-        trim, bit = eng.loudness_gain(measured, pk, TARGET, ceiling)
-        clipped = torch.zeros(1, dtype=torch.int32, device=DEV)
-        payload = eng.resample_encode(v[0], SR, rate, enc, frames_out=frames, clipped=clipped, gain=trim)
-        assert bytes(payload[0].cpu().numpy()) == _payload(runs["lim"][k]), k
-        assert int(clipped[0]) == 0 == rec["clipped"]
-        assert rec["loudness_in"] == float(loud_in[0]) and rec["loudness_out"] == float(measured[0])
-        assert rec["gain"] == float(trim[0]) and rec["peak_limited"] == bool(bit[0])
-        assert rec["limiter_gain_db"] == 20.0 * np.log10(np.float64(np.float32(g[0].item())))
-        assert rec["limiter_reduction_db"] == 20.0 * np.log10(np.float64(np.float32(info["min_gain"][0].item())))
-        assert rec["limiter_frames"] == int(info["frames"][0])
+def _device_by_hand(eng, runs, k):
+    """File k's separated planes through the public pieces: (limited planes, loudness in, the last pass's gain, its info)."""
+    enc, nch, rate, frames = SHAPES[k]
+    x = torch.from_numpy(np.frombuffer(_payload(runs["model"][k]), dtype="<f4").reshape(-1, nch).T.copy()).to(DEV)
+    ceiling, H = ld.ceiling_for(CEILING_DB, enc), ld.reach(1.5, SR)
+    loud_in = eng.loudness(x, SR)
+    g = eng.loudness_gain(loud_in, None, TARGET, None)[0]
+    v, info = eng.limit(x, SR, g, ceiling, H, "true")
+    g = g * eng.loudness_gain(eng.loudness(v, SR), None, TARGET, None)[0]
+    v, info = eng.limit(x, SR, g, ceiling, H, "true")
+    return v[0], loud_in, g, info
 
 
-def test_host_route_runs_the_definition(runs):
+def _host_by_hand(runs):
+    """The host file's separated planes through `lass_amd.loudness`: (limited planes, loudness in, gain, curve, envelope)."""
     enc, nch, rate, frames = SHAPES[2]
-    rec = runs["recs"][2]
     x = np.frombuffer(_payload(runs["model"][2]), dtype="<f4").reshape(-1, nch).T
     ceiling, H = ld.ceiling_for(CEILING_DB, enc), ld.reach(1.5, SR)
     l_in = ld.integrated_loudness(x, SR)
@@ -152,10 +143,61 @@ def test_host_route_runs_the_definition(runs):
     v = ld.limit(x, SR, g, ceiling, H)[0].astype(np.float32)
     g = np.float32(g * ld.gain_for(ld.integrated_loudness(v, SR), None, TARGET, None)[0])
     v, G, e = ld.limit(x, SR, g, ceiling, H)
-    v = v.astype(np.float32)
+    return v.astype(np.float32), l_in, g, G, e
+
+
+def _limiter_values_by_hand(rec, loud_in, g, info):
+    assert rec["loudness_in"] == float(loud_in[0])
+    assert rec["limiter_gain_db"] == 20.0 * np.log10(np.float64(np.float32(g[0].item())))
+    assert rec["limiter_reduction_db"] == 20.0 * np.log10(np.float64(np.float32(info["min_gain"][0].item())))
+    assert rec["limiter_frames"] == int(info["frames"][0])
+
+
+def test_device_files_are_the_public_pieces_by_hand(eng, runs):
+    for k, (enc, nch, rate, frames) in enumerate(SHAPES[:2]):
+        rec = runs["recs"][k]
+        v, loud_in, g, info = _device_by_hand(eng, runs, k)
+        ceiling = ld.ceiling_for(CEILING_DB, enc)
+        measured = eng.loudness(v, SR)
+        pk = eng.resample_true_peak(v, SR, rate, frames_out=frames)
+        trim, bit = eng.loudness_gain(measured, pk, TARGET, ceiling)
+        clipped = torch.zeros(1, dtype=torch.int32, device=DEV)
+        payload = eng.resample_encode(v, SR, rate, enc, frames_out=frames, clipped=clipped, gain=trim)
+        assert bytes(payload[0].cpu().numpy()) == _payload(runs["lim"][k]), k
+        assert int(clipped[0]) == 0 == rec["clipped"]
+        assert rec["loudness_out"] == float(measured[0])
+        assert rec["gain"] == float(trim[0]) and rec["peak_limited"] == bool(bit[0])
+        _limiter_values_by_hand(rec, loud_in, g, info)
+
+
+def test_host_route_runs_the_definition(runs):
+    enc, nch, rate, frames = SHAPES[2]
+    rec = runs["recs"][2]
+    ceiling, H = ld.ceiling_for(CEILING_DB, enc), ld.reach(1.5, SR)
+    v, l_in, g, G, e = _host_by_hand(runs)
     assert rec["loudness_in"] == l_in and rec["loudness_out"] == ld.integrated_loudness(v, SR)
     assert rec["limiter_gain_db"] == 20.0 * np.log10(np.float64(g)) and rec["limiter_reduction_db"] == 20.0 * np.log10(G.min())
     assert rec["limiter_frames"] == int(np.count_nonzero(ld.limiter_curve(e, g, ceiling, H)[2] < 1.0))
+
+
+def test_meter_beside_the_limiter(eng, runs):
+    """limiter=True with meter=True, the largest set of numbers a file sends to the host behind its payload: the meter writes
+    nothing into a file, each record is the limiter run's plus the three meter figures, and those are the figures of the LIMITED
+    planes - `Engine.loudness_stats` of them by hand on the device files, `lass_amd.loudness` on the host file."""
+    for k in range(3):
+        rec, met = runs["recs"][k], runs["recs_met"][k]
+        assert _payload(runs["met"][k]) == _payload(runs["lim"][k]), k
+        assert sorted(met) == sorted(LEVEL_KEYS + LIMITER_KEYS + METER_KEYS), met
+        assert {key: val for key, val in met.items() if key not in METER_KEYS} == rec
+    for k in range(2):
+        met = runs["recs_met"][k]
+        v, loud_in, g, info = _device_by_hand(eng, runs, k)
+        ten = dict(zip(eng.STATS_COLUMNS, eng.loudness_stats(v, SR)["all"][0].tolist()))
+        assert [met[key] for key in METER_KEYS] == [ten[key] for key in METER_KEYS], (k, met, ten)
+        _limiter_values_by_hand(met, loud_in, g, info)
+    v = _host_by_hand(runs)[0]
+    p, q = ld.block_powers(v, SR), ld.short_term_powers(v, SR)
+    assert [runs["recs_met"][2][key] for key in METER_KEYS] == [ld.loudness_range(q)[0], ld.max_momentary(p), ld.max_short_term(q)]
 
 
 def test_limiter_brings_device_files_closer_to_the_target(runs):
