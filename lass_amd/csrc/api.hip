@@ -1327,295 +1327,150 @@ int lass_mix_at_snr(lass_ctx* c, float* source, const float* noise, const float*
     return 0;
 }
 
-// What lass_decode_resample asks of encoding, channels, up, down and the filter, for the entry points that share its limits
-// (w: the caller's "name: ").  0, or LASS_ERR_ARG with the message set.
-static int check_resample_args(lass_ctx* c, const char* w, int channels, int encoding, int up, int down, const float* taps,
-                               int n_taps) {
-    if (encoding != LASS_WAV_PCM16 && encoding != LASS_WAV_PCM32 && encoding != LASS_WAV_F32)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "encoding must be LASS_WAV_PCM16, LASS_WAV_PCM32 or LASS_WAV_F32");
-    if (channels < 1 || channels > 8) return fail(c, LASS_ERR_ARG, std::string(w) + "1 ... 8 channels");
-    if (up < 1 || down < 1 || up > LASS_RESAMPLE_MAX_RATIO || down > LASS_RESAMPLE_MAX_RATIO)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "up and down must lie in 1 ... " + std::to_string(LASS_RESAMPLE_MAX_RATIO));
-    if (up != 1 || down != 1) {
-        if (!taps || n_taps < 1 || n_taps % 2 == 0) return fail(c, LASS_ERR_ARG, std::string(w) + "taps non-NULL, n_taps odd");
-        if (n_taps > LASS_RESAMPLE_MAX_TAPS)
-            return fail(c, LASS_ERR_ARG, std::string(w) + std::to_string(n_taps) + " taps exceed the cap of " +
-                        std::to_string(LASS_RESAMPLE_MAX_TAPS) + " (resample on the host)");
-        if (lass_resample_table_floats(up, n_taps) > LASS_RESAMPLE_MAX_TABLE)
-            return fail(c, LASS_ERR_ARG, std::string(w) + "the polyphase table up * (ceil(n_taps/up) | 1) exceeds " +
-                        std::to_string(LASS_RESAMPLE_MAX_TABLE) + " floats");
-    }
-    return 0;
-}
+// ---- the audio file entry points ------------------------------------------------------------------------------------------------
+// Each builds audio_args.h's operand structs from its positional arguments, runs its ordered list of checks there (plus, where it
+// has one, the refusal that reads device-side constants, last as ever), selects the device and launches.
+static int refuse(lass_ctx* c, const std::string& message) { return message.empty() ? 0 : fail(c, LASS_ERR_ARG, message); }
 
-// The two decode entries: one checked body (w: the entry's "name: "; planar: one output plane per channel, no down-mix).
-static int decode_resample(lass_ctx* c, const char* w, const void* raw, int64_t row_stride_bytes, int B, int frames, int channels,
-                           int encoding, int up, int down, const float* taps, int n_taps, bool planar, float* out, int L_out,
-                           void* stream) {
+// The two decode entries (planar: one output plane per channel, no down-mix).
+static int decode_resample(lass_ctx* c, const char* w, const PayloadRows& raw, int B, const RationalFilter& F, bool planar, float* out,
+                           int L_out, void* stream) {
     if (!c) return LASS_ERR_ARG;
-    if (!raw || !out || B <= 0 || B > 65535 || frames <= 0) return fail(c, LASS_ERR_ARG, std::string(w) + "raw, out non-NULL, 1 <= B <= 65535, frames >= 1");
-    if (int r = check_resample_args(c, w, channels, encoding, up, down, taps, n_taps)) return r;
-    const long long want = ((long long)frames * up + down - 1) / down;
-    if (L_out <= 0 || want != (long long)L_out)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "L_out must be ceil(frames*up/down) = " + std::to_string(want));
-    const long long row_bytes = (long long)frames * channels * (encoding == LASS_WAV_PCM16 ? 2 : 4);
-    if (row_stride_bytes < row_bytes || row_stride_bytes % 4 != 0)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "row_stride_bytes must be a multiple of 4 and hold a row (" +
-                    std::to_string(row_bytes) + " bytes)");
-    if (reinterpret_cast<uintptr_t>(raw) % 4 != 0) return fail(c, LASS_ERR_ARG, std::string(w) + "raw must be 4-byte aligned");
+    if (int r = refuse(c, check_decode(w, raw, B, F, out, L_out))) return r;
     if (int r = use_device(c)) return r;
-    HIP_TRY(c, lass_launch_decode_resample(raw, row_stride_bytes, B, frames, channels, encoding, up, down, taps, n_taps, planar, out,
-                                           L_out, (hipStream_t)stream));
+    HIP_TRY(c, lass_launch_decode_resample(raw, B, F, planar, out, L_out, (hipStream_t)stream));
     return 0;
 }
 
 int lass_decode_resample(lass_ctx* c, const void* raw, int64_t row_stride_bytes, int B, int frames, int channels, int encoding,
                          int up, int down, const float* taps, int n_taps, float* out, int L_out, void* stream) {
-    return decode_resample(c, "lass_decode_resample: ", raw, row_stride_bytes, B, frames, channels, encoding, up, down, taps, n_taps,
+    return decode_resample(c, "lass_decode_resample: ", {raw, row_stride_bytes, encoding, frames, channels}, B, {up, down, taps, n_taps},
                            false, out, L_out, stream);
 }
 
 int lass_decode_resample_planar(lass_ctx* c, const void* raw, int64_t row_stride_bytes, int B, int frames, int channels,
                                 int encoding, int up, int down, const float* taps, int n_taps, float* out, int L_out, void* stream) {
-    return decode_resample(c, "lass_decode_resample_planar: ", raw, row_stride_bytes, B, frames, channels, encoding, up, down, taps,
-                           n_taps, true, out, L_out, stream);
+    return decode_resample(c, "lass_decode_resample_planar: ", {raw, row_stride_bytes, encoding, frames, channels}, B,
+                           {up, down, taps, n_taps}, true, out, L_out, stream);
 }
 
-// What the export entries ask of the planes and frames_out, after check_resample_args (w: the entry's "name: ").
-static int check_export_planes(lass_ctx* c, const char* w, const float* planes, int64_t row_stride, int64_t plane_stride, int channels,
-                               int L_in, int up, int down, int frames_out) {
-    const long long ceiling = ((long long)L_in * up + down - 1) / down;
-    if (frames_out < 1 || (long long)frames_out > ceiling)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "frames_out must lie in 1 ... ceil(L_in*up/down) = " + std::to_string(ceiling));
-    const long long row_floats = (long long)(channels - 1) * plane_stride + L_in;
-    if (plane_stride < L_in || row_stride < row_floats)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "plane_stride must hold a plane (" + std::to_string(L_in) +
-                    " floats) and row_stride a recording (" + std::to_string(row_floats) + " floats)");
-    return 0;
-}
-
-// The two encode entries: one checked body (gain NULL: lass_resample_encode).
-static int resample_encode(lass_ctx* c, const char* w, const float* planes, int64_t row_stride, int64_t plane_stride, int B,
-                           int channels, int L_in, int up, int down, const float* taps, int n_taps, int encoding, void* out_bytes,
-                           int64_t out_row_stride_bytes, int frames_out, unsigned* clipped, const float* gain, void* stream) {
+// The three encode entries (dry NULL: no remix; gain_required: lass_resample_encode_gain).
+static int encode(lass_ctx* c, const char* w, const PlaneRows& P, const RationalFilter& F, const DrySource* dry, const float* gain,
+                  bool gain_required, const PayloadRows& out, unsigned* clipped, void* stream) {
     if (!c) return LASS_ERR_ARG;
-    if (!planes || !out_bytes || B <= 0 || B > 65535 || L_in <= 0)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "planes, out_bytes non-NULL, 1 <= B <= 65535, L_in >= 1");
-    if (int r = check_resample_args(c, w, channels, encoding, up, down, taps, n_taps)) return r;
-    if (int r = check_export_planes(c, w, planes, row_stride, plane_stride, channels, L_in, up, down, frames_out)) return r;
-    const long long row_bytes = (long long)frames_out * channels * (encoding == LASS_WAV_PCM16 ? 2 : 4);
-    if (out_row_stride_bytes < row_bytes || out_row_stride_bytes % 4 != 0)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "out_row_stride_bytes must be a multiple of 4 and hold a row (" +
-                    std::to_string(row_bytes) + " bytes)");
-    if (reinterpret_cast<uintptr_t>(out_bytes) % 4 != 0) return fail(c, LASS_ERR_ARG, std::string(w) + "out_bytes must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(planes) % 4 != 0 || reinterpret_cast<uintptr_t>(clipped) % 4 != 0)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "planes and clipped must be 4-byte aligned");
+    if (int r = refuse(c, check_encode(w, P, F, dry, gain, gain_required, out, clipped))) return r;
     if (int r = use_device(c)) return r;
-    if (gain)
-        HIP_TRY(c, lass_launch_resample_encode_gain(planes, row_stride, plane_stride, B, channels, L_in, up, down, taps, n_taps,
-                                                    encoding, out_bytes, out_row_stride_bytes, frames_out, clipped, gain,
-                                                    (hipStream_t)stream));
-    else
-        HIP_TRY(c, lass_launch_resample_encode(planes, row_stride, plane_stride, B, channels, L_in, up, down, taps, n_taps, encoding,
-                                               out_bytes, out_row_stride_bytes, frames_out, clipped, (hipStream_t)stream));
+    HIP_TRY(c, lass_launch_encode(P, F, dry, gain, out, clipped, (hipStream_t)stream));
     return 0;
 }
 
 int lass_resample_encode(lass_ctx* c, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels, int L_in,
                          int up, int down, const float* taps, int n_taps, int encoding, void* out_bytes,
                          int64_t out_row_stride_bytes, int frames_out, unsigned* clipped, void* stream) {
-    return resample_encode(c, "lass_resample_encode: ", planes, row_stride, plane_stride, B, channels, L_in, up, down, taps, n_taps,
-                           encoding, out_bytes, out_row_stride_bytes, frames_out, clipped, nullptr, stream);
+    return encode(c, "lass_resample_encode: ", {planes, row_stride, plane_stride, B, channels, L_in}, {up, down, taps, n_taps}, nullptr,
+                  nullptr, false, {out_bytes, out_row_stride_bytes, encoding, frames_out, channels}, clipped, stream);
 }
 
 int lass_resample_encode_gain(lass_ctx* c, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels,
                               int L_in, int up, int down, const float* taps, int n_taps, int encoding, const float* gain,
                               void* out_bytes, int64_t out_row_stride_bytes, int frames_out, unsigned* clipped, void* stream) {
-    const char* w = "lass_resample_encode_gain: ";
-    if (!c) return LASS_ERR_ARG;
-    if (!gain || reinterpret_cast<uintptr_t>(gain) % 4 != 0) return fail(c, LASS_ERR_ARG, std::string(w) + "gain non-NULL, 4-byte aligned");
-    return resample_encode(c, w, planes, row_stride, plane_stride, B, channels, L_in, up, down, taps, n_taps, encoding, out_bytes,
-                           out_row_stride_bytes, frames_out, clipped, gain, stream);
-}
-
-int lass_resample_peak(lass_ctx* c, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels, int L_in,
-                       int up, int down, const float* taps, int n_taps, int frames_out, float* peak, void* stream) {
-    const char* w = "lass_resample_peak: ";
-    if (!c) return LASS_ERR_ARG;
-    if (!planes || !peak || B <= 0 || B > 65535 || L_in <= 0)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "planes, peak non-NULL, 1 <= B <= 65535, L_in >= 1");
-    if (int r = check_resample_args(c, w, channels, LASS_WAV_F32, up, down, taps, n_taps)) return r;
-    if (int r = check_export_planes(c, w, planes, row_stride, plane_stride, channels, L_in, up, down, frames_out)) return r;
-    if (reinterpret_cast<uintptr_t>(planes) % 4 != 0 || reinterpret_cast<uintptr_t>(peak) % 4 != 0)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "planes and peak must be 4-byte aligned");
-    if (int r = use_device(c)) return r;
-    HIP_TRY(c, lass_launch_resample_peak(planes, row_stride, plane_stride, B, channels, L_in, up, down, taps, n_taps, frames_out, peak,
-                                         (hipStream_t)stream));
-    return 0;
-}
-
-// What the two remix entries ask of the dry source, after check_export_planes (w: the entry's "name: ").
-static int check_dry(lass_ctx* c, const char* w, const void* dry, int64_t dry_row_stride_bytes, int dry_encoding, const float* amount,
-                     int channels, int frames_out) {
-    if (!dry || !amount) return fail(c, LASS_ERR_ARG, std::string(w) + "dry and amount non-NULL");
-    if (dry_encoding != LASS_WAV_PCM16 && dry_encoding != LASS_WAV_PCM32 && dry_encoding != LASS_WAV_F32)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "dry_encoding must be LASS_WAV_PCM16, LASS_WAV_PCM32 or LASS_WAV_F32");
-    const long long row_bytes = (long long)frames_out * channels * (dry_encoding == LASS_WAV_PCM16 ? 2 : 4);
-    if (dry_row_stride_bytes < row_bytes || dry_row_stride_bytes % 4 != 0)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "dry_row_stride_bytes must be a multiple of 4 and hold frames_out frames (" +
-                    std::to_string(row_bytes) + " bytes)");
-    if (reinterpret_cast<uintptr_t>(dry) % 4 != 0 || reinterpret_cast<uintptr_t>(amount) % 4 != 0)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "dry and amount must be 4-byte aligned");
-    return 0;
+    return encode(c, "lass_resample_encode_gain: ", {planes, row_stride, plane_stride, B, channels, L_in}, {up, down, taps, n_taps},
+                  nullptr, gain, true, {out_bytes, out_row_stride_bytes, encoding, frames_out, channels}, clipped, stream);
 }
 
 int lass_remix_encode(lass_ctx* c, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels, int L_in, int up,
                       int down, const float* taps, int n_taps, const void* dry, int64_t dry_row_stride_bytes, int dry_encoding,
                       const float* amount, int encoding, const float* gain, void* out_bytes, int64_t out_row_stride_bytes,
                       int frames_out, unsigned* clipped, void* stream) {
-    const char* w = "lass_remix_encode: ";
+    const DrySource d{{dry, dry_row_stride_bytes, dry_encoding, frames_out, channels}, amount};
+    return encode(c, "lass_remix_encode: ", {planes, row_stride, plane_stride, B, channels, L_in}, {up, down, taps, n_taps}, &d, gain,
+                  false, {out_bytes, out_row_stride_bytes, encoding, frames_out, channels}, clipped, stream);
+}
+
+// The two sample-peak entries (dry NULL: no remix).
+static int sample_peak(lass_ctx* c, const char* w, const PlaneRows& P, const RationalFilter& F, const DrySource* dry, int frames_out,
+                       float* peak, void* stream) {
     if (!c) return LASS_ERR_ARG;
-    if (!planes || !out_bytes || B <= 0 || B > 65535 || L_in <= 0)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "planes, out_bytes non-NULL, 1 <= B <= 65535, L_in >= 1");
-    if (int r = check_resample_args(c, w, channels, encoding, up, down, taps, n_taps)) return r;
-    if (int r = check_export_planes(c, w, planes, row_stride, plane_stride, channels, L_in, up, down, frames_out)) return r;
-    if (int r = check_dry(c, w, dry, dry_row_stride_bytes, dry_encoding, amount, channels, frames_out)) return r;
-    const long long row_bytes = (long long)frames_out * channels * (encoding == LASS_WAV_PCM16 ? 2 : 4);
-    if (out_row_stride_bytes < row_bytes || out_row_stride_bytes % 4 != 0)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "out_row_stride_bytes must be a multiple of 4 and hold a row (" +
-                    std::to_string(row_bytes) + " bytes)");
-    if (reinterpret_cast<uintptr_t>(out_bytes) % 4 != 0) return fail(c, LASS_ERR_ARG, std::string(w) + "out_bytes must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(planes) % 4 != 0 || reinterpret_cast<uintptr_t>(clipped) % 4 != 0 ||
-        reinterpret_cast<uintptr_t>(gain) % 4 != 0)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "planes, gain and clipped must be 4-byte aligned");
+    if (int r = refuse(c, check_peak(w, P, F, dry, frames_out, nullptr, peak))) return r;
     if (int r = use_device(c)) return r;
-    HIP_TRY(c, lass_launch_remix_encode(planes, row_stride, plane_stride, B, channels, L_in, up, down, taps, n_taps, dry,
-                                        dry_row_stride_bytes, dry_encoding, amount, encoding, gain, out_bytes, out_row_stride_bytes,
-                                        frames_out, clipped, (hipStream_t)stream));
+    HIP_TRY(c, lass_launch_sample_peak(P, F, dry, frames_out, peak, (hipStream_t)stream));
     return 0;
+}
+
+int lass_resample_peak(lass_ctx* c, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels, int L_in,
+                       int up, int down, const float* taps, int n_taps, int frames_out, float* peak, void* stream) {
+    return sample_peak(c, "lass_resample_peak: ", {planes, row_stride, plane_stride, B, channels, L_in}, {up, down, taps, n_taps}, nullptr,
+                       frames_out, peak, stream);
 }
 
 int lass_remix_peak(lass_ctx* c, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels, int L_in, int up,
                     int down, const float* taps, int n_taps, const void* dry, int64_t dry_row_stride_bytes, int dry_encoding,
                     const float* amount, int frames_out, float* peak, void* stream) {
-    const char* w = "lass_remix_peak: ";
-    if (!c) return LASS_ERR_ARG;
-    if (!planes || !peak || B <= 0 || B > 65535 || L_in <= 0)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "planes, peak non-NULL, 1 <= B <= 65535, L_in >= 1");
-    if (int r = check_resample_args(c, w, channels, LASS_WAV_F32, up, down, taps, n_taps)) return r;
-    if (int r = check_export_planes(c, w, planes, row_stride, plane_stride, channels, L_in, up, down, frames_out)) return r;
-    if (int r = check_dry(c, w, dry, dry_row_stride_bytes, dry_encoding, amount, channels, frames_out)) return r;
-    if (reinterpret_cast<uintptr_t>(planes) % 4 != 0 || reinterpret_cast<uintptr_t>(peak) % 4 != 0)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "planes and peak must be 4-byte aligned");
-    if (int r = use_device(c)) return r;
-    HIP_TRY(c, lass_launch_remix_peak(planes, row_stride, plane_stride, B, channels, L_in, up, down, taps, n_taps, dry,
-                                      dry_row_stride_bytes, dry_encoding, amount, frames_out, peak, (hipStream_t)stream));
-    return 0;
+    const DrySource d{{dry, dry_row_stride_bytes, dry_encoding, frames_out, channels}, amount};
+    return sample_peak(c, "lass_remix_peak: ", {planes, row_stride, plane_stride, B, channels, L_in}, {up, down, taps, n_taps}, &d,
+                       frames_out, peak, stream);
 }
 
 int lass_resample_true_peak(lass_ctx* c, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels, int L_in,
                             int up, int down, const float* taps, int n_taps, int frames_out, int os, const float* os_taps,
                             int n_os_taps, float* peak, void* stream) {
-    const char* w = "lass_resample_true_peak: ";
+    const std::string w = "lass_resample_true_peak: ";
     if (!c) return LASS_ERR_ARG;
-    if (!planes || !peak || B <= 0 || B > 65535 || L_in <= 0)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "planes, peak non-NULL, 1 <= B <= 65535, L_in >= 1");
-    if (int r = check_resample_args(c, w, channels, LASS_WAV_F32, up, down, taps, n_taps)) return r;
-    if (int r = check_export_planes(c, w, planes, row_stride, plane_stride, channels, L_in, up, down, frames_out)) return r;
-    if (os != 2 && os != 4) return fail(c, LASS_ERR_ARG, std::string(w) + "os must be 2 or 4 (1 is lass_resample_peak)");
-    if (!os_taps || n_os_taps != 20 * os + 1)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "os_taps non-NULL, n_os_taps = 20 * os + 1 = " + std::to_string(20 * os + 1));
-    if (reinterpret_cast<uintptr_t>(planes) % 4 != 0 || reinterpret_cast<uintptr_t>(peak) % 4 != 0 ||
-        reinterpret_cast<uintptr_t>(os_taps) % 4 != 0)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "planes, os_taps and peak must be 4-byte aligned");
+    const PlaneRows P{planes, row_stride, plane_stride, B, channels, L_in};
+    const RationalFilter F{up, down, taps, n_taps};
+    const Oversampler O{os, os_taps, n_os_taps};
+    if (int r = refuse(c, check_peak(w, P, F, nullptr, frames_out, &O, peak))) return r;
     if (!lass_resample_true_peak_fits(up, down, (up == 1 && down == 1) ? 1 : n_taps, os))
-        return fail(c, LASS_ERR_ARG, std::string(w) + "at up = " + std::to_string(up) + ", down = " + std::to_string(down) +
+        return fail(c, LASS_ERR_ARG, w + "at up = " + std::to_string(up) + ", down = " + std::to_string(down) +
                     " the 21 frames one interpolated value reaches do not fit the CU's LDS beside the filter table (take the "
                     "true peak on the host)");
     if (int r = use_device(c)) return r;
-    HIP_TRY(c, lass_launch_resample_true_peak(planes, row_stride, plane_stride, B, channels, L_in, up, down, taps, n_taps, frames_out,
-                                              os, os_taps, n_os_taps, peak, (hipStream_t)stream));
+    HIP_TRY(c, lass_launch_resample_true_peak(P, F, frames_out, O, peak, (hipStream_t)stream));
     return 0;
 }
 
-// What the two meter entries ask before the filter is formed (w: the entry's "name: "; scratch_per_bin: doubles of scratch per
-// recording and hop bin beyond the 5 per plane).
-static int check_loudness_args(lass_ctx* c, const char* w, const float* planes, int64_t row_stride, int64_t plane_stride, int B,
-                               int channels, int L, const int* lengths, int hop, const double* coef, const float* weights,
-                               const double* out, const double* blocks, int nb_max, const void* scratch, size_t scratch_bytes,
-                               int scratch_per_bin) {
-    if (!planes || !coef || !out || B <= 0 || L <= 0) return fail(c, LASS_ERR_ARG, std::string(w) + "planes, coef, out non-NULL, B >= 1, L >= 1");
-    if (channels < 1 || channels > 8 || (long long)B * channels > 65535)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "1 ... 8 channels, B * channels <= 65535");
-    if (hop < 1 || hop > LASS_LOUDNESS_MAX_HOP)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "hop (rate / 10) must lie in 1 ... " + std::to_string(LASS_LOUDNESS_MAX_HOP));
-    const long long row_floats = (long long)(channels - 1) * plane_stride + L;
-    if (plane_stride < L || row_stride < row_floats)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "plane_stride must hold a plane (" + std::to_string(L) +
-                    " floats) and row_stride a recording (" + std::to_string(row_floats) + " floats)");
-    const long long bins = L / hop, nb = bins >= 4 ? bins - 3 : 0;
-    if (blocks && (long long)nb_max < nb)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "nb_max must hold the blocks of L samples (" + std::to_string(nb) + ")");
-    const size_t need = ((size_t)5 * B * channels + (size_t)scratch_per_bin * B) * bins * sizeof(double);
-    if (need && (!scratch || scratch_bytes < need))
-        return fail(c, LASS_ERR_ARG, std::string(w) + "scratch must hold " + (scratch_per_bin ? "(5 * channels + 1) * B" : "5 * B * channels") +
-                    " * (L / hop) doubles (" + std::to_string(need) + " bytes)");
-    if (reinterpret_cast<uintptr_t>(planes) % 4 != 0 || reinterpret_cast<uintptr_t>(lengths) % 4 != 0 ||
-        reinterpret_cast<uintptr_t>(weights) % 4 != 0 || reinterpret_cast<uintptr_t>(out) % 8 != 0 ||
-        reinterpret_cast<uintptr_t>(blocks) % 8 != 0 || reinterpret_cast<uintptr_t>(scratch) % 8 != 0)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "planes, lengths, weights 4-byte aligned; out, blocks, scratch 8-byte aligned");
-    return 0;
+// The two meter entries up to the launch: the checks, then the filter formed (stats: lass_loudness_stats).
+static int meter_ready(lass_ctx* c, const std::string& w, const PlaneRows& P, const int* lengths, int hop, const double* coef,
+                       const float* weights, const double* out, const double* blocks, int nb_max, const double* short_term, int ns_max,
+                       const void* scratch, size_t scratch_bytes, bool stats, LoudnessFilter* f) {
+    if (!c) return LASS_ERR_ARG;
+    if (int r = refuse(c, check_meter(w, P, lengths, hop, coef, weights, out, blocks, nb_max, short_term, ns_max, scratch, scratch_bytes,
+                                      stats)))
+        return r;
+    if (!lass_loudness_filter(coef, hop, f))
+        return fail(c, LASS_ERR_ARG, w + "coef must be finite, both biquads with their poles inside the unit circle");
+    return use_device(c);
 }
 
 int lass_loudness_stats(lass_ctx* c, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels, int L,
                         const int* lengths, int hop, const double* coef, const float* weights, double* out, double* blocks,
                         int nb_max, double* short_term, int ns_max, void* scratch, size_t scratch_bytes, void* stream) {
-    const char* w = "lass_loudness_stats: ";
-    if (!c) return LASS_ERR_ARG;
-    if (int r = check_loudness_args(c, w, planes, row_stride, plane_stride, B, channels, L, lengths, hop, coef, weights, out, blocks,
-                                    nb_max, scratch, scratch_bytes, 1))
-        return r;
-    const long long bins = L / hop, ns = bins >= 30 ? bins - 29 : 0;
-    if (short_term && ((long long)ns_max < ns || reinterpret_cast<uintptr_t>(short_term) % 8 != 0))
-        return fail(c, LASS_ERR_ARG, std::string(w) + "short_term 8-byte aligned, ns_max must hold the short-term blocks of L samples (" +
-                    std::to_string(ns) + ")");
+    const PlaneRows P{planes, row_stride, plane_stride, B, channels, L};
     LoudnessFilter f;
-    if (!lass_loudness_filter(coef, hop, &f))
-        return fail(c, LASS_ERR_ARG, std::string(w) + "coef must be finite, both biquads with their poles inside the unit circle");
-    if (int r = use_device(c)) return r;
-    HIP_TRY(c, lass_launch_loudness_stats(planes, row_stride, plane_stride, B, channels, L, lengths, hop, f, weights, out, blocks, nb_max,
-                                          short_term, ns_max, static_cast<double*>(scratch), (hipStream_t)stream));
+    if (int r = meter_ready(c, "lass_loudness_stats: ", P, lengths, hop, coef, weights, out, blocks, nb_max, short_term, ns_max, scratch,
+                            scratch_bytes, true, &f))
+        return r;
+    HIP_TRY(c, lass_launch_loudness_stats(P, lengths, hop, f, weights, out, blocks, nb_max, short_term, ns_max,
+                                          static_cast<double*>(scratch), (hipStream_t)stream));
     return 0;
 }
 
 int lass_loudness(lass_ctx* c, const float* planes, int64_t row_stride, int64_t plane_stride, int B, int channels, int L,
                   const int* lengths, int hop, const double* coef, const float* weights, double* out, double* blocks, int nb_max,
                   void* scratch, size_t scratch_bytes, void* stream) {
-    const char* w = "lass_loudness: ";
-    if (!c) return LASS_ERR_ARG;
-    if (int r = check_loudness_args(c, w, planes, row_stride, plane_stride, B, channels, L, lengths, hop, coef, weights, out, blocks,
-                                    nb_max, scratch, scratch_bytes, 0))
-        return r;
+    const PlaneRows P{planes, row_stride, plane_stride, B, channels, L};
     LoudnessFilter f;
-    if (!lass_loudness_filter(coef, hop, &f))
-        return fail(c, LASS_ERR_ARG, std::string(w) + "coef must be finite, both biquads with their poles inside the unit circle");
-    if (int r = use_device(c)) return r;
-    HIP_TRY(c, lass_launch_loudness(planes, row_stride, plane_stride, B, channels, L, lengths, hop, f, weights, out, blocks, nb_max,
-                                    static_cast<double*>(scratch), (hipStream_t)stream));
+    if (int r = meter_ready(c, "lass_loudness: ", P, lengths, hop, coef, weights, out, blocks, nb_max, nullptr, 0, scratch, scratch_bytes,
+                            false, &f))
+        return r;
+    HIP_TRY(c, lass_launch_loudness(P, lengths, hop, f, weights, out, blocks, nb_max, static_cast<double*>(scratch), (hipStream_t)stream));
     return 0;
 }
 
 int lass_loudness_gain(lass_ctx* c, const double* loudness, const float* peak, int B, double target_lufs, float ceiling, float* gain,
                        int* limited, void* stream) {
-    const char* w = "lass_loudness_gain: ";
     if (!c) return LASS_ERR_ARG;
-    if (!loudness || !gain || B <= 0) return fail(c, LASS_ERR_ARG, std::string(w) + "loudness, gain non-NULL, B >= 1");
-    if (!(ceiling >= 0.0f) || std::isinf(ceiling)) return fail(c, LASS_ERR_ARG, std::string(w) + "ceiling must be finite and >= 0 (0: none)");
-    if (ceiling > 0.0f && !peak) return fail(c, LASS_ERR_ARG, std::string(w) + "a ceiling needs peak");
-    if (std::isinf(target_lufs)) return fail(c, LASS_ERR_ARG, std::string(w) + "target_lufs must be finite, or NaN for none");
-    if (reinterpret_cast<uintptr_t>(loudness) % 8 != 0 || reinterpret_cast<uintptr_t>(peak) % 4 != 0 ||
-        reinterpret_cast<uintptr_t>(gain) % 4 != 0 || reinterpret_cast<uintptr_t>(limited) % 4 != 0)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "loudness 8-byte aligned; peak, gain, limited 4-byte aligned");
+    if (int r = refuse(c, check_gain_rule("lass_loudness_gain: ", loudness, peak, B, target_lufs, ceiling, gain, limited))) return r;
     if (int r = use_device(c)) return r;
     HIP_TRY(c, lass_launch_loudness_gain(loudness, peak, B, target_lufs, ceiling, gain, limited, (hipStream_t)stream));
     return 0;
@@ -1625,42 +1480,13 @@ int lass_limit(lass_ctx* c, const float* planes, int64_t row_stride, int64_t pla
                const float* os_taps, int n_os_taps, const float* gain, float ceiling, int H, const float* window, float* out,
                int64_t out_row_stride, int64_t out_plane_stride, float* curve, float* envelope, int64_t curve_row_stride,
                float* min_gain, int* frames, void* stream) {
-    const char* w = "lass_limit: ";
     if (!c) return LASS_ERR_ARG;
-    if (!planes || !gain || !window || !out || B <= 0 || B > 65535)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "planes, gain, window, out non-NULL, 1 <= B <= 65535");
-    if (channels < 1 || channels > 8) return fail(c, LASS_ERR_ARG, std::string(w) + "1 ... 8 channels");
-    if (L < 1) return fail(c, LASS_ERR_ARG, std::string(w) + "L >= 1");
-    if (H < 1 || H > LASS_LIMITER_MAX_H)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "H must lie in 1 ... " + std::to_string(LASS_LIMITER_MAX_H));
-    if (os != 1 && os != 2 && os != 4) return fail(c, LASS_ERR_ARG, std::string(w) + "os must be 1, 2 or 4");
-    if (os == 1 ? (os_taps ? n_os_taps != 21 : n_os_taps != 0) : (!os_taps || n_os_taps != 20 * os + 1))
-        return fail(c, LASS_ERR_ARG, std::string(w) + "os_taps non-NULL with n_os_taps = 20 * os + 1 = " + std::to_string(20 * os + 1) +
-                    " (or NULL and 0 at os == 1)");
-    if (!(ceiling > 0.0f) || std::isinf(ceiling)) return fail(c, LASS_ERR_ARG, std::string(w) + "ceiling must be finite and > 0");
-    const long long row_floats = (long long)(channels - 1) * plane_stride + L;
-    if (plane_stride < L || row_stride < row_floats)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "plane_stride must hold a plane (" + std::to_string(L) +
-                    " floats) and row_stride a recording (" + std::to_string(row_floats) + " floats)");
-    const long long out_row_floats = (long long)(channels - 1) * out_plane_stride + L;
-    if (out_plane_stride < L || out_row_stride < out_row_floats)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "out_plane_stride must hold a plane (" + std::to_string(L) +
-                    " floats) and out_row_stride a recording (" + std::to_string(out_row_floats) + " floats)");
-    if ((curve || envelope) && curve_row_stride < L)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "curve_row_stride must hold a row (" + std::to_string(L) + " floats)");
-    const uintptr_t p0 = reinterpret_cast<uintptr_t>(planes), o0 = reinterpret_cast<uintptr_t>(out);
-    const uintptr_t p1 = p0 + ((uintptr_t)(B - 1) * (uintptr_t)row_stride + (uintptr_t)row_floats) * sizeof(float);
-    const uintptr_t o1 = o0 + ((uintptr_t)(B - 1) * (uintptr_t)out_row_stride + (uintptr_t)out_row_floats) * sizeof(float);
-    if (p0 < o1 && o0 < p1)
-        return fail(c, LASS_ERR_ARG, std::string(w) + "out must not overlap planes (a tile's halo reads what a neighbour would write)");
-    for (const void* q : {(const void*)planes, (const void*)os_taps, (const void*)gain, (const void*)window, (const void*)out,
-                          (const void*)curve, (const void*)envelope, (const void*)min_gain, (const void*)frames})
-        if (reinterpret_cast<uintptr_t>(q) % 4 != 0)
-            return fail(c, LASS_ERR_ARG, std::string(w) + "planes, os_taps, gain, window, out, curve, envelope, min_gain and frames "
-                        "must be 4-byte aligned");
+    const PlaneRows P{planes, row_stride, plane_stride, B, channels, L}, O{out, out_row_stride, out_plane_stride, B, channels, L};
+    if (int r = refuse(c, check_limit("lass_limit: ", P, {os, os_taps, n_os_taps}, gain, ceiling, H, window, O, curve, envelope,
+                                      curve_row_stride, min_gain, frames)))
+        return r;
     if (int r = use_device(c)) return r;
-    HIP_TRY(c, lass_launch_limit(planes, row_stride, plane_stride, B, channels, L, os, os > 1 ? os_taps : nullptr,
-                                 os > 1 ? n_os_taps : 0, gain, ceiling, H, window, out, out_row_stride, out_plane_stride, curve, envelope,
+    HIP_TRY(c, lass_launch_limit(P, {os, os > 1 ? os_taps : nullptr, os > 1 ? n_os_taps : 0}, gain, ceiling, H, window, O, curve, envelope,
                                  curve_row_stride, min_gain, frames, (hipStream_t)stream));
     return 0;
 }

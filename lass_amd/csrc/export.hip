@@ -282,106 +282,84 @@ size_t true_peak_floats(int up, int down, int n_taps, int os, int t) {
 // One launch for the three sinks, with or without a dry source.  kPeak keeps no stage (enc, out and clipped unused), so its tiles
 // are as large as the span allows.
 template <Sink kSink, class... Dry>
-static hipError_t launch(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L_in, int up, int down,
-                         const float* taps, int n_taps, int enc, unsigned char* o, long long out_row_stride, int frames_out,
+static hipError_t launch(const PlaneRows& P, const RationalFilter& F, int enc, unsigned char* o, long long out_row_stride, int frames_out,
                          unsigned* clipped, const float* gain, unsigned* peak, hipStream_t stream, Dry... dry) {
-    if (B <= 0 || B > 65535 || ch < 1 || ch > 8 || L_in <= 0 || frames_out <= 0 || up < 1 || down < 1) return hipErrorInvalidValue;
+    const int B = P.B, ch = P.ch, up = F.up, down = F.down, n_taps = F.n_taps;
+    if (B <= 0 || B > 65535 || ch < 1 || ch > 8 || P.L <= 0 || frames_out <= 0 || up < 1 || down < 1) return hipErrorInvalidValue;
     const int bps = enc == LASS_WAV_PCM16 ? 2 : 4;
     if (up == 1 && down == 1) {
         const size_t lds = kSink == kPeak ? 0 : (size_t)kTilePlain * ch * bps + 4;
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_encode<kSink, Dry...>), dim3((frames_out + kTilePlain - 1) / kTilePlain, B), dim3(kThreads),
-                           lds, stream, planes, row_stride, plane_stride, ch, enc, o, out_row_stride, frames_out, clipped, gain, peak,
+                           lds, stream, P.p, P.row_stride, P.plane_stride, ch, enc, o, out_row_stride, frames_out, clipped, gain, peak,
                            dry...);
         return hipGetLastError();
     }
     // the largest tile whose span and stage fit beside the table (one frame needs J floats of span and at most 9 of stage: it
     // always fits under the caps); the stage starts on a multiple of four floats
-    FirPlan P;
+    FirPlan plan;
     hipError_t e = fir_plan(reinterpret_cast<const void*>(k_resample_encode<kSink, Dry...>), up, down, n_taps, frames_out, [&](int t) {
         const size_t head = (lass_resample_table_floats(up, n_taps) + lass_resample_span_floats(up, down, n_taps, t) + 3) & ~(size_t)3;
         return kSink == kPeak ? head : head + ((size_t)t * ch * bps + 4 + 3) / 4;
-    }, &P);
+    }, &plan);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_resample_encode<kSink, Dry...>), dim3(P.nblk, B), dim3(kThreads), P.lds, stream, planes,
-                       row_stride, plane_stride, L_in, ch, enc, up, down, taps, n_taps, P.J, P.tile,
-                       (int)lass_resample_span_floats(up, down, n_taps, P.tile), o, out_row_stride, frames_out, clipped, gain, peak,
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_resample_encode<kSink, Dry...>), dim3(plan.nblk, B), dim3(kThreads), plan.lds, stream, P.p,
+                       P.row_stride, P.plane_stride, P.L, ch, enc, up, down, F.taps, n_taps, plan.J, plan.tile,
+                       (int)lass_resample_span_floats(up, down, n_taps, plan.tile), o, out_row_stride, frames_out, clipped, gain, peak,
                        dry...);
     return hipGetLastError();
 }
 
-hipError_t lass_launch_resample_encode(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L_in,
-                                       int up, int down, const float* taps, int n_taps, int enc, void* out, long long out_row_stride,
-                                       int frames_out, unsigned* clipped, hipStream_t stream) {
-    return launch<kEncode>(planes, row_stride, plane_stride, B, ch, L_in, up, down, taps, n_taps, enc, static_cast<unsigned char*>(out),
-                           out_row_stride, frames_out, clipped, nullptr, nullptr, stream);
+static DryRows dry_rows(const DrySource& d) {
+    return {static_cast<const unsigned char*>(d.rows.p), d.rows.row_stride_bytes, d.amount, d.rows.enc};
 }
 
-hipError_t lass_launch_resample_encode_gain(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L_in,
-                                            int up, int down, const float* taps, int n_taps, int enc, void* out,
-                                            long long out_row_stride, int frames_out, unsigned* clipped, const float* gain,
-                                            hipStream_t stream) {
-    return launch<kEncodeGain>(planes, row_stride, plane_stride, B, ch, L_in, up, down, taps, n_taps, enc,
-                               static_cast<unsigned char*>(out), out_row_stride, frames_out, clipped, gain, nullptr, stream);
+hipError_t lass_launch_encode(const PlaneRows& P, const RationalFilter& F, const DrySource* dry, const float* gain, const PayloadRows& out,
+                              unsigned* clipped, hipStream_t stream) {
+    auto go = [&](auto... d) {
+        unsigned char* o = static_cast<unsigned char*>(const_cast<void*>(out.p));   // the one PayloadRows that is written
+        return gain ? launch<kEncodeGain>(P, F, out.enc, o, out.row_stride_bytes, out.frames, clipped, gain, nullptr, stream, d...)
+                    : launch<kEncode>(P, F, out.enc, o, out.row_stride_bytes, out.frames, clipped, nullptr, nullptr, stream, d...);
+    };
+    return dry ? go(dry_rows(*dry)) : go();
 }
 
-hipError_t lass_launch_resample_peak(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L_in, int up,
-                                     int down, const float* taps, int n_taps, int frames_out, float* peak, hipStream_t stream) {
-    if (B <= 0) return hipErrorInvalidValue;
-    hipError_t e = hipMemsetAsync(peak, 0, (size_t)B * sizeof(float), stream);
+hipError_t lass_launch_sample_peak(const PlaneRows& P, const RationalFilter& F, const DrySource* dry, int frames_out, float* peak,
+                                   hipStream_t stream) {
+    if (P.B <= 0) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(peak, 0, (size_t)P.B * sizeof(float), stream);
     if (e != hipSuccess) return e;
-    return launch<kPeak>(planes, row_stride, plane_stride, B, ch, L_in, up, down, taps, n_taps, LASS_WAV_F32, nullptr, 0, frames_out,
-                         nullptr, nullptr, reinterpret_cast<unsigned*>(peak), stream);
-}
-
-hipError_t lass_launch_remix_encode(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L_in, int up,
-                                    int down, const float* taps, int n_taps, const void* dry, long long dry_row_stride, int dry_enc,
-                                    const float* amount, int enc, const float* gain, void* out, long long out_row_stride,
-                                    int frames_out, unsigned* clipped, hipStream_t stream) {
-    const DryRows d{static_cast<const unsigned char*>(dry), dry_row_stride, amount, dry_enc};
-    unsigned char* o = static_cast<unsigned char*>(out);
-    return gain ? launch<kEncodeGain>(planes, row_stride, plane_stride, B, ch, L_in, up, down, taps, n_taps, enc, o, out_row_stride,
-                                      frames_out, clipped, gain, nullptr, stream, d)
-                : launch<kEncode>(planes, row_stride, plane_stride, B, ch, L_in, up, down, taps, n_taps, enc, o, out_row_stride,
-                                  frames_out, clipped, nullptr, nullptr, stream, d);
-}
-
-hipError_t lass_launch_remix_peak(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L_in, int up,
-                                  int down, const float* taps, int n_taps, const void* dry, long long dry_row_stride, int dry_enc,
-                                  const float* amount, int frames_out, float* peak, hipStream_t stream) {
-    if (B <= 0) return hipErrorInvalidValue;
-    hipError_t e = hipMemsetAsync(peak, 0, (size_t)B * sizeof(float), stream);
-    if (e != hipSuccess) return e;
-    const DryRows d{static_cast<const unsigned char*>(dry), dry_row_stride, amount, dry_enc};
-    return launch<kPeak>(planes, row_stride, plane_stride, B, ch, L_in, up, down, taps, n_taps, LASS_WAV_F32, nullptr, 0, frames_out,
-                         nullptr, nullptr, reinterpret_cast<unsigned*>(peak), stream, d);
+    auto go = [&](auto... d) {
+        return launch<kPeak>(P, F, LASS_WAV_F32, nullptr, 0, frames_out, nullptr, nullptr, reinterpret_cast<unsigned*>(peak), stream, d...);
+    };
+    return dry ? go(dry_rows(*dry)) : go();
 }
 
 bool lass_resample_true_peak_fits(int up, int down, int n_taps, int os) {
     return true_peak_floats(up, down, n_taps, os, 1) <= (size_t)kLdsFloats;
 }
 
-hipError_t lass_launch_resample_true_peak(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L_in,
-                                          int up, int down, const float* taps, int n_taps, int frames_out, int os, const float* os_taps,
-                                          int n_os_taps, float* peak, hipStream_t stream) {
-    if (B <= 0 || B > 65535 || ch < 1 || ch > 8 || L_in <= 0 || frames_out <= 0 || up < 1 || down < 1 || (os != 2 && os != 4) ||
-        n_os_taps != 20 * os + 1)
+hipError_t lass_launch_resample_true_peak(const PlaneRows& P, const RationalFilter& F, int frames_out, const Oversampler& O, float* peak,
+                                          hipStream_t stream) {
+    const int B = P.B, up = F.up, down = F.down, n_taps = F.n_taps, os = O.os;
+    if (B <= 0 || B > 65535 || P.ch < 1 || P.ch > 8 || P.L <= 0 || frames_out <= 0 || up < 1 || down < 1 || (os != 2 && os != 4) ||
+        O.n_taps != 20 * os + 1)
         return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(peak, 0, (size_t)B * sizeof(float), stream);
     if (e != hipSuccess) return e;
     unsigned* pk = reinterpret_cast<unsigned*>(peak);
     if (up == 1 && down == 1) {
         const size_t lds = true_peak_floats(1, 1, 1, os, kTileMax) * sizeof(float);
-        hipLaunchKernelGGL(k_true_peak<false>, dim3((frames_out + kTileMax - 1) / kTileMax, B), dim3(kThreads), lds, stream, planes,
-                           row_stride, plane_stride, L_in, ch, 1, 1, nullptr, 1, 1, kTileMax, 0, frames_out, os, os_taps, n_os_taps, pk);
+        hipLaunchKernelGGL(k_true_peak<false>, dim3((frames_out + kTileMax - 1) / kTileMax, B), dim3(kThreads), lds, stream, P.p,
+                           P.row_stride, P.plane_stride, P.L, P.ch, 1, 1, nullptr, 1, 1, kTileMax, 0, frames_out, os, O.taps, O.n_taps, pk);
         return hipGetLastError();
     }
     // the stage costs LDS beside table and span, and the span reaches 2 * kOsHalo outputs further: never a larger tile than kPeak's
-    FirPlan P;
+    FirPlan plan;
     e = fir_plan(reinterpret_cast<const void*>(k_true_peak<true>), up, down, n_taps, frames_out,
-                 [&](int t) { return true_peak_floats(up, down, n_taps, os, t); }, &P);
+                 [&](int t) { return true_peak_floats(up, down, n_taps, os, t); }, &plan);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_true_peak<true>, dim3(P.nblk, B), dim3(kThreads), P.lds, stream, planes, row_stride, plane_stride, L_in, ch, up,
-                       down, taps, n_taps, P.J, P.tile, (int)lass_resample_span_floats(up, down, n_taps, P.tile + 2 * kOsHalo),
-                       frames_out, os, os_taps, n_os_taps, pk);
+    hipLaunchKernelGGL(k_true_peak<true>, dim3(plan.nblk, B), dim3(kThreads), plan.lds, stream, P.p, P.row_stride, P.plane_stride, P.L,
+                       P.ch, up, down, F.taps, n_taps, plan.J, plan.tile,
+                       (int)lass_resample_span_floats(up, down, n_taps, plan.tile + 2 * kOsHalo), frames_out, os, O.taps, O.n_taps, pk);
     return hipGetLastError();
 }

@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "audio_args.h"  // the operand structs of the audio file launchers and lass_resample_table_floats (host only, HIP-free)
 #include "conv_route.h"  // ConvKind, the shape rules of the f32 conv families and the route of a block, LASS_NFFT & co (host only, HIP-free)
 
 // ---- conv.hip -----------------------------------------------------------------------------------------------------
@@ -276,66 +277,37 @@ hipError_t lass_launch_relayout_conv(const float* src, int Cout, int Cin, int ta
 hipError_t lass_launch_bnfold(const float* g, const float* beta, const float* mean, const float* var, int C, float eps,
                               float* scale, float* base, hipStream_t stream);
 
-// ---- resample.hip -------------------------------------------------------------------------------------------------
-// raw (B rows of interleaved frames, row_stride bytes apart; enc = LASS_WAV_*) -> out (B, L_out) mono f32: decode, down-mix,
-// out[n] = sum_m x[m] * taps[n*down - m*up + (n_taps-1)/2].  up == down == 1: no FIR (taps unused).  The caller has checked
-// the arguments (lass_decode_resample); hipErrorInvalidValue for what the kernel's LDS plan cannot hold.
-size_t lass_resample_table_floats(int up, int n_taps);  // the polyphase table in LDS: up * (ceil(n_taps/up) | 1)
-// planar: out (B, ch, L_out) instead, one plane per channel, each bit-identical to the mono call on that channel alone
-hipError_t lass_launch_decode_resample(const void* raw, long long row_stride, int B, int frames, int ch, int enc, int up, int down,
-                                       const float* taps, int n_taps, bool planar, float* out, int L_out, hipStream_t stream);
+// ---- resample.hip, export.hip, limiter.hip, loudness.hip: the audio file kernels ------------------------------------------------
+// The operands are audio_args.h's structs.  P: B recordings x ch planes of L floats (PlaneRows; strides in floats).  F: the
+// rational filter, out[n] = sum_m x[m] * taps[n*down - m*up + (n_taps-1)/2], up == down == 1: none, taps unused (RationalFilter).
+// raw / out / dry: B rows of interleaved frames, enc = LASS_WAV_*, row_stride_bytes apart (PayloadRows); with a dry source the value
+// that goes on is v = fl(x + fl(amount[b] * y)), x sample n*ch + c of the dry row (DrySource; NULL: v = y).  O: the (os, 1)
+// interpolator of polyphase.h's chain, 20*os + 1 device floats (Oversampler).  The entry points of api.hip have checked the
+// arguments (audio_args.h); each launcher keeps a cheap hipErrorInvalidValue guard, and returns it for what its LDS plan cannot hold.
 size_t lass_resample_span_floats(int up, int down, int n_taps, int tile);  // the input frames `tile` outputs reach, in LDS
+// raw -> out (B, L_out) mono f32: decode, down-mix, F.  planar: out (B, ch, L_out), each plane bit-identical to the mono call on it
+hipError_t lass_launch_decode_resample(const PayloadRows& raw, int B, const RationalFilter& F, bool planar, float* out, int L_out,
+                                       hipStream_t stream);
+// P -> out: F per plane, truncated to out.frames, times gain[b] (B device floats; NULL: none, the same bytes as gain 1), quantised
+// as wavio's writers do.  clipped (B counters, may be NULL): += the PCM samples of the row that the clip changed.
+hipError_t lass_launch_encode(const PlaneRows& P, const RationalFilter& F, const DrySource* dry, const float* gain, const PayloadRows& out,
+                              unsigned* clipped, hipStream_t stream);
+// peak[b] = max |v| over the planes of row b and n < frames_out, v what the launcher above quantises without a gain; a NaN is
+// skipped.  peak (B floats) is zero-filled here, then raised by integer atomic max on |v|'s bits.
+hipError_t lass_launch_sample_peak(const PlaneRows& P, const RationalFilter& F, const DrySource* dry, int frames_out, float* peak,
+                                   hipStream_t stream);
+// peak[b] = the larger of that and max |z[k]|, k % os != 0, z = y interpolated by O (y = 0 outside its frames_out frames).  os in
+// {2, 4}; one launch, the y of a tile and its halo in LDS.  hipErrorInvalidValue where lass_resample_true_peak_fits is false:
+bool lass_resample_true_peak_fits(int up, int down, int n_taps, int os);  // a tile of one frame fits the CU's 160 KiB
+hipError_t lass_launch_resample_true_peak(const PlaneRows& P, const RationalFilter& F, int frames_out, const Oversampler& O, float* peak,
+                                          hipStream_t stream);
+// lass_limit's kernel (include/lass_hip.h has the arithmetic): out = fl(fl(g * G) * x) with G the smoothed minimum of the gain that
+// holds g x envelope under `ceiling`; one launch, LASS_LIMITER_TILE frames per workgroup.  out: the output planes (written).
+// min_gain (1) and frames (0) are filled here, on the stream.
+hipError_t lass_launch_limit(const PlaneRows& P, const Oversampler& O, const float* gain, float ceiling, int H, const float* window,
+                             const PlaneRows& out, float* curve, float* envelope, long long curve_row_stride, float* min_gain,
+                             int* frames, hipStream_t stream);
 
-// ---- export.hip ---------------------------------------------------------------------------------------------------
-// planes (B recordings x ch planes of L_in floats; strides in floats) -> out (B rows of frames_out interleaved frames, enc =
-// LASS_WAV_*, out_row_stride bytes apart): the FIR above per plane, truncated to frames_out, quantised as wavio's writers do.
-// clipped (B counters, may be NULL): += the PCM samples of the row that the clip changed.  The caller has checked the arguments
-// (lass_resample_encode).
-hipError_t lass_launch_resample_encode(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L_in,
-                                       int up, int down, const float* taps, int n_taps, int enc, void* out, long long out_row_stride,
-                                       int frames_out, unsigned* clipped, hipStream_t stream);
-// The same with a gain: every y of row b becomes fl(gain[b] * y) before it is quantised (gain: B device floats).  One kernel body
-// with the entry above; gain[b] == 1 gives its bytes.
-hipError_t lass_launch_resample_encode_gain(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L_in,
-                                            int up, int down, const float* taps, int n_taps, int enc, void* out,
-                                            long long out_row_stride, int frames_out, unsigned* clipped, const float* gain,
-                                            hipStream_t stream);
-// peak[b] = max |y| over the planes of row b and n < frames_out, y the value the two entries above quantise (the same kernel body
-// up to where y goes); a NaN is skipped.  peak (B floats) is zero-filled here, then raised by integer atomic max on |y|'s bits.
-hipError_t lass_launch_resample_peak(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L_in, int up,
-                                     int down, const float* taps, int n_taps, int frames_out, float* peak, hipStream_t stream);
-// peak[b] = the larger of max |y| (the entry above) and max |z[k]|, k % os != 0, z[k] = sum_m y[m] * os_taps[k - m*os + 10*os] for
-// k < os * frames_out (y = 0 outside its frames_out frames): y interpolated os times by polyphase.h's chain of (os, 1), phase 0
-// left out.  os in {2, 4}, os_taps: 20*os + 1 device floats.  One launch, the y of a tile and its halo in LDS.
-// hipErrorInvalidValue where lass_resample_true_peak_fits is false.
-hipError_t lass_launch_resample_true_peak(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L_in,
-                                          int up, int down, const float* taps, int n_taps, int frames_out, int os, const float* os_taps,
-                                          int n_os_taps, float* peak, hipStream_t stream);
-// whether a tile of one frame - table, the span of its 21 first-stage outputs, stage, second table - fits the CU's 160 KiB
-bool lass_resample_true_peak_fits(int up, int down, int n_taps, int os);
-// The remix of lass_launch_resample_encode[_gain] and lass_launch_resample_peak (lass_remix_encode, lass_remix_peak): the value
-// that is quantised (times gain[b] first where gain is not NULL) or goes into the peak is v = fl(x + fl(amount[b] * y)), x sample
-// n*ch + c of row b of `dry` (B payload rows of at least frames_out frames, dry_enc = LASS_WAV_*, dry_row_stride bytes apart;
-// amount: B device floats), y the value those entries quantise.  The same kernel bodies and tile plans with one more read stream.
-// The caller has checked the arguments.
-hipError_t lass_launch_remix_encode(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L_in, int up,
-                                    int down, const float* taps, int n_taps, const void* dry, long long dry_row_stride, int dry_enc,
-                                    const float* amount, int enc, const float* gain, void* out, long long out_row_stride,
-                                    int frames_out, unsigned* clipped, hipStream_t stream);
-hipError_t lass_launch_remix_peak(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L_in, int up,
-                                  int down, const float* taps, int n_taps, const void* dry, long long dry_row_stride, int dry_enc,
-                                  const float* amount, int frames_out, float* peak, hipStream_t stream);
-
-// ---- limiter.hip --------------------------------------------------------------------------------------------------
-// lass_limit's kernel (include/lass_hip.h has the arithmetic): out = fl(fl(g * G) * x) with G the smoothed minimum of the gain
-// that holds g x envelope under `ceiling`; one launch, LASS_LIMITER_TILE frames per workgroup.  min_gain (1) and frames (0) are
-// filled here, on the stream.  The caller has checked the arguments (lass_limit).
-hipError_t lass_launch_limit(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L, int os,
-                             const float* os_taps, int n_os_taps, const float* gain, float ceiling, int H, const float* window,
-                             float* out, long long out_row_stride, long long out_plane_stride, float* curve, float* envelope,
-                             long long curve_row_stride, float* min_gain, int* frames, hipStream_t stream);
-
-// ---- loudness.hip -------------------------------------------------------------------------------------------------
 // K-weighting as the kernels take it: the two biquads (b0 b1 b2 a1 a2 of the shelf, then of the high-pass) and the powers of the
 // cascade's 4 x 4 state matrix that carry a state over one lane's samples and over one hop bin, row-major.
 struct LoudnessFilter {
@@ -346,19 +318,18 @@ struct LoudnessFilter {
 int lass_loudness_lanes(int hop);  // lanes of the wave that share a hop bin: the largest divisor of hop up to 64
 // f <- coef and the two powers for `hop`; false for a coefficient that is not finite or a pole on or outside the unit circle
 bool lass_loudness_filter(const double* coef, int hop, LoudnessFilter* f);
-// BS.1770-4 gated loudness of B recordings of ch planes (addressed as lass_launch_resample_encode's), lengths[b] <= L samples
-// each (NULL: L; clamped to 0 ... L): out (B,3) = {LUFS or -inf, blocks, blocks past both gates}; blocks (B, nb_max), optional:
-// the block powers, 0 past a recording's own count.  scratch: 5 * B * ch * (L / hop) doubles.
-hipError_t lass_launch_loudness(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L,
-                                const int* lengths, int hop, const LoudnessFilter& f, const float* weights, double* out,
+// BS.1770-4 gated loudness of P, lengths[b] <= L samples each (NULL: L; clamped to 0 ... L): out (B,3) = {LUFS or -inf, blocks,
+// blocks past both gates}; blocks (B, nb_max), optional: the block powers, 0 past a recording's own count.  scratch: 5 * B * ch *
+// (L / hop) doubles.
+hipError_t lass_launch_loudness(const PlaneRows& P, const int* lengths, int hop, const LoudnessFilter& f, const float* weights, double* out,
                                 double* blocks, int nb_max, double* scratch, hipStream_t stream);
 // The same into columns 0 ... 2 of out (B,10) by the same kernels, then one more kernel, one workgroup per recording: columns
 // 3 ... 9 = {max momentary LUFS, max short-term LUFS, LRA, ns, short-term blocks past both gates, p10, p95} (EBU Tech 3342 on 3 s
 // blocks of 30 bin sums; the two order statistics by an exact radix select).  short_term (B, ns_max), optional: the short-term
 // powers, 0 past a recording's own count.  scratch: (5 * ch + 1) * B * (L / hop) doubles.
-hipError_t lass_launch_loudness_stats(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L,
-                                      const int* lengths, int hop, const LoudnessFilter& f, const float* weights, double* out,
-                                      double* blocks, int nb_max, double* short_term, int ns_max, double* scratch, hipStream_t stream);
+hipError_t lass_launch_loudness_stats(const PlaneRows& P, const int* lengths, int hop, const LoudnessFilter& f, const float* weights,
+                                      double* out, double* blocks, int nb_max, double* short_term, int ns_max, double* scratch,
+                                      hipStream_t stream);
 // lass_loudness_gain's rule, one thread per row
 hipError_t lass_launch_loudness_gain(const double* loudness, const float* peak, int B, double target, float ceiling, float* gain,
                                      int* limited, hipStream_t stream);

@@ -191,12 +191,12 @@ __global__ __launch_bounds__(kThreads) void k_limit(const float* __restrict__ pl
 
 }  // namespace
 
-hipError_t lass_launch_limit(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L, int os,
-                             const float* os_taps, int n_os_taps, const float* gain, float ceiling, int H, const float* window,
-                             float* out, long long out_row_stride, long long out_plane_stride, float* curve, float* envelope,
-                             long long curve_row_stride, float* min_gain, int* frames, hipStream_t stream) {
-    if (B <= 0 || B > 65535 || ch < 1 || ch > 8 || L <= 0 || H < 1 || H > LASS_LIMITER_MAX_H || (os != 1 && os != 2 && os != 4) ||
-        (os > 1 && n_os_taps != 20 * os + 1))
+hipError_t lass_launch_limit(const PlaneRows& P, const Oversampler& O, const float* gain, float ceiling, int H, const float* window,
+                             const PlaneRows& out, float* curve, float* envelope, long long curve_row_stride, float* min_gain,
+                             int* frames, hipStream_t stream) {
+    const int B = P.B, L = P.L, os = O.os;
+    if (B <= 0 || B > 65535 || P.ch < 1 || P.ch > 8 || L <= 0 || H < 1 || H > LASS_LIMITER_MAX_H || (os != 1 && os != 2 && os != 4) ||
+        (os > 1 && O.n_taps != 20 * os + 1))
         return hipErrorInvalidValue;
     hipError_t e;
     if (min_gain) {
@@ -209,8 +209,8 @@ hipError_t lass_launch_limit(const float* planes, long long row_stride, long lon
     }
     const size_t lds = limit_floats(os, H) * sizeof(float);   // 41 KiB at H = 512, os = 4: under the 64 KiB that need no attribute
     const dim3 grid((unsigned)(((long long)L + kLimTile - 1) / kLimTile), B);
-    hipLaunchKernelGGL(os > 1 ? k_limit<true> : k_limit<false>, grid, dim3(kThreads), lds, stream, planes, row_stride, plane_stride, ch, L,
-                       os, os_taps, n_os_taps, gain, ceiling, H, window, out, out_row_stride, out_plane_stride, curve, envelope,
-                       curve_row_stride, reinterpret_cast<unsigned*>(min_gain), frames);
+    hipLaunchKernelGGL(os > 1 ? k_limit<true> : k_limit<false>, grid, dim3(kThreads), lds, stream, P.p, P.row_stride, P.plane_stride, P.ch, L,
+                       os, O.taps, O.n_taps, gain, ceiling, H, window, const_cast<float*>(out.p), out.row_stride, out.plane_stride, curve,
+                       envelope, curve_row_stride, reinterpret_cast<unsigned*>(min_gain), frames);
     return hipGetLastError();
 }

@@ -385,10 +385,9 @@ int lass_loudness_lanes(int hop) {
 }
 
 // The meter up to and including k_gate; out: rows of out_pitch doubles.
-static hipError_t launch_meter(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L,
-                               const int* lengths, int hop, const LoudnessFilter& f, const float* weights, double* out, int out_pitch,
-                               double* blocks, int nb_max, double* scratch, hipStream_t stream) {
-    const int bins_max = L / hop;
+static hipError_t launch_meter(const PlaneRows& P, const int* lengths, int hop, const LoudnessFilter& f, const float* weights, double* out,
+                               int out_pitch, double* blocks, int nb_max, double* scratch, hipStream_t stream) {
+    const int B = P.B, ch = P.ch, L = P.L, bins_max = L / hop;
     if (B <= 0 || ch < 1 || ch > 8 || (long long)B * ch > 65535 || hop < 1 || L < 1) return hipErrorInvalidValue;
     State* states = reinterpret_cast<State*>(scratch);
     double* sums = scratch + (size_t)4 * B * ch * bins_max;
@@ -404,12 +403,12 @@ static hipError_t launch_meter(const float* planes, long long row_stride, long l
         }
         const dim3 grid(bins_max, B * ch);
         if (bins_max > 1) {
-            hipLaunchKernelGGL(k_bins<false>, grid, dim3(kWave), lds, stream, planes, row_stride, plane_stride, ch, L, lengths, hop, nl,
+            hipLaunchKernelGGL(k_bins<false>, grid, dim3(kWave), lds, stream, P.p, P.row_stride, P.plane_stride, ch, L, lengths, hop, nl,
                                S, bins_max, f, states, sums);
         }
         hipLaunchKernelGGL(k_carry, dim3((B * ch + kWave - 1) / kWave), dim3(kWave), 0, stream, B * ch, ch, L, lengths, hop, bins_max,
                            f, states);
-        hipLaunchKernelGGL(k_bins<true>, grid, dim3(kWave), lds, stream, planes, row_stride, plane_stride, ch, L, lengths, hop, nl, S,
+        hipLaunchKernelGGL(k_bins<true>, grid, dim3(kWave), lds, stream, P.p, P.row_stride, P.plane_stride, ch, L, lengths, hop, nl, S,
                            bins_max, f, states, sums);
     }
     hipLaunchKernelGGL(k_gate, dim3(B), dim3(kGateThreads), 0, stream, sums, ch, L, lengths, hop, bins_max > 0 ? bins_max : 1, weights,
@@ -417,22 +416,20 @@ static hipError_t launch_meter(const float* planes, long long row_stride, long l
     return hipGetLastError();
 }
 
-hipError_t lass_launch_loudness(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L,
-                                const int* lengths, int hop, const LoudnessFilter& f, const float* weights, double* out,
+hipError_t lass_launch_loudness(const PlaneRows& P, const int* lengths, int hop, const LoudnessFilter& f, const float* weights, double* out,
                                 double* blocks, int nb_max, double* scratch, hipStream_t stream) {
-    return launch_meter(planes, row_stride, plane_stride, B, ch, L, lengths, hop, f, weights, out, 3, blocks, nb_max, scratch, stream);
+    return launch_meter(P, lengths, hop, f, weights, out, 3, blocks, nb_max, scratch, stream);
 }
 
-hipError_t lass_launch_loudness_stats(const float* planes, long long row_stride, long long plane_stride, int B, int ch, int L,
-                                      const int* lengths, int hop, const LoudnessFilter& f, const float* weights, double* out,
-                                      double* blocks, int nb_max, double* short_term, int ns_max, double* scratch, hipStream_t stream) {
-    hipError_t e = launch_meter(planes, row_stride, plane_stride, B, ch, L, lengths, hop, f, weights, out, 10, blocks, nb_max, scratch,
-                                stream);
+hipError_t lass_launch_loudness_stats(const PlaneRows& P, const int* lengths, int hop, const LoudnessFilter& f, const float* weights,
+                                      double* out, double* blocks, int nb_max, double* short_term, int ns_max, double* scratch,
+                                      hipStream_t stream) {
+    hipError_t e = launch_meter(P, lengths, hop, f, weights, out, 10, blocks, nb_max, scratch, stream);
     if (e != hipSuccess) return e;
-    const int bins_max = L / hop;
-    const double* sums = scratch + (size_t)4 * B * ch * bins_max;
-    hipLaunchKernelGGL(k_range, dim3(B), dim3(kGateThreads), 0, stream, sums, ch, L, lengths, hop, bins_max > 0 ? bins_max : 1, weights,
-                       out, scratch + (size_t)5 * B * ch * bins_max, short_term, ns_max);
+    const int bins_max = P.L / hop;
+    const double* sums = scratch + (size_t)4 * P.B * P.ch * bins_max;
+    hipLaunchKernelGGL(k_range, dim3(P.B), dim3(kGateThreads), 0, stream, sums, P.ch, P.L, lengths, hop, bins_max > 0 ? bins_max : 1,
+                       weights, out, scratch + (size_t)5 * P.B * P.ch * bins_max, short_term, ns_max);
     return hipGetLastError();
 }
 

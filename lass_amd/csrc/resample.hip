@@ -67,11 +67,12 @@ __global__ __launch_bounds__(kThreads) void k_decode_resample(const unsigned cha
 }
 
 template <bool PLANAR>
-hipError_t launch(const unsigned char* raw, long long row_stride, int B, int frames, int ch, int enc, int up, int down,
-                  const float* taps, int n_taps, float* out, int L_out, hipStream_t stream) {
+hipError_t launch(const PayloadRows& rows, int B, const RationalFilter& F, float* out, int L_out, hipStream_t stream) {
+    const unsigned char* raw = static_cast<const unsigned char*>(rows.p);
+    const int up = F.up, down = F.down, n_taps = F.n_taps;
     if (up == 1 && down == 1) {
-        hipLaunchKernelGGL(k_decode<PLANAR>, dim3((frames + kThreads - 1) / kThreads, B), dim3(kThreads), 0, stream, raw, row_stride,
-                           frames, ch, enc, out);
+        hipLaunchKernelGGL(k_decode<PLANAR>, dim3((rows.frames + kThreads - 1) / kThreads, B), dim3(kThreads), 0, stream, raw,
+                           rows.row_stride_bytes, rows.frames, rows.ch, rows.enc, out);
         return hipGetLastError();
     }
     // the largest tile whose input span fits beside the table (one output needs J frames: always fits under the caps)
@@ -80,27 +81,20 @@ hipError_t launch(const unsigned char* raw, long long row_stride, int B, int fra
         return lass_resample_table_floats(up, n_taps) + lass_resample_span_floats(up, down, n_taps, t);
     }, &P);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_decode_resample<PLANAR>, dim3(P.nblk, B), dim3(kThreads), P.lds, stream, raw, row_stride, frames, ch, enc,
-                       up, down, taps, n_taps, P.J, P.tile, out, L_out);
+    hipLaunchKernelGGL(k_decode_resample<PLANAR>, dim3(P.nblk, B), dim3(kThreads), P.lds, stream, raw, rows.row_stride_bytes, rows.frames,
+                       rows.ch, rows.enc, up, down, F.taps, n_taps, P.J, P.tile, out, L_out);
     return hipGetLastError();
 }
 
 }  // namespace
-
-size_t lass_resample_table_floats(int up, int n_taps) {
-    const int J = (n_taps + up - 1) / up;
-    return (size_t)up * (size_t)(J | 1);
-}
 
 size_t lass_resample_span_floats(int up, int down, int n_taps, int tile) {
     const int J = (n_taps + up - 1) / up;
     return ((size_t)(up - 1) + (size_t)(tile - 1) * down) / up + J;
 }
 
-hipError_t lass_launch_decode_resample(const void* raw, long long row_stride, int B, int frames, int ch, int enc, int up, int down,
-                                       const float* taps, int n_taps, bool planar, float* out, int L_out, hipStream_t stream) {
-    if (B <= 0 || B > 65535 || frames <= 0 || L_out <= 0 || up < 1 || down < 1 || ch < 1) return hipErrorInvalidValue;
-    const unsigned char* r = static_cast<const unsigned char*>(raw);
-    return planar ? launch<true>(r, row_stride, B, frames, ch, enc, up, down, taps, n_taps, out, L_out, stream)
-                  : launch<false>(r, row_stride, B, frames, ch, enc, up, down, taps, n_taps, out, L_out, stream);
+hipError_t lass_launch_decode_resample(const PayloadRows& raw, int B, const RationalFilter& F, bool planar, float* out, int L_out,
+                                       hipStream_t stream) {
+    if (B <= 0 || B > 65535 || raw.frames <= 0 || L_out <= 0 || F.up < 1 || F.down < 1 || raw.ch < 1) return hipErrorInvalidValue;
+    return planar ? launch<true>(raw, B, F, out, L_out, stream) : launch<false>(raw, B, F, out, L_out, stream);
 }

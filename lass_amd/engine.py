@@ -2,6 +2,7 @@
 to liblass_hip.  torch is plumbing here (device memory, streams); every number is produced by the HIP kernels."""
 from __future__ import annotations
 
+from collections import namedtuple
 from ctypes import byref, c_char_p, c_double, c_int, c_int64, c_size_t, c_void_p
 from typing import Dict, Optional
 
@@ -17,6 +18,12 @@ def _ptr(t: Optional[torch.Tensor]):
 
 def _stream(device) -> c_void_p:
     return c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+# The leading arguments of every export entry of the C layer, and the dry source's of the two remix entries, in the order of
+# include/lass_hip.h under its names: built by keyword, handed over with *.
+_ExportHead = namedtuple("_ExportHead", "planes row_stride plane_stride B channels L_in up down taps n_taps")
+_DryArgs = namedtuple("_DryArgs", "dry dry_row_stride_bytes dry_encoding amount")
 
 
 class Engine:
@@ -643,11 +650,7 @@ class Engine:
             raise _lib.LassError("raw_u8 rows are shorter than frames x channels samples")
         up, down = rs.ratio(rate_in, rate_out)
         L_out = rs.out_len(frames, up, down)
-        fir = (up, down) != (1, 1)
-        if fir and not rs.within_cap(up, down):
-            raise _lib.LassError(f"resampling {rate_in} -> {rate_out} Hz needs {rs.n_taps(up, down)} taps, over the device "
-                                 f"kernel's cap of {rs.MAX_TAPS}: resample on the host (wavio.read_wav)")
-        taps = rs.device_taps(up, down, self.device) if fir else None
+        taps = self._taps(rate_in, rate_out, "wavio.read_wav")
         shape = (B, int(channels), L_out) if planar else (B, L_out)
         if out is None:
             out = _alloc.empty(shape, dtype=torch.float32, device=self.device)
@@ -657,9 +660,21 @@ class Engine:
         stride = raw_u8.stride(0) if B > 1 else (raw_u8.shape[1] + 3) // 4 * 4  # (one row: no stride to honour)
         name = "lass_decode_resample_planar" if planar else "lass_decode_resample"
         rc = getattr(self.lib, name)(self.ctx, _ptr(raw_u8), stride, B, int(frames), int(channels), rs.ENCODINGS[encoding], up, down,
-                                     _ptr(taps), taps.numel() if fir else 1, _ptr(out), L_out, _stream(self.device))
+                                     _ptr(taps), 1 if taps is None else taps.numel(), _ptr(out), L_out, _stream(self.device))
         _lib.check(self.ctx, rc, name)
         return out
+
+    def _taps(self, rate_in: int, rate_out: int, host: str):
+        """The filter of the ratio on the device, None where there is none; a ratio beyond the kernel's tap cap raises LassError,
+        which names `host`, the host function to use instead."""
+        from . import resample as rs
+        up, down = rs.ratio(rate_in, rate_out)
+        if (up, down) == (1, 1):
+            return None
+        if not rs.within_cap(up, down):
+            raise _lib.LassError(f"resampling {rate_in} -> {rate_out} Hz needs {rs.n_taps(up, down)} taps, over the device "
+                                 f"kernel's cap of {rs.MAX_TAPS}: resample on the host ({host})")
+        return rs.device_taps(up, down, self.device)
 
     def resample(self, x: torch.Tensor, rate_in: int, rate_out: int) -> torch.Tensor:
         """(B, L) or (L,) float32 at rate_in -> float32 at rate_out: the mono float32 case of `decode_resample`."""
@@ -668,6 +683,59 @@ class Engine:
         x = x[None] if one else x
         y = self.decode_resample(x.view(torch.uint8), x.shape[1], 1, "f32", rate_in, rate_out)
         return y[0] if one else y
+
+    def _planes(self, planes: torch.Tensor):
+        """(planes as (B, C, L), row stride, plane stride) of a (B, C, L) or (C, L) float32 tensor with contiguous samples."""
+        if planes.dim() == 2:
+            planes = planes[None]
+        if planes.device != self.device or planes.dtype != torch.float32 or planes.dim() != 3 or planes.stride(2) != 1:
+            raise _lib.LassError(f"planes must be a (B, C, L) or (C, L) float32 tensor on {self.device} with contiguous samples")
+        B, C, L = planes.shape
+        plane_stride = planes.stride(1) if C > 1 else L                      # (one plane, one row: no stride to honour)
+        row_stride = planes.stride(0) if B > 1 else (C - 1) * plane_stride + L
+        return planes, row_stride, plane_stride
+
+    def _export_plan(self, planes, rate_in: int, rate_out: int, frames_out, encoding: Optional[str] = None):
+        """What the export methods share, with their refusals in their order: (head, B, C, frames_out) - head the leading arguments
+        of every export entry of the C layer (planes, row stride, plane stride, B, C, L, up, down, taps, n_taps; taps NULL and 1
+        without a filter), frames_out defaulted to its ceiling ceil(L * up / down) and held under it."""
+        from . import resample as rs
+        planes, row_stride, plane_stride = self._planes(planes)
+        if encoding is not None and encoding not in rs.ENCODINGS:
+            raise _lib.LassError(f"encoding must be one of {sorted(rs.ENCODINGS)}")
+        B, C, L = planes.shape
+        up, down = rs.ratio(rate_in, rate_out)
+        ceiling = rs.out_len(L, up, down)
+        frames_out = ceiling if frames_out is None else int(frames_out)
+        if not 1 <= frames_out <= ceiling:
+            raise _lib.LassError(f"frames_out must lie in 1 ... ceil(L * up / down) = {ceiling}")
+        taps = self._taps(rate_in, rate_out, "wavio.write_wav_*")
+        head = _ExportHead(planes=_ptr(planes), row_stride=row_stride, plane_stride=plane_stride, B=B, channels=C, L_in=L, up=up,
+                           down=down, taps=_ptr(taps), n_taps=1 if taps is None else taps.numel())
+        return head, B, C, frames_out
+
+    def _per_row(self, name: str, t: torch.Tensor, B: int, dtype) -> None:
+        """Refuse `name` unless it is a contiguous (B,) tensor of dtype on the device."""
+        if tuple(t.shape) != (B,) or t.dtype != dtype or t.device != self.device or not t.is_contiguous():
+            raise _lib.LassError(f"{name} must be a contiguous {str(dtype).split('.')[-1]} ({B},) tensor on {self.device}")
+
+    def _payload_rows(self, name: str, t: torch.Tensor, B: int, row_bytes: int) -> int:
+        """Refuse `name` unless it is a (B, >= row_bytes) uint8 tensor on the device with contiguous rows; its row stride in bytes."""
+        if (t.dim() != 2 or t.shape[0] != B or t.shape[1] < row_bytes or t.dtype != torch.uint8 or t.device != self.device
+                or t.stride(1) != 1):
+            raise _lib.LassError(f"{name} must be a ({B}, >= {row_bytes}) uint8 tensor on {self.device} with contiguous rows")
+        return t.stride(0) if B > 1 else (row_bytes + 3) // 4 * 4            # (one row: no stride to honour)
+
+    def _encode_tail(self, B: int, row_bytes: int, out, clipped, gain):
+        """The trailing arguments of the encode entries, checked: (out, allocated if None; its row stride)."""
+        if out is None:
+            out = _alloc.empty(B, (row_bytes + 3) // 4 * 4, dtype=torch.uint8, device=self.device)
+        out_stride = self._payload_rows("out", out, B, row_bytes)
+        if clipped is not None:
+            self._per_row("clipped", clipped, B, torch.int32)
+        if gain is not None:
+            self._per_row("gain", gain, B, torch.float32)
+        return out, out_stride
 
     def resample_encode(self, planes: torch.Tensor, rate_in: int, rate_out: int, encoding: str, frames_out: Optional[int] = None,
                         out: Optional[torch.Tensor] = None, clipped: Optional[torch.Tensor] = None,
@@ -682,104 +750,40 @@ class Engine:
         lass_resample_encode, as ever).  The filter is lass_amd.resample.design_taps; a ratio beyond the kernel's tap cap raises
         LassError (resample.within_cap tells beforehand)."""
         from . import resample as rs
-        planes, row_stride, plane_stride = self._planes(planes)
-        if encoding not in rs.ENCODINGS:
-            raise _lib.LassError(f"encoding must be one of {sorted(rs.ENCODINGS)}")
-        B, C, L = planes.shape
-        up, down = rs.ratio(rate_in, rate_out)
-        ceiling = rs.out_len(L, up, down)
-        frames_out = ceiling if frames_out is None else int(frames_out)
-        if not 1 <= frames_out <= ceiling:
-            raise _lib.LassError(f"frames_out must lie in 1 ... ceil(L * up / down) = {ceiling}")
-        fir = (up, down) != (1, 1)
-        if fir and not rs.within_cap(up, down):
-            raise _lib.LassError(f"resampling {rate_in} -> {rate_out} Hz needs {rs.n_taps(up, down)} taps, over the device "
-                                 f"kernel's cap of {rs.MAX_TAPS}: resample on the host (wavio.write_wav_*)")
-        taps = rs.device_taps(up, down, self.device) if fir else None
+        head, B, C, frames_out = self._export_plan(planes, rate_in, rate_out, frames_out, encoding)
         row_bytes = frames_out * C * rs.SAMPLE_BYTES[encoding]
-        if out is None:
-            out = _alloc.empty(B, (row_bytes + 3) // 4 * 4, dtype=torch.uint8, device=self.device)
-        elif (out.dim() != 2 or out.shape[0] != B or out.shape[1] < row_bytes or out.dtype != torch.uint8 or out.device != self.device
-              or out.stride(1) != 1):
-            raise _lib.LassError(f"out must be a ({B}, >= {row_bytes}) uint8 tensor on {self.device} with contiguous rows")
-        if clipped is not None and (tuple(clipped.shape) != (B,) or clipped.dtype != torch.int32 or clipped.device != self.device
-                                    or not clipped.is_contiguous()):
-            raise _lib.LassError(f"clipped must be a contiguous int32 ({B},) tensor on {self.device}")
-        out_stride = out.stride(0) if B > 1 else (row_bytes + 3) // 4 * 4
+        out, out_stride = self._encode_tail(B, row_bytes, out, clipped, gain)
+        tail = (_ptr(out), out_stride, frames_out, _ptr(clipped), _stream(self.device))
         if gain is not None:
-            if tuple(gain.shape) != (B,) or gain.dtype != torch.float32 or gain.device != self.device or not gain.is_contiguous():
-                raise _lib.LassError(f"gain must be a contiguous float32 ({B},) tensor on {self.device}")
-            rc = self.lib.lass_resample_encode_gain(self.ctx, _ptr(planes), row_stride, plane_stride, B, C, L, up, down, _ptr(taps),
-                                                    taps.numel() if fir else 1, rs.ENCODINGS[encoding], _ptr(gain), _ptr(out),
-                                                    out_stride, frames_out, _ptr(clipped), _stream(self.device))
+            rc = self.lib.lass_resample_encode_gain(self.ctx, *head, rs.ENCODINGS[encoding], _ptr(gain), *tail)
             _lib.check(self.ctx, rc, "lass_resample_encode_gain")
-            return out[:, :row_bytes]
-        rc = self.lib.lass_resample_encode(self.ctx, _ptr(planes), row_stride, plane_stride, B, C, L, up, down, _ptr(taps),
-                                           taps.numel() if fir else 1, rs.ENCODINGS[encoding], _ptr(out), out_stride, frames_out,
-                                           _ptr(clipped), _stream(self.device))
-        _lib.check(self.ctx, rc, "lass_resample_encode")
+        else:
+            rc = self.lib.lass_resample_encode(self.ctx, *head, rs.ENCODINGS[encoding], *tail)
+            _lib.check(self.ctx, rc, "lass_resample_encode")
         return out[:, :row_bytes]
-
-    def _planes(self, planes: torch.Tensor):
-        """(planes as (B, C, L), row stride, plane stride) of a (B, C, L) or (C, L) float32 tensor with contiguous samples."""
-        if planes.dim() == 2:
-            planes = planes[None]
-        if planes.device != self.device or planes.dtype != torch.float32 or planes.dim() != 3 or planes.stride(2) != 1:
-            raise _lib.LassError(f"planes must be a (B, C, L) or (C, L) float32 tensor on {self.device} with contiguous samples")
-        B, C, L = planes.shape
-        plane_stride = planes.stride(1) if C > 1 else L                      # (one plane, one row: no stride to honour)
-        row_stride = planes.stride(0) if B > 1 else (C - 1) * plane_stride + L
-        return planes, row_stride, plane_stride
 
     def resample_peak(self, planes: torch.Tensor, rate_in: int, rate_out: int, frames_out: Optional[int] = None) -> torch.Tensor:
         """(B,) float32: max |y| over the channels and the first frames_out frames of each recording, y the very float32 values
         `resample_encode` of the same arguments quantises (lass_resample_peak); a NaN is skipped."""
-        from . import resample as rs
-        planes, row_stride, plane_stride = self._planes(planes)
-        B, C, L = planes.shape
-        up, down = rs.ratio(rate_in, rate_out)
-        ceiling = rs.out_len(L, up, down)
-        frames_out = ceiling if frames_out is None else int(frames_out)
-        if not 1 <= frames_out <= ceiling:
-            raise _lib.LassError(f"frames_out must lie in 1 ... ceil(L * up / down) = {ceiling}")
-        fir = (up, down) != (1, 1)
-        if fir and not rs.within_cap(up, down):
-            raise _lib.LassError(f"resampling {rate_in} -> {rate_out} Hz needs {rs.n_taps(up, down)} taps, over the device "
-                                 f"kernel's cap of {rs.MAX_TAPS}")
-        taps = rs.device_taps(up, down, self.device) if fir else None
+        head, B, _, frames_out = self._export_plan(planes, rate_in, rate_out, frames_out)
         peak = _alloc.empty(B, dtype=torch.float32, device=self.device)
-        rc = self.lib.lass_resample_peak(self.ctx, _ptr(planes), row_stride, plane_stride, B, C, L, up, down, _ptr(taps),
-                                         taps.numel() if fir else 1, frames_out, _ptr(peak), _stream(self.device))
+        rc = self.lib.lass_resample_peak(self.ctx, *head, frames_out, _ptr(peak), _stream(self.device))
         _lib.check(self.ctx, rc, "lass_resample_peak")
         return peak
 
     def _remix_args(self, planes, rate_in, rate_out, dry, dry_encoding, amount, frames_out):
-        """What `remix_encode` and `remix_peak` share: (planes, row stride, plane stride, up, down, taps or None, frames_out, dry
-        stride), with `resample_encode`'s refusals and those of the dry source."""
+        """What `remix_encode` and `remix_peak` share: `_export_plan`'s result and the dry source's arguments (dry, row stride,
+        encoding, amount), with `resample_encode`'s refusals and those of the dry source."""
         from . import resample as rs
-        planes, row_stride, plane_stride = self._planes(planes)
-        B, C, L = planes.shape
-        up, down = rs.ratio(rate_in, rate_out)
-        ceiling = rs.out_len(L, up, down)
-        frames_out = ceiling if frames_out is None else int(frames_out)
-        if not 1 <= frames_out <= ceiling:
-            raise _lib.LassError(f"frames_out must lie in 1 ... ceil(L * up / down) = {ceiling}")
-        fir = (up, down) != (1, 1)
-        if fir and not rs.within_cap(up, down):
-            raise _lib.LassError(f"resampling {rate_in} -> {rate_out} Hz needs {rs.n_taps(up, down)} taps, over the device "
-                                 f"kernel's cap of {rs.MAX_TAPS}: resample on the host (wavio.write_wav_*)")
+        head, B, C, frames_out = self._export_plan(planes, rate_in, rate_out, frames_out)
         if dry_encoding not in rs.ENCODINGS:
             raise _lib.LassError(f"dry_encoding must be one of {sorted(rs.ENCODINGS)}")
-        dry_bytes = frames_out * C * rs.SAMPLE_BYTES[dry_encoding]
         if dry.dim() == 1:
             dry = dry[None]
-        if (dry.dim() != 2 or dry.shape[0] != B or dry.shape[1] < dry_bytes or dry.dtype != torch.uint8 or dry.device != self.device
-                or dry.stride(1) != 1):
-            raise _lib.LassError(f"dry must be a ({B}, >= {dry_bytes}) uint8 tensor on {self.device} with contiguous rows")
-        if tuple(amount.shape) != (B,) or amount.dtype != torch.float32 or amount.device != self.device or not amount.is_contiguous():
-            raise _lib.LassError(f"amount must be a contiguous float32 ({B},) tensor on {self.device}")
-        dry_stride = dry.stride(0) if B > 1 else (dry_bytes + 3) // 4 * 4     # (one row: no stride to honour)
-        return planes, row_stride, plane_stride, up, down, (rs.device_taps(up, down, self.device) if fir else None), frames_out, dry, dry_stride
+        dry_stride = self._payload_rows("dry", dry, B, frames_out * C * rs.SAMPLE_BYTES[dry_encoding])
+        self._per_row("amount", amount, B, torch.float32)
+        dry_args = _DryArgs(dry=_ptr(dry), dry_row_stride_bytes=dry_stride, dry_encoding=rs.ENCODINGS[dry_encoding], amount=_ptr(amount))
+        return head, B, C, frames_out, dry_args
 
     def remix_encode(self, planes: torch.Tensor, rate_in: int, rate_out: int, encoding: str, dry: torch.Tensor, dry_encoding: str,
                      amount: torch.Tensor, frames_out: Optional[int] = None, out: Optional[torch.Tensor] = None,
@@ -794,25 +798,10 @@ class Engine:
         from . import resample as rs
         if encoding not in rs.ENCODINGS:
             raise _lib.LassError(f"encoding must be one of {sorted(rs.ENCODINGS)}")
-        planes, row_stride, plane_stride, up, down, taps, frames_out, dry, dry_stride = self._remix_args(
-            planes, rate_in, rate_out, dry, dry_encoding, amount, frames_out)
-        B, C, L = planes.shape
+        head, B, C, frames_out, dry_args = self._remix_args(planes, rate_in, rate_out, dry, dry_encoding, amount, frames_out)
         row_bytes = frames_out * C * rs.SAMPLE_BYTES[encoding]
-        if out is None:
-            out = _alloc.empty(B, (row_bytes + 3) // 4 * 4, dtype=torch.uint8, device=self.device)
-        elif (out.dim() != 2 or out.shape[0] != B or out.shape[1] < row_bytes or out.dtype != torch.uint8 or out.device != self.device
-              or out.stride(1) != 1):
-            raise _lib.LassError(f"out must be a ({B}, >= {row_bytes}) uint8 tensor on {self.device} with contiguous rows")
-        if clipped is not None and (tuple(clipped.shape) != (B,) or clipped.dtype != torch.int32 or clipped.device != self.device
-                                    or not clipped.is_contiguous()):
-            raise _lib.LassError(f"clipped must be a contiguous int32 ({B},) tensor on {self.device}")
-        if gain is not None and (tuple(gain.shape) != (B,) or gain.dtype != torch.float32 or gain.device != self.device
-                                 or not gain.is_contiguous()):
-            raise _lib.LassError(f"gain must be a contiguous float32 ({B},) tensor on {self.device}")
-        out_stride = out.stride(0) if B > 1 else (row_bytes + 3) // 4 * 4
-        rc = self.lib.lass_remix_encode(self.ctx, _ptr(planes), row_stride, plane_stride, B, C, L, up, down, _ptr(taps),
-                                        taps.numel() if taps is not None else 1, _ptr(dry), dry_stride, rs.ENCODINGS[dry_encoding],
-                                        _ptr(amount), rs.ENCODINGS[encoding], _ptr(gain), _ptr(out), out_stride, frames_out,
+        out, out_stride = self._encode_tail(B, row_bytes, out, clipped, gain)
+        rc = self.lib.lass_remix_encode(self.ctx, *head, *dry_args, rs.ENCODINGS[encoding], _ptr(gain), _ptr(out), out_stride, frames_out,
                                         _ptr(clipped), _stream(self.device))
         _lib.check(self.ctx, rc, "lass_remix_encode")
         return out[:, :row_bytes]
@@ -821,14 +810,9 @@ class Engine:
                    frames_out: Optional[int] = None) -> torch.Tensor:
         """(B,) float32: max |v| over the channels and the first frames_out frames of each recording, v the very float32 values
         `remix_encode` of the same arguments (without a gain) quantises (lass_remix_peak); a NaN is skipped."""
-        from . import resample as rs
-        planes, row_stride, plane_stride, up, down, taps, frames_out, dry, dry_stride = self._remix_args(
-            planes, rate_in, rate_out, dry, dry_encoding, amount, frames_out)
-        B, C, L = planes.shape
+        head, B, _, frames_out, dry_args = self._remix_args(planes, rate_in, rate_out, dry, dry_encoding, amount, frames_out)
         peak = _alloc.empty(B, dtype=torch.float32, device=self.device)
-        rc = self.lib.lass_remix_peak(self.ctx, _ptr(planes), row_stride, plane_stride, B, C, L, up, down, _ptr(taps),
-                                      taps.numel() if taps is not None else 1, _ptr(dry), dry_stride, rs.ENCODINGS[dry_encoding],
-                                      _ptr(amount), frames_out, _ptr(peak), _stream(self.device))
+        rc = self.lib.lass_remix_peak(self.ctx, *head, *dry_args, frames_out, _ptr(peak), _stream(self.device))
         _lib.check(self.ctx, rc, "lass_remix_peak")
         return peak
 
@@ -843,22 +827,10 @@ class Engine:
         os_ = ld.oversampling(rate_out)
         if os_ == 1:
             return self.resample_peak(planes, rate_in, rate_out, frames_out)
-        planes, row_stride, plane_stride = self._planes(planes)
-        B, C, L = planes.shape
-        up, down = rs.ratio(rate_in, rate_out)
-        ceiling = rs.out_len(L, up, down)
-        frames_out = ceiling if frames_out is None else int(frames_out)
-        if not 1 <= frames_out <= ceiling:
-            raise _lib.LassError(f"frames_out must lie in 1 ... ceil(L * up / down) = {ceiling}")
-        fir = (up, down) != (1, 1)
-        if fir and not rs.within_cap(up, down):
-            raise _lib.LassError(f"resampling {rate_in} -> {rate_out} Hz needs {rs.n_taps(up, down)} taps, over the device "
-                                 f"kernel's cap of {rs.MAX_TAPS}")
-        taps = rs.device_taps(up, down, self.device) if fir else None
+        head, B, _, frames_out = self._export_plan(planes, rate_in, rate_out, frames_out)
         os_taps = rs.device_taps(os_, 1, self.device)
         peak = _alloc.empty(B, dtype=torch.float32, device=self.device)
-        rc = self.lib.lass_resample_true_peak(self.ctx, _ptr(planes), row_stride, plane_stride, B, C, L, up, down, _ptr(taps),
-                                              taps.numel() if fir else 1, frames_out, os_, _ptr(os_taps), os_taps.numel(), _ptr(peak),
+        rc = self.lib.lass_resample_true_peak(self.ctx, *head, frames_out, os_, _ptr(os_taps), os_taps.numel(), _ptr(peak),
                                               _stream(self.device))
         _lib.check(self.ctx, rc, "lass_resample_true_peak")
         return peak
@@ -963,8 +935,7 @@ class Engine:
         H = int(lookahead)
         if not 1 <= H <= ld.LIMITER_MAX_REACH:
             raise _lib.LassError(f"lookahead must lie in 1 ... {ld.LIMITER_MAX_REACH} frames")
-        if tuple(gain.shape) != (B,) or gain.dtype != torch.float32 or gain.device != self.device or not gain.is_contiguous():
-            raise _lib.LassError(f"gain must be a contiguous float32 ({B},) tensor on {self.device}")
+        self._per_row("gain", gain, B, torch.float32)
         os_ = ld.oversampling(rate) if peak == "true" else 1
         os_taps = rs.device_taps(os_, 1, self.device) if os_ > 1 else None
         key = (H, str(self.device))
