@@ -216,6 +216,39 @@ int lass_separate_windows_faded(lass_ctx* ctx, const float* recording, int64_t t
                                 const int* fade, const float* ramp, int F, const float* condition /* (B,512) */,
                                 float* out /* total floats */, int B, int W, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- linked channels: one mask from a guide signal, applied to every channel ------------------------ */
+
+/* A multi-channel recording as ONE separation: a GUIDE signal (the caller's: the mono down-mix, a mid signal, ...) decides the
+ * mask, and `channels` PLANES are masked with it.  For each clip or window b the network runs exactly as in the unlinked call on
+ * the guide - x0 = bn0(|STFT(guide_b)|), condition[b] - but its output head meets a unit spectrum (mag = 1, cos = 1, sin = 0), so
+ * what it leaves in out_real / out_imag is the complex mask M_b itself, (T, n_fft/2+1), Nyquist column 0.  For each channel c:
+ *   X = STFT(plane_{c,b})                          the front end's own transform (the bits of lass_stft_magphase's real / imag)
+ *   Y_re = fl(fl(X_re M_re) - fl(X_im M_im))       four products and two sums, each rounded once, no fused multiply-add
+ *   Y_im = fl(fl(X_re M_im) + fl(X_im M_re))       (rows beyond a ragged clip's own frames are exact zeros)
+ *   out_c = the iSTFT of the call's clip form      kept ranges, zero tails and fade regions as in the unlinked call
+ * Channel c's input is laid out exactly like the guide - (B, L) rows, or one row of `total` floats - and starts c * plane_stride
+ * floats after `planes`; its output is laid out the same way and starts c * out_plane_stride floats after `out`.  A plane's result
+ * does not depend on the other planes or on `channels`.  1 <= channels <= LASS_MAX_LINKED_CHANNELS (the export kernels' limit).
+ * ResUNet30 contexts at both STFT geometries, all compute modes, lass_workspace_bytes(B, L) as for the unlinked calls; the
+ * half-batch split offsets the planes as it offsets the guide, and the graph key gains the planes pointer, the two strides and the
+ * channel count.  The mask costs one network pass whatever `channels`; each channel adds one STFT and one iSTFT launch.
+ * Workspace taps after a linked call (lass_workspace_tensor): "out_real" / "out_imag" hold M; "mag" / "cos" / "sin" are SCRATCH
+ * (the unit spectrum until the head has run, then the last channel's Y_re / Y_im in "mag" / "cos").
+ * LASS_ERR_ARG, nothing launched and nothing written: whatever the unlinked call refuses, a null `planes`, channels outside
+ * 1 ... 8, a plane stride (either one) shorter than one channel's array (B * L, or total), `out` (any channel's) overlapping the
+ * guide or any input plane, a multi-STFT context. */
+#define LASS_MAX_LINKED_CHANNELS 8
+/* lengths: DEVICE int32 (B) as in lass_separate_ragged, or NULL: every clip is L samples long (the dense form) */
+int lass_separate_ragged_linked(lass_ctx* ctx, const float* guide /* (B,L) */, const int* lengths, const float* planes,
+                                int64_t plane_stride, int channels, const float* condition /* (B,512) */, float* out,
+                                int64_t out_plane_stride, int B, int L, void* workspace, size_t workspace_bytes, void* stream);
+/* starts, keep as in lass_separate_windows; fade, ramp, F as in lass_separate_windows_faded, given together, or both NULL (F is
+ * then ignored): hard seams.  With fades every output plane must hold 0 in the fade regions beforehand. */
+int lass_separate_windows_linked(lass_ctx* ctx, const float* guide /* total floats */, int64_t total, const int64_t* starts,
+                                 const int* keep, const int* fade, const float* ramp, int F, const float* planes,
+                                 int64_t plane_stride, int channels, const float* condition /* (B,512) */, float* out,
+                                 int64_t out_plane_stride, int B, int W, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Graph replay.  The third consecutive lass_separate call with the same pointers and shape is captured into a hipGraph
  * and replayed on the caller's stream from then on (one graph per context; a different combination is captured anew
  * after it, too, has been seen three times in a row).  Nothing else about the call changes; profiled
@@ -373,6 +406,15 @@ int lass_istft_windows(lass_ctx* ctx, const float* real, const float* imag, cons
 int lass_istft_windows_faded(lass_ctx* ctx, const float* real, const float* imag, const int64_t* starts, const int* keep,
                              const int* fade, const float* ramp, int F, int64_t total, int B, int T, int W, int n_fft,
                              int win_length, float* out, void* stream);
+
+/* The per-channel stage of the linked calls, for callers with a mask of their own: plane (B,L) and the complex mask m_re, m_im
+ * (B,T,n_fft/2+1) -> y_re, y_im (B,T,n_fft/2+1), Y = STFT(plane) * M by the rule of lass_separate_ragged_linked, with the context's
+ * transform (ResUNet30 contexts only).  lengths: DEVICE int32 (B) or NULL = dense; rows beyond a ragged clip's frames are 0. */
+int lass_masked_stft(lass_ctx* ctx, const float* plane, const int* lengths, int B, int L, const float* m_re, const float* m_im,
+                     float* y_re, float* y_im, void* stream);
+/* ... for the windows recording[starts[b] .. starts[b] + W) of one row of `total` floats (starts clamped as everywhere) */
+int lass_masked_stft_windows(lass_ctx* ctx, const float* recording, int64_t total, const int64_t* starts, int B, int W,
+                             const float* m_re, const float* m_im, float* y_re, float* y_im, void* stream);
 
 /* Where lass_separate(B, L) leaves a named intermediate inside the caller's workspace (f32 compute mode; in the bf16
  * modes several of these hold blocked bf16 data instead): byte offset, shape (B,C,H,W) and element strides.  Names:

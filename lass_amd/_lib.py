@@ -40,6 +40,13 @@ SYMBOLS = [
                                             c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     ("lass_istft_windows_faded", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64,
                                          c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    ("lass_separate_ragged_linked", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int,
+                                            c_int, c_void_p, c_size_t, c_void_p]),
+    ("lass_separate_windows_linked", c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                             c_int64, c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    ("lass_masked_stft", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("lass_masked_stft_windows", c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p]),
     ("lass_stft_magphase", c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_void_p]),
     ("lass_mix_at_snr", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),

@@ -796,7 +796,7 @@ int compose_head(lass_ctx* c, int Q, bool sc, HeadHost* h) {
 
 extern "C" {
 
-int lass_version(void) { return 10900; }  // 1.9.0: EBU R 128 figures (lass_resample_true_peak, lass_loudness_stats); 1.8.0: levelled export (lass_loudness, lass_resample_peak, lass_loudness_gain, lass_resample_encode_gain); 1.7.0: cross-faded window seams (lass_separate_windows_faded, lass_istft_windows_faded); 1.6.0: ResUNet30 at the (2048, 320) STFT geometry (lass_create_stft, lass_stft_geometry); 1.5.0: windows of one long row (lass_separate_windows & co); 1.4.0: per-clip lengths (lass_separate_ragged & co); 1.3.0: CLAP text tower (lass_text_*, text.hip); 1.2.0: F(4x4,3x3) kernels, lass_set_graph_replay (1.1.0: multi-STFT model, fused iSTFT, graph replay)
+int lass_version(void) { return 11000; }  // 1.10.0: linked channels (lass_separate_ragged_linked, lass_separate_windows_linked, lass_masked_stft, lass_masked_stft_windows); 1.9.0: EBU R 128 figures (lass_resample_true_peak, lass_loudness_stats); 1.8.0: levelled export (lass_loudness, lass_resample_peak, lass_loudness_gain, lass_resample_encode_gain); 1.7.0: cross-faded window seams (lass_separate_windows_faded, lass_istft_windows_faded); 1.6.0: ResUNet30 at the (2048, 320) STFT geometry (lass_create_stft, lass_stft_geometry); 1.5.0: windows of one long row (lass_separate_windows & co); 1.4.0: per-clip lengths (lass_separate_ragged & co); 1.3.0: CLAP text tower (lass_text_*, text.hip); 1.2.0: F(4x4,3x3) kernels, lass_set_graph_replay (1.1.0: multi-STFT model, fused iSTFT, graph replay)
 
 const char* lass_last_error(const lass_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_err.c_str(); }
 
@@ -1550,7 +1550,14 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
         ProfScope ps(c, st, P_STFT);
         float* x0k[kMaxBranches];
         for (int k = 0; k < nbr; ++k) x0k[k] = F(pl.x0[k]);
-        HIP_TRY(c, launch_front_end(c, mixture, cf, x0k, F(pl.mag), F(pl.cosv), F(pl.sinv), st));
+        if (cf.planes) {
+            // linked channels: the network reads the guide's magnitude through x0 alone, and the head meets the unit spectrum
+            // (mag = cos = 1, sin = 0, filled on every call, replays included) - out_real / out_imag are then the mask itself
+            HIP_TRY(c, launch_front_end(c, mixture, cf, x0k, nullptr, nullptr, nullptr, st));
+            HIP_TRY(c, lass_launch_unit_spectrum(F(pl.mag), F(pl.cosv), F(pl.sinv), (size_t)B * T * g.nbins, st));
+        } else {
+            HIP_TRY(c, launch_front_end(c, mixture, cf, x0k, F(pl.mag), F(pl.cosv), F(pl.sinv), st));
+        }
     } else {
         ProfScope ps(c, st, P_STFT);
         for (int k = 0; k < nbr; ++k) {
@@ -1657,6 +1664,22 @@ static int separate_impl(lass_ctx* c, const float* mixture, const Components* co
         if (r) return r;
         x = F(pl.decout[d]);
     }
+    if (cf.planes) {
+        // The head has read the unit spectrum: its three planes now serve as the Y scratch of one channel at a time (two of them),
+        // Y = STFT(plane) * M, which the iSTFT of the call's own form turns into that channel's output.  One launch pair per
+        // channel, in stream order: the scratch holds one channel's spectrum.
+        for (int ch = 0; ch < cf.channels; ++ch) {
+            {
+                ProfScope ps(c, st, P_STFT);
+                HIP_TRY(c, lass_launch_masked_stft(cf.planes + (size_t)ch * cf.plane_stride, cf, g.nfft, g.hop, T, g.wins[g.mask_br],
+                                                   F(pl.oreal), F(pl.oimag), F(pl.mag), F(pl.cosv), c->tw2k, st));
+            }
+            ProfScope ps(c, st, P_ISTFT);
+            HIP_TRY(c, lass_launch_istft2(F(pl.mag), F(pl.cosv), cf, T, g.nfft, g.wins[g.mask_br], g.hop, c->tw2k,
+                                          out + (size_t)ch * cf.out_plane_stride, st));
+        }
+        return 0;
+    }
     {
         ProfScope ps(c, st, P_ISTFT);
         HIP_TRY(c, lass_launch_istft2(F(pl.oreal), F(pl.oimag), cf, T, g.nfft, g.wins[g.mask_br], g.hop, c->tw2k, out, st));
@@ -1674,6 +1697,7 @@ static ClipForm upper_clips(const ClipForm& cf, int h, size_t* row) {
     if (cf.keep) u.keep = cf.keep + 2 * h;
     if (cf.fade) u.fade = cf.fade + 2 * h;
     *row = cf.starts ? 0 : (size_t)h * cf.L;
+    if (cf.planes) u.planes = cf.planes + *row;  // (the linked planes are laid out as the guide)
     return u;
 }
 
@@ -1724,6 +1748,7 @@ static int separate_call(lass_ctx* c, const float* mixture, const float* conditi
         key.gen = c->gen;
         key.starts = cf.starts; key.keep = cf.keep; key.total = cf.total;
         key.fade = cf.fade; key.ramp = cf.ramp; key.F = cf.F;
+        key.planes = cf.planes; key.plane_stride = cf.plane_stride; key.out_plane_stride = cf.out_plane_stride; key.channels = cf.channels;
         auto& slot = c->graphs.touch(key);
         if (c->graphs.drain_due()) {  // a caller cycling through many recurring keys: bound the list of evicted execs here
             HIP_TRY(c, hipSetDevice(c->device));
@@ -1799,9 +1824,10 @@ int lass_separate_ragged(lass_ctx* c, const float* mixture, const int* lengths, 
 }
 
 // lass_separate_windows and lass_separate_windows_faded behind the checks that only the latter has (fade == nullptr: the former)
+// link: the planes of a linked call (ClipForm's four fields; none: an unlinked call), checked by the caller
 static int separate_windows(lass_ctx* c, const std::string& who, const float* recording, int64_t total, const int64_t* starts,
                             const int* keep, const int* fade, const float* ramp, int F, const float* condition, float* out, int B,
-                            int W, void* workspace, size_t workspace_bytes, void* stream) {
+                            int W, void* workspace, size_t workspace_bytes, void* stream, const ClipForm& link = ClipForm()) {
     if (!recording || !starts || !keep || !condition || !out || !workspace) return fail(c, LASS_ERR_ARG, who + ": null pointer");
     if (B <= 0) return fail(c, LASS_ERR_ARG, who + ": need B >= 1");
     if (W <= c->g.nfft / 2)
@@ -1809,8 +1835,9 @@ static int separate_windows(lass_ctx* c, const std::string& who, const float* re
     if (total < W) return fail(c, LASS_ERR_ARG, who + ": the recording is shorter than one window (total < W)");
     const uintptr_t r0 = (uintptr_t)recording, o0 = (uintptr_t)out, bytes = (uintptr_t)total * sizeof(float);
     if (r0 < o0 + bytes && o0 < r0 + bytes) return fail(c, LASS_ERR_ARG, who + ": recording and out overlap");
-    return separate_call(c, recording, condition, out, ClipForm{B, W, nullptr, starts, keep, total, fade, ramp, F}, workspace,
-                         workspace_bytes, stream, who.c_str());
+    ClipForm cf{B, W, nullptr, starts, keep, total, fade, ramp, F};
+    cf.planes = link.planes; cf.plane_stride = link.plane_stride; cf.out_plane_stride = link.out_plane_stride; cf.channels = link.channels;
+    return separate_call(c, recording, condition, out, cf, workspace, workspace_bytes, stream, who.c_str());
 }
 
 int lass_separate_windows(lass_ctx* c, const float* recording, int64_t total, const int64_t* starts, const int* keep,
@@ -1829,6 +1856,84 @@ int lass_separate_windows_faded(lass_ctx* c, const float* recording, int64_t tot
     if (F < 1 || F > W) return fail(c, LASS_ERR_ARG, who + ": the fade length must lie in [1, W]");
     return separate_windows(c, who, recording, total, starts, keep, fade, ramp, F, condition, out, B, W, workspace, workspace_bytes,
                             stream);
+}
+
+// ---- linked channels: one mask from the guide, applied to every plane ----------------------------------
+// The checks that only the linked calls have: `n` floats per channel array (B * L, or total).  `link` receives the four fields.
+static int check_linked(lass_ctx* c, const std::string& who, const float* guide, int64_t n, const float* planes, int64_t plane_stride,
+                        int channels, const float* out, int64_t out_plane_stride, ClipForm* link) {
+    if (c->g.variant != 0) return fail(c, LASS_ERR_ARG, who + ": linked channels are ResUNet30's (not a multi-STFT context)");
+    if (!planes) return fail(c, LASS_ERR_ARG, who + ": null pointer");
+    if (channels < 1 || channels > LASS_MAX_LINKED_CHANNELS)
+        return fail(c, LASS_ERR_ARG, who + ": need 1 <= channels <= " + std::to_string(LASS_MAX_LINKED_CHANNELS));
+    if (n > 0 && (plane_stride < n || out_plane_stride < n))
+        return fail(c, LASS_ERR_ARG, who + ": a plane stride is shorter than one channel's array (" + std::to_string(n) + " floats)");
+    if (guide && out && n > 0) {
+        const uintptr_t bytes = (uintptr_t)n * sizeof(float);
+        const auto meets = [&](const float* a, const float* b) {
+            return (uintptr_t)a < (uintptr_t)b + bytes && (uintptr_t)b < (uintptr_t)a + bytes;
+        };
+        for (int o = 0; o < channels; ++o) {
+            const float* oc = out + (size_t)o * out_plane_stride;
+            if (meets(oc, guide)) return fail(c, LASS_ERR_ARG, who + ": out overlaps the guide");
+            for (int i = 0; i < channels; ++i)
+                if (meets(oc, planes + (size_t)i * plane_stride)) return fail(c, LASS_ERR_ARG, who + ": out overlaps an input plane");
+        }
+    }
+    link->planes = planes; link->plane_stride = plane_stride; link->out_plane_stride = out_plane_stride; link->channels = channels;
+    return 0;
+}
+
+int lass_separate_ragged_linked(lass_ctx* c, const float* guide, const int* lengths, const float* planes, int64_t plane_stride,
+                                int channels, const float* condition, float* out, int64_t out_plane_stride, int B, int L,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    if (!c) return LASS_ERR_ARG;
+    const std::string who = "lass_separate_ragged_linked";
+    ClipForm cf{B, L, lengths};
+    if (int r = check_linked(c, who, guide, B > 0 && L > 0 ? (int64_t)B * L : 0, planes, plane_stride, channels, out, out_plane_stride, &cf))
+        return r;
+    return separate_call(c, guide, condition, out, cf, workspace, workspace_bytes, stream, "lass_separate_ragged_linked");
+}
+
+int lass_separate_windows_linked(lass_ctx* c, const float* guide, int64_t total, const int64_t* starts, const int* keep, const int* fade,
+                                 const float* ramp, int F, const float* planes, int64_t plane_stride, int channels,
+                                 const float* condition, float* out, int64_t out_plane_stride, int B, int W, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+    if (!c) return LASS_ERR_ARG;
+    const std::string who = "lass_separate_windows_linked";
+    if ((fade == nullptr) != (ramp == nullptr)) return fail(c, LASS_ERR_ARG, who + ": fade and ramp go together");
+    if (fade && (F < 1 || F > W)) return fail(c, LASS_ERR_ARG, who + ": the fade length must lie in [1, W]");
+    ClipForm link;
+    if (int r = check_linked(c, who, guide, total > 0 ? total : 0, planes, plane_stride, channels, out, out_plane_stride, &link)) return r;
+    return separate_windows(c, who, guide, total, starts, keep, fade, ramp, fade ? F : 0, condition, out, B, W, workspace, workspace_bytes,
+                            stream, link);
+}
+
+// lass_masked_stft and lass_masked_stft_windows behind their argument checks
+static int masked_stft(lass_ctx* c, const char* who, const float* wav, const ClipForm& cf, const float* m_re, const float* m_im,
+                       float* y_re, float* y_im, void* stream) {
+    if (c->g.variant != 0) return fail(c, LASS_ERR_ARG, std::string(who) + ": linked channels are ResUNet30's (not a multi-STFT context)");
+    int r = check_ready(c);
+    if (r) return r;
+    if (!wav || !m_re || !m_im || !y_re || !y_im || cf.B <= 0 || cf.L <= c->g.nfft / 2 || (cf.starts && cf.total < cf.L))
+        return fail(c, LASS_ERR_ARG, std::string(who) + ": bad argument (n_fft/2 < L, W <= total)");
+    HIP_TRY(c, lass_launch_masked_stft(wav, cf, c->g.nfft, c->g.hop, 1 + cf.L / c->g.hop, c->g.wins[c->g.mask_br], m_re, m_im, y_re, y_im,
+                                       c->tw2k, (hipStream_t)stream));
+    return 0;
+}
+
+int lass_masked_stft(lass_ctx* c, const float* plane, const int* lengths, int B, int L, const float* m_re, const float* m_im,
+                     float* y_re, float* y_im, void* stream) {
+    if (!c) return LASS_ERR_ARG;
+    return masked_stft(c, "lass_masked_stft", plane, ClipForm{B, L, lengths}, m_re, m_im, y_re, y_im, stream);
+}
+
+int lass_masked_stft_windows(lass_ctx* c, const float* recording, int64_t total, const int64_t* starts, int B, int W,
+                             const float* m_re, const float* m_im, float* y_re, float* y_im, void* stream) {
+    if (!c) return LASS_ERR_ARG;
+    if (!starts) return fail(c, LASS_ERR_ARG, "lass_masked_stft_windows: null pointer");
+    return masked_stft(c, "lass_masked_stft_windows", recording, ClipForm{B, W, nullptr, starts, nullptr, total}, m_re, m_im, y_re, y_im,
+                       stream);
 }
 
 int lass_set_graph_replay(lass_ctx* c, int enabled) {

@@ -15,12 +15,16 @@ struct GraphKey {
     int64_t total = 0;                              // ... and the length of its long rows
     const void *fade = nullptr, *ramp = nullptr;    // lass_separate_windows_faded's flags and ramp (pointers again) ...
     int F = 0;                                      // ... and its fade length
+    const void* planes = nullptr;                   // the linked calls' input planes (pointer), their two strides and their count
+    int64_t plane_stride = 0, out_plane_stride = 0;
+    int channels = 0;
     int B = 0, L = 0;
     unsigned long gen = 0;  // bumped by lass_finalize: a graph holds weight pointers
     bool operator==(const GraphKey& o) const {
         return mix == o.mix && cond == o.cond && out == o.out && ws == o.ws && lens == o.lens && starts == o.starts &&
                keep == o.keep && total == o.total && fade == o.fade && ramp == o.ramp && F == o.F && B == o.B && L == o.L &&
-               gen == o.gen;
+               gen == o.gen && planes == o.planes && plane_stride == o.plane_stride && out_plane_stride == o.out_plane_stride &&
+               channels == o.channels;
     }
 };
 

@@ -240,10 +240,23 @@ struct ClipForm {
     const int* fade = nullptr;
     const float* ramp = nullptr;
     int F = 0;
+    // Linked channels (lass_separate_ragged_linked / lass_separate_windows_linked; read by api.hip alone, no kernel sees them):
+    // the rows above are the GUIDE's, and `channels` planes laid out as the guide, plane c `c * plane_stride` floats after
+    // `planes`, are masked with the guide's mask and written `c * out_plane_stride` floats after the call's output.
+    const float* planes = nullptr;
+    int64_t plane_stride = 0, out_plane_stride = 0;
+    int channels = 0;
 };
 hipError_t lass_launch_stft2(const float* wav, const ClipForm& cf, int n_fft, int hop, int T, int Tpad, int nbr,
                              const StftBranch* br, int magphase_sem, const float* s0, const float* h0,
                              const float2* tw2k, hipStream_t stream);
+// The transform of lass_launch_stft2 (one branch, window `wlen`, the same kernel body: the same bits as its real / imag) with a
+// masked epilogue: y = X * (m_re + i m_im), all (B, T, n_fft/2+1), as four products and two sums, each rounded once, no fma:
+// y_re = fl(fl(X_re m_re) - fl(X_im m_im)), y_im = fl(fl(X_re m_im) + fl(X_im m_re)).  Rows beyond a ragged clip's frames: 0.
+hipError_t lass_launch_masked_stft(const float* wav, const ClipForm& cf, int n_fft, int hop, int T, int wlen, const float* m_re,
+                                   const float* m_im, float* y_re, float* y_im, const float2* tw2k, hipStream_t stream);
+// mag = cos = 1, sin = 0 over n floats each: with it the output head leaves the complex mask itself in its outputs
+hipError_t lass_launch_unit_spectrum(float* mag, float* cosv, float* sinv, size_t n, hipStream_t stream);
 // Fused inverse STFT (inverse transforms + overlap-add + envelope + trim in one kernel, no frame scratch).
 hipError_t lass_launch_istft2(const float* real, const float* imag, const ClipForm& cf, int T, int n_fft, int wlen, int hop,
                               const float2* tw2k, float* wav, hipStream_t stream);

@@ -245,7 +245,24 @@ struct Stft2Args {
     float* real[LASS_MAX_STFT_WINDOWS];
     float* imag[LASS_MAX_STFT_WINDOWS];
     float* x0[LASS_MAX_STFT_WINDOWS];
+    static constexpr bool kMasked = false;
 };
+// ... of the masked transform (lass_launch_masked_stft): the spectrum of branch 0 is multiplied by the complex mask m_re + i m_im,
+// (B, T, N/2+1) as the spectra, before it is stored to real / imag; nothing else is computed.  A type of its own, so that the
+// kernels instantiated on Stft2Args keep their argument block and their code.
+struct MaskedStft2Args : Stft2Args {
+    const float* m_re;
+    const float* m_im;
+    static constexpr bool kMasked = true;
+};
+
+// X * M as torch float32 elementwise ops restate it: four products and two sums, each rounded once.  (The pragma, as in
+// export.hip's Mix: the toolchain's __fmul_rn / __fadd_rn are plain * and +, which HIP's default -ffp-contract=fast fuses.)
+__device__ __forceinline__ float2 masked_product(float re, float im, float mr, float mi) {
+#pragma clang fp contract(off)
+    const float a = re * mr, b = im * mi, c = re * mi, d = im * mr;
+    return make_float2(a - b, c + d);
+}
 
 // Centred, reflect-padded STFT of frames (2*blockIdx.x, 2*blockIdx.x + 1) of clip blockIdx.y for branch blockIdx.z
 // (periodic Hann of wlen samples zero-padded to N, centred), fused with magnitude / phase and the network-input prologue
@@ -253,9 +270,12 @@ struct Stft2Args {
 // rows Tb <= t < Tpad of x0 and rows Tb <= t < T of mag / cos / sin / real / imag are 0 (no such spectrum rows where the form
 // gives Tb = T), and nothing of the clip's row is read at or beyond its length.
 // MAGPHASE: torchlibrosa magphase (clamp on |X|, precompute_stfts.py:51) instead of base.py:83-88 (clamp on |X|^2).
-template <int N, bool MAGPHASE, class Clips>
+// Args = MaskedStft2Args: the same transform with a masked epilogue instead - Y = X * M stored to real / imag as
+// Y_re = fl(fl(X_re M_re) - fl(X_im M_im)), Y_im = fl(fl(X_re M_im) + fl(X_im M_re)): four products and two sums, each rounded once
+// (masked_product), no magnitude, no phase, no x0.  Rows beyond a short clip's frames are zeros as above.
+template <int N, bool MAGPHASE, class Clips, class Args = Stft2Args>
 __global__ __launch_bounds__(256) void stft2_kernel(const float* __restrict__ wav, Clips clips, int hop, int T, int Tpad,
-                                                    const float2* __restrict__ tw2k, Stft2Args a,
+                                                    const float2* __restrict__ tw2k, Args a,
                                                     const float* __restrict__ s0, const float* __restrict__ h0) {
     __shared__ float2 A[N], Bf[N], TW[2048];
     constexpr int NB = N / 2 + 1, FC = N / 2;
@@ -315,6 +335,12 @@ __global__ __launch_bounds__(256) void stft2_kernel(const float* __restrict__ wa
         for (int r = 0; r < 2; ++r) {
             if (r == 1 && !have_b) break;
             const size_t row = ((size_t)b * T + ta + r) * NB + f;
+            if constexpr (Args::kMasked) {
+                const float2 y = masked_product(re[r], im[r], a.m_re[row], a.m_im[row]);
+                real[row] = y.x;
+                imag[row] = y.y;
+                continue;
+            }
             float m, c, s;
             if (MAGPHASE) {
                 m = sqrtf(re[r] * re[r] + im[r] * im[r]);
@@ -462,6 +488,16 @@ void with_clips(const ClipForm& cf, int n_fft, int hop, F f) {
     else f(DenseClips{cf.L});
 }
 
+// mag = cos = 1, sin = 0 over n floats each: the unit spectrum that turns the output head's product into the mask itself
+__global__ __launch_bounds__(256) void unit_spectrum_kernel(float* __restrict__ mag, float* __restrict__ cosv, float* __restrict__ sinv,
+                                                            size_t n) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        mag[i] = 1.f;
+        cosv[i] = 1.f;
+        sinv[i] = 0.f;
+    }
+}
+
 bool bad_transform(int n_fft, int wlen) {
     return (n_fft != 1024 && n_fft != 2048) || wlen <= 0 || wlen > n_fft || (2048 % wlen) != 0 || ((n_fft - wlen) & 1);
 }
@@ -511,6 +547,32 @@ hipError_t lass_launch_stft2(const float* wav, const ClipForm& cf, int n_fft, in
                                           : (magphase_sem ? stft2_kernel<2048, true, C> : stft2_kernel<2048, false, C>);
         hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, wav, clips, hop, T, Tpad, tw2k, a, s0, h0);
     });
+    return hipGetLastError();
+}
+
+hipError_t lass_launch_masked_stft(const float* wav, const ClipForm& cf, int n_fft, int hop, int T, int wlen, const float* m_re,
+                                   const float* m_im, float* y_re, float* y_im, const float2* tw2k, hipStream_t stream) {
+    const int B = cf.B, L = cf.L;
+    if (!wav || !m_re || !m_im || !y_re || !y_im || B <= 0 || hop <= 0 || L <= n_fft / 2 || T != 1 + L / hop || bad_transform(n_fft, wlen))
+        return hipErrorInvalidValue;
+    if (cf.starts && cf.total < L) return hipErrorInvalidValue;
+    MaskedStft2Args a = {};
+    a.nbr = 1;
+    a.wlen[0] = wlen; a.real[0] = y_re; a.imag[0] = y_im;
+    a.m_re = m_re; a.m_im = m_im;
+    dim3 grid((T + 1) / 2, B, 1);
+    with_clips<false>(cf, n_fft, hop, [&](auto clips) {
+        using C = decltype(clips);
+        const auto kernel = n_fft == 1024 ? stft2_kernel<1024, false, C, MaskedStft2Args> : stft2_kernel<2048, false, C, MaskedStft2Args>;
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, wav, clips, hop, T, T, tw2k, a, (const float*)nullptr, (const float*)nullptr);
+    });
+    return hipGetLastError();
+}
+
+hipError_t lass_launch_unit_spectrum(float* mag, float* cosv, float* sinv, size_t n, hipStream_t stream) {
+    if (!mag || !cosv || !sinv || n == 0) return hipErrorInvalidValue;
+    const size_t blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(unit_spectrum_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, stream, mag, cosv, sinv, n);
     return hipGetLastError();
 }
 

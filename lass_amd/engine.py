@@ -324,6 +324,105 @@ class Engine:
         _lib.check(self.ctx, rc, "lass_separate_windows")
         return out
 
+    # ---- linked channels: one mask from a guide, applied to every plane ---------------------------
+    MAX_LINKED_CHANNELS = 8  # include/lass_hip.h: LASS_MAX_LINKED_CHANNELS
+
+    def _linked_io(self, guide: torch.Tensor, planes: torch.Tensor, out: Optional[torch.Tensor], zero: bool, what: str):
+        """planes (C,) + guide.shape and the output of the same shape (a fresh one zero-filled where `zero`), both contiguous
+        float32 on the engine's device, 1 <= C <= 8."""
+        planes = self._dev(planes)
+        if planes.dim() != guide.dim() + 1 or planes.shape[1:] != guide.shape or not 1 <= planes.shape[0] <= self.MAX_LINKED_CHANNELS:
+            raise ValueError(f"{what}: planes must be (C,) + {tuple(guide.shape)} with 1 <= C <= {self.MAX_LINKED_CHANNELS}")
+        if out is None:
+            out = torch.zeros_like(planes) if zero else _alloc.empty_like(planes)
+        elif (out.shape != planes.shape or out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous()):
+            raise _lib.LassError(f"out must be a contiguous float32 {tuple(planes.shape)} tensor on {self.device}")
+        return planes, out
+
+    def separate_ragged_linked(self, guide: torch.Tensor, lengths, planes: torch.Tensor, condition: torch.Tensor,
+                               out: Optional[torch.Tensor] = None, checked: bool = False) -> torch.Tensor:
+        """`separate_ragged` with linked channels (lass_separate_ragged_linked): guide (B,L) decides one mask per clip, which is
+        applied to every plane of planes (C,B,L) -> (C,B,L); plane c does not depend on the others.  lengths as for
+        `separate_ragged` (`_ragged_lengths`), or None: every clip is L samples long.  condition (B,512)."""
+        assert guide.dim() == 2 and condition.dim() == 2 and condition.shape == (guide.shape[0], arch_cond())
+        guide, condition = self._dev(guide), self._dev(condition)
+        B, L = guide.shape
+        lens = None if lengths is None else self._ragged_lengths(lengths, B, L, checked, "separate_ragged_linked")
+        planes, out = self._linked_io(guide, planes, out, False, "separate_ragged_linked")
+        ws = self._workspace(B, L)
+        rc = self.lib.lass_separate_ragged_linked(self.ctx, _ptr(guide), _ptr(lens), _ptr(planes), B * L, planes.shape[0],
+                                                  _ptr(condition), _ptr(out), B * L, B, L, _ptr(ws), ws.numel(), _stream(self.device))
+        _lib.check(self.ctx, rc, "lass_separate_ragged_linked")
+        return out
+
+    def separate_windows_linked(self, guide: torch.Tensor, planes: torch.Tensor, starts, keep, condition: torch.Tensor, window: int,
+                                out: Optional[torch.Tensor] = None, checked: bool = False, fade=None, ramp=None) -> torch.Tensor:
+        """`separate_windows` with linked channels (lass_separate_windows_linked): guide (total,) decides one mask per window,
+        which is applied to that window of every row of planes (C,total) -> out (C,total).  starts, keep, condition, fade and
+        ramp are `separate_windows`'s, the same for every plane; nothing of `out` outside the kept ranges is touched (a fresh
+        `out` is zero-filled, which the fade regions need)."""
+        if guide.dim() != 1:
+            raise ValueError("separate_windows_linked takes a 1-D guide")
+        guide = self._dev(guide)
+        total, W = guide.shape[0], int(window)
+        faded = fade is not None or ramp is not None
+        idx_f = None
+        if faded:
+            ramp = self._fade_ramp(fade, ramp, W, "separate_windows_linked")
+            idx_s, idx_k, idx_f = self._window_index(starts, keep, total, W, checked, "separate_windows_linked", fade, ramp.numel())
+        else:
+            idx_s, idx_k = self._window_index(starts, keep, total, W, checked, "separate_windows_linked")
+        B = idx_s.numel()
+        condition = self._dev(condition)
+        if condition.numel() == arch_cond() and (B > 1 or condition.dim() == 1):
+            cond = self.window_buffers(B)[2]
+            cond.copy_(condition.reshape(1, -1).expand(B, -1))
+        elif condition.shape == (B, arch_cond()):
+            cond = condition
+        else:
+            raise ValueError(f"condition must be ({B}, {arch_cond()}), (1, {arch_cond()}) or ({arch_cond()},)")
+        planes, out = self._linked_io(guide, planes, out, True, "separate_windows_linked")
+        ws = self._workspace(B, W)
+        rc = self.lib.lass_separate_windows_linked(self.ctx, _ptr(guide), total, _ptr(idx_s), _ptr(idx_k), _ptr(idx_f),
+                                                   _ptr(ramp if faded else None), ramp.numel() if faded else 0, _ptr(planes), total,
+                                                   planes.shape[0], _ptr(cond), _ptr(out), total, B, W, _ptr(ws), ws.numel(),
+                                                   _stream(self.device))
+        _lib.check(self.ctx, rc, "lass_separate_windows_linked")
+        return out
+
+    def _mask_pair(self, m_re: torch.Tensor, m_im: torch.Tensor, B: int, L: int, what: str):
+        m_re, m_im = self._dev(m_re), self._dev(m_im)
+        shape = (B, arch.frames_for(L, self.hop), self.n_fft // 2 + 1)
+        if tuple(m_re.shape) != shape or tuple(m_im.shape) != shape:
+            raise ValueError(f"{what}: the mask must be two {shape} tensors")
+        return m_re, m_im, _alloc.empty(shape, dtype=torch.float32, device=self.device), _alloc.empty(shape, dtype=torch.float32, device=self.device)
+
+    def masked_stft(self, plane: torch.Tensor, m_re: torch.Tensor, m_im: torch.Tensor, lengths=None, checked: bool = False):
+        """The per-channel stage of the linked calls (lass_masked_stft): plane (B,L) and the complex mask m_re, m_im
+        (B,T,n_fft/2+1) -> (y_re, y_im), Y = STFT(plane) * M as four float32 products and two sums, each rounded once.  lengths:
+        as for `front_end_ragged`, or None (dense); rows beyond a ragged clip's own frames are zero."""
+        plane = self._dev(plane)
+        B, L = plane.shape
+        lens = None if lengths is None else self._ragged_lengths(lengths, B, L, checked, "masked_stft")
+        m_re, m_im, y_re, y_im = self._mask_pair(m_re, m_im, B, L, "masked_stft")
+        rc = self.lib.lass_masked_stft(self.ctx, _ptr(plane), _ptr(lens), B, L, _ptr(m_re), _ptr(m_im), _ptr(y_re), _ptr(y_im),
+                                       _stream(self.device))
+        _lib.check(self.ctx, rc, "lass_masked_stft")
+        return y_re, y_im
+
+    def masked_stft_windows(self, recording: torch.Tensor, starts, window: int, m_re: torch.Tensor, m_im: torch.Tensor,
+                            checked: bool = False):
+        """`masked_stft` of the windows recording[starts[b] : starts[b] + window] of a 1-D recording (lass_masked_stft_windows)."""
+        recording = self._dev(recording)
+        total, W = recording.shape[0], int(window)
+        idx_s, _ = self._window_index(starts, None, total, W, checked, "masked_stft_windows")
+        B = idx_s.numel()
+        m_re, m_im, y_re, y_im = self._mask_pair(m_re, m_im, B, W, "masked_stft_windows")
+        rc = self.lib.lass_masked_stft_windows(self.ctx, _ptr(recording), total, _ptr(idx_s), B, W, _ptr(m_re), _ptr(m_im), _ptr(y_re),
+                                               _ptr(y_im), _stream(self.device))
+        _lib.check(self.ctx, rc, "lass_masked_stft_windows")
+        return y_re, y_im
+
     def _dev(self, t: torch.Tensor) -> torch.Tensor:
         if t.device != self.device:
             raise _lib.LassError(f"tensor on {t.device}, engine on {self.device}")

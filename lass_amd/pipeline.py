@@ -12,6 +12,7 @@ One pass over a group of files:
 
     WAV bytes -> pinned row -> H2D -> Engine.decode_resample_planar (or decode_resample for channels="mono")
               -> every plane one recording of ResUNet30.separate_long_list, with its file's condition
+                 (channels="linked": every FILE one recording of separate_long_list_linked, guided by its mono down-mix)
               -> Engine.resample_encode back to the file's rate, encoding and frame count -> D2H into a pinned row
               -> wavio.wav_header + payload written
 
@@ -92,8 +93,23 @@ def route(info, sampling_rate: int, out_rate: Optional[int] = None, true_peak: b
 
 
 def model_samples(nch: int, rate: int, frames: int, sampling_rate: int, channels: str) -> Tuple[int, int]:
-    """(planes, model-rate samples per plane) a file puts into a pass: its channels or 1, ceil(frames * up / down)."""
-    return (nch if channels == "each" else 1), rs.out_len(frames, *rs.ratio(rate, sampling_rate))
+    """(planes, model-rate samples per plane) a file puts into a pass: its channels ("each", "linked") or 1 ("mono"),
+    ceil(frames * up / down)."""
+    return (1 if channels == "mono" else nch), rs.out_len(frames, *rs.ratio(rate, sampling_rate))
+
+
+def pass_rows(n_planes: int, channels: str) -> int:
+    """The model-rate rows a file of `n_planes` planes holds in a pass: its planes, and under "linked" its guide as well."""
+    return n_planes + 1 if channels == "linked" else n_planes
+
+
+def group_by_planes(counts: Sequence[int]) -> List[List[int]]:
+    """The positions of `counts` grouped by value, groups in the order of their first member and positions ascending inside a
+    group: the files of a pass by channel count, one `ResUNet30.separate_long_list_linked` call per group."""
+    groups: Dict[int, List[int]] = {}
+    for k, n in enumerate(counts):
+        groups.setdefault(int(n), []).append(k)
+    return list(groups.values())
 
 
 def plan_passes(samples: Sequence[int], max_samples: int) -> List[List[int]]:
@@ -179,13 +195,16 @@ def plan_files(jobs, dbs, o: Options, sampling_rate: int, n_fft: int, channels: 
                out_rate: Optional[int] = None) -> List[FilePlan]:
     """One FilePlan per job, from the files' headers alone.  dbs: `check_remix_args`' list or None.  The output has the input's
     frame count at the input's rate, else ceil(model-rate samples * up / down).  ValueError, with the file's name, for a file not
-    longer than the reflect padding n_fft/2 at the model rate (`longform.plan_windows`' refusal, before anything is written)."""
+    longer than the reflect padding n_fft/2 at the model rate (`longform.plan_windows`' refusal, before anything is written), and
+    under channels="linked" for a file of more than 8 channels (the linked calls' limit)."""
     sr, plans = int(sampling_rate), []
     for k, job in enumerate(jobs):
         info = wavio.wav_info(job[0])
         how = route(info, sr, out_rate, o.true_peak)
         enc_in, nch, rate, frames = meta = info[:4] if info is not None else _host_info(job[0])
         n_planes, length = model_samples(nch, rate, frames, sr, channels)
+        if channels == "linked" and n_planes > MAX_CHANNELS:
+            raise ValueError(f'{job[0]}: channels="linked" takes at most {MAX_CHANNELS} channels, the file has {n_planes}')
         if length <= n_fft // 2:
             raise ValueError(f"{job[0]}: a recording of {length} samples is not longer than the reflect padding "
                              f"(n_fft/2 = {n_fft // 2})")
@@ -676,7 +695,11 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
     device working at `sampling_rate`, `.query_encoder` with `get_query_embed`); jobs: a sequence of (in_path, query, out_path),
     query a caption or a (512,) embedding.  channels "each": every channel of a file is separated on its own with the file's
     query and the output keeps the channel layout; "mono": the channels are averaged first (as `librosa.load(mono=True)` does) and
-    the output is mono.  encoding / out_rate None: the input file's own; the output then has the input's frame count, else
+    the output is mono; "linked": ONE mask per file, estimated from the file's mono down-mix (`Engine.decode_resample` of its raw
+    row, the "mono" path's own; on the host route `ResUNet30.downmix` of its model-rate planes) and applied to every channel
+    (`ResUNet30.separate_long_list_linked`, the files of a pass grouped by channel count) - the network runs once per file, the
+    stereo image of the target stays put, the output keeps the channel layout, everything after the separation (level, limiter,
+    remix) sees the C planes of "each", and a record gains "linked": True.  A pass counts C + 1 rows for such a file.  encoding / out_rate None: the input file's own; the output then has the input's frame count, else
     ceil(model-rate samples * up / down).  window, context, fade, fade_shape, max_batch: `ResUNet30.separate_long_list`'s.  Files
     are taken in passes of at most `max_samples` model-rate samples (all planes counted), which bounds the memory; the captions
     of a pass are embedded in one `get_query_embed` call, each distinct caption once.  profile: a dict that receives seconds per
@@ -718,8 +741,8 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
     A file not longer than n_fft/2 samples at the model rate raises ValueError before anything is written."""
     import torch
 
-    if channels not in ("each", "mono"):
-        raise ValueError('channels must be "each" or "mono"')
+    if channels not in ("each", "mono", "linked"):
+        raise ValueError('channels must be "each" or "mono" (or "linked": one mask from the down-mix for every channel)')
     if encoding is not None and encoding not in rs.ENCODINGS:
         raise ValueError(f"encoding must be one of {sorted(rs.ENCODINGS)} or None")
     ld.check_level_args(loudness, peak_ceiling_db)
@@ -736,7 +759,7 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
 
     clock, pool = _Clock(profile, dev), _Pinned()
     records: List[Optional[dict]] = [None] * len(jobs)
-    passes = plan_passes([p.n_planes * p.length for p in plans], max_samples)
+    passes = plan_passes([pass_rows(p.n_planes, channels) * p.length for p in plans], max_samples)
     with ThreadPoolExecutor(1) as reader, ThreadPoolExecutor(1) as writer:
         ctx = _Ctx(eng, sr, o, clock, pool, writer, profile)
         reads = _submit_reads(reader, plans, passes[0], channels, pool, profile) if passes else []
@@ -747,6 +770,7 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
             emb = (model.query_encoder.get_query_embed(modality="text", text=captions, device=dev).to(torch.float32)
                    if captions else None)
             planes, conds, uploaded, dry, pending = [], [], [], {}, []
+            linked = []                                              # channels="linked": (planes, guide, condition) per file
             amounts = torch.tensor([float(plans[i].amount) for i in ids], dtype=torch.float32).to(dev) if o.remix else None
             for k, (i, fut) in enumerate(zip(ids, reads)):
                 plan, got = plans[i], fut.result()
@@ -756,21 +780,39 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
                     with clock("h2d"):
                         raw = got[None, :(nbytes + 3) // 4 * 4].to(dev, non_blocking=True)
                     with clock("decode"):
-                        if channels == "each":
+                        if channels != "mono":
                             mine = list(eng.decode_resample_planar(raw, frames, nch, enc_in, rate, sr)[0])
                         else:
                             mine = [eng.decode_resample(raw, frames, nch, enc_in, rate, sr)[0]]
+                        if channels == "linked":                     # the guide is the mono path's own down-mix
+                            guide = eng.decode_resample(raw, frames, nch, enc_in, rate, sr)[0]
                     uploaded.append(got)
                 else:
                     mine = [torch.from_numpy(p).to(dev) for p in _host_resample(got, rate, sr)]
+                    if channels == "linked":
+                        guide = ss.downmix(torch.stack(mine))
                 if o.remix:
                     dry[i] = raw if plan.how == "device" else got   # kept until the file's encode: the remix's dry source
                 cond = emb[cap_of[k]] if cap_of[k] is not None else torch.as_tensor(jobs[i][1]).to(device=dev, dtype=torch.float32).reshape(-1)
+                if channels == "linked":
+                    linked.append((torch.stack(mine), guide, cond))
+                    continue
                 planes += mine
                 conds += [cond] * len(mine)
             with clock("separate"):
-                seps = ss.separate_long_list(planes, torch.stack(conds), window=window, context=context, max_batch=max_batch,
-                                             fade=fade, fade_shape=fade_shape)
+                if channels == "linked":
+                    # one network pass per file whatever its channels: the files of the pass by channel count, one call per count
+                    done = [None] * len(linked)
+                    for group in group_by_planes([f[0].shape[0] for f in linked]):
+                        outs = ss.separate_long_list_linked([linked[k][0] for k in group], torch.stack([linked[k][2] for k in group]),
+                                                            [linked[k][1] for k in group], window=window, context=context,
+                                                            max_batch=max_batch, fade=fade, fade_shape=fade_shape)
+                        for k, sep in zip(group, outs):
+                            done[k] = sep
+                    seps = [row for sep in done for row in sep]      # C planes per file, as under "each", from here on
+                else:
+                    seps = ss.separate_long_list(planes, torch.stack(conds), window=window, context=context, max_batch=max_batch,
+                                                 fade=fade, fade_shape=fade_shape)
             at = 0
             for j, i in enumerate(ids):
                 plan, mine = plans[i], seps[at:at + plans[i].n_planes]
@@ -778,6 +820,8 @@ def separate_files(model, jobs, sampling_rate: int, channels: str = "each", enco
                 if any(int(m.shape[0]) != plan.length for m in mine):
                     raise RuntimeError(f"{plan.in_path}: separated planes of {[int(m.shape[0]) for m in mine]} samples, planned {plan.length}")
                 rec = {"rate": plan.rate_o, "channels": plan.n_planes, "frames": plan.frames_o, "path": plan.how}
+                if channels == "linked":
+                    rec["linked"] = True
                 stacked = torch.stack(mine) if plan.how == "device" else None
                 if o.remix:
                     remix = _remix_record(dict(rec), plan.db)

@@ -256,11 +256,13 @@ class ResUNet30(nn.Module):
         return out
 
     @staticmethod
-    def _run_windows(eng: Engine, rec: torch.Tensor, out: torch.Tensor, window: int, groups, cond: torch.Tensor, cond_rows, ramp) -> None:
+    def _run_windows(eng: Engine, rec: torch.Tensor, out: torch.Tensor, window: int, groups, cond: torch.Tensor, cond_rows, ramp,
+                     planes: Optional[torch.Tensor] = None) -> None:
         """Groups of equally many windows of ONE row - (start, lo, hi) or, with a `ramp`, (start, lo, hi, fade_in, fade_out) - as
         one Engine.separate_windows each, on the engine's persistent index buffers.  cond_rows None: row 0 of `cond` for every
         window; else the row of `cond` per window, grouped as `groups`.  The whole plan goes up in a few copies; each group's rows
-        reach the index buffers by stream-ordered device copies: no host synchronisation."""
+        reach the index buffers by stream-ordered device copies: no host synchronisation.  planes (C, total): the linked form -
+        `rec` is the guide, `out` (C, total), every group one Engine.separate_windows_linked."""
         dev, B = eng.device, len(groups[0])
         all_starts = torch.tensor([[w[0] for w in g] for g in groups], dtype=torch.int64).to(dev)
         all_keeps = torch.tensor([[w[1:3] for w in g] for g in groups], dtype=torch.int32).to(dev)
@@ -280,6 +282,9 @@ class ResUNet30(nn.Module):
                 idx_f.copy_(all_fades[gi])
             if cond_rows is not None:
                 torch.index_select(cond, 0, all_rows[gi], out=cond_b)
+            if planes is not None:
+                eng.separate_windows_linked(rec, planes, idx_s, idx_k, cond_b, window, out=out, checked=True, fade=idx_f, ramp=ramp_d)
+                continue
             eng.separate_windows(rec, idx_s, idx_k, cond_b, window, out=out, checked=True, fade=idx_f, ramp=ramp_d)
 
     @torch.no_grad()
@@ -341,6 +346,105 @@ class ResUNet30(nn.Module):
         self._run_windows(eng, rec, out, window, groups, cond, [cond_rows[g * B:(g + 1) * B] for g in range(len(groups))], ramp)
         for i in long_ids:
             results[i] = out[offsets[i]:offsets[i] + lengths[i]]
+        return results
+
+    # ---- linked channels: one mask from a guide, applied to every channel ---------------------------
+    @staticmethod
+    def downmix(planes: torch.Tensor) -> torch.Tensor:
+        """The default guide of a (C, L) recording: the float32 mean of its planes, summed in ascending channel order and divided
+        by C once (a single plane comes back as it is, bit for bit)."""
+        acc = planes[0]
+        for c in range(1, planes.shape[0]):
+            acc = acc + planes[c]
+        return acc / planes.shape[0] if planes.shape[0] > 1 else acc
+
+    @torch.no_grad()
+    def separate_long_linked(self, planes: torch.Tensor, condition: torch.Tensor, guide: Optional[torch.Tensor] = None,
+                             window: int = 160000, context: int = 16000, max_batch: int = 16, fade: int = 0,
+                             fade_shape: str = "linear") -> torch.Tensor:
+        """`separate_long` for a multi-channel recording with LINKED channels: planes (C, L), 1 <= C <= 8 -> (C, L).  One mask
+        per window is estimated from `guide` (L,) - None: `downmix(planes)` - and applied to that window of every channel
+        (Engine.separate_windows_linked), so the network runs once per window whatever C and every channel is attenuated alike,
+        bin by bin.  window, context, max_batch, fade, fade_shape: `separate_long`'s.  L <= window: one
+        Engine.separate_ragged_linked."""
+        return self.separate_long_list_linked([planes], condition.reshape(1, -1), None if guide is None else [guide], window=window,
+                                              context=context, max_batch=max_batch, fade=fade, fade_shape=fade_shape)[0]
+
+    @torch.no_grad()
+    def separate_long_list_linked(self, recordings: Sequence[torch.Tensor], conditions, guides=None, window: int = 160000,
+                                  context: int = 16000, max_batch: int = 16, fade: int = 0,
+                                  fade_shape: str = "linear") -> List[torch.Tensor]:
+        """`separate_long_list` with linked channels: recordings = (C, L_i) float32 tensors with the SAME C, conditions (N,512),
+        guides = None or N 1-D tensors (L_i,) (an entry None: that recording's `downmix`) -> N (C, L_i) tensors on the model's
+        device, each what `separate_long_linked` gives for that recording alone (f32: bit for bit).  Recordings longer than
+        `window` are laid end to end - the guides in one device row, the planes in C rows - planned each on its own and run as
+        Engine.separate_windows_linked calls, exactly as `separate_long_list` lays out its one row; the others go through
+        Engine.separate_ragged_linked in batches of one 32-frame bucket (lass_amd.ragged.plan_batches)."""
+        if self.training:
+            raise LassError("lass_amd.ResUNet30 is inference-only (call .eval()); training is out of scope")
+        eng = self._ensure_engine()
+        dev = eng.device
+        n = len(recordings)
+        if n == 0:
+            return []
+        C = int(recordings[0].shape[0]) if recordings[0].dim() == 2 else 0
+        if any(r.dim() != 2 or int(r.shape[0]) != C for r in recordings) or not 1 <= C <= eng.MAX_LINKED_CHANNELS:
+            raise ValueError(f"separate_long_list_linked takes (C, L) recordings of one channel count, 1 <= C <= {eng.MAX_LINKED_CHANNELS}")
+        cond = conditions if torch.is_tensor(conditions) else torch.stack(list(conditions))
+        cond = cond.to(device=dev, dtype=torch.float32).contiguous()
+        if cond.shape != (n, self.condition_size):
+            raise ValueError(f"conditions must be ({n}, {self.condition_size})")
+        window, fade = int(window), int(fade)
+        if fade < 0:
+            raise ValueError("fade must not be negative")
+        lengths = [int(r.shape[1]) for r in recordings]
+        if guides is not None and (len(guides) != n or any(g is not None and tuple(g.shape) != (lengths[i],) for i, g in enumerate(guides))):
+            raise ValueError("guides must be one 1-D tensor (or None) per recording, of its recording's length")
+        recs = [r.to(device=dev, dtype=torch.float32) for r in recordings]
+        gds = [self.downmix(recs[i]) if guides is None or guides[i] is None else guides[i].to(device=dev, dtype=torch.float32)
+               for i in range(n)]
+        long_ids = [i for i in range(n) if lengths[i] > window]
+        short_ids = [i for i in range(n) if lengths[i] <= window]
+        results: List[Optional[torch.Tensor]] = [None] * n
+        if short_ids:
+            for idx, row_length in ragged.plan_batches([lengths[i] for i in short_ids], max_batch, eng.n_fft, eng.hop):
+                idx = [short_ids[j] for j in idx]
+                guide = torch.zeros(len(idx), row_length, dtype=torch.float32, device=dev)
+                planes = torch.zeros(C, len(idx), row_length, dtype=torch.float32, device=dev)
+                for r, i in enumerate(idx):
+                    guide[r, :lengths[i]].copy_(gds[i], non_blocking=True)
+                    planes[:, r, :lengths[i]].copy_(recs[i], non_blocking=True)
+                sep = eng.separate_ragged_linked(guide, [lengths[i] for i in idx], planes, cond[idx].contiguous())
+                for r, i in enumerate(idx):
+                    results[i] = sep[:, r, :lengths[i]]
+        if not long_ids:
+            return results
+        rows, cond_rows, offsets, at = [], [], {}, 0
+        for i in long_ids:
+            if fade:
+                plan = longform.plan_windows_faded(lengths[i], window, context, fade, eng.n_fft)
+            else:
+                plan = longform.plan_windows(lengths[i], window, context, eng.n_fft)
+            rows += [(w[0] + at,) + tuple(w[1:]) for w in plan]
+            cond_rows += [i] * len(plan)
+            offsets[i] = at
+            at += lengths[i]
+        guide = torch.empty(at, dtype=torch.float32, device=dev)
+        planes = torch.empty(C, at, dtype=torch.float32, device=dev)
+        for i in long_ids:
+            guide[offsets[i]:offsets[i] + lengths[i]].copy_(gds[i], non_blocking=True)
+            planes[:, offsets[i]:offsets[i] + lengths[i]].copy_(recs[i], non_blocking=True)
+        if fade:
+            out, ramp = torch.zeros_like(planes), longform.fade_ramp(fade, fade_shape)
+            groups = longform.group_windows_faded(rows, max_batch)
+        else:
+            out, ramp = _alloc.empty_like(planes), None  # the kept ranges tile every row exactly once
+            groups = longform.group_windows(rows, max_batch)
+        B = len(groups[0])
+        cond_rows += [cond_rows[-1]] * (len(groups) * B - len(cond_rows))  # (the padding rows store nothing)
+        self._run_windows(eng, guide, out, window, groups, cond, [cond_rows[g * B:(g + 1) * B] for g in range(len(groups))], ramp, planes)
+        for i in long_ids:
+            results[i] = out[:, offsets[i]:offsets[i] + lengths[i]]
         return results
 
     @torch.no_grad()

@@ -3,6 +3,7 @@ it, on 32 seeded one-minute 44.1 kHz stereo PCM16 files (synthetic ResUNet30 wei
 
     python tools/separate_files_bench.py [--files 32] [--seconds 60] [--reps 5] [--compute-dtype f32] [--loudness [--true-peak] [--meter] [--limiter]]
     python tools/separate_files_bench.py --remix DB
+    python tools/separate_files_bench.py --channels linked
 
 Leg A: `separate_files(channels="each")` - decode, resample, separate, resample back, encode and interleave on the device.
 Leg B: host decode + de-interleave + `wavio._resample` (scipy, float64), `separate_long_list`, `.cpu()`, host `_resample` back
@@ -27,6 +28,10 @@ limiter's own overshoot.  The legs before M launch what they launched without th
 --remix DB: leg A against leg X, the same call with `target_gain_db=DB` (the remix: the raw rows stay on the device and the encode
 reads them as its dry source), alternating A X A X ...; no leg B, and BOTH legs are profiled once at the end, so that the two
 `encode` stages stand side by side.
+
+--channels linked: leg A against leg K, the same call with `channels="linked"` (one mask per file from its mono down-mix, applied
+to both channels: one network pass per file instead of two), alternating A K A K ...; no leg B, and BOTH legs are profiled once at
+the end, so that the two `separate` stages stand side by side.
 """
 import argparse
 import json
@@ -95,7 +100,7 @@ def host_pieces(model, jobs):
 
 
 def leg(name: str, d: str, n: int, mode: str, true_peak: bool = False, meter: bool = False, remix_db=None):
-    """One run of leg `name` (A, B, L, R, M or X, or one of them with "-profile") in this process."""
+    """One run of leg `name` (A, B, L, R, M, X or K, or one of them with "-profile") in this process."""
     import torch
     from lass_amd import pipeline
     model = _model(mode)
@@ -113,7 +118,8 @@ def leg(name: str, d: str, n: int, mode: str, true_peak: bool = False, meter: bo
         if name == "B":
             host_pieces(model, jobs)
         else:
-            records[:] = pipeline.separate_files(model, jobs, SR, channels="each", profile=profile, **level)
+            records[:] = pipeline.separate_files(model, jobs, SR, channels="linked" if name.startswith("K") else "each", profile=profile,
+                                                 **level)
 
     run(_jobs(d, 1, "warm"))
     torch.cuda.synchronize()
@@ -141,7 +147,9 @@ def main():
     ap.add_argument("--meter", action="store_true", help="with --loudness: a leg R with meter=True")
     ap.add_argument("--limiter", action="store_true", help="with --loudness: a leg M, the last leg's call with limiter=True")
     ap.add_argument("--remix", type=float, metavar="DB", help="leg A against leg X (target_gain_db=DB) instead of leg B")
-    ap.add_argument("--leg", choices=["A", "B", "L", "R", "M", "X", "A-profile", "L-profile", "R-profile", "M-profile", "X-profile"])
+    ap.add_argument("--channels", choices=["each", "linked"], default="each", help="linked: leg A against leg K (channels=\"linked\") instead of leg B")
+    ap.add_argument("--leg", choices=["A", "B", "L", "R", "M", "X", "K", "A-profile", "L-profile", "R-profile", "M-profile", "X-profile",
+                                      "K-profile"])
     ap.add_argument("--dir")
     a = ap.parse_args()
     if a.leg:
@@ -152,14 +160,17 @@ def main():
         ap.error("--true-peak, --meter and --limiter go with --loudness")
     if a.remix is not None and a.loudness:
         ap.error("--remix stands alone: a remix is not levelled")
+    both = a.remix is not None or a.channels == "linked"  # both legs are profiled at the end
+    if a.channels == "linked" and (a.loudness or a.remix is not None):
+        ap.error("--channels linked stands alone")
     with tempfile.TemporaryDirectory() as d:
         make_files(d, a.files, a.seconds)
-        other = "L" if a.loudness else "X" if a.remix is not None else "B"
+        other = "L" if a.loudness else "X" if a.remix is not None else "K" if a.channels == "linked" else "B"
         legs = ["A", other] + (["R"] if r128 else []) + (["M"] if a.limiter else [])
-        prof = legs[-1] + "-profile" if a.loudness or a.remix is not None else "A-profile"
+        prof = legs[-1] + "-profile" if a.loudness or both else "A-profile"
         times = {name: [] for name in legs}
         split = per_file = a_split = None
-        for name in legs * a.reps + (["A-profile"] if a.remix is not None else []) + [prof]:
+        for name in legs * a.reps + (["A-profile"] if both else []) + [prof]:
             cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--leg", name, "--dir", d,
                    "--files", str(a.files), "--compute-dtype", a.compute_dtype] + ["--true-peak"] * a.true_peak + ["--meter"] * a.meter
             if a.remix is not None:
@@ -181,6 +192,8 @@ def main():
         summary = {"files": a.files, "seconds_each": a.seconds, "compute_dtype": a.compute_dtype, prof[0] + "_split_s": split}
         if a.remix is not None:
             summary.update(remix_db=a.remix, A_split_s=a_split)
+        if a.channels == "linked":
+            summary.update(channels="linked", A_split_s=a_split)
         for name, ts in times.items():
             med = statistics.median(ts)
             summary[name] = {"median_s": round(med, 4), "files_per_s": round(a.files / med, 2), "x_real_time": round(audio / med, 1),
